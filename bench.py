@@ -7,9 +7,17 @@ A step = one eqlb_se_equilibrate call = the reference's timed region, one
 mesh, with the inputs (projected flux, projected RHS) and the output resident in HBM and the
 patch SoA / reference tensors cached in the handle ("warm").  The "cold" figure
 (handle creation + patch construction + one call on host arrays, what the reference pays inside
-its timed region, se/reconstruction.hpp:275-313) is reported beside it.
+its timed region, se/reconstruction.hpp:275-313) is reported beside it with --full.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 500] [--k 2] [--stress | --ev]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 500] [--k 2] [--stress | --ev] [--full]
+                  [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps + the clock-settle probes), times exactly K steps and prints the JSON
+line with the headline fields.  --full adds everything else: the cold path, the correctness checks (divergence
+residual, host call = device call), the repeated windows, the halo exchange alone, per-kernel times and the
+roofline, and the CPU baselines.  --dump-outputs DIR writes, after the timed steps, the output of one more step of
+the timed path into a zeroed vector (with --accumulate 1 each timed step adds exactly this) as DIR/flux_hdiv.npy
+(float64; a fixed, seeded sample of 4 Mi entries where the output is larger; one file per rank for N > 1).
 
 --gpus N > 1 without a torch.distributed environment: this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (before anything
@@ -18,9 +26,9 @@ GPU): the unit-square strips of the ranks form one [0,N]x[0,1] domain; patches a
 node ownership and the partial sums of the ghost-cell RT DOFs are exchanged with the strip
 neighbours (RCCL send/recv) inside the timed step - weak scaling, 1M triangles per GPU.
 
-Rank 0 prints ONE JSON line (contract in the task description) with `roofline` (dominant kernel,
-HIP-event time measured live over the timed region) and `cpu_baseline` (the CPU restatement of
-the reference algorithm, oracle/, timed on this box's host cores).
+Rank 0 prints ONE JSON line; with --full it carries `roofline` (dominant kernel, HIP-event time
+measured live over the timed region) and `cpu_baseline` (the CPU restatement of the reference
+algorithm, oracle/, timed on the host cores).
 """
 
 import argparse
@@ -74,9 +82,26 @@ def parse():
     ap.add_argument("--multi-rhs", type=int, default=1,
                     help="1 (library default): all right-hand sides of a tiled call in one launch; 0: one launch each")
     ap.add_argument("--windows", type=int, default=5,
-                    help="the K-step window is repeated this many times; value / ms_per_step are those of the FIRST "
-                         "window (the contract's timed region), ms_per_step_windows reports min / median / max")
+                    help="--full: the K-step window is repeated this many times; value / ms_per_step are those of the "
+                         "FIRST window (the contract's timed region), ms_per_step_windows reports min / median / max")
+    ap.add_argument("--full", action="store_true",
+                    help="also the cold path, correctness checks, repeated windows, halo-only time, per-kernel times, "
+                         "roofline and CPU baselines (a plain run measures only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the timed path (one step into a zeroed vector) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_MAX_VALUES = 4 << 20  # 32 MiB of float64
+
+
+def dump_output(path, name, x):
+    """x as float64 to path/name.npy; larger outputs: the entries at a fixed, seeded sample of indices (sorted)."""
+    os.makedirs(path, exist_ok=True)
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    if x.size > DUMP_MAX_VALUES:
+        x = x[np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(path, name + ".npy"), x)
 
 
 def launch_ranks(args):
@@ -183,7 +208,8 @@ def main():
 
     # the all-cores CPU figure forks worker processes: do it BEFORE this process touches the GPU
     cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stress and not args.ev and nrhs == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stress and not args.ev \
+            and nrhs == 1:
         cpu_all = cpu_baseline_all_cores(mesh, k, ft, G, f)
 
     import torch
@@ -234,19 +260,21 @@ def main():
         eq.set_boundary(ft, node_mask=part.node_mask)
         nout = mesh.ncells * nrt
     t_sb = time.perf_counter()  # end of handle creation + patch construction
-    # (the output vector exists before the call, as the reference's flux Functions do, FluxEqlbSE.py:104-108: a
-    # freshly calloc'ed array would add its page faults to the transfer)
-    x_cold = np.zeros((nrhs, nout))
-    x_cold.fill(0.0)
-    t_c2 = time.perf_counter()
-    eq.equilibrate_host(G.reshape(nrhs, -1), f.reshape(nrhs, -1), x_cold)
-    t_c3 = time.perf_counter()
     npatch_local = eq.num_patches
-    cold = {"mesh_upload_ms": (t_c1 - t_c0) * 1e3, "create_set_boundary_ms": (t_sb - t_c1) * 1e3,
-            "host_call_ms": (t_c3 - t_c2) * 1e3, "cold_ms": ((t_sb - t_c1) + (t_c3 - t_c2)) * 1e3,
-            "patches_per_s": npatch_local / ((t_sb - t_c1) + (t_c3 - t_c2)),
-            "note": "cold_ms = handle creation + patch construction (set_boundary) + one call on pageable host "
-                    "arrays; the mesh upload is once per mesh"}
+    cold = x_cold = None
+    if args.full:
+        # (the output vector exists before the call, as the reference's flux Functions do, FluxEqlbSE.py:104-108: a
+        # freshly calloc'ed array would add its page faults to the transfer)
+        x_cold = np.zeros((nrhs, nout))
+        x_cold.fill(0.0)
+        t_c2 = time.perf_counter()
+        eq.equilibrate_host(G.reshape(nrhs, -1), f.reshape(nrhs, -1), x_cold)
+        t_c3 = time.perf_counter()
+        cold = {"mesh_upload_ms": (t_c1 - t_c0) * 1e3, "create_set_boundary_ms": (t_sb - t_c1) * 1e3,
+                "host_call_ms": (t_c3 - t_c2) * 1e3, "cold_ms": ((t_sb - t_c1) + (t_c3 - t_c2)) * 1e3,
+                "patches_per_s": npatch_local / ((t_sb - t_c1) + (t_c3 - t_c2)),
+                "note": "cold_ms = handle creation + patch construction (set_boundary) + one call on pageable host "
+                        "arrays; the mesh upload is once per mesh"}
     tiling = eq.tiling_info() if (not args.ev and args.scatter == 2) else None
 
     d_G = torch.from_numpy(G).to(dev)
@@ -309,63 +337,64 @@ def main():
     step()
     torch.cuda.synchronize()
     eq.check_status(stream)
-    x_host = d_x.cpu().numpy().copy()
     checks = {}
-    if world == 1:
-        # the host-memory call of the cold path and the device-memory call agree bitwise
-        checks["host_call_equals_device_call"] = bool(np.array_equal(x_host, x_cold.ravel()))
-    del x_cold
     res = nrm = None
-    if world == 1 and args.ev:
-        from dolfinx_eqlb_amd.eqlb.conforming import conforming_to_broken
-        res, nrm = chk.divergence_residual(mesh, k, conforming_to_broken(mesh, k, x_host),
-                                           np.zeros_like(G), f)
-    elif world == 1 and args.stress:
-        xr = x_host.reshape(2, -1)
-        rr = [chk.divergence_residual(mesh, k, xr[r], G.reshape(2, -1)[r], f.reshape(2, -1)[r]) for r in range(2)]
-        res = float(np.sqrt(rr[0][0] ** 2 + rr[1][0] ** 2))
-        nrm = float(np.sqrt(rr[0][1] ** 2 + rr[1][1] ** 2))
-        checks["weak_symmetry_residual_max"] = chk.weak_symmetry_residual(mesh, k, xr)[0]
-    elif world == 1:
-        rr = [chk.divergence_residual(mesh, k, x_host.reshape(nrhs, -1)[r], G.reshape(nrhs, -1)[r],
-                                      f.reshape(nrhs, -1)[r]) for r in range(nrhs)]
-        res = float(np.sqrt(sum(a_ ** 2 for a_, _ in rr)))
-        nrm = float(np.sqrt(sum(b_ ** 2 for _, b_ in rr)))
-    elif args.ev:
-        # across the ranks, conforming output: the reverse halo completes the DOFs on their OWNER; checked are the
-        # owned cells whose DOFs all stay here (the cells along the interface to the next rank gave their facet
-        # DOFs away: n of 4 n^2 cells)
-        import types
-        from dolfinx_eqlb_amd.eqlb.conforming import conforming_dofmap, conforming_to_broken
-        cd, _ = conforming_dofmap(mesh, k)
-        sent = np.zeros(nout, dtype=bool)
-        for d_ in part.conforming_halo(k)[0].values():
-            sent[d_] = True
-        own = np.nonzero(part.cell_owned & ~sent[cd].any(axis=1))[0]
-        xb = conforming_to_broken(mesh, k, x_host.reshape(nrhs, -1)).reshape(nrhs, mesh.ncells, nrt)
-        sub = types.SimpleNamespace(x=mesh.x, cell_nodes=mesh.cell_nodes[own], ncells=own.size)
-        r2 = n2 = 0.0
-        for r in range(nrhs):
-            a_, b_ = chk.divergence_residual(sub, k, xb[r][own].ravel(), np.zeros(own.size * nd * 2),
-                                             f.reshape(nrhs, -1, nd)[r][own].ravel())
-            r2, n2 = r2 + a_ ** 2, n2 + b_ ** 2
-        t = torch.tensor([r2, n2], dtype=torch.float64, device=dev)
-        dist.all_reduce(t)
-        res, nrm = float(np.sqrt(t[0].item())), float(np.sqrt(t[1].item()))
-    elif not args.ev:
-        # across the ranks: the owned cells hold their own rows + the rows the neighbour computed for them
-        import types
-        own = np.nonzero(part.cell_owned)[0]
-        sub = types.SimpleNamespace(x=mesh.x, cell_nodes=mesh.cell_nodes[own], ncells=own.size)
-        r2 = n2 = 0.0
-        for r in range(nrhs):
-            a_, b_ = chk.divergence_residual(sub, k, x_host.reshape(nrhs, -1, nrt)[r][own].ravel(),
-                                             G.reshape(nrhs, -1, nd * 2)[r][own].ravel(),
-                                             f.reshape(nrhs, -1, nd)[r][own].ravel())
-            r2, n2 = r2 + a_ ** 2, n2 + b_ ** 2
-        t = torch.tensor([r2, n2], dtype=torch.float64, device=dev)
-        dist.all_reduce(t)
-        res, nrm = float(np.sqrt(t[0].item())), float(np.sqrt(t[1].item()))
+    if args.full:
+        x_host = d_x.cpu().numpy().copy()
+        if world == 1:
+            # the host-memory call of the cold path and the device-memory call agree bitwise
+            checks["host_call_equals_device_call"] = bool(np.array_equal(x_host, x_cold.ravel()))
+        del x_cold
+        if world == 1 and args.ev:
+            from dolfinx_eqlb_amd.eqlb.conforming import conforming_to_broken
+            res, nrm = chk.divergence_residual(mesh, k, conforming_to_broken(mesh, k, x_host),
+                                               np.zeros_like(G), f)
+        elif world == 1 and args.stress:
+            xr = x_host.reshape(2, -1)
+            rr = [chk.divergence_residual(mesh, k, xr[r], G.reshape(2, -1)[r], f.reshape(2, -1)[r]) for r in range(2)]
+            res = float(np.sqrt(rr[0][0] ** 2 + rr[1][0] ** 2))
+            nrm = float(np.sqrt(rr[0][1] ** 2 + rr[1][1] ** 2))
+            checks["weak_symmetry_residual_max"] = chk.weak_symmetry_residual(mesh, k, xr)[0]
+        elif world == 1:
+            rr = [chk.divergence_residual(mesh, k, x_host.reshape(nrhs, -1)[r], G.reshape(nrhs, -1)[r],
+                                          f.reshape(nrhs, -1)[r]) for r in range(nrhs)]
+            res = float(np.sqrt(sum(a_ ** 2 for a_, _ in rr)))
+            nrm = float(np.sqrt(sum(b_ ** 2 for _, b_ in rr)))
+        elif args.ev:
+            # across the ranks, conforming output: the reverse halo completes the DOFs on their OWNER; checked are the
+            # owned cells whose DOFs all stay here (the cells along the interface to the next rank gave their facet
+            # DOFs away: n of 4 n^2 cells)
+            import types
+            from dolfinx_eqlb_amd.eqlb.conforming import conforming_dofmap, conforming_to_broken
+            cd, _ = conforming_dofmap(mesh, k)
+            sent = np.zeros(nout, dtype=bool)
+            for d_ in part.conforming_halo(k)[0].values():
+                sent[d_] = True
+            own = np.nonzero(part.cell_owned & ~sent[cd].any(axis=1))[0]
+            xb = conforming_to_broken(mesh, k, x_host.reshape(nrhs, -1)).reshape(nrhs, mesh.ncells, nrt)
+            sub = types.SimpleNamespace(x=mesh.x, cell_nodes=mesh.cell_nodes[own], ncells=own.size)
+            r2 = n2 = 0.0
+            for r in range(nrhs):
+                a_, b_ = chk.divergence_residual(sub, k, xb[r][own].ravel(), np.zeros(own.size * nd * 2),
+                                                 f.reshape(nrhs, -1, nd)[r][own].ravel())
+                r2, n2 = r2 + a_ ** 2, n2 + b_ ** 2
+            t = torch.tensor([r2, n2], dtype=torch.float64, device=dev)
+            dist.all_reduce(t)
+            res, nrm = float(np.sqrt(t[0].item())), float(np.sqrt(t[1].item()))
+        elif not args.ev:
+            # across the ranks: the owned cells hold their own rows + the rows the neighbour computed for them
+            import types
+            own = np.nonzero(part.cell_owned)[0]
+            sub = types.SimpleNamespace(x=mesh.x, cell_nodes=mesh.cell_nodes[own], ncells=own.size)
+            r2 = n2 = 0.0
+            for r in range(nrhs):
+                a_, b_ = chk.divergence_residual(sub, k, x_host.reshape(nrhs, -1, nrt)[r][own].ravel(),
+                                                 G.reshape(nrhs, -1, nd * 2)[r][own].ravel(),
+                                                 f.reshape(nrhs, -1, nd)[r][own].ravel())
+                r2, n2 = r2 + a_ ** 2, n2 + b_ ** 2
+            t = torch.tensor([r2, n2], dtype=torch.float64, device=dev)
+            dist.all_reduce(t)
+            res, nrm = float(np.sqrt(t[0].item())), float(np.sqrt(t[1].item()))
 
     for _ in range(args.warmup):
         step()
@@ -417,124 +446,14 @@ def main():
     else:
         npatch_total = npatch_local
     step_dev_ms = ev0.elapsed_time(ev1) / args.steps  # device time of one step on the launch stream
-    # the same window again (bench hygiene: one 2 ms window sits inside the box-to-box noise): wall clock per
-    # window, bracketed like the first one
-    win_ms = [elapsed / args.steps * 1e3]
-    for _ in range(max(0, args.windows - 1)):
+    if args.dump_outputs:
+        # what a caller of the timed path receives from one step: the step once more, into a zeroed output (each
+        # timed step added exactly this with --accumulate 1; the accumulated vector depends on the settle probes)
+        d_x.zero_()
+        step()
         torch.cuda.synchronize()
-        barrier()
-        tw0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        barrier()
-        tw = time.perf_counter() - tw0
-        if world > 1:
-            t = torch.tensor([tw], dtype=torch.float64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            tw = float(t.item())
-        win_ms.append(tw / args.steps * 1e3)
-
-    # ---- the halo exchange alone (pack, transfer, unpack-add; the rows it moves are whatever the last step left)
-    halo_info = None
-    if halo is not None:
-        scratch = torch.zeros_like(d_x)
-        for _ in range(2):
-            halo.reduce(scratch)
-        torch.cuda.synchronize()
-        barrier()
-        th0 = time.perf_counter()
-        for _ in range(args.steps):
-            halo.reduce(scratch)
-        torch.cuda.synchronize()
-        barrier()
-        th = torch.tensor([(time.perf_counter() - th0) / args.steps * 1e3], dtype=torch.float64, device=dev)
-        dist.all_reduce(th, op=dist.ReduceOp.MAX)
-        if args.ev:
-            hs, hr = part.conforming_halo(k)
-            b_s, b_r = 8 * nrhs * sum(len(v) for v in hs.values()), 8 * nrhs * sum(len(v) for v in hr.values())
-        else:
-            b_s, b_r = part.halo_bytes(nrt, nrhs)
-        hb = torch.tensor([float(b_s), float(b_r)], dtype=torch.float64, device=dev)
-        hmax = hb.clone()
-        dist.all_reduce(hmax, op=dist.ReduceOp.MAX)
-        halo_info = {"transport": "eqlb_halo_exchange (RCCL ncclSend/ncclRecv through the C ABI)" if comm is not None
-                     else "torch.distributed isend/irecv (nccl backend = RCCL)",
-                     "rank0_bytes_sent": int(b_s), "rank0_bytes_received": int(b_r),
-                     "max_bytes_sent": int(hmax[0].item()), "max_bytes_received": int(hmax[1].item()),
-                     "halo_only_ms": float(th.item()),
-                     "note": "halo_only_ms = pack + transfer + unpack-add alone, max over ranks, mean of K calls; "
-                             "inside a step it overlaps the sweep of the interior tiles"}
-        del scratch
-
-    # ---- per-kernel device times.  A step that is ONE kernel launch: the two HIP events that bracket the
-    # timed region.  A step of several kernels: the same K steps once more, now with the library's HIP
-    # event pairs around each kernel group on the launch stream (they would put barrier packets between
-    # the launches of the timed region itself).
-    bytes_sweep = float(compulsory_bytes_per_cell(k, nrhs, args.ev) * part.ncells_owned)
-    if args.ev:  # library default: tiled launch for k <= 3
-        patch_kernel = f"k_se_patch_tiled<K={k},EV>" if k <= 3 else f"k_ev_patch_fused<K={k}>"
-    elif args.scatter == 2 and args.stress:
-        patch_kernel = "k_se_stress_tiled"
-    elif args.scatter == 2:
-        patch_kernel = f"k_se_patch_tiled<K={k}>"
-    elif fused:
-        patch_kernel = f"k_se_patch_fused<K={k}>"
-    else:
-        patch_kernel = None
-    bins_ms = None
-    if single_kernel:
-        if nrhs > 1 and not args.stress:
-            patch_kernel = (f"k_se_patch_tiled_multi<K={k}> ({nrhs} right-hand sides)" if args.multi_rhs
-                            else patch_kernel + f" x{nrhs} launches")
-        kernels_ms = {patch_kernel: step_dev_ms}
-        timing_method = "two HIP events around the timed region / steps"
-    elif two_phase:
-        # per-launch event pairs would serialise the two launches of a step against the halo exchange
-        kernels_ms = {"step (two tile-range launches + halo pack / RCCL send-recv / unpack)": step_dev_ms}
-        timing_method = "two HIP events around the timed region / steps (whole step incl. halo exchange)"
-    else:
-        eq.set_option("timing", 1)
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        bins_ms = [eq.last_kernel_ms(b) for b in range(5)]
-        kernels_ms = {}
-        if fused:
-            kernels_ms[patch_kernel + (f" x{nrhs} rows" if nrhs > 1 else "")] = bins_ms[0]
-        else:
-            kernels_ms.update({f"k_se_patch<K={k},P={4 << b}>": bins_ms[b] for b in range(5) if bins_ms[b] > 0})
-        if args.stress:
-            lean = k == 2  # no flux BCs on the benchmark's stress rows
-            kernels_ms["k_se_weaksym_lean" if lean else f"k_se_weaksym<K={k}>"] = eq.last_kernel_ms(6)
-        red = eq.last_kernel_ms(5)
-        if red > 0:
-            kernels_ms["k_ev_reduce" if args.ev else "k_reduce_slots"] = red
-        if halo is not None:
-            kernels_ms["step incl. halo exchange"] = step_dev_ms
-        timing_method = ("HIP event pair per kernel group, measured over the same K steps repeated after the "
-                         "timed region (mean)")
-    eq.set_option("timing", 0)
-    kname = max(kernels_ms, key=kernels_ms.get)
-    if single_kernel or two_phase:
-        alg_bytes, t_roof = bytes_sweep, step_dev_ms
-        roof_note = None
-    elif fused or args.stress:
-        # several kernels share the sweep's compulsory bytes (inputs read once, output written once):
-        # the fraction is the whole step's, the kernel named is the longest one
-        alg_bytes = bytes_sweep
-        t_roof = step_dev_ms
-        roof_note = ("multi-kernel step: achieved = compulsory bytes of the whole step / device time of a step "
-                     "(two HIP events around the timed region / steps); `kernel` is the longest one (all_kernels_ms)")
-    else:      # one launch per bin: share of the sweep done by the dominant bin's launch
-        ncells_bin = part.patch_cells_per_bin()
-        dom = int(np.argmax(bins_ms))
-        alg_bytes = bytes_sweep * ncells_bin[dom] / float(sum(ncells_bin))
-        t_roof = bins_ms[dom]
-        roof_note = None
-    achieved = alg_bytes / (t_roof * 1e-3) / 1e9 if t_roof > 0 else 0.0
-    peak = 8000.0
-    pmc = measured_counters(kname) if n == 500 and world == 1 else {}
+        eq.check_status(stream)
+        dump_output(args.dump_outputs, "flux_hdiv" if world == 1 else f"flux_hdiv_rank{rank}", d_x.cpu().numpy())
 
     out = {
         "metric": metric_name(args),
@@ -547,9 +466,6 @@ def main():
         "settle_probes": {"n": len(settle), "ms_per_step": [float(v) for v in settle],
                           "note": "untimed probes of K steps between the W warmup steps and the timed region, "
                                   "repeated for at least 40 ms and until two agree within 1 % (GPU clocks after the idle set-up)"},
-        "ms_per_step_windows": {"n": len(win_ms), "min": float(np.min(win_ms)), "median": float(np.median(win_ms)),
-                                "max": float(np.max(win_ms)), "all": [float(w) for w in win_ms],
-                                "note": "the K-step window repeated; value / ms_per_step are the first window's"},
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -570,7 +486,135 @@ def main():
             "scatter": ("tiled" if k <= 3 else "slots") if args.ev else eq_scatter_name(args.scatter),
             "accumulate": bool(args.accumulate),
         },
-        "roofline": {
+    }
+    if tiling is not None:
+        out["config"]["tiling"] = tiling
+
+    if args.full:
+        # the same window again (bench hygiene: one 2 ms window sits inside the box-to-box noise): wall clock per
+        # window, bracketed like the first one
+        win_ms = [elapsed / args.steps * 1e3]
+        for _ in range(max(0, args.windows - 1)):
+            torch.cuda.synchronize()
+            barrier()
+            tw0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            barrier()
+            tw = time.perf_counter() - tw0
+            if world > 1:
+                t = torch.tensor([tw], dtype=torch.float64, device=dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                tw = float(t.item())
+            win_ms.append(tw / args.steps * 1e3)
+
+        # ---- the halo exchange alone (pack, transfer, unpack-add; the rows it moves are whatever the last step left)
+        halo_info = None
+        if halo is not None:
+            scratch = torch.zeros_like(d_x)
+            for _ in range(2):
+                halo.reduce(scratch)
+            torch.cuda.synchronize()
+            barrier()
+            th0 = time.perf_counter()
+            for _ in range(args.steps):
+                halo.reduce(scratch)
+            torch.cuda.synchronize()
+            barrier()
+            th = torch.tensor([(time.perf_counter() - th0) / args.steps * 1e3], dtype=torch.float64, device=dev)
+            dist.all_reduce(th, op=dist.ReduceOp.MAX)
+            if args.ev:
+                hs, hr = part.conforming_halo(k)
+                b_s, b_r = 8 * nrhs * sum(len(v) for v in hs.values()), 8 * nrhs * sum(len(v) for v in hr.values())
+            else:
+                b_s, b_r = part.halo_bytes(nrt, nrhs)
+            hb = torch.tensor([float(b_s), float(b_r)], dtype=torch.float64, device=dev)
+            hmax = hb.clone()
+            dist.all_reduce(hmax, op=dist.ReduceOp.MAX)
+            halo_info = {"transport": "eqlb_halo_exchange (RCCL ncclSend/ncclRecv through the C ABI)" if comm is not None
+                         else "torch.distributed isend/irecv (nccl backend = RCCL)",
+                         "rank0_bytes_sent": int(b_s), "rank0_bytes_received": int(b_r),
+                         "max_bytes_sent": int(hmax[0].item()), "max_bytes_received": int(hmax[1].item()),
+                         "halo_only_ms": float(th.item()),
+                         "note": "halo_only_ms = pack + transfer + unpack-add alone, max over ranks, mean of K calls; "
+                                 "inside a step it overlaps the sweep of the interior tiles"}
+            del scratch
+
+        # ---- per-kernel device times.  A step that is ONE kernel launch: the two HIP events that bracket the
+        # timed region.  A step of several kernels: the same K steps once more, now with the library's HIP
+        # event pairs around each kernel group on the launch stream (they would put barrier packets between
+        # the launches of the timed region itself).
+        bytes_sweep = float(compulsory_bytes_per_cell(k, nrhs, args.ev) * part.ncells_owned)
+        if args.ev:  # library default: tiled launch for k <= 3
+            patch_kernel = f"k_se_patch_tiled<K={k},EV>" if k <= 3 else f"k_ev_patch_fused<K={k}>"
+        elif args.scatter == 2 and args.stress:
+            patch_kernel = "k_se_stress_tiled"
+        elif args.scatter == 2:
+            patch_kernel = f"k_se_patch_tiled<K={k}>"
+        elif fused:
+            patch_kernel = f"k_se_patch_fused<K={k}>"
+        else:
+            patch_kernel = None
+        bins_ms = None
+        if single_kernel:
+            if nrhs > 1 and not args.stress:
+                patch_kernel = (f"k_se_patch_tiled_multi<K={k}> ({nrhs} right-hand sides)" if args.multi_rhs
+                                else patch_kernel + f" x{nrhs} launches")
+            kernels_ms = {patch_kernel: step_dev_ms}
+            timing_method = "two HIP events around the timed region / steps"
+        elif two_phase:
+            # per-launch event pairs would serialise the two launches of a step against the halo exchange
+            kernels_ms = {"step (two tile-range launches + halo pack / RCCL send-recv / unpack)": step_dev_ms}
+            timing_method = "two HIP events around the timed region / steps (whole step incl. halo exchange)"
+        else:
+            eq.set_option("timing", 1)
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            bins_ms = [eq.last_kernel_ms(b) for b in range(5)]
+            kernels_ms = {}
+            if fused:
+                kernels_ms[patch_kernel + (f" x{nrhs} rows" if nrhs > 1 else "")] = bins_ms[0]
+            else:
+                kernels_ms.update({f"k_se_patch<K={k},P={4 << b}>": bins_ms[b] for b in range(5) if bins_ms[b] > 0})
+            if args.stress:
+                lean = k == 2  # no flux BCs on the benchmark's stress rows
+                kernels_ms["k_se_weaksym_lean" if lean else f"k_se_weaksym<K={k}>"] = eq.last_kernel_ms(6)
+            red = eq.last_kernel_ms(5)
+            if red > 0:
+                kernels_ms["k_ev_reduce" if args.ev else "k_reduce_slots"] = red
+            if halo is not None:
+                kernels_ms["step incl. halo exchange"] = step_dev_ms
+            timing_method = ("HIP event pair per kernel group, measured over the same K steps repeated after the "
+                             "timed region (mean)")
+        eq.set_option("timing", 0)
+        kname = max(kernels_ms, key=kernels_ms.get)
+        if single_kernel or two_phase:
+            alg_bytes, t_roof = bytes_sweep, step_dev_ms
+            roof_note = None
+        elif fused or args.stress:
+            # several kernels share the sweep's compulsory bytes (inputs read once, output written once):
+            # the fraction is the whole step's, the kernel named is the longest one
+            alg_bytes = bytes_sweep
+            t_roof = step_dev_ms
+            roof_note = ("multi-kernel step: achieved = compulsory bytes of the whole step / device time of a step "
+                         "(two HIP events around the timed region / steps); `kernel` is the longest one (all_kernels_ms)")
+        else:      # one launch per bin: share of the sweep done by the dominant bin's launch
+            ncells_bin = part.patch_cells_per_bin()
+            dom = int(np.argmax(bins_ms))
+            alg_bytes = bytes_sweep * ncells_bin[dom] / float(sum(ncells_bin))
+            t_roof = bins_ms[dom]
+            roof_note = None
+        achieved = alg_bytes / (t_roof * 1e-3) / 1e9 if t_roof > 0 else 0.0
+        peak = 8000.0
+        pmc = measured_counters(kname) if n == 500 and world == 1 else {}
+
+        out["ms_per_step_windows"] = {"n": len(win_ms), "min": float(np.min(win_ms)),
+                                      "median": float(np.median(win_ms)), "max": float(np.max(win_ms)),
+                                      "all": [float(w) for w in win_ms],
+                                      "note": "the K-step window repeated; value / ms_per_step are the first window's"}
+        out["roofline"] = {
             "bound": "hbm",
             "kernel": kname,
             "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
@@ -580,41 +624,38 @@ def main():
             "kernel_ms": kernels_ms[kname],
             "kernel_ms_method": timing_method,
             "all_kernels_ms": kernels_ms,
-        },
-        "cold": cold,
-    }
-    if roof_note:
-        out["roofline"]["note"] = roof_note
-    if pmc.get("insts_valu"):
-        # the binding resource of this kernel is VALU issue + latency, not HBM:
-        # issue floor = wave-level VALU instructions / 1024 SIMDs x 2.0 ns, the MEASURED issue time of a
-        # wave64 instruction on one SIMD of this part at 4 waves/SIMD (fp64 FMA 2.10 ns, fp64 MUL / ADD and
-        # 32-bit DPP moves 1.91 - 1.98 ns: tools/microbench/valu_rate.hip, profiles/r02_valu_rate.txt) -
-        # i.e. 4 cycles at the ~2.0 GHz the chip holds under fp64 load, not at the 2.4 GHz of the data sheet
-        floor_ms = pmc["insts_valu"] / 1024.0 * VALU_NS_PER_INSTRUCTION * 1e-6
-        out["roofline"]["valu_floor_ms"] = floor_ms
-        out["roofline"]["valu_frac"] = floor_ms / kernels_ms[kname] if kernels_ms[kname] > 0 else None
-        out["roofline"]["valu_source"] = pmc.get("source")
-    if halo_info is not None:
-        out["halo"] = halo_info
-    if tiling is not None:
-        out["config"]["tiling"] = tiling
-    if res is not None:
-        out["div_residual_L2"] = res
-        out["rhs_norm_L2"] = nrm
-        out["div_residual_rel"] = res / nrm
-    if checks:
-        out["checks"] = checks
+        }
+        out["cold"] = cold
+        if roof_note:
+            out["roofline"]["note"] = roof_note
+        if pmc.get("insts_valu"):
+            # the binding resource of this kernel is VALU issue + latency, not HBM:
+            # issue floor = wave-level VALU instructions / 1024 SIMDs x 2.0 ns, the MEASURED issue time of a
+            # wave64 instruction on one SIMD of this part at 4 waves/SIMD (fp64 FMA 2.10 ns, fp64 MUL / ADD and
+            # 32-bit DPP moves 1.91 - 1.98 ns: tools/microbench/valu_rate.hip, profiles/r02_valu_rate.txt) -
+            # i.e. 4 cycles at the ~2.0 GHz the chip holds under fp64 load, not at the 2.4 GHz of the data sheet
+            floor_ms = pmc["insts_valu"] / 1024.0 * VALU_NS_PER_INSTRUCTION * 1e-6
+            out["roofline"]["valu_floor_ms"] = floor_ms
+            out["roofline"]["valu_frac"] = floor_ms / kernels_ms[kname] if kernels_ms[kname] > 0 else None
+            out["roofline"]["valu_source"] = pmc.get("source")
+        if halo_info is not None:
+            out["halo"] = halo_info
+        if res is not None:
+            out["div_residual_L2"] = res
+            out["rhs_norm_L2"] = nrm
+            out["div_residual_rel"] = res / nrm
+        if checks:
+            out["checks"] = checks
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.ev:
-        out["cpu_baseline"] = cpu_baseline_ev(mesh, k, ft, G, f)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline and args.stress:
-        out["cpu_baseline"] = cpu_baseline_stress(mesh, k, ft, G.reshape(2, -1), f.reshape(2, -1))
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
-        # (R right-hand sides: the CPU figure is the one-RHS sweep, R times the work per patch on the device side)
-        out["cpu_baseline"] = cpu_baseline(mesh, k, ft[:1], G.reshape(nrhs, -1)[0], f.reshape(nrhs, -1)[0], npatch_local)
-        if cpu_all is not None:
-            out["cpu_baseline_all_cores"] = cpu_all
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and args.ev:
+            out["cpu_baseline"] = cpu_baseline_ev(mesh, k, ft, G, f)
+        elif rank == 0 and world == 1 and not args.no_cpu_baseline and args.stress:
+            out["cpu_baseline"] = cpu_baseline_stress(mesh, k, ft, G.reshape(2, -1), f.reshape(2, -1))
+        elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+            # (R right-hand sides: the CPU figure is the one-RHS sweep, R times the work per patch on the device side)
+            out["cpu_baseline"] = cpu_baseline(mesh, k, ft[:1], G.reshape(nrhs, -1)[0], f.reshape(nrhs, -1)[0], npatch_local)
+            if cpu_all is not None:
+                out["cpu_baseline_all_cores"] = cpu_all
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

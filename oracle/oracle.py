@@ -19,9 +19,9 @@ _lib = None
 def build(force: bool = False):
     """Compile the C restatement (gcc) into oracle/_build/."""
     src = os.path.join(_HERE, "eqlb_oracle.c")
-    deps = [src, src[:-2] + ".h", src[:-2] + "_ev.c"]
-    # the library is compiled with -march=native and travels with the repository snapshot: rebuild where the
-    # host CPU is another one than the one it was built on
+    deps = [src, src[:-2] + ".h", src[:-2] + "_ev.c", os.path.join(_HERE, "Makefile")]
+    # the library travels with the repository snapshot: rebuild where the host CPU is another one than the one it
+    # was built on
     stamp, host = os.path.join(os.path.dirname(_LIB_PATH), "host.txt"), _host_cpu()
     try:
         built_on = open(stamp).read()

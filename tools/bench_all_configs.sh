@@ -1,11 +1,13 @@
 #!/bin/bash
 # bench_all_configs.sh: one bench.py line per configuration quoted in DESIGN.md section 7 (on the GPU box)
+# (--full: the windows, per-kernel times and residual printed below; logs under $OUT)
 set -e
-mkdir -p gpurun_out
-run() { n=$1; shift; python bench.py --no-cpu-baseline "$@" > gpurun_out/cfg_$n.log 2>&1; python - "$n" <<'PY'
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+run() { n=$1; shift; python bench.py --full --no-cpu-baseline "$@" > "$OUT/cfg_$n.log" 2>&1; python - "$n" "$OUT/cfg_$n.log" <<'PY'
 import json, sys
 n = sys.argv[1]
-d = json.loads(open(f"gpurun_out/cfg_{n}.log").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 w = d.get("ms_per_step_windows", {})
 print(f"{n:10s} ms/step {d['ms_per_step']:.4f} [min {w.get('min', 0):.4f} med {w.get('median', 0):.4f} max {w.get('max', 0):.4f}] value {d['value']:.3e} kernels {d['roofline'].get('all_kernels_ms')} res {d.get('div_residual_rel')}")
 PY

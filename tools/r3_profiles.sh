@@ -6,9 +6,9 @@ O=gpurun_out/r3p
 mkdir -p $O
 WHAT=${1:-traces}   # traces | pmc | pmc2  (a gpurun call is limited to 20 minutes)
 trace() { n=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_$n -- python3 bench.py --no-cpu-baseline --windows 2 "$@" > $O/t_$n.log 2>&1 || echo "trace $n failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_$n -- python3 bench.py --full --no-cpu-baseline --windows 2 "$@" > $O/t_$n.log 2>&1 || echo "trace $n failed"
   f=$(find $O/t_$n -name "*_kernel_stats.csv" | head -1)
-  { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --windows 2 $*  (MI355X, gfx950, ROCm 7.2); bench line: $(grep -a '^{"metric"' $O/t_$n.log | tail -1 | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("ms_per_step", round(d["ms_per_step"],4), "windows", [round(v,4) for v in d["ms_per_step_windows"]["all"]], "kernel_ms", d["roofline"]["all_kernels_ms"])' 2>/dev/null); the trace covers warm-up, settle probes and all windows: its average lies above the settled windows"; head -8 "$f"; } > $O/${n}_trace.csv
+  { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --windows 2 $*  (MI355X, gfx950, ROCm 7.2); bench line: $(grep -a '^{"metric"' $O/t_$n.log | tail -1 | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("ms_per_step", round(d["ms_per_step"],4), "windows", [round(v,4) for v in d["ms_per_step_windows"]["all"]], "kernel_ms", d["roofline"]["all_kernels_ms"])' 2>/dev/null); the trace covers warm-up, settle probes and all windows: its average lies above the settled windows"; head -8 "$f"; } > $O/${n}_trace.csv
   rm -rf $O/t_$n
   cat $O/${n}_trace.csv | head -4
 }

@@ -34,7 +34,7 @@ def main():
     dist.P2POp = P2POp
     # (--halo torch: a real RCCL communicator of N ranks cannot be made by one process)
     sys.argv = ["bench.py", "--gpus", os.environ["WORLD_SIZE"], "--steps", "10", "--warmup", "2", "--n", "200",
-                "--halo", "torch"] \
+                "--halo", "torch", "--full"] \
         + sys.argv[1:]  # later flags override the defaults
     import bench
     bench.main()
