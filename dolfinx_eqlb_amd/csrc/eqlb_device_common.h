@@ -23,6 +23,12 @@ __host__ __device__ constexpr double bcoef(int j, int i)
   return (i > j) ? 0.0 : ((i % 2 == 0) ? 1.0 : -1.0) * binom(j, i);
 }
 
+// weak-symmetry kernels: relative size (against the largest entry of the Schur system) below which a
+// pivot counts as zero
+#ifndef EQLB_WS_PIVOT_RTOL
+#define EQLB_WS_PIVOT_RTOL 1e-11
+#endif
+
 // ---- wave-level helpers -----------------------------------------------------------------------
 // LDS traffic between lanes of ONE wave: DS operations of a wave execute in order, the fences
 // keep the compiler from moving accesses across the hand-off.

@@ -195,6 +195,8 @@ int tile_cells_of(int k);
 int tile_cells_ev_of(int k);
 int tile_cells_max_of(int k);
 int launch_se_weaksym(int k, int P, bool no_flux_bcs, const SeArgs& a, hipStream_t stream);
+// RT_4 with P >= 16 and RT_3 with P = 64 (banded chain + border, eqlb_se_weaksym_banded.hip)
+int launch_se_weaksym_banded(int k, int P, const SeArgs& a, hipStream_t stream);
 // fused stress launch (RT_2, no stress flux BCs, patches of up to 8 facets): rows 0, 1 + weak symmetry
 // mixed: tile lists with every patch of up to 8 lanes (full ones first; generic instance of the body for the others),
 // else lists of full patches only

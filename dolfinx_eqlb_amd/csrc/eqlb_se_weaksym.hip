@@ -20,11 +20,6 @@
 namespace eqlb
 {
 
-// relative size (against the largest entry of the Schur system) below which a pivot counts as zero
-#ifndef EQLB_WS_PIVOT_RTOL
-#define EQLB_WS_PIVOT_RTOL 1e-11
-#endif
-
 template <int K, int P>
 struct WsSizes
 {
@@ -1239,9 +1234,12 @@ int launch_se_weaksym(int k, int P, bool no_flux_bcs, const SeArgs& a, hipStream
     return launch_ws_lean<8>(a, stream);
   if (k == 2)
     return launch_ws_k<2>(P, a, stream);
+  // the bins whose dense tiles do not fit the LDS (RT_4 from 9 facets, RT_3 from 33): banded solver
+  if ((k == 4 && P >= 16) || (k == 3 && P == 64))
+    return launch_se_weaksym_banded(k, P, a, stream);
   if (k == 3)
     return launch_ws_k<3>(P, a, stream);
-  if (k == 4 && P == 4) // RT_4: patches of up to 8 facets, like its row sweeps
+  if (k == 4 && P == 4) // RT_4, patches of up to 8 facets: dense tiles
     return launch_ws_t<4, 4>(a, stream);
   if (k == 4 && P == 8)
     return launch_ws_t<4, 8>(a, stream);
