@@ -35,7 +35,24 @@ EXPORTED_SYMBOLS = [
     "eqlb_ev_set_basis_transform", "eqlb_se_estimate_stress", "eqlb_oscillation",
     "eqlb_halo_exchange", "eqlb_halo_reduce", "eqlb_rccl_get_unique_id", "eqlb_rccl_comm_create",
     "eqlb_rccl_comm_destroy", "eqlb_halo_create", "eqlb_halo_destroy", "eqlb_halo_bytes", "eqlb_halo_reduce_plan",
+    "eqlb_se_tiling_blocks", "eqlb_ev_tiling_blocks",
 ]
+
+# eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
+# in the order of EQLB_TB_FULL ... EQLB_TB_PADDING; then the tiles with the zero flag (EQLB_TB_ZERO_TILES)
+TILING_BLOCK_KINDS = ("full", "interior", "nfix1", "nfix2", "nfix3", "generic", "padding")
+_TB_COUNT = 5 * len(TILING_BLOCK_KINDS) + 1
+
+
+def _tiling_blocks(fn, h):
+    """dict kind -> [count per bin 0 ... 4] (TILING_BLOCK_KINDS), and "zero_tiles" -> int."""
+    out = (C.c_int64 * _TB_COUNT)()
+    _check(fn(h, out, C.c_int32(_TB_COUNT)))
+    v = [int(x) for x in out]
+    nk = len(TILING_BLOCK_KINDS)
+    d = {kind: [v[nk * b + i] for b in range(5)] for i, kind in enumerate(TILING_BLOCK_KINDS)}
+    d["zero_tiles"] = v[5 * nk]
+    return d
 
 _lib = None
 
@@ -183,6 +200,11 @@ class SemiExplicitEquilibrator:
         return dict(zip(("ntiles", "cells_per_tile", "patch_instances", "lane_slots"),
                         [int(x.value) for x in v]))
 
+    def tiling_blocks(self):
+        """Wave-blocks of the tiled launch per body instance and bin (eqlb_se_tiling_blocks): dict kind ->
+        [count for P = 4, 8, 16, 32, 64] for the kinds of TILING_BLOCK_KINDS, and "zero_tiles"."""
+        return _tiling_blocks(lib().eqlb_se_tiling_blocks, self._h)
+
     def equilibrate_host(self, flux_dg, rhs_dg, flux_hdiv=None):
         """Host numpy arrays in/out; flux_hdiv is accumulated (+=) like the reference."""
         m = self.dmesh.mesh
@@ -324,6 +346,10 @@ class ConstrainedMinEquilibrator:
             assert nm.size == m.nnodes
         _check(lib().eqlb_ev_set_boundary(self._h, _hp(ft), _hp(bv) if bv is not None else None,
                                           _hp(nm) if nm is not None else None))
+
+    def tiling_blocks(self):
+        """As SemiExplicitEquilibrator.tiling_blocks (eqlb_ev_tiling_blocks)."""
+        return _tiling_blocks(lib().eqlb_ev_tiling_blocks, self._h)
 
     def _nout(self):
         return self.dmesh.mesh.ncells * self.nrt if self.output == 1 else self.ndofs

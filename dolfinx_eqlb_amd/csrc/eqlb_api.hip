@@ -119,6 +119,7 @@ void free_boundary(eqlb_se* h)
   dfree(h->t_pflag);
   h->ntiles = 0;
   h->t_mixed = false;
+  std::fill(h->t_blocks, h->t_blocks + EQLB_TB_COUNT, int64_t(0));
   h->boundary_set = false;
 }
 // Grouped boundary patches of the stress path (se/reconstruction.hpp:170-234, se/Patch.cpp:60-104,
@@ -550,6 +551,59 @@ void parallel_for(int64_t n, int64_t min_chunk, F f)
   w.join();
 }
 
+// Wave-blocks per bin and body instance that the tiled kernel of this handle runs over all tiles (eqlb_se_tiling_blocks):
+// the split of a tile's list by k_se_stress_tiled (h->t_stress; full_only: lists of full patches, padded) or
+// k_se_patch_tiled*, through the range functions the kernels call (eqlb_internal.h)
+void count_tile_blocks(eqlb_se* h, const std::vector<eqlb::TileDesc>& tiles, bool full_only)
+{
+  int64_t* out = h->t_blocks;
+  std::fill(out, out + EQLB_TB_COUNT, int64_t(0));
+  const int K = h->k;
+  for (const eqlb::TileDesc& td : tiles)
+  {
+    out[EQLB_TB_ZERO_TILES] += td.zero ? 1 : 0;
+    for (int b = 0; b < eqlb::MAX_BINS; ++b)
+    {
+      const int P = eqlb::BIN_P[b];
+      int64_t* o = out + EQLB_TB_PER_BIN * b;
+      if (h->t_stress)
+      {
+        if (b >= 2)
+          continue; // the fused kernel takes the bins 0, 1
+        if (full_only)
+        {
+          o[EQLB_TB_FULL] += eqlb::tile_wb_whole(td.npatch[b], P);
+          o[EQLB_TB_PADDING] += td.npatch[b] - td.nint[b];
+          continue;
+        }
+        const int nwb = eqlb::tile_wb_all(td.npatch[b], P), nwb_full = eqlb::tile_wb_whole(td.nfull[b], P);
+        int c0[3], c1[3];
+        for (int j = 0; j < 3; ++j)
+          if (b == 0)
+            eqlb::tile_nfix_range<4>(td, 0, j, c0[j], c1[j]);
+          else
+            eqlb::tile_nfix_range<8>(td, 1, j, c0[j], c1[j]);
+        int nfix = 0;
+        for (int j = 0; j < 3; ++j)
+        {
+          o[EQLB_TB_NFIX1 + j] += c1[j] - c0[j];
+          nfix += c1[j] - c0[j];
+        }
+        o[EQLB_TB_FULL] += nwb_full;
+        o[EQLB_TB_GENERIC] += nwb - nwb_full - nfix;
+        continue;
+      }
+      const int nwb = eqlb::tile_wb_all(td.npatch[b], P);
+      const int nwb_full = eqlb::tile_spec_full(K, P) ? eqlb::tile_wb_whole(td.nfull[b], P) : 0;
+      const int nwb_int = eqlb::tile_spec_interior(K, P) ? eqlb::tile_wb_whole(td.nint[b], P) : 0;
+      const int nint = std::max(nwb_int - nwb_full, 0); // (k_se_patch_tiled: u < nwb_full first, then u < nwb_int)
+      o[EQLB_TB_FULL] += nwb_full;
+      o[EQLB_TB_INTERIOR] += nint;
+      o[EQLB_TB_GENERIC] += nwb - nwb_full - nint;
+    }
+  }
+}
+
 // Tiled SoA of the plain flux equilibration (EQLB_SCATTER_TILED): cells bisected recursively by
 // their centroids into tiles of TC cells; a tile lists every (masked-in) node of its cells.
 int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::BuildArgs a, int tc_fixed = 0, int max_bin = eqlb::MAX_BINS,
@@ -877,6 +931,7 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
     }
   });
   tm.lap("tiles: patch lists");
+  count_tile_blocks(h, tiles, full_only);
   h->ntiles = ntiles;
   h->tile_tc = TC;
   h->t_nslots = slotctr;
@@ -1469,6 +1524,17 @@ int eqlb_se_tiling_info(const eqlb_se_t* h, int64_t* ntiles, int64_t* cells_per_
     *npatch_instances = h->t_npatch;
   if (nlane_slots)
     *nlane_slots = h->t_nslots;
+  return EQLB_OK;
+}
+
+int eqlb_se_tiling_blocks(const eqlb_se_t* h, int64_t* out, int32_t n)
+{
+  if (!h || !h->boundary_set)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_tiling_blocks: set the boundary first");
+  if (n < 0 || (n > 0 && !out))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_tiling_blocks: invalid argument");
+  for (int32_t i = 0; i < std::min<int32_t>(n, EQLB_TB_COUNT); ++i)
+    out[i] = h->ntiles > 0 ? h->t_blocks[i] : 0;
   return EQLB_OK;
 }
 
@@ -2645,6 +2711,13 @@ int eqlb_ev_check_status(eqlb_ev_t* h, void* stream)
 double eqlb_ev_last_kernel_ms(const eqlb_ev_t* h, int32_t which)
 {
   return h ? eqlb_se_last_kernel_ms(h->se, which) : 0.0;
+}
+
+int eqlb_ev_tiling_blocks(const eqlb_ev_t* h, int64_t* out, int32_t n)
+{
+  if (!h)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_tiling_blocks: null handle");
+  return eqlb_se_tiling_blocks(h->se, out, n);
 }
 
 } // extern "C"

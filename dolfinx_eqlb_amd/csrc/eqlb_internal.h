@@ -116,6 +116,42 @@ struct TileDesc
                            // is never written, the LDS slots of the tile are zeroed first
 };
 
+// Wave-block ranges of one bin of a tile's patch list (P lanes per patch, 64 / P patches per wave-block). The tiled
+// kernels (k_se_patch_tiled*, k_se_stress_tiled) split their lists with these functions, and so does the host count
+// behind eqlb_se_tiling_blocks: it reports what the kernels run.
+#ifndef EQLB_TILE_INTERIOR
+#define EQLB_TILE_INTERIOR 1
+#endif
+#ifndef EQLB_TILE_INTERIOR_K3
+#define EQLB_TILE_INTERIOR_K3 0 // the interior-patch instance for RT_3 as well: no gain on the Delaunay mesh (0.413 - 0.418 ms either way)
+#endif
+#ifndef EQLB_STRESS_NFIX
+#define EQLB_STRESS_NFIX 1 // MIXED kernel: instances for interior patches with P - 1, P - 2, P - 3 cells (0: generic instance)
+#endif
+// k_se_patch_tiled: an instance for whole wave-blocks of full patches (RT_1: the body is too small for the second
+// instance to pay), and one for whole wave-blocks of interior patches of any size (K = 2, P = 8, 16)
+__host__ __device__ constexpr bool tile_spec_full(int K, int P) { return P <= 8 && K >= 2; }
+__host__ __device__ constexpr bool tile_spec_interior(int K, int P)
+{
+  return EQLB_TILE_INTERIOR && ((K == 2 && (P == 8 || P == 16)) || (EQLB_TILE_INTERIOR_K3 && K == 3 && P == 8));
+}
+// wave-blocks of the first n patches: all of them (the last one may be partly empty) / the whole ones only
+__host__ __device__ __forceinline__ int tile_wb_all(int n, int P) { return (n * P + 63) >> 6; }
+__host__ __device__ __forceinline__ int tile_wb_whole(int n, int P) { return (n * P) >> 6; }
+// k_se_stress_tiled with mixed lists: the whole wave-blocks [c0, c1) of the interior patches with P - 1 - j cells,
+// j = 0, 1, 2 (the patches nval[B][j - 1] ... nval[B][j] of the bin; from nfull[B] for j = 0); c1 = c0 where no whole
+// block lies inside, or where that instance does not exist (P - 1 - j < 3)
+template <int P>
+__host__ __device__ __forceinline__ void tile_nfix_range(const TileDesc& td, int B, int j, int& c0, int& c1)
+{
+  constexpr int PER = 64 / P;
+  const int first = (j == 0) ? td.nfull[B] : td.nval[B][j - 1];
+  c0 = (first + PER - 1) / PER;
+  c1 = (EQLB_STRESS_NFIX && P - 1 - j >= 3) ? td.nval[B][j] / PER : 0;
+  if (c1 < c0)
+    c1 = c0;
+}
+
 struct TileArgs
 {
   const TileDesc* tiles;
@@ -315,6 +351,7 @@ struct eqlb_se
   // fused stress launch: the tiles list EVERY patch of the bins 0, 1 (full ones first), not the full ones only - where
   // the others are more than a few per cent of the patches (unstructured meshes); kernel with both instances
   bool t_mixed = false;
+  int64_t t_blocks[EQLB_TB_COUNT] = {}; // wave-blocks per bin and body instance of the tiled kernel (eqlb_se_tiling_blocks)
   // two-phase sweeps (multi-GPU overlap): tiles owning a priority cell are numbered first
   std::vector<int32_t> prio_cells;
   int32_t t_nprio = 0;              // number of priority tiles

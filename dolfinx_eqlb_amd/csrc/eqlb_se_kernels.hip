@@ -2109,12 +2109,6 @@ __device__ __forceinline__ void tile_sweep_flush(const SeArgs& a0, const TileArg
 #ifndef EQLB_EXP_FULLONLY
 #define EQLB_EXP_FULLONLY 0
 #endif
-#ifndef EQLB_TILE_INTERIOR
-#define EQLB_TILE_INTERIOR 1
-#endif
-#ifndef EQLB_TILE_INTERIOR_K3
-#define EQLB_TILE_INTERIOR_K3 0 // the interior-patch instance for RT_3 as well: no gain on the Delaunay mesh (0.413 - 0.418 ms either way)
-#endif
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   constexpr int NW = TILE_THREADS / 64;
   int u = wave;
@@ -2122,16 +2116,16 @@ __device__ __forceinline__ void tile_sweep_flush(const SeArgs& a0, const TileArg
 #define EQLB_TILE_BIN(B, PP)                                                                        \
   {                                                                                                 \
     const int np = td.npatch[B];                                                                    \
-    const int nwb = (np * PP + 63) >> 6;                                                            \
+    const int nwb = tile_wb_all(np, PP);                                                            \
     a.npatch = np;                                                                                  \
     a.slot_offset = td.slot_start[B];                                                               \
     a.patch_offset = td.patch_start[B];                                                             \
     /* complete wave-blocks of full patches (RT_1: the body is too small for the second instance to pay) */ \
-    constexpr bool SPEC = PP <= 8 && K >= 2;                                                        \
-    const int nwb_full = SPEC ? ((td.nfull[B] * PP) >> 6) : 0;                                      \
+    constexpr bool SPEC = tile_spec_full(K, PP);                                                    \
+    const int nwb_full = SPEC ? tile_wb_whole(td.nfull[B], PP) : 0;                                 \
     /* wave-blocks of interior patches of any size (the patches behind the full ones; K = 2, P = 8, 16) */ \
-    constexpr bool SPECI = EQLB_TILE_INTERIOR && ((K == 2 && (PP == 8 || PP == 16)) || (EQLB_TILE_INTERIOR_K3 && K == 3 && PP == 8)); \
-    const int nwb_int = SPECI ? ((td.nint[B] * PP) >> 6) : 0;                                       \
+    constexpr bool SPECI = tile_spec_interior(K, PP);                                               \
+    const int nwb_int = SPECI ? tile_wb_whole(td.nint[B], PP) : 0;                                  \
     for (; u < nwb; u += NW)                                                                        \
     {                                                                                               \
       if (u < nwb_full)                                                                             \

@@ -185,9 +185,6 @@ __device__ __forceinline__ void pcr_apply(double (&r)[NC], const PcrMult<P>& m)
 #ifndef EQLB_STRESS_ROTATED
 #define EQLB_STRESS_ROTATED 1
 #endif
-#ifndef EQLB_STRESS_NFIX
-#define EQLB_STRESS_NFIX 1 // MIXED kernel: instances for interior patches with P - 1, P - 2, P - 3 cells (0: generic instance)
-#endif
 __host__ __device__ constexpr bool rot_nz(int P, int L, int d)
 {
   const int dd = ((d % P) + P) % P, dist = (dd < P - dd) ? dd : P - dd;
@@ -1071,11 +1068,11 @@ k_se_stress_tiled(const SeArgs a0, const TileArgs ta, const StressRows rows)
        registers more than there are and the scratch it brings slows every wave of the kernel; those \
        patches run on the generic kernels (slot path) in the same call */                           \
     const int np = td.npatch[B];                                                                    \
-    const int nwb = MIXED ? ((np * PP + 63) >> 6) : ((np * PP) >> 6);                               \
+    const int nwb = MIXED ? tile_wb_all(np, PP) : tile_wb_whole(np, PP);                            \
     a.npatch = np;                                                                                  \
     a.slot_offset = td.slot_start[B];                                                               \
     a.patch_offset = td.patch_start[B];                                                             \
-    const int nwb_full = MIXED ? ((td.nfull[B] * PP) >> 6) : nwb;                                   \
+    const int nwb_full = MIXED ? tile_wb_whole(td.nfull[B], PP) : nwb;                              \
     /* separate loops, not one loop with a branch: the register allocation of the full-patch instance (no spills \
        on its own) is then not tied to the others (same wave-block -> wave assignment) */            \
     for (; u < nwb_full; u += NW)                                                                   \
@@ -1084,16 +1081,9 @@ k_se_stress_tiled(const SeArgs a0, const TileArgs ta, const StressRows rows)
     {                                                                                               \
       /* interior patches with PP - 1, PP - 2, PP - 3 cells (the tile lists are ordered by it): the whole wave-blocks \
          inside their ranges run the instance with that patch size at compile time */                \
-      constexpr int PER = 64 / PP;                                                                  \
       int c0[3], c1[3];                                                                             \
       _Pragma("unroll") for (int j = 0; j < 3; ++j)                                                 \
-      {                                                                                             \
-        const int first = (j == 0) ? td.nfull[B] : td.nval[B][j - 1];                               \
-        c0[j] = (first + PER - 1) / PER;                                                            \
-        c1[j] = (EQLB_STRESS_NFIX && PP - 1 - j >= 3) ? td.nval[B][j] / PER : 0;                    \
-        if (c1[j] < c0[j])                                                                          \
-          c1[j] = c0[j];                                                                            \
-      }                                                                                             \
+        tile_nfix_range<PP>(td, B, j, c0[j], c1[j]);                                                \
       if constexpr (EQLB_STRESS_NFIX && PP - 1 >= 3)                                                \
         for (int v = c0[0] + wave; v < c1[0]; v += NW)                                              \
           stress_patch_body<PP, false, PP - 1>(a, rows, lds, (int64_t)v * 64 + lane, sSlots, TC);   \

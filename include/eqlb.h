@@ -365,6 +365,32 @@ void eqlb_rccl_comm_destroy(void* comm);
 int eqlb_se_tiling_info(const eqlb_se_t* handle, int64_t* ntiles, int64_t* cells_per_tile,
                         int64_t* npatch_instances, int64_t* nlane_slots);
 
+/* Wave-blocks (64 lanes) of the tiled launch by instance of the patch body, summed over all tiles of the tiling
+ * built by the last eqlb_se_set_boundary: out[EQLB_TB_PER_BIN * b + i] for the bins b = 0 ... 4 (P = 4, 8, 16, 32,
+ * 64 lanes per patch) and
+ *   i = EQLB_TB_FULL      whole wave-blocks of full patches (interior, P cells; k >= 2, P <= 8)
+ *       EQLB_TB_INTERIOR  whole wave-blocks of other interior patches (flux kernel, k = 2, P = 8, 16)
+ *       EQLB_TB_NFIX1 ... EQLB_TB_NFIX3  whole wave-blocks of interior patches with P - 1, P - 2, P - 3 cells
+ *                         (fused stress kernel with mixed tile lists)
+ *       EQLB_TB_GENERIC   every other wave-block (the generic body)
+ *       EQLB_TB_PADDING   padding copies (fused stress kernel with lists of full patches only: copies of a full
+ *                         patch that own no cell fill the last wave-block)
+ * and out[EQLB_TB_ZERO_TILES]: the tiles whose cells have a vertex that is not equilibrated here (node mask, or a
+ * patch left to the generic kernels). The counts are those of the fused stress kernel where the tiling serves it
+ * (stress of RT_2 without flux BCs on the stress rows), of the flux kernel otherwise; all zero without a tiling.
+ * n: length of out (at most EQLB_TB_COUNT entries are written). eqlb_ev_tiling_blocks: the same for an EV handle. */
+#define EQLB_TB_FULL 0
+#define EQLB_TB_INTERIOR 1
+#define EQLB_TB_NFIX1 2
+#define EQLB_TB_NFIX2 3
+#define EQLB_TB_NFIX3 4
+#define EQLB_TB_GENERIC 5
+#define EQLB_TB_PADDING 6
+#define EQLB_TB_PER_BIN 7
+#define EQLB_TB_ZERO_TILES (5 * EQLB_TB_PER_BIN)
+#define EQLB_TB_COUNT (EQLB_TB_ZERO_TILES + 1)
+int eqlb_se_tiling_blocks(const eqlb_se_t* handle, int64_t* out, int32_t n);
+
 /* ---------------------------------------------------------------------------------------------
  * Constrained-minimisation equilibrator (Ern & Vohralik) - replaces
  * `reconstruct_fluxes_minimisation(a, l_pen, l, flux_hdiv, boundary_data)`
@@ -433,6 +459,7 @@ int eqlb_ev_equilibrate_lists(eqlb_ev_t* handle, const double* const* flux_dg, c
 int64_t eqlb_ev_num_patches(const eqlb_ev_t* handle);
 /* which = 0: patch kernel (all bins in one launch), 5: reduction to the conforming DOFs */
 double eqlb_ev_last_kernel_ms(const eqlb_ev_t* handle, int32_t which);
+int eqlb_ev_tiling_blocks(const eqlb_ev_t* handle, int64_t* out, int32_t n); /* as eqlb_se_tiling_blocks */
 int eqlb_ev_check_status(eqlb_ev_t* handle, void* stream); /* as eqlb_se_check_status */
 
 #ifdef __cplusplus
