@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_ev_set_basis_transform", "eqlb_se_estimate_stress", "eqlb_oscillation",
     "eqlb_halo_exchange", "eqlb_halo_reduce", "eqlb_rccl_get_unique_id", "eqlb_rccl_comm_create",
     "eqlb_rccl_comm_destroy", "eqlb_halo_create", "eqlb_halo_destroy", "eqlb_halo_bytes", "eqlb_halo_reduce_plan",
-    "eqlb_se_tiling_blocks", "eqlb_ev_tiling_blocks",
+    "eqlb_se_tiling_blocks", "eqlb_ev_tiling_blocks", "eqlb_ev_create_dg",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -298,14 +298,16 @@ class ConstrainedMinEquilibrator:
     """eqlb_ev_* handle: constrained-minimisation (Ern-Vohralik) equilibrator, flux in the
     conforming hierarchic RT_k (include/eqlb.h)."""
 
-    def __init__(self, dmesh: DeviceMesh, k: int, nrhs: int, cell_dofs=None, ndofs=None):
+    def __init__(self, dmesh: DeviceMesh, k: int, nrhs: int, cell_dofs=None, ndofs=None, degree_dg=None):
         self.dmesh = dmesh
         self.k, self.nrhs = k, nrhs
+        self.degree_dg = k - 1 if degree_dg is None else degree_dg
         self.nrt = k * (k + 2)
-        self.nd = k * (k + 1) // 2
+        self.nd = (self.degree_dg + 1) * (self.degree_dg + 2) // 2
         self.output = 0
         self._h = C.c_void_p()
-        _check(lib().eqlb_ev_create(dmesh._h, C.c_int32(k), C.c_int32(nrhs), C.byref(self._h)))
+        _check(lib().eqlb_ev_create_dg(dmesh._h, C.c_int32(k), C.c_int32(self.degree_dg), C.c_int32(nrhs),
+                                       C.byref(self._h)))
         if cell_dofs is not None:
             cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
             assert cd.shape == (dmesh.mesh.ncells, self.nrt)

@@ -1149,7 +1149,7 @@ try
   }
   (void)estimate_korn;
   std::vector<double> tab;
-  if (eqlb::fill_tables_host(k, degree_dg, tab) != 0 || degree_dg != k - 1 || k > 4)
+  if (eqlb::fill_tables_host(k, degree_dg, tab) != 0 || k > 4)
     return fail(EQLB_ERR_UNSUPPORTED, "RT_%d with DG_%d data%s is not in this build", k, degree_dg,
                 reconstruct_stress ? " (stress)" : "");
   eqlb_se* h = new eqlb_se();
@@ -1288,6 +1288,10 @@ try
   if (h->stress)
     for (size_t i = 0; i < (size_t)2 * m.nfacets && !h->stress_flux_bcs; ++i)
       h->stress_flux_bcs = (facet_type[i] == EQLB_FACET_ESSNT_DUAL);
+  // RT_2 stress: the fused tiled launch (k_se_stress_tiled) reads DG_1 data; DG_0 data take the route of stress flux
+  // BCs - rows into the slots by the patch kernels of the handle's degree, then the weak-symmetry kernel of that route
+  // (launch_se_weaksym with no_flux_bcs = false; it reads no DG data, nor do the Korn kernels)
+  const bool stress_fused_ok = h->k == 2 && h->deg == 1 && !h->stress_flux_bcs;
   // OrientedPatch::set_max_patch_size (se/Patch.cpp:337-404): every local node is checked
   for (int32_t i = 0; i < m.nnodes; ++i)
   {
@@ -1335,7 +1339,7 @@ try
   h->npatch_total = patch_off;
   // fused stress launch (RT_2, no flux BCs on the stress rows): it takes the FULL patches of the bins 0, 1 -
   // interior, as many cells as lanes -, listed first in their bin; the generic kernels take the patches behind them
-  const bool full_first = h->stress && h->k == 2 && !h->stress_flux_bcs && h->mode == 0;
+  const bool full_first = h->stress && stress_fused_ok && h->mode == 0;
   auto is_full = [&](int32_t i) {
     const int b = node_bin[i];
     return full_first && b >= 0 && b < 2 && m.h_node_ncells[i] == m.h_node_nfcts[i]
@@ -1418,7 +1422,7 @@ try
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   tm.lap("plain SoA: upload + builder");
-  h->t_stress = h->stress && h->k == 2 && !h->stress_flux_bcs && h->mode == 0;
+  h->t_stress = h->stress && stress_fused_ok && h->mode == 0;
   if (h->t_stress || (!h->stress && h->k <= 3))
   {
     // fused stress launch: its own tile size, patches of up to 8 facets (bins 0, 1)
@@ -1817,7 +1821,7 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
         select_rhs(as, r, true);
         if (evs && r == 0 && first_bin == 0)
           HIP_TRY(hipEventRecord(evs[0], sp_stream));
-        const int st = (h->mode == 1) ? eqlb::launch_ev_patch_fused(h->k, as, fb, sp_stream)
+        const int st = (h->mode == 1) ? eqlb::launch_ev_patch_fused(h->k, h->deg, as, fb, sp_stream)
                                       : eqlb::launch_se_patch_fused(h->k, h->deg, EQLB_SCATTER_SLOTS, as, fb, sp_stream);
         if (st)
           return fail(st, "fused patch kernel launch failed (k=%d)", h->k);
@@ -1853,6 +1857,10 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
       if (evs && first_bin == 0)
         HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 2], sp_stream));
       select_rhs(as, 0, true); // the kernel works on the slot rows of RHS 0 and 1
+      // the weak-symmetry kernels address the tensors TE ... VQ of the table buffer by the offsets of DG_{k-1}: with
+      // data of a lower degree the segments in front of them (F, H, D) are shorter, the base pointer moves by the
+      // difference (every read stays inside the buffer; TE ... VQ do not depend on the degree)
+      as.tables = h->tables + eqlb::table_offset_te(h->k, h->deg) - eqlb::table_offset_te(h->k, h->k - 1);
       // (overlapping groups of boundary patches: one pass per level, a pass skips the patches of other levels)
       for (int lv = 0; lv < h->ws_levels; ++lv)
         for (int b = 0; b < eqlb::MAX_BINS; ++b)
@@ -1863,7 +1871,8 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
           as.slot_offset = bin_so(b);
           as.patch_offset = bin_po(b);
           as.ws_level = lv;
-          const int st = eqlb::launch_se_weaksym(h->k, h->bins[b].P, !h->stress_flux_bcs, as, sp_stream);
+          const int st = eqlb::launch_se_weaksym(h->k, h->bins[b].P, !h->stress_flux_bcs && h->deg == h->k - 1, as,
+                                                 sp_stream);
           if (st)
             return fail(st, "weak-symmetry kernel launch failed (k=%d, P=%d)", h->k, h->bins[b].P);
         }
@@ -2465,12 +2474,17 @@ int eqlb_halo_unpack_add(int32_t nrhs, int32_t nlist, int32_t nrt, int64_t ncell
 
 // ---- constrained-minimisation (EV) equilibrator ---------------------------------------------------
 int eqlb_ev_create(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, eqlb_ev_t** handle)
+{
+  return eqlb_ev_create_dg(mesh, k, k - 1, nrhs, handle);
+}
+
+int eqlb_ev_create_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, eqlb_ev_t** handle)
 try
 {
   if (!handle)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_create: null argument");
   eqlb_se* se = nullptr;
-  const int st = eqlb_se_create(mesh, k, k - 1, nrhs, 0, 0, &se);
+  const int st = eqlb_se_create(mesh, k, degree_dg, nrhs, 0, 0, &se);
   if (st)
     return st;
   se->mode = 1;

@@ -225,6 +225,19 @@ int launch_se_patch_fused(int k, int deg, int scatter, const SeArgs& a, const Fu
 int launch_se_patch_tiled(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, hipStream_t stream);
 int launch_se_patch_tiled_multi(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, const MultiRhs& mr,
                                 hipStream_t stream);
+// the same launches for projected data of degree deg < k - 1 (eqlb_se_kernels_lowdeg*.hip): the launchers above hand
+// every call with deg != k - 1 over to these
+int launch_se_patch_lowdeg(int k, int deg, int P, int solver, int scatter, const SeArgs& a, hipStream_t stream,
+                           int mode);
+int launch_se_patch_fused_lowdeg(int k, int deg, int scatter, const SeArgs& a, const FusedBins& fb,
+                                 hipStream_t stream);
+int launch_se_patch_tiled_lowdeg(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, hipStream_t stream);
+int launch_se_patch_tiled_multi_lowdeg(int k, int deg, int mode, const SeArgs& a, const TileArgs& t,
+                                       const MultiRhs& mr, hipStream_t stream);
+int launch_ev_patch_fused_lowdeg(int k, int deg, const SeArgs& a, const FusedBins& fb, hipStream_t stream);
+int launch_se_patch_k4_lowdeg(int deg, int P, int solver, int scatter, const SeArgs& a, hipStream_t stream,
+                              int mode); // eqlb_se_kernels_lowdeg_k4.hip
+int fill_tables_k4_lowdeg(int deg, std::vector<double>& out); // tables of RT_4 / DG_deg, deg < 3
 void launch_tile_facet_owner(const DeviceMesh& m, int64_t n, const int32_t* tile_cells, int32_t* code,
                              hipStream_t stream);
 int tile_cells_of(int k);
@@ -239,7 +252,7 @@ int launch_se_weaksym_banded(int k, int P, const SeArgs& a, hipStream_t stream);
 int launch_se_stress_tiled(const SeArgs& a, const TileArgs& t, const double* const* g, const double* const* f,
                            double* const* x, hipStream_t stream, bool mixed = false);
 int stress_tile_cells();
-int launch_ev_patch_fused(int k, const SeArgs& a, const FusedBins& fb, hipStream_t stream);
+int launch_ev_patch_fused(int k, int deg, const SeArgs& a, const FusedBins& fb, hipStream_t stream);
 // conforming <-> broken layout of the EV equilibrator (eqlb_ev.hip); cell_dofs may be nullptr
 // (default numbering: facet*k + j, then nfacets*k + cell*(k^2-k) + i)
 // facet_maps: nullptr (hierarchic RT_k: -I / B) or [3][2][k][k]: broken facet DOFs = map[lf][reversed] x conforming ones
@@ -280,6 +293,7 @@ void device_tiling_prepare();
 int device_tile_order(const DeviceMesh& m, int tc, int32_t ntiles, const double blo[2], const double bhi[2], double inv,
                       std::vector<int32_t>& order);
 size_t table_doubles(int k, int deg);
+size_t table_offset_te(int k, int deg); // first double of TE in the table buffer (Sizes::OFF_TE)
 int fill_tables_host(int k, int deg, std::vector<double>& out);
 
 } // namespace eqlb

@@ -34,9 +34,16 @@
 #define EQLB_PCR_SELECTS 0
 #endif
 
+// EQLB_SE_TEMPLATES_ONLY: the templates of this file without its non-template definitions, for the translation
+// units of the instances at lower data degrees (eqlb_se_kernels_lowdeg.hip, eqlb_se_kernels_lowdeg_k4.hip)
+#ifndef EQLB_SE_TEMPLATES_ONLY
+#define EQLB_SE_TEMPLATES_ONLY 0
+#endif
+
 namespace eqlb
 {
 
+#if !EQLB_SE_TEMPLATES_ONLY
 size_t table_doubles(int k, int deg)
 {
   const int nrt = nrt_of(k), nd = nd_of(deg), nq = nq_of(k);
@@ -49,6 +56,14 @@ size_t table_doubles(int k, int deg)
          + (size_t)9 * k * k + (size_t)3 * nrt * 2 + (size_t)NCOMBO * 2 * nh * 3
          + (size_t)hrow + (size_t)NCOMBO * nh * nd * 2;
 }
+
+size_t table_offset_te(int k, int deg)
+{
+  const int nrt = nrt_of(k), nd = nd_of(deg), nq = nq_of(k);
+  const int hrow = nd * nq + ((nd * nq) & 1);
+  return (size_t)3 * nrt * nrt + (size_t)9 * nd * k + (size_t)3 * hrow + (size_t)6 * nd * nq;
+}
+#endif
 
 template <int K, int DEG>
 static void fill_tables_t(std::vector<double>& out)
@@ -88,6 +103,7 @@ static void fill_tables_t(std::vector<double>& out)
   out.insert(out.end(), R::WG, R::WG + R::WG_SIZE);
 }
 
+#if !EQLB_SE_TEMPLATES_ONLY
 int fill_tables_host(int k, int deg, std::vector<double>& out)
 {
   if (k == 1 && deg == 0)
@@ -104,10 +120,16 @@ int fill_tables_host(int k, int deg, std::vector<double>& out)
     fill_tables_t<3, 1>(out);
   else if (k == 3 && deg == 0)
     fill_tables_t<3, 0>(out);
+  else if (k == 4 && deg >= 0 && deg < 3)
+  {
+    if (fill_tables_k4_lowdeg(deg, out) != 0) // (eqlb_se_kernels_lowdeg_k4.hip: tables generated by the build)
+      return EQLB_ERR_UNSUPPORTED;
+  }
   else
     return EQLB_ERR_UNSUPPORTED;
   return (out.size() == table_doubles(k, deg)) ? 0 : EQLB_ERR_UNSUPPORTED;
 }
+#endif
 
 #ifndef EQLB_EV_FMA
 #define EQLB_EV_FMA 1
@@ -491,6 +513,14 @@ __device__ __forceinline__ void se_patch_body(const SeArgs& a, const int64_t blo
               dvg += gh0;
             else
               dvg += gh1;
+          }
+          else if constexpr (DEG == 0 && K >= 2)
+          {
+            // P0 data: G is constant on the cell, div G = 0 - no D contraction, the one H row weighted by detJ f
+            // (RT_1 keeps the generic contraction, whose D rows are zero as well)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+              Rq[q] = __builtin_fma(fd, tH[q], Rq[q]);
           }
           else if constexpr (DEG == 2 && EQLB_P2_DIV_NODAL)
           {
@@ -1939,8 +1969,11 @@ static int launch_ev_fused_kd(const SeArgs& a, const FusedBins& fb, hipStream_t 
   return (hipGetLastError() == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
-int launch_ev_patch_fused(int k, const SeArgs& a, const FusedBins& fb, hipStream_t stream)
+#if !EQLB_SE_TEMPLATES_ONLY
+int launch_ev_patch_fused(int k, int deg, const SeArgs& a, const FusedBins& fb, hipStream_t stream)
 {
+  if (deg != k - 1)
+    return launch_ev_patch_fused_lowdeg(k, deg, a, fb, stream);
   if (k == 1)
     return launch_ev_fused_kd<1, 0>(a, fb, stream);
   if (k == 2)
@@ -1949,6 +1982,7 @@ int launch_ev_patch_fused(int k, const SeArgs& a, const FusedBins& fb, hipStream
     return launch_ev_fused_kd<3, 2>(a, fb, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
+#endif
 
 // ---- tiled launch: no slot buffer, no reduction pass ----------------------------------------------
 // One workgroup (8 waves) per tile of TC owned cells.  It solves every patch that touches an owned
@@ -1982,6 +2016,7 @@ constexpr int tile_cells_c(int k) { return (k >= 3) ? EQLB_TILE_CELLS_K3 : EQLB_
 #endif
 // largest tile the LDS budget of two workgroups per CU allows (k <= 2: 490 x 144 B + tensors <= 80 KB)
 constexpr int tile_cells_max_c(int k) { return (k >= 3) ? EQLB_TILE_CELLS_K3 : (EQLB_TILE_CELLS > 490 ? EQLB_TILE_CELLS : 490); }
+#if !EQLB_SE_TEMPLATES_ONLY
 int tile_cells_of(int k) { return tile_cells_c(k); }
 int tile_cells_ev_of(int k) { return (k >= 3) ? EQLB_TILE_CELLS_K3_EV : tile_cells_c(k); }
 int tile_cells_max_of(int k) { return tile_cells_max_c(k); }
@@ -2016,6 +2051,7 @@ void launch_tile_facet_owner(const DeviceMesh& m, int64_t n, const int32_t* tile
     hipLaunchKernelGGL(k_tile_facet_owner, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n,
                        tile_cells, m.cell_facets, m.facet_cells_off, m.facet_cells, m.facet_perm, code);
 }
+#endif
 
 // MODE 0: semi-explicit flux, flux_hdiv in the broken layout.  MODE 1: EV patch problems; flush to
 // the conforming DOFs (ta.facet_owner != nullptr) or to the broken layout ("output" = 1).
@@ -2458,9 +2494,12 @@ static int launch_tiled_multi_kd(const SeArgs& a, const TileArgs& t, const Multi
   return (hipGetLastError() == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
+#if !EQLB_SE_TEMPLATES_ONLY
 int launch_se_patch_tiled_multi(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, const MultiRhs& mr,
                                 hipStream_t stream)
 {
+  if (deg != k - 1)
+    return launch_se_patch_tiled_multi_lowdeg(k, deg, mode, a, t, mr, stream);
   if (mode == 1)
   {
     if (k == 1)
@@ -2479,6 +2518,7 @@ int launch_se_patch_tiled_multi(int k, int deg, int mode, const SeArgs& a, const
     return launch_tiled_multi_kd<3, 2, 0>(a, t, mr, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
+#endif
 
 template <int K, int DEG, int MODE>
 static int launch_tiled_kd(const SeArgs& a, const TileArgs& t, hipStream_t stream)
@@ -2501,8 +2541,11 @@ static int launch_tiled_kd(const SeArgs& a, const TileArgs& t, hipStream_t strea
   return (hipGetLastError() == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
+#if !EQLB_SE_TEMPLATES_ONLY
 int launch_se_patch_tiled(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, hipStream_t stream)
 {
+  if (deg != k - 1)
+    return launch_se_patch_tiled_lowdeg(k, deg, mode, a, t, stream);
   if (mode == 1)
   {
     if (k == 1)
@@ -2587,6 +2630,7 @@ int launch_reduce_slots_cells(int nrt, int32_t ncells, int64_t nlist, const int3
     return EQLB_ERR_UNSUPPORTED;
   return 0;
 }
+#endif
 
 // ---- dispatch -------------------------------------------------------------------------------------
 template <int K, int DEG, int P, int SOLVER, int SCATTER, int MODE = 0>
@@ -2679,9 +2723,12 @@ static int launch_fused_kd(int scatter, const SeArgs& a, const FusedBins& fb, hi
   return (hipGetLastError() == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
+#if !EQLB_SE_TEMPLATES_ONLY
 int launch_se_patch_fused(int k, int deg, int scatter, const SeArgs& a, const FusedBins& fb,
                           hipStream_t stream)
 {
+  if (deg != k - 1)
+    return launch_se_patch_fused_lowdeg(k, deg, scatter, a, fb, stream);
   if (k == 1 && deg == 0)
     return launch_fused_kd<1, 0>(scatter, a, fb, stream);
   if (k == 2 && deg == 1)
@@ -2691,17 +2738,20 @@ int launch_se_patch_fused(int k, int deg, int scatter, const SeArgs& a, const Fu
   return EQLB_ERR_UNSUPPORTED;
 }
 
+#endif
+
 // k = 4 (three interior unknowns per cell).  Register solver (three interior unknowns condensed per cell, 3 x 3
 // blocks handed down the chain): every lanes-per-patch bin, slots or atomics.  Dense LDS Cholesky: patches of up to
 // 8 facets (its tile of 52 x 52 / 2 doubles per patch and the 80 KB of RT_4 tensors fill the LDS); the only path of
 // the EV patch problems at k = 4.
+template <int DEG>
 static int launch_k4(int P, int solver, int scatter, const SeArgs& a, hipStream_t stream, int mode)
 {
   if (solver == EQLB_SOLVER_SHUFFLE && mode == 0)
   {
     if (scatter == EQLB_SCATTER_SLOTS)
-      return launch_p<4, 3, 1, 0>(P, a, stream);
-    return launch_p<4, 3, 1, 1>(P, a, stream);
+      return launch_p<4, DEG, 1, 0>(P, a, stream);
+    return launch_p<4, DEG, 1, 1>(P, a, stream);
   }
   if (solver == EQLB_SOLVER_SHUFFLE && mode == 1 && scatter == EQLB_SCATTER_SLOTS)
   {
@@ -2709,15 +2759,15 @@ static int launch_k4(int P, int solver, int scatter, const SeArgs& a, hipStream_
     switch (P)
     {
     case 4:
-      return launch_t<4, 3, 4, 1, 0, 1>(a, stream);
+      return launch_t<4, DEG, 4, 1, 0, 1>(a, stream);
     case 8:
-      return launch_t<4, 3, 8, 1, 0, 1>(a, stream);
+      return launch_t<4, DEG, 8, 1, 0, 1>(a, stream);
     case 16:
-      return launch_t<4, 3, 16, 1, 0, 1>(a, stream);
+      return launch_t<4, DEG, 16, 1, 0, 1>(a, stream);
     case 32:
-      return launch_t<4, 3, 32, 1, 0, 1>(a, stream);
+      return launch_t<4, DEG, 32, 1, 0, 1>(a, stream);
     case 64:
-      return launch_t<4, 3, 64, 1, 0, 1>(a, stream);
+      return launch_t<4, DEG, 64, 1, 0, 1>(a, stream);
     }
     return EQLB_ERR_UNSUPPORTED;
   }
@@ -2727,18 +2777,21 @@ static int launch_k4(int P, int solver, int scatter, const SeArgs& a, hipStream_
   {
     if (scatter != EQLB_SCATTER_SLOTS)
       return EQLB_ERR_UNSUPPORTED;
-    return (P == 4) ? launch_t<4, 3, 4, 0, 0, 1>(a, stream) : launch_t<4, 3, 8, 0, 0, 1>(a, stream);
+    return (P == 4) ? launch_t<4, DEG, 4, 0, 0, 1>(a, stream) : launch_t<4, DEG, 8, 0, 0, 1>(a, stream);
   }
   if (scatter == EQLB_SCATTER_SLOTS)
-    return (P == 4) ? launch_t<4, 3, 4, 0, 0>(a, stream) : launch_t<4, 3, 8, 0, 0>(a, stream);
-  return (P == 4) ? launch_t<4, 3, 4, 0, 1>(a, stream) : launch_t<4, 3, 8, 0, 1>(a, stream);
+    return (P == 4) ? launch_t<4, DEG, 4, 0, 0>(a, stream) : launch_t<4, DEG, 8, 0, 0>(a, stream);
+  return (P == 4) ? launch_t<4, DEG, 4, 0, 1>(a, stream) : launch_t<4, DEG, 8, 0, 1>(a, stream);
 }
 
+#if !EQLB_SE_TEMPLATES_ONLY
 int launch_se_patch(int k, int deg, int P, int solver, int scatter, const SeArgs& a,
                     hipStream_t stream, int mode)
 {
+  if (deg != k - 1)
+    return launch_se_patch_lowdeg(k, deg, P, solver, scatter, a, stream, mode);
   if (k == 4 && deg == 3)
-    return launch_k4(P, solver, scatter, a, stream, mode);
+    return launch_k4<3>(P, solver, scatter, a, stream, mode);
   if (mode != 0)
     return EQLB_ERR_UNSUPPORTED; // k <= 3: the EV patch problems run on the fused / tiled launches
   if (k == 1 && deg == 0)
@@ -2749,5 +2802,6 @@ int launch_se_patch(int k, int deg, int P, int solver, int scatter, const SeArgs
     return launch_kd<3, 2>(P, solver, scatter, a, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
+#endif
 
 } // namespace eqlb

@@ -313,6 +313,8 @@ struct BoundaryData
   eqlb_ev_t* ev = nullptr;
   std::vector<double> basis_C, basis_R;
   int se_degree_dg = -1;
+  int ev_degree_dg = -1;
+  std::vector<std::pair<std::string, int>> ev_options; // re-applied when the EV handle is rebuilt for another degree
 
   BoundaryData(std::vector<std::vector<std::shared_ptr<FluxBC>>>& list_bcs,
                std::vector<std::shared_ptr<Function>>& bflux, std::shared_ptr<FunctionSpace> V_, bool rt_custom,
@@ -452,14 +454,19 @@ struct BoundaryData
                                nullptr));
     return se;
   }
-  eqlb_ev_t* ev_handle()
+  eqlb_ev_t* ev_handle(int degree_dg)
   {
     if (custom)
       throw std::runtime_error("reconstruct_fluxes_minimisation: the boundary data belongs to the discontinuous "
                                "(semi-explicit) flux space");
-    if (ev)
+    if (ev && ev_degree_dg == degree_dg)
       return ev;
-    check(eqlb_ev_create(mesh->h, k, nrhs, &ev));
+    eqlb_ev_destroy(ev);
+    ev = nullptr;
+    check(eqlb_ev_create_dg(mesh->h, k, degree_dg, nrhs, &ev));
+    ev_degree_dg = degree_dg;
+    for (const auto& o : ev_options)
+      check(eqlb_ev_set_option(ev, o.first.c_str(), o.second));
     if (!V->cell_dofs.empty())
       check(eqlb_ev_set_dofmap(ev, V->cell_dofs.data(), V->ndofs_user));
     if (!basis_C.empty())
@@ -493,6 +500,7 @@ struct BoundaryData
     }
     eqlb_ev_destroy(ev); // rebuilt with the new basis on the next call
     ev = nullptr;
+    ev_options.clear();
   }
   void set_option(const std::string& key, int value)
   {
@@ -503,7 +511,10 @@ struct BoundaryData
       check(eqlb_se_set_option(se, key.c_str(), value));
     }
     else
-      check(eqlb_ev_set_option(ev_handle(), key.c_str(), value));
+    {
+      check(eqlb_ev_set_option(ev_handle(ev ? ev_degree_dg : k - 1), key.c_str(), value));
+      ev_options.emplace_back(key, value);
+    }
   }
 };
 
@@ -556,9 +567,6 @@ void semiexplt(std::vector<std::shared_ptr<Function>>& flux_hdiv, std::vector<st
     if (k < 2)
       throw std::runtime_error("Stress equilibration: RT_k with k>1 required!");
   }
-  if (degree_dg != k - 1)
-    throw std::runtime_error("Equilibration: projected data of degree < k-1 has to be embedded into DG_{k-1} first "
-                             "(dolfinx_eqlb_amd.lsolver.embed_dg; the FluxEqlbSE class does it)");
   eqlb_se_t* h = bd->se_handle(degree_dg, reconstruct_stress);
   std::vector<const double*> g(n), f(n);
   std::vector<double*> x(n);
@@ -598,16 +606,19 @@ void minimisation(const Form&, const Form&, const std::vector<std::shared_ptr<Fo
   }
   const int mem = memspace_of(flux_hdiv, gs, fs);
   const int k = bd->k;
+  // G_i, f_i in one DG_d, d <= k-1 (the kernels read DG_d directly)
+  const int degree_dg = gs[0]->V->degree;
   for (size_t i = 0; i < n; ++i)
   {
     const auto &Vh = flux_hdiv[i]->V, &Vg = gs[i]->V, &Vf = fs[i]->V;
     if (Vh != bd->V && !(Vh->family == "RT" && !Vh->discontinuous && Vh->degree == k && Vh->mesh == bd->mesh))
       throw std::runtime_error("Equilibration: flux_hdiv must live in the flux space of the boundary data");
-    if (Vg->family != "DG" || Vf->family != "DG" || Vg->bs != 2 || Vf->bs != 1 || Vg->degree != k - 1
-        || Vf->degree != k - 1 || Vg->mesh != bd->mesh || Vf->mesh != bd->mesh)
+    if (Vg->family != "DG" || Vf->family != "DG" || Vg->bs != 2 || Vf->bs != 1 || Vg->degree != degree_dg
+        || Vf->degree != degree_dg || degree_dg < 0 || degree_dg > k - 1 || Vg->mesh != bd->mesh
+        || Vf->mesh != bd->mesh)
       throw std::runtime_error("Equilibration: Input sizes does not match");
   }
-  eqlb_ev_t* h = bd->ev_handle();
+  eqlb_ev_t* h = bd->ev_handle(degree_dg);
   std::vector<const double*> g(n), f(n);
   std::vector<double*> x(n);
   for (size_t i = 0; i < n; ++i)

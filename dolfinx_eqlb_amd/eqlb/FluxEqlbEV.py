@@ -32,16 +32,20 @@ class FluxEqlbEV:
         self.list_rhs = [np.ascontiguousarray(r, dtype=np.float64).ravel().copy() for r in list_rhs]
         self.list_proj_flux = [np.ascontiguousarray(g, dtype=np.float64).ravel().copy()
                                for g in list_proj_flux]
-        nd = degree_flux * (degree_flux + 1) // 2
-        if any(r.size != nd * msh.ncells for r in self.list_rhs) or \
+        # data in DG_d, d <= k-1 (the same for all fluxes): read by the kernels as they are
+        nd = self.list_rhs[0].size // msh.ncells if self.list_rhs else 0
+        degree_dg = {1: 0, 3: 1, 6: 2, 10: 3}.get(nd)
+        if degree_dg is None or degree_dg > degree_flux - 1 or \
+                any(r.size != nd * msh.ncells for r in self.list_rhs) or \
                 any(g.size != 2 * nd * msh.ncells for g in self.list_proj_flux):
             raise RuntimeError("Equilibration: Input sizes does not match")
+        self.degree_dg = degree_dg
         c = _adapter.module()
         # V_flux: conforming RT_k (FluxEqlbEV.py:100)
         self.cell_dofs, self.ndofs = conforming_dofmap(msh, degree_flux)
         self.V_flux = _adapter.flux_space(msh, degree_flux, False)
-        V_g = _adapter.dg_space(msh, degree_flux - 1, 2)
-        V_f = _adapter.dg_space(msh, degree_flux - 1, 1)
+        V_g = _adapter.dg_space(msh, degree_dg, 2)
+        V_f = _adapter.dg_space(msh, degree_dg, 1)
         self.list_flux = np.zeros((self.n_fluxes, self.ndofs))
         self._f_flux = [_adapter.function(self.V_flux, self.list_flux[i]) for i in range(self.n_fluxes)]
         # the forms of FluxEqlbEV.py:113-134: a, l_pen carry no data, l_i depends on (G_i, f_i)

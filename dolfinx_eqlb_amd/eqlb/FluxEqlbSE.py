@@ -41,20 +41,14 @@ class FluxEqlbSE:
             raise RuntimeError("Equilibration: Input sizes does not match")
         if degree_dg > degree_flux - 1:  # se/reconstruction.hpp:363-373
             raise RuntimeError("Equilibration: Wrong polynomial degree of the projected RHS")
-        if degree_dg < degree_flux - 1:
-            # lower-degree data: embedded exactly into DG_{k-1}, the space the kernels work in
-            from ..lsolver import embed_dg
-            self.list_rhs = [embed_dg(r, msh.ncells, degree_dg, degree_flux - 1) for r in self.list_rhs]
-            self.list_proj_flux = [embed_dg(g, msh.ncells, degree_dg, degree_flux - 1, bs=2)
-                                   for g in self.list_proj_flux]
-            degree_dg = degree_flux - 1
+        # DG_d data of any d <= k-1 go to the kernels as they are
         self.degree_dg = degree_dg
         if equilibrate_stress:  # se/reconstruction.hpp:376-388
             if self.n_fluxes < 2:
                 raise RuntimeError("Stress equilibration: Specify all rows of stress tensor")
             if degree_flux < 2:
                 raise RuntimeError("Stress equilibration: RT_k with k>1 required!")
-        # function spaces (FluxEqlbSE.py:94-105): discontinuous hierarchic RT_k, DG_{k-1} (x 2)
+        # function spaces (FluxEqlbSE.py:94-105): discontinuous hierarchic RT_k, DG_d (x 2) of the data
         self.V_flux = _adapter.flux_space(msh, degree_flux, True)
         self.V_flux_dg = _adapter.dg_space(msh, degree_dg, 2)
         self.V_rhs = _adapter.dg_space(msh, degree_dg, 1)
@@ -97,7 +91,7 @@ class FluxEqlbSE:
                                            self.equilibrate_stresses)
 
     def get_reconstructed_fluxes(self, subproblem: int):
-        """(corrector in discontinuous hierarchic RT_k, projected flux in DG_{k-1}^2): the
+        """(corrector in discontinuous hierarchic RT_k, the caller's projected flux in DG_d^2): the
         reconstructed flux is their sum (FluxEqlbSE.py:176-186)."""
         return self.list_flux[subproblem], self.list_proj_flux[subproblem]
 

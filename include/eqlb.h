@@ -28,7 +28,8 @@ extern "C" {
 #define EQLB_OK 0
 #define EQLB_ERR_INVALID_ARGUMENT (-1) /* size / degree mismatch, se/reconstruction.hpp:358-388 */
 #define EQLB_ERR_PATCH_TOO_SMALL (-2)  /* patch with one cell, se/Patch.cpp:353-359 */
-#define EQLB_ERR_UNSUPPORTED (-3)      /* configuration outside this build */
+#define EQLB_ERR_UNSUPPORTED (-3)      /* configuration outside this build: k > 4, or an option / path the handle does
+                                          not offer */
 #define EQLB_ERR_DEVICE (-4)           /* HIP runtime failure / no device */
 #define EQLB_ERR_PATCH_TOO_LARGE (-5)  /* patch with more than 63 cells (one wavefront per patch) */
 #define EQLB_ERR_SINGULAR (-6)         /* patch system not positive definite (incompatible data) */
@@ -88,8 +89,13 @@ void eqlb_mesh_destroy(eqlb_mesh_t* mesh);
 
 /*
  * Semi-explicit equilibrator for RT_k fluxes with projected flux / RHS in DG_{degree_dg}
- * (degree_dg <= k-1; the reference requires deg(flux_dg) == deg(rhs_dg) <= k-1,
- * se/reconstruction.hpp:363-373) and nrhs simultaneously equilibrated fluxes.
+ * (0 <= degree_dg <= k-1, else EQLB_ERR_INVALID_ARGUMENT "Wrong polynomial degree"; the reference requires
+ * deg(flux_dg) == deg(rhs_dg) <= k-1, se/reconstruction.hpp:363-373) and nrhs simultaneously equilibrated fluxes.
+ * Every pair 1 <= k <= 4, 0 <= degree_dg <= k-1 runs on the device on every path (SE, stress, EV, multi-RHS, node
+ * masks, host / device memory): the kernels read the data in DG_{degree_dg} directly (a P_{k-1} primal solution
+ * equilibrated into RT_k gives degree_dg = k-2), flux_dg / rhs_dg have (degree_dg+1)(degree_dg+2)/2 values per cell
+ * (x 2 for flux_dg).  RT_2 stress with DG_0 data runs the slot path and the weak-symmetry kernel (the route of stress
+ * flux BCs) instead of the fused tiled stress launch, which reads DG_1 data.
  * Replaces the per-call setup of se::reconstruction<T,k> (se/reconstruction.hpp:62-163:
  * KernelData tabulation, kernel generation, Patch/PatchData allocation) - done once here and
  * cached on the device.  reconstruct_stress / korn are the flags of
@@ -267,7 +273,9 @@ double eqlb_se_last_kernel_ms(const eqlb_se_t* handle, int32_t which);
  *                              demo/poisson/demo_error_estimation.py:93-100 for the SE flux)
  *   facet_jump [nrhs][nfacets] max_j | j-th moment of [(sigma_eq + G).n] | on interior facets, 0 on
  *                              boundary facets (H(div) conformity, check_eqlb_conditions.py:294-359)
- * Any output may be NULL.  Arrays in the layouts of eqlb_se_equilibrate; memspace as there. */
+ * Any output may be NULL.  Arrays in the layouts of eqlb_se_equilibrate; memspace as there.
+ * flux_dg / rhs_dg in DG_{k-1} (here and in eqlb_ev_estimate, eqlb_oscillation): data of a lower degree are
+ * embedded first (dolfinx_eqlb_amd.lsolver.embed_dg; exact, DG_d is a subspace of DG_{k-1}). */
 int eqlb_se_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux_hdiv,
                      const double* flux_dg, const double* rhs_dg, double* cell_div2,
                      double* cell_sig2, double* facet_jump, int32_t memspace, void* stream);
@@ -412,7 +420,10 @@ int eqlb_se_tiling_blocks(const eqlb_se_t* handle, int64_t* out, int32_t n);
  * ------------------------------------------------------------------------------------------- */
 typedef struct eqlb_ev eqlb_ev_t;
 
+/* eqlb_ev_create: G, f in DG_{k-1}; eqlb_ev_create_dg: in DG_{degree_dg}, 0 <= degree_dg <= k-1 (as eqlb_se_create;
+ * the same minimisation problem as with the data embedded into DG_{k-1}) */
 int eqlb_ev_create(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, eqlb_ev_t** handle);
+int eqlb_ev_create_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, eqlb_ev_t** handle);
 void eqlb_ev_destroy(eqlb_ev_t* handle);
 
 /* "output": 0 conforming DOFs (default), 1 broken hierarchic RT_k layout [ncells*k(k+2)] as

@@ -11,8 +11,13 @@ mkdir -p "$T/dolfinx_eqlb_amd/csrc" "$T/include" build_exp
 for f in $(git ls-tree --name-only "$REV" dolfinx_eqlb_amd/csrc/ include/); do
   git show "$REV:$f" > "$T/$f"
 done
+# tables that revision's Makefile generates instead of keeping them in git (tools/gen_tables.py --build)
+if [ -f "$T/dolfinx_eqlb_amd/csrc/eqlb_se_kernels_lowdeg_k4.hip" ]; then
+  python3 tools/gen_tables.py --build "$T/dolfinx_eqlb_amd/csrc/eqlb_tables_build_gen.h"
+fi
 OBJS=""
-for f in eqlb_api eqlb_patch_builder eqlb_se_kernels eqlb_projection eqlb_korn eqlb_se_weaksym eqlb_ev eqlb_estimate; do
+# every translation unit of that revision (the object list of its Makefile)
+for f in $(git ls-tree --name-only "$REV" dolfinx_eqlb_amd/csrc/ | grep '\.hip$' | xargs -n1 basename | sed 's/\.hip$//'); do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -c "$T/dolfinx_eqlb_amd/csrc/$f.hip" -o "$T/$f.o" &
   OBJS="$OBJS $T/$f.o"
 done

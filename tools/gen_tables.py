@@ -18,7 +18,8 @@ Basix nor quadrature loops:
                        w.r.t. 1-s (reversed facet), cf. se/KernelData.cpp:49-64
   NREF[3][2], NOUT[3]  reference facet normals of the RT functionals and their outwardness
 
-Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h)
+Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
+      go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
 """
 
 import os
@@ -33,6 +34,9 @@ from dolfinx_eqlb_amd.elmtlib import e_raviart_thomas as ert  # noqa: E402
 from dolfinx_eqlb_amd.elmtlib.lagrange import Lagrange  # noqa: E402
 
 PAIRS = [(1, 0), (2, 1), (3, 2), (4, 3), (2, 0), (3, 1), (3, 0)]  # (k, degree of DG data)
+# RT_4 with data of degree < 3: 0.4 MB of literals, generated at build time (csrc/Makefile, `--build`) into
+# eqlb_tables_build_gen.h, which git ignores
+PAIRS_BUILD = [(4, 2), (4, 1), (4, 0)]
 NCOMBO = 12  # (fm, fp, rev) combinations with fm != fp
 
 
@@ -264,12 +268,8 @@ def tables_float(k, deg):
     return out
 
 
-def emit(path):
-    lines = ["// GENERATED by tools/gen_tables.py - do not edit.",
-             "// Exact reference-cell tensors of the hierarchic RT_k / DG_deg pair (see the generator).",
-             "#pragma once", "", "namespace eqlb_tables {", "",
-             "template <int K, int DEG> struct Ref;", ""]
-    for (k, deg) in PAIRS:
+def _emit_refs(lines, pairs):
+    for (k, deg) in pairs:
         t = tables_exact(k, deg)
         nrt, nd, nq = t["nrt"], t["nd"], t["nq"]
         lines.append(f"template <> struct Ref<{k}, {deg}> {{")
@@ -309,6 +309,14 @@ def emit(path):
         lines.append(f"  static constexpr int MONO_Y[{nq}] = {{{', '.join(str(m) for _, m in t['monos'])}}};")
         lines.append("};")
         lines.append("")
+
+
+def emit(path):
+    lines = ["// GENERATED by tools/gen_tables.py - do not edit.",
+             "// Exact reference-cell tensors of the hierarchic RT_k / DG_deg pair (see the generator).",
+             "#pragma once", "", "namespace eqlb_tables {", "",
+             "template <int K, int DEG> struct Ref;", ""]
+    _emit_refs(lines, PAIRS)
     # Lagrange P_d (Basix numbering, equispaced): monomial coefficients and inverse mass matrix
     lines.append("// Lagrange P_d on the reference triangle: LAG_COEF[i][m] = coefficient of monomial m")
     lines.append("// (order: deg 0; x, y; x^2, xy, y^2; ...) of basis function i; LAG_MINV = inverse of int psi_i psi_j")
@@ -336,8 +344,24 @@ def emit(path):
         fh.write("\n".join(lines) + "\n")
 
 
+def emit_build(path):
+    """The pairs of PAIRS_BUILD, behind the committed header (written by the build)."""
+    lines = ["// GENERATED by tools/gen_tables.py --build at build time - do not edit, not in git.",
+             "#pragma once", "", '#include "eqlb_tables_gen.h"', "", "namespace eqlb_tables {", ""]
+    _emit_refs(lines, PAIRS_BUILD)
+    lines.append("} // namespace eqlb_tables")
+    tmp = path + ".tmp"
+    with open(tmp, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    os.replace(tmp, path)  # a make interrupted mid-write leaves no truncated header behind
+
+
 if __name__ == "__main__":
     here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(here, "..", "dolfinx_eqlb_amd", "csrc", "eqlb_tables_gen.h")
-    emit(os.path.normpath(out))
-    print("wrote", os.path.normpath(out))
+    if len(sys.argv) == 3 and sys.argv[1] == "--build":
+        emit_build(sys.argv[2])
+        print("wrote", sys.argv[2])
+    else:
+        out = os.path.join(here, "..", "dolfinx_eqlb_amd", "csrc", "eqlb_tables_gen.h")
+        emit(os.path.normpath(out))
+        print("wrote", os.path.normpath(out))
