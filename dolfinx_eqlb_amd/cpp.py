@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_halo_exchange", "eqlb_halo_reduce", "eqlb_rccl_get_unique_id", "eqlb_rccl_comm_create",
     "eqlb_rccl_comm_destroy", "eqlb_halo_create", "eqlb_halo_destroy", "eqlb_halo_bytes", "eqlb_halo_reduce_plan",
     "eqlb_se_tiling_blocks", "eqlb_ev_tiling_blocks", "eqlb_ev_create_dg",
+    "eqlb_se_estimate_dg", "eqlb_ev_estimate_dg", "eqlb_oscillation_dg", "eqlb_boundary_residual",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -421,12 +422,25 @@ def project_dg(dmesh: DeviceMesh, degree: int, qpoints, qweights, qvalues, bs: i
     return out
 
 
-def estimate(dmesh: DeviceMesh, k: int, flux_hdiv, flux_dg, rhs_dg, conforming_flux=False):
+def _degree_dg(k: int, degree_dg):
+    """Degree of the projected data of an estimator call (None: k-1, the entry points without _dg)."""
+    if k < 1 or k > 4:
+        raise RuntimeError(f"Equilibration: flux degree k = {k} outside 1 ... 4")
+    if degree_dg is None:
+        return k - 1
+    if degree_dg < 0 or degree_dg > k - 1:
+        raise RuntimeError("Equilibration: Wrong polynomial degree of the projected RHS")
+    return int(degree_dg)
+
+
+def estimate(dmesh: DeviceMesh, k: int, flux_hdiv, flux_dg, rhs_dg, conforming_flux=False, degree_dg=None):
     """eqlb_se_estimate (eqlb_ev_estimate with conforming_flux=True: the flux is an EV result in
     the broken layout) on host arrays [nrhs, ...]: returns (cell_div2 [nrhs, ncells],
-    cell_sig2 [nrhs, ncells], facet_jump [nrhs, nfacets])."""
+    cell_sig2 [nrhs, ncells], facet_jump [nrhs, nfacets]).  degree_dg: flux_dg / rhs_dg are DG_{degree_dg}
+    data, 0 <= degree_dg <= k-1 (eqlb_se_estimate_dg / eqlb_ev_estimate_dg); None: DG_{k-1}."""
     m = dmesh.mesh
-    nrt, nd = k * (k + 2), k * (k + 1) // 2
+    deg = _degree_dg(k, degree_dg)
+    nrt, nd = k * (k + 2), (deg + 1) * (deg + 2) // 2
     x = np.ascontiguousarray(flux_hdiv, dtype=np.float64).reshape(-1, m.ncells * nrt)
     nrhs = x.shape[0]
     g = np.ascontiguousarray(flux_dg, dtype=np.float64).reshape(nrhs, -1)
@@ -436,10 +450,27 @@ def estimate(dmesh: DeviceMesh, k: int, flux_hdiv, flux_dg, rhs_dg, conforming_f
     div2 = np.zeros((nrhs, m.ncells))
     sig2 = np.zeros((nrhs, m.ncells))
     jump = np.zeros((nrhs, m.nfacets))
-    fn = lib().eqlb_ev_estimate if conforming_flux else lib().eqlb_se_estimate
-    _check(fn(dmesh._h, C.c_int32(k), C.c_int32(nrhs), _hp(x), _hp(g), _hp(f),
-              _hp(div2), _hp(sig2), _hp(jump), C.c_int32(MEM_HOST), None))
+    estimate_raw(dmesh, k, nrhs, _hp(x), _hp(g), _hp(f), _hp(div2), _hp(sig2), _hp(jump), conforming_flux,
+                 degree_dg, MEM_HOST)
     return div2, sig2, jump
+
+
+def _vp(p):
+    return p if p is None or isinstance(p, C.c_void_p) else C.c_void_p(p)
+
+
+def estimate_raw(dmesh: DeviceMesh, k: int, nrhs: int, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
+                 conforming_flux=False, degree_dg=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_se_estimate[_dg] / eqlb_ev_estimate[_dg] on raw pointers (ints or None for an output that is not
+    wanted) in `memspace`, ordered on `stream`; device arrays stay where they are."""
+    ptrs = [_vp(p) for p in (flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump)]
+    tail = (C.c_int32(memspace), C.c_void_p(stream))
+    if degree_dg is None:
+        fn = lib().eqlb_ev_estimate if conforming_flux else lib().eqlb_se_estimate
+        _check(fn(dmesh._h, C.c_int32(k), C.c_int32(nrhs), *ptrs, *tail))
+    else:
+        fn = lib().eqlb_ev_estimate_dg if conforming_flux else lib().eqlb_se_estimate_dg
+        _check(fn(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), *ptrs, *tail))
 
 
 def estimate_stress(dmesh: DeviceMesh, k: int, flux_hdiv, korn=None, pi_1: float = 1.0):
@@ -460,10 +491,12 @@ def estimate_stress(dmesh: DeviceMesh, k: int, flux_hdiv, korn=None, pi_1: float
     return energy, wsym, asym
 
 
-def oscillation(dmesh: DeviceMesh, k: int, flux, flux_dg, qpoints, qweights, fvalues, korn=None):
-    """eqlb_oscillation on host arrays: flux [nrhs, ncells*k(k+2)], flux_dg [nrhs, ncells*k(k+1)] or None
-    (conforming flux in the broken layout), fvalues [nrhs, ncells, nq].  Returns [nrhs, ncells]."""
+def oscillation(dmesh: DeviceMesh, k: int, flux, flux_dg, qpoints, qweights, fvalues, korn=None, degree_dg=None):
+    """eqlb_oscillation on host arrays: flux [nrhs, ncells*k(k+2)], flux_dg [nrhs, ncells*nd*2] or None
+    (conforming flux in the broken layout), fvalues [nrhs, ncells, nq].  Returns [nrhs, ncells].
+    degree_dg: flux_dg is DG_{degree_dg} data (eqlb_oscillation_dg); None: DG_{k-1}."""
     m = dmesh.mesh
+    deg = _degree_dg(k, degree_dg)
     x = np.ascontiguousarray(flux, dtype=np.float64).reshape(-1, m.ncells * k * (k + 2))
     nrhs = x.shape[0]
     g = None if flux_dg is None else np.ascontiguousarray(flux_dg, dtype=np.float64).reshape(nrhs, -1)
@@ -471,14 +504,56 @@ def oscillation(dmesh: DeviceMesh, k: int, flux, flux_dg, qpoints, qweights, fva
     qw = np.ascontiguousarray(qweights, dtype=np.float64)
     nq = qw.size
     fv = np.ascontiguousarray(fvalues, dtype=np.float64)
-    if fv.size != nrhs * m.ncells * nq or (g is not None and g.shape[1] != m.ncells * k * (k + 1)):
+    if fv.size != nrhs * m.ncells * nq or (g is not None and g.shape[1] != m.ncells * (deg + 1) * (deg + 2)):
         raise RuntimeError("Equilibration: Input sizes does not match")
     kc = None if korn is None else np.ascontiguousarray(korn, dtype=np.float64)
     out = np.zeros((nrhs, m.ncells))
-    _check(lib().eqlb_oscillation(dmesh._h, C.c_int32(k), C.c_int32(nrhs), _hp(x),
-                                  _hp(g) if g is not None else None, C.c_int32(nq), _hp(qp), _hp(qw), _hp(fv),
-                                  _hp(kc) if kc is not None else None, _hp(out), C.c_int32(MEM_HOST), None))
+    oscillation_raw(dmesh, k, nrhs, _hp(x), _hp(g) if g is not None else None, qp, qw, _hp(fv),
+                    _hp(kc) if kc is not None else None, _hp(out), degree_dg, MEM_HOST)
     return out
+
+
+def oscillation_raw(dmesh: DeviceMesh, k: int, nrhs: int, flux, flux_dg, qpoints, qweights, fvalues, korn, out,
+                    degree_dg=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_oscillation[_dg] on raw pointers in `memspace`, ordered on `stream`; the rule (qpoints [nq, 2],
+    qweights [nq]) is given as host arrays in either case."""
+    qp = np.ascontiguousarray(qpoints, dtype=np.float64)
+    qw = np.ascontiguousarray(qweights, dtype=np.float64)
+    head = (dmesh._h, C.c_int32(k)) + (() if degree_dg is None else (C.c_int32(degree_dg),))
+    fn = lib().eqlb_oscillation if degree_dg is None else lib().eqlb_oscillation_dg
+    _check(fn(*head, C.c_int32(nrhs), _vp(flux), _vp(flux_dg), C.c_int32(qw.size), _hp(qp), _hp(qw), _vp(fvalues),
+              _vp(korn), _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def boundary_residual(dmesh: DeviceMesh, k: int, flux, flux_dg, facets, boundary_values=None, degree_dg=None):
+    """eqlb_boundary_residual on host arrays: per listed flux-BC facet the largest deviation of the facet DOFs of
+    flux + flux_dg from the boundary DOFs (check_eqlb_conditions.boundary_flux_residual per facet).
+    flux [nrhs, ncells*k(k+2)], flux_dg [nrhs, ncells*nd*2] in DG_{degree_dg} (None: k-1) or None (conforming
+    flux in the broken layout), boundary_values [nrhs, ncells*k(k+2)] or None (homogeneous condition).
+    Returns [nrhs, len(facets)]."""
+    m = dmesh.mesh
+    deg = _degree_dg(k, degree_dg)
+    x = np.ascontiguousarray(flux, dtype=np.float64).reshape(-1, m.ncells * k * (k + 2))
+    nrhs = x.shape[0]
+    g = None if flux_dg is None else np.ascontiguousarray(flux_dg, dtype=np.float64).reshape(nrhs, -1)
+    bv = None if boundary_values is None else np.ascontiguousarray(boundary_values, dtype=np.float64)
+    if (g is not None and g.shape[1] != m.ncells * (deg + 1) * (deg + 2)) or (bv is not None and bv.size != x.size):
+        raise RuntimeError("Equilibration: Input sizes does not match")
+    fl = np.ascontiguousarray(facets, dtype=np.int32).reshape(-1)
+    if fl.size and (fl.min() < 0 or fl.max() >= m.nfacets):
+        raise RuntimeError("Equilibration: boundary facet outside the mesh")
+    out = np.zeros((nrhs, fl.size))
+    boundary_residual_raw(dmesh, k, deg, nrhs, _hp(x), _hp(g) if g is not None else None, fl.size, _hp(fl),
+                          _hp(bv) if bv is not None else None, _hp(out), MEM_HOST)
+    return out
+
+
+def boundary_residual_raw(dmesh: DeviceMesh, k: int, degree_dg: int, nrhs: int, flux, flux_dg, nfacets_bc: int,
+                          facets, boundary_values, out, memspace=MEM_DEVICE, stream=0):
+    """eqlb_boundary_residual on raw pointers in `memspace` (facets: int32), ordered on `stream`."""
+    _check(lib().eqlb_boundary_residual(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), _vp(flux),
+                                        _vp(flux_dg), C.c_int32(nfacets_bc), _vp(facets), _vp(boundary_values),
+                                        _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
 
 
 def halo_pack(x_ptr, cells_ptr, buf_ptr, nrhs, nlist, nrt, ncells, clear=True, stream=0):

@@ -2269,22 +2269,33 @@ int eqlb_get_reference_table(int32_t k, int32_t degree_dg, const char* name, dou
   return (int)len;
 }
 
-static int estimate_impl(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux_hdiv,
+// degree of the projected data of an estimator call: 0 ... k - 1 (the pairs the tables exist for)
+static int check_degree_dg(const char* who, int32_t k, int32_t degree_dg)
+{
+  if (degree_dg < 0 || degree_dg > k - 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: Wrong polynomial degree of the projected RHS (degree_dg = %d, k = %d)",
+                who, (int)degree_dg, (int)k);
+  return EQLB_OK;
+}
+
+static int estimate_impl(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_hdiv,
                          const double* flux_dg, const double* rhs_dg, double* cell_div2,
                          double* cell_sig2, double* facet_jump, int32_t memspace, void* stream_,
                          double alpha, double beta)
 {
   if (!mesh || !flux_hdiv || !flux_dg || !rhs_dg || nrhs < 1 || k < 1 || k > 4)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate: invalid argument");
+  if (check_degree_dg("eqlb_se_estimate", k, degree_dg))
+    return EQLB_ERR_INVALID_ARGUMENT;
   const eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const int nrt = k * (k + 2), nd = k * (k + 1) / 2;
+  const int nrt = k * (k + 2), nd = (degree_dg + 1) * (degree_dg + 2) / 2;
   const size_t n_x = (size_t)nrhs * m.ncells * nrt, n_g = (size_t)nrhs * m.ncells * nd * 2,
                n_f = (size_t)nrhs * m.ncells * nd;
   const size_t n_c = (size_t)nrhs * m.ncells, n_e = (size_t)nrhs * m.nfacets;
   if (memspace == EQLB_MEM_DEVICE)
   {
-    const int st = eqlb::launch_estimate(m, k, nrhs, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2,
+    const int st = eqlb::launch_estimate(m, k, degree_dg, nrhs, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2,
                                          facet_jump, alpha, beta, stream);
     return st ? fail(st, "eqlb_se_estimate: kernel launch failed") : EQLB_OK;
   }
@@ -2298,7 +2309,8 @@ static int estimate_impl(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const doubl
     st |= upload<double>(&d_s, nullptr, n_c);
   if (facet_jump)
     st |= upload<double>(&d_j, nullptr, n_e);
-  int rc = st ? EQLB_ERR_DEVICE : eqlb::launch_estimate(m, k, nrhs, d_x, d_g, d_f, d_d, d_s, d_j, alpha, beta, stream);
+  int rc = st ? EQLB_ERR_DEVICE : eqlb::launch_estimate(m, k, degree_dg, nrhs, d_x, d_g, d_f, d_d, d_s, d_j, alpha, beta,
+                                                        stream);
   hipError_t e = hipSuccess;
   if (!rc && cell_div2)
     e = hipMemcpy(cell_div2, d_d, n_c * sizeof(double), hipMemcpyDeviceToHost);
@@ -2321,7 +2333,15 @@ int eqlb_se_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* f
                      const double* flux_dg, const double* rhs_dg, double* cell_div2,
                      double* cell_sig2, double* facet_jump, int32_t memspace, void* stream)
 {
-  return estimate_impl(mesh, k, nrhs, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
+  return estimate_impl(mesh, k, k - 1, nrhs, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
+                       memspace, stream, 0.0, 1.0);
+}
+
+int eqlb_se_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_hdiv,
+                        const double* flux_dg, const double* rhs_dg, double* cell_div2, double* cell_sig2,
+                        double* facet_jump, int32_t memspace, void* stream)
+{
+  return estimate_impl(mesh, k, degree_dg, nrhs, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
                        memspace, stream, 0.0, 1.0);
 }
 
@@ -2329,7 +2349,15 @@ int eqlb_ev_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* f
                      const double* flux_dg, const double* rhs_dg, double* cell_div2,
                      double* cell_sig2, double* facet_jump, int32_t memspace, void* stream)
 {
-  return estimate_impl(mesh, k, nrhs, flux_broken, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
+  return estimate_impl(mesh, k, k - 1, nrhs, flux_broken, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
+                       memspace, stream, -1.0, 0.0);
+}
+
+int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_broken,
+                        const double* flux_dg, const double* rhs_dg, double* cell_div2, double* cell_sig2,
+                        double* facet_jump, int32_t memspace, void* stream)
+{
+  return estimate_impl(mesh, k, degree_dg, nrhs, flux_broken, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
                        memspace, stream, -1.0, 0.0);
 }
 
@@ -2423,19 +2451,31 @@ int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdi
 
 int eqlb_oscillation(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux, const double* flux_dg,
                      int32_t nq, const double* qpoints, const double* qweights, const double* fvalues,
-                     const double* korn, double* out, int32_t memspace, void* stream_)
+                     const double* korn, double* out, int32_t memspace, void* stream)
+{
+  return eqlb_oscillation_dg(mesh, k, k - 1, nrhs, flux, flux_dg, nq, qpoints, qweights, fvalues, korn, out,
+                             memspace, stream);
+}
+
+int eqlb_oscillation_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux,
+                        const double* flux_dg, int32_t nq, const double* qpoints, const double* qweights,
+                        const double* fvalues, const double* korn, double* out, int32_t memspace, void* stream_)
 {
   if (!mesh || !flux || !qpoints || !qweights || !fvalues || !out || nrhs < 1 || k < 1 || k > 4 || nq < 1
       || nq > 128)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_oscillation: invalid argument");
   if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_oscillation: unknown memory space");
+  if (check_degree_dg("eqlb_oscillation", k, degree_dg))
+    return EQLB_ERR_INVALID_ARGUMENT;
   const eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const size_t nx = (size_t)nrhs * m.ncells * k * (k + 2), ng = (size_t)nrhs * m.ncells * k * (k + 1);
+  const size_t nx = (size_t)nrhs * m.ncells * k * (k + 2),
+               ng = (size_t)nrhs * m.ncells * (degree_dg + 1) * (degree_dg + 2);
   int rc;
   if (memspace == EQLB_MEM_DEVICE)
-    rc = eqlb::launch_oscillation(m, k, nrhs, flux, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
+    rc = eqlb::launch_oscillation(m, k, degree_dg, nrhs, flux, flux_dg, nq, qpoints, qweights, fvalues, korn, out,
+                                  stream);
   else
   {
     Staging s;
@@ -2446,11 +2486,55 @@ int eqlb_oscillation(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* f
     double* d_o = s.out(out, (size_t)nrhs * m.ncells);
     if (s.bad)
       return fail(EQLB_ERR_DEVICE, "eqlb_oscillation: device allocation failed");
-    rc = eqlb::launch_oscillation(m, k, nrhs, d_x, d_g, nq, qpoints, qweights, d_f, d_k, d_o, stream);
+    rc = eqlb::launch_oscillation(m, k, degree_dg, nrhs, d_x, d_g, nq, qpoints, qweights, d_f, d_k, d_o, stream);
     if (!rc && !s.fetch())
       rc = EQLB_ERR_DEVICE;
   }
   return rc ? fail(rc, "eqlb_oscillation: device error") : EQLB_OK;
+}
+
+int eqlb_boundary_residual(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux,
+                           const double* flux_dg, int32_t nfacets_bc, const int32_t* facets,
+                           const double* boundary_values, double* out, int32_t memspace, void* stream_)
+{
+  if (!mesh || !flux || nrhs < 1 || k < 1 || k > 4 || nfacets_bc < 0 || (nfacets_bc > 0 && (!facets || !out)))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_boundary_residual: invalid argument");
+  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_boundary_residual: unknown memory space");
+  if (check_degree_dg("eqlb_boundary_residual", k, degree_dg))
+    return EQLB_ERR_INVALID_ARGUMENT;
+  const eqlb::DeviceMesh& m = mesh->m;
+  if (memspace == EQLB_MEM_HOST)
+    for (int32_t i = 0; i < nfacets_bc; ++i)
+      if (facets[i] < 0 || facets[i] >= m.nfacets)
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_boundary_residual: facets[%d] = %d is no facet of the mesh",
+                    (int)i, (int)facets[i]);
+  if (nfacets_bc == 0)
+    return EQLB_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const size_t nx = (size_t)nrhs * m.ncells * k * (k + 2),
+               ng = (size_t)nrhs * m.ncells * (degree_dg + 1) * (degree_dg + 2);
+  int rc;
+  if (memspace == EQLB_MEM_DEVICE)
+    rc = eqlb::launch_boundary_residual(m, k, degree_dg, nrhs, flux, flux_dg, nfacets_bc, facets, boundary_values,
+                                        out, stream);
+  else
+  {
+    Staging s;
+    const double* d_x = s.in(flux, nx);
+    const double* d_g = s.in(flux_dg, ng);
+    const double* d_b = s.in(boundary_values, nx);
+    double* d_o = s.out(out, (size_t)nrhs * nfacets_bc);
+    int32_t* d_l = nullptr;
+    if (upload(&d_l, facets, (size_t)nfacets_bc))
+      s.bad = true;
+    rc = s.bad ? EQLB_ERR_DEVICE
+               : eqlb::launch_boundary_residual(m, k, degree_dg, nrhs, d_x, d_g, nfacets_bc, d_l, d_b, d_o, stream);
+    if (!rc && !s.fetch())
+      rc = EQLB_ERR_DEVICE;
+    dfree(d_l);
+  }
+  return rc ? fail(rc, "eqlb_boundary_residual: device error") : EQLB_OK;
 }
 
 int eqlb_halo_pack(int32_t nrhs, int32_t nlist, int32_t nrt, int64_t ncells, const int64_t* cells,

@@ -8,18 +8,28 @@
 //   || Pi f - div(sigma_eq + G) ||^2_T = m^T GMI m / |detJ|,   || sigma_eq ||^2_T = c^T (sum_x g_x S_x) c,
 // and the normal-flux jump of sigma_eq + G on an interior facet from the outward moments of both
 // cells (reversal matrix B when their facet parameters run against each other).
+//
+// The data G, f come in DG_d, 0 <= d <= k - 1 (the reference accepts any such degree, se/reconstruction.hpp:363-373):
+// every kernel below is a template of (K, DEG) that contracts them with the tensors HG, DM, F0, MRD, MPS of the pair,
+// so nothing is embedded into DG_{k-1}.  The DEG = k - 1 instances live in this translation unit, the ones for
+// d < k - 1 in eqlb_estimate_lowdeg.hip / eqlb_estimate_lowdeg_k4.hip.
 #include "eqlb_device_common.h"
 #include <cmath>
 #include <vector>
 #include "eqlb_tables_gen.h"
 
+// EQLB_EST_TEMPLATES_ONLY: the templates of this file without its non-template definitions, for the translation
+// units of the instances at lower data degrees
+#ifndef EQLB_EST_TEMPLATES_ONLY
+#define EQLB_EST_TEMPLATES_ONLY 0
+#endif
+
 namespace eqlb
 {
 
-template <int K>
+template <int K, int DEG = K - 1>
 struct EstTables
 {
-  static constexpr int DEG = K - 1;
   using R = eqlb_tables::Ref<K, DEG>;
   static constexpr int NRT = R::NRT, ND = R::ND, NQ = R::NQ;
   static constexpr int OFF_S = 0, OFF_HG = OFF_S + R::S_SIZE, OFF_DM = OFF_HG + R::HG_SIZE,
@@ -40,14 +50,14 @@ struct EstTables
 };
 
 // one thread per cell: divergence residual and flux norm
-template <int K>
+template <int K, int DEG>
 __global__ void __launch_bounds__(256)
 k_estimate_cells(int32_t ncells, const double* __restrict__ tab, const double* __restrict__ cellJ,
                  const double* __restrict__ x_eq, const double* __restrict__ flux_dg,
                  const double* __restrict__ rhs_dg, double* __restrict__ div2, double* __restrict__ sig2,
                  const double alpha, const double beta)
 {
-  using E = EstTables<K>;
+  using E = EstTables<K, DEG>;
   constexpr int NRT = E::NRT, ND = E::ND, NQ = E::NQ;
   extern __shared__ double st[];
   for (int i = threadIdx.x; i < E::TOTAL; i += 256)
@@ -81,10 +91,20 @@ k_estimate_cells(int32_t ncells, const double* __restrict__ tab, const double* _
     {
       const double gx = G[2 * i], gy = G[2 * i + 1];
       const double h0 = beta * (a00 * gx + a01 * gy), h1 = beta * (a10 * gx + a11 * gy), fd = detJ * f[i];
+      if constexpr (DEG == 0 && K >= 2)
+      {
+        // P0 data: div G = 0, the rows of DM are zero (RT_1 keeps the generic contraction)
 #pragma unroll
-      for (int q = 0; q < NQ; ++q)
-        m[q] += fd * st[E::OFF_HG + i * NQ + q] - h0 * st[E::OFF_DM + (i * 2 + 0) * NQ + q]
-                - h1 * st[E::OFF_DM + (i * 2 + 1) * NQ + q];
+        for (int q = 0; q < NQ; ++q)
+          m[q] += fd * st[E::OFF_HG + i * NQ + q];
+      }
+      else
+      {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+          m[q] += fd * st[E::OFF_HG + i * NQ + q] - h0 * st[E::OFF_DM + (i * 2 + 0) * NQ + q]
+                  - h1 * st[E::OFF_DM + (i * 2 + 1) * NQ + q];
+      }
     }
     double s = 0.0;
 #pragma unroll
@@ -103,15 +123,35 @@ k_estimate_cells(int32_t ncells, const double* __restrict__ tab, const double* _
     const double g0 = (J00 * J00 + J10 * J10) * ia, g1 = (J00 * J01 + J10 * J11) * ia,
                  g2 = (J01 * J01 + J11 * J11) * ia;
     double s = 0.0;
-    for (int i = 0; i < NRT; ++i)
+    // The loops over the rows of S (and of MRD below) are unrolled in full at d < k - 1, so that cf stays in
+    // registers.  The d = k - 1 instances keep the loop the compiler makes of it (RT_4 / DG_3 indexes cf in 208 B
+    // of scratch): their code is left as it was, hence the two copies.
+    if constexpr (DEG == K - 1)
     {
-      double r = 0.0;
+      for (int i = 0; i < NRT; ++i)
+      {
+        double r = 0.0;
 #pragma unroll
-      for (int j = 0; j < NRT; ++j)
-        r += (g0 * st[E::OFF_S + i * NRT + j] + g1 * st[E::OFF_S + (NRT + i) * NRT + j]
-              + g2 * st[E::OFF_S + (2 * NRT + i) * NRT + j])
-             * cf[j];
-      s += cf[i] * r;
+        for (int j = 0; j < NRT; ++j)
+          r += (g0 * st[E::OFF_S + i * NRT + j] + g1 * st[E::OFF_S + (NRT + i) * NRT + j]
+                + g2 * st[E::OFF_S + (2 * NRT + i) * NRT + j])
+               * cf[j];
+        s += cf[i] * r;
+      }
+    }
+    else
+    {
+#pragma unroll
+      for (int i = 0; i < NRT; ++i)
+      {
+        double r = 0.0;
+#pragma unroll
+        for (int j = 0; j < NRT; ++j)
+          r += (g0 * st[E::OFF_S + i * NRT + j] + g1 * st[E::OFF_S + (NRT + i) * NRT + j]
+                + g2 * st[E::OFF_S + (2 * NRT + i) * NRT + j])
+               * cf[j];
+        s += cf[i] * r;
+      }
     }
     // S1 holds phi_i^x phi_j^y + phi_i^y phi_j^x, so c^T S1 c counts the mixed term twice as needed
     if (alpha != 0.0)
@@ -125,8 +165,17 @@ k_estimate_cells(int32_t ncells, const double* __restrict__ tab, const double* _
       {
         const double gx = G[2 * d], gy = G[2 * d + 1];
         const double t0 = J00 * gx + J10 * gy, t1 = J01 * gx + J11 * gy; // J^T G_d
-        for (int i = 0; i < NRT; ++i)
-          sgm += cf[i] * (st[E::OFF_MRD + (i * ND + d) * 2] * t0 + st[E::OFF_MRD + (i * ND + d) * 2 + 1] * t1);
+        if constexpr (DEG == K - 1)
+        {
+          for (int i = 0; i < NRT; ++i)
+            sgm += cf[i] * (st[E::OFF_MRD + (i * ND + d) * 2] * t0 + st[E::OFF_MRD + (i * ND + d) * 2 + 1] * t1);
+        }
+        else
+        {
+#pragma unroll
+          for (int i = 0; i < NRT; ++i)
+            sgm += cf[i] * (st[E::OFF_MRD + (i * ND + d) * 2] * t0 + st[E::OFF_MRD + (i * ND + d) * 2 + 1] * t1);
+        }
 #pragma unroll
         for (int e = 0; e < ND; ++e)
           gg += st[E::OFF_MPS + d * ND + e] * (gx * G[2 * e] + gy * G[2 * e + 1]);
@@ -138,12 +187,12 @@ k_estimate_cells(int32_t ncells, const double* __restrict__ tab, const double* _
 }
 
 // outward moments of (sigma_eq + G) on local facet lf of cell c
-template <int K>
+template <int K, int DEG>
 __device__ __forceinline__ void facet_moments(const double* st, const double* cellJ, const double* x_eq,
                                               const double* flux_dg, int32_t c, int lf, double beta,
                                               double* mu)
 {
-  using E = EstTables<K>;
+  using E = EstTables<K, DEG>;
   constexpr int NRT = E::NRT, ND = E::ND;
   const double* J = cellJ + 4 * (int64_t)c;
   const double detJ = J[0] * J[3] - J[1] * J[2];
@@ -169,7 +218,7 @@ __device__ __forceinline__ void facet_moments(const double* st, const double* ce
 }
 
 // one thread per facet: max_j |moment_j of the normal-flux jump| (0 on boundary facets)
-template <int K>
+template <int K, int DEG>
 __global__ void __launch_bounds__(256)
 k_estimate_facets(int32_t nfacets, const double* __restrict__ tab, const double* __restrict__ cellJ,
                   const int32_t* __restrict__ cell_facets, const uint8_t* __restrict__ facet_perm,
@@ -177,7 +226,7 @@ k_estimate_facets(int32_t nfacets, const double* __restrict__ tab, const double*
                   const double* __restrict__ x_eq, const double* __restrict__ flux_dg,
                   double* __restrict__ jump, const double beta)
 {
-  using E = EstTables<K>;
+  using E = EstTables<K, DEG>;
   extern __shared__ double st[];
   for (int i = threadIdx.x; i < E::TOTAL; i += 256)
     st[i] = tab[i];
@@ -202,8 +251,8 @@ k_estimate_facets(int32_t nfacets, const double* __restrict__ tab, const double*
       l1 = l;
   }
   double m0[K], m1[K];
-  facet_moments<K>(st, cellJ, x_eq, flux_dg, c0, l0, beta, m0);
-  facet_moments<K>(st, cellJ, x_eq, flux_dg, c1, l1, beta, m1);
+  facet_moments<K, DEG>(st, cellJ, x_eq, flux_dg, c0, l0, beta, m0);
+  facet_moments<K, DEG>(st, cellJ, x_eq, flux_dg, c1, l1, beta, m1);
   const bool rev = facet_perm[(int64_t)c0 * 3 + l0] != facet_perm[(int64_t)c1 * 3 + l1];
   double worst = 0.0;
 #pragma unroll
@@ -218,12 +267,70 @@ k_estimate_facets(int32_t nfacets, const double* __restrict__ tab, const double*
   jump[fct] = worst;
 }
 
-template <int K>
-static int launch_estimate_k(const DeviceMesh& m, int nrhs, const double* x_eq, const double* flux_dg,
-                             const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                             double beta, hipStream_t stream)
+// Flux boundary condition (check_boundary_conditions, python/dolfinx_eqlb/eqlb/check_eqlb_conditions.py:90-179):
+// one thread per listed boundary facet, out = max_j | facet DOF j of (sigma_eq + G) - boundary DOF j |, seen from
+// the facet's first cell.  In the hierarchic basis the facet DOFs are the moments of the (reference) normal flux
+// against s^j, those of G come from F0 of the pair.  flux_dg == nullptr: a conforming flux, sigma_eq is the total
+// flux; bvals == nullptr: homogeneous condition.  A facet id outside the mesh gives NaN and reads nothing.
+template <int K, int DEG>
+__global__ void __launch_bounds__(256)
+k_boundary_residual(int32_t nlist, int32_t nfacets, const int32_t* __restrict__ facets,
+                    const double* __restrict__ f0, const double* __restrict__ cellJ,
+                    const int32_t* __restrict__ cell_facets, const int32_t* __restrict__ facet_cells_off,
+                    const int32_t* __restrict__ facet_cells, const double* __restrict__ x_eq,
+                    const double* __restrict__ flux_dg, const double* __restrict__ bvals, double* __restrict__ out)
 {
-  using E = EstTables<K>;
+  using R = eqlb_tables::Ref<K, DEG>;
+  constexpr int NRT = R::NRT, ND = R::ND;
+  const int32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= nlist)
+    return;
+  const int32_t fct = facets[t];
+  if (fct < 0 || fct >= nfacets)
+  {
+    out[t] = __builtin_nan("");
+    return;
+  }
+  const int32_t c = facet_cells[facet_cells_off[fct]];
+  int lf = 0;
+#pragma unroll
+  for (int l = 1; l < 3; ++l)
+    if (cell_facets[(int64_t)c * 3 + l] == fct)
+      lf = l;
+  const double* dofs = x_eq + (int64_t)c * NRT + lf * K;
+  double mu[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+    mu[j] = dofs[j];
+  if (flux_dg)
+  {
+    const double* J = cellJ + 4 * (int64_t)c;
+    const double a00 = J[3], a01 = -J[1], a10 = -J[2], a11 = J[0];
+    const double nx = (lf == 2) ? 0.0 : -1.0, ny = (lf == 0) ? -1.0 : ((lf == 1) ? 0.0 : 1.0);
+    const double nu0 = a00 * nx + a10 * ny, nu1 = a01 * nx + a11 * ny; // adj^T N_f
+    const double* G = flux_dg + (int64_t)c * ND * 2;
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+    {
+      const double gn = G[2 * i] * nu0 + G[2 * i + 1] * nu1;
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        mu[j] += f0[(lf * ND + i) * K + j] * gn;
+    }
+  }
+  double worst = 0.0;
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+    worst = fmax(worst, fabs(bvals ? mu[j] - bvals[(int64_t)c * NRT + lf * K + j] : mu[j]));
+  out[t] = worst;
+}
+
+template <int K, int DEG>
+static int launch_estimate_kd(const DeviceMesh& m, int nrhs, const double* x_eq, const double* flux_dg,
+                              const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
+                              double beta, hipStream_t stream)
+{
+  using E = EstTables<K, DEG>;
   std::vector<double> t;
   E::fill(t);
   double* d_t = nullptr;
@@ -235,12 +342,12 @@ static int launch_estimate_k(const DeviceMesh& m, int nrhs, const double* x_eq, 
   for (int r = 0; r < nrhs && e == hipSuccess; ++r)
   {
     if (div2 || sig2)
-      hipLaunchKernelGGL(k_estimate_cells<K>, dim3((m.ncells + 255) / 256), dim3(256), lds, stream, m.ncells,
+      hipLaunchKernelGGL((k_estimate_cells<K, DEG>), dim3((m.ncells + 255) / 256), dim3(256), lds, stream, m.ncells,
                          d_t, m.cellJ, x_eq + r * nx, flux_dg + r * ng, rhs_dg + r * nf,
                          div2 ? div2 + (int64_t)r * m.ncells : nullptr,
                          sig2 ? sig2 + (int64_t)r * m.ncells : nullptr, alpha, beta);
     if (jump)
-      hipLaunchKernelGGL(k_estimate_facets<K>, dim3((m.nfacets + 255) / 256), dim3(256), lds, stream,
+      hipLaunchKernelGGL((k_estimate_facets<K, DEG>), dim3((m.nfacets + 255) / 256), dim3(256), lds, stream,
                          m.nfacets, d_t, m.cellJ, m.cell_facets, m.facet_perm, m.facet_cells_off,
                          m.facet_cells, x_eq + r * nx, flux_dg + r * ng, jump + (int64_t)r * m.nfacets, beta);
     e = hipGetLastError();
@@ -251,20 +358,67 @@ static int launch_estimate_k(const DeviceMesh& m, int nrhs, const double* x_eq, 
   return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
-int launch_estimate(const DeviceMesh& m, int k, int nrhs, const double* x_eq, const double* flux_dg,
+// [nrhs][nlist] residuals of the flux boundary condition on the listed facets (DEVICE pointers)
+template <int K, int DEG>
+static int launch_boundary_residual_kd(const DeviceMesh& m, int nrhs, const double* x_eq, const double* flux_dg,
+                                       int32_t nlist, const int32_t* facets, const double* bvals, double* out,
+                                       hipStream_t stream)
+{
+  using R = eqlb_tables::Ref<K, DEG>;
+  double* d_t = nullptr;
+  if (hipMalloc(&d_t, R::F0_SIZE * sizeof(double)) != hipSuccess)
+    return EQLB_ERR_DEVICE;
+  hipError_t e = hipMemcpyAsync(d_t, R::F0, R::F0_SIZE * sizeof(double), hipMemcpyHostToDevice, stream);
+  const int64_t nx = (int64_t)m.ncells * R::NRT, ng = (int64_t)m.ncells * R::ND * 2;
+  for (int r = 0; r < nrhs && e == hipSuccess; ++r)
+  {
+    hipLaunchKernelGGL((k_boundary_residual<K, DEG>), dim3((nlist + 255) / 256), dim3(256), 0, stream, nlist,
+                       m.nfacets, facets, d_t, m.cellJ, m.cell_facets, m.facet_cells_off, m.facet_cells,
+                       x_eq + r * nx, flux_dg ? flux_dg + r * ng : nullptr, bvals ? bvals + r * nx : nullptr,
+                       out + (int64_t)r * nlist);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(stream); // the table buffer is freed below
+  (void)hipFree(d_t);
+  return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
+}
+
+#if !EQLB_EST_TEMPLATES_ONLY
+int launch_estimate(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                     const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
                     double beta, hipStream_t stream)
 {
+  if (deg != k - 1)
+    return launch_estimate_lowdeg(m, k, deg, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
   if (k == 1)
-    return launch_estimate_k<1>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<1, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
   if (k == 2)
-    return launch_estimate_k<2>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<2, 1>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
   if (k == 3)
-    return launch_estimate_k<3>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<3, 2>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
   if (k == 4)
-    return launch_estimate_k<4>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<4, 3>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
+
+int launch_boundary_residual(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
+                             const double* flux_dg, int32_t nlist, const int32_t* facets, const double* bvals,
+                             double* out, hipStream_t stream)
+{
+  if (deg != k - 1)
+    return launch_boundary_residual_lowdeg(m, k, deg, nrhs, x_eq, flux_dg, nlist, facets, bvals, out, stream);
+  if (k == 1)
+    return launch_boundary_residual_kd<1, 0>(m, nrhs, x_eq, flux_dg, nlist, facets, bvals, out, stream);
+  if (k == 2)
+    return launch_boundary_residual_kd<2, 1>(m, nrhs, x_eq, flux_dg, nlist, facets, bvals, out, stream);
+  if (k == 3)
+    return launch_boundary_residual_kd<3, 2>(m, nrhs, x_eq, flux_dg, nlist, facets, bvals, out, stream);
+  if (k == 4)
+    return launch_boundary_residual_kd<4, 3>(m, nrhs, x_eq, flux_dg, nlist, facets, bvals, out, stream);
+  return EQLB_ERR_UNSUPPORTED;
+}
+#endif
 
 // ---- stress estimator (demo/elasticity/demo_error_estimation.py:49-148) --------------------------------
 // delta_sigma = (row 0; row 1) of an equilibrated stress.  Per cell, with W^{ab}_{rs} = c_r^T SU^{ab} c_s on the
@@ -357,6 +511,7 @@ k_estimate_stress_cells(int32_t ncells, const double* __restrict__ tab, const do
   }
 }
 
+#if !EQLB_EST_TEMPLATES_ONLY
 // node value = sum of the vertex values of the cells around the node, in the order of the CSR list
 __global__ void __launch_bounds__(256)
 k_gather_vertex_values(int32_t nnodes, const int32_t* __restrict__ node_cells_off,
@@ -424,20 +579,21 @@ int launch_estimate_stress(const DeviceMesh& m, const int32_t* node_cells, int k
     return launch_estimate_stress_k<4>(m, node_cells, x0, x1, korn, pi_1, energy, wsym, node_asym, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
+#endif
 
 // ---- data oscillation ((h_T / pi) || f - div sigma ||_T of demo/poisson/demo_error_estimation.py:93-100,
 //      with the Korn constant in front for stresses, demo/elasticity/demo_error_estimation.py:104-106) -------
 // detJ * div(sigma_eq + beta G) is a polynomial of P_{k-1}(ref): its monomial coefficients are GMI * (moments),
 // the moments as in k_estimate_cells.  f comes as point values at the images of a reference rule.
 // qtab: [nq][NQ] monomial values at the points, then [nq] weights.
-template <int K>
+template <int K, int DEG>
 __global__ void __launch_bounds__(256)
 k_oscillation_cells(int32_t ncells, const double* __restrict__ tab, const double* __restrict__ qtab, int nq,
                     const double* __restrict__ cellJ, const double* __restrict__ x_eq,
                     const double* __restrict__ flux_dg, const double* __restrict__ fvalues,
                     const double* __restrict__ korn, double* __restrict__ out)
 {
-  using E = EstTables<K>;
+  using E = EstTables<K, DEG>;
   constexpr int NRT = E::NRT, ND = E::ND, NQ = E::NQ;
   extern __shared__ double st[];
   double* sq = st + E::TOTAL;
@@ -459,7 +615,7 @@ k_oscillation_cells(int32_t ncells, const double* __restrict__ tab, const double
 #pragma unroll
   for (int q = 1; q < NQ; ++q)
     m[q] = cf[3 * K + q - 1];
-  if (flux_dg)
+  if (flux_dg && !(DEG == 0 && K >= 2)) // P0 data: div G = 0 (RT_1 keeps the generic contraction)
   {
     const double* G = flux_dg + (int64_t)c * ND * 2;
 #pragma unroll
@@ -501,13 +657,13 @@ k_oscillation_cells(int32_t ncells, const double* __restrict__ tab, const double
   out[c] = ck * ck * h2 / (PI * PI) * fabs(detJ) * s;
 }
 
-template <int K>
-static int launch_oscillation_k(const DeviceMesh& m, int nrhs, const double* x_eq, const double* flux_dg, int nq,
-                                const double* qpoints, const double* qweights, const double* fvalues,
-                                const double* korn, double* out, hipStream_t stream)
+template <int K, int DEG>
+static int launch_oscillation_kd(const DeviceMesh& m, int nrhs, const double* x_eq, const double* flux_dg, int nq,
+                                 const double* qpoints, const double* qweights, const double* fvalues,
+                                 const double* korn, double* out, hipStream_t stream)
 {
-  using E = EstTables<K>;
-  using R = eqlb_tables::Ref<K, K - 1>;
+  using E = EstTables<K, DEG>;
+  using R = eqlb_tables::Ref<K, DEG>;
   std::vector<double> t;
   E::fill(t);
   std::vector<double> qt((size_t)nq * (E::NQ + 1));
@@ -532,7 +688,7 @@ static int launch_oscillation_k(const DeviceMesh& m, int nrhs, const double* x_e
   const int64_t nx = (int64_t)m.ncells * E::NRT, ng = (int64_t)m.ncells * E::ND * 2;
   for (int r = 0; r < nrhs && e == hipSuccess; ++r)
   {
-    hipLaunchKernelGGL(k_oscillation_cells<K>, dim3((m.ncells + 255) / 256), dim3(256), lds, stream, m.ncells, d_t,
+    hipLaunchKernelGGL((k_oscillation_cells<K, DEG>), dim3((m.ncells + 255) / 256), dim3(256), lds, stream, m.ncells, d_t,
                        d_q, nq, m.cellJ, x_eq + r * nx, flux_dg ? flux_dg + r * ng : nullptr,
                        fvalues + (int64_t)r * m.ncells * nq, korn, out + (int64_t)r * m.ncells);
     e = hipGetLastError();
@@ -544,20 +700,24 @@ static int launch_oscillation_k(const DeviceMesh& m, int nrhs, const double* x_e
   return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
-int launch_oscillation(const DeviceMesh& m, int k, int nrhs, const double* x_eq, const double* flux_dg, int nq,
-                       const double* qpoints, const double* qweights, const double* fvalues, const double* korn,
-                       double* out, hipStream_t stream)
+#if !EQLB_EST_TEMPLATES_ONLY
+int launch_oscillation(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
+                       int nq, const double* qpoints, const double* qweights, const double* fvalues,
+                       const double* korn, double* out, hipStream_t stream)
 {
+  if (deg != k - 1)
+    return launch_oscillation_lowdeg(m, k, deg, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out,
+                                     stream);
   if (k == 1)
-    return launch_oscillation_k<1>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
+    return launch_oscillation_kd<1, 0>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
   if (k == 2)
-    return launch_oscillation_k<2>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
+    return launch_oscillation_kd<2, 1>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
   if (k == 3)
-    return launch_oscillation_k<3>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
+    return launch_oscillation_kd<3, 2>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
   if (k == 4)
-    return launch_oscillation_k<4>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
+    return launch_oscillation_kd<4, 3>(m, nrhs, x_eq, flux_dg, nq, qpoints, qweights, fvalues, korn, out, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
-
+#endif
 
 } // namespace eqlb

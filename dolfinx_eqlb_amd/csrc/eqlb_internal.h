@@ -273,15 +273,39 @@ void launch_project_dg(int64_t ncells, int nd, int nq, int bs, const double* Pm,
 void launch_korn(const DeviceMesh& m, const int64_t* node_slot, const int64_t* node_patch,
                  const int32_t* slot_cell, const uint32_t* slot_info, const uint8_t* pn,
                  const uint8_t* pflag, double* cks, double* korn, hipStream_t stream);
-int launch_estimate(const DeviceMesh& m, int k, int nrhs, const double* x_eq, const double* flux_dg,
+// estimator step (eqlb_estimate.hip); flux_dg / rhs_dg in DG_deg, 0 <= deg <= k - 1
+int launch_estimate(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                     const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
                     double beta, hipStream_t stream);
+int launch_boundary_residual(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
+                             const double* flux_dg, int32_t nlist, const int32_t* facets, const double* bvals,
+                             double* out, hipStream_t stream);
 int launch_estimate_stress(const DeviceMesh& m, const int32_t* node_cells, int k, const double* x0,
                            const double* x1, const double* korn, double pi_1, double* energy, double* wsym,
                            double* node_asym, hipStream_t stream);
-int launch_oscillation(const DeviceMesh& m, int k, int nrhs, const double* x_eq, const double* flux_dg, int nq,
-                       const double* qpoints, const double* qweights, const double* fvalues, const double* korn,
-                       double* out, hipStream_t stream);
+int launch_oscillation(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
+                       int nq, const double* qpoints, const double* qweights, const double* fvalues,
+                       const double* korn, double* out, hipStream_t stream);
+// the same launches for deg < k - 1 (eqlb_estimate_lowdeg.hip, which passes k = 4 on to eqlb_estimate_lowdeg_k4.hip):
+// the launchers above hand every call with deg != k - 1 over to these
+int launch_estimate_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
+                           const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
+                           double beta, hipStream_t stream);
+int launch_boundary_residual_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
+                                    const double* flux_dg, int32_t nlist, const int32_t* facets,
+                                    const double* bvals, double* out, hipStream_t stream);
+int launch_oscillation_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
+                              const double* flux_dg, int nq, const double* qpoints, const double* qweights,
+                              const double* fvalues, const double* korn, double* out, hipStream_t stream);
+int launch_estimate_k4_lowdeg(const DeviceMesh& m, int deg, int nrhs, const double* x_eq, const double* flux_dg,
+                              const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
+                              double beta, hipStream_t stream);
+int launch_boundary_residual_k4_lowdeg(const DeviceMesh& m, int deg, int nrhs, const double* x_eq,
+                                       const double* flux_dg, int32_t nlist, const int32_t* facets,
+                                       const double* bvals, double* out, hipStream_t stream);
+int launch_oscillation_k4_lowdeg(const DeviceMesh& m, int deg, int nrhs, const double* x_eq, const double* flux_dg,
+                                 int nq, const double* qpoints, const double* qweights, const double* fvalues,
+                                 const double* korn, double* out, hipStream_t stream);
 int set_error(int code, const char* fmt, ...); // thread-local message of eqlb_last_error + the code back
 void launch_halo_pack(int nrhs, int32_t nlist, int32_t nrt, int64_t ncells, const int64_t* cells, double* x,
                       double* buf, int clear, hipStream_t stream);

@@ -272,17 +272,18 @@ def cell_diameter(mesh):
     return np.sqrt((e ** 2).sum(axis=2)).max(axis=1)
 
 
-def oscillation_term(mesh, k, sigma, flux_dg, f, qdegree, korn=None):
+def oscillation_term(mesh, k, sigma, flux_dg, f, qdegree, korn=None, degree_dg=None):
     """C_K^2 (h_T/pi)^2 || f - div(sigma + G) ||^2_T per cell (demo/poisson/demo_error_estimation.py:96-98),
-    numpy statement: f callable f(x, y), sigma [ncells*k(k+2)] broken hierarchic RT_k, flux_dg the DG_{k-1}^2
-    part G of the total flux or None."""
+    numpy statement: f callable f(x, y), sigma [ncells*k(k+2)] broken hierarchic RT_k, flux_dg the DG_d^2
+    part G of the total flux (d = degree_dg, k-1 if None) or None."""
+    degree_dg = k - 1 if degree_dg is None else degree_dg
     J, detJ, K = cell_geometry(mesh)
     rt = ert.HierarchicRT(k)
     qp, qw = make_quadrature_triangle(qdegree)
     c = np.asarray(sigma).reshape(mesh.ncells, rt.ndofs)
     div = np.einsum("ci,qi->cq", c, rt.tabulate_div(qp)) / detJ[:, None]
     if flux_dg is not None:
-        dg = Lagrange(k - 1)
+        dg = Lagrange(degree_dg)
         gr = dg.tabulate(qp, 1)[1:]                               # [2, q, nd] reference derivatives
         G = np.asarray(flux_dg).reshape(mesh.ncells, dg.ndofs, 2)
         # d/dx_i = sum_a K[a, i] d/dX_a

@@ -56,8 +56,9 @@ def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int 
 def embed_dg(values, ncells: int, degree_from: int, degree_to: int, bs: int = 1):
     """Exact embedding DG_{degree_from} -> DG_{degree_to} (degree_to >= degree_from) of nodal
     values [ncells*nd_from*bs]: the reference accepts projected data of any degree <= k-1
-    (se/reconstruction.hpp:363-373) and the equilibrators read it as it is; the estimator entry points
-    (eqlb_se_estimate, eqlb_ev_estimate, eqlb_oscillation) take DG_{k-1}, which contains it."""
+    (se/reconstruction.hpp:363-373).  The equilibrators and the estimator entry points (eqlb_se_estimate_dg,
+    eqlb_ev_estimate_dg, eqlb_oscillation_dg, eqlb_boundary_residual) read it as it is; the embedding is what
+    the tests compare them with."""
     import numpy as np
 
     from ..elmtlib.lagrange import Lagrange

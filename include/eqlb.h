@@ -274,11 +274,21 @@ double eqlb_se_last_kernel_ms(const eqlb_se_t* handle, int32_t which);
  *   facet_jump [nrhs][nfacets] max_j | j-th moment of [(sigma_eq + G).n] | on interior facets, 0 on
  *                              boundary facets (H(div) conformity, check_eqlb_conditions.py:294-359)
  * Any output may be NULL.  Arrays in the layouts of eqlb_se_equilibrate; memspace as there.
- * flux_dg / rhs_dg in DG_{k-1} (here and in eqlb_ev_estimate, eqlb_oscillation): data of a lower degree are
- * embedded first (dolfinx_eqlb_amd.lsolver.embed_dg; exact, DG_d is a subspace of DG_{k-1}). */
+ * flux_dg / rhs_dg in DG_{k-1} (here and in eqlb_ev_estimate, eqlb_oscillation).  Data of a lower degree go to the
+ * *_dg entry points below as they are; nothing has to be embedded into DG_{k-1} first. */
 int eqlb_se_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux_hdiv,
                      const double* flux_dg, const double* rhs_dg, double* cell_div2,
                      double* cell_sig2, double* facet_jump, int32_t memspace, void* stream);
+
+/* eqlb_se_estimate with projected data of degree degree_dg, 0 <= degree_dg <= k - 1 (the reference accepts any
+ * such degree, se/reconstruction.hpp:363-373, and its acceptance predicates take the functions as they are,
+ * check_eqlb_conditions.py:183-359):  flux_dg [nrhs][ncells*nd*2], rhs_dg [nrhs][ncells*nd],
+ * nd = (degree_dg+1)(degree_dg+2)/2, read natively on the device.  eqlb_se_estimate is the case
+ * degree_dg = k - 1.  A degree outside 0 ... k - 1: EQLB_ERR_INVALID_ARGUMENT "Wrong polynomial degree" as
+ * eqlb_se_create, nothing is launched. */
+int eqlb_se_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_hdiv,
+                        const double* flux_dg, const double* rhs_dg, double* cell_div2, double* cell_sig2,
+                        double* facet_jump, int32_t memspace, void* stream);
 
 /* The same quantities for a conforming (EV) flux handed over in the broken layout
  * (eqlb_ev_set_option "output" = 1): the total flux is sigma_eq itself, so
@@ -287,6 +297,12 @@ int eqlb_se_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* f
 int eqlb_ev_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux_broken,
                      const double* flux_dg, const double* rhs_dg, double* cell_div2,
                      double* cell_sig2, double* facet_jump, int32_t memspace, void* stream);
+
+/* eqlb_ev_estimate with flux_dg / rhs_dg in DG_{degree_dg} as eqlb_se_estimate_dg takes them (err_sig of
+ * demo/poisson/demo_error_estimation.py:97-100 with a P_{degree_dg+1} primal solution). */
+int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_broken,
+                        const double* flux_dg, const double* rhs_dg, double* cell_div2, double* cell_sig2,
+                        double* facet_jump, int32_t memspace, void* stream);
 
 /* Stress estimator terms of demo/elasticity/demo_error_estimation.py:49-148 for an equilibrated stress
  * delta_sigma = (row 0; row 1), flux_hdiv [2][ncells*k(k+2)] as eqlb_se_equilibrate writes it, per cell:
@@ -315,6 +331,30 @@ int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdi
 int eqlb_oscillation(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux, const double* flux_dg,
                      int32_t nq, const double* qpoints, const double* qweights, const double* fvalues,
                      const double* korn, double* out, int32_t memspace, void* stream);
+
+/* eqlb_oscillation with flux_dg [nrhs][ncells*nd*2] in DG_{degree_dg}, 0 <= degree_dg <= k - 1 (err_osc of
+ * demo/poisson/demo_error_estimation.py:96-98 for projected data of a lower degree); eqlb_oscillation is the case
+ * degree_dg = k - 1.  A degree outside 0 ... k - 1: EQLB_ERR_INVALID_ARGUMENT. */
+int eqlb_oscillation_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux,
+                        const double* flux_dg, int32_t nq, const double* qpoints, const double* qweights,
+                        const double* fvalues, const double* korn, double* out, int32_t memspace, void* stream);
+
+/* Flux boundary condition of an equilibrated flux on the device - check_boundary_conditions of the reference
+ * (python/dolfinx_eqlb/eqlb/check_eqlb_conditions.py:90-179), the fourth acceptance predicate next to the
+ * divergence, jump and weak-symmetry ones above.  Per listed boundary facet
+ *   out [nrhs][nfacets_bc] = max_j | facet DOF j of (flux + flux_dg) - boundary DOF j |
+ * in the hierarchic basis, whose facet DOFs are the moments of the normal flux.
+ *   flux     [nrhs][ncells*k(k+2)]   RT_k coefficients in the broken hierarchic layout
+ *   flux_dg  [nrhs][ncells*nd*2]     DG_{degree_dg} part of a semi-explicit flux, or NULL: flux is the total flux
+ *                                    (a conforming flux, eqlb_ev_set_option "output" = 1)
+ *   facets   [nfacets_bc] int32      the flux-BC facets (in the memory space of the call)
+ *   boundary_values [nrhs][ncells*k(k+2)] as eqlb_se_set_boundary takes them, or NULL: homogeneous condition
+ * An interior facet is seen from its first cell.  nfacets_bc = 0 is allowed.  Host memory space: a facet id
+ * outside the mesh is EQLB_ERR_INVALID_ARGUMENT; device memory space: its result is NaN, nothing is read.
+ * degree_dg outside 0 ... k - 1: EQLB_ERR_INVALID_ARGUMENT. */
+int eqlb_boundary_residual(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux,
+                           const double* flux_dg, int32_t nfacets_bc, const int32_t* facets,
+                           const double* boundary_values, double* out, int32_t memspace, void* stream);
 
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the
