@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_rccl_comm_destroy", "eqlb_halo_create", "eqlb_halo_destroy", "eqlb_halo_bytes", "eqlb_halo_reduce_plan",
     "eqlb_se_tiling_blocks", "eqlb_ev_tiling_blocks", "eqlb_ev_create_dg",
     "eqlb_se_estimate_dg", "eqlb_ev_estimate_dg", "eqlb_oscillation_dg", "eqlb_boundary_residual",
+    "eqlb_se_large_patch_info", "eqlb_ev_large_patch_info",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -54,6 +55,13 @@ def _tiling_blocks(fn, h):
     d = {kind: [v[nk * b + i] for b in range(5)] for i, kind in enumerate(TILING_BLOCK_KINDS)}
     d["zero_tiles"] = v[5 * nk]
     return d
+
+def _large_patch_info(fn, h):
+    """(number of patches on the large-patch kernel, cells of the largest one)."""
+    n, mx = C.c_int64(0), C.c_int32(0)
+    _check(fn(h, C.byref(n), C.byref(mx)))
+    return int(n.value), int(mx.value)
+
 
 _lib = None
 
@@ -206,6 +214,11 @@ class SemiExplicitEquilibrator:
         [count for P = 4, 8, 16, 32, 64] for the kinds of TILING_BLOCK_KINDS, and "zero_tiles"."""
         return _tiling_blocks(lib().eqlb_se_tiling_blocks, self._h)
 
+    def large_patch_info(self):
+        """(npatches, max_cells) of the patches with more than 63 cells or 64 facets that the last set_boundary
+        handed to the large-patch kernel (option "large_patches"; eqlb_se_large_patch_info)."""
+        return _large_patch_info(lib().eqlb_se_large_patch_info, self._h)
+
     def equilibrate_host(self, flux_dg, rhs_dg, flux_hdiv=None):
         """Host numpy arrays in/out; flux_hdiv is accumulated (+=) like the reference."""
         m = self.dmesh.mesh
@@ -353,6 +366,10 @@ class ConstrainedMinEquilibrator:
     def tiling_blocks(self):
         """As SemiExplicitEquilibrator.tiling_blocks (eqlb_ev_tiling_blocks)."""
         return _tiling_blocks(lib().eqlb_ev_tiling_blocks, self._h)
+
+    def large_patch_info(self):
+        """As SemiExplicitEquilibrator.large_patch_info (eqlb_ev_large_patch_info)."""
+        return _large_patch_info(lib().eqlb_ev_large_patch_info, self._h)
 
     def _nout(self):
         return self.dmesh.mesh.ncells * self.nrt if self.output == 1 else self.ndofs

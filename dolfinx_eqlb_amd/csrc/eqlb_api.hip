@@ -110,6 +110,14 @@ void free_boundary(eqlb_se* h)
   dfree(h->pn);
   dfree(h->pflag);
   dfree(h->slots); // re-zeroed on the next call (node_mask may have changed)
+  dfree(h->l_off);
+  dfree(h->l_slot_cell);
+  dfree(h->l_slot_info);
+  dfree(h->l_pflag);
+  dfree(h->l_cells);
+  dfree(h->l_ws);
+  h->l_npatch = h->l_nslots = h->l_ncells = 0;
+  h->l_maxcells = 0;
   dfree(h->t_tiles);
   dfree(h->t_tile_cells);
   dfree(h->t_facet_owner);
@@ -1247,6 +1255,13 @@ int eqlb_se_set_option(eqlb_se_t* h, const char* key, int32_t value)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "multi_rhs must be 0 or 1");
     h->multi_rhs = value;
   }
+  else if (!strcmp(key, "large_patches"))
+  {
+    // takes effect at the next eqlb_se_set_boundary
+    if (value != 0 && value != 1)
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "large_patches must be 0 or 1");
+    h->large_patches = value;
+  }
   else if (!strcmp(key, "tile_first"))
   {
     if (value < 0)
@@ -1310,6 +1325,7 @@ try
   std::vector<int64_t> node_slot(m.nnodes, -1), node_patch(m.nnodes, -1);
   int64_t count[eqlb::MAX_BINS] = {0, 0, 0, 0, 0};
   std::vector<int8_t> node_bin(m.nnodes, -1);
+  std::vector<int32_t> large_nodes; // patches of more than 63 cells or more than 64 facets
   for (int32_t i = 0; i < m.nnodes; ++i)
   {
     if (node_mask && !node_mask[i])
@@ -1319,8 +1335,25 @@ try
     while (b < eqlb::MAX_BINS && eqlb::BIN_P[b] < nf)
       ++b;
     if (b == eqlb::MAX_BINS || m.h_node_ncells[i] > 63)
-      return fail(EQLB_ERR_PATCH_TOO_LARGE, "Patch around node %d has %d cells (limit 63)", i,
-                  m.h_node_ncells[i]);
+    {
+      if (!h->large_patches)
+        return fail(EQLB_ERR_PATCH_TOO_LARGE, "Patch around node %d has %d cells (limit 63)", i,
+                    m.h_node_ncells[i]);
+      // option "large_patches": the patch goes to the multi-wave kernel (a CSR-style SoA of its own, below); its node
+      // stays out of the bins and is, for the tiles, a node that another path equilibrates
+      if (h->stress)
+        return fail(EQLB_ERR_PATCH_TOO_LARGE,
+                    "Patch around node %d has %d cells: the stress equilibration (weak symmetry, Korn constants) is "
+                    "limited to 63 cells per patch, \"large_patches\" covers flux equilibration only",
+                    i, m.h_node_ncells[i]);
+      if (h->mode == 1 && h->k >= 4)
+        return fail(EQLB_ERR_PATCH_TOO_LARGE,
+                    "Patch around node %d has %d cells: the constrained minimisation at RT_4 is limited to 63 cells per "
+                    "patch, \"large_patches\" covers it for RT_1 ... RT_3",
+                    i, m.h_node_ncells[i]);
+      large_nodes.push_back(i);
+      continue;
+    }
     node_bin[i] = (int8_t)b;
     ++count[b];
   }
@@ -1422,6 +1455,75 @@ try
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   tm.lap("plain SoA: upload + builder");
+  if (!large_nodes.empty())
+  {
+    // large patches: lane slots in CSR form (l_off), the same descriptor bits, flags per right-hand side; the cell
+    // count of a patch is the difference of its offsets
+    const int64_t nl = (int64_t)large_nodes.size();
+    std::vector<int64_t> lslot(m.nnodes, -1), lpatch(m.nnodes, -1);
+    std::vector<int32_t> off(nl + 1, 0);
+    std::vector<uint8_t> is_large(m.nnodes, 0);
+    int64_t acc = 0;
+    for (int64_t p = 0; p < nl; ++p)
+    {
+      const int32_t nd = large_nodes[p];
+      lslot[nd] = acc;
+      lpatch[nd] = p;
+      is_large[nd] = 1;
+      off[p] = (int32_t)acc;
+      acc += m.h_node_ncells[nd];
+      h->l_maxcells = std::max(h->l_maxcells, m.h_node_ncells[nd]);
+      if (acc > 0x7fffff00)
+        return fail(EQLB_ERR_UNSUPPORTED, "large-patch SoA exceeds 2^31 lane slots");
+    }
+    off[nl] = (int32_t)acc;
+    std::vector<int32_t> lc;
+    for (int32_t c = 0; c < m.ncells; ++c)
+      for (int j = 0; j < 3; ++j)
+        if (is_large[m.h_cell_nodes[3 * (size_t)c + j]])
+        {
+          lc.push_back(c);
+          break;
+        }
+    int64_t *d_lslot = nullptr, *d_lpatch = nullptr;
+    int stl = 0;
+    stl |= upload(&h->l_off, off.data(), off.size());
+    stl |= upload<int32_t>(&h->l_slot_cell, nullptr, (size_t)acc);
+    stl |= upload<uint32_t>(&h->l_slot_info, nullptr, (size_t)acc);
+    stl |= upload<uint8_t>(&h->l_pflag, nullptr, (size_t)nl * h->nrhs);
+    stl |= upload(&h->l_cells, lc.data(), lc.size());
+    stl |= upload<double>(&h->l_ws, nullptr, eqlb::large_patch_ws_doubles(h->k, acc, nl));
+    stl |= upload(&d_lslot, lslot.data(), lslot.size());
+    stl |= upload(&d_lpatch, lpatch.data(), lpatch.size());
+    hipError_t e = hipSuccess;
+    if (!stl)
+    {
+      eqlb::BuildArgs al = a;
+      al.node_ws = nullptr;
+      al.node_slot = d_lslot;
+      al.node_patch = d_lpatch;
+      al.npatch_total = nl;
+      al.slot_cell = h->l_slot_cell;
+      al.slot_info = h->l_slot_info;
+      al.pn = nullptr;
+      al.pflag = h->l_pflag;
+      al.large = 1;
+      eqlb::launch_build_patches(al, nullptr);
+      e = hipGetLastError();
+      if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    }
+    dfree(d_lslot);
+    dfree(d_lpatch);
+    if (stl)
+      return EQLB_ERR_DEVICE;
+    if (e != hipSuccess)
+      return fail(EQLB_ERR_DEVICE, "large-patch builder: %s", hipGetErrorString(e));
+    h->l_npatch = nl;
+    h->l_nslots = acc;
+    h->l_ncells = (int64_t)lc.size();
+    tm.lap("large-patch SoA");
+  }
   h->t_stress = h->stress && stress_fused_ok && h->mode == 0;
   if (h->t_stress || (!h->stress && h->k <= 3))
   {
@@ -1475,6 +1577,10 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
   if (!h->boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_kornconst: boundary data not set");
+  if (h->l_npatch > 0)
+    return fail(EQLB_ERR_PATCH_TOO_LARGE,
+                "eqlb_se_kornconst: the Korn constants are limited to 63 cells per patch, \"large_patches\" covers flux "
+                "equilibration only");
   const eqlb::DeviceMesh& m = h->mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!h->d_cks && upload<double>(&h->d_cks, nullptr, (size_t)m.nnodes))
@@ -1539,6 +1645,17 @@ int eqlb_se_tiling_blocks(const eqlb_se_t* h, int64_t* out, int32_t n)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_tiling_blocks: invalid argument");
   for (int32_t i = 0; i < std::min<int32_t>(n, EQLB_TB_COUNT); ++i)
     out[i] = h->ntiles > 0 ? h->t_blocks[i] : 0;
+  return EQLB_OK;
+}
+
+int eqlb_se_large_patch_info(const eqlb_se_t* h, int64_t* npatches, int32_t* max_cells)
+{
+  if (!h || !h->boundary_set)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_large_patch_info: set the boundary first");
+  if (npatches)
+    *npatches = h->l_npatch;
+  if (max_cells)
+    *max_cells = h->l_maxcells;
   return EQLB_OK;
 }
 
@@ -1611,6 +1728,7 @@ try
     a.node_slot = nullptr;
     a.node_patch = nullptr;
     a.npatch_total = 0;
+    a.large = h->large_patches; // fans of more than 63 cells as well (the stride holds them)
     a.stride = stride;
     a.ex_ncells = d_n;
     a.ex_cells = d_c;
@@ -1677,6 +1795,9 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
   const size_t s_x = ev_conf ? (size_t)h->ev_ndofs : s_slot, n_x = (size_t)h->nrhs * s_x;
   if (!h->accumulate && scatter_eff == EQLB_SCATTER_ATOMIC)
     return fail(EQLB_ERR_UNSUPPORTED, "\"accumulate\" = 0 is not available with the atomic scatter");
+  if (h->l_npatch > 0 && scatter_eff == EQLB_SCATTER_ATOMIC)
+    return fail(EQLB_ERR_UNSUPPORTED,
+                "patches of more than 63 cells (\"large_patches\") run with the slot or the tiled scatter, not the atomic one");
   if (h->mode == 1 && (scatter_eff == EQLB_SCATTER_ATOMIC || (h->solver != EQLB_SOLVER_SHUFFLE && h->k != 4)))
     return fail(EQLB_ERR_UNSUPPORTED, "EV equilibration runs with the shuffle solver (tiled or slot scatter)");
 
@@ -1765,6 +1886,48 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
   // (the rest of a fused stress launch runs its patch kernels on a side stream next to the fused kernel)
   hipStream_t sp_stream = stream;
   int sp_phase = 0;
+  // the slot buffer, zeroed where rows of an earlier run over more bins than `cover` would be added again (see below)
+  auto ensure_slots = [&](int cover, hipStream_t s) -> int {
+    if (!h->slots)
+    {
+      if (upload<double>(&h->slots, nullptr, n_slot * 3))
+        return EQLB_ERR_DEVICE;
+      // slots of (cell, vertex) pairs whose node is not equilibrated here (node_mask, other path) stay zero
+      // (on the stream of the patch kernels: a fill on the null stream is not ordered against the non-blocking side
+      // stream of a fused stress launch and could wipe rows its kernels have already written)
+      HIP_TRY(hipMemsetAsync(h->slots, 0, n_slot * 3 * sizeof(double), s));
+      h->slots_first_bin = eqlb::MAX_BINS;
+    }
+    // The reduction adds ALL slot rows of a cell.  A run over the bins >= first_bin rewrites only their rows: rows
+    // of the lower bins left by an earlier run over more bins (option "scatter" / "solver" changed on this handle)
+    // would be added again on top of what the tiled launch wrote
+    if (h->slots_first_bin < cover)
+      HIP_TRY(hipMemsetAsync(h->slots, 0, n_slot * 3 * sizeof(double), s));
+    h->slots_first_bin = cover;
+    return EQLB_OK;
+  };
+  // patches of more than 63 cells: one workgroup each, rows into the slot buffer (rewritten by every call); timing
+  // slot MAX_BINS + 2
+  auto run_large = [&](hipStream_t s) -> int {
+    eqlb::SeArgs al = a;
+    al.slot_cell = h->l_slot_cell;
+    al.slot_info = h->l_slot_info;
+    al.pn = nullptr;
+    al.pflag = h->l_pflag;
+    al.npatch_total = h->l_npatch;
+    if (evs)
+      HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 4], s));
+    for (int r = 0; r < h->nrhs; ++r)
+    {
+      select_rhs(al, r, true);
+      const int st = eqlb::launch_se_patch_large(h->k, h->deg, h->mode, al, h->l_off, h->l_ws, s);
+      if (st)
+        return fail(st, "large-patch kernel launch failed (k=%d)", h->k);
+    }
+    if (evs)
+      HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 5], s));
+    return EQLB_OK;
+  };
   auto run_slot_path = [&](int first_bin, int accumulate) -> int {
     const bool rest = first_bin < 0;
     auto bin_np = [&](int b) -> int64_t {
@@ -1785,22 +1948,8 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
           return fail(EQLB_ERR_UNSUPPORTED, "compact slot reduction for %d DOFs per cell is not in this build", h->nrt);
       return EQLB_OK;
     }
-    if (!h->slots)
-    {
-      if (upload<double>(&h->slots, nullptr, n_slot * 3))
-        return EQLB_ERR_DEVICE;
-      // slots of (cell, vertex) pairs whose node is not equilibrated here (node_mask, other path) stay zero
-      // (on the stream of the patch kernels: a fill on the null stream is not ordered against the non-blocking side
-      // stream of a fused stress launch and could wipe rows its kernels have already written)
-      HIP_TRY(hipMemsetAsync(h->slots, 0, n_slot * 3 * sizeof(double), sp_stream));
-      h->slots_first_bin = eqlb::MAX_BINS;
-    }
-    // The reduction adds ALL slot rows of a cell.  A run over the bins >= first_bin rewrites only their rows: rows
-    // of the lower bins left by an earlier run over more bins (option "scatter" / "solver" changed on this handle)
-    // would be added again on top of what the tiled launch wrote
-    if (h->slots_first_bin < cover)
-      HIP_TRY(hipMemsetAsync(h->slots, 0, n_slot * 3 * sizeof(double), sp_stream));
-    h->slots_first_bin = cover;
+    if (const int st = ensure_slots(cover, sp_stream))
+      return st;
     eqlb::SeArgs as = a;
     if ((h->mode == 1 && h->k <= 3) || (h->fused && h->solver == EQLB_SOLVER_SHUFFLE && h->k <= 3))
     {
@@ -1849,6 +1998,9 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
         if (evs && first_bin == 0)
           HIP_TRY(hipEventRecord(evs[2 * b + 1], sp_stream));
       }
+    if (h->l_npatch > 0 && !rest)
+      if (const int st = run_large(sp_stream))
+        return st;
     if (h->stress)
     {
       // weak symmetry of rows 0, 1 on the patch-local stresses held in the slots
@@ -2008,6 +2160,27 @@ static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const doub
       }
     if (evs)
       HIP_TRY(hipEventRecord(evs[1], stream));
+    if (h->l_npatch > 0 && with_first_range)
+    {
+      // The tiles treat the node of a large patch like a masked node (TileDesc::zero): its rows are missing from what
+      // they wrote.  The large-patch kernel puts them into the slot buffer - every other row of it is zero - and a
+      // compact reduction over the cells of those patches (EV: the conforming reduction) ADDS them behind the tiles.
+      // (EV: k_ev_reduce runs over the whole mesh - 3 nrt doubles per cell and right-hand side, zeros but for the hub's
+      // cells, correct and in fixed order; a conforming reduction over l_cells and their facets is the follow-up)
+      if (const int st = ensure_slots(eqlb::MAX_BINS, stream))
+        return st;
+      if (const int st = run_large(stream))
+        return st;
+      for (int r = 0; r < h->nrhs; ++r)
+      {
+        const double* sl = h->slots + (size_t)r * s_slot * 3;
+        if (ev_conf)
+          eqlb::launch_ev_reduce(m, h->k, 1, h->ev_cell_dofs, h->ev_ndofs, sl, d_x[r], 1, h->ev_basis,
+                                 (h->ev_basis && h->ev_basis_has_R) ? h->ev_basis + h->nrt * h->nrt : nullptr, stream);
+        else if (eqlb::launch_reduce_slots_cells(h->nrt, m.ncells, h->l_ncells, h->l_cells, sl, d_x[r], stream))
+          return fail(EQLB_ERR_UNSUPPORTED, "compact slot reduction for %d DOFs per cell is not in this build", h->nrt);
+      }
+    }
     if (rest_now)
     {
       HIP_TRY(hipStreamWaitEvent(stream, h->ev_join, 0));
@@ -2147,13 +2320,15 @@ int eqlb_se_check_status(eqlb_se_t* h, void* stream_)
 
 double eqlb_se_last_kernel_ms(const eqlb_se_t* h, int32_t which)
 {
-  // which = b (0..4): patch kernel of bin b (P = 4 << b); 5: slot reduction; 6: weak-symmetry kernels.
+  // which = b (0..4): patch kernel of bin b (P = 4 << b); 5: slot reduction; 6: weak-symmetry kernels; 7: large-patch kernel.
   // Average device time per launch over the calls recorded since timing was enabled
   // (at most the last EV_RING calls).  Synchronises with the recorded events.
-  if (!h || !h->ev || h->ev_calls == 0 || which < 0 || which > eqlb::MAX_BINS + 1)
+  if (!h || !h->ev || h->ev_calls == 0 || which < 0 || which > eqlb::MAX_BINS + 2)
     return 0.0;
   if (which == eqlb::MAX_BINS + 1 && !h->stress)
     return 0.0;
+  if (which == eqlb::MAX_BINS + 2 && (h->l_npatch == 0 || h->scatter_last == EQLB_SCATTER_ATOMIC))
+    return 0.0; // 7: the large-patch kernel (all right-hand sides of a call)
   const bool fused_run = (h->mode == 1 && h->k <= 3) || h->scatter_last == EQLB_SCATTER_TILED
                          || (h->fused && h->solver == EQLB_SOLVER_SHUFFLE && h->k <= 3);
   if (which < eqlb::MAX_BINS && ((fused_run && which != 0) || (!fused_run && h->bins[which].npatch == 0)))
@@ -2615,7 +2790,7 @@ int eqlb_ev_set_option(eqlb_ev_t* h, const char* key, int32_t value)
     return EQLB_OK;
   }
   if (!strcmp(key, "timing") || !strcmp(key, "scatter") || !strcmp(key, "accumulate") || !strcmp(key, "tile_cells")
-      || !strcmp(key, "multi_rhs"))
+      || !strcmp(key, "multi_rhs") || !strcmp(key, "large_patches"))
     return eqlb_se_set_option(h->se, key, value);
   return fail(EQLB_ERR_INVALID_ARGUMENT, "unknown option '%s'", key);
 }
@@ -2809,6 +2984,13 @@ int eqlb_ev_check_status(eqlb_ev_t* h, void* stream)
 double eqlb_ev_last_kernel_ms(const eqlb_ev_t* h, int32_t which)
 {
   return h ? eqlb_se_last_kernel_ms(h->se, which) : 0.0;
+}
+
+int eqlb_ev_large_patch_info(const eqlb_ev_t* h, int64_t* npatches, int32_t* max_cells)
+{
+  if (!h)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_large_patch_info: null handle");
+  return eqlb_se_large_patch_info(h->se, npatches, max_cells);
 }
 
 int eqlb_ev_tiling_blocks(const eqlb_ev_t* h, int64_t* out, int32_t n)

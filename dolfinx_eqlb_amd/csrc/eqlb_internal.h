@@ -212,6 +212,9 @@ struct BuildArgs
   int32_t stride;
   int32_t *ex_ncells, *ex_cells, *ex_fcts;
   int8_t *ex_fl, *ex_il, *ex_rev;
+  // 1: fans of any length are walked (large-patch SoA, export of a handle with "large_patches"); pn may then be
+  // nullptr (the CSR offsets of that SoA hold the cell counts, a uint8_t would wrap at 256)
+  int32_t large;
 };
 
 void launch_build_patches(const BuildArgs& a, hipStream_t stream);
@@ -243,6 +246,12 @@ void launch_tile_facet_owner(const DeviceMesh& m, int64_t n, const int32_t* tile
 int tile_cells_of(int k);
 int tile_cells_ev_of(int k);
 int tile_cells_max_of(int k);
+// patches of more than 63 cells / 64 facets, one workgroup per patch (eqlb_se_large.hip): a.slot_cell / slot_info /
+// pflag / npatch_total address the large-patch SoA, off its CSR offsets [npatch + 1], a.out the slot buffer;
+// ws: large_patch_ws_doubles(k, lane slots, patches) doubles of work space
+int launch_se_patch_large(int k, int deg, int mode, const SeArgs& a, const int32_t* off, double* ws,
+                          hipStream_t stream);
+size_t large_patch_ws_doubles(int k, int64_t nslots, int64_t npatch);
 int launch_se_weaksym(int k, int P, bool no_flux_bcs, const SeArgs& a, hipStream_t stream);
 // RT_4 with P >= 16 and RT_3 with P = 64 (banded chain + border, eqlb_se_weaksym_banded.hip)
 int launch_se_weaksym_banded(int k, int P, const SeArgs& a, hipStream_t stream);
@@ -394,6 +403,18 @@ struct eqlb_se
   std::vector<int32_t> prio_cells;
   int32_t t_nprio = 0;              // number of priority tiles
   int32_t tile_first = 0, tile_count = -1; // options "tile_first" / "tile_count" (-1: to the end)
+  // patches of more than 63 cells or more than 64 facets (option "large_patches"): a CSR-style SoA of their own,
+  // outside the five lanes-per-patch bins; k_se_patch_large writes their rows into the slot buffer
+  int large_patches = 0;            // option "large_patches"
+  int64_t l_npatch = 0, l_nslots = 0;
+  int32_t l_maxcells = 0;
+  int32_t* l_off = nullptr;         // [l_npatch + 1] first lane slot of the patch
+  int32_t* l_slot_cell = nullptr;   // [l_nslots]
+  uint32_t* l_slot_info = nullptr;  // [l_nslots]
+  uint8_t* l_pflag = nullptr;       // [nrhs][l_npatch]
+  int32_t* l_cells = nullptr;       // cells with a vertex whose patch is a large one (compact reduction)
+  int64_t l_ncells = 0;
+  double* l_ws = nullptr;           // work space of k_se_patch_large
   double* slots = nullptr;          // [nrhs][ncells][3][nrt]
   int slots_first_bin = 0;          // the slot rows of the bins >= this one hold values of the last slot-path run
   int32_t* status = nullptr;
@@ -401,7 +422,7 @@ struct eqlb_se
   double *d_flux_dg = nullptr, *d_rhs_dg = nullptr, *d_flux_hdiv = nullptr;
   double *d_cks = nullptr, *d_korn = nullptr; // Korn estimate: per node / staging per cell
   // timing ("timing" option): ring of event sets, one set per equilibrate call
-  static constexpr int EV_RING = 64, EV_PER_SET = 2 * eqlb::MAX_BINS + 4;
-  hipEvent_t* ev = nullptr; // [EV_RING][EV_PER_SET]: bin b start/end at 2b, 2b+1; reduce start/end; weak symmetry start/end
+  static constexpr int EV_RING = 64, EV_PER_SET = 2 * eqlb::MAX_BINS + 6;
+  hipEvent_t* ev = nullptr; // [EV_RING][EV_PER_SET]: bin b start/end at 2b, 2b+1; reduce start/end; weak symmetry start/end; large-patch kernel start/end
   int64_t ev_calls = 0;     // calls recorded since timing was (re)enabled
 };

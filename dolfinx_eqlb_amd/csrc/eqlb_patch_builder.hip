@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256) k_build_patches(BuildArgs a)
       a.ex_rev[2 * exo + 2 * i + 1] = -1;
     }
   }
-  if (n < 2 || n + 2 > 65 || (ex && n + 2 > a.stride))
+  if (n < 2 || (n + 2 > 65 && !a.large) || (ex && n + 2 > a.stride))
     return; // rejected on the host (EQLB_ERR_PATCH_TOO_SMALL / _TOO_LARGE)
 
   // --- start facet (Patch.cpp:425-484): interior -> first facet of the node; boundary ->
@@ -215,7 +215,8 @@ __global__ void __launch_bounds__(256) k_build_patches(BuildArgs a)
 
   if (patch >= 0)
   {
-    a.pn[patch] = (uint8_t)n;
+    if (a.pn)
+      a.pn[patch] = (uint8_t)n;
     const int32_t fct_n = fct; // boundary: E_n
     for (int r = 0; r < a.nrhs; ++r)
     {

@@ -2626,6 +2626,12 @@ int launch_reduce_slots_cells(int nrt, int32_t ncells, int64_t nlist, const int3
   const int64_t grid = (ntotal + block - 1) / block;
   if (nrt == 8)
     hipLaunchKernelGGL(k_reduce_slots_cells<8>, dim3(grid), dim3(block), 0, stream, ntotal, cells, slots, x);
+  else if (nrt == 3) // (RT_1, RT_3, RT_4: the rows of the large patches behind a tiled launch)
+    hipLaunchKernelGGL(k_reduce_slots_cells<3>, dim3(grid), dim3(block), 0, stream, ntotal, cells, slots, x);
+  else if (nrt == 15)
+    hipLaunchKernelGGL(k_reduce_slots_cells<15>, dim3(grid), dim3(block), 0, stream, ntotal, cells, slots, x);
+  else if (nrt == 24)
+    hipLaunchKernelGGL(k_reduce_slots_cells<24>, dim3(grid), dim3(block), 0, stream, ntotal, cells, slots, x);
   else
     return EQLB_ERR_UNSUPPORTED;
   return 0;

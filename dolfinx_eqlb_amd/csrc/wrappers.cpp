@@ -314,7 +314,9 @@ struct BoundaryData
   std::vector<double> basis_C, basis_R;
   int se_degree_dg = -1;
   int ev_degree_dg = -1;
-  std::vector<std::pair<std::string, int>> ev_options; // re-applied when the EV handle is rebuilt for another degree
+  // options set through set_option: applied behind eqlb_*_create and before eqlb_*_set_boundary, so they also reach
+  // a handle that does not exist yet or is rebuilt for another degree ("large_patches" acts in set_boundary)
+  std::vector<std::pair<std::string, int>> se_options, ev_options;
 
   BoundaryData(std::vector<std::vector<std::shared_ptr<FluxBC>>>& list_bcs,
                std::vector<std::shared_ptr<Function>>& bflux, std::shared_ptr<FunctionSpace> V_, bool rt_custom,
@@ -449,9 +451,20 @@ struct BoundaryData
     eqlb_se_destroy(se);
     se = nullptr;
     check(eqlb_se_create(mesh->h, k, degree_dg, nrhs, stress ? 1 : 0, 0, &se));
+    try
+    {
+      for (const auto& o : se_options)
+        check(eqlb_se_set_option(se, o.first.c_str(), o.second));
+      check(eqlb_se_set_boundary(se, facet_type.data(), boundary_values.empty() ? nullptr : boundary_values.data(),
+                                 nullptr));
+    }
+    catch (...)
+    {
+      eqlb_se_destroy(se); // no handle without boundary data is kept
+      se = nullptr;
+      throw;
+    }
     se_degree_dg = degree_dg;
-    check(eqlb_se_set_boundary(se, facet_type.data(), boundary_values.empty() ? nullptr : boundary_values.data(),
-                               nullptr));
     return se;
   }
   eqlb_ev_t* ev_handle(int degree_dg)
@@ -464,19 +477,28 @@ struct BoundaryData
     eqlb_ev_destroy(ev);
     ev = nullptr;
     check(eqlb_ev_create_dg(mesh->h, k, degree_dg, nrhs, &ev));
-    ev_degree_dg = degree_dg;
-    for (const auto& o : ev_options)
-      check(eqlb_ev_set_option(ev, o.first.c_str(), o.second));
-    if (!V->cell_dofs.empty())
-      check(eqlb_ev_set_dofmap(ev, V->cell_dofs.data(), V->ndofs_user));
-    if (!basis_C.empty())
+    try
     {
-      // the boundary DOFs of this object are facet moments, i.e. hierarchic DOFs: the library converts them
-      check(eqlb_ev_set_basis_transform(ev, basis_C.data(), basis_R.empty() ? nullptr : basis_R.data()));
-      check(eqlb_ev_set_option(ev, "boundary_basis", 1));
+      for (const auto& o : ev_options)
+        check(eqlb_ev_set_option(ev, o.first.c_str(), o.second));
+      if (!V->cell_dofs.empty())
+        check(eqlb_ev_set_dofmap(ev, V->cell_dofs.data(), V->ndofs_user));
+      if (!basis_C.empty())
+      {
+        // the boundary DOFs of this object are facet moments, i.e. hierarchic DOFs: the library converts them
+        check(eqlb_ev_set_basis_transform(ev, basis_C.data(), basis_R.empty() ? nullptr : basis_R.data()));
+        check(eqlb_ev_set_option(ev, "boundary_basis", 1));
+      }
+      check(eqlb_ev_set_boundary(ev, facet_type.data(), boundary_values.empty() ? nullptr : boundary_values.data(),
+                                 nullptr));
     }
-    check(eqlb_ev_set_boundary(ev, facet_type.data(), boundary_values.empty() ? nullptr : boundary_values.data(),
-                               nullptr));
+    catch (...)
+    {
+      eqlb_ev_destroy(ev); // no handle without boundary data is kept
+      ev = nullptr;
+      throw;
+    }
+    ev_degree_dg = degree_dg;
     return ev;
   }
   // Output basis of the conforming flux (eqlb_ev_set_basis_transform): C [k(k+2)]^2 from the hierarchic
@@ -500,20 +522,63 @@ struct BoundaryData
     }
     eqlb_ev_destroy(ev); // rebuilt with the new basis on the next call
     ev = nullptr;
-    ev_options.clear();
+    // (the options of the old handle go with it, except the one that decides whether the new one can be built)
+    ev_options.erase(std::remove_if(ev_options.begin(), ev_options.end(),
+                                    [](const std::pair<std::string, int>& o) { return o.first != "large_patches"; }),
+                     ev_options.end());
   }
   void set_option(const std::string& key, int value)
   {
+    // The option is checked at once - on the handle if there is one, else on a throw-away handle - and only a valid
+    // one is kept (one entry per key) for handles created or rebuilt later.  "large_patches" acts in
+    // eqlb_*_set_boundary: an existing handle is dropped and rebuilt with it on the next call.
+    const bool rebuild = key == "large_patches";
+    auto keep = [&](std::vector<std::pair<std::string, int>>& opts) {
+      for (auto& o : opts)
+        if (o.first == key)
+        {
+          o.second = value;
+          return;
+        }
+      opts.emplace_back(key, value);
+    };
     if (custom)
     {
-      if (!se)
-        throw std::runtime_error("BoundaryData.set_option: no handle yet (options apply after the first call)");
-      check(eqlb_se_set_option(se, key.c_str(), value));
+      if (se)
+        check(eqlb_se_set_option(se, key.c_str(), value));
+      else
+      {
+        eqlb_se_t* tmp = nullptr;
+        check(eqlb_se_create(mesh->h, k, k - 1, 1, 0, 0, &tmp));
+        const int st = eqlb_se_set_option(tmp, key.c_str(), value);
+        eqlb_se_destroy(tmp);
+        check(st);
+      }
+      keep(se_options);
+      if (se && rebuild)
+      {
+        eqlb_se_destroy(se);
+        se = nullptr;
+      }
     }
     else
     {
-      check(eqlb_ev_set_option(ev_handle(ev ? ev_degree_dg : k - 1), key.c_str(), value));
-      ev_options.emplace_back(key, value);
+      if (ev)
+        check(eqlb_ev_set_option(ev, key.c_str(), value));
+      else
+      {
+        eqlb_ev_t* tmp = nullptr;
+        check(eqlb_ev_create_dg(mesh->h, k, k - 1, 1, &tmp));
+        const int st = eqlb_ev_set_option(tmp, key.c_str(), value);
+        eqlb_ev_destroy(tmp);
+        check(st);
+      }
+      keep(ev_options);
+      if (ev && rebuild)
+      {
+        eqlb_ev_destroy(ev);
+        ev = nullptr;
+      }
     }
   }
 };

@@ -22,7 +22,10 @@ class FluxEqlbEV:
     """Equilibrate fluxes by a series of constrained minimisation problems."""
 
     def __init__(self, degree_flux: int, msh: Mesh, list_rhs: typing.List[np.ndarray],
-                 list_proj_flux: typing.List[np.ndarray]):
+                 list_proj_flux: typing.List[np.ndarray], large_patches: bool = False):
+        # large_patches (not in the reference, which has no limit): vertex patches of more than 63 cells run on the
+        # library's large-patch kernel (option "large_patches", RT_1 ... RT_3) instead of being refused
+        self.large_patches = bool(large_patches)
         self.degree_flux = degree_flux
         self.n_fluxes = len(list_rhs)
         self.equilibrate_stresses = False  # FluxEqlbEV.py:43
@@ -63,6 +66,8 @@ class FluxEqlbEV:
         self.list_bfunctions = [np.zeros(self.ndofs) for _ in range(self.n_fluxes)]
         self.boundary_data = boundarydata(list_bcs_flux, self.list_bfunctions, self.V_flux, False,
                                           list_bfct_prime, self.equilibrate_stresses)
+        if self.large_patches:
+            self.boundary_data.set_option("large_patches", 1)
         self.facet_type = self.boundary_data.facet_type
 
     def equilibrate_fluxes(self):

@@ -23,7 +23,11 @@ class FluxEqlbSE:
     def __init__(self, degree_flux: int, msh: Mesh, list_rhs: typing.List[np.ndarray],
                  list_proj_flux: typing.List[np.ndarray],
                  equilibrate_stress: typing.Optional[bool] = False,
-                 estimate_korn_constant: typing.Optional[bool] = False):
+                 estimate_korn_constant: typing.Optional[bool] = False,
+                 large_patches: bool = False):
+        # large_patches (not in the reference, which has no limit): vertex patches of more than 63 cells run on the
+        # library's large-patch kernel (option "large_patches") instead of being refused
+        self.large_patches = bool(large_patches)
         self.degree_flux = degree_flux
         self.n_fluxes = len(list_rhs)
         self.equilibrate_stresses = bool(equilibrate_stress)
@@ -73,6 +77,8 @@ class FluxEqlbSE:
         self.list_bfunctions = [np.zeros(self.list_flux.shape[1]) for _ in range(self.n_fluxes)]
         self.boundary_data = boundarydata(list_bcs_flux, self.list_bfunctions, self.V_flux, True,
                                           list_bfct_prime, self.equilibrate_stresses)
+        if self.large_patches:
+            self.boundary_data.set_option("large_patches", 1)
         self.facet_type = self.boundary_data.facet_type
 
     def equilibrate_fluxes(self):

@@ -31,7 +31,9 @@ extern "C" {
 #define EQLB_ERR_UNSUPPORTED (-3)      /* configuration outside this build: k > 4, or an option / path the handle does
                                           not offer */
 #define EQLB_ERR_DEVICE (-4)           /* HIP runtime failure / no device */
-#define EQLB_ERR_PATCH_TOO_LARGE (-5)  /* patch with more than 63 cells (one wavefront per patch) */
+#define EQLB_ERR_PATCH_TOO_LARGE (-5)  /* patch with more than 63 cells or more than 64 facets on a handle without the \
+                                         option "large_patches" (one wavefront per patch); with the option: on a     \
+                                         stress handle and on an EV handle at RT_4, which stay limited to 63 cells   */
 #define EQLB_ERR_SINGULAR (-6)         /* patch system not positive definite (incompatible data) */
 #define EQLB_ERR_NO_MEMORY (-7)        /* host allocation failed during set-up */
 
@@ -124,7 +126,15 @@ void eqlb_se_destroy(eqlb_se_t* handle);
  * atomic scatter), "tile_cells" (cells per tile of the tiled launch, 0 = automatic; capped by the LDS of a
  * workgroup; applies to the next eqlb_se_set_boundary - a tuning knob), "multi_rhs" (1, default: the tiled
  * launch sweeps all right-hand sides of a call - the reference loops them inside the patch,
- * se/solve_patch_semiexplt.hpp:1040-1075; 0: one launch per right-hand side). */
+ * se/solve_patch_semiexplt.hpp:1040-1075; 0: one launch per right-hand side), "large_patches" (0, default: a
+ * vertex with more than 63 cells or more than 64 patch facets makes eqlb_se_set_boundary fail with
+ * EQLB_ERR_PATCH_TOO_LARGE; 1: from the next eqlb_se_set_boundary on such patches are equilibrated by a kernel of
+ * their own, one workgroup per patch with its work space in device memory - no cap on the cells of a patch (the
+ * reference has none either, se/Patch.cpp:337-404); the lane slots of all large patches of a mesh are counted in 32
+ * bits.  Flux equilibration RT_1 ... RT_4 with every data degree, slot and tiled scatter; the atomic scatter is
+ * refused with EQLB_ERR_UNSUPPORTED when a large patch is present, a stress handle and eqlb_se_kornconst with
+ * EQLB_ERR_PATCH_TOO_LARGE.  On
+ * a mesh without such a patch the option changes nothing: the same launches, the same bits). */
 int eqlb_se_set_option(eqlb_se_t* handle, const char* key, int32_t value);
 
 /*
@@ -261,7 +271,8 @@ int eqlb_se_check_status(eqlb_se_t* handle, void* stream);
  * kernel `which` over the recorded calls: which = b in 0..4: patch kernel of the bin with
  * P = 4 << b lanes per patch (single-launch paths - tiled and fused - report in slot 0);
  * which = 5: slot-reduction kernel (0 on the tiled path); which = 6: the weak-symmetry kernels of a
- * stress equilibration (all bins together).  Synchronises with the events;
+ * stress equilibration (all bins together); which = 7: the kernel of the large patches (option
+ * "large_patches"; all right-hand sides of a call).  Synchronises with the events;
  * 0 if nothing was recorded.  Setting the option again resets the ring. */
 double eqlb_se_last_kernel_ms(const eqlb_se_t* handle, int32_t which);
 
@@ -439,6 +450,12 @@ int eqlb_se_tiling_info(const eqlb_se_t* handle, int64_t* ntiles, int64_t* cells
 #define EQLB_TB_COUNT (EQLB_TB_ZERO_TILES + 1)
 int eqlb_se_tiling_blocks(const eqlb_se_t* handle, int64_t* out, int32_t n);
 
+/* Patches that the last eqlb_se_set_boundary handed to the large-patch kernel (option "large_patches"): their number
+ * and the cells of the largest one; 0 / 0 without the option, without such a patch or with its node masked out.
+ * Either pointer may be NULL.  eqlb_ev_large_patch_info: the same for an EV handle.  eqlb_se_num_patches /
+ * eqlb_ev_num_patches count the patches of the lanes-per-patch bins only: add npatches for all patches. */
+int eqlb_se_large_patch_info(const eqlb_se_t* handle, int64_t* npatches, int32_t* max_cells);
+
 /* ---------------------------------------------------------------------------------------------
  * Constrained-minimisation equilibrator (Ern & Vohralik) - replaces
  * `reconstruct_fluxes_minimisation(a, l_pen, l, flux_hdiv, boundary_data)`
@@ -468,7 +485,8 @@ void eqlb_ev_destroy(eqlb_ev_t* handle);
 
 /* "output": 0 conforming DOFs (default), 1 broken hierarchic RT_k layout [ncells*k(k+2)] as
  * eqlb_se_equilibrate writes it; "timing", "scatter" (EQLB_SCATTER_AUTO / _SLOTS / _TILED),
- * "accumulate": as eqlb_se_set_option; "boundary_basis": 0 (default) the boundary values of
+ * "accumulate", "multi_rhs", "tile_cells", "large_patches" (RT_1 ... RT_3; at RT_4 a patch of more than 63 cells
+ * stays refused): as eqlb_se_set_option; "boundary_basis": 0 (default) the boundary values of
  * eqlb_ev_set_boundary are DOFs of the output basis (eqlb_ev_set_basis_transform), 1 they are DOFs of the
  * conforming hierarchic RT_k whatever the output basis (what a caller has who computes the facet moments
  * int_E g s^j itself; set before eqlb_ev_set_boundary). */
@@ -511,6 +529,7 @@ int64_t eqlb_ev_num_patches(const eqlb_ev_t* handle);
 /* which = 0: patch kernel (all bins in one launch), 5: reduction to the conforming DOFs */
 double eqlb_ev_last_kernel_ms(const eqlb_ev_t* handle, int32_t which);
 int eqlb_ev_tiling_blocks(const eqlb_ev_t* handle, int64_t* out, int32_t n); /* as eqlb_se_tiling_blocks */
+int eqlb_ev_large_patch_info(const eqlb_ev_t* handle, int64_t* npatches, int32_t* max_cells); /* as eqlb_se_large_patch_info */
 int eqlb_ev_check_status(eqlb_ev_t* handle, void* stream); /* as eqlb_se_check_status */
 
 #ifdef __cplusplus
