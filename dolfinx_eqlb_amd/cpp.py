@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_se_tiling_blocks", "eqlb_ev_tiling_blocks", "eqlb_ev_create_dg",
     "eqlb_se_estimate_dg", "eqlb_ev_estimate_dg", "eqlb_oscillation_dg", "eqlb_boundary_residual",
     "eqlb_se_large_patch_info", "eqlb_ev_large_patch_info",
+    "eqlb_indicator_total", "eqlb_mark_doerfler",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -571,6 +572,51 @@ def boundary_residual_raw(dmesh: DeviceMesh, k: int, degree_dg: int, nrhs: int, 
     _check(lib().eqlb_boundary_residual(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), _vp(flux),
                                         _vp(flux_dg), C.c_int32(nfacets_bc), _vp(facets), _vp(boundary_values),
                                         _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def indicator_total(terms, pair_last_two=False):
+    """eqlb_indicator_total on host arrays: terms [nterms, ncells] squared cell-wise estimator terms (1 ... 8 of
+    them).  Returns (cell_eta2 [ncells], totals [nterms + 1]): the sum of the terms per cell - with pair_last_two
+    the last two enter as (sqrt a + sqrt b)^2 - and the sums over the cells of every term, then of cell_eta2
+    (eqlb.marking.indicator_total is the numpy statement)."""
+    t = [np.ascontiguousarray(v, dtype=np.float64).ravel() for v in terms]
+    if not t or any(v.size != t[0].size for v in t):
+        raise RuntimeError("Equilibration: Input sizes does not match")
+    ncells = t[0].size
+    eta2, totals = np.zeros(ncells), np.zeros(len(t) + 1)
+    indicator_total_raw(ncells, [v.ctypes.data for v in t], pair_last_two, _hp(eta2), _hp(totals), MEM_HOST)
+    return eta2, totals
+
+
+def indicator_total_raw(ncells: int, terms, pair_last_two, cell_eta2, totals, memspace=MEM_DEVICE, stream=0):
+    """eqlb_indicator_total on raw pointers (ints; None for an output that is not wanted) in `memspace`, ordered on
+    `stream`: terms is a sequence of pointers to [ncells] arrays, totals [len(terms) + 1] lies in `memspace` too."""
+    ptrs = (C.c_void_p * max(len(terms), 1))(*[p.value if isinstance(p, C.c_void_p) else p for p in terms])
+    _check(lib().eqlb_indicator_total(C.c_int64(ncells), C.c_int32(len(terms)), ptrs,
+                                      C.c_int32(1 if pair_last_two else 0), _vp(cell_eta2), _vp(totals),
+                                      C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def mark_doerfler(cell_eta2, theta: float):
+    """eqlb_mark_doerfler on a host array of non-negative indicators [ncells].  Returns (marked, eta2_total): the
+    sorted int32 ids of the shortest list of cells, largest indicators first and equal ones in ascending id, whose
+    sum exceeds theta * eta2_total (every cell if theta is 1 within 1e-8), and the sum of the indicators.  The
+    list goes to the refiner as it is, e.g. mesh.compute_incident_entities(mesh, marked, 2, 1)
+    (eqlb.doerfler_marking is the numpy statement)."""
+    eta = np.ascontiguousarray(cell_eta2, dtype=np.float64).ravel()
+    marked = np.empty(max(eta.size, 1), dtype=np.int32)
+    nmarked, total = C.c_int64(0), C.c_double(0.0)
+    mark_doerfler_raw(eta.size, _hp(eta), theta, _hp(marked), C.addressof(nmarked), C.addressof(total), MEM_HOST)
+    return marked[:nmarked.value].copy(), float(total.value)
+
+
+def mark_doerfler_raw(ncells: int, cell_eta2, theta: float, marked, nmarked, eta2_total, memspace=MEM_DEVICE,
+                      stream=0):
+    """eqlb_mark_doerfler on raw pointers (ints; eta2_total may be None) in `memspace`, ordered on `stream`:
+    marked [ncells] int32, nmarked [1] int64 and eta2_total [1] double lie in `memspace` too.  Device memory: nothing
+    waits for the device; nmarked = -1 reports a negative or NaN indicator."""
+    _check(lib().eqlb_mark_doerfler(C.c_int64(ncells), _vp(cell_eta2), C.c_double(theta), _vp(marked), _vp(nmarked),
+                                    _vp(eta2_total), C.c_int32(memspace), C.c_void_p(stream)))
 
 
 def halo_pack(x_ptr, cells_ptr, buf_ptr, nrhs, nlist, nrt, ncells, clear=True, stream=0):

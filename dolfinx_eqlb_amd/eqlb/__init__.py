@@ -9,10 +9,13 @@ done by the HIP library behind dolfinx_eqlb_amd.cpp.
 from . import bcs as _bcs
 from . import FluxEqlbEV as _ev
 from . import FluxEqlbSE as _se
+from . import marking as _marking
 
 FluxEqlbSE = _se.FluxEqlbSE
 FluxEqlbEV = _ev.FluxEqlbEV
 fluxbc = _bcs.fluxbc
 boundarydata = _bcs.boundarydata
+# numpy statement of the marking rule of cpp.mark_doerfler (the device path)
+doerfler_marking = _marking.doerfler_marking
 
-__all__ = ("FluxEqlbSE", "FluxEqlbEV", "fluxbc", "boundarydata")
+__all__ = ("FluxEqlbSE", "FluxEqlbEV", "fluxbc", "boundarydata", "doerfler_marking")

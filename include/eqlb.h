@@ -367,6 +367,44 @@ int eqlb_boundary_residual(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int3
                            const double* flux_dg, int32_t nfacets_bc, const int32_t* facets,
                            const double* boundary_values, double* out, int32_t memspace, void* stream);
 
+/* Estimator total and cell-wise refinement indicator from squared cell-wise terms as the estimator entries above
+ * write them - the sums the reference takes on the host (demo/poisson/demo_error_estimation.py:115-123,
+ * demo/elasticity/demo_error_estimation.py:135-146).
+ *   terms [nterms] HOST array of pointers; terms[i] [ncells] in the memory space of the call, 1 <= nterms <= 8
+ *   pair_last_two   0: cell_eta2 = sum_i terms[i];  1 (needs nterms >= 2): the last two terms a, b enter as
+ *                   (sqrt a + sqrt b)^2 = a + b + 2 sqrt(a) sqrt(b)  (Leta_sig + Leta_osc + 2 sqrt(Leta_sig) sqrt(Leta_osc)),
+ *                   the terms before them are added as they are
+ *   cell_eta2 [ncells]      the indicator per cell, or NULL
+ *   totals    [nterms + 1]  sum over the cells of every term, then of cell_eta2, or NULL
+ * One streaming kernel plus a one-block reduction; the sums are built from per-thread partials in a fixed order
+ * (no floating-point atomics): the same input gives the same bits.  Device memory space: everything is enqueued on
+ * `stream`, nothing waits for the device, totals is written on the device.  Host memory space: staged, synchronous. */
+int eqlb_indicator_total(int64_t ncells, int32_t nterms, const double* const* terms, int32_t pair_last_two,
+                         double* cell_eta2, double* totals, int32_t memspace, void* stream);
+
+/* Doerfler marking as the reference's adaptive demos do it on the host (demo/poisson_adaptive/demo_lshape.py:216-242,
+ * demo_discont-coeff.py:339-365, demo/elasticity_adaptive/demo_cook.py:262-295): with the cells ordered by descending
+ * cell_eta2, mark the shortest prefix whose running sum is strictly greater than theta * sum(cell_eta2); every cell
+ * if no prefix exceeds it (all indicators zero; theta so close to 1 that rounding decides) or if
+ * |theta - 1| <= 1e-8 (the np.isclose(doerfler, 1.0) branch).
+ * Ties: the reference's order among equal values is unspecified (np.argsort); here EQUAL VALUES ARE TAKEN IN
+ * ASCENDING CELL ID, so of the cells equal to the threshold value the ones with the lowest ids are marked.
+ *   cell_eta2  [ncells]  non-negative indicators (-0.0 counts as 0)
+ *   marked     [ncells]  capacity ncells; the first nmarked entries receive the marked cell ids in ascending order
+ *                        (the reference's np.sort), the rest is not touched
+ *   nmarked    [1]       number of marked cells
+ *   eta2_total [1]       sum(cell_eta2), or NULL
+ * all in the memory space of the call.  No sort runs: the threshold value is found by a radix select on the bit
+ * pattern (16 passes of 4 bits, per-bucket counts and fp64 sums), the list is written by an ordered compaction.  Sums
+ * are reduced in a fixed order, so the result is bitwise reproducible; the device's summation order differs from the
+ * host loop's, so a running sum within rounding (ncells 2^-53 relative) of the cut-off may fall on either side.
+ * Errors: theta outside (0, 1 + 1e-8] or ncells < 1: EQLB_ERR_INVALID_ARGUMENT, nothing is launched or written.
+ * A negative or NaN indicator: host memory space: EQLB_ERR_INVALID_ARGUMENT naming the first such cell; device memory
+ * space: nmarked = -1 and marked is not touched (the first pass counts them; nothing is read out of range).
+ * Device memory space: everything is enqueued on `stream`, nothing waits for the device. */
+int eqlb_mark_doerfler(int64_t ncells, const double* cell_eta2, double theta, int32_t* marked, int64_t* nmarked,
+                       double* eta2_total, int32_t memspace, void* stream);
+
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the
  * partial sums of the ghost-cell rows are sent to the owning rank and added there.  DEVICE pointers:
