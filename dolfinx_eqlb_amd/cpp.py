@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_se_estimate_dg", "eqlb_ev_estimate_dg", "eqlb_oscillation_dg", "eqlb_boundary_residual",
     "eqlb_se_large_patch_info", "eqlb_ev_large_patch_info",
     "eqlb_indicator_total", "eqlb_mark_doerfler",
+    "eqlb_primal_flux_dg", "eqlb_primal_stress_dg", "eqlb_get_primal_table",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -617,6 +618,92 @@ def mark_doerfler_raw(ncells: int, cell_eta2, theta: float, marked, nmarked, eta
     waits for the device; nmarked = -1 reports a negative or NaN indicator."""
     _check(lib().eqlb_mark_doerfler(C.c_int64(ncells), _vp(cell_eta2), C.c_double(theta), _vp(marked), _vp(nmarked),
                                     _vp(eta2_total), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def _primal_sizes(p: int, degree_dg: int):
+    if p < 1 or p > 4 or degree_dg < 0 or degree_dg > 3:
+        raise RuntimeError(f"Local solver: degrees p = {p}, degree_dg = {degree_dg} outside 1 ... 4, 0 ... 3")
+    return (p + 1) * (p + 2) // 2, (degree_dg + 1) * (degree_dg + 2) // 2
+
+
+def _primal_op(op, nd, ndp):
+    if op is None:
+        return None
+    t = np.ascontiguousarray(op, dtype=np.float64)
+    if t.size != 2 * nd * ndp:
+        raise RuntimeError("Local solver: Input sizes does not match")
+    return t
+
+
+def get_primal_table(p: int, degree_dg: int):
+    """The built-in table PG<p,d> [2, nd_d, nd_p] of primal_flux_dg (eqlb_get_primal_table): DG_d DOFs of the
+    reference gradient of the P_p basis functions (tools/gen_tables.py: primal_table_exact)."""
+    ndp, nd = (p + 1) * (p + 2) // 2, (degree_dg + 1) * (degree_dg + 2) // 2
+    out = np.zeros(max(2 * nd * ndp, 1))
+    n = lib().eqlb_get_primal_table(C.c_int32(p), C.c_int32(degree_dg), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        raise RuntimeError(lib().eqlb_last_error().decode())
+    return out[:n].reshape(2, nd, ndp)
+
+
+def primal_flux_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, coeff=None, op=None):
+    """eqlb_primal_flux_dg on host arrays: the DG_{degree_dg}^2 DOFs of -coeff grad(u_h) for u_h in P_p given by
+    its cell dofmap cell_dofs [ncells, nd_p] and solution vectors u [nrhs, ndofs] (or [ndofs]); coeff [ncells]
+    or None (1); op [2, nd_d, nd_p] replaces the built-in table.  Returns [nrhs, ncells*nd_d*2]."""
+    m = dmesh.mesh
+    ndp, nd = _primal_sizes(p, degree_dg)
+    cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+    uu = np.ascontiguousarray(u, dtype=np.float64)
+    uu = uu.reshape(1, -1) if uu.ndim < 2 else uu.reshape(uu.shape[0], -1)
+    kc = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.float64)
+    if cd.size != m.ncells * ndp or uu.size == 0 or (kc is not None and kc.size != m.ncells):
+        raise RuntimeError("Local solver: Input sizes does not match")
+    t = _primal_op(op, nd, ndp)
+    out = np.zeros((uu.shape[0], m.ncells * nd * 2))
+    primal_flux_dg_raw(dmesh, p, degree_dg, uu.shape[0], _hp(cd), uu.shape[1], _hp(uu),
+                       _hp(kc) if kc is not None else None, _hp(out), t, MEM_HOST)
+    return out
+
+
+def primal_flux_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, nrhs: int, cell_dofs, ndofs: int, u, coeff,
+                       flux_dg, op=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_primal_flux_dg on raw pointers (ints; coeff may be None) in `memspace`, ordered on `stream`: cell_dofs
+    int32 [ncells, nd_p], u [nrhs, ndofs], flux_dg [nrhs, ncells*nd_d*2].  op is a host array or None.  Device
+    memory: one kernel, nothing waits for the device."""
+    t = None if op is None else np.ascontiguousarray(op, dtype=np.float64)
+    _check(lib().eqlb_primal_flux_dg(dmesh._h, C.c_int32(p), C.c_int32(degree_dg), C.c_int32(nrhs), _vp(cell_dofs),
+                                     C.c_int64(ndofs), _vp(u), _vp(coeff), _hp(t) if t is not None else None,
+                                     _vp(flux_dg), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def primal_stress_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, pi_1: float = 1.0, cell_pi1=None,
+                     op=None):
+    """eqlb_primal_stress_dg on host arrays: rows of -(2 eps(u_h) + pi_1 div(u_h) I) for the blocked displacement
+    u [ndofs, 2] in P_p^2 (scalar dofmap cell_dofs), pi_1 per cell where cell_pi1 [ncells] is given.  Returns
+    [2, ncells*nd_d*2]."""
+    m = dmesh.mesh
+    ndp, nd = _primal_sizes(p, degree_dg)
+    cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    kc = None if cell_pi1 is None else np.ascontiguousarray(cell_pi1, dtype=np.float64)
+    if cd.size != m.ncells * ndp or uu.size == 0 or uu.size % 2 or (kc is not None and kc.size != m.ncells):
+        raise RuntimeError("Local solver: Input sizes does not match")
+    t = _primal_op(op, nd, ndp)
+    out = np.zeros((2, m.ncells * nd * 2))
+    primal_stress_dg_raw(dmesh, p, degree_dg, _hp(cd), uu.size // 2, _hp(uu), pi_1,
+                         _hp(kc) if kc is not None else None, _hp(out), t, MEM_HOST)
+    return out
+
+
+def primal_stress_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, ndofs: int, u, pi_1: float, cell_pi1,
+                         flux_dg, op=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_primal_stress_dg on raw pointers (ints; cell_pi1 may be None) in `memspace`, ordered on `stream`:
+    u [ndofs, 2] blocked, flux_dg [2, ncells*nd_d*2]."""
+    t = None if op is None else np.ascontiguousarray(op, dtype=np.float64)
+    _check(lib().eqlb_primal_stress_dg(dmesh._h, C.c_int32(p), C.c_int32(degree_dg), _vp(cell_dofs),
+                                       C.c_int64(ndofs), _vp(u), C.c_double(pi_1), _vp(cell_pi1),
+                                       _hp(t) if t is not None else None, _vp(flux_dg), C.c_int32(memspace),
+                                       C.c_void_p(stream)))
 
 
 def halo_pack(x_ptr, cells_ptr, buf_ptr, nrhs, nlist, nrt, ncells, clear=True, stream=0):

@@ -1,0 +1,411 @@
+// Projected flux / stress of a P_p primal solution on the device - the step in front of the equilibration that the
+// reference writes in UFL: sigma_h = -grad(u_h), -k grad(u_h) with a cell-wise k (demo/poisson_adaptive/
+// demo_discont-coeff.py), 2 eps(u_h) + pi_1 div(u_h) I (demo/elasticity_adaptive/demo_cook.py), handed to
+// local_projection(V_flux_proj, [sigma_h]) (python/dolfinx_eqlb/lsolver/projection.py:17-77).
+//
+// Quadrature-free: on an affine cell grad u_h = K^T grad_X u_h with K = J^-1, and grad_X u_h lies in P_{p-1}^2 on the
+// reference cell, so its DG_d DOFs are ONE constant matrix per (p, d) applied to the DOFs of the cell,
+//   gref[n][X]    = sum_i PG<p,d>[X][n][i] u[cell_dofs[c][i]]        (tools/gen_tables.py: primal_table_exact)
+//   flux_dg[c][n] = -kappa_c K_c^T gref[n]
+// and for a displacement u = (u_0, u_1) with gu[r][d] = d_d u_r from the same gref per component:
+//   sigma = gu + gu^T + pi_1 tr(gu) I,   output row r = -sigma[r][:].
+//
+// k_primal_flux<P, D, STRESS>: a streaming gather kernel, one thread per cell, PF_THREADS cells per workgroup.
+//  - the index rows of the workgroup's cells are read as one contiguous piece and handed out through LDS, the table
+//    (a kernel argument: built-in or the caller's `op`) is staged in LDS once;
+//  - the 2 nd_d values of a cell are staged in LDS (row stride 2 nd_d + 1 doubles: an odd stride of 8-byte words, no
+//    bank conflict of the thread-per-row writes) and written as the contiguous piece of flux_dg the workgroup owns;
+//  - several right-hand sides reuse the index row, which stays in registers;
+//  - every gathered index is checked against [0, ndofs): a cell with a bad index writes NaN and reads nothing there.
+// The nd_p products of a contraction are rounded one by one, put in ascending order by a sorting network and added
+// from the smallest up.  The sum then depends on the SET of products only: a caller's table `op` whose columns are
+// permuted together with cell_dofs gives the same bits as the built-in one.  No atomics, no scratch, one fixed order
+// of operations per value: two runs give the same bits.
+#include "eqlb_device_common.h"
+#include "eqlb_tables_gen.h"
+#include <cmath>
+#include <cstring>
+
+#define fail eqlb::set_error
+
+namespace eqlb
+{
+
+constexpr int PF_THREADS = 256;
+constexpr int PF_PMAX = 4, PF_DMAX = 3;
+
+template <int P, int D>
+struct PrimalOp
+{
+  double v[2 * nd_of(D) * nd_of(P)]; // PG[X][n][i]
+};
+
+// Batcher's merge exchange for N keys (any N) as a list of compare-exchange pairs
+template <int N>
+struct SortNet
+{
+  int n;
+  int a[N * N + 1], b[N * N + 1];
+  constexpr SortNet() : n(0), a{}, b{}
+  {
+    for (int p = 1; p < N; p <<= 1)
+      for (int k = p; k >= 1; k >>= 1)
+        for (int j = k % p; j + k < N; j += 2 * k)
+          for (int i = 0; i < k && i + j + k < N; ++i)
+            if ((i + j) / (2 * p) == (i + j + k) / (2 * p))
+            {
+              a[n] = i + j;
+              b[n] = i + j + k;
+              ++n;
+            }
+  }
+};
+
+// sum of t[0 .. N) that does not depend on their order: ascending by the network, then added from the smallest up
+// (compare and select, not min / max: a NaN stays in the list and reaches the sum)
+template <int N>
+__device__ __forceinline__ double sorted_sum(double (&t)[N])
+{
+  constexpr SortNet<N> net{};
+#pragma unroll
+  for (int c = 0; c < net.n; ++c)
+  {
+    const double x = t[net.a[c]], y = t[net.b[c]];
+    const bool sw = y < x;
+    t[net.a[c]] = sw ? y : x;
+    t[net.b[c]] = sw ? x : y;
+  }
+  double s = t[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i)
+    s = __dadd_rn(s, t[i]);
+  return s;
+}
+
+template <int P, int D, bool STRESS>
+__global__ void __launch_bounds__(PF_THREADS)
+k_primal_flux(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __restrict__ cell_dofs,
+              const double* __restrict__ u, const double* __restrict__ cellJ, const double* __restrict__ coeff,
+              double pi_1, const PrimalOp<P, D> op, double* __restrict__ out)
+{
+  constexpr int NP = nd_of(P), ND = nd_of(D), ROW = 2 * ND, S = ROW + 1;
+  constexpr int NBUF = (PF_THREADS * S > (PF_THREADS * NP + 1) / 2) ? PF_THREADS * S : (PF_THREADS * NP + 1) / 2;
+  __shared__ double sPG[2 * ND * NP];
+  __shared__ double sbuf[NBUF]; // first the index rows of the workgroup, then its output rows
+  const int t = threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * PF_THREADS;
+  const int nloc = (ncells - base < PF_THREADS) ? (int)(ncells - base) : PF_THREADS;
+  const bool active = t < nloc;
+  for (int i = t; i < 2 * ND * NP; i += PF_THREADS)
+    sPG[i] = op.v[i];
+  int32_t* sidx = reinterpret_cast<int32_t*>(sbuf);
+  const int32_t* rows = cell_dofs + base * NP;
+  for (int e = t; e < nloc * NP; e += PF_THREADS)
+    sidx[e] = rows[e];
+  __syncthreads();
+  int32_t idx[NP];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < NP; ++i)
+  {
+    idx[i] = active ? sidx[t * NP + i] : 0;
+    ok = ok && idx[i] >= 0 && (int64_t)idx[i] < ndofs;
+  }
+  double K00 = 0.0, K01 = 0.0, K10 = 0.0, K11 = 0.0, kap = 1.0;
+  if (active)
+  {
+    const double2* Jp = reinterpret_cast<const double2*>(cellJ + 4 * (base + t));
+    const double2 r0 = Jp[0], r1 = Jp[1]; // J00 J01 | J10 J11
+    const double idet = 1.0 / (r0.x * r1.y - r0.y * r1.x);
+    K00 = r1.y * idet;
+    K01 = -r0.y * idet;
+    K10 = -r1.x * idet;
+    K11 = r0.x * idet;
+    if (coeff)
+      kap = coeff[base + t];
+    else if constexpr (STRESS)
+      kap = pi_1;
+  }
+  const double bad = __longlong_as_double(0x7ff8000000000000ll);
+  __syncthreads(); // the index rows are in registers: sbuf takes the output rows
+  if constexpr (!STRESS)
+  {
+    for (int r = 0; r < nrhs; ++r)
+    {
+      if (active)
+      {
+        const double* ur = u + (int64_t)r * ndofs;
+        double uu[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+          uu[i] = ok ? ur[idx[i]] : 0.0;
+#pragma unroll
+        for (int n = 0; n < ND; ++n)
+        {
+          double g[2];
+#pragma unroll
+          for (int X = 0; X < 2; ++X)
+          {
+            double tt[NP];
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+              tt[i] = __dmul_rn(sPG[(X * ND + n) * NP + i], uu[i]);
+            g[X] = sorted_sum<NP>(tt);
+          }
+          const double f0 = -kap * (K00 * g[0] + K10 * g[1]), f1 = -kap * (K01 * g[0] + K11 * g[1]);
+          sbuf[t * S + 2 * n] = ok ? f0 : bad;
+          sbuf[t * S + 2 * n + 1] = ok ? f1 : bad;
+        }
+      }
+      __syncthreads();
+      double* o = out + ((int64_t)r * ncells + base) * ROW;
+      for (int e = t; e < nloc * ROW; e += PF_THREADS)
+        o[e] = sbuf[(e / ROW) * S + (e % ROW)];
+      __syncthreads();
+    }
+  }
+  else
+  {
+    double val[2][ROW]; // rows of -sigma
+    if (active)
+    {
+      double uu[2][NP];
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+      {
+        const double2 w = ok ? reinterpret_cast<const double2*>(u)[idx[i]] : make_double2(0.0, 0.0);
+        uu[0][i] = w.x;
+        uu[1][i] = w.y;
+      }
+#pragma unroll
+      for (int n = 0; n < ND; ++n)
+      {
+        double gu[2][2]; // gu[r][d] = d_d u_r
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+        {
+          double g[2];
+#pragma unroll
+          for (int X = 0; X < 2; ++X)
+          {
+            double tt[NP];
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+              tt[i] = __dmul_rn(sPG[(X * ND + n) * NP + i], uu[r][i]);
+            g[X] = sorted_sum<NP>(tt);
+          }
+          gu[r][0] = K00 * g[0] + K10 * g[1];
+          gu[r][1] = K01 * g[0] + K11 * g[1];
+        }
+        const double ld = kap * (gu[0][0] + gu[1][1]), sh = gu[0][1] + gu[1][0];
+        val[0][2 * n] = ok ? -(2.0 * gu[0][0] + ld) : bad;
+        val[0][2 * n + 1] = ok ? -sh : bad;
+        val[1][2 * n] = ok ? -sh : bad;
+        val[1][2 * n + 1] = ok ? -(2.0 * gu[1][1] + ld) : bad;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+    {
+      if (active)
+      {
+#pragma unroll
+        for (int j = 0; j < ROW; ++j)
+          sbuf[t * S + j] = val[r][j];
+      }
+      __syncthreads();
+      double* o = out + ((int64_t)r * ncells + base) * ROW;
+      for (int e = t; e < nloc * ROW; e += PF_THREADS)
+        o[e] = sbuf[(e / ROW) * S + (e % ROW)];
+      __syncthreads();
+    }
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
+template <int P, int D>
+static void builtin_table(double* out)
+{
+  using T = eqlb_tables::Primal<P, D>;
+  for (int i = 0; i < 2 * T::ND * T::NP; ++i)
+    out[i] = T::PG[i];
+}
+
+template <int P, int D>
+static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
+                            const double* u, const double* cellJ, const double* coeff, double pi_1, const double* op,
+                            double* out, hipStream_t stream)
+{
+  PrimalOp<P, D> tab;
+  if (op)
+    std::memcpy(tab.v, op, sizeof(tab.v));
+  else
+    builtin_table<P, D>(tab.v);
+  const unsigned grid = (unsigned)(((int64_t)ncells + PF_THREADS - 1) / PF_THREADS);
+  if (stress)
+    hipLaunchKernelGGL((k_primal_flux<P, D, true>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs,
+                       cell_dofs, u, cellJ, coeff, pi_1, tab, out);
+  else
+    hipLaunchKernelGGL((k_primal_flux<P, D, false>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs,
+                       cell_dofs, u, cellJ, coeff, pi_1, tab, out);
+  return hipGetLastError();
+}
+
+template <int P>
+static hipError_t launch_p(int d, bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
+                           const double* u, const double* cellJ, const double* coeff, double pi_1, const double* op,
+                           double* out, hipStream_t stream)
+{
+  switch (d)
+  {
+  case 0:
+    return launch_pd<P, 0>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  case 1:
+    return launch_pd<P, 1>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  case 2:
+    return launch_pd<P, 2>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  default:
+    return launch_pd<P, 3>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  }
+}
+
+// all pointers but op DEVICE; enqueues on stream
+static hipError_t launch_primal_flux(int p, int d, bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs,
+                                     const int32_t* cell_dofs, const double* u, const double* cellJ,
+                                     const double* coeff, double pi_1, const double* op, double* out,
+                                     hipStream_t stream)
+{
+  switch (p)
+  {
+  case 1:
+    return launch_p<1>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  case 2:
+    return launch_p<2>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  case 3:
+    return launch_p<3>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  default:
+    return launch_p<4>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+  }
+}
+
+template <int P>
+static int table_p(int d, double* out)
+{
+  switch (d)
+  {
+  case 0:
+    builtin_table<P, 0>(out);
+    break;
+  case 1:
+    builtin_table<P, 1>(out);
+    break;
+  case 2:
+    builtin_table<P, 2>(out);
+    break;
+  default:
+    builtin_table<P, 3>(out);
+  }
+  return 2 * nd_of(d) * nd_of(P);
+}
+
+static size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// the common body of the two entry points; stress: u [ndofs][2], two output rows, coeff = cell_pi1
+static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32_t d, int32_t nrhs, bool stress,
+                            const int32_t* cell_dofs, int64_t ndofs, const double* u, const double* coeff,
+                            double pi_1, const double* op, double* flux_dg, int32_t memspace, void* stream_)
+{
+  if (p < 1 || p > PF_PMAX || d < 0 || d > PF_DMAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degrees p = %d, degree_dg = %d outside 1 ... 4, 0 ... 3", who, (int)p,
+                (int)d);
+  if (nrhs < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d", who, (int)nrhs);
+  if (!mesh || !cell_dofs || !u || !flux_dg || ndofs < 1 || ndofs > INT32_MAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid argument", who);
+  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  const DeviceMesh& m = mesh->m;
+  const int np = nd_of(p), nd = nd_of(d);
+  const int32_t ncells = m.ncells;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (memspace == EQLB_MEM_DEVICE)
+  {
+    const hipError_t e
+        = launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, cell_dofs, u, m.cellJ, coeff, pi_1, op, flux_dg, stream);
+    return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+  }
+  // host memory: bad tables are caught here, before anything is launched
+  const size_t nidx = (size_t)ncells * np;
+  for (size_t i = 0; i < nidx; ++i)
+    if (cell_dofs[i] < 0 || (int64_t)cell_dofs[i] >= ndofs)
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_dofs[%lld][%d] = %d outside [0, %lld)", who,
+                  (long long)(i / np), (int)(i % np), (int)cell_dofs[i], (long long)ndofs);
+  const size_t ib = pad256(sizeof(int32_t) * nidx), ub = pad256(sizeof(double) * (size_t)ndofs * (stress ? 2 : nrhs)),
+               cb = pad256(sizeof(double) * (size_t)ncells),
+               ob = sizeof(double) * (size_t)(stress ? 2 : nrhs) * ncells * nd * 2;
+  char* buf = nullptr;
+  if (hipMalloc((void**)&buf, ib + ub + cb + ob) != hipSuccess)
+    return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
+  int32_t* d_idx = (int32_t*)buf;
+  double* d_u = (double*)(buf + ib);
+  double* d_c = (double*)(buf + ib + ub);
+  double* d_out = (double*)(buf + ib + ub + cb);
+  hipError_t e = hipMemcpyAsync(d_idx, cell_dofs, sizeof(int32_t) * nidx, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_u, u, sizeof(double) * (size_t)ndofs * (stress ? 2 : nrhs), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && coeff)
+    e = hipMemcpyAsync(d_c, coeff, sizeof(double) * (size_t)ncells, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, d_idx, d_u, m.cellJ, coeff ? d_c : nullptr, pi_1, op,
+                           d_out, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(flux_dg, d_out, ob, hipMemcpyDeviceToHost, stream);
+  const hipError_t es = hipStreamSynchronize(stream);
+  (void)hipFree(buf);
+  if (e == hipSuccess)
+    e = es;
+  return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+}
+
+} // namespace eqlb
+
+extern "C" {
+
+int eqlb_primal_flux_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
+                        int64_t ndofs, const double* u, const double* cell_coeff, const double* op, double* flux_dg,
+                        int32_t memspace, void* stream)
+{
+  return eqlb::primal_flux_call("eqlb_primal_flux_dg", mesh, p, degree_dg, nrhs, false, cell_dofs, ndofs, u,
+                                cell_coeff, 1.0, op, flux_dg, memspace, stream);
+}
+
+int eqlb_primal_stress_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const int32_t* cell_dofs, int64_t ndofs,
+                          const double* u, double pi_1, const double* cell_pi1, const double* op, double* flux_dg,
+                          int32_t memspace, void* stream)
+{
+  return eqlb::primal_flux_call("eqlb_primal_stress_dg", mesh, p, degree_dg, 1, true, cell_dofs, ndofs, u, cell_pi1,
+                                pi_1, op, flux_dg, memspace, stream);
+}
+
+int eqlb_get_primal_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity)
+{
+  using namespace eqlb;
+  if (p < 1 || p > PF_PMAX || degree_dg < 0 || degree_dg > PF_DMAX || !out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_primal_table: degrees p = %d, degree_dg = %d outside 1 ... 4, 0 ... 3",
+                (int)p, (int)degree_dg);
+  if (capacity < 2 * nd_of(degree_dg) * nd_of(p))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_primal_table: capacity too small");
+  switch (p)
+  {
+  case 1:
+    return table_p<1>(degree_dg, out);
+  case 2:
+    return table_p<2>(degree_dg, out);
+  case 3:
+    return table_p<3>(degree_dg, out);
+  default:
+    return table_p<4>(degree_dg, out);
+  }
+}
+
+} // extern "C"

@@ -6,6 +6,7 @@ callables f(x, y) -> array [..., bs] (or [...] for bs = 1) evaluated at the phys
 points, or precomputed point values.
 """
 
+import dataclasses
 import typing
 
 import numpy as np
@@ -21,11 +22,70 @@ def quadrature_points_physical(mesh, qpoints):
     return x0[:, None, :] + np.einsum("cij,qj->cqi", J, qpoints)
 
 
+@dataclasses.dataclass
+class PrimalFlux:
+    """sigma_h = -coeff grad(u_h) of a conforming P_p solution as an entry of `data` of local_projection: u [ndofs],
+    cell_dofs [ncells, (p+1)(p+2)/2] (DOF transformations applied), coeff [ncells] or None.  Formed on the device
+    from the solution vector (cpp.primal_flux_dg), without quadrature."""
+    u: typing.Any
+    cell_dofs: typing.Any
+    p: int
+    coeff: typing.Any = None
+
+
+@dataclasses.dataclass
+class PrimalStress:
+    """Row `row` (0 or 1) of sigma_h = -(2 eps(u_h) + pi_1 div(u_h) I) of a displacement u [ndofs, 2] in P_p^2 as an
+    entry of `data` of local_projection (cpp.primal_stress_dg); pi_1 a number or an array [ncells]."""
+    u: typing.Any
+    cell_dofs: typing.Any
+    p: int
+    pi_1: typing.Any
+    row: int
+
+
+def _device_mesh(dmesh):
+    """The cpp.DeviceMesh behind `dmesh` (made once per flat mesh container and kept on it)."""
+    from .. import cpp
+    if isinstance(dmesh, cpp.DeviceMesh):
+        return dmesh
+    cached = getattr(dmesh, "_cpp_device_mesh", None)
+    if cached is None:
+        cached = cpp.DeviceMesh(dmesh)
+        try:
+            dmesh._cpp_device_mesh = cached
+        except AttributeError:
+            pass
+    return cached
+
+
+def _check_primal(mesh, bs, d):
+    ndp = (d.p + 1) * (d.p + 2) // 2
+    stress = isinstance(d, PrimalStress)
+    usize = np.size(d.u)
+    if (bs != 2 or np.size(d.cell_dofs) != mesh.ncells * ndp or usize == 0 or (stress and usize % 2)
+            or (stress and d.row not in (0, 1))):
+        raise RuntimeError("Local solver: Input sizes does not match")
+
+
+def _project_primal(dmesh, degree, d):
+    from .. import cpp
+    dm = _device_mesh(dmesh)
+    if isinstance(d, PrimalStress):
+        per_cell = np.ndim(d.pi_1) > 0
+        out = cpp.primal_stress_dg(dm, d.p, degree, d.cell_dofs, d.u, 1.0 if per_cell else float(d.pi_1),
+                                   d.pi_1 if per_cell else None)
+        return np.ascontiguousarray(out[d.row])
+    return cpp.primal_flux_dg(dm, d.p, degree, d.cell_dofs, np.asarray(d.u, dtype=np.float64).reshape(1, -1),
+                              d.coeff)[0]
+
+
 def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int = 1,
                      quadrature_degree: typing.Optional[int] = None,
                      solver: str = "cholesky") -> typing.List[np.ndarray]:
     """Project every entry of `data` into DG_degree (block size bs); returns the DOF arrays
-    [ncells*nd*bs] (cell-major, x[bs*dof+cb]).  data[i]: callable(x, y) or array [ncells, nq, bs].
+    [ncells*nd*bs] (cell-major, x[bs*dof+cb]).  data[i]: callable(x, y), array [ncells, nq, bs], or a PrimalFlux /
+    PrimalStress (bs = 2: the flux or a stress row of a P_p solution, formed on the device from its DOFs).
     `dmesh`: flat mesh container (or a `cpp.DeviceMesh` of one).  The solve runs through
     `local_solver_<solver>` of the compiled module (names of python/dolfinx_eqlb/wrappers.cpp:52-80):
     a = (u, v) on DG_degree, l_i = (f_i, v) given by the point values of f_i."""
@@ -35,9 +95,17 @@ def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int 
     qdeg = 2 * degree + 2 if quadrature_degree is None else quadrature_degree
     qp, qw = make_quadrature_triangle(qdeg)
     xq = None
-    V = _adapter.dg_space(mesh, degree, bs)
+    is_primal = [isinstance(d, (PrimalFlux, PrimalStress)) for d in data]
+    for d, pr in zip(data, is_primal):
+        if pr:
+            _check_primal(mesh, bs, d)
+    V = _adapter.dg_space(mesh, degree, bs) if not (data and all(is_primal)) else None
     sols, forms = [], []
-    for d in data:
+    primal = {}
+    for i, d in enumerate(data):
+        if is_primal[i]:
+            primal[i] = _project_primal(dmesh, degree, d)
+            continue
         if callable(d):
             if xq is None:
                 xq = quadrature_points_physical(mesh, qp)
@@ -49,8 +117,10 @@ def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int 
         forms.append(c.Form.from_point_values(qp, qw, np.ascontiguousarray(v.reshape(mesh.ncells, qw.size, bs))))
         sols.append(c.Function(V))
     fn = {"cholesky": c.local_solver_cholesky, "lu": c.local_solver_lu, "cg": c.local_solver_cg}[solver]
-    fn(sols, c.Form([]), forms)
-    return [s_.array for s_ in sols]
+    if V is not None:
+        fn(sols, c.Form([]), forms)
+    rest = iter(s_.array for s_ in sols)
+    return [primal[i] if i in primal else next(rest) for i in range(len(data))]
 
 
 def embed_dg(values, ncells: int, degree_from: int, degree_to: int, bs: int = 1):

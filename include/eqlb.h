@@ -232,6 +232,51 @@ int eqlb_project_dg(eqlb_mesh_t* mesh, int32_t degree, int32_t bs, int32_t nrhs,
                     const double* qpoints, const double* qweights, const double* qvalues,
                     double* out, int32_t memspace, void* stream);
 
+/*
+ * Projected flux of a conforming P_p primal solution, formed on the device from the solution vector: what the
+ * reference writes as sigma_h = -grad(u_h) (demo/poisson/demo_reconstruction.py) or -k grad(u_h) with a cell-wise k
+ * (demo/poisson_adaptive/demo_discont-coeff.py) and hands to local_projection(V_flux_proj, [sigma_h])
+ * (python/dolfinx_eqlb/lsolver/projection.py:17-77).  Quadrature-free and exact: on an affine cell
+ * grad u_h = K^T grad_X u_h, K = J^-1, and the DG_d DOFs of grad_X u_h are one constant matrix PG<p,d> (exact
+ * rationals, tools/gen_tables.py) applied to the DOFs of the cell:
+ *   flux_dg[r][c][n][:] = -cell_coeff[c] K_c^T sum_i PG[:][n][i] u[r][cell_dofs[c][i]]
+ * the nodal values of the gradient for degree_dg >= p-1, its L2 projection below.  1 <= p <= 4, 0 <= degree_dg <= 3.
+ *   cell_dofs  [ncells][nd_p] int32  the caller's cell dofmap of the P_p space with the DOF transformations applied
+ *                                    (interior edge DOFs ordered along the global edge direction), nd_p = (p+1)(p+2)/2
+ *   u          [nrhs][ndofs]         solution vectors
+ *   cell_coeff [ncells] or NULL      cell-wise coefficient (NULL: 1)
+ *   op         HOST, [2][nd_d][nd_p] row-major, or NULL: replaces the built-in PG<p,d>, whose P_p is the equispaced
+ *                                    Lagrange element in Basix numbering.  The hook for a caller whose P_p has another
+ *                                    node set or numbering - DOLFINx' GLL-warped variant at p >= 3, which cannot be
+ *                                    generated offline here: op[X][n][i] = DG_d DOF n of d/dX of the caller's basis
+ *                                    function i.  Read during the call, not retained.
+ *   flux_dg    [nrhs][ncells*nd_d*2] OVERWRITTEN, in the layout eqlb_se_equilibrate reads
+ * cell_dofs, u, cell_coeff and flux_dg lie in `memspace`, with the semantics of eqlb_se_equilibrate (device memory:
+ * one kernel on `stream`, nothing waits).  Each contraction adds its products in ascending order, so its result does
+ * not depend on the order of the columns of op / cell_dofs, and two runs give the same bits.
+ * Errors: p or degree_dg out of range, nrhs < 1: EQLB_ERR_INVALID_ARGUMENT.  An index outside [0, ndofs): host
+ * memory space: EQLB_ERR_INVALID_ARGUMENT before anything is launched; device memory space: the values of that cell
+ * are NaN, nothing is read out of range.
+ */
+int eqlb_primal_flux_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
+                        int64_t ndofs, const double* u, const double* cell_coeff, const double* op, double* flux_dg,
+                        int32_t memspace, void* stream);
+
+/* The same for a displacement u_h in P_p^2 and the stress of demo/elasticity_adaptive/demo_cook.py,
+ * sigma_h = 2 eps(u_h) + pi_1 div(u_h) I (local_projection of its rows, lsolver/projection.py:17-77):
+ *   u        [ndofs][2]  blocked displacement (x[2*dof + r]), cell_dofs the scalar dofmap as above
+ *   pi_1, cell_pi1 [ncells] or NULL  the ratio lambda / mu: per cell where cell_pi1 is given, else the scalar
+ *   flux_dg  [2][ncells*nd_d*2]  row r = -sigma_h[r][:], the two rows a stress handle takes as its first two
+ *                                right-hand sides
+ * Everything else as eqlb_primal_flux_dg. */
+int eqlb_primal_stress_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const int32_t* cell_dofs, int64_t ndofs,
+                          const double* u, double pi_1, const double* cell_pi1, const double* op, double* flux_dg,
+                          int32_t memspace, void* stream);
+
+/* The built-in table PG<p,d> [2][nd_d][nd_p] of eqlb_primal_flux_dg, host only (like eqlb_get_reference_table):
+ * returns the number of doubles copied (<= capacity), or a negative error. */
+int eqlb_get_primal_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity);
+
 /* Largest number of cells of a patch of the mesh (OrientedPatch::ncells_max). */
 int32_t eqlb_mesh_max_patch_cells(const eqlb_mesh_t* mesh);
 

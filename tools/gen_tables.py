@@ -17,6 +17,8 @@ Basix nor quadrature loops:
   B[k][k]              B_ji = C(j,i)(-1)^i : moments w.r.t. s of a trace given by its moments
                        w.r.t. 1-s (reversed facet), cf. se/KernelData.cpp:49-64
   NREF[3][2], NOUT[3]  reference facet normals of the RT functionals and their outwardness
+  PG[2][nd_d][nd_p]    projected reference gradient of a P_p function in DG_d (eqlb_primal_flux.hip): the DG_d nodal
+                       values of d/dX phi_i for d >= p-1 (exact), Minv_d int psi_n d/dX phi_i (L2 projection) below
 
 Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
       go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
@@ -38,6 +40,8 @@ PAIRS = [(1, 0), (2, 1), (3, 2), (4, 3), (2, 0), (3, 1), (3, 0)]  # (k, degree o
 # eqlb_tables_build_gen.h, which git ignores
 PAIRS_BUILD = [(4, 2), (4, 1), (4, 0)]
 NCOMBO = 12  # (fm, fp, rev) combinations with fm != fp
+# (degree p of the primal P_p solution, degree d of the projected flux) of the PG tables
+PAIRS_PRIMAL = [(p, d) for p in range(1, 5) for d in range(4)]
 
 
 def combo(fm, fp, rev):
@@ -245,6 +249,35 @@ def reduced_tensors(k, S, B):
     return TE, WQ
 
 
+def _evaluate_exact(p, x, y):
+    return sum((c * x ** a * y ** b for (a, b), c in p.items()), Fraction(0))
+
+
+def primal_table_exact(p, d):
+    """PG[X][n][i]: DG_d DOF n of the projection of d/dX phi_i, phi_i the basis of P_p (Basix numbering of
+    elmtlib/lagrange.py for both).  grad_X P_p lies in P_{p-1}^2: for d >= p-1 the projection is the nodal
+    interpolation (what embed_dg produces from the DG_{p-1} values), below it is the L2 projection, whose
+    |detJ| cancels on an affine cell."""
+    el, dg = Lagrange(p), Lagrange(d)
+    npp, nd = el.ndofs, dg.ndofs
+    grads = [[der(el.basis[i]) for i in range(npp)] for der in (P.ddx, P.ddy)]
+    if d >= p - 1:
+        return [[[_evaluate_exact(grads[X][i], *dg.nodes[n]) for i in range(npp)] for n in range(nd)]
+                for X in range(2)]
+    mass = [[P.integrate_triangle(P.mul(dg.basis[i], dg.basis[j])) for j in range(nd)] for i in range(nd)]
+    out = []
+    for X in range(2):
+        load = [[P.integrate_triangle(P.mul(dg.basis[n], grads[X][i])) for i in range(npp)] for n in range(nd)]
+        out.append(P.solve_exact(mass, load))
+    return out
+
+
+def primal_table_float(p, d):
+    import numpy as np
+    nd, npp = (d + 1) * (d + 2) // 2, (p + 1) * (p + 2) // 2
+    return np.array([float(v) for v in _flat(primal_table_exact(p, d))]).reshape(2, nd, npp)
+
+
 def _flat(x):
     if isinstance(x, list):
         for y in x:
@@ -332,6 +365,17 @@ def emit(path):
         lines.append(f"  static constexpr int ND = {nd};")
         lines.append(f"  static constexpr double COEF[{nd * nd}] = {{" + ", ".join(repr(float(v)) for v in _flat(coef)) + "};")
         lines.append(f"  static constexpr double MINV[{nd * nd}] = {{" + ", ".join(repr(float(v)) for v in _flat(minv)) + "};")
+        lines.append("};")
+    lines.append("")
+    lines.append("// projected reference gradient of P_p in DG_d: PG[X][n][i] = DG_d DOF n of d/dX phi_i (nodal values for")
+    lines.append("// d >= p-1, L2 projection below); flux_dg = -kappa K^T PG u_cell (eqlb_primal_flux.hip)")
+    lines.append("template <int P, int D> struct Primal;")
+    for (p, d) in PAIRS_PRIMAL:
+        npp, nd = (p + 1) * (p + 2) // 2, (d + 1) * (d + 2) // 2
+        lines.append(f"template <> struct Primal<{p}, {d}> {{")
+        lines.append(f"  static constexpr int NP = {npp}, ND = {nd};")
+        lines.append(f"  static constexpr double PG[{2 * nd * npp}] = {{"
+                     + ", ".join(repr(float(v)) for v in _flat(primal_table_exact(p, d))) + "};")
         lines.append("};")
     lines.append("")
     lines.append("// reference facet normals of the RT functionals (e_raviart_thomas.py:82) and whether the")
