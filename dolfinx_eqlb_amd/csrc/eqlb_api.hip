@@ -3,6 +3,7 @@
 // (cpp/dolfinx_eqlb/se/reconstruction.hpp:337-407) with the per-call setup hoisted into the
 // handle.  There is NO CPU fallback: without a HIP device every compute entry point fails.
 #include "eqlb_internal.h"
+#include "eqlb_host_util.h"
 
 #include <algorithm>
 #include <chrono>
@@ -19,33 +20,6 @@
 namespace
 {
 thread_local std::string g_error;
-
-// EQLB_PROFILE_SETUP=1: wall time of the set-up phases on stderr
-struct SetupTimer
-{
-  bool on;
-  std::chrono::steady_clock::time_point t0;
-  SetupTimer() : on(getenv("EQLB_PROFILE_SETUP") != nullptr), t0(std::chrono::steady_clock::now()) {}
-  void lap(const char* what)
-  {
-    if (!on)
-      return;
-    const auto t1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[eqlb setup] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-    t0 = t1;
-  }
-};
-
-int fail(int code, const char* fmt, ...)
-{
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-  return code;
-}
 
 } // namespace
 namespace eqlb
@@ -64,34 +38,6 @@ int set_error(int code, const char* fmt, ...)
 } // namespace eqlb
 namespace
 {
-
-#define HIP_TRY(expr)                                                                             \
-  do                                                                                              \
-  {                                                                                               \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess)                                                                         \
-      return fail(EQLB_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));                \
-  } while (0)
-
-template <typename T>
-int upload(T** dst, const T* src, size_t n)
-{
-  *dst = nullptr;
-  if (n == 0)
-    n = 1;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(T)));
-  if (src)
-    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-
-template <typename T>
-void dfree(T*& p)
-{
-  if (p)
-    (void)hipFree(p);
-  p = nullptr;
-}
 
 void free_boundary(eqlb_se* h)
 {
@@ -232,781 +178,10 @@ int find_stress_groups(const eqlb::DeviceMesh& m, const int8_t* facet_type, cons
   return EQLB_OK;
 }
 
-// Recursive coordinate bisection of the cell centroids into chunks of exactly `tc` cells (the last
-// one may be short): compact tiles keep the share of rim patches, which are solved by every tile
-// they touch, small.
-// (centroids relative to the bounding box of the mesh, in single precision: the bisection only compares them,
-// ties go by the cell id, and a 12-byte item moves through the selection passes twice as fast as a 24-byte one)
-struct TileItem
-{
-  float x, y;
-  int32_t cell;
-};
-
-// Context of the bisection: cell -> nodes and a per-node stamp to count the nodes a cut separates
-struct RcbCtx
-{
-  const int32_t* cell_nodes;
-  std::vector<int64_t> stamp; // [nnodes] 2 * epoch + side of the last cell that touched the node
-  std::vector<int64_t> cut;   // [nnodes] epoch in which the node was counted as cut
-  int64_t epoch = 0;
-};
-
-static inline bool rcb_less(const TileItem& p, const TileItem& q, int axis)
-{
-  const float u = axis ? p.y : p.x, v = axis ? q.y : q.x;
-  return u < v || (u == v && p.cell < q.cell);
-}
-
-// std::vector without value initialisation: the big scratch arrays of the tile builder are written completely by the
-// worker threads - a zero fill by the calling thread would touch (page-fault) tens of MB serially first
-template <typename T>
-struct default_init_alloc : std::allocator<T>
-{
-  template <typename U>
-  struct rebind
-  {
-    using other = default_init_alloc<U>;
-  };
-  template <typename U, typename... A>
-  void construct(U* p, A&&... a)
-  {
-    if constexpr (sizeof...(A) == 0)
-      ::new (static_cast<void*>(p)) U;
-    else
-      ::new (static_cast<void*>(p)) U(std::forward<A>(a)...);
-  }
-};
-template <typename T>
-using uvec = std::vector<T, default_init_alloc<T>>;
-
-// Host worker threads of the set-up: capped (the tile builder keeps an O(nnodes) stamp per worker: 16 MB each at
-// 4M nodes, on every rank of a node) and exception safe - an exception inside a std::thread would call
-// std::terminate; the first one is kept and re-thrown by join() in the calling thread, where the C entry points
-// turn it into an error code (EQLB_GUARD).
-static int host_workers(int64_t wanted)
-{
-  const int64_t hw = std::max<int64_t>(1, std::min<int64_t>(std::thread::hardware_concurrency(), 32));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(hw, wanted));
-}
-struct Workers
-{
-  std::vector<std::thread> th;
-  std::exception_ptr err;
-  std::mutex mu;
-  template <typename F>
-  void spawn(F f)
-  {
-    th.emplace_back([this, f]() {
-      try
-      {
-        f();
-      }
-      catch (...)
-      {
-        std::lock_guard<std::mutex> g(mu);
-        if (!err)
-          err = std::current_exception();
-      }
-    });
-  }
-  void join()
-  {
-    for (auto& x : th)
-      x.join();
-    th.clear();
-    if (err)
-    {
-      std::exception_ptr e = err;
-      err = nullptr;
-      std::rethrow_exception(e);
-    }
-  }
-  ~Workers()
-  {
-    for (auto& x : th)
-      if (x.joinable())
-        x.join();
-  }
-};
-
-// The same partition as rcb_partition (the key (coordinate, cell id) is a total order, so the two halves are
-// determined as SETS) on the host threads, for the few large segments at the top of the recursion where the
-// subtrees do not yet occupy the cores: histogram of the coordinate -> bucket of the splitting element ->
-// exact splitter inside that bucket -> counting partition through a scratch array.
-static void rcb_partition_parallel(TileItem* a, int64_t n, int64_t nl, int axis, float lo, float hi,
-                                   std::vector<TileItem>& tmp)
-{
-  const int nt = host_workers(n / (1 << 15));
-  constexpr int NBK = 4096;
-  const float scale = (hi > lo) ? (float)NBK / (hi - lo) : 0.0f;
-  auto bucket = [&](const TileItem& t) {
-    const int b = (int)(((axis ? t.y : t.x) - lo) * scale);
-    return b < 0 ? 0 : (b >= NBK ? NBK - 1 : b);
-  };
-  auto run = [&](auto f) {
-    Workers w;
-    for (int t = 1; t < nt; ++t)
-      w.spawn([f, t]() { f(t); });
-    f(0);
-    w.join();
-  };
-  std::vector<int64_t> hist((size_t)nt * NBK, 0);
-  run([&](int t) {
-    int64_t* hh = &hist[(size_t)t * NBK];
-    for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i)
-      ++hh[bucket(a[i])];
-  });
-  int bs = 0;
-  int64_t before = 0;
-  for (; bs < NBK; ++bs)
-  {
-    int64_t c = 0;
-    for (int t = 0; t < nt; ++t)
-      c += hist[(size_t)t * NBK + bs];
-    if (before + c > nl)
-      break;
-    before += c;
-  }
-  if (bs == NBK) // nl == n: nothing to split
-    return;
-  // the nl-th smallest element lives in bucket bs (buckets are ordered by the coordinate)
-  std::vector<TileItem> cand;
-  for (int64_t i = 0; i < n; ++i)
-    if (bucket(a[i]) == bs)
-      cand.push_back(a[i]);
-  std::nth_element(cand.begin(), cand.begin() + (nl - before), cand.end(),
-                   [axis](const TileItem& p, const TileItem& q) { return rcb_less(p, q, axis); });
-  const TileItem piv = cand[(size_t)(nl - before)];
-  // counting partition: [elements below the splitter | the rest]
-  std::vector<int64_t> cnt((size_t)nt + 1, 0);
-  run([&](int t) {
-    int64_t c = 0;
-    for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i)
-      c += rcb_less(a[i], piv, axis) ? 1 : 0;
-    cnt[(size_t)t + 1] = c;
-  });
-  for (int t = 0; t < nt; ++t)
-    cnt[(size_t)t + 1] += cnt[(size_t)t];
-  if ((int64_t)tmp.size() < n)
-    tmp.resize((size_t)n);
-  run([&](int t) {
-    const int64_t b = n * t / nt, e = n * (t + 1) / nt;
-    int64_t l = cnt[(size_t)t], r = nl + (b - cnt[(size_t)t]);
-    for (int64_t i = b; i < e; ++i)
-    {
-      if (rcb_less(a[i], piv, axis))
-        tmp[(size_t)l++] = a[i];
-      else
-        tmp[(size_t)r++] = a[i];
-    }
-  });
-  run([&](int t) {
-    const int64_t b = n * t / nt, e = n * (t + 1) / nt;
-    std::copy(tmp.begin() + b, tmp.begin() + e, a + b);
-  });
-}
-
-static void rcb_partition(TileItem* a, int64_t n, int64_t nl, int axis)
-{
-  if (axis == 0)
-    std::nth_element(a, a + nl, a + n, [](const TileItem& p, const TileItem& q) {
-      return p.x < q.x || (p.x == q.x && p.cell < q.cell);
-    });
-  else
-    std::nth_element(a, a + nl, a + n, [](const TileItem& p, const TileItem& q) {
-      return p.y < q.y || (p.y == q.y && p.cell < q.cell);
-    });
-}
-
-// nodes with cells on both sides of the partition [0, nl) | [nl, n): their patches are solved twice
-static int64_t rcb_cut_nodes(const TileItem* a, int64_t n, int64_t nl, RcbCtx& c)
-{
-  const int64_t ep = ++c.epoch;
-  int64_t ncut = 0;
-  for (int64_t i = 0; i < n; ++i)
-  {
-    const int64_t tag = 2 * ep + (i < nl ? 0 : 1);
-    const int32_t* cn = c.cell_nodes + 3 * (size_t)a[i].cell;
-    for (int j = 0; j < 3; ++j)
-    {
-      int64_t& st = c.stamp[cn[j]];
-      if (st / 2 == ep && st != tag && c.cut[cn[j]] != ep)
-      {
-        c.cut[cn[j]] = ep;
-        ++ncut;
-      }
-      st = tag;
-    }
-  }
-  return ncut;
-}
-
-// pool of bisection contexts for the worker threads (a context is [nnodes]-sized)
-struct RcbPool
-{
-  const int32_t* cell_nodes;
-  int32_t nnodes;
-  const uint8_t* stretched = nullptr; // [ncells] 1: longest edge^2 > 6 |det J| (aspect ratio above ~3)
-  std::mutex mtx;
-  std::vector<std::unique_ptr<RcbCtx>> free_list;
-  std::unique_ptr<RcbCtx> acquire()
-  {
-    {
-      std::lock_guard<std::mutex> g(mtx);
-      if (!free_list.empty())
-      {
-        auto c = std::move(free_list.back());
-        free_list.pop_back();
-        return c;
-      }
-    }
-    return std::unique_ptr<RcbCtx>(new RcbCtx{cell_nodes, std::vector<int64_t>(nnodes, -1), std::vector<int64_t>(nnodes, -1), 0});
-  }
-  void release(std::unique_ptr<RcbCtx> c)
-  {
-    std::lock_guard<std::mutex> g(mtx);
-    free_list.push_back(std::move(c));
-  }
-};
-
-// The subtrees are independent of one another (a context only remembers the nodes of ITS current cut), so
-// the upper levels hand their halves to other host threads: same tiles as the serial recursion.
-void rcb_split(TileItem* a, int64_t n, int64_t ntile, int tc, RcbPool& pool, RcbCtx* c, int depth)
-{
-  if (ntile <= 1 || n <= tc)
-    return;
-  float lo[2] = {3e38f, 3e38f}, hi[2] = {-3e38f, -3e38f};
-  int64_t nstretched = 0;
-  const bool last_levels = ntile <= 64;
-  for (int64_t i = 0; i < n; ++i)
-  {
-    lo[0] = std::min(lo[0], a[i].x);
-    hi[0] = std::max(hi[0], a[i].x);
-    lo[1] = std::min(lo[1], a[i].y);
-    hi[1] = std::max(hi[1], a[i].y);
-    if (last_levels && pool.stretched)
-      nstretched += pool.stretched[a[i].cell];
-  }
-  const int64_t tl = ntile / 2;
-  const int64_t nl = std::min<int64_t>(n, tl * tc);
-  int axis = (hi[0] - lo[0] >= hi[1] - lo[1]) ? 0 : 1;
-  // the last levels decide the shape of the tiles: there the cut is chosen by what it costs - the
-  // nodes it separates - not by the extent of the bounding box (which misleads on stretched cells:
-  // boundary layers, polar meshes)
-  // (where the cells of the segment are not stretched - fewer than 2 % with an aspect ratio above ~3 - the longer
-  //  side of the bounding box IS the cheaper cut, and the two trial partitions with their node counts, which
-  //  dominated the set-up time of isotropic meshes, are skipped)
-  std::unique_ptr<RcbCtx> own;
-  if (last_levels && nstretched * 50 > n)
-  {
-    if (!c)
-    {
-      own = pool.acquire();
-      c = own.get();
-    }
-    rcb_partition(a, n, nl, axis);
-    const int64_t c0 = rcb_cut_nodes(a, n, nl, *c);
-    std::vector<TileItem> first(a, a + n); // the partition along `axis`, in case it wins
-    rcb_partition(a, n, nl, 1 - axis);
-    const int64_t c1 = rcb_cut_nodes(a, n, nl, *c);
-    if (c1 < c0)
-      axis = 1 - axis; // already partitioned along it
-    else
-      std::copy(first.begin(), first.end(), a);
-  }
-  else if (n >= (1 << 18) && depth <= 2) // the top of the tree: few segments, many idle cores
-  {
-    std::vector<TileItem> tmp;
-    rcb_partition_parallel(a, n, nl, axis, lo[axis], hi[axis], tmp);
-  }
-  else
-    rcb_partition(a, n, nl, axis);
-  constexpr int PAR_DEPTH = 5; // up to 32 concurrent subtrees
-  if (depth < PAR_DEPTH && n > 16 * (int64_t)tc)
-  {
-    // (a context taken above stays with this thread's half)
-    auto left = std::async(std::launch::async, [&]() { rcb_split(a, nl, tl, tc, pool, nullptr, depth + 1); });
-    rcb_split(a + nl, n - nl, ntile - tl, tc, pool, c, depth + 1);
-    left.get();
-  }
-  else
-  {
-    rcb_split(a, nl, tl, tc, pool, c, depth + 1);
-    rcb_split(a + nl, n - nl, ntile - tl, tc, pool, c, depth + 1);
-  }
-  if (own)
-    pool.release(std::move(own));
-}
-
-// f(i) for i in [0, n) on the host threads (contiguous chunks)
-template <typename F>
-void parallel_for(int64_t n, int64_t min_chunk, F f)
-{
-  const int64_t nt = host_workers(n / std::max<int64_t>(min_chunk, 1));
-  if (nt <= 1)
-  {
-    for (int64_t i = 0; i < n; ++i)
-      f(i);
-    return;
-  }
-  Workers w;
-  for (int64_t t = 0; t < nt; ++t)
-    w.spawn([=]() {
-      for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i)
-        f(i);
-    });
-  w.join();
-}
-
-// Wave-blocks per bin and body instance that the tiled kernel of this handle runs over all tiles (eqlb_se_tiling_blocks):
-// the split of a tile's list by k_se_stress_tiled (h->t_stress; full_only: lists of full patches, padded) or
-// k_se_patch_tiled*, through the range functions the kernels call (eqlb_internal.h)
-void count_tile_blocks(eqlb_se* h, const std::vector<eqlb::TileDesc>& tiles, bool full_only)
-{
-  int64_t* out = h->t_blocks;
-  std::fill(out, out + EQLB_TB_COUNT, int64_t(0));
-  const int K = h->k;
-  for (const eqlb::TileDesc& td : tiles)
-  {
-    out[EQLB_TB_ZERO_TILES] += td.zero ? 1 : 0;
-    for (int b = 0; b < eqlb::MAX_BINS; ++b)
-    {
-      const int P = eqlb::BIN_P[b];
-      int64_t* o = out + EQLB_TB_PER_BIN * b;
-      if (h->t_stress)
-      {
-        if (b >= 2)
-          continue; // the fused kernel takes the bins 0, 1
-        if (full_only)
-        {
-          o[EQLB_TB_FULL] += eqlb::tile_wb_whole(td.npatch[b], P);
-          o[EQLB_TB_PADDING] += td.npatch[b] - td.nint[b];
-          continue;
-        }
-        const int nwb = eqlb::tile_wb_all(td.npatch[b], P), nwb_full = eqlb::tile_wb_whole(td.nfull[b], P);
-        int c0[3], c1[3];
-        for (int j = 0; j < 3; ++j)
-          if (b == 0)
-            eqlb::tile_nfix_range<4>(td, 0, j, c0[j], c1[j]);
-          else
-            eqlb::tile_nfix_range<8>(td, 1, j, c0[j], c1[j]);
-        int nfix = 0;
-        for (int j = 0; j < 3; ++j)
-        {
-          o[EQLB_TB_NFIX1 + j] += c1[j] - c0[j];
-          nfix += c1[j] - c0[j];
-        }
-        o[EQLB_TB_FULL] += nwb_full;
-        o[EQLB_TB_GENERIC] += nwb - nwb_full - nfix;
-        continue;
-      }
-      const int nwb = eqlb::tile_wb_all(td.npatch[b], P);
-      const int nwb_full = eqlb::tile_spec_full(K, P) ? eqlb::tile_wb_whole(td.nfull[b], P) : 0;
-      const int nwb_int = eqlb::tile_spec_interior(K, P) ? eqlb::tile_wb_whole(td.nint[b], P) : 0;
-      const int nint = std::max(nwb_int - nwb_full, 0); // (k_se_patch_tiled: u < nwb_full first, then u < nwb_int)
-      o[EQLB_TB_FULL] += nwb_full;
-      o[EQLB_TB_INTERIOR] += nint;
-      o[EQLB_TB_GENERIC] += nwb - nwb_full - nint;
-    }
-  }
-}
-
-// Tiled SoA of the plain flux equilibration (EQLB_SCATTER_TILED): cells bisected recursively by
-// their centroids into tiles of TC cells; a tile lists every (masked-in) node of its cells.
-int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::BuildArgs a, int tc_fixed = 0, int max_bin = eqlb::MAX_BINS,
-                bool full_only = false)
-{
-  // nodes of bins >= max_bin are left out (like masked-out nodes): another path equilibrates them.
-  // full_only (fused stress launch on the crossed benchmark meshes): so are all patches that are not FULL (interior,
-  // as many cells as lanes); the lists of a tile are padded to whole wave-blocks with copies of a full patch that
-  // own no cell
-  const eqlb::DeviceMesh& m = h->mesh->m;
-  const int32_t nc = m.ncells;
-  std::vector<int8_t> node_bin(node_bin_all);
-  std::vector<uint8_t> is_rest(max_bin < eqlb::MAX_BINS ? m.nnodes : 0, 0);
-  h->t_rest = 0;
-  for (int32_t i = 0; i < m.nnodes; ++i)
-  {
-    int8_t& b = node_bin[i];
-    if (b < 0)
-      continue;
-    const bool full = m.h_node_ncells[i] == m.h_node_nfcts[i] && m.h_node_ncells[i] == eqlb::BIN_P[b];
-    if (b >= max_bin || (full_only && !full))
-    {
-      b = -1;
-      ++h->t_rest;
-      if (!is_rest.empty())
-        is_rest[i] = 1;
-    }
-  }
-  dfree(h->rest_cells);
-  h->nrest_cells = 0;
-  if (!is_rest.empty() && h->t_rest > 0)
-  {
-    // cells with a vertex whose patch the generic kernels take: the compact reduction of their slot rows
-    std::vector<int32_t> rc;
-    for (int32_t c = 0; c < nc; ++c)
-      for (int j = 0; j < 3; ++j)
-      {
-        const int32_t nd = m.h_cell_nodes[3 * (size_t)c + j];
-        if (is_rest[nd])
-        {
-          rc.push_back(c);
-          break;
-        }
-      }
-    h->nrest_cells = (int64_t)rc.size();
-    if (upload(&h->rest_cells, rc.data(), std::max<size_t>(rc.size(), 1)))
-      return EQLB_ERR_DEVICE;
-  }
-  // Tile size: the default, or - on meshes that fill the chip several times over - the size that
-  // makes the tiles fill whole rounds of the 512 workgroup slots (2 per CU): 1M triangles in 2 045
-  // tiles of 489 cells run in 4 rounds, 2 084 tiles of 480 cells leave 36 tiles for a fifth
-  int TC = tc_fixed > 0 ? tc_fixed : eqlb::tile_cells_of(h->k);
-  if (tc_fixed > 0)
-  {
-    // fused stress launch (tc_fixed = the largest tile its LDS holds): ONE workgroup per CU, so a partial last
-    // round of the 256 slots costs a full round - fit the tile size to whole rounds as below
-    const int64_t slots = 256, tcmax = tc_fixed;
-    TC = (int)std::min<int64_t>(tcmax, 448);
-    if ((int64_t)nc >= slots * 256)
-    {
-      const int64_t rounds = ((int64_t)nc + slots * tcmax - 1) / (slots * tcmax);
-      TC = (int)(((int64_t)nc + rounds * slots - 1) / (rounds * slots));
-    }
-    if (h->tile_cells_user > 0)
-      TC = (int)std::min<int64_t>(h->tile_cells_user, tcmax);
-  }
-  if (tc_fixed <= 0)
-  {
-    // resident workgroup slots of the chip: two per CU for k <= 2, one for k = 3
-    const bool ev3 = h->mode == 1 && h->k >= 3; // EV mode of RT_3 stages 7 KB more tensors: smaller tiles
-    const int64_t slots = (h->k <= 2) ? 512 : 256, tcmax = ev3 ? eqlb::tile_cells_ev_of(h->k) : eqlb::tile_cells_max_of(h->k);
-    if (ev3)
-      TC = eqlb::tile_cells_ev_of(h->k);
-    if ((int64_t)nc >= slots * 256)
-    {
-      const int64_t rounds = ((int64_t)nc + slots * tcmax - 1) / (slots * tcmax);
-      TC = (int)(((int64_t)nc + rounds * slots - 1) / (rounds * slots));
-    }
-    if (h->tile_cells_user > 0) // tuning knob (option "tile_cells"), capped by what the LDS of a workgroup holds
-      TC = (int)std::min<int64_t>(h->tile_cells_user, tcmax);
-  }
-  SetupTimer tm;
-  uvec<TileItem> items(nc);
-  const int32_t ntiles = (nc + TC - 1) / TC;
-  bool cached = false;
-  {
-    std::lock_guard<std::mutex> g(h->mesh->tiling_mutex);
-    auto it = h->mesh->tiling_order.find(TC);
-    if (it != h->mesh->tiling_order.end() && (int32_t)it->second.size() == nc)
-    {
-      for (int32_t p = 0; p < nc; ++p)
-        items[p] = {0.0f, 0.0f, it->second[p]};
-      cached = true;
-    }
-  }
-  if (!cached)
-  {
-  std::vector<uint8_t> stretched(nc);
-  // bounding box of the nodes: the centroids are stored relative to it (one scale for both directions)
-  double blo[2] = {1e300, 1e300}, bhi[2] = {-1e300, -1e300};
-  for (int32_t i = 0; i < m.nnodes; ++i)
-    for (int d = 0; d < 2; ++d)
-    {
-      blo[d] = std::min(blo[d], m.h_x[3 * (size_t)i + d]);
-      bhi[d] = std::max(bhi[d], m.h_x[3 * (size_t)i + d]);
-    }
-  const double ext = std::max(bhi[0] - blo[0], bhi[1] - blo[1]);
-  const double inv = (ext > 0.0) ? 1.0 / (3.0 * ext) : 0.0;
-  // the bisection on the device (one radix sort per level of the tree; eqlb_tiling_device.hip) unless the mesh
-  // has stretched cells, where the host bisection below picks the cuts of the last levels by their cost
-  bool on_device = false;
-  {
-    const char* env = getenv("EQLB_TILING");
-    if (!(env && !strcmp(env, "host")) && nc >= 4096)
-    {
-      std::vector<int32_t> dord;
-      const int r = eqlb::device_tile_order(m, TC, ntiles, blo, bhi, inv, dord);
-      if (r < 0)
-        return fail(EQLB_ERR_DEVICE, "tiling on the device failed");
-      if (r == 0)
-      {
-        for (int32_t p = 0; p < nc; ++p)
-          items[p] = {0.0f, 0.0f, dord[p]};
-        on_device = true;
-        tm.lap("tiles: bisection (device)");
-      }
-    }
-  }
-  if (!on_device)
-  {
-  parallel_for(nc, 1 << 16, [&](int64_t c) {
-    const int32_t* cn = &m.h_cell_nodes[3 * (size_t)c];
-    double cx = 0.0, cy = 0.0;
-    for (int j = 0; j < 3; ++j)
-    {
-      cx += m.h_x[3 * (size_t)cn[j]] - blo[0];
-      cy += m.h_x[3 * (size_t)cn[j] + 1] - blo[1];
-    }
-    items[c] = {(float)(cx * inv), (float)(cy * inv), (int32_t)c};
-    const double* p0 = &m.h_x[3 * (size_t)cn[0]];
-    const double* p1 = &m.h_x[3 * (size_t)cn[1]];
-    const double* p2 = &m.h_x[3 * (size_t)cn[2]];
-    const double e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e2x = p2[0] - p0[0], e2y = p2[1] - p0[1];
-    const double l2 = std::max(std::max(e1x * e1x + e1y * e1y, e2x * e2x + e2y * e2y),
-                               (e2x - e1x) * (e2x - e1x) + (e2y - e1y) * (e2y - e1y));
-    stretched[c] = l2 > 6.0 * std::fabs(e1x * e2y - e1y * e2x) ? 1 : 0;
-  });
-  RcbPool pool{m.h_cell_nodes.data(), m.nnodes, stretched.data(), {}, {}};
-  tm.lap("tiles: centroids");
-  rcb_split(items.data(), nc, ntiles, TC, pool, nullptr, 0);
-  tm.lap("tiles: bisection");
-  // ascending cell ids inside a tile: the flush of a tile then touches flux_hdiv in long runs
-  parallel_for(ntiles, 16, [&](int64_t t) {
-    std::sort(items.begin() + (size_t)t * TC, items.begin() + std::min<size_t>((size_t)(t + 1) * TC, nc),
-              [](const TileItem& p, const TileItem& q) { return p.cell < q.cell; });
-  });
-  }
-  std::vector<int32_t> ord(nc);
-  for (int32_t p = 0; p < nc; ++p)
-    ord[p] = items[p].cell;
-  std::lock_guard<std::mutex> g(h->mesh->tiling_mutex);
-  h->mesh->tiling_order[TC] = std::move(ord);
-  }
-  // tiles that own a priority cell (ghost rows a neighbour rank waits for) are numbered first: a
-  // first launch over them, the halo exchange, and the launch over the rest then overlap
-  std::vector<int32_t> order(ntiles);
-  {
-    std::vector<uint8_t> tile_prio(ntiles, 0);
-    if (!h->prio_cells.empty())
-    {
-      std::vector<uint8_t> is_prio(nc, 0);
-      for (int32_t c : h->prio_cells)
-        if (c >= 0 && c < nc)
-          is_prio[c] = 1;
-      for (int32_t p = 0; p < nc; ++p)
-        if (is_prio[items[p].cell])
-          tile_prio[p / TC] = 1;
-    }
-    int32_t np = 0;
-    for (int32_t t = 0; t < ntiles; ++t)
-      if (tile_prio[t])
-        order[np++] = t;
-    h->t_nprio = np;
-    for (int32_t t = 0; t < ntiles; ++t)
-      if (!tile_prio[t])
-        order[np++] = t;
-  }
-  tm.lap("tiles: sort + priority");
-  uvec<int32_t> tile_cells((size_t)ntiles * TC), cell_tile(nc), cell_pos(nc);
-  parallel_for(ntiles, 16, [&](int64_t t) {
-    const int64_t src = (int64_t)order[t] * TC, len = std::min<int64_t>(TC, nc - src);
-    for (int64_t q = 0; q < len; ++q)
-    {
-      const int32_t c = items[src + q].cell;
-      tile_cells[(size_t)t * TC + q] = c;
-      cell_tile[c] = (int32_t)t;
-      cell_pos[c] = (int32_t)((int64_t)t * TC + q);
-    }
-    for (int64_t q = len; q < TC; ++q)
-      tile_cells[(size_t)t * TC + q] = -1;
-  });
-  std::vector<eqlb::TileDesc> tiles(ntiles);
-  // pass 1 (host threads, a chunk of tiles each): the nodes of every tile by bin - full interior patches
-  // (as many cells as lanes, no boundary facet: their wave-blocks run the specialised body of the kernel)
-  // first -, in order of first appearance; flat storage, 3 TC entries per tile
-  constexpr int NB = eqlb::MAX_BINS;
-  uvec<int32_t> tnodes((size_t)ntiles * 3 * TC);
-  constexpr int NCL = 6; // classes of a bin: full | interior with P - 1, P - 2, P - 3 cells | other interior | boundary
-  std::vector<int32_t> tcount((size_t)ntiles * NCL * NB, 0); // [tile][bin][class]
-  auto tile_chunks = [&](auto work) {
-    const int64_t nt = host_workers(ntiles / 32);
-    if (nt <= 1)
-    {
-      work(0, ntiles);
-      return;
-    }
-    Workers wk;
-    for (int64_t w = 0; w < nt; ++w)
-      wk.spawn([&work, ntiles, w, nt]() { work((int64_t)ntiles * w / nt, (int64_t)ntiles * (w + 1) / nt); });
-    wk.join();
-  };
-  // sort key of a node: NCL * bin + class (full interior patch 0 | interior patch with P - 1, P - 2, P - 3 cells 1, 2, 3 |
-  // other interior patch 4 | boundary patch 5); -1: not listed
-  // (one byte per node, cache resident, instead of three scattered reads per visit of a node)
-  std::vector<int8_t> nkey(m.nnodes);
-  parallel_for(m.nnodes, 1 << 16, [&](int64_t nd) {
-    const int b_ = node_bin[nd];
-    if (b_ < 0)
-    {
-      nkey[nd] = -1;
-      return;
-    }
-    const bool interior = m.h_node_ncells[nd] == m.h_node_nfcts[nd]; // no boundary facet at the node
-    const int missing = eqlb::BIN_P[b_] - m.h_node_ncells[nd];         // idle lanes of the patch group
-    nkey[nd] = (int8_t)(NCL * b_ + (interior ? ((missing >= 0 && missing <= 3) ? missing : 4) : 5));
-  });
-  tile_chunks([&](int64_t t0, int64_t t1) {
-    std::vector<int32_t> stamp(m.nnodes, -1), seen(3 * (size_t)TC);
-    for (int64_t t = t0; t < t1; ++t)
-    {
-      int nseen = 0;
-      int32_t* cnt = &tcount[(size_t)t * NCL * NB];
-      auto key = [&](int32_t nd) { return (int)nkey[nd]; };
-      for (int q = 0; q < TC; ++q)
-      {
-        const int32_t c = tile_cells[(size_t)t * TC + q];
-        if (c < 0)
-          continue;
-        for (int j = 0; j < 3; ++j)
-        {
-          const int32_t nd = m.h_cell_nodes[3 * (size_t)c + j];
-          if (nkey[nd] < 0)
-            tiles[t].zero = 1; // masked-out vertex: the (cell, vertex) row of this tile stays unwritten
-          if (nkey[nd] < 0 || stamp[nd] == (int32_t)t)
-            continue;
-          stamp[nd] = (int32_t)t;
-          seen[nseen++] = nd;
-          ++cnt[key(nd)];
-        }
-      }
-      int32_t pos[NCL * NB], acc = 0; // stable counting sort by (bin, class)
-      for (int q = 0; q < NCL * NB; ++q)
-      {
-        pos[q] = acc;
-        acc += cnt[q];
-      }
-      int32_t* out = &tnodes[(size_t)t * 3 * TC];
-      for (int i = 0; i < nseen; ++i)
-        out[pos[key(seen[i])]++] = seen[i];
-      for (int b_ = 0; b_ < NB; ++b_)
-      {
-        const int32_t* cb = cnt + NCL * b_;
-        tiles[t].nfull[b_] = cb[0];
-        tiles[t].nint[b_] = cb[0] + cb[1] + cb[2] + cb[3] + cb[4];
-        tiles[t].npatch[b_] = tiles[t].nint[b_] + cb[5];
-        if (b_ < 2)
-        {
-          tiles[t].nval[b_][0] = cb[0] + cb[1];
-          tiles[t].nval[b_][1] = cb[0] + cb[1] + cb[2];
-          tiles[t].nval[b_][2] = cb[0] + cb[1] + cb[2] + cb[3];
-        }
-        if (full_only)
-        {
-          // whole wave-blocks: nint keeps the number of real patches, the others are copies (pass 2)
-          const int per = 64 / eqlb::BIN_P[b_];
-          const int padded = (per > 0) ? (cb[0] + per - 1) / per * per : cb[0];
-          tiles[t].nfull[b_] = padded;
-          tiles[t].npatch[b_] = padded;
-          if (b_ < 2)
-            tiles[t].nval[b_][0] = tiles[t].nval[b_][1] = tiles[t].nval[b_][2] = padded;
-        }
-      }
-    }
-  });
-  // lane slots and patch instances in tile order (serial prefix), then filled by the host threads
-  int64_t slotctr = 0, ninst = 0;
-  for (int32_t t = 0; t < ntiles; ++t)
-    for (int b_ = 0; b_ < NB; ++b_)
-    {
-      tiles[t].slot_start[b_] = (int32_t)slotctr;
-      tiles[t].patch_start[b_] = (int32_t)ninst;
-      slotctr += (int64_t)tiles[t].npatch[b_] * eqlb::BIN_P[b_];
-      ninst += tiles[t].npatch[b_];
-      slotctr = (slotctr + 63) & ~(int64_t)63;
-      if (slotctr > 0x7fffff00)
-        return fail(EQLB_ERR_UNSUPPORTED, "tiled patch SoA exceeds 2^31 lane slots");
-    }
-  uvec<int32_t> inst_node((size_t)ninst), inst_slot((size_t)ninst), inst_tile((size_t)ninst);
-  tile_chunks([&](int64_t t0, int64_t t1) {
-    for (int64_t t = t0; t < t1; ++t)
-    {
-      const int32_t* src = &tnodes[(size_t)t * 3 * TC];
-      for (int b_ = 0; b_ < NB; ++b_)
-      {
-        int32_t slot = tiles[t].slot_start[b_];
-        const int32_t nreal = full_only ? tiles[t].nint[b_] : tiles[t].npatch[b_];
-        for (int32_t i = 0, p_ = tiles[t].patch_start[b_]; i < tiles[t].npatch[b_]; ++i, ++p_, slot += eqlb::BIN_P[b_])
-        {
-          // (padding copy: the last real patch once more, tile -1 = it owns no cell and stores nothing)
-          inst_node[p_] = (i < nreal) ? *src++ : src[-1];
-          inst_slot[p_] = slot;
-          inst_tile[p_] = (i < nreal) ? (int32_t)t : -1;
-        }
-      }
-    }
-  });
-  tm.lap("tiles: patch lists");
-  count_tile_blocks(h, tiles, full_only);
-  h->ntiles = ntiles;
-  h->tile_tc = TC;
-  h->t_nslots = slotctr;
-  h->t_npatch = (int64_t)inst_node.size();
-  int32_t *d_inode = nullptr, *d_islot = nullptr, *d_itile = nullptr, *d_ctile = nullptr, *d_cpos = nullptr;
-  int st = 0;
-  st |= upload(&h->t_tiles, tiles.data(), tiles.size());
-  st |= upload(&h->t_tile_cells, tile_cells.data(), tile_cells.size());
-  st |= upload<int32_t>(&h->t_slot_cell, nullptr, (size_t)std::max<int64_t>(slotctr, 1));
-  st |= upload<uint32_t>(&h->t_slot_info, nullptr, (size_t)std::max<int64_t>(slotctr, 1));
-  st |= upload<uint8_t>(&h->t_pn, nullptr, (size_t)std::max<int64_t>(h->t_npatch, 1));
-  st |= upload<uint8_t>(&h->t_pflag, nullptr, (size_t)std::max<int64_t>(h->t_npatch, 1) * h->nrhs);
-  st |= upload(&d_inode, inst_node.data(), std::max<size_t>(inst_node.size(), 1));
-  st |= upload(&d_islot, inst_slot.data(), std::max<size_t>(inst_slot.size(), 1));
-  st |= upload(&d_itile, inst_tile.data(), std::max<size_t>(inst_tile.size(), 1));
-  st |= upload(&d_ctile, cell_tile.data(), cell_tile.size());
-  st |= upload(&d_cpos, cell_pos.data(), cell_pos.size());
-  hipError_t e = hipSuccess;
-  if (!st)
-  {
-    e = hipMemset(h->t_slot_cell, 0xff, sizeof(int32_t) * std::max<int64_t>(slotctr, 1));
-    if (e == hipSuccess)
-      e = hipMemset(h->t_slot_info, 0, sizeof(uint32_t) * std::max<int64_t>(slotctr, 1));
-    a.ninst = h->t_npatch;
-    a.inst_node = d_inode;
-    a.inst_slot = d_islot;
-    a.inst_tile = d_itile;
-    a.cell_tile = d_ctile;
-    a.cell_pos = d_cpos;
-    a.tile_cells = TC;
-    a.npatch_total = h->t_npatch;
-    a.slot_cell = h->t_slot_cell;
-    a.slot_info = h->t_slot_info;
-    a.pn = h->t_pn;
-    a.pflag = h->t_pflag;
-    a.stride = 0;
-    a.ex_ncells = nullptr;
-    if (e == hipSuccess && a.ninst > 0)
-    {
-      eqlb::launch_build_patches(a, nullptr);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-      e = hipDeviceSynchronize();
-  }
-  tm.lap("tiles: upload + builder kernel");
-  dfree(d_inode);
-  dfree(d_islot);
-  dfree(d_itile);
-  dfree(d_ctile);
-  dfree(d_cpos);
-  if (st)
-    return EQLB_ERR_DEVICE;
-  if (e != hipSuccess)
-    return fail(EQLB_ERR_DEVICE, "tiled patch builder: %s", hipGetErrorString(e));
-  return EQLB_OK;
-}
 } // namespace
 
 extern "C" {
 
-// Nothing may leave an extern "C" entry point as an exception (a ctypes / cgo / JNI caller would be terminated):
-// function-try-blocks around the entries that allocate on the host or start worker threads.
-#define EQLB_CATCH_ALL                                                                                       \
-  catch (const std::bad_alloc&) { return fail(EQLB_ERR_NO_MEMORY, "host memory exhausted"); }                \
-  catch (const std::exception& e) { return fail(EQLB_ERR_DEVICE, "internal error: %s", e.what()); }         \
-  catch (...) { return fail(EQLB_ERR_DEVICE, "internal error"); }
 
 const char* eqlb_last_error(void) { return g_error.c_str(); }
 
@@ -1550,8 +725,8 @@ try
       if (const char* env = getenv("EQLB_STRESS_MIXED_TILES"))
         h->t_mixed = env[0] != '0';
     }
-    const int stt = h->t_stress ? build_tiles(h, node_bin, a, eqlb::stress_tile_cells(), 2, !h->t_mixed)
-                                : build_tiles(h, node_bin, a);
+    const int stt = h->t_stress ? eqlb::build_tiles(h, node_bin, a, eqlb::stress_tile_cells(), 2, !h->t_mixed)
+                                : eqlb::build_tiles(h, node_bin, a);
     if (stt)
       return stt;
     if (h->mode == 1)
@@ -1602,20 +777,6 @@ try
     HIP_TRY(hipStreamSynchronize(stream));
   }
   return EQLB_OK;
-}
-EQLB_CATCH_ALL
-
-int eqlb_se_equilibrate_with_kornconst(eqlb_se_t* h, const double* flux_dg, const double* rhs_dg,
-                                       double* flux_hdiv, double* cells_kornconst,
-                                       int32_t memspace, void* stream_)
-try
-{
-  if (!cells_kornconst)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  const int st = eqlb_se_equilibrate(h, flux_dg, rhs_dg, flux_hdiv, memspace, stream_);
-  if (st)
-    return st;
-  return eqlb_se_kornconst(h, cells_kornconst, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -1670,22 +831,6 @@ try
 EQLB_CATCH_ALL
 
 int32_t eqlb_se_num_priority_tiles(const eqlb_se_t* h) { return (h && h->boundary_set) ? h->t_nprio : 0; }
-
-int eqlb_se_equilibrate_tiles(eqlb_se_t* h, const double* flux_dg, const double* rhs_dg, double* flux_hdiv,
-                              int32_t tile_first, int32_t tile_count, void* stream)
-try
-{
-  if (!h || tile_first < 0)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_equilibrate_tiles: invalid argument");
-  const int32_t f0 = h->tile_first, c0 = h->tile_count;
-  h->tile_first = tile_first;
-  h->tile_count = tile_count;
-  const int st = eqlb_se_equilibrate(h, flux_dg, rhs_dg, flux_hdiv, EQLB_MEM_DEVICE, stream);
-  h->tile_first = f0;
-  h->tile_count = c0;
-  return st;
-}
-EQLB_CATCH_ALL
 
 int eqlb_se_export_patches(eqlb_se_t* h, int32_t stride, int32_t* ncells, int32_t* cells,
                            int32_t* fcts, int8_t* fcts_local, int8_t* inodes_local,
@@ -1762,592 +907,6 @@ try
   return st ? EQLB_ERR_DEVICE : EQLB_OK;
 }
 EQLB_CATCH_ALL
-
-// The sweep on per-right-hand-side arrays: g[r], f[r], x[r] are the blocks of RHS r (host or device).
-static int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const double* const* f_in,
-                             double* const* x_io, int32_t memspace, void* stream_)
-{
-  if (!h || !g_in || !f_in || !x_io)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  for (int r = 0; r < h->nrhs; ++r)
-    if (!g_in[r] || !f_in[r] || !x_io[r])
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  if (!h->boundary_set)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_equilibrate: boundary data not set");
-  const eqlb::DeviceMesh& m = h->mesh->m;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const size_t s_g = (size_t)m.ncells * h->nd * 2, s_f = (size_t)m.ncells * h->nd; // block sizes
-  const size_t n_g = (size_t)h->nrhs * s_g, n_f = (size_t)h->nrhs * s_f;
-  // EQLB_SCATTER_AUTO: the tiled launch where it applies and is the fastest (k <= 3, plain flux
-  // equilibration, shuffle solver), else slots + reduction
-  int scatter_eff = h->scatter;
-  // stress of RT_2 without flux BCs on the stress rows: rows 0, 1 and their weak symmetry in one tiled launch
-  const bool stress_fused = h->stress && h->t_stress && h->ntiles > 0 && h->solver == EQLB_SOLVER_SHUFFLE
-                            && (scatter_eff == EQLB_SCATTER_AUTO || scatter_eff == EQLB_SCATTER_TILED);
-  if (scatter_eff == EQLB_SCATTER_AUTO)
-    scatter_eff = (stress_fused || (!h->stress && h->k <= 3 && h->solver == EQLB_SOLVER_SHUFFLE && h->ntiles > 0))
-                      ? EQLB_SCATTER_TILED
-                      : EQLB_SCATTER_SLOTS;
-  h->scatter_last = scatter_eff;
-  const size_t s_slot = (size_t)m.ncells * h->nrt, n_slot = (size_t)h->nrhs * s_slot;
-  // EV mode writes conforming DOFs unless the broken layout is requested
-  const bool ev_conf = h->mode == 1 && h->ev_output == 0;
-  const size_t s_x = ev_conf ? (size_t)h->ev_ndofs : s_slot, n_x = (size_t)h->nrhs * s_x;
-  if (!h->accumulate && scatter_eff == EQLB_SCATTER_ATOMIC)
-    return fail(EQLB_ERR_UNSUPPORTED, "\"accumulate\" = 0 is not available with the atomic scatter");
-  if (h->l_npatch > 0 && scatter_eff == EQLB_SCATTER_ATOMIC)
-    return fail(EQLB_ERR_UNSUPPORTED,
-                "patches of more than 63 cells (\"large_patches\") run with the slot or the tiled scatter, not the atomic one");
-  if (h->mode == 1 && (scatter_eff == EQLB_SCATTER_ATOMIC || (h->solver != EQLB_SOLVER_SHUFFLE && h->k != 4)))
-    return fail(EQLB_ERR_UNSUPPORTED, "EV equilibration runs with the shuffle solver (tiled or slot scatter)");
-
-  std::vector<const double*> d_g(g_in, g_in + h->nrhs), d_f(f_in, f_in + h->nrhs);
-  std::vector<double*> d_x(x_io, x_io + h->nrhs);
-  if (memspace == EQLB_MEM_HOST)
-  {
-    if (!h->d_flux_dg)
-    {
-      if (upload<double>(&h->d_flux_dg, nullptr, n_g) || upload<double>(&h->d_rhs_dg, nullptr, n_f)
-          || upload<double>(&h->d_flux_hdiv, nullptr, n_x))
-        return EQLB_ERR_DEVICE;
-    }
-    for (int r = 0; r < h->nrhs; ++r)
-    {
-      HIP_TRY(hipMemcpyAsync(h->d_flux_dg + r * s_g, g_in[r], s_g * sizeof(double), hipMemcpyHostToDevice, stream));
-      HIP_TRY(hipMemcpyAsync(h->d_rhs_dg + r * s_f, f_in[r], s_f * sizeof(double), hipMemcpyHostToDevice, stream));
-      if (h->accumulate)
-        HIP_TRY(hipMemcpyAsync(h->d_flux_hdiv + r * s_x, x_io[r], s_x * sizeof(double), hipMemcpyHostToDevice, stream));
-      d_g[r] = h->d_flux_dg + r * s_g;
-      d_f[r] = h->d_rhs_dg + r * s_f;
-      d_x[r] = h->d_flux_hdiv + r * s_x;
-    }
-  }
-  else if (memspace != EQLB_MEM_DEVICE)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_equilibrate: unknown memory space");
-
-  hipEvent_t* evs = nullptr;
-  if (h->timing)
-  {
-    if (h->ev && !h->ev[eqlb_se::EV_RING * eqlb_se::EV_PER_SET - 1])
-    {
-      // an earlier hipEventCreate failed half way: start over
-      for (int i = 0; i < eqlb_se::EV_RING * eqlb_se::EV_PER_SET; ++i)
-        if (h->ev[i])
-          (void)hipEventDestroy(h->ev[i]);
-      delete[] h->ev;
-      h->ev = nullptr;
-    }
-    if (!h->ev)
-    {
-      h->ev = new hipEvent_t[eqlb_se::EV_RING * eqlb_se::EV_PER_SET](); // null until created
-      for (int i = 0; i < eqlb_se::EV_RING * eqlb_se::EV_PER_SET; ++i)
-        HIP_TRY(hipEventCreate(&h->ev[i]));
-    }
-    evs = h->ev + (h->ev_calls % eqlb_se::EV_RING) * eqlb_se::EV_PER_SET;
-  }
-
-  eqlb::SeArgs a{};
-  a.cellJ = m.cellJ;
-  a.slot_cell = h->slot_cell;
-  a.slot_info = h->slot_info;
-  a.pn = h->pn;
-  a.pflag = h->pflag;
-  a.tables = h->tables;
-  a.bvals = h->bvals;
-  a.status = h->status;
-  a.npatch_total = h->npatch_total;
-  a.ncells = m.ncells;
-  a.nrhs = h->nrhs;
-  // data of right-hand side r: the kernels address block rhs_in of flux_dg / rhs_dg and block rhs_out
-  // of out; the caller's arrays arrive block by block, the slot buffer is one array
-  auto select_rhs = [&](eqlb::SeArgs& aa, int r, bool to_slots) {
-    aa.rhs = r;
-    aa.flux_dg = d_g[r];
-    aa.rhs_dg = d_f[r];
-    aa.rhs_in = 0;
-    if (to_slots)
-    {
-      aa.out = h->slots;
-      aa.rhs_out = r;
-    }
-    else
-    {
-      aa.out = d_x[r];
-      aa.rhs_out = 0;
-    }
-  };
-
-  // ---- slot path: (cell, vertex) rows into the slot buffer, weak symmetry on the slot rows, reduction.
-  // first_bin > 0: only the patches of the bins >= first_bin (the rest of a fused stress launch);
-  // their sums are ADDED to what the tiled launch wrote ----
-  // first_bin = -1: the REST of a fused stress launch - in the bins 0, 1 the patches behind the full ones
-  // (Bin::nfull), the higher bins entirely; sums added by the compact reduction over the cells they touch
-  // sp_stream / sp_phase: stream of the launches; phase 0 everything, 1 the patch kernels only, 2 the reduction only
-  // (the rest of a fused stress launch runs its patch kernels on a side stream next to the fused kernel)
-  hipStream_t sp_stream = stream;
-  int sp_phase = 0;
-  // the slot buffer, zeroed where rows of an earlier run over more bins than `cover` would be added again (see below)
-  auto ensure_slots = [&](int cover, hipStream_t s) -> int {
-    if (!h->slots)
-    {
-      if (upload<double>(&h->slots, nullptr, n_slot * 3))
-        return EQLB_ERR_DEVICE;
-      // slots of (cell, vertex) pairs whose node is not equilibrated here (node_mask, other path) stay zero
-      // (on the stream of the patch kernels: a fill on the null stream is not ordered against the non-blocking side
-      // stream of a fused stress launch and could wipe rows its kernels have already written)
-      HIP_TRY(hipMemsetAsync(h->slots, 0, n_slot * 3 * sizeof(double), s));
-      h->slots_first_bin = eqlb::MAX_BINS;
-    }
-    // The reduction adds ALL slot rows of a cell.  A run over the bins >= first_bin rewrites only their rows: rows
-    // of the lower bins left by an earlier run over more bins (option "scatter" / "solver" changed on this handle)
-    // would be added again on top of what the tiled launch wrote
-    if (h->slots_first_bin < cover)
-      HIP_TRY(hipMemsetAsync(h->slots, 0, n_slot * 3 * sizeof(double), s));
-    h->slots_first_bin = cover;
-    return EQLB_OK;
-  };
-  // patches of more than 63 cells: one workgroup each, rows into the slot buffer (rewritten by every call); timing
-  // slot MAX_BINS + 2
-  auto run_large = [&](hipStream_t s) -> int {
-    eqlb::SeArgs al = a;
-    al.slot_cell = h->l_slot_cell;
-    al.slot_info = h->l_slot_info;
-    al.pn = nullptr;
-    al.pflag = h->l_pflag;
-    al.npatch_total = h->l_npatch;
-    if (evs)
-      HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 4], s));
-    for (int r = 0; r < h->nrhs; ++r)
-    {
-      select_rhs(al, r, true);
-      const int st = eqlb::launch_se_patch_large(h->k, h->deg, h->mode, al, h->l_off, h->l_ws, s);
-      if (st)
-        return fail(st, "large-patch kernel launch failed (k=%d)", h->k);
-    }
-    if (evs)
-      HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 5], s));
-    return EQLB_OK;
-  };
-  auto run_slot_path = [&](int first_bin, int accumulate) -> int {
-    const bool rest = first_bin < 0;
-    auto bin_np = [&](int b) -> int64_t {
-      if (rest) // (tiles with every patch of the bins 0, 1: the higher bins only)
-        return (b < 2) ? (h->t_mixed ? 0 : h->bins[b].npatch - h->bins[b].nfull) : h->bins[b].npatch;
-      return (b >= first_bin) ? h->bins[b].npatch : 0;
-    };
-    auto bin_po = [&](int b) -> int64_t { return h->bins[b].patch_offset + ((rest && b < 2) ? h->bins[b].nfull : 0); };
-    auto bin_so = [&](int b) -> int64_t {
-      return h->bins[b].slot_offset + ((rest && b < 2) ? h->bins[b].nfull * h->bins[b].P : 0);
-    };
-    const int cover = rest ? 1 : first_bin; // 0: every patch writes its slot rows
-    if (sp_phase == 2)
-    {
-      for (int r = 0; r < h->nrhs; ++r)
-        if (eqlb::launch_reduce_slots_cells(h->nrt, m.ncells, h->nrest_cells, h->rest_cells,
-                                            h->slots + (size_t)r * s_slot * 3, d_x[r], sp_stream))
-          return fail(EQLB_ERR_UNSUPPORTED, "compact slot reduction for %d DOFs per cell is not in this build", h->nrt);
-      return EQLB_OK;
-    }
-    if (const int st = ensure_slots(cover, sp_stream))
-      return st;
-    eqlb::SeArgs as = a;
-    if ((h->mode == 1 && h->k <= 3) || (h->fused && h->solver == EQLB_SOLVER_SHUFFLE && h->k <= 3))
-    {
-      // all bins in one launch; timing slot 0 holds the fused kernel
-      eqlb::FusedBins fb{};
-      int64_t nb = 0;
-      for (int b = 0; b < eqlb::MAX_BINS; ++b)
-      {
-        fb.block_start[b] = nb;
-        fb.npatch[b] = bin_np(b);
-        fb.slot_offset[b] = bin_so(b);
-        fb.patch_offset[b] = bin_po(b);
-        nb += (fb.npatch[b] * h->bins[b].P + 255) / 256;
-      }
-      fb.block_start[eqlb::MAX_BINS] = nb;
-      for (int r = 0; r < h->nrhs; ++r)
-      {
-        select_rhs(as, r, true);
-        if (evs && r == 0 && first_bin == 0)
-          HIP_TRY(hipEventRecord(evs[0], sp_stream));
-        const int st = (h->mode == 1) ? eqlb::launch_ev_patch_fused(h->k, h->deg, as, fb, sp_stream)
-                                      : eqlb::launch_se_patch_fused(h->k, h->deg, EQLB_SCATTER_SLOTS, as, fb, sp_stream);
-        if (st)
-          return fail(st, "fused patch kernel launch failed (k=%d)", h->k);
-      }
-      if (evs && first_bin == 0)
-        HIP_TRY(hipEventRecord(evs[1], sp_stream));
-    }
-    else
-      for (int b = 0; b < eqlb::MAX_BINS; ++b)
-      {
-        if (bin_np(b) == 0)
-          continue;
-        as.npatch = bin_np(b);
-        as.slot_offset = bin_so(b);
-        as.patch_offset = bin_po(b);
-        if (evs && first_bin == 0)
-          HIP_TRY(hipEventRecord(evs[2 * b], sp_stream));
-        for (int r = 0; r < h->nrhs; ++r)
-        {
-          select_rhs(as, r, true);
-          const int st = eqlb::launch_se_patch(h->k, h->deg, h->bins[b].P, h->solver, EQLB_SCATTER_SLOTS, as, sp_stream, h->mode);
-          if (st)
-            return fail(st, "patch kernel launch failed (k=%d, P=%d)", h->k, h->bins[b].P);
-        }
-        if (evs && first_bin == 0)
-          HIP_TRY(hipEventRecord(evs[2 * b + 1], sp_stream));
-      }
-    if (h->l_npatch > 0 && !rest)
-      if (const int st = run_large(sp_stream))
-        return st;
-    if (h->stress)
-    {
-      // weak symmetry of rows 0, 1 on the patch-local stresses held in the slots
-      // (se/reconstruction.hpp:237-270; the grouped boundary patches of :170-234 are flagged by the
-      // patch builder: PFLAG_WS_SKIP / PFLAG_WS_GROUP)
-      if (evs && first_bin == 0)
-        HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 2], sp_stream));
-      select_rhs(as, 0, true); // the kernel works on the slot rows of RHS 0 and 1
-      // the weak-symmetry kernels address the tensors TE ... VQ of the table buffer by the offsets of DG_{k-1}: with
-      // data of a lower degree the segments in front of them (F, H, D) are shorter, the base pointer moves by the
-      // difference (every read stays inside the buffer; TE ... VQ do not depend on the degree)
-      as.tables = h->tables + eqlb::table_offset_te(h->k, h->deg) - eqlb::table_offset_te(h->k, h->k - 1);
-      // (overlapping groups of boundary patches: one pass per level, a pass skips the patches of other levels)
-      for (int lv = 0; lv < h->ws_levels; ++lv)
-        for (int b = 0; b < eqlb::MAX_BINS; ++b)
-        {
-          if (bin_np(b) == 0)
-            continue;
-          as.npatch = bin_np(b);
-          as.slot_offset = bin_so(b);
-          as.patch_offset = bin_po(b);
-          as.ws_level = lv;
-          const int st = eqlb::launch_se_weaksym(h->k, h->bins[b].P, !h->stress_flux_bcs && h->deg == h->k - 1, as,
-                                                 sp_stream);
-          if (st)
-            return fail(st, "weak-symmetry kernel launch failed (k=%d, P=%d)", h->k, h->bins[b].P);
-        }
-      if (evs && first_bin == 0)
-        HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 3], sp_stream));
-    }
-    if (evs && first_bin == 0)
-      HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS], sp_stream));
-    // blocks that lie behind one another (one array, the usual case) are reduced by one launch
-    bool contiguous = true;
-    for (int r = 1; r < h->nrhs; ++r)
-      contiguous = contiguous && d_x[r] == d_x[0] + r * s_x;
-    const int nlaunch = contiguous ? 1 : h->nrhs, per = contiguous ? h->nrhs : 1;
-    if (rest && sp_phase == 1)
-      return EQLB_OK;
-    if (rest)
-    {
-      // only the cells that a patch of the generic kernels touches (the slot rows of their other vertices are zero)
-      for (int r = 0; r < h->nrhs; ++r)
-        if (eqlb::launch_reduce_slots_cells(h->nrt, m.ncells, h->nrest_cells, h->rest_cells,
-                                            h->slots + (size_t)r * s_slot * 3, d_x[r], sp_stream))
-          return fail(EQLB_ERR_UNSUPPORTED, "compact slot reduction for %d DOFs per cell is not in this build", h->nrt);
-      return EQLB_OK;
-    }
-    for (int l = 0; l < nlaunch; ++l)
-    {
-      const double* sl = h->slots + (size_t)l * s_slot * 3;
-      if (ev_conf)
-        eqlb::launch_ev_reduce(m, h->k, per, h->ev_cell_dofs, h->ev_ndofs, sl, d_x[l], accumulate, h->ev_basis,
-                               (h->ev_basis && h->ev_basis_has_R) ? h->ev_basis + h->nrt * h->nrt : nullptr, sp_stream);
-      else if (eqlb::launch_reduce_slots(h->nrt, m.ncells, per, sl, d_x[l], accumulate, sp_stream))
-        return fail(EQLB_ERR_UNSUPPORTED, "slot reduction for %d DOFs per cell is not in this build", h->nrt);
-    }
-    if (evs && first_bin == 0)
-      HIP_TRY(hipEventRecord(evs[2 * eqlb::MAX_BINS + 1], sp_stream));
-    return EQLB_OK;
-  };
-
-  if (scatter_eff == EQLB_SCATTER_TILED)
-  {
-    if ((h->stress && !stress_fused) || h->solver != EQLB_SOLVER_SHUFFLE || h->ntiles == 0)
-      return fail(EQLB_ERR_UNSUPPORTED,
-                  "the tiled scatter is available for k <= 3 with the shuffle solver (stress: RT_2 without "
-                  "flux boundary conditions on the stress rows)");
-    if (h->tile_first > h->ntiles)
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "tile_first %d beyond the %d tiles", h->tile_first, h->ntiles);
-    const int32_t tcount = (h->tile_count < 0) ? h->ntiles - h->tile_first
-                                               : std::min(h->tile_count, h->ntiles - h->tile_first);
-    eqlb::TileArgs ta{h->t_tiles, h->t_tile_cells, tcount, h->tile_tc,
-                      ev_conf ? h->t_facet_owner : nullptr, h->ev_cell_dofs, h->ev_ndofs, m.nfacets,
-                      h->tile_first, h->accumulate, ev_conf ? h->ev_basis : nullptr,
-                      (ev_conf && h->ev_basis && h->ev_basis_has_R) ? h->ev_basis + h->nrt * h->nrt : nullptr};
-    eqlb::SeArgs at = a;
-    at.slot_cell = h->t_slot_cell;
-    at.slot_info = h->t_slot_info;
-    at.pn = h->t_pn;
-    at.pflag = h->t_pflag;
-    at.npatch_total = h->t_npatch;
-    if (evs)
-      HIP_TRY(hipEventRecord(evs[0], stream));
-    int r0 = 0;
-    // the rest of a fused stress launch (boundary patches, interior patches that are not full, bins of more than 8
-    // lanes): its patch kernels - a handful of small launches, 50 us back to back at 1M triangles - run on a side
-    // stream NEXT TO the fused kernel, their sums are added behind it.  With the FIRST range of tiles of a two-phase
-    // sweep: its patches touch ghost cells like any other, and the caller packs the ghost rows behind that range
-    // (option accumulate = 0: the tiled launches STORE, the rest can only be added behind the last of them; an empty
-    // range - a rank without priority tiles, or with priority tiles only - takes nothing along)
-    const bool with_first_range = tcount > 0 && (h->accumulate ? h->tile_first == 0 : h->tile_first + tcount == h->ntiles);
-    const bool rest_now = stress_fused && h->t_rest > 0
-#ifdef EQLB_EXP_REST_LAST // (the order before the fix, to show that tests/test_gpu_halo.py sees it)
-                          && (h->tile_first + tcount == h->ntiles);
-#else
-                          && with_first_range;
-#endif
-    if (rest_now)
-    {
-      if (!h->side_stream)
-      {
-        HIP_TRY(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-      }
-      HIP_TRY(hipEventRecord(h->ev_fork, stream));
-      HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-      hipEvent_t* keep = evs;
-      evs = nullptr;
-      sp_stream = h->side_stream;
-      sp_phase = 1;
-      const int st = run_slot_path(-1, 1);
-      sp_stream = stream;
-      sp_phase = 0;
-      evs = keep;
-      if (st)
-        return st;
-      HIP_TRY(hipEventRecord(h->ev_join, h->side_stream));
-    }
-    if (stress_fused)
-    {
-      // rows 0, 1 of the stress and their weak symmetry in one launch
-      select_rhs(at, 0, false);
-      const int st = eqlb::launch_se_stress_tiled(at, ta, d_g.data(), d_f.data(), d_x.data(), stream, h->t_mixed);
-      if (st)
-        return fail(st, "fused stress kernel launch failed");
-      r0 = 2;
-    }
-    if (h->multi_rhs && h->nrhs - r0 > 1)
-    {
-      // all (remaining) right-hand sides in one launch per chunk of MULTI_RHS_MAX
-      for (int rb = r0; rb < h->nrhs; rb += eqlb::MULTI_RHS_MAX)
-      {
-        eqlb::MultiRhs mr{};
-        mr.n = std::min(eqlb::MULTI_RHS_MAX, h->nrhs - rb);
-        mr.rhs0 = rb;
-        for (int i = 0; i < mr.n; ++i)
-        {
-          mr.g[i] = d_g[rb + i];
-          mr.f[i] = d_f[rb + i];
-          mr.x[i] = d_x[rb + i];
-        }
-        select_rhs(at, rb, false);
-        const int st = eqlb::launch_se_patch_tiled_multi(h->k, h->deg, h->mode, at, ta, mr, stream);
-        if (st)
-          return fail(st, "tiled multi-RHS patch kernel launch failed (k=%d)", h->k);
-      }
-    }
-    else
-      for (int r = r0; r < h->nrhs; ++r)
-      {
-        select_rhs(at, r, false);
-        const int st = eqlb::launch_se_patch_tiled(h->k, h->deg, h->mode, at, ta, stream);
-        if (st)
-          return fail(st, "tiled patch kernel launch failed (k=%d)", h->k);
-      }
-    if (evs)
-      HIP_TRY(hipEventRecord(evs[1], stream));
-    if (h->l_npatch > 0 && with_first_range)
-    {
-      // The tiles treat the node of a large patch like a masked node (TileDesc::zero): its rows are missing from what
-      // they wrote.  The large-patch kernel puts them into the slot buffer - every other row of it is zero - and a
-      // compact reduction over the cells of those patches (EV: the conforming reduction) ADDS them behind the tiles.
-      // (EV: k_ev_reduce runs over the whole mesh - 3 nrt doubles per cell and right-hand side, zeros but for the hub's
-      // cells, correct and in fixed order; a conforming reduction over l_cells and their facets is the follow-up)
-      if (const int st = ensure_slots(eqlb::MAX_BINS, stream))
-        return st;
-      if (const int st = run_large(stream))
-        return st;
-      for (int r = 0; r < h->nrhs; ++r)
-      {
-        const double* sl = h->slots + (size_t)r * s_slot * 3;
-        if (ev_conf)
-          eqlb::launch_ev_reduce(m, h->k, 1, h->ev_cell_dofs, h->ev_ndofs, sl, d_x[r], 1, h->ev_basis,
-                                 (h->ev_basis && h->ev_basis_has_R) ? h->ev_basis + h->nrt * h->nrt : nullptr, stream);
-        else if (eqlb::launch_reduce_slots_cells(h->nrt, m.ncells, h->l_ncells, h->l_cells, sl, d_x[r], stream))
-          return fail(EQLB_ERR_UNSUPPORTED, "compact slot reduction for %d DOFs per cell is not in this build", h->nrt);
-      }
-    }
-    if (rest_now)
-    {
-      HIP_TRY(hipStreamWaitEvent(stream, h->ev_join, 0));
-      hipEvent_t* keep = evs;
-      evs = nullptr;
-      sp_phase = 2;
-      const int st = run_slot_path(-1, 1);
-      sp_phase = 0;
-      evs = keep;
-      if (st)
-        return st;
-    }
-  }
-  else if (scatter_eff == EQLB_SCATTER_SLOTS)
-  {
-    const int st = run_slot_path(0, h->accumulate);
-    if (st)
-      return st;
-  }
-  else
-  {
-    // fp64 global atomics straight into flux_hdiv
-    if (h->stress)
-      return fail(EQLB_ERR_UNSUPPORTED, "stress equilibration needs the slot or the tiled scatter");
-    eqlb::SeArgs aa = a;
-    if (h->fused && h->solver == EQLB_SOLVER_SHUFFLE && h->k <= 3)
-    {
-      eqlb::FusedBins fb{};
-      int64_t nb = 0;
-      for (int b = 0; b < eqlb::MAX_BINS; ++b)
-      {
-        fb.block_start[b] = nb;
-        fb.npatch[b] = h->bins[b].npatch;
-        fb.slot_offset[b] = h->bins[b].slot_offset;
-        fb.patch_offset[b] = h->bins[b].patch_offset;
-        nb += (h->bins[b].npatch * h->bins[b].P + 255) / 256;
-      }
-      fb.block_start[eqlb::MAX_BINS] = nb;
-      for (int r = 0; r < h->nrhs; ++r)
-      {
-        select_rhs(aa, r, false);
-        if (evs && r == 0)
-          HIP_TRY(hipEventRecord(evs[0], stream));
-        const int st = eqlb::launch_se_patch_fused(h->k, h->deg, scatter_eff, aa, fb, stream);
-        if (st)
-          return fail(st, "fused patch kernel launch failed (k=%d)", h->k);
-      }
-      if (evs)
-        HIP_TRY(hipEventRecord(evs[1], stream));
-    }
-    else
-      for (int b = 0; b < eqlb::MAX_BINS; ++b)
-      {
-        if (h->bins[b].npatch == 0)
-          continue;
-        aa.npatch = h->bins[b].npatch;
-        aa.slot_offset = h->bins[b].slot_offset;
-        aa.patch_offset = h->bins[b].patch_offset;
-        if (evs)
-          HIP_TRY(hipEventRecord(evs[2 * b], stream));
-        for (int r = 0; r < h->nrhs; ++r)
-        {
-          select_rhs(aa, r, false);
-          const int st = eqlb::launch_se_patch(h->k, h->deg, h->bins[b].P, h->solver, scatter_eff, aa, stream);
-          if (st)
-            return fail(st, "patch kernel launch failed (k=%d, P=%d)", h->k, h->bins[b].P);
-        }
-        if (evs)
-          HIP_TRY(hipEventRecord(evs[2 * b + 1], stream));
-      }
-  }
-  if (evs)
-    ++h->ev_calls;
-  HIP_TRY(hipGetLastError());
-
-  if (memspace == EQLB_MEM_HOST)
-  {
-    for (int r = 0; r < h->nrhs; ++r)
-      HIP_TRY(hipMemcpyAsync(x_io[r], d_x[r], s_x * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    int32_t status = 0;
-    HIP_TRY(hipMemcpy(&status, h->status, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (status)
-    {
-      (void)hipMemset(h->status, 0, sizeof(int32_t));
-      return fail(EQLB_ERR_SINGULAR, "patch system not positive definite");
-    }
-  }
-  return EQLB_OK;
-}
-
-int eqlb_se_equilibrate_lists(eqlb_se_t* h, const double* const* flux_dg, const double* const* rhs_dg,
-                              double* const* flux_hdiv, int32_t memspace, void* stream)
-try
-{
-  return equilibrate_lists(h, flux_dg, rhs_dg, flux_hdiv, memspace, stream);
-}
-EQLB_CATCH_ALL
-
-int eqlb_se_equilibrate(eqlb_se_t* h, const double* flux_dg, const double* rhs_dg,
-                        double* flux_hdiv, int32_t memspace, void* stream_)
-try
-{
-  if (!h || !flux_dg || !rhs_dg || !flux_hdiv)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  const eqlb::DeviceMesh& m = h->mesh->m;
-  const size_t s_g = (size_t)m.ncells * h->nd * 2, s_f = (size_t)m.ncells * h->nd;
-  const size_t s_x = (h->mode == 1 && h->ev_output == 0) ? (size_t)h->ev_ndofs : (size_t)m.ncells * h->nrt;
-  std::vector<const double*> g(h->nrhs), f(h->nrhs);
-  std::vector<double*> x(h->nrhs);
-  for (int r = 0; r < h->nrhs; ++r)
-  {
-    g[r] = flux_dg + r * s_g;
-    f[r] = rhs_dg + r * s_f;
-    x[r] = flux_hdiv + r * s_x;
-  }
-  return equilibrate_lists(h, g.data(), f.data(), x.data(), memspace, stream_);
-}
-EQLB_CATCH_ALL
-
-int eqlb_se_check_status(eqlb_se_t* h, void* stream_)
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_check_status: null handle");
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  int32_t status = 0;
-  HIP_TRY(hipMemcpyAsync(&status, h->status, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (status)
-  {
-    HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(int32_t), stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return fail(EQLB_ERR_SINGULAR, "patch system not positive definite");
-  }
-  return EQLB_OK;
-}
-
-double eqlb_se_last_kernel_ms(const eqlb_se_t* h, int32_t which)
-{
-  // which = b (0..4): patch kernel of bin b (P = 4 << b); 5: slot reduction; 6: weak-symmetry kernels; 7: large-patch kernel.
-  // Average device time per launch over the calls recorded since timing was enabled
-  // (at most the last EV_RING calls).  Synchronises with the recorded events.
-  if (!h || !h->ev || h->ev_calls == 0 || which < 0 || which > eqlb::MAX_BINS + 2)
-    return 0.0;
-  if (which == eqlb::MAX_BINS + 1 && !h->stress)
-    return 0.0;
-  if (which == eqlb::MAX_BINS + 2 && (h->l_npatch == 0 || h->scatter_last == EQLB_SCATTER_ATOMIC))
-    return 0.0; // 7: the large-patch kernel (all right-hand sides of a call)
-  const bool fused_run = (h->mode == 1 && h->k <= 3) || h->scatter_last == EQLB_SCATTER_TILED
-                         || (h->fused && h->solver == EQLB_SOLVER_SHUFFLE && h->k <= 3);
-  if (which < eqlb::MAX_BINS && ((fused_run && which != 0) || (!fused_run && h->bins[which].npatch == 0)))
-    return 0.0;
-  if (which == eqlb::MAX_BINS && h->scatter_last != EQLB_SCATTER_SLOTS)
-    return 0.0;
-  const int64_t nset = std::min<int64_t>(h->ev_calls, eqlb_se::EV_RING);
-  double sum = 0.0;
-  for (int64_t s = 0; s < nset; ++s)
-  {
-    hipEvent_t* evs = h->ev + s * eqlb_se::EV_PER_SET;
-    float ms = 0.f;
-    if (hipEventSynchronize(evs[2 * which + 1]) != hipSuccess
-        || hipEventElapsedTime(&ms, evs[2 * which], evs[2 * which + 1]) != hipSuccess)
-      return 0.0;
-    sum += ms;
-  }
-  return sum / (double)nset;
-}
 
 int eqlb_project_dg(eqlb_mesh_t* mesh, int32_t degree, int32_t bs, int32_t nrhs, int32_t nq,
                     const double* qpoints, const double* qweights, const double* qvalues,
@@ -2952,39 +1511,7 @@ try
 }
 EQLB_CATCH_ALL
 
-int eqlb_ev_equilibrate(eqlb_ev_t* h, const double* flux_dg, const double* rhs_dg,
-                        double* flux_hdiv, int32_t memspace, void* stream)
-try
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  return eqlb_se_equilibrate(h->se, flux_dg, rhs_dg, flux_hdiv, memspace, stream);
-}
-EQLB_CATCH_ALL
-
-int eqlb_ev_equilibrate_lists(eqlb_ev_t* h, const double* const* flux_dg, const double* const* rhs_dg,
-                              double* const* flux_hdiv, int32_t memspace, void* stream)
-try
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  return equilibrate_lists(h->se, flux_dg, rhs_dg, flux_hdiv, memspace, stream);
-}
-EQLB_CATCH_ALL
-
 int64_t eqlb_ev_num_patches(const eqlb_ev_t* h) { return h ? h->se->npatch_total : 0; }
-
-int eqlb_ev_check_status(eqlb_ev_t* h, void* stream)
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_check_status: null handle");
-  return eqlb_se_check_status(h->se, stream);
-}
-
-double eqlb_ev_last_kernel_ms(const eqlb_ev_t* h, int32_t which)
-{
-  return h ? eqlb_se_last_kernel_ms(h->se, which) : 0.0;
-}
 
 int eqlb_ev_large_patch_info(const eqlb_ev_t* h, int64_t* npatches, int32_t* max_cells)
 {

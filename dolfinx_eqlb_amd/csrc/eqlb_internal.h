@@ -421,8 +421,27 @@ struct eqlb_se
   // staging for host-memory calls
   double *d_flux_dg = nullptr, *d_rhs_dg = nullptr, *d_flux_hdiv = nullptr;
   double *d_cks = nullptr, *d_korn = nullptr; // Korn estimate: per node / staging per cell
-  // timing ("timing" option): ring of event sets, one set per equilibrate call
-  static constexpr int EV_RING = 64, EV_PER_SET = 2 * eqlb::MAX_BINS + 6;
-  hipEvent_t* ev = nullptr; // [EV_RING][EV_PER_SET]: bin b start/end at 2b, 2b+1; reduce start/end; weak symmetry start/end; large-patch kernel start/end
+  // timing ("timing" option): ring of event sets, one set per equilibrate call.  A set holds a begin and an end event
+  // per timing slot; the slots are the `which` of eqlb_se_last_kernel_ms
+  enum EvSlot
+  {
+    EV_BIN0 = 0,                // patch kernel of bin b: EV_BIN0 + b (a launch of all bins at once: EV_BIN0)
+    EV_REDUCE = eqlb::MAX_BINS, // slot reduction
+    EV_WEAKSYM,                 // weak-symmetry kernels
+    EV_LARGE,                   // large-patch kernel
+    EV_NSLOTS
+  };
+  static constexpr int ev_begin(int slot) { return 2 * slot; }
+  static constexpr int ev_end(int slot) { return 2 * slot + 1; }
+  static constexpr int EV_RING = 64, EV_PER_SET = 2 * EV_NSLOTS;
+  hipEvent_t* ev = nullptr; // [EV_RING][EV_PER_SET]
   int64_t ev_calls = 0;     // calls recorded since timing was (re)enabled
 };
+
+namespace eqlb
+{
+// host side of the tiling (eqlb_tiling_host.hip): the tiled SoA of the handle from the bins of its nodes.  Nodes of
+// bins >= max_bin are left to another path; full_only: so are all patches that are not full
+int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, BuildArgs a, int tc_fixed = 0,
+                int max_bin = MAX_BINS, bool full_only = false);
+} // namespace eqlb
