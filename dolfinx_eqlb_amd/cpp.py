@@ -251,6 +251,15 @@ class SemiExplicitEquilibrator:
                                                         _hp(korn), C.c_int32(MEM_HOST), None))
         return flux_hdiv, korn
 
+    def kornconst_host(self, korn=None):
+        """eqlb_se_kornconst: the squared Korn constants of the patches added to korn [ncells] (host memory)."""
+        m = self.dmesh.mesh
+        if korn is None:
+            korn = np.zeros(m.ncells)
+        assert korn.dtype == np.float64 and korn.flags.c_contiguous and korn.size == m.ncells
+        _check(lib().eqlb_se_kornconst(self._h, _hp(korn), C.c_int32(MEM_HOST), None))
+        return korn
+
     def equilibrate_device(self, flux_dg_ptr: int, rhs_dg_ptr: int, flux_hdiv_ptr: int,
                            stream: int = 0):
         """Raw device pointers (e.g. torch tensor .data_ptr()) and a hipStream_t handle;

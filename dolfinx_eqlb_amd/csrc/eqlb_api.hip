@@ -62,6 +62,12 @@ void free_boundary(eqlb_se* h)
   dfree(h->l_pflag);
   dfree(h->l_cells);
   dfree(h->l_ws);
+  dfree(h->l_nodes);
+  dfree(h->l_wsym_off);
+  dfree(h->l_wsym_ws);
+  dfree(h->l_rest_cells);
+  h->l_nrest_cells = 0;
+  h->l_stress = false;
   h->l_npatch = h->l_nslots = h->l_ncells = 0;
   h->l_maxcells = 0;
   dfree(h->t_tiles);
@@ -437,6 +443,13 @@ int eqlb_se_set_option(eqlb_se_t* h, const char* key, int32_t value)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "large_patches must be 0 or 1");
     h->large_patches = value;
   }
+  else if (!strcmp(key, "large_patches_stress"))
+  {
+    // takes effect at the next eqlb_se_set_boundary, on a handle with "large_patches" = 1
+    if (value != 0 && value != 1)
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "large_patches_stress must be 0 or 1");
+    h->large_patches_stress = value;
+  }
   else if (!strcmp(key, "tile_first"))
   {
     if (value < 0)
@@ -516,7 +529,7 @@ try
                     m.h_node_ncells[i]);
       // option "large_patches": the patch goes to the multi-wave kernel (a CSR-style SoA of its own, below); its node
       // stays out of the bins and is, for the tiles, a node that another path equilibrates
-      if (h->stress)
+      if (h->stress && !h->large_patches_stress)
         return fail(EQLB_ERR_PATCH_TOO_LARGE,
                     "Patch around node %d has %d cells: the stress equilibration (weak symmetry, Korn constants) is "
                     "limited to 63 cells per patch, \"large_patches\" covers flux equilibration only",
@@ -608,6 +621,14 @@ try
     const int stg = find_stress_groups(m, facet_type, node_mask, ws, grp, lvl, h->ws_levels, any);
     if (stg)
       return stg;
+    // a large patch inside a group (its two-cell members never are large): the weak-symmetry kernel of the large
+    // patches does not read the rows of other patches
+    for (int32_t nd : large_nodes)
+      if (any && ws[nd] != 0)
+        return fail(EQLB_ERR_UNSUPPORTED,
+                    "Patch around node %d has %d cells and is the internal patch of group %d of boundary patches with "
+                    "tractions on both stress rows: groups are limited to 63 cells per patch (\"large_patches_stress\")",
+                    nd, m.h_node_ncells[nd], grp[nd]);
     if (any)
     {
       if (upload(&h->node_ws, ws.data(), ws.size()) || upload(&h->node_group, grp.data(), grp.size())
@@ -668,6 +689,16 @@ try
     stl |= upload<uint8_t>(&h->l_pflag, nullptr, (size_t)nl * h->nrhs);
     stl |= upload(&h->l_cells, lc.data(), lc.size());
     stl |= upload<double>(&h->l_ws, nullptr, eqlb::large_patch_ws_doubles(h->k, acc, nl));
+    stl |= upload(&h->l_nodes, large_nodes.data(), large_nodes.size());
+    if (h->stress)
+    {
+      // work space of the weak-symmetry kernel: per patch, quadratic in its cells (the Schur matrix)
+      std::vector<int64_t> woff(nl + 1, 0);
+      for (int64_t p = 0; p < nl; ++p)
+        woff[p + 1] = woff[p] + (int64_t)eqlb::large_patch_weaksym_ws_doubles(h->k, m.h_node_ncells[large_nodes[p]]);
+      stl |= upload(&h->l_wsym_off, woff.data(), (size_t)nl);
+      stl |= upload<double>(&h->l_wsym_ws, nullptr, (size_t)woff[nl]);
+    }
     stl |= upload(&d_lslot, lslot.data(), lslot.size());
     stl |= upload(&d_lpatch, lpatch.data(), lpatch.size());
     hipError_t e = hipSuccess;
@@ -697,6 +728,7 @@ try
     h->l_npatch = nl;
     h->l_nslots = acc;
     h->l_ncells = (int64_t)lc.size();
+    h->l_stress = h->large_patches_stress != 0;
     tm.lap("large-patch SoA");
   }
   h->t_stress = h->stress && stress_fused_ok && h->mode == 0;
@@ -739,6 +771,25 @@ try
       HIP_TRY(hipDeviceSynchronize());
     }
   }
+  if (h->t_stress && h->l_npatch > 0)
+  {
+    // fused stress launch: the rows of the rest and of the large patches go through the slot buffer together; one
+    // compact reduction over the cells that either of them touches
+    std::vector<uint8_t> touched(m.nnodes, 0);
+    for (int32_t i = 0; i < m.nnodes; ++i)
+      touched[i] = (!node_mask || node_mask[i]) && (node_bin[i] < 0 || node_bin[i] >= 2 || (!h->t_mixed && !is_full(i)));
+    std::vector<int32_t> rc;
+    for (int32_t c = 0; c < m.ncells; ++c)
+      for (int j = 0; j < 3; ++j)
+        if (touched[m.h_cell_nodes[3 * (size_t)c + j]])
+        {
+          rc.push_back(c);
+          break;
+        }
+    h->l_nrest_cells = (int64_t)rc.size();
+    if (upload(&h->l_rest_cells, rc.data(), rc.size()))
+      return EQLB_ERR_DEVICE;
+  }
   tm.lap("tiles (total)");
   h->boundary_set = true;
   return EQLB_OK;
@@ -752,7 +803,7 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
   if (!h->boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_kornconst: boundary data not set");
-  if (h->l_npatch > 0)
+  if (h->l_npatch > 0 && !h->l_stress)
     return fail(EQLB_ERR_PATCH_TOO_LARGE,
                 "eqlb_se_kornconst: the Korn constants are limited to 63 cells per patch, \"large_patches\" covers flux "
                 "equilibration only");
@@ -769,7 +820,8 @@ try
     d_korn = h->d_korn;
   }
   eqlb::launch_korn(m, h->node_slot, h->node_patch, h->slot_cell, h->slot_info, h->pn, h->pflag,
-                    h->d_cks, d_korn, stream);
+                    h->d_cks, d_korn, stream, h->l_npatch, h->l_nodes, h->l_off, h->l_slot_cell, h->l_slot_info,
+                    h->l_pflag);
   HIP_TRY(hipGetLastError());
   if (memspace == EQLB_MEM_HOST)
   {

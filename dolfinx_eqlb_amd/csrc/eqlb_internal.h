@@ -252,6 +252,12 @@ int tile_cells_max_of(int k);
 int launch_se_patch_large(int k, int deg, int mode, const SeArgs& a, const int32_t* off, double* ws,
                           hipStream_t stream);
 size_t large_patch_ws_doubles(int k, int64_t nslots, int64_t npatch);
+// weak symmetry of the stress rows 0, 1 on the large patches (eqlb_se_weaksym_large.hip, RT_2 ... RT_4): a addresses the
+// large-patch SoA as for launch_se_patch_large, a.out the slot buffer that holds the rows of that kernel; patch p works in
+// ws + wsoff[p], large_patch_weaksym_ws_doubles(k, cells of the patch) doubles (quadratic in the cells: the Schur matrix)
+int launch_se_weaksym_large(int k, const SeArgs& a, const int32_t* off, const int64_t* wsoff, double* ws,
+                            hipStream_t stream);
+size_t large_patch_weaksym_ws_doubles(int k, int64_t ncells_of_patch);
 int launch_se_weaksym(int k, int P, bool no_flux_bcs, const SeArgs& a, hipStream_t stream);
 // RT_4 with P >= 16 and RT_3 with P = 64 (banded chain + border, eqlb_se_weaksym_banded.hip)
 int launch_se_weaksym_banded(int k, int P, const SeArgs& a, hipStream_t stream);
@@ -279,9 +285,12 @@ int projection_matrix_host(int degree, int nq, const double* pts, const double* 
                            std::vector<double>& Pm);
 void launch_project_dg(int64_t ncells, int nd, int nq, int bs, const double* Pm, const double* qv,
                        double* out, hipStream_t stream);
+// l_npatch > 0: the fans of the large patches as well, through their SoA (l_nodes: the patch nodes)
 void launch_korn(const DeviceMesh& m, const int64_t* node_slot, const int64_t* node_patch,
                  const int32_t* slot_cell, const uint32_t* slot_info, const uint8_t* pn,
-                 const uint8_t* pflag, double* cks, double* korn, hipStream_t stream);
+                 const uint8_t* pflag, double* cks, double* korn, hipStream_t stream, int64_t l_npatch = 0,
+                 const int32_t* l_nodes = nullptr, const int32_t* l_off = nullptr, const int32_t* l_slot_cell = nullptr,
+                 const uint32_t* l_slot_info = nullptr, const uint8_t* l_pflag = nullptr);
 // estimator step (eqlb_estimate.hip); flux_dg / rhs_dg in DG_deg, 0 <= deg <= k - 1
 int launch_estimate(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                     const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
@@ -415,6 +424,14 @@ struct eqlb_se
   int32_t* l_cells = nullptr;       // cells with a vertex whose patch is a large one (compact reduction)
   int64_t l_ncells = 0;
   double* l_ws = nullptr;           // work space of k_se_patch_large
+  // option "large_patches_stress": weak symmetry and Korn constants on the large patches as well
+  int large_patches_stress = 0;
+  bool l_stress = false;            // value of the option at the last eqlb_se_set_boundary (with "large_patches" = 1)
+  int32_t* l_nodes = nullptr;       // [l_npatch] patch nodes (Korn constants)
+  int64_t* l_wsym_off = nullptr;    // [l_npatch] first double of the patch in l_wsym_ws (stress handles)
+  double* l_wsym_ws = nullptr;      // work space of k_se_weaksym_large
+  int32_t* l_rest_cells = nullptr;  // fused stress launch: rest_cells and l_cells merged (one compact reduction)
+  int64_t l_nrest_cells = 0;
   double* slots = nullptr;          // [nrhs][ncells][3][nrt]
   int slots_first_bin = 0;          // the slot rows of the bins >= this one hold values of the last slot-path run
   int32_t* status = nullptr;

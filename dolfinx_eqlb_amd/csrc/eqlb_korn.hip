@@ -21,6 +21,11 @@ struct KornArgs
   const uint8_t* pn;
   const uint8_t* pflag;       // rhs 0
   double* cks;                // [nnodes]
+  // large patches (nullptr: the plain SoA above): thread p walks the fan of patch p of the large-patch SoA - slot_cell /
+  // slot_info / pflag are then that SoA's, the cell count is the difference of its CSR offsets
+  const int32_t* l_nodes;     // [nlarge] patch nodes
+  const int32_t* l_off;       // [nlarge + 1]
+  int32_t nlarge;
 };
 
 __device__ inline void xy(const double* x, int32_t node, double& a, double& b)
@@ -31,17 +36,19 @@ __device__ inline void xy(const double* x, int32_t node, double& a, double& b)
 
 __global__ void __launch_bounds__(256) k_korn_patch(KornArgs a)
 {
-  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
-  if (node >= a.nnodes)
+  const int32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool large = a.l_nodes != nullptr;
+  if (idx >= (large ? a.nlarge : a.nnodes))
     return;
-  const int64_t slot0 = a.node_slot[node];
+  const int32_t node = large ? a.l_nodes[idx] : idx;
+  const int64_t slot0 = large ? (int64_t)a.l_off[idx] : a.node_slot[node];
   if (slot0 < 0)
   {
     a.cks[node] = 0.0;
     return;
   }
-  const int64_t patch = a.node_patch[node];
-  const int n = a.pn[patch];
+  const int64_t patch = large ? (int64_t)idx : a.node_patch[node];
+  const int n = large ? (int)(a.l_off[idx + 1] - a.l_off[idx]) : (int)a.pn[patch];
   const bool interior = (a.pflag[patch] & PFLAG_INTERIOR) != 0;
   const double pi = 3.14159265358979323846;
   double xi0, xi1;
@@ -164,10 +171,20 @@ k_korn_cells(int32_t ncells, const int32_t* cell_nodes, const double* cks, doubl
 
 void launch_korn(const DeviceMesh& m, const int64_t* node_slot, const int64_t* node_patch,
                  const int32_t* slot_cell, const uint32_t* slot_info, const uint8_t* pn,
-                 const uint8_t* pflag, double* cks, double* korn, hipStream_t stream)
+                 const uint8_t* pflag, double* cks, double* korn, hipStream_t stream, int64_t l_npatch,
+                 const int32_t* l_nodes, const int32_t* l_off, const int32_t* l_slot_cell, const uint32_t* l_slot_info,
+                 const uint8_t* l_pflag)
 {
-  KornArgs a{m.nnodes, m.ncells, m.x, m.cell_nodes, node_slot, node_patch, slot_cell, slot_info, pn, pflag, cks};
+  KornArgs a{m.nnodes, m.ncells, m.x,  m.cell_nodes, node_slot, node_patch, slot_cell, slot_info, pn, pflag, cks,
+             nullptr,  nullptr,  0};
   hipLaunchKernelGGL(k_korn_patch, dim3((m.nnodes + 255) / 256), dim3(256), 0, stream, a);
+  if (l_npatch > 0)
+  {
+    // behind the launch above, which wrote 0 for the nodes of the large patches
+    KornArgs al{m.nnodes, m.ncells, m.x,     m.cell_nodes, nullptr,         nullptr, l_slot_cell, l_slot_info, nullptr,
+                l_pflag,  cks,      l_nodes, l_off,        (int32_t)l_npatch};
+    hipLaunchKernelGGL(k_korn_patch, dim3((unsigned)((l_npatch + 255) / 256)), dim3(256), 0, stream, al);
+  }
   hipLaunchKernelGGL(k_korn_cells, dim3((m.ncells + 255) / 256), dim3(256), 0, stream, m.ncells,
                      m.cell_nodes, cks, korn);
 }

@@ -294,6 +294,28 @@ int launch_large(const Sweep& s, hipStream_t st, hipEvent_t* evs)
   return mark_end(evs, eqlb_se::EV_LARGE, st);
 }
 
+// Weak symmetry of rows 0, 1 on the large patches: one launch for all of them, behind launch_large (it corrects the slot
+// rows that kernel wrote) and before the reduction that consumes them.  Timing slot of the weak-symmetry kernels:
+// `begin` opens it, else the launch extends the slot that launch_weaksym has opened on this stream
+int launch_weaksym_large(const Sweep& s, hipStream_t st, hipEvent_t* evs, bool begin)
+{
+  const eqlb_se* h = s.h;
+  eqlb::SeArgs al = s.a;
+  al.slot_cell = h->l_slot_cell;
+  al.slot_info = h->l_slot_info;
+  al.pn = nullptr;
+  al.pflag = h->l_pflag;
+  al.npatch_total = h->l_npatch;
+  select_rhs(s, al, 0, true);
+  al.tables = h->tables + eqlb::table_offset_te(h->k, h->deg) - eqlb::table_offset_te(h->k, h->k - 1); // as launch_weaksym
+  if (begin)
+    EQLB_TRY(mark_begin(evs, eqlb_se::EV_WEAKSYM, st));
+  const int st_ = eqlb::launch_se_weaksym_large(h->k, al, h->l_off, h->l_wsym_off, h->l_wsym_ws, st);
+  if (st_)
+    return fail(st_, "weak-symmetry kernel launch of the large patches failed (k=%d)", h->k);
+  return mark_end(evs, eqlb_se::EV_WEAKSYM, st);
+}
+
 // Weak symmetry of rows 0, 1 on the patch-local stresses held in the slots
 // (se/reconstruction.hpp:237-270; the grouped boundary patches of :170-234 are flagged by the
 // patch builder: PFLAG_WS_SKIP / PFLAG_WS_GROUP)
@@ -374,6 +396,8 @@ int sweep_slots(const Sweep& s)
     EQLB_TRY(launch_large(s, s.stream, s.evs));
   if (h->stress)
     EQLB_TRY(launch_weaksym(s, pr, s.stream, s.evs));
+  if (h->stress && h->l_npatch > 0)
+    EQLB_TRY(launch_weaksym_large(s, s.stream, s.evs, false));
   EQLB_TRY(mark_begin(s.evs, eqlb_se::EV_REDUCE, s.stream));
   EQLB_TRY(reduce_all(s, s.stream));
   return mark_end(s.evs, eqlb_se::EV_REDUCE, s.stream);
@@ -445,7 +469,10 @@ int sweep_tiled(const Sweep& s)
   // The rest of a fused stress launch (boundary patches, interior patches that are not full, bins of more than 8
   // lanes): its patch kernels - a handful of small launches, 50 us back to back at 1M triangles - run on a side
   // stream NEXT TO the fused kernel, untimed; their sums are added behind it
-  const bool rest_now = s.stress_fused && h->t_rest > 0 && with_first_range;
+  // The large patches of a stress handle go the same way, behind the rest: flux rows, then their weak symmetry (both
+  // timed: the slots of the large-patch kernel and of the weak-symmetry kernels)
+  const bool large_now = h->l_npatch > 0 && with_first_range;
+  const bool rest_now = s.stress_fused && with_first_range && (h->t_rest > 0 || large_now);
   if (rest_now)
   {
     if (!h->side_stream)
@@ -458,8 +485,16 @@ int sweep_tiled(const Sweep& s)
     HIP_TRY(hipEventRecord(h->ev_fork, s.stream));
     HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
     EQLB_TRY(ensure_slots(s, COVER_REST, h->side_stream));
-    EQLB_TRY(launch_patches(s, rest, EQLB_SCATTER_SLOTS, h->side_stream, nullptr));
-    EQLB_TRY(launch_weaksym(s, rest, h->side_stream, nullptr));
+    if (h->t_rest > 0)
+    {
+      EQLB_TRY(launch_patches(s, rest, EQLB_SCATTER_SLOTS, h->side_stream, nullptr));
+      EQLB_TRY(launch_weaksym(s, rest, h->side_stream, nullptr));
+    }
+    if (large_now)
+    {
+      EQLB_TRY(launch_large(s, h->side_stream, s.evs));
+      EQLB_TRY(launch_weaksym_large(s, h->side_stream, s.evs, true));
+    }
     HIP_TRY(hipEventRecord(h->ev_join, h->side_stream));
   }
   int r0 = 0;
@@ -474,7 +509,7 @@ int sweep_tiled(const Sweep& s)
   }
   EQLB_TRY(launch_tiled_rhs(s, at, ta, r0));
   EQLB_TRY(mark_end(s.evs, eqlb_se::EV_BIN0, s.stream));
-  if (h->l_npatch > 0 && with_first_range)
+  if (large_now && !s.stress_fused)
   {
     // The tiles treat the node of a large patch like a masked node (TileDesc::zero): its rows are missing from what
     // they wrote.  The large-patch kernel puts them into the slot buffer - every other row of it is zero - and a
@@ -487,7 +522,10 @@ int sweep_tiled(const Sweep& s)
   {
     // only the cells that a patch of the generic kernels touches
     HIP_TRY(hipStreamWaitEvent(s.stream, h->ev_join, 0));
-    EQLB_TRY(reduce_cells(s, h->nrest_cells, h->rest_cells, s.stream));
+    if (large_now)
+      EQLB_TRY(reduce_cells(s, h->l_nrest_cells, h->l_rest_cells, s.stream));
+    else
+      EQLB_TRY(reduce_cells(s, h->nrest_cells, h->rest_cells, s.stream));
   }
   return EQLB_OK;
 }

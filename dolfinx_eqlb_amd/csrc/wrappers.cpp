@@ -315,7 +315,8 @@ struct BoundaryData
   int se_degree_dg = -1;
   int ev_degree_dg = -1;
   // options set through set_option: applied behind eqlb_*_create and before eqlb_*_set_boundary, so they also reach
-  // a handle that does not exist yet or is rebuilt for another degree ("large_patches" acts in set_boundary)
+  // a handle that does not exist yet or is rebuilt for another degree ("large_patches" and "large_patches_stress" act
+  // in set_boundary)
   std::vector<std::pair<std::string, int>> se_options, ev_options;
 
   BoundaryData(std::vector<std::vector<std::shared_ptr<FluxBC>>>& list_bcs,
@@ -531,8 +532,9 @@ struct BoundaryData
   {
     // The option is checked at once - on the handle if there is one, else on a throw-away handle - and only a valid
     // one is kept (one entry per key) for handles created or rebuilt later.  "large_patches" acts in
-    // eqlb_*_set_boundary: an existing handle is dropped and rebuilt with it on the next call.
-    const bool rebuild = key == "large_patches";
+    // eqlb_*_set_boundary, and so does "large_patches_stress" (SE handles only): an existing handle is dropped and
+    // rebuilt with it on the next call.
+    const bool rebuild = key == "large_patches" || key == "large_patches_stress";
     auto keep = [&](std::vector<std::pair<std::string, int>>& opts) {
       for (auto& o : opts)
         if (o.first == key)

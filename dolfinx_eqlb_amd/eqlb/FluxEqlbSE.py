@@ -79,6 +79,9 @@ class FluxEqlbSE:
                                           list_bfct_prime, self.equilibrate_stresses)
         if self.large_patches:
             self.boundary_data.set_option("large_patches", 1)
+            if self.equilibrate_stresses or self.estimate_korn_constant:
+                # weak symmetry and Korn constants on those patches as well
+                self.boundary_data.set_option("large_patches_stress", 1)
         self.facet_type = self.boundary_data.facet_type
 
     def equilibrate_fluxes(self):

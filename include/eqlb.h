@@ -33,7 +33,8 @@ extern "C" {
 #define EQLB_ERR_DEVICE (-4)           /* HIP runtime failure / no device */
 #define EQLB_ERR_PATCH_TOO_LARGE (-5)  /* patch with more than 63 cells or more than 64 facets on a handle without the \
                                          option "large_patches" (one wavefront per patch); with the option: on a     \
-                                         stress handle and on an EV handle at RT_4, which stay limited to 63 cells   */
+                                         stress handle and for the Korn constants unless "large_patches_stress" is   \
+                                         set as well, and on an EV handle at RT_4, which stays limited to 63 cells   */
 #define EQLB_ERR_SINGULAR (-6)         /* patch system not positive definite (incompatible data) */
 #define EQLB_ERR_NO_MEMORY (-7)        /* host allocation failed during set-up */
 
@@ -134,7 +135,15 @@ void eqlb_se_destroy(eqlb_se_t* handle);
  * bits.  Flux equilibration RT_1 ... RT_4 with every data degree, slot and tiled scatter; the atomic scatter is
  * refused with EQLB_ERR_UNSUPPORTED when a large patch is present, a stress handle and eqlb_se_kornconst with
  * EQLB_ERR_PATCH_TOO_LARGE.  On
- * a mesh without such a patch the option changes nothing: the same launches, the same bits). */
+ * a mesh without such a patch the option changes nothing: the same launches, the same bits),
+ * "large_patches_stress" (0, default; 1: from the next eqlb_se_set_boundary on, on a handle that also has
+ * "large_patches" = 1, a stress handle accepts patches of more than 63 cells - their rows 0, 1 get the weak-symmetry
+ * step from a kernel of their own, one workgroup per patch, RT_2 ... RT_4, slot scatter and the fused tiled stress
+ * launch - and eqlb_se_kornconst / eqlb_se_equilibrate_with_kornconst walk their fans as well, on stress and plain
+ * handles alike.  A large patch that is the internal patch of a group of boundary patches - RT_2, tractions on both
+ * stress rows around a two-cell boundary vertex, se/reconstruction.hpp:170-234 - is refused at eqlb_se_set_boundary
+ * with EQLB_ERR_UNSUPPORTED.  Any other value than 0 or 1: EQLB_ERR_INVALID_ARGUMENT.  With 0 every refusal above
+ * stays; on a mesh without a large patch the option changes nothing.  EV handles do not have this key). */
 int eqlb_se_set_option(eqlb_se_t* handle, const char* key, int32_t value);
 
 /*
