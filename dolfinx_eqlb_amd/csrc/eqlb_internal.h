@@ -228,6 +228,20 @@ int launch_se_patch_fused(int k, int deg, int scatter, const SeArgs& a, const Fu
 int launch_se_patch_tiled(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, hipStream_t stream);
 int launch_se_patch_tiled_multi(int k, int deg, int mode, const SeArgs& a, const TileArgs& t, const MultiRhs& mr,
                                 hipStream_t stream);
+// RT_2 / P1, SE mode: the tiled launch whose full 8-cell patches run on four lanes, two ring cells per lane
+// (eqlb_se_kernels_pair.hip); launch_se_patch_tiled hands over to it where the instance is built and the handle has
+// one right-hand side
+#ifndef EQLB_PAIR_LANES
+#define EQLB_PAIR_LANES 1 // 0: the full-patch instance, 8 per wave-block, for every full patch (register report and A/B)
+#endif
+#ifndef EQLB_PAIR_OPAQUE
+#define EQLB_PAIR_OPAQUE 0 // opaque lane index for the lane predicates of the pair-lane instance (119 VGPRs either way)
+#endif
+#ifndef EQLB_PAIR_WQ_SPLIT
+#define EQLB_PAIR_WQ_SPLIT 1 // pair-lane instance: the load tensor in batches of one metric row (3 reads of 16 bytes) instead of 9 (0: 86 spilled registers)
+#endif
+bool pair_lanes_built();
+int launch_se_patch_tiled_pair(const SeArgs& a, const TileArgs& t, hipStream_t stream);
 // the same launches for projected data of degree deg < k - 1 (eqlb_se_kernels_lowdeg*.hip): the launchers above hand
 // every call with deg != k - 1 over to these
 int launch_se_patch_lowdeg(int k, int deg, int P, int solver, int scatter, const SeArgs& a, hipStream_t stream,

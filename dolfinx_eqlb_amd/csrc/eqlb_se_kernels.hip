@@ -2123,9 +2123,15 @@ __device__ __forceinline__ void tile_stage(const SeArgs& a0, const TileArgs& ta,
   __syncthreads();
 }
 
+// one wave-block of 16 full 8-cell patches on four lanes per patch, two ring cells per lane (eqlb_se_kernels_pair.hip);
+// slot_base: the first slot of the wave-block in the lane space of the bin (wave-uniform), lane: the lane of the wave
+template <int K, int DEG>
+__device__ void se_pair_body(const SeArgs& a, int64_t slot_base, int lane, double* lds, double* tile_slots);
+
 // second half: every patch of the tile for ONE right-hand side (a0.rhs, a0.flux_dg, a0.rhs_dg, a0.out), then the
-// flush of the tile's rows
-template <int K, int DEG, int MODE>
+// flush of the tile's rows.  PAIR: the leading full patches of the bin P = 8 run in wave-blocks of 16 on se_pair_body,
+// the remainder of fewer than 16 on the full-patch instance below, 8 per wave-block
+template <int K, int DEG, int MODE, bool PAIR = false>
 __device__ __forceinline__ void tile_sweep_flush(const SeArgs& a0, const TileArgs& ta, const int tile, double* lds)
 {
   constexpr int TILE_THREADS = tile_threads_c(K);
@@ -2148,30 +2154,47 @@ __device__ __forceinline__ void tile_sweep_flush(const SeArgs& a0, const TileArg
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   constexpr int NW = TILE_THREADS / 64;
   int u = wave;
+  if constexpr (PAIR) // (the wave-block counter as well)
+    u = __builtin_amdgcn_readfirstlane(u);
   SeArgs a = a0;
+  // (PAIR: the counts of the tile as wave-uniform values in scalar registers - that kernel has no vector register to spare)
+#define EQLB_TILE_UNI(x) (PAIR ? __builtin_amdgcn_readfirstlane(x) : (x))
 #define EQLB_TILE_BIN(B, PP)                                                                        \
   {                                                                                                 \
-    const int np = td.npatch[B];                                                                    \
+    const int np = EQLB_TILE_UNI(td.npatch[B]);                                                     \
     const int nwb = tile_wb_all(np, PP);                                                            \
     a.npatch = np;                                                                                  \
-    a.slot_offset = td.slot_start[B];                                                               \
-    a.patch_offset = td.patch_start[B];                                                             \
+    a.slot_offset = EQLB_TILE_UNI(td.slot_start[B]);                                                \
+    a.patch_offset = EQLB_TILE_UNI(td.patch_start[B]);                                              \
     /* complete wave-blocks of full patches (RT_1: the body is too small for the second instance to pay) */ \
     constexpr bool SPEC = tile_spec_full(K, PP);                                                    \
-    const int nwb_full = SPEC ? tile_wb_whole(td.nfull[B], PP) : 0;                                 \
+    const int nfull_b = EQLB_TILE_UNI(td.nfull[B]);                                                 \
+    const int nwb_full = SPEC ? tile_wb_whole(nfull_b, PP) : 0;                                     \
     /* wave-blocks of interior patches of any size (the patches behind the full ones; K = 2, P = 8, 16) */ \
     constexpr bool SPECI = tile_spec_interior(K, PP);                                               \
-    const int nwb_int = SPECI ? tile_wb_whole(td.nint[B], PP) : 0;                                  \
-    for (; u < nwb; u += NW)                                                                        \
+    const int nwb_int = SPECI ? tile_wb_whole(EQLB_TILE_UNI(td.nint[B]), PP) : 0;                   \
+    /* PAIR: units [0, npair) are wave-blocks of 16 full patches (the 64-lane blocks 2 u, 2 u + 1 of the list), */ \
+    /* unit u >= npair is the 64-lane block u + npair */                                            \
+    constexpr bool PAIRB = PAIR && PP == 8 && K == 2 && MODE == 0;                                  \
+    const int npair = PAIRB ? (nfull_b >> 4) : 0;                                                   \
+    const int nun = nwb - npair;                                                                    \
+    for (; u < nun; u += NW)                                                                        \
     {                                                                                               \
-      if (u < nwb_full)                                                                             \
-        se_patch_body<K, DEG, PP, EQLB_TILE_SOLVER, 2, 64, MODE, SPEC>(a, 0, lds, true, (int64_t)u * 64 + lane, sSlots); \
-      else if (SPECI && u < nwb_int)                                                                \
-        se_patch_body<K, DEG, PP, EQLB_TILE_SOLVER, 2, 64, MODE, false, SPECI>(a, 0, lds, true, (int64_t)u * 64 + lane, sSlots); \
+      if constexpr (PAIRB)                                                                          \
+        if (u < npair)                                                                              \
+        {                                                                                           \
+          se_pair_body<K, DEG>(a, (int64_t)u * 128, lane, lds, sSlots);                             \
+          continue;                                                                                 \
+        }                                                                                           \
+      const int v = u + npair;                                                                      \
+      if (v < nwb_full)                                                                             \
+        se_patch_body<K, DEG, PP, EQLB_TILE_SOLVER, 2, 64, MODE, SPEC>(a, 0, lds, true, (int64_t)v * 64 + lane, sSlots); \
+      else if (SPECI && v < nwb_int)                                                                \
+        se_patch_body<K, DEG, PP, EQLB_TILE_SOLVER, 2, 64, MODE, false, SPECI>(a, 0, lds, true, (int64_t)v * 64 + lane, sSlots); \
       else if (!EQLB_EXP_FULLONLY) /* timing experiment: only the full-patch instance */            \
-        se_patch_body<K, DEG, PP, EQLB_TILE_SOLVER, 2, 64, MODE>(a, 0, lds, true, (int64_t)u * 64 + lane, sSlots); \
+        se_patch_body<K, DEG, PP, EQLB_TILE_SOLVER, 2, 64, MODE>(a, 0, lds, true, (int64_t)v * 64 + lane, sSlots); \
     }                                                                                               \
-    u -= nwb;                                                                                       \
+    u -= nun;                                                                                       \
   }
 #ifndef EQLB_EXP_NOBODY
   EQLB_TILE_BIN(0, 4)
@@ -2185,6 +2208,7 @@ __device__ __forceinline__ void tile_sweep_flush(const SeArgs& a0, const TileArg
   (void)td;
 #endif
 #undef EQLB_TILE_BIN
+#undef EQLB_TILE_UNI
   const int32_t* cells = ta.tile_cells + (int64_t)tile * TC;
   const bool conforming = MODE == 1 && ta.facet_owner != nullptr;
   // flush operands of the broken layout: the old values of flux_hdiv are fetched BEFORE the barrier
@@ -2558,8 +2582,11 @@ int launch_se_patch_tiled(int k, int deg, int mode, const SeArgs& a, const TileA
   }
   if (k == 1 && deg == 0)
     return launch_tiled_kd<1, 0, 0>(a, t, stream);
+  // (handles with ONE right-hand side: with several, the launches per right-hand side stay bitwise equal to
+  // k_se_patch_tiled_multi, whose full patches run lane = cell)
   if (k == 2 && deg == 1)
-    return launch_tiled_kd<2, 1, 0>(a, t, stream);
+    return (pair_lanes_built() && a.nrhs == 1) ? launch_se_patch_tiled_pair(a, t, stream)
+                                               : launch_tiled_kd<2, 1, 0>(a, t, stream);
   if (k == 3 && deg == 2)
     return launch_tiled_kd<3, 2, 0>(a, t, stream);
   return EQLB_ERR_UNSUPPORTED;

@@ -1,0 +1,30 @@
+"""The lane arithmetic of the RT_2 full-patch body on the host (no GPU): tools/pair_chain_emul.cpp runs the templates
+of dolfinx_eqlb_amd/csrc/eqlb_pair_chain.h with the lanes of a patch as array indices - the pair-lane mapping (4 lanes,
+two ring cells each) and the lane = cell mapping (8 lanes) on the same random rings of 8 cells - and compares them
+with each other, with a dense solve of the reduced system and with a sequential walk round the ring. The bounds are
+the program's own (printed with the figures); it is built as a plain executable with the address and
+undefined-behaviour sanitizers where the compiler has them."""
+
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_pair_chain_emulation(tmp_path):
+    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler")
+    src = os.path.join(ROOT, "tools", "pair_chain_emul.cpp")
+    exe = str(tmp_path / "pair_chain_emul")
+    base = [cxx, "-O1", "-std=c++17", "-Wall", "-Werror", src, "-o", exe]
+    san = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True,
+                         text=True)
+    if san.returncode != 0:   # (a compiler without the sanitizer runtimes: the comparison still runs)
+        subprocess.run(base, check=True)
+    run = subprocess.run([exe, "500"], capture_output=True, text=True)
+    print(run.stdout, run.stderr)
+    assert run.returncode == 0 and run.stdout.strip().endswith("PASS")
