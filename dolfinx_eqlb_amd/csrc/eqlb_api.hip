@@ -4,6 +4,7 @@
 // handle.  There is NO CPU fallback: without a HIP device every compute entry point fails.
 #include "eqlb_internal.h"
 #include "eqlb_host_util.h"
+#include "eqlb_topology_check.h"
 
 #include <algorithm>
 #include <chrono>
@@ -257,6 +258,13 @@ try
     d.h_node_nfcts[i] = node_facets_offsets[i + 1] - node_facets_offsets[i];
     d.ncells_max = std::max(d.ncells_max, d.h_node_ncells[i]);
   }
+  // One-cell facets per node: with the two counts above they tell whether the patch builder can walk the node (one
+  // closed ring or one open fan, eqlb_topology_check.h).  Nothing is refused here: the local mesh of a rank
+  // legitimately holds nodes it does not own at which two fans meet; eqlb_se_set_boundary refuses them when they are
+  // to be equilibrated.
+  d.h_node_nbnd.resize(nnodes);
+  eqlb::count_node_boundary_facets(nnodes, node_facets_offsets, node_facets, facet_cells_offsets, d.h_node_nbnd.data());
+  d.h_facet_cells_off.assign(facet_cells_offsets, facet_cells_offsets + (size_t)nfacets + 1);
   d.h_x.assign(x, x + (size_t)nnodes * 3);
   d.h_cell_nodes.assign(cell_nodes, cell_nodes + (size_t)ncells * 3);
   d.h_facet_nodes.assign(facet_nodes, facet_nodes + (size_t)nfacets * 2);
@@ -487,14 +495,16 @@ try
     for (size_t i = 0; i < nb && !inhomogeneous; ++i)
       inhomogeneous = (boundary_values[i] != 0.0);
   }
-  h->stress_flux_bcs = false;
+  // (into a local: the handle is not touched before the last check that can refuse the table with the old boundary
+  // data still in place; the sweep reads h->stress_flux_bcs)
+  bool stress_flux_bcs = false;
   if (h->stress)
-    for (size_t i = 0; i < (size_t)2 * m.nfacets && !h->stress_flux_bcs; ++i)
-      h->stress_flux_bcs = (facet_type[i] == EQLB_FACET_ESSNT_DUAL);
+    for (size_t i = 0; i < (size_t)2 * m.nfacets && !stress_flux_bcs; ++i)
+      stress_flux_bcs = (facet_type[i] == EQLB_FACET_ESSNT_DUAL);
   // RT_2 stress: the fused tiled launch (k_se_stress_tiled) reads DG_1 data; DG_0 data take the route of stress flux
   // BCs - rows into the slots by the patch kernels of the handle's degree, then the weak-symmetry kernel of that route
   // (launch_se_weaksym with no_flux_bcs = false; it reads no DG data, nor do the Korn kernels)
-  const bool stress_fused_ok = h->k == 2 && h->deg == 1 && !h->stress_flux_bcs;
+  const bool stress_fused_ok = h->k == 2 && h->deg == 1 && !stress_flux_bcs;
   // OrientedPatch::set_max_patch_size (se/Patch.cpp:337-404): every local node is checked
   for (int32_t i = 0; i < m.nnodes; ++i)
   {
@@ -505,8 +515,32 @@ try
     if (m.h_node_ncells[i] < 1)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "node %d belongs to no cell", i);
   }
+  // What the patch builder cannot walk (eqlb_topology_check.h), refused before the old tables are freed: a refused
+  // call leaves the handle as it was.  Facets both of whose nodes are masked out are not looked at.
+  {
+    const eqlb::TopoFinding tf = eqlb::check_boundary_topology(
+        m.nnodes, m.nfacets, h->nrhs, m.h_node_ncells.data(), m.h_node_nfcts.data(), m.h_node_nbnd.data(),
+        m.h_facet_nodes.data(), m.h_facet_cells_off.data(), facet_type, node_mask);
+    if (tf.verdict == eqlb::TOPO_NODE_NOT_WALKABLE)
+      return fail(EQLB_ERR_UNSUPPORTED,
+                  "Patch around node %d (%d cells, %d facets, %d of them boundary facets) is neither one closed ring nor "
+                  "one open fan of cells: a vertex where the boundary touches itself cannot be equilibrated",
+                  tf.index, m.h_node_ncells[tf.index], m.h_node_nfcts[tf.index], m.h_node_nbnd[tf.index]);
+    if (tf.verdict == eqlb::TOPO_BOUNDARY_FACET_UNTYPED)
+      return fail(EQLB_ERR_INVALID_ARGUMENT,
+                  "eqlb_se_set_boundary: boundary facet %d (nodes %d, %d) has type 0 on right-hand side %d: every "
+                  "facet with one cell at an equilibrated node needs a boundary condition",
+                  tf.index, m.h_facet_nodes[2 * (size_t)tf.index], m.h_facet_nodes[2 * (size_t)tf.index + 1], tf.row);
+    if (tf.verdict == eqlb::TOPO_INTERIOR_FACET_TYPED)
+      return fail(EQLB_ERR_INVALID_ARGUMENT,
+                  "eqlb_se_set_boundary: facet %d (nodes %d, %d) lies between two cells and has type %d on right-hand "
+                  "side %d: only facets with one cell carry boundary conditions",
+                  tf.index, m.h_facet_nodes[2 * (size_t)tf.index], m.h_facet_nodes[2 * (size_t)tf.index + 1],
+                  (int)facet_type[(size_t)tf.row * m.nfacets + tf.index], tf.row);
+  }
   tm.lap("checks");
   free_boundary(h);
+  h->stress_flux_bcs = stress_flux_bcs;
   tm.lap("free old tables");
 
   // bins by lanes per patch: P = smallest of {4,8,16,32,64} >= number of patch facets

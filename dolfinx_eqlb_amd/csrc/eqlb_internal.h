@@ -54,6 +54,8 @@ struct DeviceMesh
   uint8_t* facet_perm = nullptr;
   // host copies needed for binning / tiling
   std::vector<int32_t> h_node_ncells, h_node_nfcts, h_cell_nodes;
+  std::vector<int32_t> h_node_nbnd;       // one-cell facets at each node (eqlb_topology_check.h: which nodes the builder can walk)
+  std::vector<int32_t> h_facet_cells_off; // offsets of the facet -> cell table (1 or 2 cells per facet)
   std::vector<int32_t> h_facet_nodes, h_node_facets_off, h_node_facets, h_node_cells_off, h_node_cells;
   std::vector<double> h_x;
 };

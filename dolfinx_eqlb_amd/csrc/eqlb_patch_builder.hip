@@ -9,7 +9,13 @@
 // The reference finds "the other facet of the cell that belongs to the patch" by searching a
 // sorted copy of the node's facet list (Patch.cpp:718-756); a facet belongs to the patch iff it
 // contains the patch node, which is what is tested here (same result, no sort).
+//
+// The walk is defined on one closed ring or one open fan of cells that starts at a typed one-cell facet
+// (eqlb_topology_check.h).  eqlb_se_set_boundary refuses a table that breaks this at a node it equilibrates, so every
+// thread that has a slot to write walks safely; a thread with nothing to write does not walk.  The export launch has
+// an entry for every node, masked out or not: there a node that cannot be walked keeps its cell count and the -1 fill.
 #include "eqlb_internal.h"
+#include "eqlb_topology_check.h"
 
 namespace eqlb
 {
@@ -73,6 +79,8 @@ __global__ void __launch_bounds__(256) k_build_patches(BuildArgs a)
   const int64_t patch = inst ? tid_g : ((slot0 >= 0) ? a.node_patch[node] : -1);
   const bool ex = (a.ex_ncells != nullptr) && !inst;
   const int64_t exo = (int64_t)node * a.stride;
+  if (!ex && slot0 < 0)
+    return; // masked out, or the patch of another launch (large-patch SoA): nothing to write
 
   if (ex)
   {
@@ -90,6 +98,13 @@ __global__ void __launch_bounds__(256) k_build_patches(BuildArgs a)
   }
   if (n < 2 || (n + 2 > 65 && !a.large) || (ex && n + 2 > a.stride))
     return; // rejected on the host (EQLB_ERR_PATCH_TOO_SMALL / _TOO_LARGE)
+  if (ex)
+  {
+    // nodes that are not equilibrated come here too (the rim of a rank's local mesh): two fans that meet at the node
+    // cannot be walked
+    if (!node_walkable(n, nf, node_boundary_facets(nfcts, nf, a.facet_cells_off)))
+      return;
+  }
 
   // --- start facet (Patch.cpp:425-484): interior -> first facet of the node; boundary ->
   // first flux-BC facet of RHS 0 if any, else the first primal-Dirichlet facet
@@ -106,6 +121,10 @@ __global__ void __launch_bounds__(256) k_build_patches(BuildArgs a)
         f_ef = nfcts[i];
     }
     fct_first = (f_ef >= 0) ? f_ef : f_ep;
+    // no typed facet at the node, or a typed facet between two cells: no defined start (refused on the host for the
+    // nodes that are equilibrated; the export leaves the -1 fill)
+    if (fct_first < 0 || a.facet_cells_off[fct_first + 1] - a.facet_cells_off[fct_first] != 1)
+      return;
   }
 
   int32_t cell, fct; // current cell T_a and facet E_a

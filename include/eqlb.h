@@ -164,6 +164,20 @@ int eqlb_se_set_option(eqlb_se_t* handle, const char* key, int32_t value);
  * Builds the oriented patch fans (OrientedPatch::initialize_patch, se/Patch.cpp:406-635, and
  * the reversal flags of se/solve_patch_semiexplt.hpp:324-389) with a HIP kernel into
  * lane-contiguous SoA buffers, binned by patch size.  Host pointers.
+ *
+ * The walk round a node is defined on one closed ring of cells or on one open fan between two boundary facets, and it
+ * starts at a typed boundary facet.  Tables that break this are refused before anything is built or freed, and the
+ * message names the node or the facet.  After one of these two refusals - as after a facet type out of range or a
+ * masked-in node with one cell, which are checked before them - the handle is as it was and keeps the boundary data
+ * of the last accepted call.  That holds for no other refusal of this call: EQLB_ERR_PATCH_TOO_LARGE, the refusals of
+ * grouped boundary patches of a stress handle and device errors come after the old tables are freed and leave the
+ * handle without boundary data.
+ *   EQLB_ERR_UNSUPPORTED       a node with mask != 0 at which the boundary touches itself (two fans of cells that meet
+ *                              in the node only: n cells, n + 2 facets, 4 of them with one cell); mask it out
+ *   EQLB_ERR_INVALID_ARGUMENT  on any right-hand side: a facet with one cell and type EQLB_FACET_INTERNAL (the rim of a
+ *                              hole that the caller left out), or a facet between two cells with another type
+ * Only facets with a node of mask != 0 are looked at: the local mesh of a rank (every cell with a node it owns) holds
+ * nodes it does not own where two fans meet, and artificial boundary facets between them.
  */
 int eqlb_se_set_boundary(eqlb_se_t* handle, const int8_t* facet_type,
                          const double* boundary_values, const uint8_t* node_mask);
@@ -219,6 +233,9 @@ int64_t eqlb_se_num_patches(const eqlb_se_t* handle);
  *   ncells [nnodes], cells [nnodes][stride], fcts [nnodes][stride],
  *   fcts_local [nnodes][2*stride], inodes_local [nnodes][stride], reversed [nnodes][2*stride]
  *   ([2a], [2a+1] = E_{a-1} / E_a of cell T_a reversed, 0-based cell a).  Host pointers.
+ * Every node has a row, whether its mask is set or not.  A node that cannot be walked (see eqlb_se_set_boundary: two
+ * fans that meet in the node, no typed boundary facet at it, patches the handle refuses for their size) gets its
+ * cell count in ncells and -1 everywhere else; no new return code.
  */
 int eqlb_se_export_patches(eqlb_se_t* handle, int32_t stride, int32_t* ncells, int32_t* cells,
                            int32_t* fcts, int8_t* fcts_local, int8_t* inodes_local,
@@ -605,7 +622,10 @@ int eqlb_ev_set_basis_transform(eqlb_ev_t* handle, const double* C, const double
 /* facet_type as eqlb_se_set_boundary; boundary_values [nrhs][ndofs] conforming boundary DOFs
  * (facet DOFs of the prescribed normal flux on the flux-BC facets, zero elsewhere) or NULL; the
  * per-patch values hat_a * g (base/BoundaryData.cpp:687-745) are formed in the kernel.
- * node_mask as eqlb_se_set_boundary. */
+ * node_mask as eqlb_se_set_boundary; the same tables are refused with the same codes (EQLB_ERR_UNSUPPORTED for a
+ * node with mask != 0 where two fans of cells meet, EQLB_ERR_INVALID_ARGUMENT for an untyped facet with one cell or a
+ * typed facet between two cells at such a node); after these refusals, and after no other, the handle keeps its
+ * boundary data. */
 int eqlb_ev_set_boundary(eqlb_ev_t* handle, const int8_t* facet_type,
                          const double* boundary_values, const uint8_t* node_mask);
 

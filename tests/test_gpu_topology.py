@@ -1,0 +1,401 @@
+"""Domains whose boundary is more than one simple loop, on the device against the oracle and against the
+independent predicates; and the facet-type tables and node masks eqlb_se_set_boundary refuses.
+
+Meshes of tests/topology_meshes.py (sub-meshes of one perturbed, orientation-shuffled 8 x 8 crossed square, all
+below one default tile): a hole, two holes, an L-shape, two components; three boundary layouts each (all
+primal-Dirichlet, flux BCs on the lower part of the outer boundary, flux BCs round the middle - on `hole` the whole
+inner loop).  Every flux case asserts
+
+  * device against oracle: 1e-11 of the largest coefficient (tests/test_gpu_parity.py), 1e-10 for stress and k = 4;
+  * the tiled launch - default tile, and tiles of 31 cells that straddle hole, corner and gap - against the slot
+    path: 1e-13 (k <= 2), 1e-12 (k = 3), 1e-11 (stress), as check_case of tests/test_gpu_tile_dispatch.py;
+  * two calls on one handle bitwise equal;
+  * independent of the oracle: divergence residual < 1e-10 x norm, jumps < 1e-9 (test_k4_matches_oracle), the
+    flux-BC residual on the flux-BC facets within 1e-11 x the scale of the boundary DOFs of the data, host statement
+    and eqlb_boundary_residual alike (tests/test_gpu_estimate_lower_degree.py::test_boundary_residual).
+
+The refusals reach no patch kernel: the tables are checked on the host before anything is built.
+"""
+
+import numpy as np
+import pytest
+
+import topology_meshes as tm
+from dolfinx_eqlb_amd.eqlb import check_eqlb_conditions as chk
+
+pytestmark = pytest.mark.gpu
+RTOL = 1e-11
+
+
+@pytest.fixture(scope="module")
+def cpp():
+    from dolfinx_eqlb_amd import cpp as c
+    assert c.device_count() >= 1, "GPU tests need a HIP device"
+    return c
+
+
+_REF = {}
+
+
+def _ref(key, fn):
+    """Oracle results are computed once and shared."""
+    if key not in _REF:
+        _REF[key] = fn()
+    return _REF[key]
+
+
+def _twice(eq, G, f):
+    x1 = eq.equilibrate_host(G, f)
+    x2 = eq.equilibrate_host(G, f)
+    assert np.array_equal(x1, x2)
+    return x1
+
+
+def _nblocks(eq):
+    tb = eq.tiling_blocks()
+    return sum(sum(v) for key, v in tb.items() if key != "zero_tiles")
+
+
+def check_conditions(cpp, dm, mesh, k, ft_row, x, G, f, total_flux=False):
+    """The predicates that do not know the oracle.  total_flux: x is sigma itself (EV form), else sigma_eq."""
+    from test_gpu_estimate_lower_degree import residual_per_facet
+    nrt = k * (k + 2)
+    Gt = np.zeros_like(G) if total_flux else G
+    res, nrm = chk.divergence_residual(mesh, k, x, Gt, f)
+    assert res < 1e-10 * nrm, (res, nrm)
+    assert chk.check_jump_condition(mesh, k, x, Gt, atol=1e-9)
+    facets = np.nonzero(ft_row == 2)[0]
+    if facets.size:
+        zero = np.zeros(mesh.ncells * nrt)
+        scale = residual_per_facet(mesh, k, k - 1, zero, G, facets, zero).max()
+        got = cpp.boundary_residual(dm, k, x[None], None if total_flux else G[None], facets, None)[0]
+        ref = residual_per_facet(mesh, k, k - 1, x, Gt, facets, zero)
+        print(f"  flux-BC residual on {facets.size} facets: device {got.max():.3e}, numpy {ref.max():.3e}, "
+              f"scale {scale:.3e}")
+        assert got.max() < 1e-11 * scale and np.abs(got - ref).max() < 1e-11 * scale
+
+
+def _se(cpp, dm, k, nrhs, ft, scatter, tile_cells=0, stress=False, mask=None):
+    eq = cpp.SemiExplicitEquilibrator(dm, k, nrhs, reconstruct_stress=stress)
+    eq.set_option("scatter", scatter)
+    if tile_cells:
+        eq.set_option("tile_cells", tile_cells)
+    eq.set_boundary(ft, node_mask=mask)
+    return eq
+
+
+# ------------------------------------------------------------------------------------------------ flux, SE
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("layout", tm.LAYOUTS)
+@pytest.mark.parametrize("name", tm.NAMES)
+def test_se_matches_oracle(cpp, oracle_mod, name, layout, k):
+    mesh, ft, G, f = tm.case(name, layout, k)
+    ref = _ref(("se", name, layout, k), lambda: oracle_mod.se_reconstruct(mesh, k, ft, G, f))
+    scale = np.abs(ref).max()
+    dm = cpp.DeviceMesh(mesh)
+    xs = _twice(_se(cpp, dm, k, 1, ft, 0), G, f)
+    print(f"  slots - oracle {np.abs(xs - ref).max() / scale:.3e}")
+    assert np.abs(xs - ref).max() <= RTOL * scale
+    check_conditions(cpp, dm, mesh, k, ft[0], xs[0], G[0], f[0])
+    for tile_cells in (0, tm.TILE_SMALL):
+        eq = _se(cpp, dm, k, 1, ft, 2, tile_cells)
+        ntiles = eq.tiling_info()["ntiles"]
+        assert ntiles > 1 if tile_cells else ntiles == 1
+        xt = _twice(eq, G, f)
+        print(f"  {ntiles} tiles: tiled - oracle {np.abs(xt - ref).max() / scale:.3e}, tiled - slots "
+              f"{np.abs(xt - xs).max() / scale:.3e}")
+        assert np.abs(xt - ref).max() <= RTOL * scale
+        assert np.abs(xt - xs).max() <= (1e-13 if k <= 2 else 1e-12) * scale
+        check_conditions(cpp, dm, mesh, k, ft[0], xt[0], G[0], f[0])
+
+
+@pytest.mark.parametrize("name", tm.NAMES)
+def test_se_k4_matches_oracle(cpp, oracle_mod, name):
+    k = 4
+    mesh, ft, G, f = tm.case(name, "dirichlet", k)
+    ref = oracle_mod.se_reconstruct(mesh, k, ft, G, f)
+    dm = cpp.DeviceMesh(mesh)
+    x = _twice(_se(cpp, dm, k, 1, ft, -1), G, f)
+    print(f"  device - oracle {np.abs(x - ref).max() / np.abs(ref).max():.3e}")
+    assert np.abs(x - ref).max() <= 1e-10 * np.abs(ref).max()
+    check_conditions(cpp, dm, mesh, k, ft[0], x[0], G[0], f[0])
+
+
+# ------------------------------------------------------------------------------------------------ flux, EV
+@pytest.mark.parametrize("layout", tm.LAYOUTS)
+@pytest.mark.parametrize("name", tm.NAMES)
+def test_ev_matches_oracle(cpp, oracle_mod, name, layout):
+    from dolfinx_eqlb_amd.eqlb.conforming import conforming_dofmap, conforming_to_broken
+    k = 2
+    mesh, ft, G, f = tm.case(name, layout, k)
+    cd, nd = conforming_dofmap(mesh, k)
+    ref = conforming_to_broken(mesh, k, oracle_mod.ev_reconstruct(mesh, k, ft, G, f, cd, nd)[0])[None]
+    scale = np.abs(ref).max()
+    dm = cpp.DeviceMesh(mesh)
+    out, blocks = {}, {}
+    for key, scatter, tile_cells in (("slots", 0, 0), ("tiled", -1, 0), ("small", -1, tm.TILE_SMALL)):
+        eq = cpp.ConstrainedMinEquilibrator(dm, k, 1)
+        eq.set_option("output", 1)
+        eq.set_option("scatter", scatter)
+        if tile_cells:
+            eq.set_option("tile_cells", tile_cells)
+        eq.set_boundary(ft)
+        x = out[key] = _twice(eq, G, f)
+        blocks[key] = _nblocks(eq)
+        print(f"  {key}: device - oracle {np.abs(x - ref).max() / scale:.3e}")
+        assert np.abs(x - ref).max() <= RTOL * scale
+        check_conditions(cpp, dm, mesh, k, ft[0], x[0], G[0], f[0], total_flux=True)
+    # (the EV handle reports no tile count: every tile lists the patches of all its vertices, so several tiles run
+    # more wave-blocks than one)
+    assert blocks["small"] > blocks["tiled"] > 0
+    for key in ("tiled", "small"):
+        assert np.abs(out[key] - out["slots"]).max() <= 1e-13 * scale
+
+
+# ------------------------------------------------------------------------------------------------ stress
+def _stress_case(name, layout):
+    from synthetic import make_compatible_stress_data
+    mesh = tm.mesh_of(name)
+    ft = np.repeat(tm.facet_table(mesh, layout), 2, axis=0)
+    G, f = make_compatible_stress_data(mesh, 2, ft)
+    return mesh, ft, G, f
+
+
+def _check_stress(cpp, dm, mesh, ft, x, G, f):
+    from test_gpu_stress import asym_moments
+    for r in range(2):
+        check_conditions(cpp, dm, mesh, 2, ft[r], x[r], G[r], f[r])
+    assert np.abs(asym_moments(mesh, 2, x)[1]).max() < 1e-11      # (the bound of tests/test_gpu_stress.py)
+    assert chk.check_weak_symmetry_condition(mesh, 2, x)
+
+
+@pytest.mark.parametrize("name", tm.NAMES)
+def test_stress_fused_launch(cpp, oracle_mod, name):
+    """RT_2 stress without flux BCs: the fused tiled launch (one tile, tiles of 31 cells) against the slot path and
+    the oracle.  (The oracle accepts both stress layouts on all four meshes, run on the CPU; neither is one of the
+    reference's expected failures, which need different boundary types on the two rows.)"""
+    mesh, ft, G, f = _ref(("stress-case", name, "dirichlet"), lambda: _stress_case(name, "dirichlet"))
+    ref = oracle_mod.se_reconstruct(mesh, 2, ft, G, f, stress=True)
+    scale = np.abs(ref).max()
+    dm = cpp.DeviceMesh(mesh)
+    xs = _twice(_se(cpp, dm, 2, 2, ft, 0, stress=True), G, f)
+    assert np.abs(xs - ref).max() <= 1e-10 * scale
+    _check_stress(cpp, dm, mesh, ft, xs, G, f)
+    for tile_cells in (0, tm.TILE_SMALL):
+        eq = _se(cpp, dm, 2, 2, ft, -1, tile_cells, stress=True)
+        ntiles = eq.tiling_info()["ntiles"]
+        assert ntiles > 1 if tile_cells else ntiles == 1
+        xt = _twice(eq, G, f)
+        print(f"  {ntiles} tiles: fused - oracle {np.abs(xt - ref).max() / scale:.3e}, fused - slots "
+              f"{np.abs(xt - xs).max() / scale:.3e}")
+        assert np.abs(xt - ref).max() <= 1e-10 * scale
+        assert np.abs(xt - xs).max() <= 1e-11 * scale
+        _check_stress(cpp, dm, mesh, ft, xt, G, f)
+
+
+@pytest.mark.parametrize("name", tm.NAMES)
+def test_stress_slot_route_with_tractions(cpp, oracle_mod, name):
+    """Traction conditions round the middle on both stress rows (on `hole`: the whole inner loop; on `two_parts`
+    the two-cell corners are grouped with their internal patches): row sweeps into the slots, weak-symmetry kernel."""
+    mesh, ft, G, f = _ref(("stress-case", name, "flux_middle"), lambda: _stress_case(name, "flux_middle"))
+    assert np.count_nonzero(ft == 2) == 2 * tm.MIDDLE_FACETS[name]
+    ref = oracle_mod.se_reconstruct(mesh, 2, ft, G, f, stress=True)
+    dm = cpp.DeviceMesh(mesh)
+    x = _twice(_se(cpp, dm, 2, 2, ft, -1, stress=True), G, f)
+    print(f"  device - oracle {np.abs(x - ref).max() / np.abs(ref).max():.3e}")
+    assert np.abs(x - ref).max() <= 1e-10 * np.abs(ref).max()
+    _check_stress(cpp, dm, mesh, ft, x, G, f)
+
+
+# -------------------------------------------------------------------------------- fans, Korn constants, mirror
+@pytest.mark.parametrize("layout", tm.LAYOUTS)
+@pytest.mark.parametrize("name", tm.NAMES)
+def test_patch_export_bit_exact(cpp, oracle_mod, name, layout):
+    """Start facet and direction of the walk on every loop of the boundary, flux-BC facets first."""
+    mesh = tm.mesh_of(name)
+    ft = tm.facet_table(mesh, layout)
+    eq = _se(cpp, cpp.DeviceMesh(mesh), 1, 1, ft, -1)
+    dev = eq.export_patches()
+    ref = oracle_mod.build_patches(mesh, ft)
+    assert dev["stride"] == ref["stride"]
+    for key in ("ncells", "cells", "fcts", "fcts_local", "inodes_local"):
+        assert np.array_equal(dev[key], ref[key]), key
+
+
+@pytest.mark.parametrize("name", ["hole", "two_parts"])
+def test_korn_constants(cpp, oracle_mod, name):
+    mesh, ft, G, f = tm.case(name, "flux_middle", 2)
+    eq = cpp.SemiExplicitEquilibrator(cpp.DeviceMesh(mesh), 2, 1, estimate_korn=True)
+    eq.set_boundary(ft)
+    _, korn = eq.equilibrate_host_with_kornconst(G, f)
+    ref = oracle_mod.se_korn(mesh, ft)
+    assert np.abs(korn - ref).max() <= 1e-11 * ref.max()       # (tests/test_korn.py::test_gpu_korn_equals_oracle)
+    assert np.array_equal(eq.kornconst_host(), korn)
+
+
+def test_mirror_class_on_hole(oracle_mod):
+    """FluxEqlbSE builds the table from facet lists (boundarydata), not from a raw array."""
+    from dolfinx_eqlb_amd.eqlb.FluxEqlbSE import FluxEqlbSE
+    mesh, ft, G, f = tm.case("hole", "dirichlet", 2)
+    eq = FluxEqlbSE(2, mesh, [f[0]], [G[0]])
+    eq.set_boundary_conditions([mesh.boundary_facets()], [[]])
+    eq.equilibrate_fluxes()
+    ref = _ref(("se", "hole", "dirichlet", 2), lambda: oracle_mod.se_reconstruct(mesh, 2, ft, G, f))
+    assert np.abs(eq.get_reconstructed_fluxes(0)[0] - ref[0]).max() <= RTOL * np.abs(ref).max()
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+def _oracle_over_nodes(oracle_mod, mesh, k, ft, G, f, mask):
+    ref = np.zeros((1, mesh.ncells * k * (k + 2)))
+    for node in np.nonzero(mask)[0]:
+        oracle_mod.se_reconstruct(mesh, k, ft, G, f, flux_hdiv=ref, node_range=(int(node), int(node) + 1))
+    return ref
+
+
+def test_pinched_vertex_is_refused_unless_masked_out(cpp, oracle_mod):
+    from synthetic import facet_types, make_compatible_data
+    k = 2
+    mesh = tm.mesh_of("bowtie")
+    node = tm.pinched_node(mesh)
+    ft = facet_types(mesh)
+    G, f = make_compatible_data(mesh, k, ft, seed=31)
+    G, f = G[None], f[None]
+    dm = cpp.DeviceMesh(mesh)
+    eq = cpp.SemiExplicitEquilibrator(dm, k, 1)
+    with pytest.raises(RuntimeError, match=rf"node {node} \(4 cells, 6 facets"):
+        eq.set_boundary(ft)
+    other = np.ones(mesh.nnodes, dtype=np.uint8)
+    other[(node + 1) % mesh.nnodes] = 0
+    with pytest.raises(RuntimeError, match=rf"node {node} "):
+        eq.set_boundary(ft, node_mask=other)
+    mask = np.ones(mesh.nnodes, dtype=np.uint8)
+    mask[node] = 0
+    ref = _oracle_over_nodes(oracle_mod, mesh, k, ft, G, f, mask)
+    for scatter in (0, 2):
+        eq.set_option("scatter", scatter)
+        eq.set_boundary(ft, node_mask=mask)
+        x = _twice(eq, G, f)
+        assert np.abs(x - ref).max() <= RTOL * np.abs(ref).max()
+    # the export has an entry for every node: the pinched one keeps its cell count and the -1 fill
+    dev = eq.export_patches()
+    assert dev["ncells"][node] == 4
+    for key in ("cells", "fcts", "fcts_local", "inodes_local", "reversed"):
+        assert np.all(dev[key][node] == -1), key
+    for nd in np.nonzero(mask)[0]:
+        fan = oracle_mod.build_patches(mesh, ft, node_range=(int(nd), int(nd) + 1))
+        for key in ("ncells", "cells", "fcts", "fcts_local", "inodes_local"):
+            assert np.array_equal(dev[key][nd], fan[key][0]), (key, nd)
+
+
+def _interior_facet_at_boundary_node(mesh):
+    """A two-cell facet with a node on the inner loop: typed, it could be taken for the start of that node's walk."""
+    inner_nodes = np.unique(mesh.facet_nodes[tm.inner_loop_facets(mesh)])
+    two = np.nonzero(np.diff(mesh.facet_cells_offsets) == 2)[0]
+    return int(two[np.isin(mesh.facet_nodes[two], inner_nodes).any(axis=1)][0])
+
+
+def test_bad_facet_tables_are_refused_and_leave_the_handle_untouched(cpp, oracle_mod):
+    k = 2
+    mesh, ft, G, f = tm.case("hole", "dirichlet", k)
+    ref = _ref(("se", "hole", "dirichlet", k), lambda: oracle_mod.se_reconstruct(mesh, k, ft, G, f))
+    scale = np.abs(ref).max()
+    ref2 = np.concatenate([ref, ref])
+    f_b = int(tm.inner_loop_facets(mesh)[5])
+    f_i = _interior_facet_at_boundary_node(mesh)
+    dm = cpp.DeviceMesh(mesh)
+    for nrhs, row in ((1, 0), (2, 1)):
+        good = np.repeat(ft, nrhs, axis=0)
+        Gr, fr = np.repeat(G, nrhs, axis=0), np.repeat(f, nrhs, axis=0)
+        eq = cpp.SemiExplicitEquilibrator(dm, k, nrhs)
+        eq.set_boundary(good)
+        x0 = eq.equilibrate_host(Gr, fr)
+        assert np.abs(x0 - ref2[:nrhs]).max() <= RTOL * scale
+        for fct, value, what in ((f_b, 0, "boundary facet"), (f_i, 1, "facet"), (f_i, 2, "facet")):
+            bad = good.copy()
+            bad[row, fct] = value
+            with pytest.raises(RuntimeError, match=rf"{what} {fct} .*right-hand side {row}"):
+                eq.set_boundary(bad)
+            # the refused call changed nothing: the same numbers without a new table, and with the valid one
+            assert np.array_equal(eq.equilibrate_host(Gr, fr), x0)
+            eq.set_boundary(good)
+            assert np.array_equal(eq.equilibrate_host(Gr, fr), x0)
+
+
+@pytest.mark.parametrize("name", ["hole", "two_parts"])
+def test_refused_table_leaves_a_stress_handle_untouched(cpp, oracle_mod, name):
+    """The sweep of a stress handle chooses its weak-symmetry kernel by whether the ACCEPTED table has tractions.  A
+    refused table without any (its inner boundary untyped) must not switch a handle with tractions to the kernel
+    that ignores the boundary, skip and group flags of the patches (`two_parts`: two-cell corners grouped with their
+    internal patches); a refused table with a typed interior facet must not take a handle off the fused launch."""
+    mesh, ft, G, f = _ref(("stress-case", name, "flux_middle"), lambda: _stress_case(name, "flux_middle"))
+    inner = tm.inner_loop_facets(mesh)
+    dm = cpp.DeviceMesh(mesh)
+    eq = cpp.SemiExplicitEquilibrator(dm, 2, 2, reconstruct_stress=True)
+    eq.set_boundary(ft)
+    x0 = eq.equilibrate_host(G, f)
+    ref = oracle_mod.se_reconstruct(mesh, 2, ft, G, f, stress=True)
+    assert np.abs(x0 - ref).max() <= 1e-10 * np.abs(ref).max()
+    bad = np.repeat(tm.facet_table(mesh, "dirichlet"), 2, axis=0)
+    bad[:, inner] = 0
+    assert not np.any(bad == 2)
+    with pytest.raises(RuntimeError, match=rf"boundary facet {int(inner.min())} "):
+        eq.set_boundary(bad)
+    assert np.array_equal(eq.equilibrate_host(G, f), x0)
+    eq.set_boundary(ft)
+    assert np.array_equal(eq.equilibrate_host(G, f), x0)
+    # the other way round: a handle on the fused launch, a refused table with a flux-BC type on an interior facet
+    mesh, ftd, Gd, fd = _ref(("stress-case", name, "dirichlet"), lambda: _stress_case(name, "dirichlet"))
+    eq = cpp.SemiExplicitEquilibrator(dm, 2, 2, reconstruct_stress=True)
+    eq.set_boundary(ftd)
+    x0 = eq.equilibrate_host(Gd, fd)
+    f_i = int(np.nonzero(np.diff(mesh.facet_cells_offsets) == 2)[0][7])
+    bad = ftd.copy()
+    bad[1, f_i] = 2
+    with pytest.raises(RuntimeError, match=rf"facet {f_i} .*right-hand side 1"):
+        eq.set_boundary(bad)
+    assert np.array_equal(eq.equilibrate_host(Gd, fd), x0)
+    assert eq.tiling_info()["ntiles"] == 1
+
+
+def test_untyped_facets_between_masked_out_nodes_are_accepted(cpp, oracle_mod):
+    k = 2
+    mesh, ft, G, f = tm.case("hole", "dirichlet", k)
+    inner = tm.inner_loop_facets(mesh)
+    bad = ft.copy()
+    bad[0, inner] = 0
+    mask = np.ones(mesh.nnodes, dtype=np.uint8)
+    mask[np.unique(mesh.facet_nodes[inner])] = 0
+    eq = cpp.SemiExplicitEquilibrator(cpp.DeviceMesh(mesh), k, 1)
+    with pytest.raises(RuntimeError, match=rf"boundary facet {int(inner.min())} "):
+        eq.set_boundary(bad)
+    one = mask.copy()
+    one[mesh.facet_nodes[inner.min(), 0]] = 1      # one node of an untyped facet is equilibrated: still refused
+    with pytest.raises(RuntimeError, match=rf"boundary facet {int(inner.min())} "):
+        eq.set_boundary(bad, node_mask=one)
+    eq.set_boundary(bad, node_mask=mask)
+    x = _twice(eq, G, f)
+    ref = _oracle_over_nodes(oracle_mod, mesh, k, ft, G, f, mask)
+    assert np.abs(x - ref).max() <= RTOL * np.abs(ref).max()
+    # nodes without a typed facet are not walked by the export either
+    dev = eq.export_patches()
+    for nd in np.nonzero(mask == 0)[0]:
+        assert dev["ncells"][nd] == np.diff(mesh.node_cells_offsets)[nd] and np.all(dev["cells"][nd] == -1)
+
+
+def test_untyped_hole_is_refused_through_the_other_entry_points(cpp):
+    from dolfinx_eqlb_amd.eqlb.FluxEqlbSE import FluxEqlbSE
+    k = 2
+    mesh, ft, G, f = tm.case("hole", "dirichlet", k)
+    inner = tm.inner_loop_facets(mesh)
+    bad = ft.copy()
+    bad[0, inner] = 0
+    ev = cpp.ConstrainedMinEquilibrator(cpp.DeviceMesh(mesh), k, 1)
+    with pytest.raises(RuntimeError, match=rf"boundary facet {int(inner.min())} "):
+        ev.set_boundary(bad)
+    ev.set_boundary(ft)
+    # a caller of the mirror class who lists the outer boundary only
+    outer = np.setdiff1d(mesh.boundary_facets(), inner)
+    eq = FluxEqlbSE(k, mesh, [f[0]], [G[0]])
+    eq.set_boundary_conditions([outer], [[]])
+    with pytest.raises(RuntimeError, match=rf"boundary facet {int(inner.min())} .*needs a boundary condition"):
+        eq.equilibrate_fluxes()
