@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_se_large_patch_info", "eqlb_ev_large_patch_info",
     "eqlb_indicator_total", "eqlb_mark_doerfler",
     "eqlb_primal_flux_dg", "eqlb_primal_stress_dg", "eqlb_get_primal_table",
+    "eqlb_facet_points", "eqlb_flux_bc_dofs", "eqlb_se_update_flux_bc", "eqlb_ev_update_flux_bc",
+    "eqlb_se_get_boundary_values", "eqlb_ev_get_boundary_values",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -63,6 +65,53 @@ def _large_patch_info(fn, h):
     n, mx = C.c_int64(0), C.c_int32(0)
     _check(fn(h, C.byref(n), C.byref(mx)))
     return int(n.value), int(mx.value)
+
+
+def _rule(s, w=None):
+    """Facet rule as host arrays: parameters s in [0, 1] and (optionally) weights w on [0, 1]."""
+    ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+    ww = None if w is None else np.ascontiguousarray(w, dtype=np.float64).ravel()
+    if ww is not None and ww.size != ss.size:
+        raise RuntimeError("Equilibration: Input sizes does not match")
+    return ss, ww
+
+
+def _update_flux_bc(fn, eq, rhs, facets, values, s, w, vector):
+    """Host arrays -> eqlb_*_update_flux_bc: values [nlist, k] facet DOFs (s is None), point values [nlist, nq]
+    of the normal flux, or [nlist, nq, 2] of a vector field (vector=True)."""
+    fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if s is None:
+        nq, ss, ww = 0, None, None
+        need = fl.size * eq.k
+    else:
+        ss, ww = _rule(s, w)
+        if ww is None:
+            raise RuntimeError("Equilibration: point values need the weights of the facet rule")
+        nq = ss.size
+        need = fl.size * nq * (2 if vector else 1)
+    if v.size != need:
+        raise RuntimeError("Equilibration: Input sizes does not match")
+    _check(fn(eq._h, C.c_int32(rhs), C.c_int32(fl.size), _hp(fl), C.c_int32(nq),
+              _hp(ss) if ss is not None else None, _hp(ww) if ww is not None else None, _hp(v),
+              C.c_int32(1 if vector else 0), None, C.c_int32(MEM_HOST), None))
+
+
+def _update_flux_bc_raw(fn, eq, rhs, nlist, facets, values, s, w, vector, nrejected, memspace, stream):
+    if s is None:
+        nq, ss, ww = 0, None, None
+    else:
+        ss, ww = _rule(s, w)
+        nq = ss.size
+    _check(fn(eq._h, C.c_int32(rhs), C.c_int32(nlist), _vp(facets), C.c_int32(nq),
+              _hp(ss) if ss is not None else None, _hp(ww) if ww is not None else None, _vp(values),
+              C.c_int32(1 if vector else 0), _vp(nrejected), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def _get_boundary_values(fn, eq):
+    out = np.zeros((eq.nrhs, eq.dmesh.mesh.ncells * eq.nrt))
+    _check(fn(eq._h, _hp(out), C.c_int32(MEM_HOST), None))
+    return out
 
 
 _lib = None
@@ -199,6 +248,26 @@ class SemiExplicitEquilibrator:
             assert nm.size == m.nnodes
         _check(lib().eqlb_se_set_boundary(self._h, _hp(ft), _hp(bv) if bv is not None else None,
                                           _hp(nm) if nm is not None else None))
+
+    def update_flux_bc(self, rhs: int, facets, values, s=None, w=None, vector=False):
+        """eqlb_se_update_flux_bc on host arrays: new boundary values of right-hand side `rhs` on the listed
+        flux-BC facets, nothing else of the handle changes.  values [nlist, k] facet DOFs as flux_bc_dofs returns
+        them (s is None), or point values at the rule (s, w): [nlist, nq] normal flux, [nlist, nq, 2] with vector."""
+        _update_flux_bc(lib().eqlb_se_update_flux_bc, self, rhs, facets, values, s, w, vector)
+
+    def update_flux_bc_raw(self, rhs: int, nlist: int, facets, values, s=None, w=None, vector=False, nrejected=None,
+                           memspace=MEM_DEVICE, stream=0):
+        """eqlb_se_update_flux_bc on raw pointers (ints) in `memspace`, ordered on `stream`; s, w stay host arrays.
+        Device memory: one kernel, nothing waits; nrejected [1] int32 (or None) counts the refused entries."""
+        _update_flux_bc_raw(lib().eqlb_se_update_flux_bc, self, rhs, nlist, facets, values, s, w, vector, nrejected,
+                            memspace, stream)
+
+    def get_boundary_values(self):
+        """eqlb_se_get_boundary_values: the table [nrhs, ncells*k(k+2)] of the handle (zeros if homogeneous)."""
+        return _get_boundary_values(lib().eqlb_se_get_boundary_values, self)
+
+    def get_boundary_values_raw(self, out, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_se_get_boundary_values(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
 
     @property
     def num_patches(self):
@@ -373,6 +442,28 @@ class ConstrainedMinEquilibrator:
             assert nm.size == m.nnodes
         _check(lib().eqlb_ev_set_boundary(self._h, _hp(ft), _hp(bv) if bv is not None else None,
                                           _hp(nm) if nm is not None else None))
+
+    def update_flux_bc(self, rhs: int, facets, values, s=None, w=None, vector=False):
+        """eqlb_ev_update_flux_bc on host arrays: new boundary values of right-hand side `rhs` on the listed
+        flux-BC facets, nothing else of the handle changes; the values
+        are moments in the frame of the facet's cell whatever the output basis is.  values [nlist, k] facet DOFs as flux_bc_dofs returns
+        them (s is None), or point values at the rule (s, w): [nlist, nq] normal flux, [nlist, nq, 2] with vector."""
+        _update_flux_bc(lib().eqlb_ev_update_flux_bc, self, rhs, facets, values, s, w, vector)
+
+    def update_flux_bc_raw(self, rhs: int, nlist: int, facets, values, s=None, w=None, vector=False, nrejected=None,
+                           memspace=MEM_DEVICE, stream=0):
+        """eqlb_ev_update_flux_bc on raw pointers (ints) in `memspace`, ordered on `stream`; s, w stay host arrays.
+        Device memory: one kernel, nothing waits; nrejected [1] int32 (or None) counts the refused entries."""
+        _update_flux_bc_raw(lib().eqlb_ev_update_flux_bc, self, rhs, nlist, facets, values, s, w, vector, nrejected,
+                            memspace, stream)
+
+    def get_boundary_values(self):
+        """eqlb_ev_get_boundary_values: the table [nrhs, ncells*k(k+2)] of the handle in the broken per-cell
+        layout (zeros if homogeneous)."""
+        return _get_boundary_values(lib().eqlb_ev_get_boundary_values, self)
+
+    def get_boundary_values_raw(self, out, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_ev_get_boundary_values(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
 
     def tiling_blocks(self):
         """As SemiExplicitEquilibrator.tiling_blocks (eqlb_ev_tiling_blocks)."""
@@ -582,6 +673,45 @@ def boundary_residual_raw(dmesh: DeviceMesh, k: int, degree_dg: int, nrhs: int, 
     _check(lib().eqlb_boundary_residual(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), _vp(flux),
                                         _vp(flux_dg), C.c_int32(nfacets_bc), _vp(facets), _vp(boundary_values),
                                         _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def facet_points(dmesh: DeviceMesh, facets, s):
+    """eqlb_facet_points on host arrays: physical points [nlist, nq, 2] of the facet parameters s on the listed
+    boundary facets, seen from the facet's cell (eqlb.bcs._facet_points)."""
+    fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+    ss, _ = _rule(s)
+    out = np.zeros((fl.size, ss.size, 2))
+    facet_points_raw(dmesh, fl.size, _hp(fl), ss, _hp(out), MEM_HOST)
+    return out
+
+
+def facet_points_raw(dmesh: DeviceMesh, nlist: int, facets, s, xq, memspace=MEM_DEVICE, stream=0):
+    """eqlb_facet_points on raw pointers in `memspace` (facets int32, xq [nlist, nq, 2]); s is a host array."""
+    ss, _ = _rule(s)
+    _check(lib().eqlb_facet_points(dmesh._h, C.c_int32(nlist), _vp(facets), C.c_int32(ss.size), _hp(ss), _vp(xq),
+                                   C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def flux_bc_dofs(dmesh: DeviceMesh, k: int, facets, s, w, values, vector=False):
+    """eqlb_flux_bc_dofs on host arrays: facet DOFs [nlist, k] of the hierarchic RT_k from the point values
+    [nlist, nq] of the normal flux, or [nlist, nq, 2] of a vector field with vector=True."""
+    fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+    ss, ww = _rule(s, w)
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.size != fl.size * ss.size * (2 if vector else 1):
+        raise RuntimeError("Equilibration: Input sizes does not match")
+    out = np.zeros((fl.size, max(k, 0)))
+    flux_bc_dofs_raw(dmesh, k, fl.size, _hp(fl), ss, ww, _hp(v), vector, _hp(out), MEM_HOST)
+    return out
+
+
+def flux_bc_dofs_raw(dmesh: DeviceMesh, k: int, nlist: int, facets, s, w, values, vector, dofs, memspace=MEM_DEVICE,
+                     stream=0):
+    """eqlb_flux_bc_dofs on raw pointers in `memspace`, ordered on `stream`; s, w are host arrays."""
+    ss, ww = _rule(s, w)
+    _check(lib().eqlb_flux_bc_dofs(dmesh._h, C.c_int32(k), C.c_int32(nlist), _vp(facets), C.c_int32(ss.size), _hp(ss),
+                                   _hp(ww) if ww is not None else None, _vp(values), C.c_int32(1 if vector else 0),
+                                   _vp(dofs), C.c_int32(memspace), C.c_void_p(stream)))
 
 
 def indicator_total(terms, pair_last_two=False):

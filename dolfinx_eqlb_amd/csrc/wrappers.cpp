@@ -307,6 +307,8 @@ struct BoundaryData
   std::vector<int8_t> facet_type;      // [nrhs][nfacets]
   std::vector<double> boundary_values; // [nrhs][ndofs], empty: homogeneous
   std::vector<std::shared_ptr<Function>> boundary_flux;
+  std::vector<std::vector<std::shared_ptr<FluxBC>>> bcs; // the conditions, kept for update()
+  int qdegree;                                           // rule of the projected conditions
   // device handles, created with the first equilibration call (the degree of the projected data is
   // known only then, se/reconstruction.hpp:363-373) and kept
   eqlb_se_t* se = nullptr;
@@ -322,7 +324,8 @@ struct BoundaryData
   BoundaryData(std::vector<std::vector<std::shared_ptr<FluxBC>>>& list_bcs,
                std::vector<std::shared_ptr<Function>>& bflux, std::shared_ptr<FunctionSpace> V_, bool rt_custom,
                int quadrature_degree, const std::vector<std::vector<int32_t>>& fct_esntbound_prime, bool rstress)
-      : V(std::move(V_)), custom(rt_custom), stress(rstress), boundary_flux(bflux)
+      : V(std::move(V_)), custom(rt_custom), stress(rstress), boundary_flux(bflux), bcs(list_bcs),
+        qdegree(quadrature_degree)
   {
     if (!V || V->family != "RT")
       throw std::runtime_error("BoundaryData: V_flux_hdiv must be an RT space");
@@ -335,10 +338,7 @@ struct BoundaryData
     if ((int)bflux.size() != nrhs || (int)fct_esntbound_prime.size() != nrhs)
       throw std::runtime_error("Size of input data does not match!");
     const int64_t ndofs = V->ndofs();
-    const int nrt = k * (k + 2);
     facet_type.assign((size_t)nrhs * mesh->nfacets, (int8_t)EQLB_FACET_INTERNAL);
-    bool inhomogeneous = false;
-    std::vector<double> sq, wq, vals, cdata, coefs;
     for (int r = 0; r < nrhs; ++r)
     {
       if (!bflux[r] || bflux[r]->on_device || bflux[r]->size() != ndofs)
@@ -350,11 +350,33 @@ struct BoundaryData
           throw std::runtime_error("BoundaryData: facet index out of range");
         ft[f] = EQLB_FACET_ESSNT_PRIMAL;
       }
-      double* xb = bflux[r]->data();
-      for (const auto& bc : list_bcs[r])
+    }
+    if (evaluate(nullptr, nullptr))
+      store_boundary_values();
+  }
+  void store_boundary_values()
+  {
+    const int64_t ndofs = V->ndofs();
+    boundary_values.resize((size_t)nrhs * ndofs);
+    for (int r = 0; r < nrhs; ++r)
+      std::copy_n(boundary_flux[r]->data(), ndofs, &boundary_values[(size_t)r * ndofs]);
+  }
+  // The FluxBC kernels with their current constants and coefficients -> facet types and boundary functions.  Returns
+  // whether any DOF is non-zero.  facets / moments (per right-hand side, or nullptr): the flux-BC facets that carry a
+  // kernel and their k DOFs in the frame of the facet's cell, as eqlb_*_update_flux_bc takes them.
+  bool evaluate(std::vector<std::vector<int32_t>>* facets, std::vector<std::vector<double>>* moments)
+  {
+    const int nrt = k * (k + 2);
+    bool inhomogeneous = false;
+    std::vector<double> sq, wq, vals, cdata, coefs;
+    for (int r = 0; r < nrhs; ++r)
+    {
+      int8_t* ft = &facet_type[(size_t)r * mesh->nfacets];
+      double* xb = boundary_flux[r]->data();
+      for (const auto& bc : bcs[r])
       {
         // base/BoundaryData.cpp:437-445: the number of evaluation points must fit the rule in use
-        facet_rule(bc->projection ? quadrature_degree : interpolation_degree(k), sq, wq);
+        facet_rule(bc->projection ? qdegree : interpolation_degree(k), sq, wq);
         const int nq = (int)sq.size();
         if (nq != bc->nevals)
           throw std::runtime_error("BoundaryData: Number of evaluation points (FluxBC) does not match!");
@@ -407,6 +429,11 @@ struct BoundaryData
             dof[j] = scale * acc;
             inhomogeneous = inhomogeneous || dof[j] != 0.0;
           }
+          if (facets)
+          {
+            (*facets)[r].push_back(fct);
+            (*moments)[r].insert((*moments)[r].end(), dof, dof + k);
+          }
           if (custom)
             for (int j = 0; j < k; ++j)
               xb[(size_t)cell * nrt + lf * k + j] = dof[j];
@@ -426,11 +453,40 @@ struct BoundaryData
         }
       }
     }
-    if (inhomogeneous)
+    return inhomogeneous;
+  }
+  // New values of the flux BCs on unchanged facets (a load step, a time step): the kernels are evaluated again, and
+  // a device handle that exists receives the facet DOFs through eqlb_*_update_flux_bc - its patches, bins and tiles
+  // stay.  A handle created later reads boundary_values as before.
+  void update()
+  {
+    std::vector<std::vector<int32_t>> fl(nrhs);
+    std::vector<std::vector<double>> fd(nrhs);
+    if (evaluate(&fl, &fd) || !boundary_values.empty())
+      store_boundary_values();
+    try
     {
-      boundary_values.resize((size_t)nrhs * ndofs);
       for (int r = 0; r < nrhs; ++r)
-        std::copy_n(bflux[r]->data(), ndofs, &boundary_values[(size_t)r * ndofs]);
+      {
+        const int32_t n = (int32_t)fl[r].size();
+        if (n == 0)
+          continue;
+        if (se)
+          check(eqlb_se_update_flux_bc(se, r, n, fl[r].data(), 0, nullptr, nullptr, fd[r].data(), 0, nullptr,
+                                       EQLB_MEM_HOST, g_stream));
+        if (ev)
+          check(eqlb_ev_update_flux_bc(ev, r, n, fl[r].data(), 0, nullptr, nullptr, fd[r].data(), 0, nullptr,
+                                       EQLB_MEM_HOST, g_stream));
+      }
+    }
+    catch (...)
+    {
+      // no handle with a half-written table is kept: the next call rebuilds it from boundary_values
+      eqlb_se_destroy(se);
+      eqlb_ev_destroy(ev);
+      se = nullptr;
+      ev = nullptr;
+      throw;
     }
   }
   ~BoundaryData()
@@ -885,6 +941,8 @@ PYBIND11_MODULE(_cpp, m)
            py::arg("reconstruct_stress"))
       .def("set_basis_transform", &BoundaryData::set_basis_transform, py::arg("C"), py::arg("R") = py::none(),
            "Output basis of the conforming flux: y_cell = C c_cell, R on the facet block of reflected facets")
+      .def("update", &BoundaryData::update,
+           "Evaluate the flux BCs again (same facets, new values) and push them to the device handle in place")
       .def("set_option", &BoundaryData::set_option, py::arg("key"), py::arg("value"),
            "Integer options of the device handle (eqlb_se_set_option / eqlb_ev_set_option)")
       .def_property_readonly("facet_type", [](const BoundaryData& b) {

@@ -70,6 +70,15 @@ class FluxEqlbEV:
             self.boundary_data.set_option("large_patches", 1)
         self.facet_type = self.boundary_data.facet_type
 
+    def update_boundary_values(self):
+        """New values of the flux BCs on the same facets - a `fluxbc` whose callable closes over a time or a load
+        factor: the conditions are evaluated again into `list_bfunctions`, and the device handle, if it exists,
+        receives the facet DOFs in place (`BoundaryData.update`, eqlb_ev_update_flux_bc); patches and tiles stay.
+        Not in the reference, which rebuilds its BoundaryData."""
+        if self.boundary_data is None:
+            raise RuntimeError("Boundary conditions have not been set")
+        self.boundary_data.update()
+
     def equilibrate_fluxes(self):
         """Equilibrate the fluxes (accumulates into list_flux, FluxEqlbEV.py:167-176)."""
         if self.boundary_data is None:

@@ -59,6 +59,7 @@ extern "C" {
 
 typedef struct eqlb_mesh eqlb_mesh_t;
 typedef struct eqlb_se eqlb_se_t;
+typedef struct eqlb_ev eqlb_ev_t; /* the constrained-minimisation equilibrator, below */
 
 /* Message of the last error on this thread ("" if none). */
 const char* eqlb_last_error(void);
@@ -438,6 +439,86 @@ int eqlb_boundary_residual(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int3
                            const double* flux_dg, int32_t nfacets_bc, const int32_t* facets,
                            const double* boundary_values, double* out, int32_t memspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * New values of the flux boundary conditions without rebuilding the patches - the tractions of a stress handle, the
+ * prescribed normal flux of a Poisson or Darcy flux, in a load-stepping or time-dependent computation.  The reference
+ * rebuilds its BoundaryData for this (base/BoundaryData.cpp:279-633); here bins, tiles, groups of boundary patches
+ * and the choice of the launches depend on the facet TYPES alone, and the kernels read the values at run time.  So the
+ * values are rewritten in place on the listed facets, and eqlb_se_set_boundary / eqlb_ev_set_boundary stay the calls
+ * that change types or node masks.
+ *
+ * Common to the four entry points below:
+ *   facets [nlist] int32   boundary facets (facets with one cell), in the memory space of the call
+ *   s [nq], w [nq]         HOST arrays in either memory space: parameters 0 <= s <= 1 along the facet and weights of a
+ *                          rule on [0, 1]; nq <= 64.  They travel inside the kernel argument: nothing is uploaded.
+ * A facet is seen from its one cell, in the convention of eqlb/bcs.py (_facet_points): local facet 0 has the reference
+ * points (1 - s, s), facet 1 (0, s), facet 2 (s, 0) - the low local vertex of the facet comes first.
+ * Device memory space: one kernel on `stream` (hipStream_t, NULL = default stream), nothing waits for the device.  Host
+ * memory space: staged and synchronous.  One thread per listed facet; every facet, cell and node index is checked
+ * before it is used.  A facet listed twice receives one of its two rows.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Physical points xq [nlist][nq][2] = x_0 + J X(s) of the facet parameters on the listed facets: where a caller
+ * evaluates its boundary data, e.g. as a torch expression on the device.  1 <= nq <= 64.
+ * Errors: null mesh, nlist < 0, nq outside 1 ... 64, s outside [0, 1], unknown memory space: EQLB_ERR_INVALID_ARGUMENT
+ * before any device call.  A facet id outside the mesh or a facet between two cells: host memory space:
+ * EQLB_ERR_INVALID_ARGUMENT naming the facet, nothing is written; device memory space: its points are NaN, nothing is
+ * read out of range. */
+int eqlb_facet_points(eqlb_mesh_t* mesh, int32_t nlist, const int32_t* facets, int32_t nq, const double* s,
+                      double* xq, int32_t memspace, void* stream);
+
+/* Facet DOFs of the hierarchic RT_k from point values, dofs [nlist][k], as base::BoundaryData forms them on the host
+ * (base/BoundaryData.cpp:470-575):
+ *   DOF_j = pf_f sign(det J) |E| sum_q w_q g_q s_q^j,   j < k,   pf_f = +1 for local facet 1, -1 otherwise
+ *   vector = 0: g_q = values[i][q], the prescribed normal flux, values [nlist][nq]
+ *   vector = 1: g_q = values[i][q][:] . n_out with the outward unit normal of the facet, values [nlist][nq][2]
+ * sign(det J) and |E| come from the vertices of the cell.  The k sums run over q in ascending order with s^j as a
+ * running product and without fused multiply-adds: two runs give the same bits, and so does the instance of the
+ * kernel inside eqlb_*_update_flux_bc.  1 <= k <= 4, 1 <= nq <= 64; values and dofs lie in `memspace`.
+ * Errors: as eqlb_facet_points, and k outside 1 ... 4, vector other than 0 / 1; device memory space: the DOFs of a
+ * refused facet are NaN. */
+int eqlb_flux_bc_dofs(eqlb_mesh_t* mesh, int32_t k, int32_t nlist, const int32_t* facets, int32_t nq, const double* s,
+                      const double* w, const double* values, int32_t vector, double* dofs, int32_t memspace,
+                      void* stream);
+
+/* Replace the boundary values of right-hand side `rhs` on the listed facets in the table of the handle
+ * (boundary_values of eqlb_se_set_boundary).  Facets that are not listed keep their values; facet types, node mask,
+ * patches and tiles stay as they are.
+ *   nq = 0:   values [nlist][k] are facet DOFs as eqlb_flux_bc_dofs writes them (s, w may be NULL)
+ *   nq >= 1:  values are point values as eqlb_flux_bc_dofs takes them; the moments are formed in the same kernel, so
+ *             a step costs one launch
+ *   nrejected [1] int32 in the memory space of the call, or NULL: see below
+ * The values are always moments in the frame of the facet's cell.  The EV handle keeps its table in that broken
+ * per-cell layout, so eqlb_ev_update_flux_bc takes the same values whatever "boundary_basis" and
+ * eqlb_ev_set_basis_transform say (eqlb_ev_set_boundary converts its conforming DOFs into this layout).
+ * A handle whose last eqlb_*_set_boundary had boundary_values NULL or all zero owns no table: the first update
+ * allocates it and fills it with zeros on `stream` - THE ONLY UPDATE THAT ALLOCATES (hipMalloc may wait for the
+ * device).  Later updates in device memory neither allocate nor wait; an equilibrate call enqueued later on the same
+ * stream sees the new values.  Values below the kernels' threshold of 1e-7 on every DOF of a facet equilibrate like a
+ * homogeneous condition (base/BoundaryData.cpp:714-725).
+ * Refusals:
+ *   EQLB_ERR_INVALID_ARGUMENT  null handle, nlist < 0, nq outside 0 ... 64, s outside [0, 1], vector other than 0 / 1,
+ *                              unknown memory space, rhs outside 0 ... nrhs - 1, or no accepted eqlb_*_set_boundary
+ *                              on the handle - all before any device call
+ *   every listed facet must have one cell and the type EQLB_FACET_ESSNT_DUAL on right-hand side rhs.
+ *     Host memory space: a facet that breaks this is EQLB_ERR_INVALID_ARGUMENT, the message names the facet, and
+ *     NOTHING is written (the list is checked by a pass of its own); nrejected receives the number of such entries.
+ *     Device memory space: such an entry writes nothing and reads nothing out of range, the other entries are
+ *     written; nrejected receives the number of such entries (0: the whole list was accepted) - the convention of
+ *     eqlb_mark_doerfler's nmarked = -1.  The call itself returns EQLB_OK. */
+int eqlb_se_update_flux_bc(eqlb_se_t* handle, int32_t rhs, int32_t nlist, const int32_t* facets, int32_t nq,
+                           const double* s, const double* w, const double* values, int32_t vector,
+                           int32_t* nrejected, int32_t memspace, void* stream);
+int eqlb_ev_update_flux_bc(eqlb_ev_t* handle, int32_t rhs, int32_t nlist, const int32_t* facets, int32_t nq,
+                           const double* s, const double* w, const double* values, int32_t vector,
+                           int32_t* nrejected, int32_t memspace, void* stream);
+
+/* The table of the handle, out [nrhs][ncells*k(k+2)] in `memspace` (zeros for a handle without a table): what
+ * eqlb_boundary_residual takes as boundary_values.  For an EV handle the broken per-cell layout as well.
+ * EQLB_ERR_INVALID_ARGUMENT without boundary data.  Device memory space: a copy on `stream`. */
+int eqlb_se_get_boundary_values(eqlb_se_t* handle, double* out, int32_t memspace, void* stream);
+int eqlb_ev_get_boundary_values(eqlb_ev_t* handle, double* out, int32_t memspace, void* stream);
+
 /* Estimator total and cell-wise refinement indicator from squared cell-wise terms as the estimator entries above
  * write them - the sums the reference takes on the host (demo/poisson/demo_error_estimation.py:115-123,
  * demo/elasticity/demo_error_estimation.py:135-146).
@@ -584,7 +665,6 @@ int eqlb_se_large_patch_info(const eqlb_se_t* handle, int64_t* npatches, int32_t
  * `eqlb_ev_set_dofmap` installs the caller's cell->dof table instead (the conforming dofmap
  * `V_flux.dofmap.list` of ev/Patch.cpp:497-501, local order of the hierarchic element).
  * ------------------------------------------------------------------------------------------- */
-typedef struct eqlb_ev eqlb_ev_t;
 
 /* eqlb_ev_create: G, f in DG_{k-1}; eqlb_ev_create_dg: in DG_{degree_dg}, 0 <= degree_dg <= k-1 (as eqlb_se_create;
  * the same minimisation problem as with the data embedded into DG_{k-1}) */
