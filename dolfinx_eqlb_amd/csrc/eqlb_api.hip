@@ -1,22 +1,17 @@
-// Host side of the C ABI (include/eqlb.h): device residency of mesh / patch SoA, binning of
-// patches by size, kernel launches.  Mirrors the driver se::reconstruction<T>
-// (cpp/dolfinx_eqlb/se/reconstruction.hpp:337-407) with the per-call setup hoisted into the
-// handle.  There is NO CPU fallback: without a HIP device every compute entry point fails.
-#include "eqlb_internal.h"
-#include "eqlb_host_util.h"
-#include "eqlb_topology_check.h"
+// Host side of the C ABI (include/eqlb.h): device residency of the mesh, the handles and their options, the
+// entries around the sweep (Korn constants, patch export, projection, estimators).  Mirrors the driver
+// se::reconstruction<T> (cpp/dolfinx_eqlb/se/reconstruction.hpp:337-407) with the per-call setup hoisted into the
+// handle: eqlb_boundary_setup.hip builds the patch SoA, eqlb_sweep.hip runs the equilibration.  There is NO CPU
+// fallback: without a HIP device every compute entry point fails.
+#include "eqlb_handle.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <future>
-#include <memory>
 #include <mutex>
-#include <thread>
 
 namespace
 {
@@ -37,158 +32,8 @@ int set_error(int code, const char* fmt, ...)
   return code;
 }
 } // namespace eqlb
-namespace
-{
-
-void free_boundary(eqlb_se* h)
-{
-  dfree(h->facet_type);
-  dfree(h->node_ws);
-  dfree(h->node_group);
-  dfree(h->node_wslevel);
-  h->ws_levels = 1;
-  dfree(h->rest_cells);
-  h->nrest_cells = 0;
-  dfree(h->bvals);
-  dfree(h->node_slot);
-  dfree(h->node_patch);
-  dfree(h->slot_cell);
-  dfree(h->slot_info);
-  dfree(h->pn);
-  dfree(h->pflag);
-  dfree(h->slots); // re-zeroed on the next call (node_mask may have changed)
-  dfree(h->l_off);
-  dfree(h->l_slot_cell);
-  dfree(h->l_slot_info);
-  dfree(h->l_pflag);
-  dfree(h->l_cells);
-  dfree(h->l_ws);
-  dfree(h->l_nodes);
-  dfree(h->l_wsym_off);
-  dfree(h->l_wsym_ws);
-  dfree(h->l_rest_cells);
-  h->l_nrest_cells = 0;
-  h->l_stress = false;
-  h->l_npatch = h->l_nslots = h->l_ncells = 0;
-  h->l_maxcells = 0;
-  dfree(h->t_tiles);
-  dfree(h->t_tile_cells);
-  dfree(h->t_facet_owner);
-  dfree(h->t_slot_cell);
-  dfree(h->t_slot_info);
-  dfree(h->t_pn);
-  dfree(h->t_pflag);
-  h->ntiles = 0;
-  h->t_mixed = false;
-  std::fill(h->t_blocks, h->t_blocks + EQLB_TB_COUNT, int64_t(0));
-  h->boundary_set = false;
-}
-// Grouped boundary patches of the stress path (se/reconstruction.hpp:170-234, se/Patch.cpp:60-104,
-// 762-784; RT_2 only): a node whose two boundary facets carry flux BCs on both stress rows
-// (base/BoundaryData.cpp:611-631) and that has two cells is grouped with the adjacent internal patch.
-// The reference treats the groups one after the other in node order and lets the weak-symmetry step of a
-// group see what the EARLIER groups added to the global stress on the cells of its internal patch
-// (se/solve_patch_weaksym.hpp:100-131 reads the global vector).  On the device all row-wise sweeps come first
-// and every (cell, vertex) contribution keeps its own slot row, so "what has been added so far" is a sum of
-// slot rows: own row + rows of the vertices that are two-cell members of the own group + rows of the vertices
-// that belong to an EARLIER group (group ids are handed out in the reference's discovery order; the patch
-// builder marks those vertices).  The symmetry step of an earlier group has modified the rows of its internal
-// patch, so overlapping groups are ordered: level of a group = 1 + the highest level among the earlier groups
-// that own a vertex of one of its internal patch's cells; the weak-symmetry kernel runs level by level.
-// ws: 0 normal, 1 two-cell member, 2 internal patch; level [nnodes]: level of the node's group (0 elsewhere).
-int find_stress_groups(const eqlb::DeviceMesh& m, const int8_t* facet_type, const uint8_t* node_mask,
-                       std::vector<int8_t>& ws, std::vector<int32_t>& group, std::vector<int8_t>& level,
-                       int& nlevels, bool& any)
-{
-  const int32_t nn = m.nnodes;
-  ws.assign(nn, 0);
-  group.assign(nn, -1);
-  any = false;
-  std::vector<int8_t> cnt(nn, 0);
-  for (int r = 0; r < 2; ++r)
-    for (int32_t f = 0; f < m.nfacets; ++f)
-      if (facet_type[(size_t)r * m.nfacets + f] == EQLB_FACET_ESSNT_DUAL)
-      {
-        ++cnt[m.h_facet_nodes[2 * (size_t)f]];
-        ++cnt[m.h_facet_nodes[2 * (size_t)f + 1]];
-      }
-  int32_t ngroups = 0;
-  for (int32_t node = 0; node < nn; ++node)
-  {
-    if (node_mask && !node_mask[node])
-      continue;
-    if (cnt[node] != 4 || group[node] >= 0 || m.h_node_ncells[node] != 2)
-      continue;
-    int32_t inner = -1;
-    for (int32_t q = m.h_node_facets_off[node]; q < m.h_node_facets_off[node + 1] && inner < 0; ++q)
-    {
-      const int32_t f = m.h_node_facets[q];
-      if (facet_type[f] == EQLB_FACET_INTERNAL)
-        inner = (m.h_facet_nodes[2 * (size_t)f] == node) ? m.h_facet_nodes[2 * (size_t)f + 1]
-                                                         : m.h_facet_nodes[2 * (size_t)f];
-    }
-    if (inner < 0)
-      continue;
-    std::vector<int32_t> members{inner};
-    for (int32_t q = m.h_node_cells_off[inner]; q < m.h_node_cells_off[inner + 1]; ++q)
-      for (int v = 0; v < 3; ++v)
-      {
-        const int32_t pnt = m.h_cell_nodes[3 * (size_t)m.h_node_cells[q] + v];
-        if (cnt[pnt] == 4 && m.h_node_ncells[pnt] == 2
-            && std::find(members.begin(), members.end(), pnt) == members.end())
-          members.push_back(pnt);
-      }
-    if (members.size() < 2)
-      continue;
-    for (int32_t nd : members)
-    {
-      if (group[nd] >= 0 || (node_mask && !node_mask[nd]))
-        return fail(EQLB_ERR_UNSUPPORTED,
-                    "Incompatible mesh! To many patches with 2 cells on neumann boundary.");
-      group[nd] = ngroups;
-      ws[nd] = (nd == inner) ? 2 : 1;
-    }
-    ++ngroups;
-    any = true;
-  }
-  // levels of overlapping groups (ascending group id = the reference's order)
-  level.assign(nn, 0);
-  nlevels = 1;
-  if (any)
-  {
-    std::vector<int32_t> inner_of(ngroups, -1);
-    for (int32_t node = 0; node < nn; ++node)
-      if (ws[node] == 2)
-        inner_of[group[node]] = node;
-    std::vector<int> glevel(ngroups, 0);
-    for (int32_t g = 0; g < ngroups; ++g)
-    {
-      const int32_t node = inner_of[g];
-      int lv = 0;
-      for (int32_t q = m.h_node_cells_off[node]; q < m.h_node_cells_off[node + 1]; ++q)
-        for (int v = 0; v < 3; ++v)
-        {
-          const int32_t nd = m.h_cell_nodes[3 * (size_t)m.h_node_cells[q] + v];
-          if (group[nd] >= 0 && group[nd] < g)
-            lv = std::max(lv, glevel[group[nd]] + 1);
-        }
-      glevel[g] = lv;
-      nlevels = std::max(nlevels, lv + 1);
-    }
-    if (nlevels > eqlb::WS_MAX_LEVELS)
-      return fail(EQLB_ERR_UNSUPPORTED, "more than %d levels of overlapping groups of boundary patches",
-                  eqlb::WS_MAX_LEVELS);
-    for (int32_t node = 0; node < nn; ++node)
-      if (group[node] >= 0)
-        level[node] = (int8_t)glevel[group[node]];
-  }
-  return EQLB_OK;
-}
-
-} // namespace
 
 extern "C" {
-
 
 const char* eqlb_last_error(void) { return g_error.c_str(); }
 
@@ -378,9 +223,7 @@ void eqlb_se_destroy(eqlb_se_t* h)
 {
   if (!h)
     return;
-  free_boundary(h);
   dfree(h->tables);
-  dfree(h->slots);
   dfree(h->status);
   dfree(h->d_flux_dg);
   dfree(h->d_rhs_dg);
@@ -477,367 +320,14 @@ int eqlb_se_set_option(eqlb_se_t* h, const char* key, int32_t value)
   return EQLB_OK;
 }
 
-int eqlb_se_set_boundary(eqlb_se_t* h, const int8_t* facet_type, const double* boundary_values,
-                         const uint8_t* node_mask)
-try
-{
-  if (!h || !facet_type)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_set_boundary: null argument");
-  SetupTimer tm;
-  const eqlb::DeviceMesh& m = h->mesh->m;
-  for (size_t i = 0; i < (size_t)h->nrhs * m.nfacets; ++i)
-    if (facet_type[i] < EQLB_FACET_INTERNAL || facet_type[i] > EQLB_FACET_ESSNT_DUAL)
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_set_boundary: facet type %d out of range", (int)facet_type[i]);
-  bool inhomogeneous = false;
-  if (boundary_values)
-  {
-    const size_t nb = (size_t)h->nrhs * m.ncells * h->nrt;
-    for (size_t i = 0; i < nb && !inhomogeneous; ++i)
-      inhomogeneous = (boundary_values[i] != 0.0);
-  }
-  // (into a local: the handle is not touched before the last check that can refuse the table with the old boundary
-  // data still in place; the sweep reads h->stress_flux_bcs)
-  bool stress_flux_bcs = false;
-  if (h->stress)
-    for (size_t i = 0; i < (size_t)2 * m.nfacets && !stress_flux_bcs; ++i)
-      stress_flux_bcs = (facet_type[i] == EQLB_FACET_ESSNT_DUAL);
-  // RT_2 stress: the fused tiled launch (k_se_stress_tiled) reads DG_1 data; DG_0 data take the route of stress flux
-  // BCs - rows into the slots by the patch kernels of the handle's degree, then the weak-symmetry kernel of that route
-  // (launch_se_weaksym with no_flux_bcs = false; it reads no DG data, nor do the Korn kernels)
-  const bool stress_fused_ok = h->k == 2 && h->deg == 1 && !stress_flux_bcs;
-  // OrientedPatch::set_max_patch_size (se/Patch.cpp:337-404): every local node is checked
-  for (int32_t i = 0; i < m.nnodes; ++i)
-  {
-    if (node_mask && !node_mask[i])
-      continue; // the reference loops the owned nodes only (size_local)
-    if (m.h_node_ncells[i] == 1)
-      return fail(EQLB_ERR_PATCH_TOO_SMALL, "Patch around node %d has only 1 cells.", i);
-    if (m.h_node_ncells[i] < 1)
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "node %d belongs to no cell", i);
-  }
-  // What the patch builder cannot walk (eqlb_topology_check.h), refused before the old tables are freed: a refused
-  // call leaves the handle as it was.  Facets both of whose nodes are masked out are not looked at.
-  {
-    const eqlb::TopoFinding tf = eqlb::check_boundary_topology(
-        m.nnodes, m.nfacets, h->nrhs, m.h_node_ncells.data(), m.h_node_nfcts.data(), m.h_node_nbnd.data(),
-        m.h_facet_nodes.data(), m.h_facet_cells_off.data(), facet_type, node_mask);
-    if (tf.verdict == eqlb::TOPO_NODE_NOT_WALKABLE)
-      return fail(EQLB_ERR_UNSUPPORTED,
-                  "Patch around node %d (%d cells, %d facets, %d of them boundary facets) is neither one closed ring nor "
-                  "one open fan of cells: a vertex where the boundary touches itself cannot be equilibrated",
-                  tf.index, m.h_node_ncells[tf.index], m.h_node_nfcts[tf.index], m.h_node_nbnd[tf.index]);
-    if (tf.verdict == eqlb::TOPO_BOUNDARY_FACET_UNTYPED)
-      return fail(EQLB_ERR_INVALID_ARGUMENT,
-                  "eqlb_se_set_boundary: boundary facet %d (nodes %d, %d) has type 0 on right-hand side %d: every "
-                  "facet with one cell at an equilibrated node needs a boundary condition",
-                  tf.index, m.h_facet_nodes[2 * (size_t)tf.index], m.h_facet_nodes[2 * (size_t)tf.index + 1], tf.row);
-    if (tf.verdict == eqlb::TOPO_INTERIOR_FACET_TYPED)
-      return fail(EQLB_ERR_INVALID_ARGUMENT,
-                  "eqlb_se_set_boundary: facet %d (nodes %d, %d) lies between two cells and has type %d on right-hand "
-                  "side %d: only facets with one cell carry boundary conditions",
-                  tf.index, m.h_facet_nodes[2 * (size_t)tf.index], m.h_facet_nodes[2 * (size_t)tf.index + 1],
-                  (int)facet_type[(size_t)tf.row * m.nfacets + tf.index], tf.row);
-  }
-  tm.lap("checks");
-  free_boundary(h);
-  h->stress_flux_bcs = stress_flux_bcs;
-  tm.lap("free old tables");
-
-  // bins by lanes per patch: P = smallest of {4,8,16,32,64} >= number of patch facets
-  std::vector<int64_t> node_slot(m.nnodes, -1), node_patch(m.nnodes, -1);
-  int64_t count[eqlb::MAX_BINS] = {0, 0, 0, 0, 0};
-  std::vector<int8_t> node_bin(m.nnodes, -1);
-  std::vector<int32_t> large_nodes; // patches of more than 63 cells or more than 64 facets
-  for (int32_t i = 0; i < m.nnodes; ++i)
-  {
-    if (node_mask && !node_mask[i])
-      continue;
-    const int nf = m.h_node_nfcts[i];
-    int b = 0;
-    while (b < eqlb::MAX_BINS && eqlb::BIN_P[b] < nf)
-      ++b;
-    if (b == eqlb::MAX_BINS || m.h_node_ncells[i] > 63)
-    {
-      if (!h->large_patches)
-        return fail(EQLB_ERR_PATCH_TOO_LARGE, "Patch around node %d has %d cells (limit 63)", i,
-                    m.h_node_ncells[i]);
-      // option "large_patches": the patch goes to the multi-wave kernel (a CSR-style SoA of its own, below); its node
-      // stays out of the bins and is, for the tiles, a node that another path equilibrates
-      if (h->stress && !h->large_patches_stress)
-        return fail(EQLB_ERR_PATCH_TOO_LARGE,
-                    "Patch around node %d has %d cells: the stress equilibration (weak symmetry, Korn constants) is "
-                    "limited to 63 cells per patch, \"large_patches\" covers flux equilibration only",
-                    i, m.h_node_ncells[i]);
-      if (h->mode == 1 && h->k >= 4)
-        return fail(EQLB_ERR_PATCH_TOO_LARGE,
-                    "Patch around node %d has %d cells: the constrained minimisation at RT_4 is limited to 63 cells per "
-                    "patch, \"large_patches\" covers it for RT_1 ... RT_3",
-                    i, m.h_node_ncells[i]);
-      large_nodes.push_back(i);
-      continue;
-    }
-    node_bin[i] = (int8_t)b;
-    ++count[b];
-  }
-  int64_t slot_off = 0, patch_off = 0;
-  for (int b = 0; b < eqlb::MAX_BINS; ++b)
-  {
-    h->bins[b].P = eqlb::BIN_P[b];
-    h->bins[b].npatch = count[b];
-    h->bins[b].slot_offset = slot_off;
-    h->bins[b].patch_offset = patch_off;
-    slot_off += count[b] * eqlb::BIN_P[b];
-    patch_off += count[b];
-    count[b] = 0;
-  }
-  h->nslots = slot_off;
-  h->npatch_total = patch_off;
-  // fused stress launch (RT_2, no flux BCs on the stress rows): it takes the FULL patches of the bins 0, 1 -
-  // interior, as many cells as lanes -, listed first in their bin; the generic kernels take the patches behind them
-  const bool full_first = h->stress && stress_fused_ok && h->mode == 0;
-  auto is_full = [&](int32_t i) {
-    const int b = node_bin[i];
-    return full_first && b >= 0 && b < 2 && m.h_node_ncells[i] == m.h_node_nfcts[i]
-           && m.h_node_ncells[i] == eqlb::BIN_P[b];
-  };
-  for (int pass = 0; pass < 2; ++pass)
-  {
-    for (int32_t i = 0; i < m.nnodes; ++i)
-    {
-      const int b = node_bin[i];
-      if (b < 0 || is_full(i) != (pass == 0))
-        continue;
-      node_patch[i] = h->bins[b].patch_offset + count[b];
-      node_slot[i] = h->bins[b].slot_offset + count[b] * eqlb::BIN_P[b];
-      ++count[b];
-    }
-    if (pass == 0)
-      for (int b = 0; b < eqlb::MAX_BINS; ++b)
-        h->bins[b].nfull = count[b];
-  }
-
-  tm.lap("binning");
-  int st = 0;
-  st |= upload(&h->facet_type, facet_type, (size_t)h->nrhs * m.nfacets);
-  if (inhomogeneous)
-    st |= upload(&h->bvals, boundary_values, (size_t)h->nrhs * m.ncells * h->nrt);
-  st |= upload(&h->node_slot, node_slot.data(), (size_t)m.nnodes);
-  st |= upload(&h->node_patch, node_patch.data(), (size_t)m.nnodes);
-  st |= upload<int32_t>(&h->slot_cell, nullptr, (size_t)h->nslots);
-  st |= upload<uint32_t>(&h->slot_info, nullptr, (size_t)h->nslots);
-  st |= upload<uint8_t>(&h->pn, nullptr, (size_t)h->npatch_total);
-  st |= upload<uint8_t>(&h->pflag, nullptr, (size_t)h->npatch_total * h->nrhs);
-  if (st)
-    return EQLB_ERR_DEVICE;
-  HIP_TRY(hipMemset(h->slot_cell, 0xff, sizeof(int32_t) * std::max<int64_t>(h->nslots, 1)));
-  HIP_TRY(hipMemset(h->slot_info, 0, sizeof(uint32_t) * std::max<int64_t>(h->nslots, 1)));
-
-  eqlb::BuildArgs a{};
-  a.nnodes = m.nnodes;
-  a.nfacets = m.nfacets;
-  a.nrhs = h->nrhs;
-  a.cell_nodes = m.cell_nodes;
-  a.cell_facets = m.cell_facets;
-  a.facet_nodes = m.facet_nodes;
-  a.facet_cells_off = m.facet_cells_off;
-  a.facet_cells = m.facet_cells;
-  a.node_cells_off = m.node_cells_off;
-  a.node_facets_off = m.node_facets_off;
-  a.node_facets = m.node_facets;
-  a.facet_perm = m.facet_perm;
-  a.facet_type = h->facet_type;
-  if (h->stress && h->k == 2 && h->stress_flux_bcs)
-  {
-    std::vector<int8_t> ws, lvl;
-    std::vector<int32_t> grp;
-    bool any = false;
-    h->ws_levels = 1;
-    const int stg = find_stress_groups(m, facet_type, node_mask, ws, grp, lvl, h->ws_levels, any);
-    if (stg)
-      return stg;
-    // a large patch inside a group (its two-cell members never are large): the weak-symmetry kernel of the large
-    // patches does not read the rows of other patches
-    for (int32_t nd : large_nodes)
-      if (any && ws[nd] != 0)
-        return fail(EQLB_ERR_UNSUPPORTED,
-                    "Patch around node %d has %d cells and is the internal patch of group %d of boundary patches with "
-                    "tractions on both stress rows: groups are limited to 63 cells per patch (\"large_patches_stress\")",
-                    nd, m.h_node_ncells[nd], grp[nd]);
-    if (any)
-    {
-      if (upload(&h->node_ws, ws.data(), ws.size()) || upload(&h->node_group, grp.data(), grp.size())
-          || upload(&h->node_wslevel, lvl.data(), lvl.size()))
-        return EQLB_ERR_DEVICE;
-      a.node_ws = h->node_ws;
-      a.node_group = h->node_group;
-      a.node_wslevel = h->node_wslevel;
-    }
-  }
-  a.node_slot = h->node_slot;
-  a.node_patch = h->node_patch;
-  a.npatch_total = h->npatch_total;
-  a.slot_cell = h->slot_cell;
-  a.slot_info = h->slot_info;
-  a.pn = h->pn;
-  a.pflag = h->pflag;
-  a.stride = 0;
-  eqlb::launch_build_patches(a, nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  tm.lap("plain SoA: upload + builder");
-  if (!large_nodes.empty())
-  {
-    // large patches: lane slots in CSR form (l_off), the same descriptor bits, flags per right-hand side; the cell
-    // count of a patch is the difference of its offsets
-    const int64_t nl = (int64_t)large_nodes.size();
-    std::vector<int64_t> lslot(m.nnodes, -1), lpatch(m.nnodes, -1);
-    std::vector<int32_t> off(nl + 1, 0);
-    std::vector<uint8_t> is_large(m.nnodes, 0);
-    int64_t acc = 0;
-    for (int64_t p = 0; p < nl; ++p)
-    {
-      const int32_t nd = large_nodes[p];
-      lslot[nd] = acc;
-      lpatch[nd] = p;
-      is_large[nd] = 1;
-      off[p] = (int32_t)acc;
-      acc += m.h_node_ncells[nd];
-      h->l_maxcells = std::max(h->l_maxcells, m.h_node_ncells[nd]);
-      if (acc > 0x7fffff00)
-        return fail(EQLB_ERR_UNSUPPORTED, "large-patch SoA exceeds 2^31 lane slots");
-    }
-    off[nl] = (int32_t)acc;
-    std::vector<int32_t> lc;
-    for (int32_t c = 0; c < m.ncells; ++c)
-      for (int j = 0; j < 3; ++j)
-        if (is_large[m.h_cell_nodes[3 * (size_t)c + j]])
-        {
-          lc.push_back(c);
-          break;
-        }
-    int64_t *d_lslot = nullptr, *d_lpatch = nullptr;
-    int stl = 0;
-    stl |= upload(&h->l_off, off.data(), off.size());
-    stl |= upload<int32_t>(&h->l_slot_cell, nullptr, (size_t)acc);
-    stl |= upload<uint32_t>(&h->l_slot_info, nullptr, (size_t)acc);
-    stl |= upload<uint8_t>(&h->l_pflag, nullptr, (size_t)nl * h->nrhs);
-    stl |= upload(&h->l_cells, lc.data(), lc.size());
-    stl |= upload<double>(&h->l_ws, nullptr, eqlb::large_patch_ws_doubles(h->k, acc, nl));
-    stl |= upload(&h->l_nodes, large_nodes.data(), large_nodes.size());
-    if (h->stress)
-    {
-      // work space of the weak-symmetry kernel: per patch, quadratic in its cells (the Schur matrix)
-      std::vector<int64_t> woff(nl + 1, 0);
-      for (int64_t p = 0; p < nl; ++p)
-        woff[p + 1] = woff[p] + (int64_t)eqlb::large_patch_weaksym_ws_doubles(h->k, m.h_node_ncells[large_nodes[p]]);
-      stl |= upload(&h->l_wsym_off, woff.data(), (size_t)nl);
-      stl |= upload<double>(&h->l_wsym_ws, nullptr, (size_t)woff[nl]);
-    }
-    stl |= upload(&d_lslot, lslot.data(), lslot.size());
-    stl |= upload(&d_lpatch, lpatch.data(), lpatch.size());
-    hipError_t e = hipSuccess;
-    if (!stl)
-    {
-      eqlb::BuildArgs al = a;
-      al.node_ws = nullptr;
-      al.node_slot = d_lslot;
-      al.node_patch = d_lpatch;
-      al.npatch_total = nl;
-      al.slot_cell = h->l_slot_cell;
-      al.slot_info = h->l_slot_info;
-      al.pn = nullptr;
-      al.pflag = h->l_pflag;
-      al.large = 1;
-      eqlb::launch_build_patches(al, nullptr);
-      e = hipGetLastError();
-      if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    }
-    dfree(d_lslot);
-    dfree(d_lpatch);
-    if (stl)
-      return EQLB_ERR_DEVICE;
-    if (e != hipSuccess)
-      return fail(EQLB_ERR_DEVICE, "large-patch builder: %s", hipGetErrorString(e));
-    h->l_npatch = nl;
-    h->l_nslots = acc;
-    h->l_ncells = (int64_t)lc.size();
-    h->l_stress = h->large_patches_stress != 0;
-    tm.lap("large-patch SoA");
-  }
-  h->t_stress = h->stress && stress_fused_ok && h->mode == 0;
-  if (h->t_stress || (!h->stress && h->k <= 3))
-  {
-    // fused stress launch: its own tile size, patches of up to 8 facets (bins 0, 1)
-    h->t_mixed = false;
-    if (h->t_stress)
-    {
-      // Patches of the bins 0, 1 that are not full (interior with fewer cells than lanes, boundary): on the crossed
-      // benchmark meshes the boundary patches only (0.4 %) - the tiles list the full patches and the others go with
-      // the rest (generic kernels on a side stream next to the fused kernel); on unstructured meshes most patches -
-      // the tiles list every patch of the two bins and the kernel carries both instances of the body.
-      // EQLB_STRESS_MIXED_TILES=0/1 forces the choice.
-      int64_t nlisted = 0, nnotfull = 0;
-      for (int32_t i = 0; i < m.nnodes; ++i)
-      {
-        const int8_t b = node_bin[i];
-        if (b < 0 || b >= 2)
-          continue;
-        ++nlisted;
-        if (!(m.h_node_ncells[i] == m.h_node_nfcts[i] && m.h_node_ncells[i] == eqlb::BIN_P[b]))
-          ++nnotfull;
-      }
-      h->t_mixed = nnotfull * 20 > nlisted;
-      if (const char* env = getenv("EQLB_STRESS_MIXED_TILES"))
-        h->t_mixed = env[0] != '0';
-    }
-    const int stt = h->t_stress ? eqlb::build_tiles(h, node_bin, a, eqlb::stress_tile_cells(), 2, !h->t_mixed)
-                                : eqlb::build_tiles(h, node_bin, a);
-    if (stt)
-      return stt;
-    if (h->mode == 1)
-    {
-      const int64_t ne = (int64_t)h->ntiles * h->tile_tc * 3;
-      if (upload<int32_t>(&h->t_facet_owner, nullptr, (size_t)std::max<int64_t>(ne, 1)))
-        return EQLB_ERR_DEVICE;
-      eqlb::launch_tile_facet_owner(m, ne, h->t_tile_cells, h->t_facet_owner, nullptr);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  }
-  if (h->t_stress && h->l_npatch > 0)
-  {
-    // fused stress launch: the rows of the rest and of the large patches go through the slot buffer together; one
-    // compact reduction over the cells that either of them touches
-    std::vector<uint8_t> touched(m.nnodes, 0);
-    for (int32_t i = 0; i < m.nnodes; ++i)
-      touched[i] = (!node_mask || node_mask[i]) && (node_bin[i] < 0 || node_bin[i] >= 2 || (!h->t_mixed && !is_full(i)));
-    std::vector<int32_t> rc;
-    for (int32_t c = 0; c < m.ncells; ++c)
-      for (int j = 0; j < 3; ++j)
-        if (touched[m.h_cell_nodes[3 * (size_t)c + j]])
-        {
-          rc.push_back(c);
-          break;
-        }
-    h->l_nrest_cells = (int64_t)rc.size();
-    if (upload(&h->l_rest_cells, rc.data(), rc.size()))
-      return EQLB_ERR_DEVICE;
-  }
-  tm.lap("tiles (total)");
-  h->boundary_set = true;
-  return EQLB_OK;
-}
-EQLB_CATCH_ALL
-
 int eqlb_se_kornconst(eqlb_se_t* h, double* cells_kornconst, int32_t memspace, void* stream_)
 try
 {
   if (!h || !cells_kornconst)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  if (!h->boundary_set)
+  if (!h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_kornconst: boundary data not set");
-  if (h->l_npatch > 0 && !h->l_stress)
+  if (h->bt.l_npatch > 0 && !h->bt.l_stress)
     return fail(EQLB_ERR_PATCH_TOO_LARGE,
                 "eqlb_se_kornconst: the Korn constants are limited to 63 cells per patch, \"large_patches\" covers flux "
                 "equilibration only");
@@ -853,9 +343,9 @@ try
     HIP_TRY(hipMemcpyAsync(h->d_korn, cells_kornconst, sizeof(double) * m.ncells, hipMemcpyHostToDevice, stream));
     d_korn = h->d_korn;
   }
-  eqlb::launch_korn(m, h->node_slot, h->node_patch, h->slot_cell, h->slot_info, h->pn, h->pflag,
-                    h->d_cks, d_korn, stream, h->l_npatch, h->l_nodes, h->l_off, h->l_slot_cell, h->l_slot_info,
-                    h->l_pflag);
+  eqlb::launch_korn(m, h->bt.node_slot, h->bt.node_patch, h->bt.slot_cell, h->bt.slot_info, h->bt.pn, h->bt.pflag,
+                    h->d_cks, d_korn, stream, h->bt.l_npatch, h->bt.l_nodes, h->bt.l_off, h->bt.l_slot_cell, h->bt.l_slot_info,
+                    h->bt.l_pflag);
   HIP_TRY(hipGetLastError());
   if (memspace == EQLB_MEM_HOST)
   {
@@ -866,43 +356,43 @@ try
 }
 EQLB_CATCH_ALL
 
-int64_t eqlb_se_num_patches(const eqlb_se_t* h) { return h ? h->npatch_total : 0; }
+int64_t eqlb_se_num_patches(const eqlb_se_t* h) { return h ? h->bt.npatch_total : 0; }
 
 int eqlb_se_tiling_info(const eqlb_se_t* h, int64_t* ntiles, int64_t* cells_per_tile,
                         int64_t* npatch_instances, int64_t* nlane_slots)
 {
-  if (!h || !h->boundary_set)
+  if (!h || !h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_tiling_info: set the boundary first");
   if (ntiles)
-    *ntiles = h->ntiles;
+    *ntiles = h->bt.ntiles;
   if (cells_per_tile)
-    *cells_per_tile = h->tile_tc;
+    *cells_per_tile = h->bt.tile_tc;
   if (npatch_instances)
-    *npatch_instances = h->t_npatch;
+    *npatch_instances = h->bt.t_npatch;
   if (nlane_slots)
-    *nlane_slots = h->t_nslots;
+    *nlane_slots = h->bt.t_nslots;
   return EQLB_OK;
 }
 
 int eqlb_se_tiling_blocks(const eqlb_se_t* h, int64_t* out, int32_t n)
 {
-  if (!h || !h->boundary_set)
+  if (!h || !h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_tiling_blocks: set the boundary first");
   if (n < 0 || (n > 0 && !out))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_tiling_blocks: invalid argument");
   for (int32_t i = 0; i < std::min<int32_t>(n, EQLB_TB_COUNT); ++i)
-    out[i] = h->ntiles > 0 ? h->t_blocks[i] : 0;
+    out[i] = h->bt.ntiles > 0 ? h->bt.t_blocks[i] : 0;
   return EQLB_OK;
 }
 
 int eqlb_se_large_patch_info(const eqlb_se_t* h, int64_t* npatches, int32_t* max_cells)
 {
-  if (!h || !h->boundary_set)
+  if (!h || !h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_large_patch_info: set the boundary first");
   if (npatches)
-    *npatches = h->l_npatch;
+    *npatches = h->bt.l_npatch;
   if (max_cells)
-    *max_cells = h->l_maxcells;
+    *max_cells = h->bt.l_maxcells;
   return EQLB_OK;
 }
 
@@ -916,7 +406,7 @@ try
 }
 EQLB_CATCH_ALL
 
-int32_t eqlb_se_num_priority_tiles(const eqlb_se_t* h) { return (h && h->boundary_set) ? h->t_nprio : 0; }
+int32_t eqlb_se_num_priority_tiles(const eqlb_se_t* h) { return (h && h->bt.boundary_set) ? h->bt.t_nprio : 0; }
 
 int eqlb_se_export_patches(eqlb_se_t* h, int32_t stride, int32_t* ncells, int32_t* cells,
                            int32_t* fcts, int8_t* fcts_local, int8_t* inodes_local,
@@ -925,7 +415,7 @@ try
 {
   if (!h || !ncells || !cells || !fcts || !fcts_local || !inodes_local || !reversed)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_export_patches: null argument");
-  if (!h->boundary_set)
+  if (!h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_export_patches: set the boundary first");
   const eqlb::DeviceMesh& m = h->mesh->m;
   if (stride < m.ncells_max + 2)
@@ -955,7 +445,7 @@ try
     a.node_facets_off = m.node_facets_off;
     a.node_facets = m.node_facets;
     a.facet_perm = m.facet_perm;
-    a.facet_type = h->facet_type;
+    a.facet_type = h->bt.facet_type;
     a.node_slot = nullptr;
     a.node_patch = nullptr;
     a.npatch_total = 0;
@@ -1556,48 +1046,7 @@ int eqlb_ev_set_basis_transform(eqlb_ev_t* h, const double* C, const double* R)
 
 int64_t eqlb_ev_num_dofs(const eqlb_ev_t* h) { return h ? h->se->ev_ndofs : 0; }
 
-int eqlb_ev_set_boundary(eqlb_ev_t* h, const int8_t* facet_type, const double* boundary_values,
-                         const uint8_t* node_mask)
-try
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_boundary: null argument");
-  eqlb_se* se = h->se;
-  const int st = eqlb_se_set_boundary(se, facet_type, nullptr, node_mask);
-  if (st)
-    return st;
-  const eqlb::DeviceMesh& m = se->mesh->m;
-  bool inhomogeneous = false;
-  const size_t nb = (size_t)se->nrhs * se->ev_ndofs;
-  if (boundary_values)
-    for (size_t i = 0; i < nb && !inhomogeneous; ++i)
-      inhomogeneous = (boundary_values[i] != 0.0);
-  if (inhomogeneous)
-  {
-    // conforming boundary DOFs -> the broken per-cell layout the patch kernel reads
-    double* d_conf = nullptr;
-    if (upload(&d_conf, boundary_values, nb)
-        || upload<double>(&se->bvals, nullptr, (size_t)se->nrhs * m.ncells * se->nrt))
-    {
-      dfree(d_conf);
-      return EQLB_ERR_DEVICE;
-    }
-    hipError_t e = hipMemset(se->bvals, 0, sizeof(double) * (size_t)se->nrhs * m.ncells * se->nrt);
-    if (e == hipSuccess)
-    {
-      eqlb::launch_ev_boundary_to_broken(m, se->k, se->nrhs, se->ev_cell_dofs, se->ev_ndofs, d_conf, se->bvals,
-                                         (se->ev_basis && !se->ev_bv_hier) ? se->ev_basis + se->nrt * se->nrt + se->k * se->k : nullptr, nullptr);
-      e = hipDeviceSynchronize();
-    }
-    dfree(d_conf);
-    if (e != hipSuccess)
-      return fail(EQLB_ERR_DEVICE, "eqlb_ev_set_boundary: %s", hipGetErrorString(e));
-  }
-  return EQLB_OK;
-}
-EQLB_CATCH_ALL
-
-int64_t eqlb_ev_num_patches(const eqlb_ev_t* h) { return h ? h->se->npatch_total : 0; }
+int64_t eqlb_ev_num_patches(const eqlb_ev_t* h) { return h ? h->se->bt.npatch_total : 0; }
 
 int eqlb_ev_large_patch_info(const eqlb_ev_t* h, int64_t* npatches, int32_t* max_cells)
 {

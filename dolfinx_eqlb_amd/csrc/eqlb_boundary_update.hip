@@ -7,7 +7,7 @@
 //   DOF_j = pf_f sign(det J) |E| sum_q w_q g_q s_q^j,   pf_f = +1 for local facet 1, -1 otherwise.
 // The lists are O(sqrt(N)) long: the kernels are bound by the launch latency and are not tuned.
 #include "eqlb_internal.h"
-#include "eqlb_host_util.h"
+#include "eqlb_handle.h"
 
 #include <cmath>
 #include <cstring>
@@ -317,7 +317,7 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
   if (rhs < 0 || rhs >= h->nrhs)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: right-hand side %d outside 0 ... %d", who, (int)rhs, h->nrhs - 1);
-  if (!h->boundary_set)
+  if (!h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: boundary data not set (no accepted eqlb_%s_set_boundary)", who,
                 h->mode == 1 ? "ev" : "se");
   const eqlb::DeviceMesh& m = h->mesh->m;
@@ -330,15 +330,15 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
   a.vector = vector;
   a.rhs = rhs;
   a.values = values;
-  a.facet_type = h->facet_type + (size_t)rhs * m.nfacets;
+  a.facet_type = h->bt.facet_type + (size_t)rhs * m.nfacets;
   const size_t ntable = (size_t)h->nrhs * m.ncells * h->nrt;
   // a handle with homogeneous values has no table: the first update allocates it, zero-filled, ordered on the stream
   auto ensure_table = [&]() -> int {
-    if (h->bvals)
+    if (h->bt.bvals)
       return EQLB_OK;
-    if (upload<double>(&h->bvals, nullptr, ntable))
+    if (h->bt.bvals.alloc(ntable))
       return EQLB_ERR_DEVICE;
-    HIP_TRY(hipMemsetAsync(h->bvals, 0, sizeof(double) * ntable, stream));
+    HIP_TRY(hipMemsetAsync(h->bt.bvals, 0, sizeof(double) * ntable, stream));
     return EQLB_OK;
   };
   if (memspace == EQLB_MEM_DEVICE)
@@ -348,7 +348,7 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
     if (nlist == 0)
       return EQLB_OK;
     EQLB_TRY(ensure_table());
-    a.bvals = h->bvals;
+    a.bvals = h->bt.bvals;
     a.nrejected = nrejected;
     launch_flux_bc(a, rule, stream);
     HIP_TRY(hipGetLastError());
@@ -386,7 +386,7 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
                 who, (int)i, (int)f, (int)rhs);
   }
   EQLB_TRY(ensure_table());
-  a.bvals = h->bvals;
+  a.bvals = h->bt.bvals;
   a.nrejected = nullptr;
   a.first_bad = nullptr;
   a.check_only = 0;
@@ -402,24 +402,24 @@ int get_boundary_values(const char* who, eqlb_se* h, double* out, int32_t memspa
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
   if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
-  if (!h->boundary_set)
+  if (!h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: boundary data not set", who);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const size_t bytes = sizeof(double) * (size_t)h->nrhs * h->mesh->m.ncells * h->nrt;
   if (memspace == EQLB_MEM_DEVICE)
   {
-    if (h->bvals)
-      HIP_TRY(hipMemcpyAsync(out, h->bvals, bytes, hipMemcpyDeviceToDevice, stream));
+    if (h->bt.bvals)
+      HIP_TRY(hipMemcpyAsync(out, h->bt.bvals, bytes, hipMemcpyDeviceToDevice, stream));
     else
       HIP_TRY(hipMemsetAsync(out, 0, bytes, stream));
     return EQLB_OK;
   }
-  if (!h->bvals)
+  if (!h->bt.bvals)
   {
     std::memset(out, 0, bytes);
     return EQLB_OK;
   }
-  HIP_TRY(hipMemcpyAsync(out, h->bvals, bytes, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(out, h->bt.bvals, bytes, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return EQLB_OK;
 }

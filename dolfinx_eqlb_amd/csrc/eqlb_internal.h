@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/eqlb.h"
+#include "eqlb_bins.h" // MAX_BINS, BIN_P, Bin, WS_MAX_LEVELS: shared with the planner of the set-up
 
 namespace eqlb
 {
@@ -33,13 +34,9 @@ constexpr uint8_t PFLAG_WS_SKIP = 8, PFLAG_WS_GROUP = 16;
 // level of the patch's group among overlapping groups (bits 5, 6 of the flag of RHS 0): the weak-symmetry kernel
 // runs once per level, se/reconstruction.hpp:170-234 treats the groups one after the other
 constexpr uint8_t PFLAG_WS_LEVEL_SHIFT = 5;
-constexpr int WS_MAX_LEVELS = 4;
 // slot_info bits 8-10 (plain SoA): local vertex v of the cell belongs to a two-cell patch of the
 // lane's group -> its slot row is added to the stress coefficients (bit 8 + v)
 constexpr uint32_t INFO_GROUPROW_SHIFT = 8;
-
-constexpr int MAX_BINS = 5;          // lanes per patch P = 4, 8, 16, 32, 64
-constexpr int BIN_P[MAX_BINS] = {4, 8, 16, 32, 64};
 
 struct DeviceMesh
 {
@@ -58,16 +55,6 @@ struct DeviceMesh
   std::vector<int32_t> h_facet_cells_off; // offsets of the facet -> cell table (1 or 2 cells per facet)
   std::vector<int32_t> h_facet_nodes, h_node_facets_off, h_node_facets, h_node_cells_off, h_node_cells;
   std::vector<double> h_x;
-};
-
-struct Bin
-{
-  int P = 0;
-  int64_t npatch = 0;
-  int64_t slot_offset = 0;   // into slot arrays
-  int64_t patch_offset = 0;  // into patch arrays
-  int64_t nfull = 0;         // fused stress tiles: the leading patches of the bin are the FULL ones (interior, as many
-                             // cells as lanes) that the fused kernel takes; the slot path takes [nfull, npatch)
 };
 
 // kernel arguments of the patch kernel (one launch per bin)
@@ -366,115 +353,4 @@ struct eqlb_mesh
   std::map<int, std::vector<int32_t>> tiling_order;
 };
 
-struct eqlb_ev
-{
-  struct eqlb_se* se = nullptr; // patch topology, tables, slots, timing of the shared machinery
-};
-
-struct eqlb_se
-{
-  eqlb_mesh* mesh = nullptr;
-  int k = 0, deg = 0, nrhs = 0, stress = 0;
-  int nrt = 0, nd = 0;
-  int solver = EQLB_SOLVER_SHUFFLE, scatter = EQLB_SCATTER_AUTO, timing = 0, fused = 1;
-  int accumulate = 1;               // option "accumulate": 0 stores the result instead of adding it
-  int multi_rhs = 1;                // option "multi_rhs": all right-hand sides of a tiled call in one launch
-  int scatter_last = EQLB_SCATTER_SLOTS; // scatter mode the last equilibrate call resolved to
-  int mode = 0;                     // 1: constrained-minimisation (EV) patch problems
-  int ev_output = 0;                // EV: 0 conforming DOFs, 1 broken hierarchic RT_k layout
-  int tile_cells_user = 0;          // option "tile_cells": cells per tile of the tiled launch (0 = automatic)
-  int ev_bv_hier = 0;               // EV: boundary values in the hierarchic basis although a basis transform is set
-  int32_t* ev_cell_dofs = nullptr;  // EV: device copy of the caller's dofmap or nullptr (default)
-  int64_t ev_ndofs = 0;             // EV: number of conforming flux DOFs
-  double* ev_basis = nullptr;       // EV: device copy of [C (nrt x nrt) | R (k x k) | facet maps 3 x 2 x k x k] or nullptr
-  bool ev_basis_has_R = false;
-  bool stress_flux_bcs = true;       // some facet of stress row 0 / 1 carries a flux BC
-  bool boundary_set = false;
-  int64_t npatch_total = 0, nslots = 0;
-  eqlb::Bin bins[eqlb::MAX_BINS];
-  // device
-  double* tables = nullptr;
-  int8_t* facet_type = nullptr;     // [nrhs][nfacets]
-  int8_t* node_ws = nullptr;        // grouped stress patches (stress && k == 2 && groups exist)
-  int32_t* node_group = nullptr;
-  int8_t* node_wslevel = nullptr;   // level of the node's group among overlapping groups
-  int ws_levels = 1;                // passes of the weak-symmetry kernel
-  double* bvals = nullptr;          // [nrhs][ncells*nrt] global boundary DOFs (nullptr: homogeneous)
-  int64_t* node_slot = nullptr;     // [nnodes] first slot of the node's patch or -1
-  int64_t* node_patch = nullptr;    // [nnodes] patch index or -1
-  int32_t* node_P = nullptr;        // [nnodes] lanes per patch
-  int32_t* slot_cell = nullptr;
-  uint32_t* slot_info = nullptr;
-  uint8_t* pn = nullptr;
-  uint8_t* pflag = nullptr;
-  // tiled SoA (plain SE, EQLB_SCATTER_TILED)
-  int32_t ntiles = 0, tile_tc = 0;
-  bool t_stress = false;            // the tiles serve the fused stress launch (bins P <= 8 only)
-  int64_t t_rest = 0;               // patches left to the generic kernels when t_stress (everything but full patches)
-  hipStream_t side_stream = nullptr; // the rest's patch kernels run here, next to the fused kernel
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int32_t* rest_cells = nullptr;    // cells with a vertex whose patch runs on the generic kernels (compact reduction)
-  int64_t nrest_cells = 0;
-  int64_t t_nslots = 0, t_npatch = 0;
-  eqlb::TileDesc* t_tiles = nullptr;
-  int32_t *t_tile_cells = nullptr, *t_slot_cell = nullptr, *t_facet_owner = nullptr;
-  uint32_t* t_slot_info = nullptr;
-  uint8_t *t_pn = nullptr, *t_pflag = nullptr;
-  // fused stress launch: the tiles list EVERY patch of the bins 0, 1 (full ones first), not the full ones only - where
-  // the others are more than a few per cent of the patches (unstructured meshes); kernel with both instances
-  bool t_mixed = false;
-  int64_t t_blocks[EQLB_TB_COUNT] = {}; // wave-blocks per bin and body instance of the tiled kernel (eqlb_se_tiling_blocks)
-  // two-phase sweeps (multi-GPU overlap): tiles owning a priority cell are numbered first
-  std::vector<int32_t> prio_cells;
-  int32_t t_nprio = 0;              // number of priority tiles
-  int32_t tile_first = 0, tile_count = -1; // options "tile_first" / "tile_count" (-1: to the end)
-  // patches of more than 63 cells or more than 64 facets (option "large_patches"): a CSR-style SoA of their own,
-  // outside the five lanes-per-patch bins; k_se_patch_large writes their rows into the slot buffer
-  int large_patches = 0;            // option "large_patches"
-  int64_t l_npatch = 0, l_nslots = 0;
-  int32_t l_maxcells = 0;
-  int32_t* l_off = nullptr;         // [l_npatch + 1] first lane slot of the patch
-  int32_t* l_slot_cell = nullptr;   // [l_nslots]
-  uint32_t* l_slot_info = nullptr;  // [l_nslots]
-  uint8_t* l_pflag = nullptr;       // [nrhs][l_npatch]
-  int32_t* l_cells = nullptr;       // cells with a vertex whose patch is a large one (compact reduction)
-  int64_t l_ncells = 0;
-  double* l_ws = nullptr;           // work space of k_se_patch_large
-  // option "large_patches_stress": weak symmetry and Korn constants on the large patches as well
-  int large_patches_stress = 0;
-  bool l_stress = false;            // value of the option at the last eqlb_se_set_boundary (with "large_patches" = 1)
-  int32_t* l_nodes = nullptr;       // [l_npatch] patch nodes (Korn constants)
-  int64_t* l_wsym_off = nullptr;    // [l_npatch] first double of the patch in l_wsym_ws (stress handles)
-  double* l_wsym_ws = nullptr;      // work space of k_se_weaksym_large
-  int32_t* l_rest_cells = nullptr;  // fused stress launch: rest_cells and l_cells merged (one compact reduction)
-  int64_t l_nrest_cells = 0;
-  double* slots = nullptr;          // [nrhs][ncells][3][nrt]
-  int slots_first_bin = 0;          // the slot rows of the bins >= this one hold values of the last slot-path run
-  int32_t* status = nullptr;
-  // staging for host-memory calls
-  double *d_flux_dg = nullptr, *d_rhs_dg = nullptr, *d_flux_hdiv = nullptr;
-  double *d_cks = nullptr, *d_korn = nullptr; // Korn estimate: per node / staging per cell
-  // timing ("timing" option): ring of event sets, one set per equilibrate call.  A set holds a begin and an end event
-  // per timing slot; the slots are the `which` of eqlb_se_last_kernel_ms
-  enum EvSlot
-  {
-    EV_BIN0 = 0,                // patch kernel of bin b: EV_BIN0 + b (a launch of all bins at once: EV_BIN0)
-    EV_REDUCE = eqlb::MAX_BINS, // slot reduction
-    EV_WEAKSYM,                 // weak-symmetry kernels
-    EV_LARGE,                   // large-patch kernel
-    EV_NSLOTS
-  };
-  static constexpr int ev_begin(int slot) { return 2 * slot; }
-  static constexpr int ev_end(int slot) { return 2 * slot + 1; }
-  static constexpr int EV_RING = 64, EV_PER_SET = 2 * EV_NSLOTS;
-  hipEvent_t* ev = nullptr; // [EV_RING][EV_PER_SET]
-  int64_t ev_calls = 0;     // calls recorded since timing was (re)enabled
-};
-
-namespace eqlb
-{
-// host side of the tiling (eqlb_tiling_host.hip): the tiled SoA of the handle from the bins of its nodes.  Nodes of
-// bins >= max_bin are left to another path; full_only: so are all patches that are not full
-int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, BuildArgs a, int tc_fixed = 0,
-                int max_bin = MAX_BINS, bool full_only = false);
-} // namespace eqlb
+struct eqlb_se; // the handle behind eqlb_se_t / eqlb_ev_t: eqlb_handle.h (host code only)

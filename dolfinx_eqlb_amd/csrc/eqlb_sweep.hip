@@ -1,7 +1,7 @@
 // The equilibration sweep behind eqlb_se_equilibrate*: resolves the scatter mode of a call, stages host data, and
 // issues the launches of the tiled, the slot or the atomic route.  Host code only; the kernels and their launchers
 // live in the eqlb_se_*.hip / eqlb_stress_tiled.hip / eqlb_ev.hip files.
-#include "eqlb_host_util.h"
+#include "eqlb_handle.h"
 
 #include <algorithm>
 
@@ -32,28 +32,28 @@ struct Sweep
 int plan_sweep(eqlb_se* h, int& scatter, bool& stress_fused)
 {
   scatter = h->scatter;
-  stress_fused = h->stress && h->t_stress && h->ntiles > 0 && h->solver == EQLB_SOLVER_SHUFFLE
+  stress_fused = h->stress && h->bt.t_stress && h->bt.ntiles > 0 && h->solver == EQLB_SOLVER_SHUFFLE
                  && (scatter == EQLB_SCATTER_AUTO || scatter == EQLB_SCATTER_TILED);
   if (scatter == EQLB_SCATTER_AUTO)
-    scatter = (stress_fused || (!h->stress && h->k <= 3 && h->solver == EQLB_SOLVER_SHUFFLE && h->ntiles > 0))
+    scatter = (stress_fused || (!h->stress && h->k <= 3 && h->solver == EQLB_SOLVER_SHUFFLE && h->bt.ntiles > 0))
                   ? EQLB_SCATTER_TILED
                   : EQLB_SCATTER_SLOTS;
   h->scatter_last = scatter;
   if (!h->accumulate && scatter == EQLB_SCATTER_ATOMIC)
     return fail(EQLB_ERR_UNSUPPORTED, "\"accumulate\" = 0 is not available with the atomic scatter");
-  if (h->l_npatch > 0 && scatter == EQLB_SCATTER_ATOMIC)
+  if (h->bt.l_npatch > 0 && scatter == EQLB_SCATTER_ATOMIC)
     return fail(EQLB_ERR_UNSUPPORTED,
                 "patches of more than 63 cells (\"large_patches\") run with the slot or the tiled scatter, not the atomic one");
   if (h->mode == 1 && (scatter == EQLB_SCATTER_ATOMIC || (h->solver != EQLB_SOLVER_SHUFFLE && h->k != 4)))
     return fail(EQLB_ERR_UNSUPPORTED, "EV equilibration runs with the shuffle solver (tiled or slot scatter)");
   if (scatter == EQLB_SCATTER_TILED)
   {
-    if ((h->stress && !stress_fused) || h->solver != EQLB_SOLVER_SHUFFLE || h->ntiles == 0)
+    if ((h->stress && !stress_fused) || h->solver != EQLB_SOLVER_SHUFFLE || h->bt.ntiles == 0)
       return fail(EQLB_ERR_UNSUPPORTED,
                   "the tiled scatter is available for k <= 3 with the shuffle solver (stress: RT_2 without "
                   "flux boundary conditions on the stress rows)");
-    if (h->tile_first > h->ntiles)
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "tile_first %d beyond the %d tiles", h->tile_first, h->ntiles);
+    if (h->tile_first > h->bt.ntiles)
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "tile_first %d beyond the %d tiles", h->tile_first, h->bt.ntiles);
   }
   if (scatter == EQLB_SCATTER_ATOMIC && h->stress)
     return fail(EQLB_ERR_UNSUPPORTED, "stress equilibration needs the slot or the tiled scatter");
@@ -144,7 +144,7 @@ void select_rhs(const Sweep& s, eqlb::SeArgs& aa, int r, bool to_slots)
   aa.flux_dg = s.d_g[r];
   aa.rhs_dg = s.d_f[r];
   aa.rhs_in = 0;
-  aa.out = to_slots ? s.h->slots : s.d_x[r];
+  aa.out = to_slots ? s.h->bt.slots : s.d_x[r];
   aa.rhs_out = to_slots ? r : 0;
 }
 
@@ -165,9 +165,9 @@ PatchRange all_patches(const eqlb_se* h)
   PatchRange pr;
   for (int b = 0; b < eqlb::MAX_BINS; ++b)
   {
-    pr.npatch[b] = h->bins[b].npatch;
-    pr.slot_offset[b] = h->bins[b].slot_offset;
-    pr.patch_offset[b] = h->bins[b].patch_offset;
+    pr.npatch[b] = h->bt.bins[b].npatch;
+    pr.slot_offset[b] = h->bt.bins[b].slot_offset;
+    pr.patch_offset[b] = h->bt.bins[b].patch_offset;
   }
   return pr;
 }
@@ -179,8 +179,8 @@ PatchRange rest_of_fused_stress(const eqlb_se* h)
   PatchRange pr = all_patches(h);
   for (int b = 0; b < 2; ++b)
   {
-    const eqlb::Bin& bin = h->bins[b];
-    pr.npatch[b] = h->t_mixed ? 0 : bin.npatch - bin.nfull;
+    const eqlb::Bin& bin = h->bt.bins[b];
+    pr.npatch[b] = h->bt.t_mixed ? 0 : bin.npatch - bin.nfull;
     pr.slot_offset[b] += bin.nfull * bin.P;
     pr.patch_offset[b] += bin.nfull;
   }
@@ -200,21 +200,21 @@ int ensure_slots(const Sweep& s, SlotCover cover, hipStream_t st)
 {
   eqlb_se* h = s.h;
   const size_t bytes = (size_t)h->nrhs * s.s_slot * 3 * sizeof(double);
-  if (!h->slots)
+  if (!h->bt.slots)
   {
-    if (upload<double>(&h->slots, nullptr, bytes / sizeof(double)))
+    if (h->bt.slots.alloc(bytes / sizeof(double)))
       return EQLB_ERR_DEVICE;
     // slots of (cell, vertex) pairs whose node is not equilibrated here (node_mask, other path) stay zero
     // (on the stream of the patch kernels: a fill on the null stream is not ordered against the non-blocking side
     // stream of a fused stress launch and could wipe rows its kernels have already written)
-    HIP_TRY(hipMemsetAsync(h->slots, 0, bytes, st));
+    HIP_TRY(hipMemsetAsync(h->bt.slots, 0, bytes, st));
     h->slots_first_bin = eqlb::MAX_BINS;
   }
   // The reduction adds ALL slot rows of a cell.  A run over a part of the patches rewrites only their rows: rows
   // of the others left by an earlier run over more of them (option "scatter" / "solver" changed on this handle)
   // would be added again on top of what the tiled launch wrote
   if (h->slots_first_bin < cover)
-    HIP_TRY(hipMemsetAsync(h->slots, 0, bytes, st));
+    HIP_TRY(hipMemsetAsync(h->bt.slots, 0, bytes, st));
   h->slots_first_bin = cover;
   return EQLB_OK;
 }
@@ -236,7 +236,7 @@ int launch_patches(const Sweep& s, const PatchRange& pr, int scatter, hipStream_
       fb.npatch[b] = pr.npatch[b];
       fb.slot_offset[b] = pr.slot_offset[b];
       fb.patch_offset[b] = pr.patch_offset[b];
-      nb += (pr.npatch[b] * h->bins[b].P + 255) / 256;
+      nb += (pr.npatch[b] * h->bt.bins[b].P + 255) / 256;
     }
     fb.block_start[eqlb::MAX_BINS] = nb;
     for (int r = 0; r < h->nrhs; ++r)
@@ -264,9 +264,9 @@ int launch_patches(const Sweep& s, const PatchRange& pr, int scatter, hipStream_
     for (int r = 0; r < h->nrhs; ++r)
     {
       select_rhs(s, as, r, to_slots);
-      const int st_ = eqlb::launch_se_patch(h->k, h->deg, h->bins[b].P, h->solver, scatter, as, st, mode);
+      const int st_ = eqlb::launch_se_patch(h->k, h->deg, h->bt.bins[b].P, h->solver, scatter, as, st, mode);
       if (st_)
-        return fail(st_, "patch kernel launch failed (k=%d, P=%d)", h->k, h->bins[b].P);
+        return fail(st_, "patch kernel launch failed (k=%d, P=%d)", h->k, h->bt.bins[b].P);
     }
     EQLB_TRY(mark_end(evs, eqlb_se::EV_BIN0 + b, st));
   }
@@ -278,16 +278,16 @@ int launch_large(const Sweep& s, hipStream_t st, hipEvent_t* evs)
 {
   const eqlb_se* h = s.h;
   eqlb::SeArgs al = s.a;
-  al.slot_cell = h->l_slot_cell;
-  al.slot_info = h->l_slot_info;
+  al.slot_cell = h->bt.l_slot_cell;
+  al.slot_info = h->bt.l_slot_info;
   al.pn = nullptr;
-  al.pflag = h->l_pflag;
-  al.npatch_total = h->l_npatch;
+  al.pflag = h->bt.l_pflag;
+  al.npatch_total = h->bt.l_npatch;
   EQLB_TRY(mark_begin(evs, eqlb_se::EV_LARGE, st));
   for (int r = 0; r < h->nrhs; ++r)
   {
     select_rhs(s, al, r, true);
-    const int st_ = eqlb::launch_se_patch_large(h->k, h->deg, h->mode, al, h->l_off, h->l_ws, st);
+    const int st_ = eqlb::launch_se_patch_large(h->k, h->deg, h->mode, al, h->bt.l_off, h->bt.l_ws, st);
     if (st_)
       return fail(st_, "large-patch kernel launch failed (k=%d)", h->k);
   }
@@ -301,16 +301,16 @@ int launch_weaksym_large(const Sweep& s, hipStream_t st, hipEvent_t* evs, bool b
 {
   const eqlb_se* h = s.h;
   eqlb::SeArgs al = s.a;
-  al.slot_cell = h->l_slot_cell;
-  al.slot_info = h->l_slot_info;
+  al.slot_cell = h->bt.l_slot_cell;
+  al.slot_info = h->bt.l_slot_info;
   al.pn = nullptr;
-  al.pflag = h->l_pflag;
-  al.npatch_total = h->l_npatch;
+  al.pflag = h->bt.l_pflag;
+  al.npatch_total = h->bt.l_npatch;
   select_rhs(s, al, 0, true);
   al.tables = h->tables + eqlb::table_offset_te(h->k, h->deg) - eqlb::table_offset_te(h->k, h->k - 1); // as launch_weaksym
   if (begin)
     EQLB_TRY(mark_begin(evs, eqlb_se::EV_WEAKSYM, st));
-  const int st_ = eqlb::launch_se_weaksym_large(h->k, al, h->l_off, h->l_wsym_off, h->l_wsym_ws, st);
+  const int st_ = eqlb::launch_se_weaksym_large(h->k, al, h->bt.l_off, h->bt.l_wsym_off, h->bt.l_wsym_ws, st);
   if (st_)
     return fail(st_, "weak-symmetry kernel launch of the large patches failed (k=%d)", h->k);
   return mark_end(evs, eqlb_se::EV_WEAKSYM, st);
@@ -330,7 +330,7 @@ int launch_weaksym(const Sweep& s, const PatchRange& pr, hipStream_t st, hipEven
   // difference (every read stays inside the buffer; TE ... VQ do not depend on the degree)
   as.tables = h->tables + eqlb::table_offset_te(h->k, h->deg) - eqlb::table_offset_te(h->k, h->k - 1);
   // (overlapping groups of boundary patches: one pass per level, a pass skips the patches of other levels)
-  for (int lv = 0; lv < h->ws_levels; ++lv)
+  for (int lv = 0; lv < h->bt.ws_levels; ++lv)
     for (int b = 0; b < eqlb::MAX_BINS; ++b)
     {
       if (pr.npatch[b] == 0)
@@ -339,9 +339,9 @@ int launch_weaksym(const Sweep& s, const PatchRange& pr, hipStream_t st, hipEven
       as.slot_offset = pr.slot_offset[b];
       as.patch_offset = pr.patch_offset[b];
       as.ws_level = lv;
-      const int st_ = eqlb::launch_se_weaksym(h->k, h->bins[b].P, !h->stress_flux_bcs && h->deg == h->k - 1, as, st);
+      const int st_ = eqlb::launch_se_weaksym(h->k, h->bt.bins[b].P, !h->bt.stress_flux_bcs && h->deg == h->k - 1, as, st);
       if (st_)
-        return fail(st_, "weak-symmetry kernel launch failed (k=%d, P=%d)", h->k, h->bins[b].P);
+        return fail(st_, "weak-symmetry kernel launch failed (k=%d, P=%d)", h->k, h->bt.bins[b].P);
     }
   return mark_end(evs, eqlb_se::EV_WEAKSYM, st);
 }
@@ -357,7 +357,7 @@ int reduce_all(const Sweep& s, hipStream_t st)
   const int nlaunch = contiguous ? 1 : h->nrhs, per = contiguous ? h->nrhs : 1;
   for (int l = 0; l < nlaunch; ++l)
   {
-    const double* sl = h->slots + (size_t)l * s.s_slot * 3;
+    const double* sl = h->bt.slots + (size_t)l * s.s_slot * 3;
     if (s.ev_conf)
       eqlb::launch_ev_reduce(s.m, h->k, per, h->ev_cell_dofs, h->ev_ndofs, sl, s.d_x[l], h->accumulate, h->ev_basis,
                              basis_R(h), st);
@@ -376,7 +376,7 @@ int reduce_cells(const Sweep& s, int64_t nlist, const int32_t* cells, hipStream_
   const eqlb_se* h = s.h;
   for (int r = 0; r < h->nrhs; ++r)
   {
-    const double* sl = h->slots + (size_t)r * s.s_slot * 3;
+    const double* sl = h->bt.slots + (size_t)r * s.s_slot * 3;
     if (s.ev_conf)
       eqlb::launch_ev_reduce(s.m, h->k, 1, h->ev_cell_dofs, h->ev_ndofs, sl, s.d_x[r], 1, h->ev_basis, basis_R(h), st);
     else if (eqlb::launch_reduce_slots_cells(h->nrt, s.m.ncells, nlist, cells, sl, s.d_x[r], st))
@@ -392,11 +392,11 @@ int sweep_slots(const Sweep& s)
   const PatchRange pr = all_patches(h);
   EQLB_TRY(ensure_slots(s, COVER_ALL, s.stream));
   EQLB_TRY(launch_patches(s, pr, EQLB_SCATTER_SLOTS, s.stream, s.evs));
-  if (h->l_npatch > 0)
+  if (h->bt.l_npatch > 0)
     EQLB_TRY(launch_large(s, s.stream, s.evs));
   if (h->stress)
     EQLB_TRY(launch_weaksym(s, pr, s.stream, s.evs));
-  if (h->stress && h->l_npatch > 0)
+  if (h->stress && h->bt.l_npatch > 0)
     EQLB_TRY(launch_weaksym_large(s, s.stream, s.evs, false));
   EQLB_TRY(mark_begin(s.evs, eqlb_se::EV_REDUCE, s.stream));
   EQLB_TRY(reduce_all(s, s.stream));
@@ -448,31 +448,31 @@ int launch_tiled_rhs(const Sweep& s, eqlb::SeArgs& at, const eqlb::TileArgs& ta,
 int sweep_tiled(const Sweep& s)
 {
   eqlb_se* h = s.h;
-  const int32_t tcount = (h->tile_count < 0) ? h->ntiles - h->tile_first
-                                             : std::min(h->tile_count, h->ntiles - h->tile_first);
-  const eqlb::TileArgs ta{h->t_tiles, h->t_tile_cells, tcount, h->tile_tc,
-                          s.ev_conf ? h->t_facet_owner : nullptr, h->ev_cell_dofs, h->ev_ndofs, s.m.nfacets,
+  const int32_t tcount = (h->tile_count < 0) ? h->bt.ntiles - h->tile_first
+                                             : std::min(h->tile_count, h->bt.ntiles - h->tile_first);
+  const eqlb::TileArgs ta{h->bt.t_tiles, h->bt.t_tile_cells, tcount, h->bt.tile_tc,
+                          s.ev_conf ? h->bt.t_facet_owner : nullptr, h->ev_cell_dofs, h->ev_ndofs, s.m.nfacets,
                           h->tile_first, h->accumulate, s.ev_conf ? h->ev_basis : nullptr,
                           s.ev_conf ? basis_R(h) : nullptr};
   eqlb::SeArgs at = s.a;
-  at.slot_cell = h->t_slot_cell;
-  at.slot_info = h->t_slot_info;
-  at.pn = h->t_pn;
-  at.pflag = h->t_pflag;
-  at.npatch_total = h->t_npatch;
+  at.slot_cell = h->bt.t_slot_cell;
+  at.slot_info = h->bt.t_slot_info;
+  at.pn = h->bt.t_pn;
+  at.pflag = h->bt.t_pflag;
+  at.npatch_total = h->bt.t_npatch;
   EQLB_TRY(mark_begin(s.evs, eqlb_se::EV_BIN0, s.stream));
   // What the tiles leave out - the rest of a fused stress launch, the large patches - goes along with the FIRST range
   // of tiles of a two-phase sweep: its patches touch ghost cells like any other, and the caller packs the ghost rows
   // behind that range (option accumulate = 0: the tiled launches STORE, the sums can only be added behind the last of
   // them; an empty range - a rank without priority tiles, or with priority tiles only - takes nothing along)
-  const bool with_first_range = tcount > 0 && (h->accumulate ? h->tile_first == 0 : h->tile_first + tcount == h->ntiles);
+  const bool with_first_range = tcount > 0 && (h->accumulate ? h->tile_first == 0 : h->tile_first + tcount == h->bt.ntiles);
   // The rest of a fused stress launch (boundary patches, interior patches that are not full, bins of more than 8
   // lanes): its patch kernels - a handful of small launches, 50 us back to back at 1M triangles - run on a side
   // stream NEXT TO the fused kernel, untimed; their sums are added behind it
   // The large patches of a stress handle go the same way, behind the rest: flux rows, then their weak symmetry (both
   // timed: the slots of the large-patch kernel and of the weak-symmetry kernels)
-  const bool large_now = h->l_npatch > 0 && with_first_range;
-  const bool rest_now = s.stress_fused && with_first_range && (h->t_rest > 0 || large_now);
+  const bool large_now = h->bt.l_npatch > 0 && with_first_range;
+  const bool rest_now = s.stress_fused && with_first_range && (h->bt.t_rest > 0 || large_now);
   if (rest_now)
   {
     if (!h->side_stream)
@@ -485,7 +485,7 @@ int sweep_tiled(const Sweep& s)
     HIP_TRY(hipEventRecord(h->ev_fork, s.stream));
     HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
     EQLB_TRY(ensure_slots(s, COVER_REST, h->side_stream));
-    if (h->t_rest > 0)
+    if (h->bt.t_rest > 0)
     {
       EQLB_TRY(launch_patches(s, rest, EQLB_SCATTER_SLOTS, h->side_stream, nullptr));
       EQLB_TRY(launch_weaksym(s, rest, h->side_stream, nullptr));
@@ -502,7 +502,7 @@ int sweep_tiled(const Sweep& s)
   {
     // rows 0, 1 of the stress and their weak symmetry in one launch
     select_rhs(s, at, 0, false);
-    const int st = eqlb::launch_se_stress_tiled(at, ta, s.d_g, s.d_f, s.d_x, s.stream, h->t_mixed);
+    const int st = eqlb::launch_se_stress_tiled(at, ta, s.d_g, s.d_f, s.d_x, s.stream, h->bt.t_mixed);
     if (st)
       return fail(st, "fused stress kernel launch failed");
     r0 = 2;
@@ -516,16 +516,16 @@ int sweep_tiled(const Sweep& s)
     // compact reduction over the cells of those patches ADDS them behind the tiles
     EQLB_TRY(ensure_slots(s, COVER_LARGE, s.stream));
     EQLB_TRY(launch_large(s, s.stream, s.evs));
-    EQLB_TRY(reduce_cells(s, h->l_ncells, h->l_cells, s.stream));
+    EQLB_TRY(reduce_cells(s, h->bt.l_ncells, h->bt.l_cells, s.stream));
   }
   if (rest_now)
   {
     // only the cells that a patch of the generic kernels touches
     HIP_TRY(hipStreamWaitEvent(s.stream, h->ev_join, 0));
     if (large_now)
-      EQLB_TRY(reduce_cells(s, h->l_nrest_cells, h->l_rest_cells, s.stream));
+      EQLB_TRY(reduce_cells(s, h->bt.l_nrest_cells, h->bt.l_rest_cells, s.stream));
     else
-      EQLB_TRY(reduce_cells(s, h->nrest_cells, h->rest_cells, s.stream));
+      EQLB_TRY(reduce_cells(s, h->bt.nrest_cells, h->bt.rest_cells, s.stream));
   }
   return EQLB_OK;
 }
@@ -539,7 +539,7 @@ int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const double* con
   for (int r = 0; r < h->nrhs; ++r)
     if (!g_in[r] || !f_in[r] || !x_io[r])
       return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  if (!h->boundary_set)
+  if (!h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_equilibrate: boundary data not set");
   const eqlb::DeviceMesh& m = h->mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -565,14 +565,14 @@ int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const double* con
 
   eqlb::SeArgs a{};
   a.cellJ = m.cellJ;
-  a.slot_cell = h->slot_cell;
-  a.slot_info = h->slot_info;
-  a.pn = h->pn;
-  a.pflag = h->pflag;
+  a.slot_cell = h->bt.slot_cell;
+  a.slot_info = h->bt.slot_info;
+  a.pn = h->bt.pn;
+  a.pflag = h->bt.pflag;
   a.tables = h->tables;
-  a.bvals = h->bvals;
+  a.bvals = h->bt.bvals;
   a.status = h->status;
-  a.npatch_total = h->npatch_total;
+  a.npatch_total = h->bt.npatch_total;
   a.ncells = m.ncells;
   a.nrhs = h->nrhs;
   const Sweep s{h, m, stream, scatter, stress_fused, ev_conf, s_g, s_f, s_slot, s_x, d_g.data(), d_f.data(), d_x.data(),
@@ -679,11 +679,11 @@ double eqlb_se_last_kernel_ms(const eqlb_se_t* h, int32_t which)
     return 0.0;
   if (which == eqlb_se::EV_WEAKSYM && !h->stress)
     return 0.0;
-  if (which == eqlb_se::EV_LARGE && (h->l_npatch == 0 || h->scatter_last == EQLB_SCATTER_ATOMIC))
+  if (which == eqlb_se::EV_LARGE && (h->bt.l_npatch == 0 || h->scatter_last == EQLB_SCATTER_ATOMIC))
     return 0.0; // the large-patch kernel (all right-hand sides of a call)
   const bool fused_run = (h->mode == 1 && h->k <= 3) || h->scatter_last == EQLB_SCATTER_TILED
                          || (h->fused && h->solver == EQLB_SOLVER_SHUFFLE && h->k <= 3);
-  if (which < eqlb::MAX_BINS && ((fused_run && which != 0) || (!fused_run && h->bins[which].npatch == 0)))
+  if (which < eqlb::MAX_BINS && ((fused_run && which != 0) || (!fused_run && h->bt.bins[which].npatch == 0)))
     return 0.0;
   if (which == eqlb_se::EV_REDUCE && h->scatter_last != EQLB_SCATTER_SLOTS)
     return 0.0;

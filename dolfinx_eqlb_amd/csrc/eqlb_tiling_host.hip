@@ -1,7 +1,8 @@
 // Tiles of the tiled launch (EQLB_SCATTER_TILED) on the host: recursive coordinate bisection of the cell centroids
-// (rcb_split) and the tiled patch SoA built from it (build_tiles, called by eqlb_se_set_boundary).  Host code only;
-// the device bisection it tries first is eqlb_tiling_device.hip.
-#include "eqlb_host_util.h"
+// (rcb_split) and the tiled patch SoA planned from it (plan_tiles, called by eqlb_se_set_boundary before the handle
+// changes; eqlb_boundary_setup.hip uploads the plan).  Host code only; the device bisection it tries first is
+// eqlb_tiling_device.hip.
+#include "eqlb_handle.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,32 +40,10 @@ static inline bool rcb_less(const TileItem& p, const TileItem& q, int axis)
   return u < v || (u == v && p.cell < q.cell);
 }
 
-// std::vector without value initialisation: the big scratch arrays of the tile builder are written completely by the
-// worker threads - a zero fill by the calling thread would touch (page-fault) tens of MB serially first
-template <typename T>
-struct default_init_alloc : std::allocator<T>
-{
-  template <typename U>
-  struct rebind
-  {
-    using other = default_init_alloc<U>;
-  };
-  template <typename U, typename... A>
-  void construct(U* p, A&&... a)
-  {
-    if constexpr (sizeof...(A) == 0)
-      ::new (static_cast<void*>(p)) U;
-    else
-      ::new (static_cast<void*>(p)) U(std::forward<A>(a)...);
-  }
-};
-template <typename T>
-using uvec = std::vector<T, default_init_alloc<T>>;
-
 // Host worker threads of the set-up: capped (the tile builder keeps an O(nnodes) stamp per worker: 16 MB each at
 // 4M nodes, on every rank of a node) and exception safe - an exception inside a std::thread would call
 // std::terminate; the first one is kept and re-thrown by join() in the calling thread, where the C entry points
-// turn it into an error code (EQLB_GUARD).
+// turn it into an error code (EQLB_CATCH_ALL).
 static int host_workers(int64_t wanted)
 {
   const int64_t hw = std::max<int64_t>(1, std::min<int64_t>(std::thread::hardware_concurrency(), 32));
@@ -340,14 +319,12 @@ void parallel_for(int64_t n, int64_t min_chunk, F f)
   w.join();
 }
 
-// Wave-blocks per bin and body instance that the tiled kernel of this handle runs over all tiles (eqlb_se_tiling_blocks):
-// the split of a tile's list by k_se_stress_tiled (h->t_stress; full_only: lists of full patches, padded) or
-// k_se_patch_tiled*, through the range functions the kernels call (eqlb_internal.h)
-void count_tile_blocks(eqlb_se* h, const std::vector<eqlb::TileDesc>& tiles, bool full_only)
+// Wave-blocks per bin and body instance that the tiled kernel runs over all tiles (eqlb_se_tiling_blocks): the split of
+// a tile's list by k_se_stress_tiled (t_stress; full_only: lists of full patches, padded) or k_se_patch_tiled*,
+// through the range functions the kernels call (eqlb_internal.h)
+void count_tile_blocks(int K, bool t_stress, bool full_only, const std::vector<eqlb::TileDesc>& tiles, int64_t* out)
 {
-  int64_t* out = h->t_blocks;
   std::fill(out, out + EQLB_TB_COUNT, int64_t(0));
-  const int K = h->k;
   for (const eqlb::TileDesc& td : tiles)
   {
     out[EQLB_TB_ZERO_TILES] += td.zero ? 1 : 0;
@@ -355,7 +332,7 @@ void count_tile_blocks(eqlb_se* h, const std::vector<eqlb::TileDesc>& tiles, boo
     {
       const int P = eqlb::BIN_P[b];
       int64_t* o = out + EQLB_TB_PER_BIN * b;
-      if (h->t_stress)
+      if (t_stress)
       {
         if (b >= 2)
           continue; // the fused kernel takes the bins 0, 1
@@ -392,108 +369,23 @@ void count_tile_blocks(eqlb_se* h, const std::vector<eqlb::TileDesc>& tiles, boo
     }
   }
 }
-} // namespace
 
-namespace eqlb
+// The cells in the order of the tile bisection, chunks of tc cells with ascending ids inside a chunk: from the cache of
+// the mesh, else by the bisection on the device (one radix sort per level of the tree; eqlb_tiling_device.hip) or,
+// where the mesh has stretched cells or is small, on the host threads - and then kept in the cache
+int bisect_cells(eqlb_mesh* mesh, int tc, int32_t ntiles, SetupTimer& tm, eqlb::uvec<int32_t>& cells)
 {
-// Tiled SoA of the plain flux equilibration (EQLB_SCATTER_TILED): cells bisected recursively by
-// their centroids into tiles of TC cells; a tile lists every (masked-in) node of its cells.
-int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::BuildArgs a, int tc_fixed, int max_bin,
-                bool full_only)
-{
-  // nodes of bins >= max_bin are left out (like masked-out nodes): another path equilibrates them.
-  // full_only (fused stress launch on the crossed benchmark meshes): so are all patches that are not FULL (interior,
-  // as many cells as lanes); the lists of a tile are padded to whole wave-blocks with copies of a full patch that
-  // own no cell
-  const eqlb::DeviceMesh& m = h->mesh->m;
+  const eqlb::DeviceMesh& m = mesh->m;
   const int32_t nc = m.ncells;
-  std::vector<int8_t> node_bin(node_bin_all);
-  std::vector<uint8_t> is_rest(max_bin < eqlb::MAX_BINS ? m.nnodes : 0, 0);
-  h->t_rest = 0;
-  for (int32_t i = 0; i < m.nnodes; ++i)
   {
-    int8_t& b = node_bin[i];
-    if (b < 0)
-      continue;
-    const bool full = m.h_node_ncells[i] == m.h_node_nfcts[i] && m.h_node_ncells[i] == eqlb::BIN_P[b];
-    if (b >= max_bin || (full_only && !full))
+    std::lock_guard<std::mutex> g(mesh->tiling_mutex);
+    auto it = mesh->tiling_order.find(tc);
+    if (it != mesh->tiling_order.end() && (int32_t)it->second.size() == nc)
     {
-      b = -1;
-      ++h->t_rest;
-      if (!is_rest.empty())
-        is_rest[i] = 1;
+      cells.assign(it->second.begin(), it->second.end());
+      return EQLB_OK;
     }
   }
-  dfree(h->rest_cells);
-  h->nrest_cells = 0;
-  if (!is_rest.empty() && h->t_rest > 0)
-  {
-    // cells with a vertex whose patch the generic kernels take: the compact reduction of their slot rows
-    std::vector<int32_t> rc;
-    for (int32_t c = 0; c < nc; ++c)
-      for (int j = 0; j < 3; ++j)
-      {
-        const int32_t nd = m.h_cell_nodes[3 * (size_t)c + j];
-        if (is_rest[nd])
-        {
-          rc.push_back(c);
-          break;
-        }
-      }
-    h->nrest_cells = (int64_t)rc.size();
-    if (upload(&h->rest_cells, rc.data(), std::max<size_t>(rc.size(), 1)))
-      return EQLB_ERR_DEVICE;
-  }
-  // Tile size: the default, or - on meshes that fill the chip several times over - the size that
-  // makes the tiles fill whole rounds of the 512 workgroup slots (2 per CU): 1M triangles in 2 045
-  // tiles of 489 cells run in 4 rounds, 2 084 tiles of 480 cells leave 36 tiles for a fifth
-  int TC = tc_fixed > 0 ? tc_fixed : eqlb::tile_cells_of(h->k);
-  if (tc_fixed > 0)
-  {
-    // fused stress launch (tc_fixed = the largest tile its LDS holds): ONE workgroup per CU, so a partial last
-    // round of the 256 slots costs a full round - fit the tile size to whole rounds as below
-    const int64_t slots = 256, tcmax = tc_fixed;
-    TC = (int)std::min<int64_t>(tcmax, 448);
-    if ((int64_t)nc >= slots * 256)
-    {
-      const int64_t rounds = ((int64_t)nc + slots * tcmax - 1) / (slots * tcmax);
-      TC = (int)(((int64_t)nc + rounds * slots - 1) / (rounds * slots));
-    }
-    if (h->tile_cells_user > 0)
-      TC = (int)std::min<int64_t>(h->tile_cells_user, tcmax);
-  }
-  if (tc_fixed <= 0)
-  {
-    // resident workgroup slots of the chip: two per CU for k <= 2, one for k = 3
-    const bool ev3 = h->mode == 1 && h->k >= 3; // EV mode of RT_3 stages 7 KB more tensors: smaller tiles
-    const int64_t slots = (h->k <= 2) ? 512 : 256, tcmax = ev3 ? eqlb::tile_cells_ev_of(h->k) : eqlb::tile_cells_max_of(h->k);
-    if (ev3)
-      TC = eqlb::tile_cells_ev_of(h->k);
-    if ((int64_t)nc >= slots * 256)
-    {
-      const int64_t rounds = ((int64_t)nc + slots * tcmax - 1) / (slots * tcmax);
-      TC = (int)(((int64_t)nc + rounds * slots - 1) / (rounds * slots));
-    }
-    if (h->tile_cells_user > 0) // tuning knob (option "tile_cells"), capped by what the LDS of a workgroup holds
-      TC = (int)std::min<int64_t>(h->tile_cells_user, tcmax);
-  }
-  SetupTimer tm;
-  uvec<TileItem> items(nc);
-  const int32_t ntiles = (nc + TC - 1) / TC;
-  bool cached = false;
-  {
-    std::lock_guard<std::mutex> g(h->mesh->tiling_mutex);
-    auto it = h->mesh->tiling_order.find(TC);
-    if (it != h->mesh->tiling_order.end() && (int32_t)it->second.size() == nc)
-    {
-      for (int32_t p = 0; p < nc; ++p)
-        items[p] = {0.0f, 0.0f, it->second[p]};
-      cached = true;
-    }
-  }
-  if (!cached)
-  {
-  std::vector<uint8_t> stretched(nc);
   // bounding box of the nodes: the centroids are stored relative to it (one scale for both directions)
   double blo[2] = {1e300, 1e300}, bhi[2] = {-1e300, -1e300};
   for (int32_t i = 0; i < m.nnodes; ++i)
@@ -504,125 +396,134 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
     }
   const double ext = std::max(bhi[0] - blo[0], bhi[1] - blo[1]);
   const double inv = (ext > 0.0) ? 1.0 / (3.0 * ext) : 0.0;
-  // the bisection on the device (one radix sort per level of the tree; eqlb_tiling_device.hip) unless the mesh
-  // has stretched cells, where the host bisection below picks the cuts of the last levels by their cost
-  bool on_device = false;
+  std::vector<int32_t> ord;
+  const char* env = getenv("EQLB_TILING");
+  int on_host = 1;
+  if (!(env && !strcmp(env, "host")) && nc >= 4096)
   {
-    const char* env = getenv("EQLB_TILING");
-    if (!(env && !strcmp(env, "host")) && nc >= 4096)
-    {
-      std::vector<int32_t> dord;
-      const int r = eqlb::device_tile_order(m, TC, ntiles, blo, bhi, inv, dord);
-      if (r < 0)
-        return fail(EQLB_ERR_DEVICE, "tiling on the device failed");
-      if (r == 0)
+    on_host = eqlb::device_tile_order(m, tc, ntiles, blo, bhi, inv, ord); // 1: stretched mesh
+    if (on_host < 0)
+      return fail(EQLB_ERR_DEVICE, "tiling on the device failed");
+    if (!on_host)
+      tm.lap("tiles: bisection (device)");
+  }
+  if (on_host)
+  {
+    eqlb::uvec<TileItem> items(nc);
+    std::vector<uint8_t> stretched(nc);
+    parallel_for(nc, 1 << 16, [&](int64_t c) {
+      const int32_t* cn = &m.h_cell_nodes[3 * (size_t)c];
+      double cx = 0.0, cy = 0.0;
+      for (int j = 0; j < 3; ++j)
       {
-        for (int32_t p = 0; p < nc; ++p)
-          items[p] = {0.0f, 0.0f, dord[p]};
-        on_device = true;
-        tm.lap("tiles: bisection (device)");
+        cx += m.h_x[3 * (size_t)cn[j]] - blo[0];
+        cy += m.h_x[3 * (size_t)cn[j] + 1] - blo[1];
       }
-    }
+      items[c] = {(float)(cx * inv), (float)(cy * inv), (int32_t)c};
+      const double* p0 = &m.h_x[3 * (size_t)cn[0]];
+      const double* p1 = &m.h_x[3 * (size_t)cn[1]];
+      const double* p2 = &m.h_x[3 * (size_t)cn[2]];
+      const double e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e2x = p2[0] - p0[0], e2y = p2[1] - p0[1];
+      const double l2 = std::max(std::max(e1x * e1x + e1y * e1y, e2x * e2x + e2y * e2y),
+                                 (e2x - e1x) * (e2x - e1x) + (e2y - e1y) * (e2y - e1y));
+      stretched[c] = l2 > 6.0 * std::fabs(e1x * e2y - e1y * e2x) ? 1 : 0;
+    });
+    RcbPool pool{m.h_cell_nodes.data(), m.nnodes, stretched.data(), {}, {}};
+    tm.lap("tiles: centroids");
+    rcb_split(items.data(), nc, ntiles, tc, pool, nullptr, 0);
+    tm.lap("tiles: bisection");
+    // ascending cell ids inside a tile: the flush of a tile then touches flux_hdiv in long runs
+    parallel_for(ntiles, 16, [&](int64_t t) {
+      std::sort(items.begin() + (size_t)t * tc, items.begin() + std::min<size_t>((size_t)(t + 1) * tc, nc),
+                [](const TileItem& p, const TileItem& q) { return p.cell < q.cell; });
+    });
+    ord.resize(nc);
+    for (int32_t p = 0; p < nc; ++p)
+      ord[p] = items[p].cell;
   }
-  if (!on_device)
-  {
-  parallel_for(nc, 1 << 16, [&](int64_t c) {
-    const int32_t* cn = &m.h_cell_nodes[3 * (size_t)c];
-    double cx = 0.0, cy = 0.0;
-    for (int j = 0; j < 3; ++j)
-    {
-      cx += m.h_x[3 * (size_t)cn[j]] - blo[0];
-      cy += m.h_x[3 * (size_t)cn[j] + 1] - blo[1];
-    }
-    items[c] = {(float)(cx * inv), (float)(cy * inv), (int32_t)c};
-    const double* p0 = &m.h_x[3 * (size_t)cn[0]];
-    const double* p1 = &m.h_x[3 * (size_t)cn[1]];
-    const double* p2 = &m.h_x[3 * (size_t)cn[2]];
-    const double e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e2x = p2[0] - p0[0], e2y = p2[1] - p0[1];
-    const double l2 = std::max(std::max(e1x * e1x + e1y * e1y, e2x * e2x + e2y * e2y),
-                               (e2x - e1x) * (e2x - e1x) + (e2y - e1y) * (e2y - e1y));
-    stretched[c] = l2 > 6.0 * std::fabs(e1x * e2y - e1y * e2x) ? 1 : 0;
-  });
-  RcbPool pool{m.h_cell_nodes.data(), m.nnodes, stretched.data(), {}, {}};
-  tm.lap("tiles: centroids");
-  rcb_split(items.data(), nc, ntiles, TC, pool, nullptr, 0);
-  tm.lap("tiles: bisection");
-  // ascending cell ids inside a tile: the flush of a tile then touches flux_hdiv in long runs
-  parallel_for(ntiles, 16, [&](int64_t t) {
-    std::sort(items.begin() + (size_t)t * TC, items.begin() + std::min<size_t>((size_t)(t + 1) * TC, nc),
-              [](const TileItem& p, const TileItem& q) { return p.cell < q.cell; });
-  });
-  }
-  std::vector<int32_t> ord(nc);
-  for (int32_t p = 0; p < nc; ++p)
-    ord[p] = items[p].cell;
-  std::lock_guard<std::mutex> g(h->mesh->tiling_mutex);
-  h->mesh->tiling_order[TC] = std::move(ord);
-  }
-  // tiles that own a priority cell (ghost rows a neighbour rank waits for) are numbered first: a
-  // first launch over them, the halo exchange, and the launch over the rest then overlap
+  cells.assign(ord.begin(), ord.end());
+  std::lock_guard<std::mutex> g(mesh->tiling_mutex);
+  mesh->tiling_order[tc] = std::move(ord);
+  return EQLB_OK;
+}
+
+// Tiles that own a priority cell (ghost rows a neighbour rank waits for) are numbered first: a first launch over them,
+// the halo exchange, and the launch over the rest then overlap.  Fills the cell tables of the tiles in that numbering.
+void number_tiles(const std::vector<int32_t>& prio_cells, int32_t nc, const eqlb::uvec<int32_t>& cells,
+                  eqlb::TilePlan& tp)
+{
+  const int32_t ntiles = tp.ntiles, TC = tp.tc;
   std::vector<int32_t> order(ntiles);
+  std::vector<uint8_t> tile_prio(ntiles, 0);
+  if (!prio_cells.empty())
   {
-    std::vector<uint8_t> tile_prio(ntiles, 0);
-    if (!h->prio_cells.empty())
-    {
-      std::vector<uint8_t> is_prio(nc, 0);
-      for (int32_t c : h->prio_cells)
-        if (c >= 0 && c < nc)
-          is_prio[c] = 1;
-      for (int32_t p = 0; p < nc; ++p)
-        if (is_prio[items[p].cell])
-          tile_prio[p / TC] = 1;
-    }
-    int32_t np = 0;
-    for (int32_t t = 0; t < ntiles; ++t)
-      if (tile_prio[t])
-        order[np++] = t;
-    h->t_nprio = np;
-    for (int32_t t = 0; t < ntiles; ++t)
-      if (!tile_prio[t])
-        order[np++] = t;
+    std::vector<uint8_t> is_prio(nc, 0);
+    for (int32_t c : prio_cells)
+      if (c >= 0 && c < nc)
+        is_prio[c] = 1;
+    for (int32_t p = 0; p < nc; ++p)
+      if (is_prio[cells[p]])
+        tile_prio[p / TC] = 1;
   }
-  tm.lap("tiles: sort + priority");
-  uvec<int32_t> tile_cells((size_t)ntiles * TC), cell_tile(nc), cell_pos(nc);
+  int32_t np = 0;
+  for (int32_t t = 0; t < ntiles; ++t)
+    if (tile_prio[t])
+      order[np++] = t;
+  tp.nprio = np;
+  for (int32_t t = 0; t < ntiles; ++t)
+    if (!tile_prio[t])
+      order[np++] = t;
+  tp.tile_cells.resize((size_t)ntiles * TC);
+  tp.cell_tile.resize(nc);
+  tp.cell_pos.resize(nc);
   parallel_for(ntiles, 16, [&](int64_t t) {
     const int64_t src = (int64_t)order[t] * TC, len = std::min<int64_t>(TC, nc - src);
     for (int64_t q = 0; q < len; ++q)
     {
-      const int32_t c = items[src + q].cell;
-      tile_cells[(size_t)t * TC + q] = c;
-      cell_tile[c] = (int32_t)t;
-      cell_pos[c] = (int32_t)((int64_t)t * TC + q);
+      const int32_t c = cells[src + q];
+      tp.tile_cells[(size_t)t * TC + q] = c;
+      tp.cell_tile[c] = (int32_t)t;
+      tp.cell_pos[c] = (int32_t)((int64_t)t * TC + q);
     }
     for (int64_t q = len; q < TC; ++q)
-      tile_cells[(size_t)t * TC + q] = -1;
+      tp.tile_cells[(size_t)t * TC + q] = -1;
   });
-  std::vector<eqlb::TileDesc> tiles(ntiles);
-  // pass 1 (host threads, a chunk of tiles each): the nodes of every tile by bin - full interior patches
-  // (as many cells as lanes, no boundary facet: their wave-blocks run the specialised body of the kernel)
-  // first -, in order of first appearance; flat storage, 3 TC entries per tile
-  constexpr int NB = eqlb::MAX_BINS;
-  uvec<int32_t> tnodes((size_t)ntiles * 3 * TC);
-  constexpr int NCL = 6; // classes of a bin: full | interior with P - 1, P - 2, P - 3 cells | other interior | boundary
-  std::vector<int32_t> tcount((size_t)ntiles * NCL * NB, 0); // [tile][bin][class]
-  auto tile_chunks = [&](auto work) {
-    const int64_t nt = host_workers(ntiles / 32);
-    if (nt <= 1)
-    {
-      work(0, ntiles);
-      return;
-    }
-    Workers wk;
-    for (int64_t w = 0; w < nt; ++w)
-      wk.spawn([&work, ntiles, w, nt]() { work((int64_t)ntiles * w / nt, (int64_t)ntiles * (w + 1) / nt); });
-    wk.join();
-  };
+}
+
+// work(t0, t1) on chunks of tiles, one per host thread
+template <typename F>
+void tile_chunks(int32_t ntiles, F work)
+{
+  const int64_t nt = host_workers(ntiles / 32);
+  if (nt <= 1)
+  {
+    work(0, ntiles);
+    return;
+  }
+  Workers wk;
+  for (int64_t w = 0; w < nt; ++w)
+    wk.spawn([&work, ntiles, w, nt]() { work((int64_t)ntiles * w / nt, (int64_t)ntiles * (w + 1) / nt); });
+  wk.join();
+}
+
+constexpr int NB = eqlb::MAX_BINS;
+constexpr int NCL = 6; // classes of a bin: full | interior with P - 1, P - 2, P - 3 cells | other interior | boundary
+
+// Pass 1 (host threads, a chunk of tiles each): the listed nodes of every tile by bin and class - full interior
+// patches (their wave-blocks run the specialised body of the kernel) first -, in order of first appearance; tnodes:
+// flat storage, 3 TC entries per tile.  full_only: the lists of a tile are padded to whole wave-blocks with copies of
+// a full patch that own no cell (nint keeps the number of real patches)
+void list_tile_patches(const eqlb::DeviceMesh& m, const std::vector<int8_t>& tile_bin, bool full_only,
+                       eqlb::TilePlan& tp, eqlb::uvec<int32_t>& tnodes)
+{
+  const int TC = tp.tc;
+  std::vector<eqlb::TileDesc>& tiles = tp.tiles;
   // sort key of a node: NCL * bin + class (full interior patch 0 | interior patch with P - 1, P - 2, P - 3 cells 1, 2, 3 |
   // other interior patch 4 | boundary patch 5); -1: not listed
   // (one byte per node, cache resident, instead of three scattered reads per visit of a node)
   std::vector<int8_t> nkey(m.nnodes);
   parallel_for(m.nnodes, 1 << 16, [&](int64_t nd) {
-    const int b_ = node_bin[nd];
+    const int b_ = tile_bin[nd];
     if (b_ < 0)
     {
       nkey[nd] = -1;
@@ -630,18 +531,21 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
     }
     const bool interior = m.h_node_ncells[nd] == m.h_node_nfcts[nd]; // no boundary facet at the node
     const int missing = eqlb::BIN_P[b_] - m.h_node_ncells[nd];         // idle lanes of the patch group
-    nkey[nd] = (int8_t)(NCL * b_ + (interior ? ((missing >= 0 && missing <= 3) ? missing : 4) : 5));
+    const int cls = eqlb::patch_is_full(m.h_node_ncells[nd], m.h_node_nfcts[nd], b_) ? 0
+                    : !interior                                                       ? 5
+                    : (missing >= 1 && missing <= 3)                                  ? missing
+                                                                                      : 4;
+    nkey[nd] = (int8_t)(NCL * b_ + cls);
   });
-  tile_chunks([&](int64_t t0, int64_t t1) {
+  tile_chunks(tp.ntiles, [&](int64_t t0, int64_t t1) {
     std::vector<int32_t> stamp(m.nnodes, -1), seen(3 * (size_t)TC);
     for (int64_t t = t0; t < t1; ++t)
     {
       int nseen = 0;
-      int32_t* cnt = &tcount[(size_t)t * NCL * NB];
-      auto key = [&](int32_t nd) { return (int)nkey[nd]; };
+      int32_t cnt[NCL * NB] = {};
       for (int q = 0; q < TC; ++q)
       {
-        const int32_t c = tile_cells[(size_t)t * TC + q];
+        const int32_t c = tp.tile_cells[(size_t)t * TC + q];
         if (c < 0)
           continue;
         for (int j = 0; j < 3; ++j)
@@ -653,7 +557,7 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
             continue;
           stamp[nd] = (int32_t)t;
           seen[nseen++] = nd;
-          ++cnt[key(nd)];
+          ++cnt[nkey[nd]];
         }
       }
       int32_t pos[NCL * NB], acc = 0; // stable counting sort by (bin, class)
@@ -664,7 +568,7 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
       }
       int32_t* out = &tnodes[(size_t)t * 3 * TC];
       for (int i = 0; i < nseen; ++i)
-        out[pos[key(seen[i])]++] = seen[i];
+        out[pos[nkey[seen[i]]]++] = seen[i];
       for (int b_ = 0; b_ < NB; ++b_)
       {
         const int32_t* cb = cnt + NCL * b_;
@@ -679,7 +583,7 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
         }
         if (full_only)
         {
-          // whole wave-blocks: nint keeps the number of real patches, the others are copies (pass 2)
+          // whole wave-blocks: nint keeps the number of real patches, the others are copies (place_instances)
           const int per = 64 / eqlb::BIN_P[b_];
           const int padded = (per > 0) ? (cb[0] + per - 1) / per * per : cb[0];
           tiles[t].nfull[b_] = padded;
@@ -690,9 +594,14 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
       }
     }
   });
-  // lane slots and patch instances in tile order (serial prefix), then filled by the host threads
+}
+
+// Lane slots and patch instances in tile order (serial prefix), then filled by the host threads
+int place_instances(bool full_only, const eqlb::uvec<int32_t>& tnodes, eqlb::TilePlan& tp)
+{
+  std::vector<eqlb::TileDesc>& tiles = tp.tiles;
   int64_t slotctr = 0, ninst = 0;
-  for (int32_t t = 0; t < ntiles; ++t)
+  for (int32_t t = 0; t < tp.ntiles; ++t)
     for (int b_ = 0; b_ < NB; ++b_)
     {
       tiles[t].slot_start[b_] = (int32_t)slotctr;
@@ -703,11 +612,14 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
       if (slotctr > 0x7fffff00)
         return fail(EQLB_ERR_UNSUPPORTED, "tiled patch SoA exceeds 2^31 lane slots");
     }
-  uvec<int32_t> inst_node((size_t)ninst), inst_slot((size_t)ninst), inst_tile((size_t)ninst);
-  tile_chunks([&](int64_t t0, int64_t t1) {
+  tp.nslots = slotctr;
+  tp.inst_node.resize((size_t)ninst);
+  tp.inst_slot.resize((size_t)ninst);
+  tp.inst_tile.resize((size_t)ninst);
+  tile_chunks(tp.ntiles, [&](int64_t t0, int64_t t1) {
     for (int64_t t = t0; t < t1; ++t)
     {
-      const int32_t* src = &tnodes[(size_t)t * 3 * TC];
+      const int32_t* src = &tnodes[(size_t)t * 3 * tp.tc];
       for (int b_ = 0; b_ < NB; ++b_)
       {
         int32_t slot = tiles[t].slot_start[b_];
@@ -715,70 +627,40 @@ int build_tiles(eqlb_se* h, const std::vector<int8_t>& node_bin_all, eqlb::Build
         for (int32_t i = 0, p_ = tiles[t].patch_start[b_]; i < tiles[t].npatch[b_]; ++i, ++p_, slot += eqlb::BIN_P[b_])
         {
           // (padding copy: the last real patch once more, tile -1 = it owns no cell and stores nothing)
-          inst_node[p_] = (i < nreal) ? *src++ : src[-1];
-          inst_slot[p_] = slot;
-          inst_tile[p_] = (i < nreal) ? (int32_t)t : -1;
+          tp.inst_node[p_] = (i < nreal) ? *src++ : src[-1];
+          tp.inst_slot[p_] = slot;
+          tp.inst_tile[p_] = (i < nreal) ? (int32_t)t : -1;
         }
       }
     }
   });
+  return EQLB_OK;
+}
+} // namespace
+
+namespace eqlb
+{
+// Tiled SoA of the plain flux equilibration (EQLB_SCATTER_TILED) and of the fused stress launch: cells bisected
+// recursively by their centroids into tiles of TC cells; a tile lists every node of its cells that bp.tile_bin lists
+// (not the masked-out ones, not those left to another path)
+int plan_tiles(const eqlb_se* h, const BoundaryPlan& bp, TilePlan& tp)
+{
+  const DeviceMesh& m = h->mesh->m;
+  const bool full_only = bp.t_stress && !bp.t_mixed;
+  tp.tc = choose_tile_cells(h->k, h->mode, m.ncells, bp.t_stress ? stress_tile_cells() : 0, h->tile_cells_user,
+                            {tile_cells_of(h->k), tile_cells_ev_of(h->k), tile_cells_max_of(h->k)});
+  tp.ntiles = (m.ncells + tp.tc - 1) / tp.tc;
+  SetupTimer tm;
+  uvec<int32_t> cells;
+  EQLB_TRY(bisect_cells(h->mesh, tp.tc, tp.ntiles, tm, cells));
+  number_tiles(h->prio_cells, m.ncells, cells, tp);
+  tm.lap("tiles: sort + priority");
+  tp.tiles.assign(tp.ntiles, TileDesc{});
+  uvec<int32_t> tnodes((size_t)tp.ntiles * 3 * tp.tc);
+  list_tile_patches(m, bp.tile_bin, full_only, tp, tnodes);
+  EQLB_TRY(place_instances(full_only, tnodes, tp));
   tm.lap("tiles: patch lists");
-  count_tile_blocks(h, tiles, full_only);
-  h->ntiles = ntiles;
-  h->tile_tc = TC;
-  h->t_nslots = slotctr;
-  h->t_npatch = (int64_t)inst_node.size();
-  int32_t *d_inode = nullptr, *d_islot = nullptr, *d_itile = nullptr, *d_ctile = nullptr, *d_cpos = nullptr;
-  int st = 0;
-  st |= upload(&h->t_tiles, tiles.data(), tiles.size());
-  st |= upload(&h->t_tile_cells, tile_cells.data(), tile_cells.size());
-  st |= upload<int32_t>(&h->t_slot_cell, nullptr, (size_t)std::max<int64_t>(slotctr, 1));
-  st |= upload<uint32_t>(&h->t_slot_info, nullptr, (size_t)std::max<int64_t>(slotctr, 1));
-  st |= upload<uint8_t>(&h->t_pn, nullptr, (size_t)std::max<int64_t>(h->t_npatch, 1));
-  st |= upload<uint8_t>(&h->t_pflag, nullptr, (size_t)std::max<int64_t>(h->t_npatch, 1) * h->nrhs);
-  st |= upload(&d_inode, inst_node.data(), std::max<size_t>(inst_node.size(), 1));
-  st |= upload(&d_islot, inst_slot.data(), std::max<size_t>(inst_slot.size(), 1));
-  st |= upload(&d_itile, inst_tile.data(), std::max<size_t>(inst_tile.size(), 1));
-  st |= upload(&d_ctile, cell_tile.data(), cell_tile.size());
-  st |= upload(&d_cpos, cell_pos.data(), cell_pos.size());
-  hipError_t e = hipSuccess;
-  if (!st)
-  {
-    e = hipMemset(h->t_slot_cell, 0xff, sizeof(int32_t) * std::max<int64_t>(slotctr, 1));
-    if (e == hipSuccess)
-      e = hipMemset(h->t_slot_info, 0, sizeof(uint32_t) * std::max<int64_t>(slotctr, 1));
-    a.ninst = h->t_npatch;
-    a.inst_node = d_inode;
-    a.inst_slot = d_islot;
-    a.inst_tile = d_itile;
-    a.cell_tile = d_ctile;
-    a.cell_pos = d_cpos;
-    a.tile_cells = TC;
-    a.npatch_total = h->t_npatch;
-    a.slot_cell = h->t_slot_cell;
-    a.slot_info = h->t_slot_info;
-    a.pn = h->t_pn;
-    a.pflag = h->t_pflag;
-    a.stride = 0;
-    a.ex_ncells = nullptr;
-    if (e == hipSuccess && a.ninst > 0)
-    {
-      eqlb::launch_build_patches(a, nullptr);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-      e = hipDeviceSynchronize();
-  }
-  tm.lap("tiles: upload + builder kernel");
-  dfree(d_inode);
-  dfree(d_islot);
-  dfree(d_itile);
-  dfree(d_ctile);
-  dfree(d_cpos);
-  if (st)
-    return EQLB_ERR_DEVICE;
-  if (e != hipSuccess)
-    return fail(EQLB_ERR_DEVICE, "tiled patch builder: %s", hipGetErrorString(e));
+  count_tile_blocks(h->k, bp.t_stress, full_only, tp.tiles, tp.blocks);
   return EQLB_OK;
 }
 } // namespace eqlb

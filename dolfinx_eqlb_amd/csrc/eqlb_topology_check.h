@@ -1,7 +1,8 @@
-// What the patch builder can walk.  eqlb_api.hip includes this file for the checks of eqlb_se_set_boundary, and the
-// stand-alone host program tools/topology_check_emul.cpp includes it with a plain C++ compiler: it calls nothing of
-// HIP.  The two per-node functions (count of one-cell facets, the walkable predicate) are also what the export launch
-// of k_build_patches runs, so that host and kernel cannot drift apart; for that one use, and only when hipcc reads
+// What the patch builder can walk.  eqlb_boundary_plan.h includes this file for the checks of eqlb_se_set_boundary
+// (and through it eqlb_handle.h: eqlb_api.hip counts the one-cell facets of a mesh with it), and the stand-alone host
+// programs tools/topology_check_emul.cpp and tools/boundary_plan_emul.cpp include it with a plain C++ compiler: it
+// calls nothing of HIP.  The two per-node functions (count of one-cell facets, the walkable predicate) are also what
+// the export launch of k_build_patches runs, so that host and kernel cannot drift apart; for that one use, and only when hipcc reads
 // the file, the macro below marks them __host__ __device__.
 //
 // k_build_patches (eqlb_patch_builder.hip) walks the cells round a node from a start facet, crossing one facet per

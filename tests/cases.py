@@ -90,3 +90,28 @@ def fan_chain_mesh():
     cells = [[i2, 3, 4], [i2, 4, 5], [i2, 11, 12], [i2, 12, 3], [i1, 6, 7], [i1, 7, 8], [i1, 8, 9], [i1, 9, 10],
              [i3, 5, 6], [i3, 10, 11], [i3, i2, 5], [i3, 11, i2], [i1, i3, 6], [i1, 10, i3]]
     return create_mesh(x, np.array(cells, dtype=np.int32))
+
+
+def big_double_fan_mesh(m, order=0):
+    """An interior node I1 of valence m + 3 and a second interior node I2 of valence 6 joined by an edge and
+    ringed by boundary nodes of two cells: with tractions on the whole boundary the two-cell patches form
+    groups whose internal patches (around I1 and I2) overlap; `order` = 1 reverses the node numbering."""
+    from dolfinx_eqlb_amd.mesh import create_mesh
+    # I1 at (-0.5, 0), I2 at (0.5, 0); ring: b0 .. b3 around I2 (right), c0 .. c_m around I1 (left)
+    rb = [[1.5, 0.0], [1.0, 1.0], [0.0, 1.1], [0.0, -1.1], [1.0, -1.0]]
+    th = np.linspace(np.pi / 2.0 + 0.3, 3.0 * np.pi / 2.0 - 0.3, m)
+    rc = np.stack([-0.5 + 1.2 * np.cos(th), 1.1 * np.sin(th)], 1)
+    x = np.concatenate([[[-0.5, 0.0], [0.5, 0.05]], rb, rc])
+    i1, i2 = 0, 1
+    b = 2 + np.arange(5)      # b0 b1 b2 (top) ... b3 b4 (bottom)
+    c = 7 + np.arange(m)      # from top to bottom on the left
+    cells = [[i2, b[0], b[1]], [i2, b[1], b[2]], [i2, b[3], b[4]], [i2, b[4], b[0]],
+             [i1, i2, b[2]], [i1, b[3], i2], [i1, b[2], c[0]], [i1, c[m - 1], b[3]]]
+    cells += [[i1, c[j], c[j + 1]] for j in range(m - 1)]
+    cells = np.array(cells, dtype=np.int32)
+    if order:
+        perm = np.arange(x.shape[0])[::-1].copy()
+        xn = np.empty_like(x)
+        xn[perm] = x
+        x, cells = xn, perm[cells].astype(np.int32)
+    return create_mesh(x, cells)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import galerkin as gk
+from cases import big_double_fan_mesh
 from test_gpu_unstructured import delaunay_mesh
 from test_oracle_stress import asym_moments
 
@@ -116,31 +117,6 @@ def test_large_boundary_patch(oracle_mod, k, m, layout):
     ft = flux_types(mesh, sels)
     G, f, bv = gk.solve_elasticity(mesh, k, ft, seed=3 * m + k)
     run_stress(oracle_mod, mesh, k, ft, G, f, bv)
-
-
-def big_double_fan_mesh(m, order=0):
-    """An interior node I1 of valence m + 3 and a second interior node I2 of valence 6 joined by an edge and
-    ringed by boundary nodes of two cells: with tractions on the whole boundary the two-cell patches form
-    groups whose internal patches (around I1 and I2) overlap; `order` = 1 reverses the node numbering."""
-    from dolfinx_eqlb_amd.mesh import create_mesh
-    # I1 at (-0.5, 0), I2 at (0.5, 0); ring: b0 .. b3 around I2 (right), c0 .. c_m around I1 (left)
-    rb = [[1.5, 0.0], [1.0, 1.0], [0.0, 1.1], [0.0, -1.1], [1.0, -1.0]]
-    th = np.linspace(np.pi / 2.0 + 0.3, 3.0 * np.pi / 2.0 - 0.3, m)
-    rc = np.stack([-0.5 + 1.2 * np.cos(th), 1.1 * np.sin(th)], 1)
-    x = np.concatenate([[[-0.5, 0.0], [0.5, 0.05]], rb, rc])
-    i1, i2 = 0, 1
-    b = 2 + np.arange(5)      # b0 b1 b2 (top) ... b3 b4 (bottom)
-    c = 7 + np.arange(m)      # from top to bottom on the left
-    cells = [[i2, b[0], b[1]], [i2, b[1], b[2]], [i2, b[3], b[4]], [i2, b[4], b[0]],
-             [i1, i2, b[2]], [i1, b[3], i2], [i1, b[2], c[0]], [i1, c[m - 1], b[3]]]
-    cells += [[i1, c[j], c[j + 1]] for j in range(m - 1)]
-    cells = np.array(cells, dtype=np.int32)
-    if order:
-        perm = np.arange(x.shape[0])[::-1].copy()
-        xn = np.empty_like(x)
-        xn[perm] = x
-        x, cells = xn, perm[cells].astype(np.int32)
-    return create_mesh(x, cells)
 
 
 @pytest.mark.parametrize("k,m", [(4, 10), (4, 30), (3, 40)])

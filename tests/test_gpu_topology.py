@@ -399,3 +399,59 @@ def test_untyped_hole_is_refused_through_the_other_entry_points(cpp):
     eq.set_boundary_conditions([outer], [[]])
     with pytest.raises(RuntimeError, match=rf"boundary facet {int(inner.min())} .*needs a boundary condition"):
         eq.equilibrate_fluxes()
+
+
+# ------------------------------------------------- refusals by patch size and by groups: planned before the tables go
+def _refused_call_changes_nothing(eq, G, f, good, good_mask, bad, bad_mask, match):
+    eq.set_boundary(good, node_mask=good_mask)
+    x0 = eq.equilibrate_host(G, f)
+    assert np.all(np.isfinite(x0)) and np.abs(x0).max() > 0
+    with pytest.raises(RuntimeError, match=match):
+        eq.set_boundary(bad, node_mask=bad_mask)
+    assert np.array_equal(eq.equilibrate_host(G, f), x0)
+    eq.set_boundary(good, node_mask=good_mask)
+    assert np.array_equal(eq.equilibrate_host(G, f), x0)
+
+
+@pytest.mark.parametrize("stress", [False, True])
+def test_refused_large_patch_leaves_the_handle_untouched(cpp, stress):
+    """A hub of 70 cells: accepted while it is masked out, refused without the mask - on a plain handle for its size
+    ("limit 63"), on a stress handle with "large_patches" because weak symmetry on such patches is a further option.
+    Both refusals come from the bins, which are planned before the old tables are dropped."""
+    from dolfinx_eqlb_amd.mesh import create_disk
+    from synthetic import facet_types, make_compatible_data, make_compatible_stress_data
+    mesh = create_disk(70, 1)
+    hub = int(np.argmax(np.diff(mesh.node_cells_offsets)))
+    assert np.diff(mesh.node_cells_offsets)[hub] == 70
+    mask = np.ones(mesh.nnodes, dtype=np.uint8)
+    mask[hub] = 0
+    nrhs = 2 if stress else 1
+    ft = np.repeat(facet_types(mesh, None), nrhs, axis=0)
+    if stress:
+        G, f = make_compatible_stress_data(mesh, 2, ft)
+    else:
+        G, f = (a[None] for a in make_compatible_data(mesh, 2, ft, seed=31))
+    eq = cpp.SemiExplicitEquilibrator(cpp.DeviceMesh(mesh), 2, nrhs, reconstruct_stress=stress)
+    if stress:
+        eq.set_option("large_patches", 1)
+    _refused_call_changes_nothing(eq, G, f, ft, mask, ft, None, "stress" if stress else "limit 63")
+
+
+def test_refused_group_leaves_the_handle_untouched(cpp):
+    """A hub of 64 cells on a stress handle that takes large patches: accepted with a Dirichlet table, refused with
+    tractions everywhere, where the hub would be the internal patch of a group of boundary patches."""
+    from cases import big_double_fan_mesh
+    from synthetic import facet_types, make_compatible_stress_data
+    mesh = big_double_fan_mesh(61, 0)
+    assert np.diff(mesh.node_cells_offsets).max() == 64
+    good = np.repeat(facet_types(mesh, None), 2, axis=0)
+    bad = np.repeat(facet_types(mesh, lambda p: np.ones(len(p), dtype=bool)), 2, axis=0)
+    G, f = make_compatible_stress_data(mesh, 2, good)
+    eq = cpp.SemiExplicitEquilibrator(cpp.DeviceMesh(mesh), 2, 2, reconstruct_stress=True)
+    eq.set_option("large_patches", 1)
+    eq.set_option("large_patches_stress", 1)
+    eq.set_boundary(good)
+    ntiles = eq.tiling_info()["ntiles"]
+    assert eq.large_patch_info()[0] == 1
+    _refused_call_changes_nothing(eq, G, f, good, None, bad, None, "group")
+    assert eq.tiling_info()["ntiles"] == ntiles

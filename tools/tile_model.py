@@ -1,5 +1,5 @@
 """Cost model of the tiled launch: wave-blocks per tile and rounds on 8 waves for several tile
-sizes (RCB tiles as in eqlb_tiling_host.hip::build_tiles).  usage: python tools/tile_model.py [n]"""
+sizes (RCB tiles as in eqlb_tiling_host.hip::plan_tiles).  usage: python tools/tile_model.py [n]"""
 import sys
 import numpy as np
 sys.path.insert(0, ".")
