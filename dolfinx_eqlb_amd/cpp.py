@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_primal_flux_dg", "eqlb_primal_stress_dg", "eqlb_get_primal_table",
     "eqlb_facet_points", "eqlb_flux_bc_dofs", "eqlb_se_update_flux_bc", "eqlb_ev_update_flux_bc",
     "eqlb_se_get_boundary_values", "eqlb_ev_get_boundary_values",
+    "eqlb_mesh_create_from_cells", "eqlb_mesh_counts", "eqlb_mesh_export", "eqlb_mesh_boundary_facets",
+    "eqlb_mesh_find_facets",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -199,6 +201,110 @@ class DeviceMesh:
         _check(lib().eqlb_mesh_create(C.c_int32(mesh.nnodes), C.c_int32(mesh.ncells),
                                       C.c_int32(mesh.nfacets), *[_hp(a) for a in arrs],
                                       C.byref(self._h)))
+
+    @classmethod
+    def from_cells(cls, x, cell_nodes, device=False, stream=0):
+        """eqlb_mesh_create_from_cells: the connectivity is built on the device from the coordinates and the cells
+        alone, in the numbering of mesh.create_mesh; `.mesh` is filled from eqlb_mesh_export.
+        device=False: host arrays, x [n, 2] or [n, 3].  device=True: x [n, 3] float64 and cell_nodes [m, 3] int32 are
+        contiguous torch tensors on the device (their data_ptr() is handed over), read on `stream`."""
+        from .mesh import Mesh
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        self.mesh = None
+        if device:
+            if tuple(x.shape[1:]) != (3,) or tuple(cell_nodes.shape[1:]) != (3,) \
+                    or not x.is_contiguous() or not cell_nodes.is_contiguous() \
+                    or x.element_size() != 8 or cell_nodes.element_size() != 4:
+                raise RuntimeError("DeviceMesh.from_cells: contiguous x [n, 3] float64 and cell_nodes [m, 3] int32 expected")
+            nnodes, ncells = int(x.shape[0]), int(cell_nodes.shape[0])
+            px, pc = C.c_void_p(x.data_ptr()), C.c_void_p(cell_nodes.data_ptr())
+        else:
+            x2 = np.asarray(x, dtype=np.float64)
+            if x2.ndim != 2 or x2.shape[1] not in (2, 3):
+                raise RuntimeError("DeviceMesh.from_cells: x [n, 2] or [n, 3] expected")
+            hx = np.zeros((x2.shape[0], 3))
+            hx[:, :x2.shape[1]] = x2
+            hc = np.ascontiguousarray(cell_nodes, dtype=np.int32)
+            if hc.ndim != 2 or hc.shape[1] != 3:
+                raise RuntimeError("DeviceMesh.from_cells: cell_nodes [m, 3] expected")
+            nnodes, ncells = hx.shape[0], hc.shape[0]
+            px, pc = _hp(hx), _hp(hc)
+        _check(lib().eqlb_mesh_create_from_cells(C.c_int32(nnodes), C.c_int32(ncells), px, pc,
+                                                 C.c_int32(MEM_DEVICE if device else MEM_HOST), C.c_void_p(stream),
+                                                 C.byref(self._h)))
+        if device:
+            hx = x.cpu().numpy().astype(np.float64, copy=False)
+            hc = cell_nodes.cpu().numpy().astype(np.int32, copy=False)
+        t = self.export()
+        self.mesh = Mesh(hx, hc, t["cell_facets"], t["facet_nodes"], t["facet_cells_offsets"], t["facet_cells"],
+                         t["node_cells_offsets"], t["node_cells"], t["node_facets_offsets"], t["node_facets"],
+                         t["facet_perm"])
+        return self
+
+    def counts(self):
+        """(nnodes, ncells, nfacets) of the handle (eqlb_mesh_counts)."""
+        v = [C.c_int32(0) for _ in range(3)]
+        _check(lib().eqlb_mesh_counts(self._h, *[C.byref(a) for a in v]))
+        return tuple(int(a.value) for a in v)
+
+    def export(self):
+        """The tables of the handle as host arrays (eqlb_mesh_export), by the field names of mesh.Mesh."""
+        nn, nc, nf = self.counts()
+        off = {"facet_cells_offsets": np.zeros(nf + 1, dtype=np.int32),
+               "node_cells_offsets": np.zeros(nn + 1, dtype=np.int32),
+               "node_facets_offsets": np.zeros(nn + 1, dtype=np.int32)}
+        _check(lib().eqlb_mesh_export(self._h, None, None, _hp(off["facet_cells_offsets"]), None,
+                                      _hp(off["node_cells_offsets"]), None, _hp(off["node_facets_offsets"]), None,
+                                      None, C.c_int32(MEM_HOST), None))
+        t = {"cell_facets": np.zeros((nc, 3), dtype=np.int32), "facet_nodes": np.zeros((nf, 2), dtype=np.int32),
+             "facet_cells": np.zeros(int(off["facet_cells_offsets"][-1]), dtype=np.int32),
+             "node_cells": np.zeros(int(off["node_cells_offsets"][-1]), dtype=np.int32),
+             "node_facets": np.zeros(int(off["node_facets_offsets"][-1]), dtype=np.int32),
+             "facet_perm": np.zeros((nc, 3), dtype=np.uint8)}
+        _check(lib().eqlb_mesh_export(self._h, _hp(t["cell_facets"]), _hp(t["facet_nodes"]), None,
+                                      _hp(t["facet_cells"]), None, _hp(t["node_cells"]), None, _hp(t["node_facets"]),
+                                      _hp(t["facet_perm"]), C.c_int32(MEM_HOST), None))
+        t.update(off)
+        return t
+
+    def export_raw(self, cell_facets=None, facet_nodes=None, facet_cells_offsets=None, facet_cells=None,
+                   node_cells_offsets=None, node_cells=None, node_facets_offsets=None, node_facets=None,
+                   facet_perm=None, memspace=MEM_DEVICE, stream=0):
+        """eqlb_mesh_export on raw pointers (ints, None for a table that is not wanted) in `memspace`."""
+        _check(lib().eqlb_mesh_export(self._h, _vp(cell_facets), _vp(facet_nodes), _vp(facet_cells_offsets),
+                                      _vp(facet_cells), _vp(node_cells_offsets), _vp(node_cells),
+                                      _vp(node_facets_offsets), _vp(node_facets), _vp(facet_perm),
+                                      C.c_int32(memspace), C.c_void_p(stream)))
+
+    def boundary_facets(self):
+        """Ids of the facets with one cell, ascending (eqlb_mesh_boundary_facets)."""
+        n = C.c_int32(0)
+        out = np.zeros(self.counts()[2], dtype=np.int32)
+        _check(lib().eqlb_mesh_boundary_facets(self._h, _hp(out), C.c_int32(out.size), C.byref(n),
+                                               C.c_int32(MEM_HOST), None))
+        return out[:n.value].copy()
+
+    def boundary_facets_raw(self, facets, capacity, memspace=MEM_DEVICE, stream=0):
+        """eqlb_mesh_boundary_facets on a raw pointer; returns (status, count) - the count is reported even when the
+        capacity is refused."""
+        n = C.c_int32(0)
+        st = lib().eqlb_mesh_boundary_facets(self._h, _vp(facets), C.c_int32(capacity), C.byref(n),
+                                             C.c_int32(memspace), C.c_void_p(stream))
+        return int(st), int(n.value)
+
+    def find_facets(self, pairs):
+        """Facet id of every node pair [npairs, 2] in either order, -1 where the pair is no edge of the mesh
+        (eqlb_mesh_find_facets): translates facets tagged by their vertices into the ids of facet_type."""
+        p = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(p.shape[0], dtype=np.int32)
+        _check(lib().eqlb_mesh_find_facets(self._h, C.c_int32(p.shape[0]), _hp(p), _hp(out), C.c_int32(MEM_HOST),
+                                           None))
+        return out
+
+    def find_facets_raw(self, npairs, pairs, facets, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_mesh_find_facets(self._h, C.c_int32(npairs), _vp(pairs), _vp(facets), C.c_int32(memspace),
+                                           C.c_void_p(stream)))
 
     @property
     def max_patch_cells(self):

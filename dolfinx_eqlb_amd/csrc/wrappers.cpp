@@ -93,6 +93,57 @@ struct Mesh
   Mesh(const Mesh&) = delete;
   Mesh& operator=(const Mesh&) = delete;
 
+  // the topology derived on the device (eqlb_mesh_create_from_cells); the host vectors come from the export
+  static std::shared_ptr<Mesh> from_cells(carray<double> x_, carray<int32_t> cn)
+  {
+    if (x_.ndim() != 2 || (x_.shape(1) != 2 && x_.shape(1) != 3) || cn.ndim() != 2 || cn.shape(1) != 3)
+      throw std::runtime_error("Mesh.from_cells: x [nnodes, 2 or 3], cell_nodes [ncells, 3] expected");
+    std::shared_ptr<Mesh> m(new Mesh());
+    m->nnodes = (int32_t)x_.shape(0);
+    m->ncells = (int32_t)cn.shape(0);
+    const int gdim = (int)x_.shape(1);
+    m->x.assign(3 * (size_t)m->nnodes, 0.0);
+    for (size_t i = 0; i < (size_t)m->nnodes; ++i)
+      for (int j = 0; j < gdim; ++j)
+        m->x[3 * i + j] = x_.data()[gdim * i + j];
+    m->cell_nodes.assign(cn.data(), cn.data() + cn.size());
+    check(eqlb_mesh_create_from_cells(m->nnodes, m->ncells, m->x.data(), m->cell_nodes.data(), EQLB_MEM_HOST, nullptr,
+                                      &m->h));
+    check(eqlb_mesh_counts(m->h, nullptr, nullptr, &m->nfacets));
+    m->cell_facets.resize(3 * (size_t)m->ncells);
+    m->facet_nodes.resize(2 * (size_t)m->nfacets);
+    m->facet_cells_off.resize((size_t)m->nfacets + 1);
+    m->facet_cells.resize(3 * (size_t)m->ncells);
+    m->facet_perm.resize(3 * (size_t)m->ncells);
+    check(eqlb_mesh_export(m->h, m->cell_facets.data(), m->facet_nodes.data(), m->facet_cells_off.data(),
+                           m->facet_cells.data(), nullptr, nullptr, nullptr, nullptr, m->facet_perm.data(),
+                           EQLB_MEM_HOST, nullptr));
+    return m;
+  }
+
+  py::array_t<int32_t> boundary_facets() const
+  {
+    int32_t n = 0;
+    std::vector<int32_t> all((size_t)nfacets);
+    check(eqlb_mesh_boundary_facets(h, all.data(), nfacets, &n, EQLB_MEM_HOST, nullptr));
+    return py::array_t<int32_t>(n, all.data());
+  }
+
+  py::array_t<int32_t> find_facets(carray<int32_t> pairs) const
+  {
+    if (pairs.size() % 2 != 0)
+      throw std::runtime_error("Mesh.find_facets: pairs [npairs, 2] expected");
+    const int32_t np_ = (int32_t)(pairs.size() / 2);
+    py::array_t<int32_t> out(np_);
+    check(eqlb_mesh_find_facets(h, np_, pairs.data(), out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
+
+private:
+  Mesh() = default;
+
+public:
+
   // affine map of a cell: J (dx_i/dX_j), detJ
   double jacobian(int32_t c, double J[2][2]) const
   {
@@ -869,6 +920,11 @@ PYBIND11_MODULE(_cpp, m)
            py::arg("x"), py::arg("cell_nodes"), py::arg("cell_facets"), py::arg("facet_nodes"),
            py::arg("facet_cells_offsets"), py::arg("facet_cells"), py::arg("node_cells_offsets"),
            py::arg("node_cells"), py::arg("node_facets_offsets"), py::arg("node_facets"), py::arg("facet_perm"))
+      .def_static("from_cells", &Mesh::from_cells, py::arg("x"), py::arg("cell_nodes"),
+                  "Mesh from coordinates [nnodes, 2 or 3] and cells [ncells, 3]: the connectivity is built on the device")
+      .def("boundary_facets", &Mesh::boundary_facets, "ids of the facets with one cell, ascending")
+      .def("find_facets", &Mesh::find_facets, py::arg("pairs"),
+           "facet id of every node pair [npairs, 2] (either order), -1 where the pair is no edge")
       .def_readonly("nnodes", &Mesh::nnodes)
       .def_readonly("ncells", &Mesh::ncells)
       .def_readonly("nfacets", &Mesh::nfacets)

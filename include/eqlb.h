@@ -92,6 +92,73 @@ int eqlb_mesh_create(int32_t nnodes, int32_t ncells, int32_t nfacets, const doub
 void eqlb_mesh_destroy(eqlb_mesh_t* mesh);
 
 /*
+ * The same handle from coordinates and cells alone: every other table of eqlb_mesh_create is derived on the device.
+ * The reference gets its topology from DOLFINx and makes a new mesh in every step of its adaptive demos
+ * (demo/poisson_adaptive/demo_lshape.py, demo_discont-coeff.py, demo/elasticity_adaptive/demo_cook.py: mesh.refine,
+ * then FluxEquilibrator.initialise_mesh_info again).
+ *   x           [nnodes][3]   coordinates
+ *   cell_nodes  [ncells][3]   any local order
+ *   memspace    EQLB_MEM_HOST or EQLB_MEM_DEVICE: where x and cell_nodes lie; nothing is retained
+ *   stream      hipStream_t (NULL = default stream): the build is enqueued there and the call WAITS for it before it
+ *               returns, because the host copies of the tables are part of the handle
+ * Numbering - the handle is what eqlb_mesh_create builds from the arrays of dolfinx_eqlb_amd.mesh.create_mesh, bit for
+ * bit, and from eqlb_se_create on nothing tells the two kinds of handle apart:
+ *   facets       the unique edges in ascending order of the 64-bit key min(a, b) * nnodes + max(a, b); facet_nodes has
+ *                the low node first
+ *   cell_facets  local facet f lies opposite local vertex f (vertex pairs [1,2], [0,2], [0,1])
+ *   facet_perm   [c][f] = (first vertex of that pair > second)
+ *   facet_cells, node_cells, node_facets  CSR with ascending entries; a node that no cell uses has empty rows
+ * One stable radix sort of the 3 ncells (key, 3 cell + f) pairs, head flags and a scan give the facets; two more
+ * stable sorts give the per-node tables.  Integer work only, no atomics but atomicMin on the error words: two calls
+ * give the same bits.  Peak device memory during the call: the handle's arrays plus 84 bytes per cell and the work
+ * space of the sort, freed before the call returns.
+ * Refusals - *mesh is not written by any of them, and the next valid call works:
+ *   before anything is launched
+ *     EQLB_ERR_INVALID_ARGUMENT  null or empty input; a memspace that is neither constant; 3 * ncells > INT32_MAX
+ *     EQLB_ERR_DEVICE            no device
+ *   found on the device (EQLB_ERR_INVALID_ARGUMENT; the message names the lowest offender).  The keys are formed from
+ *   the indices themselves and no index is used to address memory before the error words have been read back clean:
+ *     a node index outside [0, nnodes)        names the cell
+ *     a cell with a repeated node             names the cell
+ *     an edge shared by more than two cells   names its two nodes
+ */
+int eqlb_mesh_create_from_cells(int32_t nnodes, int32_t ncells, const double* x, const int32_t* cell_nodes,
+                                int32_t memspace, void* stream, eqlb_mesh_t** mesh);
+
+/* The four entries below work on every mesh handle, whichever call made it. */
+
+/* Sizes of the mesh; any output may be NULL. */
+int eqlb_mesh_counts(const eqlb_mesh_t* mesh, int32_t* nnodes, int32_t* ncells, int32_t* nfacets);
+
+/* The tables of the handle in the layout of eqlb_mesh_create - how the caller of eqlb_mesh_create_from_cells learns
+ * the numbering.  Any output may be NULL.  Sizes: cell_facets, facet_perm [ncells][3]; facet_nodes [nfacets][2]; the
+ * offsets [nfacets + 1] / [nnodes + 1]; facet_cells, node_cells 3 ncells entries, node_facets 2 nfacets entries (for a
+ * handle of eqlb_mesh_create: the last offset of its tables).  Host memory space: synchronous.  Device memory space:
+ * copies on `stream`, nothing waits. */
+int eqlb_mesh_export(eqlb_mesh_t* mesh, int32_t* cell_facets, int32_t* facet_nodes, int32_t* facet_cells_offsets,
+                     int32_t* facet_cells, int32_t* node_cells_offsets, int32_t* node_cells,
+                     int32_t* node_facets_offsets, int32_t* node_facets, uint8_t* facet_perm, int32_t memspace,
+                     void* stream);
+
+/* The facets with one cell in ascending id, written by an ordered compaction (flags, scan, scatter; no atomics).
+ *   facets [capacity] in `memspace`; nfacets entries are always enough (NULL with capacity 0 is accepted and
+ *          treated like any other capacity)
+ *   n      HOST: always the full count, so the call waits for `stream` in either memory space
+ * capacity smaller than the count: EQLB_ERR_INVALID_ARGUMENT, *n holds the count, facets is not written. */
+int eqlb_mesh_boundary_facets(eqlb_mesh_t* mesh, int32_t* facets, int32_t capacity, int32_t* n, int32_t memspace,
+                              void* stream);
+
+/* Facet ids of node pairs - how a DOLFINx caller translates tagged facets (their vertex pairs) into the ids that
+ * facet_type of eqlb_se_set_boundary is indexed with.
+ *   node_pairs [npairs][2], facets [npairs] in `memspace`
+ * facets[i] = the facet whose two nodes are the pair, in either order; -1 for a pair that is no edge of the mesh or
+ * has a node outside [0, nnodes).  One thread per pair walks the facets of the first node; nothing is assumed about
+ * the order of the facet ids (a handle of eqlb_mesh_create carries the caller's numbering).  Device memory space: one
+ * kernel on `stream`, nothing waits; host memory space: staged, synchronous. */
+int eqlb_mesh_find_facets(eqlb_mesh_t* mesh, int32_t npairs, const int32_t* node_pairs, int32_t* facets,
+                          int32_t memspace, void* stream);
+
+/*
  * Semi-explicit equilibrator for RT_k fluxes with projected flux / RHS in DG_{degree_dg}
  * (0 <= degree_dg <= k-1, else EQLB_ERR_INVALID_ARGUMENT "Wrong polynomial degree"; the reference requires
  * deg(flux_dg) == deg(rhs_dg) <= k-1, se/reconstruction.hpp:363-373) and nrhs simultaneously equilibrated fluxes.
