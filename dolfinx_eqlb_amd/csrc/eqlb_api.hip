@@ -252,12 +252,7 @@ int eqlb_se_set_option(eqlb_se_t* h, const char* key, int32_t value)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_set_option: null argument");
   if (!strcmp(key, "solver"))
   {
-#ifdef EQLB_EXP_SOLVER9 // timing-only variant without the solve (wrong results): experiment builds only
-    const bool exp9 = value == 9;
-#else
-    const bool exp9 = false;
-#endif
-    if (value != EQLB_SOLVER_LDS_CHOLESKY && value != EQLB_SOLVER_SHUFFLE && !exp9)
+    if (value != EQLB_SOLVER_LDS_CHOLESKY && value != EQLB_SOLVER_SHUFFLE)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "unknown solver %d", value);
     h->solver = value;
   }

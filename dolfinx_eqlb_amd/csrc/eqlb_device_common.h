@@ -25,9 +25,6 @@ __host__ __device__ constexpr double bcoef(int j, int i)
 
 // weak-symmetry kernels: relative size (against the largest entry of the Schur system) below which a
 // pivot counts as zero
-#ifndef EQLB_WS_PIVOT_RTOL
-#define EQLB_WS_PIVOT_RTOL 1e-11
-#endif
 
 // ---- wave-level helpers -----------------------------------------------------------------------
 // LDS traffic between lanes of ONE wave: DS operations of a wave execute in order, the fences
@@ -47,9 +44,6 @@ __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 // gfx9 dpp_ctrl codes: quad_perm 0x00-0xff, row_shl:n 0x100+n, row_shr:n 0x110+n, wave_shl:1 0x130,
 // wave_shr:1 0x138, row_mirror 0x140, row_half_mirror 0x141.  Lanes without a source get 0
 // (bound_ctrl: the destination needs no copy of the old value, one v_mov_dpp per dword).
-#ifndef EQLB_USE_DPP
-#define EQLB_USE_DPP 1
-#endif
 template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v)
 {
@@ -63,9 +57,9 @@ __device__ __forceinline__ double dpp_d(double v)
 template <int P, int OFF>
 __device__ __forceinline__ double lane_down_d(double v, int gbase, int sub)
 {
-  if constexpr (EQLB_USE_DPP && P <= 16)
+  if constexpr (P <= 16)
     return dpp_d<0x110 + OFF>(v);
-  else if constexpr (EQLB_USE_DPP && OFF == 1)
+  else if constexpr (OFF == 1)
     return dpp_d<0x138>(v);
   else
     return __shfl(v, gbase + ((sub >= OFF) ? sub - OFF : sub), 64);
@@ -74,43 +68,18 @@ __device__ __forceinline__ double lane_down_d(double v, int gbase, int sub)
 template <int P>
 __device__ __forceinline__ double lane_up1_d(double v, int gbase, int sub)
 {
-  if constexpr (EQLB_USE_DPP && P <= 16)
+  if constexpr (P <= 16)
     return dpp_d<0x101>(v);
-  else if constexpr (EQLB_USE_DPP)
-    return dpp_d<0x130>(v);
   else
-    return __shfl(v, gbase + ((sub + 1 < P) ? sub + 1 : sub), 64);
+    return dpp_d<0x130>(v);
 }
 // sum over the P lanes of a group, result in every lane
-// EQLB_GSUM_SWIZZLE: the butterfly of group_sum_d through ds_swizzle_b32 (LDS crossbar, no LDS memory, no address
-// register) instead of DPP moves: the same pairs in the same order, bit-identical sums; 2 VALU issue slots less per
-// step at the price of the LDS pipe's latency
-#ifndef EQLB_GSUM_SWIZZLE
-#define EQLB_GSUM_SWIZZLE 0
-#endif
-template <int XOR>
-__device__ __forceinline__ double swizzle_xor_d(double v)
-{
-  constexpr int PAT = (XOR << 10) | 0x1f; // bit-mask mode: lane' = ((lane & 0x1f) | 0) ^ XOR within 32 lanes
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_ds_swizzle(lo, PAT);
-  hi = __builtin_amdgcn_ds_swizzle(hi, PAT);
-  return __hiloint2double(hi, lo);
-}
+// (DPP moves; the same butterfly through ds_swizzle_b32 gave bit-identical sums and was not faster: 2 VALU issue
+// slots less per step at the price of the LDS pipe's latency, DESIGN.md "retired build switches")
 template <int P>
 __device__ __forceinline__ double group_sum_d(double v, int gbase, int sub)
 {
-  if constexpr (EQLB_GSUM_SWIZZLE && P <= 16)
-  {
-    v += swizzle_xor_d<1>(v);
-    v += swizzle_xor_d<2>(v);
-    if constexpr (P >= 8)
-      v += swizzle_xor_d<4>(v);
-    if constexpr (P >= 16)
-      v += swizzle_xor_d<8>(v);
-    return v;
-  }
-  else if constexpr (EQLB_USE_DPP && P <= 16)
+  if constexpr (P <= 16)
   {
     v += dpp_d<0xB1>(v); // quad_perm [1,0,3,2]
     v += dpp_d<0x4E>(v); // quad_perm [2,3,0,1]
@@ -131,31 +100,20 @@ __device__ __forceinline__ double group_sum_d(double v, int gbase, int sub)
 
 // ---- reciprocal / reciprocal square root: hardware seed + 2 Newton steps (full fp64 accuracy for
 // the well-scaled pivots of the patch systems; no denormal/overflow scaling as in the IEEE division)
-#ifndef EQLB_FAST_RCP
-#define EQLB_FAST_RCP 1
-#endif
 __device__ __forceinline__ double rcp_d(double x)
 {
-#if EQLB_FAST_RCP
   double r = __builtin_amdgcn_rcp(x);
   r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
   r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
   return r;
-#else
-  return 1.0 / x;
-#endif
 }
 __device__ __forceinline__ double rsqrt_d(double x)
 {
-#if EQLB_FAST_RCP
   double y = __builtin_amdgcn_rsq(x);
   // y <- y + y * (1 - x y^2) / 2
   y = __builtin_fma(y * 0.5, __builtin_fma(-x * y, y, 1.0), y);
   y = __builtin_fma(y * 0.5, __builtin_fma(-x * y, y, 1.0), y);
   return y;
-#else
-  return 1.0 / sqrt(x);
-#endif
 }
 
 
@@ -168,9 +126,6 @@ __host__ __device__ constexpr int combo_index(int fm, int fp, bool rev)
 }
 
 // ---- compile-time sizes of a (K, DEG, P) patch kernel ------------------------------------------
-#ifndef EQLB_WQ_PAD
-#define EQLB_WQ_PAD 0 // 13 was measured: RT_3 0.300 -> 0.325 ms at 1M triangles, 2.30 -> 2.47 at 8M (see Sizes::NCMBH)
-#endif
 template <int K, int DEG, int P>
 struct Sizes
 {
@@ -203,12 +158,13 @@ struct Sizes
   // RT_3 tiles stage only the combinations WITHOUT the reversal flag of the load tensor (half of WQ: the LDS
   // decides their tile size); for a reversed minus facet the load follows from Q_rev = Q blockdiag(B, I):
   // load_h = sum_j B[j][h] load_j for the K unknowns [d | um] (se_patch_body, HALFWQ)
-  // EQLB_WQ_PAD > 0 pads the combinations of the staged half: a wave reads the same (row, column) of different
+  // The combinations of the staged half are NOT padded (NCMBH = NCMB): a wave reads the same (row, column) of different
   // combinations at once, and their natural stride of 3 NH NCOLS doubles (k = 3: 216 doubles = 432 dwords = 16 mod 32
-  // banks) puts three of the six combinations on the same banks of a ds_read2_b64.  Built with 13 doubles more (458
-  // dwords, banks of its own for every combination) and measured SLOWER (0.325 against 0.300 ms: the rows lose their
-  // 16-byte alignment, the reads are no longer paired) - kept at 0
-  static constexpr int NCMB = 3 * NH * NCOLS, NCMBH = NCMB + ((K == 3) ? EQLB_WQ_PAD : 0);
+  // banks) puts three of the six combinations on the same banks of a ds_read2_b64.  A padding of 13 doubles (458
+  // dwords, banks of its own for every combination) was measured SLOWER: RT_3 0.300 -> 0.325 ms at 1M triangles,
+  // 2.30 -> 2.47 at 8M (the rows lose their 16-byte alignment, the reads are no longer paired;
+  // profiles/r03_wqpad_ab.txt)
+  static constexpr int NCMB = 3 * NH * NCOLS, NCMBH = NCMB;
   static constexpr int NWQH = (NCOMBO / 2) * NCMBH, NTAB_HALF = NTAB - NWQT + NWQH;
   // workgroup size: as many waves as fit a 64 KiB LDS budget for the dense tiles (at least one)
   // k = 4 (dense LDS solver): the tables and the patch tiles leave no room for WG, it is read from global memory

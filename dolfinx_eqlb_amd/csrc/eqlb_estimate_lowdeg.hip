@@ -1,10 +1,9 @@
 // Estimator and acceptance kernels for projected data of a degree below k - 1 (see eqlb_se_kernels_lowdeg.hip for
-// the equilibrators): the instances of the bodies of eqlb_estimate.hip at (K, DEG) = (2, 0), (3, 1), (3, 0); k = 4
+// the equilibrators): the instances of the bodies of eqlb_estimate_kernels.h at (K, DEG) = (2, 0), (3, 1), (3, 0); k = 4
 // with DEG = 2, 1, 0 in eqlb_estimate_lowdeg_k4.hip.  flux_dg / rhs_dg are read in DG_d with the tensors HG, DM, F0,
 // MRD, MPS of the pair - no embedding pass and no temporary of DG_{k-1} size.  A translation unit of its own, so
 // that the code objects of the DEG = k - 1 kernels in eqlb_estimate.hip stay as they are.
-#define EQLB_EST_TEMPLATES_ONLY 1
-#include "eqlb_estimate.hip"
+#include "eqlb_estimate_kernels.h"
 
 namespace eqlb
 {

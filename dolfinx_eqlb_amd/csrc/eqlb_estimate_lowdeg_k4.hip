@@ -1,7 +1,6 @@
 // RT_4 estimator and acceptance kernels for projected data in DG_2, DG_1, DG_0 (see eqlb_estimate_lowdeg.hip).  Their
 // reference tensors are not in git: the build writes them (tools/gen_tables.py --build, csrc/Makefile).
-#define EQLB_EST_TEMPLATES_ONLY 1
-#include "eqlb_estimate.hip"
+#include "eqlb_estimate_kernels.h"
 #include "eqlb_tables_build_gen.h"
 
 namespace eqlb

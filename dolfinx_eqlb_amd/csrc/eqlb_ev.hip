@@ -1,5 +1,5 @@
 // Layout kernels of the constrained-minimisation (EV) equilibrator: the patch kernel
-// (eqlb_se_kernels.hip, MODE 1) produces patch-local coefficients in the broken hierarchic RT_k
+// (eqlb_se_body.h, MODE 1) produces patch-local coefficients in the broken hierarchic RT_k
 // layout [cell][vertex slot][k(k+2)]; the flux of FluxEqlbEV lives in an H(div)-conforming space
 // (python/dolfinx_eqlb/eqlb/FluxEqlbEV.py:94-101, scatter ev/solve_patch.hpp:223-227).  Here the
 // conforming version of the hierarchic RT_k is used: facet DOFs in the global facet frame, a cell

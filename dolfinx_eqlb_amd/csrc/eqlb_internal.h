@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/eqlb.h"
+#include "eqlb_tuning.h"
 #include "eqlb_bins.h" // MAX_BINS, BIN_P, Bin, WS_MAX_LEVELS: shared with the planner of the set-up
 
 namespace eqlb
@@ -108,22 +109,11 @@ struct TileDesc
 // Wave-block ranges of one bin of a tile's patch list (P lanes per patch, 64 / P patches per wave-block). The tiled
 // kernels (k_se_patch_tiled*, k_se_stress_tiled) split their lists with these functions, and so does the host count
 // behind eqlb_se_tiling_blocks: it reports what the kernels run.
-#ifndef EQLB_TILE_INTERIOR
-#define EQLB_TILE_INTERIOR 1
-#endif
-#ifndef EQLB_TILE_INTERIOR_K3
-#define EQLB_TILE_INTERIOR_K3 0 // the interior-patch instance for RT_3 as well: no gain on the Delaunay mesh (0.413 - 0.418 ms either way)
-#endif
-#ifndef EQLB_STRESS_NFIX
-#define EQLB_STRESS_NFIX 1 // MIXED kernel: instances for interior patches with P - 1, P - 2, P - 3 cells (0: generic instance)
-#endif
 // k_se_patch_tiled: an instance for whole wave-blocks of full patches (RT_1: the body is too small for the second
-// instance to pay), and one for whole wave-blocks of interior patches of any size (K = 2, P = 8, 16)
+// instance to pay), and one for whole wave-blocks of interior patches of any size (K = 2, P = 8, 16; for RT_3, P = 8
+// as well: no gain on the Delaunay mesh, 0.413 - 0.418 ms either way)
 __host__ __device__ constexpr bool tile_spec_full(int K, int P) { return P <= 8 && K >= 2; }
-__host__ __device__ constexpr bool tile_spec_interior(int K, int P)
-{
-  return EQLB_TILE_INTERIOR && ((K == 2 && (P == 8 || P == 16)) || (EQLB_TILE_INTERIOR_K3 && K == 3 && P == 8));
-}
+__host__ __device__ constexpr bool tile_spec_interior(int K, int P) { return K == 2 && (P == 8 || P == 16); }
 // wave-blocks of the first n patches: all of them (the last one may be partly empty) / the whole ones only
 __host__ __device__ __forceinline__ int tile_wb_all(int n, int P) { return (n * P + 63) >> 6; }
 __host__ __device__ __forceinline__ int tile_wb_whole(int n, int P) { return (n * P) >> 6; }
@@ -136,7 +126,7 @@ __host__ __device__ __forceinline__ void tile_nfix_range(const TileDesc& td, int
   constexpr int PER = 64 / P;
   const int first = (j == 0) ? td.nfull[B] : td.nval[B][j - 1];
   c0 = (first + PER - 1) / PER;
-  c1 = (EQLB_STRESS_NFIX && P - 1 - j >= 3) ? td.nval[B][j] / PER : 0;
+  c1 = (P - 1 - j >= 3) ? td.nval[B][j] / PER : 0;
   if (c1 < c0)
     c1 = c0;
 }
@@ -220,15 +210,6 @@ int launch_se_patch_tiled_multi(int k, int deg, int mode, const SeArgs& a, const
 // RT_2 / P1, SE mode: the tiled launch whose full 8-cell patches run on four lanes, two ring cells per lane
 // (eqlb_se_kernels_pair.hip); launch_se_patch_tiled hands over to it where the instance is built and the handle has
 // one right-hand side
-#ifndef EQLB_PAIR_LANES
-#define EQLB_PAIR_LANES 1 // 0: the full-patch instance, 8 per wave-block, for every full patch (register report and A/B)
-#endif
-#ifndef EQLB_PAIR_OPAQUE
-#define EQLB_PAIR_OPAQUE 0 // opaque lane index for the lane predicates of the pair-lane instance (119 VGPRs either way)
-#endif
-#ifndef EQLB_PAIR_WQ_SPLIT
-#define EQLB_PAIR_WQ_SPLIT 1 // pair-lane instance: the load tensor in batches of one metric row (3 reads of 16 bytes) instead of 9 (0: 86 spilled registers)
-#endif
 bool pair_lanes_built();
 int launch_se_patch_tiled_pair(const SeArgs& a, const TileArgs& t, hipStream_t stream);
 // the same launches for projected data of degree deg < k - 1 (eqlb_se_kernels_lowdeg*.hip): the launchers above hand

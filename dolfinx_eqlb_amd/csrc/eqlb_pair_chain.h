@@ -3,7 +3,7 @@
 // The patch is a ring of 8 cells; cell i has the minus facet E_i and the plus facet E_{i+1} (E_8 = E_0).  Two mappings:
 //   pair_*  four lanes per patch, lane l holds the ring cells 2 l ("cell 0 of the lane") and 2 l + 1 ("cell 1"): the
 //           facet E_{2l+1} is interior to the lane, only E_{2l} and E_{2l+2} are exchanged with the neighbour lanes;
-//   cell_*  eight lanes per patch, lane i holds cell i: the arithmetic of se_patch_body (eqlb_se_kernels.hip, K = 2,
+//   cell_*  eight lanes per patch, lane i holds cell i: the arithmetic of se_patch_body (eqlb_se_body.h, K = 2,
 //           FULL) restated over the same primitives, as the yardstick of the emulation.
 // T is the value type of one register across the lanes (device: double, host: an array indexed by the lane), X the
 // lane exchange: X::dn(v) / X::up(v) the value of the previous / next lane of the group (cyclic), X::dn2(v) of the

@@ -1,12 +1,12 @@
 // Patch kernels for projected data of a degree below k - 1: RT_k with flux_dg / rhs_dg in DG_d, d < k - 1, which the
 // reference accepts for any d <= k - 1 (se/reconstruction.hpp:363-373) and its unit tests produce from P_{k-1} primal
-// solutions (d = k - 2).  The instances of the templates of eqlb_se_kernels.hip at (K, DEG) = (2, 0), (3, 1), (3, 0)
+// solutions (d = k - 2).  The instances of the templates of eqlb_se_launch.h and eqlb_se_tile.h at (K, DEG) = (2, 0), (3, 1), (3, 0)
 // for every launch family that runs at DEG = k - 1: tiled (single and multi right-hand side, SE and EV), fused slot
 // launches, per-bin launches; k = 4 with DEG = 2, 1, 0 in eqlb_se_kernels_lowdeg_k4.hip.  The data are read in DG_d
 // directly - the tensors F, H, D, HG, WG of the pair (tools/gen_tables.py) - so nothing is embedded into DG_{k-1}.
 // Translation units of their own: they compile in parallel with eqlb_se_kernels.hip, whose instances they leave alone.
-#define EQLB_SE_TEMPLATES_ONLY 1
-#include "eqlb_se_kernels.hip"
+#include "eqlb_se_launch.h"
+#include "eqlb_se_tile.h"
 
 namespace eqlb
 {

@@ -3,8 +3,7 @@
 // are the largest part of the lower-degree build; in a translation unit of their own they compile in parallel with
 // the rest.  Their reference tensors (0.4 MB of literals) are not in git: the build writes them
 // (tools/gen_tables.py --build, csrc/Makefile).
-#define EQLB_SE_TEMPLATES_ONLY 1
-#include "eqlb_se_kernels.hip"
+#include "eqlb_se_launch.h"
 #include "eqlb_tables_build_gen.h"
 
 namespace eqlb

@@ -10,8 +10,7 @@
 #include "eqlb_internal.h"
 
 #if EQLB_PAIR_LANES
-#define EQLB_SE_TEMPLATES_ONLY 1
-#include "eqlb_se_kernels.hip"
+#include "eqlb_se_tile.h"
 #include "eqlb_pair_chain.h"
 
 namespace eqlb
@@ -23,10 +22,7 @@ struct PairDpp
   using mask = bool;
   static __device__ __forceinline__ int sub()
   {
-    int t = threadIdx.x;
-#if EQLB_PAIR_OPAQUE
-    asm volatile("" : "+v"(t)); // (keeps the lane predicates from being hoisted to the top of the tile loops)
-#endif
+    int t = threadIdx.x; // (an opaque lane index is not needed here: 119 VGPRs either way)
     return t & 3;
   }
   static __device__ __forceinline__ double cst(double c) { return c; }
@@ -300,12 +296,8 @@ __device__ __forceinline__ void se_pair_body(const SeArgs& a, const int64_t slot
 #pragma unroll
       for (int x = 0; x < 3; ++x)
       {
-#if EQLB_PAIR_WQ_SPLIT
+        // (the load tensor in batches of one metric row, 3 reads of 16 bytes: all 9 at once spill 86 registers)
         pair_fence(ci, (x > 0) ? sx[x - 1] : ((h == 0) ? te[c][NTES - 1] : le[c][h - 1]));
-#else
-        if (x == 0)
-          pair_fence(ci, (h == 0) ? te[c][NTES - 1] : le[c][h - 1]);
-#endif
         const double* wq = row16<true>(sWQ + ci * 3 * NH * NCOLS + (x * NH + h) * NCOLS);
         double s_ = 0.0;
 #pragma unroll

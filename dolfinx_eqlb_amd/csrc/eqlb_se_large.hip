@@ -1,7 +1,7 @@
 // Vertex patches that do not fit one wavefront (more than 63 cells or more than 64 patch facets): one WORKGROUP per
 // patch, the cells of the fan strided over its threads.
 //
-// Same formulation as se_patch_body (eqlb_se_kernels.hip; numpy statement tests/proto_gpu_math.py): own-frame outward
+// Same formulation as se_patch_body (eqlb_se_body.h; numpy statement tests/proto_gpu_math.py): own-frame outward
 // flux moments, element matrix and load from the reduced tensors TE / WQ of the handle's table buffer, the HB rule for
 // inhomogeneous flux BCs with its 1e-7 skip, MODE 1 = the constrained-minimisation (EV) patch problem in the same
 // reduced unknowns.  What differs is the mapping, so the result differs from the one-wave path by rounding only:

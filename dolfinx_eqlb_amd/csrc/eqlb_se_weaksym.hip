@@ -299,12 +299,6 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
   constexpr int NLR = W::REG_A ? W::TRI : 1, NDR = W::REG_A ? W::DIMMAX : 1;
   double Lr[NLR], Dr[NDR];
   const bool use_reg = W::REG_A && !requires_bcs; // uniform within a patch group
-#ifdef EQLB_WS_SKIP_CHOL // timing experiment (wrong results)
-  for (int i = 0; i < NLR; ++i)
-    Lr[i] = 1.0;
-  for (int i = 0; i < NDR; ++i)
-    Dr[i] = 1.0;
-#else
   if constexpr (W::REG_A)
   {
     if (use_reg)
@@ -363,8 +357,6 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
         wave_sync();
       }
     }
-#ifndef EQLB_WS_SKIP_Y
-#endif
   // ---- Y_k = L_k^-1 B_k: every lane forward-substitutes whole columns ----
   for (int col = sub; col < 2 * npnt; col += P)
   {
@@ -429,8 +421,6 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
     }
   }
   wave_sync();
-#ifndef EQLB_WS_SKIP_SCHUR
-#endif
   // ---- Schur complement C -= sum_k Y_k^T Y_k ----
   for (int e = sub; e < npnt * npnt; e += P)
   {
@@ -442,8 +432,6 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
     Cg[r * DCMAX + c] -= t;
   }
   wave_sync();
-#endif
-#ifndef EQLB_WS_SKIP_LU
   // ---- dense LU with partial pivoting of the (npnt [+1])^2 Schur system ----
   if constexpr (W::REG_LU)
   {
@@ -622,7 +610,6 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
       Rg[c] = gm[c];
   }
   wave_sync();
-#endif
   // ---- u_k = -L_k^-T (Y_k gamma) ----
   for (int e = sub; e < 2 * dim; e += P)
   {
@@ -717,9 +704,6 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
 // without pivoting - row of ring point sub + 1 in lane sub, row of the patch node in every lane, the
 // mean-value multiplier of interior patches analytically (see below).
 // 184 doubles of LDS per patch instead of 438.
-#ifndef EQLB_WS_LEAN_WAVES
-#define EQLB_WS_LEAN_WAVES 2
-#endif
 template <int P>
 struct WsLean
 {
@@ -1044,12 +1028,6 @@ __global__ void __launch_bounds__(256, EQLB_WS_LEAN_WAVES) k_se_weaksym_lean(con
       for (int c = 0; c <= NPT; ++c)
         rn[c] = (c == 0) ? 1.0 : 0.0;
     }
-#ifdef EQLB_WSL_SKIP_LU // timing experiment (wrong results)
-#pragma unroll
-    for (int c = 0; c < NPT; ++c)
-      gam[c] = rv[c] + rn[c];
-    g_own = rv[NPT];
-#else
     // elimination without pivoting: pivot 0 is the replicated node row, pivot p the row of lane p - 1
     {
       if (!(rn[0] > 0.0))
@@ -1093,7 +1071,6 @@ __global__ void __launch_bounds__(256, EQLB_WS_LEAN_WAVES) k_se_weaksym_lean(con
         t -= rn[c] * gam[c];
       gam[0] = t * rcp_d(rn[0]);
     }
-#endif
     if (meanvalue)
     {
       const double shift = (m0 * gam[0] + group_sum_d<P>(m_own * g_own, gb, sub)) * rcp_d(sum_m);

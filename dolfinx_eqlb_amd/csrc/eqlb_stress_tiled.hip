@@ -29,15 +29,6 @@
 //     mean-value multiplier is eliminated analytically: lambda = sum R / sum M, gamma_node := 0);
 //   * u_k = -A^-1 (B_k gamma) re-uses the multipliers of the cyclic reduction.
 #include "eqlb_device_common.h"
-#ifndef EQLB_STRESS_RING_BPERM
-#define EQLB_STRESS_RING_BPERM 1 // cyclic neighbours of full patches by ds_bpermute (2 per double) instead of two DPP moves + select per dword: 0.538 -> 0.531 ms
-#endif
-#ifndef EQLB_STRESS_REPCR
-#define EQLB_STRESS_REPCR 0
-#endif
-#ifndef EQLB_STRESS_REBUILD_B
-#define EQLB_STRESS_REBUILD_B 1
-#endif
 
 namespace eqlb
 {
@@ -54,37 +45,22 @@ namespace
 constexpr int SK = 2, SND = 3, SNQ = 3, SNH = 3, SNRT = 8, SNPK = 6;
 
 // ---- lane exchange inside a group of P lanes -------------------------------------------------------
-// FULL (every patch of the wave-block has exactly P cells and is interior): cyclic neighbours by DPP
-// row shifts; otherwise ds_bpermute with the lane computed at run time
+// FULL (every patch of the wave-block has exactly P cells and is interior): cyclic neighbours by ds_bpermute with a
+// lane that is arithmetic on sub (2 per double) instead of two DPP moves + select per dword: 0.538 -> 0.531 ms;
+// otherwise ds_bpermute with the lane computed at run time
 template <int P, bool FULL>
 __device__ __forceinline__ double from_prev(double v, int gbase, int sub, int prevl)
 {
-#if EQLB_STRESS_RING_BPERM
   if constexpr (FULL)
     return shfl_d(v, gbase + ((sub + P - 1) & (P - 1)));
-#else
-  if constexpr (FULL)
-  {
-    const double a = dpp_d<0x111>(v), b = dpp_d<0x100 + (P - 1)>(v);
-    return (sub == 0) ? b : a;
-  }
-#endif
   else
     return shfl_d(v, gbase + prevl);
 }
 template <int P, bool FULL>
 __device__ __forceinline__ double from_next(double v, int gbase, int sub, int nextl)
 {
-#if EQLB_STRESS_RING_BPERM
   if constexpr (FULL)
     return shfl_d(v, gbase + ((sub + 1) & (P - 1)));
-#else
-  if constexpr (FULL)
-  {
-    const double a = dpp_d<0x101>(v), b = dpp_d<0x110 + (P - 1)>(v);
-    return (sub == P - 1) ? b : a;
-  }
-#endif
   else
     return shfl_d(v, gbase + nextl);
 }
@@ -101,9 +77,6 @@ __device__ __forceinline__ void ldrow_pair(const double* p, double (&r)[2])
 // b: diagonal, am: coupling to row i - 1 (0 in lane 0), rows outside the chain are identity rows with
 // zero couplings; what a shift drags in from a neighbouring patch group is multiplied by an exact zero.
 // The multipliers of the levels are returned for later columns (pcr_apply).
-#ifndef EQLB_PCR_SELECTS
-#define EQLB_PCR_SELECTS 0 // see eqlb_se_kernels.hip
-#endif
 template <int P>
 struct PcrMult
 {
@@ -121,7 +94,7 @@ __device__ __forceinline__ void pcr_level(double& b, double& am, double (&r)[NC]
     const double ib = rcp_d(b);
     const double ib_lo = dpp_d<0x110 + S>(ib), a_lo = dpp_d<0x110 + S>(am);
     const double ib_hi = dpp_d<0x100 + S>(ib), a_hi = dpp_d<0x100 + S>(am);
-    const double cp = EQLB_PCR_SELECTS ? ((sub + S < P) ? a_hi : 0.0) : a_hi; // coupling to row i + S (eqlb_se_kernels.hip)
+    const double cp = a_hi; // coupling to row i + S; no select forces the zeros across the chain ends (eqlb_se_body.h)
     const double al = am * ib_lo, ga = cp * ib_hi;
     b = __builtin_fma(-ga, cp, __builtin_fma(-al, am, b));
 #pragma unroll
@@ -130,7 +103,7 @@ __device__ __forceinline__ void pcr_level(double& b, double& am, double (&r)[NC]
       const double lo = dpp_d<0x110 + S>(r[c]), hi = dpp_d<0x100 + S>(r[c]);
       r[c] = __builtin_fma(-ga, hi, __builtin_fma(-al, lo, r[c]));
     }
-    am = EQLB_PCR_SELECTS ? ((sub >= 2 * S) ? -al * a_lo : 0.0) : -al * a_lo;
+    am = -al * a_lo;
     m.al[L] = al;
     m.ga[L] = ga;
   }
@@ -181,10 +154,8 @@ __device__ __forceinline__ void pcr_apply(double (&r)[NC], const PcrMult<P>& m)
 // for the compiler to skip the zeros).  Stored by OFFSET - entry d of lane i belongs to ring point (i + d) mod P -
 // the three entries sit in the registers 0, 1, P - 1 of every lane, a level of the reduction with stride s reads
 // offset d + s from the lane s below and d - s from the lane s above (register indices fixed at compile time), and
-// the zeros are known: offsets farther than 2^l from 0 are still zero before level l.
-#ifndef EQLB_STRESS_ROTATED
-#define EQLB_STRESS_ROTATED 1
-#endif
+// the zeros are known: offsets farther than 2^l from 0 are still zero before level l.  (Against columns by ring
+// point: 0.3996 -> 0.3917 ms, profiles/r03_stress_rotated_revfma_ab.txt.)
 __host__ __device__ constexpr bool rot_nz(int P, int L, int d)
 {
   const int dd = ((d % P) + P) % P, dist = (dd < P - dd) ? dd : P - dd;
@@ -688,7 +659,7 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
     build_B(k, ci, (k == 0) ? J10 : -J00, (k == 0) ? J11 : -J01, Brow[k], bcn[k], Bd[k], Bdc[k]);
     // columns of B_k through the chain reduction: ring points, and the patch node on boundary patches
     constexpr int NCEN = INTK ? 0 : 1;
-    constexpr bool ROT = INTK && EQLB_STRESS_ROTATED;
+    constexpr bool ROT = INTK;
     double col[P + NCEN];
     if constexpr (ROT)
     {
@@ -774,7 +745,7 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
       rn[0] += group_sum_d<P>(bch * tn, gbase, sub) + qn0 * zn0 + qn1 * zn1;
     }
   }
-  if constexpr (INTK && EQLB_STRESS_ROTATED)
+  if constexpr (INTK)
   {
     // S[sub][c] = rotated[(c - sub) mod NR]: a rotation of the NR registers by `sub`, one conditional step per bit
 #pragma unroll
@@ -839,15 +810,12 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
       for (int c = 1; c <= NPT; ++c)
         rv[c] -= f * rn[c];
     }
-#ifndef EQLB_STRESS_GJ
-#define EQLB_STRESS_GJ 1
-#endif
-    if constexpr (EQLB_STRESS_GJ)
     {
       // Gauss-Jordan: the rows ABOVE the pivot are lanes that execute the row update anyway (their factor was a
       // forced zero), so eliminating there as well costs no instruction - and leaves every lane with its own
       // diagonal entry only: no back substitution, i.e. no second chain of eight dependent broadcasts and
-      // reciprocals.  (Full interior patches: the node multiplier is fixed to zero above, rn = e_0.)
+      // reciprocals.  (Full interior patches: the node multiplier is fixed to zero above, rn = e_0.)  Against forward
+      // elimination + back substitution: 0.3945 -> 0.3825 ms, profiles/r03_stress_gj_ab.txt
       double dinv = 1.0;
 #pragma unroll
       for (int p = 1; p < NPT; ++p)
@@ -880,44 +848,6 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
         gam0 = t * rcp_d(rn[0]);
       }
     }
-    else
-    {
-    double gam[NPT];
-#pragma unroll
-    for (int p = 1; p < NPT; ++p)
-    {
-      double pr[NPT + 1];
-#pragma unroll
-      for (int c = p; c <= NPT; ++c)
-        pr[c] = from_lane(rv[c], gbase + p - 1);
-      if (!(pr[p] > 0.0))
-        sing = 1;
-      const double f = (sub + 1 > p) ? rv[p] * rcp_d(pr[p]) : 0.0;
-#pragma unroll
-      for (int c = p + 1; c <= NPT; ++c)
-        rv[c] -= f * pr[c];
-    }
-    // back substitution
-#pragma unroll
-    for (int p = NPT - 1; p >= 1; --p)
-    {
-      double t = rv[NPT];
-#pragma unroll
-      for (int c = p + 1; c < NPT; ++c)
-        t -= rv[c] * gam[c];
-      t *= rcp_d(rv[p]);
-      if (sub + 1 == p)
-        gam_own = t;
-      gam[p] = from_lane(t, gbase + p - 1);
-    }
-    {
-      double t = rn[NPT];
-#pragma unroll
-      for (int c = 1; c < NPT; ++c)
-        t -= rn[c] * gam[c];
-      gam0 = t * rcp_d(rn[0]);
-    }
-    }
     if (meanvalue)
     {
       const double shift = (Mc * gam0 + group_sum_d<P>(Mr * gam_own, gbase, sub)) * rcp_d(sum_m);
@@ -936,7 +866,6 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
     const double g_prev = ring_prev(gam_own);
     const double g_next = ring_next(gam_own);
     double vr[2], vd[2];
-#if EQLB_STRESS_REBUILD_B
     // B_k is NOT carried across the Schur solve (12 doubles per lane at the point of the highest register
     // pressure): re-derived from the tensor and J; the opaque copies keep the compiler from merging the two
     // computations back into held values
@@ -946,7 +875,6 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
 #pragma unroll
     for (int k = 0; k < 2; ++k)
       build_B(k, ci2, (k == 0) ? j10 : -j00, (k == 0) ? j11 : -j01, Brow[k], bcn[k], Bd[k], Bdc[k]);
-#endif
 #pragma unroll
     for (int k = 0; k < 2; ++k)
     {
@@ -954,15 +882,7 @@ __device__ __forceinline__ void stress_patch_body(const SeArgs& a, const StressR
       vd[k] = -(group_sum_d<P>(Bd[k] * gam_own, gbase, sub) + Bdc[k] * gam0);
     }
     double cu[2] = {in_chain ? vr[0] : 0.0, in_chain ? vr[1] : 0.0};
-#if EQLB_STRESS_REPCR
-    {
-      bool pd2 = true;
-      PcrMult<P> m2;
-      pcr_chain<P, 2>(Dp_keep, am_keep, cu, sub, pd2, m2);
-    }
-#else
-    pcr_apply<P, 2>(cu, mult);
-#endif
+    pcr_apply<P, 2>(cu, mult); // (the stored multipliers of the first reduction)
 #pragma unroll
     for (int k = 0; k < 2; ++k)
     {
@@ -1012,15 +932,6 @@ __device__ __forceinline__ int xcd_remap2(int b, int n)
   return ((x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
 
-#ifndef EQLB_STRESS_THREADS
-#define EQLB_STRESS_THREADS 512
-#endif
-#ifndef EQLB_STRESS_WAVES
-#define EQLB_STRESS_WAVES 2 // waves per SIMD asked from the register allocator
-#endif
-#ifndef EQLB_STRESS_TILE_CELLS
-#define EQLB_STRESS_TILE_CELLS 524
-#endif
 // LARGEST tile: 2 rows x 524 x 18 doubles + 11.9 KB of tables = 159.3 KB; the body needs the whole register budget
 // of two waves per SIMD, so one 8-wave workgroup per CU is resident anyway and may use all of its LDS.  The
 // tile builder picks the size below this that fills whole rounds of the 256 workgroup slots (1M triangles:
@@ -1084,13 +995,13 @@ k_se_stress_tiled(const SeArgs a0, const TileArgs ta, const StressRows rows)
       int c0[3], c1[3];                                                                             \
       _Pragma("unroll") for (int j = 0; j < 3; ++j)                                                 \
         tile_nfix_range<PP>(td, B, j, c0[j], c1[j]);                                                \
-      if constexpr (EQLB_STRESS_NFIX && PP - 1 >= 3)                                                \
+      if constexpr (PP - 1 >= 3)                                                                    \
         for (int v = c0[0] + wave; v < c1[0]; v += NW)                                              \
           stress_patch_body<PP, false, PP - 1>(a, rows, lds, (int64_t)v * 64 + lane, sSlots, TC);   \
-      if constexpr (EQLB_STRESS_NFIX && PP - 2 >= 3)                                                \
+      if constexpr (PP - 2 >= 3)                                                                    \
         for (int v = c0[1] + ((wave + 3) & (NW - 1)); v < c1[1]; v += NW)                           \
           stress_patch_body<PP, false, (PP - 2 >= 3 ? PP - 2 : 0)>(a, rows, lds, (int64_t)v * 64 + lane, sSlots, TC); \
-      if constexpr (EQLB_STRESS_NFIX && PP - 3 >= 3)                                                \
+      if constexpr (PP - 3 >= 3)                                                                    \
         for (int v = c0[2] + ((wave + 5) & (NW - 1)); v < c1[2]; v += NW)                           \
           stress_patch_body<PP, false, (PP - 3 >= 3 ? PP - 3 : 0)>(a, rows, lds, (int64_t)v * 64 + lane, sSlots, TC); \
       /* everything else: the generic instance */                                                   \

@@ -1,0 +1,55 @@
+// The build parameters of the kernels: every macro a -D on the compiler's command line may override (tools/build_variant.sh),
+// each a number of size, occupancy or tolerance.  Code variants are not here: an experiment that was decided is
+// resolved in the source, with its figure at the code that won ("retired build switches").
+// tests/test_build_switches.py holds the sources to this list.
+#pragma once
+
+// ---- tiled flux launch (eqlb_se_tile.h) ----
+#ifndef EQLB_TILE_THREADS
+#define EQLB_TILE_THREADS 512 // k <= 2: 8 waves per tile, two workgroups per CU
+#endif
+#ifndef EQLB_TILE_THREADS_K3
+#define EQLB_TILE_THREADS_K3 512 // the k = 3 body runs at 2 waves/SIMD: ONE 8-wave workgroup per CU with the whole LDS
+#endif
+#ifndef EQLB_TILE_CELLS
+#define EQLB_TILE_CELLS 480 // 480 cells x 18 packed values + tables: two workgroups per CU (SE and EV)
+#endif
+#ifndef EQLB_TILE_CELLS_K3
+#define EQLB_TILE_CELLS_K3 492 // LARGEST tile: 492 cells x 36 packed values (141.7 KB) + 21.2 KB of tables (half of WQ) of the 160 KB: one workgroup per CU
+#endif
+#ifndef EQLB_TILE_CELLS_K3_EV
+#define EQLB_TILE_CELLS_K3_EV 468 // EV mode stages 7.2 KB more tensors (HG, WG)
+#endif
+#ifndef EQLB_PAIR_LANES
+#define EQLB_PAIR_LANES 1 // full 8-cell RT_2 patches on four lanes (eqlb_se_kernels_pair.hip); 0: the full-patch instance, 8 per wave-block, for every full patch (register report and A/B)
+#endif
+
+// ---- per-bin and fused flux launches (eqlb_se_launch.h) ----
+#ifndef EQLB_K4_WAVES
+#define EQLB_K4_WAVES 1 // waves per SIMD asked for the register-solver kernels at k = 4 (1: up to 512 registers)
+#endif
+#ifndef EQLB_FUSED_WAVES
+#define EQLB_FUSED_WAVES 4 // waves per SIMD asked for k_se_patch_fused at k <= 2
+#endif
+#ifndef EQLB_PERSIST_OVERSUB
+#define EQLB_PERSIST_OVERSUB 1 // persistent grid of k_se_patch_fused: this many times the resident workgroups of the device
+#endif
+
+// ---- tiled stress launch (eqlb_stress_tiled.hip) ----
+#ifndef EQLB_STRESS_THREADS
+#define EQLB_STRESS_THREADS 512 // threads of a workgroup of k_se_stress_tiled
+#endif
+#ifndef EQLB_STRESS_WAVES
+#define EQLB_STRESS_WAVES 2 // waves per SIMD asked from the register allocator
+#endif
+#ifndef EQLB_STRESS_TILE_CELLS
+#define EQLB_STRESS_TILE_CELLS 524 // largest stress tile (STRESS_TCMAX)
+#endif
+
+// ---- weak-symmetry kernels (eqlb_se_weaksym*.hip) ----
+#ifndef EQLB_WS_LEAN_WAVES
+#define EQLB_WS_LEAN_WAVES 2 // waves per SIMD asked for k_se_weaksym_lean
+#endif
+#ifndef EQLB_WS_PIVOT_RTOL
+#define EQLB_WS_PIVOT_RTOL 1e-11 // relative size (against the largest entry of the Schur system) below which a pivot counts as zero
+#endif

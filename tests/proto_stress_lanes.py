@@ -73,7 +73,7 @@ def element_data(mesh, tab, fan, node, c0, c1):
 def pcr_solve(P, Dp, OffC, cols):
     """Parallel cyclic reduction of the chain: Dp diagonal, OffC[i] coupling of row i to row i + 1;
     rows outside the chain are identity rows with zero couplings.  cols [ncol, P] right-hand sides
-    (zero outside the chain).  The level structure of EQLB_PCR_LEVEL in eqlb_se_kernels.hip."""
+    (zero outside the chain).  The level structure of EQLB_PCR_LEVEL in eqlb_se_body.h."""
     b = Dp.copy()
     am = np.concatenate([[0.0], OffC[:-1]])  # coupling to row i - 1
     r = cols.copy()

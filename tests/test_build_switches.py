@@ -1,0 +1,91 @@
+"""Source lint of dolfinx_eqlb_amd/csrc: no file includes a .hip, and the EQLB_* names a -D on the
+compiler's command line can override are exactly those declared in eqlb_tuning.h (numeric
+parameters of size, occupancy and tolerance; decided code variants are resolved in the source,
+DESIGN.md "retired build switches")."""
+
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "dolfinx_eqlb_amd", "csrc")
+TUNING = "eqlb_tuning.h"
+
+# Names that the rules below find but that are no build parameters:
+#   include guards: none in csrc (its headers use #pragma once)
+#   function-like helper macros: defined unconditionally, so the rules do not find them
+#   the platform test of eqlb_pair_chain.h, which the host emulation (tools/pair_chain_emul.cpp) includes too:
+#   its function qualifier is defined under "#ifndef EQLB_PC_FN"
+EXCLUDED = {"EQLB_PC_FN"}
+
+
+def _sources():
+    # (eqlb_tables_build_gen.h: written by the build, literals only)
+    files = [f for f in glob.glob(os.path.join(CSRC, "*")) if f.endswith((".hip", ".h", ".cpp", ".hpp"))]
+    assert len(files) > 30
+    return {os.path.basename(f): open(f).read() for f in sorted(files)}
+
+
+def _strip_comments(text):
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def _directives(text):
+    """(directive, rest) of every preprocessor line, continuation lines joined"""
+    text = _strip_comments(text).replace("\\\n", " ")
+    return re.findall(r"^[ \t]*#[ \t]*(\w+)\b[ \t]*(.*)$", text, flags=re.M)
+
+
+def _overridable(text):
+    """EQLB_* names tested by #if / #ifdef / #ifndef / #elif / defined(), or #defined under an #ifndef of themselves"""
+    names, guard = set(), []
+    for d, rest in _directives(text):
+        if d in ("if", "ifdef", "ifndef", "elif"):
+            names |= set(re.findall(r"\bEQLB_\w+", rest))
+        if d in ("if", "ifdef", "ifndef"):
+            guard.append(rest.split()[0] if d == "ifndef" and rest.split() else None)
+        elif d == "endif":
+            guard.pop()
+        elif d == "define":
+            m = re.match(r"(EQLB_\w+)", rest)
+            if m and m.group(1) in guard:
+                names.add(m.group(1))
+    return names
+
+
+def _defined(text):
+    return {m.group(1) for d, rest in _directives(text) if d == "define" for m in [re.match(r"(EQLB_\w+)", rest)] if m}
+
+
+def test_no_file_includes_a_hip():
+    for name, text in _sources().items():
+        for d, rest in _directives(text):
+            assert not (d == "include" and ".hip" in rest), f"{name}: #include {rest}"
+
+
+def test_overridable_names_are_those_of_the_tuning_header():
+    src = _sources()
+    declared = _overridable(src[TUNING])
+    assert declared and declared == _defined(src[TUNING])
+    found = set()
+    for text in src.values():
+        found |= _overridable(text)
+    assert found - EXCLUDED == declared, sorted((found - EXCLUDED) ^ declared)
+
+
+def test_parameters_are_defined_in_the_tuning_header_only():
+    src = _sources()
+    declared = _overridable(src[TUNING])
+    for name, text in src.items():
+        if name != TUNING:
+            assert not (_defined(text) & declared), f"{name}: {sorted(_defined(text) & declared)}"
+
+
+def test_every_parameter_is_used():
+    src = _sources()
+    used = set()
+    for name, text in src.items():
+        if name != TUNING:
+            used |= set(re.findall(r"\bEQLB_\w+", _strip_comments(text)))
+    assert _overridable(src[TUNING]) <= used

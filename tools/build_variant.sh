@@ -1,5 +1,6 @@
 #!/bin/bash
-# build_variant.sh NAME "-DFOO -DBAR": timing-experiment build of libeqlb_amd.so into build_exp/lib_NAME.so
+# build_variant.sh NAME "-DFOO=1 -DBAR=2": timing-experiment build of libeqlb_amd.so into build_exp/lib_NAME.so with other
+# values of the build parameters (csrc/eqlb_tuning.h)
 # (only eqlb_se_kernels.hip is recompiled; run with EQLB_AMD_LIB=build_exp/lib_NAME.so python bench.py)
 set -e
 cd "$(dirname "$0")/.."
