@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_se_get_boundary_values", "eqlb_ev_get_boundary_values",
     "eqlb_mesh_create_from_cells", "eqlb_mesh_counts", "eqlb_mesh_export", "eqlb_mesh_boundary_facets",
     "eqlb_mesh_find_facets",
+    "eqlb_mesh_refine_plan", "eqlb_refine_counts", "eqlb_refine_write", "eqlb_refine_create_mesh",
+    "eqlb_refine_parent_facets", "eqlb_refine_destroy",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -164,6 +166,8 @@ def lib():
         for name in ("eqlb_mesh_destroy", "eqlb_se_destroy", "eqlb_ev_destroy", "eqlb_halo_destroy",
                      "eqlb_rccl_comm_destroy"):
             getattr(L, name).restype = None
+        if hasattr(L, "eqlb_refine_destroy"):   # (a library of an earlier revision, EQLB_AMD_LIB: A/B runs of bench.py)
+            L.eqlb_refine_destroy.restype = None
         _lib = L
     return _lib
 
@@ -306,6 +310,52 @@ class DeviceMesh:
         _check(lib().eqlb_mesh_find_facets(self._h, C.c_int32(npairs), _vp(pairs), _vp(facets), C.c_int32(memspace),
                                            C.c_void_p(stream)))
 
+    def refine_raw(self, marked, nmarked, capacity, memspace=MEM_DEVICE, stream=0):
+        """eqlb_mesh_refine_plan on raw pointers (ints) in `memspace`: the marked list and its int64 length exactly as
+        mark_doerfler_raw leaves them.  Returns a RefinePlan; this mesh must outlive it."""
+        return RefinePlan(self, marked, nmarked, capacity, memspace, stream)
+
+    def refine(self, marked, device=False, stream=0):
+        """The mesh refined at the cells `marked` by longest-edge closure and bisection, on the device
+        (eqlb_mesh_refine_plan ...; the rule: mesh.refine.refine_longest_edge).  Returns a Refinement: `.dmesh` (the new
+        DeviceMesh, `.mesh` filled as from_cells does), `.parent_cell`, `.node_parent_facet`, `.parent_facet`, `.counts`.
+        device=False: `marked` is a host array of cell ids.  device=True: `marked` is a pair (ids, count) of torch
+        tensors on the device (int32 [capacity], int64 [1]) as mark_doerfler_raw leaves them, read on `stream`; the
+        parent arrays come back as device tensors."""
+        from .mesh import Mesh
+        if device:
+            import torch
+            ids, count = marked
+            if ids.element_size() != 4 or count.element_size() != 8 or not ids.is_contiguous():
+                raise RuntimeError("DeviceMesh.refine: contiguous int32 ids and an int64 count expected")
+            plan = self.refine_raw(ids.data_ptr(), count.data_ptr(), int(ids.numel()), MEM_DEVICE, stream)
+        else:
+            ids = np.ascontiguousarray(marked, dtype=np.int32).ravel()
+            count = np.array([ids.size], dtype=np.int64)
+            plan = self.refine_raw(ids.ctypes.data, count.ctypes.data, ids.size, MEM_HOST, stream)
+        try:
+            nn2, nc2, nbis, ncut = plan.counts()
+            hx = np.zeros((nn2, 3))
+            hc = np.zeros((nc2, 3), dtype=np.int32)
+            dm = plan.create_mesh(stream)
+            nf2 = dm.counts()[2]
+            if device:
+                pc, npf, pf = [torch.empty(n, dtype=torch.int32, device=ids.device) for n in (nc2, nbis, nf2)]
+                plan.write_raw(None, None, pc.data_ptr(), npf.data_ptr(), MEM_DEVICE, stream)
+                plan.parent_facets_raw(dm, pf.data_ptr(), MEM_DEVICE, stream)
+                plan.write_raw(hx.ctypes.data, hc.ctypes.data, None, None, MEM_HOST, stream)   # (waits for `stream`)
+            else:
+                pc, npf, pf = [np.zeros(n, dtype=np.int32) for n in (nc2, nbis, nf2)]
+                plan.write_raw(hx.ctypes.data, hc.ctypes.data, pc.ctypes.data, npf.ctypes.data, MEM_HOST, stream)
+                plan.parent_facets_raw(dm, pf.ctypes.data, MEM_HOST, stream)
+        finally:
+            plan.close()
+        t = dm.export()
+        dm.mesh = Mesh(hx, hc, t["cell_facets"], t["facet_nodes"], t["facet_cells_offsets"], t["facet_cells"],
+                       t["node_cells_offsets"], t["node_cells"], t["node_facets_offsets"], t["node_facets"],
+                       t["facet_perm"])
+        return Refinement(dm, pc, npf, pf, {"nnodes2": nn2, "ncells2": nc2, "nbisected": nbis, "ncells_cut": ncut})
+
     @property
     def max_patch_cells(self):
         return int(lib().eqlb_mesh_max_patch_cells(self._h))
@@ -320,6 +370,62 @@ class DeviceMesh:
             self.close()
         except Exception:
             pass
+
+
+class RefinePlan:
+    """eqlb_refine_t: closure and scans of a refinement, kept on the device (DeviceMesh.refine_raw)."""
+
+    def __init__(self, dmesh, marked, nmarked, capacity, memspace, stream):
+        self.dmesh = dmesh   # the plan reads the handle: keep it alive
+        self._h = C.c_void_p()
+        _check(lib().eqlb_mesh_refine_plan(dmesh._h, _vp(marked), _vp(nmarked), C.c_int64(capacity),
+                                           C.c_int32(memspace), C.c_void_p(stream), C.byref(self._h)))
+
+    def counts(self):
+        """(nnodes2, ncells2, nbisected, ncells_cut) (eqlb_refine_counts)."""
+        v = [C.c_int32(0) for _ in range(4)]
+        _check(lib().eqlb_refine_counts(self._h, *[C.byref(a) for a in v]))
+        return tuple(int(a.value) for a in v)
+
+    def write_raw(self, x2, cell_nodes2, parent_cell, node_parent_facet, memspace=MEM_DEVICE, stream=0):
+        """eqlb_refine_write on raw pointers (ints, None for an output that is not wanted) in `memspace`."""
+        _check(lib().eqlb_refine_write(self._h, _vp(x2), _vp(cell_nodes2), _vp(parent_cell), _vp(node_parent_facet),
+                                       C.c_int32(memspace), C.c_void_p(stream)))
+
+    def create_mesh(self, stream=0):
+        """eqlb_refine_create_mesh: the DeviceMesh of the refined mesh (`.mesh` is not filled)."""
+        dm = DeviceMesh.__new__(DeviceMesh)
+        dm._h = C.c_void_p()
+        dm.mesh = None
+        _check(lib().eqlb_refine_create_mesh(self._h, C.c_void_p(stream), C.byref(dm._h)))
+        return dm
+
+    def parent_facets_raw(self, refined, parent_facet, memspace=MEM_DEVICE, stream=0):
+        """eqlb_refine_parent_facets on a raw pointer [nfacets of `refined`] in `memspace`."""
+        _check(lib().eqlb_refine_parent_facets(self._h, refined._h, _vp(parent_facet), C.c_int32(memspace),
+                                               C.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib().eqlb_refine_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Refinement:
+    """Result of DeviceMesh.refine: the refined DeviceMesh and the parent tables (host arrays or device tensors)."""
+
+    def __init__(self, dmesh, parent_cell, node_parent_facet, parent_facet, counts):
+        self.dmesh = dmesh
+        self.parent_cell = parent_cell
+        self.node_parent_facet = node_parent_facet
+        self.parent_facet = parent_facet
+        self.counts = counts
 
 
 class SemiExplicitEquilibrator:
@@ -847,8 +953,9 @@ def mark_doerfler(cell_eta2, theta: float):
     """eqlb_mark_doerfler on a host array of non-negative indicators [ncells].  Returns (marked, eta2_total): the
     sorted int32 ids of the shortest list of cells, largest indicators first and equal ones in ascending id, whose
     sum exceeds theta * eta2_total (every cell if theta is 1 within 1e-8), and the sum of the indicators.  The
-    list goes to the refiner as it is, e.g. mesh.compute_incident_entities(mesh, marked, 2, 1)
-    (eqlb.doerfler_marking is the numpy statement)."""
+    list goes to the refiner as it is: DeviceMesh.refine(marked) refines on the device (from device memory:
+    mark_doerfler_raw, then DeviceMesh.refine_raw on the same two pointers); a DOLFINx caller who refines on the host
+    passes it to mesh.compute_incident_entities(mesh, marked, 2, 1) (eqlb.doerfler_marking is the numpy statement)."""
     eta = np.ascontiguousarray(cell_eta2, dtype=np.float64).ravel()
     marked = np.empty(max(eta.size, 1), dtype=np.int32)
     nmarked, total = C.c_int64(0), C.c_double(0.0)

@@ -109,16 +109,34 @@ struct Mesh
     m->cell_nodes.assign(cn.data(), cn.data() + cn.size());
     check(eqlb_mesh_create_from_cells(m->nnodes, m->ncells, m->x.data(), m->cell_nodes.data(), EQLB_MEM_HOST, nullptr,
                                       &m->h));
-    check(eqlb_mesh_counts(m->h, nullptr, nullptr, &m->nfacets));
-    m->cell_facets.resize(3 * (size_t)m->ncells);
-    m->facet_nodes.resize(2 * (size_t)m->nfacets);
-    m->facet_cells_off.resize((size_t)m->nfacets + 1);
-    m->facet_cells.resize(3 * (size_t)m->ncells);
-    m->facet_perm.resize(3 * (size_t)m->ncells);
-    check(eqlb_mesh_export(m->h, m->cell_facets.data(), m->facet_nodes.data(), m->facet_cells_off.data(),
-                           m->facet_cells.data(), nullptr, nullptr, nullptr, nullptr, m->facet_perm.data(),
-                           EQLB_MEM_HOST, nullptr));
+    m->export_tables();
     return m;
+  }
+
+  // the mesh refined at the cells `marked` on the device (eqlb_mesh_refine_plan ...): the new Mesh, parent_cell,
+  // node_parent_facet, parent_facet
+  py::tuple refine(carray<int32_t> marked) const
+  {
+    struct Plan
+    {
+      eqlb_refine_t* p = nullptr;
+      ~Plan() { eqlb_refine_destroy(p); }
+    } plan;
+    const int64_t nmarked = (int64_t)marked.size();
+    check(eqlb_mesh_refine_plan(h, marked.data(), &nmarked, nmarked, EQLB_MEM_HOST, nullptr, &plan.p));
+    std::shared_ptr<Mesh> m(new Mesh());
+    int32_t nbis = 0;
+    check(eqlb_refine_counts(plan.p, &m->nnodes, &m->ncells, &nbis, nullptr));
+    m->x.resize(3 * (size_t)m->nnodes);
+    m->cell_nodes.resize(3 * (size_t)m->ncells);
+    py::array_t<int32_t> parent_cell(m->ncells), node_parent_facet(nbis);
+    check(eqlb_refine_write(plan.p, m->x.data(), m->cell_nodes.data(), parent_cell.mutable_data(),
+                            node_parent_facet.mutable_data(), EQLB_MEM_HOST, nullptr));
+    check(eqlb_refine_create_mesh(plan.p, nullptr, &m->h));
+    m->export_tables();
+    py::array_t<int32_t> parent_facet(m->nfacets);
+    check(eqlb_refine_parent_facets(plan.p, m->h, parent_facet.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return py::make_tuple(m, parent_cell, node_parent_facet, parent_facet);
   }
 
   py::array_t<int32_t> boundary_facets() const
@@ -141,6 +159,19 @@ struct Mesh
 
 private:
   Mesh() = default;
+
+  // nfacets and the host tables of a handle built on the device
+  void export_tables()
+  {
+    check(eqlb_mesh_counts(h, nullptr, nullptr, &nfacets));
+    cell_facets.resize(3 * (size_t)ncells);
+    facet_nodes.resize(2 * (size_t)nfacets);
+    facet_cells_off.resize((size_t)nfacets + 1);
+    facet_cells.resize(3 * (size_t)ncells);
+    facet_perm.resize(3 * (size_t)ncells);
+    check(eqlb_mesh_export(h, cell_facets.data(), facet_nodes.data(), facet_cells_off.data(), facet_cells.data(),
+                           nullptr, nullptr, nullptr, nullptr, facet_perm.data(), EQLB_MEM_HOST, nullptr));
+  }
 
 public:
 
@@ -925,6 +956,15 @@ PYBIND11_MODULE(_cpp, m)
       .def("boundary_facets", &Mesh::boundary_facets, "ids of the facets with one cell, ascending")
       .def("find_facets", &Mesh::find_facets, py::arg("pairs"),
            "facet id of every node pair [npairs, 2] (either order), -1 where the pair is no edge")
+      .def("refine", &Mesh::refine, py::arg("marked"),
+           "(Mesh, parent_cell, node_parent_facet, parent_facet) of the mesh refined at the marked cells by longest-edge "
+           "closure and bisection, on the device")
+      .def_property_readonly("x", [](const Mesh& s) {
+        return py::array_t<double>({(py::ssize_t)s.nnodes, (py::ssize_t)3}, s.x.data());
+      })
+      .def_property_readonly("cell_nodes", [](const Mesh& s) {
+        return py::array_t<int32_t>({(py::ssize_t)s.ncells, (py::ssize_t)3}, s.cell_nodes.data());
+      })
       .def_readonly("nnodes", &Mesh::nnodes)
       .def_readonly("ncells", &Mesh::ncells)
       .def_readonly("nfacets", &Mesh::nfacets)

@@ -208,3 +208,6 @@ def create_disk(nsectors: int, nrings: int, shuffle_seed=None, radius: float = 1
     if shuffle_seed is not None:
         cells = _shuffle_local_order(cells, shuffle_seed)
     return create_mesh(x, cells)
+
+
+from .refine import parent_facets, refine_longest_edge  # noqa: E402,F401  (the statement of eqlb_mesh_refine_plan)

@@ -624,6 +624,83 @@ int eqlb_indicator_total(int64_t ncells, int32_t nterms, const double* const* te
 int eqlb_mark_doerfler(int64_t ncells, const double* cell_eta2, double theta, int32_t* marked, int64_t* nmarked,
                        double* eta2_total, int32_t memspace, void* stream);
 
+/*
+ * Refinement of the marked cells on the device - the step after the marking in the reference's adaptive demos
+ * (demo/poisson_adaptive/demo_lshape.py, demo_discont-coeff.py, demo/elasticity_adaptive/demo_cook.py:
+ * mesh.compute_incident_entities(mesh, marked, 2, 1), mesh.refine(mesh, edges), then the mesh information again).  The
+ * numbering of mesh.refine cannot be pinned, so dolfinx_eqlb_amd.mesh.refine.refine_longest_edge states the result in
+ * numpy and these entries reproduce it bit for bit.  The rule, in the facet ids of the handle:
+ *   length   len2[f] = dx * dx + dy * dy with dx = x[hi] - x[lo], dy likewise, from the two nodes of facet_nodes[f];
+ *            every operation is rounded on its own (no fused multiply-add)
+ *   order    facet f is longer than g if len2[f] > len2[g], or if they are equal and f < g.  The order is global and
+ *            strict: both cells of a facet agree on it.  L(c) is the longest facet of cell c, l(c) its local index
+ *   seed     E0 = every facet of every marked cell (duplicates in the list are allowed, its order does not matter)
+ *   closure  the smallest set E that contains E0 such that every cell with a facet in E has L(c) in E.  With succ(c)
+ *            the other cell of L(c) (c itself on the boundary) and A the cells reachable along succ from the cells with
+ *            a facet in E0: E = E0 and L(c) for c in A.  A is found by pointer doubling in ceil(log2(ncells)) passes, so
+ *            the number of launches depends on ncells alone
+ *   nodes    one per facet of E: node nnodes + (rank of the facet among E in ascending facet id) at
+ *            0.5 * (x[lo] + x[hi]), all three components
+ *   cells    a cell without a facet in E is copied.  Otherwise, with l = l(c), a = v[l], b = v[(l+1)%3], c' = v[(l+2)%3],
+ *            m the new node of local facet l, q that of local facet (l+1)%3 and p that of (l+2)%3 where those facets
+ *            are in E, the children are (a,p,m), (p,b,m) if p exists, else (a,b,m); then (a,m,q), (q,m,c') if q exists,
+ *            else (a,m,c') - in the orientation of the parent.  The children of cell c start at the exclusive prefix
+ *            sum of 1 + (number of its facets in E)
+ * With every cell marked this is the longest-edge 4-split; the red refinement DOLFINx applies when everything is
+ * refined is not provided.  Coarsening and distributed meshes (the closure would cross ranks) are not provided either.
+ * Integer work, the lengths and the midpoints; no sort, no floating-point atomics: two calls give the same bits.
+ */
+typedef struct eqlb_refine eqlb_refine_t;
+
+/* Closure and scans: replaces compute_incident_entities and the marking half of mesh.refine.
+ *   marked   [capacity]  cell ids; the first *nmarked entries are read
+ *   nmarked  [1]         both in `memspace`, exactly as eqlb_mark_doerfler leaves them
+ *   stream   hipStream_t (NULL = default stream): everything is enqueued there and the call WAITS ONCE, for the counts
+ *            that size the outputs; the flag and offset arrays stay on the device in the plan
+ * The handle may come from eqlb_mesh_create or eqlb_mesh_create_from_cells; it is only read and must outlive the plan.
+ * *nmarked == 0 is valid: the result is the mesh itself.
+ * Refusals (EQLB_ERR_INVALID_ARGUMENT; *plan is not written, the next valid call works):
+ *   null arguments, capacity < 0, an unknown memory space
+ *   *nmarked < 0 - the -1 that eqlb_mark_doerfler writes for a negative or NaN indicator included; *nmarked > capacity
+ *   a marked id outside [0, ncells): the message names the lowest such id; no id addresses memory before it is checked
+ *   3 * ncells2 > INT32_MAX (the limit of eqlb_mesh_create_from_cells)
+ * In the device memory space the list and its length are checked by the kernels and reported after the one wait. */
+int eqlb_mesh_refine_plan(eqlb_mesh_t* mesh, const int32_t* marked, const int64_t* nmarked, int64_t capacity,
+                          int32_t memspace, void* stream, eqlb_refine_t** plan);
+
+/* Sizes of the result; any output may be NULL.  nnodes2 = nnodes + nbisected; ncells_cut: cells with a facet in E. */
+int eqlb_refine_counts(const eqlb_refine_t* plan, int32_t* nnodes2, int32_t* ncells2, int32_t* nbisected,
+                       int32_t* ncells_cut);
+
+/* The refined mesh in the form eqlb_mesh_create_from_cells takes, and the parent tables - the output half of
+ * mesh.refine.  Any output may be NULL.
+ *   x2                 [nnodes2][3]         the old nodes first, unchanged, then the midpoints
+ *   cell_nodes2        [ncells2][3]
+ *   parent_cell        [ncells2]            cell of the old mesh a new cell came from (non-decreasing)
+ *   node_parent_facet  [nnodes2 - nnodes]   old facet a new node bisects; P1 prolongation is (u[lo] + u[hi]) / 2
+ * Device memory space: enqueued on `stream`, nothing waits.  Host memory space: staged, synchronous. */
+int eqlb_refine_write(eqlb_refine_t* plan, double* x2, int32_t* cell_nodes2, int32_t* parent_cell,
+                      int32_t* node_parent_facet, int32_t memspace, void* stream);
+
+/* The handle of the refined mesh (FluxEquilibrator.initialise_mesh_info after mesh.refine): coordinates and cells are
+ * written into device arrays of the call and handed to the device-memory path of eqlb_mesh_create_from_cells, so they
+ * never visit the host on this route.  Waits as that call does.  Destroy *refined with eqlb_mesh_destroy. */
+int eqlb_refine_create_mesh(eqlb_refine_t* plan, void* stream, eqlb_mesh_t** refined);
+
+/* parent_facet [nfacets2] in `memspace`, in the facet numbering of `refined` (a handle of the refined mesh, from
+ * eqlb_refine_create_mesh or built by the caller from the output of eqlb_refine_write):
+ *   the old facet, if the new facet is an unbisected old facet
+ *   the bisected old facet, if exactly one end is a new node and the other is an end of the facet that node bisects
+ *   -1 otherwise (the new interior edges)
+ * facet_type of eqlb_se_set_boundary on the new mesh is then a gather: new[f] = parent_facet[f] < 0 ? 0 :
+ * old[parent_facet[f]] - what a DOLFINx caller gets from transferring facet tags.  One thread per new facet; an old
+ * facet is looked up by walking the facets of its first node as eqlb_mesh_find_facets does.  Device memory space: one
+ * kernel on `stream`, nothing waits; host memory space: staged, synchronous. */
+int eqlb_refine_parent_facets(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t* parent_facet, int32_t memspace,
+                              void* stream);
+
+void eqlb_refine_destroy(eqlb_refine_t* plan);
+
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the
  * partial sums of the ghost-cell rows are sent to the owning rank and added there.  DEVICE pointers:
