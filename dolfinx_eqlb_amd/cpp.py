@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_mesh_find_facets",
     "eqlb_mesh_refine_plan", "eqlb_refine_counts", "eqlb_refine_write", "eqlb_refine_create_mesh",
     "eqlb_refine_parent_facets", "eqlb_refine_destroy",
+    "eqlb_mesh_lagrange_dofmap", "eqlb_get_prolong_table", "eqlb_refine_prolong_lagrange", "eqlb_refine_prolong_dg",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -310,18 +311,40 @@ class DeviceMesh:
         _check(lib().eqlb_mesh_find_facets(self._h, C.c_int32(npairs), _vp(pairs), _vp(facets), C.c_int32(memspace),
                                            C.c_void_p(stream)))
 
+    def lagrange_dofmap_raw(self, p, cell_dofs, memspace=MEM_DEVICE, stream=0):
+        """eqlb_mesh_lagrange_dofmap on a raw pointer [ncells, nd_p] int32 in `memspace`; returns ndofs."""
+        n = C.c_int64(0)
+        _check(lib().eqlb_mesh_lagrange_dofmap(self._h, C.c_int32(p), _vp(cell_dofs), C.byref(n), C.c_int32(memspace),
+                                               C.c_void_p(stream)))
+        return int(n.value)
+
+    def lagrange_dofmap(self, p, device=False, stream=0):
+        """(cell_dofs [ncells, nd_p] int32, ndofs) of the conforming P_p space, 1 <= p <= 4, in the numbering of
+        mesh.transfer.lagrange_dofmap (eqlb_mesh_lagrange_dofmap): what primal_flux_dg and Refinement.prolong take on
+        a handle that has no dofmap of the caller's.  device=True: a torch tensor on the device, written on `stream`."""
+        nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2
+        nc = self.counts()[1]
+        if device:
+            import torch
+            cd = torch.empty((nc, nd), dtype=torch.int32, device="cuda")
+            return cd, self.lagrange_dofmap_raw(p, cd.data_ptr(), MEM_DEVICE, stream)
+        cd = np.zeros((nc, nd), dtype=np.int32)
+        return cd, self.lagrange_dofmap_raw(p, cd.ctypes.data, MEM_HOST, stream)
+
     def refine_raw(self, marked, nmarked, capacity, memspace=MEM_DEVICE, stream=0):
         """eqlb_mesh_refine_plan on raw pointers (ints) in `memspace`: the marked list and its int64 length exactly as
         mark_doerfler_raw leaves them.  Returns a RefinePlan; this mesh must outlive it."""
         return RefinePlan(self, marked, nmarked, capacity, memspace, stream)
 
-    def refine(self, marked, device=False, stream=0):
+    def refine(self, marked, device=False, stream=0, keep_plan=False):
         """The mesh refined at the cells `marked` by longest-edge closure and bisection, on the device
         (eqlb_mesh_refine_plan ...; the rule: mesh.refine.refine_longest_edge).  Returns a Refinement: `.dmesh` (the new
         DeviceMesh, `.mesh` filled as from_cells does), `.parent_cell`, `.node_parent_facet`, `.parent_facet`, `.counts`.
         device=False: `marked` is a host array of cell ids.  device=True: `marked` is a pair (ids, count) of torch
         tensors on the device (int32 [capacity], int64 [1]) as mark_doerfler_raw leaves them, read on `stream`; the
-        parent arrays come back as device tensors."""
+        parent arrays come back as device tensors.
+        keep_plan=True keeps the plan open on the Refinement (`.plan`), so that Refinement.prolong / prolong_dg can
+        carry solutions and DG data over; Refinement.close() releases it.  This mesh must outlive it."""
         from .mesh import Mesh
         if device:
             import torch
@@ -348,13 +371,17 @@ class DeviceMesh:
                 pc, npf, pf = [np.zeros(n, dtype=np.int32) for n in (nc2, nbis, nf2)]
                 plan.write_raw(hx.ctypes.data, hc.ctypes.data, pc.ctypes.data, npf.ctypes.data, MEM_HOST, stream)
                 plan.parent_facets_raw(dm, pf.ctypes.data, MEM_HOST, stream)
-        finally:
+        except BaseException:
+            plan.close()
+            raise
+        if not keep_plan:
             plan.close()
         t = dm.export()
         dm.mesh = Mesh(hx, hc, t["cell_facets"], t["facet_nodes"], t["facet_cells_offsets"], t["facet_cells"],
                        t["node_cells_offsets"], t["node_cells"], t["node_facets_offsets"], t["node_facets"],
                        t["facet_perm"])
-        return Refinement(dm, pc, npf, pf, {"nnodes2": nn2, "ncells2": nc2, "nbisected": nbis, "ncells_cut": ncut})
+        return Refinement(dm, pc, npf, pf, {"nnodes2": nn2, "ncells2": nc2, "nbisected": nbis, "ncells_cut": ncut},
+                          plan if keep_plan else None)
 
     @property
     def max_patch_cells(self):
@@ -405,6 +432,19 @@ class RefinePlan:
         _check(lib().eqlb_refine_parent_facets(self._h, refined._h, _vp(parent_facet), C.c_int32(memspace),
                                                C.c_void_p(stream)))
 
+    def prolong_lagrange_raw(self, refined, p, bs, nrhs, cell_dofs, ndofs, u, cell_dofs2, ndofs2, u2,
+                             memspace=MEM_DEVICE, stream=0):
+        """eqlb_refine_prolong_lagrange on raw pointers (ints) in `memspace`: u [nrhs, ndofs*bs] of the P_p space on
+        the mesh of the plan -> u2 [nrhs, ndofs2*bs] on `refined`, through the caller's dofmaps."""
+        _check(lib().eqlb_refine_prolong_lagrange(self._h, refined._h, C.c_int32(p), C.c_int32(bs), C.c_int32(nrhs),
+                                                  _vp(cell_dofs), C.c_int64(ndofs), _vp(u), _vp(cell_dofs2),
+                                                  C.c_int64(ndofs2), _vp(u2), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def prolong_dg_raw(self, refined, degree, bs, nrhs, values, out, memspace=MEM_DEVICE, stream=0):
+        """eqlb_refine_prolong_dg on raw pointers (ints) in `memspace`: [nrhs, ncells*nd*bs] -> [nrhs, ncells2*nd*bs]."""
+        _check(lib().eqlb_refine_prolong_dg(self._h, refined._h, C.c_int32(degree), C.c_int32(bs), C.c_int32(nrhs),
+                                            _vp(values), _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
     def close(self):
         if self._h:
             lib().eqlb_refine_destroy(self._h)
@@ -420,12 +460,100 @@ class RefinePlan:
 class Refinement:
     """Result of DeviceMesh.refine: the refined DeviceMesh and the parent tables (host arrays or device tensors)."""
 
-    def __init__(self, dmesh, parent_cell, node_parent_facet, parent_facet, counts):
+    def __init__(self, dmesh, parent_cell, node_parent_facet, parent_facet, counts, plan=None):
         self.dmesh = dmesh
         self.parent_cell = parent_cell
         self.node_parent_facet = node_parent_facet
         self.parent_facet = parent_facet
         self.counts = counts
+        self.plan = plan   # the open RefinePlan of DeviceMesh.refine(..., keep_plan=True), else None
+
+    def _kept_plan(self, who):
+        if self.plan is None or not self.plan._h:
+            raise RuntimeError(f"Refinement.{who}: the plan of the refinement was not kept "
+                               "(DeviceMesh.refine(..., keep_plan=True)) or is closed")
+        return self.plan
+
+    def prolong(self, p, u, cell_dofs=None, cell_dofs2=None, bs=1, ndofs2=None, out=None, stream=0):
+        """u [nrhs, ndofs*bs] (or [ndofs*bs]) in P_p on the old mesh -> [nrhs, ndofs2*bs] on the refined mesh
+        (eqlb_refine_prolong_lagrange; the rule: mesh.transfer.prolong_lagrange).  Host arrays, or torch tensors on the
+        device, which are read and written on `stream`.  cell_dofs / cell_dofs2: the caller's dofmaps, None:
+        lagrange_dofmap of the two handles; ndofs2: size of the new space (None: that of lagrange_dofmap, or max + 1
+        of a host cell_dofs2 - required with a caller's dofmap on the device).  Every DOF of cell_dofs2 is written,
+        the other entries keep what `out` holds (None: zeros)."""
+        plan = self._kept_plan("prolong")
+        dev = hasattr(u, "data_ptr")
+        nd = (p + 1) * (p + 2) // 2
+        if cell_dofs is None:
+            cell_dofs, _ = plan.dmesh.lagrange_dofmap(p, device=dev, stream=stream)
+        if cell_dofs2 is None:
+            cell_dofs2, ndofs2 = self.dmesh.lagrange_dofmap(p, device=dev, stream=stream)
+        if dev:
+            import torch
+            if ndofs2 is None:
+                raise RuntimeError("Refinement.prolong: ndofs2 is needed with a caller's cell_dofs2 on the device")
+            if not (u.is_contiguous() and cell_dofs.is_contiguous() and cell_dofs2.is_contiguous()) \
+                    or u.element_size() != 8 or cell_dofs.element_size() != 4 or cell_dofs2.element_size() != 4:
+                raise RuntimeError("Refinement.prolong: contiguous float64 u and int32 dofmaps expected")
+            uu = u.reshape(1, -1) if u.dim() == 1 else u
+            if out is None:   # the zero fill goes on `stream`, in front of the kernel; nothing waits
+                fill = torch.cuda.ExternalStream(stream) if stream else torch.cuda.default_stream(u.device)
+                with torch.cuda.stream(fill):
+                    out = torch.zeros((uu.shape[0], int(ndofs2) * bs), dtype=torch.float64, device=u.device)
+            ptrs = (cell_dofs.data_ptr(), uu.data_ptr(), cell_dofs2.data_ptr(), out.data_ptr())
+            ncd, ncd2, nu, nout = cell_dofs.numel(), cell_dofs2.numel(), uu.shape[1], out.numel()
+            memspace = MEM_DEVICE
+        else:
+            uu = np.ascontiguousarray(u, dtype=np.float64)
+            uu = uu.reshape(1, -1) if uu.ndim == 1 else uu
+            cell_dofs = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+            cell_dofs2 = np.ascontiguousarray(cell_dofs2, dtype=np.int32)
+            if ndofs2 is None:
+                ndofs2 = int(cell_dofs2.max()) + 1
+            if out is None:
+                out = np.zeros((uu.shape[0], int(ndofs2) * bs))
+            assert out.dtype == np.float64 and out.flags.c_contiguous
+            ptrs = (cell_dofs.ctypes.data, uu.ctypes.data, cell_dofs2.ctypes.data, out.ctypes.data)
+            ncd, ncd2, nu, nout = cell_dofs.size, cell_dofs2.size, uu.shape[1], out.size
+            memspace = MEM_HOST
+        nrhs = int(uu.shape[0])
+        nc, nc2 = plan.dmesh.counts()[1], self.counts["ncells2"]
+        if nu % bs != 0 or ncd != nc * nd or ncd2 != nc2 * nd or nout != nrhs * int(ndofs2) * bs:
+            raise RuntimeError("Refinement.prolong: Input sizes does not match")
+        plan.prolong_lagrange_raw(self.dmesh, p, bs, nrhs, ptrs[0], nu // bs, ptrs[1], ptrs[2], int(ndofs2), ptrs[3],
+                                  memspace, stream)
+        return out[0] if len(u.shape) == 1 and len(out.shape) == 2 else out
+
+    def prolong_dg(self, degree, values, bs=1, stream=0):
+        """values [nrhs, ncells*nd*bs] (or 1-D) of DG_degree data on the old mesh -> [nrhs, ncells2*nd*bs] on the
+        refined mesh (eqlb_refine_prolong_dg): flux_dg with bs = 2, rhs_dg with bs = 1, a cell-wise coefficient with
+        degree = 0.  Host arrays, or torch tensors on the device, read and written on `stream`."""
+        plan = self._kept_plan("prolong_dg")
+        nd = (degree + 1) * (degree + 2) // 2
+        nc, nc2 = plan.dmesh.counts()[1], self.counts["ncells2"]
+        dev = hasattr(values, "data_ptr")
+        if dev:
+            import torch
+            if not values.is_contiguous() or values.element_size() != 8:
+                raise RuntimeError("Refinement.prolong_dg: contiguous float64 values expected")
+            v = values.reshape(1, -1) if values.dim() == 1 else values
+            out = torch.empty((v.shape[0], nc2 * nd * bs), dtype=torch.float64, device=values.device)
+            pin, pout, memspace = v.data_ptr(), out.data_ptr(), MEM_DEVICE
+        else:
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            v = v.reshape(1, -1) if v.ndim == 1 else v
+            out = np.zeros((v.shape[0], nc2 * nd * bs))
+            pin, pout, memspace = v.ctypes.data, out.ctypes.data, MEM_HOST
+        if nd < 1 or v.shape[1] != nc * nd * bs:
+            raise RuntimeError("Refinement.prolong_dg: Input sizes does not match")
+        plan.prolong_dg_raw(self.dmesh, degree, bs, int(v.shape[0]), pin, pout, memspace, stream)
+        return out[0] if len(values.shape) == 1 else out
+
+    def close(self):
+        """Releases the kept plan (the refined DeviceMesh stays)."""
+        if self.plan is not None:
+            self.plan.close()
+            self.plan = None
 
 
 class SemiExplicitEquilibrator:
@@ -996,6 +1124,16 @@ def get_primal_table(p: int, degree_dg: int):
     if n < 0:
         raise RuntimeError(lib().eqlb_last_error().decode())
     return out[:n].reshape(2, nd, ndp)
+
+
+def get_prolong_table(q: int):
+    """The built-in table PT<q> [(2q+1)(q+1), nd_q] of the prolongation (eqlb_get_prolong_table), 1 <= q <= 4."""
+    nrow, nd = (2 * max(q, 0) + 1) * (max(q, 0) + 1), (max(q, 0) + 1) * (max(q, 0) + 2) // 2
+    out = np.zeros((nrow, nd))
+    n = lib().eqlb_get_prolong_table(C.c_int32(q), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
 
 
 def primal_flux_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, coeff=None, op=None):

@@ -22,7 +22,7 @@
 // of the old coordinates; eqlb_refine_parent_facets one kernel over the facets of the refined handle.
 // The number of launches depends on ncells alone.  The flags are bytes (cells) and words (facets, scanned as they
 // are); the only atomics are atomicMin on the error word and one integer add per wave for the count of cut cells.
-#include "eqlb_host_util.h"
+#include "eqlb_refine_plan.h"
 
 #include <cstring> // (rocprim's texture iterator calls memset)
 #include <rocprim/rocprim.hpp>
@@ -300,17 +300,6 @@ int check_memspace(const char* who, int32_t memspace)
 const char* const WHO = "eqlb_mesh_refine_plan";
 } // namespace
 } // namespace eqlb
-
-struct eqlb_refine
-{
-  const eqlb_mesh* mesh = nullptr;
-  int32_t nnodes = 0, ncells = 0, nfacets = 0;
-  int32_t nbis = 0, ncells2 = 0, ncut = 0;
-  eqlb::DevBuf<int32_t> fE, frank; // [nfacets + 1] flag of E; exclusive scan: rank among E
-  eqlb::DevBuf<int32_t> bis_facet; // [nbis] of [nfacets]: the facets of E, ascending
-  eqlb::DevBuf<uint32_t> coff;     // [ncells + 1] first child
-  eqlb::DevBuf<uint8_t> lloc;      // [ncells] l(c)
-};
 
 namespace eqlb
 {

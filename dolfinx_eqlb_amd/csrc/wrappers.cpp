@@ -58,6 +58,8 @@ inline void check(int status)
 void* g_stream = nullptr; // hipStream_t of device-memory calls (set_stream)
 
 // ---- stand-ins of the DOLFINx objects -------------------------------------------------------------
+struct Transfer;
+
 struct Mesh
 {
   eqlb_mesh_t* h = nullptr;
@@ -114,29 +116,18 @@ struct Mesh
   }
 
   // the mesh refined at the cells `marked` on the device (eqlb_mesh_refine_plan ...): the new Mesh, parent_cell,
-  // node_parent_facet, parent_facet
-  py::tuple refine(carray<int32_t> marked) const
+  // node_parent_facet, parent_facet; with keep_plan a Transfer (below) as fifth entry, which carries host arrays over
+  static py::tuple refine(std::shared_ptr<Mesh> self, carray<int32_t> marked, bool keep_plan);
+
+  // (cell_dofs [ncells, nd_p], ndofs) of the conforming P_p space (eqlb_mesh_lagrange_dofmap)
+  py::tuple lagrange_dofmap(int p) const
   {
-    struct Plan
-    {
-      eqlb_refine_t* p = nullptr;
-      ~Plan() { eqlb_refine_destroy(p); }
-    } plan;
-    const int64_t nmarked = (int64_t)marked.size();
-    check(eqlb_mesh_refine_plan(h, marked.data(), &nmarked, nmarked, EQLB_MEM_HOST, nullptr, &plan.p));
-    std::shared_ptr<Mesh> m(new Mesh());
-    int32_t nbis = 0;
-    check(eqlb_refine_counts(plan.p, &m->nnodes, &m->ncells, &nbis, nullptr));
-    m->x.resize(3 * (size_t)m->nnodes);
-    m->cell_nodes.resize(3 * (size_t)m->ncells);
-    py::array_t<int32_t> parent_cell(m->ncells), node_parent_facet(nbis);
-    check(eqlb_refine_write(plan.p, m->x.data(), m->cell_nodes.data(), parent_cell.mutable_data(),
-                            node_parent_facet.mutable_data(), EQLB_MEM_HOST, nullptr));
-    check(eqlb_refine_create_mesh(plan.p, nullptr, &m->h));
-    m->export_tables();
-    py::array_t<int32_t> parent_facet(m->nfacets);
-    check(eqlb_refine_parent_facets(plan.p, m->h, parent_facet.mutable_data(), EQLB_MEM_HOST, nullptr));
-    return py::make_tuple(m, parent_cell, node_parent_facet, parent_facet);
+    if (p < 1 || p > 4)
+      throw std::runtime_error("Mesh.lagrange_dofmap: p outside 1 ... 4");
+    py::array_t<int32_t> cd({(py::ssize_t)ncells, (py::ssize_t)((p + 1) * (p + 2) / 2)});
+    int64_t ndofs = 0;
+    check(eqlb_mesh_lagrange_dofmap(h, p, cd.mutable_data(), &ndofs, EQLB_MEM_HOST, nullptr));
+    return py::make_tuple(cd, ndofs);
   }
 
   py::array_t<int32_t> boundary_facets() const
@@ -187,6 +178,91 @@ public:
     return J[0][0] * J[1][1] - J[0][1] * J[1][0];
   }
 };
+
+// The open plan of a refinement with the two meshes it connects: prolongation of host arrays
+// (eqlb_refine_prolong_lagrange, eqlb_refine_prolong_dg)
+struct Transfer
+{
+  eqlb_refine_t* plan = nullptr;
+  std::shared_ptr<Mesh> coarse, fine; // the plan reads the old handle: both stay alive with the carrier
+  ~Transfer() { eqlb_refine_destroy(plan); }
+  Transfer() = default;
+  Transfer(const Transfer&) = delete;
+  Transfer& operator=(const Transfer&) = delete;
+
+  // u [nrhs, ndofs*bs] or [ndofs*bs] -> [nrhs, ndofs2*bs]; dofmaps None: lagrange_dofmap of the two meshes
+  darray prolong(int p, darray u, py::object cell_dofs, py::object cell_dofs2, int bs, py::object ndofs2_) const
+  {
+    if (p < 1 || p > 4 || bs < 1)
+      throw std::runtime_error("Transfer.prolong: p outside 1 ... 4 or bs < 1");
+    const int nd = (p + 1) * (p + 2) / 2;
+    const py::ssize_t nrhs = u.ndim() == 2 ? u.shape(0) : 1, nu = u.size() / nrhs;
+    int64_t ndofs2 = 0;
+    carray<int32_t> cd = cell_dofs.is_none() ? coarse->lagrange_dofmap(p)[0].cast<carray<int32_t>>()
+                                             : cell_dofs.cast<carray<int32_t>>();
+    carray<int32_t> cd2;
+    if (cell_dofs2.is_none())
+    {
+      py::tuple t = fine->lagrange_dofmap(p);
+      cd2 = t[0].cast<carray<int32_t>>();
+      ndofs2 = t[1].cast<int64_t>();
+    }
+    else
+    {
+      cd2 = cell_dofs2.cast<carray<int32_t>>();
+      for (py::ssize_t i = 0; i < cd2.size(); ++i)
+        ndofs2 = std::max<int64_t>(ndofs2, (int64_t)cd2.data()[i] + 1);
+    }
+    if (!ndofs2_.is_none())
+      ndofs2 = ndofs2_.cast<int64_t>();
+    if (nu % bs != 0 || cd.size() != (py::ssize_t)coarse->ncells * nd || cd2.size() != (py::ssize_t)fine->ncells * nd)
+      throw std::runtime_error("Transfer.prolong: Input sizes does not match");
+    darray out({nrhs, (py::ssize_t)(ndofs2 * bs)});
+    std::fill(out.mutable_data(), out.mutable_data() + out.size(), 0.0);
+    check(eqlb_refine_prolong_lagrange(plan, fine->h, p, bs, (int32_t)nrhs, cd.data(), nu / bs, u.data(), cd2.data(),
+                                       ndofs2, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
+
+  // values [nrhs, ncells*nd*bs] or 1-D -> [nrhs, ncells2*nd*bs]
+  darray prolong_dg(int degree, darray values, int bs) const
+  {
+    if (degree < 0 || degree > 3 || bs < 1)
+      throw std::runtime_error("Transfer.prolong_dg: degree outside 0 ... 3 or bs < 1");
+    const py::ssize_t row = (py::ssize_t)((degree + 1) * (degree + 2) / 2) * bs;
+    const py::ssize_t nrhs = values.ndim() == 2 ? values.shape(0) : 1;
+    if (values.size() != nrhs * coarse->ncells * row)
+      throw std::runtime_error("Transfer.prolong_dg: Input sizes does not match");
+    darray out({nrhs, (py::ssize_t)fine->ncells * row});
+    check(eqlb_refine_prolong_dg(plan, fine->h, degree, bs, (int32_t)nrhs, values.data(), out.mutable_data(),
+                                 EQLB_MEM_HOST, nullptr));
+    return out;
+  }
+};
+
+py::tuple Mesh::refine(std::shared_ptr<Mesh> self, carray<int32_t> marked, bool keep_plan)
+{
+  std::shared_ptr<Transfer> tr(new Transfer());
+  tr->coarse = self;
+  const int64_t nmarked = (int64_t)marked.size();
+  check(eqlb_mesh_refine_plan(self->h, marked.data(), &nmarked, nmarked, EQLB_MEM_HOST, nullptr, &tr->plan));
+  std::shared_ptr<Mesh> m(new Mesh());
+  int32_t nbis = 0;
+  check(eqlb_refine_counts(tr->plan, &m->nnodes, &m->ncells, &nbis, nullptr));
+  m->x.resize(3 * (size_t)m->nnodes);
+  m->cell_nodes.resize(3 * (size_t)m->ncells);
+  py::array_t<int32_t> parent_cell(m->ncells), node_parent_facet(nbis);
+  check(eqlb_refine_write(tr->plan, m->x.data(), m->cell_nodes.data(), parent_cell.mutable_data(),
+                          node_parent_facet.mutable_data(), EQLB_MEM_HOST, nullptr));
+  check(eqlb_refine_create_mesh(tr->plan, nullptr, &m->h));
+  m->export_tables();
+  py::array_t<int32_t> parent_facet(m->nfacets);
+  check(eqlb_refine_parent_facets(tr->plan, m->h, parent_facet.mutable_data(), EQLB_MEM_HOST, nullptr));
+  if (!keep_plan)
+    return py::make_tuple(m, parent_cell, node_parent_facet, parent_facet);
+  tr->fine = m;
+  return py::make_tuple(m, parent_cell, node_parent_facet, parent_facet, tr);
+}
 
 // family "DG": discontinuous Lagrange P_degree (block size bs); family "RT": the hierarchic RT_degree of
 // create_hierarchic_rt (elmtlib/e_raviart_thomas.py:14-196) - discontinuous: global DOF = cell * k(k+2) +
@@ -956,9 +1032,11 @@ PYBIND11_MODULE(_cpp, m)
       .def("boundary_facets", &Mesh::boundary_facets, "ids of the facets with one cell, ascending")
       .def("find_facets", &Mesh::find_facets, py::arg("pairs"),
            "facet id of every node pair [npairs, 2] (either order), -1 where the pair is no edge")
-      .def("refine", &Mesh::refine, py::arg("marked"),
+      .def("refine", &Mesh::refine, py::arg("marked"), py::arg("keep_plan") = false,
            "(Mesh, parent_cell, node_parent_facet, parent_facet) of the mesh refined at the marked cells by longest-edge "
-           "closure and bisection, on the device")
+           "closure and bisection, on the device; keep_plan=True appends a Transfer that prolongs host arrays")
+      .def("lagrange_dofmap", &Mesh::lagrange_dofmap, py::arg("p"),
+           "(cell_dofs [ncells, nd_p] int32, ndofs) of the conforming P_p space, 1 <= p <= 4")
       .def_property_readonly("x", [](const Mesh& s) {
         return py::array_t<double>({(py::ssize_t)s.nnodes, (py::ssize_t)3}, s.x.data());
       })
@@ -969,6 +1047,17 @@ PYBIND11_MODULE(_cpp, m)
       .def_readonly("ncells", &Mesh::ncells)
       .def_readonly("nfacets", &Mesh::nfacets)
       .def_property_readonly("max_patch_cells", [](const Mesh& s) { return eqlb_mesh_max_patch_cells(s.h); });
+
+  py::class_<Transfer, std::shared_ptr<Transfer>>(m, "Transfer",
+                                                  "Open plan of Mesh.refine(..., keep_plan=True): carries P_p solutions "
+                                                  "and DG data from the old mesh to the refined one")
+      .def("prolong", &Transfer::prolong, py::arg("p"), py::arg("u"), py::arg("cell_dofs") = py::none(),
+           py::arg("cell_dofs2") = py::none(), py::arg("bs") = 1, py::arg("ndofs2") = py::none(),
+           "u [nrhs, ndofs*bs] in P_p on the old mesh -> [nrhs, ndofs2*bs] on the refined mesh")
+      .def("prolong_dg", &Transfer::prolong_dg, py::arg("degree"), py::arg("values"), py::arg("bs") = 1,
+           "DG_degree values [nrhs, ncells*nd*bs] -> [nrhs, ncells2*nd*bs]")
+      .def_readonly("coarse", &Transfer::coarse)
+      .def_readonly("fine", &Transfer::fine);
 
   py::class_<FunctionSpace, std::shared_ptr<FunctionSpace>>(m, "FunctionSpace")
       .def(py::init<std::shared_ptr<Mesh>, std::string, int, int, bool>(), py::arg("mesh"), py::arg("family"),

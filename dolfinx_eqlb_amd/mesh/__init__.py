@@ -211,3 +211,4 @@ def create_disk(nsectors: int, nrings: int, shuffle_seed=None, radius: float = 1
 
 
 from .refine import parent_facets, refine_longest_edge  # noqa: E402,F401  (the statement of eqlb_mesh_refine_plan)
+from .transfer import lagrange_dofmap, prolong_dg, prolong_lagrange, prolong_table  # noqa: E402,F401  (eqlb_refine_prolong_*)

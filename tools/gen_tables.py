@@ -19,6 +19,9 @@ Basix nor quadrature loops:
   NREF[3][2], NOUT[3]  reference facet normals of the RT functionals and their outwardness
   PG[2][nd_d][nd_p]    projected reference gradient of a P_p function in DG_d (eqlb_primal_flux.hip): the DG_d nodal
                        values of d/dX phi_i for d >= p-1 (exact), Minv_d int psi_n d/dX phi_i (L2 projection) below
+  PT[(2q+1)(q+1)][nd_q] values of the P_q basis functions at the half-spacing lattice of the reference triangle, the
+                       prolongation across one bisection level (eqlb_transfer.hip; the lattice and its row order:
+                       dolfinx_eqlb_amd/mesh/transfer.py)
 
 Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
       go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
@@ -376,6 +379,18 @@ def emit(path):
         lines.append(f"  static constexpr int NP = {npp}, ND = {nd};")
         lines.append(f"  static constexpr double PG[{2 * nd * npp}] = {{"
                      + ", ".join(repr(float(v)) for v in _flat(primal_table_exact(p, d))) + "};")
+        lines.append("};")
+    lines.append("")
+    from dolfinx_eqlb_amd.mesh.transfer import prolong_table_exact
+    lines.append("// prolongation of P_q across one bisection level: PT[row][k] = basis function k of the equispaced P_q at the")
+    lines.append("// lattice point (i, j) / (2q), row = j (2q+1) - j (j-1) / 2 + i (mesh/transfer.py, eqlb_transfer.hip)")
+    lines.append("template <int Q> struct Prolong;")
+    for q in range(1, 5):
+        t = prolong_table_exact(q)
+        lines.append(f"template <> struct Prolong<{q}> {{")
+        lines.append(f"  static constexpr int NROW = {len(t)}, ND = {len(t[0])};")
+        lines.append(f"  static constexpr double PT[{len(t) * len(t[0])}] = {{"
+                     + ", ".join(repr(float(v)) for row in t for v in row) + "};")
         lines.append("};")
     lines.append("")
     lines.append("// reference facet normals of the RT functionals (e_raviart_thomas.py:82) and whether the")
