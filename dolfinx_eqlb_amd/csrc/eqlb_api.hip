@@ -206,9 +206,7 @@ try
   // the dense LDS Cholesky at 250 000 triangles; the EV patch problems at k = 4 stay on the dense solver)
   h->nrt = k * (k + 2);
   h->nd = (degree_dg + 1) * (degree_dg + 2) / 2;
-  int st = upload(&h->tables, tab.data(), tab.size());
-  st |= upload<int32_t>(&h->status, nullptr, 1);
-  if (st)
+  if (h->tables.upload(tab.data(), tab.size()) || h->status.alloc(1))
   {
     eqlb_se_destroy(h);
     return EQLB_ERR_DEVICE;
@@ -223,13 +221,6 @@ void eqlb_se_destroy(eqlb_se_t* h)
 {
   if (!h)
     return;
-  dfree(h->tables);
-  dfree(h->status);
-  dfree(h->d_flux_dg);
-  dfree(h->d_rhs_dg);
-  dfree(h->d_flux_hdiv);
-  dfree(h->d_cks);
-  dfree(h->d_korn);
   if (h->ev)
   {
     for (int i = 0; i < eqlb_se::EV_RING * eqlb_se::EV_PER_SET; ++i)
@@ -328,12 +319,12 @@ try
                 "equilibration only");
   const eqlb::DeviceMesh& m = h->mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (!h->d_cks && upload<double>(&h->d_cks, nullptr, (size_t)m.nnodes))
+  if (!h->d_cks && h->d_cks.alloc((size_t)m.nnodes))
     return EQLB_ERR_DEVICE;
   double* d_korn = cells_kornconst;
   if (memspace == EQLB_MEM_HOST)
   {
-    if (!h->d_korn && upload<double>(&h->d_korn, nullptr, (size_t)m.ncells))
+    if (!h->d_korn && h->d_korn.alloc((size_t)m.ncells))
       return EQLB_ERR_DEVICE;
     HIP_TRY(hipMemcpyAsync(h->d_korn, cells_kornconst, sizeof(double) * m.ncells, hipMemcpyHostToDevice, stream));
     d_korn = h->d_korn;
@@ -416,16 +407,11 @@ try
   if (stride < m.ncells_max + 2)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_export_patches: stride too small");
   const size_t nn = (size_t)m.nnodes;
-  int32_t *d_n = nullptr, *d_c = nullptr, *d_f = nullptr;
-  int8_t *d_fl = nullptr, *d_il = nullptr, *d_rv = nullptr;
-  int st = 0;
-  st |= upload<int32_t>(&d_n, nullptr, nn);
-  st |= upload<int32_t>(&d_c, nullptr, nn * stride);
-  st |= upload<int32_t>(&d_f, nullptr, nn * stride);
-  st |= upload<int8_t>(&d_fl, nullptr, nn * stride * 2);
-  st |= upload<int8_t>(&d_il, nullptr, nn * stride);
-  st |= upload<int8_t>(&d_rv, nullptr, nn * stride * 2);
-  if (!st)
+  eqlb::HostCall s;
+  const auto d_n = s.out(ncells, nn), d_c = s.out(cells, nn * stride), d_f = s.out(fcts, nn * stride);
+  const auto d_fl = s.out(fcts_local, nn * stride * 2), d_il = s.out(inodes_local, nn * stride),
+             d_rv = s.out(reversed, nn * stride * 2);
+  if (s.upload(nullptr) == hipSuccess)
   {
     eqlb::BuildArgs a{};
     a.nnodes = m.nnodes;
@@ -453,29 +439,10 @@ try
     a.ex_il = d_il;
     a.ex_rev = d_rv;
     eqlb::launch_build_patches(a, nullptr);
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess)
-      e = hipMemcpy(ncells, d_n, nn * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-      e = hipMemcpy(cells, d_c, nn * stride * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-      e = hipMemcpy(fcts, d_f, nn * stride * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-      e = hipMemcpy(fcts_local, d_fl, nn * stride * 2, hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-      e = hipMemcpy(inodes_local, d_il, nn * stride, hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-      e = hipMemcpy(reversed, d_rv, nn * stride * 2, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-      st = fail(EQLB_ERR_DEVICE, "eqlb_se_export_patches: %s", hipGetErrorString(e));
+    s.note(hipGetLastError());
   }
-  dfree(d_n);
-  dfree(d_c);
-  dfree(d_f);
-  dfree(d_fl);
-  dfree(d_il);
-  dfree(d_rv);
-  return st ? EQLB_ERR_DEVICE : EQLB_OK;
+  const hipError_t e = s.finish(nullptr);
+  return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "eqlb_se_export_patches: %s", hipGetErrorString(e));
 }
 EQLB_CATCH_ALL
 
@@ -494,38 +461,18 @@ try
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const int64_t ncells = (int64_t)mesh->m.ncells * nrhs; // the RHS are stacked cell blocks
   const size_t n_in = (size_t)ncells * nq * bs, n_out = (size_t)ncells * nd * bs;
-  double *d_P = nullptr, *d_in = nullptr, *d_out = nullptr;
-  if (upload(&d_P, Pm.data(), Pm.size()))
-    return EQLB_ERR_DEVICE;
-  int rc = EQLB_OK;
-  if (memspace == EQLB_MEM_HOST)
+  const bool host = memspace == EQLB_MEM_HOST;
+  eqlb::HostCall s; // (the projection matrix is staged in either memory space)
+  const auto d_P = s.in(Pm.data(), Pm.size());
+  const auto d_in = s.in(host ? qvalues : nullptr, n_in);
+  const auto d_out = s.out(host ? out : nullptr, n_out);
+  if (s.upload(stream) == hipSuccess)
   {
-    if (upload(&d_in, qvalues, n_in) || upload<double>(&d_out, nullptr, n_out))
-      rc = EQLB_ERR_DEVICE;
+    eqlb::launch_project_dg(ncells, nd, nq, bs, d_P, host ? d_in.get() : qvalues, host ? d_out.get() : out, stream);
+    s.note(hipGetLastError());
   }
-  else
-  {
-    d_in = const_cast<double*>(qvalues);
-    d_out = out;
-  }
-  if (!rc)
-  {
-    eqlb::launch_project_dg(ncells, nd, nq, bs, d_P, d_in, d_out, stream);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && memspace == EQLB_MEM_HOST)
-      e = hipMemcpy(out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(stream); // d_P is freed below
-    if (e != hipSuccess)
-      rc = fail(EQLB_ERR_DEVICE, "eqlb_project_dg: %s", hipGetErrorString(e));
-  }
-  dfree(d_P);
-  if (memspace == EQLB_MEM_HOST)
-  {
-    dfree(d_in);
-    dfree(d_out);
-  }
-  return rc;
+  const hipError_t e = s.finish(stream);
+  return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "eqlb_project_dg: %s", hipGetErrorString(e));
 }
 EQLB_CATCH_ALL
 
@@ -604,32 +551,14 @@ static int estimate_impl(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_
                                          facet_jump, alpha, beta, stream);
     return st ? fail(st, "eqlb_se_estimate: kernel launch failed") : EQLB_OK;
   }
-  if (memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate: unknown memory space");
-  double *d_x = nullptr, *d_g = nullptr, *d_f = nullptr, *d_d = nullptr, *d_s = nullptr, *d_j = nullptr;
-  int st = upload(&d_x, flux_hdiv, n_x) | upload(&d_g, flux_dg, n_g) | upload(&d_f, rhs_dg, n_f);
-  if (cell_div2)
-    st |= upload<double>(&d_d, nullptr, n_c);
-  if (cell_sig2)
-    st |= upload<double>(&d_s, nullptr, n_c);
-  if (facet_jump)
-    st |= upload<double>(&d_j, nullptr, n_e);
-  int rc = st ? EQLB_ERR_DEVICE : eqlb::launch_estimate(m, k, degree_dg, nrhs, d_x, d_g, d_f, d_d, d_s, d_j, alpha, beta,
-                                                        stream);
-  hipError_t e = hipSuccess;
-  if (!rc && cell_div2)
-    e = hipMemcpy(cell_div2, d_d, n_c * sizeof(double), hipMemcpyDeviceToHost);
-  if (!rc && e == hipSuccess && cell_sig2)
-    e = hipMemcpy(cell_sig2, d_s, n_c * sizeof(double), hipMemcpyDeviceToHost);
-  if (!rc && e == hipSuccess && facet_jump)
-    e = hipMemcpy(facet_jump, d_j, n_e * sizeof(double), hipMemcpyDeviceToHost);
-  dfree(d_x);
-  dfree(d_g);
-  dfree(d_f);
-  dfree(d_d);
-  dfree(d_s);
-  dfree(d_j);
-  if (rc || e != hipSuccess)
+  EQLB_TRY(eqlb::check_memspace("eqlb_se_estimate", memspace));
+  eqlb::HostCall s;
+  const auto d_x = s.in(flux_hdiv, n_x), d_g = s.in(flux_dg, n_g), d_f = s.in(rhs_dg, n_f);
+  const auto d_d = s.out(cell_div2, n_c), d_s = s.out(cell_sig2, n_c), d_j = s.out(facet_jump, n_e);
+  int rc = EQLB_OK;
+  if (s.upload(stream) == hipSuccess)
+    rc = eqlb::launch_estimate(m, k, degree_dg, nrhs, d_x, d_g, d_f, d_d, d_s, d_j, alpha, beta, stream);
+  if (s.finish(stream) != hipSuccess || rc)
     return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate: device error");
   return EQLB_OK;
 }
@@ -666,64 +595,13 @@ int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t
                        memspace, stream, -1.0, 0.0);
 }
 
-// Host arrays of a call staged on the device for its duration (inputs copied in, outputs copied back).
-namespace
-{
-struct Staging
-{
-  std::vector<double*> bufs;
-  struct Out
-  {
-    double *host, *dev;
-    size_t n;
-  };
-  std::vector<Out> outs;
-  bool bad = false;
-  const double* in(const double* host, size_t n)
-  {
-    if (!host)
-      return nullptr;
-    double* d = nullptr;
-    if (upload(&d, host, n))
-      bad = true;
-    bufs.push_back(d);
-    return d;
-  }
-  double* out(double* host, size_t n)
-  {
-    if (!host)
-      return nullptr;
-    double* d = nullptr;
-    if (upload<double>(&d, nullptr, n))
-      bad = true;
-    bufs.push_back(d);
-    outs.push_back({host, d, n});
-    return d;
-  }
-  bool fetch()
-  {
-    for (const Out& o : outs)
-      if (hipMemcpy(o.host, o.dev, o.n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return false;
-    return true;
-  }
-  ~Staging()
-  {
-    for (double* b : bufs)
-      if (b)
-        (void)hipFree(b);
-  }
-};
-} // namespace
-
 int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv, const double* korn,
                             double pi_1, double* cell_energy, double* cell_wsym, double* node_asym,
                             int32_t memspace, void* stream_)
 {
   if (!mesh || !flux_hdiv || k < 1 || k > 4 || !(pi_1 > -1.0))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate_stress: invalid argument");
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate_stress: unknown memory space");
+  EQLB_TRY(eqlb::check_memspace("eqlb_se_estimate_stress", memspace));
   eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (node_asym)
@@ -739,16 +617,13 @@ int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdi
                                       cell_wsym, node_asym, stream);
   else
   {
-    Staging s;
-    const double* d_x = s.in(flux_hdiv, 2 * nx);
-    const double* d_k = s.in(korn, m.ncells);
-    double* d_e = s.out(cell_energy, m.ncells);
-    double* d_w = s.out(cell_wsym, m.ncells);
-    double* d_a = s.out(node_asym, m.nnodes);
-    if (s.bad)
+    eqlb::HostCall s;
+    const auto d_x = s.in(flux_hdiv, 2 * nx), d_k = s.in(korn, m.ncells);
+    const auto d_e = s.out(cell_energy, m.ncells), d_w = s.out(cell_wsym, m.ncells), d_a = s.out(node_asym, m.nnodes);
+    if (s.upload(stream) != hipSuccess)
       return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate_stress: device allocation failed");
     rc = eqlb::launch_estimate_stress(m, m.node_cells, k, d_x, d_x + nx, d_k, pi_1, d_e, d_w, d_a, stream);
-    if (!rc && !s.fetch())
+    if (s.finish(stream) != hipSuccess)
       rc = EQLB_ERR_DEVICE;
   }
   return rc ? fail(rc, "eqlb_se_estimate_stress: device error") : EQLB_OK;
@@ -769,8 +644,7 @@ int eqlb_oscillation_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t
   if (!mesh || !flux || !qpoints || !qweights || !fvalues || !out || nrhs < 1 || k < 1 || k > 4 || nq < 1
       || nq > 128)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_oscillation: invalid argument");
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_oscillation: unknown memory space");
+  EQLB_TRY(eqlb::check_memspace("eqlb_oscillation", memspace));
   if (check_degree_dg("eqlb_oscillation", k, degree_dg))
     return EQLB_ERR_INVALID_ARGUMENT;
   const eqlb::DeviceMesh& m = mesh->m;
@@ -783,16 +657,14 @@ int eqlb_oscillation_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t
                                   stream);
   else
   {
-    Staging s;
-    const double* d_x = s.in(flux, nx);
-    const double* d_g = s.in(flux_dg, ng);
-    const double* d_f = s.in(fvalues, (size_t)nrhs * m.ncells * nq);
-    const double* d_k = s.in(korn, m.ncells);
-    double* d_o = s.out(out, (size_t)nrhs * m.ncells);
-    if (s.bad)
+    eqlb::HostCall s;
+    const auto d_x = s.in(flux, nx), d_g = s.in(flux_dg, ng), d_f = s.in(fvalues, (size_t)nrhs * m.ncells * nq),
+               d_k = s.in(korn, m.ncells);
+    const auto d_o = s.out(out, (size_t)nrhs * m.ncells);
+    if (s.upload(stream) != hipSuccess)
       return fail(EQLB_ERR_DEVICE, "eqlb_oscillation: device allocation failed");
     rc = eqlb::launch_oscillation(m, k, degree_dg, nrhs, d_x, d_g, nq, qpoints, qweights, d_f, d_k, d_o, stream);
-    if (!rc && !s.fetch())
+    if (s.finish(stream) != hipSuccess)
       rc = EQLB_ERR_DEVICE;
   }
   return rc ? fail(rc, "eqlb_oscillation: device error") : EQLB_OK;
@@ -804,8 +676,7 @@ int eqlb_boundary_residual(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int3
 {
   if (!mesh || !flux || nrhs < 1 || k < 1 || k > 4 || nfacets_bc < 0 || (nfacets_bc > 0 && (!facets || !out)))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_boundary_residual: invalid argument");
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_boundary_residual: unknown memory space");
+  EQLB_TRY(eqlb::check_memspace("eqlb_boundary_residual", memspace));
   if (check_degree_dg("eqlb_boundary_residual", k, degree_dg))
     return EQLB_ERR_INVALID_ARGUMENT;
   const eqlb::DeviceMesh& m = mesh->m;
@@ -825,19 +696,15 @@ int eqlb_boundary_residual(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int3
                                         out, stream);
   else
   {
-    Staging s;
-    const double* d_x = s.in(flux, nx);
-    const double* d_g = s.in(flux_dg, ng);
-    const double* d_b = s.in(boundary_values, nx);
-    double* d_o = s.out(out, (size_t)nrhs * nfacets_bc);
-    int32_t* d_l = nullptr;
-    if (upload(&d_l, facets, (size_t)nfacets_bc))
-      s.bad = true;
-    rc = s.bad ? EQLB_ERR_DEVICE
-               : eqlb::launch_boundary_residual(m, k, degree_dg, nrhs, d_x, d_g, nfacets_bc, d_l, d_b, d_o, stream);
-    if (!rc && !s.fetch())
+    eqlb::HostCall s;
+    const auto d_x = s.in(flux, nx), d_g = s.in(flux_dg, ng), d_b = s.in(boundary_values, nx);
+    const auto d_l = s.in(facets, (size_t)nfacets_bc);
+    const auto d_o = s.out(out, (size_t)nrhs * nfacets_bc);
+    rc = EQLB_OK;
+    if (s.upload(stream) == hipSuccess)
+      rc = eqlb::launch_boundary_residual(m, k, degree_dg, nrhs, d_x, d_g, nfacets_bc, d_l, d_b, d_o, stream);
+    if (s.finish(stream) != hipSuccess)
       rc = EQLB_ERR_DEVICE;
-    dfree(d_l);
   }
   return rc ? fail(rc, "eqlb_boundary_residual: device error") : EQLB_OK;
 }
@@ -889,12 +756,7 @@ void eqlb_ev_destroy(eqlb_ev_t* h)
 {
   if (!h)
     return;
-  if (h->se)
-  {
-    dfree(h->se->ev_cell_dofs);
-    dfree(h->se->ev_basis);
-    eqlb_se_destroy(h->se);
-  }
+  eqlb_se_destroy(h->se);
   delete h;
 }
 
@@ -907,9 +769,9 @@ int eqlb_ev_set_option(eqlb_ev_t* h, const char* key, int32_t value)
     if (value != 0 && value != 1)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "unknown output layout %d", value);
     h->se->ev_output = value;
-    dfree(h->se->d_flux_hdiv); // staging size depends on the layout
-    dfree(h->se->d_flux_dg);
-    dfree(h->se->d_rhs_dg);
+    h->se->d_flux_hdiv.reset(); // staging size depends on the layout
+    h->se->d_flux_dg.reset();
+    h->se->d_rhs_dg.reset();
     return EQLB_OK;
   }
   if (!strcmp(key, "boundary_basis"))
@@ -932,10 +794,10 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_dofmap: null argument");
   eqlb_se* se = h->se;
   const eqlb::DeviceMesh& m = se->mesh->m;
-  dfree(se->ev_cell_dofs);
-  dfree(se->d_flux_hdiv);
-  dfree(se->d_flux_dg);
-  dfree(se->d_rhs_dg);
+  se->ev_cell_dofs.reset();
+  se->d_flux_hdiv.reset(); // staging size depends on the number of DOFs
+  se->d_flux_dg.reset();
+  se->d_rhs_dg.reset();
   if (!cell_dofs)
   {
     se->ev_ndofs = (int64_t)m.nfacets * se->k + (int64_t)m.ncells * (se->k * se->k - se->k);
@@ -945,7 +807,7 @@ try
   for (size_t i = 0; i < n; ++i)
     if (cell_dofs[i] < 0 || cell_dofs[i] >= ndofs)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_dofmap: DOF %d out of range", cell_dofs[i]);
-  if (upload(&se->ev_cell_dofs, cell_dofs, n))
+  if (se->ev_cell_dofs.upload(cell_dofs, n))
     return EQLB_ERR_DEVICE;
   se->ev_ndofs = ndofs;
   return EQLB_OK;
@@ -957,7 +819,7 @@ int eqlb_ev_set_basis_transform(eqlb_ev_t* h, const double* C, const double* R)
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_basis_transform: null argument");
   eqlb_se* se = h->se;
-  dfree(se->ev_basis);
+  se->ev_basis.reset();
   se->ev_basis_has_R = false;
   if (!C)
     return EQLB_OK;
@@ -1033,7 +895,7 @@ int eqlb_ev_set_basis_transform(eqlb_ev_t* h, const double* C, const double* R)
         maps[((f * 2 + 1) * k + i) * k + j] = a_;
       }
   }
-  if (upload(&se->ev_basis, buf.data(), buf.size()))
+  if (se->ev_basis.upload(buf.data(), buf.size()))
     return EQLB_ERR_DEVICE;
   se->ev_basis_has_R = R != nullptr;
   return EQLB_OK;

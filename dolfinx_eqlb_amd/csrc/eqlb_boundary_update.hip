@@ -267,40 +267,6 @@ inline void launch_flux_bc(const BcArgs& a, const BcRule& rule, hipStream_t stre
                      dim3(eqlb::BC_THREADS), 0, stream, a, rule);
 }
 
-// device buffer of a host-memory call: [facets | values | out | two counters]
-struct HostStage
-{
-  char* buf = nullptr;
-  int32_t* facets = nullptr;
-  double *values = nullptr, *out = nullptr;
-  int32_t* counters = nullptr;
-  ~HostStage()
-  {
-    if (buf)
-      (void)hipFree(buf);
-  }
-  hipError_t init(int32_t nlist, const int32_t* h_facets, size_t nvalues, const double* h_values, size_t nout,
-                  hipStream_t stream)
-  {
-    const size_t fb = (sizeof(int32_t) * (size_t)nlist + 15) / 16 * 16, vb = sizeof(double) * nvalues,
-                 ob = sizeof(double) * nout;
-    hipError_t e = hipMalloc((void**)&buf, fb + vb + ob + 16);
-    if (e != hipSuccess)
-      return e;
-    facets = (int32_t*)buf;
-    values = (double*)(buf + fb);
-    out = (double*)(buf + fb + vb);
-    counters = (int32_t*)(buf + fb + vb + ob);
-    const int32_t init_c[2] = {0, INT32_MAX};
-    e = hipMemcpyAsync(facets, h_facets, sizeof(int32_t) * (size_t)nlist, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && nvalues)
-      e = hipMemcpyAsync(values, h_values, vb, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(counters, init_c, sizeof(init_c), hipMemcpyHostToDevice, stream);
-    return e;
-  }
-};
-
 int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, const int32_t* facets, int32_t nq,
                    const double* s, const double* w, const double* values, int32_t vector, int32_t* nrejected,
                    int32_t memspace, void* stream_)
@@ -310,8 +276,7 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid list (nlist = %d)", who, (int)nlist);
   if (vector != 0 && vector != 1)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: vector must be 0 or 1", who);
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(eqlb::check_memspace(who, memspace));
   EQLB_TRY(check_rule(who, nq, 0, s, w, true));
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
@@ -360,17 +325,21 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
     return EQLB_OK;
   // host memory space: a pass that only checks the list, then the pass that writes - a refused list leaves the table
   // as it was
-  HostStage st;
-  HIP_TRY(st.init(nlist, facets, values_count(nlist, h->k, nq, vector), values, 0, stream));
-  a.facets = st.facets;
-  a.values = st.values;
-  a.nrejected = st.counters;
-  a.first_bad = st.counters + 1;
+  const int32_t cnt_init[2] = {0, INT32_MAX};
+  int32_t cnt[2] = {0, 0};
+  eqlb::HostCall st;
+  const auto d_facets = st.in(facets, (size_t)nlist);
+  const auto d_values = st.in(values, values_count(nlist, h->k, nq, vector));
+  const auto d_cnt = st.in(cnt_init, 2); // rejected facets, first of them
+  st.out_prefix(cnt, d_cnt, 2);
+  HIP_TRY(st.upload(stream));
+  a.facets = d_facets;
+  a.values = d_values;
+  a.nrejected = d_cnt;
+  a.first_bad = d_cnt + 1;
   a.check_only = 1;
   launch_flux_bc(a, rule, stream);
-  int32_t cnt[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(cnt, st.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(st.finish(stream));
   if (cnt[0] > 0)
   {
     const int32_t i = cnt[1], f = facets[i];
@@ -391,8 +360,8 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
   a.first_bad = nullptr;
   a.check_only = 0;
   launch_flux_bc(a, rule, stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(stream));
+  st.note(hipGetLastError());
+  HIP_TRY(st.finish(stream));
   return EQLB_OK;
 }
 
@@ -400,8 +369,7 @@ int get_boundary_values(const char* who, eqlb_se* h, double* out, int32_t memspa
 {
   if (!h || !out)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(eqlb::check_memspace(who, memspace));
   if (!h->bt.boundary_set)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: boundary data not set", who);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -434,8 +402,7 @@ try
   const char* who = "eqlb_facet_points";
   if (nlist < 0 || (nlist > 0 && (!facets || !xq)))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid list (nlist = %d)", who, (int)nlist);
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(eqlb::check_memspace(who, memspace));
   EQLB_TRY(check_rule(who, nq, 1, s, nullptr, false));
   if (!mesh)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null mesh", who);
@@ -456,14 +423,14 @@ try
     HIP_TRY(hipGetLastError());
     return EQLB_OK;
   }
-  const size_t nout = (size_t)nlist * nq * 2;
-  HostStage st;
-  HIP_TRY(st.init(nlist, facets, 0, nullptr, nout, stream));
-  a.facets = st.facets;
-  hipLaunchKernelGGL(eqlb::k_facet_points, grid, block, 0, stream, a, rule, st.out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(xq, st.out, sizeof(double) * nout, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  eqlb::HostCall st;
+  const auto d_facets = st.in(facets, (size_t)nlist);
+  const auto d_xq = st.out(xq, (size_t)nlist * nq * 2);
+  HIP_TRY(st.upload(stream));
+  a.facets = d_facets;
+  hipLaunchKernelGGL(eqlb::k_facet_points, grid, block, 0, stream, a, rule, d_xq.get());
+  st.note(hipGetLastError());
+  HIP_TRY(st.finish(stream));
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
@@ -480,8 +447,7 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid list (nlist = %d)", who, (int)nlist);
   if (vector != 0 && vector != 1)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: vector must be 0 or 1", who);
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(eqlb::check_memspace(who, memspace));
   EQLB_TRY(check_rule(who, nq, 1, s, w, true));
   if (!mesh)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null mesh", who);
@@ -505,16 +471,17 @@ try
     HIP_TRY(hipGetLastError());
     return EQLB_OK;
   }
-  const size_t nout = (size_t)nlist * k;
-  HostStage st;
-  HIP_TRY(st.init(nlist, facets, values_count(nlist, k, nq, vector), values, nout, stream));
-  a.facets = st.facets;
-  a.values = st.values;
-  a.dofs = st.out;
+  eqlb::HostCall st;
+  const auto d_facets = st.in(facets, (size_t)nlist);
+  const auto d_values = st.in(values, values_count(nlist, k, nq, vector));
+  const auto d_dofs = st.out(dofs, (size_t)nlist * k);
+  HIP_TRY(st.upload(stream));
+  a.facets = d_facets;
+  a.values = d_values;
+  a.dofs = d_dofs;
   launch_flux_bc(a, rule, stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(dofs, st.out, sizeof(double) * nout, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  st.note(hipGetLastError());
+  HIP_TRY(st.finish(stream));
   return EQLB_OK;
 }
 EQLB_CATCH_ALL

@@ -157,14 +157,9 @@ static int launch_estimate_stress_k(const DeviceMesh& m, const int32_t* node_cel
   using R = eqlb_tables::Ref<K, K - 1>;
   std::vector<double> t(R::SU, R::SU + R::SU_SIZE);
   t.insert(t.end(), R::V, R::V + R::V_SIZE);
-  double *d_t = nullptr, *d_a = nullptr;
-  if (hipMalloc(&d_t, t.size() * sizeof(double)) != hipSuccess)
+  DevBuf<double> d_t, d_a;
+  if (d_t.alloc(t.size()) || (node_asym && d_a.alloc(3 * (size_t)m.ncells)))
     return EQLB_ERR_DEVICE;
-  if (node_asym && hipMalloc(&d_a, sizeof(double) * 3 * (size_t)m.ncells) != hipSuccess)
-  {
-    (void)hipFree(d_t);
-    return EQLB_ERR_DEVICE;
-  }
   hipError_t e = hipMemcpyAsync(d_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, stream);
   if (e == hipSuccess)
   {
@@ -177,9 +172,7 @@ static int launch_estimate_stress_k(const DeviceMesh& m, const int32_t* node_cel
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipStreamSynchronize(stream); // the buffers are freed below
-  (void)hipFree(d_t);
-  (void)hipFree(d_a);
+    e = hipStreamSynchronize(stream); // the buffers end with this call
   return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 

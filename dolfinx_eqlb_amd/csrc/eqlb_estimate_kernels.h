@@ -16,6 +16,7 @@
 #pragma once
 
 #include "eqlb_device_common.h"
+#include "eqlb_host_util.h"
 #include <cmath>
 #include <vector>
 #include "eqlb_tables_gen.h"
@@ -329,8 +330,8 @@ static int launch_estimate_kd(const DeviceMesh& m, int nrhs, const double* x_eq,
   using E = EstTables<K, DEG>;
   std::vector<double> t;
   E::fill(t);
-  double* d_t = nullptr;
-  if (hipMalloc(&d_t, t.size() * sizeof(double)) != hipSuccess)
+  DevBuf<double> d_t;
+  if (d_t.alloc(t.size()))
     return EQLB_ERR_DEVICE;
   hipError_t e = hipMemcpyAsync(d_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, stream);
   const size_t lds = t.size() * sizeof(double);
@@ -349,8 +350,7 @@ static int launch_estimate_kd(const DeviceMesh& m, int nrhs, const double* x_eq,
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipStreamSynchronize(stream); // the table buffer is freed below
-  (void)hipFree(d_t);
+    e = hipStreamSynchronize(stream); // the table buffer ends with this call
   return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
@@ -361,8 +361,8 @@ static int launch_boundary_residual_kd(const DeviceMesh& m, int nrhs, const doub
                                        hipStream_t stream)
 {
   using R = eqlb_tables::Ref<K, DEG>;
-  double* d_t = nullptr;
-  if (hipMalloc(&d_t, R::F0_SIZE * sizeof(double)) != hipSuccess)
+  DevBuf<double> d_t;
+  if (d_t.alloc(R::F0_SIZE))
     return EQLB_ERR_DEVICE;
   hipError_t e = hipMemcpyAsync(d_t, R::F0, R::F0_SIZE * sizeof(double), hipMemcpyHostToDevice, stream);
   const int64_t nx = (int64_t)m.ncells * R::NRT, ng = (int64_t)m.ncells * R::ND * 2;
@@ -375,8 +375,7 @@ static int launch_boundary_residual_kd(const DeviceMesh& m, int nrhs, const doub
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipStreamSynchronize(stream); // the table buffer is freed below
-  (void)hipFree(d_t);
+    e = hipStreamSynchronize(stream); // the table buffer ends with this call
   return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 
@@ -472,14 +471,9 @@ static int launch_oscillation_kd(const DeviceMesh& m, int nrhs, const double* x_
       qt[(size_t)q * E::NQ + p] = std::pow(qpoints[2 * q], R::MONO_X[p]) * std::pow(qpoints[2 * q + 1], R::MONO_Y[p]);
     qt[(size_t)nq * E::NQ + q] = qweights[q];
   }
-  double *d_t = nullptr, *d_q = nullptr;
-  if (hipMalloc(&d_t, t.size() * sizeof(double)) != hipSuccess)
+  DevBuf<double> d_t, d_q;
+  if (d_t.alloc(t.size()) || d_q.alloc(qt.size()))
     return EQLB_ERR_DEVICE;
-  if (hipMalloc(&d_q, qt.size() * sizeof(double)) != hipSuccess)
-  {
-    (void)hipFree(d_t);
-    return EQLB_ERR_DEVICE;
-  }
   hipError_t e = hipMemcpyAsync(d_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(d_q, qt.data(), qt.size() * sizeof(double), hipMemcpyHostToDevice, stream);
@@ -493,9 +487,7 @@ static int launch_oscillation_kd(const DeviceMesh& m, int nrhs, const double* x_
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipStreamSynchronize(stream);
-  (void)hipFree(d_t);
-  (void)hipFree(d_q);
+    e = hipStreamSynchronize(stream); // the table buffers end with this call
   return (e == hipSuccess) ? 0 : EQLB_ERR_DEVICE;
 }
 

@@ -8,7 +8,7 @@
 // RCCL is NOT linked: the five entry points are resolved at run time, first among the libraries already
 // loaded into the process (a caller that made its communicator with the RCCL bundled with PyTorch must get
 // THAT library's ncclSend for it), then from librccl.so(.1) of the ROCm installation.
-#include "eqlb_internal.h"
+#include "eqlb_host_util.h"
 
 #include <dlfcn.h>
 
@@ -19,7 +19,6 @@
 #include <new>
 #include <vector>
 
-#define fail eqlb::set_error
 
 namespace
 {
@@ -207,7 +206,8 @@ struct eqlb_halo
   int64_t nentries = 0;
   std::vector<int32_t> peers;
   std::vector<int64_t> nsend, nrecv;
-  std::vector<int64_t*> send_idx, recv_idx; // device
+  eqlb::DevCarve mem;                       // one allocation: the lists and the buffers below are its pieces
+  std::vector<int64_t*> send_idx, recv_idx; // device (nullptr: empty list)
   std::vector<double*> send_buf, recv_buf;  // device
 };
 
@@ -245,22 +245,36 @@ try
   h->recv_idx.assign(npeers, nullptr);
   h->send_buf.assign(npeers, nullptr);
   h->recv_buf.assign(npeers, nullptr);
-  auto dev = [](void** p, const void* src, size_t bytes) {
-    if (bytes == 0)
-      return true;
-    if (hipMalloc(p, bytes) != hipSuccess)
-      return false;
-    return !src || hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
+  std::vector<eqlb::DevPiece<int64_t>> p_si(npeers), p_ri(npeers);
+  std::vector<eqlb::DevPiece<double>> p_sb(npeers), p_rb(npeers);
+  const size_t row = (size_t)nrhs * nrt;
   for (int32_t i = 0; i < npeers; ++i)
   {
-    const size_t bs = (size_t)nsend[i] * nrhs * nrt * sizeof(double), br = (size_t)nrecv[i] * nrhs * nrt * sizeof(double);
-    if (!dev(reinterpret_cast<void**>(&h->send_idx[i]), send_idx[i], (size_t)nsend[i] * sizeof(int64_t))
-        || !dev(reinterpret_cast<void**>(&h->recv_idx[i]), recv_idx[i], (size_t)nrecv[i] * sizeof(int64_t))
-        || !dev(reinterpret_cast<void**>(&h->send_buf[i]), nullptr, bs)
-        || !dev(reinterpret_cast<void**>(&h->recv_buf[i]), nullptr, br))
-      return fail(EQLB_ERR_DEVICE, "eqlb_halo_create: device allocation failed");
+    if (nsend[i] > 0)
+    {
+      p_si[i] = h->mem.piece<int64_t>((size_t)nsend[i]);
+      p_sb[i] = h->mem.piece<double>((size_t)nsend[i] * row);
+    }
+    if (nrecv[i] > 0)
+    {
+      p_ri[i] = h->mem.piece<int64_t>((size_t)nrecv[i]);
+      p_rb[i] = h->mem.piece<double>((size_t)nrecv[i] * row);
+    }
   }
+  hipError_t e = h->mem.alloc();
+  for (int32_t i = 0; i < npeers && e == hipSuccess; ++i)
+  {
+    h->send_idx[i] = p_si[i];
+    h->recv_idx[i] = p_ri[i];
+    h->send_buf[i] = p_sb[i];
+    h->recv_buf[i] = p_rb[i];
+    if (nsend[i] > 0)
+      e = hipMemcpy(h->send_idx[i], send_idx[i], (size_t)nsend[i] * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (nrecv[i] > 0 && e == hipSuccess)
+      e = hipMemcpy(h->recv_idx[i], recv_idx[i], (size_t)nrecv[i] * sizeof(int64_t), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess)
+    return fail(EQLB_ERR_DEVICE, "eqlb_halo_create: device allocation failed");
   *handle = h.release();
   return EQLB_OK;
 }
@@ -269,24 +283,7 @@ catch (const std::bad_alloc&)
   return fail(EQLB_ERR_NO_MEMORY, "host memory exhausted");
 }
 
-void eqlb_halo_destroy(eqlb_halo_t* h)
-{
-  if (!h)
-    return;
-  for (auto* p : h->send_idx)
-    if (p)
-      (void)hipFree(p);
-  for (auto* p : h->recv_idx)
-    if (p)
-      (void)hipFree(p);
-  for (auto* p : h->send_buf)
-    if (p)
-      (void)hipFree(p);
-  for (auto* p : h->recv_buf)
-    if (p)
-      (void)hipFree(p);
-  delete h;
-}
+void eqlb_halo_destroy(eqlb_halo_t* h) { delete h; }
 
 int eqlb_halo_bytes(const eqlb_halo_t* h, int64_t* bytes_sent, int64_t* bytes_received)
 {

@@ -98,13 +98,13 @@ struct eqlb_se
   int ev_output = 0;                // EV: 0 conforming DOFs, 1 broken hierarchic RT_k layout
   int tile_cells_user = 0;          // option "tile_cells": cells per tile of the tiled launch (0 = automatic)
   int ev_bv_hier = 0;               // EV: boundary values in the hierarchic basis although a basis transform is set
-  int32_t* ev_cell_dofs = nullptr;  // EV: device copy of the caller's dofmap or nullptr (default)
+  eqlb::DevBuf<int32_t> ev_cell_dofs; // EV: device copy of the caller's dofmap or nullptr (default)
   int64_t ev_ndofs = 0;             // EV: number of conforming flux DOFs
-  double* ev_basis = nullptr;       // EV: device copy of [C (nrt x nrt) | R (k x k) | facet maps 3 x 2 x k x k] or nullptr
+  eqlb::DevBuf<double> ev_basis;    // EV: device copy of [C (nrt x nrt) | R (k x k) | facet maps 3 x 2 x k x k] or nullptr
   bool ev_basis_has_R = false;
   eqlb::BoundaryTables bt;          // what eqlb_se_set_boundary builds
   // device
-  double* tables = nullptr;
+  eqlb::DevBuf<double> tables;
   hipStream_t side_stream = nullptr; // the rest's patch kernels run here, next to the fused kernel
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // two-phase sweeps (multi-GPU overlap): tiles owning a priority cell are numbered first (BoundaryTables::t_nprio)
@@ -114,10 +114,10 @@ struct eqlb_se
   // option "large_patches_stress": weak symmetry and Korn constants on the large patches as well
   int large_patches_stress = 0;
   int slots_first_bin = 0;          // the slot rows of the bins >= this one hold values of the last slot-path run
-  int32_t* status = nullptr;
-  // staging for host-memory calls
-  double *d_flux_dg = nullptr, *d_rhs_dg = nullptr, *d_flux_hdiv = nullptr;
-  double *d_cks = nullptr, *d_korn = nullptr; // Korn estimate: per node / staging per cell
+  eqlb::DevBuf<int32_t> status;
+  // staging for host-memory calls: allocated by the first one, kept for the next
+  eqlb::DevBuf<double> d_flux_dg, d_rhs_dg, d_flux_hdiv;
+  eqlb::DevBuf<double> d_cks, d_korn; // Korn estimate: per node / staging per cell
   // timing ("timing" option): ring of event sets, one set per equilibrate call.  A set holds a begin and an end event
   // per timing slot; the slots are the `which` of eqlb_se_last_kernel_ms
   enum EvSlot

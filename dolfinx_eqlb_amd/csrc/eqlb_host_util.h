@@ -1,6 +1,12 @@
-// Host helpers of the translation units behind the C ABI (eqlb_api.hip, eqlb_boundary_setup.hip,
-// eqlb_boundary_update.hip, eqlb_sweep.hip, eqlb_tiling_host.hip; they include it through eqlb_handle.h): error return,
-// device upload / free and the owner of a device array, the exception barrier of the entry points, set-up profiling.
+// Host helpers of every translation unit that allocates device memory or stages a host-memory call: error return,
+// the owners of device memory (DevBuf, DevCarve, StreamBuf - no other file names the allocator), the staged host call
+// (HostCall), the exception barrier of the entry points, set-up profiling.  Host code only.  Included
+//   through eqlb_handle.h by eqlb_api.hip, eqlb_boundary_setup.hip, eqlb_boundary_update.hip, eqlb_sweep.hip,
+//     eqlb_tiling_host.hip,
+//   through eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip,
+//   through eqlb_estimate_kernels.h by eqlb_estimate.hip, eqlb_estimate_lowdeg.hip, eqlb_estimate_lowdeg_k4.hip,
+//   directly by eqlb_mesh_build.hip, eqlb_marking.hip, eqlb_primal_flux.hip, eqlb_tiling_device.hip,
+//     eqlb_halo_rccl.hip.
 #pragma once
 
 #include "eqlb_internal.h"
@@ -12,6 +18,7 @@
 #include <exception>
 #include <new>
 #include <utility>
+#include <vector>
 
 namespace
 {
@@ -103,6 +110,12 @@ public:
     return ::upload(&p_, src, n);
   }
   int alloc(size_t n) { return upload(nullptr, n); }
+  // the same without a message: n elements (at least one), for callers that word their own error
+  hipError_t alloc_raw(size_t n)
+  {
+    reset();
+    return hipMalloc(reinterpret_cast<void**>(&p_), (n ? n : 1) * sizeof(T));
+  }
 };
 
 // std::vector without value initialisation: the big scratch arrays of the tile builder are written completely by the
@@ -126,6 +139,162 @@ struct default_init_alloc : std::allocator<T>
 };
 template <typename T>
 using uvec = std::vector<T, default_init_alloc<T>>;
+
+
+// blocks of `threads` that cover n items
+inline unsigned grid_of(int64_t n, int threads = 256) { return (unsigned)((n + threads - 1) / threads); }
+
+// bytes up to the next multiple of 256: the alignment of the pieces of a carved allocation
+inline size_t round_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the memory space of a call is one of the two the ABI names
+inline int check_memspace(const char* who, int32_t memspace)
+{
+  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  return EQLB_OK;
+}
+
+// One device allocation carved into typed pieces: declare the pieces, alloc() once, read the pointers back from the
+// pieces.  Every piece starts on a multiple of 256 bytes; one of length zero is allowed.  Not movable (the pieces
+// point back at it).  A piece reads as nullptr until alloc(): keep it (auto) and let it convert where it is used.
+class DevCarve;
+template <typename T>
+struct DevPiece
+{
+  const DevCarve* owner = nullptr; // nullptr: no such piece, reads as nullptr
+  size_t off = 0;
+  inline T* get() const;
+  operator T*() const { return get(); }
+  DevPiece at(size_t i) const { return {owner, off + i * sizeof(T)}; } // the piece from element i on
+};
+
+class DevCarve
+{
+  DevBuf<char> buf_;
+  size_t bytes_ = 0;
+
+public:
+  DevCarve() = default;
+  DevCarve(const DevCarve&) = delete;
+  DevCarve& operator=(const DevCarve&) = delete;
+  template <typename T>
+  DevPiece<T> piece(size_t n)
+  {
+    DevPiece<T> p{this, bytes_};
+    bytes_ += round_up256(n * sizeof(T));
+    return p;
+  }
+  hipError_t alloc() { return buf_.alloc_raw(bytes_); }
+  char* base() const { return buf_.get(); }
+  size_t bytes() const { return bytes_; }
+};
+
+template <typename T>
+inline T* DevPiece<T>::get() const
+{
+  return (owner && owner->base()) ? reinterpret_cast<T*>(owner->base() + off) : nullptr;
+}
+
+// Work space of a device-memory call that must not wait: taken from the stream-ordered allocator and given back in
+// stream order when the owner ends.
+class StreamBuf
+{
+  void* p_ = nullptr;
+  hipStream_t stream_ = nullptr;
+
+public:
+  StreamBuf() = default;
+  StreamBuf(const StreamBuf&) = delete;
+  StreamBuf& operator=(const StreamBuf&) = delete;
+  ~StreamBuf()
+  {
+    if (p_)
+      (void)hipFreeAsync(p_, stream_);
+  }
+  hipError_t alloc(size_t bytes, hipStream_t stream)
+  {
+    stream_ = stream;
+    return hipMallocAsync(&p_, bytes, stream);
+  }
+  template <typename T>
+  T* as() const
+  {
+    return static_cast<T*>(p_);
+  }
+};
+
+// A host-memory call: the same work as the device-memory call, staged and synchronous.  Declare the arrays (a null
+// host pointer stays null), upload(stream) allocates once and sends the inputs on the caller's stream, the entry point
+// runs what its device branch runs on the pieces, finish(stream) enqueues the copies back on the same stream, waits for
+// it once and returns the first error seen anywhere.  An output whose length is known only after the run: out_prefix
+// after the first finish, then finish again.
+class HostCall
+{
+  struct Copy
+  {
+    void* host;
+    size_t off, bytes;
+  };
+  DevCarve mem_;
+  std::vector<Copy> ins_, outs_;
+  hipError_t err_ = hipSuccess;
+
+public:
+  template <typename T>
+  DevPiece<T> in(const T* host, size_t n)
+  {
+    if (!host)
+      return {};
+    const DevPiece<T> p = mem_.piece<T>(n);
+    ins_.push_back({const_cast<T*>(host), p.off, n * sizeof(T)});
+    return p;
+  }
+  template <typename T>
+  DevPiece<T> out(T* host, size_t n)
+  {
+    if (!host)
+      return {};
+    const DevPiece<T> p = mem_.piece<T>(n);
+    outs_.push_back({host, p.off, n * sizeof(T)});
+    return p;
+  }
+  template <typename T>
+  DevPiece<T> scratch(size_t n)
+  {
+    return mem_.piece<T>(n);
+  }
+  // the first n elements of a piece, copied back by the next finish
+  template <typename T>
+  void out_prefix(T* host, const DevPiece<T>& p, size_t n)
+  {
+    outs_.push_back({host, p.off, n * sizeof(T)});
+  }
+  // an error of the run between upload and finish
+  void note(hipError_t e)
+  {
+    if (err_ == hipSuccess)
+      err_ = e;
+  }
+  hipError_t upload(hipStream_t stream)
+  {
+    note(mem_.alloc());
+    for (const Copy& c : ins_)
+      if (err_ == hipSuccess && c.bytes)
+        note(hipMemcpyAsync(mem_.base() + c.off, c.host, c.bytes, hipMemcpyHostToDevice, stream));
+    return err_;
+  }
+  hipError_t finish(hipStream_t stream)
+  {
+    for (const Copy& c : outs_)
+      if (err_ == hipSuccess && c.bytes)
+        note(hipMemcpyAsync(c.host, mem_.base() + c.off, c.bytes, hipMemcpyDeviceToHost, stream));
+    outs_.clear();
+    if (mem_.base())
+      note(hipStreamSynchronize(stream)); // (also after an error: the allocation ends with this object)
+    return err_;
+  }
+};
 
 } // namespace eqlb
 

@@ -14,9 +14,8 @@
 // Every floating-point sum is made of per-thread partials in a fixed order, reduced by fixed trees: no fp atomics,
 // two calls on the same input give the same bits.
 #include "eqlb_device_common.h"
+#include "eqlb_host_util.h"
 #include <cmath>
-
-#define fail eqlb::set_error
 
 namespace eqlb
 {
@@ -471,21 +470,8 @@ k_indicator_reduce(int G, int nterms, const double* __restrict__ part, double* _
 }
 
 // ---- work space -----------------------------------------------------------------------------------------------
-// Device-memory calls take it from the stream-ordered allocator and give it back in stream order: nothing waits.
-static hipError_t ws_alloc(void** p, size_t bytes, hipStream_t stream, bool ordered)
-{
-  return ordered ? hipMallocAsync(p, bytes, stream) : hipMalloc(p, bytes);
-}
-static void ws_free(void* p, hipStream_t stream, bool ordered)
-{
-  if (!p)
-    return;
-  if (ordered)
-    (void)hipFreeAsync(p, stream);
-  else
-    (void)hipFree(p);
-}
-
+// Device-memory calls take it from the stream-ordered allocator and give it back in stream order (StreamBuf): nothing
+// waits.  Host-memory calls carve it out of their staging allocation.
 constexpr size_t MK_WS_STATE = 256; // MarkState, padded
 static_assert(sizeof(MarkState) <= MK_WS_STATE, "work space layout");
 constexpr size_t MK_WS_PSUM = MK_WS_STATE, MK_WS_PCNT = MK_WS_PSUM + sizeof(double) * MK_BUCKETS * MK_MAXBLOCKS,
@@ -548,49 +534,34 @@ int eqlb_indicator_total(int64_t ncells, int32_t nterms, const double* const* te
   for (int j = 0; j < nterms; ++j)
     if (!terms[j])
       return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_indicator_total: invalid argument");
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_indicator_total: unknown memory space");
+  EQLB_TRY(check_memspace("eqlb_indicator_total", memspace));
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const size_t part_bytes = sizeof(double) * (MK_MAXTERMS + 1) * MK_MAXBLOCKS, cb = sizeof(double) * (size_t)ncells;
+  const size_t npart = (size_t)(MK_MAXTERMS + 1) * MK_MAXBLOCKS;
   const int pair = pair_last_two ? 1 : 0;
   TermPtrs tp = {};
   if (memspace == EQLB_MEM_DEVICE)
   {
     for (int j = 0; j < nterms; ++j)
       tp.p[j] = terms[j];
-    void* part = nullptr;
-    if (totals && ws_alloc(&part, part_bytes, stream, true) != hipSuccess)
+    StreamBuf part;
+    if (totals && part.alloc(sizeof(double) * npart, stream) != hipSuccess)
       return fail(EQLB_ERR_DEVICE, "eqlb_indicator_total: device allocation failed");
-    const hipError_t e = enqueue_indicator(ncells, nterms, pair, tp, cell_eta2, totals, (double*)part, stream);
-    ws_free(part, stream, true);
+    const hipError_t e = enqueue_indicator(ncells, nterms, pair, tp, cell_eta2, totals, part.as<double>(), stream);
     return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "eqlb_indicator_total: %s", hipGetErrorString(e));
   }
   // host memory: stage, run, return finished values
-  char* buf = nullptr;
-  const size_t tot_bytes = sizeof(double) * (MK_MAXTERMS + 1);
-  if (hipMalloc((void**)&buf, part_bytes + tot_bytes + cb * (size_t)(nterms + 1)) != hipSuccess)
+  HostCall s;
+  const auto d_part = s.scratch<double>(npart);
+  const auto d_tot = s.out(totals, (size_t)nterms + 1), d_cell = s.out(cell_eta2, (size_t)ncells);
+  DevPiece<double> d_term[MK_MAXTERMS];
+  for (int j = 0; j < nterms; ++j)
+    d_term[j] = s.in(terms[j], (size_t)ncells);
+  if (s.upload(stream) != hipSuccess)
     return fail(EQLB_ERR_DEVICE, "eqlb_indicator_total: device allocation failed");
-  double* d_part = (double*)buf;
-  double* d_tot = (double*)(buf + part_bytes);
-  double* d_cell = (double*)(buf + part_bytes + tot_bytes);
-  hipError_t e = hipSuccess;
-  for (int j = 0; j < nterms && e == hipSuccess; ++j)
-  {
-    double* d = d_cell + (size_t)(j + 1) * ncells;
-    tp.p[j] = d;
-    e = hipMemcpyAsync(d, terms[j], cb, hipMemcpyHostToDevice, stream);
-  }
-  if (e == hipSuccess)
-    e = enqueue_indicator(ncells, nterms, pair, tp, cell_eta2 ? d_cell : nullptr, totals ? d_tot : nullptr, d_part,
-                          stream);
-  if (e == hipSuccess && cell_eta2)
-    e = hipMemcpyAsync(cell_eta2, d_cell, cb, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && totals)
-    e = hipMemcpyAsync(totals, d_tot, sizeof(double) * (nterms + 1), hipMemcpyDeviceToHost, stream);
-  const hipError_t es = hipStreamSynchronize(stream);
-  (void)hipFree(buf);
-  if (e == hipSuccess)
-    e = es;
+  for (int j = 0; j < nterms; ++j)
+    tp.p[j] = d_term[j];
+  s.note(enqueue_indicator(ncells, nterms, pair, tp, d_cell, d_tot, d_part, stream));
+  const hipError_t e = s.finish(stream);
   return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "eqlb_indicator_total: %s", hipGetErrorString(e));
 }
 
@@ -602,16 +573,14 @@ int eqlb_mark_doerfler(int64_t ncells, const double* cell_eta2, double theta, in
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mark_doerfler: invalid argument (ncells = %lld)", (long long)ncells);
   if (!(theta > 0.0 && theta <= 1.0 + 1e-8))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mark_doerfler: theta = %g outside (0, 1]", theta);
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mark_doerfler: unknown memory space");
+  EQLB_TRY(check_memspace("eqlb_mark_doerfler", memspace));
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (memspace == EQLB_MEM_DEVICE)
   {
-    void* ws = nullptr;
-    if (ws_alloc(&ws, MK_WS_BYTES, stream, true) != hipSuccess)
+    StreamBuf ws;
+    if (ws.alloc(MK_WS_BYTES, stream) != hipSuccess)
       return fail(EQLB_ERR_DEVICE, "eqlb_mark_doerfler: device allocation failed");
-    const hipError_t e = enqueue_mark(ncells, cell_eta2, theta, marked, nmarked, eta2_total, (char*)ws, stream);
-    ws_free(ws, stream, true);
+    const hipError_t e = enqueue_mark(ncells, cell_eta2, theta, marked, nmarked, eta2_total, ws.as<char>(), stream);
     return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "eqlb_mark_doerfler: %s", hipGetErrorString(e));
   }
   for (int64_t i = 0; i < ncells; ++i)
@@ -619,29 +588,23 @@ int eqlb_mark_doerfler(int64_t ncells, const double* cell_eta2, double theta, in
       return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mark_doerfler: negative or NaN indicator in cell %lld",
                   (long long)i);
   // host memory: stage, run, return finished values; only marked[0 .. nmarked) is written
-  const size_t cb = sizeof(double) * (size_t)ncells, mb = sizeof(int32_t) * (size_t)ncells, sb = 64;
-  char* buf = nullptr;
-  if (hipMalloc((void**)&buf, MK_WS_BYTES + sb + cb + mb) != hipSuccess)
-    return fail(EQLB_ERR_DEVICE, "eqlb_mark_doerfler: device allocation failed");
-  int64_t* d_n = (int64_t*)(buf + MK_WS_BYTES);
-  double* d_total = (double*)(buf + MK_WS_BYTES + 8);
-  double* d_eta = (double*)(buf + MK_WS_BYTES + sb);
-  int32_t* d_marked = (int32_t*)(buf + MK_WS_BYTES + sb + cb);
   int64_t nm = 0;
   double total = 0.0;
-  hipError_t e = hipMemcpyAsync(d_eta, cell_eta2, cb, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess)
-    e = enqueue_mark(ncells, d_eta, theta, d_marked, d_n, d_total, buf, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&nm, d_n, sizeof(int64_t), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&total, d_total, sizeof(double), hipMemcpyDeviceToHost, stream);
-  hipError_t es = hipStreamSynchronize(stream);
-  if (e == hipSuccess)
-    e = es;
+  HostCall s;
+  const auto d_ws = s.scratch<char>(MK_WS_BYTES);
+  const auto d_n = s.out(&nm, 1);
+  const auto d_total = s.out(&total, 1);
+  const auto d_eta = s.in(cell_eta2, (size_t)ncells);
+  const auto d_marked = s.scratch<int32_t>((size_t)ncells);
+  if (s.upload(stream) != hipSuccess)
+    return fail(EQLB_ERR_DEVICE, "eqlb_mark_doerfler: device allocation failed");
+  s.note(enqueue_mark(ncells, d_eta, theta, d_marked, d_n, d_total, d_ws, stream));
+  hipError_t e = s.finish(stream);
   if (e == hipSuccess && nm > 0 && nm <= ncells)
-    e = hipMemcpy(marked, d_marked, sizeof(int32_t) * (size_t)nm, hipMemcpyDeviceToHost);
-  (void)hipFree(buf);
+  {
+    s.out_prefix(marked, d_marked, (size_t)nm);
+    e = s.finish(stream);
+  }
   if (e != hipSuccess)
     return fail(EQLB_ERR_DEVICE, "eqlb_mark_doerfler: %s", hipGetErrorString(e));
   if (nm < 1 || nm > ncells)

@@ -195,8 +195,6 @@ k_find_facets(int32_t npairs, int32_t nnodes, const int32_t* __restrict__ pairs,
   out[i] = found;
 }
 
-inline unsigned grid_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 inline unsigned bits_of(unsigned long long v) // bits needed for the values 0 ... v
 {
   unsigned b = 1;
@@ -204,8 +202,6 @@ inline unsigned bits_of(unsigned long long v) // bits needed for the values 0 ..
     ++b;
   return b;
 }
-
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct MeshDeleter
 {
@@ -245,16 +241,17 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   EQLB_TRY(dalloc(&d.facet_perm, (size_t)n3));
   HIP_TRY(hipMemcpyAsync(d.cell_nodes, cell_nodes, sizeof(int32_t) * (size_t)n3, in_kind, stream));
 
-  const size_t b_k = up256(8 * (size_t)n3), b_v = up256(4 * (size_t)n3);
-  DevBuf<char> pool, tmp;
+  DevCarve pool;
+  const auto p_keys_in = pool.piece<unsigned long long>((size_t)n3), p_keys_out = pool.piece<unsigned long long>((size_t)n3);
+  const auto p_vals_in = pool.piece<int32_t>((size_t)n3), p_vals_out = pool.piece<int32_t>((size_t)n3),
+             p_fid = pool.piece<int32_t>((size_t)n3);
+  DevBuf<char> tmp;
   DevBuf<BuildWords> words;
-  EQLB_TRY(pool.alloc(2 * b_k + 3 * b_v));
+  if (pool.alloc() != hipSuccess)
+    return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", WHO);
   EQLB_TRY(words.alloc(1));
-  unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(pool.get());
-  unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(pool.get() + b_k);
-  int32_t* vals_in = reinterpret_cast<int32_t*>(pool.get() + 2 * b_k);
-  int32_t* vals_out = reinterpret_cast<int32_t*>(pool.get() + 2 * b_k + b_v);
-  int32_t* fid = reinterpret_cast<int32_t*>(pool.get() + 2 * b_k + 2 * b_v);
+  unsigned long long *keys_in = p_keys_in, *keys_out = p_keys_out;
+  int32_t *vals_in = p_vals_in, *vals_out = p_vals_out, *fid = p_fid;
 
   const unsigned key_bits = bits_of((unsigned long long)nnodes * (unsigned long long)nnodes - 1ull);
   size_t t_sort = 0, t_scan = 0;
@@ -314,10 +311,11 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   EQLB_TRY(dalloc(&d.node_facets_off, (size_t)nnodes + 1));
   EQLB_TRY(dalloc(&d.node_facets, (size_t)n2));
   EQLB_TRY(dalloc(&d.cellJ, (size_t)ncells * 4));
-  // the pool again: three buffers of max(n3, n2) <= 2 n3 entries of 4 bytes
-  uint32_t* nk_in = reinterpret_cast<uint32_t*>(pool.get());
-  uint32_t* nk_out = reinterpret_cast<uint32_t*>(pool.get() + b_k);
-  int32_t* nv_in = reinterpret_cast<int32_t*>(pool.get() + 2 * b_k);
+  // the pool again: three buffers of max(n3, n2) <= 2 n3 entries of 4 bytes (the third runs over the two value
+  // pieces, which follow each other)
+  uint32_t* nk_in = reinterpret_cast<uint32_t*>(keys_in);
+  uint32_t* nk_out = reinterpret_cast<uint32_t*>(keys_out);
+  int32_t* nv_in = vals_in;
   const unsigned node_bits = bits_of((unsigned long long)nnodes - 1ull);
   DevBuf<char> tmp_b;
   DevBuf<int32_t> cnt; // [3][nnodes] cells, facets, one-cell facets per node
@@ -402,12 +400,6 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   return EQLB_OK;
 }
 
-int check_memspace(const char* who, int32_t memspace)
-{
-  if (memspace != EQLB_MEM_HOST && memspace != EQLB_MEM_DEVICE)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
-  return EQLB_OK;
-}
 } // namespace
 } // namespace eqlb
 
@@ -495,35 +487,33 @@ try
   const eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const int32_t nf = m.nfacets;
-  eqlb::DevBuf<int32_t> pos, staged;
-  eqlb::DevBuf<char> tmp;
+  const bool host = memspace == EQLB_MEM_HOST;
   size_t tb = 0;
-  HIP_TRY(rocprim::inclusive_scan(nullptr, tb, pos.get(), pos.get(), (size_t)nf, rocprim::plus<int32_t>(), stream));
-  EQLB_TRY(pos.alloc((size_t)nf));
-  EQLB_TRY(tmp.alloc(tb));
+  HIP_TRY(rocprim::inclusive_scan(nullptr, tb, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)nf,
+                                  rocprim::plus<int32_t>(), stream));
+  int32_t count = 0;
+  eqlb::HostCall s;
+  const auto pos = s.scratch<int32_t>((size_t)nf);
+  const auto tmp = s.scratch<char>(tb);
+  const auto staged = s.scratch<int32_t>(host ? (size_t)std::min(capacity, nf) : 0);
+  s.out_prefix(&count, pos.at((size_t)nf - 1), 1);
+  HIP_TRY(s.upload(stream));
   hipLaunchKernelGGL(eqlb::k_boundary_flags, dim3(eqlb::grid_of(nf)), dim3(256), 0, stream, nf, m.facet_cells_off,
                      pos.get());
   HIP_TRY(rocprim::inclusive_scan(tmp.get(), tb, pos.get(), pos.get(), (size_t)nf, rocprim::plus<int32_t>(), stream));
-  int32_t count = 0;
-  HIP_TRY(hipMemcpyAsync(&count, pos.get() + (nf - 1), sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(s.finish(stream));
   *n = count;
   if (count > capacity)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mesh_boundary_facets: capacity %d, the mesh has %d boundary facets",
                 capacity, count);
   if (count == 0)
     return EQLB_OK;
-  int32_t* out = facets;
-  if (memspace == EQLB_MEM_HOST)
-  {
-    EQLB_TRY(staged.alloc((size_t)count));
-    out = staged.get();
-  }
-  hipLaunchKernelGGL(eqlb::k_boundary_scatter, dim3(eqlb::grid_of(nf)), dim3(256), 0, stream, nf, pos.get(), out);
-  if (memspace == EQLB_MEM_HOST)
-    HIP_TRY(hipMemcpyAsync(facets, out, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream)); // the scan buffer is freed on return
-  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(eqlb::k_boundary_scatter, dim3(eqlb::grid_of(nf)), dim3(256), 0, stream, nf, pos.get(),
+                     host ? staged.get() : facets);
+  s.note(hipGetLastError());
+  if (host)
+    s.out_prefix(facets, staged, (size_t)count);
+  HIP_TRY(s.finish(stream)); // (in either memory space: the scan buffer ends with this call)
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
@@ -546,15 +536,14 @@ try
     HIP_TRY(hipGetLastError());
     return EQLB_OK;
   }
-  eqlb::DevBuf<int32_t> d_pairs, d_out;
-  EQLB_TRY(d_pairs.alloc(2 * (size_t)npairs));
-  EQLB_TRY(d_out.alloc((size_t)npairs));
-  HIP_TRY(hipMemcpyAsync(d_pairs.get(), node_pairs, 8 * (size_t)npairs, hipMemcpyHostToDevice, stream));
+  eqlb::HostCall s;
+  const auto d_pairs = s.in(node_pairs, 2 * (size_t)npairs);
+  const auto d_out = s.out(facets, (size_t)npairs);
+  HIP_TRY(s.upload(stream));
   hipLaunchKernelGGL(eqlb::k_find_facets, dim3(eqlb::grid_of(npairs)), dim3(256), 0, stream, npairs, m.nnodes,
                      d_pairs.get(), m.node_facets_off, m.node_facets, m.facet_nodes, d_out.get());
-  HIP_TRY(hipMemcpyAsync(facets, d_out.get(), 4 * (size_t)npairs, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  HIP_TRY(hipGetLastError());
+  s.note(hipGetLastError());
+  HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }
 EQLB_CATCH_ALL

@@ -288,15 +288,6 @@ k_parent_facets(int32_t nfacets2, int32_t nnodes, const int32_t* __restrict__ fa
   parent_facet[f2] = found;
 }
 
-inline unsigned grid_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-int check_memspace(const char* who, int32_t memspace)
-{
-  if (memspace != EQLB_MEM_HOST && memspace != EQLB_MEM_DEVICE)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
-  return EQLB_OK;
-}
-
 const char* const WHO = "eqlb_mesh_refine_plan";
 } // namespace
 } // namespace eqlb
@@ -503,28 +494,13 @@ try
     return eqlb::enqueue_write(plan, x2, cell_nodes2, parent_cell, node_parent_facet, stream);
   const size_t nx = 3 * ((size_t)plan->nnodes + (size_t)plan->nbis), n3 = 3 * (size_t)plan->ncells2,
                nc2 = (size_t)plan->ncells2, nb = (size_t)plan->nbis;
-  eqlb::DevBuf<double> d_x;
-  eqlb::DevBuf<int32_t> d_c, d_pc, d_npf;
-  if (x2)
-    EQLB_TRY(d_x.alloc(nx));
-  if (cell_nodes2)
-    EQLB_TRY(d_c.alloc(n3));
-  if (parent_cell)
-    EQLB_TRY(d_pc.alloc(nc2));
-  if (node_parent_facet)
-    EQLB_TRY(d_npf.alloc(nb));
-  EQLB_TRY(eqlb::enqueue_write(plan, d_x.get(), d_c.get(), d_pc.get(), d_npf.get(), stream));
-  if (x2)
-    HIP_TRY(hipMemcpyAsync(x2, d_x.get(), sizeof(double) * nx, hipMemcpyDeviceToHost, stream));
-  if (cell_nodes2)
-    HIP_TRY(hipMemcpyAsync(cell_nodes2, d_c.get(), sizeof(int32_t) * n3, hipMemcpyDeviceToHost, stream));
-  if (parent_cell)
-    HIP_TRY(hipMemcpyAsync(parent_cell, d_pc.get(), sizeof(int32_t) * nc2, hipMemcpyDeviceToHost, stream));
-  if (node_parent_facet && nb)
-    HIP_TRY(hipMemcpyAsync(node_parent_facet, d_npf.get(), sizeof(int32_t) * nb, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  HIP_TRY(hipGetLastError());
-  return EQLB_OK;
+  eqlb::HostCall s;
+  const auto d_x = s.out(x2, nx);
+  const auto d_c = s.out(cell_nodes2, n3), d_pc = s.out(parent_cell, nc2), d_npf = s.out(node_parent_facet, nb);
+  HIP_TRY(s.upload(stream));
+  const int rc = eqlb::enqueue_write(plan, d_x, d_c, d_pc, d_npf, stream);
+  HIP_TRY(s.finish(stream));
+  return rc;
 }
 EQLB_CATCH_ALL
 
@@ -559,21 +535,15 @@ try
                 r.ncells, plan->nnodes + plan->nbis, plan->ncells2);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const int32_t nf2 = r.nfacets;
-  eqlb::DevBuf<int32_t> staged;
-  int32_t* out = parent_facet;
+  eqlb::HostCall s;
+  const auto staged = s.out(memspace == EQLB_MEM_HOST ? parent_facet : nullptr, (size_t)nf2);
   if (memspace == EQLB_MEM_HOST)
-  {
-    EQLB_TRY(staged.alloc((size_t)nf2));
-    out = staged.get();
-  }
+    HIP_TRY(s.upload(stream));
   hipLaunchKernelGGL(eqlb::k_parent_facets, dim3(eqlb::grid_of(nf2)), dim3(256), 0, stream, nf2, plan->nnodes,
-                     r.facet_nodes, plan->bis_facet.get(), m.facet_nodes, m.node_facets_off, m.node_facets, out);
-  HIP_TRY(hipGetLastError());
-  if (memspace == EQLB_MEM_HOST)
-  {
-    HIP_TRY(hipMemcpyAsync(parent_facet, out, sizeof(int32_t) * (size_t)nf2, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
+                     r.facet_nodes, plan->bis_facet.get(), m.facet_nodes, m.node_facets_off, m.node_facets,
+                     memspace == EQLB_MEM_HOST ? staged.get() : parent_facet);
+  s.note(hipGetLastError());
+  HIP_TRY(s.finish(stream)); // (a device-memory call staged nothing: no copy and no wait)
   return EQLB_OK;
 }
 EQLB_CATCH_ALL

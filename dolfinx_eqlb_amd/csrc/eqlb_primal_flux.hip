@@ -22,11 +22,10 @@
 // permuted together with cell_dofs gives the same bits as the built-in one.  No atomics, no scratch, one fixed order
 // of operations per value: two runs give the same bits.
 #include "eqlb_device_common.h"
+#include "eqlb_host_util.h"
 #include "eqlb_tables_gen.h"
 #include <cmath>
 #include <cstring>
-
-#define fail eqlb::set_error
 
 namespace eqlb
 {
@@ -308,8 +307,6 @@ static int table_p(int d, double* out)
   return 2 * nd_of(d) * nd_of(P);
 }
 
-static size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // the common body of the two entry points; stress: u [ndofs][2], two output rows, coeff = cell_pi1
 static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32_t d, int32_t nrhs, bool stress,
                             const int32_t* cell_dofs, int64_t ndofs, const double* u, const double* coeff,
@@ -322,8 +319,7 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d", who, (int)nrhs);
   if (!mesh || !cell_dofs || !u || !flux_dg || ndofs < 1 || ndofs > INT32_MAX)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid argument", who);
-  if (memspace != EQLB_MEM_DEVICE && memspace != EQLB_MEM_HOST)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(check_memspace(who, memspace));
   const DeviceMesh& m = mesh->m;
   const int np = nd_of(p), nd = nd_of(d);
   const int32_t ncells = m.ncells;
@@ -340,30 +336,15 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
     if (cell_dofs[i] < 0 || (int64_t)cell_dofs[i] >= ndofs)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_dofs[%lld][%d] = %d outside [0, %lld)", who,
                   (long long)(i / np), (int)(i % np), (int)cell_dofs[i], (long long)ndofs);
-  const size_t ib = pad256(sizeof(int32_t) * nidx), ub = pad256(sizeof(double) * (size_t)ndofs * (stress ? 2 : nrhs)),
-               cb = pad256(sizeof(double) * (size_t)ncells),
-               ob = sizeof(double) * (size_t)(stress ? 2 : nrhs) * ncells * nd * 2;
-  char* buf = nullptr;
-  if (hipMalloc((void**)&buf, ib + ub + cb + ob) != hipSuccess)
+  const size_t nu = (size_t)ndofs * (stress ? 2 : nrhs), nout = (size_t)(stress ? 2 : nrhs) * ncells * nd * 2;
+  HostCall s;
+  const auto d_idx = s.in(cell_dofs, nidx);
+  const auto d_u = s.in(u, nu), d_c = s.in(coeff, (size_t)ncells);
+  const auto d_out = s.out(flux_dg, nout);
+  if (s.upload(stream) != hipSuccess)
     return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
-  int32_t* d_idx = (int32_t*)buf;
-  double* d_u = (double*)(buf + ib);
-  double* d_c = (double*)(buf + ib + ub);
-  double* d_out = (double*)(buf + ib + ub + cb);
-  hipError_t e = hipMemcpyAsync(d_idx, cell_dofs, sizeof(int32_t) * nidx, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_u, u, sizeof(double) * (size_t)ndofs * (stress ? 2 : nrhs), hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && coeff)
-    e = hipMemcpyAsync(d_c, coeff, sizeof(double) * (size_t)ncells, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess)
-    e = launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, d_idx, d_u, m.cellJ, coeff ? d_c : nullptr, pi_1, op,
-                           d_out, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(flux_dg, d_out, ob, hipMemcpyDeviceToHost, stream);
-  const hipError_t es = hipStreamSynchronize(stream);
-  (void)hipFree(buf);
-  if (e == hipSuccess)
-    e = es;
+  s.note(launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, d_idx, d_u, m.cellJ, d_c, pi_1, op, d_out, stream));
+  const hipError_t e = s.finish(stream);
   return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
 }
 

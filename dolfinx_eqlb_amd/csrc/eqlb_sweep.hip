@@ -66,8 +66,7 @@ int stage_in(eqlb_se* h, size_t s_g, size_t s_f, size_t s_x, const double* const
 {
   if (!h->d_flux_dg)
   {
-    if (upload<double>(&h->d_flux_dg, nullptr, h->nrhs * s_g) || upload<double>(&h->d_rhs_dg, nullptr, h->nrhs * s_f)
-        || upload<double>(&h->d_flux_hdiv, nullptr, h->nrhs * s_x))
+    if (h->d_flux_dg.alloc(h->nrhs * s_g) || h->d_rhs_dg.alloc(h->nrhs * s_f) || h->d_flux_hdiv.alloc(h->nrhs * s_x))
       return EQLB_ERR_DEVICE;
   }
   for (int r = 0; r < h->nrhs; ++r)
@@ -88,12 +87,13 @@ int stage_out(eqlb_se* h, size_t s_x, double* const* x_io, double* const* d_x, h
 {
   for (int r = 0; r < h->nrhs; ++r)
     HIP_TRY(hipMemcpyAsync(x_io[r], d_x[r], s_x * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
   int32_t status = 0;
-  HIP_TRY(hipMemcpy(&status, h->status, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpyAsync(&status, h->status, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   if (status)
   {
-    (void)hipMemset(h->status, 0, sizeof(int32_t));
+    HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(int32_t), stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return fail(EQLB_ERR_SINGULAR, "patch system not positive definite");
   }
   return EQLB_OK;
@@ -552,12 +552,9 @@ int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const double* con
 
   std::vector<const double*> d_g(g_in, g_in + h->nrhs), d_f(f_in, f_in + h->nrhs);
   std::vector<double*> d_x(x_io, x_io + h->nrhs);
+  EQLB_TRY(eqlb::check_memspace("eqlb_se_equilibrate", memspace));
   if (memspace == EQLB_MEM_HOST)
-  {
     EQLB_TRY(stage_in(h, s_g, s_f, s_x, g_in, f_in, x_io, d_g.data(), d_f.data(), d_x.data(), stream));
-  }
-  else if (memspace != EQLB_MEM_DEVICE)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_equilibrate: unknown memory space");
 
   hipEvent_t* evs = nullptr;
   if (h->timing)

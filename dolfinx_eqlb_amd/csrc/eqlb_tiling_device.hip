@@ -15,7 +15,7 @@
 // Not taken for meshes with stretched cells (aspect ratio above ~3 in more than 0.1 % of the cells): there the
 // host bisection chooses the cut of the last levels by the nodes it separates (rcb_split), which needs the mesh
 // connectivity per trial cut.
-#include "eqlb_internal.h"
+#include "eqlb_host_util.h"
 
 #include <cstring> // (rocprim's texture iterator calls memset)
 #include <rocprim/rocprim.hpp>
@@ -186,21 +186,6 @@ k_tile_keys(int32_t nc, int tc, const int32_t* __restrict__ ord, unsigned long l
     keys[p] = ((unsigned long long)(p / tc) << 32) | (unsigned int)ord[p];
 }
 
-struct DevBuf
-{
-  void* p = nullptr;
-  ~DevBuf()
-  {
-    if (p)
-      (void)hipFree(p);
-  }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-  template <typename T>
-  T* as()
-  {
-    return static_cast<T*>(p);
-  }
-};
 } // namespace
 
 __global__ void k_tiling_touch(int* p)
@@ -242,38 +227,31 @@ int device_tile_order(const DeviceMesh& m, int tc, int32_t ntiles, const double 
             std::chrono::duration<double, std::milli>(t1 - t_last).count());
     t_last = t1;
   };
-  // one allocation for everything (a dozen hipMalloc / hipFree pairs cost more than the sorts)
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_f = up(sizeof(float) * (size_t)nc), b_i = up(sizeof(int32_t) * (size_t)nc), b_k = up(8 * (size_t)nc),
-               b_s = up(4 * (size_t)nseg_all), b_b = up(16 * (size_t)maxseg);
+  // one allocation for everything (a dozen allocations of their own cost more than the sorts)
   size_t tmp_bytes = 0;
   if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                 (int32_t*)nullptr, (int32_t*)nullptr, (size_t)nc, 0u, 64u, (hipStream_t)0)
       != hipSuccess)
     return -1;
-  const size_t total = 2 * b_f + 2 * b_i + 2 * b_k + 5 * b_s + 2 * b_b + 256 + up(tmp_bytes);
-  DevBuf pool;
-  if (!pool.alloc(total))
+  DevCarve pool;
+  const auto p_cx = pool.piece<float>((size_t)nc), p_cy = pool.piece<float>((size_t)nc);
+  const auto p_ord0 = pool.piece<int32_t>((size_t)nc), p_ord1 = pool.piece<int32_t>((size_t)nc);
+  const auto p_keys0 = pool.piece<unsigned long long>((size_t)nc), p_keys1 = pool.piece<unsigned long long>((size_t)nc);
+  const auto p_off = pool.piece<int32_t>((size_t)nseg_all), p_n = pool.piece<int32_t>((size_t)nseg_all),
+             p_nl = pool.piece<int32_t>((size_t)nseg_all), p_left = pool.piece<int32_t>((size_t)nseg_all),
+             p_right = pool.piece<int32_t>((size_t)nseg_all);
+  const auto p_box0 = pool.piece<float>(4 * (size_t)maxseg), p_box1 = pool.piece<float>(4 * (size_t)maxseg);
+  const auto p_cnt = pool.piece<unsigned long long>(1);
+  const auto p_tmp = pool.piece<char>(tmp_bytes);
+  if (pool.alloc() != hipSuccess)
     return -1;
-  char* base = pool.as<char>();
-  auto take = [&](size_t b) {
-    char* q = base;
-    base += b;
-    return q;
-  };
-  float* cx = reinterpret_cast<float*>(take(b_f));
-  float* cy = reinterpret_cast<float*>(take(b_f));
-  int32_t* ord2[2] = {reinterpret_cast<int32_t*>(take(b_i)), reinterpret_cast<int32_t*>(take(b_i))};
-  unsigned long long* keys2[2] = {reinterpret_cast<unsigned long long*>(take(b_k)),
-                                  reinterpret_cast<unsigned long long*>(take(b_k))};
-  int32_t* s_off = reinterpret_cast<int32_t*>(take(b_s));
-  int32_t* s_n = reinterpret_cast<int32_t*>(take(b_s));
-  int32_t* s_nl = reinterpret_cast<int32_t*>(take(b_s));
-  int32_t* s_left = reinterpret_cast<int32_t*>(take(b_s));
-  int32_t* s_right = reinterpret_cast<int32_t*>(take(b_s));
-  float* box2[2] = {reinterpret_cast<float*>(take(b_b)), reinterpret_cast<float*>(take(b_b))};
-  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(take(256));
-  void* d_tmp = take(up(tmp_bytes));
+  float *cx = p_cx, *cy = p_cy;
+  int32_t* ord2[2] = {p_ord0, p_ord1};
+  unsigned long long* keys2[2] = {p_keys0, p_keys1};
+  int32_t *s_off = p_off, *s_n = p_n, *s_nl = p_nl, *s_left = p_left, *s_right = p_right;
+  float* box2[2] = {p_box0, p_box1};
+  unsigned long long* d_cnt = p_cnt;
+  void* d_tmp = p_tmp.get();
   if (hipMemcpyAsync(s_off, t.off.data(), 4 * (size_t)nseg_all, hipMemcpyHostToDevice, 0) != hipSuccess
       || hipMemcpyAsync(s_n, t.n.data(), 4 * (size_t)nseg_all, hipMemcpyHostToDevice, 0) != hipSuccess
       || hipMemcpyAsync(s_nl, t.nl.data(), 4 * (size_t)nseg_all, hipMemcpyHostToDevice, 0) != hipSuccess

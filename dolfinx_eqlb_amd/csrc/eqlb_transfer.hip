@@ -271,12 +271,10 @@ k_lagrange_dofmap(int32_t ncells, int32_t nnodes, int32_t nfacets, int p, const 
     o[col++] = (int32_t)(ibase + j);
 }
 
-inline unsigned grid_of(int64_t n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }
-
 template <bool DG>
 void launch_prolong(int q, const ProlongArgs& a, hipStream_t stream)
 {
-  const dim3 grid(grid_of(a.ncells)), block(TR_THREADS);
+  const dim3 grid(grid_of(a.ncells, TR_THREADS)), block(TR_THREADS);
   switch (q)
   {
   case 1:
@@ -300,8 +298,7 @@ int common_args(const char* who, eqlb_refine_t* plan, eqlb_mesh_t* refined, int3
 {
   if (bs < 1 || nrhs < 1)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: bs = %d, nrhs = %d (both at least 1)", who, (int)bs, (int)nrhs);
-  if (memspace != EQLB_MEM_HOST && memspace != EQLB_MEM_DEVICE)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(check_memspace(who, memspace));
   const DeviceMesh &m = plan->mesh->m, &r = refined->m;
   if (r.nnodes != plan->nnodes + plan->nbis || r.ncells != plan->ncells2)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: the handle has %d nodes and %d cells, the refined mesh %d and %d", who,
@@ -348,8 +345,7 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
   if (p < 1 || p > TR_PMAX)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4", who, (int)p);
-  if (memspace != EQLB_MEM_HOST && memspace != EQLB_MEM_DEVICE)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
+  EQLB_TRY(check_memspace(who, memspace));
   const DeviceMesh& m = mesh->m;
   const int ne = p - 1, ni = (p - 1) * (p - 2) / 2, nd = nd_of(p);
   const int64_t ndofs = (int64_t)m.nnodes + (int64_t)m.nfacets * ne + (int64_t)m.ncells * ni;
@@ -357,21 +353,16 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %lld DOFs do not fit 32 bits", who, (long long)ndofs);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const size_t n = (size_t)m.ncells * nd;
-  DevBuf<int32_t> staged;
-  int32_t* out = cell_dofs;
-  if (memspace == EQLB_MEM_HOST)
-  {
-    EQLB_TRY(staged.alloc(n));
-    out = staged.get();
-  }
-  hipLaunchKernelGGL(k_lagrange_dofmap, dim3(grid_of(m.ncells)), dim3(TR_THREADS), 0, stream, m.ncells, m.nnodes,
-                     m.nfacets, (int)p, m.cell_nodes, m.cell_facets, m.facet_perm, out);
-  HIP_TRY(hipGetLastError());
-  if (memspace == EQLB_MEM_HOST)
-  {
-    HIP_TRY(hipMemcpyAsync(cell_dofs, out, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
+  const bool host = memspace == EQLB_MEM_HOST;
+  HostCall s; // (a device-memory call stages nothing: no allocation, no copy and no wait)
+  const auto staged = s.out(host ? cell_dofs : nullptr, n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  hipLaunchKernelGGL(k_lagrange_dofmap, dim3(grid_of(m.ncells, TR_THREADS)), dim3(TR_THREADS), 0, stream, m.ncells,
+                     m.nnodes, m.nfacets, (int)p, m.cell_nodes, m.cell_facets, m.facet_perm,
+                     host ? staged.get() : cell_dofs);
+  s.note(hipGetLastError());
+  HIP_TRY(s.finish(stream));
   if (ndofs_out)
     *ndofs_out = ndofs;
   return EQLB_OK;
@@ -434,25 +425,20 @@ try
   const size_t nu = (size_t)nrhs * ndofs * bs, nu2 = (size_t)nrhs * ndofs2 * bs;
   EQLB_TRY(check_dofmap(who, "cell_dofs", cell_dofs, (size_t)plan->ncells, nd, ndofs));
   EQLB_TRY(check_dofmap(who, "cell_dofs2", cell_dofs2, (size_t)plan->ncells2, nd, ndofs2));
-  DevBuf<int32_t> d_cd, d_cd2;
-  DevBuf<double> d_u, d_u2;
-  EQLB_TRY(d_cd.alloc(n1));
-  EQLB_TRY(d_cd2.alloc(n2));
-  EQLB_TRY(d_u.alloc(nu));
-  EQLB_TRY(d_u2.alloc(nu2));
-  HIP_TRY(hipMemcpyAsync(d_cd.get(), cell_dofs, sizeof(int32_t) * n1, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_cd2.get(), cell_dofs2, sizeof(int32_t) * n2, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_u.get(), u, sizeof(double) * nu, hipMemcpyHostToDevice, stream));
+  HostCall s;
+  const auto d_cd = s.in(cell_dofs, n1), d_cd2 = s.in(cell_dofs2, n2);
+  const auto d_u = s.in(u, nu);
   // (entries that no DOF of cell_dofs2 names keep what the caller had there)
-  HIP_TRY(hipMemcpyAsync(d_u2.get(), u2, sizeof(double) * nu2, hipMemcpyHostToDevice, stream));
-  a.cell_dofs = d_cd.get();
-  a.cell_dofs2 = d_cd2.get();
-  a.in = d_u.get();
-  a.out = d_u2.get();
+  const auto d_u2 = s.in(static_cast<const double*>(u2), nu2);
+  s.out_prefix(u2, d_u2, nu2);
+  HIP_TRY(s.upload(stream));
+  a.cell_dofs = d_cd;
+  a.cell_dofs2 = d_cd2;
+  a.in = d_u;
+  a.out = d_u2;
   launch_prolong<false>(p, a, stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(u2, d_u2.get(), sizeof(double) * nu2, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  s.note(hipGetLastError());
+  HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
@@ -472,27 +458,20 @@ try
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const size_t row = (size_t)nd_of(degree) * bs;
   const size_t n1 = (size_t)nrhs * plan->ncells * row, n2 = (size_t)nrhs * plan->ncells2 * row;
-  DevBuf<double> d_in, d_out;
-  a.in = in;
-  a.out = out;
-  if (memspace == EQLB_MEM_HOST)
-  {
-    EQLB_TRY(d_in.alloc(n1));
-    EQLB_TRY(d_out.alloc(n2));
-    HIP_TRY(hipMemcpyAsync(d_in.get(), in, sizeof(double) * n1, hipMemcpyHostToDevice, stream));
-    a.in = d_in.get();
-    a.out = d_out.get();
-  }
+  const bool host = memspace == EQLB_MEM_HOST;
+  HostCall s; // (a device-memory call stages nothing: no allocation, no copy and no wait)
+  const auto d_in = s.in(host ? in : nullptr, n1);
+  const auto d_out = s.out(host ? out : nullptr, n2);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  a.in = host ? d_in.get() : in;
+  a.out = host ? d_out.get() : out;
   if (degree == 0)
-    hipLaunchKernelGGL(k_prolong_dg0, dim3(grid_of(a.ncells)), dim3(TR_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_prolong_dg0, dim3(grid_of(a.ncells, TR_THREADS)), dim3(TR_THREADS), 0, stream, a);
   else
     launch_prolong<true>(degree, a, stream);
-  HIP_TRY(hipGetLastError());
-  if (memspace == EQLB_MEM_HOST)
-  {
-    HIP_TRY(hipMemcpyAsync(out, d_out.get(), sizeof(double) * n2, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
+  s.note(hipGetLastError());
+  HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }
 EQLB_CATCH_ALL

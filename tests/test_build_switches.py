@@ -1,7 +1,8 @@
 """Source lint of dolfinx_eqlb_amd/csrc: no file includes a .hip, and the EQLB_* names a -D on the
 compiler's command line can override are exactly those declared in eqlb_tuning.h (numeric
 parameters of size, occupancy and tolerance; decided code variants are resolved in the source,
-DESIGN.md "retired build switches")."""
+DESIGN.md "retired build switches").  Device memory has one home: only eqlb_host_util.h names the
+allocator, and the hand-rolled stagings it replaced stay away."""
 
 import glob
 import os
@@ -89,3 +90,30 @@ def test_every_parameter_is_used():
         if name != TUNING:
             used |= set(re.findall(r"\bEQLB_\w+", _strip_comments(text)))
     assert _overridable(src[TUNING]) <= used
+
+
+def _hip_sources():
+    return {name: text for name, text in _sources().items() if name.endswith((".hip", ".h"))}
+
+
+def test_only_the_host_helpers_name_the_device_allocator():
+    # (comments included: a file that speaks of the allocator is about to call it)
+    for name, text in _hip_sources().items():
+        if name != "eqlb_host_util.h":
+            found = sorted(set(re.findall(r"\bhip(?:Malloc|Free|MallocAsync|FreeAsync)\b", text)))
+            assert not found, f"{name}: {found}"
+    helpers = _hip_sources()["eqlb_host_util.h"]
+    for word in ("hipMalloc", "hipFree", "hipMallocAsync", "hipFreeAsync"):
+        assert re.search(rf"\b{word}\b", helpers), word
+
+
+def test_the_replaced_stagings_stay_away():
+    for name, text in _hip_sources().items():
+        for gone in (r"#\s*define\s+fail\b", r"\bstruct\s+Staging\b", r"\bstruct\s+HostStage\b"):
+            assert not re.search(gone, text), f"{name}: {gone}"
+
+
+def test_grid_of_is_defined_once():
+    defs = [name for name, text in _hip_sources().items()
+            for _ in re.finditer(r"^[ \t]*(?:\w+[ \t]+)+grid_of[ \t]*\([^;{]*\)\s*\{", _strip_comments(text), flags=re.M)]
+    assert defs == ["eqlb_host_util.h"], defs
