@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_mesh_refine_plan", "eqlb_refine_counts", "eqlb_refine_write", "eqlb_refine_create_mesh",
     "eqlb_refine_parent_facets", "eqlb_refine_destroy",
     "eqlb_mesh_lagrange_dofmap", "eqlb_get_prolong_table", "eqlb_refine_prolong_lagrange", "eqlb_refine_prolong_dg",
+    "eqlb_refine_facet_types", "eqlb_refine_child_facets", "eqlb_get_flux_bc_prolong_table",
+    "eqlb_refine_prolong_flux_bc", "eqlb_se_carry_boundary", "eqlb_ev_carry_boundary",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -111,6 +113,16 @@ def _update_flux_bc_raw(fn, eq, rhs, nlist, facets, values, s, w, vector, nrejec
     _check(fn(eq._h, C.c_int32(rhs), C.c_int32(nlist), _vp(facets), C.c_int32(nq),
               _hp(ss) if ss is not None else None, _hp(ww) if ww is not None else None, _vp(values),
               C.c_int32(1 if vector else 0), _vp(nrejected), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def _carry_boundary(fn, eq, old, refinement, node_mask, stream):
+    plan = refinement._kept_plan("carry_boundary")
+    nm = None
+    if node_mask is not None:
+        nm = np.ascontiguousarray(node_mask, dtype=np.uint8)
+        if nm.size != refinement.counts["nnodes2"]:
+            raise RuntimeError("carry_boundary: Input sizes does not match")
+    _check(fn(old._h, plan._h, eq._h, _hp(nm) if nm is not None else None, C.c_void_p(stream)))
 
 
 def _get_boundary_values(fn, eq):
@@ -445,6 +457,24 @@ class RefinePlan:
         _check(lib().eqlb_refine_prolong_dg(self._h, refined._h, C.c_int32(degree), C.c_int32(bs), C.c_int32(nrhs),
                                             _vp(values), _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
 
+    def facet_types_raw(self, refined, nrhs, facet_type, facet_type2, memspace=MEM_DEVICE, stream=0):
+        """eqlb_refine_facet_types on raw pointers (ints) in `memspace`: int8 [nrhs, nfacets] -> [nrhs, nfacets2]."""
+        _check(lib().eqlb_refine_facet_types(self._h, refined._h, C.c_int32(nrhs), _vp(facet_type), _vp(facet_type2),
+                                             C.c_int32(memspace), C.c_void_p(stream)))
+
+    def child_facets_raw(self, refined, nlist, facets, children, memspace=MEM_DEVICE, stream=0):
+        """eqlb_refine_child_facets on raw pointers (ints) in `memspace`: old ids [nlist] -> children [nlist, 2]."""
+        _check(lib().eqlb_refine_child_facets(self._h, refined._h, C.c_int32(nlist), _vp(facets), _vp(children),
+                                              C.c_int32(memspace), C.c_void_p(stream)))
+
+    def prolong_flux_bc_raw(self, refined, k, nrhs, boundary_values, nlist, facets2, dofs, memspace=MEM_DEVICE,
+                            stream=0):
+        """eqlb_refine_prolong_flux_bc on raw pointers (ints) in `memspace`: the table [nrhs, ncells*k(k+2)] of the old
+        mesh -> dofs [nrhs, nlist, k] of the listed boundary facets of `refined`."""
+        _check(lib().eqlb_refine_prolong_flux_bc(self._h, refined._h, C.c_int32(k), C.c_int32(nrhs),
+                                                 _vp(boundary_values), C.c_int32(nlist), _vp(facets2), _vp(dofs),
+                                                 C.c_int32(memspace), C.c_void_p(stream)))
+
     def close(self):
         if self._h:
             lib().eqlb_refine_destroy(self._h)
@@ -549,6 +579,80 @@ class Refinement:
         plan.prolong_dg_raw(self.dmesh, degree, bs, int(v.shape[0]), pin, pout, memspace, stream)
         return out[0] if len(values.shape) == 1 else out
 
+    def facet_types(self, facet_type, stream=0):
+        """facet_type [nrhs, nfacets] (or 1-D) int8 of the old mesh -> [nrhs, nfacets2] of the refined mesh: the type
+        of the parent facet, EQLB_FACET_INTERNAL where there is none (eqlb_refine_facet_types; the rule:
+        mesh.refine.carry_facet_types).  Host arrays, or torch tensors on the device, read and written on `stream`."""
+        plan = self._kept_plan("facet_types")
+        nf, nf2 = plan.dmesh.counts()[2], self.dmesh.counts()[2]
+        if hasattr(facet_type, "data_ptr"):
+            import torch
+            if not facet_type.is_contiguous() or facet_type.element_size() != 1:
+                raise RuntimeError("Refinement.facet_types: contiguous int8 types expected")
+            ft = facet_type.reshape(1, -1) if facet_type.dim() == 1 else facet_type
+            out = torch.empty((ft.shape[0], nf2), dtype=torch.int8, device=facet_type.device)
+            pin, pout, memspace = ft.data_ptr(), out.data_ptr(), MEM_DEVICE
+        else:
+            ft = np.ascontiguousarray(facet_type, dtype=np.int8)
+            ft = ft.reshape(1, -1) if ft.ndim == 1 else ft
+            out = np.zeros((ft.shape[0], nf2), dtype=np.int8)
+            pin, pout, memspace = ft.ctypes.data, out.ctypes.data, MEM_HOST
+        if ft.shape[1] != nf:
+            raise RuntimeError("Refinement.facet_types: Input sizes does not match")
+        plan.facet_types_raw(self.dmesh, int(ft.shape[0]), pin, pout, memspace, stream)
+        return out[0] if len(facet_type.shape) == 1 else out
+
+    def child_facets(self, facets, flat=False, stream=0):
+        """children [nlist, 2] int32 of the old facets `facets` in the numbering of the refined mesh, (f2, -1) for a
+        facet that is not bisected (eqlb_refine_child_facets; the rule: mesh.refine.child_facets) - the inverse of
+        `.parent_facet` for the facets of a flux boundary condition, a Dirichlet list, facet tags.  flat=True (host
+        arrays): the list of the children without the -1 entries, in the order of `facets`.  Host arrays, or torch
+        tensors on the device, read and written on `stream`."""
+        plan = self._kept_plan("child_facets")
+        if hasattr(facets, "data_ptr"):
+            import torch
+            if flat:
+                raise RuntimeError("Refinement.child_facets: flat=True needs host arrays")
+            if not facets.is_contiguous() or facets.element_size() != 4:
+                raise RuntimeError("Refinement.child_facets: contiguous int32 ids expected")
+            out = torch.empty((facets.numel(), 2), dtype=torch.int32, device=facets.device)
+            plan.child_facets_raw(self.dmesh, int(facets.numel()), facets.data_ptr(), out.data_ptr(), MEM_DEVICE,
+                                  stream)
+            return out
+        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+        out = np.zeros((fl.size, 2), dtype=np.int32)
+        plan.child_facets_raw(self.dmesh, fl.size, fl.ctypes.data, out.ctypes.data, MEM_HOST, stream)
+        return out[out >= 0] if flat else out
+
+    def prolong_flux_bc(self, k, boundary_values, facets2, stream=0):
+        """The table boundary_values [nrhs, ncells*k(k+2)] (or 1-D) of the old mesh -> dofs [nrhs, nlist, k] of the
+        boundary facets `facets2` of the refined mesh, each row as update_flux_bc takes it without a rule
+        (eqlb_refine_prolong_flux_bc; the rule: mesh.transfer.prolong_flux_bc).  Host arrays, or torch tensors on the
+        device, read and written on `stream`."""
+        plan = self._kept_plan("prolong_flux_bc")
+        nc = plan.dmesh.counts()[1]
+        ntab = nc * max(int(k), 0) * (max(int(k), 0) + 2)
+        if hasattr(boundary_values, "data_ptr"):
+            import torch
+            if not (boundary_values.is_contiguous() and facets2.is_contiguous()) \
+                    or boundary_values.element_size() != 8 or facets2.element_size() != 4:
+                raise RuntimeError("Refinement.prolong_flux_bc: contiguous float64 values and int32 ids expected")
+            bv = boundary_values.reshape(1, -1) if boundary_values.dim() == 1 else boundary_values
+            nlist = int(facets2.numel())
+            out = torch.empty((bv.shape[0], nlist, max(int(k), 0)), dtype=torch.float64, device=bv.device)
+            ptrs, memspace = (bv.data_ptr(), facets2.data_ptr(), out.data_ptr()), MEM_DEVICE
+        else:
+            bv = np.ascontiguousarray(boundary_values, dtype=np.float64)
+            bv = bv.reshape(1, -1) if bv.ndim == 1 else bv
+            fl = np.ascontiguousarray(facets2, dtype=np.int32).ravel()
+            nlist = fl.size
+            out = np.zeros((bv.shape[0], nlist, max(int(k), 0)))
+            ptrs, memspace = (bv.ctypes.data, fl.ctypes.data, out.ctypes.data), MEM_HOST
+        if ntab > 0 and bv.shape[1] != ntab:
+            raise RuntimeError("Refinement.prolong_flux_bc: Input sizes does not match")
+        plan.prolong_flux_bc_raw(self.dmesh, k, int(bv.shape[0]), ptrs[0], nlist, ptrs[1], ptrs[2], memspace, stream)
+        return out[0] if len(boundary_values.shape) == 1 else out
+
     def close(self):
         """Releases the kept plan (the refined DeviceMesh stays)."""
         if self.plan is not None:
@@ -601,6 +705,13 @@ class SemiExplicitEquilibrator:
         Device memory: one kernel, nothing waits; nrejected [1] int32 (or None) counts the refused entries."""
         _update_flux_bc_raw(lib().eqlb_se_update_flux_bc, self, rhs, nlist, facets, values, s, w, vector, nrejected,
                             memspace, stream)
+
+    def carry_boundary(self, old, refinement, node_mask=None, stream=0):
+        """eqlb_se_carry_boundary: the boundary conditions of `old` (a SemiExplicitEquilibrator on the coarse mesh with
+        an accepted set_boundary) set on this handle, which lives on `refinement.dmesh`; `refinement` keeps its plan
+        (DeviceMesh.refine(..., keep_plan=True)).  The facet types are gathered on the device and planned as
+        set_boundary plans them; a value table of `old` is carried from table to table on the device."""
+        _carry_boundary(lib().eqlb_se_carry_boundary, self, old, refinement, node_mask, stream)
 
     def get_boundary_values(self):
         """eqlb_se_get_boundary_values: the table [nrhs, ncells*k(k+2)] of the handle (zeros if homogeneous)."""
@@ -796,6 +907,11 @@ class ConstrainedMinEquilibrator:
         Device memory: one kernel, nothing waits; nrejected [1] int32 (or None) counts the refused entries."""
         _update_flux_bc_raw(lib().eqlb_ev_update_flux_bc, self, rhs, nlist, facets, values, s, w, vector, nrejected,
                             memspace, stream)
+
+    def carry_boundary(self, old, refinement, node_mask=None, stream=0):
+        """eqlb_ev_carry_boundary: as SemiExplicitEquilibrator.carry_boundary, on the broken per-cell table of the EV
+        handle; the dofmap and the basis transform of this handle are set first, as before set_boundary."""
+        _carry_boundary(lib().eqlb_ev_carry_boundary, self, old, refinement, node_mask, stream)
 
     def get_boundary_values(self):
         """eqlb_ev_get_boundary_values: the table [nrhs, ncells*k(k+2)] of the handle in the broken per-cell
@@ -1131,6 +1247,16 @@ def get_prolong_table(q: int):
     nrow, nd = (2 * max(q, 0) + 1) * (max(q, 0) + 1), (max(q, 0) + 1) * (max(q, 0) + 2) // 2
     out = np.zeros((nrow, nd))
     n = lib().eqlb_get_prolong_table(C.c_int32(q), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
+def get_flux_bc_prolong_table(k: int):
+    """The built-in table FB<k> [6, k, k] of the flux-BC prolongation (eqlb_get_flux_bc_prolong_table), 1 <= k <= 4."""
+    kk = max(int(k), 1)
+    out = np.zeros((6, kk, kk))
+    n = lib().eqlb_get_flux_bc_prolong_table(C.c_int32(k), _hp(out), C.c_int32(out.size))
     if n < 0:
         _check(n)
     return out

@@ -2,8 +2,8 @@
 // the owners of device memory (DevBuf, DevCarve, StreamBuf - no other file names the allocator), the staged host call
 // (HostCall), the exception barrier of the entry points, set-up profiling.  Host code only.  Included
 //   through eqlb_handle.h by eqlb_api.hip, eqlb_boundary_setup.hip, eqlb_boundary_update.hip, eqlb_sweep.hip,
-//     eqlb_tiling_host.hip,
-//   through eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip,
+//     eqlb_tiling_host.hip, eqlb_bc_carry.hip,
+//   through eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip, eqlb_bc_carry.hip,
 //   through eqlb_estimate_kernels.h by eqlb_estimate.hip, eqlb_estimate_lowdeg.hip, eqlb_estimate_lowdeg_k4.hip,
 //   directly by eqlb_mesh_build.hip, eqlb_marking.hip, eqlb_primal_flux.hip, eqlb_tiling_device.hip,
 //     eqlb_halo_rccl.hip.

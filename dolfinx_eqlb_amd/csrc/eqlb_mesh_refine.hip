@@ -22,6 +22,7 @@
 // of the old coordinates; eqlb_refine_parent_facets one kernel over the facets of the refined handle.
 // The number of launches depends on ncells alone.  The flags are bytes (cells) and words (facets, scanned as they
 // are); the only atomics are atomicMin on the error word and one integer add per wave for the count of cut cells.
+#include "eqlb_refine_device.h"
 #include "eqlb_refine_plan.h"
 
 #include <cstring> // (rocprim's texture iterator calls memset)
@@ -266,26 +267,7 @@ k_parent_facets(int32_t nfacets2, int32_t nnodes, const int32_t* __restrict__ fa
   const int32_t f2 = blockIdx.x * blockDim.x + threadIdx.x;
   if (f2 >= nfacets2)
     return;
-  const int32_t n0 = facet_nodes2[2 * (int64_t)f2], n1 = facet_nodes2[2 * (int64_t)f2 + 1];
-  const int32_t lo = n0 < n1 ? n0 : n1, hi = n0 < n1 ? n1 : n0;
-  int32_t found = -1;
-  if (hi < nnodes)
-  {
-    for (int32_t q = node_facets_off[lo]; q < node_facets_off[lo + 1] && found < 0; ++q)
-    {
-      const int32_t g = node_facets[q];
-      const int32_t a = facet_nodes[2 * (int64_t)g], b = facet_nodes[2 * (int64_t)g + 1];
-      if ((a == lo && b == hi) || (a == hi && b == lo))
-        found = g;
-    }
-  }
-  else if (lo < nnodes)
-  {
-    const int32_t g = bis_facet[hi - nnodes];
-    if (facet_nodes[2 * (int64_t)g] == lo || facet_nodes[2 * (int64_t)g + 1] == lo)
-      found = g;
-  }
-  parent_facet[f2] = found;
+  parent_facet[f2] = parent_facet_of(f2, nnodes, facet_nodes2, bis_facet, facet_nodes, node_facets_off, node_facets);
 }
 
 const char* const WHO = "eqlb_mesh_refine_plan";

@@ -238,6 +238,43 @@ struct Transfer
                                  EQLB_MEM_HOST, nullptr));
     return out;
   }
+
+  // facet_type [nrhs, nfacets] or 1-D -> [nrhs, nfacets2] (eqlb_refine_facet_types)
+  py::array_t<int8_t> facet_types(carray<int8_t> facet_type) const
+  {
+    const py::ssize_t nrhs = facet_type.ndim() == 2 ? facet_type.shape(0) : 1;
+    if (facet_type.size() != nrhs * coarse->nfacets)
+      throw std::runtime_error("Transfer.facet_types: Input sizes does not match");
+    py::array_t<int8_t> out({nrhs, (py::ssize_t)fine->nfacets});
+    check(eqlb_refine_facet_types(plan, fine->h, (int32_t)nrhs, facet_type.data(), out.mutable_data(), EQLB_MEM_HOST,
+                                  nullptr));
+    return out;
+  }
+
+  // old facet ids [nlist] -> children [nlist, 2] in the numbering of the refined mesh (eqlb_refine_child_facets)
+  py::array_t<int32_t> child_facets(carray<int32_t> facets) const
+  {
+    const py::ssize_t nlist = facets.size();
+    py::array_t<int32_t> out({nlist, (py::ssize_t)2});
+    check(eqlb_refine_child_facets(plan, fine->h, (int32_t)nlist, facets.data(), out.mutable_data(), EQLB_MEM_HOST,
+                                   nullptr));
+    return out;
+  }
+
+  // boundary_values [nrhs, ncells*k(k+2)] or 1-D -> dofs [nrhs, nlist, k] of the boundary facets facets2 of the
+  // refined mesh (eqlb_refine_prolong_flux_bc)
+  darray prolong_flux_bc(int k, darray boundary_values, carray<int32_t> facets2) const
+  {
+    if (k < 1 || k > 4)
+      throw std::runtime_error("Transfer.prolong_flux_bc: k outside 1 ... 4");
+    const py::ssize_t nrhs = boundary_values.ndim() == 2 ? boundary_values.shape(0) : 1, nlist = facets2.size();
+    if (boundary_values.size() != nrhs * coarse->ncells * k * (k + 2))
+      throw std::runtime_error("Transfer.prolong_flux_bc: Input sizes does not match");
+    darray out({nrhs, nlist, (py::ssize_t)k});
+    check(eqlb_refine_prolong_flux_bc(plan, fine->h, k, (int32_t)nrhs, boundary_values.data(), (int32_t)nlist,
+                                      facets2.data(), out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
 };
 
 py::tuple Mesh::refine(std::shared_ptr<Mesh> self, carray<int32_t> marked, bool keep_plan)
@@ -1056,6 +1093,13 @@ PYBIND11_MODULE(_cpp, m)
            "u [nrhs, ndofs*bs] in P_p on the old mesh -> [nrhs, ndofs2*bs] on the refined mesh")
       .def("prolong_dg", &Transfer::prolong_dg, py::arg("degree"), py::arg("values"), py::arg("bs") = 1,
            "DG_degree values [nrhs, ncells*nd*bs] -> [nrhs, ncells2*nd*bs]")
+      .def("facet_types", &Transfer::facet_types, py::arg("facet_type"),
+           "facet types [nrhs, nfacets] of the old mesh -> [nrhs, nfacets2]: the type of the parent facet, 0 without one")
+      .def("child_facets", &Transfer::child_facets, py::arg("facets"),
+           "old facet ids [nlist] -> children [nlist, 2] on the refined mesh, (f2, -1) for a facet that is not bisected")
+      .def("prolong_flux_bc", &Transfer::prolong_flux_bc, py::arg("k"), py::arg("boundary_values"), py::arg("facets2"),
+           "flux-BC table [nrhs, ncells*k(k+2)] of the old mesh -> facet DOFs [nrhs, nlist, k] of the listed boundary "
+           "facets of the refined mesh")
       .def_readonly("coarse", &Transfer::coarse)
       .def_readonly("fine", &Transfer::fine);
 

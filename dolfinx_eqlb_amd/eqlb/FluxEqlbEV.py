@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _adapter
 from ..mesh import Mesh
-from .bcs import boundarydata, fluxbc
+from .bcs import boundarydata, fluxbc, refined_conditions
 from .conforming import conforming_dofmap
 
 
@@ -69,6 +69,17 @@ class FluxEqlbEV:
         if self.large_patches:
             self.boundary_data.set_option("large_patches", 1)
         self.facet_type = self.boundary_data.facet_type
+        self.list_bfct_prime, self.list_bcs_flux = list(list_bfct_prime), [list(b) for b in list_bcs_flux]
+
+    def refined(self, transfer, list_rhs: typing.List[np.ndarray], list_proj_flux: typing.List[np.ndarray]):
+        """As FluxEqlbSE.refined: the equilibrator on the refined mesh of `transfer` with the same degree and
+        `large_patches`, the data of the fine mesh, and the boundary conditions of this one on the child facets."""
+        if self.boundary_data is None:
+            raise RuntimeError("Boundary conditions have not been set")
+        fine, prime, bcs = refined_conditions(transfer, self.list_bfct_prime, self.list_bcs_flux)
+        eq = FluxEqlbEV(self.degree_flux, fine, list_rhs, list_proj_flux, self.large_patches)
+        eq.set_boundary_conditions(prime, bcs)
+        return eq
 
     def update_boundary_values(self):
         """New values of the flux BCs on the same facets - a `fluxbc` whose callable closes over a time or a load

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _adapter
 from ..mesh import Mesh
-from .bcs import boundarydata, fluxbc  # noqa: F401  (fluxbc is re-exported from here)
+from .bcs import boundarydata, fluxbc, refined_conditions  # noqa: F401  (fluxbc is re-exported from here)
 
 
 class FluxEqlbSE:
@@ -83,6 +83,21 @@ class FluxEqlbSE:
                 # weak symmetry and Korn constants on those patches as well
                 self.boundary_data.set_option("large_patches_stress", 1)
         self.facet_type = self.boundary_data.facet_type
+        self.list_bfct_prime, self.list_bcs_flux = list(list_bfct_prime), [list(b) for b in list_bcs_flux]
+
+    def refined(self, transfer, list_rhs: typing.List[np.ndarray], list_proj_flux: typing.List[np.ndarray]):
+        """The equilibrator of the next level of an adaptive loop: on the refined mesh of `transfer` (a
+        `_cpp.Transfer` of Mesh.refine(..., keep_plan=True), or a `cpp.Refinement` with its plan kept), with the same
+        degree and flags, the data `list_rhs` / `list_proj_flux` of the fine mesh, and the boundary conditions of this
+        one: every facet list goes through `child_facets`, every `fluxbc` is evaluated again on the fine facets.
+        Not in the reference, whose demos set the conditions up again on every level."""
+        if self.boundary_data is None:
+            raise RuntimeError("Boundary conditions have not been set")
+        fine, prime, bcs = refined_conditions(transfer, self.list_bfct_prime, self.list_bcs_flux)
+        eq = FluxEqlbSE(self.degree_flux, fine, list_rhs, list_proj_flux, self.equilibrate_stresses,
+                        self.estimate_korn_constant, self.large_patches)
+        eq.set_boundary_conditions(prime, bcs)
+        return eq
 
     def update_boundary_values(self):
         """New values of the flux BCs on the same facets - a `fluxbc` whose callable closes over a time or a load

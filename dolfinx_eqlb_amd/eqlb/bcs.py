@@ -101,6 +101,32 @@ class fluxbc:
         return c.FluxBC(V, facets, ptr, int(nq), [], [], [])
 
 
+def refined_conditions(transfer, list_bfct_prime, list_bcs_flux):
+    """(fine mesh, list_bfct_prime, list_bcs_flux) on the refined mesh of `transfer` - a `_cpp.Transfer`
+    (Mesh.refine(..., keep_plan=True)) or a `cpp.Refinement` with its plan kept.  Every Dirichlet list and every
+    `fluxbc.facets` list goes through `child_facets`; each `fluxbc` is rebuilt with the same value, `scalar`,
+    `requires_projection` and quadrature degree, so its callable is evaluated again on the fine facets - what a
+    DOLFINx user gets from transferred facet tags."""
+    from ..mesh import Mesh, create_mesh
+
+    fine = getattr(transfer, "fine", None)
+    if fine is None:
+        fine = transfer.dmesh.mesh
+    if not isinstance(fine, Mesh):
+        handle = fine
+        fine = create_mesh(np.asarray(handle.x)[:, :2], np.asarray(handle.cell_nodes, dtype=np.int32))
+        fine._cpp_mesh = handle   # (_adapter.cpp_mesh: the handle of the refinement serves the spaces as well)
+
+    def children(facets):
+        ch = np.asarray(transfer.child_facets(np.ascontiguousarray(facets, dtype=np.int32).ravel()))
+        return ch[ch >= 0].astype(np.int32)
+
+    prime = [children(d) for d in list_bfct_prime]
+    bcs = [[fluxbc(bc.value, children(bc.facets), None, bc.requires_projection, bc._quadrature_degree, bc.scalar)
+            for bc in row] for row in list_bcs_flux]
+    return fine, prime, bcs
+
+
 def boundarydata(flux_conditions: typing.List[typing.List[fluxbc]],
                  boundary_data: typing.List[typing.Any], V, custom_rt: bool,
                  dirichlet_facets: typing.List[np.ndarray], equilibrate_stress: bool):

@@ -17,6 +17,10 @@ eqlb_refine_* entries of include/eqlb.h) reproduces it bit for bit.
            The children of cell c start at the exclusive prefix sum of 1 + (number of its facets in E).
 
 With every cell marked this is the longest-edge 4-split, not a red refinement.
+
+Between the facets of the two meshes: parent_facets (eqlb_refine_parent_facets), and from it carry_facet_types
+(eqlb_refine_facet_types: the type table of the equilibrator on the refined mesh) and its inverse for facet lists,
+child_facets (eqlb_refine_child_facets).
 """
 
 import numpy as np
@@ -132,3 +136,46 @@ def parent_facets(mesh, node_parent_facet, mesh2):
     on_parent = (fn[g, 0] == lo[one_new]) | (fn[g, 1] == lo[one_new])
     out[one_new] = np.where(on_parent, g, -1)
     return out
+
+
+def carry_facet_types(facet_type, parent_facet):
+    """facet_type2 [nrhs, nfacets2] int8 (or 1-D) of the refined mesh: the type of the parent facet, EQLB_FACET_INTERNAL
+    (0) where a facet has none (parent_facet < 0) - the statement of eqlb_refine_facet_types.  Any old value is copied
+    as it is."""
+    ft = np.asarray(facet_type, dtype=np.int8)
+    pf = np.asarray(parent_facet, dtype=np.int64)
+    if ft.shape[-1] == 0:
+        return np.zeros(ft.shape[:-1] + (pf.size,), dtype=np.int8)
+    return np.where(pf < 0, np.int8(0), ft[..., np.maximum(pf, 0)]).astype(np.int8)
+
+
+def child_facets(mesh, node_parent_facet, mesh2, facets=None):
+    """children [n, 2] int32 of the old facets `facets` (None: all of them) in the facet numbering of the refined mesh
+    `mesh2` - the inverse of parent_facets, for facet lists.  An old facet with the nodes lo < hi that is not bisected
+    has (facet(lo, hi), -1); one bisected by the new node m has (facet(lo, m), facet(m, hi)).  A pair that is no facet
+    of mesh2 gives -1 (a mesh2 that is not the refined mesh)."""
+    nn, nn2 = mesh.nnodes, mesh2.nnodes
+    f = np.arange(mesh.nfacets, dtype=np.int64) if facets is None else np.asarray(facets, dtype=np.int64).ravel()
+    bad = f[(f < 0) | (f >= mesh.nfacets)]
+    if bad.size:
+        raise ValueError(f"child_facets: facet {int(bad[0])} outside [0, {mesh.nfacets})")
+    npf = np.asarray(node_parent_facet, dtype=np.int64)
+    new_node = np.full(mesh.nfacets, -1, dtype=np.int64)
+    new_node[npf] = nn + np.arange(npf.size)
+    fn = mesh.facet_nodes.astype(np.int64)
+    lo, hi = fn[f].min(axis=1), fn[f].max(axis=1)
+    m = new_node[f]
+
+    fn2 = mesh2.facet_nodes.astype(np.int64)
+    keys = fn2.min(axis=1) * nn2 + fn2.max(axis=1)
+    order = np.argsort(keys, kind="stable")
+
+    def find(a, b):
+        k = np.minimum(a, b) * nn2 + np.maximum(a, b)
+        pos = np.minimum(np.searchsorted(keys[order], k), keys.size - 1)
+        return np.where(keys[order][pos] == k, order[pos], -1)
+
+    cut = m >= 0
+    first = np.where(cut, find(lo, np.where(cut, m, hi)), find(lo, hi))
+    second = np.where(cut, find(np.where(cut, m, lo), hi), -1)
+    return np.stack([first, second], axis=1).astype(np.int32)

@@ -21,6 +21,9 @@ Function of the old mesh into the space of the new one).  This file defines the 
             the refined mesh, a facet DOF from the first cell of its facet -> cell table, an interior DOF from its cell
 
 DG_0 is the constant: every child takes the value of its parent.
+
+The flux-BC DOF table of the equilibrator crosses the refinement by prolong_flux_bc (eqlb_refine_prolong_flux_bc); its
+rule stands in front of it below.
 """
 
 from fractions import Fraction
@@ -198,3 +201,131 @@ def prolong_lagrange(mesh, mesh2, parent_cell, node_parent_facet, p, u, cell_dof
     if one:
         u2, A2 = u2[0], A2[0]
     return (u2, A2) if return_abs else u2
+
+
+# ---- flux boundary conditions -------------------------------------------------------------------------------------
+# The facet DOFs of local facet l of a cell are moments of the normal flux g (csrc/eqlb_boundary_update.hip):
+#   DOF_j = pf_l sign(det J) |E| int_0^1 g(s) s^j ds,  pf_l = +1 for l = 1, -1 otherwise,
+# s from the low local vertex va = (l == 0) ? 1 : 0 to vb = (l == 2) ? 1 : 2.  A boundary facet of the refined mesh is
+# a whole parent facet or one of its halves, and a child keeps the orientation of its parent: with (a, b) the positions
+# of the child's va, vb nodes on the parent facet (0: the parent's va node, 1: its vb node, 1/2: the bisecting node;
+# node ids are matched, never coordinates), s = alpha + beta t, alpha = a, beta = b - a, and
+#   dof2_j = sigma sum_i FB[m][j][i] dof_i,  sigma = pf_{l2} pf_l,  FB[m] = |beta| M H^{-1},
+#   M[j][n] = int_0^1 (alpha + beta t)^n t^j dt,  H[j][i] = 1 / (i + j + 1)
+# - the facet length cancels, no coordinates are read.  Every product is rounded on its own, the sum runs in ascending
+# i, sigma is applied last.
+
+FLUX_BC_MAPS = ((0, 2), (2, 0), (0, 1), (1, 2), (1, 0), (2, 1))   # (a, b) in half units, in the order of the table
+
+
+def _solve_exact(A, B):
+    """A^{-1} B in Fractions (Gauss-Jordan with the first non-zero pivot)."""
+    n = len(A)
+    M = [list(A[i]) + list(B[i]) for i in range(n)]
+    for c in range(n):
+        piv = next(r for r in range(c, n) if M[r][c] != 0)
+        M[c], M[piv] = M[piv], M[c]
+        M[c] = [v / M[c][c] for v in M[c]]
+        for r in range(n):
+            if r != c and M[r][c] != 0:
+                M[r] = [v - M[r][c] * w for v, w in zip(M[r], M[c])]
+    return [row[n:] for row in M]
+
+
+@lru_cache(maxsize=None)
+def flux_bc_table_exact(k):
+    """FB [6][k][k] Fractions: the facet DOFs of a child facet from those of its parent, one matrix per map of
+    FLUX_BC_MAPS."""
+    if k < 1 or k > 4:
+        raise ValueError(f"flux_bc_table: k = {k} outside 1 ... 4")
+    from math import comb
+    H = [[Fraction(1, i + j + 1) for i in range(k)] for j in range(k)]
+    Hinv = _solve_exact(H, [[Fraction(int(i == j)) for j in range(k)] for i in range(k)])
+    out = []
+    for a2, b2 in FLUX_BC_MAPS:
+        al, be = Fraction(a2, 2), Fraction(b2 - a2, 2)
+        M = [[sum((comb(n, r) * al ** (n - r) * be ** r * Fraction(1, j + r + 1) for r in range(n + 1)), Fraction(0))
+              for n in range(k)] for j in range(k)]
+        out.append(tuple(tuple(abs(be) * sum((M[j][n] * Hinv[n][i] for n in range(k)), Fraction(0))
+                               for i in range(k)) for j in range(k)))
+    return tuple(out)
+
+
+def flux_bc_table(k):
+    """The table [6, k, k] as doubles, each entry rounded once."""
+    return np.array([[[float(v) for v in row] for row in m] for m in flux_bc_table_exact(k)])
+
+
+def flux_bc_maps(mesh, mesh2, parent_cell, node_parent_facet, facets2):
+    """(cell2, l2, cell, l, m) of the listed boundary facets of the refined mesh: the one cell of the facet and its
+    local index there, the parent cell and the local index of the parent facet there, the map of FLUX_BC_MAPS."""
+    from .refine import parent_facets
+    f2 = np.asarray(facets2, dtype=np.int64).ravel()
+    nn = mesh.nnodes
+    for i, f in enumerate(f2):
+        if f < 0 or f >= mesh2.nfacets:
+            raise ValueError(f"prolong_flux_bc: facets2[{i}] = {int(f)} is no facet of the refined mesh")
+    cnt = np.diff(mesh2.facet_cells_offsets)[f2]
+    if np.any(cnt != 1):
+        i = int(np.nonzero(cnt != 1)[0][0])
+        raise ValueError(f"prolong_flux_bc: facets2[{i}] = {int(f2[i])} lies between two cells")
+    pf = parent_facets(mesh, node_parent_facet, mesh2).astype(np.int64)[f2]
+    if np.any(pf < 0):
+        i = int(np.nonzero(pf < 0)[0][0])
+        raise ValueError(f"prolong_flux_bc: facets2[{i}] = {int(f2[i])} has no parent facet")
+    npf = np.asarray(node_parent_facet, dtype=np.int64)
+    C = mesh2.facet_cells[mesh2.facet_cells_offsets[f2]].astype(np.int64)
+    P = np.asarray(parent_cell, dtype=np.int64)[C]
+    hit2 = mesh2.cell_facets[C] == f2[:, None]
+    hit = mesh.cell_facets[P] == pf[:, None]
+    if not (np.all(hit2.sum(axis=1) == 1) and np.all(hit.sum(axis=1) == 1)):
+        raise ValueError("prolong_flux_bc: the parent facet is no facet of the parent cell")
+    l2, l = np.argmax(hit2, axis=1), np.argmax(hit, axis=1)
+    va = lambda lf: np.where(lf == 0, 1, 0)   # noqa: E731  (the low local vertex first)
+    vb = lambda lf: np.where(lf == 2, 1, 2)   # noqa: E731
+    rows = np.arange(f2.size)
+    w, v = mesh2.cell_nodes.astype(np.int64)[C], mesh.cell_nodes.astype(np.int64)[P]
+    pa, pb = v[rows, va(l)], v[rows, vb(l)]
+
+    def position(n):
+        new = n >= nn
+        mid = new & (npf[np.where(new, n - nn, 0)] == pf) if npf.size else np.zeros_like(new)
+        return np.where(n == pa, 0, np.where(n == pb, 2, np.where(mid, 1, -1)))
+
+    a, b = position(w[rows, va(l2)]), position(w[rows, vb(l2)])
+    m = np.full(f2.size, -1, dtype=np.int64)
+    for idx, (a2, b2) in enumerate(FLUX_BC_MAPS):
+        m[(a == a2) & (b == b2)] = idx
+    if np.any(m < 0):
+        raise ValueError("prolong_flux_bc: a facet is neither its parent facet nor one of its halves")
+    return C, l2, P, l, m
+
+
+def apply_flux_bc_maps(k, m, dofs, sigma):
+    """(val, A) [..., nlist, k]: sigma sum_i FB[m][j][i] dofs[..., i] and sum_i |FB| |dofs| for the maps m [nlist] and
+    the signs sigma [nlist]; dofs [..., nlist, k].  Products rounded one by one, added in ascending i, sigma last."""
+    T = flux_bc_table(k)[np.asarray(m, dtype=np.int64)]                 # [nlist, k, k]
+    d = np.asarray(dofs, dtype=np.float64)
+    val = T[..., 0] * d[..., None, 0]
+    A = np.abs(T[..., 0]) * np.abs(d[..., None, 0])
+    for i in range(1, k):
+        val = val + T[..., i] * d[..., None, i]
+        A = A + np.abs(T[..., i]) * np.abs(d[..., None, i])
+    return np.asarray(sigma, dtype=np.float64)[:, None] * val, A
+
+
+def prolong_flux_bc(mesh, mesh2, parent_cell, node_parent_facet, k, boundary_values, facets2, return_abs=False):
+    """boundary_values [nrhs, ncells*k(k+2)] (the layout of eqlb_se_set_boundary; or 1-D) of the old mesh ->
+    dofs [nrhs, nlist, k]: the facet DOFs of the boundary facets `facets2` of the refined mesh, each row in the form
+    update_flux_bc takes without a rule.  return_abs: also A_j = sum_i |FB[m][j][i]| |dof_i|."""
+    C, l2, P, l, m = flux_bc_maps(mesh, mesh2, parent_cell, node_parent_facet, facets2)
+    nrt = k * (k + 2)
+    bv = np.asarray(boundary_values, dtype=np.float64)
+    one = bv.ndim == 1
+    bv = bv.reshape(-1, mesh.ncells, nrt)
+    d = bv[:, P[:, None], l[:, None] * k + np.arange(k)[None, :]]       # [nrhs, nlist, k]
+    sigma = np.where(l2 == 1, 1.0, -1.0) * np.where(l == 1, 1.0, -1.0)
+    val, A = apply_flux_bc_maps(k, m, d, sigma)
+    if one:
+        val, A = val[0], A[0]
+    return (val, A) if return_abs else val

@@ -718,8 +718,10 @@ int eqlb_refine_parent_facets(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t
  *   owner     every global P_p DOF is written once: a vertex DOF by the first cell of the node -> cell table of the
  *             refined handle, a facet DOF by the first cell of its facet -> cell table, an interior DOF by its cell.
  *             No atomics, no reduction across threads: the result does not depend on scheduling
- * Not provided: DOLFINx' GLL-warped node set at p >= 3 (its DOF points are no lattice points), the flux-boundary DOF
- * table, restriction / coarsening, several levels in one call, distributed meshes.
+ * The boundary conditions of the equilibrator cross the refinement through the entries behind
+ * eqlb_refine_prolong_dg (eqlb_refine_facet_types ... eqlb_ev_carry_boundary).
+ * Not provided: DOLFINx' GLL-warped node set at p >= 3 (its DOF points are no lattice points), restriction /
+ * coarsening, several levels in one call, distributed meshes.
  */
 
 /* The cell dofmap of the conforming P_p space (1 <= p <= 4) in the numbering of the project's own solvers - for a
@@ -767,6 +769,81 @@ int eqlb_refine_prolong_lagrange(eqlb_refine_t* plan, eqlb_mesh_t* refined, int3
  * Memory spaces, launch and refusals as eqlb_refine_prolong_lagrange (degree in place of p). */
 int eqlb_refine_prolong_dg(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t degree, int32_t bs, int32_t nrhs,
                            const double* in, double* out, int32_t memspace, void* stream);
+
+/*
+ * Boundary conditions across the refinement: what a DOLFINx caller gets from transferring facet tags to the mesh of
+ * mesh.refine and setting the boundary conditions up again.  dolfinx_eqlb_amd.mesh.refine (carry_facet_types,
+ * child_facets) and mesh.transfer (prolong_flux_bc) state the result in numpy; these entries reproduce it bit for bit.
+ *   types     facet_type2[r][f2] = parent_facet[f2] < 0 ? EQLB_FACET_INTERNAL : facet_type[r][parent_facet[f2]], with
+ *             parent_facet exactly as eqlb_refine_parent_facets defines it
+ *   children  the inverse, for facet lists: an old facet with the nodes lo < hi that is not bisected has the children
+ *             (f2, -1), f2 the facet (lo, hi) of the refined mesh; one bisected by the new node m has
+ *             (facet(lo, m), facet(m, hi))
+ *   values    the table [nrhs][ncells * k(k+2)] of eqlb_se_set_boundary keeps the k DOFs of local facet l of a cell at
+ *             cell * k(k+2) + l * k + j:  DOF_j = pf_l sign(det J) |E| int_0^1 g(s) s^j ds, pf_l = +1 for l = 1 and -1
+ *             otherwise, s from the low local vertex va = (l == 0) ? 1 : 0 to vb = (l == 2) ? 1 : 2.  A boundary facet
+ *             f2 of the refined mesh, local facet l2 of its one cell C, is the parent facet parent_facet[f2] (local
+ *             facet l of the parent cell P) or one of its halves.  The position of a node of f2 on the parent facet is
+ *             0 if it is P's va node, 1 if it is P's vb node, 1/2 if it is the node that bisects the facet - found by
+ *             matching node ids, never coordinates.  With (a, b) the positions of C's own va, vb nodes the child
+ *             parameter t maps to s = a + (b - a) t; the six maps in the order of the table are
+ *             (0,1) (1,0) (0,1/2) (1/2,1) (1/2,0) (1,1/2).  Reading the parent DOFs as the moments of the one g in
+ *             P_{k-1} that has them,
+ *               dof2_j = sigma sum_i FB<k>[m][j][i] dof_i,  sigma = pf_{l2} pf_l,  FB<k>[m] = |b - a| M H^{-1},
+ *               M[j][n] = int_0^1 (a + (b - a) t)^n t^j dt,  H[j][i] = 1 / (i + j + 1):
+ *             exact rationals rounded once to double (tools/gen_tables.py).  Children keep the orientation of their
+ *             parent, so the two sign(det J) cancel, and so does the facet length.  Every product is rounded on its
+ *             own and added in ascending i, sigma is applied last: a whole, equally directed facet carries its DOFs
+ *             bit for bit, everything at k = 1 is exact, two calls give the same bits
+ * All of them: one thread per facet or per list entry, every index checked before it addresses anything.  Device memory
+ * space: one kernel on `stream`, nothing waits; host memory space: staged, synchronous, a refusal names the offender
+ * and nothing is written.  Refusals (EQLB_ERR_INVALID_ARGUMENT, before anything is launched; the next valid call
+ * works): null arguments, k outside 1 ... 4, nrhs < 1, nlist < 0, an unknown memory space, a `refined` whose node or
+ * cell count is not the plan's.
+ */
+
+/* facet_type [nrhs][nfacets] of the mesh of the plan -> facet_type2 [nrhs][nfacets2] of `refined`, OVERWRITTEN.  A
+ * value outside EQLB_FACET_* is copied as it is (eqlb_se_set_boundary refuses it). */
+int eqlb_refine_facet_types(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t nrhs, const int8_t* facet_type,
+                            int8_t* facet_type2, int32_t memspace, void* stream);
+
+/* children [nlist][2] of the old facets facets [nlist] (the facets of a flux boundary condition, of a Dirichlet list,
+ * facet tags), in the numbering of `refined`.  An id outside [0, nfacets): host memory space: refused by name; device
+ * memory space: (-1, -1). */
+int eqlb_refine_child_facets(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t nlist, const int32_t* facets,
+                             int32_t* children, int32_t memspace, void* stream);
+
+/* The built-in table FB<k> [6][k][k], 1 <= k <= 4, host only (like eqlb_get_prolong_table): returns the number of
+ * doubles copied (<= capacity), or a negative error. */
+int eqlb_get_flux_bc_prolong_table(int32_t k, double* out, int32_t capacity);
+
+/* boundary_values [nrhs][ncells * k(k+2)] on the mesh of the plan -> dofs [nrhs][nlist][k], the facet DOFs of the
+ * listed boundary facets facets2 [nlist] of `refined`: each row in the form eqlb_*_update_flux_bc takes with nq = 0.
+ * A listed facet that is out of range, lies between two cells or has no parent: host memory space: refused by name,
+ * nothing written; device memory space: its rows are NaN, its neighbours are written and nothing out of range is
+ * read. */
+int eqlb_refine_prolong_flux_bc(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t k, int32_t nrhs,
+                                const double* boundary_values, int32_t nlist, const int32_t* facets2, double* dofs,
+                                int32_t memspace, void* stream);
+
+/* The boundary conditions of `old` (a handle on the mesh of the plan with an accepted eqlb_se_set_boundary) set on
+ * `fresh`, a handle the caller created on the refined mesh with its own options:
+ *   - the facet types are gathered on the device and their nrhs * nfacets2 bytes copied to the host for the planner;
+ *   - eqlb_se_set_boundary(fresh, types2, NULL, node_mask2) runs: its refusals and its "handle as it was" guarantees
+ *     pass through unchanged (node_mask2: HOST [nnodes2] or NULL - ownership on the new mesh is the caller's);
+ *   - if `old` owns a value table, the DOFs of the facets of type EQLB_FACET_ESSNT_DUAL are carried on the device from
+ *     table to table, by one kernel over the facets of the refined mesh for all right-hand sides: the old table never
+ *     visits the host, and `fresh` gets its table as the first eqlb_se_update_flux_bc allocates it.  If `old` owns
+ *     none, `fresh` owns none.
+ * Waits as eqlb_se_set_boundary waits.  Refusals (EQLB_ERR_INVALID_ARGUMENT, `fresh` as it was): null handles or plan,
+ * `old` without boundary data, different k, nrhs or stress flag, an `old` whose mesh is not the plan's, a `fresh`
+ * whose mesh does not have the plan's refined counts.
+ * eqlb_ev_carry_boundary does the same on the broken per-cell table of the EV handle; the dofmap and the basis
+ * transform of `fresh` are set by the caller first, as before eqlb_ev_set_boundary. */
+int eqlb_se_carry_boundary(const eqlb_se_t* old, eqlb_refine_t* plan, eqlb_se_t* fresh, const uint8_t* node_mask2,
+                           void* stream);
+int eqlb_ev_carry_boundary(const eqlb_ev_t* old, eqlb_refine_t* plan, eqlb_ev_t* fresh, const uint8_t* node_mask2,
+                           void* stream);
 
 void eqlb_refine_destroy(eqlb_refine_t* plan);
 

@@ -22,6 +22,8 @@ Basix nor quadrature loops:
   PT[(2q+1)(q+1)][nd_q] values of the P_q basis functions at the half-spacing lattice of the reference triangle, the
                        prolongation across one bisection level (eqlb_transfer.hip; the lattice and its row order:
                        dolfinx_eqlb_amd/mesh/transfer.py)
+  FB[6][k][k]          facet DOFs of a flux boundary condition on a child facet from those of its parent, one matrix
+                       per map of the facet parameter (eqlb_bc_carry.hip; mesh/transfer.py: flux_bc_table_exact)
 
 Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
       go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
@@ -391,6 +393,18 @@ def emit(path):
         lines.append(f"  static constexpr int NROW = {len(t)}, ND = {len(t[0])};")
         lines.append(f"  static constexpr double PT[{len(t) * len(t[0])}] = {{"
                      + ", ".join(repr(float(v)) for row in t for v in row) + "};")
+        lines.append("};")
+    lines.append("")
+    from dolfinx_eqlb_amd.mesh.transfer import flux_bc_table_exact
+    lines.append("// facet DOFs of a flux boundary condition across one bisection level: FB[m][j][i], child DOF j from parent DOF i")
+    lines.append("// for the maps m = (0,1), (1,0), (0,1/2), (1/2,1), (1/2,0), (1,1/2) of the facet parameter (mesh/transfer.py,")
+    lines.append("// eqlb_bc_carry.hip)")
+    lines.append("template <int K> struct FluxBcProlong;")
+    for k in range(1, 5):
+        t = flux_bc_table_exact(k)
+        lines.append(f"template <> struct FluxBcProlong<{k}> {{")
+        lines.append(f"  static constexpr double FB[{6 * k * k}] = {{"
+                     + ", ".join(repr(float(v)) for m in t for row in m for v in row) + "};")
         lines.append("};")
     lines.append("")
     lines.append("// reference facet normals of the RT functionals (e_raviart_thomas.py:82) and whether the")
