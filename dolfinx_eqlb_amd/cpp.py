@@ -49,6 +49,9 @@ EXPORTED_SYMBOLS = [
     "eqlb_mesh_lagrange_dofmap", "eqlb_get_prolong_table", "eqlb_refine_prolong_lagrange", "eqlb_refine_prolong_dg",
     "eqlb_refine_facet_types", "eqlb_refine_child_facets", "eqlb_get_flux_bc_prolong_table",
     "eqlb_refine_prolong_flux_bc", "eqlb_se_carry_boundary", "eqlb_ev_carry_boundary",
+    "eqlb_get_stiffness_table", "eqlb_get_load_table", "eqlb_primal_create", "eqlb_primal_destroy",
+    "eqlb_primal_ndofs", "eqlb_primal_set_dirichlet", "eqlb_primal_load", "eqlb_primal_apply",
+    "eqlb_primal_diagonal", "eqlb_primal_residual", "eqlb_primal_solve",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -179,8 +182,9 @@ def lib():
         for name in ("eqlb_mesh_destroy", "eqlb_se_destroy", "eqlb_ev_destroy", "eqlb_halo_destroy",
                      "eqlb_rccl_comm_destroy"):
             getattr(L, name).restype = None
-        if hasattr(L, "eqlb_refine_destroy"):   # (a library of an earlier revision, EQLB_AMD_LIB: A/B runs of bench.py)
-            L.eqlb_refine_destroy.restype = None
+        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy"):
+            if hasattr(L, name):   # (a library of an earlier revision, EQLB_AMD_LIB: A/B runs of bench.py)
+                getattr(L, name).restype = None
         _lib = L
     return _lib
 
@@ -1320,6 +1324,153 @@ def primal_stress_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, n
                                        C.c_int64(ndofs), _vp(u), C.c_double(pi_1), _vp(cell_pi1),
                                        _hp(t) if t is not None else None, _vp(flux_dg), C.c_int32(memspace),
                                        C.c_void_p(stream)))
+
+
+def get_stiffness_table(p: int):
+    """The built-in table Stiff<p> [3, nd_p, nd_p] of PrimalPoisson (eqlb_get_stiffness_table), 1 <= p <= 4."""
+    nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2
+    out = np.zeros((3, nd, nd))
+    n = lib().eqlb_get_stiffness_table(C.c_int32(p), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
+def get_load_table(p: int, degree_dg: int):
+    """The built-in table Load<p,d> [nd_p, nd_d] of PrimalPoisson.load (eqlb_get_load_table)."""
+    ndp, nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2, (max(int(degree_dg), 0) + 1) * (max(int(degree_dg), 0) + 2) // 2
+    out = np.zeros((ndp, nd))
+    n = lib().eqlb_get_load_table(C.c_int32(p), C.c_int32(degree_dg), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
+PRIMAL_INFO = ("iterations", "converged", "nb", "rnorm", "replacements", "breakdown", "tol", "facets_skipped")
+
+
+class PrimalPoisson:
+    """eqlb_primal_t: -div(coeff grad u) = f on the conforming P_p space of the handle (1 <= p <= 4), in the numbering
+    of DeviceMesh.lagrange_dofmap: the operator matrix-free, the load vector, the residual and a Jacobi-preconditioned
+    CG on the device (lsolver.primal.PoissonOperator is the numpy statement).  coeff: host array [ncells] or None (1).
+    The methods take and return host arrays; the `_raw` variants take raw pointers (ints) in `memspace`, ordered on
+    `stream`.  The entries of one handle share its work space: one stream, one call after the other."""
+
+    def __init__(self, dmesh: DeviceMesh, p: int, coeff=None, stream=0):
+        self.dmesh = dmesh   # the handle reads the mesh: keep it alive
+        self.p = int(p)
+        self._h = C.c_void_p()
+        kc = None
+        if coeff is not None:
+            kc = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+            if kc.size != dmesh.counts()[1]:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        _check(lib().eqlb_primal_create(dmesh._h, C.c_int32(p), _hp(kc) if kc is not None else None,
+                                        C.c_int32(MEM_HOST), C.c_void_p(stream), C.byref(self._h)))
+        n = C.c_int64(0)
+        _check(lib().eqlb_primal_ndofs(self._h, C.byref(n)))
+        self.ndofs = int(n.value)
+
+    @classmethod
+    def create_raw(cls, dmesh: DeviceMesh, p: int, coeff=None, memspace=MEM_DEVICE, stream=0):
+        """eqlb_primal_create with the coefficient [ncells] behind a raw pointer in `memspace` (None: 1)."""
+        self = cls.__new__(cls)
+        self.dmesh, self.p, self._h = dmesh, int(p), C.c_void_p()
+        _check(lib().eqlb_primal_create(dmesh._h, C.c_int32(p), _vp(coeff), C.c_int32(memspace), C.c_void_p(stream),
+                                        C.byref(self._h)))
+        n = C.c_int64(0)
+        _check(lib().eqlb_primal_ndofs(self._h, C.byref(n)))
+        self.ndofs = int(n.value)
+        return self
+
+    def _vec(self, a):
+        v = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if v.size != self.ndofs:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        return v
+
+    def set_dirichlet(self, facets, stream=0):
+        """Fixed are the vertex and facet DOFs of the listed facets; a repeated call replaces the mask."""
+        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+        self.set_dirichlet_raw(fl.size, fl.ctypes.data if fl.size else None, MEM_HOST, stream)
+
+    def set_dirichlet_raw(self, nlist, facets, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_primal_set_dirichlet(self._h, C.c_int32(nlist), _vp(facets), C.c_int32(memspace),
+                                               C.c_void_p(stream)))
+
+    def load(self, degree_dg, rhs_dg, b_extra=None, stream=0):
+        """b [ndofs] from the DG_d nodal values rhs_dg [ncells * nd_d], + b_extra [ndofs] where given."""
+        d = max(int(degree_dg), 0)
+        f = np.ascontiguousarray(rhs_dg, dtype=np.float64).ravel()
+        if 0 <= degree_dg <= 3 and f.size != self.dmesh.counts()[1] * (d + 1) * (d + 2) // 2:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        e = None if b_extra is None else self._vec(b_extra)
+        b = np.zeros(self.ndofs)
+        self.load_raw(degree_dg, f.ctypes.data, None if e is None else e.ctypes.data, b.ctypes.data, MEM_HOST, stream)
+        return b
+
+    def load_raw(self, degree_dg, rhs_dg, b_extra, b, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_primal_load(self._h, C.c_int32(degree_dg), _vp(rhs_dg), _vp(b_extra), _vp(b),
+                                      C.c_int32(memspace), C.c_void_p(stream)))
+
+    def apply(self, u, masked=False, stream=0):
+        """y = A u; masked: 0 on the fixed rows."""
+        uu, y = self._vec(u), np.zeros(self.ndofs)
+        self.apply_raw(uu.ctypes.data, y.ctypes.data, masked, MEM_HOST, stream)
+        return y
+
+    def apply_raw(self, u, y, masked=False, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_primal_apply(self._h, _vp(u), _vp(y), C.c_int32(1 if masked else 0), C.c_int32(memspace),
+                                       C.c_void_p(stream)))
+
+    def diagonal(self, stream=0):
+        out = np.zeros(self.ndofs)
+        self.diagonal_raw(out.ctypes.data, MEM_HOST, stream)
+        return out
+
+    def diagonal_raw(self, out, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_primal_diagonal(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def residual(self, b, u, norms=False, stream=0):
+        """r = b - A u with 0 on the fixed rows; norms=True: (r, || r ||_2, nb)."""
+        bb, uu, r = self._vec(b), self._vec(u), np.zeros(self.ndofs)
+        nv = np.zeros(2)
+        self.residual_raw(bb.ctypes.data, uu.ctypes.data, r.ctypes.data, nv.ctypes.data if norms else None, MEM_HOST,
+                          stream)
+        return (r, float(nv[0]), float(nv[1])) if norms else r
+
+    def residual_raw(self, b, u, r, norms=None, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_primal_residual(self._h, _vp(b), _vp(u), _vp(r), _vp(norms), C.c_int32(memspace),
+                                          C.c_void_p(stream)))
+
+    def solve(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
+        """Jacobi-preconditioned CG from the start u (its fixed rows hold the Dirichlet values).  Returns (u, info):
+        the solution and a dict with the keys of PRIMAL_INFO.  Not converged is a result, not an error."""
+        bb = self._vec(b)
+        uu = self._vec(u).copy()
+        info = self.solve_raw(bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
+        return uu, info
+
+    def solve_raw(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
+        """eqlb_primal_solve on raw pointers: u is overwritten by the solution; waits for the device; returns info."""
+        v = (C.c_double * 8)()
+        _check(lib().eqlb_primal_solve(self._h, _vp(b), _vp(u), C.c_double(rtol), C.c_double(atol), C.c_int32(maxit),
+                                       v, C.c_int32(memspace), C.c_void_p(stream)))
+        info = dict(zip(PRIMAL_INFO, [float(x) for x in v]))
+        for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
+            info[key] = int(info[key])
+        return info
+
+    def close(self):
+        if self._h:
+            lib().eqlb_primal_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def halo_pack(x_ptr, cells_ptr, buf_ptr, nrhs, nlist, nrt, ncells, clear=True, stream=0):

@@ -6,7 +6,7 @@
 //   through eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip, eqlb_bc_carry.hip,
 //   through eqlb_estimate_kernels.h by eqlb_estimate.hip, eqlb_estimate_lowdeg.hip, eqlb_estimate_lowdeg_k4.hip,
 //   directly by eqlb_mesh_build.hip, eqlb_marking.hip, eqlb_primal_flux.hip, eqlb_tiling_device.hip,
-//     eqlb_halo_rccl.hip.
+//     eqlb_halo_rccl.hip, eqlb_primal_solve.hip.
 #pragma once
 
 #include "eqlb_internal.h"

@@ -15,6 +15,7 @@
 // two calls on the same input give the same bits.
 #include "eqlb_device_common.h"
 #include "eqlb_host_util.h"
+#include "eqlb_reduce.h"
 #include <cmath>
 
 namespace eqlb
@@ -424,16 +425,7 @@ k_indicator_total(int64_t n, int nterms, int pair, TermPtrs tp, double* __restri
   for (int j = 0; j <= MK_MAXTERMS; ++j)
     sh[j][t] = acc[j];
   __syncthreads();
-  for (int s = MK_THREADS / 2; s >= 1; s >>= 1)
-  {
-    if (t < s)
-    {
-#pragma unroll
-      for (int j = 0; j <= MK_MAXTERMS; ++j)
-        sh[j][t] += sh[j][t + s];
-    }
-    __syncthreads();
-  }
+  EQLB_BLOCK_TREE_SUM(sh, t, MK_MAXTERMS + 1, MK_THREADS)
   if (t <= MK_MAXTERMS)
     part[(int64_t)t * G + blockIdx.x] = sh[t][0];
 }
@@ -453,16 +445,7 @@ k_indicator_reduce(int G, int nterms, const double* __restrict__ part, double* _
     sh[j][t] = a;
   }
   __syncthreads();
-  for (int s = MK_THREADS / 2; s >= 1; s >>= 1)
-  {
-    if (t < s)
-    {
-#pragma unroll
-      for (int j = 0; j <= MK_MAXTERMS; ++j)
-        sh[j][t] += sh[j][t + s];
-    }
-    __syncthreads();
-  }
+  EQLB_BLOCK_TREE_SUM(sh, t, MK_MAXTERMS + 1, MK_THREADS)
   if (t < nterms)
     totals[t] = sh[t][0];
   if (t == nterms)

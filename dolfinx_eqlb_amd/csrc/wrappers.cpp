@@ -277,6 +277,102 @@ struct Transfer
   }
 };
 
+// -div(coeff grad u) = f on the conforming P_p space of the mesh, in the numbering of Mesh.lagrange_dofmap: operator,
+// load, residual and Jacobi-preconditioned CG on the device (eqlb_primal_*), on host arrays
+struct PrimalPoisson
+{
+  eqlb_primal_t* h = nullptr;
+  std::shared_ptr<Mesh> mesh; // the handle reads the mesh: it stays alive with the carrier
+  int p = 0;
+  int64_t ndofs = 0;
+
+  PrimalPoisson(std::shared_ptr<Mesh> mesh_, int p_, py::object coeff) : mesh(mesh_), p(p_)
+  {
+    carray<double> kc;
+    if (!coeff.is_none())
+    {
+      kc = coeff.cast<carray<double>>();
+      if (kc.size() != mesh->ncells)
+        throw std::runtime_error("PrimalPoisson: coeff [ncells] expected");
+    }
+    check(eqlb_primal_create(mesh->h, p, coeff.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr, &h));
+    check(eqlb_primal_ndofs(h, &ndofs));
+  }
+  ~PrimalPoisson() { eqlb_primal_destroy(h); }
+  PrimalPoisson(const PrimalPoisson&) = delete;
+  PrimalPoisson& operator=(const PrimalPoisson&) = delete;
+
+  void need(const darray& v, const char* who) const
+  {
+    if (v.size() != ndofs)
+      throw std::runtime_error(std::string("PrimalPoisson.") + who + ": Input sizes does not match");
+  }
+  void set_dirichlet(carray<int32_t> facets)
+  {
+    check(eqlb_primal_set_dirichlet(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, EQLB_MEM_HOST,
+                                    nullptr));
+  }
+  darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
+  {
+    if (degree_dg >= 0 && degree_dg <= 3
+        && rhs_dg.size() != (py::ssize_t)mesh->ncells * ((degree_dg + 1) * (degree_dg + 2) / 2))
+      throw std::runtime_error("PrimalPoisson.load: Input sizes does not match");
+    darray e;
+    if (!b_extra.is_none())
+    {
+      e = b_extra.cast<darray>();
+      need(e, "load");
+    }
+    darray b((py::ssize_t)ndofs);
+    check(eqlb_primal_load(h, degree_dg, rhs_dg.data(), b_extra.is_none() ? nullptr : e.data(), b.mutable_data(),
+                           EQLB_MEM_HOST, nullptr));
+    return b;
+  }
+  darray apply(darray u, bool masked) const
+  {
+    need(u, "apply");
+    darray y((py::ssize_t)ndofs);
+    check(eqlb_primal_apply(h, u.data(), y.mutable_data(), masked ? 1 : 0, EQLB_MEM_HOST, nullptr));
+    return y;
+  }
+  darray diagonal() const
+  {
+    darray out((py::ssize_t)ndofs);
+    check(eqlb_primal_diagonal(h, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
+  // (r, || r ||_2, nb)
+  py::tuple residual(darray b, darray u) const
+  {
+    need(b, "residual");
+    need(u, "residual");
+    darray r((py::ssize_t)ndofs);
+    double norms[2] = {0.0, 0.0};
+    check(eqlb_primal_residual(h, b.data(), u.data(), r.mutable_data(), norms, EQLB_MEM_HOST, nullptr));
+    return py::make_tuple(r, norms[0], norms[1]);
+  }
+  // (u, info): the solution from the start u (its fixed rows hold the Dirichlet values) and the info dict
+  py::tuple solve(darray b, darray u, double rtol, double atol, int maxit) const
+  {
+    need(b, "solve");
+    need(u, "solve");
+    darray x((py::ssize_t)ndofs);
+    std::copy(u.data(), u.data() + ndofs, x.mutable_data());
+    double v[8] = {};
+    check(eqlb_primal_solve(h, b.data(), x.mutable_data(), rtol, atol, maxit, v, EQLB_MEM_HOST, nullptr));
+    py::dict info;
+    info["iterations"] = (int64_t)v[0];
+    info["converged"] = (int64_t)v[1];
+    info["nb"] = v[2];
+    info["rnorm"] = v[3];
+    info["replacements"] = (int64_t)v[4];
+    info["breakdown"] = (int64_t)v[5];
+    info["tol"] = v[6];
+    info["facets_skipped"] = (int64_t)v[7];
+    return py::make_tuple(x, info);
+  }
+};
+
 py::tuple Mesh::refine(std::shared_ptr<Mesh> self, carray<int32_t> marked, bool keep_plan)
 {
   std::shared_ptr<Transfer> tr(new Transfer());
@@ -1102,6 +1198,25 @@ PYBIND11_MODULE(_cpp, m)
            "facets of the refined mesh")
       .def_readonly("coarse", &Transfer::coarse)
       .def_readonly("fine", &Transfer::fine);
+
+  py::class_<PrimalPoisson, std::shared_ptr<PrimalPoisson>>(
+      m, "PrimalPoisson", "-div(coeff grad u) = f on the P_p space of the mesh (numbering of Mesh.lagrange_dofmap): "
+                          "matrix-free operator, load, residual and Jacobi-preconditioned CG on the device")
+      .def(py::init<std::shared_ptr<Mesh>, int, py::object>(), py::arg("mesh"), py::arg("p"),
+           py::arg("coeff") = py::none())
+      .def("set_dirichlet", &PrimalPoisson::set_dirichlet, py::arg("facets"),
+           "fixed are the vertex and facet DOFs of the listed facets; a repeated call replaces the mask")
+      .def("load", &PrimalPoisson::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
+           "b [ndofs] from DG_d nodal values rhs_dg [ncells*nd_d], + b_extra where given")
+      .def("apply", &PrimalPoisson::apply, py::arg("u"), py::arg("masked") = false, "y = A u; masked: 0 on the fixed rows")
+      .def("diagonal", &PrimalPoisson::diagonal)
+      .def("residual", &PrimalPoisson::residual, py::arg("b"), py::arg("u"),
+           "(r, || r ||_2, nb): r = b - A u with 0 on the fixed rows")
+      .def("solve", &PrimalPoisson::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
+           py::arg("maxit") = 10000, "(u, info): PCG from the start u, whose fixed rows hold the Dirichlet values")
+      .def_readonly("mesh", &PrimalPoisson::mesh)
+      .def_readonly("p", &PrimalPoisson::p)
+      .def_readonly("ndofs", &PrimalPoisson::ndofs);
 
   py::class_<FunctionSpace, std::shared_ptr<FunctionSpace>>(m, "FunctionSpace")
       .def(py::init<std::shared_ptr<Mesh>, std::string, int, int, bool>(), py::arg("mesh"), py::arg("family"),

@@ -1,0 +1,339 @@
+"""The P_p Poisson problem -div(kappa grad u) = f on the handle's own space - the statement of the rule.
+
+The adaptive demos of the reference solve the primal problem with PETSc (demo/poisson_adaptive/demo_lshape.py,
+demo_discont-coeff.py, demo/poisson/demo_reconstruction.py).  This file defines, in numpy, what the device path
+(eqlb_primal_* of include/eqlb.h, csrc/eqlb_primal_solve.hip) computes; the device reproduces the operator, the load,
+the diagonal and the residual bit for bit.
+
+  space     the numbering of mesh/transfer.py: lagrange_dofmap, equispaced P_p in Basix order, 1 <= p <= 4.  The owner
+            of a DOF follows from its index: d < nnodes is a vertex DOF, then nfacets (p-1) facet DOFs, then the
+            cell-interior DOFs
+  tables    Stiff<p> [3][nd_p][nd_p]: S0 = int dX phi_i dX phi_j, S1 = int (dX phi_i dY phi_j + dY phi_i dX phi_j),
+            S2 = int dY phi_i dY phi_j on the reference triangle; Load<p,d> [nd_p][nd_d]: int phi_i chi_n with chi_n the
+            DG_d nodal basis of rhs_dg.  Exact Fractions, each rounded once to double
+  geometry  J = (x1 - x0 | x2 - x0) (the handle's cellJ), det = J00 J11 - J01 J10, idet = 1 / det,
+            K00 = J11 idet, K01 = -J01 idet, K10 = -J10 idet, K11 = J00 idet,
+            C00 = K00 K00 + K01 K01, C01 = K00 K10 + K01 K11, C11 = K10 K10 + K11 K11, w = kappa_c |det|
+  cell      t_m[i] = sum_j S_m[i][j] u[dof(c, j)], m = 0, 1, 2: every product rounded on its own, added in ascending j;
+            y_loc[c][i] = w ((C00 t_0[i] + C01 t_1[i]) + C11 t_2[i]); every operation rounded on its own (no fused
+            multiply-add)
+  owner sum y[d] = the y_loc entries of DOF d, added from the first cell on: a vertex DOF takes the cells in the order
+            of the node -> cell table, a facet DOF those of the facet -> cell table, an interior DOF has its one cell
+  load      per cell |det| (sum_n Load[i][n] rhs_dg[c][n]) (ascending n), through the same owner sum, + b_extra[d]
+  diagonal  w ((C00 S0[i][i] + C01 S1[i][i]) + C11 S2[i][i]) through the same owner sum
+  residual  r = b - A u, 0 on the rows where `fixed` is set
+
+Every statement can return the sum of the absolute values of its terms (return_abs), so that a test bounds the
+comparison with an independently rounded computation by terms * 2^-53 * abs-sum.
+
+pcg() states the Jacobi-preconditioned CG of eqlb_primal_solve with np.sum for the inner products: the reference for
+iteration counts and for the host tests (the device reduces in another order, so its iterates differ in the last bits).
+"""
+
+from fractions import Fraction
+from functools import lru_cache
+
+import numpy as np
+
+from ..elmtlib import polynomials as P
+from ..elmtlib.lagrange import Lagrange
+from ..mesh.transfer import lagrange_dofmap, nd_of
+
+
+@lru_cache(maxsize=None)
+def stiffness_table_exact(p):
+    """S [3][nd_p][nd_p] Fractions."""
+    if p < 1 or p > 4:
+        raise ValueError(f"stiffness_table: p = {p} outside 1 ... 4")
+    basis = Lagrange(p).basis
+    dx, dy = [P.ddx(b) for b in basis], [P.ddy(b) for b in basis]
+    n = len(basis)
+    integ = P.integrate_triangle
+    S0 = tuple(tuple(integ(P.mul(dx[i], dx[j])) for j in range(n)) for i in range(n))
+    S1 = tuple(tuple(integ(P.mul(dx[i], dy[j])) + integ(P.mul(dy[i], dx[j])) for j in range(n)) for i in range(n))
+    S2 = tuple(tuple(integ(P.mul(dy[i], dy[j])) for j in range(n)) for i in range(n))
+    return (S0, S1, S2)
+
+
+@lru_cache(maxsize=None)
+def load_table_exact(p, d):
+    """Load [nd_p][nd_d] Fractions."""
+    if p < 1 or p > 4 or d < 0 or d > 3:
+        raise ValueError(f"load_table: p = {p}, d = {d} outside 1 ... 4, 0 ... 3")
+    phi, chi = Lagrange(p).basis, Lagrange(d).basis
+    return tuple(tuple(P.integrate_triangle(P.mul(a, b)) for b in chi) for a in phi)
+
+
+def stiffness_table(p):
+    """The table [3, nd_p, nd_p] as doubles, each entry rounded once."""
+    return np.array([[[float(v) for v in row] for row in m] for m in stiffness_table_exact(p)])
+
+
+def load_table(p, d):
+    """The table [nd_p, nd_d] as doubles, each entry rounded once."""
+    return np.array([[float(v) for v in row] for row in load_table_exact(p, d)])
+
+
+def dirichlet_mask(mesh, p, facets):
+    """fixed [ndofs] bool: the vertex and facet DOFs of the listed facets."""
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    for i, v in enumerate(f):
+        if v < 0 or v >= mesh.nfacets:
+            raise ValueError(f"dirichlet_mask: facets[{i}] = {int(v)} is no facet of the mesh")
+    ndofs = lagrange_dofmap(mesh, p)[1]
+    fixed = np.zeros(ndofs, dtype=bool)
+    fixed[mesh.facet_nodes[f].ravel()] = True
+    for j in range(p - 1):
+        fixed[mesh.nnodes + f * (p - 1) + j] = True
+    return fixed
+
+
+def neumann_load(mesh, p, bcs, quadrature_degree=None):
+    """b_extra [ndofs] of a problem with prescribed normal flux: for every `fluxbc` of `bcs` with a callable value,
+    -int_E g phi_i over its boundary facets E, g the normal flux sigma . n (the callable itself with scalar=True, else
+    the outward normal component of its vector), by Gauss quadrature (default degree 2 p + 4) on the host - O(sqrt N)
+    facets - in the numbering of lagrange_dofmap.  The flux-BC DOF table of the equilibrator cannot supply this vector:
+    it stops at moment k - 1, and the trace of P_p needs moment p."""
+    from ..elmtlib.quadrature import make_quadrature_interval
+    cd, ndofs = lagrange_dofmap(mesh, p)
+    b = np.zeros(ndofs)
+    s, wq = make_quadrature_interval(2 * p + 4 if quadrature_degree is None else int(quadrature_degree))
+    z = np.zeros_like(s)
+    ref = (np.stack([1 - s, s], 1), np.stack([z, s], 1), np.stack([s, z], 1))    # facet 0, 1, 2 (eqlb/bcs.py)
+    phi = [Lagrange(p).tabulate(pts)[0] for pts in ref]                          # [nq, nd]
+    ends = ((1, 2), (0, 2), (0, 1))
+    for bc in bcs:
+        if getattr(bc, "value", None) is None:
+            continue
+        for f in np.asarray(bc.facets, dtype=np.int64).ravel():
+            if f < 0 or f >= mesh.nfacets or mesh.facet_cells_offsets[f + 1] - mesh.facet_cells_offsets[f] != 1:
+                raise ValueError(f"neumann_load: facet {int(f)} is no boundary facet of the mesh")
+            c = int(mesh.facet_cells[mesh.facet_cells_offsets[f]])
+            lf = int(np.nonzero(mesh.cell_facets[c] == f)[0][0])
+            xc = mesh.x[mesh.cell_nodes[c], :2]
+            xa, xb, xo = xc[ends[lf][0]], xc[ends[lf][1]], xc[lf]
+            tvec = xb - xa
+            length = float(np.hypot(*tvec))
+            n = np.array([tvec[1], -tvec[0]]) / length
+            if np.dot(n, xa - xo) < 0.0:
+                n = -n
+            xq = xc[0][None, :] + ref[lf] @ np.stack([xc[1] - xc[0], xc[2] - xc[0]])
+            val = np.asarray(bc.value(xq[:, 0], xq[:, 1]), dtype=np.float64)
+            if getattr(bc, "scalar", False):
+                g = np.broadcast_to(val, s.shape)
+            else:
+                g = np.broadcast_to(val[0], s.shape) * n[0] + np.broadcast_to(val[1], s.shape) * n[1]
+            np.add.at(b, cd[c], -length * ((wq * g) @ phi[lf]))
+    return b
+
+
+def _sum_products(T, v):
+    """(val, A) [ncells, n]: sum_j T[i][j] v[c][j] in ascending j, products rounded one by one, and sum |T| |v|."""
+    val = T[None, :, 0] * v[:, None, 0]
+    A = np.abs(T[None, :, 0]) * np.abs(v[:, None, 0])
+    for j in range(1, T.shape[1]):
+        val = val + T[None, :, j] * v[:, None, j]
+        A = A + np.abs(T[None, :, j]) * np.abs(v[:, None, j])
+    return val, A
+
+
+class PoissonOperator:
+    """The statements on one mesh: PoissonOperator(mesh, p, coeff=None), coeff [ncells] the cell-wise kappa."""
+
+    def __init__(self, mesh, p, coeff=None):
+        if p < 1 or p > 4:
+            raise ValueError(f"PoissonOperator: p = {p} outside 1 ... 4")
+        self.mesh, self.p, self.nd = mesh, p, nd_of(p)
+        cd, self.ndofs = lagrange_dofmap(mesh, p)
+        self.cell_dofs = cd.astype(np.int64)
+        x, cn = mesh.x, mesh.cell_nodes
+        J00, J01 = x[cn[:, 1], 0] - x[cn[:, 0], 0], x[cn[:, 2], 0] - x[cn[:, 0], 0]
+        J10, J11 = x[cn[:, 1], 1] - x[cn[:, 0], 1], x[cn[:, 2], 1] - x[cn[:, 0], 1]
+        det = J00 * J11 - J01 * J10
+        idet = 1.0 / det
+        K00, K01, K10, K11 = J11 * idet, -J01 * idet, -J10 * idet, J00 * idet
+        self.C00 = K00 * K00 + K01 * K01
+        self.C01 = K00 * K10 + K01 * K11
+        self.C11 = K10 * K10 + K11 * K11
+        self.adet = np.abs(det)
+        kappa = np.ones(mesh.ncells) if coeff is None else np.asarray(coeff, dtype=np.float64).ravel()
+        if kappa.size != mesh.ncells:
+            raise ValueError("PoissonOperator: coeff [ncells] expected")
+        self.w = kappa * self.adet
+        self.S = stiffness_table(p)
+        self.fixed = np.zeros(self.ndofs, dtype=bool)
+        self._slots()
+
+    def _slots(self):
+        """slot lists of the owner sum: for every vertex and facet DOF the flat indices c * nd + i of its y_loc entries
+        in the order of the node -> cell / facet -> cell table; the local index comes from matching ids."""
+        m, p, nd = self.mesh, self.p, self.nd
+        cd = self.cell_dofs
+        nn, nf, ne = m.nnodes, m.nfacets, p - 1
+        off, slots = [0], []
+        for n in range(nn):
+            for c in m.node_cells[m.node_cells_offsets[n]:m.node_cells_offsets[n + 1]]:
+                slots.append(int(c) * nd + int(np.nonzero(cd[c] == n)[0][0]))
+            off.append(len(slots))
+        for f in range(nf):
+            cells = m.facet_cells[m.facet_cells_offsets[f]:m.facet_cells_offsets[f + 1]]
+            for j in range(ne):
+                d = nn + f * ne + j
+                for c in cells:
+                    slots.append(int(c) * nd + int(np.nonzero(cd[c] == d)[0][0]))
+                off.append(len(slots))
+        self.slot_off = np.array(off, dtype=np.int64)
+        self.slots = np.array(slots, dtype=np.int64)
+        self.nshared = nn + nf * ne
+
+    def set_dirichlet(self, facets):
+        """A repeated call replaces the mask."""
+        self.fixed = dirichlet_mask(self.mesh, self.p, facets)
+
+    # ---- the statements ----
+    def _combine(self, t, w, A=None):
+        """w ((C00 t0 + C01 t1) + C11 t2) on [3][ncells, nd]; with A the same with absolute values."""
+        c0, c1, c2 = self.C00[:, None], self.C01[:, None], self.C11[:, None]
+        val = w[:, None] * ((c0 * t[0] + c1 * t[1]) + c2 * t[2])
+        if A is None:
+            return val
+        return val, np.abs(w)[:, None] * ((np.abs(c0) * A[0] + np.abs(c1) * A[1]) + np.abs(c2) * A[2])
+
+    def cell_product(self, u, return_abs=False):
+        """y_loc [ncells, nd]."""
+        uc = np.asarray(u, dtype=np.float64)[self.cell_dofs]
+        t, A = zip(*[_sum_products(self.S[m], uc) for m in range(3)])
+        val, Ab = self._combine(t, self.w, A)
+        return (val, Ab) if return_abs else val
+
+    def owner_sum(self, y_loc, return_abs=False):
+        """y [ndofs] from y_loc [ncells, nd]."""
+        flat = np.ascontiguousarray(y_loc, dtype=np.float64).ravel()
+        y = np.zeros(self.ndofs)
+        A = np.zeros(self.ndofs)
+        ni = self.nd - 3 * self.p
+        y[self.nshared:] = np.asarray(y_loc)[:, 3 * self.p:].ravel() if ni else 0.0
+        A[self.nshared:] = np.abs(y[self.nshared:])
+        off = self.slot_off
+        cnt = np.diff(off)
+        first = self.slots[off[:-1]]
+        y[:self.nshared] = flat[first]
+        A[:self.nshared] = np.abs(flat[first])
+        for k in range(1, int(cnt.max())):
+            sel = np.nonzero(cnt > k)[0]
+            v = flat[self.slots[off[sel] + k]]
+            y[sel] = y[sel] + v
+            A[sel] = A[sel] + np.abs(v)
+        return (y, A) if return_abs else y
+
+    def apply(self, u, masked=False, return_abs=False):
+        """y = A u; masked: 0 on the fixed rows."""
+        if return_abs:
+            yl, Al = self.cell_product(u, True)
+            y = self.owner_sum(yl)
+            A = self.owner_sum(Al)
+        else:
+            y, A = self.owner_sum(self.cell_product(u)), None
+        if masked:
+            y[self.fixed] = 0.0
+        return (y, A) if return_abs else y
+
+    def load(self, degree_dg, rhs_dg, b_extra=None, return_abs=False):
+        """b [ndofs] from rhs_dg [ncells * nd_d] (DG_d nodal values)."""
+        if degree_dg < 0 or degree_dg > 3:
+            raise ValueError(f"load: degree_dg = {degree_dg} outside 0 ... 3")
+        L = load_table(self.p, degree_dg)
+        f = np.asarray(rhs_dg, dtype=np.float64).reshape(self.mesh.ncells, nd_of(degree_dg))
+        s, A = _sum_products(L, f)
+        b = self.owner_sum(self.adet[:, None] * s)
+        Ab = self.owner_sum(self.adet[:, None] * A)
+        if b_extra is not None:
+            e = np.asarray(b_extra, dtype=np.float64)
+            b = b + e
+            Ab = Ab + np.abs(e)
+        return (b, Ab) if return_abs else b
+
+    def diagonal(self, return_abs=False):
+        """The diagonal of the cell matrices through the owner sum."""
+        t = [np.broadcast_to(np.diagonal(self.S[m])[None, :], (self.mesh.ncells, self.nd)) for m in range(3)]
+        val, A = self._combine(t, self.w, [np.abs(x) for x in t])
+        d = self.owner_sum(val)
+        return (d, self.owner_sum(A)) if return_abs else d
+
+    def residual(self, b, u, fixed=None, return_abs=False):
+        """r = b - A u, 0 on the rows where `fixed` (default: the mask of set_dirichlet) is set."""
+        fx = self.fixed if fixed is None else np.asarray(fixed, dtype=bool)
+        bb = np.asarray(b, dtype=np.float64)
+        if return_abs:
+            y, A = self.apply(u, return_abs=True)
+            A = A + np.abs(bb)
+        else:
+            y, A = self.apply(u), None
+        r = bb - y
+        r[fx] = 0.0
+        if return_abs:
+            A[fx] = 0.0
+        return (r, A) if return_abs else r
+
+    def reference_norm(self, b, u):
+        """nb = || (b - A u^)_free ||_2 with u^ = u with its free rows set to 0: includes the lifting of the data."""
+        uh = np.where(self.fixed, np.asarray(u, dtype=np.float64), 0.0)
+        r = self.residual(b, uh)
+        return float(np.sqrt(np.sum(r * r)))
+
+    def pcg(self, b, u, rtol=1e-8, atol=0.0, maxit=1000):
+        """Jacobi-preconditioned CG from the start u, whose fixed rows hold the Dirichlet values (untouched).
+        tol = max(rtol nb, atol).  When the recurrence residual reaches tol the true residual b - A u is computed with
+        one more product: above tol it replaces the recurrence residual and the iteration goes on.  Returns (u, info)
+        with info = dict(iterations, converged, nb, rnorm, replacements, breakdown) as eqlb_primal_solve."""
+        if maxit < 1:
+            raise ValueError(f"pcg: maxit = {maxit}")
+        if not (rtol >= 0.0 and atol >= 0.0):
+            raise ValueError(f"pcg: rtol = {rtol}, atol = {atol} negative or NaN")
+        if not self.fixed.any():
+            raise ValueError("pcg: singular: no Dirichlet DOF")
+        u = np.array(u, dtype=np.float64)
+        b = np.asarray(b, dtype=np.float64)
+        nb = self.reference_norm(b, u)
+        tol = max(rtol * nb, atol)
+        info = dict(iterations=0, converged=0, nb=nb, rnorm=nb, replacements=0, breakdown=0)
+        if tol == 0.0 and nb == 0.0:
+            u[~self.fixed] = 0.0
+            info.update(converged=1, rnorm=0.0)
+            return u, info
+        diag = self.diagonal()
+        r = self.residual(b, u)
+        rr = np.sum(r * r)
+        if np.sqrt(rr) <= tol:
+            info.update(converged=1, rnorm=float(np.sqrt(rr)))
+            return u, info
+        z = r / diag
+        rho = np.sum(r * z)
+        d = z.copy()
+        for it in range(1, maxit + 1):
+            q = self.apply(d, masked=True)
+            dq = np.sum(d * q)
+            if not dq > 0.0:
+                info["breakdown"] = 1
+                break
+            alpha = rho / dq
+            u = u + alpha * d
+            r = r - alpha * q
+            info["iterations"] = it
+            rr = np.sum(r * r)
+            if np.sqrt(rr) <= tol:
+                rt = self.residual(b, u)
+                rr = np.sum(rt * rt)
+                if np.sqrt(rr) <= tol:
+                    info["converged"] = 1
+                    break
+                r = rt
+                info["replacements"] += 1
+            z = r / diag
+            rho_new = np.sum(r * z)
+            beta = rho_new / rho
+            rho = rho_new
+            d = z + beta * d
+        rt = self.residual(b, u)
+        info["rnorm"] = float(np.sqrt(np.sum(rt * rt)))
+        return u, info

@@ -847,6 +847,83 @@ int eqlb_ev_carry_boundary(const eqlb_ev_t* old, eqlb_refine_t* plan, eqlb_ev_t*
 
 void eqlb_refine_destroy(eqlb_refine_t* plan);
 
+/* ---- The P_p Poisson problem on the device: matrix-free operator, load, residual, Jacobi-preconditioned CG ----------
+ * -div(kappa grad u) = f with a cell-wise kappa, Dirichlet and Neumann parts, on the conforming P_p space of the handle
+ * (1 <= p <= 4): the primal solves of demo/poisson_adaptive/demo_lshape.py, demo_discont-coeff.py and
+ * demo/poisson/demo_reconstruction.py, in the numbering of eqlb_mesh_lagrange_dofmap (equispaced P_p, Basix order).  A
+ * caller with another numbering permutes; the owner of a DOF follows from its index (d < nnodes: a vertex DOF, then
+ * nfacets (p-1) facet DOFs, then the cell-interior DOFs).
+ *
+ * The rule is stated in numpy in dolfinx_eqlb_amd/lsolver/primal.py; apply, load, diagonal and residual reproduce it
+ * bit for bit:
+ *   cell       J = cellJ of the handle, K = J^-1, C = K K^T, w = kappa_c |det J|;
+ *              t_m[i] = sum_j S_m[i][j] u[dof(c, j)] (m = 0, 1, 2: the table Stiff<p>, products rounded one by one,
+ *              ascending j), y_loc[c][i] = w ((C00 t_0[i] + C01 t_1[i]) + C11 t_2[i]), no fused multiply-add
+ *   owner sum  y[d] = the y_loc entries of DOF d added from the first cell on, in the order of the node -> cell table
+ *              (vertex DOFs) or the facet -> cell table (facet DOFs); an interior DOF has its one cell
+ * A store pass (one thread per cell) and a sum pass (one thread per DOF): no atomics, two calls give the same bits.
+ *
+ * The handle keeps the dofmap, kappa, the slot lists of the sum pass, the Dirichlet mask, the diagonal and the work
+ * vectors of the solver, all allocated by eqlb_primal_create: no entry below allocates device memory in device memory
+ * space.  The entries of one handle use its work space: calls on one handle belong on one stream, one after the other.
+ * The mesh must outlive the handle.
+ *   cell_coeff [ncells] in `memspace` or NULL (kappa = 1), copied
+ * Host-only getters of the tables, like eqlb_get_primal_table (the number of doubles copied, or a negative error):
+ *   eqlb_get_stiffness_table  Stiff<p> [3][nd_p][nd_p]: S0 = int dX phi_i dX phi_j, S1 = int (dX phi_i dY phi_j +
+ *                             dY phi_i dX phi_j), S2 = int dY phi_i dY phi_j on the reference triangle
+ *   eqlb_get_load_table       Load<p,d> [nd_p][nd_d] = int phi_i chi_n, chi_n the DG_d nodal basis of rhs_dg
+ */
+typedef struct eqlb_primal eqlb_primal_t;
+int eqlb_get_stiffness_table(int32_t p, double* out, int32_t capacity);
+int eqlb_get_load_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity);
+int eqlb_primal_create(eqlb_mesh_t* mesh, int32_t p, const double* cell_coeff, int32_t memspace, void* stream,
+                       eqlb_primal_t** handle);
+void eqlb_primal_destroy(eqlb_primal_t* handle);
+int eqlb_primal_ndofs(const eqlb_primal_t* handle, int64_t* ndofs);
+
+/* Fixed are the vertex and facet DOFs of the listed facets [nlist] (the lists eqlb_refine_child_facets carries across
+ * a refinement); a repeated call replaces the mask, nlist = 0 clears it.  A facet id outside the mesh: host memory
+ * space: refused by name, the mask as it was; device memory space: skipped and counted in the handle's status word,
+ * nothing is read or written out of range. */
+int eqlb_primal_set_dirichlet(eqlb_primal_t* handle, int32_t nlist, const int32_t* facets, int32_t memspace,
+                              void* stream);
+
+/* b [ndofs]: per cell |det J| sum_n Load[i][n] rhs_dg[c][n] (ascending n) through the owner sum, + b_extra[d] where
+ * b_extra [ndofs] is given (the Neumann part, lsolver.neumann_load).  rhs_dg [ncells][nd_d], 0 <= degree_dg <= 3.
+ * y = A u: masked != 0 gives 0 on the fixed rows, masked = 0 the raw operator.
+ * out = the diagonal of the cell matrices through the owner sum (the Jacobi preconditioner).
+ * r = b - A u with 0 on the fixed rows; norms [2] in `memspace` or NULL: || r ||_2 and the reference norm nb of
+ * eqlb_primal_solve for this b and u.
+ * Device memory space: enqueued on `stream`, nothing waits.  Host memory space: staged, synchronous. */
+int eqlb_primal_load(eqlb_primal_t* handle, int32_t degree_dg, const double* rhs_dg, const double* b_extra, double* b,
+                     int32_t memspace, void* stream);
+int eqlb_primal_apply(eqlb_primal_t* handle, const double* u, double* y, int32_t masked, int32_t memspace,
+                      void* stream);
+int eqlb_primal_diagonal(eqlb_primal_t* handle, double* out, int32_t memspace, void* stream);
+int eqlb_primal_residual(eqlb_primal_t* handle, const double* b, const double* u, double* r, double* norms,
+                         int32_t memspace, void* stream);
+
+/* Jacobi-preconditioned CG for A u = b on the free rows.  WAITS for the device by nature: the host reads the residual
+ * norm every few iterations, and once before it returns.
+ *   u [ndofs] in: the start (Refinement.prolong delivers one) and, on the fixed rows, the Dirichlet values, which are
+ *             not touched; out: the solution
+ *   nb        the reference norm || (b - A u^)_free ||_2 with u^ = u with its free rows set to 0: it includes the
+ *             lifting of inhomogeneous Dirichlet data;  tol = max(rtol nb, atol); tol = 0 with nb = 0 returns u^
+ *   stop      when the recurrence residual reaches tol the true residual b - A u is computed with one more product;
+ *             above tol it replaces the recurrence residual and the iteration goes on: at a converged exit the true
+ *             residual is <= tol.  The loop is bounded by maxit in every case; a NaN in b or p^T A p <= 0 ends it with
+ *             breakdown = 1, converged = 0
+ *   info      HOST [8]: iterations, converged (1/0), nb, final true || r ||_2, residual replacements, breakdown (1/0),
+ *             tol, facet ids skipped by eqlb_primal_set_dirichlet in device memory space
+ * Alpha, beta, rho and || r ||^2 stay in device memory and are read by the next kernel; inner products are sums of
+ * per-thread partials in a fixed order, reduced by fixed trees (two solves give the same bits; the bits differ from
+ * the numpy statement, whose np.sum adds in another order).
+ * The return value is EQLB_OK also when the iteration did not converge: that is a result, not an error.  Refused before
+ * anything is launched (EQLB_ERR_INVALID_ARGUMENT): maxit < 1, rtol or atol negative or NaN, null arguments, a handle
+ * without one fixed DOF ("singular: no Dirichlet DOF"). */
+int eqlb_primal_solve(eqlb_primal_t* handle, const double* b, double* u, double rtol, double atol, int32_t maxit,
+                      double* info, int32_t memspace, void* stream);
+
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the
  * partial sums of the ghost-cell rows are sent to the owning rank and added there.  DEVICE pointers:

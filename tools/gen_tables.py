@@ -24,6 +24,9 @@ Basix nor quadrature loops:
                        dolfinx_eqlb_amd/mesh/transfer.py)
   FB[6][k][k]          facet DOFs of a flux boundary condition on a child facet from those of its parent, one matrix
                        per map of the facet parameter (eqlb_bc_carry.hip; mesh/transfer.py: flux_bc_table_exact)
+  ST[3][nd_p][nd_p]    reference stiffness of P_p: int dX phi_i dX phi_j, int (dX phi_i dY phi_j + dY phi_i dX phi_j),
+                       int dY phi_i dY phi_j (eqlb_primal_solve.hip; lsolver/primal.py: stiffness_table_exact)
+  LD[nd_p][nd_d]       int phi_i chi_n, chi_n the DG_d nodal basis: the load of P_p against DG_d data (load_table_exact)
 
 Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
       go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
@@ -394,6 +397,30 @@ def emit(path):
         lines.append(f"  static constexpr double PT[{len(t) * len(t[0])}] = {{"
                      + ", ".join(repr(float(v)) for row in t for v in row) + "};")
         lines.append("};")
+    lines.append("")
+    from dolfinx_eqlb_amd.lsolver.primal import load_table_exact, stiffness_table_exact
+    lines.append("// reference stiffness of P_p: ST[m][i][j], S0 = int dX phi_i dX phi_j, S1 = int (dX phi_i dY phi_j + dY phi_i dX phi_j),")
+    lines.append("// S2 = int dY phi_i dY phi_j (lsolver/primal.py, eqlb_primal_solve.hip)")
+    lines.append("template <int P> struct Stiff;")
+    for p in range(1, 5):
+        t = stiffness_table_exact(p)
+        n = len(t[0])
+        lines.append(f"template <> struct Stiff<{p}> {{")
+        lines.append(f"  static constexpr int ND = {n};")
+        lines.append(f"  static constexpr double ST[{3 * n * n}] = {{"
+                     + ", ".join(repr(float(v)) for m in t for row in m for v in row) + "};")
+        lines.append("};")
+    lines.append("")
+    lines.append("// load of P_p against DG_d data: LD[i][n] = int phi_i chi_n, chi_n the DG_d nodal basis of rhs_dg")
+    lines.append("template <int P, int D> struct Load;")
+    for p in range(1, 5):
+        for d in range(4):
+            t = load_table_exact(p, d)
+            lines.append(f"template <> struct Load<{p}, {d}> {{")
+            lines.append(f"  static constexpr int NP = {len(t)}, ND = {len(t[0])};")
+            lines.append(f"  static constexpr double LD[{len(t) * len(t[0])}] = {{"
+                         + ", ".join(repr(float(v)) for row in t for v in row) + "};")
+            lines.append("};")
     lines.append("")
     from dolfinx_eqlb_amd.mesh.transfer import flux_bc_table_exact
     lines.append("// facet DOFs of a flux boundary condition across one bisection level: FB[m][j][i], child DOF j from parent DOF i")

@@ -1,0 +1,250 @@
+#!/usr/bin/env python3
+"""primal_solve_time.py: timings of the P_p Poisson solve on the device (cpp.PrimalPoisson) at about 1M triangles.
+
+For P_1 and P_2 on create_unit_square(N, shuffle_seed=3, perturb=0.15) (N = 500: 1,000,000 cells), f = f_ex of
+tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all around:
+  product    device time of one operator product y = A u, by device events around --products (>= 100) products after
+             a warm-up; the byte count of a product computed from the shapes, and the achieved bytes/s against the
+             measured HBM copy rate (6.29 TB/s, float4 copy)
+  iteration  device time of one PCG iteration: events around a solve of exactly --iterations iterations (rtol = 0)
+  zero       iterations and time to rtol 1e-8 from u = 0
+  prolonged  the same mesh refined at 2 % of its cells (fixed seed) on the device: iterations and time to rtol 1e-8 from
+             zero and from the prolonged solution of the unrefined mesh
+  host       scipy.sparse.linalg.cg with the same diagonal preconditioner and tolerance on the matrix assembled from the
+             same tables, and spsolve, on the host of the same machine (--host; each under a time budget, reported as
+             "not finished" beyond it)
+  --check-every LIB:N ...   the PCG of P_2 to rtol 1e-8 from zero once per library (builds of libeqlb_amd.so with
+             -DEQLB_PRIMAL_CHECK_EVERY=N, tools/build_variant.sh NAME "-D..." eqlb_primal_solve), each in a child process
+Prints one line per figure and, last, one JSON line with all of them.  Nothing here is a pass/fail condition.
+"""
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+HBM_COPY_RATE = 6.29e12   # bytes/s, measured float4 copy on the MI355X
+
+
+def say(*a):
+    print(*a, flush=True)
+
+
+def f_ex(x, y):
+    s, c = np.sin, np.cos
+    return 2 * np.pi ** 2 * s(np.pi * x) * s(np.pi * y) * (1 + x) - 2 * np.pi * c(np.pi * x) * s(np.pi * y)
+
+
+def rhs_dg(mesh, d):
+    """f_ex interpolated at the DG_d nodes (nodal values [ncells * nd_d])"""
+    from dolfinx_eqlb_amd.elmtlib.lagrange import lagrange_nodes
+    X = np.array([[float(a), float(b)] for a, b in lagrange_nodes(d)])
+    xc = mesh.x[mesh.cell_nodes, :2]
+    pts = xc[:, None, 0, :] + X[None, :, 0:1] * (xc[:, 1] - xc[:, 0])[:, None, :] \
+        + X[None, :, 1:2] * (xc[:, 2] - xc[:, 0])[:, None, :]
+    return np.ascontiguousarray(f_ex(pts[..., 0], pts[..., 1]).ravel())
+
+
+def product_bytes(mesh, p):
+    """compulsory bytes of one product from the shapes: the cell pass reads the dofmap, cellJ and u once and writes
+    y_loc; the sum pass reads y_loc, the slot lists, the two offset tables and the mask and writes y"""
+    nd, ne = (p + 1) * (p + 2) // 2, p - 1
+    nc, nn, nf = mesh.ncells, mesh.nnodes, mesh.nfacets
+    ndofs = nn + nf * ne + nc * (p - 1) * (p - 2) // 2
+    cell = nc * nd * 4 + nc * 32 + ndofs * 8 + nc * nd * 8
+    gather = nc * nd * 8 + 3 * nc * (1 + ne) * 4 + (nn + nf + 2) * 4 + ndofs + ndofs * 8
+    return cell + gather, ndofs
+
+
+def timed_solve(torch, h, b, u0, rtol, maxit):
+    """(info, device ms) of one solve from u0 (copied), events around it"""
+    u = u0.clone()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    info = h.solve_raw(b.data_ptr(), u.data_ptr(), rtol, 0.0, maxit)
+    e1.record()
+    torch.cuda.synchronize()
+    return info, e0.elapsed_time(e1), u
+
+
+def make_problem(cpp, torch, dm, p):
+    mesh = dm.mesh
+    h = cpp.PrimalPoisson(dm, p)
+    h.set_dirichlet(mesh.boundary_facets())
+    f = torch.from_numpy(rhs_dg(mesh, p - 1)).cuda()
+    b = torch.zeros(h.ndofs, dtype=torch.float64, device="cuda")
+    h.load_raw(p - 1, f.data_ptr(), None, b.data_ptr())
+    torch.cuda.synchronize()
+    return h, b
+
+
+def host_matrix(mesh, p):
+    """A (csr) from the statement's tables, the free rows, in the handle's numbering"""
+    import scipy.sparse as sp
+    from dolfinx_eqlb_amd.lsolver import primal
+    from dolfinx_eqlb_amd.mesh.transfer import lagrange_dofmap
+    cd, ndofs = lagrange_dofmap(mesh, p)
+    x, cn = mesh.x, mesh.cell_nodes
+    J00, J01 = x[cn[:, 1], 0] - x[cn[:, 0], 0], x[cn[:, 2], 0] - x[cn[:, 0], 0]
+    J10, J11 = x[cn[:, 1], 1] - x[cn[:, 0], 1], x[cn[:, 2], 1] - x[cn[:, 0], 1]
+    det = J00 * J11 - J01 * J10
+    K00, K01, K10, K11 = J11 / det, -J01 / det, -J10 / det, J00 / det
+    C = (K00 * K00 + K01 * K01, K00 * K10 + K01 * K11, K10 * K10 + K11 * K11)
+    S = primal.stiffness_table(p)
+    Ke = np.abs(det)[:, None, None] * sum(C[m][:, None, None] * S[m][None] for m in range(3))
+    nl = cd.shape[1]
+    A = sp.csr_matrix((Ke.ravel(), (np.repeat(cd, nl, axis=1).ravel(), np.tile(cd, (1, nl)).ravel())),
+                      shape=(ndofs, ndofs))
+    fixed = primal.dirichlet_mask(mesh, p, mesh.boundary_facets())
+    return A, np.nonzero(~fixed)[0]
+
+
+def host_figures(mesh, p, b, budget, direct):
+    import scipy.sparse.linalg as spla
+    out = {}
+    t0 = time.perf_counter()
+    A, free = host_matrix(mesh, p)
+    Aff = A[free][:, free].tocsr()
+    bf = b[free]
+    out["assemble_s"] = time.perf_counter() - t0
+    say(f"  host: assembled {Aff.shape[0]} free rows in {out['assemble_s']:.1f} s")
+    dinv = 1.0 / Aff.diagonal()
+    M = spla.LinearOperator(Aff.shape, matvec=lambda v: dinv * v)
+    n = [0]
+    t0 = time.perf_counter()
+
+    class Budget(Exception):
+        pass
+
+    def cb(_):
+        n[0] += 1
+        if time.perf_counter() - t0 > budget:
+            raise Budget()
+
+    try:
+        _, flag = spla.cg(Aff, bf, rtol=1e-8, atol=0.0, M=M, maxiter=200000, callback=cb)
+        out["cg"] = dict(iterations=n[0], seconds=time.perf_counter() - t0, converged=int(flag == 0))
+    except Budget:
+        out["cg"] = dict(iterations=n[0], seconds=time.perf_counter() - t0, converged=0, note="not finished")
+    say(f"  host: scipy cg (Jacobi, rtol 1e-8): {out['cg']}")
+    if not direct:
+        say("  host: spsolve not measured at this degree (--spsolve-degrees)")
+        return out
+    t0 = time.perf_counter()
+    spla.spsolve(Aff.tocsc(), bf)
+    out["spsolve_s"] = time.perf_counter() - t0
+    say(f"  host: spsolve {out['spsolve_s']:.1f} s")
+    return out
+
+
+def run_degree(args, cpp, torch, dm, p, res):
+    mesh = dm.mesh
+    h, b = make_problem(cpp, torch, dm, p)
+    nbytes, ndofs = product_bytes(mesh, p)
+    r = dict(ncells=mesh.ncells, ndofs=ndofs, product_bytes=nbytes)
+    u = torch.from_numpy(np.random.default_rng(0).standard_normal(ndofs)).cuda()
+    y = torch.empty_like(u)
+    for _ in range(10):
+        h.apply_raw(u.data_ptr(), y.data_ptr(), True)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(args.products):
+        h.apply_raw(u.data_ptr(), y.data_ptr(), True)
+    e1.record()
+    torch.cuda.synchronize()
+    r["product_ms"] = e0.elapsed_time(e1) / args.products
+    r["product_bytes_per_s"] = nbytes / (r["product_ms"] * 1e-3)
+    r["product_fraction_of_copy_rate"] = r["product_bytes_per_s"] / HBM_COPY_RATE
+    say(f"P_{p}: {mesh.ncells} cells, {ndofs} DOFs; product {r['product_ms']:.4f} ms over {args.products} products, "
+        f"{nbytes / 1e6:.1f} MB -> {r['product_bytes_per_s'] / 1e12:.3f} TB/s = "
+        f"{100 * r['product_fraction_of_copy_rate']:.1f} % of the copy rate")
+    zero = torch.zeros(ndofs, dtype=torch.float64, device="cuda")
+    timed_solve(torch, h, b, zero, 0.0, 20)   # warm-up
+    info, ms, _ = timed_solve(torch, h, b, zero, 0.0, args.iterations)
+    r["iteration_ms"] = ms / max(info["iterations"], 1)
+    say(f"P_{p}: PCG iteration {r['iteration_ms']:.4f} ms ({info['iterations']} iterations in {ms:.1f} ms)")
+    info, ms, usol = timed_solve(torch, h, b, zero, 1e-8, args.maxit)
+    r["zero"] = dict(iterations=info["iterations"], ms=ms, converged=info["converged"],
+                     replacements=info["replacements"])
+    say(f"P_{p}: to rtol 1e-8 from zero: {r['zero']}")
+    if args.check_only:
+        res[f"P{p}"] = r
+        return
+    # 2 % refinement on the device, the solution prolonged
+    marked = np.random.default_rng(42).choice(mesh.ncells, size=mesh.ncells // 50, replace=False).astype(np.int32)
+    ref = dm.refine(np.sort(marked), keep_plan=True)
+    h2, b2 = make_problem(cpp, torch, ref.dmesh, p)
+    u2 = ref.prolong(p, usol).reshape(-1)
+    # the prolonged values of the boundary DOFs are the (zero) Dirichlet values of the new mesh
+    zero2 = torch.zeros(h2.ndofs, dtype=torch.float64, device="cuda")
+    i0, ms0, _ = timed_solve(torch, h2, b2, zero2, 1e-8, args.maxit)
+    i1, ms1, _ = timed_solve(torch, h2, b2, u2, 1e-8, args.maxit)
+    r["refined"] = dict(ncells=ref.dmesh.mesh.ncells, ndofs=h2.ndofs,
+                        zero=dict(iterations=i0["iterations"], ms=ms0, converged=i0["converged"]),
+                        prolonged=dict(iterations=i1["iterations"], ms=ms1, converged=i1["converged"]))
+    say(f"P_{p}: refined at 2 % ({r['refined']['ncells']} cells): from zero {r['refined']['zero']}, "
+        f"from the prolonged solution {r['refined']['prolonged']}")
+    ref.close()
+    if args.host:
+        r["host"] = host_figures(mesh, p, b.cpu().numpy(), args.host_budget, p in args.spsolve_degrees)
+    res[f"P{p}"] = r
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--n", type=int, default=500, help="squares per side (4 n^2 triangles)")
+    ap.add_argument("--degrees", type=int, nargs="+", default=[1, 2])
+    ap.add_argument("--products", type=int, default=200)
+    ap.add_argument("--iterations", type=int, default=200)
+    ap.add_argument("--maxit", type=int, default=100000)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--host-budget", type=float, default=150.0, help="seconds for the host cg")
+    ap.add_argument("--spsolve-degrees", type=int, nargs="*", default=[1],
+                    help="degrees at which --host also runs spsolve (P_2 at 1M triangles takes minutes and many GB)")
+    ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
+    ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.products < 100:
+        ap.error("--products: at least 100")
+    res = {}
+    if not args.check_only:
+        for item in args.check_every:
+            lib, n = item.rsplit(":", 1)
+            env = dict(os.environ, EQLB_AMD_LIB=os.path.abspath(lib))
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--n", str(args.n), "--degrees", "2",
+                                  "--check-only", "--maxit", str(args.maxit)], env=env, capture_output=True, text=True,
+                                 timeout=600)
+            last = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+            if out.returncode != 0 or not last:
+                say(f"check-every {n}: child failed ({out.returncode}): {out.stderr[-400:]}")
+                sys.exit(1)
+            z = json.loads(last[-1])["P2"]
+            res.setdefault("check_every", {})[n] = dict(ms=z["zero"]["ms"], iterations=z["zero"]["iterations"],
+                                                        iteration_ms=z["iteration_ms"])
+            say(f"EQLB_PRIMAL_CHECK_EVERY = {n}: P_2 to rtol 1e-8 from zero {z['zero']['ms']:.1f} ms, "
+                f"{z['zero']['iterations']} iterations; iteration {z['iteration_ms']:.4f} ms")
+    import torch
+    torch.cuda.init()
+    from dolfinx_eqlb_amd import cpp
+    from dolfinx_eqlb_amd.mesh import create_unit_square
+    t0 = time.perf_counter()
+    dm = cpp.DeviceMesh(create_unit_square(args.n, shuffle_seed=3, perturb=0.15))
+    say(f"mesh: {dm.mesh.ncells} cells in {time.perf_counter() - t0:.1f} s")
+    for p in args.degrees:
+        run_degree(args, cpp, torch, dm, p, res)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
