@@ -90,81 +90,59 @@ try
     if (!ok)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mesh_create: inconsistent connectivity tables");
   }
-  eqlb_mesh* m = new eqlb_mesh();
+  std::unique_ptr<eqlb_mesh> m(new eqlb_mesh());
   eqlb::DeviceMesh& d = m->m;
+  eqlb::HostMesh& hm = m->host;
   d.nnodes = nnodes;
   d.ncells = ncells;
   d.nfacets = nfacets;
-  d.h_node_ncells.resize(nnodes);
-  d.h_node_nfcts.resize(nnodes);
+  hm.node_ncells.resize(nnodes);
+  hm.node_nfcts.resize(nnodes);
   for (int32_t i = 0; i < nnodes; ++i)
   {
-    d.h_node_ncells[i] = node_cells_offsets[i + 1] - node_cells_offsets[i];
-    d.h_node_nfcts[i] = node_facets_offsets[i + 1] - node_facets_offsets[i];
-    d.ncells_max = std::max(d.ncells_max, d.h_node_ncells[i]);
+    hm.node_ncells[i] = node_cells_offsets[i + 1] - node_cells_offsets[i];
+    hm.node_nfcts[i] = node_facets_offsets[i + 1] - node_facets_offsets[i];
+    d.ncells_max = std::max(d.ncells_max, hm.node_ncells[i]);
   }
   // One-cell facets per node: with the two counts above they tell whether the patch builder can walk the node (one
   // closed ring or one open fan, eqlb_topology_check.h).  Nothing is refused here: the local mesh of a rank
   // legitimately holds nodes it does not own at which two fans meet; eqlb_se_set_boundary refuses them when they are
   // to be equilibrated.
-  d.h_node_nbnd.resize(nnodes);
-  eqlb::count_node_boundary_facets(nnodes, node_facets_offsets, node_facets, facet_cells_offsets, d.h_node_nbnd.data());
-  d.h_facet_cells_off.assign(facet_cells_offsets, facet_cells_offsets + (size_t)nfacets + 1);
-  d.h_x.assign(x, x + (size_t)nnodes * 3);
-  d.h_cell_nodes.assign(cell_nodes, cell_nodes + (size_t)ncells * 3);
-  d.h_facet_nodes.assign(facet_nodes, facet_nodes + (size_t)nfacets * 2);
-  d.h_node_facets_off.assign(node_facets_offsets, node_facets_offsets + (size_t)nnodes + 1);
-  d.h_node_facets.assign(node_facets, node_facets + (size_t)node_facets_offsets[nnodes]);
-  d.h_node_cells_off.assign(node_cells_offsets, node_cells_offsets + (size_t)nnodes + 1);
-  d.h_node_cells.assign(node_cells, node_cells + (size_t)node_cells_offsets[nnodes]);
+  hm.node_nbnd.resize(nnodes);
+  eqlb::count_node_boundary_facets(nnodes, node_facets_offsets, node_facets, facet_cells_offsets, hm.node_nbnd.data());
+  hm.facet_cells_off.assign(facet_cells_offsets, facet_cells_offsets + (size_t)nfacets + 1);
+  hm.x.assign(x, x + (size_t)nnodes * 3);
+  hm.cell_nodes.assign(cell_nodes, cell_nodes + (size_t)ncells * 3);
+  hm.facet_nodes.assign(facet_nodes, facet_nodes + (size_t)nfacets * 2);
+  hm.node_facets_off.assign(node_facets_offsets, node_facets_offsets + (size_t)nnodes + 1);
+  hm.node_facets.assign(node_facets, node_facets + (size_t)node_facets_offsets[nnodes]);
+  hm.node_cells_off.assign(node_cells_offsets, node_cells_offsets + (size_t)nnodes + 1);
+  hm.node_cells.assign(node_cells, node_cells + (size_t)node_cells_offsets[nnodes]);
   int st = 0;
-  st |= upload(&d.x, x, (size_t)nnodes * 3);
-  st |= upload(&d.cell_nodes, cell_nodes, (size_t)ncells * 3);
-  st |= upload(&d.cell_facets, cell_facets, (size_t)ncells * 3);
-  st |= upload(&d.facet_nodes, facet_nodes, (size_t)nfacets * 2);
-  st |= upload(&d.facet_cells_off, facet_cells_offsets, (size_t)nfacets + 1);
-  st |= upload(&d.facet_cells, facet_cells, (size_t)facet_cells_offsets[nfacets]);
-  st |= upload(&d.node_cells_off, node_cells_offsets, (size_t)nnodes + 1);
-  st |= upload(&d.node_facets_off, node_facets_offsets, (size_t)nnodes + 1);
-  st |= upload(&d.node_facets, node_facets, (size_t)node_facets_offsets[nnodes]);
-  st |= upload(&d.facet_perm, facet_perm, (size_t)ncells * 3);
-  st |= upload<double>(&d.cellJ, nullptr, (size_t)ncells * 4);
+  st |= m->x.upload(x, (size_t)nnodes * 3);
+  st |= m->cell_nodes.upload(cell_nodes, (size_t)ncells * 3);
+  st |= m->cell_facets.upload(cell_facets, (size_t)ncells * 3);
+  st |= m->facet_nodes.upload(facet_nodes, (size_t)nfacets * 2);
+  st |= m->facet_cells_off.upload(facet_cells_offsets, (size_t)nfacets + 1);
+  st |= m->facet_cells.upload(facet_cells, (size_t)facet_cells_offsets[nfacets]);
+  st |= m->node_cells_off.upload(node_cells_offsets, (size_t)nnodes + 1);
+  st |= m->node_facets_off.upload(node_facets_offsets, (size_t)nnodes + 1);
+  st |= m->node_facets.upload(node_facets, (size_t)node_facets_offsets[nnodes]);
+  st |= m->facet_perm.upload(facet_perm, (size_t)ncells * 3);
+  st |= m->cellJ.alloc((size_t)ncells * 4);
   if (st)
-  {
-    eqlb_mesh_destroy(m);
     return EQLB_ERR_DEVICE;
-  }
+  m->publish();
   eqlb::launch_cell_geometry(ncells, d.x, d.cell_nodes, d.cellJ, nullptr);
   eqlb::device_tiling_prepare(); // code object of the tile builder loaded here, not inside the first set_boundary
   if (hipDeviceSynchronize() != hipSuccess)
-  {
-    eqlb_mesh_destroy(m);
     return fail(EQLB_ERR_DEVICE, "eqlb_mesh_create: geometry kernel failed");
-  }
-  *mesh = m;
+  *mesh = m.release();
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
 
-void eqlb_mesh_destroy(eqlb_mesh_t* m)
-{
-  if (!m)
-    return;
-  eqlb::DeviceMesh& d = m->m;
-  dfree(d.x);
-  dfree(d.cellJ);
-  dfree(d.cell_nodes);
-  dfree(d.cell_facets);
-  dfree(d.facet_nodes);
-  dfree(d.facet_cells_off);
-  dfree(d.facet_cells);
-  dfree(d.node_cells_off);
-  dfree(d.node_facets_off);
-  dfree(d.node_facets);
-  dfree(d.node_cells);
-  dfree(d.facet_perm);
-  delete m;
-}
+void eqlb_mesh_destroy(eqlb_mesh_t* m) { delete m; }
 
 int32_t eqlb_mesh_max_patch_cells(const eqlb_mesh_t* mesh) { return mesh ? mesh->m.ncells_max : 0; }
 
@@ -194,7 +172,7 @@ try
   if (eqlb::fill_tables_host(k, degree_dg, tab) != 0 || k > 4)
     return fail(EQLB_ERR_UNSUPPORTED, "RT_%d with DG_%d data%s is not in this build", k, degree_dg,
                 reconstruct_stress ? " (stress)" : "");
-  eqlb_se* h = new eqlb_se();
+  std::unique_ptr<eqlb_se> h(new eqlb_se());
   h->mesh = mesh;
   h->k = k;
   h->deg = degree_dg;
@@ -207,35 +185,14 @@ try
   h->nrt = k * (k + 2);
   h->nd = (degree_dg + 1) * (degree_dg + 2) / 2;
   if (h->tables.upload(tab.data(), tab.size()) || h->status.alloc(1))
-  {
-    eqlb_se_destroy(h);
     return EQLB_ERR_DEVICE;
-  }
   (void)hipMemset(h->status, 0, sizeof(int32_t));
-  *handle = h;
+  *handle = h.release();
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
 
-void eqlb_se_destroy(eqlb_se_t* h)
-{
-  if (!h)
-    return;
-  if (h->ev)
-  {
-    for (int i = 0; i < eqlb_se::EV_RING * eqlb_se::EV_PER_SET; ++i)
-      if (h->ev[i])
-        (void)hipEventDestroy(h->ev[i]);
-    delete[] h->ev;
-  }
-  if (h->ev_fork)
-    (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join)
-    (void)hipEventDestroy(h->ev_join);
-  if (h->side_stream)
-    (void)hipStreamDestroy(h->side_stream);
-  delete h;
-}
+void eqlb_se_destroy(eqlb_se_t* h) { delete h; }
 
 int eqlb_se_set_option(eqlb_se_t* h, const char* key, int32_t value)
 {
@@ -602,18 +559,15 @@ int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdi
   if (!mesh || !flux_hdiv || k < 1 || k > 4 || !(pi_1 > -1.0))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate_stress: invalid argument");
   EQLB_TRY(eqlb::check_memspace("eqlb_se_estimate_stress", memspace));
-  eqlb::DeviceMesh& m = mesh->m;
+  const eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (node_asym)
-  {
-    std::lock_guard<std::mutex> g(mesh->tiling_mutex); // (the mesh-level lock: first use from several threads)
-    if (!m.node_cells && upload(&m.node_cells, m.h_node_cells.data(), m.h_node_cells.size()))
-      return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate_stress: device allocation failed");
-  }
+  const int32_t* node_cells = nullptr; // (first use from several threads: the handle's lock is taken there)
+  if (node_asym && eqlb::mesh_node_cells(mesh, &node_cells))
+    return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate_stress: device allocation failed");
   const size_t nx = (size_t)m.ncells * k * (k + 2);
   int rc;
   if (memspace == EQLB_MEM_DEVICE)
-    rc = eqlb::launch_estimate_stress(m, m.node_cells, k, flux_hdiv, flux_hdiv + nx, korn, pi_1, cell_energy,
+    rc = eqlb::launch_estimate_stress(m, node_cells, k, flux_hdiv, flux_hdiv + nx, korn, pi_1, cell_energy,
                                       cell_wsym, node_asym, stream);
   else
   {
@@ -622,7 +576,7 @@ int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdi
     const auto d_e = s.out(cell_energy, m.ncells), d_w = s.out(cell_wsym, m.ncells), d_a = s.out(node_asym, m.nnodes);
     if (s.upload(stream) != hipSuccess)
       return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate_stress: device allocation failed");
-    rc = eqlb::launch_estimate_stress(m, m.node_cells, k, d_x, d_x + nx, d_k, pi_1, d_e, d_w, d_a, stream);
+    rc = eqlb::launch_estimate_stress(m, node_cells, k, d_x, d_x + nx, d_k, pi_1, d_e, d_w, d_a, stream);
     if (s.finish(stream) != hipSuccess)
       rc = EQLB_ERR_DEVICE;
   }
@@ -739,26 +693,18 @@ try
 {
   if (!handle)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_create: null argument");
+  std::unique_ptr<eqlb_ev> h(new eqlb_ev());
   eqlb_se* se = nullptr;
-  const int st = eqlb_se_create(mesh, k, degree_dg, nrhs, 0, 0, &se);
-  if (st)
-    return st;
+  EQLB_TRY(eqlb_se_create(mesh, k, degree_dg, nrhs, 0, 0, &se));
+  h->se.reset(se);
   se->mode = 1;
   se->ev_ndofs = (int64_t)mesh->m.nfacets * k + (int64_t)mesh->m.ncells * (k * k - k);
-  eqlb_ev* h = new eqlb_ev();
-  h->se = se;
-  *handle = h;
+  *handle = h.release();
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
 
-void eqlb_ev_destroy(eqlb_ev_t* h)
-{
-  if (!h)
-    return;
-  eqlb_se_destroy(h->se);
-  delete h;
-}
+void eqlb_ev_destroy(eqlb_ev_t* h) { delete h; }
 
 int eqlb_ev_set_option(eqlb_ev_t* h, const char* key, int32_t value)
 {
@@ -783,7 +729,7 @@ int eqlb_ev_set_option(eqlb_ev_t* h, const char* key, int32_t value)
   }
   if (!strcmp(key, "timing") || !strcmp(key, "scatter") || !strcmp(key, "accumulate") || !strcmp(key, "tile_cells")
       || !strcmp(key, "multi_rhs") || !strcmp(key, "large_patches"))
-    return eqlb_se_set_option(h->se, key, value);
+    return eqlb_se_set_option(h->se.get(), key, value);
   return fail(EQLB_ERR_INVALID_ARGUMENT, "unknown option '%s'", key);
 }
 
@@ -792,7 +738,7 @@ try
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_dofmap: null argument");
-  eqlb_se* se = h->se;
+  eqlb_se* se = h->se.get();
   const eqlb::DeviceMesh& m = se->mesh->m;
   se->ev_cell_dofs.reset();
   se->d_flux_hdiv.reset(); // staging size depends on the number of DOFs
@@ -818,7 +764,7 @@ int eqlb_ev_set_basis_transform(eqlb_ev_t* h, const double* C, const double* R)
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_basis_transform: null argument");
-  eqlb_se* se = h->se;
+  eqlb_se* se = h->se.get();
   se->ev_basis.reset();
   se->ev_basis_has_R = false;
   if (!C)
@@ -909,14 +855,14 @@ int eqlb_ev_large_patch_info(const eqlb_ev_t* h, int64_t* npatches, int32_t* max
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_large_patch_info: null handle");
-  return eqlb_se_large_patch_info(h->se, npatches, max_cells);
+  return eqlb_se_large_patch_info(h->se.get(), npatches, max_cells);
 }
 
 int eqlb_ev_tiling_blocks(const eqlb_ev_t* h, int64_t* out, int32_t n)
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_tiling_blocks: null handle");
-  return eqlb_se_tiling_blocks(h->se, out, n);
+  return eqlb_se_tiling_blocks(h->se.get(), out, n);
 }
 
 } // extern "C"

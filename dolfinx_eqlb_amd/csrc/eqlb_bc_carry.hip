@@ -494,7 +494,7 @@ try
     const int32_t i = bad, f = (i >= 0 && i < nlist) ? facets2[i] : -1;
     if (f < 0 || f >= r.nfacets)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets2[%d] = %d is no facet of the refined mesh", who, (int)i, (int)f);
-    if (r.h_facet_cells_off[(size_t)f + 1] - r.h_facet_cells_off[f] != 1)
+    if (refined->host.facet_cells_off[(size_t)f + 1] - refined->host.facet_cells_off[f] != 1)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets2[%d] = %d lies between two cells", who, (int)i, (int)f);
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets2[%d] = %d has no parent facet", who, (int)i, (int)f);
   }
@@ -521,7 +521,7 @@ try
 {
   if (!old || !plan || !fresh)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_carry_boundary: null argument");
-  return eqlb::carry_boundary("eqlb_ev_carry_boundary", "ev", old->se, plan, fresh->se, fresh, node_mask2, stream);
+  return eqlb::carry_boundary("eqlb_ev_carry_boundary", "ev", old->se.get(), plan, fresh->se.get(), fresh, node_mask2, stream);
 }
 EQLB_CATCH_ALL
 

@@ -22,7 +22,17 @@
 namespace eqlb
 {
 
-// The host copies of the mesh that the planner reads (the h_* vectors of DeviceMesh)
+// The host copies of the mesh, kept by the mesh handle for the planners (boundary plan, tiling, the boundary-facet checks
+// of the update and carry entries, the lengths of eqlb_mesh_export).  Filled once by the creator of the handle
+struct HostMesh
+{
+  std::vector<int32_t> node_ncells, node_nfcts, node_nbnd;       // cells / facets / one-cell facets at each node
+  std::vector<int32_t> cell_nodes, facet_nodes, facet_cells_off; // [ncells][3], [nfacets][2], [nfacets + 1]
+  std::vector<int32_t> node_facets_off, node_facets, node_cells_off, node_cells; // CSR
+  std::vector<double> x;                                         // [nnodes][3]
+};
+
+// What the planner reads of them (host_topology of eqlb_boundary_setup.hip; the stand-alone programs fill their own)
 struct HostTopology
 {
   int32_t nnodes, ncells, nfacets;

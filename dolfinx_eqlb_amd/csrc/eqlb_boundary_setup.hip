@@ -14,11 +14,13 @@ using eqlb::BoundaryPlan;
 using eqlb::BoundaryTables;
 using eqlb::DevBuf;
 
-eqlb::HostTopology host_topology(const eqlb::DeviceMesh& m)
+eqlb::HostTopology host_topology(const eqlb_mesh& mesh)
 {
-  return {m.nnodes, m.ncells, m.nfacets, m.h_node_ncells.data(), m.h_node_nfcts.data(), m.h_node_nbnd.data(),
-          m.h_cell_nodes.data(), m.h_facet_nodes.data(), m.h_facet_cells_off.data(), m.h_node_facets_off.data(),
-          m.h_node_facets.data(), m.h_node_cells_off.data(), m.h_node_cells.data()};
+  const eqlb::DeviceMesh& m = mesh.m;
+  const eqlb::HostMesh& h = mesh.host;
+  return {m.nnodes, m.ncells, m.nfacets, h.node_ncells.data(), h.node_nfcts.data(), h.node_nbnd.data(),
+          h.cell_nodes.data(), h.facet_nodes.data(), h.facet_cells_off.data(), h.node_facets_off.data(),
+          h.node_facets.data(), h.node_cells_off.data(), h.node_cells.data()};
 }
 
 // arguments of the patch builder that every SoA of the handle shares: the mesh and the facet types
@@ -243,7 +245,7 @@ try
   SetupTimer tm;
   const eqlb::PlanOptions opt{h->k, h->deg, h->nrhs, h->nrt, h->stress, h->mode, h->large_patches,
                               h->large_patches_stress, eqlb::large_patch_weaksym_ws_doubles};
-  const eqlb::HostTopology topo = host_topology(h->mesh->m);
+  const eqlb::HostTopology topo = host_topology(*h->mesh);
   BoundaryPlan plan; // (plan_boundary, in its two halves)
   int st = eqlb::check_boundary_table(topo, opt, facet_type, node_mask, plan);
   tm.lap("checks");
@@ -282,7 +284,7 @@ try
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_set_boundary: null argument");
-  eqlb_se* se = h->se;
+  eqlb_se* se = h->se.get();
   EQLB_TRY(eqlb_se_set_boundary(se, facet_type, nullptr, node_mask));
   const eqlb::DeviceMesh& m = se->mesh->m;
   bool inhomogeneous = false;

@@ -243,14 +243,15 @@ void fill_rule(BcRule& r, int32_t nq, const double* s, const double* w)
 }
 
 // host memory space of the mesh-only entry points: the listed facets are boundary facets of the mesh
-int check_boundary_facets(const char* who, const eqlb::DeviceMesh& m, int32_t nlist, const int32_t* facets)
+int check_boundary_facets(const char* who, const eqlb_mesh* mesh, int32_t nlist, const int32_t* facets)
 {
+  const std::vector<int32_t>& off = mesh->host.facet_cells_off;
   for (int32_t i = 0; i < nlist; ++i)
   {
     const int32_t f = facets[i];
-    if (f < 0 || f >= m.nfacets)
+    if (f < 0 || f >= mesh->m.nfacets)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is no facet of the mesh", who, (int)i, (int)f);
-    if (m.h_facet_cells_off[(size_t)f + 1] - m.h_facet_cells_off[f] != 1)
+    if (off[(size_t)f + 1] - off[f] != 1)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d lies between two cells", who, (int)i, (int)f);
   }
   return EQLB_OK;
@@ -347,7 +348,8 @@ int update_flux_bc(const char* who, eqlb_se* h, int32_t rhs, int32_t nlist, cons
       *nrejected = cnt[0];
     if (f < 0 || f >= m.nfacets)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is no facet of the mesh", who, (int)i, (int)f);
-    if (m.h_facet_cells_off[(size_t)f + 1] - m.h_facet_cells_off[f] != 1)
+    const std::vector<int32_t>& off = h->mesh->host.facet_cells_off;
+    if (off[(size_t)f + 1] - off[f] != 1)
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d lies between two cells: no flux boundary condition",
                   who, (int)i, (int)f);
     return fail(EQLB_ERR_INVALID_ARGUMENT,
@@ -408,7 +410,7 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null mesh", who);
   const eqlb::DeviceMesh& m = mesh->m;
   if (memspace == EQLB_MEM_HOST)
-    EQLB_TRY(check_boundary_facets(who, m, nlist, facets));
+    EQLB_TRY(check_boundary_facets(who, mesh, nlist, facets));
   if (nlist == 0)
     return EQLB_OK;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -453,7 +455,7 @@ try
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null mesh", who);
   const eqlb::DeviceMesh& m = mesh->m;
   if (memspace == EQLB_MEM_HOST)
-    EQLB_TRY(check_boundary_facets(who, m, nlist, facets));
+    EQLB_TRY(check_boundary_facets(who, mesh, nlist, facets));
   if (nlist == 0)
     return EQLB_OK;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -501,7 +503,7 @@ int eqlb_ev_update_flux_bc(eqlb_ev_t* h, int32_t rhs, int32_t nlist, const int32
                            int32_t* nrejected, int32_t memspace, void* stream)
 try
 {
-  return update_flux_bc("eqlb_ev_update_flux_bc", h ? h->se : nullptr, rhs, nlist, facets, nq, s, w, values, vector,
+  return update_flux_bc("eqlb_ev_update_flux_bc", h ? h->se.get() : nullptr, rhs, nlist, facets, nq, s, w, values, vector,
                         nrejected, memspace, stream);
 }
 EQLB_CATCH_ALL
@@ -513,7 +515,7 @@ int eqlb_se_get_boundary_values(eqlb_se_t* h, double* out, int32_t memspace, voi
 
 int eqlb_ev_get_boundary_values(eqlb_ev_t* h, double* out, int32_t memspace, void* stream)
 {
-  return get_boundary_values("eqlb_ev_get_boundary_values", h ? h->se : nullptr, out, memspace, stream);
+  return get_boundary_values("eqlb_ev_get_boundary_values", h ? h->se.get() : nullptr, out, memspace, stream);
 }
 
 } // extern "C"

@@ -233,7 +233,7 @@ try
         return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_halo_create: receive index %lld of peer entry %d out of range",
                     (long long)recv_idx[i][j], i);
   }
-  std::unique_ptr<eqlb_halo, void (*)(eqlb_halo*)> h(new eqlb_halo(), [](eqlb_halo* p) { eqlb_halo_destroy(p); });
+  std::unique_ptr<eqlb_halo> h(new eqlb_halo());
   h->nrhs = nrhs;
   h->nrt = nrt;
   h->nentries = nentries;

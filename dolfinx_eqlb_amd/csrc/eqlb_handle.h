@@ -3,8 +3,7 @@
 // file.
 #pragma once
 
-#include "eqlb_boundary_plan.h"
-#include "eqlb_host_util.h"
+#include "eqlb_mesh_handle.h" // (eqlb_boundary_plan.h, eqlb_host_util.h)
 
 namespace eqlb
 {
@@ -80,11 +79,6 @@ struct BoundaryTables
 int plan_tiles(const eqlb_se* h, const BoundaryPlan& bp, TilePlan& tp);
 } // namespace eqlb
 
-struct eqlb_ev
-{
-  struct eqlb_se* se = nullptr; // patch topology, tables, slots, timing of the shared machinery
-};
-
 struct eqlb_se
 {
   eqlb_mesh* mesh = nullptr;
@@ -105,8 +99,13 @@ struct eqlb_se
   eqlb::BoundaryTables bt;          // what eqlb_se_set_boundary builds
   // device
   eqlb::DevBuf<double> tables;
-  hipStream_t side_stream = nullptr; // the rest's patch kernels run here, next to the fused kernel
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // the side lane of the fused stress launch: the rest's patch kernels run on its stream, next to the fused kernel,
+  // between the two events.  Empty until a sweep needs it; built as a whole (eqlb_sweep.hip) or not at all
+  struct SideLane
+  {
+    eqlb::DevStream stream;
+    eqlb::DevEvent fork, join;
+  } side;
   // two-phase sweeps (multi-GPU overlap): tiles owning a priority cell are numbered first (BoundaryTables::t_nprio)
   std::vector<int32_t> prio_cells;
   int32_t tile_first = 0, tile_count = -1; // options "tile_first" / "tile_count" (-1: to the end)
@@ -131,6 +130,11 @@ struct eqlb_se
   static constexpr int ev_begin(int slot) { return 2 * slot; }
   static constexpr int ev_end(int slot) { return 2 * slot + 1; }
   static constexpr int EV_RING = 64, EV_PER_SET = 2 * EV_NSLOTS;
-  hipEvent_t* ev = nullptr; // [EV_RING][EV_PER_SET]
-  int64_t ev_calls = 0;     // calls recorded since timing was (re)enabled
+  std::vector<eqlb::DevEvent> ev; // [EV_RING][EV_PER_SET], empty until the first timed call: all of them or none
+  int64_t ev_calls = 0;           // calls recorded since timing was (re)enabled
+};
+
+struct eqlb_ev
+{
+  std::unique_ptr<eqlb_se> se; // patch topology, tables, slots, timing of the shared machinery
 };

@@ -1,12 +1,14 @@
 // Host helpers of every translation unit that allocates device memory or stages a host-memory call: error return,
-// the owners of device memory (DevBuf, DevCarve, StreamBuf - no other file names the allocator), the staged host call
-// (HostCall), the exception barrier of the entry points, set-up profiling.  Host code only.  Included
-//   through eqlb_handle.h by eqlb_api.hip, eqlb_boundary_setup.hip, eqlb_boundary_update.hip, eqlb_sweep.hip,
-//     eqlb_tiling_host.hip, eqlb_bc_carry.hip,
-//   through eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip, eqlb_bc_carry.hip,
+// the owners of device memory (DevBuf, DevCarve, StreamBuf - no other file names the allocator) and of events and
+// streams (DevEvent, DevStream - no other file creates or destroys one), the staged host call (HostCall), the exception
+// barrier of the entry points, set-up profiling.  Host code only.  Included
+//   through eqlb_mesh_handle.h (the units that dereference a mesh handle)
+//     and eqlb_handle.h by eqlb_api.hip, eqlb_boundary_setup.hip, eqlb_boundary_update.hip, eqlb_sweep.hip,
+//       eqlb_tiling_host.hip, eqlb_bc_carry.hip,
+//     and eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip, eqlb_bc_carry.hip,
+//     directly by eqlb_mesh_build.hip, eqlb_marking.hip, eqlb_primal_flux.hip, eqlb_primal_solve.hip,
 //   through eqlb_estimate_kernels.h by eqlb_estimate.hip, eqlb_estimate_lowdeg.hip, eqlb_estimate_lowdeg_k4.hip,
-//   directly by eqlb_mesh_build.hip, eqlb_marking.hip, eqlb_primal_flux.hip, eqlb_tiling_device.hip,
-//     eqlb_halo_rccl.hip, eqlb_primal_solve.hip.
+//   directly by eqlb_tiling_device.hip, eqlb_halo_rccl.hip.
 #pragma once
 
 #include "eqlb_internal.h"
@@ -61,25 +63,6 @@ int fail(int code, const char* fmt, Args... args)
       return st_;                                                                                 \
   } while (0)
 
-template <typename T>
-int upload(T** dst, const T* src, size_t n)
-{
-  *dst = nullptr;
-  if (n == 0)
-    n = 1;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(T)));
-  if (src)
-    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-
-template <typename T>
-void dfree(T*& p)
-{
-  if (p)
-    (void)hipFree(p);
-  p = nullptr;
-}
 } // namespace
 
 
@@ -100,14 +83,24 @@ public:
     return *this;
   }
   ~DevBuf() { reset(); }
-  void reset() { dfree(p_); }
+  void reset()
+  {
+    if (p_)
+      (void)hipFree(p_);
+    p_ = nullptr;
+  }
   T* get() const { return p_; }
   operator T*() const { return p_; }
   // n elements (at least one), copied from src unless that is nullptr; what the buffer held before is freed first
   int upload(const T* src, size_t n)
   {
     reset();
-    return ::upload(&p_, src, n);
+    if (n == 0)
+      n = 1;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T)));
+    if (src)
+      HIP_TRY(hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
   }
   int alloc(size_t n) { return upload(nullptr, n); }
   // the same without a message: n elements (at least one), for callers that word their own error
@@ -223,6 +216,32 @@ public:
     return static_cast<T*>(p_);
   }
 };
+
+// An event / a stream and its owner: created with the given flags, destroyed with the owner, move-only.  Reads as the
+// plain handle (nullptr until create()); no other file names the calls that create or destroy one.
+template <typename H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class DevHandle
+{
+  H h_ = nullptr;
+
+public:
+  DevHandle() = default;
+  DevHandle(DevHandle&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+  DevHandle& operator=(DevHandle&& o) noexcept
+  {
+    std::swap(h_, o.h_); // (o destroys what this one held)
+    return *this;
+  }
+  ~DevHandle()
+  {
+    if (h_)
+      (void)Destroy(h_);
+  }
+  hipError_t create(unsigned flags) { return h_ ? hipSuccess : Create(&h_, flags); }
+  operator H() const { return h_; }
+};
+using DevEvent = DevHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using DevStream = DevHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
 
 // A host-memory call: the same work as the device-memory call, staged and synchronous.  Declare the arrays (a null
 // host pointer stays null), upload(stream) allocates once and sends the inputs on the caller's stream, the entry point

@@ -5,8 +5,6 @@
 
 #include <cstdint>
 #include <string>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "../../include/eqlb.h"
@@ -39,23 +37,19 @@ constexpr uint8_t PFLAG_WS_LEVEL_SHIFT = 5;
 // lane's group -> its slot row is added to the stress coefficients (bit 8 + v)
 constexpr uint32_t INFO_GROUPROW_SHIFT = 8;
 
+// The device arrays of a mesh as every launcher takes them: a plain view that owns nothing.  The owner is the handle
+// (struct eqlb_mesh, eqlb_mesh_handle.h), which fills the view from its buffers and keeps the host copies the planners
+// read (HostMesh).
 struct DeviceMesh
 {
   int32_t nnodes = 0, ncells = 0, nfacets = 0, ncells_max = 0;
-  // device arrays
-  double* x = nullptr;            // [nnodes][3]
-  double* cellJ = nullptr;        // [ncells][4] J00 J01 J10 J11 (dx_i/dX_j), cached affine maps
-  int32_t *cell_nodes = nullptr, *cell_facets = nullptr, *facet_nodes = nullptr;
-  int32_t *facet_cells_off = nullptr, *facet_cells = nullptr;
-  int32_t *node_cells_off = nullptr, *node_facets_off = nullptr, *node_facets = nullptr;
-  int32_t* node_cells = nullptr;  // uploaded on first use (node-wise gathers of the estimator step)
-  uint8_t* facet_perm = nullptr;
-  // host copies needed for binning / tiling
-  std::vector<int32_t> h_node_ncells, h_node_nfcts, h_cell_nodes;
-  std::vector<int32_t> h_node_nbnd;       // one-cell facets at each node (eqlb_topology_check.h: which nodes the builder can walk)
-  std::vector<int32_t> h_facet_cells_off; // offsets of the facet -> cell table (1 or 2 cells per facet)
-  std::vector<int32_t> h_facet_nodes, h_node_facets_off, h_node_facets, h_node_cells_off, h_node_cells;
-  std::vector<double> h_x;
+  const double* x = nullptr;      // [nnodes][3]
+  double* cellJ = nullptr;        // [ncells][4] J00 J01 J10 J11 (dx_i/dX_j), cached affine maps (launch_cell_geometry)
+  const int32_t *cell_nodes = nullptr, *cell_facets = nullptr, *facet_nodes = nullptr;
+  const int32_t *facet_cells_off = nullptr, *facet_cells = nullptr;
+  const int32_t *node_cells_off = nullptr, *node_facets_off = nullptr, *node_facets = nullptr;
+  const int32_t* node_cells = nullptr; // nullptr until mesh_node_cells() of the handle has uploaded it: read it there
+  const uint8_t* facet_perm = nullptr;
 };
 
 // kernel arguments of the patch kernel (one launch per bin)
@@ -324,14 +318,5 @@ int fill_tables_host(int k, int deg, std::vector<double>& out);
 
 } // namespace eqlb
 
-struct eqlb_mesh
-{
-  eqlb::DeviceMesh m;
-  // cells in the order of the tile bisection (sorted by cell id inside every tile), per tile size: the tiling
-  // depends on the mesh alone, so further handles on the mesh (SE + EV, a stress handle ...) and further
-  // eqlb_se_set_boundary calls reuse it
-  std::mutex tiling_mutex;
-  std::map<int, std::vector<int32_t>> tiling_order;
-};
-
+struct eqlb_mesh; // the handle behind eqlb_mesh_t: eqlb_mesh_handle.h (host code only)
 struct eqlb_se; // the handle behind eqlb_se_t / eqlb_ev_t: eqlb_handle.h (host code only)

@@ -14,7 +14,7 @@
 // Every floating-point sum is made of per-thread partials in a fixed order, reduced by fixed trees: no fp atomics,
 // two calls on the same input give the same bits.
 #include "eqlb_device_common.h"
-#include "eqlb_host_util.h"
+#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_reduce.h"
 #include <cmath>
 

@@ -33,7 +33,7 @@
 // that the build holds one pool of 28 N bytes (two 8 N key buffers, two 4 N value buffers, 4 N facet ids: 84 bytes
 // per cell) and the work space of rocPRIM (a few MB at 1M cells), both freed before the call returns; phase B
 // reuses the pool (2 F <= 2 N entries of 4 bytes fit the 8 N buffers).
-#include "eqlb_host_util.h"
+#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_topology_check.h"
 
 #include <cstring> // (rocprim's texture iterator calls memset)
@@ -203,17 +203,6 @@ inline unsigned bits_of(unsigned long long v) // bits needed for the values 0 ..
   return b;
 }
 
-struct MeshDeleter
-{
-  void operator()(eqlb_mesh* m) const { eqlb_mesh_destroy(m); }
-};
-
-template <typename T>
-int dalloc(T** p, size_t n)
-{
-  return ::upload<T>(p, nullptr, n);
-}
-
 const char* const WHO = "eqlb_mesh_create_from_cells";
 
 int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* cell_nodes, int32_t memspace,
@@ -230,16 +219,18 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   };
   const int64_t n3 = 3 * (int64_t)ncells;
   const hipMemcpyKind in_kind = memspace == EQLB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  std::unique_ptr<eqlb_mesh, MeshDeleter> owner(new eqlb_mesh());
-  DeviceMesh& d = owner->m;
+  std::unique_ptr<eqlb_mesh> owner(new eqlb_mesh());
+  eqlb_mesh& o = *owner; // the buffers; the view d learns of them when the last one is allocated
+  DeviceMesh& d = o.m;
+  HostMesh& hm = o.host;
   d.nnodes = nnodes;
   d.ncells = ncells;
 
   // ---- phase A: facets ------------------------------------------------------------------------------------------
-  EQLB_TRY(dalloc(&d.cell_nodes, (size_t)n3));
-  EQLB_TRY(dalloc(&d.cell_facets, (size_t)n3));
-  EQLB_TRY(dalloc(&d.facet_perm, (size_t)n3));
-  HIP_TRY(hipMemcpyAsync(d.cell_nodes, cell_nodes, sizeof(int32_t) * (size_t)n3, in_kind, stream));
+  EQLB_TRY(o.cell_nodes.alloc((size_t)n3));
+  EQLB_TRY(o.cell_facets.alloc((size_t)n3));
+  EQLB_TRY(o.facet_perm.alloc((size_t)n3));
+  HIP_TRY(hipMemcpyAsync(o.cell_nodes, cell_nodes, sizeof(int32_t) * (size_t)n3, in_kind, stream));
 
   DevCarve pool;
   const auto p_keys_in = pool.piece<unsigned long long>((size_t)n3), p_keys_out = pool.piece<unsigned long long>((size_t)n3);
@@ -265,8 +256,8 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(words.get()), INT32_MAX, 2, stream));
   HIP_TRY(hipMemsetAsync(&words.get()->shared_key, 0xff, sizeof(unsigned long long), stream));
   HIP_TRY(hipMemsetAsync(&words.get()->nfacets, 0, 2 * sizeof(int32_t), stream));
-  hipLaunchKernelGGL(k_edge_keys, dim3(grid_of(ncells)), dim3(256), 0, stream, ncells, nnodes, d.cell_nodes, keys_in,
-                     vals_in, d.facet_perm, words.get());
+  hipLaunchKernelGGL(k_edge_keys, dim3(grid_of(ncells)), dim3(256), 0, stream, ncells, nnodes, o.cell_nodes, keys_in,
+                     vals_in, o.facet_perm, words.get());
   {
     size_t tb = tmp_bytes;
     HIP_TRY(rocprim::radix_sort_pairs(tmp.get(), tb, keys_in, keys_out, vals_in, vals_out, (size_t)n3, 0u, key_bits,
@@ -297,20 +288,21 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   d.nfacets = nfacets;
   const int64_t n2 = 2 * (int64_t)nfacets;
 
-  EQLB_TRY(dalloc(&d.facet_nodes, (size_t)n2));
-  EQLB_TRY(dalloc(&d.facet_cells_off, (size_t)nfacets + 1));
-  EQLB_TRY(dalloc(&d.facet_cells, (size_t)n3));
+  EQLB_TRY(o.facet_nodes.alloc((size_t)n2));
+  EQLB_TRY(o.facet_cells_off.alloc((size_t)nfacets + 1));
+  EQLB_TRY(o.facet_cells.alloc((size_t)n3));
   hipLaunchKernelGGL(k_facet_tables, dim3(grid_of(n3)), dim3(256), 0, stream, n3, nnodes, nfacets, keys_out, vals_out,
-                     fid, d.cell_facets, d.facet_cells, d.facet_cells_off, d.facet_nodes);
+                     fid, o.cell_facets, o.facet_cells, o.facet_cells_off, o.facet_nodes);
 
   // ---- phase B: the per-node tables (every node index is known to be valid from here on) ----------------------
-  EQLB_TRY(dalloc(&d.x, (size_t)nnodes * 3));
-  HIP_TRY(hipMemcpyAsync(d.x, x, sizeof(double) * (size_t)nnodes * 3, in_kind, stream));
-  EQLB_TRY(dalloc(&d.node_cells_off, (size_t)nnodes + 1));
-  EQLB_TRY(dalloc(&d.node_cells, (size_t)n3));
-  EQLB_TRY(dalloc(&d.node_facets_off, (size_t)nnodes + 1));
-  EQLB_TRY(dalloc(&d.node_facets, (size_t)n2));
-  EQLB_TRY(dalloc(&d.cellJ, (size_t)ncells * 4));
+  EQLB_TRY(o.x.alloc((size_t)nnodes * 3));
+  HIP_TRY(hipMemcpyAsync(o.x, x, sizeof(double) * (size_t)nnodes * 3, in_kind, stream));
+  EQLB_TRY(o.node_cells_off.alloc((size_t)nnodes + 1));
+  EQLB_TRY(o.node_cells.alloc((size_t)n3));
+  EQLB_TRY(o.node_facets_off.alloc((size_t)nnodes + 1));
+  EQLB_TRY(o.node_facets.alloc((size_t)n2));
+  EQLB_TRY(o.cellJ.alloc((size_t)ncells * 4));
+  o.publish();
   // the pool again: three buffers of max(n3, n2) <= 2 n3 entries of 4 bytes (the third runs over the two value
   // pieces, which follow each other)
   uint32_t* nk_in = reinterpret_cast<uint32_t*>(keys_in);
@@ -321,9 +313,9 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   DevBuf<int32_t> cnt; // [3][nnodes] cells, facets, one-cell facets per node
   EQLB_TRY(cnt.alloc(3 * (size_t)nnodes));
   size_t tb_c = 0, tb_f = 0, tb_r = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb_c, nk_in, nk_out, nv_in, d.node_cells, (size_t)n3, 0u, node_bits,
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb_c, nk_in, nk_out, nv_in, o.node_cells.get(), (size_t)n3, 0u, node_bits,
                                     stream));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb_f, nk_in, nk_out, nv_in, d.node_facets, (size_t)n2, 0u, node_bits,
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb_f, nk_in, nk_out, nv_in, o.node_facets.get(), (size_t)n2, 0u, node_bits,
                                     stream));
   HIP_TRY(rocprim::reduce(nullptr, tb_r, cnt.get(), &words.get()->ncells_max, (int32_t)0, (size_t)nnodes,
                           rocprim::maximum<int32_t>(), stream));
@@ -331,65 +323,56 @@ int build_mesh(int32_t nnodes, int32_t ncells, const double* x, const int32_t* c
   EQLB_TRY(tmp_b.alloc(tmp_b_bytes));
 
   // the facet tables have been written: keys_out / vals_out / fid are free (same stream)
-  hipLaunchKernelGGL(k_node_pairs, dim3(grid_of(n3)), dim3(256), 0, stream, n3, 3, d.cell_nodes, nk_in, nv_in);
+  hipLaunchKernelGGL(k_node_pairs, dim3(grid_of(n3)), dim3(256), 0, stream, n3, 3, o.cell_nodes, nk_in, nv_in);
   {
     size_t tb = tmp_b_bytes;
-    HIP_TRY(rocprim::radix_sort_pairs(tmp_b.get(), tb, nk_in, nk_out, nv_in, d.node_cells, (size_t)n3, 0u, node_bits,
+    HIP_TRY(rocprim::radix_sort_pairs(tmp_b.get(), tb, nk_in, nk_out, nv_in, o.node_cells.get(), (size_t)n3, 0u, node_bits,
                                       stream));
   }
-  hipLaunchKernelGGL(k_csr_offsets, dim3(grid_of(n3 + 1)), dim3(256), 0, stream, n3, nnodes, nk_out, d.node_cells_off);
-  hipLaunchKernelGGL(k_node_pairs, dim3(grid_of(n2)), dim3(256), 0, stream, n2, 2, d.facet_nodes, nk_in, nv_in);
+  hipLaunchKernelGGL(k_csr_offsets, dim3(grid_of(n3 + 1)), dim3(256), 0, stream, n3, nnodes, nk_out, o.node_cells_off);
+  hipLaunchKernelGGL(k_node_pairs, dim3(grid_of(n2)), dim3(256), 0, stream, n2, 2, o.facet_nodes, nk_in, nv_in);
   {
     size_t tb = tmp_b_bytes;
-    HIP_TRY(rocprim::radix_sort_pairs(tmp_b.get(), tb, nk_in, nk_out, nv_in, d.node_facets, (size_t)n2, 0u, node_bits,
+    HIP_TRY(rocprim::radix_sort_pairs(tmp_b.get(), tb, nk_in, nk_out, nv_in, o.node_facets.get(), (size_t)n2, 0u, node_bits,
                                       stream));
   }
-  hipLaunchKernelGGL(k_csr_offsets, dim3(grid_of(n2 + 1)), dim3(256), 0, stream, n2, nnodes, nk_out, d.node_facets_off);
+  hipLaunchKernelGGL(k_csr_offsets, dim3(grid_of(n2 + 1)), dim3(256), 0, stream, n2, nnodes, nk_out, o.node_facets_off);
   int32_t *c_nc = cnt.get(), *c_nf = cnt.get() + nnodes, *c_nb = cnt.get() + 2 * (size_t)nnodes;
-  hipLaunchKernelGGL(k_node_counts, dim3(grid_of(nnodes)), dim3(256), 0, stream, nnodes, d.node_cells_off,
-                     d.node_facets_off, d.node_facets, d.facet_cells_off, c_nc, c_nf, c_nb);
+  hipLaunchKernelGGL(k_node_counts, dim3(grid_of(nnodes)), dim3(256), 0, stream, nnodes, o.node_cells_off,
+                     o.node_facets_off, o.node_facets, o.facet_cells_off, c_nc, c_nf, c_nb);
   {
     size_t tb = tmp_b_bytes;
     HIP_TRY(rocprim::reduce(tmp_b.get(), tb, c_nc, &words.get()->ncells_max, (int32_t)0, (size_t)nnodes,
                             rocprim::maximum<int32_t>(), stream));
   }
-  launch_cell_geometry(ncells, d.x, d.cell_nodes, d.cellJ, stream);
+  launch_cell_geometry(ncells, o.x, o.cell_nodes, o.cellJ, stream);
   lap("from_cells: node tables (2 sorts)");
 
   // ---- phase C: the host copies ---------------------------------------------------------------------------------
-  d.h_node_ncells.resize(nnodes);
-  d.h_node_nfcts.resize(nnodes);
-  d.h_node_nbnd.resize(nnodes);
-  d.h_facet_cells_off.resize((size_t)nfacets + 1);
-  d.h_facet_nodes.resize((size_t)n2);
-  d.h_node_facets_off.resize((size_t)nnodes + 1);
-  d.h_node_facets.resize((size_t)n2);
-  d.h_node_cells_off.resize((size_t)nnodes + 1);
-  d.h_node_cells.resize((size_t)n3);
-  d.h_x.resize((size_t)nnodes * 3);
-  d.h_cell_nodes.resize((size_t)n3);
-  auto down = [&](std::vector<int32_t>& h, const int32_t* src) {
-    return hipMemcpyAsync(h.data(), src, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, stream);
+  auto down = [&](std::vector<int32_t>& h, const int32_t* src, size_t n) {
+    h.resize(n);
+    return hipMemcpyAsync(h.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream);
   };
-  HIP_TRY(down(d.h_node_ncells, c_nc));
-  HIP_TRY(down(d.h_node_nfcts, c_nf));
-  HIP_TRY(down(d.h_node_nbnd, c_nb));
-  HIP_TRY(down(d.h_facet_cells_off, d.facet_cells_off));
-  HIP_TRY(down(d.h_facet_nodes, d.facet_nodes));
-  HIP_TRY(down(d.h_node_facets_off, d.node_facets_off));
-  HIP_TRY(down(d.h_node_facets, d.node_facets));
-  HIP_TRY(down(d.h_node_cells_off, d.node_cells_off));
-  HIP_TRY(down(d.h_node_cells, d.node_cells));
+  HIP_TRY(down(hm.node_ncells, c_nc, (size_t)nnodes));
+  HIP_TRY(down(hm.node_nfcts, c_nf, (size_t)nnodes));
+  HIP_TRY(down(hm.node_nbnd, c_nb, (size_t)nnodes));
+  HIP_TRY(down(hm.facet_cells_off, o.facet_cells_off, (size_t)nfacets + 1));
+  HIP_TRY(down(hm.facet_nodes, o.facet_nodes, (size_t)n2));
+  HIP_TRY(down(hm.node_facets_off, o.node_facets_off, (size_t)nnodes + 1));
+  HIP_TRY(down(hm.node_facets, o.node_facets, (size_t)n2));
+  HIP_TRY(down(hm.node_cells_off, o.node_cells_off, (size_t)nnodes + 1));
+  HIP_TRY(down(hm.node_cells, o.node_cells, (size_t)n3));
   HIP_TRY(hipMemcpyAsync(&w, words.get(), sizeof(w), hipMemcpyDeviceToHost, stream));
   if (memspace == EQLB_MEM_HOST)
   {
-    memcpy(d.h_x.data(), x, sizeof(double) * d.h_x.size());
-    memcpy(d.h_cell_nodes.data(), cell_nodes, sizeof(int32_t) * d.h_cell_nodes.size());
+    hm.x.assign(x, x + (size_t)nnodes * 3);
+    hm.cell_nodes.assign(cell_nodes, cell_nodes + (size_t)n3);
   }
   else
   {
-    HIP_TRY(hipMemcpyAsync(d.h_x.data(), d.x, sizeof(double) * d.h_x.size(), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(down(d.h_cell_nodes, d.cell_nodes));
+    hm.x.resize((size_t)nnodes * 3);
+    HIP_TRY(hipMemcpyAsync(hm.x.data(), o.x, sizeof(double) * hm.x.size(), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(down(hm.cell_nodes, o.cell_nodes, (size_t)n3));
   }
   device_tiling_prepare(); // as eqlb_mesh_create: the code object of the tile builder is loaded here
   HIP_TRY(hipStreamSynchronize(stream));
@@ -442,15 +425,13 @@ int eqlb_mesh_export(eqlb_mesh_t* mesh, int32_t* cell_facets, int32_t* facet_nod
   if (!mesh)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_mesh_export: null mesh");
   EQLB_TRY(eqlb::check_memspace("eqlb_mesh_export", memspace));
-  eqlb::DeviceMesh& m = mesh->m;
+  const eqlb::DeviceMesh& m = mesh->m;
+  const eqlb::HostMesh& hm = mesh->host;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (node_cells)
-  {
-    // a handle of eqlb_mesh_create uploads this table on first use (eqlb_se_estimate_stress)
-    std::lock_guard<std::mutex> g(mesh->tiling_mutex);
-    if (!m.node_cells && upload(&m.node_cells, m.h_node_cells.data(), m.h_node_cells.size()))
-      return fail(EQLB_ERR_DEVICE, "eqlb_mesh_export: device allocation failed");
-  }
+  // a handle of eqlb_mesh_create uploads this table on first use
+  const int32_t* d_node_cells = nullptr;
+  if (node_cells && eqlb::mesh_node_cells(mesh, &d_node_cells))
+    return fail(EQLB_ERR_DEVICE, "eqlb_mesh_export: device allocation failed");
   const hipMemcpyKind kind = memspace == EQLB_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   const size_t n3 = 3 * (size_t)m.ncells, nn = (size_t)m.nnodes, nf = (size_t)m.nfacets;
   struct
@@ -462,11 +443,11 @@ int eqlb_mesh_export(eqlb_mesh_t* mesh, int32_t* cell_facets, int32_t* facet_nod
       {cell_facets, m.cell_facets, 4 * n3},
       {facet_nodes, m.facet_nodes, 8 * nf},
       {facet_cells_offsets, m.facet_cells_off, 4 * (nf + 1)},
-      {facet_cells, m.facet_cells, 4 * (size_t)m.h_facet_cells_off[nf]},
+      {facet_cells, m.facet_cells, 4 * (size_t)hm.facet_cells_off[nf]},
       {node_cells_offsets, m.node_cells_off, 4 * (nn + 1)},
-      {node_cells, m.node_cells, 4 * (size_t)m.h_node_cells_off[nn]},
+      {node_cells, d_node_cells, 4 * (size_t)hm.node_cells_off[nn]},
       {node_facets_offsets, m.node_facets_off, 4 * (nn + 1)},
-      {node_facets, m.node_facets, 4 * (size_t)m.h_node_facets_off[nn]},
+      {node_facets, m.node_facets, 4 * (size_t)hm.node_facets_off[nn]},
       {facet_perm, m.facet_perm, n3},
   };
   for (const auto& j : jobs)

@@ -22,7 +22,7 @@
 // permuted together with cell_dofs gives the same bits as the built-in one.  No atomics, no scratch, one fixed order
 // of operations per value: two runs give the same bits.
 #include "eqlb_device_common.h"
-#include "eqlb_host_util.h"
+#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_tables_gen.h"
 #include <cmath>
 #include <cstring>

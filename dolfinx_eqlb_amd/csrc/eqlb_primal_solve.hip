@@ -24,7 +24,7 @@
 // remaining kernels of a batch return at once, so the result does not depend on how often the host looks: it reads
 // the state every EQLB_PRIMAL_CHECK_EVERY iterations.  Nothing is allocated inside the iteration.
 #include "eqlb_device_common.h"
-#include "eqlb_host_util.h"
+#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_reduce.h"
 #include "eqlb_tables_gen.h"
 
@@ -694,7 +694,7 @@ try
   if (!mesh || !handle)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
   EQLB_TRY(check_memspace(who, memspace));
-  DeviceMesh& m = mesh->m;
+  const DeviceMesh& m = mesh->m;
   const int ne = p - 1, ni = (p - 1) * (p - 2) / 2, nd = nd_of(p);
   const int64_t ndofs = (int64_t)m.nnodes + (int64_t)m.nfacets * ne + (int64_t)m.ncells * ni;
   if (ndofs > INT32_MAX || (int64_t)m.ncells * nd > INT32_MAX || m.ncells < 1)
@@ -702,7 +702,8 @@ try
                 (long long)m.ncells * nd);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   // a handle of eqlb_mesh_create keeps node -> cell on the host until somebody needs it on the device
-  if (!m.node_cells && upload(&m.node_cells, m.h_node_cells.data(), m.h_node_cells.size()))
+  const int32_t* node_cells = nullptr;
+  if (mesh_node_cells(mesh, &node_cells))
     return EQLB_ERR_DEVICE;
   std::unique_ptr<eqlb_primal> h(new eqlb_primal);
   h->mesh = mesh;
@@ -744,7 +745,7 @@ try
   // the dofmap, by the kernel behind eqlb_mesh_lagrange_dofmap (device memory space: one launch, nothing waits)
   EQLB_TRY(eqlb_mesh_lagrange_dofmap(mesh, p, h->cell_dofs.get(), nullptr, EQLB_MEM_DEVICE, stream_));
   const int64_t nshared = (int64_t)m.nnodes + (int64_t)m.nfacets * ne;
-  hipLaunchKernelGGL(k_primal_slots, dim3(grid_of(nshared, PS_THREADS)), dim3(PS_THREADS), 0, stream, s, m.node_cells,
+  hipLaunchKernelGGL(k_primal_slots, dim3(grid_of(nshared, PS_THREADS)), dim3(PS_THREADS), 0, stream, s, node_cells,
                      m.facet_cells, h->cell_dofs.get(), h->slots.get(), h->status.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));

@@ -2,7 +2,7 @@
 // transfer entries read from it (eqlb_transfer.hip).  Host code only.
 #pragma once
 
-#include "eqlb_host_util.h"
+#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 
 struct eqlb_refine
 {

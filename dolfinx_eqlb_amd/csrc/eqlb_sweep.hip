@@ -23,7 +23,7 @@ struct Sweep
   const double* const* d_f;
   double* const* d_x;
   eqlb::SeArgs a;          // arguments common to the patch kernels of the call
-  hipEvent_t* evs;         // event set of this call, or nullptr (option "timing" off)
+  const eqlb::DevEvent* evs; // event set of this call, or nullptr (option "timing" off)
 };
 
 // Resolves EQLB_SCATTER_AUTO - the tiled launch where it applies and is the fastest (k <= 3, plain flux
@@ -100,36 +100,27 @@ int stage_out(eqlb_se* h, size_t s_x, double* const* x_io, double* const* d_x, h
 }
 
 // Option "timing": the event set of this call in the ring of the handle (created on first use)
-int timing_events(eqlb_se* h, hipEvent_t*& evs)
+int timing_events(eqlb_se* h, const eqlb::DevEvent*& evs)
 {
-  constexpr int N = eqlb_se::EV_RING * eqlb_se::EV_PER_SET;
-  if (h->ev && !h->ev[N - 1])
+  if (h->ev.empty())
   {
-    // an earlier hipEventCreate failed half way: start over
-    for (int i = 0; i < N; ++i)
-      if (h->ev[i])
-        (void)hipEventDestroy(h->ev[i]);
-    delete[] h->ev;
-    h->ev = nullptr;
+    std::vector<eqlb::DevEvent> ring(eqlb_se::EV_RING * eqlb_se::EV_PER_SET);
+    for (eqlb::DevEvent& e : ring)
+      HIP_TRY(e.create(hipEventDefault));
+    h->ev = std::move(ring);
   }
-  if (!h->ev)
-  {
-    h->ev = new hipEvent_t[N](); // null until created
-    for (int i = 0; i < N; ++i)
-      HIP_TRY(hipEventCreate(&h->ev[i]));
-  }
-  evs = h->ev + (h->ev_calls % eqlb_se::EV_RING) * eqlb_se::EV_PER_SET;
+  evs = h->ev.data() + (h->ev_calls % eqlb_se::EV_RING) * eqlb_se::EV_PER_SET;
   return EQLB_OK;
 }
 
 // begin / end of a timing slot on a stream; evs == nullptr: untimed
-int mark_begin(hipEvent_t* evs, int slot, hipStream_t st)
+int mark_begin(const eqlb::DevEvent* evs, int slot, hipStream_t st)
 {
   if (evs)
     HIP_TRY(hipEventRecord(evs[eqlb_se::ev_begin(slot)], st));
   return EQLB_OK;
 }
-int mark_end(hipEvent_t* evs, int slot, hipStream_t st)
+int mark_end(const eqlb::DevEvent* evs, int slot, hipStream_t st)
 {
   if (evs)
     HIP_TRY(hipEventRecord(evs[eqlb_se::ev_end(slot)], st));
@@ -221,7 +212,7 @@ int ensure_slots(const Sweep& s, SlotCover cover, hipStream_t st)
 
 // Patch kernels of a range on stream st: rows into the slot buffer (scatter = SLOTS) or added to flux_hdiv by fp64
 // atomics (ATOMIC).  All bins in one launch where that kernel exists (timing slot of bin 0), else one launch per bin.
-int launch_patches(const Sweep& s, const PatchRange& pr, int scatter, hipStream_t st, hipEvent_t* evs)
+int launch_patches(const Sweep& s, const PatchRange& pr, int scatter, hipStream_t st, const eqlb::DevEvent* evs)
 {
   const eqlb_se* h = s.h;
   const bool to_slots = scatter == EQLB_SCATTER_SLOTS;
@@ -274,7 +265,7 @@ int launch_patches(const Sweep& s, const PatchRange& pr, int scatter, hipStream_
 }
 
 // Patches of more than 63 cells: one workgroup each, rows into the slot buffer (rewritten by every call)
-int launch_large(const Sweep& s, hipStream_t st, hipEvent_t* evs)
+int launch_large(const Sweep& s, hipStream_t st, const eqlb::DevEvent* evs)
 {
   const eqlb_se* h = s.h;
   eqlb::SeArgs al = s.a;
@@ -297,7 +288,7 @@ int launch_large(const Sweep& s, hipStream_t st, hipEvent_t* evs)
 // Weak symmetry of rows 0, 1 on the large patches: one launch for all of them, behind launch_large (it corrects the slot
 // rows that kernel wrote) and before the reduction that consumes them.  Timing slot of the weak-symmetry kernels:
 // `begin` opens it, else the launch extends the slot that launch_weaksym has opened on this stream
-int launch_weaksym_large(const Sweep& s, hipStream_t st, hipEvent_t* evs, bool begin)
+int launch_weaksym_large(const Sweep& s, hipStream_t st, const eqlb::DevEvent* evs, bool begin)
 {
   const eqlb_se* h = s.h;
   eqlb::SeArgs al = s.a;
@@ -319,7 +310,7 @@ int launch_weaksym_large(const Sweep& s, hipStream_t st, hipEvent_t* evs, bool b
 // Weak symmetry of rows 0, 1 on the patch-local stresses held in the slots
 // (se/reconstruction.hpp:237-270; the grouped boundary patches of :170-234 are flagged by the
 // patch builder: PFLAG_WS_SKIP / PFLAG_WS_GROUP)
-int launch_weaksym(const Sweep& s, const PatchRange& pr, hipStream_t st, hipEvent_t* evs)
+int launch_weaksym(const Sweep& s, const PatchRange& pr, hipStream_t st, const eqlb::DevEvent* evs)
 {
   const eqlb_se* h = s.h;
   EQLB_TRY(mark_begin(evs, eqlb_se::EV_WEAKSYM, st));
@@ -475,27 +466,29 @@ int sweep_tiled(const Sweep& s)
   const bool rest_now = s.stress_fused && with_first_range && (h->bt.t_rest > 0 || large_now);
   if (rest_now)
   {
-    if (!h->side_stream)
+    if (!h->side.stream)
     {
-      HIP_TRY(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+      eqlb_se::SideLane lane;
+      HIP_TRY(lane.stream.create(hipStreamNonBlocking));
+      HIP_TRY(lane.fork.create(hipEventDisableTiming));
+      HIP_TRY(lane.join.create(hipEventDisableTiming));
+      h->side = std::move(lane);
     }
     const PatchRange rest = rest_of_fused_stress(h);
-    HIP_TRY(hipEventRecord(h->ev_fork, s.stream));
-    HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-    EQLB_TRY(ensure_slots(s, COVER_REST, h->side_stream));
+    HIP_TRY(hipEventRecord(h->side.fork, s.stream));
+    HIP_TRY(hipStreamWaitEvent(h->side.stream, h->side.fork, 0));
+    EQLB_TRY(ensure_slots(s, COVER_REST, h->side.stream));
     if (h->bt.t_rest > 0)
     {
-      EQLB_TRY(launch_patches(s, rest, EQLB_SCATTER_SLOTS, h->side_stream, nullptr));
-      EQLB_TRY(launch_weaksym(s, rest, h->side_stream, nullptr));
+      EQLB_TRY(launch_patches(s, rest, EQLB_SCATTER_SLOTS, h->side.stream, nullptr));
+      EQLB_TRY(launch_weaksym(s, rest, h->side.stream, nullptr));
     }
     if (large_now)
     {
-      EQLB_TRY(launch_large(s, h->side_stream, s.evs));
-      EQLB_TRY(launch_weaksym_large(s, h->side_stream, s.evs, true));
+      EQLB_TRY(launch_large(s, h->side.stream, s.evs));
+      EQLB_TRY(launch_weaksym_large(s, h->side.stream, s.evs, true));
     }
-    HIP_TRY(hipEventRecord(h->ev_join, h->side_stream));
+    HIP_TRY(hipEventRecord(h->side.join, h->side.stream));
   }
   int r0 = 0;
   if (s.stress_fused)
@@ -521,7 +514,7 @@ int sweep_tiled(const Sweep& s)
   if (rest_now)
   {
     // only the cells that a patch of the generic kernels touches
-    HIP_TRY(hipStreamWaitEvent(s.stream, h->ev_join, 0));
+    HIP_TRY(hipStreamWaitEvent(s.stream, h->side.join, 0));
     if (large_now)
       EQLB_TRY(reduce_cells(s, h->bt.l_nrest_cells, h->bt.l_rest_cells, s.stream));
     else
@@ -556,7 +549,7 @@ int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const double* con
   if (memspace == EQLB_MEM_HOST)
     EQLB_TRY(stage_in(h, s_g, s_f, s_x, g_in, f_in, x_io, d_g.data(), d_f.data(), d_x.data(), stream));
 
-  hipEvent_t* evs = nullptr;
+  const eqlb::DevEvent* evs = nullptr;
   if (h->timing)
     EQLB_TRY(timing_events(h, evs));
 
@@ -672,7 +665,7 @@ double eqlb_se_last_kernel_ms(const eqlb_se_t* h, int32_t which)
   // 6: weak-symmetry kernels; 7: large-patch kernel.
   // Average device time per launch over the calls recorded since timing was enabled
   // (at most the last EV_RING calls).  Synchronises with the recorded events.
-  if (!h || !h->ev || h->ev_calls == 0 || which < 0 || which >= eqlb_se::EV_NSLOTS)
+  if (!h || h->ev.empty() || h->ev_calls == 0 || which < 0 || which >= eqlb_se::EV_NSLOTS)
     return 0.0;
   if (which == eqlb_se::EV_WEAKSYM && !h->stress)
     return 0.0;
@@ -688,7 +681,7 @@ double eqlb_se_last_kernel_ms(const eqlb_se_t* h, int32_t which)
   double sum = 0.0;
   for (int64_t s = 0; s < nset; ++s)
   {
-    hipEvent_t* evs = h->ev + s * eqlb_se::EV_PER_SET;
+    const eqlb::DevEvent* evs = h->ev.data() + s * eqlb_se::EV_PER_SET;
     float ms = 0.f;
     if (hipEventSynchronize(evs[eqlb_se::ev_end(which)]) != hipSuccess
         || hipEventElapsedTime(&ms, evs[eqlb_se::ev_begin(which)], evs[eqlb_se::ev_end(which)]) != hipSuccess)
@@ -705,7 +698,7 @@ try
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  return eqlb_se_equilibrate(h->se, flux_dg, rhs_dg, flux_hdiv, memspace, stream);
+  return eqlb_se_equilibrate(h->se.get(), flux_dg, rhs_dg, flux_hdiv, memspace, stream);
 }
 EQLB_CATCH_ALL
 
@@ -715,7 +708,7 @@ try
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "Equilibration: Input sizes does not match");
-  return eqlb_se_equilibrate_lists(h->se, flux_dg, rhs_dg, flux_hdiv, memspace, stream);
+  return eqlb_se_equilibrate_lists(h->se.get(), flux_dg, rhs_dg, flux_hdiv, memspace, stream);
 }
 EQLB_CATCH_ALL
 
@@ -723,12 +716,12 @@ int eqlb_ev_check_status(eqlb_ev_t* h, void* stream)
 {
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_ev_check_status: null handle");
-  return eqlb_se_check_status(h->se, stream);
+  return eqlb_se_check_status(h->se.get(), stream);
 }
 
 double eqlb_ev_last_kernel_ms(const eqlb_ev_t* h, int32_t which)
 {
-  return h ? eqlb_se_last_kernel_ms(h->se, which) : 0.0;
+  return h ? eqlb_se_last_kernel_ms(h->se.get(), which) : 0.0;
 }
 
 } // extern "C"

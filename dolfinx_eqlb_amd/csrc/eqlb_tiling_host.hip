@@ -376,6 +376,7 @@ void count_tile_blocks(int K, bool t_stress, bool full_only, const std::vector<e
 int bisect_cells(eqlb_mesh* mesh, int tc, int32_t ntiles, SetupTimer& tm, eqlb::uvec<int32_t>& cells)
 {
   const eqlb::DeviceMesh& m = mesh->m;
+  const eqlb::HostMesh& hm = mesh->host;
   const int32_t nc = m.ncells;
   {
     std::lock_guard<std::mutex> g(mesh->tiling_mutex);
@@ -391,8 +392,8 @@ int bisect_cells(eqlb_mesh* mesh, int tc, int32_t ntiles, SetupTimer& tm, eqlb::
   for (int32_t i = 0; i < m.nnodes; ++i)
     for (int d = 0; d < 2; ++d)
     {
-      blo[d] = std::min(blo[d], m.h_x[3 * (size_t)i + d]);
-      bhi[d] = std::max(bhi[d], m.h_x[3 * (size_t)i + d]);
+      blo[d] = std::min(blo[d], hm.x[3 * (size_t)i + d]);
+      bhi[d] = std::max(bhi[d], hm.x[3 * (size_t)i + d]);
     }
   const double ext = std::max(bhi[0] - blo[0], bhi[1] - blo[1]);
   const double inv = (ext > 0.0) ? 1.0 / (3.0 * ext) : 0.0;
@@ -412,23 +413,23 @@ int bisect_cells(eqlb_mesh* mesh, int tc, int32_t ntiles, SetupTimer& tm, eqlb::
     eqlb::uvec<TileItem> items(nc);
     std::vector<uint8_t> stretched(nc);
     parallel_for(nc, 1 << 16, [&](int64_t c) {
-      const int32_t* cn = &m.h_cell_nodes[3 * (size_t)c];
+      const int32_t* cn = &hm.cell_nodes[3 * (size_t)c];
       double cx = 0.0, cy = 0.0;
       for (int j = 0; j < 3; ++j)
       {
-        cx += m.h_x[3 * (size_t)cn[j]] - blo[0];
-        cy += m.h_x[3 * (size_t)cn[j] + 1] - blo[1];
+        cx += hm.x[3 * (size_t)cn[j]] - blo[0];
+        cy += hm.x[3 * (size_t)cn[j] + 1] - blo[1];
       }
       items[c] = {(float)(cx * inv), (float)(cy * inv), (int32_t)c};
-      const double* p0 = &m.h_x[3 * (size_t)cn[0]];
-      const double* p1 = &m.h_x[3 * (size_t)cn[1]];
-      const double* p2 = &m.h_x[3 * (size_t)cn[2]];
+      const double* p0 = &hm.x[3 * (size_t)cn[0]];
+      const double* p1 = &hm.x[3 * (size_t)cn[1]];
+      const double* p2 = &hm.x[3 * (size_t)cn[2]];
       const double e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e2x = p2[0] - p0[0], e2y = p2[1] - p0[1];
       const double l2 = std::max(std::max(e1x * e1x + e1y * e1y, e2x * e2x + e2y * e2y),
                                  (e2x - e1x) * (e2x - e1x) + (e2y - e1y) * (e2y - e1y));
       stretched[c] = l2 > 6.0 * std::fabs(e1x * e2y - e1y * e2x) ? 1 : 0;
     });
-    RcbPool pool{m.h_cell_nodes.data(), m.nnodes, stretched.data(), {}, {}};
+    RcbPool pool{hm.cell_nodes.data(), m.nnodes, stretched.data(), {}, {}};
     tm.lap("tiles: centroids");
     rcb_split(items.data(), nc, ntiles, tc, pool, nullptr, 0);
     tm.lap("tiles: bisection");
@@ -513,32 +514,33 @@ constexpr int NCL = 6; // classes of a bin: full | interior with P - 1, P - 2, P
 // patches (their wave-blocks run the specialised body of the kernel) first -, in order of first appearance; tnodes:
 // flat storage, 3 TC entries per tile.  full_only: the lists of a tile are padded to whole wave-blocks with copies of
 // a full patch that own no cell (nint keeps the number of real patches)
-void list_tile_patches(const eqlb::DeviceMesh& m, const std::vector<int8_t>& tile_bin, bool full_only,
+void list_tile_patches(const eqlb::HostMesh& m, const std::vector<int8_t>& tile_bin, bool full_only,
                        eqlb::TilePlan& tp, eqlb::uvec<int32_t>& tnodes)
 {
   const int TC = tp.tc;
+  const size_t nnodes = m.node_ncells.size();
   std::vector<eqlb::TileDesc>& tiles = tp.tiles;
   // sort key of a node: NCL * bin + class (full interior patch 0 | interior patch with P - 1, P - 2, P - 3 cells 1, 2, 3 |
   // other interior patch 4 | boundary patch 5); -1: not listed
   // (one byte per node, cache resident, instead of three scattered reads per visit of a node)
-  std::vector<int8_t> nkey(m.nnodes);
-  parallel_for(m.nnodes, 1 << 16, [&](int64_t nd) {
+  std::vector<int8_t> nkey(nnodes);
+  parallel_for(nnodes, 1 << 16, [&](int64_t nd) {
     const int b_ = tile_bin[nd];
     if (b_ < 0)
     {
       nkey[nd] = -1;
       return;
     }
-    const bool interior = m.h_node_ncells[nd] == m.h_node_nfcts[nd]; // no boundary facet at the node
-    const int missing = eqlb::BIN_P[b_] - m.h_node_ncells[nd];         // idle lanes of the patch group
-    const int cls = eqlb::patch_is_full(m.h_node_ncells[nd], m.h_node_nfcts[nd], b_) ? 0
+    const bool interior = m.node_ncells[nd] == m.node_nfcts[nd]; // no boundary facet at the node
+    const int missing = eqlb::BIN_P[b_] - m.node_ncells[nd];         // idle lanes of the patch group
+    const int cls = eqlb::patch_is_full(m.node_ncells[nd], m.node_nfcts[nd], b_) ? 0
                     : !interior                                                       ? 5
                     : (missing >= 1 && missing <= 3)                                  ? missing
                                                                                       : 4;
     nkey[nd] = (int8_t)(NCL * b_ + cls);
   });
   tile_chunks(tp.ntiles, [&](int64_t t0, int64_t t1) {
-    std::vector<int32_t> stamp(m.nnodes, -1), seen(3 * (size_t)TC);
+    std::vector<int32_t> stamp(nnodes, -1), seen(3 * (size_t)TC);
     for (int64_t t = t0; t < t1; ++t)
     {
       int nseen = 0;
@@ -550,7 +552,7 @@ void list_tile_patches(const eqlb::DeviceMesh& m, const std::vector<int8_t>& til
           continue;
         for (int j = 0; j < 3; ++j)
         {
-          const int32_t nd = m.h_cell_nodes[3 * (size_t)c + j];
+          const int32_t nd = m.cell_nodes[3 * (size_t)c + j];
           if (nkey[nd] < 0)
             tiles[t].zero = 1; // masked-out vertex: the (cell, vertex) row of this tile stays unwritten
           if (nkey[nd] < 0 || stamp[nd] == (int32_t)t)
@@ -657,7 +659,7 @@ int plan_tiles(const eqlb_se* h, const BoundaryPlan& bp, TilePlan& tp)
   tm.lap("tiles: sort + priority");
   tp.tiles.assign(tp.ntiles, TileDesc{});
   uvec<int32_t> tnodes((size_t)tp.ntiles * 3 * tp.tc);
-  list_tile_patches(m, bp.tile_bin, full_only, tp, tnodes);
+  list_tile_patches(h->mesh->host, bp.tile_bin, full_only, tp, tnodes);
   EQLB_TRY(place_instances(full_only, tnodes, tp));
   tm.lap("tiles: patch lists");
   count_tile_blocks(h->k, bp.t_stress, full_only, tp.tiles, tp.blocks);

@@ -401,11 +401,9 @@ try
                 (long long)ndofs, (long long)ndofs2);
   ProlongArgs a;
   EQLB_TRY(common_args(who, plan, refined, bs, nrhs, memspace, a));
-  DeviceMesh& r = refined->m;
   // a handle of eqlb_mesh_create keeps node -> cell on the host until somebody needs it on the device
-  if (!r.node_cells && upload(&r.node_cells, r.h_node_cells.data(), r.h_node_cells.size()))
+  if (mesh_node_cells(refined, &a.node_cells2))
     return EQLB_ERR_DEVICE;
-  a.node_cells2 = r.node_cells;
   a.ndofs = ndofs;
   a.ndofs2 = ndofs2;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);

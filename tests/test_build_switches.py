@@ -2,7 +2,8 @@
 compiler's command line can override are exactly those declared in eqlb_tuning.h (numeric
 parameters of size, occupancy and tolerance; decided code variants are resolved in the source,
 DESIGN.md "retired build switches").  Device memory has one home: only eqlb_host_util.h names the
-allocator, and the hand-rolled stagings it replaced stay away."""
+allocator and the calls that create or destroy an event or a stream, and the hand-rolled stagings, frees and
+first-use uploads it replaced stay away."""
 
 import glob
 import os
@@ -105,6 +106,40 @@ def test_only_the_host_helpers_name_the_device_allocator():
     helpers = _hip_sources()["eqlb_host_util.h"]
     for word in ("hipMalloc", "hipFree", "hipMallocAsync", "hipFreeAsync"):
         assert re.search(rf"\b{word}\b", helpers), word
+
+
+def test_only_the_host_helpers_name_the_event_and_stream_calls():
+    # (comments included, as for the allocator)
+    calls = r"\bhip(?:EventCreate\w*|EventDestroy|StreamCreate\w*|StreamDestroy)\b"
+    for name, text in _hip_sources().items():
+        if name != "eqlb_host_util.h":
+            found = sorted(set(re.findall(calls, text)))
+            assert not found, f"{name}: {found}"
+    helpers = _hip_sources()["eqlb_host_util.h"]
+    for word in ("hipEventCreateWithFlags", "hipEventDestroy", "hipStreamCreateWithFlags", "hipStreamDestroy"):
+        assert re.search(rf"\b{word}\b", helpers), word
+
+
+def test_no_file_frees_or_uploads_through_a_bare_pointer():
+    # the free functions dfree(p) and upload(&p, ...) are gone: DevBuf frees and uploads what it owns
+    for name, text in _hip_sources().items():
+        if name != "eqlb_host_util.h":
+            for gone in (r"\bdfree\s*\(", r"(?<![\w.>])upload\s*(?:<[^>]*>\s*)?\(\s*&"):
+                assert not re.search(gone, text), f"{name}: {gone}"
+
+
+def test_the_mesh_view_holds_no_host_copies():
+    text = _strip_comments(_hip_sources()["eqlb_internal.h"])
+    body = re.search(r"\bstruct\s+DeviceMesh\s*\{(.*?)\n\};", text, flags=re.S)
+    assert body and "nnodes" in body.group(1)
+    assert "std::vector" not in body.group(1)
+    assert not re.search(r"\bstruct\s+eqlb_mesh\s*\{", text)  # (the owner lives in a host-only header)
+
+
+def test_node_cells_is_uploaded_in_one_place():
+    # the hand-written "upload on first use" test of the table, with any receiver
+    for name, text in _hip_sources().items():
+        assert not re.search(r"!\s*[\w.>-]*\bnode_cells\s*&&", text), name
 
 
 def test_the_replaced_stagings_stay_away():
