@@ -52,6 +52,9 @@ EXPORTED_SYMBOLS = [
     "eqlb_get_stiffness_table", "eqlb_get_load_table", "eqlb_primal_create", "eqlb_primal_destroy",
     "eqlb_primal_ndofs", "eqlb_primal_set_dirichlet", "eqlb_primal_load", "eqlb_primal_apply",
     "eqlb_primal_diagonal", "eqlb_primal_residual", "eqlb_primal_solve",
+    "eqlb_get_cross_table", "eqlb_elasticity_create", "eqlb_elasticity_destroy", "eqlb_elasticity_ndofs",
+    "eqlb_elasticity_set_dirichlet", "eqlb_elasticity_load", "eqlb_elasticity_apply", "eqlb_elasticity_diagonal",
+    "eqlb_elasticity_residual", "eqlb_elasticity_solve",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -182,7 +185,7 @@ def lib():
         for name in ("eqlb_mesh_destroy", "eqlb_se_destroy", "eqlb_ev_destroy", "eqlb_halo_destroy",
                      "eqlb_rccl_comm_destroy"):
             getattr(L, name).restype = None
-        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy"):
+        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy", "eqlb_elasticity_destroy"):
             if hasattr(L, name):   # (a library of an earlier revision, EQLB_AMD_LIB: A/B runs of bench.py)
                 getattr(L, name).restype = None
         _lib = L
@@ -1346,6 +1349,16 @@ def get_load_table(p: int, degree_dg: int):
     return out
 
 
+def get_cross_table(p: int):
+    """The built-in table Cross<p> [nd_p, nd_p] of PrimalElasticity (eqlb_get_cross_table), 1 <= p <= 4."""
+    nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2
+    out = np.zeros((nd, nd))
+    n = lib().eqlb_get_cross_table(C.c_int32(p), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
 PRIMAL_INFO = ("iterations", "converged", "nb", "rnorm", "replacements", "breakdown", "tol", "facets_skipped")
 
 
@@ -1464,6 +1477,138 @@ class PrimalPoisson:
     def close(self):
         if self._h:
             lib().eqlb_primal_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PrimalElasticity:
+    """eqlb_elasticity_t: -div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2 (1 <= p <= 4) with the pi_1 / cell_pi1 convention
+    of primal_stress_dg, in the scalar numbering of DeviceMesh.lagrange_dofmap, blocked: x[2 dof + r].  `ndofs` is the
+    scalar count; every vector has 2 ndofs rows.  The operator matrix-free, the load vector, the residual and a
+    Jacobi-preconditioned CG on the device (lsolver.primal.ElasticityOperator is the numpy statement).  cell_pi1: host
+    array [ncells] or None (the scalar everywhere).  Shaped as PrimalPoisson: the methods take and return host arrays;
+    the `_raw` variants take raw pointers (ints) in `memspace`, ordered on `stream`."""
+
+    def __init__(self, dmesh: DeviceMesh, p: int, pi_1: float = 1.0, cell_pi1=None, stream=0):
+        self.dmesh = dmesh   # the handle reads the mesh: keep it alive
+        self.p = int(p)
+        self._h = C.c_void_p()
+        kc = None
+        if cell_pi1 is not None:
+            kc = np.ascontiguousarray(cell_pi1, dtype=np.float64).ravel()
+            if kc.size != dmesh.counts()[1]:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        _check(lib().eqlb_elasticity_create(dmesh._h, C.c_int32(p), C.c_double(pi_1),
+                                            _hp(kc) if kc is not None else None, C.c_int32(MEM_HOST),
+                                            C.c_void_p(stream), C.byref(self._h)))
+        self._read_ndofs()
+
+    @classmethod
+    def create_raw(cls, dmesh: DeviceMesh, p: int, pi_1: float = 1.0, cell_pi1=None, memspace=MEM_DEVICE, stream=0):
+        """eqlb_elasticity_create with cell_pi1 [ncells] behind a raw pointer in `memspace` (None: the scalar)."""
+        self = cls.__new__(cls)
+        self.dmesh, self.p, self._h = dmesh, int(p), C.c_void_p()
+        _check(lib().eqlb_elasticity_create(dmesh._h, C.c_int32(p), C.c_double(pi_1), _vp(cell_pi1),
+                                            C.c_int32(memspace), C.c_void_p(stream), C.byref(self._h)))
+        self._read_ndofs()
+        return self
+
+    def _read_ndofs(self):
+        n = C.c_int64(0)
+        _check(lib().eqlb_elasticity_ndofs(self._h, C.byref(n)))
+        self.ndofs = int(n.value)
+
+    def _vec(self, a):
+        v = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if v.size != 2 * self.ndofs:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        return v
+
+    def set_dirichlet(self, facets0, facets1, stream=0):
+        """Fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r (the facets
+        with type 1 in row r of a stress handle); a repeated call replaces the mask."""
+        f0 = np.ascontiguousarray(facets0, dtype=np.int32).ravel()
+        f1 = np.ascontiguousarray(facets1, dtype=np.int32).ravel()
+        self.set_dirichlet_raw(f0.size, f0.ctypes.data if f0.size else None, f1.size,
+                               f1.ctypes.data if f1.size else None, MEM_HOST, stream)
+
+    def set_dirichlet_raw(self, nlist0, facets0, nlist1, facets1, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_elasticity_set_dirichlet(self._h, C.c_int32(nlist0), _vp(facets0), C.c_int32(nlist1),
+                                                   _vp(facets1), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def load(self, degree_dg, rhs_dg, b_extra=None, stream=0):
+        """b [2 ndofs] from the DG_d nodal values rhs_dg [2][ncells * nd_d] of the two components, + b_extra [2 ndofs]
+        where given (lsolver.traction_load)."""
+        d = max(int(degree_dg), 0)
+        f = np.ascontiguousarray(rhs_dg, dtype=np.float64).ravel()
+        if 0 <= degree_dg <= 3 and f.size != 2 * self.dmesh.counts()[1] * (d + 1) * (d + 2) // 2:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        e = None if b_extra is None else self._vec(b_extra)
+        b = np.zeros(2 * self.ndofs)
+        self.load_raw(degree_dg, f.ctypes.data, None if e is None else e.ctypes.data, b.ctypes.data, MEM_HOST, stream)
+        return b
+
+    def load_raw(self, degree_dg, rhs_dg, b_extra, b, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_elasticity_load(self._h, C.c_int32(degree_dg), _vp(rhs_dg), _vp(b_extra), _vp(b),
+                                          C.c_int32(memspace), C.c_void_p(stream)))
+
+    def apply(self, u, masked=False, stream=0):
+        """y = A u; masked: 0 on the fixed rows."""
+        uu, y = self._vec(u), np.zeros(2 * self.ndofs)
+        self.apply_raw(uu.ctypes.data, y.ctypes.data, masked, MEM_HOST, stream)
+        return y
+
+    def apply_raw(self, u, y, masked=False, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_elasticity_apply(self._h, _vp(u), _vp(y), C.c_int32(1 if masked else 0),
+                                           C.c_int32(memspace), C.c_void_p(stream)))
+
+    def diagonal(self, stream=0):
+        out = np.zeros(2 * self.ndofs)
+        self.diagonal_raw(out.ctypes.data, MEM_HOST, stream)
+        return out
+
+    def diagonal_raw(self, out, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_elasticity_diagonal(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def residual(self, b, u, norms=False, stream=0):
+        """r = b - A u with 0 on the fixed rows; norms=True: (r, || r ||_2, nb)."""
+        bb, uu, r = self._vec(b), self._vec(u), np.zeros(2 * self.ndofs)
+        nv = np.zeros(2)
+        self.residual_raw(bb.ctypes.data, uu.ctypes.data, r.ctypes.data, nv.ctypes.data if norms else None, MEM_HOST,
+                          stream)
+        return (r, float(nv[0]), float(nv[1])) if norms else r
+
+    def residual_raw(self, b, u, r, norms=None, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_elasticity_residual(self._h, _vp(b), _vp(u), _vp(r), _vp(norms), C.c_int32(memspace),
+                                              C.c_void_p(stream)))
+
+    def solve(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
+        """Jacobi-preconditioned CG from the start u (its fixed rows hold the Dirichlet values).  Returns (u, info):
+        the solution and a dict with the keys of PRIMAL_INFO.  Not converged is a result, not an error."""
+        bb = self._vec(b)
+        uu = self._vec(u).copy()
+        info = self.solve_raw(bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
+        return uu, info
+
+    def solve_raw(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
+        """eqlb_elasticity_solve on raw pointers: u is overwritten by the solution; waits for the device; returns
+        info."""
+        v = (C.c_double * 8)()
+        _check(lib().eqlb_elasticity_solve(self._h, _vp(b), _vp(u), C.c_double(rtol), C.c_double(atol),
+                                           C.c_int32(maxit), v, C.c_int32(memspace), C.c_void_p(stream)))
+        info = dict(zip(PRIMAL_INFO, [float(x) for x in v]))
+        for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
+            info[key] = int(info[key])
+        return info
+
+    def close(self):
+        if self._h:
+            lib().eqlb_elasticity_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -23,9 +23,10 @@
 // forms alpha, beta, rho and the stop flag IN DEVICE MEMORY (PcgState) for the next kernel.  Once the flag is set the
 // remaining kernels of a batch return at once, so the result does not depend on how often the host looks: it reads
 // the state every EQLB_PRIMAL_CHECK_EVERY iterations.  Nothing is allocated inside the iteration.
+// The sum pass, the CG kernels and the host loop lie in eqlb_primal_common.h, which eqlb_primal_elasticity.hip shares.
 #include "eqlb_device_common.h"
 #include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
-#include "eqlb_reduce.h"
+#include "eqlb_primal_common.h" // the sum pass, the kernels and the host loop of the CG: shared with the elasticity unit
 #include "eqlb_tables_gen.h"
 
 #include <climits>
@@ -35,26 +36,6 @@ namespace eqlb
 {
 namespace
 {
-constexpr int PS_THREADS = 256;
-constexpr int PS_MAXBLOCKS = 512; // blocks of a streaming kernel over the DOFs
-constexpr int PS_PMAX = 4, PS_DMAX = 3;
-constexpr int PRIMAL_CHECK_EVERY = EQLB_PRIMAL_CHECK_EVERY;
-static_assert(PRIMAL_CHECK_EVERY >= 1, "EQLB_PRIMAL_CHECK_EVERY");
-
-enum CellMode
-{
-  CELL_OPERATOR = 0,
-  CELL_DIAGONAL = 1,
-  CELL_LOAD = 2
-};
-
-// scalars of the iteration, in device memory
-struct PcgState
-{
-  double rho, pq, alpha, beta, rr, nb, tol, rtrue;
-  int32_t iters, done, breakdown, converged, replacements, pad;
-};
-
 struct CellArgs
 {
   int32_t ncells;
@@ -171,141 +152,6 @@ __global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a)
     o[e] = sbuf[(e / NP) * S + (e % NP)];
 }
 
-// the shapes of the space and the tables of the sum pass
-struct SpaceArgs
-{
-  int64_t ndofs;
-  int32_t nnodes, nfacets, ncells, ne, ni, nd;
-  const int32_t *nco, *fco; // offsets of node -> cell, facet -> cell
-  const int32_t* slots;     // [3 ncells (1 + ne)] flat indices c * nd + i into y_loc
-};
-
-__host__ __device__ inline int stream_blocks(int64_t n)
-{
-  const int64_t b = (n + PS_THREADS - 1) / PS_THREADS;
-  return (int)(b < PS_MAXBLOCKS ? (b < 1 ? 1 : b) : PS_MAXBLOCKS);
-}
-
-// first slot and number of slots of the vertex or facet DOF d < nnodes + nfacets * ne
-__device__ __forceinline__ void slot_range(const SpaceArgs& s, int64_t d, int64_t& beg, int& cnt)
-{
-  if (d < s.nnodes)
-  {
-    beg = s.nco[d];
-    cnt = s.nco[d + 1] - s.nco[d];
-  }
-  else
-  {
-    const int64_t q = d - s.nnodes, f = q / s.ne;
-    const int j = (int)(q - f * s.ne);
-    cnt = s.fco[f + 1] - s.fco[f];
-    beg = 3 * (int64_t)s.ncells + (int64_t)s.fco[f] * s.ne + (int64_t)j * cnt;
-  }
-}
-
-// one thread per vertex / facet DOF: its slots in the order of the node -> cell / facet -> cell table; the local index
-// comes from matching ids.  A cell that does not hold the DOF (a broken table) gets its entry 0 and is counted
-__global__ void __launch_bounds__(PS_THREADS)
-k_primal_slots(const SpaceArgs s, const int32_t* __restrict__ node_cells, const int32_t* __restrict__ facet_cells,
-               const int32_t* __restrict__ cell_dofs, int32_t* __restrict__ slots, int32_t* __restrict__ status)
-{
-  const int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  const int64_t nshared = (int64_t)s.nnodes + (int64_t)s.nfacets * s.ne;
-  if (d >= nshared)
-    return;
-  int64_t beg;
-  int cnt;
-  slot_range(s, d, beg, cnt);
-  const int32_t* cells = d < s.nnodes ? node_cells + s.nco[d] : facet_cells + s.fco[(d - s.nnodes) / s.ne];
-  for (int k = 0; k < cnt; ++k)
-  {
-    const int64_t c = cells[k];
-    int loc = -1;
-    for (int i = 0; i < s.nd; ++i)
-      loc = (cell_dofs[c * s.nd + i] == (int32_t)d) ? i : loc;
-    if (loc < 0)
-    {
-      atomicAdd(status + 2, 1);
-      loc = 0;
-    }
-    slots[beg + k] = (int32_t)(c * s.nd + loc);
-  }
-}
-
-enum GatherDot
-{
-  DOT_NONE = 0,
-  DOT_W_Y = 1, // sum_d w[d] y[d]
-  DOT_R_R = 2  // sum_d r[d]^2
-};
-
-struct GatherArgs
-{
-  SpaceArgs s;
-  const double* yloc;
-  const uint8_t* fixed; // nullptr: the raw operator
-  const double* add;    // nullptr or b_extra
-  const double* b;      // with r: r = b - sum (0 on fixed rows)
-  const double* w;      // DOT_W_Y
-  double *y, *r;        // each nullptr or [ndofs]
-  double* part;         // [gridDim.x] block partials of the inner product
-  int32_t dot;
-  const PcgState* st;
-};
-
-__global__ void __launch_bounds__(PS_THREADS) k_primal_gather(const GatherArgs a)
-{
-#pragma clang fp contract(off)
-  __shared__ double sh[1][PS_THREADS];
-  if (a.st && a.st->done)
-    return;
-  const SpaceArgs& s = a.s;
-  const int t = threadIdx.x;
-  const int64_t nshared = (int64_t)s.nnodes + (int64_t)s.nfacets * s.ne;
-  double acc = 0.0;
-  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < s.ndofs; d += (int64_t)gridDim.x * PS_THREADS)
-  {
-    double v;
-    if (d < nshared)
-    {
-      int64_t beg;
-      int cnt;
-      slot_range(s, d, beg, cnt);
-      v = cnt > 0 ? a.yloc[s.slots[beg]] : 0.0;
-      for (int k = 1; k < cnt; ++k)
-        v = v + a.yloc[s.slots[beg + k]];
-    }
-    else
-    {
-      const int64_t q = d - nshared, c = q / s.ni;
-      v = a.yloc[c * s.nd + 3 + 3 * s.ne + (q - c * s.ni)];
-    }
-    if (a.add)
-      v = v + a.add[d];
-    const bool fx = a.fixed && a.fixed[d];
-    const double yv = fx ? 0.0 : v;
-    if (a.y)
-      a.y[d] = yv;
-    double rv = 0.0;
-    if (a.r)
-    {
-      rv = fx ? 0.0 : a.b[d] - v;
-      a.r[d] = rv;
-    }
-    if (a.dot == DOT_W_Y)
-      acc = acc + a.w[d] * yv;
-    else if (a.dot == DOT_R_R)
-      acc = acc + rv * rv;
-  }
-  if (a.dot == DOT_NONE)
-    return;
-  sh[0][t] = acc;
-  __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 1, PS_THREADS)
-  if (t == 0)
-    a.part[blockIdx.x] = sh[0][0];
-}
-
 // the mask of the listed facets; ids outside the mesh are skipped and counted (status[0]), valid ones counted (status[1])
 __global__ void __launch_bounds__(PS_THREADS)
 k_primal_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t nnodes, int32_t nfacets, int32_t ne,
@@ -327,168 +173,6 @@ k_primal_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t nnodes,
     fixed[(int64_t)nnodes + (int64_t)f * ne + j] = 1;
 }
 
-// ---- vector kernels of the iteration (grid-stride, block partials in a fixed order) -------------------------------
-// z = r / diag on the free rows (0 on the fixed ones); partials of r.r and r.z: part[0][block], part[1][block]
-__global__ void __launch_bounds__(PS_THREADS)
-k_pcg_precond(int64_t n, const double* __restrict__ r, const double* __restrict__ diag,
-              const uint8_t* __restrict__ fixed, double* __restrict__ z, double* __restrict__ part)
-{
-#pragma clang fp contract(off)
-  __shared__ double sh[2][PS_THREADS];
-  const int t = threadIdx.x, G = gridDim.x;
-  double a0 = 0.0, a1 = 0.0;
-  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)G * PS_THREADS)
-  {
-    const double rv = r[d], zv = fixed[d] ? 0.0 : rv / diag[d];
-    z[d] = zv;
-    a0 = a0 + rv * rv;
-    a1 = a1 + rv * zv;
-  }
-  sh[0][t] = a0;
-  sh[1][t] = a1;
-  __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 2, PS_THREADS)
-  if (t < 2)
-    part[(int64_t)t * G + blockIdx.x] = sh[t][0];
-}
-
-// u += alpha p, r -= alpha q, z = r / diag on the free rows; the fixed rows are not touched; partials as k_pcg_precond
-__global__ void __launch_bounds__(PS_THREADS)
-k_pcg_update(int64_t n, const PcgState* __restrict__ st, const double* __restrict__ p, const double* __restrict__ q,
-             const double* __restrict__ diag, const uint8_t* __restrict__ fixed, double* __restrict__ u,
-             double* __restrict__ r, double* __restrict__ z, double* __restrict__ part)
-{
-#pragma clang fp contract(off)
-  __shared__ double sh[2][PS_THREADS];
-  if (st->done)
-    return;
-  const int t = threadIdx.x, G = gridDim.x;
-  const double alpha = st->alpha;
-  double a0 = 0.0, a1 = 0.0;
-  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)G * PS_THREADS)
-  {
-    if (fixed[d])
-      continue; // (r and z are 0 there since the start)
-    u[d] = u[d] + alpha * p[d];
-    const double rv = r[d] - alpha * q[d], zv = rv / diag[d];
-    r[d] = rv;
-    z[d] = zv;
-    a0 = a0 + rv * rv;
-    a1 = a1 + rv * zv;
-  }
-  sh[0][t] = a0;
-  sh[1][t] = a1;
-  __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 2, PS_THREADS)
-  if (t < 2)
-    part[(int64_t)t * G + blockIdx.x] = sh[t][0];
-}
-
-// p = z + beta p (first: p = z)
-__global__ void __launch_bounds__(PS_THREADS)
-k_pcg_direction(int64_t n, const PcgState* __restrict__ st, int first, const double* __restrict__ z,
-                double* __restrict__ p)
-{
-#pragma clang fp contract(off)
-  if (st->done)
-    return;
-  const double beta = first ? 0.0 : st->beta;
-  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
-    p[d] = first ? z[d] : z[d] + beta * p[d];
-}
-
-// u = u^: the free rows set to 0 (nothing to solve)
-__global__ void __launch_bounds__(PS_THREADS)
-k_pcg_clear_free(int64_t n, const uint8_t* __restrict__ fixed, double* __restrict__ u)
-{
-  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
-    if (!fixed[d])
-      u[d] = 0.0;
-}
-
-enum ScalarStep
-{
-  STEP_NORM = 0,    // out[0] = sqrt(channel 0)
-  STEP_NB = 1,      // nb = sqrt(channel 0), tol = max(rtol nb, atol)
-  STEP_START = 2,   // rr, rho from the start residual; done if it is within tol already
-  STEP_ALPHA = 3,   // pq = channel 0: breakdown unless > 0, else alpha = rho / pq
-  STEP_BETA = 4,    // rr, rho_new: one more iteration done; done if sqrt(rr) <= tol, else beta, rho
-  STEP_TRUE = 5,    // rtrue = sqrt(channel 0); converged if <= tol
-  STEP_REPLACE = 6  // after the true residual replaced r: beta = rho_new / rho, rho = rho_new, the iteration goes on
-};
-
-// one block: the channels' totals over the G block partials by the same tree, then thread 0 moves the state
-__global__ void __launch_bounds__(PS_THREADS)
-k_pcg_scalar(int step, int G, const double* __restrict__ part, PcgState* __restrict__ st, double rtol, double atol,
-             double* __restrict__ out)
-{
-  __shared__ double sh[2][PS_THREADS];
-  const int t = threadIdx.x;
-  const bool two = step == STEP_START || step == STEP_BETA || step == STEP_REPLACE;
-  if (st && st->done && step != STEP_TRUE && step != STEP_NORM && step != STEP_REPLACE)
-    return;
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-  {
-    double a = 0.0;
-    if (j == 0 || two)
-      for (int b = t; b < G; b += PS_THREADS)
-        a += part[(int64_t)j * G + b];
-    sh[j][t] = a;
-  }
-  __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 2, PS_THREADS)
-  if (t != 0)
-    return;
-  const double s0 = sh[0][0], s1 = sh[1][0];
-  switch (step)
-  {
-  case STEP_NORM:
-    out[0] = sqrt(s0);
-    break;
-  case STEP_NB:
-    st->nb = sqrt(s0);
-    st->tol = fmax(rtol * st->nb, atol);
-    break;
-  case STEP_START:
-    st->rr = s0;
-    st->rho = s1;
-    if (sqrt(s0) <= st->tol)
-      st->done = 1;
-    break;
-  case STEP_ALPHA:
-    st->pq = s0;
-    if (!(s0 > 0.0))
-    {
-      st->breakdown = 1;
-      st->done = 1;
-    }
-    else
-      st->alpha = st->rho / s0;
-    break;
-  case STEP_BETA:
-    st->rr = s0;
-    st->iters += 1;
-    if (sqrt(s0) <= st->tol)
-      st->done = 1; // (rho stays that of the last direction: STEP_REPLACE needs it if the true residual is above tol)
-    else
-    {
-      st->beta = s1 / st->rho;
-      st->rho = s1;
-    }
-    break;
-  case STEP_TRUE:
-    st->rtrue = sqrt(s0);
-    st->converged = (st->rtrue <= st->tol) ? 1 : 0;
-    break;
-  default: // STEP_REPLACE
-    st->rr = s0;
-    st->beta = s1 / st->rho;
-    st->rho = s1;
-    st->replacements += 1;
-    st->done = 0;
-  }
-}
 
 // ---- host side ------------------------------------------------------------------------------------------------
 template <int P, int MODE>
@@ -580,15 +264,13 @@ GatherArgs gather_args(const eqlb_primal& h, bool masked, const PcgState* st)
 
 hipError_t launch_gather(const eqlb_primal& h, const GatherArgs& g, hipStream_t stream)
 {
-  hipLaunchKernelGGL(k_primal_gather, dim3(stream_blocks(h.ndofs)), dim3(PS_THREADS), 0, stream, g);
+  hipLaunchKernelGGL(k_primal_gather<1>, dim3(stream_blocks(h.ndofs)), dim3(PS_THREADS), 0, stream, g);
   return hipGetLastError();
 }
 
-hipError_t launch_scalar(const eqlb_primal& h, int step, double rtol, double atol, double* out, hipStream_t stream)
+PcgWork pcg_work(const eqlb_primal& h)
 {
-  hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(PS_THREADS), 0, stream, step, stream_blocks(h.ndofs), h.part.get(),
-                     h.st.get(), rtol, atol, out);
-  return hipGetLastError();
+  return PcgWork{h.ndofs, h.diag, h.fixed, h.r, h.z, h.d, h.q, h.part, h.st};
 }
 
 // y = A u (masked or raw); all pointers DEVICE
@@ -901,11 +583,11 @@ try
   {
     // the reference norm first, into the work vector q: the residual proper then leaves r as the caller sees it
     s.note(enqueue_residual(*h, pb, pu, h->q, true, stream));
-    s.note(launch_scalar(*h, STEP_NORM, 0.0, 0.0, pn + 1, stream));
+    s.note(launch_scalar(pcg_work(*h), STEP_NORM, 0.0, 0.0, pn + 1, stream));
   }
   s.note(enqueue_residual(*h, pb, pu, host ? d_r.get() : r, false, stream));
   if (pn)
-    s.note(launch_scalar(*h, STEP_NORM, 0.0, 0.0, pn, stream));
+    s.note(launch_scalar(pcg_work(*h), STEP_NORM, 0.0, 0.0, pn, stream));
   HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }
@@ -932,112 +614,21 @@ try
   HIP_TRY(hipStreamSynchronize(stream));
   if (status[1] < 1)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)h->ndofs;
-  HostCall s;
-  const auto d_b = s.in(host ? b : nullptr, n);
-  const auto d_u = s.in(host ? static_cast<const double*>(u) : nullptr, n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  const double* pb = host ? d_b.get() : b;
-  double* pu = host ? d_u.get() : u;
-  PcgState* st = h->st;
-  const int G = stream_blocks(h->ndofs);
-  const dim3 grid(G), block(PS_THREADS);
-  const int64_t nn = h->ndofs;
-  PcgState hs{};
-  auto read_state = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(&hs, st, sizeof(PcgState), hipMemcpyDeviceToHost, stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(stream);
+  auto residual = [&](const double* pb, const double* pu, double* r, bool only_fixed) {
+    return enqueue_residual(*h, pb, pu, r, only_fixed, stream);
   };
-  // the true residual of the current u into q, its norm into the state
-  auto true_residual = [&]() {
-    s.note(enqueue_residual(*h, pb, pu, h->q, false, stream));
-    s.note(launch_scalar(*h, STEP_TRUE, rtol, atol, nullptr, stream));
+  auto product = [&](const PcgState* st) {
+    const hipError_t e = launch_cell<CELL_OPERATOR>(h->p, 0, cell_args(*h, h->d, false, st), stream);
+    if (e != hipSuccess)
+      return e;
+    GatherArgs g = gather_args(*h, true, st);
+    g.y = h->q;
+    g.w = h->d;
+    g.dot = DOT_W_Y;
+    return launch_gather(*h, g, stream);
   };
-  s.note(hipMemsetAsync(st, 0, sizeof(PcgState), stream));
-  // nb and tol from u^
-  s.note(enqueue_residual(*h, pb, pu, h->q, true, stream));
-  s.note(launch_scalar(*h, STEP_NB, rtol, atol, nullptr, stream));
-  // the start: r = b - A u, z = r / diag, rho, p = z
-  s.note(enqueue_residual(*h, pb, pu, h->r, false, stream));
-  hipLaunchKernelGGL(k_pcg_precond, grid, block, 0, stream, nn, h->r.get(), h->diag.get(), h->fixed.get(), h->z.get(),
-                     h->part.get());
-  s.note(launch_scalar(*h, STEP_START, rtol, atol, nullptr, stream));
-  hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 1, h->z.get(), h->d.get());
-  s.note(hipGetLastError());
-  s.note(read_state());
-  bool have_true = false; // q holds the true residual of the current u and the state its norm
-  if (s.finish(stream) == hipSuccess && hs.tol == 0.0 && hs.nb == 0.0)
-  {
-    // nothing to solve: u^ is the solution (the free rows of u are set to 0 by the start residual's mask)
-    hipLaunchKernelGGL(k_pcg_clear_free, grid, block, 0, stream, nn, h->fixed.get(), pu);
-    s.note(hipGetLastError());
-    hs.converged = 1;
-    hs.rtrue = 0.0;
-    have_true = true;
-  }
-  else
-  {
-    while (s.finish(stream) == hipSuccess && !hs.breakdown && !hs.converged)
-    {
-      if (hs.done)
-      {
-        // the recurrence residual reached tol: the true one decides
-        true_residual();
-        s.note(read_state());
-        have_true = true;
-        if (hs.converged || hs.iters >= maxit)
-          break;
-        s.note(hipMemcpyAsync(h->r.get(), h->q.get(), n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(k_pcg_precond, grid, block, 0, stream, nn, h->r.get(), h->diag.get(), h->fixed.get(),
-                           h->z.get(), h->part.get());
-        s.note(launch_scalar(*h, STEP_REPLACE, rtol, atol, nullptr, stream));
-        hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 0, h->z.get(), h->d.get());
-        s.note(hipGetLastError());
-        have_true = false;
-      }
-      if (hs.iters >= maxit)
-        break;
-      const int batch = (maxit - hs.iters < PRIMAL_CHECK_EVERY) ? maxit - hs.iters : PRIMAL_CHECK_EVERY;
-      for (int it = 0; it < batch; ++it)
-      {
-        s.note(launch_cell<CELL_OPERATOR>(h->p, 0, cell_args(*h, h->d, false, st), stream));
-        GatherArgs g = gather_args(*h, true, st);
-        g.y = h->q;
-        g.w = h->d;
-        g.dot = DOT_W_Y;
-        s.note(launch_gather(*h, g, stream));
-        s.note(launch_scalar(*h, STEP_ALPHA, rtol, atol, nullptr, stream));
-        hipLaunchKernelGGL(k_pcg_update, grid, block, 0, stream, nn, st, h->d.get(), h->q.get(), h->diag.get(),
-                           h->fixed.get(), pu, h->r.get(), h->z.get(), h->part.get());
-        s.note(launch_scalar(*h, STEP_BETA, rtol, atol, nullptr, stream));
-        hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 0, h->z.get(), h->d.get());
-        s.note(hipGetLastError());
-      }
-      have_true = false;
-      s.note(read_state());
-    }
-  }
-  if (!have_true)
-  {
-    true_residual();
-    const int conv = hs.converged;
-    s.note(read_state());
-    hs.converged = conv; // (a run that ended at maxit or broke down is not converged, whatever its last residual)
-  }
-  if (host)
-    s.out_prefix(u, d_u, n);
-  HIP_TRY(s.finish(stream));
-  info[0] = (double)hs.iters;
-  info[1] = (double)hs.converged;
-  info[2] = hs.nb;
-  info[3] = hs.rtrue;
-  info[4] = (double)hs.replacements;
-  info[5] = (double)hs.breakdown;
-  info[6] = hs.tol;
-  info[7] = (double)status[0];
-  return EQLB_OK;
+  return pcg_solve(pcg_work(*h), residual, product, b, u, rtol, atol, maxit, info, status[0],
+                   memspace == EQLB_MEM_HOST, stream);
 }
 EQLB_CATCH_ALL
 

@@ -373,6 +373,104 @@ struct PrimalPoisson
   }
 };
 
+// -div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2 in the scalar numbering of Mesh.lagrange_dofmap, blocked x[2 dof + r]:
+// the counterpart of PrimalPoisson (eqlb_elasticity_*), on host arrays; ndofs is the scalar count, vectors have 2 ndofs
+struct PrimalElasticity
+{
+  eqlb_elasticity_t* h = nullptr;
+  std::shared_ptr<Mesh> mesh; // the handle reads the mesh: it stays alive with the carrier
+  int p = 0;
+  int64_t ndofs = 0;
+
+  PrimalElasticity(std::shared_ptr<Mesh> mesh_, int p_, double pi_1, py::object cell_pi1) : mesh(mesh_), p(p_)
+  {
+    carray<double> kc;
+    if (!cell_pi1.is_none())
+    {
+      kc = cell_pi1.cast<carray<double>>();
+      if (kc.size() != mesh->ncells)
+        throw std::runtime_error("PrimalElasticity: cell_pi1 [ncells] expected");
+    }
+    check(eqlb_elasticity_create(mesh->h, p, pi_1, cell_pi1.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr,
+                                 &h));
+    check(eqlb_elasticity_ndofs(h, &ndofs));
+  }
+  ~PrimalElasticity() { eqlb_elasticity_destroy(h); }
+  PrimalElasticity(const PrimalElasticity&) = delete;
+  PrimalElasticity& operator=(const PrimalElasticity&) = delete;
+
+  void need(const darray& v, const char* who) const
+  {
+    if (v.size() != 2 * ndofs)
+      throw std::runtime_error(std::string("PrimalElasticity.") + who + ": Input sizes does not match");
+  }
+  void set_dirichlet(carray<int32_t> facets0, carray<int32_t> facets1)
+  {
+    check(eqlb_elasticity_set_dirichlet(h, (int32_t)facets0.size(), facets0.size() ? facets0.data() : nullptr,
+                                        (int32_t)facets1.size(), facets1.size() ? facets1.data() : nullptr,
+                                        EQLB_MEM_HOST, nullptr));
+  }
+  darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
+  {
+    if (degree_dg >= 0 && degree_dg <= 3
+        && rhs_dg.size() != 2 * (py::ssize_t)mesh->ncells * ((degree_dg + 1) * (degree_dg + 2) / 2))
+      throw std::runtime_error("PrimalElasticity.load: Input sizes does not match");
+    darray e;
+    if (!b_extra.is_none())
+    {
+      e = b_extra.cast<darray>();
+      need(e, "load");
+    }
+    darray b((py::ssize_t)(2 * ndofs));
+    check(eqlb_elasticity_load(h, degree_dg, rhs_dg.data(), b_extra.is_none() ? nullptr : e.data(), b.mutable_data(),
+                               EQLB_MEM_HOST, nullptr));
+    return b;
+  }
+  darray apply(darray u, bool masked) const
+  {
+    need(u, "apply");
+    darray y((py::ssize_t)(2 * ndofs));
+    check(eqlb_elasticity_apply(h, u.data(), y.mutable_data(), masked ? 1 : 0, EQLB_MEM_HOST, nullptr));
+    return y;
+  }
+  darray diagonal() const
+  {
+    darray out((py::ssize_t)(2 * ndofs));
+    check(eqlb_elasticity_diagonal(h, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
+  // (r, || r ||_2, nb)
+  py::tuple residual(darray b, darray u) const
+  {
+    need(b, "residual");
+    need(u, "residual");
+    darray r((py::ssize_t)(2 * ndofs));
+    double norms[2] = {0.0, 0.0};
+    check(eqlb_elasticity_residual(h, b.data(), u.data(), r.mutable_data(), norms, EQLB_MEM_HOST, nullptr));
+    return py::make_tuple(r, norms[0], norms[1]);
+  }
+  // (u, info): the solution from the start u (its fixed rows hold the Dirichlet values) and the info dict
+  py::tuple solve(darray b, darray u, double rtol, double atol, int maxit) const
+  {
+    need(b, "solve");
+    need(u, "solve");
+    darray x((py::ssize_t)(2 * ndofs));
+    std::copy(u.data(), u.data() + 2 * ndofs, x.mutable_data());
+    double v[8] = {};
+    check(eqlb_elasticity_solve(h, b.data(), x.mutable_data(), rtol, atol, maxit, v, EQLB_MEM_HOST, nullptr));
+    py::dict info;
+    info["iterations"] = (int64_t)v[0];
+    info["converged"] = (int64_t)v[1];
+    info["nb"] = v[2];
+    info["rnorm"] = v[3];
+    info["replacements"] = (int64_t)v[4];
+    info["breakdown"] = (int64_t)v[5];
+    info["tol"] = v[6];
+    info["facets_skipped"] = (int64_t)v[7];
+    return py::make_tuple(x, info);
+  }
+};
+
 py::tuple Mesh::refine(std::shared_ptr<Mesh> self, carray<int32_t> marked, bool keep_plan)
 {
   std::shared_ptr<Transfer> tr(new Transfer());
@@ -1217,6 +1315,28 @@ PYBIND11_MODULE(_cpp, m)
       .def_readonly("mesh", &PrimalPoisson::mesh)
       .def_readonly("p", &PrimalPoisson::p)
       .def_readonly("ndofs", &PrimalPoisson::ndofs);
+
+  py::class_<PrimalElasticity, std::shared_ptr<PrimalElasticity>>(
+      m, "PrimalElasticity", "-div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2 of the mesh (scalar numbering of "
+                             "Mesh.lagrange_dofmap, blocked x[2 dof + r]): matrix-free operator, load, residual and "
+                             "Jacobi-preconditioned CG on the device")
+      .def(py::init<std::shared_ptr<Mesh>, int, double, py::object>(), py::arg("mesh"), py::arg("p"),
+           py::arg("pi_1") = 1.0, py::arg("cell_pi1") = py::none())
+      .def("set_dirichlet", &PrimalElasticity::set_dirichlet, py::arg("facets0"), py::arg("facets1"),
+           "fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r; a repeated "
+           "call replaces the mask")
+      .def("load", &PrimalElasticity::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
+           "b [2 ndofs] from DG_d nodal values rhs_dg [2, ncells*nd_d], + b_extra where given")
+      .def("apply", &PrimalElasticity::apply, py::arg("u"), py::arg("masked") = false,
+           "y = A u; masked: 0 on the fixed rows")
+      .def("diagonal", &PrimalElasticity::diagonal)
+      .def("residual", &PrimalElasticity::residual, py::arg("b"), py::arg("u"),
+           "(r, || r ||_2, nb): r = b - A u with 0 on the fixed rows")
+      .def("solve", &PrimalElasticity::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
+           py::arg("maxit") = 10000, "(u, info): PCG from the start u, whose fixed rows hold the Dirichlet values")
+      .def_readonly("mesh", &PrimalElasticity::mesh)
+      .def_readonly("p", &PrimalElasticity::p)
+      .def_readonly("ndofs", &PrimalElasticity::ndofs);
 
   py::class_<FunctionSpace, std::shared_ptr<FunctionSpace>>(m, "FunctionSpace")
       .def(py::init<std::shared_ptr<Mesh>, std::string, int, int, bool>(), py::arg("mesh"), py::arg("family"),

@@ -1,8 +1,9 @@
-"""Cell-local solvers: mirror of python/dolfinx_eqlb/lsolver (projection.py, lsolver.py); primal.py: the statement of
-the P_p Poisson solve on the device (cpp.PrimalPoisson)."""
+"""Cell-local solvers: mirror of python/dolfinx_eqlb/lsolver (projection.py, lsolver.py); primal.py: the statements of
+the P_p Poisson solve and the P_p^2 elasticity solve on the device (cpp.PrimalPoisson, cpp.PrimalElasticity)."""
 
-from .primal import PoissonOperator, load_table, neumann_load, stiffness_table
+from .primal import (ElasticityOperator, PoissonOperator, cross_table, load_table, neumann_load, stiffness_table,
+                     traction_load)
 from .projection import PrimalFlux, PrimalStress, embed_dg, local_projection
 
 __all__ = ["local_projection", "embed_dg", "PrimalFlux", "PrimalStress", "PoissonOperator", "neumann_load",
-           "stiffness_table", "load_table"]
+           "stiffness_table", "load_table", "ElasticityOperator", "traction_load", "cross_table"]

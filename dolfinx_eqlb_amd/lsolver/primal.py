@@ -28,6 +28,24 @@ comparison with an independently rounded computation by terms * 2^-53 * abs-sum.
 
 pcg() states the Jacobi-preconditioned CG of eqlb_primal_solve with np.sum for the inner products: the reference for
 iteration counts and for the host tests (the device reduces in another order, so its iterates differ in the last bits).
+
+ElasticityOperator states the same for -div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2 (eqlb_elasticity_* of
+include/eqlb.h, csrc/eqlb_primal_elasticity.hip), the primal solve of demo/elasticity_adaptive/demo_cook.py, in the
+non-dimensional form and with the pi_1 / cell_pi1 convention of eqlb_primal_stress_dg:
+
+  layout    the scalar numbering of lagrange_dofmap, blocked: u[2 dof + r]
+  tables    S0, S2 of Stiff<p> and Cross<p> [nd_p][nd_p] = int dX phi_i dY phi_j: M_00 = S0, M_01 = Cross,
+            M_10 = Cross^T, M_11 = S2 (S1 == Cross + Cross^T exactly)
+  geometry  K as above, K[X][d]; Q[a][b][X][Y] = K[X][a] K[Y][b]
+  cell      g_XY^s[i] = sum_j M_XY[i][j] u_s[j], u_s[j] = u[2 dof(c, j) + s], ascending j, products rounded one by one;
+            D_ab^s[i] = (Q[a][b][0][0] g_00^s[i] + Q[a][b][0][1] g_01^s[i])
+                      + (Q[a][b][1][0] g_10^s[i] + Q[a][b][1][1] g_11^s[i])          ( = int d_a phi_i d_b u_s )
+            y_loc[c][i][0] = |det| (((D_00^0 + D_11^0) + (D_00^0 + D_10^1)) + pi_c (D_00^0 + D_01^1))
+            y_loc[c][i][1] = |det| (((D_00^1 + D_11^1) + (D_01^0 + D_11^1)) + pi_c (D_10^0 + D_11^1))
+            that is |det| ((D_00^r + D_11^r) + sum_s D_sr^s + pi_c sum_s D_rs^s); no fused multiply-add
+  owner sum as above, per (dof, r)
+  load      per cell and component |det| (sum_n Load[i][n] rhs_dg[r][c][n]) through the owner sum, + b_extra[2 d + r]
+  diagonal  g_XY = M_XY[i][i], D_ab as above, |det| (((D_00 + D_11) + D_rr) + pi_c D_rr) through the owner sum
 """
 
 from fractions import Fraction
@@ -62,6 +80,22 @@ def load_table_exact(p, d):
         raise ValueError(f"load_table: p = {p}, d = {d} outside 1 ... 4, 0 ... 3")
     phi, chi = Lagrange(p).basis, Lagrange(d).basis
     return tuple(tuple(P.integrate_triangle(P.mul(a, b)) for b in chi) for a in phi)
+
+
+@lru_cache(maxsize=None)
+def cross_table_exact(p):
+    """Cross [nd_p][nd_p] Fractions: int dX phi_i dY phi_j on the reference triangle.  S1 == Cross + Cross^T exactly."""
+    if p < 1 or p > 4:
+        raise ValueError(f"cross_table: p = {p} outside 1 ... 4")
+    basis = Lagrange(p).basis
+    dx, dy = [P.ddx(b) for b in basis], [P.ddy(b) for b in basis]
+    n = len(basis)
+    return tuple(tuple(P.integrate_triangle(P.mul(dx[i], dy[j])) for j in range(n)) for i in range(n))
+
+
+def cross_table(p):
+    """The table [nd_p, nd_p] as doubles, each entry rounded once."""
+    return np.array([[float(v) for v in row] for row in cross_table_exact(p)])
 
 
 def stiffness_table(p):
@@ -337,3 +371,128 @@ class PoissonOperator:
         rt = self.residual(b, u)
         info["rnorm"] = float(np.sqrt(np.sum(rt * rt)))
         return u, info
+
+
+def traction_load(mesh, p, bcs_rows, quadrature_degree=None):
+    """b_extra [2 ndofs], blocked, of an elasticity problem with prescribed tractions: bcs_rows = (bcs_0, bcs_1), the
+    lists of `fluxbc` objects of the two stress rows; b_extra[2 d + r] = neumann_load(mesh, p, bcs_r)[d].  Row r of a
+    stress handle equilibrates -sigma_r, so its flux boundary condition prescribes -sigma_r . n = -t_r, and
+    neumann_load returns -int_E g phi_i: with g = -t_r that is +int_E t_r phi_i, the traction term of the weak form - the
+    sign is already the one neumann_load uses, and the same objects serve the equilibrator and this load."""
+    if len(bcs_rows) != 2:
+        raise ValueError("traction_load: two lists of boundary conditions expected, one per stress row")
+    rows = [neumann_load(mesh, p, bcs, quadrature_degree) for bcs in bcs_rows]
+    return np.ascontiguousarray(np.stack(rows, axis=1).ravel())
+
+
+class ElasticityOperator(PoissonOperator):
+    """The statements of -div(2 eps(u) + pi_1 div(u) I) = f on one mesh: ElasticityOperator(mesh, p, pi_1=1.0,
+    cell_pi1=None), cell_pi1 [ncells] the cell-wise pi_1 (else the scalar).  Vectors are blocked, [2 ndofs]; `ndofs`
+    is the scalar count.  owner_sum, residual, reference_norm and pcg are those of PoissonOperator on the blocked
+    vectors."""
+
+    def __init__(self, mesh, p, pi_1=1.0, cell_pi1=None):
+        if p < 1 or p > 4:
+            raise ValueError(f"ElasticityOperator: p = {p} outside 1 ... 4")
+        self.mesh, self.p, self.nd = mesh, p, nd_of(p)
+        cd, self.ndofs = lagrange_dofmap(mesh, p)
+        self.cell_dofs = cd.astype(np.int64)
+        x, cn = mesh.x, mesh.cell_nodes
+        J00, J01 = x[cn[:, 1], 0] - x[cn[:, 0], 0], x[cn[:, 2], 0] - x[cn[:, 0], 0]
+        J10, J11 = x[cn[:, 1], 1] - x[cn[:, 0], 1], x[cn[:, 2], 1] - x[cn[:, 0], 1]
+        det = J00 * J11 - J01 * J10
+        idet = 1.0 / det
+        K = ((J11 * idet, -J01 * idet), (-J10 * idet, J00 * idet))             # K[X][d]
+        self.Q = [[[K[X][a] * K[Y][b] for X in range(2) for Y in range(2)] for b in range(2)] for a in range(2)]
+        self.adet = np.abs(det)
+        if cell_pi1 is None:
+            self.pi = np.full(mesh.ncells, float(pi_1))
+        else:
+            self.pi = np.asarray(cell_pi1, dtype=np.float64).ravel()
+            if self.pi.size != mesh.ncells:
+                raise ValueError("ElasticityOperator: cell_pi1 [ncells] expected")
+        S = stiffness_table(p)
+        C = cross_table(p)
+        self.M = (S[0], C, np.ascontiguousarray(C.T), S[2])                     # M_00, M_01, M_10, M_11
+        self.fixed = np.zeros(2 * self.ndofs, dtype=bool)
+        self._slots()
+
+    def set_dirichlet(self, facets_row0, facets_row1):
+        """Fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r (the facets
+        with ft[r] == 1 of a stress handle's facet types).  A repeated call replaces the mask."""
+        m = [dirichlet_mask(self.mesh, self.p, f) for f in (facets_row0, facets_row1)]
+        self.fixed = np.ascontiguousarray(np.stack(m, axis=1).ravel())
+
+    # ---- the statements ----
+    def _D(self, g, a, b, A=None):
+        """(Q0 g0 + Q1 g1) + (Q2 g2 + Q3 g3) on [ncells, nd]; with A the same with absolute values."""
+        q = [v[:, None] for v in self.Q[a][b]]
+        val = (q[0] * g[0] + q[1] * g[1]) + (q[2] * g[2] + q[3] * g[3])
+        if A is None:
+            return val
+        q = [np.abs(v) for v in q]
+        return val, (q[0] * A[0] + q[1] * A[1]) + (q[2] * A[2] + q[3] * A[3])
+
+    def cell_product(self, u, return_abs=False):
+        """y_loc [ncells, nd, 2]."""
+        uc = np.asarray(u, dtype=np.float64).reshape(self.ndofs, 2)[self.cell_dofs]    # [c, j, s]
+        D = [[[None, None], [None, None]] for _ in range(2)]                             # D[s][a][b] = (val, abs)
+        for s in range(2):
+            g, A = zip(*[_sum_products(self.M[m], uc[:, :, s]) for m in range(4)])
+            for a in range(2):
+                for b in range(2):
+                    D[s][a][b] = self._D(g, a, b, A)
+        w, pi = self.adet[:, None], self.pi[:, None]
+        wa, pa = np.abs(w), np.abs(pi)
+        v = lambda s, a, b: D[s][a][b][0]   # noqa: E731
+        n = lambda s, a, b: D[s][a][b][1]   # noqa: E731
+        y0 = w * (((v(0, 0, 0) + v(0, 1, 1)) + (v(0, 0, 0) + v(1, 1, 0))) + pi * (v(0, 0, 0) + v(1, 0, 1)))
+        y1 = w * (((v(1, 0, 0) + v(1, 1, 1)) + (v(0, 0, 1) + v(1, 1, 1))) + pi * (v(0, 1, 0) + v(1, 1, 1)))
+        val = np.stack([y0, y1], axis=2)
+        if not return_abs:
+            return val
+        a0 = wa * (((n(0, 0, 0) + n(0, 1, 1)) + (n(0, 0, 0) + n(1, 1, 0))) + pa * (n(0, 0, 0) + n(1, 0, 1)))
+        a1 = wa * (((n(1, 0, 0) + n(1, 1, 1)) + (n(0, 0, 1) + n(1, 1, 1))) + pa * (n(0, 1, 0) + n(1, 1, 1)))
+        return val, np.stack([a0, a1], axis=2)
+
+    def owner_sum(self, y_loc, return_abs=False):
+        """y [2 ndofs] from y_loc [ncells, nd, 2]: the scalar owner sum per component."""
+        yl = np.asarray(y_loc, dtype=np.float64)
+        parts = [PoissonOperator.owner_sum(self, yl[:, :, r], True) for r in range(2)]
+        y = np.ascontiguousarray(np.stack([q[0] for q in parts], axis=1).ravel())
+        A = np.ascontiguousarray(np.stack([q[1] for q in parts], axis=1).ravel())
+        return (y, A) if return_abs else y
+
+    def load(self, degree_dg, rhs_dg, b_extra=None, return_abs=False):
+        """b [2 ndofs] from rhs_dg [2][ncells * nd_d] (DG_d nodal values of the two components)."""
+        if degree_dg < 0 or degree_dg > 3:
+            raise ValueError(f"load: degree_dg = {degree_dg} outside 0 ... 3")
+        L = load_table(self.p, degree_dg)
+        f = np.asarray(rhs_dg, dtype=np.float64).reshape(2, self.mesh.ncells, nd_of(degree_dg))
+        s, A = zip(*[_sum_products(L, f[r]) for r in range(2)])
+        b = self.owner_sum(self.adet[:, None, None] * np.stack(s, axis=2))
+        Ab = self.owner_sum(self.adet[:, None, None] * np.stack(A, axis=2))
+        if b_extra is not None:
+            e = np.asarray(b_extra, dtype=np.float64)
+            b = b + e
+            Ab = Ab + np.abs(e)
+        return (b, Ab) if return_abs else b
+
+    def diagonal(self, return_abs=False):
+        """The diagonal of the cell matrices through the owner sum."""
+        g = [np.broadcast_to(np.diagonal(self.M[m])[None, :], (self.mesh.ncells, self.nd)) for m in range(4)]
+        ga = [np.abs(x) for x in g]
+        D = [[self._D(g, a, b, ga) for b in range(2)] for a in range(2)]
+        w, pi = self.adet[:, None], self.pi[:, None]
+        val = [w * (((D[0][0][0] + D[1][1][0]) + D[r][r][0]) + pi * D[r][r][0]) for r in range(2)]
+        A = [np.abs(w) * (((D[0][0][1] + D[1][1][1]) + D[r][r][1]) + np.abs(pi) * D[r][r][1]) for r in range(2)]
+        d = self.owner_sum(np.stack(val, axis=2))
+        return (d, self.owner_sum(np.stack(A, axis=2))) if return_abs else d
+
+    def pcg(self, b, u, rtol=1e-8, atol=0.0, maxit=1000):
+        """The CG of PoissonOperator.pcg on the blocked vectors (eqlb_elasticity_solve).  Each component needs a
+        Dirichlet DOF; a rotation the mask leaves free is the caller's responsibility."""
+        for r in range(2):
+            if not self.fixed[r::2].any():
+                raise ValueError(f"pcg: singular: component {r} has no Dirichlet DOF")
+        return PoissonOperator.pcg(self, b, u, rtol, atol, maxit)

@@ -924,6 +924,64 @@ int eqlb_primal_residual(eqlb_primal_t* handle, const double* b, const double* u
 int eqlb_primal_solve(eqlb_primal_t* handle, const double* b, double* u, double rtol, double atol, int32_t maxit,
                       double* info, int32_t memspace, void* stream);
 
+/* ---- The P_p^2 linear-elasticity problem on the device: the counterpart of eqlb_primal_* ------------------------------
+ * -div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2, 1 <= p <= 4: the primal solve of demo/elasticity_adaptive/demo_cook.py,
+ * in the non-dimensional form and with the pi_1 / cell_pi1 convention of eqlb_primal_stress_dg (per cell where cell_pi1
+ * is given, else the scalar), so that the solution and the stress formed from it use the same law.  The space is the
+ * scalar numbering of eqlb_mesh_lagrange_dofmap, blocked as eqlb_primal_stress_dg and the prolongation with bs = 2
+ * read it: x[2 dof + r].  eqlb_elasticity_ndofs gives the scalar count; every vector below has 2 ndofs rows.
+ *
+ * The rule is stated in numpy in dolfinx_eqlb_amd/lsolver/primal.py (ElasticityOperator); apply, load, diagonal and
+ * residual reproduce it bit for bit.  No fused multiply-add anywhere; every operation is rounded on its own:
+ *   cell       J = cellJ of the handle, K = J^-1 as for eqlb_primal_* (K[X][d]); Q[a][b][X][Y] = K[X][a] K[Y][b];
+ *              u_s[j] = u[2 dof(c, j) + s];
+ *              g_XY^s[i] = sum_j M_XY[i][j] u_s[j], ascending j, with M_00 = S0, M_11 = S2 of Stiff<p>, M_01 = Cross<p>,
+ *              M_10 = Cross<p>^T;
+ *              D_ab^s[i] = (Q[a][b][0][0] g_00^s[i] + Q[a][b][0][1] g_01^s[i])
+ *                        + (Q[a][b][1][0] g_10^s[i] + Q[a][b][1][1] g_11^s[i])        ( = int d_a phi_i d_b u_s )
+ *              y_loc[c][i][0] = |det J| (((D_00^0 + D_11^0) + (D_00^0 + D_10^1)) + pi_c (D_00^0 + D_01^1))
+ *              y_loc[c][i][1] = |det J| (((D_00^1 + D_11^1) + (D_01^0 + D_11^1)) + pi_c (D_10^0 + D_11^1))
+ *   owner sum  as for eqlb_primal_*, per (dof, r)
+ *   diagonal   g_XY = M_XY[i][i], D_ab as above, |det J| (((D_00 + D_11) + D_rr) + pi_c D_rr), through the owner sum
+ *   load       per cell and component |det J| sum_n Load[i][n] rhs_dg[r][c][n] (ascending n), through the owner sum,
+ *              + b_extra[2 d + r] where given (the tractions, lsolver.traction_load)
+ * Host-only getter: eqlb_get_cross_table  Cross<p> [nd_p][nd_p] = int dX phi_i dY phi_j on the reference triangle
+ * (S1 of Stiff<p> equals Cross + Cross^T exactly).
+ *
+ * Every entry behaves as its eqlb_primal_* counterpart: device memory space enqueues on `stream` and nothing waits, host
+ * memory space is staged and synchronous; nothing is allocated after create; two calls give the same bits; calls on one
+ * handle belong on one stream, one after the other; the mesh must outlive the handle.
+ *   cell_pi1 [ncells] in `memspace` or NULL (the scalar pi_1 everywhere), copied
+ *   set_dirichlet  facets0 [nlist0], facets1 [nlist1]: fixed are the rows 2 dof + r of the vertex and facet DOFs of the
+ *              facets listed for component r (the facets with type 1 in row r of a stress handle); a repeated call
+ *              replaces the mask.  A facet id outside the mesh: host memory space: refused by name, the mask as it was;
+ *              device memory space: skipped and counted
+ *   load       rhs_dg [2][ncells][nd_d], 0 <= degree_dg <= 3; b_extra [2 ndofs] or NULL; b [2 ndofs]
+ *   residual   norms [2] in `memspace` or NULL, as eqlb_primal_residual
+ *   solve      the Jacobi-preconditioned CG of eqlb_primal_solve, word for word, on the 2 ndofs rows; info HOST [8] as
+ *              there.  EQLB_OK also for a run that did not converge.  Refused before anything is launched
+ *              (EQLB_ERR_INVALID_ARGUMENT): maxit < 1, rtol or atol negative or NaN, null arguments, and a component
+ *              without one listed valid facet ("singular: component r has no Dirichlet DOF").  That refusal catches the
+ *              translations only: a mask that leaves a rotation free (one fixed row per component, say) is the caller's
+ *              responsibility and shows as breakdown or as no convergence within maxit. */
+typedef struct eqlb_elasticity eqlb_elasticity_t;
+int eqlb_get_cross_table(int32_t p, double* out, int32_t capacity);
+int eqlb_elasticity_create(eqlb_mesh_t* mesh, int32_t p, double pi_1, const double* cell_pi1, int32_t memspace,
+                           void* stream, eqlb_elasticity_t** handle);
+void eqlb_elasticity_destroy(eqlb_elasticity_t* handle);
+int eqlb_elasticity_ndofs(const eqlb_elasticity_t* handle, int64_t* ndofs);
+int eqlb_elasticity_set_dirichlet(eqlb_elasticity_t* handle, int32_t nlist0, const int32_t* facets0, int32_t nlist1,
+                                  const int32_t* facets1, int32_t memspace, void* stream);
+int eqlb_elasticity_load(eqlb_elasticity_t* handle, int32_t degree_dg, const double* rhs_dg, const double* b_extra,
+                         double* b, int32_t memspace, void* stream);
+int eqlb_elasticity_apply(eqlb_elasticity_t* handle, const double* u, double* y, int32_t masked, int32_t memspace,
+                          void* stream);
+int eqlb_elasticity_diagonal(eqlb_elasticity_t* handle, double* out, int32_t memspace, void* stream);
+int eqlb_elasticity_residual(eqlb_elasticity_t* handle, const double* b, const double* u, double* r, double* norms,
+                             int32_t memspace, void* stream);
+int eqlb_elasticity_solve(eqlb_elasticity_t* handle, const double* b, double* u, double rtol, double atol,
+                          int32_t maxit, double* info, int32_t memspace, void* stream);
+
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the
  * partial sums of the ghost-cell rows are sent to the owning rank and added there.  DEVICE pointers:

@@ -1,0 +1,287 @@
+"""The P_p^2 elasticity solve as far as it can be checked without a device: the table Cross<p> against quadrature, in
+exact rationals against Stiff<p> and bit for bit against the library, the numpy statement
+(dolfinx_eqlb_amd/lsolver/primal.py: ElasticityOperator) against the assembled Galerkin matrix, its PCG against a direct
+solve, traction_load, the mask per component, and the refusals of the ABI that come before the device is touched."""
+
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import scipy.sparse.linalg as spla
+
+import elasticity_cases as ec
+import galerkin as gk
+from dolfinx_eqlb_amd.elmtlib.lagrange import Lagrange
+from dolfinx_eqlb_amd.elmtlib.quadrature import make_quadrature_triangle
+from dolfinx_eqlb_amd.lsolver import primal
+from dolfinx_eqlb_amd.mesh import create_unit_square
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INVALID_ARGUMENT = -1
+U = ec.U
+ENTRIES = ("eqlb_get_cross_table", "eqlb_elasticity_create", "eqlb_elasticity_ndofs", "eqlb_elasticity_set_dirichlet",
+           "eqlb_elasticity_load", "eqlb_elasticity_apply", "eqlb_elasticity_diagonal", "eqlb_elasticity_residual",
+           "eqlb_elasticity_solve")
+METHODS = ("set_dirichlet", "load", "apply", "diagonal", "residual", "solve")
+
+MESH = create_unit_square(4, shuffle_seed=3, perturb=0.15)
+
+
+def _ratio(diff, bound):
+    """max of diff / bound with 0 / 0 = 0 (printed); the assertion is diff <= bound entry by entry"""
+    return float(np.max(np.where(bound > 0.0, diff / np.where(bound > 0.0, bound, 1.0), np.where(diff > 0.0, np.inf, 0.0))))
+
+
+# ---- the table ------------------------------------------------------------------------------------------------------
+def _abs_tab(el, pts):
+    """tabulate (value, dX, dY) with the absolute value of every monomial term: the abs-sum of the evaluation"""
+    from dolfinx_eqlb_amd.elmtlib import polynomials as P
+    out = np.zeros((3, pts.shape[0], el.ndofs))
+    for i, b in enumerate(el.basis):
+        for n, poly in enumerate((b, P.ddx(b), P.ddy(b))):
+            out[n, :, i] = P.evaluate({k: abs(v) for k, v in poly.items()}, pts)
+    return out
+
+
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_cross_table_equals_quadrature_and_splits_s1_exactly(p):
+    """|table - quadrature| <= terms 2^-53 abs-sum with the count of test_primal_host.py: nq sums, two polynomial
+    evaluations of at most nd_p monomials with powers up to p (nd_p + p + 1 each), 3 products, the rounding of points
+    and weights (4) and of the table entry (1).  In Fractions: S1 == Cross + Cross^T, entry by entry."""
+    el = Lagrange(p)
+    qp, qw = make_quadrature_triangle(2 * p)
+    t, a = el.tabulate(qp, 1), _abs_tab(el, qp)
+    Cx = primal.cross_table(p)
+    terms = qw.size + 2 * (el.ndofs + p + 1) + 3 + 4 + 1
+    diff = np.abs(Cx - np.einsum("q,qi,qj->ij", qw, t[1], t[2]))
+    bound = terms * U * np.einsum("q,qi,qj->ij", qw, a[1], a[2])
+    print(f"Cross<{p}>: max |diff| / bound = {_ratio(diff, bound):.3f}")
+    assert np.all(diff <= bound)
+    S, E = primal.stiffness_table_exact(p), primal.cross_table_exact(p)
+    n = len(E)
+    assert len(S[1]) == n and all(S[1][i][j] == E[i][j] + E[j][i] for i in range(n) for j in range(n))
+    assert any(E[i][j] != E[j][i] for i in range(n) for j in range(n))     # (Cross itself is not symmetric)
+    with pytest.raises(ValueError):
+        primal.cross_table_exact(5)
+
+
+def test_library_table_is_the_generated_one():
+    from dolfinx_eqlb_amd import cpp
+    for p in range(1, 5):
+        assert np.array_equal(cpp.get_cross_table(p), primal.cross_table(p))
+    L = cpp.lib()
+    buf = np.zeros(4)
+    for p in (0, 5):
+        assert L.eqlb_get_cross_table(C.c_int32(p), buf.ctypes.data_as(C.c_void_p), C.c_int32(4)) == INVALID_ARGUMENT
+    assert L.eqlb_get_cross_table(C.c_int32(2), buf.ctypes.data_as(C.c_void_p), C.c_int32(4)) == INVALID_ARGUMENT
+    assert "capacity" in L.eqlb_last_error().decode()
+    assert L.eqlb_get_cross_table(C.c_int32(1), None, C.c_int32(9)) == INVALID_ARGUMENT
+
+
+# ---- the statement against the assembled matrix --------------------------------------------------------------------
+@pytest.mark.parametrize("per_cell", [False, True])
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_statement_equals_the_assembled_operator(p, per_cell):
+    mesh = MESH
+    rng = np.random.default_rng(5 + p)
+    pi_1, cell_pi1 = (1.0, ec.pi1_of(mesh.ncells)) if per_cell else (3.5, None)
+    op = primal.ElasticityOperator(mesh, p, pi_1, cell_pi1)
+    d = min(p - 1, 3) if p > 1 else 1
+    nd = (d + 1) * (d + 2) // 2
+    f = rng.standard_normal((2, mesh.ncells * nd))
+    A, Aabs, b, babs = ec.assemble(mesh, p, pi_1, cell_pi1, d, f)
+    assert A.shape[0] == 2 * op.ndofs
+    u = rng.standard_normal(2 * op.ndofs)
+    valence = int(np.diff(mesh.node_cells_offsets).max())
+    ts, ta = ec.chain_terms(p, valence, make_quadrature_triangle(2 * p + 4)[1].size)
+    # operator
+    y, yabs = op.apply(u, return_abs=True)
+    diff, bound = np.abs(y - A @ u), U * (ts * yabs + ta * (Aabs @ np.abs(u)))
+    print(f"p={p} per_cell={per_cell}: apply max |diff| / bound = {_ratio(diff, bound):.3f} (terms {(ts, ta)})")
+    assert np.all(diff <= bound)
+    # load (b_extra is added as it is)
+    e = rng.standard_normal(2 * op.ndofs)
+    bs, bsabs = op.load(d, f, return_abs=True)
+    diff, bound = np.abs(bs - b), U * (ts * bsabs + ta * babs)
+    print(f"p={p} per_cell={per_cell}: load max |diff| / bound = {_ratio(diff, bound):.3f}")
+    assert np.all(diff <= bound)
+    assert np.array_equal(op.load(d, f, e), bs + e)
+    # diagonal
+    dg, dabs = op.diagonal(return_abs=True)
+    diff, bound = np.abs(dg - A.diagonal()), U * (ts * dabs + ta * Aabs.diagonal())
+    print(f"p={p} per_cell={per_cell}: diagonal max |diff| / bound = {_ratio(diff, bound):.3f}")
+    assert np.all(diff <= bound) and np.all(dg > 0.0)
+    # residual and mask
+    bf = mesh.boundary_facets()
+    op.set_dirichlet(bf, bf)
+    r = op.residual(bs, u)
+    assert np.array_equal(r[~op.fixed], (bs - y)[~op.fixed]) and np.all(r[op.fixed] == 0.0)
+    ym = op.apply(u, masked=True)
+    assert np.array_equal(ym[~op.fixed], y[~op.fixed]) and np.all(ym[op.fixed] == 0.0)
+
+
+# ---- the mask -------------------------------------------------------------------------------------------------------
+def test_dirichlet_mask_is_per_component_replaces_and_refuses():
+    mesh = MESH
+    p = 3
+    op = primal.ElasticityOperator(mesh, p)
+    sides = gk.side_facets(mesh)
+    ft = gk.elasticity_facet_types(mesh, [(True, False), (False, True)])
+    lists = ec.dirichlet_lists(ft)
+    op.set_dirichlet(*lists)
+    for r in range(2):
+        assert np.array_equal(op.fixed[r::2], primal.dirichlet_mask(mesh, p, lists[r]))
+    assert not np.array_equal(op.fixed[0::2], op.fixed[1::2])
+    # a repeated call replaces the mask
+    op.set_dirichlet(sides[0][:1], [])
+    assert op.fixed[0::2].sum() == 2 + (p - 1) and not op.fixed[1::2].any()
+    for bad in ([mesh.nfacets], [-1]):
+        with pytest.raises(ValueError, match="no facet"):
+            op.set_dirichlet(sides[0], bad)
+        with pytest.raises(ValueError, match="no facet"):
+            op.set_dirichlet(bad, sides[0])
+    n = 2 * op.ndofs
+    with pytest.raises(ValueError, match="component 1 has no Dirichlet"):
+        op.pcg(np.zeros(n), np.zeros(n))
+    op.set_dirichlet([], sides[0])
+    with pytest.raises(ValueError, match="component 0 has no Dirichlet"):
+        op.pcg(np.zeros(n), np.zeros(n))
+
+
+# ---- the PCG statement ----------------------------------------------------------------------------------------------
+def energy_bound(A, free, tol, u_direct):
+    """|| u - u_direct ||_A <= tol / sqrt(lambda_min(A_ff)) + cond(A_ff) 2^-52 || u_direct ||_A: the first term from
+    || e ||_A^2 = r^T A_ff^-1 r <= || r ||^2 / lambda_min, the second the accuracy of the direct solve itself (the
+    bounds of test_primal_host.py)."""
+    Aff = A[free][:, free].toarray()
+    lam = np.linalg.eigvalsh(Aff)
+    ud = u_direct[free]
+    return tol / np.sqrt(lam[0]) + (lam[-1] / lam[0]) * 2.0 ** -52 * np.sqrt(ud @ (Aff @ ud)), Aff
+
+
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_pcg_statement_meets_its_stop_rule_and_the_direct_solve(p):
+    mesh = MESH
+    rng = np.random.default_rng(p)
+    cell_pi1 = ec.pi1_of(mesh.ncells)
+    op = primal.ElasticityOperator(mesh, p, cell_pi1=cell_pi1)
+    ft = gk.elasticity_facet_types(mesh, [(True, False)])          # traction-free in row 0 on side 0
+    op.set_dirichlet(*ec.dirichlet_lists(ft))
+    d = min(p, 3)
+    f = rng.standard_normal((2, mesh.ncells * (d + 1) * (d + 2) // 2))
+    b = op.load(d, f)
+    n = 2 * op.ndofs
+    u0 = np.where(op.fixed, rng.standard_normal(n), 0.0)           # inhomogeneous Dirichlet values
+    u, info = op.pcg(b, u0, rtol=1e-10, maxit=4000)
+    assert info["converged"] == 1 and info["breakdown"] == 0 and 0 < info["iterations"] < 4000
+    tol = 1e-10 * info["nb"]
+    assert np.array_equal(u[op.fixed], u0[op.fixed])
+    r = op.residual(b, u)
+    assert np.sqrt(np.sum(r * r)) <= tol and info["rnorm"] <= tol
+    A = ec.assemble(mesh, p, 1.0, cell_pi1)[0]
+    free = np.nonzero(~op.fixed)[0]
+    ud = u0.copy()
+    ud[free] = spla.spsolve(A[free][:, free].tocsc(), (b - A @ u0)[free])
+    bound, Aff = energy_bound(A, free, tol, ud)
+    e = (u - ud)[free]
+    err = np.sqrt(e @ (Aff @ e))
+    print(f"p={p}: {info['iterations']} iterations, energy error {err:.3e}, bound {bound:.3e}")
+    assert err <= bound
+    # the limits
+    u3, i3 = op.pcg(b, u0, rtol=1e-10, maxit=3)
+    assert i3["converged"] == 0 and i3["iterations"] == 3
+    uz, iz = op.pcg(np.zeros(n), np.where(op.fixed, 0.0, 1.0), rtol=0.0, atol=0.0, maxit=5)
+    assert iz["converged"] == 1 and iz["iterations"] == 0 and np.all(uz == 0.0)
+
+
+# ---- traction_load --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_traction_load_is_the_boundary_integral_row_by_row(p):
+    """b_extra[2 d + r] is neumann_load of row r, bit for bit; summed over the DOFs, row r is -int_E g_r (partition of
+    unity).  With g_r = -t_r, the value a stress handle's row prescribes, that is +int_E t_r: the traction term."""
+    from dolfinx_eqlb_amd.eqlb.bcs import fluxbc
+    mesh = create_unit_square(3, shuffle_seed=1, perturb=0.2)
+    sides = gk.side_facets(mesh)
+    t0 = lambda x, y: 1.0 + x * x + 0.0 * y      # noqa: E731     on y = 0: int_0^1 1 + x^2 = 4/3
+    t1 = lambda x, y: 2.0 * y + 0.0 * x          # noqa: E731     on x = 1: int_0^1 2 y = 1
+    rows = [[fluxbc(lambda x, y: -t0(x, y), sides[1], scalar=True)],
+            [fluxbc(lambda x, y: -t1(x, y), sides[2], scalar=True), fluxbc(None, sides[3])]]
+    b = primal.traction_load(mesh, p, rows)
+    ndofs = primal.lagrange_dofmap(mesh, p)[1]
+    assert b.shape == (2 * ndofs,)
+    for r in range(2):
+        assert np.array_equal(b[r::2], primal.neumann_load(mesh, p, rows[r]))
+    assert abs(b[0::2].sum() - 4.0 / 3.0) < 1e-13 and abs(b[1::2].sum() - 1.0) < 1e-13
+    with pytest.raises(ValueError, match="two lists"):
+        primal.traction_load(mesh, p, rows[:1])
+
+
+# ---- ABI ------------------------------------------------------------------------------------------------------------
+def test_entries_are_declared_exported_and_bound():
+    from dolfinx_eqlb_amd import cpp, lsolver
+    header = open(os.path.join(ROOT, "include", "eqlb.h")).read()
+    L = cpp.lib()
+    for name in ENTRIES:
+        assert re.search(r"^int\s+" + name + r"\(", header, flags=re.M), name
+        assert name in cpp.EXPORTED_SYMBOLS and hasattr(L, name), name
+    assert re.search(r"^void\s+eqlb_elasticity_destroy\(", header, flags=re.M)
+    assert "eqlb_elasticity_destroy" in cpp.EXPORTED_SYMBOLS and hasattr(L, "eqlb_elasticity_destroy")
+    for name in METHODS:
+        assert hasattr(cpp.PrimalElasticity, name) and hasattr(cpp.PrimalElasticity, name + "_raw"), name
+    assert hasattr(cpp.PrimalElasticity, "create_raw") and hasattr(cpp, "get_cross_table")
+    for name in ("ElasticityOperator", "traction_load"):
+        assert getattr(lsolver, name) is getattr(primal, name)
+    from dolfinx_eqlb_amd import _cpp
+    for name in METHODS:
+        assert hasattr(_cpp.PrimalElasticity, name), name
+
+
+def test_abi_refuses_bad_arguments_before_the_device():
+    from dolfinx_eqlb_amd import cpp
+    L = cpp.lib()
+    L.eqlb_elasticity_create.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p]
+    L.eqlb_elasticity_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                        C.c_void_p, C.c_int32, C.c_void_p]
+    val = np.full(8, 7.0)
+    pv = val.ctypes.data_as(C.c_void_p)
+    fake = C.c_void_p(0x5EED5EED)   # never dereferenced: the refusal comes first
+    host, h = C.c_int32(0), C.c_void_p()
+
+    def refused(st, *words):
+        assert st == INVALID_ARGUMENT
+        msg = L.eqlb_last_error().decode()
+        for w in words:
+            assert w in msg, (w, msg)
+
+    for p in (0, 5, -1):
+        refused(L.eqlb_elasticity_create(fake, p, 1.0, None, 0, None, C.byref(h)), "eqlb_elasticity_create", "p =")
+    refused(L.eqlb_elasticity_create(None, 2, 1.0, None, 0, None, C.byref(h)), "eqlb_elasticity_create", "null")
+    refused(L.eqlb_elasticity_create(fake, 2, 1.0, None, 0, None, None), "eqlb_elasticity_create", "null")
+    assert not h
+    for d in (-1, 4):
+        refused(L.eqlb_elasticity_load(fake, C.c_int32(d), pv, None, pv, host, None), "eqlb_elasticity_load",
+                "degree_dg")
+    refused(L.eqlb_elasticity_load(None, C.c_int32(1), pv, None, pv, host, None), "eqlb_elasticity_load", "null")
+    for maxit in (0, -3):
+        refused(L.eqlb_elasticity_solve(fake, pv, pv, 1e-8, 0.0, maxit, pv, 0, None), "eqlb_elasticity_solve", "maxit")
+    for rtol, atol in ((-1e-8, 0.0), (1e-8, -1.0), (float("nan"), 0.0), (0.0, float("nan"))):
+        refused(L.eqlb_elasticity_solve(fake, pv, pv, rtol, atol, 10, pv, 0, None), "eqlb_elasticity_solve", "rtol")
+    refused(L.eqlb_elasticity_solve(None, pv, pv, 1e-8, 0.0, 10, pv, 0, None), "eqlb_elasticity_solve", "null")
+    sd = L.eqlb_elasticity_set_dirichlet
+    refused(sd(fake, C.c_int32(-1), pv, C.c_int32(0), None, host, None), "eqlb_elasticity_set_dirichlet", "nlist0")
+    refused(sd(fake, C.c_int32(0), None, C.c_int32(-2), pv, host, None), "eqlb_elasticity_set_dirichlet", "nlist1")
+    refused(sd(fake, C.c_int32(2), None, C.c_int32(0), None, host, None), "eqlb_elasticity_set_dirichlet", "null")
+    refused(sd(fake, C.c_int32(0), None, C.c_int32(2), None, host, None), "eqlb_elasticity_set_dirichlet", "null")
+    refused(sd(None, C.c_int32(1), pv, C.c_int32(1), pv, host, None), "eqlb_elasticity_set_dirichlet", "null")
+    refused(L.eqlb_elasticity_apply(None, pv, pv, C.c_int32(0), host, None), "eqlb_elasticity_apply", "null")
+    refused(L.eqlb_elasticity_diagonal(None, pv, host, None), "eqlb_elasticity_diagonal", "null")
+    refused(L.eqlb_elasticity_residual(None, pv, pv, pv, None, host, None), "eqlb_elasticity_residual", "null")
+    n = C.c_int64(-5)
+    refused(L.eqlb_elasticity_ndofs(None, C.byref(n)), "eqlb_elasticity_ndofs")
+    assert n.value == -5 and np.all(val == 7.0)
+    L.eqlb_elasticity_destroy(None)
+    L.eqlb_elasticity_create.argtypes = None
+    L.eqlb_elasticity_solve.argtypes = None

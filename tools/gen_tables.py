@@ -27,6 +27,8 @@ Basix nor quadrature loops:
   ST[3][nd_p][nd_p]    reference stiffness of P_p: int dX phi_i dX phi_j, int (dX phi_i dY phi_j + dY phi_i dX phi_j),
                        int dY phi_i dY phi_j (eqlb_primal_solve.hip; lsolver/primal.py: stiffness_table_exact)
   LD[nd_p][nd_d]       int phi_i chi_n, chi_n the DG_d nodal basis: the load of P_p against DG_d data (load_table_exact)
+  CR[nd_p][nd_p]       int dX phi_i dY phi_j: with ST the four reference blocks of the elasticity operator
+                       (eqlb_primal_elasticity.hip; lsolver/primal.py: cross_table_exact)
 
 Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
       go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
@@ -421,6 +423,19 @@ def emit(path):
             lines.append(f"  static constexpr double LD[{len(t) * len(t[0])}] = {{"
                          + ", ".join(repr(float(v)) for row in t for v in row) + "};")
             lines.append("};")
+    lines.append("")
+    from dolfinx_eqlb_amd.lsolver.primal import cross_table_exact
+    lines.append("// cross block of the reference stiffness of P_p: CR[i][j] = int dX phi_i dY phi_j; S1 == CR + CR^T exactly")
+    lines.append("// (lsolver/primal.py, eqlb_primal_elasticity.hip)")
+    lines.append("template <int P> struct Cross;")
+    for p in range(1, 5):
+        t = cross_table_exact(p)
+        n = len(t)
+        lines.append(f"template <> struct Cross<{p}> {{")
+        lines.append(f"  static constexpr int ND = {n};")
+        lines.append(f"  static constexpr double CR[{n * n}] = {{"
+                     + ", ".join(repr(float(v)) for row in t for v in row) + "};")
+        lines.append("};")
     lines.append("")
     from dolfinx_eqlb_amd.mesh.transfer import flux_bc_table_exact
     lines.append("// facet DOFs of a flux boundary condition across one bisection level: FB[m][j][i], child DOF j from parent DOF i")

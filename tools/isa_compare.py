@@ -13,6 +13,10 @@ only and kernels that differ are listed, and any of them makes the exit status 1
 device code are skipped.  It only diffs two builds against each other.
 
   --units a.hip b.hip   only these units
+  --rename OLD=NEW      a kernel of REV that has another symbol in the tree (one that became a template, say): compared
+                        under the new name.  Substrings of the mangled names; each must match one symbol
+  --ignore-pcrel        the literal of the s_add_u32 behind an s_getpc_b64 (the distance from the code to a constant
+                        table, which moves when the unit's symbols are emitted in another order) is not compared
   --cache DIR           keep REV's side there (by commit hash) for the next call
 At most 8 compile jobs run at a time.
 """
@@ -56,7 +60,7 @@ def export_rev(rev, dst):
            os.path.join(dst, CSRC, "eqlb_tables_build_gen.h"))
 
 
-def functions_of(disasm):
+def functions_of(disasm, ignore_pcrel=False):
     """symbol -> instruction lines, without the address and encoding comment"""
     funcs, cur = {}, None
     for line in disasm.splitlines():
@@ -66,6 +70,8 @@ def functions_of(disasm):
         elif cur is not None and line.startswith(("\t", " ")):
             text = line.split("//")[0].strip()
             if text:
+                if ignore_pcrel and cur and cur[-1].startswith("s_getpc_b64") and text.startswith("s_add_u32"):
+                    text = re.sub(r"0x[0-9a-f]+$", "<pcrel>", text)
                 cur.append(text)
     return funcs
 
@@ -91,7 +97,7 @@ def kernels_of(notes):
     return {k[:-3] if k.endswith(".kd") else k: v for k, v in kernels.items()}
 
 
-def device_code(src, flags, work):
+def device_code(src, flags, work, ignore_pcrel=False):
     """{'funcs': ..., 'meta': ...} of one unit, or None if it has no device code"""
     stem = os.path.join(work, os.path.basename(src)[:-4])
     sh("/opt/rocm/bin/hipcc", *flags, "--cuda-device-only", "-c", src, "-o", stem + ".bundle")
@@ -99,16 +105,26 @@ def device_code(src, flags, work):
        "--targets=" + TARGET, "--input=" + stem + ".bundle", "--output=" + stem + ".co")
     if os.path.getsize(stem + ".co") == 0:
         return None
-    funcs = functions_of(sh(os.path.join(LLVM, "llvm-objdump"), "-d", stem + ".co"))
+    funcs = functions_of(sh(os.path.join(LLVM, "llvm-objdump"), "-d", stem + ".co"), ignore_pcrel)
     meta = kernels_of(sh(os.path.join(LLVM, "llvm-readelf"), "--notes", stem + ".co"))
     return {"funcs": funcs, "meta": meta} if funcs or meta else None
 
 
-def compare(unit, old, new):
+def renamed(side, renames):
+    """REV's side with the symbols of --rename under their names in the tree"""
+    for old, new in renames:
+        for part in ("funcs", "meta"):
+            hits = [n for n in side[part] if old in n and new not in n]
+            if len(hits) == 1:
+                side[part][hits[0].replace(old, new)] = side[part].pop(hits[0])
+    return side
+
+
+def compare(unit, old, new, renames=()):
     """summary line and findings of one unit"""
     if old is None and new is None:
         return None, []
-    old = old or {"funcs": {}, "meta": {}}
+    old = renamed(old, renames) if old else {"funcs": {}, "meta": {}}
     new = new or {"funcs": {}, "meta": {}}
     names_old = set(old["funcs"]) | set(old["meta"])
     names_new = set(new["funcs"]) | set(new["meta"])
@@ -136,6 +152,8 @@ def main():
     ap.add_argument("rev", nargs="?", default="HEAD")
     ap.add_argument("--units", nargs="+")
     ap.add_argument("--cache")
+    ap.add_argument("--rename", nargs="+", default=[], metavar="OLD=NEW")
+    ap.add_argument("--ignore-pcrel", action="store_true")
     args = ap.parse_args()
     sha = sh("git", "rev-parse", args.rev + "^{commit}").strip()
     tmp = tempfile.mkdtemp(prefix="eqlb_isa.")
@@ -146,7 +164,7 @@ def main():
         flags = make_var(sides["tree"], "print-flags")
         units = {s: make_var(d, "print-srcs") for s, d in sides.items()}
         todo = args.units or sorted(set(units["rev"]) | set(units["tree"]))
-        cache = os.path.join(args.cache, sha) if args.cache else None
+        cache = os.path.join(args.cache, sha + ("-nopcrel" if args.ignore_pcrel else "")) if args.cache else None
         result = {"rev": {}, "tree": {}}
         jobs = {}
         with concurrent.futures.ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:
@@ -159,8 +177,8 @@ def main():
                     elif cached and os.path.exists(cached):
                         result[side][u] = json.load(open(cached))
                     else:
-                        jobs[pool.submit(device_code, os.path.join(d, u), flags,
-                                         os.path.join(tmp, "out_" + side))] = (side, u, cached)
+                        jobs[pool.submit(device_code, os.path.join(d, u), flags, os.path.join(tmp, "out_" + side),
+                                         args.ignore_pcrel)] = (side, u, cached)
             for fut in concurrent.futures.as_completed(jobs):
                 side, u, cached = jobs[fut]
                 result[side][u] = fut.result()
@@ -173,7 +191,7 @@ def main():
         shutil.rmtree(tmp, ignore_errors=True)
     bad = 0
     for u in todo:
-        line, findings = compare(u, result["rev"][u], result["tree"][u])
+        line, findings = compare(u, result["rev"][u], result["tree"][u], [r.split("=", 1) for r in args.rename])
         if line is None:
             print(f"{u}: no device code, skipped")
             continue

@@ -13,6 +13,9 @@ tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all ar
   host       scipy.sparse.linalg.cg with the same diagonal preconditioner and tolerance on the matrix assembled from the
              same tables, and spsolve, on the host of the same machine (--host; each under a time budget, reported as
              "not finished" beyond it)
+  --elasticity  after the Poisson figures, the same figures for the P_p^2 elasticity solve (cpp.PrimalElasticity): pi_1 = 1,
+             u = 0 all around in both rows, the body force (f_ex, f_ex(y, x)); vectors have 2 ndofs rows, the solution
+             is prolonged with bs = 2, and the product time is also given as a multiple of Poisson's at the same degree
   --check-every LIB:N ...   the PCG of P_2 to rtol 1e-8 from zero once per library (builds of libeqlb_amd.so with
              -DEQLB_PRIMAL_CHECK_EVERY=N, tools/build_variant.sh NAME "-D..." eqlb_primal_solve), each in a child process
 Prints one line per figure and, last, one JSON line with all of them.  Nothing here is a pass/fail condition.
@@ -44,25 +47,27 @@ def f_ex(x, y):
     return 2 * np.pi ** 2 * s(np.pi * x) * s(np.pi * y) * (1 + x) - 2 * np.pi * c(np.pi * x) * s(np.pi * y)
 
 
-def rhs_dg(mesh, d):
-    """f_ex interpolated at the DG_d nodes (nodal values [ncells * nd_d])"""
+def rhs_dg(mesh, d, swap=False):
+    """f_ex interpolated at the DG_d nodes (nodal values [ncells * nd_d]); swap: f_ex(y, x)"""
     from dolfinx_eqlb_amd.elmtlib.lagrange import lagrange_nodes
     X = np.array([[float(a), float(b)] for a, b in lagrange_nodes(d)])
     xc = mesh.x[mesh.cell_nodes, :2]
     pts = xc[:, None, 0, :] + X[None, :, 0:1] * (xc[:, 1] - xc[:, 0])[:, None, :] \
         + X[None, :, 1:2] * (xc[:, 2] - xc[:, 0])[:, None, :]
-    return np.ascontiguousarray(f_ex(pts[..., 0], pts[..., 1]).ravel())
+    return np.ascontiguousarray(f_ex(pts[..., 1 if swap else 0], pts[..., 0 if swap else 1]).ravel())
 
 
-def product_bytes(mesh, p):
+def product_bytes(mesh, p, bs=1):
     """compulsory bytes of one product from the shapes: the cell pass reads the dofmap, cellJ and u once and writes
-    y_loc; the sum pass reads y_loc, the slot lists, the two offset tables and the mask and writes y"""
+    y_loc; the sum pass reads y_loc, the slot lists, the two offset tables and the mask and writes y.  bs components
+    per DOF (elasticity: 2): u, y_loc, the mask and y grow by bs, the dofmap, cellJ and the lists do not.  Returns the
+    bytes and the number of rows bs * ndofs"""
     nd, ne = (p + 1) * (p + 2) // 2, p - 1
     nc, nn, nf = mesh.ncells, mesh.nnodes, mesh.nfacets
     ndofs = nn + nf * ne + nc * (p - 1) * (p - 2) // 2
-    cell = nc * nd * 4 + nc * 32 + ndofs * 8 + nc * nd * 8
-    gather = nc * nd * 8 + 3 * nc * (1 + ne) * 4 + (nn + nf + 2) * 4 + ndofs + ndofs * 8
-    return cell + gather, ndofs
+    cell = nc * nd * 4 + nc * 32 + bs * ndofs * 8 + bs * nc * nd * 8
+    gather = bs * nc * nd * 8 + 3 * nc * (1 + ne) * 4 + (nn + nf + 2) * 4 + bs * ndofs + bs * ndofs * 8
+    return cell + gather, bs * ndofs
 
 
 def timed_solve(torch, h, b, u0, rtol, maxit):
@@ -77,15 +82,50 @@ def timed_solve(torch, h, b, u0, rtol, maxit):
     return info, e0.elapsed_time(e1), u
 
 
-def make_problem(cpp, torch, dm, p):
+def make_problem(cpp, torch, dm, p, elasticity=False):
     mesh = dm.mesh
-    h = cpp.PrimalPoisson(dm, p)
-    h.set_dirichlet(mesh.boundary_facets())
-    f = torch.from_numpy(rhs_dg(mesh, p - 1)).cuda()
-    b = torch.zeros(h.ndofs, dtype=torch.float64, device="cuda")
+    if elasticity:
+        h = cpp.PrimalElasticity(dm, p, 1.0)
+        h.set_dirichlet(mesh.boundary_facets(), mesh.boundary_facets())
+        f = torch.from_numpy(np.stack([rhs_dg(mesh, p - 1), rhs_dg(mesh, p - 1, swap=True)])).cuda()
+    else:
+        h = cpp.PrimalPoisson(dm, p)
+        h.set_dirichlet(mesh.boundary_facets())
+        f = torch.from_numpy(rhs_dg(mesh, p - 1)).cuda()
+    b = torch.zeros((2 if elasticity else 1) * h.ndofs, dtype=torch.float64, device="cuda")
     h.load_raw(p - 1, f.data_ptr(), None, b.data_ptr())
     torch.cuda.synchronize()
     return h, b
+
+
+def host_matrix_elasticity(mesh, p):
+    """A (csr, blocked rows 2 dof + r) of the elasticity problem with pi_1 = 1 from the statement's tables, and the free
+    rows: per cell adet (delta_rs (D_00 + D_11) + D_sr + D_rs)[i][j] with D_ab = sum_XY K[X][a] K[Y][b] M_XY"""
+    import scipy.sparse as sp
+    from dolfinx_eqlb_amd.lsolver import primal
+    from dolfinx_eqlb_amd.mesh.transfer import lagrange_dofmap
+    cd, ndofs = lagrange_dofmap(mesh, p)
+    x, cn = mesh.x, mesh.cell_nodes
+    J00, J01 = x[cn[:, 1], 0] - x[cn[:, 0], 0], x[cn[:, 2], 0] - x[cn[:, 0], 0]
+    J10, J11 = x[cn[:, 1], 1] - x[cn[:, 0], 1], x[cn[:, 2], 1] - x[cn[:, 0], 1]
+    det = J00 * J11 - J01 * J10
+    K = ((J11 / det, -J01 / det), (-J10 / det, J00 / det))
+    S, Cx = primal.stiffness_table(p), primal.cross_table(p)
+    M = ((S[0], Cx), (Cx.T, S[2]))
+    D = [[sum((K[X][a] * K[Y][b])[:, None, None] * M[X][Y][None] for X in range(2) for Y in range(2))
+          for b in range(2)] for a in range(2)]
+    nl = cd.shape[1]
+    Ke = np.zeros((mesh.ncells, nl, 2, nl, 2))
+    for r in range(2):
+        Ke[:, :, r, :, r] += D[0][0] + D[1][1]
+        for c in range(2):
+            Ke[:, :, r, :, c] += D[c][r] + D[r][c]
+    Ke *= np.abs(det)[:, None, None, None, None]
+    vd = (2 * cd[:, :, None] + np.arange(2)[None, None, :]).reshape(mesh.ncells, 2 * nl)
+    A = sp.csr_matrix((Ke.ravel(), (np.repeat(vd, 2 * nl, axis=1).ravel(), np.tile(vd, (1, 2 * nl)).ravel())),
+                      shape=(2 * ndofs, 2 * ndofs))
+    fixed = np.repeat(primal.dirichlet_mask(mesh, p, mesh.boundary_facets()), 2)
+    return A, np.nonzero(~fixed)[0]
 
 
 def host_matrix(mesh, p):
@@ -109,11 +149,11 @@ def host_matrix(mesh, p):
     return A, np.nonzero(~fixed)[0]
 
 
-def host_figures(mesh, p, b, budget, direct):
+def host_figures(mesh, p, b, budget, direct, elasticity=False):
     import scipy.sparse.linalg as spla
     out = {}
     t0 = time.perf_counter()
-    A, free = host_matrix(mesh, p)
+    A, free = host_matrix_elasticity(mesh, p) if elasticity else host_matrix(mesh, p)
     Aff = A[free][:, free].tocsr()
     bf = b[free]
     out["assemble_s"] = time.perf_counter() - t0
@@ -147,10 +187,12 @@ def host_figures(mesh, p, b, budget, direct):
     return out
 
 
-def run_degree(args, cpp, torch, dm, p, res):
+def run_degree(args, cpp, torch, dm, p, res, elasticity=False):
+    """the figures of one degree; with elasticity the name of the degree is E_p and ndofs counts the 2 ndofs rows"""
     mesh = dm.mesh
-    h, b = make_problem(cpp, torch, dm, p)
-    nbytes, ndofs = product_bytes(mesh, p)
+    bs, P = (2, "E") if elasticity else (1, "P")
+    h, b = make_problem(cpp, torch, dm, p, elasticity)
+    nbytes, ndofs = product_bytes(mesh, p, bs)
     r = dict(ncells=mesh.ncells, ndofs=ndofs, product_bytes=nbytes)
     u = torch.from_numpy(np.random.default_rng(0).standard_normal(ndofs)).cuda()
     y = torch.empty_like(u)
@@ -166,39 +208,43 @@ def run_degree(args, cpp, torch, dm, p, res):
     r["product_ms"] = e0.elapsed_time(e1) / args.products
     r["product_bytes_per_s"] = nbytes / (r["product_ms"] * 1e-3)
     r["product_fraction_of_copy_rate"] = r["product_bytes_per_s"] / HBM_COPY_RATE
-    say(f"P_{p}: {mesh.ncells} cells, {ndofs} DOFs; product {r['product_ms']:.4f} ms over {args.products} products, "
+    say(f"{P}_{p}: {mesh.ncells} cells, {ndofs} DOFs; product {r['product_ms']:.4f} ms over {args.products} products, "
         f"{nbytes / 1e6:.1f} MB -> {r['product_bytes_per_s'] / 1e12:.3f} TB/s = "
         f"{100 * r['product_fraction_of_copy_rate']:.1f} % of the copy rate")
+    if elasticity and f"P{p}" in res:
+        r["product_over_poisson"] = r["product_ms"] / res[f"P{p}"]["product_ms"]
+        say(f"E_{p}: product = {r['product_over_poisson']:.2f} x the Poisson product (expected between 1 and about 2.7: "
+            f"twice the vector data against 8 contractions for 3)")
     zero = torch.zeros(ndofs, dtype=torch.float64, device="cuda")
     timed_solve(torch, h, b, zero, 0.0, 20)   # warm-up
     info, ms, _ = timed_solve(torch, h, b, zero, 0.0, args.iterations)
     r["iteration_ms"] = ms / max(info["iterations"], 1)
-    say(f"P_{p}: PCG iteration {r['iteration_ms']:.4f} ms ({info['iterations']} iterations in {ms:.1f} ms)")
+    say(f"{P}_{p}: PCG iteration {r['iteration_ms']:.4f} ms ({info['iterations']} iterations in {ms:.1f} ms)")
     info, ms, usol = timed_solve(torch, h, b, zero, 1e-8, args.maxit)
     r["zero"] = dict(iterations=info["iterations"], ms=ms, converged=info["converged"],
                      replacements=info["replacements"])
-    say(f"P_{p}: to rtol 1e-8 from zero: {r['zero']}")
+    say(f"{P}_{p}: to rtol 1e-8 from zero: {r['zero']}")
     if args.check_only:
-        res[f"P{p}"] = r
+        res[f"{P}{p}"] = r
         return
     # 2 % refinement on the device, the solution prolonged
     marked = np.random.default_rng(42).choice(mesh.ncells, size=mesh.ncells // 50, replace=False).astype(np.int32)
     ref = dm.refine(np.sort(marked), keep_plan=True)
-    h2, b2 = make_problem(cpp, torch, ref.dmesh, p)
-    u2 = ref.prolong(p, usol).reshape(-1)
+    h2, b2 = make_problem(cpp, torch, ref.dmesh, p, elasticity)
+    u2 = ref.prolong(p, usol, bs=bs).reshape(-1)
     # the prolonged values of the boundary DOFs are the (zero) Dirichlet values of the new mesh
-    zero2 = torch.zeros(h2.ndofs, dtype=torch.float64, device="cuda")
+    zero2 = torch.zeros(bs * h2.ndofs, dtype=torch.float64, device="cuda")
     i0, ms0, _ = timed_solve(torch, h2, b2, zero2, 1e-8, args.maxit)
     i1, ms1, _ = timed_solve(torch, h2, b2, u2, 1e-8, args.maxit)
-    r["refined"] = dict(ncells=ref.dmesh.mesh.ncells, ndofs=h2.ndofs,
+    r["refined"] = dict(ncells=ref.dmesh.mesh.ncells, ndofs=bs * h2.ndofs,
                         zero=dict(iterations=i0["iterations"], ms=ms0, converged=i0["converged"]),
                         prolonged=dict(iterations=i1["iterations"], ms=ms1, converged=i1["converged"]))
-    say(f"P_{p}: refined at 2 % ({r['refined']['ncells']} cells): from zero {r['refined']['zero']}, "
+    say(f"{P}_{p}: refined at 2 % ({r['refined']['ncells']} cells): from zero {r['refined']['zero']}, "
         f"from the prolonged solution {r['refined']['prolonged']}")
     ref.close()
     if args.host:
-        r["host"] = host_figures(mesh, p, b.cpu().numpy(), args.host_budget, p in args.spsolve_degrees)
-    res[f"P{p}"] = r
+        r["host"] = host_figures(mesh, p, b.cpu().numpy(), args.host_budget, p in args.spsolve_degrees, elasticity)
+    res[f"{P}{p}"] = r
 
 
 def main():
@@ -212,6 +258,7 @@ def main():
     ap.add_argument("--host-budget", type=float, default=150.0, help="seconds for the host cg")
     ap.add_argument("--spsolve-degrees", type=int, nargs="*", default=[1],
                     help="degrees at which --host also runs spsolve (P_2 at 1M triangles takes minutes and many GB)")
+    ap.add_argument("--elasticity", action="store_true", help="the same figures for cpp.PrimalElasticity as well")
     ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
     ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -243,6 +290,9 @@ def main():
     say(f"mesh: {dm.mesh.ncells} cells in {time.perf_counter() - t0:.1f} s")
     for p in args.degrees:
         run_degree(args, cpp, torch, dm, p, res)
+    if args.elasticity and not args.check_only:
+        for p in args.degrees:
+            run_degree(args, cpp, torch, dm, p, res, elasticity=True)
     print(json.dumps(res))
 
 
