@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_get_cross_table", "eqlb_elasticity_create", "eqlb_elasticity_destroy", "eqlb_elasticity_ndofs",
     "eqlb_elasticity_set_dirichlet", "eqlb_elasticity_load", "eqlb_elasticity_apply", "eqlb_elasticity_diagonal",
     "eqlb_elasticity_residual", "eqlb_elasticity_solve",
+    "eqlb_hierarchy_create", "eqlb_hierarchy_destroy", "eqlb_hierarchy_restrict", "eqlb_hierarchy_precondition",
+    "eqlb_hierarchy_solve",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -185,7 +187,7 @@ def lib():
         for name in ("eqlb_mesh_destroy", "eqlb_se_destroy", "eqlb_ev_destroy", "eqlb_halo_destroy",
                      "eqlb_rccl_comm_destroy"):
             getattr(L, name).restype = None
-        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy", "eqlb_elasticity_destroy"):
+        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy", "eqlb_elasticity_destroy", "eqlb_hierarchy_destroy"):
             if hasattr(L, name):   # (a library of an earlier revision, EQLB_AMD_LIB: A/B runs of bench.py)
                 getattr(L, name).restype = None
         _lib = L
@@ -1609,6 +1611,96 @@ class PrimalElasticity:
     def close(self):
         if self._h:
             lib().eqlb_elasticity_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Multilevel:
+    """eqlb_hierarchy_t: the multilevel preconditioner (additive multilevel diagonal scaling, BPX) of the P_p solves over
+    the levels of an adaptive loop, and the CG of the finest handle with it (lsolver.multilevel.Hierarchy is the numpy
+    statement).  solvers: PrimalPoisson handles, or PrimalElasticity handles, coarsest first, all of one p;
+    refinements[l]: the Refinement of DeviceMesh.refine(..., keep_plan=True) from the mesh of solvers[l] to that of
+    solvers[l + 1].  Everything is borrowed (and kept alive here); masks and diagonals are read when a call runs, so
+    set_dirichlet on a level takes effect at the next call.  One level is plain Jacobi.  The methods take and return host
+    arrays; the `_raw` variants take raw pointers (ints) in `memspace`, ordered on `stream`.  The calls use the work
+    space of the solver handles: one stream, one call after the other."""
+
+    def __init__(self, solvers, refinements, stream=0):
+        self.solvers, self.refinements = list(solvers), list(refinements)
+        self._h = C.c_void_p()
+        n = len(self.solvers)
+        if n < 1 or len(self.refinements) != n - 1:
+            raise RuntimeError("Multilevel: one Refinement per pair of neighbouring levels expected")
+        el = [isinstance(s, PrimalElasticity) for s in self.solvers]
+        if any(el) != all(el) or not all(isinstance(s, (PrimalPoisson, PrimalElasticity)) for s in self.solvers):
+            raise RuntimeError("Multilevel: PrimalPoisson handles or PrimalElasticity handles expected, not a mixture")
+        self.bs = 2 if el[0] else 1
+        plans = [r._kept_plan("Multilevel") for r in self.refinements]
+        self.nrows = [self.bs * s.ndofs for s in self.solvers]
+        sv = (C.c_void_p * n)(*[s._h.value for s in self.solvers])
+        ms = (C.c_void_p * n)(*[s.dmesh._h.value for s in self.solvers])
+        pl = (C.c_void_p * max(n - 1, 1))(*[q._h.value for q in plans])
+        _check(lib().eqlb_hierarchy_create(C.c_int32(n), C.c_int32(self.bs), sv, pl, ms, C.c_void_p(stream),
+                                           C.byref(self._h)))
+
+    @property
+    def nlevels(self):
+        return len(self.solvers)
+
+    def _vec(self, a, level):
+        v = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if v.size != self.nrows[level]:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        return v
+
+    def restrict(self, level, r, masked=True, stream=0):
+        """r of level + 1 -> P^T r of `level` (the transpose of Refinement.prolong); masked: 0 on the fixed rows of
+        `level`."""
+        ok = 0 <= level < self.nlevels - 1
+        rr = self._vec(r, level + 1) if ok else np.ascontiguousarray(r, dtype=np.float64).ravel()
+        out = np.zeros(self.nrows[level] if ok else 1)
+        self.restrict_raw(level, rr.ctypes.data, out.ctypes.data, masked, MEM_HOST, stream)
+        return out
+
+    def restrict_raw(self, level, r_fine, r_coarse, masked=True, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_hierarchy_restrict(self._h, C.c_int32(level), _vp(r_fine), _vp(r_coarse),
+                                             C.c_int32(1 if masked else 0), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def precondition(self, r, stream=0):
+        """z = M r on the finest level."""
+        rr, z = self._vec(r, -1), np.zeros(self.nrows[-1])
+        self.precondition_raw(rr.ctypes.data, z.ctypes.data, MEM_HOST, stream)
+        return z
+
+    def precondition_raw(self, r, z, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_hierarchy_precondition(self._h, _vp(r), _vp(z), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def solve(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
+        """The CG of the finest handle with the multilevel preconditioner, from the start u (its fixed rows hold the
+        Dirichlet values).  Returns (u, info) as PrimalPoisson.solve; breakdown also reports r . z <= 0."""
+        bb = self._vec(b, -1)
+        uu = self._vec(u, -1).copy()
+        info = self.solve_raw(bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
+        return uu, info
+
+    def solve_raw(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
+        """eqlb_hierarchy_solve on raw pointers: u is overwritten by the solution; waits for the device; returns info."""
+        v = (C.c_double * 8)()
+        _check(lib().eqlb_hierarchy_solve(self._h, _vp(b), _vp(u), C.c_double(rtol), C.c_double(atol), C.c_int32(maxit),
+                                          v, C.c_int32(memspace), C.c_void_p(stream)))
+        info = dict(zip(PRIMAL_INFO, [float(x) for x in v]))
+        for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
+            info[key] = int(info[key])
+        return info
+
+    def close(self):
+        if self._h:
+            lib().eqlb_hierarchy_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -319,4 +319,42 @@ int fill_tables_host(int k, int deg, std::vector<double>& out);
 } // namespace eqlb
 
 struct eqlb_mesh; // the handle behind eqlb_mesh_t: eqlb_mesh_handle.h (host code only)
+struct eqlb_refine; // the plan behind eqlb_refine_t: eqlb_refine_plan.h (host code only)
+struct eqlb_primal; // the solver handles: eqlb_primal_solve.hip, eqlb_primal_elasticity.hip
+struct eqlb_elasticity;
+
+namespace eqlb
+{
+// A solver handle (eqlb_primal_t, bs = 1; eqlb_elasticity_t, bs = 2) as the hierarchy unit eqlb_multilevel.hip sees it:
+// a view that owns nothing.  All pointers DEVICE; vectors have bs * ndofs rows.  The launches are those of the handle's
+// own unit, on its own kernels.
+struct SolverLevel
+{
+  void* handle;
+  eqlb_mesh* mesh;
+  int p, bs;
+  int64_t ndofs;            // scalar count
+  const int32_t* cell_dofs; // [ncells][nd_p]
+  const double* diag;
+  const uint8_t* fixed;
+  const int32_t* status;    // [4] the status word of the mask (skipped ids, listed valid ones per component)
+  double* yloc;             // [ncells][nd_p][bs]: the input of the owner sum
+  double *r, *z, *d, *q, *part; // the vectors and block partials of the handle's CG
+  void* st;                 // its PcgState
+  // y = owner sum of yloc (0 on the fixed rows if masked); st: nullptr, or a PcgState whose stop flag skips the launch
+  hipError_t (*owner_sum)(void* handle, double* y, bool masked, const void* st, hipStream_t stream);
+  // r = b - A u (0 on the fixed rows; u^ instead of u with only_fixed), the block partials of r.r in part
+  hipError_t (*residual)(void* handle, const double* b, const double* u, double* r, bool only_fixed, hipStream_t stream);
+  // q = A d on the free rows, the block partials of d.q in part; returns at once when st says done
+  hipError_t (*product)(void* handle, hipStream_t stream);
+};
+void primal_level(eqlb_primal* h, SolverLevel& v);
+void elasticity_level(eqlb_elasticity* h, SolverLevel& v);
+// eqlb_transfer.hip: the store pass of the restriction r = P^T r2 from `refined` to the mesh of `plan`, into
+// yloc [ncells][nd_p][bs]; DEVICE pointers, one launch, nothing waits.  done: nullptr, or a flag in device memory that
+// makes the kernel return at once when set
+int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const int32_t* cell_dofs2,
+                    int64_t ndofs2, const double* r2, double* yloc, const int32_t* done, hipStream_t stream);
+} // namespace eqlb
+
 struct eqlb_se; // the handle behind eqlb_se_t / eqlb_ev_t: eqlb_handle.h (host code only)

@@ -1,12 +1,14 @@
 // What the P_p Poisson solve (eqlb_primal_solve.hip) and the P_p^2 elasticity solve (eqlb_primal_elasticity.hip) share:
 // the sum pass of the store-and-sum operator, the vector kernels and the scalar kernel of the Jacobi-preconditioned CG,
 // and the host loop that drives them.  Everything lies in an unnamed namespace: each unit gets its own copy, under the
-// names the kernels had while they lived in eqlb_primal_solve.hip.
+// names the kernels had while they lived in eqlb_primal_solve.hip.  The hierarchy unit (eqlb_multilevel.hip) takes the
+// state, the scalar and direction kernels and the host loop from here and brings its own preconditioner steps.
 //  k_primal_slots    builds the slot lists of the sum pass once at create (scalar numbering: both problems use it)
 //  k_primal_gather<BS>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
 //                    x[BS * dof + r].  BS = 1 is the kernel of the Poisson unit, instruction for instruction
 //  k_pcg_*           work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
-//  pcg_solve         the host side of the iteration on a PcgWork
+//  pcg_solve         the host side of the iteration on a PcgWork; the preconditioner enters through its `steps`
+//                    (JacobiSteps here; the hierarchy unit eqlb_multilevel.hip brings its own)
 #pragma once
 
 #include "eqlb_device_common.h"
@@ -360,14 +362,37 @@ inline hipError_t launch_scalar(const PcgWork& w, int step, double rtol, double 
   return hipGetLastError();
 }
 
-// The Jacobi-preconditioned CG of eqlb_primal_solve / eqlb_elasticity_solve behind their argument checks.
+// The two places where the preconditioner enters the iteration, for z = r / diag: both kernels fuse it
+struct JacobiSteps
+{
+  static constexpr int check_every = PRIMAL_CHECK_EVERY; // iterations between two reads of the state by the host
+  const PcgWork& w;
+  hipStream_t stream;
+  // z from the r of the start or of a replacement, the partials of r.r and r.z, the scalar step (STEP_START / _REPLACE)
+  hipError_t restart(int step, double rtol, double atol) const
+  {
+    hipLaunchKernelGGL(k_pcg_precond, dim3(stream_blocks(w.n)), dim3(PS_THREADS), 0, stream, w.n, w.r, w.diag, w.fixed,
+                       w.z, w.part);
+    return launch_scalar(w, step, rtol, atol, nullptr, stream);
+  }
+  // u += alpha d, r -= alpha q, z from the new r, the partials of r.r and r.z, STEP_BETA
+  hipError_t advance(double* pu, double rtol, double atol) const
+  {
+    hipLaunchKernelGGL(k_pcg_update, dim3(stream_blocks(w.n)), dim3(PS_THREADS), 0, stream, w.n, w.st, w.d, w.q, w.diag,
+                       w.fixed, pu, w.r, w.z, w.part);
+    return launch_scalar(w, STEP_BETA, rtol, atol, nullptr, stream);
+  }
+};
+
+// The preconditioned CG of eqlb_primal_solve / eqlb_elasticity_solve / eqlb_hierarchy_solve behind their argument checks.
 //   residual(b, u, r, only_fixed)  enqueues r = b - A u (0 on the fixed rows; u^ instead of u with only_fixed) and
 //                                  leaves the block partials of r.r in w.part
 //   product(st)                    enqueues q = A d on the free rows with the block partials of d.q in w.part
+//   steps                          the preconditioner: restart(step, rtol, atol) and advance(u, rtol, atol) as JacobiSteps
 // skipped: the facet ids the mask skipped (info[7]).  b, u in host memory with `host` are staged here.
-template <class Residual, class Product>
-int pcg_solve(const PcgWork& w, Residual&& residual, Product&& product, const double* b, double* u, double rtol,
-              double atol, int32_t maxit, double* info, int32_t skipped, bool host, hipStream_t stream)
+template <class Residual, class Product, class Steps>
+int pcg_solve(const PcgWork& w, Residual&& residual, Product&& product, const Steps& steps, const double* b, double* u,
+              double rtol, double atol, int32_t maxit, double* info, int32_t skipped, bool host, hipStream_t stream)
 {
   const size_t n = (size_t)w.n;
   HostCall s;
@@ -395,10 +420,9 @@ int pcg_solve(const PcgWork& w, Residual&& residual, Product&& product, const do
   // nb and tol from u^
   s.note(residual(pb, pu, w.q, true));
   s.note(launch_scalar(w, STEP_NB, rtol, atol, nullptr, stream));
-  // the start: r = b - A u, z = r / diag, rho, p = z
+  // the start: r = b - A u, z from r, rho, p = z
   s.note(residual(pb, pu, w.r, false));
-  hipLaunchKernelGGL(k_pcg_precond, grid, block, 0, stream, nn, w.r, w.diag, w.fixed, w.z, w.part);
-  s.note(launch_scalar(w, STEP_START, rtol, atol, nullptr, stream));
+  s.note(steps.restart(STEP_START, rtol, atol));
   hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 1, w.z, w.d);
   s.note(hipGetLastError());
   s.note(read_state());
@@ -425,22 +449,19 @@ int pcg_solve(const PcgWork& w, Residual&& residual, Product&& product, const do
         if (hs.converged || hs.iters >= maxit)
           break;
         s.note(hipMemcpyAsync(w.r, w.q, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(k_pcg_precond, grid, block, 0, stream, nn, w.r, w.diag, w.fixed, w.z, w.part);
-        s.note(launch_scalar(w, STEP_REPLACE, rtol, atol, nullptr, stream));
+        s.note(steps.restart(STEP_REPLACE, rtol, atol));
         hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 0, w.z, w.d);
         s.note(hipGetLastError());
         have_true = false;
       }
       if (hs.iters >= maxit)
         break;
-      const int batch = (maxit - hs.iters < PRIMAL_CHECK_EVERY) ? maxit - hs.iters : PRIMAL_CHECK_EVERY;
+      const int batch = (maxit - hs.iters < Steps::check_every) ? maxit - hs.iters : Steps::check_every;
       for (int it = 0; it < batch; ++it)
       {
         s.note(product(st));
         s.note(launch_scalar(w, STEP_ALPHA, rtol, atol, nullptr, stream));
-        hipLaunchKernelGGL(k_pcg_update, grid, block, 0, stream, nn, st, w.d, w.q, w.diag, w.fixed, pu, w.r, w.z,
-                           w.part);
-        s.note(launch_scalar(w, STEP_BETA, rtol, atol, nullptr, stream));
+        s.note(steps.advance(pu, rtol, atol));
         hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 0, w.z, w.d);
         s.note(hipGetLastError());
       }

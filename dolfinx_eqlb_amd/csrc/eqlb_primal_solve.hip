@@ -308,6 +308,19 @@ hipError_t enqueue_residual(const eqlb_primal& h, const double* b, const double*
   return launch_gather(h, g, stream);
 }
 
+// q = A d on the free rows (the direction d of the handle), the block partials of d.q in h.part
+hipError_t enqueue_product(const eqlb_primal& h, const PcgState* st, hipStream_t stream)
+{
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, h.d, false, st), stream);
+  if (e != hipSuccess)
+    return e;
+  GatherArgs g = gather_args(h, true, st);
+  g.y = h.q;
+  g.w = h.d;
+  g.dot = DOT_W_Y;
+  return launch_gather(h, g, stream);
+}
+
 int check_handle(const char* who, const eqlb_primal* h)
 {
   if (!h)
@@ -315,6 +328,37 @@ int check_handle(const char* who, const eqlb_primal* h)
   return EQLB_OK;
 }
 } // namespace
+
+// the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
+void primal_level(eqlb_primal* h, SolverLevel& v)
+{
+  v = SolverLevel{};
+  v.handle = h;
+  v.mesh = h->mesh;
+  v.p = h->p;
+  v.bs = 1;
+  v.ndofs = h->ndofs;
+  v.cell_dofs = h->cell_dofs;
+  v.diag = h->diag;
+  v.fixed = h->fixed;
+  v.status = h->status;
+  v.yloc = h->yloc;
+  v.r = h->r, v.z = h->z, v.d = h->d, v.q = h->q, v.part = h->part;
+  v.st = h->st.get();
+  v.owner_sum = [](void* hh, double* y, bool masked, const void* st, hipStream_t stream) {
+    const eqlb_primal& s = *static_cast<eqlb_primal*>(hh);
+    GatherArgs g = gather_args(s, masked, static_cast<const PcgState*>(st));
+    g.y = y;
+    return launch_gather(s, g, stream);
+  };
+  v.residual = [](void* hh, const double* b, const double* u, double* r, bool only_fixed, hipStream_t stream) {
+    return enqueue_residual(*static_cast<eqlb_primal*>(hh), b, u, r, only_fixed, stream);
+  };
+  v.product = [](void* hh, hipStream_t stream) {
+    const eqlb_primal& s = *static_cast<eqlb_primal*>(hh);
+    return enqueue_product(s, s.st.get(), stream);
+  };
+}
 } // namespace eqlb
 
 extern "C" {
@@ -617,17 +661,9 @@ try
   auto residual = [&](const double* pb, const double* pu, double* r, bool only_fixed) {
     return enqueue_residual(*h, pb, pu, r, only_fixed, stream);
   };
-  auto product = [&](const PcgState* st) {
-    const hipError_t e = launch_cell<CELL_OPERATOR>(h->p, 0, cell_args(*h, h->d, false, st), stream);
-    if (e != hipSuccess)
-      return e;
-    GatherArgs g = gather_args(*h, true, st);
-    g.y = h->q;
-    g.w = h->d;
-    g.dot = DOT_W_Y;
-    return launch_gather(*h, g, stream);
-  };
-  return pcg_solve(pcg_work(*h), residual, product, b, u, rtol, atol, maxit, info, status[0],
+  auto product = [&](const PcgState* st) { return enqueue_product(*h, st, stream); };
+  const PcgWork w = pcg_work(*h);
+  return pcg_solve(w, residual, product, JacobiSteps{w, stream}, b, u, rtol, atol, maxit, info, status[0],
                    memspace == EQLB_MEM_HOST, stream);
 }
 EQLB_CATCH_ALL

@@ -228,6 +228,105 @@ __global__ void __launch_bounds__(TR_THREADS) k_prolong(const ProlongArgs a)
   }
 }
 
+// The store pass of r = P^T r2, the transpose of k_prolong<Q, false> (include/eqlb.h: eqlb_hierarchy_restrict; the numpy
+// statement: mesh/transfer.py: restrict_lagrange): one thread per PARENT cell, which walks its 1 ... 4 children and,
+// within a child, the local DOFs that child owns - the owner test of k_prolong, so every fine DOF is taken once - and
+// adds PT[row][i] * r2[dof2] to its ND x BS sums in registers; the sums go to the row of y_loc [ncells][ND][BS] the
+// cell owns, with plain stores.  The owner sum of the coarse solver handle adds the rows up: no atomics anywhere.
+// The table is staged in LDS as in k_prolong (the rows differ from lane to lane); the loop over the local DOFs is not
+// unrolled (the row, the index and the owner bit of DOF n are looked up, the ND sums stay in registers).  a.in = r2,
+// a.out = y_loc, a.cell_dofs2 / a.ndofs2 the fine dofmap; a bad index or a child that is no child of its parent makes
+// the row of the cell NaN.  done: nullptr, or the stop flag of a CG in device memory - set, the kernel returns at once.
+template <int Q, int BS>
+__global__ void __launch_bounds__(TR_THREADS) k_restrict(const ProlongArgs a, const int32_t* __restrict__ done)
+{
+#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
+  using T = eqlb_tables::Prolong<Q>;
+  constexpr int ND = nd_of(Q), NROW = T::NROW;
+  static constexpr DofNum<Q> num{}; // (indexed by a run-time n: a table in constant memory, not a private copy)
+  static_assert(T::ND == ND && NROW == (2 * Q + 1) * (Q + 1), "table shape");
+  __shared__ double sT[NROW * ND];
+  if (done && *done) // (inside a batch of CG iterations whose stop flag is set: nothing reads the result)
+    return;
+  for (int i = threadIdx.x; i < NROW * ND; i += TR_THREADS)
+    sT[i] = T::PT[i];
+  __syncthreads();
+  const int32_t c = blockIdx.x * TR_THREADS + threadIdx.x;
+  if (c >= a.ncells)
+    return;
+  const int32_t v[3] = {a.cell_nodes[3 * (int64_t)c], a.cell_nodes[3 * (int64_t)c + 1], a.cell_nodes[3 * (int64_t)c + 2]};
+  const int64_t first = a.coff[c];
+  const int nchild = (int)(a.coff[c + 1] - a.coff[c]); // 1 ... 4
+  double acc[ND][BS];
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int b = 0; b < BS; ++b)
+      acc[i][b] = 0.0;
+  bool started = false, good = true;
+  for (int k = 0; k < nchild; ++k)
+  {
+    const int64_t c2 = first + k;
+    const int32_t w[3] = {a.cell_nodes2[3 * c2], a.cell_nodes2[3 * c2 + 1], a.cell_nodes2[3 * c2 + 2]};
+    int hx[3], hy[3];
+    const bool found = child_positions(a, v, w, hx, hy);
+    good = good && found;
+    // bit n: the child owns its local DOF n (interior DOFs: always)
+    uint32_t own = ~0u << (3 * Q);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      own |= (a.node_cells2[a.node_cells_off2[w[j]]] == c2) ? (1u << j) : 0u;
+    if constexpr (Q > 1)
+    {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+      {
+        const int32_t f = a.cell_facets2[3 * c2 + j];
+        const uint32_t bits = ((1u << (Q - 1)) - 1u) << (3 + j * (Q - 1));
+        own |= (a.facet_cells2[a.facet_cells_off2[f]] == c2) ? bits : 0u;
+      }
+    }
+#pragma unroll 1
+    for (int n = 0; n < ND; ++n)
+    {
+      if (!((own >> n) & 1u))
+        continue;
+      const int32_t d2 = a.cell_dofs2[c2 * ND + n];
+      if (d2 < 0 || (int64_t)d2 >= a.ndofs2)
+      {
+        good = false;
+        continue;
+      }
+      const int lx = Q * hx[0] + num.a[n] * (hx[1] - hx[0]) + num.b[n] * (hx[2] - hx[0]);
+      const int ly = Q * hy[0] + num.a[n] * (hy[1] - hy[0]) + num.b[n] * (hy[2] - hy[0]);
+      const double* t = sT + (found ? ly * (2 * Q + 1) - ly * (ly - 1) / 2 + lx : 0) * ND;
+      double rv[BS];
+#pragma unroll
+      for (int b = 0; b < BS; ++b)
+        rv[b] = a.in[(int64_t)d2 * BS + b];
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+      {
+        const double ti = t[i];
+#pragma unroll
+        for (int b = 0; b < BS; ++b)
+        {
+          const double term = ti * rv[b];
+          acc[i][b] = started ? acc[i][b] + term : term;
+        }
+      }
+      started = true;
+    }
+  }
+  const double bad = __longlong_as_double(0x7ff8000000000000ll);
+  double* o = a.out + (int64_t)c * ND * BS;
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int b = 0; b < BS; ++b)
+      o[i * BS + b] = good ? acc[i][b] : bad;
+}
+
 // DG_0: every child takes the value of its parent
 __global__ void __launch_bounds__(TR_THREADS) k_prolong_dg0(const ProlongArgs a)
 {
@@ -331,6 +430,40 @@ int check_dofmap(const char* who, const char* name, const int32_t* cd, size_t nc
   return EQLB_OK;
 }
 } // namespace
+
+// the store pass of the restriction for the hierarchy unit (eqlb_multilevel.hip): DEVICE pointers, one launch
+int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const int32_t* cell_dofs2,
+                    int64_t ndofs2, const double* r2, double* yloc, const int32_t* done, hipStream_t stream)
+{
+  if (p < 1 || p > TR_PMAX || (bs != 1 && bs != 2))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4, or bs = %d not 1 or 2", who, p, bs);
+  ProlongArgs a;
+  EQLB_TRY(common_args(who, plan, refined, bs, 1, EQLB_MEM_DEVICE, a));
+  if (mesh_node_cells(refined, &a.node_cells2))
+    return EQLB_ERR_DEVICE;
+  a.cell_dofs2 = cell_dofs2;
+  a.ndofs2 = ndofs2;
+  a.in = r2;
+  a.out = yloc;
+  const dim3 grid(grid_of(a.ncells, TR_THREADS)), block(TR_THREADS);
+#define EQLB_RESTRICT_CASE(QQ)                                                                                         \
+  case QQ:                                                                                                             \
+    if (bs == 1)                                                                                                       \
+      hipLaunchKernelGGL((k_restrict<QQ, 1>), grid, block, 0, stream, a, done);                                        \
+    else                                                                                                               \
+      hipLaunchKernelGGL((k_restrict<QQ, 2>), grid, block, 0, stream, a, done);                                        \
+    break;
+  switch (p)
+  {
+    EQLB_RESTRICT_CASE(1)
+    EQLB_RESTRICT_CASE(2)
+    EQLB_RESTRICT_CASE(3)
+    EQLB_RESTRICT_CASE(4)
+  }
+#undef EQLB_RESTRICT_CASE
+  HIP_TRY(hipGetLastError());
+  return EQLB_OK;
+}
 } // namespace eqlb
 
 extern "C" {

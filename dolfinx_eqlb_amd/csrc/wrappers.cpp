@@ -471,6 +471,85 @@ struct PrimalElasticity
   }
 };
 
+// The multilevel preconditioner over the levels of an adaptive loop (eqlb_hierarchy_*), on host arrays: solvers coarsest
+// first, all PrimalPoisson or all PrimalElasticity; transfers[l] the Transfer of Mesh.refine(..., keep_plan=True) from
+// the mesh of solvers[l] to that of solvers[l + 1]
+struct Multilevel
+{
+  eqlb_hierarchy_t* h = nullptr;
+  py::list keep_solvers, keep_transfers; // everything is borrowed: it stays alive with the carrier
+  int bs = 1, nlevels = 0;
+  std::vector<int64_t> n;                // rows of a vector per level
+
+  Multilevel(py::list solvers, py::list transfers) : keep_solvers(solvers), keep_transfers(transfers)
+  {
+    nlevels = (int)py::len(solvers);
+    if (nlevels < 1 || (int)py::len(transfers) != nlevels - 1)
+      throw std::runtime_error("Multilevel: one Transfer per pair of neighbouring levels expected");
+    const bool el = py::isinstance<PrimalElasticity>(solvers[0]);
+    bs = el ? 2 : 1;
+    std::vector<void*> sv;
+    std::vector<eqlb_mesh_t*> ms;
+    std::vector<eqlb_refine_t*> pl;
+    for (int l = 0; l < nlevels; ++l)
+    {
+      if (el)
+      {
+        auto s = solvers[l].cast<std::shared_ptr<PrimalElasticity>>();
+        sv.push_back(s->h), ms.push_back(s->mesh->h), n.push_back(2 * s->ndofs);
+      }
+      else
+      {
+        auto s = solvers[l].cast<std::shared_ptr<PrimalPoisson>>();
+        sv.push_back(s->h), ms.push_back(s->mesh->h), n.push_back(s->ndofs);
+      }
+      if (l < nlevels - 1)
+        pl.push_back(transfers[l].cast<std::shared_ptr<Transfer>>()->plan);
+    }
+    check(eqlb_hierarchy_create(nlevels, bs, sv.data(), pl.data(), ms.data(), nullptr, &h));
+  }
+  ~Multilevel() { eqlb_hierarchy_destroy(h); }
+  Multilevel(const Multilevel&) = delete;
+  Multilevel& operator=(const Multilevel&) = delete;
+
+  // level + 1 -> level
+  darray restrict(int level, darray r, bool masked) const
+  {
+    if (level >= 0 && level < nlevels - 1 && r.size() != n[level + 1])
+      throw std::runtime_error("Multilevel.restrict: Input sizes does not match");
+    darray out((py::ssize_t)(level >= 0 && level < nlevels - 1 ? n[level] : 1));
+    check(eqlb_hierarchy_restrict(h, level, r.data(), out.mutable_data(), masked ? 1 : 0, EQLB_MEM_HOST, nullptr));
+    return out;
+  }
+  darray precondition(darray r) const
+  {
+    if (r.size() != n.back())
+      throw std::runtime_error("Multilevel.precondition: Input sizes does not match");
+    darray z((py::ssize_t)n.back());
+    check(eqlb_hierarchy_precondition(h, r.data(), z.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return z;
+  }
+  py::tuple solve(darray b, darray u, double rtol, double atol, int maxit) const
+  {
+    if (b.size() != n.back() || u.size() != n.back())
+      throw std::runtime_error("Multilevel.solve: Input sizes does not match");
+    darray x((py::ssize_t)n.back());
+    std::copy(u.data(), u.data() + n.back(), x.mutable_data());
+    double v[8] = {};
+    check(eqlb_hierarchy_solve(h, b.data(), x.mutable_data(), rtol, atol, maxit, v, EQLB_MEM_HOST, nullptr));
+    py::dict info;
+    info["iterations"] = (int64_t)v[0];
+    info["converged"] = (int64_t)v[1];
+    info["nb"] = v[2];
+    info["rnorm"] = v[3];
+    info["replacements"] = (int64_t)v[4];
+    info["breakdown"] = (int64_t)v[5];
+    info["tol"] = v[6];
+    info["facets_skipped"] = (int64_t)v[7];
+    return py::make_tuple(x, info);
+  }
+};
+
 py::tuple Mesh::refine(std::shared_ptr<Mesh> self, carray<int32_t> marked, bool keep_plan)
 {
   std::shared_ptr<Transfer> tr(new Transfer());
@@ -1337,6 +1416,19 @@ PYBIND11_MODULE(_cpp, m)
       .def_readonly("mesh", &PrimalElasticity::mesh)
       .def_readonly("p", &PrimalElasticity::p)
       .def_readonly("ndofs", &PrimalElasticity::ndofs);
+
+  py::class_<Multilevel, std::shared_ptr<Multilevel>>(
+      m, "Multilevel", "Multilevel preconditioner (BPX) over the levels of an adaptive loop: solvers coarsest first (all "
+                       "PrimalPoisson or all PrimalElasticity), transfers[l] the Transfer of Mesh.refine(..., "
+                       "keep_plan=True) between level l and l + 1 (eqlb_hierarchy_*)")
+      .def(py::init<py::list, py::list>(), py::arg("solvers"), py::arg("transfers"))
+      .def("restrict", &Multilevel::restrict, py::arg("level"), py::arg("r"), py::arg("masked") = true,
+           "r [level + 1] -> P^T r [level]; masked: 0 on the fixed rows of the coarse level")
+      .def("precondition", &Multilevel::precondition, py::arg("r"), "z = M r on the finest level")
+      .def("solve", &Multilevel::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
+           py::arg("maxit") = 10000, "(u, info): the CG of the finest solver with the multilevel preconditioner")
+      .def_readonly("nlevels", &Multilevel::nlevels)
+      .def_readonly("bs", &Multilevel::bs);
 
   py::class_<FunctionSpace, std::shared_ptr<FunctionSpace>>(m, "FunctionSpace")
       .def(py::init<std::shared_ptr<Mesh>, std::string, int, int, bool>(), py::arg("mesh"), py::arg("family"),

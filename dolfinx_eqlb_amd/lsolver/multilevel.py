@@ -1,0 +1,148 @@
+"""The multilevel preconditioner of the P_p solves over a hierarchy of refined meshes - the statement of the rule.
+
+The Jacobi-preconditioned CG of lsolver/primal.py needs O(1/h) iterations.  With the levels an adaptive loop leaves
+behind (DeviceMesh.refine(..., keep_plan=True)), the additive multilevel diagonal scaling (BPX)
+
+    z = sum_l  P_L ... P_{l+1}  D_l^-1  P_{l+1}^T ... P_L^T  r
+
+brings that down to a count that hardly grows with the level: P_{l+1} the prolongation from level l to level l + 1
+(mesh.transfer.prolong_lagrange), D_l the diagonal of the operator of level l.  It is symmetric positive definite on the
+free rows by construction, has no damping parameter and needs no operator product.  This file defines, in numpy, what
+the device path (eqlb_hierarchy_* of include/eqlb.h, csrc/eqlb_multilevel.hip) computes; restrict and precondition are
+reproduced bit for bit, because nothing in them reduces across threads except owner sums.
+
+  levels     ops[0] ... ops[L]: PoissonOperator or ElasticityOperator of lsolver/primal.py, coarsest first, with their
+             masks (set_dirichlet); links[l] = (parent_cell, node_parent_facet) of the refinement ops[l].mesh ->
+             ops[l + 1].mesh (or any object with these two attributes, such as cpp.Refinement)
+  restrict   mesh.transfer.restrict_lagrange with the owner sum of the coarse operator, masked at the coarse level
+  down       r_L = r with the fixed rows set to 0;  r_l = restrict(r_{l+1})
+  coarsest   z_0 = r_0 / diag_0 on the free rows, 0 elsewhere
+  up         z_{l+1} = prolong(z_l) + r_{l+1} / diag_{l+1} on the free rows of level l + 1, 0 on its fixed rows: the
+             quotient and the sum are rounded singly
+  pcg        PoissonOperator.pcg with z = precondition(r) in the place of z = r / diag: the same start, the same
+             reference norm, the true residual decides, replacement.  One more breakdown: r . z <= 0 (or NaN)
+
+One level is plain Jacobi.
+"""
+
+import numpy as np
+
+from ..mesh.transfer import prolong_lagrange, restrict_lagrange
+from .primal import PoissonOperator
+
+
+class Hierarchy:
+    """Hierarchy(ops, links): the statements on a hierarchy of levels, coarsest first."""
+
+    def __init__(self, ops, links):
+        ops, links = list(ops), list(links)
+        if len(ops) < 1 or len(links) != len(ops) - 1:
+            raise ValueError("Hierarchy: one link per pair of neighbouring levels expected")
+        if any(o.p != ops[0].p for o in ops):
+            raise ValueError("Hierarchy: levels of different p")
+        self.ops, self.p = ops, ops[0].p
+        self.bs = ops[0].fixed.size // ops[0].ndofs
+        self.links = [(lk.parent_cell, lk.node_parent_facet) if hasattr(lk, "parent_cell") else tuple(lk)
+                      for lk in links]
+        self.links = [(np.asarray(pc), np.asarray(npf)) for pc, npf in self.links]
+        for l, (pc, _) in enumerate(self.links):
+            if pc.size != ops[l + 1].mesh.ncells:
+                raise ValueError(f"Hierarchy: link {l} does not fit the mesh of level {l + 1}")
+        self._diag = [None] * len(ops)
+
+    @property
+    def nlevels(self):
+        return len(self.ops)
+
+    def diag(self, level):
+        if self._diag[level] is None:
+            self._diag[level] = self.ops[level].diagonal()
+        return self._diag[level]
+
+    def restrict(self, level, r_fine, masked=True, return_abs=False):
+        """level + 1 -> level."""
+        if level < 0 or level >= self.nlevels - 1:
+            raise ValueError(f"Hierarchy.restrict: level = {level} outside 0 ... {self.nlevels - 2}")
+        lo, hi = self.ops[level], self.ops[level + 1]
+        pc, npf = self.links[level]
+        return restrict_lagrange(lo.mesh, hi.mesh, pc, npf, self.p, r_fine, bs=self.bs,
+                                 fixed=lo.fixed if masked else None, return_abs=return_abs, op=lo)
+
+    def prolong(self, level, z):
+        """level -> level + 1."""
+        lo, hi = self.ops[level], self.ops[level + 1]
+        pc, npf = self.links[level]
+        return prolong_lagrange(lo.mesh, hi.mesh, pc, npf, self.p, z, bs=self.bs)
+
+    def precondition(self, r):
+        L = self.nlevels - 1
+        rs = [None] * (L + 1)
+        rs[L] = np.where(self.ops[L].fixed, 0.0, np.asarray(r, dtype=np.float64))
+        for l in range(L - 1, -1, -1):
+            rs[l] = self.restrict(l, rs[l + 1])
+        z = np.where(self.ops[0].fixed, 0.0, rs[0] / self.diag(0))
+        for l in range(1, L + 1):
+            z = np.where(self.ops[l].fixed, 0.0, self.prolong(l - 1, z) + rs[l] / self.diag(l))
+        return z
+
+    def pcg(self, b, u, rtol=1e-8, atol=0.0, maxit=1000):
+        """The CG of PoissonOperator.pcg on the finest level with this preconditioner.  Returns (u, info) with the
+        same keys."""
+        op = self.ops[-1]
+        if maxit < 1:
+            raise ValueError(f"pcg: maxit = {maxit}")
+        if not (rtol >= 0.0 and atol >= 0.0):
+            raise ValueError(f"pcg: rtol = {rtol}, atol = {atol} negative or NaN")
+        for c in range(self.bs):
+            if not op.fixed[c::self.bs].any():
+                raise ValueError("pcg: singular: no Dirichlet DOF")
+        u = np.array(u, dtype=np.float64)
+        b = np.asarray(b, dtype=np.float64)
+        nb = PoissonOperator.reference_norm(op, b, u)
+        tol = max(rtol * nb, atol)
+        info = dict(iterations=0, converged=0, nb=nb, rnorm=nb, replacements=0, breakdown=0)
+        if tol == 0.0 and nb == 0.0:
+            u[~op.fixed] = 0.0
+            info.update(converged=1, rnorm=0.0)
+            return u, info
+        r = op.residual(b, u)
+        rr = np.sum(r * r)
+        if np.sqrt(rr) <= tol:
+            info.update(converged=1, rnorm=float(np.sqrt(rr)))
+            return u, info
+        z = self.precondition(r)
+        rho = np.sum(r * z)
+        if not rho > 0.0:
+            info["breakdown"] = 1
+            maxit = 0
+        d = z.copy()
+        for it in range(1, maxit + 1):
+            q = op.apply(d, masked=True)
+            dq = np.sum(d * q)
+            if not dq > 0.0:
+                info["breakdown"] = 1
+                break
+            alpha = rho / dq
+            u = u + alpha * d
+            r = r - alpha * q
+            info["iterations"] = it
+            rr = np.sum(r * r)
+            if np.sqrt(rr) <= tol:
+                rt = op.residual(b, u)
+                rr = np.sum(rt * rt)
+                if np.sqrt(rr) <= tol:
+                    info["converged"] = 1
+                    break
+                r = rt
+                info["replacements"] += 1
+            z = self.precondition(r)
+            rho_new = np.sum(r * z)
+            if not rho_new > 0.0:
+                info["breakdown"] = 1
+                break
+            beta = rho_new / rho
+            rho = rho_new
+            d = z + beta * d
+        rt = op.residual(b, u)
+        info["rnorm"] = float(np.sqrt(np.sum(rt * rt)))
+        return u, info

@@ -214,3 +214,4 @@ from .refine import parent_facets, refine_longest_edge  # noqa: E402,F401  (the 
 from .refine import carry_facet_types, child_facets  # noqa: E402,F401  (eqlb_refine_facet_types, eqlb_refine_child_facets)
 from .transfer import lagrange_dofmap, prolong_dg, prolong_lagrange, prolong_table  # noqa: E402,F401  (eqlb_refine_prolong_*)
 from .transfer import flux_bc_table, flux_bc_table_exact, prolong_flux_bc  # noqa: E402,F401  (eqlb_refine_prolong_flux_bc)
+from .transfer import restrict_lagrange  # noqa: E402,F401  (eqlb_hierarchy_restrict)

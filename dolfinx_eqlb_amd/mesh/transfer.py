@@ -329,3 +329,70 @@ def prolong_flux_bc(mesh, mesh2, parent_cell, node_parent_facet, k, boundary_val
     if one:
         val, A = val[0], A[0]
     return (val, A) if return_abs else val
+
+
+# ---- the transpose of the prolongation --------------------------------------------------------------------------------
+# r = P^T r2 with P the matrix of prolong_lagrange, in a fixed order of operations: a store pass per coarse cell and
+# the owner sum of the coarse level (csrc/eqlb_transfer.hip: k_restrict, then the sum pass of the coarse solver handle).
+#   store pass  y_loc[c][i][b] = sum PT[row(k, n)][i] * r2[bs * dof2(c2, n) + b] over the children c2 = first + k of c in
+#               ascending k and, within a child, over its local DOFs n in ascending n - only the DOFs the child OWNS
+#               (dof_owners of the refined mesh: the rule by which prolong_lagrange stores, so every fine DOF is taken
+#               exactly once); row(k, n) is the lattice row of prolong_lagrange.  Every product is rounded on its own and
+#               the first term starts the sum; a cell whose children own nothing gives 0.0
+#   owner sum   of the coarse level, as PoissonOperator.owner_sum of lsolver/primal.py, per component
+#   mask        0 on the rows of `fixed` where given
+
+def restrict_store_pass(mesh, mesh2, parent_cell, node_parent_facet, p, r2, bs=1):
+    """(y_loc, A_loc) [ncells, nd_p, bs]: the store pass of restrict_lagrange and the same with absolute values."""
+    if p < 1 or p > 4:
+        raise ValueError(f"restrict_lagrange: p = {p} outside 1 ... 4")
+    pc = np.asarray(parent_cell, dtype=np.int64)
+    if pc.size != mesh2.ncells or np.any(np.diff(pc) < 0):
+        raise ValueError("restrict_lagrange: the children of a cell are expected side by side, in the order of the cells")
+    nd, nc = nd_of(p), mesh.ncells
+    cd2, ndofs2 = lagrange_dofmap(mesh2, p)
+    cd2 = cd2.astype(np.int64)
+    rr = np.asarray(r2, dtype=np.float64).reshape(ndofs2, bs)
+    rows = lattice_rows(p, child_vertex_positions(mesh, mesh2, pc, node_parent_facet))
+    own = dof_owners(mesh2, p)
+    T = prolong_table(p)
+    first = np.searchsorted(pc, np.arange(nc), side="left")
+    nchild = np.searchsorted(pc, np.arange(nc), side="right") - first
+    y = np.zeros((nc, nd, bs))
+    A = np.zeros((nc, nd, bs))
+    started = np.zeros(nc, dtype=bool)
+    for k in range(int(nchild.max())):
+        for n in range(nd):
+            c = np.nonzero(nchild > k)[0]
+            c = c[own[first[c] + k, n]]
+            if c.size == 0:
+                continue
+            c2 = first[c] + k
+            term = T[rows[c2, n]][:, :, None] * rr[cd2[c2, n]][:, None, :]          # [sel, nd, bs]
+            y[c] = np.where(started[c, None, None], y[c] + term, term)
+            A[c] = A[c] + np.abs(term)
+            started[c] = True
+    return y, A
+
+
+def restrict_lagrange(mesh, mesh2, parent_cell, node_parent_facet, p, r2, bs=1, fixed=None, return_abs=False, op=None):
+    """r2 [ndofs2*bs] (read as r2[dof*bs + b]) of the P_p space on the refined mesh -> r = P^T r2 [ndofs*bs] on the old
+    one, P the matrix of prolong_lagrange in the numbering of lagrange_dofmap; the order of operations stands in front
+    of restrict_store_pass.  fixed [ndofs*bs] bool: these rows give 0.  return_abs: also the sum of the absolute values
+    of the terms.  op: the operator of lsolver/primal.py on `mesh` whose slot lists the owner sum uses (None: a
+    PoissonOperator(mesh, p) is built for it)."""
+    from ..lsolver.primal import PoissonOperator
+    y, A = restrict_store_pass(mesh, mesh2, parent_cell, node_parent_facet, p, r2, bs)
+    if op is None:
+        op = PoissonOperator(mesh, p)
+    parts = [PoissonOperator.owner_sum(op, y[:, :, b]) for b in range(bs)]
+    r = np.ascontiguousarray(np.stack(parts, axis=1).ravel())
+    Ar = None
+    if return_abs:
+        Ar = np.ascontiguousarray(np.stack([PoissonOperator.owner_sum(op, A[:, :, b]) for b in range(bs)], axis=1).ravel())
+    if fixed is not None:
+        fx = np.asarray(fixed, dtype=bool).ravel()
+        r[fx] = 0.0
+        if return_abs:
+            Ar[fx] = 0.0
+    return (r, Ar) if return_abs else r

@@ -720,8 +720,9 @@ int eqlb_refine_parent_facets(eqlb_refine_t* plan, eqlb_mesh_t* refined, int32_t
  *             No atomics, no reduction across threads: the result does not depend on scheduling
  * The boundary conditions of the equilibrator cross the refinement through the entries behind
  * eqlb_refine_prolong_dg (eqlb_refine_facet_types ... eqlb_ev_carry_boundary).
- * Not provided: DOLFINx' GLL-warped node set at p >= 3 (its DOF points are no lattice points), restriction /
- * coarsening, several levels in one call, distributed meshes.
+ * The transpose of the P_p prolongation and several levels in one call: eqlb_hierarchy_* below.
+ * Not provided: DOLFINx' GLL-warped node set at p >= 3 (its DOF points are no lattice points), coarsening of a mesh,
+ * distributed meshes.
  */
 
 /* The cell dofmap of the conforming P_p space (1 <= p <= 4) in the numbering of the project's own solvers - for a
@@ -981,6 +982,50 @@ int eqlb_elasticity_residual(eqlb_elasticity_t* handle, const double* b, const d
                              int32_t memspace, void* stream);
 int eqlb_elasticity_solve(eqlb_elasticity_t* handle, const double* b, double* u, double rtol, double atol,
                           int32_t maxit, double* info, int32_t memspace, void* stream);
+
+/* ---- A hierarchy of refined levels: the transpose of the prolongation and a multilevel preconditioner (BPX) -------------
+ * The Jacobi-preconditioned CG of eqlb_primal_solve / eqlb_elasticity_solve needs O(1/h) iterations.  An adaptive loop
+ * leaves a hierarchy behind: the solver handle of every level and the plan of every refinement (eqlb_mesh_refine_plan,
+ * kept open).  On it the additive multilevel diagonal scaling
+ *     z = sum_l P ... P D_l^-1 P^T ... P^T r     (P: eqlb_refine_prolong_lagrange, D_l: the diagonal of level l)
+ * is symmetric positive definite on the free rows by construction, has no parameter and needs no operator product;
+ * the iteration count of the CG then hardly grows with the level.  The rule is stated as numpy in
+ * dolfinx_eqlb_amd/mesh/transfer.py: restrict_lagrange and dolfinx_eqlb_amd/lsolver/multilevel.py: Hierarchy;
+ * eqlb_hierarchy_restrict and eqlb_hierarchy_precondition reproduce it bit for bit, and two calls give the same bits:
+ *   restrict  r = P^T r2 as a store pass and an owner sum, no atomics.  Store pass, per cell c of the coarse level:
+ *             y_loc[c][i][b] = sum PT[row(k, n)][i] * r2[bs * dof2(c2, n) + b] over the children c2 = first + k of c in
+ *             ascending k and within a child over its local DOFs n in ascending n, only those the child OWNS (the rule
+ *             by which the prolongation stores: every fine DOF is taken once); row(k, n) is the lattice row of the
+ *             prolongation; every product is rounded on its own, the first term starts the sum, a cell whose children
+ *             own nothing gives 0.0.  Owner sum: that of the coarse solver handle (eqlb_primal_apply).  Mask: 0 on the
+ *             fixed rows of the coarse handle if `masked`
+ *   precondition  r_L = r with the fixed rows of the finest level set to 0; r_l = restrict(r_{l+1}), masked;
+ *             z_0 = r_0 / diag_0 on the free rows of level 0, 0 elsewhere; z_{l+1} = prolong(z_l) + r_{l+1} / diag_{l+1}
+ *             on the free rows of level l + 1 (quotient and sum rounded singly), 0 on its fixed rows; z = z_L
+ *   solve     the CG of eqlb_primal_solve on the finest handle with this preconditioner in the place of z = r / diag:
+ *             the same start, reference norm, stopping rule (the true residual decides, replacement), info [8], maxit
+ *             and breakdown semantics, and one more breakdown: r . z <= 0 (or NaN).  It waits for the device
+ * solvers [nlevels], coarsest first: eqlb_primal_t* (bs = 1) or eqlb_elasticity_t* (bs = 2), all of one p; meshes[l]
+ * the mesh of solvers[l]; plans[l] (l < nlevels - 1) the plan from meshes[l] to meshes[l + 1].  Everything is BORROWED
+ * and must outlive the hierarchy.  Masks and diagonals of the handles are read when an entry runs:
+ * eqlb_*_set_dirichlet on a level takes effect at the next call.  All work space is allocated at create; in DEVICE
+ * memory space no later entry allocates, everything is enqueued on `stream` and nothing waits (but solve).  HOST memory
+ * space is staged and synchronous.  The entries use the work space of the solver handles: one stream, one call after
+ * the other, not concurrently with an entry of one of the handles.  Vectors of level l have bs * ndofs_l doubles.
+ * Refused by name before anything is launched: null arguments, nlevels < 1, bs not 1 or 2, levels of different p, a
+ * plan whose counts do not fit its two meshes, a solver whose mesh is not that of its level, `level` outside
+ * 0 ... nlevels - 2, an unknown memory space.  nlevels = 1 is plain Jacobi.
+ * Not provided: the multiplicative cycle, skipping the unchanged regions of locally refined levels, a solve on the
+ * coarsest level. */
+typedef struct eqlb_hierarchy eqlb_hierarchy_t;
+int eqlb_hierarchy_create(int32_t nlevels, int32_t bs, void* const* solvers, eqlb_refine_t* const* plans,
+                          eqlb_mesh_t* const* meshes, void* stream, eqlb_hierarchy_t** out);
+void eqlb_hierarchy_destroy(eqlb_hierarchy_t* handle);
+int eqlb_hierarchy_restrict(eqlb_hierarchy_t* handle, int32_t level, const double* r_fine, double* r_coarse,
+                            int32_t masked, int32_t memspace, void* stream); /* level + 1 -> level */
+int eqlb_hierarchy_precondition(eqlb_hierarchy_t* handle, const double* r, double* z, int32_t memspace, void* stream);
+int eqlb_hierarchy_solve(eqlb_hierarchy_t* handle, const double* b, double* u, double rtol, double atol,
+                         int32_t maxit, double* info, int32_t memspace, void* stream);
 
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the

@@ -16,6 +16,13 @@ tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all ar
   --elasticity  after the Poisson figures, the same figures for the P_p^2 elasticity solve (cpp.PrimalElasticity): pi_1 = 1,
              u = 0 all around in both rows, the body force (f_ex, f_ex(y, x)); vectors have 2 ndofs rows, the solution
              is prolonged with bs = 2, and the product time is also given as a multiple of Poisson's at the same degree
+  --multilevel  instead of the figures above: a hierarchy by uniform marking on the device from create_unit_square(
+             --coarse-n) up to within 10 % of 1M triangles (every level has four times the cells), one solver handle per
+             level, and for every degree (with --elasticity also for the elasticity solve) the device time of one
+             application of the multilevel preconditioner (cpp.Multilevel.precondition_raw), of one iteration, the
+             iterations and the time to rtol 1e-8 from zero of the Jacobi entry and of the hierarchy in the same process,
+             and an estimate of the launch share of an application: the time per launch of an application on the
+             coarsest levels alone (up to 4 096 cells: nothing but launches), times the launches of the full one
   --check-every LIB:N ...   the PCG of P_2 to rtol 1e-8 from zero once per library (builds of libeqlb_amd.so with
              -DEQLB_PRIMAL_CHECK_EVERY=N, tools/build_variant.sh NAME "-D..." eqlb_primal_solve), each in a child process
 Prints one line per figure and, last, one JSON line with all of them.  Nothing here is a pass/fail condition.
@@ -247,6 +254,85 @@ def run_degree(args, cpp, torch, dm, p, res, elasticity=False):
     res[f"{P}{p}"] = r
 
 
+def timed_calls(torch, fn, n):
+    """device ms per call of fn, by events around n calls after a warm-up of 5"""
+    for _ in range(5):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def run_multilevel(args, cpp, torch, res):
+    """the figures of --multilevel"""
+    from dolfinx_eqlb_amd.mesh import create_unit_square
+    base = create_unit_square(args.coarse_n, shuffle_seed=3, perturb=0.15)
+    L = max(1, int(round(np.log(1.0e6 / base.ncells) / np.log(4.0))))
+    if abs(base.ncells * 4 ** L - 1.0e6) > 1.0e5:
+        say(f"--coarse-n {args.coarse_n}: {base.ncells * 4 ** L} cells on level {L} are not within 10 % of 1M triangles")
+        sys.exit(1)
+    t0 = time.perf_counter()
+    dms, refs = [cpp.DeviceMesh(base)], []
+    for _ in range(L):
+        refs.append(dms[-1].refine(np.arange(dms[-1].mesh.ncells, dtype=np.int32), keep_plan=True))
+        dms.append(refs[-1].dmesh)
+    cells = [d.mesh.ncells for d in dms]
+    say(f"hierarchy: {L + 1} levels, cells {cells} in {time.perf_counter() - t0:.1f} s")
+    small = max(2, sum(1 for c in cells if c <= 4096))   # levels of the launch-bound sub-hierarchy
+    for elasticity in ([False, True] if args.elasticity else [False]):
+        bs, P = (2, "E") if elasticity else (1, "P")
+        for p in args.degrees:
+            hs = []
+            for dm in dms[:-1]:
+                bf = dm.mesh.boundary_facets()
+                hs.append(cpp.PrimalElasticity(dm, p, 1.0) if elasticity else cpp.PrimalPoisson(dm, p))
+                hs[-1].set_dirichlet(*([bf, bf] if elasticity else [bf]))
+            top, b = make_problem(cpp, torch, dms[-1], p, elasticity)
+            hs.append(top)
+            ml = cpp.Multilevel(hs, refs)
+            n = bs * top.ndofs
+            r = dict(levels=L + 1, cells=cells, ndofs=n)
+            x = torch.from_numpy(np.random.default_rng(0).standard_normal(n)).cuda()
+            z = torch.empty_like(x)
+            r["precondition_ms"] = timed_calls(torch, lambda: ml.precondition_raw(x.data_ptr(), z.data_ptr()),
+                                               args.products)
+            mls = cpp.Multilevel(hs[:small], refs[:small - 1])
+            ns = bs * hs[small - 1].ndofs
+            xs, zs = x[:ns].clone(), z[:ns].clone()
+            per_launch = timed_calls(torch, lambda: mls.precondition_raw(xs.data_ptr(), zs.data_ptr()),
+                                     args.products) / (2 + 4 * (small - 1))
+            mls.close()
+            r["launches"] = 2 + 4 * L
+            r["launch_ms"] = per_launch
+            r["launch_share"] = min(1.0, r["launches"] * per_launch / r["precondition_ms"])
+            say(f"{P}_{p}: {n} rows; one application {r['precondition_ms']:.4f} ms over {args.products} applications, "
+                f"{r['launches']} launches of about {1e3 * per_launch:.1f} us each (measured on the {small} coarsest "
+                f"levels): launch share about {100 * r['launch_share']:.0f} %")
+            zero = torch.zeros(n, dtype=torch.float64, device="cuda")
+            timed_solve(torch, ml, b, zero, 0.0, 8)   # warm-up
+            info, ms, _ = timed_solve(torch, ml, b, zero, 0.0, args.iterations)
+            r["iteration_ms"] = ms / max(info["iterations"], 1)
+            say(f"{P}_{p}: iteration with the hierarchy {r['iteration_ms']:.4f} ms ({info['iterations']} iterations in "
+                f"{ms:.1f} ms)")
+            info, ms, _ = timed_solve(torch, top, b, zero, 0.0, args.iterations)
+            r["jacobi_iteration_ms"] = ms / max(info["iterations"], 1)
+            for name, h in (("jacobi", top), ("hierarchy", ml)):
+                info, ms, _ = timed_solve(torch, h, b, zero, 1e-8, args.maxit)
+                r[name] = dict(iterations=info["iterations"], ms=ms, converged=info["converged"],
+                               replacements=info["replacements"], breakdown=info["breakdown"])
+                say(f"{P}_{p}: {name} to rtol 1e-8 from zero: {r[name]}")
+            r["speedup"] = r["jacobi"]["ms"] / r["hierarchy"]["ms"]
+            say(f"{P}_{p}: Jacobi iteration {r['jacobi_iteration_ms']:.4f} ms; the hierarchy solves in "
+                f"1 / {r['speedup']:.2f} of the time of Jacobi")
+            ml.close()
+            res[f"ML_{P}{p}"] = r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=500, help="squares per side (4 n^2 triangles)")
@@ -259,6 +345,8 @@ def main():
     ap.add_argument("--spsolve-degrees", type=int, nargs="*", default=[1],
                     help="degrees at which --host also runs spsolve (P_2 at 1M triangles takes minutes and many GB)")
     ap.add_argument("--elasticity", action="store_true", help="the same figures for cpp.PrimalElasticity as well")
+    ap.add_argument("--multilevel", action="store_true", help="the figures of the multilevel preconditioner instead")
+    ap.add_argument("--coarse-n", type=int, default=2, help="--multilevel: squares per side of the coarsest mesh")
     ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
     ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -285,6 +373,10 @@ def main():
     torch.cuda.init()
     from dolfinx_eqlb_amd import cpp
     from dolfinx_eqlb_amd.mesh import create_unit_square
+    if args.multilevel:
+        run_multilevel(args, cpp, torch, res)
+        print(json.dumps(res))
+        return
     t0 = time.perf_counter()
     dm = cpp.DeviceMesh(create_unit_square(args.n, shuffle_seed=3, perturb=0.15))
     say(f"mesh: {dm.mesh.ncells} cells in {time.perf_counter() - t0:.1f} s")
