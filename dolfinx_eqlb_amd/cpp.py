@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_elasticity_residual", "eqlb_elasticity_solve",
     "eqlb_hierarchy_create", "eqlb_hierarchy_destroy", "eqlb_hierarchy_restrict", "eqlb_hierarchy_precondition",
     "eqlb_hierarchy_solve",
+    "eqlb_primal_apply_many", "eqlb_primal_solve_many", "eqlb_hierarchy_precondition_many",
+    "eqlb_hierarchy_solve_many",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -1364,6 +1366,21 @@ def get_cross_table(p: int):
 PRIMAL_INFO = ("iterations", "converged", "nb", "rnorm", "replacements", "breakdown", "tol", "facets_skipped")
 
 
+def _primal_info(v):
+    info = dict(zip(PRIMAL_INFO, [float(x) for x in v]))
+    for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
+        info[key] = int(info[key])
+    return info
+
+
+def _columns(a, n):
+    """[nrhs][n] as one contiguous array; the column count comes from the array"""
+    v = np.ascontiguousarray(a, dtype=np.float64)
+    if v.ndim != 2 or v.shape[0] < 1 or v.shape[1] != n:
+        raise RuntimeError("Local solver: Input sizes does not match")
+    return v
+
+
 class PrimalPoisson:
     """eqlb_primal_t: -div(coeff grad u) = f on the conforming P_p space of the handle (1 <= p <= 4), in the numbering
     of DeviceMesh.lagrange_dofmap: the operator matrix-free, the load vector, the residual and a Jacobi-preconditioned
@@ -1475,6 +1492,36 @@ class PrimalPoisson:
         for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
             info[key] = int(info[key])
         return info
+
+    def apply_many(self, U, masked=False, stream=0):
+        """Y [nrhs][ndofs]: row c is apply(U[c]), bit for bit, in one call."""
+        uu = _columns(U, self.ndofs)
+        y = np.zeros_like(uu)
+        self.apply_many_raw(uu.shape[0], uu.ctypes.data, y.ctypes.data, masked, MEM_HOST, stream)
+        return y
+
+    def apply_many_raw(self, nrhs, u, y, masked=False, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_primal_apply_many(self._h, C.c_int32(nrhs), _vp(u), _vp(y), C.c_int32(1 if masked else 0),
+                                            C.c_int32(memspace), C.c_void_p(stream)))
+
+    def solve_many(self, B, U, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
+        """nrhs systems in one call: row c of the result and infos[c] are solve(B[c], U[c]), bit for bit.  Returns
+        (U, infos)."""
+        bb = _columns(B, self.ndofs)
+        uu = _columns(U, self.ndofs).copy()
+        if uu.shape != bb.shape:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        infos = self.solve_many_raw(bb.shape[0], bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
+        return uu, infos
+
+    def solve_many_raw(self, nrhs, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
+        """eqlb_primal_solve_many on raw pointers: u [nrhs][ndofs] is overwritten by the solutions; waits for the
+        device; returns the list of the columns' info."""
+        v = (C.c_double * (8 * max(int(nrhs), 1)))()
+        _check(lib().eqlb_primal_solve_many(self._h, C.c_int32(nrhs), _vp(b), _vp(u), C.c_double(rtol),
+                                            C.c_double(atol), C.c_int32(maxit), v, C.c_int32(memspace),
+                                            C.c_void_p(stream)))
+        return [_primal_info(v[8 * c:8 * c + 8]) for c in range(int(nrhs))]
 
     def close(self):
         if self._h:
@@ -1697,6 +1744,36 @@ class Multilevel:
         for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
             info[key] = int(info[key])
         return info
+
+    def precondition_many(self, R, stream=0):
+        """Z [nrhs][n]: row c is precondition(R[c]), bit for bit, in one call (Poisson handles only)."""
+        rr = _columns(R, self.nrows[-1])
+        z = np.zeros_like(rr)
+        self.precondition_many_raw(rr.shape[0], rr.ctypes.data, z.ctypes.data, MEM_HOST, stream)
+        return z
+
+    def precondition_many_raw(self, nrhs, r, z, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_hierarchy_precondition_many(self._h, C.c_int32(nrhs), _vp(r), _vp(z), C.c_int32(memspace),
+                                                      C.c_void_p(stream)))
+
+    def solve_many(self, B, U, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
+        """nrhs systems in one call: row c of the result and infos[c] are solve(B[c], U[c]), bit for bit (Poisson
+        handles only).  Returns (U, infos)."""
+        bb = _columns(B, self.nrows[-1])
+        uu = _columns(U, self.nrows[-1]).copy()
+        if uu.shape != bb.shape:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        infos = self.solve_many_raw(bb.shape[0], bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
+        return uu, infos
+
+    def solve_many_raw(self, nrhs, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
+        """eqlb_hierarchy_solve_many on raw pointers: u [nrhs][n] is overwritten by the solutions; waits for the
+        device; returns the list of the columns' info."""
+        v = (C.c_double * (8 * max(int(nrhs), 1)))()
+        _check(lib().eqlb_hierarchy_solve_many(self._h, C.c_int32(nrhs), _vp(b), _vp(u), C.c_double(rtol),
+                                               C.c_double(atol), C.c_int32(maxit), v, C.c_int32(memspace),
+                                               C.c_void_p(stream)))
+        return [_primal_info(v[8 * c:8 * c + 8]) for c in range(int(nrhs))]
 
     def close(self):
         if self._h:

@@ -355,6 +355,35 @@ void elasticity_level(eqlb_elasticity* h, SolverLevel& v);
 // makes the kernel return at once when set
 int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const int32_t* cell_dofs2,
                     int64_t ndofs2, const double* r2, double* yloc, const int32_t* done, hipStream_t stream);
+
+// ---- several right-hand sides in one call (eqlb_*_many; Poisson handles only) ----------------------------------------
+// The columns a launch works on: R <= 4 columns lie one after another (vectors [R][n], y_loc [R][ncells nd_p], block
+// partials [R][2][G], states [R]).  Column c runs if bit c of mask is set and, with check, the stop flag of its state
+// st[c] (a PcgState in device memory) is not set; the others are neither read nor written.
+struct ManyCols
+{
+  int32_t R;
+  uint32_t mask;
+  int32_t check;
+  const void* st;
+};
+// the work space of a Poisson handle for R columns, grown by the call that needs it and reused afterwards; all DEVICE
+struct ManyLevel
+{
+  double *yloc, *r, *z, *d, *q, *part;
+  void* st;
+};
+int primal_many_level(eqlb_primal* h, int R, ManyLevel& v);
+// the launches of the handle's unit on these columns, as owner_sum / residual / product of SolverLevel; vectors [R][n]
+hipError_t primal_many_owner_sum(eqlb_primal* h, const ManyCols& c, double* y, bool masked, hipStream_t stream);
+hipError_t primal_many_residual(eqlb_primal* h, const ManyCols& c, const double* b, const double* u, double* r,
+                                bool only_fixed, hipStream_t stream);
+hipError_t primal_many_product(eqlb_primal* h, const ManyCols& c, hipStream_t stream);
+// launch_restrict on the columns of c: r2 [R][ndofs2] into yloc [R][ncells nd_p]; done0 / done_stride: the stop flag
+// of column 0 and the distance to the next one in int32, or nullptr
+int launch_restrict_many(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int R, uint32_t mask,
+                         const int32_t* cell_dofs2, int64_t ndofs2, const double* r2, double* yloc, const int32_t* done0,
+                         int done_stride, hipStream_t stream);
 } // namespace eqlb
 
 struct eqlb_se; // the handle behind eqlb_se_t / eqlb_ev_t: eqlb_handle.h (host code only)

@@ -20,9 +20,14 @@
 // but k_prolong returns at once when the stop flag is set; the host reads the state every ML_CHECK_EVERY iterations - an
 // iteration is about 4 L launches longer than a Jacobi one and the count is small, so the batch is shorter.
 // All work space (r_l, z_l and the prolongation temporary t_l of every level) is carved out of one allocation at create.
+// Several right-hand sides (eqlb_hierarchy_precondition_many, eqlb_hierarchy_solve_many; Poisson handles only): the
+// k_ml_*_many variants below work on the columns of a ManyCols, the restriction store pass is launch_restrict_many, the
+// owner sum primal_many_owner_sum, the prolongation takes the columns as its nrhs - still 2 + 4 L launches; their work
+// space is grown by the first call that needs it (prepare_many).  eqlb_primal_many.h states the rule.
 #include "eqlb_device_common.h"
 #include "eqlb_refine_plan.h" // (eqlb_mesh_handle.h, eqlb_host_util.h)
 #include "eqlb_primal_common.h" // PcgState, the scalar and vector kernels and the host loop of the CG
+#include "eqlb_primal_many.h" // their column variants: several right-hand sides in one call
 
 #include <climits>
 #include <vector>
@@ -161,6 +166,179 @@ k_ml_scalar(int step, int G, const double* __restrict__ part, PcgState* __restri
     st->done = 1;
   }
 }
+
+// ---- the same kernels on columns (eqlb_hierarchy_*_many; eqlb_primal_many.h states the rule): one thread per DOF
+// carries the values of that DOF in the columns of its ManyCols, vectors [R][n], partials [R][2][G] ------------------
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_mask_many(int64_t n, const ManyCols cols, const double* __restrict__ r, const uint8_t* __restrict__ fixed,
+               double* __restrict__ out)
+{
+  const uint32_t live = many_live(cols);
+  if (!live)
+    return;
+  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
+  {
+    const bool fx = fixed[d];
+#pragma unroll
+    for (int k = 0; k < MANY_R; ++k)
+      if ((live >> k) & 1u)
+        out[k * n + d] = fx ? 0.0 : r[k * n + d];
+  }
+}
+
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_combine_many(int64_t n, const ManyCols cols, const double* __restrict__ t, const double* __restrict__ r,
+                  const double* __restrict__ diag, const uint8_t* __restrict__ fixed, double* __restrict__ z)
+{
+#pragma clang fp contract(off) // the statement rounds the quotient and the sum singly
+  const uint32_t live = many_live(cols);
+  if (!live)
+    return;
+  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
+  {
+    const bool fx = fixed[d];
+    const double dg = diag[d];
+#pragma unroll
+    for (int k = 0; k < MANY_R; ++k)
+    {
+      if (!((live >> k) & 1u))
+        continue;
+      const double jac = r[k * n + d] / dg;
+      const double v = t ? t[k * n + d] + jac : jac;
+      z[k * n + d] = fx ? 0.0 : v;
+    }
+  }
+}
+
+// partials of r.r of column k: part[2 k][block]
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_update_many(int64_t n, const ManyCols cols, const double* __restrict__ p, const double* __restrict__ q,
+                 const uint8_t* __restrict__ fixed, double* __restrict__ u, double* __restrict__ r,
+                 double* __restrict__ part)
+{
+#pragma clang fp contract(off)
+  __shared__ double sh[MANY_R][PS_THREADS];
+  const uint32_t live = many_live(cols);
+  if (!live)
+    return;
+  const PcgState* st = static_cast<const PcgState*>(cols.st);
+  const int t = threadIdx.x;
+  double alpha[MANY_R];
+#pragma unroll
+  for (int k = 0; k < MANY_R; ++k)
+    alpha[k] = ((live >> k) & 1u) ? st[k].alpha : 0.0;
+  double a0[MANY_R] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)gridDim.x * PS_THREADS)
+  {
+    if (fixed[d])
+      continue; // (r is 0 there since the start)
+#pragma unroll
+    for (int k = 0; k < MANY_R; ++k)
+    {
+      if (!((live >> k) & 1u))
+        continue;
+      const int64_t e = k * n + d;
+      u[e] = u[e] + alpha[k] * p[e];
+      const double rv = r[e] - alpha[k] * q[e];
+      r[e] = rv;
+      a0[k] = a0[k] + rv * rv;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < MANY_R; ++k)
+    sh[k][t] = a0[k];
+  __syncthreads();
+  EQLB_BLOCK_TREE_SUM(sh, t, MANY_R, PS_THREADS)
+  if (t < MANY_R && ((live >> t) & 1u))
+    part[(int64_t)(2 * t) * gridDim.x + blockIdx.x] = sh[t][0];
+}
+
+// partials of x.y of column k: part[2 k + 1][block]
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_dot_many(int64_t n, const ManyCols cols, const double* __restrict__ x, const double* __restrict__ y,
+              double* __restrict__ part)
+{
+#pragma clang fp contract(off)
+  __shared__ double sh[MANY_R][PS_THREADS];
+  const uint32_t live = many_live(cols);
+  if (!live)
+    return;
+  const int t = threadIdx.x, G = gridDim.x;
+  double a0[MANY_R] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)G * PS_THREADS)
+  {
+#pragma unroll
+    for (int k = 0; k < MANY_R; ++k)
+      if ((live >> k) & 1u)
+        a0[k] = a0[k] + x[k * n + d] * y[k * n + d];
+  }
+#pragma unroll
+  for (int k = 0; k < MANY_R; ++k)
+    sh[k][t] = a0[k];
+  __syncthreads();
+  EQLB_BLOCK_TREE_SUM(sh, t, MANY_R, PS_THREADS)
+  if (t < MANY_R && ((live >> t) & 1u))
+    part[(int64_t)(2 * t + 1) * G + blockIdx.x] = sh[t][0];
+}
+
+// k_ml_scalar, one block per column of mask
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_scalar_many(int step, int G, uint32_t mask, const double* __restrict__ part_, PcgState* __restrict__ st_)
+{
+  __shared__ double sh[2][PS_THREADS];
+  const int t = threadIdx.x;
+  if (!((mask >> blockIdx.x) & 1u))
+    return;
+  PcgState* st = st_ + blockIdx.x;
+  const double* part = part_ + (int64_t)blockIdx.x * 2 * G;
+  if (st->done && step != STEP_REPLACE)
+    return;
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+  {
+    double a = 0.0;
+    for (int b = t; b < G; b += PS_THREADS)
+      a += part[(int64_t)j * G + b];
+    sh[j][t] = a;
+  }
+  __syncthreads();
+  EQLB_BLOCK_TREE_SUM(sh, t, 2, PS_THREADS)
+  if (t != 0)
+    return;
+  const double s0 = sh[0][0], s1 = sh[1][0];
+  st->rr = s0;
+  bool goes_on = true;
+  if (step == STEP_START)
+  {
+    st->rho = s1;
+    goes_on = !(sqrt(s0) <= st->tol);
+    st->done = goes_on ? 0 : 1;
+  }
+  else if (step == STEP_BETA)
+  {
+    st->iters += 1;
+    goes_on = !(sqrt(s0) <= st->tol);
+    if (goes_on)
+    {
+      st->beta = s1 / st->rho;
+      st->rho = s1;
+    }
+    else
+      st->done = 1;
+  }
+  else // STEP_REPLACE
+  {
+    st->beta = s1 / st->rho;
+    st->rho = s1;
+    st->replacements += 1;
+    st->done = 0;
+  }
+  if (goes_on && !(s1 > 0.0))
+  {
+    st->breakdown = 1;
+    st->done = 1;
+  }
+}
 } // namespace
 } // namespace eqlb
 
@@ -173,6 +351,12 @@ struct eqlb_hierarchy
   std::vector<int64_t> n; // bs * ndofs per level
   eqlb::DevCarve mem;
   std::vector<eqlb::DevPiece<double>> r, z, t;
+  // the *_many entries: r_l, z_l, t_l for many_R columns, grown by the first call that needs them; the views of the
+  // levels' own work space for columns, read anew by every call
+  int many_R = 0;
+  eqlb::DevBuf<char> many_mem;
+  std::vector<double*> mr, mz, mt;
+  std::vector<eqlb::ManyLevel> mlv;
 };
 
 namespace eqlb
@@ -257,6 +441,124 @@ struct MultilevelSteps
     if (enqueue_precondition("eqlb_hierarchy_solve", h, w.r, w.z, w.st, stream) != EQLB_OK)
       return hipErrorUnknown;
     return rz_and_scalar(STEP_BETA, w.st);
+  }
+};
+
+// ---- several right-hand sides ----------------------------------------------------------------------------------------
+// what every *_many entry checks, and the work space for R columns: r_l, z_l, t_l here, y_loc (and, on the finest
+// level, the vectors of the CG) in the solver handles
+int prepare_many(const char* who, eqlb_hierarchy* h, int32_t nrhs, const void* a, const void* b, int32_t memspace)
+{
+  if (!h || !a || !b)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (nrhs < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d (at least 1)", who, (int)nrhs);
+  if (h->bs != 1)
+    return fail(EQLB_ERR_UNSUPPORTED, "%s: several right-hand sides are provided for Poisson handles (bs = 1) only", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  const int R = nrhs < MANY_R ? nrhs : MANY_R;
+  h->mlv.resize(h->nlevels);
+  for (int l = 0; l < h->nlevels; ++l)
+    EQLB_TRY(primal_many_level(static_cast<eqlb_primal*>(h->lv[l].handle), R, h->mlv[l]));
+  if (R > h->many_R && h->nlevels > 1)
+  {
+    std::vector<size_t> off(3 * h->nlevels);
+    size_t bytes = 0;
+    for (int l = 0; l < h->nlevels; ++l)
+      for (int j = 0; j < 3; ++j)
+      {
+        off[3 * l + j] = bytes;
+        bytes += round_up256((size_t)R * h->n[l] * sizeof(double));
+      }
+    h->many_R = 0;
+    HIP_TRY(h->many_mem.alloc_raw(bytes)); // (frees the smaller one first)
+    h->mr.resize(h->nlevels);
+    h->mz.resize(h->nlevels);
+    h->mt.resize(h->nlevels);
+    for (int l = 0; l < h->nlevels; ++l)
+    {
+      h->mr[l] = reinterpret_cast<double*>(h->many_mem.get() + off[3 * l]);
+      h->mz[l] = reinterpret_cast<double*>(h->many_mem.get() + off[3 * l + 1]);
+      h->mt[l] = reinterpret_cast<double*>(h->many_mem.get() + off[3 * l + 2]);
+    }
+    h->many_R = R;
+  }
+  return EQLB_OK;
+}
+
+// enqueue_precondition on the columns of c: r, z DEVICE [R][n_L]; 2 + 4 L launches whatever R is
+int enqueue_precondition_many(const char* who, const eqlb_hierarchy& h, const ManyCols& c, const double* r, double* z,
+                              hipStream_t stream)
+{
+  const int L = h.nlevels - 1;
+  const dim3 block(PS_THREADS);
+  const double* const none = nullptr;
+  if (L == 0)
+  {
+    hipLaunchKernelGGL(k_ml_combine_many, dim3(stream_blocks(h.n[0])), block, 0, stream, h.n[0], c, none, r,
+                       h.lv[0].diag, h.lv[0].fixed, z);
+    HIP_TRY(hipGetLastError());
+    return EQLB_OK;
+  }
+  const PcgState* st = static_cast<const PcgState*>(c.st);
+  const int32_t* done0 = (c.check && st) ? &st->done : nullptr;
+  constexpr int done_stride = (int)(sizeof(PcgState) / sizeof(int32_t));
+  hipLaunchKernelGGL(k_ml_mask_many, dim3(stream_blocks(h.n[L])), block, 0, stream, h.n[L], c, r, h.lv[L].fixed,
+                     h.mr[L]);
+  HIP_TRY(hipGetLastError());
+  for (int l = L - 1; l >= 0; --l)
+  {
+    const SolverLevel &lo = h.lv[l], &hi = h.lv[l + 1];
+    EQLB_TRY(launch_restrict_many(who, h.plans[l], hi.mesh, h.p, c.R, c.mask, hi.cell_dofs, hi.ndofs, h.mr[l + 1],
+                                  h.mlv[l].yloc, done0, done_stride, stream));
+    HIP_TRY(primal_many_owner_sum(static_cast<eqlb_primal*>(lo.handle), c, h.mr[l], true, stream));
+  }
+  hipLaunchKernelGGL(k_ml_combine_many, dim3(stream_blocks(h.n[0])), block, 0, stream, h.n[0], c, none,
+                     static_cast<const double*>(h.mr[0]), h.lv[0].diag, h.lv[0].fixed, h.mz[0]);
+  HIP_TRY(hipGetLastError());
+  for (int l = 1; l <= L; ++l)
+  {
+    // (k_prolong knows no columns to leave out: it prolongs all R, into a t_l whose idle columns nobody reads)
+    EQLB_TRY(eqlb_refine_prolong_lagrange(h.plans[l - 1], h.lv[l].mesh, h.p, 1, c.R, h.lv[l - 1].cell_dofs,
+                                          h.lv[l - 1].ndofs, h.mz[l - 1], h.lv[l].cell_dofs, h.lv[l].ndofs, h.mt[l],
+                                          EQLB_MEM_DEVICE, stream));
+    hipLaunchKernelGGL(k_ml_combine_many, dim3(stream_blocks(h.n[l])), block, 0, stream, h.n[l], c,
+                       static_cast<const double*>(h.mt[l]), static_cast<const double*>(h.mr[l]), h.lv[l].diag,
+                       h.lv[l].fixed, l == L ? z : h.mz[l]);
+    HIP_TRY(hipGetLastError());
+  }
+  return EQLB_OK;
+}
+
+// MultilevelSteps on columns
+struct MultilevelStepsMany
+{
+  static constexpr int check_every = ML_CHECK_EVERY;
+  const eqlb_hierarchy& h;
+  const ManyWork& w;
+  hipStream_t stream;
+  hipError_t rz_and_scalar(const ManyCols& c, int step) const
+  {
+    const int G = stream_blocks(w.n);
+    hipLaunchKernelGGL(k_ml_dot_many, dim3(G), dim3(PS_THREADS), 0, stream, w.n, c, static_cast<const double*>(w.r),
+                       static_cast<const double*>(w.z), w.part);
+    hipLaunchKernelGGL(k_ml_scalar_many, dim3(w.R), dim3(PS_THREADS), 0, stream, step, G, c.mask,
+                       static_cast<const double*>(w.part), w.st);
+    return hipGetLastError();
+  }
+  hipError_t restart(const ManyCols& c, int step, double, double) const
+  {
+    if (enqueue_precondition_many("eqlb_hierarchy_solve_many", h, c, w.r, w.z, stream) != EQLB_OK)
+      return hipErrorUnknown;
+    return rz_and_scalar(c, step);
+  }
+  hipError_t advance(const ManyCols& c, double* pu, double, double) const
+  {
+    hipLaunchKernelGGL(k_ml_update_many, dim3(stream_blocks(w.n)), dim3(PS_THREADS), 0, stream, w.n, c,
+                       static_cast<const double*>(w.d), static_cast<const double*>(w.q), w.fixed, pu, w.r, w.part);
+    if (enqueue_precondition_many("eqlb_hierarchy_solve_many", h, c, w.r, w.z, stream) != EQLB_OK)
+      return hipErrorUnknown;
+    return rz_and_scalar(c, STEP_BETA);
   }
 };
 } // namespace
@@ -417,6 +719,84 @@ try
   auto product = [&](const PcgState*) { return top.product(top.handle, stream); };
   return pcg_solve(w, residual, product, MultilevelSteps{*h, w, stream}, b, u, rtol, atol, maxit, info, status[0],
                    memspace == EQLB_MEM_HOST, stream);
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_precondition_many(eqlb_hierarchy_t* h, int32_t nrhs, const double* r, double* z, int32_t memspace,
+                                     void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_precondition_many";
+  EQLB_TRY(prepare_many(who, h, nrhs, r, z, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)h->n[h->nlevels - 1];
+  HostCall s;
+  const auto d_r = s.in(host ? r : nullptr, nrhs * n);
+  const auto d_z = s.out(host ? z : nullptr, nrhs * n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double* pr = host ? d_r.get() : r;
+  double* pz = host ? d_z.get() : z;
+  int st = EQLB_OK;
+  for (int32_t c0 = 0; c0 < nrhs && st == EQLB_OK; c0 += MANY_R)
+  {
+    const int R = nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R;
+    st = enqueue_precondition_many(who, *h, ManyCols{R, (1u << R) - 1u, 0, nullptr}, pr + c0 * n, pz + c0 * n, stream);
+  }
+  HIP_TRY(s.finish(stream));
+  return st;
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_solve_many(eqlb_hierarchy_t* h, int32_t nrhs, const double* b, double* u, double rtol, double atol,
+                              int32_t maxit, double* info, int32_t memspace, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_solve_many";
+  if (maxit < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
+  if (!(rtol >= 0.0) || !(atol >= 0.0))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
+  if (!info)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(prepare_many(who, h, nrhs, b, u, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const SolverLevel& top = h->lv[h->nlevels - 1];
+  eqlb_primal* const th = static_cast<eqlb_primal*>(top.handle);
+  // the status word of the finest mask: the call waits by nature, and nothing is launched for a singular problem
+  int32_t status[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(status, top.status, sizeof(status), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (status[1] < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: the finest level has no Dirichlet DOF", who);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)h->n[h->nlevels - 1];
+  HostCall s;
+  const auto d_b = s.in(host ? b : nullptr, nrhs * n);
+  const auto d_u = s.in(host ? static_cast<const double*>(u) : nullptr, nrhs * n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double* pb = host ? d_b.get() : b;
+  double* pu = host ? d_u.get() : u;
+  auto residual = [&](const ManyCols& c, const double* xb, const double* xu, double* r, bool only_fixed) {
+    return primal_many_residual(th, c, xb, xu, r, only_fixed, stream);
+  };
+  auto product = [&](const ManyCols& c) { return primal_many_product(th, c, stream); };
+  const ManyLevel& tv = h->mlv[h->nlevels - 1];
+  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
+  {
+    const ManyWork w{(int64_t)n, nrhs - c0 < MANY_R ? (int)(nrhs - c0) : MANY_R, top.diag, top.fixed, tv.r, tv.z, tv.d,
+                     tv.q,       tv.part, static_cast<PcgState*>(tv.st)};
+    EQLB_TRY(pcg_solve_many(w, residual, product, MultilevelStepsMany{*h, w, stream}, pb + c0 * n, pu + c0 * n, rtol,
+                            atol, maxit, info + 8 * (size_t)c0, status[0], stream));
+  }
+  if (host)
+    s.out_prefix(u, d_u, nrhs * n);
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
 }
 EQLB_CATCH_ALL
 

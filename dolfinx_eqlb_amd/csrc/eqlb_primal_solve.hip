@@ -24,9 +24,13 @@
 // remaining kernels of a batch return at once, so the result does not depend on how often the host looks: it reads
 // the state every EQLB_PRIMAL_CHECK_EVERY iterations.  Nothing is allocated inside the iteration.
 // The sum pass, the CG kernels and the host loop lie in eqlb_primal_common.h, which eqlb_primal_elasticity.hip shares.
+// Several right-hand sides in one call (eqlb_primal_apply_many, eqlb_primal_solve_many): k_primal_cell_many<P, R> here,
+// the other column kernels and the host loop in eqlb_primal_many.h, which states the rule; the work space for the
+// columns is grown on demand (primal_many_level).  The single-vector entries keep their kernels.
 #include "eqlb_device_common.h"
 #include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_primal_common.h" // the sum pass, the kernels and the host loop of the CG: shared with the elasticity unit
+#include "eqlb_primal_many.h" // their column variants: several right-hand sides in one call
 #include "eqlb_tables_gen.h"
 
 #include <climits>
@@ -152,6 +156,121 @@ __global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a)
     o[e] = sbuf[(e / NP) * S + (e % NP)];
 }
 
+// The store pass of the operator on R columns: k_primal_cell<P, CELL_OPERATOR, 0> with the index row, J, the
+// coefficient and the table read once and applied to the columns of u [R][ndofs].  A table entry is read from LDS once
+// and multiplied into the R sums, each of which runs in the order of the single kernel.  The R rows of a cell stay in
+// registers (R nd_p solution values, R nd_p results) and go out column by column through the one sbuf, so the LDS
+// footprint is that of the single kernel.  Columns that do not run (ManyCols) are neither read nor written.
+template <int P, int R>
+__global__ void __launch_bounds__(PS_THREADS) k_primal_cell_many(const CellArgs a, const ManyCols cols, int64_t ustride,
+                                                                 int64_t ystride)
+{
+#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
+  constexpr int NP = nd_of(P), S = NP | 1;
+  constexpr int NTAB = 3 * NP * NP;
+  static_assert(eqlb_tables::Stiff<P>::ND == NP && R >= 1 && R <= MANY_R, "table shape");
+  __shared__ double sT[NTAB];
+  __shared__ double sbuf[PS_THREADS * S]; // first the index rows of the workgroup, then its output rows, a column at a time
+  const uint32_t live = many_live(cols);
+  if (!live)
+    return;
+  const int t = threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * PS_THREADS;
+  const int nloc = (a.ncells - base < PS_THREADS) ? (int)(a.ncells - base) : PS_THREADS;
+  const bool active = t < nloc;
+  for (int i = t; i < NTAB; i += PS_THREADS)
+    sT[i] = eqlb_tables::Stiff<P>::ST[i];
+  int32_t idx[NP];
+  {
+    int32_t* sidx = reinterpret_cast<int32_t*>(sbuf);
+    const int32_t* rows = a.cell_dofs + base * NP;
+    for (int e = t; e < nloc * NP; e += PS_THREADS)
+      sidx[e] = rows[e];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+      idx[i] = active ? sidx[t * NP + i] : 0;
+  }
+  __syncthreads(); // the table is staged; the index rows are in registers: sbuf takes the output rows
+  double out[R][NP];
+#pragma unroll
+  for (int c = 0; c < R; ++c)
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+      out[c][i] = 0.0;
+  if (active)
+  {
+    const double2* Jp = reinterpret_cast<const double2*>(a.cellJ + 4 * (base + t));
+    const double2 r0 = Jp[0], r1 = Jp[1]; // J00 J01 | J10 J11
+    const double det = r0.x * r1.y - r0.y * r1.x;
+    const double adet = fabs(det);
+    const double idet = 1.0 / det;
+    const double K00 = r1.y * idet, K01 = -r0.y * idet, K10 = -r1.x * idet, K11 = r0.x * idet;
+    const double C00 = K00 * K00 + K01 * K01, C01 = K00 * K10 + K01 * K11, C11 = K10 * K10 + K11 * K11;
+    const double w = (a.coeff ? a.coeff[base + t] : 1.0) * adet;
+    double uu[R][NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+    {
+      const bool zero = a.only_fixed && !a.fixed[idx[i]];
+#pragma unroll
+      for (int c = 0; c < R; ++c)
+      {
+        const double v = ((live >> c) & 1u) ? a.u[c * ustride + idx[i]] : 0.0;
+        uu[c][i] = zero ? 0.0 : v;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+    {
+      double tm[R][3];
+#pragma unroll
+      for (int m = 0; m < 3; ++m)
+      {
+        const double* row = sT + (m * NP + i) * NP;
+        double s[R];
+        {
+          const double e = row[0];
+#pragma unroll
+          for (int c = 0; c < R; ++c)
+            s[c] = e * uu[c][0];
+        }
+#pragma unroll
+        for (int j = 1; j < NP; ++j)
+        {
+          const double e = row[j];
+#pragma unroll
+          for (int c = 0; c < R; ++c)
+            s[c] = s[c] + e * uu[c][j];
+        }
+#pragma unroll
+        for (int c = 0; c < R; ++c)
+          tm[c][m] = s[c];
+      }
+#pragma unroll
+      for (int c = 0; c < R; ++c)
+        out[c][i] = w * ((C00 * tm[c][0] + C01 * tm[c][1]) + C11 * tm[c][2]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < R; ++c)
+  {
+    if (!((live >> c) & 1u)) // (the same in every thread)
+      continue;
+    if (active)
+    {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+        sbuf[t * S + i] = out[c][i];
+    }
+    __syncthreads();
+    double* o = a.yloc + c * ystride + base * NP;
+    for (int e = t; e < nloc * NP; e += PS_THREADS)
+      o[e] = sbuf[(e / NP) * S + (e % NP)];
+    __syncthreads(); // (the next column overwrites sbuf)
+  }
+}
+
 // the mask of the listed facets; ids outside the mesh are skipped and counted (status[0]), valid ones counted (status[1])
 __global__ void __launch_bounds__(PS_THREADS)
 k_primal_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t nnodes, int32_t nfacets, int32_t ne,
@@ -230,6 +349,10 @@ struct eqlb_primal
   eqlb::DevPiece<double> coeff, yloc, diag, r, z, d, q, part;
   eqlb::DevPiece<uint8_t> fixed;
   eqlb::DevPiece<eqlb::PcgState> st;
+  // the work space of the *_many entries for many_R columns: grown by the first call that needs it, then reused
+  int many_R = 0;
+  eqlb::DevBuf<char> many_mem;
+  eqlb::ManyLevel many{};
 };
 
 namespace eqlb
@@ -327,7 +450,139 @@ int check_handle(const char* who, const eqlb_primal* h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
   return EQLB_OK;
 }
+
+// ---- the same launches on columns: u [R][ndofs], y_loc and the vectors in the handle's work space for columns ------
+template <int P>
+hipError_t launch_cell_many_r(const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride, hipStream_t stream)
+{
+  const dim3 grid(grid_of(a.ncells, PS_THREADS)), block(PS_THREADS);
+  switch (c.R)
+  {
+  case 1:
+    hipLaunchKernelGGL((k_primal_cell_many<P, 1>), grid, block, 0, stream, a, c, ustride, ystride);
+    break;
+  case 2:
+    hipLaunchKernelGGL((k_primal_cell_many<P, 2>), grid, block, 0, stream, a, c, ustride, ystride);
+    break;
+  case 3:
+    hipLaunchKernelGGL((k_primal_cell_many<P, 3>), grid, block, 0, stream, a, c, ustride, ystride);
+    break;
+  default:
+    hipLaunchKernelGGL((k_primal_cell_many<P, 4>), grid, block, 0, stream, a, c, ustride, ystride);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_cell_many(const eqlb_primal& h, const ManyCols& c, const double* u, bool only_fixed, hipStream_t stream)
+{
+  CellArgs a = cell_args(h, u, only_fixed, nullptr);
+  a.yloc = h.many.yloc;
+  const int64_t ystride = (int64_t)h.space.ncells * h.nd;
+  switch (h.p)
+  {
+  case 1:
+    return launch_cell_many_r<1>(a, c, h.ndofs, ystride, stream);
+  case 2:
+    return launch_cell_many_r<2>(a, c, h.ndofs, ystride, stream);
+  case 3:
+    return launch_cell_many_r<3>(a, c, h.ndofs, ystride, stream);
+  default:
+    return launch_cell_many_r<4>(a, c, h.ndofs, ystride, stream);
+  }
+}
+
+ManyGatherArgs gather_many_args(const eqlb_primal& h, const ManyCols& c, bool masked)
+{
+  ManyGatherArgs m{};
+  m.g = gather_args(h, masked, nullptr);
+  m.g.yloc = h.many.yloc;
+  m.g.part = h.many.part;
+  m.cols = c;
+  m.ystride = (int64_t)h.space.ncells * h.nd;
+  return m;
+}
+
+hipError_t launch_gather_many(const eqlb_primal& h, const ManyGatherArgs& m, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_primal_gather_many, dim3(stream_blocks(h.ndofs)), dim3(PS_THREADS), 0, stream, m);
+  return hipGetLastError();
+}
+
+ManyWork many_work(const eqlb_primal& h, int R)
+{
+  return ManyWork{h.ndofs,  R,        h.diag,   h.fixed,     h.many.r,
+                  h.many.z, h.many.d, h.many.q, h.many.part, static_cast<PcgState*>(h.many.st)};
+}
+
+// what every *_many entry checks about its column count and its arrays
+int check_many(const char* who, int32_t nrhs, const void* a, const void* b)
+{
+  if (nrhs < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d (at least 1)", who, (int)nrhs);
+  if (!a || !b)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  return EQLB_OK;
+}
 } // namespace
+
+int primal_many_level(eqlb_primal* h, int R, ManyLevel& v)
+{
+  if (R > h->many_R)
+  {
+    const size_t n = (size_t)h->ndofs, ny = (size_t)h->space.ncells * h->nd;
+    size_t off = 0;
+    auto piece = [&](size_t bytes) {
+      const size_t o = off;
+      off += round_up256(bytes);
+      return o;
+    };
+    const size_t o_y = piece(R * ny * sizeof(double)), o_r = piece(R * n * sizeof(double)),
+                 o_z = piece(R * n * sizeof(double)), o_d = piece(R * n * sizeof(double)),
+                 o_q = piece(R * n * sizeof(double)), o_p = piece((size_t)R * 2 * PS_MAXBLOCKS * sizeof(double)),
+                 o_s = piece(R * sizeof(PcgState));
+    h->many_R = 0;
+    h->many = ManyLevel{};
+    HIP_TRY(h->many_mem.alloc_raw(off)); // (frees the smaller one first)
+    char* base = h->many_mem.get();
+    auto dp = [&](size_t o) { return reinterpret_cast<double*>(base + o); };
+    h->many = ManyLevel{dp(o_y), dp(o_r), dp(o_z), dp(o_d), dp(o_q), dp(o_p), base + o_s};
+    h->many_R = R;
+  }
+  v = h->many;
+  return EQLB_OK;
+}
+
+hipError_t primal_many_owner_sum(eqlb_primal* h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
+{
+  ManyGatherArgs m = gather_many_args(*h, c, masked);
+  m.g.y = y;
+  return launch_gather_many(*h, m, stream);
+}
+
+hipError_t primal_many_residual(eqlb_primal* h, const ManyCols& c, const double* b, const double* u, double* r,
+                                bool only_fixed, hipStream_t stream)
+{
+  const hipError_t e = launch_cell_many(*h, c, u, only_fixed, stream);
+  if (e != hipSuccess)
+    return e;
+  ManyGatherArgs m = gather_many_args(*h, c, true);
+  m.g.b = b;
+  m.g.r = r;
+  m.g.dot = DOT_R_R;
+  return launch_gather_many(*h, m, stream);
+}
+
+hipError_t primal_many_product(eqlb_primal* h, const ManyCols& c, hipStream_t stream)
+{
+  const hipError_t e = launch_cell_many(*h, c, h->many.d, false, stream);
+  if (e != hipSuccess)
+    return e;
+  ManyGatherArgs m = gather_many_args(*h, c, true);
+  m.g.y = h->many.q;
+  m.g.w = h->many.d;
+  m.g.dot = DOT_W_Y;
+  return launch_gather_many(*h, m, stream);
+}
 
 // the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
 void primal_level(eqlb_primal* h, SolverLevel& v)
@@ -665,6 +920,89 @@ try
   const PcgWork w = pcg_work(*h);
   return pcg_solve(w, residual, product, JacobiSteps{w, stream}, b, u, rtol, atol, maxit, info, status[0],
                    memspace == EQLB_MEM_HOST, stream);
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_apply_many(eqlb_primal_t* h, int32_t nrhs, const double* u, double* y, int32_t masked,
+                           int32_t memspace, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_primal_apply_many";
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_many(who, nrhs, u, y));
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)h->ndofs;
+  ManyLevel lv;
+  EQLB_TRY(primal_many_level(h, nrhs < MANY_R ? nrhs : MANY_R, lv));
+  HostCall s;
+  const auto d_u = s.in(host ? u : nullptr, nrhs * n);
+  const auto d_y = s.out(host ? y : nullptr, nrhs * n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double* pu = host ? d_u.get() : u;
+  double* py = host ? d_y.get() : y;
+  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
+  {
+    const int R = nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R;
+    const ManyCols cols{R, (1u << R) - 1u, 0, nullptr};
+    s.note(launch_cell_many(*h, cols, pu + c0 * n, false, stream));
+    s.note(primal_many_owner_sum(h, cols, py + c0 * n, masked != 0, stream));
+  }
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_solve_many(eqlb_primal_t* h, int32_t nrhs, const double* b, double* u, double rtol, double atol,
+                           int32_t maxit, double* info, int32_t memspace, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_primal_solve_many";
+  if (maxit < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
+  if (!(rtol >= 0.0) || !(atol >= 0.0))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_many(who, nrhs, b, u));
+  if (!info)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
+  int32_t status[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (status[1] < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
+  ManyLevel lv;
+  EQLB_TRY(primal_many_level(h, nrhs < MANY_R ? nrhs : MANY_R, lv));
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)h->ndofs;
+  HostCall s;
+  const auto d_b = s.in(host ? b : nullptr, nrhs * n);
+  const auto d_u = s.in(host ? static_cast<const double*>(u) : nullptr, nrhs * n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double* pb = host ? d_b.get() : b;
+  double* pu = host ? d_u.get() : u;
+  auto residual = [&](const ManyCols& c, const double* xb, const double* xu, double* r, bool only_fixed) {
+    return primal_many_residual(h, c, xb, xu, r, only_fixed, stream);
+  };
+  auto product = [&](const ManyCols& c) { return primal_many_product(h, c, stream); };
+  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
+  {
+    const ManyWork w = many_work(*h, nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R);
+    EQLB_TRY(pcg_solve_many(w, residual, product, JacobiStepsMany{w, stream}, pb + c0 * n, pu + c0 * n, rtol, atol,
+                            maxit, info + 8 * (size_t)c0, status[0], stream));
+  }
+  if (host)
+    s.out_prefix(u, d_u, nrhs * n);
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
 }
 EQLB_CATCH_ALL
 

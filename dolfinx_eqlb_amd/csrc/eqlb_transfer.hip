@@ -327,6 +327,110 @@ __global__ void __launch_bounds__(TR_THREADS) k_restrict(const ProlongArgs a, co
       o[i * BS + b] = good ? acc[i][b] : bad;
 }
 
+// k_restrict<Q, 1> on R columns: r2 [R][ndofs2] -> y_loc [R][ncells][ND].  The children, their owner bits, the indices
+// and the table rows are found once per cell and applied to the columns; the sum of a column runs in the order of the
+// single kernel.  Column k runs if bit k of mask is set and its stop flag done0[k done_stride] (done0: nullptr or the
+// flag of column 0 in device memory) is not; the others are neither read nor written.
+template <int Q, int R>
+__global__ void __launch_bounds__(TR_THREADS)
+k_restrict_many(const ProlongArgs a, uint32_t mask, const int32_t* __restrict__ done0, int done_stride, int64_t ystride)
+{
+#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
+  using T = eqlb_tables::Prolong<Q>;
+  constexpr int ND = nd_of(Q), NROW = T::NROW;
+  static constexpr DofNum<Q> num{}; // (indexed by a run-time n: a table in constant memory, not a private copy)
+  static_assert(T::ND == ND && NROW == (2 * Q + 1) * (Q + 1), "table shape");
+  __shared__ double sT[NROW * ND];
+  uint32_t live = 0;
+#pragma unroll
+  for (int k = 0; k < R; ++k)
+    if (((mask >> k) & 1u) && !(done0 && done0[(int64_t)k * done_stride]))
+      live |= 1u << k;
+  if (!live)
+    return;
+  for (int i = threadIdx.x; i < NROW * ND; i += TR_THREADS)
+    sT[i] = T::PT[i];
+  __syncthreads();
+  const int32_t c = blockIdx.x * TR_THREADS + threadIdx.x;
+  if (c >= a.ncells)
+    return;
+  const int32_t v[3] = {a.cell_nodes[3 * (int64_t)c], a.cell_nodes[3 * (int64_t)c + 1], a.cell_nodes[3 * (int64_t)c + 2]};
+  const int64_t first = a.coff[c];
+  const int nchild = (int)(a.coff[c + 1] - a.coff[c]); // 1 ... 4
+  double acc[ND][R];
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+      acc[i][k] = 0.0;
+  bool started = false, good = true;
+  for (int j = 0; j < nchild; ++j)
+  {
+    const int64_t c2 = first + j;
+    const int32_t w[3] = {a.cell_nodes2[3 * c2], a.cell_nodes2[3 * c2 + 1], a.cell_nodes2[3 * c2 + 2]};
+    int hx[3], hy[3];
+    const bool found = child_positions(a, v, w, hx, hy);
+    good = good && found;
+    // bit n: the child owns its local DOF n (interior DOFs: always)
+    uint32_t own = ~0u << (3 * Q);
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+      own |= (a.node_cells2[a.node_cells_off2[w[e]]] == c2) ? (1u << e) : 0u;
+    if constexpr (Q > 1)
+    {
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+      {
+        const int32_t f = a.cell_facets2[3 * c2 + e];
+        const uint32_t bits = ((1u << (Q - 1)) - 1u) << (3 + e * (Q - 1));
+        own |= (a.facet_cells2[a.facet_cells_off2[f]] == c2) ? bits : 0u;
+      }
+    }
+#pragma unroll 1
+    for (int n = 0; n < ND; ++n)
+    {
+      if (!((own >> n) & 1u))
+        continue;
+      const int32_t d2 = a.cell_dofs2[c2 * ND + n];
+      if (d2 < 0 || (int64_t)d2 >= a.ndofs2)
+      {
+        good = false;
+        continue;
+      }
+      const int lx = Q * hx[0] + num.a[n] * (hx[1] - hx[0]) + num.b[n] * (hx[2] - hx[0]);
+      const int ly = Q * hy[0] + num.a[n] * (hy[1] - hy[0]) + num.b[n] * (hy[2] - hy[0]);
+      const double* t = sT + (found ? ly * (2 * Q + 1) - ly * (ly - 1) / 2 + lx : 0) * ND;
+      double rv[R];
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        rv[k] = ((live >> k) & 1u) ? a.in[k * a.ndofs2 + d2] : 0.0;
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+      {
+        const double ti = t[i];
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+        {
+          const double term = ti * rv[k];
+          acc[i][k] = started ? acc[i][k] + term : term;
+        }
+      }
+      started = true;
+    }
+  }
+  const double bad = __longlong_as_double(0x7ff8000000000000ll);
+#pragma unroll
+  for (int k = 0; k < R; ++k)
+  {
+    if (!((live >> k) & 1u))
+      continue;
+    double* o = a.out + k * ystride + (int64_t)c * ND;
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+      o[i] = good ? acc[i][k] : bad;
+  }
+}
+
 // DG_0: every child takes the value of its parent
 __global__ void __launch_bounds__(TR_THREADS) k_prolong_dg0(const ProlongArgs a)
 {
@@ -461,6 +565,42 @@ int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int 
     EQLB_RESTRICT_CASE(4)
   }
 #undef EQLB_RESTRICT_CASE
+  HIP_TRY(hipGetLastError());
+  return EQLB_OK;
+}
+
+// the same on R <= 4 columns of r2 [R][ndofs2] (scalar spaces only)
+int launch_restrict_many(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int R, uint32_t mask,
+                         const int32_t* cell_dofs2, int64_t ndofs2, const double* r2, double* yloc, const int32_t* done0,
+                         int done_stride, hipStream_t stream)
+{
+  if (p < 1 || p > TR_PMAX || R < 1 || R > 4)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4, or %d columns outside 1 ... 4", who, p, R);
+  ProlongArgs a;
+  EQLB_TRY(common_args(who, plan, refined, 1, R, EQLB_MEM_DEVICE, a));
+  if (mesh_node_cells(refined, &a.node_cells2))
+    return EQLB_ERR_DEVICE;
+  a.cell_dofs2 = cell_dofs2;
+  a.ndofs2 = ndofs2;
+  a.in = r2;
+  a.out = yloc;
+  const int64_t ystride = (int64_t)a.ncells * nd_of(p);
+  const dim3 grid(grid_of(a.ncells, TR_THREADS)), block(TR_THREADS);
+#define EQLB_RESTRICT_MANY(QQ, RR)                                                                                     \
+  case 4 * QQ + RR:                                                                                                    \
+    hipLaunchKernelGGL((k_restrict_many<QQ, RR>), grid, block, 0, stream, a, mask, done0, done_stride, ystride);      \
+    break;
+#define EQLB_RESTRICT_MANY_Q(QQ)                                                                                       \
+  EQLB_RESTRICT_MANY(QQ, 1) EQLB_RESTRICT_MANY(QQ, 2) EQLB_RESTRICT_MANY(QQ, 3) EQLB_RESTRICT_MANY(QQ, 4)
+  switch (4 * p + R)
+  {
+    EQLB_RESTRICT_MANY_Q(1)
+    EQLB_RESTRICT_MANY_Q(2)
+    EQLB_RESTRICT_MANY_Q(3)
+    EQLB_RESTRICT_MANY_Q(4)
+  }
+#undef EQLB_RESTRICT_MANY_Q
+#undef EQLB_RESTRICT_MANY
   HIP_TRY(hipGetLastError());
   return EQLB_OK;
 }

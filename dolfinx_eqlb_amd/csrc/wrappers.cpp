@@ -277,6 +277,32 @@ struct Transfer
   }
 };
 
+// several right-hand sides: the column count of an array [nrhs][n], and the list of the columns' info dicts
+static int32_t many_columns(const darray& a, int64_t n, const char* who)
+{
+  if (a.ndim() != 2 || a.shape(0) < 1 || a.shape(1) != n)
+    throw std::runtime_error(std::string(who) + ": Input sizes does not match");
+  return (int32_t)a.shape(0);
+}
+static py::list many_info(const std::vector<double>& v)
+{
+  py::list out;
+  for (size_t c = 0; c + 8 <= v.size(); c += 8)
+  {
+    py::dict info;
+    info["iterations"] = (int64_t)v[c];
+    info["converged"] = (int64_t)v[c + 1];
+    info["nb"] = v[c + 2];
+    info["rnorm"] = v[c + 3];
+    info["replacements"] = (int64_t)v[c + 4];
+    info["breakdown"] = (int64_t)v[c + 5];
+    info["tol"] = v[c + 6];
+    info["facets_skipped"] = (int64_t)v[c + 7];
+    out.append(info);
+  }
+  return out;
+}
+
 // -div(coeff grad u) = f on the conforming P_p space of the mesh, in the numbering of Mesh.lagrange_dofmap: operator,
 // load, residual and Jacobi-preconditioned CG on the device (eqlb_primal_*), on host arrays
 struct PrimalPoisson
@@ -370,6 +396,27 @@ struct PrimalPoisson
     info["tol"] = v[6];
     info["facets_skipped"] = (int64_t)v[7];
     return py::make_tuple(x, info);
+  }
+  // Y [nrhs][ndofs]: row c is apply(U[c])
+  darray apply_many(darray U, bool masked) const
+  {
+    const int32_t nrhs = many_columns(U, ndofs, "PrimalPoisson.apply_many");
+    darray y({(py::ssize_t)nrhs, (py::ssize_t)ndofs});
+    check(eqlb_primal_apply_many(h, nrhs, U.data(), y.mutable_data(), masked ? 1 : 0, EQLB_MEM_HOST, nullptr));
+    return y;
+  }
+  // (U, infos): row c and infos[c] are solve(B[c], U[c])
+  py::tuple solve_many(darray B, darray U, double rtol, double atol, int maxit) const
+  {
+    const int32_t nrhs = many_columns(B, ndofs, "PrimalPoisson.solve_many");
+    if (many_columns(U, ndofs, "PrimalPoisson.solve_many") != nrhs)
+      throw std::runtime_error("PrimalPoisson.solve_many: Input sizes does not match");
+    darray x({(py::ssize_t)nrhs, (py::ssize_t)ndofs});
+    std::copy(U.data(), U.data() + (int64_t)nrhs * ndofs, x.mutable_data());
+    std::vector<double> v(8 * (size_t)nrhs, 0.0);
+    check(eqlb_primal_solve_many(h, nrhs, B.data(), x.mutable_data(), rtol, atol, maxit, v.data(), EQLB_MEM_HOST,
+                                 nullptr));
+    return py::make_tuple(x, many_info(v));
   }
 };
 
@@ -547,6 +594,27 @@ struct Multilevel
     info["tol"] = v[6];
     info["facets_skipped"] = (int64_t)v[7];
     return py::make_tuple(x, info);
+  }
+  // Z [nrhs][n]: row c is precondition(R[c]) (Poisson handles only)
+  darray precondition_many(darray R) const
+  {
+    const int32_t nrhs = many_columns(R, n.back(), "Multilevel.precondition_many");
+    darray z({(py::ssize_t)nrhs, (py::ssize_t)n.back()});
+    check(eqlb_hierarchy_precondition_many(h, nrhs, R.data(), z.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return z;
+  }
+  // (U, infos): row c and infos[c] are solve(B[c], U[c]) (Poisson handles only)
+  py::tuple solve_many(darray B, darray U, double rtol, double atol, int maxit) const
+  {
+    const int32_t nrhs = many_columns(B, n.back(), "Multilevel.solve_many");
+    if (many_columns(U, n.back(), "Multilevel.solve_many") != nrhs)
+      throw std::runtime_error("Multilevel.solve_many: Input sizes does not match");
+    darray x({(py::ssize_t)nrhs, (py::ssize_t)n.back()});
+    std::copy(U.data(), U.data() + (int64_t)nrhs * n.back(), x.mutable_data());
+    std::vector<double> v(8 * (size_t)nrhs, 0.0);
+    check(eqlb_hierarchy_solve_many(h, nrhs, B.data(), x.mutable_data(), rtol, atol, maxit, v.data(), EQLB_MEM_HOST,
+                                    nullptr));
+    return py::make_tuple(x, many_info(v));
   }
 };
 
@@ -1391,6 +1459,11 @@ PYBIND11_MODULE(_cpp, m)
            "(r, || r ||_2, nb): r = b - A u with 0 on the fixed rows")
       .def("solve", &PrimalPoisson::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
            py::arg("maxit") = 10000, "(u, info): PCG from the start u, whose fixed rows hold the Dirichlet values")
+      .def("apply_many", &PrimalPoisson::apply_many, py::arg("U"), py::arg("masked") = false,
+           "Y [nrhs][ndofs]: row c is apply(U[c]), bit for bit, in one call")
+      .def("solve_many", &PrimalPoisson::solve_many, py::arg("B"), py::arg("U"), py::arg("rtol") = 1e-8,
+           py::arg("atol") = 0.0, py::arg("maxit") = 10000,
+           "(U, infos): nrhs systems in one call; row c and infos[c] are solve(B[c], U[c]), bit for bit")
       .def_readonly("mesh", &PrimalPoisson::mesh)
       .def_readonly("p", &PrimalPoisson::p)
       .def_readonly("ndofs", &PrimalPoisson::ndofs);
@@ -1427,6 +1500,11 @@ PYBIND11_MODULE(_cpp, m)
       .def("precondition", &Multilevel::precondition, py::arg("r"), "z = M r on the finest level")
       .def("solve", &Multilevel::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
            py::arg("maxit") = 10000, "(u, info): the CG of the finest solver with the multilevel preconditioner")
+      .def("precondition_many", &Multilevel::precondition_many, py::arg("R"),
+           "Z [nrhs][n]: row c is precondition(R[c]), bit for bit, in one call (Poisson handles only)")
+      .def("solve_many", &Multilevel::solve_many, py::arg("B"), py::arg("U"), py::arg("rtol") = 1e-8,
+           py::arg("atol") = 0.0, py::arg("maxit") = 10000,
+           "(U, infos): nrhs systems in one call; row c and infos[c] are solve(B[c], U[c]) (Poisson handles only)")
       .def_readonly("nlevels", &Multilevel::nlevels)
       .def_readonly("bs", &Multilevel::bs);
 

@@ -28,7 +28,7 @@ One level is plain Jacobi.
 import numpy as np
 
 from ..mesh.transfer import prolong_lagrange, restrict_lagrange
-from .primal import PoissonOperator
+from .primal import PoissonOperator, pcg_columns
 
 
 class Hierarchy:
@@ -146,3 +146,10 @@ class Hierarchy:
         rt = op.residual(b, u)
         info["rnorm"] = float(np.sqrt(np.sum(rt * rt)))
         return u, info
+
+    def pcg_many(self, B, U, rtol=1e-8, atol=0.0, maxit=1000):
+        """Several right-hand sides B [nrhs][n] from the starts U [nrhs][n]: by definition the loop over the columns
+        of pcg (eqlb_hierarchy_solve_many; scalar hierarchies only).  Returns (U, [info_c])."""
+        if self.bs != 1:
+            raise ValueError("pcg_many: several right-hand sides are provided for the Poisson operator only")
+        return pcg_columns(self.pcg, B, U, rtol, atol, maxit)

@@ -372,6 +372,21 @@ class PoissonOperator:
         info["rnorm"] = float(np.sqrt(np.sum(rt * rt)))
         return u, info
 
+    def pcg_many(self, B, U, rtol=1e-8, atol=0.0, maxit=1000):
+        """Several right-hand sides B [nrhs][ndofs] from the starts U [nrhs][ndofs]: BY DEFINITION the loop over the
+        columns of pcg - eqlb_primal_solve_many has no statement of its own.  Returns (U, [info_c])."""
+        return pcg_columns(self.pcg, B, U, rtol, atol, maxit)
+
+
+def pcg_columns(pcg, B, U, rtol, atol, maxit):
+    """(U, [info_c]) with (U[c], info_c) = pcg(B[c], U[c], ...): the statement of the *_many solves."""
+    B = np.asarray(B, dtype=np.float64)
+    U = np.asarray(U, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] < 1 or U.shape != B.shape:
+        raise ValueError(f"pcg_many: B {B.shape} and U {U.shape} are not two arrays [nrhs][ndofs], nrhs >= 1")
+    out = [pcg(B[c], U[c], rtol=rtol, atol=atol, maxit=maxit) for c in range(B.shape[0])]
+    return np.stack([u for u, _ in out]), [info for _, info in out]
+
 
 def traction_load(mesh, p, bcs_rows, quadrature_degree=None):
     """b_extra [2 ndofs], blocked, of an elasticity problem with prescribed tractions: bcs_rows = (bcs_0, bcs_1), the

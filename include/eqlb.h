@@ -925,6 +925,31 @@ int eqlb_primal_residual(eqlb_primal_t* handle, const double* b, const double* u
 int eqlb_primal_solve(eqlb_primal_t* handle, const double* b, double* u, double rtol, double atol, int32_t maxit,
                       double* info, int32_t memspace, void* stream);
 
+/* Several right-hand sides in one call: nrhs independent systems A u_c = b_c on one handle, the same operator and the
+ * same Dirichlet mask.  Vectors are [nrhs][ndofs], one column after another - the layout eqlb_primal_flux_dg and
+ * eqlb_refine_prolong_lagrange read, so the output of one goes into the next unchanged.
+ * THE RULE: column c of eqlb_primal_apply_many is eqlb_primal_apply of u_c, column c of eqlb_primal_solve_many is
+ * eqlb_primal_solve of (b_c, u_c): the same bits of the result and the same info.  There is no tolerance in it.  Every
+ * column has its own alpha, beta, rho, tolerance, stop flag, replacement count and breakdown flag, and freezes at its
+ * stop flag as the single solve does - while other columns go on, while it waits for the host's true-residual check,
+ * and for good once it has converged, broken down (a NaN in b_c leaves the other columns' bits alone) or reached
+ * maxit.  The host sizes a batch by the live column with the fewest iterations left.
+ *   info      HOST [nrhs][8], a row as info of eqlb_primal_solve
+ * Any nrhs >= 1; the kernels carry at most four columns, a larger count runs as successive groups of four (columns
+ * are independent: the grouping does not show in the results).  The operator kernel reads the index row, the Jacobian,
+ * the coefficient and the table once per cell for the columns of a group; the streaming kernels carry the values of a
+ * DOF in all columns in one thread; the scalar kernel runs one block per column.  The work space for the columns
+ * belongs to the handle: grown by the first call that needs it (a wider group later grows it again), reused afterwards;
+ * nothing is allocated inside the iteration.  solve_many waits for the device; apply_many in DEVICE memory space
+ * enqueues and returns, unless it has to grow the work space.  Refused by name before anything is launched
+ * (EQLB_ERR_INVALID_ARGUMENT), and the next valid call works: null arguments, nrhs < 1, maxit < 1, rtol or atol negative
+ * or NaN, an unknown memory space, a handle without one fixed DOF.
+ * Not provided: several right-hand sides for the elasticity operator. */
+int eqlb_primal_apply_many(eqlb_primal_t* handle, int32_t nrhs, const double* u, double* y, int32_t masked,
+                           int32_t memspace, void* stream);
+int eqlb_primal_solve_many(eqlb_primal_t* handle, int32_t nrhs, const double* b, double* u, double rtol, double atol,
+                           int32_t maxit, double* info, int32_t memspace, void* stream);
+
 /* ---- The P_p^2 linear-elasticity problem on the device: the counterpart of eqlb_primal_* ------------------------------
  * -div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2, 1 <= p <= 4: the primal solve of demo/elasticity_adaptive/demo_cook.py,
  * in the non-dimensional form and with the pi_1 / cell_pi1 convention of eqlb_primal_stress_dg (per cell where cell_pi1
@@ -1026,6 +1051,19 @@ int eqlb_hierarchy_restrict(eqlb_hierarchy_t* handle, int32_t level, const doubl
 int eqlb_hierarchy_precondition(eqlb_hierarchy_t* handle, const double* r, double* z, int32_t memspace, void* stream);
 int eqlb_hierarchy_solve(eqlb_hierarchy_t* handle, const double* b, double* u, double rtol, double atol,
                          int32_t maxit, double* info, int32_t memspace, void* stream);
+/* Several right-hand sides on a hierarchy of Poisson handles, by the rule of eqlb_primal_solve_many: column c of
+ * eqlb_hierarchy_precondition_many is eqlb_hierarchy_precondition of r_c, column c of eqlb_hierarchy_solve_many is
+ * eqlb_hierarchy_solve of (b_c, u_c) - the same bits, the same info [nrhs][8].  Vectors [nrhs][ndofs_L], groups of at
+ * most four columns.  One application of the preconditioner stays at 2 + 4 L launches whatever the column count is
+ * (the prolongation takes the columns as its nrhs); only the scalar launches gain blocks.  The work space for the
+ * columns (r_l, z_l, t_l here, y_loc in every level's handle, the CG vectors in the finest) is grown by the first
+ * call that needs it and reused.  Refused by name before anything is launched, the next valid call works: null
+ * arguments, nrhs < 1, maxit < 1, rtol or atol negative or NaN, an unknown memory space, a finest level without one
+ * fixed DOF, and a hierarchy of elasticity handles (bs = 2): EQLB_ERR_UNSUPPORTED. */
+int eqlb_hierarchy_precondition_many(eqlb_hierarchy_t* handle, int32_t nrhs, const double* r, double* z,
+                                     int32_t memspace, void* stream);
+int eqlb_hierarchy_solve_many(eqlb_hierarchy_t* handle, int32_t nrhs, const double* b, double* u, double rtol,
+                              double atol, int32_t maxit, double* info, int32_t memspace, void* stream);
 
 /* Multi-GPU decomposition by node ownership (the reference has no distributed
  * equilibration, se/reconstruction.hpp:90 loops the owned nodes only): after the local sweep the

@@ -23,6 +23,15 @@ tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all ar
              iterations and the time to rtol 1e-8 from zero of the Jacobi entry and of the hierarchy in the same process,
              and an estimate of the launch share of an application: the time per launch of an application on the
              coarsest levels alone (up to 4 096 cells: nothing but launches), times the launches of the full one
+  --nrhs R ...  instead of the figures above, on the hierarchy of --multilevel (9 levels, 1M triangles): several right-hand
+             sides in one call against one call per right-hand side, in one process and on the same handles.  For every
+             degree, for the Jacobi entry (cpp.PrimalPoisson) and the hierarchy entry (cpp.Multilevel) and for every
+             R given: R calls of solve_raw - the only way before the *_many entries, which they leave alone - against
+             one solve_many_raw of the same R systems (b_c = (1 + c / 2) b plus 1 % noise of its own, rtol 1e-8 from
+             zero).  Each pair is repeated --repeats (>= 5) times after clock-settle probes as bench.py runs them
+             (repeated for at least 40 ms and until two agree within 1 %, at most 24); median and spread (max - min)
+             of the wall time of the calls, which wait for the device, are printed, and whether the gain of the
+             many-solve exceeds the spread of the R single calls
   --check-every LIB:N ...   the PCG of P_2 to rtol 1e-8 from zero once per library (builds of libeqlb_amd.so with
              -DEQLB_PRIMAL_CHECK_EVERY=N, tools/build_variant.sh NAME "-D..." eqlb_primal_solve), each in a child process
 Prints one line per figure and, last, one JSON line with all of them.  Nothing here is a pass/fail condition.
@@ -268,8 +277,22 @@ def timed_calls(torch, fn, n):
     return e0.elapsed_time(e1) / n
 
 
-def run_multilevel(args, cpp, torch, res):
-    """the figures of --multilevel"""
+def settle_probes(fn):
+    """untimed calls of fn for at least 40 ms and until two agree within 1 % (at most 24): the clocks after the idle
+    set-up, as bench.py settles them; returns the probe times in ms"""
+    probes, t0 = [], time.perf_counter()
+    while len(probes) < 24:
+        tp = time.perf_counter()
+        fn()
+        probes.append((time.perf_counter() - tp) * 1e3)
+        if len(probes) >= 2 and (time.perf_counter() - t0) * 1e3 >= 40.0 \
+                and abs(probes[-1] - probes[-2]) <= 0.01 * probes[-2]:
+            break
+    return probes
+
+
+def device_hierarchy(args, cpp):
+    """the levels of --multilevel: (DeviceMesh per level, Refinement per link, cells per level)"""
     from dolfinx_eqlb_amd.mesh import create_unit_square
     base = create_unit_square(args.coarse_n, shuffle_seed=3, perturb=0.15)
     L = max(1, int(round(np.log(1.0e6 / base.ncells) / np.log(4.0))))
@@ -283,7 +306,70 @@ def run_multilevel(args, cpp, torch, res):
         dms.append(refs[-1].dmesh)
     cells = [d.mesh.ncells for d in dms]
     say(f"hierarchy: {L + 1} levels, cells {cells} in {time.perf_counter() - t0:.1f} s")
-    small = max(2, sum(1 for c in cells if c <= 4096))   # levels of the launch-bound sub-hierarchy
+    return dms, refs, cells
+
+
+def run_many(args, cpp, torch, res):
+    """the figures of --nrhs"""
+    dms, refs, cells = device_hierarchy(args, cpp)
+    L = len(refs)
+    rmax = max(args.nrhs)
+    for p in args.degrees:
+        hs = []
+        for dm in dms[:-1]:
+            hs.append(cpp.PrimalPoisson(dm, p))
+            hs[-1].set_dirichlet(dm.mesh.boundary_facets())
+        top, b = make_problem(cpp, torch, dms[-1], p)
+        hs.append(top)
+        ml = cpp.Multilevel(hs, refs)
+        n = top.ndofs
+        gen = torch.Generator(device="cuda").manual_seed(p)
+        B = torch.stack([(1.0 + 0.5 * c) * b + 0.01 * b.abs().max()
+                         * torch.randn(n, dtype=torch.float64, device="cuda", generator=gen) for c in range(rmax)])
+        U = torch.zeros_like(B)
+        for name, h in (("jacobi", top), ("hierarchy", ml)):
+            for R in args.nrhs:
+                def singles():
+                    U.zero_()
+                    return [h.solve_raw(B[c].data_ptr(), U[c].data_ptr(), 1e-8, 0.0, args.maxit) for c in range(R)]
+
+                def many():
+                    U.zero_()
+                    return h.solve_many_raw(R, B.data_ptr(), U.data_ptr(), 1e-8, 0.0, args.maxit)
+
+                i_single, x_single = singles(), U[:R].clone()
+                i_many, x_many = many(), U[:R].clone()
+                same = bool(torch.equal(x_single.view(torch.int64), x_many.view(torch.int64))) and i_single == i_many
+                probes = settle_probes(many)
+                t_single, t_many = [], []
+                for _ in range(args.repeats):
+                    for fn, out in ((singles, t_single), (many, t_many)):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        out.append((time.perf_counter() - t0) * 1e3)
+                ms, mm = float(np.median(t_single)), float(np.median(t_many))
+                ss, sm = float(np.ptp(t_single)), float(np.ptp(t_many))
+                r = dict(levels=L + 1, cells=cells[-1], ndofs=n, nrhs=R, repeats=args.repeats,
+                         iterations=[i["iterations"] for i in i_many], converged=[i["converged"] for i in i_many],
+                         same_bits_and_info=same, settle_probes=len(probes),
+                         single_ms=dict(median=ms, spread=ss, all=t_single),
+                         many_ms=dict(median=mm, spread=sm, all=t_many), ratio=mm / ms,
+                         gain_exceeds_spread=bool(ms - mm > ss))
+                res[f"MANY_{name}_P{p}_R{R}"] = r
+                say(f"P_{p} {name} R = {R}: {R} x solve {ms:.2f} ms (spread {ss:.2f}), 1 x solve_many {mm:.2f} ms "
+                    f"(spread {sm:.2f}) = {mm / ms:.3f} of it over {args.repeats} repeats after {len(probes)} probes; "
+                    f"iterations {r['iterations']}; same bits and info: {same}; gain exceeds the spread of the single "
+                    f"calls: {r['gain_exceeds_spread']}")
+        ml.close()
+
+
+def run_multilevel(args, cpp, torch, res):
+    """the figures of --multilevel"""
+    dms, refs, cells = device_hierarchy(args, cpp)
+    L = len(refs)
+    small =max(2, sum(1 for c in cells if c <= 4096))   # levels of the launch-bound sub-hierarchy
     for elasticity in ([False, True] if args.elasticity else [False]):
         bs, P = (2, "E") if elasticity else (1, "P")
         for p in args.degrees:
@@ -347,11 +433,16 @@ def main():
     ap.add_argument("--elasticity", action="store_true", help="the same figures for cpp.PrimalElasticity as well")
     ap.add_argument("--multilevel", action="store_true", help="the figures of the multilevel preconditioner instead")
     ap.add_argument("--coarse-n", type=int, default=2, help="--multilevel: squares per side of the coarsest mesh")
+    ap.add_argument("--nrhs", type=int, nargs="+", default=[], metavar="R",
+                    help="several right-hand sides in one call against one call each, on the hierarchy of --multilevel")
+    ap.add_argument("--repeats", type=int, default=5, help="--nrhs: timed repeats of every pair (at least 5)")
     ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
     ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.products < 100:
         ap.error("--products: at least 100")
+    if args.repeats < 5 or any(r < 1 for r in args.nrhs):
+        ap.error("--repeats: at least 5; --nrhs: at least 1")
     res = {}
     if not args.check_only:
         for item in args.check_every:
@@ -373,6 +464,10 @@ def main():
     torch.cuda.init()
     from dolfinx_eqlb_amd import cpp
     from dolfinx_eqlb_amd.mesh import create_unit_square
+    if args.nrhs:
+        run_many(args, cpp, torch, res)
+        print(json.dumps(res))
+        return
     if args.multilevel:
         run_multilevel(args, cpp, torch, res)
         print(json.dumps(res))
