@@ -325,9 +325,61 @@ struct eqlb_elasticity;
 
 namespace eqlb
 {
+// ---- the columns of a P_p solve: 1 ... MANY_R right-hand sides in one launch (eqlb_primal_common.h states the rule) ----
+constexpr int MANY_R = 4; // columns of one group; more run group after group
+
+// scalars of the iteration of one column, in device memory
+struct PcgState
+{
+  double rho, pq, alpha, beta, rr, nb, tol, rtrue;
+  int32_t iters, done, breakdown, converged, replacements, pad;
+};
+
+// The columns a launch works on: R <= MANY_R columns lie one after another (vectors [R][n], y_loc [R][ncells nd_p bs],
+// block partials [R][2][G], states [R]).  Column c runs if bit c of mask is set and, with check, the stop flag of its
+// state st[c] is not set; the others are neither read nor written.  A launch that knows no state: check = 0, st = nullptr
+struct ManyCols
+{
+  int32_t R;
+  uint32_t mask;
+  int32_t check;
+  const PcgState* st; // [R] DEVICE
+};
+
+// bit c: column c runs in this launch; NC: the column slots of the kernel (R <= NC)
+template <int NC>
+__device__ __forceinline__ uint32_t cols_live(const ManyCols& c)
+{
+  uint32_t live = 0;
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+    if (k < c.R && ((c.mask >> k) & 1u) && !(c.check && c.st[k].done))
+      live |= 1u << k;
+  return live;
+}
+// column k of a kernel with NC slots runs (behind `if (!live) return;` the one column of NC = 1 does)
+template <int NC>
+__device__ __forceinline__ bool col_on(uint32_t live, int k)
+{
+  return NC == 1 || ((live >> k) & 1u);
+}
+
+// The work space of a solver handle for R columns of n rows each, all DEVICE: a view that owns nothing.  One column is
+// carved out of the handle's allocation at create; more (Poisson handles only) are grown by the first call that needs
+// them and reused afterwards
+struct PcgWork
+{
+  int64_t n; // rows of a column: bs * ndofs
+  int R;     // columns of the launches on it
+  const double* diag;
+  const uint8_t* fixed;
+  double *yloc, *r, *z, *d, *q, *part; // y_loc [R][ncells nd_p bs], vectors [R][n], block partials [R][2][G]
+  PcgState* st;                        // [R]
+};
+
 // A solver handle (eqlb_primal_t, bs = 1; eqlb_elasticity_t, bs = 2) as the hierarchy unit eqlb_multilevel.hip sees it:
-// a view that owns nothing.  All pointers DEVICE; vectors have bs * ndofs rows.  The launches are those of the handle's
-// own unit, on its own kernels.
+// a view that owns nothing.  All pointers DEVICE; vectors have bs * ndofs rows per column.  The launches are those of
+// the handle's own unit, on its own kernels; they work on the columns of c in the work space for c.R columns.
 struct SolverLevel
 {
   void* handle;
@@ -338,52 +390,23 @@ struct SolverLevel
   const double* diag;
   const uint8_t* fixed;
   const int32_t* status;    // [4] the status word of the mask (skipped ids, listed valid ones per component)
-  double* yloc;             // [ncells][nd_p][bs]: the input of the owner sum
-  double *r, *z, *d, *q, *part; // the vectors and block partials of the handle's CG
-  void* st;                 // its PcgState
-  // y = owner sum of yloc (0 on the fixed rows if masked); st: nullptr, or a PcgState whose stop flag skips the launch
-  hipError_t (*owner_sum)(void* handle, double* y, bool masked, const void* st, hipStream_t stream);
+  // the work space for R columns (R > 1: grown here if need be; an elasticity handle refuses); to be called before a
+  // launch on R columns
+  int (*work)(void* handle, int R, PcgWork& w);
+  // y = owner sum of y_loc (0 on the fixed rows if masked)
+  hipError_t (*owner_sum)(void* handle, const ManyCols& c, double* y, bool masked, hipStream_t stream);
   // r = b - A u (0 on the fixed rows; u^ instead of u with only_fixed), the block partials of r.r in part
-  hipError_t (*residual)(void* handle, const double* b, const double* u, double* r, bool only_fixed, hipStream_t stream);
-  // q = A d on the free rows, the block partials of d.q in part; returns at once when st says done
-  hipError_t (*product)(void* handle, hipStream_t stream);
+  hipError_t (*residual)(void* handle, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
+                         hipStream_t stream);
+  // q = A d on the free rows, the block partials of d.q in part
+  hipError_t (*product)(void* handle, const ManyCols& c, hipStream_t stream);
 };
 void primal_level(eqlb_primal* h, SolverLevel& v);
 void elasticity_level(eqlb_elasticity* h, SolverLevel& v);
-// eqlb_transfer.hip: the store pass of the restriction r = P^T r2 from `refined` to the mesh of `plan`, into
-// yloc [ncells][nd_p][bs]; DEVICE pointers, one launch, nothing waits.  done: nullptr, or a flag in device memory that
-// makes the kernel return at once when set
-int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const int32_t* cell_dofs2,
-                    int64_t ndofs2, const double* r2, double* yloc, const int32_t* done, hipStream_t stream);
-
-// ---- several right-hand sides in one call (eqlb_*_many; Poisson handles only) ----------------------------------------
-// The columns a launch works on: R <= 4 columns lie one after another (vectors [R][n], y_loc [R][ncells nd_p], block
-// partials [R][2][G], states [R]).  Column c runs if bit c of mask is set and, with check, the stop flag of its state
-// st[c] (a PcgState in device memory) is not set; the others are neither read nor written.
-struct ManyCols
-{
-  int32_t R;
-  uint32_t mask;
-  int32_t check;
-  const void* st;
-};
-// the work space of a Poisson handle for R columns, grown by the call that needs it and reused afterwards; all DEVICE
-struct ManyLevel
-{
-  double *yloc, *r, *z, *d, *q, *part;
-  void* st;
-};
-int primal_many_level(eqlb_primal* h, int R, ManyLevel& v);
-// the launches of the handle's unit on these columns, as owner_sum / residual / product of SolverLevel; vectors [R][n]
-hipError_t primal_many_owner_sum(eqlb_primal* h, const ManyCols& c, double* y, bool masked, hipStream_t stream);
-hipError_t primal_many_residual(eqlb_primal* h, const ManyCols& c, const double* b, const double* u, double* r,
-                                bool only_fixed, hipStream_t stream);
-hipError_t primal_many_product(eqlb_primal* h, const ManyCols& c, hipStream_t stream);
-// launch_restrict on the columns of c: r2 [R][ndofs2] into yloc [R][ncells nd_p]; done0 / done_stride: the stop flag
-// of column 0 and the distance to the next one in int32, or nullptr
-int launch_restrict_many(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int R, uint32_t mask,
-                         const int32_t* cell_dofs2, int64_t ndofs2, const double* r2, double* yloc, const int32_t* done0,
-                         int done_stride, hipStream_t stream);
+// eqlb_transfer.hip: the store pass of the restriction r = P^T r2 from `refined` to the mesh of `plan` on the columns
+// of c: r2 [R][ndofs2 bs] into yloc [R][ncells nd_p bs] (bs = 2: one column); DEVICE pointers, one launch, nothing waits
+int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const ManyCols& c,
+                    const int32_t* cell_dofs2, int64_t ndofs2, const double* r2, double* yloc, hipStream_t stream);
 } // namespace eqlb
 
 struct eqlb_se; // the handle behind eqlb_se_t / eqlb_ev_t: eqlb_handle.h (host code only)

@@ -1,12 +1,23 @@
-// What the P_p Poisson solve (eqlb_primal_solve.hip) and the P_p^2 elasticity solve (eqlb_primal_elasticity.hip) share:
-// the sum pass of the store-and-sum operator, the vector kernels and the scalar kernel of the Jacobi-preconditioned CG,
-// and the host loop that drives them.  Everything lies in an unnamed namespace: each unit gets its own copy, under the
-// names the kernels had while they lived in eqlb_primal_solve.hip.  The hierarchy unit (eqlb_multilevel.hip) takes the
-// state, the scalar and direction kernels and the host loop from here and brings its own preconditioner steps.
+// What the P_p Poisson solve (eqlb_primal_solve.hip), the P_p^2 elasticity solve (eqlb_primal_elasticity.hip) and the
+// hierarchy (eqlb_multilevel.hip) share: the sum pass of the store-and-sum operator, the vector kernels and the scalar
+// kernel of the preconditioned CG, and the host loop that drives them - ONE implementation for 1 ... MANY_R right-hand
+// sides (eqlb_*_many of include/eqlb.h); the single-vector entries are its one-column callers.  Everything lies in an
+// unnamed namespace: each unit gets its own copy.
+// THE RULE: column c of a many-solve is the single solve of (b_c, u_c) - the same bits, the same info.  What makes it hold:
+//  - one thread per DOF carries the values of that DOF in all columns: the grid is stream_blocks(n), the per-thread
+//    order over the DOFs and the block tree do not depend on the columns, so every inner product of a column is the
+//    same sum whatever runs beside it.  Block partials [R][2][G];
+//  - every column has its own PcgState; a kernel works on the columns of its ManyCols (eqlb_internal.h) and leaves the
+//    others alone, so a column freezes at its stop flag while the others go on, and waits untouched for the host;
+//  - k_pcg_scalar runs one block per column.
+// Vectors are [R][n], one column after another (the layout eqlb_primal_flux_dg and eqlb_refine_prolong_lagrange read);
+// R <= MANY_R columns per group, a larger count runs group after group.  The column slots of a kernel are its template
+// parameter NC (arrays [NC], shared [NC or 2 NC][PS_THREADS]): NC = 1 serves one column, NC = MANY_R two to four.
 //  k_primal_slots    builds the slot lists of the sum pass once at create (scalar numbering: both problems use it)
-//  k_primal_gather<BS>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
-//                    x[BS * dof + r].  BS = 1 is the kernel of the Poisson unit, instruction for instruction
-//  k_pcg_*           work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
+//  k_primal_gather<BS, NC>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
+//                    x[BS * dof + r]; columns for BS = 1 only
+//  k_pcg_*<NC>       work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
+//  k_pcg_scalar      the scalar steps; `ml`: the breakdown rule of a preconditioner that is no positive diagonal
 //  pcg_solve         the host side of the iteration on a PcgWork; the preconditioner enters through its `steps`
 //                    (JacobiSteps here; the hierarchy unit eqlb_multilevel.hip brings its own)
 #pragma once
@@ -32,13 +43,6 @@ enum CellMode
   CELL_OPERATOR = 0,
   CELL_DIAGONAL = 1,
   CELL_LOAD = 2
-};
-
-// scalars of the iteration, in device memory
-struct PcgState
-{
-  double rho, pq, alpha, beta, rr, nb, tol, rtrue;
-  int32_t iters, done, breakdown, converged, replacements, pad;
 };
 
 // the shapes of the space and the tables of the sum pass
@@ -112,157 +116,257 @@ enum GatherDot
 struct GatherArgs
 {
   SpaceArgs s;
-  const double* yloc;
+  const double* yloc;   // column c: yloc + c * ystride
   const uint8_t* fixed; // nullptr: the raw operator
-  const double* add;    // nullptr or b_extra
+  const double* add;    // nullptr or b_extra (one column)
   const double* b;      // with r: r = b - sum (0 on fixed rows)
   const double* w;      // DOT_W_Y
-  double *y, *r;        // each nullptr or [ndofs]
-  double* part;         // [gridDim.x] block partials of the inner product
+  double *y, *r;        // each nullptr or column 0 of [R][BS ndofs]; so are b, w
+  double* part;         // [R][2][gridDim.x] block partials of the inner product: channel 0 is written
   int32_t dot;
-  const PcgState* st;
+  ManyCols cols;
+  int64_t ystride;
 };
 
-// the sum pass with BS components per DOF: e = BS d + r runs over the blocked vectors, y_loc holds BS values per
-// (cell, local index), the component fastest.  BS = 1 is the sum pass of the Poisson problem as it was
-template <int BS>
+// the launch of a streaming kernel template on the columns of c: the one-column instance or the MANY_R-column one.
+// MAXC = 1 (inside a template: the steps of a unit whose handles hold one column) instantiates no wider kernel
+#define EQLB_LAUNCH_COLS(MAXC, KERNEL, R, n, stream, ...)                                                              \
+  do                                                                                                                   \
+  {                                                                                                                    \
+    if constexpr ((MAXC) == 1)                                                                                         \
+      hipLaunchKernelGGL(KERNEL<1>, dim3(stream_blocks(n)), dim3(PS_THREADS), 0, stream, __VA_ARGS__);                 \
+    else if ((R) == 1)                                                                                                 \
+      hipLaunchKernelGGL(KERNEL<1>, dim3(stream_blocks(n)), dim3(PS_THREADS), 0, stream, __VA_ARGS__);                 \
+    else                                                                                                               \
+      hipLaunchKernelGGL(KERNEL<MANY_R>, dim3(stream_blocks(n)), dim3(PS_THREADS), 0, stream, __VA_ARGS__);            \
+  } while (0)
+
+// the sum pass with BS components per DOF on the live columns: e = BS d + r runs over the blocked vectors, y_loc holds
+// BS values per (cell, local index), the component fastest.  The slot range of a DOF is found once; the sum of a
+// column runs in the order of the slot list
+template <int BS, int NC>
 __global__ void __launch_bounds__(PS_THREADS) k_primal_gather(const GatherArgs a)
 {
 #pragma clang fp contract(off)
-  __shared__ double sh[1][PS_THREADS];
-  if (a.st && a.st->done)
+  static_assert(BS == 1 || NC == 1, "columns for scalar spaces only");
+  __shared__ double sh[NC][PS_THREADS];
+  const uint32_t live = cols_live<NC>(a.cols);
+  if (!live)
     return;
   const SpaceArgs& s = a.s;
   const int t = threadIdx.x;
-  const int64_t nshared = (int64_t)s.nnodes + (int64_t)s.nfacets * s.ne;
-  double acc = 0.0;
-  for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + t; e < s.ndofs * BS; e += (int64_t)gridDim.x * PS_THREADS)
+  const int64_t nshared = (int64_t)s.nnodes + (int64_t)s.nfacets * s.ne, n = s.ndofs * BS;
+  double acc[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+    acc[k] = 0.0;
+  for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + t; e < n; e += (int64_t)gridDim.x * PS_THREADS)
   {
     const int64_t d = e / BS;
     const int r = (int)(e - d * BS);
-    double v;
+    int64_t beg = 0;
+    int cnt = 0;
     if (d < nshared)
-    {
-      int64_t beg;
-      int cnt;
       slot_range(s, d, beg, cnt);
-      v = cnt > 0 ? a.yloc[(int64_t)s.slots[beg] * BS + r] : 0.0;
-      for (int k = 1; k < cnt; ++k)
-        v = v + a.yloc[(int64_t)s.slots[beg + k] * BS + r];
-    }
     else
     {
       const int64_t q = d - nshared, c = q / s.ni;
-      v = a.yloc[(c * s.nd + 3 + 3 * s.ne + (q - c * s.ni)) * BS + r];
+      beg = c * s.nd + 3 + 3 * s.ne + (q - c * s.ni); // (the one entry of an interior DOF)
     }
-    if (a.add)
-      v = v + a.add[e];
-    const bool fx = a.fixed && a.fixed[e];
-    const double yv = fx ? 0.0 : v;
-    if (a.y)
-      a.y[e] = yv;
-    double rv = 0.0;
-    if (a.r)
+    bool fx = false;
+    if constexpr (NC > 1)
+      fx = a.fixed && a.fixed[e]; // (once for the columns; the one-column instance asks behind its sum)
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
     {
-      rv = fx ? 0.0 : a.b[e] - v;
-      a.r[e] = rv;
+      if (!col_on<NC>(live, k))
+        continue;
+      const double* yl = a.yloc + k * a.ystride;
+      double v;
+      if (d < nshared)
+      {
+        v = cnt > 0 ? yl[(int64_t)s.slots[beg] * BS + r] : 0.0;
+        for (int j = 1; j < cnt; ++j)
+          v = v + yl[(int64_t)s.slots[beg + j] * BS + r];
+      }
+      else
+        v = yl[beg * BS + r];
+      const int64_t x = k * n + e;
+      if constexpr (NC == 1)
+      {
+        if (a.add)
+          v = v + a.add[x];
+        fx = a.fixed && a.fixed[e];
+      }
+      const double yv = fx ? 0.0 : v;
+      if (a.y)
+        a.y[x] = yv;
+      double rv = 0.0;
+      if (a.r)
+      {
+        rv = fx ? 0.0 : a.b[x] - v;
+        a.r[x] = rv;
+      }
+      if (a.dot == DOT_W_Y)
+        acc[k] = acc[k] + a.w[x] * yv;
+      else if (a.dot == DOT_R_R)
+        acc[k] = acc[k] + rv * rv;
     }
-    if (a.dot == DOT_W_Y)
-      acc = acc + a.w[e] * yv;
-    else if (a.dot == DOT_R_R)
-      acc = acc + rv * rv;
   }
   if (a.dot == DOT_NONE)
     return;
-  sh[0][t] = acc;
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+    sh[k][t] = acc[k];
   __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 1, PS_THREADS)
-  if (t == 0)
-    a.part[blockIdx.x] = sh[0][0];
+  EQLB_BLOCK_TREE_SUM(sh, t, NC, PS_THREADS)
+  if (t < NC && col_on<NC>(live, t))
+    a.part[(int64_t)(2 * t) * gridDim.x + blockIdx.x] = sh[t][0];
 }
 
-// ---- vector kernels of the iteration (grid-stride, block partials in a fixed order) -------------------------------
-// z = r / diag on the free rows (0 on the fixed ones); partials of r.r and r.z: part[0][block], part[1][block]
+// ---- vector kernels of the iteration (grid-stride, block partials in a fixed order): the columns of a DOF in one
+// thread.  Channel j of column k: sh[2 k + j], part[(2 k + j) G + block] ----------------------------------------------
+// z = r / diag on the free rows (0 on the fixed ones); partials of r.r and r.z: channels 0 and 1
+template <int NC>
 __global__ void __launch_bounds__(PS_THREADS)
-k_pcg_precond(int64_t n, const double* __restrict__ r, const double* __restrict__ diag,
+k_pcg_precond(int64_t n, const ManyCols cols, const double* __restrict__ r, const double* __restrict__ diag,
               const uint8_t* __restrict__ fixed, double* __restrict__ z, double* __restrict__ part)
 {
 #pragma clang fp contract(off)
-  __shared__ double sh[2][PS_THREADS];
+  __shared__ double sh[2 * NC][PS_THREADS];
+  const uint32_t live = cols_live<NC>(cols);
+  if (!live)
+    return;
   const int t = threadIdx.x, G = gridDim.x;
-  double a0 = 0.0, a1 = 0.0;
+  double a0[NC], a1[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+    a0[k] = a1[k] = 0.0;
   for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)G * PS_THREADS)
   {
-    const double rv = r[d], zv = fixed[d] ? 0.0 : rv / diag[d];
-    z[d] = zv;
-    a0 = a0 + rv * rv;
-    a1 = a1 + rv * zv;
+    const bool fx = fixed[d];
+    const double dg = diag[d];
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+    {
+      if (!col_on<NC>(live, k))
+        continue;
+      const double rv = r[k * n + d], zv = fx ? 0.0 : rv / dg;
+      z[k * n + d] = zv;
+      a0[k] = a0[k] + rv * rv;
+      a1[k] = a1[k] + rv * zv;
+    }
   }
-  sh[0][t] = a0;
-  sh[1][t] = a1;
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+  {
+    sh[2 * k][t] = a0[k];
+    sh[2 * k + 1][t] = a1[k];
+  }
   __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 2, PS_THREADS)
-  if (t < 2)
+  EQLB_BLOCK_TREE_SUM(sh, t, 2 * NC, PS_THREADS)
+  if (t < 2 * NC && col_on<NC>(live, t / 2))
     part[(int64_t)t * G + blockIdx.x] = sh[t][0];
 }
 
 // u += alpha p, r -= alpha q, z = r / diag on the free rows; the fixed rows are not touched; partials as k_pcg_precond
+template <int NC>
 __global__ void __launch_bounds__(PS_THREADS)
-k_pcg_update(int64_t n, const PcgState* __restrict__ st, const double* __restrict__ p, const double* __restrict__ q,
+k_pcg_update(int64_t n, const ManyCols cols, const double* __restrict__ p, const double* __restrict__ q,
              const double* __restrict__ diag, const uint8_t* __restrict__ fixed, double* __restrict__ u,
              double* __restrict__ r, double* __restrict__ z, double* __restrict__ part)
 {
 #pragma clang fp contract(off)
-  __shared__ double sh[2][PS_THREADS];
-  if (st->done)
+  __shared__ double sh[2 * NC][PS_THREADS];
+  const uint32_t live = cols_live<NC>(cols);
+  if (!live)
     return;
   const int t = threadIdx.x, G = gridDim.x;
-  const double alpha = st->alpha;
-  double a0 = 0.0, a1 = 0.0;
+  double alpha[NC], a0[NC], a1[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+  {
+    alpha[k] = col_on<NC>(live, k) ? cols.st[k].alpha : 0.0;
+    a0[k] = a1[k] = 0.0;
+  }
   for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)G * PS_THREADS)
   {
     if (fixed[d])
       continue; // (r and z are 0 there since the start)
-    u[d] = u[d] + alpha * p[d];
-    const double rv = r[d] - alpha * q[d], zv = rv / diag[d];
-    r[d] = rv;
-    z[d] = zv;
-    a0 = a0 + rv * rv;
-    a1 = a1 + rv * zv;
+    const double dg = diag[d];
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+    {
+      if (!col_on<NC>(live, k))
+        continue;
+      const int64_t e = k * n + d;
+      u[e] = u[e] + alpha[k] * p[e];
+      const double rv = r[e] - alpha[k] * q[e], zv = rv / dg;
+      r[e] = rv;
+      z[e] = zv;
+      a0[k] = a0[k] + rv * rv;
+      a1[k] = a1[k] + rv * zv;
+    }
   }
-  sh[0][t] = a0;
-  sh[1][t] = a1;
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+  {
+    sh[2 * k][t] = a0[k];
+    sh[2 * k + 1][t] = a1[k];
+  }
   __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, 2, PS_THREADS)
-  if (t < 2)
+  EQLB_BLOCK_TREE_SUM(sh, t, 2 * NC, PS_THREADS)
+  if (t < 2 * NC && col_on<NC>(live, t / 2))
     part[(int64_t)t * G + blockIdx.x] = sh[t][0];
 }
 
 // p = z + beta p (first: p = z)
+template <int NC>
 __global__ void __launch_bounds__(PS_THREADS)
-k_pcg_direction(int64_t n, const PcgState* __restrict__ st, int first, const double* __restrict__ z,
-                double* __restrict__ p)
+k_pcg_direction(int64_t n, const ManyCols cols, int first, const double* __restrict__ z, double* __restrict__ p)
 {
 #pragma clang fp contract(off)
-  if (st->done)
+  const uint32_t live = cols_live<NC>(cols);
+  if (!live)
     return;
-  const double beta = first ? 0.0 : st->beta;
+  double beta[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+    beta[k] = (!first && col_on<NC>(live, k)) ? cols.st[k].beta : 0.0;
   for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
-    p[d] = first ? z[d] : z[d] + beta * p[d];
+  {
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+    {
+      if (!col_on<NC>(live, k))
+        continue;
+      const int64_t e = k * n + d;
+      p[e] = first ? z[e] : z[e] + beta[k] * p[e];
+    }
+  }
 }
 
 // u = u^: the free rows set to 0 (nothing to solve)
+template <int NC>
 __global__ void __launch_bounds__(PS_THREADS)
-k_pcg_clear_free(int64_t n, const uint8_t* __restrict__ fixed, double* __restrict__ u)
+k_pcg_clear_free(int64_t n, const ManyCols cols, const uint8_t* __restrict__ fixed, double* __restrict__ u)
 {
+  const uint32_t live = cols_live<NC>(cols);
+  if (!live)
+    return;
   for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
     if (!fixed[d])
-      u[d] = 0.0;
+    {
+#pragma unroll
+      for (int k = 0; k < NC; ++k)
+        if (col_on<NC>(live, k))
+          u[k * n + d] = 0.0;
+    }
 }
 
 enum ScalarStep
 {
-  STEP_NORM = 0,    // out[0] = sqrt(channel 0)
+  STEP_NORM = 0,    // out[0] = sqrt(channel 0); knows no state
   STEP_NB = 1,      // nb = sqrt(channel 0), tol = max(rtol nb, atol)
   STEP_START = 2,   // rr, rho from the start residual; done if it is within tol already
   STEP_ALPHA = 3,   // pq = channel 0: breakdown unless > 0, else alpha = rho / pq
@@ -271,15 +375,21 @@ enum ScalarStep
   STEP_REPLACE = 6  // after the true residual replaced r: beta = rho_new / rho, rho = rho_new, the iteration goes on
 };
 
-// one block: the channels' totals over the G block partials by the same tree, then thread 0 moves the state
+// One block per column: block k forms the channels' totals over the G block partials of column k by the same tree,
+// then its thread 0 moves the state of column k.  mask picks the columns; the stop flag is looked at per step.  ml: the
+// preconditioner is no positive diagonal - breakdown where the iteration would go on with r.z <= 0 or NaN
 __global__ void __launch_bounds__(PS_THREADS)
-k_pcg_scalar(int step, int G, const double* __restrict__ part, PcgState* __restrict__ st, double rtol, double atol,
-             double* __restrict__ out)
+k_pcg_scalar(int step, int ml, int G, uint32_t mask, const double* __restrict__ part_, PcgState* __restrict__ st_,
+             double rtol, double atol, double* __restrict__ out)
 {
   __shared__ double sh[2][PS_THREADS];
   const int t = threadIdx.x;
+  if (!((mask >> blockIdx.x) & 1u))
+    return;
+  PcgState* st = st_ + blockIdx.x; // (not read at STEP_NORM)
+  const double* part = part_ + (int64_t)blockIdx.x * 2 * G;
   const bool two = step == STEP_START || step == STEP_BETA || step == STEP_REPLACE;
-  if (st && st->done && step != STEP_TRUE && step != STEP_NORM && step != STEP_REPLACE)
+  if (step != STEP_NORM && step != STEP_TRUE && step != STEP_REPLACE && st->done)
     return;
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -295,6 +405,7 @@ k_pcg_scalar(int step, int G, const double* __restrict__ part, PcgState* __restr
   if (t != 0)
     return;
   const double s0 = sh[0][0], s1 = sh[1][0];
+  bool goes_on = two; // the iteration goes on with s1 as its r.z
   switch (step)
   {
   case STEP_NORM:
@@ -308,7 +419,10 @@ k_pcg_scalar(int step, int G, const double* __restrict__ part, PcgState* __restr
     st->rr = s0;
     st->rho = s1;
     if (sqrt(s0) <= st->tol)
+    {
       st->done = 1;
+      goes_on = false;
+    }
     break;
   case STEP_ALPHA:
     st->pq = s0;
@@ -324,7 +438,10 @@ k_pcg_scalar(int step, int G, const double* __restrict__ part, PcgState* __restr
     st->rr = s0;
     st->iters += 1;
     if (sqrt(s0) <= st->tol)
+    {
       st->done = 1; // (rho stays that of the last direction: STEP_REPLACE needs it if the true residual is above tol)
+      goes_on = false;
+    }
     else
     {
       st->beta = s1 / st->rho;
@@ -342,151 +459,235 @@ k_pcg_scalar(int step, int G, const double* __restrict__ part, PcgState* __restr
     st->replacements += 1;
     st->done = 0;
   }
+  if (ml && goes_on && !(s1 > 0.0))
+  {
+    st->breakdown = 1;
+    st->done = 1;
+  }
 }
 
 // ---- host side of the iteration ------------------------------------------------------------------------------------
-// the vectors of one handle: n rows (the blocked length), all in device memory
-struct PcgWork
+inline ManyCols work_cols(const PcgWork& w, uint32_t mask, bool check)
 {
-  int64_t n;
-  const double* diag;
-  const uint8_t* fixed;
-  double *r, *z, *d, *q, *part;
-  PcgState* st;
-};
+  return ManyCols{w.R, mask, check ? 1 : 0, w.st};
+}
 
-inline hipError_t launch_scalar(const PcgWork& w, int step, double rtol, double atol, double* out, hipStream_t stream)
+// the scalar step on the columns of mask (STEP_NORM: the total of column 0 into out, no state)
+inline hipError_t launch_scalar(const PcgWork& w, uint32_t mask, int step, int ml, double rtol, double atol, double* out,
+                                hipStream_t stream)
 {
-  hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(PS_THREADS), 0, stream, step, stream_blocks(w.n), w.part, w.st, rtol,
-                     atol, out);
+  hipLaunchKernelGGL(k_pcg_scalar, dim3(w.R), dim3(PS_THREADS), 0, stream, step, ml, stream_blocks(w.n), mask,
+                     static_cast<const double*>(w.part), w.st, rtol, atol, out);
   return hipGetLastError();
 }
 
 // The two places where the preconditioner enters the iteration, for z = r / diag: both kernels fuse it
+template <int MAXC> // the columns the handles of the unit hold at the most: 1 or MANY_R
 struct JacobiSteps
 {
-  static constexpr int check_every = PRIMAL_CHECK_EVERY; // iterations between two reads of the state by the host
+  static constexpr int max_cols = MAXC;
+  static constexpr int check_every = PRIMAL_CHECK_EVERY; // iterations between two reads of the states by the host
   const PcgWork& w;
   hipStream_t stream;
   // z from the r of the start or of a replacement, the partials of r.r and r.z, the scalar step (STEP_START / _REPLACE)
-  hipError_t restart(int step, double rtol, double atol) const
+  hipError_t restart(const ManyCols& c, int step, double rtol, double atol) const
   {
-    hipLaunchKernelGGL(k_pcg_precond, dim3(stream_blocks(w.n)), dim3(PS_THREADS), 0, stream, w.n, w.r, w.diag, w.fixed,
-                       w.z, w.part);
-    return launch_scalar(w, step, rtol, atol, nullptr, stream);
+    EQLB_LAUNCH_COLS(MAXC, k_pcg_precond, w.R, w.n, stream, w.n, c, static_cast<const double*>(w.r), w.diag, w.fixed, w.z,
+                     w.part);
+    return launch_scalar(w, c.mask, step, 0, rtol, atol, nullptr, stream);
   }
   // u += alpha d, r -= alpha q, z from the new r, the partials of r.r and r.z, STEP_BETA
-  hipError_t advance(double* pu, double rtol, double atol) const
+  hipError_t advance(const ManyCols& c, double* pu, double rtol, double atol) const
   {
-    hipLaunchKernelGGL(k_pcg_update, dim3(stream_blocks(w.n)), dim3(PS_THREADS), 0, stream, w.n, w.st, w.d, w.q, w.diag,
-                       w.fixed, pu, w.r, w.z, w.part);
-    return launch_scalar(w, STEP_BETA, rtol, atol, nullptr, stream);
+    EQLB_LAUNCH_COLS(MAXC, k_pcg_update, w.R, w.n, stream, w.n, c, static_cast<const double*>(w.d),
+                     static_cast<const double*>(w.q), w.diag, w.fixed, pu, w.r, w.z, w.part);
+    return launch_scalar(w, c.mask, STEP_BETA, 0, rtol, atol, nullptr, stream);
   }
 };
 
-// The preconditioned CG of eqlb_primal_solve / eqlb_elasticity_solve / eqlb_hierarchy_solve behind their argument checks.
-//   residual(b, u, r, only_fixed)  enqueues r = b - A u (0 on the fixed rows; u^ instead of u with only_fixed) and
-//                                  leaves the block partials of r.r in w.part
-//   product(st)                    enqueues q = A d on the free rows with the block partials of d.q in w.part
-//   steps                          the preconditioner: restart(step, rtol, atol) and advance(u, rtol, atol) as JacobiSteps
-// skipped: the facet ids the mask skipped (info[7]).  b, u in host memory with `host` are staged here.
+// The preconditioned CG of eqlb_primal_solve / eqlb_elasticity_solve / eqlb_hierarchy_solve and their _many forms behind
+// the argument checks, column by column, for one group of w.R <= MANY_R columns; b, u DEVICE [R][n], info HOST [R][8].
+//   residual(cols, b, u, r, only_fixed)  enqueues r = b - A u (0 on the fixed rows; u^ instead of u with only_fixed) on
+//                                        the columns of `cols` and leaves the block partials of r.r in w.part
+//   product(cols)                        enqueues q = A d on the free rows with the block partials of d.q in w.part
+//   steps                                the preconditioner: restart(cols, step, rtol, atol) and
+//                                        advance(cols, u, rtol, atol) as JacobiSteps
+// skipped: the facet ids the mask skipped (info[7]).
+// At each read of the states the columns whose flag is set get the true residual; of these the ones above tolerance get
+// the replacement and the restart, alone; a column that has converged, broken down or reached maxit is retired and no
+// later launch names it.  Inside a batch a column stops at its own flag, so the batch may be sized by the live column
+// with the fewest iterations left: the others go on in the next one.
 template <class Residual, class Product, class Steps>
-int pcg_solve(const PcgWork& w, Residual&& residual, Product&& product, const Steps& steps, const double* b, double* u,
-              double rtol, double atol, int32_t maxit, double* info, int32_t skipped, bool host, hipStream_t stream)
+int pcg_solve(const PcgWork& w, Residual&& residual, Product&& product, const Steps& steps, const double* pb, double* pu,
+              double rtol, double atol, int32_t maxit, double* info, int32_t skipped, hipStream_t stream)
 {
-  const size_t n = (size_t)w.n;
+  const int R = w.R;
+  const uint32_t all = (1u << R) - 1u;
+  PcgState hs[MANY_R]{}, tmp[MANY_R]{};
+  bool have_true[MANY_R] = {false, false, false, false}; // q holds the true residual of the column's u, the state its norm
+  hipError_t err = hipSuccess;
+  auto note = [&](hipError_t e) {
+    if (err == hipSuccess)
+      err = e;
+  };
+  auto in = [](uint32_t mask, int c) { return ((mask >> c) & 1u) != 0; };
+  auto read_states = [&](uint32_t mask) {
+    note(hipMemcpyAsync(tmp, w.st, (size_t)R * sizeof(PcgState), hipMemcpyDeviceToHost, stream));
+    note(hipStreamSynchronize(stream));
+    for (int c = 0; c < R && err == hipSuccess; ++c)
+      if (in(mask, c))
+        hs[c] = tmp[c];
+  };
+  auto true_residual = [&](uint32_t mask) {
+    note(residual(work_cols(w, mask, false), pb, pu, w.q, false));
+    note(launch_scalar(w, mask, STEP_TRUE, 0, rtol, atol, nullptr, stream));
+  };
+  auto direction = [&](uint32_t mask, int first) {
+    EQLB_LAUNCH_COLS(Steps::max_cols, k_pcg_direction, R, w.n, stream, w.n, work_cols(w, mask, true), first,
+                     static_cast<const double*>(w.z), w.d);
+    note(hipGetLastError());
+  };
+  note(hipMemsetAsync(w.st, 0, (size_t)R * sizeof(PcgState), stream));
+  note(residual(work_cols(w, all, false), pb, pu, w.q, true));
+  note(launch_scalar(w, all, STEP_NB, 0, rtol, atol, nullptr, stream));
+  note(residual(work_cols(w, all, false), pb, pu, w.r, false));
+  note(steps.restart(work_cols(w, all, false), STEP_START, rtol, atol));
+  direction(all, 1);
+  read_states(all);
+  uint32_t live = all, nothing = 0;
+  for (int c = 0; c < R; ++c)
+    if (hs[c].tol == 0.0 && hs[c].nb == 0.0)
+      nothing |= 1u << c;
+  if (err == hipSuccess && nothing)
+  {
+    // nothing to solve in these columns: u^ is the solution
+    EQLB_LAUNCH_COLS(Steps::max_cols, k_pcg_clear_free, R, w.n, stream, w.n, work_cols(w, nothing, false), w.fixed, pu);
+    note(hipGetLastError());
+    for (int c = 0; c < R; ++c)
+      if (in(nothing, c))
+      {
+        hs[c].converged = 1;
+        hs[c].rtrue = 0.0;
+        have_true[c] = true;
+      }
+    live &= ~nothing;
+  }
+  // Every pass ends with a batch in which each live column takes at least one iteration or raises its flag for good
+  // (breakdown), and a column is retired at iters >= maxit: maxit passes at the most, and two for the ends.  With no
+  // replacement it is ceil(maxit / check_every) passes.
+  const int max_passes = maxit + 2;
+  for (int pass = 0; pass < max_passes && err == hipSuccess && live; ++pass)
+  {
+    uint32_t flagged = 0;
+    for (int c = 0; c < R; ++c)
+      if (in(live, c))
+      {
+        if (hs[c].breakdown || hs[c].converged)
+          live &= ~(1u << c);
+        else if (hs[c].done)
+          flagged |= 1u << c;
+      }
+    if (flagged)
+    {
+      // the recurrence residual of these columns reached tol: the true one decides
+      true_residual(flagged);
+      read_states(flagged);
+      uint32_t replace = 0;
+      for (int c = 0; c < R; ++c)
+        if (in(flagged, c))
+        {
+          have_true[c] = true;
+          if (hs[c].converged || hs[c].iters >= maxit)
+            live &= ~(1u << c);
+          else
+            replace |= 1u << c;
+        }
+      if (replace)
+      {
+        for (int c = 0; c < R; ++c)
+          if (in(replace, c))
+          {
+            note(hipMemcpyAsync(w.r + c * w.n, w.q + c * w.n, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice,
+                                stream));
+            have_true[c] = false;
+          }
+        note(steps.restart(work_cols(w, replace, false), STEP_REPLACE, rtol, atol));
+        direction(replace, 0);
+      }
+    }
+    int batch = Steps::check_every;
+    for (int c = 0; c < R; ++c)
+      if (in(live, c))
+      {
+        if (hs[c].iters >= maxit)
+          live &= ~(1u << c);
+        else if (maxit - hs[c].iters < batch)
+          batch = maxit - hs[c].iters;
+      }
+    if (!live)
+      break;
+    const ManyCols cols = work_cols(w, live, true);
+    for (int it = 0; it < batch; ++it)
+    {
+      note(product(cols));
+      note(launch_scalar(w, live, STEP_ALPHA, 0, rtol, atol, nullptr, stream));
+      note(steps.advance(cols, pu, rtol, atol));
+      direction(live, 0);
+    }
+    for (int c = 0; c < R; ++c)
+      if (in(live, c))
+        have_true[c] = false;
+    read_states(live);
+  }
+  uint32_t last = 0;
+  for (int c = 0; c < R; ++c)
+    if (!have_true[c])
+      last |= 1u << c;
+  if (last)
+  {
+    int conv[MANY_R];
+    for (int c = 0; c < R; ++c)
+      conv[c] = hs[c].converged;
+    true_residual(last);
+    read_states(last);
+    for (int c = 0; c < R; ++c)
+      hs[c].converged = conv[c]; // (a run that ended at maxit or broke down is not converged, whatever its last residual)
+  }
+  HIP_TRY(err);
+  for (int c = 0; c < R; ++c)
+  {
+    double* o = info + 8 * c;
+    o[0] = (double)hs[c].iters;
+    o[1] = (double)hs[c].converged;
+    o[2] = hs[c].nb;
+    o[3] = hs[c].rtrue;
+    o[4] = (double)hs[c].replacements;
+    o[5] = (double)hs[c].breakdown;
+    o[6] = hs[c].tol;
+    o[7] = (double)skipped;
+  }
+  return EQLB_OK;
+}
+
+// b, u [nrhs][n] of a solve entry, staged when they lie in host memory, handed to `group(R, b, u, info)` in groups of
+// R <= MANY_R columns (DEVICE pointers; info HOST [R][8]); u is copied back at the end
+template <class Group>
+int pcg_solve_groups(int64_t n_, int32_t nrhs, const double* b, double* u, double* info, bool host, hipStream_t stream,
+                     Group&& group)
+{
+  const size_t n = (size_t)n_;
   HostCall s;
-  const auto d_b = s.in(host ? b : nullptr, n);
-  const auto d_u = s.in(host ? static_cast<const double*>(u) : nullptr, n);
+  const auto d_b = s.in(host ? b : nullptr, nrhs * n);
+  const auto d_u = s.in(host ? static_cast<const double*>(u) : nullptr, nrhs * n);
   if (host)
     HIP_TRY(s.upload(stream));
   const double* pb = host ? d_b.get() : b;
   double* pu = host ? d_u.get() : u;
-  PcgState* st = w.st;
-  const int G = stream_blocks(w.n);
-  const dim3 grid(G), block(PS_THREADS);
-  const int64_t nn = w.n;
-  PcgState hs{};
-  auto read_state = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(&hs, st, sizeof(PcgState), hipMemcpyDeviceToHost, stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(stream);
-  };
-  // the true residual of the current u into q, its norm into the state
-  auto true_residual = [&]() {
-    s.note(residual(pb, pu, w.q, false));
-    s.note(launch_scalar(w, STEP_TRUE, rtol, atol, nullptr, stream));
-  };
-  s.note(hipMemsetAsync(st, 0, sizeof(PcgState), stream));
-  // nb and tol from u^
-  s.note(residual(pb, pu, w.q, true));
-  s.note(launch_scalar(w, STEP_NB, rtol, atol, nullptr, stream));
-  // the start: r = b - A u, z from r, rho, p = z
-  s.note(residual(pb, pu, w.r, false));
-  s.note(steps.restart(STEP_START, rtol, atol));
-  hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 1, w.z, w.d);
-  s.note(hipGetLastError());
-  s.note(read_state());
-  bool have_true = false; // q holds the true residual of the current u and the state its norm
-  if (s.finish(stream) == hipSuccess && hs.tol == 0.0 && hs.nb == 0.0)
-  {
-    // nothing to solve: u^ is the solution (the free rows of u are set to 0 by the start residual's mask)
-    hipLaunchKernelGGL(k_pcg_clear_free, grid, block, 0, stream, nn, w.fixed, pu);
-    s.note(hipGetLastError());
-    hs.converged = 1;
-    hs.rtrue = 0.0;
-    have_true = true;
-  }
-  else
-  {
-    while (s.finish(stream) == hipSuccess && !hs.breakdown && !hs.converged)
-    {
-      if (hs.done)
-      {
-        // the recurrence residual reached tol: the true one decides
-        true_residual();
-        s.note(read_state());
-        have_true = true;
-        if (hs.converged || hs.iters >= maxit)
-          break;
-        s.note(hipMemcpyAsync(w.r, w.q, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        s.note(steps.restart(STEP_REPLACE, rtol, atol));
-        hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 0, w.z, w.d);
-        s.note(hipGetLastError());
-        have_true = false;
-      }
-      if (hs.iters >= maxit)
-        break;
-      const int batch = (maxit - hs.iters < Steps::check_every) ? maxit - hs.iters : Steps::check_every;
-      for (int it = 0; it < batch; ++it)
-      {
-        s.note(product(st));
-        s.note(launch_scalar(w, STEP_ALPHA, rtol, atol, nullptr, stream));
-        s.note(steps.advance(pu, rtol, atol));
-        hipLaunchKernelGGL(k_pcg_direction, grid, block, 0, stream, nn, st, 0, w.z, w.d);
-        s.note(hipGetLastError());
-      }
-      have_true = false;
-      s.note(read_state());
-    }
-  }
-  if (!have_true)
-  {
-    true_residual();
-    const int conv = hs.converged;
-    s.note(read_state());
-    hs.converged = conv; // (a run that ended at maxit or broke down is not converged, whatever its last residual)
-  }
+  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
+    EQLB_TRY(group(nrhs - c0 < MANY_R ? (int)(nrhs - c0) : MANY_R, pb + c0 * n, pu + c0 * n, info + 8 * (size_t)c0));
   if (host)
-    s.out_prefix(u, d_u, n);
+    s.out_prefix(u, d_u, nrhs * n);
   HIP_TRY(s.finish(stream));
-  info[0] = (double)hs.iters;
-  info[1] = (double)hs.converged;
-  info[2] = hs.nb;
-  info[3] = hs.rtrue;
-  info[4] = (double)hs.replacements;
-  info[5] = (double)hs.breakdown;
-  info[6] = hs.tol;
-  info[7] = (double)skipped;
   return EQLB_OK;
 }
 } // namespace

@@ -20,7 +20,8 @@
 //    would not fit a static block; 128 cells need 31 KB + 5.4 KB.  The tables (S0, S2, Cross: 3 nd_p^2 doubles; or
 //    Load<P, D>) are read as a broadcast, the index rows of the workgroup move through LDS as one contiguous piece, and
 //    so do the output rows y_loc [ncells][nd_p][2].
-//  k_primal_gather<2>, k_pcg_*, pcg_solve: eqlb_primal_common.h, on n = 2 ndofs rows with the mask per row.
+//  k_primal_gather<2, 1>, k_pcg_*<1>, pcg_solve: eqlb_primal_common.h, on one column of n = 2 ndofs rows with the
+//    mask per row.
 #include "eqlb_device_common.h"
 #include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_primal_common.h"
@@ -283,7 +284,9 @@ namespace eqlb
 {
 namespace
 {
-ElastCellArgs cell_args(const eqlb_elasticity& h, const double* u, bool only_fixed, const PcgState* st)
+const ManyCols ONE_COLUMN{1, 1u, 0, nullptr}; // a launch that knows no state (the handle has one column)
+
+ElastCellArgs cell_args(const eqlb_elasticity& h, const ManyCols& c, const double* u, bool only_fixed)
 {
   ElastCellArgs a{};
   a.ncells = h.space.ncells;
@@ -295,61 +298,61 @@ ElastCellArgs cell_args(const eqlb_elasticity& h, const double* u, bool only_fix
   a.fixed = h.fixed;
   a.only_fixed = only_fixed ? 1 : 0;
   a.yloc = h.yloc;
-  a.st = st;
+  a.st = c.check ? c.st : nullptr;
   return a;
 }
 
-GatherArgs gather_args(const eqlb_elasticity& h, bool masked, const PcgState* st)
+GatherArgs gather_args(const eqlb_elasticity& h, const ManyCols& c, bool masked)
 {
   GatherArgs g{};
   g.s = h.space;
   g.yloc = h.yloc;
   g.fixed = masked ? h.fixed.get() : nullptr;
   g.part = h.part;
-  g.st = st;
+  g.cols = c;
   return g;
 }
 
 hipError_t launch_gather(const eqlb_elasticity& h, const GatherArgs& g, hipStream_t stream)
 {
-  hipLaunchKernelGGL(k_primal_gather<2>, dim3(stream_blocks(2 * h.ndofs)), dim3(PS_THREADS), 0, stream, g);
+  hipLaunchKernelGGL((k_primal_gather<2, 1>), dim3(stream_blocks(2 * h.ndofs)), dim3(PS_THREADS), 0, stream, g);
   return hipGetLastError();
 }
 
 PcgWork pcg_work(const eqlb_elasticity& h)
 {
-  return PcgWork{2 * h.ndofs, h.diag, h.fixed, h.r, h.z, h.d, h.q, h.part, h.st};
+  return PcgWork{2 * h.ndofs, 1, h.diag, h.fixed, h.yloc, h.r, h.z, h.d, h.q, h.part, h.st};
+}
+
+// y = owner sum of y_loc (masked or raw); y DEVICE
+hipError_t enqueue_owner_sum(const eqlb_elasticity& h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
+{
+  GatherArgs g = gather_args(h, c, masked);
+  g.y = y;
+  return launch_gather(h, g, stream);
 }
 
 // y = A u (masked or raw); all pointers DEVICE
 hipError_t enqueue_apply(const eqlb_elasticity& h, const double* u, double* y, bool masked, hipStream_t stream)
 {
-  hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, u, false, nullptr), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, masked, nullptr);
-  g.y = y;
-  return launch_gather(h, g, stream);
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, ONE_COLUMN, u, false), stream);
+  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, y, masked, stream);
 }
 
 hipError_t enqueue_diagonal(const eqlb_elasticity& h, double* out, hipStream_t stream)
 {
-  hipError_t e = launch_cell<CELL_DIAGONAL>(h.p, 0, cell_args(h, nullptr, false, nullptr), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, false, nullptr);
-  g.y = out;
-  return launch_gather(h, g, stream);
+  const hipError_t e = launch_cell<CELL_DIAGONAL>(h.p, 0, cell_args(h, ONE_COLUMN, nullptr, false), stream);
+  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, out, false, stream);
 }
 
 // r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in h.part
-hipError_t enqueue_residual(const eqlb_elasticity& h, const double* b, const double* u, double* r, bool only_fixed,
-                            hipStream_t stream)
+hipError_t enqueue_residual(const eqlb_elasticity& h, const ManyCols& c, const double* b, const double* u, double* r,
+                            bool only_fixed, hipStream_t stream)
 {
-  hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, u, only_fixed, nullptr), stream);
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, c, u, only_fixed), stream);
   if (e != hipSuccess)
     return e;
-  GatherArgs g = gather_args(h, true, nullptr);
+  GatherArgs g = gather_args(h, c, true);
   g.b = b;
   g.r = r;
   g.dot = DOT_R_R;
@@ -357,12 +360,12 @@ hipError_t enqueue_residual(const eqlb_elasticity& h, const double* b, const dou
 }
 
 // q = A d on the free rows (the direction d of the handle), the block partials of d.q in h.part
-hipError_t enqueue_product(const eqlb_elasticity& h, const PcgState* st, hipStream_t stream)
+hipError_t enqueue_product(const eqlb_elasticity& h, const ManyCols& c, hipStream_t stream)
 {
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, h.d, false, st), stream);
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, c, h.d, false), stream);
   if (e != hipSuccess)
     return e;
-  GatherArgs g = gather_args(h, true, st);
+  GatherArgs g = gather_args(h, c, true);
   g.y = h.q;
   g.w = h.d;
   g.dot = DOT_W_Y;
@@ -390,21 +393,22 @@ void elasticity_level(eqlb_elasticity* h, SolverLevel& v)
   v.diag = h->diag;
   v.fixed = h->fixed;
   v.status = h->status;
-  v.yloc = h->yloc;
-  v.r = h->r, v.z = h->z, v.d = h->d, v.q = h->q, v.part = h->part;
-  v.st = h->st.get();
-  v.owner_sum = [](void* hh, double* y, bool masked, const void* st, hipStream_t stream) {
-    const eqlb_elasticity& s = *static_cast<eqlb_elasticity*>(hh);
-    GatherArgs g = gather_args(s, masked, static_cast<const PcgState*>(st));
-    g.y = y;
-    return launch_gather(s, g, stream);
+  v.work = [](void* hh, int R, PcgWork& w) {
+    if (R != 1)
+      return fail(EQLB_ERR_UNSUPPORTED,
+                  "elasticity_level: several right-hand sides are provided for Poisson handles (bs = 1) only");
+    w = pcg_work(*static_cast<eqlb_elasticity*>(hh));
+    return (int)EQLB_OK;
   };
-  v.residual = [](void* hh, const double* b, const double* u, double* r, bool only_fixed, hipStream_t stream) {
-    return enqueue_residual(*static_cast<eqlb_elasticity*>(hh), b, u, r, only_fixed, stream);
+  v.owner_sum = [](void* hh, const ManyCols& c, double* y, bool masked, hipStream_t stream) {
+    return enqueue_owner_sum(*static_cast<eqlb_elasticity*>(hh), c, y, masked, stream);
   };
-  v.product = [](void* hh, hipStream_t stream) {
-    const eqlb_elasticity& s = *static_cast<eqlb_elasticity*>(hh);
-    return enqueue_product(s, s.st.get(), stream);
+  v.residual = [](void* hh, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
+                  hipStream_t stream) {
+    return enqueue_residual(*static_cast<eqlb_elasticity*>(hh), c, b, u, r, only_fixed, stream);
+  };
+  v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
+    return enqueue_product(*static_cast<eqlb_elasticity*>(hh), c, stream);
   };
 }
 } // namespace eqlb
@@ -575,8 +579,8 @@ try
   const auto d_b = s.out(host ? b : nullptr, n);
   if (host)
     HIP_TRY(s.upload(stream));
-  s.note(launch_cell<CELL_LOAD>(h->p, degree_dg, cell_args(*h, host ? d_f.get() : rhs_dg, false, nullptr), stream));
-  GatherArgs g = gather_args(*h, false, nullptr);
+  s.note(launch_cell<CELL_LOAD>(h->p, degree_dg, cell_args(*h, ONE_COLUMN, host ? d_f.get() : rhs_dg, false), stream));
+  GatherArgs g = gather_args(*h, ONE_COLUMN, false);
   g.add = host ? d_e.get() : b_extra;
   g.y = host ? d_b.get() : b;
   s.note(launch_gather(*h, g, stream));
@@ -654,12 +658,12 @@ try
   if (pn)
   {
     // the reference norm first, into the work vector q: the residual proper then leaves r as the caller sees it
-    s.note(enqueue_residual(*h, pb, pu, h->q, true, stream));
-    s.note(launch_scalar(pcg_work(*h), STEP_NORM, 0.0, 0.0, pn + 1, stream));
+    s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, h->q, true, stream));
+    s.note(launch_scalar(pcg_work(*h), 1u, STEP_NORM, 0, 0.0, 0.0, pn + 1, stream));
   }
-  s.note(enqueue_residual(*h, pb, pu, host ? d_r.get() : r, false, stream));
+  s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, host ? d_r.get() : r, false, stream));
   if (pn)
-    s.note(launch_scalar(pcg_work(*h), STEP_NORM, 0.0, 0.0, pn, stream));
+    s.note(launch_scalar(pcg_work(*h), 1u, STEP_NORM, 0, 0.0, 0.0, pn, stream));
   HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }
@@ -688,13 +692,16 @@ try
     if (status[1 + r] < 1)
       return fail(EQLB_ERR_INVALID_ARGUMENT,
                   "%s: singular: component %d has no Dirichlet DOF (eqlb_elasticity_set_dirichlet first)", who, r);
-  auto residual = [&](const double* pb, const double* pu, double* r, bool only_fixed) {
-    return enqueue_residual(*h, pb, pu, r, only_fixed, stream);
+  auto residual = [&](const ManyCols& c, const double* pb, const double* pu, double* r, bool only_fixed) {
+    return enqueue_residual(*h, c, pb, pu, r, only_fixed, stream);
   };
-  auto product = [&](const PcgState* st) { return enqueue_product(*h, st, stream); };
+  auto product = [&](const ManyCols& c) { return enqueue_product(*h, c, stream); };
   const PcgWork w = pcg_work(*h);
-  return pcg_solve(w, residual, product, JacobiSteps{w, stream}, b, u, rtol, atol, maxit, info, status[0],
-                   memspace == EQLB_MEM_HOST, stream);
+  return pcg_solve_groups(w.n, 1, b, u, info, memspace == EQLB_MEM_HOST, stream,
+                          [&](int, const double* pb, double* pu, double* pinfo) {
+                            return pcg_solve(w, residual, product, JacobiSteps<1>{w, stream}, pb, pu, rtol, atol, maxit,
+                                             pinfo, status[0], stream);
+                          });
 }
 EQLB_CATCH_ALL
 

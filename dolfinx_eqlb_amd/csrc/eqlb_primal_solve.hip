@@ -6,7 +6,7 @@
 // operator, load, diagonal and residual reproduce the numpy statement bit for bit.
 //
 // The operator is a store pass plus a per-destination sum pass - no atomics, one fixed order of operations per value:
-//  k_primal_cell<P, MODE, D>  one thread per cell, PS_THREADS cells per workgroup.  The table (Stiff<P>: 675 doubles,
+//  k_primal_cell<P, MODE, D, R>  one thread per cell, PS_THREADS cells per workgroup.  The table (Stiff<P>: 675 doubles,
 //    5.4 KB at P = 4; Load<P, D>) is staged in LDS once per workgroup and read as a broadcast; the index rows of the
 //    workgroup's cells are read as one contiguous piece and handed out through LDS; the nd_p values of a cell are
 //    staged in LDS (odd row stride: no bank conflict of the thread-per-row writes) and written as the contiguous piece
@@ -24,13 +24,12 @@
 // remaining kernels of a batch return at once, so the result does not depend on how often the host looks: it reads
 // the state every EQLB_PRIMAL_CHECK_EVERY iterations.  Nothing is allocated inside the iteration.
 // The sum pass, the CG kernels and the host loop lie in eqlb_primal_common.h, which eqlb_primal_elasticity.hip shares.
-// Several right-hand sides in one call (eqlb_primal_apply_many, eqlb_primal_solve_many): k_primal_cell_many<P, R> here,
-// the other column kernels and the host loop in eqlb_primal_many.h, which states the rule; the work space for the
-// columns is grown on demand (primal_many_level).  The single-vector entries keep their kernels.
+// Several right-hand sides in one call (eqlb_primal_apply_many, eqlb_primal_solve_many) run on the same kernels and
+// the same host loop: k_primal_cell<P, CELL_OPERATOR, 0, R> here, the rest in eqlb_primal_common.h, which states the
+// rule.  The work space for one column is carved at create, the one for more is grown on demand (primal_work).
 #include "eqlb_device_common.h"
 #include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
 #include "eqlb_primal_common.h" // the sum pass, the kernels and the host loop of the CG: shared with the elasticity unit
-#include "eqlb_primal_many.h" // their column variants: several right-hand sides in one call
 #include "eqlb_tables_gen.h"
 
 #include <climits>
@@ -45,24 +44,31 @@ struct CellArgs
   int32_t ncells;
   const int32_t* cell_dofs; // [ncells][nd_p]
   const double *cellJ, *coeff;
-  const double* u;      // operator: [ndofs]; load: rhs_dg [ncells][nd_d]
+  const double* u;      // operator: column 0 of [R][ndofs], column c at u + c * ustride; load: rhs_dg [ncells][nd_d]
   const uint8_t* fixed; // operator, only_fixed: the free rows of u read as 0
   int32_t only_fixed;
-  double* yloc; // [ncells][nd_p]
-  const PcgState* st;
+  double* yloc; // [ncells][nd_p], column c at yloc + c * ystride
 };
 
-template <int P, int MODE, int D>
-__global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a)
+// MODE = CELL_OPERATOR runs on R columns: the index row, J, the coefficient and the table are read once and applied to
+// the columns of u.  A table entry is read from LDS once and multiplied into the R sums, each of which runs in the one
+// order.  With R > 1 the R rows of a cell stay in registers (R nd_p solution values, R nd_p results) and go out column
+// by column through the one sbuf, so the LDS footprint does not depend on R; with R = 1 the row goes straight to sbuf.
+// Columns that do not run (ManyCols) are neither read nor written.  Diagonal and load know one column.
+template <int P, int MODE, int D, int R>
+__global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a, const ManyCols cols, int64_t ustride,
+                                                            int64_t ystride)
 {
 #pragma clang fp contract(off) // the statement rounds every product and every sum on its own
   constexpr int NP = nd_of(P), ND = nd_of(D), S = NP | 1;
   constexpr int NTAB = (MODE == CELL_LOAD) ? NP * ND : 3 * NP * NP;
   static_assert(eqlb_tables::Stiff<P>::ND == NP && eqlb_tables::Load<P, D>::NP == NP && eqlb_tables::Load<P, D>::ND == ND,
                 "table shape");
+  static_assert(R >= 1 && R <= MANY_R && (R == 1 || MODE == CELL_OPERATOR), "columns for the operator only");
   __shared__ double sT[NTAB];
-  __shared__ double sbuf[PS_THREADS * S]; // first the index rows of the workgroup, then its output rows
-  if (a.st && a.st->done)
+  __shared__ double sbuf[PS_THREADS * S]; // first the index rows of the workgroup, then its output rows, a column at a time
+  const uint32_t live = cols_live<R>(cols);
+  if (!live)
     return;
   const int t = threadIdx.x;
   const int64_t base = (int64_t)blockIdx.x * PS_THREADS;
@@ -88,6 +94,15 @@ __global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a)
       idx[i] = active ? sidx[t * NP + i] : 0;
   }
   __syncthreads(); // the table is staged; the index rows are in registers: sbuf takes the output rows
+  [[maybe_unused]] double out[R > 1 ? R : 1][R > 1 ? NP : 1];
+  if constexpr (R > 1)
+  {
+#pragma unroll
+    for (int c = 0; c < R; ++c)
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+        out[c][i] = 0.0;
+  }
   if (active)
   {
     const double2* Jp = reinterpret_cast<const double2*>(a.cellJ + 4 * (base + t));
@@ -117,157 +132,85 @@ __global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a)
       const double K00 = r1.y * idet, K01 = -r0.y * idet, K10 = -r1.x * idet, K11 = r0.x * idet;
       const double C00 = K00 * K00 + K01 * K01, C01 = K00 * K10 + K01 * K11, C11 = K10 * K10 + K11 * K11;
       const double w = (a.coeff ? a.coeff[base + t] : 1.0) * adet;
-      [[maybe_unused]] double uu[NP];
+      [[maybe_unused]] double uu[R][NP];
       if constexpr (MODE == CELL_OPERATOR)
       {
 #pragma unroll
         for (int i = 0; i < NP; ++i)
         {
-          const double v = a.u[idx[i]];
-          uu[i] = (a.only_fixed && !a.fixed[idx[i]]) ? 0.0 : v;
+          const bool zero = a.only_fixed && !a.fixed[idx[i]];
+#pragma unroll
+          for (int c = 0; c < R; ++c)
+          {
+            const double v = col_on<R>(live, c) ? a.u[c * ustride + idx[i]] : 0.0;
+            uu[c][i] = zero ? 0.0 : v;
+          }
         }
       }
 #pragma unroll
       for (int i = 0; i < NP; ++i)
       {
-        double tm[3];
+        double tm[R][3];
 #pragma unroll
         for (int m = 0; m < 3; ++m)
         {
           const double* row = sT + (m * NP + i) * NP;
           if constexpr (MODE == CELL_DIAGONAL)
-            tm[m] = row[i];
+            tm[0][m] = row[i];
           else
           {
-            double s = row[0] * uu[0];
+            double s[R];
+            {
+              const double e = row[0];
+#pragma unroll
+              for (int c = 0; c < R; ++c)
+                s[c] = e * uu[c][0];
+            }
 #pragma unroll
             for (int j = 1; j < NP; ++j)
-              s = s + row[j] * uu[j];
-            tm[m] = s;
+            {
+              const double e = row[j];
+#pragma unroll
+              for (int c = 0; c < R; ++c)
+                s[c] = s[c] + e * uu[c][j];
+            }
+#pragma unroll
+            for (int c = 0; c < R; ++c)
+              tm[c][m] = s[c];
           }
-        }
-        sbuf[t * S + i] = w * ((C00 * tm[0] + C01 * tm[1]) + C11 * tm[2]);
-      }
-    }
-  }
-  __syncthreads();
-  double* o = a.yloc + base * NP;
-  for (int e = t; e < nloc * NP; e += PS_THREADS)
-    o[e] = sbuf[(e / NP) * S + (e % NP)];
-}
-
-// The store pass of the operator on R columns: k_primal_cell<P, CELL_OPERATOR, 0> with the index row, J, the
-// coefficient and the table read once and applied to the columns of u [R][ndofs].  A table entry is read from LDS once
-// and multiplied into the R sums, each of which runs in the order of the single kernel.  The R rows of a cell stay in
-// registers (R nd_p solution values, R nd_p results) and go out column by column through the one sbuf, so the LDS
-// footprint is that of the single kernel.  Columns that do not run (ManyCols) are neither read nor written.
-template <int P, int R>
-__global__ void __launch_bounds__(PS_THREADS) k_primal_cell_many(const CellArgs a, const ManyCols cols, int64_t ustride,
-                                                                 int64_t ystride)
-{
-#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
-  constexpr int NP = nd_of(P), S = NP | 1;
-  constexpr int NTAB = 3 * NP * NP;
-  static_assert(eqlb_tables::Stiff<P>::ND == NP && R >= 1 && R <= MANY_R, "table shape");
-  __shared__ double sT[NTAB];
-  __shared__ double sbuf[PS_THREADS * S]; // first the index rows of the workgroup, then its output rows, a column at a time
-  const uint32_t live = many_live(cols);
-  if (!live)
-    return;
-  const int t = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * PS_THREADS;
-  const int nloc = (a.ncells - base < PS_THREADS) ? (int)(a.ncells - base) : PS_THREADS;
-  const bool active = t < nloc;
-  for (int i = t; i < NTAB; i += PS_THREADS)
-    sT[i] = eqlb_tables::Stiff<P>::ST[i];
-  int32_t idx[NP];
-  {
-    int32_t* sidx = reinterpret_cast<int32_t*>(sbuf);
-    const int32_t* rows = a.cell_dofs + base * NP;
-    for (int e = t; e < nloc * NP; e += PS_THREADS)
-      sidx[e] = rows[e];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-      idx[i] = active ? sidx[t * NP + i] : 0;
-  }
-  __syncthreads(); // the table is staged; the index rows are in registers: sbuf takes the output rows
-  double out[R][NP];
-#pragma unroll
-  for (int c = 0; c < R; ++c)
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-      out[c][i] = 0.0;
-  if (active)
-  {
-    const double2* Jp = reinterpret_cast<const double2*>(a.cellJ + 4 * (base + t));
-    const double2 r0 = Jp[0], r1 = Jp[1]; // J00 J01 | J10 J11
-    const double det = r0.x * r1.y - r0.y * r1.x;
-    const double adet = fabs(det);
-    const double idet = 1.0 / det;
-    const double K00 = r1.y * idet, K01 = -r0.y * idet, K10 = -r1.x * idet, K11 = r0.x * idet;
-    const double C00 = K00 * K00 + K01 * K01, C01 = K00 * K10 + K01 * K11, C11 = K10 * K10 + K11 * K11;
-    const double w = (a.coeff ? a.coeff[base + t] : 1.0) * adet;
-    double uu[R][NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-    {
-      const bool zero = a.only_fixed && !a.fixed[idx[i]];
-#pragma unroll
-      for (int c = 0; c < R; ++c)
-      {
-        const double v = ((live >> c) & 1u) ? a.u[c * ustride + idx[i]] : 0.0;
-        uu[c][i] = zero ? 0.0 : v;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-    {
-      double tm[R][3];
-#pragma unroll
-      for (int m = 0; m < 3; ++m)
-      {
-        const double* row = sT + (m * NP + i) * NP;
-        double s[R];
-        {
-          const double e = row[0];
-#pragma unroll
-          for (int c = 0; c < R; ++c)
-            s[c] = e * uu[c][0];
-        }
-#pragma unroll
-        for (int j = 1; j < NP; ++j)
-        {
-          const double e = row[j];
-#pragma unroll
-          for (int c = 0; c < R; ++c)
-            s[c] = s[c] + e * uu[c][j];
         }
 #pragma unroll
         for (int c = 0; c < R; ++c)
-          tm[c][m] = s[c];
+        {
+          const double v = w * ((C00 * tm[c][0] + C01 * tm[c][1]) + C11 * tm[c][2]);
+          if constexpr (R == 1)
+            sbuf[t * S + i] = v;
+          else
+            out[c][i] = v;
+        }
       }
-#pragma unroll
-      for (int c = 0; c < R; ++c)
-        out[c][i] = w * ((C00 * tm[c][0] + C01 * tm[c][1]) + C11 * tm[c][2]);
     }
   }
 #pragma unroll
   for (int c = 0; c < R; ++c)
   {
-    if (!((live >> c) & 1u)) // (the same in every thread)
+    if (!col_on<R>(live, c)) // (the same in every thread)
       continue;
-    if (active)
+    if constexpr (R > 1)
     {
+      if (active)
+      {
 #pragma unroll
-      for (int i = 0; i < NP; ++i)
-        sbuf[t * S + i] = out[c][i];
+        for (int i = 0; i < NP; ++i)
+          sbuf[t * S + i] = out[c][i];
+      }
     }
     __syncthreads();
     double* o = a.yloc + c * ystride + base * NP;
     for (int e = t; e < nloc * NP; e += PS_THREADS)
       o[e] = sbuf[(e / NP) * S + (e % NP)];
-    __syncthreads(); // (the next column overwrites sbuf)
+    if constexpr (R > 1)
+      __syncthreads(); // (the next column overwrites sbuf)
   }
 }
 
@@ -294,43 +237,64 @@ k_primal_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t nnodes,
 
 
 // ---- host side ------------------------------------------------------------------------------------------------
+// the launch on the columns of c: the load by its DG degree d, the operator by its column count, the diagonal as it is
 template <int P, int MODE>
-hipError_t launch_cell_d(int d, const CellArgs& a, hipStream_t stream)
+hipError_t launch_cell_p(int d, const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride,
+                         hipStream_t stream)
 {
   const dim3 grid(grid_of(a.ncells, PS_THREADS)), block(PS_THREADS);
-  if constexpr (MODE != CELL_LOAD)
-    hipLaunchKernelGGL((k_primal_cell<P, MODE, 0>), grid, block, 0, stream, a);
-  else
+#define EQLB_CELL(DD, RR)                                                                                              \
+  hipLaunchKernelGGL((k_primal_cell<P, MODE, DD, RR>), grid, block, 0, stream, a, c, ustride, ystride)
+  if constexpr (MODE == CELL_LOAD)
     switch (d)
     {
     case 0:
-      hipLaunchKernelGGL((k_primal_cell<P, MODE, 0>), grid, block, 0, stream, a);
+      EQLB_CELL(0, 1);
       break;
     case 1:
-      hipLaunchKernelGGL((k_primal_cell<P, MODE, 1>), grid, block, 0, stream, a);
+      EQLB_CELL(1, 1);
       break;
     case 2:
-      hipLaunchKernelGGL((k_primal_cell<P, MODE, 2>), grid, block, 0, stream, a);
+      EQLB_CELL(2, 1);
       break;
     default:
-      hipLaunchKernelGGL((k_primal_cell<P, MODE, 3>), grid, block, 0, stream, a);
+      EQLB_CELL(3, 1);
     }
+  else if constexpr (MODE == CELL_OPERATOR)
+    switch (c.R)
+    {
+    case 1:
+      EQLB_CELL(0, 1);
+      break;
+    case 2:
+      EQLB_CELL(0, 2);
+      break;
+    case 3:
+      EQLB_CELL(0, 3);
+      break;
+    default:
+      EQLB_CELL(0, 4);
+    }
+  else
+    EQLB_CELL(0, 1);
+#undef EQLB_CELL
   return hipGetLastError();
 }
 
 template <int MODE>
-hipError_t launch_cell(int p, int d, const CellArgs& a, hipStream_t stream)
+hipError_t launch_cell(int p, int d, const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride,
+                       hipStream_t stream)
 {
   switch (p)
   {
   case 1:
-    return launch_cell_d<1, MODE>(d, a, stream);
+    return launch_cell_p<1, MODE>(d, a, c, ustride, ystride, stream);
   case 2:
-    return launch_cell_d<2, MODE>(d, a, stream);
+    return launch_cell_p<2, MODE>(d, a, c, ustride, ystride, stream);
   case 3:
-    return launch_cell_d<3, MODE>(d, a, stream);
+    return launch_cell_p<3, MODE>(d, a, c, ustride, ystride, stream);
   default:
-    return launch_cell_d<4, MODE>(d, a, stream);
+    return launch_cell_p<4, MODE>(d, a, c, ustride, ystride, stream);
   }
 }
 } // namespace
@@ -349,185 +313,29 @@ struct eqlb_primal
   eqlb::DevPiece<double> coeff, yloc, diag, r, z, d, q, part;
   eqlb::DevPiece<uint8_t> fixed;
   eqlb::DevPiece<eqlb::PcgState> st;
-  // the work space of the *_many entries for many_R columns: grown by the first call that needs it, then reused
-  int many_R = 0;
-  eqlb::DevBuf<char> many_mem;
-  eqlb::ManyLevel many{};
+  // the work space for 2 ... MANY_R columns (wide.R of them): grown by the first call that needs it, then reused
+  eqlb::DevBuf<char> wide_mem;
+  eqlb::PcgWork wide{};
 };
 
 namespace eqlb
 {
 namespace
 {
-CellArgs cell_args(const eqlb_primal& h, const double* u, bool only_fixed, const PcgState* st)
+const ManyCols ONE_COLUMN{1, 1u, 0, nullptr}; // a launch on one vector that knows no state
+
+// the work space the launches on R columns use: the carve of the handle for one, the grown one (primal_work) for more
+PcgWork work_of(const eqlb_primal& h, int R)
 {
-  CellArgs a{};
-  a.ncells = h.space.ncells;
-  a.cell_dofs = h.cell_dofs;
-  a.cellJ = h.mesh->m.cellJ;
-  a.coeff = h.has_coeff ? h.coeff.get() : nullptr;
-  a.u = u;
-  a.fixed = h.fixed;
-  a.only_fixed = only_fixed ? 1 : 0;
-  a.yloc = h.yloc;
-  a.st = st;
-  return a;
+  PcgWork w = R == 1 ? PcgWork{h.ndofs, 1, h.diag, h.fixed, h.yloc, h.r, h.z, h.d, h.q, h.part, h.st} : h.wide;
+  w.R = R;
+  return w;
 }
 
-GatherArgs gather_args(const eqlb_primal& h, bool masked, const PcgState* st)
+// grows the work space for R > 1 columns if need be
+int primal_work(eqlb_primal* h, int R, PcgWork& w)
 {
-  GatherArgs g{};
-  g.s = h.space;
-  g.yloc = h.yloc;
-  g.fixed = masked ? h.fixed.get() : nullptr;
-  g.part = h.part;
-  g.st = st;
-  return g;
-}
-
-hipError_t launch_gather(const eqlb_primal& h, const GatherArgs& g, hipStream_t stream)
-{
-  hipLaunchKernelGGL(k_primal_gather<1>, dim3(stream_blocks(h.ndofs)), dim3(PS_THREADS), 0, stream, g);
-  return hipGetLastError();
-}
-
-PcgWork pcg_work(const eqlb_primal& h)
-{
-  return PcgWork{h.ndofs, h.diag, h.fixed, h.r, h.z, h.d, h.q, h.part, h.st};
-}
-
-// y = A u (masked or raw); all pointers DEVICE
-hipError_t enqueue_apply(const eqlb_primal& h, const double* u, double* y, bool masked, hipStream_t stream)
-{
-  hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, u, false, nullptr), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, masked, nullptr);
-  g.y = y;
-  return launch_gather(h, g, stream);
-}
-
-hipError_t enqueue_diagonal(const eqlb_primal& h, double* out, hipStream_t stream)
-{
-  hipError_t e = launch_cell<CELL_DIAGONAL>(h.p, 0, cell_args(h, nullptr, false, nullptr), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, false, nullptr);
-  g.y = out;
-  return launch_gather(h, g, stream);
-}
-
-// r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in h.part
-hipError_t enqueue_residual(const eqlb_primal& h, const double* b, const double* u, double* r, bool only_fixed,
-                            hipStream_t stream)
-{
-  hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, u, only_fixed, nullptr), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, true, nullptr);
-  g.b = b;
-  g.r = r;
-  g.dot = DOT_R_R;
-  return launch_gather(h, g, stream);
-}
-
-// q = A d on the free rows (the direction d of the handle), the block partials of d.q in h.part
-hipError_t enqueue_product(const eqlb_primal& h, const PcgState* st, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, h.d, false, st), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, true, st);
-  g.y = h.q;
-  g.w = h.d;
-  g.dot = DOT_W_Y;
-  return launch_gather(h, g, stream);
-}
-
-int check_handle(const char* who, const eqlb_primal* h)
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
-  return EQLB_OK;
-}
-
-// ---- the same launches on columns: u [R][ndofs], y_loc and the vectors in the handle's work space for columns ------
-template <int P>
-hipError_t launch_cell_many_r(const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride, hipStream_t stream)
-{
-  const dim3 grid(grid_of(a.ncells, PS_THREADS)), block(PS_THREADS);
-  switch (c.R)
-  {
-  case 1:
-    hipLaunchKernelGGL((k_primal_cell_many<P, 1>), grid, block, 0, stream, a, c, ustride, ystride);
-    break;
-  case 2:
-    hipLaunchKernelGGL((k_primal_cell_many<P, 2>), grid, block, 0, stream, a, c, ustride, ystride);
-    break;
-  case 3:
-    hipLaunchKernelGGL((k_primal_cell_many<P, 3>), grid, block, 0, stream, a, c, ustride, ystride);
-    break;
-  default:
-    hipLaunchKernelGGL((k_primal_cell_many<P, 4>), grid, block, 0, stream, a, c, ustride, ystride);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_cell_many(const eqlb_primal& h, const ManyCols& c, const double* u, bool only_fixed, hipStream_t stream)
-{
-  CellArgs a = cell_args(h, u, only_fixed, nullptr);
-  a.yloc = h.many.yloc;
-  const int64_t ystride = (int64_t)h.space.ncells * h.nd;
-  switch (h.p)
-  {
-  case 1:
-    return launch_cell_many_r<1>(a, c, h.ndofs, ystride, stream);
-  case 2:
-    return launch_cell_many_r<2>(a, c, h.ndofs, ystride, stream);
-  case 3:
-    return launch_cell_many_r<3>(a, c, h.ndofs, ystride, stream);
-  default:
-    return launch_cell_many_r<4>(a, c, h.ndofs, ystride, stream);
-  }
-}
-
-ManyGatherArgs gather_many_args(const eqlb_primal& h, const ManyCols& c, bool masked)
-{
-  ManyGatherArgs m{};
-  m.g = gather_args(h, masked, nullptr);
-  m.g.yloc = h.many.yloc;
-  m.g.part = h.many.part;
-  m.cols = c;
-  m.ystride = (int64_t)h.space.ncells * h.nd;
-  return m;
-}
-
-hipError_t launch_gather_many(const eqlb_primal& h, const ManyGatherArgs& m, hipStream_t stream)
-{
-  hipLaunchKernelGGL(k_primal_gather_many, dim3(stream_blocks(h.ndofs)), dim3(PS_THREADS), 0, stream, m);
-  return hipGetLastError();
-}
-
-ManyWork many_work(const eqlb_primal& h, int R)
-{
-  return ManyWork{h.ndofs,  R,        h.diag,   h.fixed,     h.many.r,
-                  h.many.z, h.many.d, h.many.q, h.many.part, static_cast<PcgState*>(h.many.st)};
-}
-
-// what every *_many entry checks about its column count and its arrays
-int check_many(const char* who, int32_t nrhs, const void* a, const void* b)
-{
-  if (nrhs < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d (at least 1)", who, (int)nrhs);
-  if (!a || !b)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  return EQLB_OK;
-}
-} // namespace
-
-int primal_many_level(eqlb_primal* h, int R, ManyLevel& v)
-{
-  if (R > h->many_R)
+  if (R > 1 && R > h->wide.R)
   {
     const size_t n = (size_t)h->ndofs, ny = (size_t)h->space.ncells * h->nd;
     size_t off = 0;
@@ -540,49 +348,180 @@ int primal_many_level(eqlb_primal* h, int R, ManyLevel& v)
                  o_z = piece(R * n * sizeof(double)), o_d = piece(R * n * sizeof(double)),
                  o_q = piece(R * n * sizeof(double)), o_p = piece((size_t)R * 2 * PS_MAXBLOCKS * sizeof(double)),
                  o_s = piece(R * sizeof(PcgState));
-    h->many_R = 0;
-    h->many = ManyLevel{};
-    HIP_TRY(h->many_mem.alloc_raw(off)); // (frees the smaller one first)
-    char* base = h->many_mem.get();
+    h->wide = PcgWork{};
+    HIP_TRY(h->wide_mem.alloc_raw(off)); // (frees the smaller one first)
+    char* base = h->wide_mem.get();
     auto dp = [&](size_t o) { return reinterpret_cast<double*>(base + o); };
-    h->many = ManyLevel{dp(o_y), dp(o_r), dp(o_z), dp(o_d), dp(o_q), dp(o_p), base + o_s};
-    h->many_R = R;
+    h->wide = PcgWork{h->ndofs, R,        h->diag,  h->fixed, dp(o_y), dp(o_r),
+                      dp(o_z),  dp(o_d),  dp(o_q),  dp(o_p),  reinterpret_cast<PcgState*>(base + o_s)};
   }
-  v = h->many;
+  w = work_of(*h, R);
   return EQLB_OK;
 }
 
-hipError_t primal_many_owner_sum(eqlb_primal* h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
+// the store pass on the columns of c: u [R][ndofs] (load: rhs_dg) into the y_loc of the work space for c.R columns
+template <int MODE>
+hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const double* u, bool only_fixed,
+                       hipStream_t stream)
 {
-  ManyGatherArgs m = gather_many_args(*h, c, masked);
-  m.g.y = y;
-  return launch_gather_many(*h, m, stream);
+  CellArgs a{};
+  a.ncells = h.space.ncells;
+  a.cell_dofs = h.cell_dofs;
+  a.cellJ = h.mesh->m.cellJ;
+  a.coeff = h.has_coeff ? h.coeff.get() : nullptr;
+  a.u = u;
+  a.fixed = h.fixed;
+  a.only_fixed = only_fixed ? 1 : 0;
+  a.yloc = work_of(h, c.R).yloc;
+  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, stream);
 }
 
-hipError_t primal_many_residual(eqlb_primal* h, const ManyCols& c, const double* b, const double* u, double* r,
-                                bool only_fixed, hipStream_t stream)
+GatherArgs gather_args(const eqlb_primal& h, const ManyCols& c, bool masked)
 {
-  const hipError_t e = launch_cell_many(*h, c, u, only_fixed, stream);
-  if (e != hipSuccess)
-    return e;
-  ManyGatherArgs m = gather_many_args(*h, c, true);
-  m.g.b = b;
-  m.g.r = r;
-  m.g.dot = DOT_R_R;
-  return launch_gather_many(*h, m, stream);
+  const PcgWork w = work_of(h, c.R);
+  GatherArgs g{};
+  g.s = h.space;
+  g.yloc = w.yloc;
+  g.fixed = masked ? h.fixed.get() : nullptr;
+  g.part = w.part;
+  g.cols = c;
+  g.ystride = (int64_t)h.space.ncells * h.nd;
+  return g;
 }
 
-hipError_t primal_many_product(eqlb_primal* h, const ManyCols& c, hipStream_t stream)
+hipError_t launch_gather(const eqlb_primal& h, const GatherArgs& g, hipStream_t stream)
 {
-  const hipError_t e = launch_cell_many(*h, c, h->many.d, false, stream);
+  const dim3 grid(stream_blocks(h.ndofs)), block(PS_THREADS);
+  if (g.cols.R == 1)
+    hipLaunchKernelGGL((k_primal_gather<1, 1>), grid, block, 0, stream, g);
+  else
+    hipLaunchKernelGGL((k_primal_gather<1, MANY_R>), grid, block, 0, stream, g);
+  return hipGetLastError();
+}
+
+// y = owner sum of y_loc (masked or raw) on the columns of c; y DEVICE [R][ndofs]
+hipError_t enqueue_owner_sum(const eqlb_primal& h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
+{
+  GatherArgs g = gather_args(h, c, masked);
+  g.y = y;
+  return launch_gather(h, g, stream);
+}
+
+hipError_t enqueue_diagonal(const eqlb_primal& h, double* out, hipStream_t stream)
+{
+  const hipError_t e = launch_cell<CELL_DIAGONAL>(h, ONE_COLUMN, 0, nullptr, false, stream);
+  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, out, false, stream);
+}
+
+// r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in part
+hipError_t enqueue_residual(const eqlb_primal& h, const ManyCols& c, const double* b, const double* u, double* r,
+                            bool only_fixed, hipStream_t stream)
+{
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h, c, 0, u, only_fixed, stream);
   if (e != hipSuccess)
     return e;
-  ManyGatherArgs m = gather_many_args(*h, c, true);
-  m.g.y = h->many.q;
-  m.g.w = h->many.d;
-  m.g.dot = DOT_W_Y;
-  return launch_gather_many(*h, m, stream);
+  GatherArgs g = gather_args(h, c, true);
+  g.b = b;
+  g.r = r;
+  g.dot = DOT_R_R;
+  return launch_gather(h, g, stream);
 }
+
+// q = A d on the free rows (the direction d of the work space), the block partials of d.q in part
+hipError_t enqueue_product(const eqlb_primal& h, const ManyCols& c, hipStream_t stream)
+{
+  const PcgWork w = work_of(h, c.R);
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h, c, 0, w.d, false, stream);
+  if (e != hipSuccess)
+    return e;
+  GatherArgs g = gather_args(h, c, true);
+  g.y = w.q;
+  g.w = w.d;
+  g.dot = DOT_W_Y;
+  return launch_gather(h, g, stream);
+}
+
+int check_handle(const char* who, const eqlb_primal* h)
+{
+  if (!h)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
+  return EQLB_OK;
+}
+
+// what every *_many entry checks about its column count
+int check_nrhs(const char* who, int32_t nrhs)
+{
+  if (nrhs < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d (at least 1)", who, (int)nrhs);
+  return EQLB_OK;
+}
+
+// eqlb_primal_apply and eqlb_primal_apply_many behind their names
+int primal_apply(const char* who, eqlb_primal* h, int32_t nrhs, const double* u, double* y, int32_t masked,
+                 int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_nrhs(who, nrhs));
+  if (!u || !y)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)h->ndofs;
+  PcgWork w;
+  EQLB_TRY(primal_work(h, nrhs < MANY_R ? nrhs : MANY_R, w));
+  HostCall s;
+  const auto d_u = s.in(host ? u : nullptr, nrhs * n);
+  const auto d_y = s.out(host ? y : nullptr, nrhs * n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double* pu = host ? d_u.get() : u;
+  double* py = host ? d_y.get() : y;
+  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
+  {
+    const int R = nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R;
+    const ManyCols cols{R, (1u << R) - 1u, 0, nullptr};
+    s.note(launch_cell<CELL_OPERATOR>(*h, cols, 0, pu + c0 * n, false, stream));
+    s.note(enqueue_owner_sum(*h, cols, py + c0 * n, masked != 0, stream));
+  }
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+// eqlb_primal_solve and eqlb_primal_solve_many behind their names
+int primal_solve(const char* who, eqlb_primal* h, int32_t nrhs, const double* b, double* u, double rtol, double atol,
+                 int32_t maxit, double* info, int32_t memspace, void* stream_)
+{
+  if (maxit < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
+  if (!(rtol >= 0.0) || !(atol >= 0.0))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_nrhs(who, nrhs));
+  if (!b || !u || !info)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
+  int32_t status[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (status[1] < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
+  PcgWork grown;
+  EQLB_TRY(primal_work(h, nrhs < MANY_R ? nrhs : MANY_R, grown));
+  auto residual = [&](const ManyCols& c, const double* xb, const double* xu, double* r, bool only_fixed) {
+    return enqueue_residual(*h, c, xb, xu, r, only_fixed, stream);
+  };
+  auto product = [&](const ManyCols& c) { return enqueue_product(*h, c, stream); };
+  return pcg_solve_groups(h->ndofs, nrhs, b, u, info, memspace == EQLB_MEM_HOST, stream,
+                          [&](int R, const double* pb, double* pu, double* pinfo) {
+                            const PcgWork w = work_of(*h, R);
+                            return pcg_solve(w, residual, product, JacobiSteps<MANY_R>{w, stream}, pb, pu, rtol, atol, maxit,
+                                             pinfo, status[0], stream);
+                          });
+}
+} // namespace
 
 // the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
 void primal_level(eqlb_primal* h, SolverLevel& v)
@@ -597,21 +536,16 @@ void primal_level(eqlb_primal* h, SolverLevel& v)
   v.diag = h->diag;
   v.fixed = h->fixed;
   v.status = h->status;
-  v.yloc = h->yloc;
-  v.r = h->r, v.z = h->z, v.d = h->d, v.q = h->q, v.part = h->part;
-  v.st = h->st.get();
-  v.owner_sum = [](void* hh, double* y, bool masked, const void* st, hipStream_t stream) {
-    const eqlb_primal& s = *static_cast<eqlb_primal*>(hh);
-    GatherArgs g = gather_args(s, masked, static_cast<const PcgState*>(st));
-    g.y = y;
-    return launch_gather(s, g, stream);
+  v.work = [](void* hh, int R, PcgWork& w) { return primal_work(static_cast<eqlb_primal*>(hh), R, w); };
+  v.owner_sum = [](void* hh, const ManyCols& c, double* y, bool masked, hipStream_t stream) {
+    return enqueue_owner_sum(*static_cast<eqlb_primal*>(hh), c, y, masked, stream);
   };
-  v.residual = [](void* hh, const double* b, const double* u, double* r, bool only_fixed, hipStream_t stream) {
-    return enqueue_residual(*static_cast<eqlb_primal*>(hh), b, u, r, only_fixed, stream);
+  v.residual = [](void* hh, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
+                  hipStream_t stream) {
+    return enqueue_residual(*static_cast<eqlb_primal*>(hh), c, b, u, r, only_fixed, stream);
   };
-  v.product = [](void* hh, hipStream_t stream) {
-    const eqlb_primal& s = *static_cast<eqlb_primal*>(hh);
-    return enqueue_product(s, s.st.get(), stream);
+  v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
+    return enqueue_product(*static_cast<eqlb_primal*>(hh), c, stream);
   };
 }
 } // namespace eqlb
@@ -803,8 +737,8 @@ try
   const auto d_b = s.out(host ? b : nullptr, n);
   if (host)
     HIP_TRY(s.upload(stream));
-  s.note(launch_cell<CELL_LOAD>(h->p, degree_dg, cell_args(*h, host ? d_f.get() : rhs_dg, false, nullptr), stream));
-  GatherArgs g = gather_args(*h, false, nullptr);
+  s.note(launch_cell<CELL_LOAD>(*h, ONE_COLUMN, degree_dg, host ? d_f.get() : rhs_dg, false, stream));
+  GatherArgs g = gather_args(*h, ONE_COLUMN, false);
   g.add = host ? d_e.get() : b_extra;
   g.y = host ? d_b.get() : b;
   s.note(launch_gather(*h, g, stream));
@@ -816,23 +750,15 @@ EQLB_CATCH_ALL
 int eqlb_primal_apply(eqlb_primal_t* h, const double* u, double* y, int32_t masked, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_apply";
-  EQLB_TRY(check_handle(who, h));
-  if (!u || !y)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)h->ndofs;
-  HostCall s;
-  const auto d_u = s.in(host ? u : nullptr, n);
-  const auto d_y = s.out(host ? y : nullptr, n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  s.note(enqueue_apply(*h, host ? d_u.get() : u, host ? d_y.get() : y, masked != 0, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::primal_apply("eqlb_primal_apply", h, 1, u, y, masked, memspace, stream_);
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_apply_many(eqlb_primal_t* h, int32_t nrhs, const double* u, double* y, int32_t masked,
+                           int32_t memspace, void* stream_)
+try
+{
+  return eqlb::primal_apply("eqlb_primal_apply_many", h, nrhs, u, y, masked, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -881,12 +807,12 @@ try
   if (pn)
   {
     // the reference norm first, into the work vector q: the residual proper then leaves r as the caller sees it
-    s.note(enqueue_residual(*h, pb, pu, h->q, true, stream));
-    s.note(launch_scalar(pcg_work(*h), STEP_NORM, 0.0, 0.0, pn + 1, stream));
+    s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, h->q, true, stream));
+    s.note(launch_scalar(work_of(*h, 1), 1u, STEP_NORM, 0, 0.0, 0.0, pn + 1, stream));
   }
-  s.note(enqueue_residual(*h, pb, pu, host ? d_r.get() : r, false, stream));
+  s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, host ? d_r.get() : r, false, stream));
   if (pn)
-    s.note(launch_scalar(pcg_work(*h), STEP_NORM, 0.0, 0.0, pn, stream));
+    s.note(launch_scalar(work_of(*h, 1), 1u, STEP_NORM, 0, 0.0, 0.0, pn, stream));
   HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }
@@ -896,63 +822,7 @@ int eqlb_primal_solve(eqlb_primal_t* h, const double* b, double* u, double rtol,
                       double* info, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_solve";
-  if (maxit < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
-  if (!(rtol >= 0.0) || !(atol >= 0.0))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
-  EQLB_TRY(check_handle(who, h));
-  if (!b || !u || !info)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
-  int32_t status[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (status[1] < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
-  auto residual = [&](const double* pb, const double* pu, double* r, bool only_fixed) {
-    return enqueue_residual(*h, pb, pu, r, only_fixed, stream);
-  };
-  auto product = [&](const PcgState* st) { return enqueue_product(*h, st, stream); };
-  const PcgWork w = pcg_work(*h);
-  return pcg_solve(w, residual, product, JacobiSteps{w, stream}, b, u, rtol, atol, maxit, info, status[0],
-                   memspace == EQLB_MEM_HOST, stream);
-}
-EQLB_CATCH_ALL
-
-int eqlb_primal_apply_many(eqlb_primal_t* h, int32_t nrhs, const double* u, double* y, int32_t masked,
-                           int32_t memspace, void* stream_)
-try
-{
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_apply_many";
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_many(who, nrhs, u, y));
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)h->ndofs;
-  ManyLevel lv;
-  EQLB_TRY(primal_many_level(h, nrhs < MANY_R ? nrhs : MANY_R, lv));
-  HostCall s;
-  const auto d_u = s.in(host ? u : nullptr, nrhs * n);
-  const auto d_y = s.out(host ? y : nullptr, nrhs * n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  const double* pu = host ? d_u.get() : u;
-  double* py = host ? d_y.get() : y;
-  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
-  {
-    const int R = nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R;
-    const ManyCols cols{R, (1u << R) - 1u, 0, nullptr};
-    s.note(launch_cell_many(*h, cols, pu + c0 * n, false, stream));
-    s.note(primal_many_owner_sum(h, cols, py + c0 * n, masked != 0, stream));
-  }
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::primal_solve("eqlb_primal_solve", h, 1, b, u, rtol, atol, maxit, info, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -960,49 +830,7 @@ int eqlb_primal_solve_many(eqlb_primal_t* h, int32_t nrhs, const double* b, doub
                            int32_t maxit, double* info, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_solve_many";
-  if (maxit < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
-  if (!(rtol >= 0.0) || !(atol >= 0.0))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_many(who, nrhs, b, u));
-  if (!info)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
-  int32_t status[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (status[1] < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
-  ManyLevel lv;
-  EQLB_TRY(primal_many_level(h, nrhs < MANY_R ? nrhs : MANY_R, lv));
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)h->ndofs;
-  HostCall s;
-  const auto d_b = s.in(host ? b : nullptr, nrhs * n);
-  const auto d_u = s.in(host ? static_cast<const double*>(u) : nullptr, nrhs * n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  const double* pb = host ? d_b.get() : b;
-  double* pu = host ? d_u.get() : u;
-  auto residual = [&](const ManyCols& c, const double* xb, const double* xu, double* r, bool only_fixed) {
-    return primal_many_residual(h, c, xb, xu, r, only_fixed, stream);
-  };
-  auto product = [&](const ManyCols& c) { return primal_many_product(h, c, stream); };
-  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
-  {
-    const ManyWork w = many_work(*h, nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R);
-    EQLB_TRY(pcg_solve_many(w, residual, product, JacobiStepsMany{w, stream}, pb + c0 * n, pu + c0 * n, rtol, atol,
-                            maxit, info + 8 * (size_t)c0, status[0], stream));
-  }
-  if (host)
-    s.out_prefix(u, d_u, nrhs * n);
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::primal_solve("eqlb_primal_solve_many", h, nrhs, b, u, rtol, atol, maxit, info, memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -236,116 +236,23 @@ __global__ void __launch_bounds__(TR_THREADS) k_prolong(const ProlongArgs a)
 // The table is staged in LDS as in k_prolong (the rows differ from lane to lane); the loop over the local DOFs is not
 // unrolled (the row, the index and the owner bit of DOF n are looked up, the ND sums stay in registers).  a.in = r2,
 // a.out = y_loc, a.cell_dofs2 / a.ndofs2 the fine dofmap; a bad index or a child that is no child of its parent makes
-// the row of the cell NaN.  done: nullptr, or the stop flag of a CG in device memory - set, the kernel returns at once.
-template <int Q, int BS>
-__global__ void __launch_bounds__(TR_THREADS) k_restrict(const ProlongArgs a, const int32_t* __restrict__ done)
+// the row of the cell NaN.
+// R columns (BS = 1 only): r2 [R][ndofs2] -> y_loc [R][ncells][ND].  The children, their owner bits, the indices and
+// the table rows are found once per cell and applied to the columns; the sum of a column runs in the one order.  The
+// columns that run are those of cols (eqlb_internal.h: inside a batch of CG iterations a column whose stop flag is set
+// is left alone - nothing reads its result); the others are neither read nor written.
+template <int Q, int BS, int R>
+__global__ void __launch_bounds__(TR_THREADS) k_restrict(const ProlongArgs a, const ManyCols cols, int64_t ystride)
 {
 #pragma clang fp contract(off) // the statement rounds every product and every sum on its own
   using T = eqlb_tables::Prolong<Q>;
   constexpr int ND = nd_of(Q), NROW = T::NROW;
+  constexpr int NV = BS * R; // values per fine DOF: the components of the one column, or the columns
   static constexpr DofNum<Q> num{}; // (indexed by a run-time n: a table in constant memory, not a private copy)
   static_assert(T::ND == ND && NROW == (2 * Q + 1) * (Q + 1), "table shape");
+  static_assert(BS == 1 || R == 1, "columns for scalar spaces only");
   __shared__ double sT[NROW * ND];
-  if (done && *done) // (inside a batch of CG iterations whose stop flag is set: nothing reads the result)
-    return;
-  for (int i = threadIdx.x; i < NROW * ND; i += TR_THREADS)
-    sT[i] = T::PT[i];
-  __syncthreads();
-  const int32_t c = blockIdx.x * TR_THREADS + threadIdx.x;
-  if (c >= a.ncells)
-    return;
-  const int32_t v[3] = {a.cell_nodes[3 * (int64_t)c], a.cell_nodes[3 * (int64_t)c + 1], a.cell_nodes[3 * (int64_t)c + 2]};
-  const int64_t first = a.coff[c];
-  const int nchild = (int)(a.coff[c + 1] - a.coff[c]); // 1 ... 4
-  double acc[ND][BS];
-#pragma unroll
-  for (int i = 0; i < ND; ++i)
-#pragma unroll
-    for (int b = 0; b < BS; ++b)
-      acc[i][b] = 0.0;
-  bool started = false, good = true;
-  for (int k = 0; k < nchild; ++k)
-  {
-    const int64_t c2 = first + k;
-    const int32_t w[3] = {a.cell_nodes2[3 * c2], a.cell_nodes2[3 * c2 + 1], a.cell_nodes2[3 * c2 + 2]};
-    int hx[3], hy[3];
-    const bool found = child_positions(a, v, w, hx, hy);
-    good = good && found;
-    // bit n: the child owns its local DOF n (interior DOFs: always)
-    uint32_t own = ~0u << (3 * Q);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      own |= (a.node_cells2[a.node_cells_off2[w[j]]] == c2) ? (1u << j) : 0u;
-    if constexpr (Q > 1)
-    {
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-      {
-        const int32_t f = a.cell_facets2[3 * c2 + j];
-        const uint32_t bits = ((1u << (Q - 1)) - 1u) << (3 + j * (Q - 1));
-        own |= (a.facet_cells2[a.facet_cells_off2[f]] == c2) ? bits : 0u;
-      }
-    }
-#pragma unroll 1
-    for (int n = 0; n < ND; ++n)
-    {
-      if (!((own >> n) & 1u))
-        continue;
-      const int32_t d2 = a.cell_dofs2[c2 * ND + n];
-      if (d2 < 0 || (int64_t)d2 >= a.ndofs2)
-      {
-        good = false;
-        continue;
-      }
-      const int lx = Q * hx[0] + num.a[n] * (hx[1] - hx[0]) + num.b[n] * (hx[2] - hx[0]);
-      const int ly = Q * hy[0] + num.a[n] * (hy[1] - hy[0]) + num.b[n] * (hy[2] - hy[0]);
-      const double* t = sT + (found ? ly * (2 * Q + 1) - ly * (ly - 1) / 2 + lx : 0) * ND;
-      double rv[BS];
-#pragma unroll
-      for (int b = 0; b < BS; ++b)
-        rv[b] = a.in[(int64_t)d2 * BS + b];
-#pragma unroll
-      for (int i = 0; i < ND; ++i)
-      {
-        const double ti = t[i];
-#pragma unroll
-        for (int b = 0; b < BS; ++b)
-        {
-          const double term = ti * rv[b];
-          acc[i][b] = started ? acc[i][b] + term : term;
-        }
-      }
-      started = true;
-    }
-  }
-  const double bad = __longlong_as_double(0x7ff8000000000000ll);
-  double* o = a.out + (int64_t)c * ND * BS;
-#pragma unroll
-  for (int i = 0; i < ND; ++i)
-#pragma unroll
-    for (int b = 0; b < BS; ++b)
-      o[i * BS + b] = good ? acc[i][b] : bad;
-}
-
-// k_restrict<Q, 1> on R columns: r2 [R][ndofs2] -> y_loc [R][ncells][ND].  The children, their owner bits, the indices
-// and the table rows are found once per cell and applied to the columns; the sum of a column runs in the order of the
-// single kernel.  Column k runs if bit k of mask is set and its stop flag done0[k done_stride] (done0: nullptr or the
-// flag of column 0 in device memory) is not; the others are neither read nor written.
-template <int Q, int R>
-__global__ void __launch_bounds__(TR_THREADS)
-k_restrict_many(const ProlongArgs a, uint32_t mask, const int32_t* __restrict__ done0, int done_stride, int64_t ystride)
-{
-#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
-  using T = eqlb_tables::Prolong<Q>;
-  constexpr int ND = nd_of(Q), NROW = T::NROW;
-  static constexpr DofNum<Q> num{}; // (indexed by a run-time n: a table in constant memory, not a private copy)
-  static_assert(T::ND == ND && NROW == (2 * Q + 1) * (Q + 1), "table shape");
-  __shared__ double sT[NROW * ND];
-  uint32_t live = 0;
-#pragma unroll
-  for (int k = 0; k < R; ++k)
-    if (((mask >> k) & 1u) && !(done0 && done0[(int64_t)k * done_stride]))
-      live |= 1u << k;
+  const uint32_t live = cols_live<R>(cols);
   if (!live)
     return;
   for (int i = threadIdx.x; i < NROW * ND; i += TR_THREADS)
@@ -357,12 +264,12 @@ k_restrict_many(const ProlongArgs a, uint32_t mask, const int32_t* __restrict__ 
   const int32_t v[3] = {a.cell_nodes[3 * (int64_t)c], a.cell_nodes[3 * (int64_t)c + 1], a.cell_nodes[3 * (int64_t)c + 2]};
   const int64_t first = a.coff[c];
   const int nchild = (int)(a.coff[c + 1] - a.coff[c]); // 1 ... 4
-  double acc[ND][R];
+  double acc[ND][NV];
 #pragma unroll
   for (int i = 0; i < ND; ++i)
 #pragma unroll
-    for (int k = 0; k < R; ++k)
-      acc[i][k] = 0.0;
+    for (int b = 0; b < NV; ++b)
+      acc[i][b] = 0.0;
   bool started = false, good = true;
   for (int j = 0; j < nchild; ++j)
   {
@@ -400,34 +307,51 @@ k_restrict_many(const ProlongArgs a, uint32_t mask, const int32_t* __restrict__ 
       const int lx = Q * hx[0] + num.a[n] * (hx[1] - hx[0]) + num.b[n] * (hx[2] - hx[0]);
       const int ly = Q * hy[0] + num.a[n] * (hy[1] - hy[0]) + num.b[n] * (hy[2] - hy[0]);
       const double* t = sT + (found ? ly * (2 * Q + 1) - ly * (ly - 1) / 2 + lx : 0) * ND;
-      double rv[R];
+      double rv[NV];
 #pragma unroll
-      for (int k = 0; k < R; ++k)
-        rv[k] = ((live >> k) & 1u) ? a.in[k * a.ndofs2 + d2] : 0.0;
+      for (int b = 0; b < NV; ++b)
+      {
+        if constexpr (R == 1)
+          rv[b] = a.in[(int64_t)d2 * BS + b];
+        else
+          rv[b] = col_on<R>(live, b) ? a.in[b * a.ndofs2 + d2] : 0.0;
+      }
 #pragma unroll
       for (int i = 0; i < ND; ++i)
       {
         const double ti = t[i];
 #pragma unroll
-        for (int k = 0; k < R; ++k)
+        for (int b = 0; b < NV; ++b)
         {
-          const double term = ti * rv[k];
-          acc[i][k] = started ? acc[i][k] + term : term;
+          const double term = ti * rv[b];
+          acc[i][b] = started ? acc[i][b] + term : term;
         }
       }
       started = true;
     }
   }
   const double bad = __longlong_as_double(0x7ff8000000000000ll);
-#pragma unroll
-  for (int k = 0; k < R; ++k)
+  if constexpr (R == 1)
   {
-    if (!((live >> k) & 1u))
-      continue;
-    double* o = a.out + k * ystride + (int64_t)c * ND;
+    double* o = a.out + (int64_t)c * ND * BS;
 #pragma unroll
     for (int i = 0; i < ND; ++i)
-      o[i] = good ? acc[i][k] : bad;
+#pragma unroll
+      for (int b = 0; b < BS; ++b)
+        o[i * BS + b] = good ? acc[i][b] : bad;
+  }
+  else
+  {
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+    {
+      if (!col_on<R>(live, k))
+        continue;
+      double* o = a.out + k * ystride + (int64_t)c * ND;
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+        o[i] = good ? acc[i][k] : bad;
+    }
   }
 }
 
@@ -535,49 +459,18 @@ int check_dofmap(const char* who, const char* name, const int32_t* cd, size_t nc
 }
 } // namespace
 
-// the store pass of the restriction for the hierarchy unit (eqlb_multilevel.hip): DEVICE pointers, one launch
-int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const int32_t* cell_dofs2,
-                    int64_t ndofs2, const double* r2, double* yloc, const int32_t* done, hipStream_t stream)
+// the store pass of the restriction for the hierarchy unit (eqlb_multilevel.hip) on the columns of c: DEVICE pointers,
+// one launch
+int launch_restrict(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int bs, const ManyCols& c,
+                    const int32_t* cell_dofs2, int64_t ndofs2, const double* r2, double* yloc, hipStream_t stream)
 {
+  const int R = c.R;
   if (p < 1 || p > TR_PMAX || (bs != 1 && bs != 2))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4, or bs = %d not 1 or 2", who, p, bs);
+  if (R < 1 || R > MANY_R || (bs == 2 && R != 1))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %d columns outside 1 ... 4 (bs = 2: one)", who, R);
   ProlongArgs a;
-  EQLB_TRY(common_args(who, plan, refined, bs, 1, EQLB_MEM_DEVICE, a));
-  if (mesh_node_cells(refined, &a.node_cells2))
-    return EQLB_ERR_DEVICE;
-  a.cell_dofs2 = cell_dofs2;
-  a.ndofs2 = ndofs2;
-  a.in = r2;
-  a.out = yloc;
-  const dim3 grid(grid_of(a.ncells, TR_THREADS)), block(TR_THREADS);
-#define EQLB_RESTRICT_CASE(QQ)                                                                                         \
-  case QQ:                                                                                                             \
-    if (bs == 1)                                                                                                       \
-      hipLaunchKernelGGL((k_restrict<QQ, 1>), grid, block, 0, stream, a, done);                                        \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_restrict<QQ, 2>), grid, block, 0, stream, a, done);                                        \
-    break;
-  switch (p)
-  {
-    EQLB_RESTRICT_CASE(1)
-    EQLB_RESTRICT_CASE(2)
-    EQLB_RESTRICT_CASE(3)
-    EQLB_RESTRICT_CASE(4)
-  }
-#undef EQLB_RESTRICT_CASE
-  HIP_TRY(hipGetLastError());
-  return EQLB_OK;
-}
-
-// the same on R <= 4 columns of r2 [R][ndofs2] (scalar spaces only)
-int launch_restrict_many(const char* who, eqlb_refine* plan, eqlb_mesh* refined, int p, int R, uint32_t mask,
-                         const int32_t* cell_dofs2, int64_t ndofs2, const double* r2, double* yloc, const int32_t* done0,
-                         int done_stride, hipStream_t stream)
-{
-  if (p < 1 || p > TR_PMAX || R < 1 || R > 4)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4, or %d columns outside 1 ... 4", who, p, R);
-  ProlongArgs a;
-  EQLB_TRY(common_args(who, plan, refined, 1, R, EQLB_MEM_DEVICE, a));
+  EQLB_TRY(common_args(who, plan, refined, bs, R, EQLB_MEM_DEVICE, a));
   if (mesh_node_cells(refined, &a.node_cells2))
     return EQLB_ERR_DEVICE;
   a.cell_dofs2 = cell_dofs2;
@@ -586,21 +479,23 @@ int launch_restrict_many(const char* who, eqlb_refine* plan, eqlb_mesh* refined,
   a.out = yloc;
   const int64_t ystride = (int64_t)a.ncells * nd_of(p);
   const dim3 grid(grid_of(a.ncells, TR_THREADS)), block(TR_THREADS);
-#define EQLB_RESTRICT_MANY(QQ, RR)                                                                                     \
-  case 4 * QQ + RR:                                                                                                    \
-    hipLaunchKernelGGL((k_restrict_many<QQ, RR>), grid, block, 0, stream, a, mask, done0, done_stride, ystride);      \
+  // slot 0 of a degree: bs = 2 (one column); slots 1 ... 4: the column counts of bs = 1
+#define EQLB_RESTRICT_CASE(QQ, BB, RR)                                                                                 \
+  case 5 * QQ + (BB == 2 ? 0 : RR):                                                                                    \
+    hipLaunchKernelGGL((k_restrict<QQ, BB, RR>), grid, block, 0, stream, a, c, ystride);                               \
     break;
-#define EQLB_RESTRICT_MANY_Q(QQ)                                                                                       \
-  EQLB_RESTRICT_MANY(QQ, 1) EQLB_RESTRICT_MANY(QQ, 2) EQLB_RESTRICT_MANY(QQ, 3) EQLB_RESTRICT_MANY(QQ, 4)
-  switch (4 * p + R)
+#define EQLB_RESTRICT_Q(QQ)                                                                                            \
+  EQLB_RESTRICT_CASE(QQ, 1, 1) EQLB_RESTRICT_CASE(QQ, 1, 2) EQLB_RESTRICT_CASE(QQ, 1, 3) EQLB_RESTRICT_CASE(QQ, 1, 4)  \
+  EQLB_RESTRICT_CASE(QQ, 2, 1)
+  switch (5 * p + (bs == 2 ? 0 : R))
   {
-    EQLB_RESTRICT_MANY_Q(1)
-    EQLB_RESTRICT_MANY_Q(2)
-    EQLB_RESTRICT_MANY_Q(3)
-    EQLB_RESTRICT_MANY_Q(4)
+    EQLB_RESTRICT_Q(1)
+    EQLB_RESTRICT_Q(2)
+    EQLB_RESTRICT_Q(3)
+    EQLB_RESTRICT_Q(4)
   }
-#undef EQLB_RESTRICT_MANY_Q
-#undef EQLB_RESTRICT_MANY
+#undef EQLB_RESTRICT_Q
+#undef EQLB_RESTRICT_CASE
   HIP_TRY(hipGetLastError());
   return EQLB_OK;
 }

@@ -1,5 +1,5 @@
 """Several right-hand sides in one P_p Poisson solve on the device (cpp.PrimalPoisson.apply_many / solve_many,
-cpp.Multilevel.precondition_many / solve_many; csrc/eqlb_primal_many.h).  THE RULE is the whole contract: column c of a
+cpp.Multilevel.precondition_many / solve_many; csrc/eqlb_primal_common.h).  THE RULE is the whole contract: column c of a
 many-call is the single call on (b_c, u_c) - the same bits of the result, the same info.  No tolerance appears below
 except in the chain test, whose bounds are those of check_solution of tests/test_gpu_primal_solve.py.
 
