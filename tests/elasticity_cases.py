@@ -1,8 +1,8 @@
-"""Shared by tests/test_primal_elasticity_host.py and tests/test_gpu_primal_elasticity.py: the Galerkin matrix and load
-of the P_p^2 elasticity problem -div(2 eps(u) + pi_1 div(u) I) = f assembled the way galerkin.solve_elasticity builds
+"""Shared by tests/test_primal_elasticity_host.py, tests/test_primal_meshes_host.py and
+tests/test_gpu_primal_elasticity.py: the Galerkin matrix and load of the P_p^2 elasticity problem -div(2 eps(u) + pi_1 div(u) I) = f assembled the way galerkin.solve_elasticity builds
 its cell matrices (quadrature on physical gradients, scipy), with pi_1 in front of the div-div term, in the blocked
 numbering x[2 dof + r]: the independently rounded computation the statement of dolfinx_eqlb_amd/lsolver/primal.py
-(ElasticityOperator) is compared with."""
+(ElasticityOperator) is compared with, and that comparison itself (check_statement)."""
 
 import numpy as np
 import scipy.sparse as sp
@@ -78,3 +78,53 @@ def pi1_of(ncells, seed=23):
 def dirichlet_lists(ft):
     """the two facet lists of set_dirichlet from facet types [2, nfacets]: the facets with ft[r] == 1"""
     return [np.nonzero(ft[r] == 1)[0].astype(np.int32) for r in range(2)]
+
+
+def check_statement(mesh, p, per_cell, name=""):
+    """The statement (lsolver.primal.ElasticityOperator) against the assembled operator on one mesh, with the scalar
+    pi_1 = 3.5 or the per-cell pi_1 of pi1_of: apply, load and diagonal within chain_terms of the mesh's own valence,
+    b_extra added as it is, residual and mask (Dirichlet all around in both rows).  Returns the largest |diff| / bound
+    of (apply, load, diagonal)."""
+    from dolfinx_eqlb_amd.lsolver import primal
+    from primal_cases import ratio
+    rng = np.random.default_rng(5 + p)
+    pi_1, cell_pi1 = (1.0, pi1_of(mesh.ncells)) if per_cell else (3.5, None)
+    op = primal.ElasticityOperator(mesh, p, pi_1, cell_pi1)
+    d = min(p - 1, 3) if p > 1 else 1
+    nd = (d + 1) * (d + 2) // 2
+    f = rng.standard_normal((2, mesh.ncells * nd))
+    A, Aabs, b, babs = assemble(mesh, p, pi_1, cell_pi1, d, f)
+    assert A.shape[0] == 2 * op.ndofs
+    u = rng.standard_normal(2 * op.ndofs)
+    valence = int(np.diff(mesh.node_cells_offsets).max())
+    ts, ta = chain_terms(p, valence, make_quadrature_triangle(2 * p + 4)[1].size)
+    label = f"{name} p={p} per_cell={per_cell}".strip()
+    ratios = []
+    # operator
+    y, yabs = op.apply(u, return_abs=True)
+    diff, bound = np.abs(y - A @ u), U * (ts * yabs + ta * (Aabs @ np.abs(u)))
+    ratios.append(ratio(diff, bound))
+    print(f"{label}: apply max |diff| / bound = {ratios[-1]:.3f} (terms {(ts, ta)})")
+    assert np.all(diff <= bound)
+    # load (b_extra is added as it is)
+    e = rng.standard_normal(2 * op.ndofs)
+    bs, bsabs = op.load(d, f, return_abs=True)
+    diff, bound = np.abs(bs - b), U * (ts * bsabs + ta * babs)
+    ratios.append(ratio(diff, bound))
+    print(f"{label}: load max |diff| / bound = {ratios[-1]:.3f}")
+    assert np.all(diff <= bound)
+    assert np.array_equal(op.load(d, f, e), bs + e)
+    # diagonal
+    dg, dabs = op.diagonal(return_abs=True)
+    diff, bound = np.abs(dg - A.diagonal()), U * (ts * dabs + ta * Aabs.diagonal())
+    ratios.append(ratio(diff, bound))
+    print(f"{label}: diagonal max |diff| / bound = {ratios[-1]:.3f}")
+    assert np.all(diff <= bound) and np.all(dg > 0.0)
+    # residual and mask
+    bf = mesh.boundary_facets()
+    op.set_dirichlet(bf, bf)
+    r = op.residual(bs, u)
+    assert np.array_equal(r[~op.fixed], (bs - y)[~op.fixed]) and np.all(r[op.fixed] == 0.0)
+    ym = op.apply(u, masked=True)
+    assert np.array_equal(ym[~op.fixed], y[~op.fixed]) and np.all(ym[op.fixed] == 0.0)
+    return tuple(ratios)

@@ -73,6 +73,39 @@ def dense_prolongation(mesh, mesh2, parent_cell, npf, p):
     return np.ascontiguousarray(tr.prolong_lagrange(mesh, mesh2, parent_cell, npf, p, np.eye(n)).T)
 
 
+def check_restriction(mesh, mesh2, pcell, npf, p, bs, P=None, name=""):
+    """mesh.transfer.restrict_lagrange of one link against the dense P^T (P: dense_prolongation of the link, built here
+    where not given): the values and the abs-sum within restrict_terms, the pairing <P u, r2> = <u, R r2>, the mask.
+    Returns max deviation / (2^-53 abs-sum) and the number of roundings allowed."""
+    if P is None:
+        P = dense_prolongation(mesh, mesh2, pcell, npf, p)
+    n, n2 = P.shape[1], P.shape[0]
+    rng = np.random.default_rng(10 * p + bs)
+    r2 = rng.standard_normal(n2 * bs)
+    r, A = tr.restrict_lagrange(mesh, mesh2, pcell, npf, p, r2, bs=bs, return_abs=True)
+    ref = (P.T @ r2.reshape(n2, bs)).ravel()
+    Aref = (np.abs(P).T @ np.abs(r2).reshape(n2, bs)).ravel()
+    # the abs-sum of the statement is |P|^T |r2|, added in another order
+    terms = sum(restrict_terms(mesh, p))
+    assert np.all(np.abs(A - Aref) <= terms * U * Aref)
+    dev = np.abs(r - ref)
+    worst = float(np.max(dev / (U * Aref)))
+    print(f"{name} p={p} bs={bs}: max deviation / (2^-53 abs-sum) {worst:.2f}, allowed {terms}".strip())
+    assert np.all(dev <= terms * U * Aref)
+    # the pairing <P u, r2> = <u, R r2>: the bound above per entry against |u|, the prolongation's own nd_p roundings per
+    # entry against |r2|, and the two inner products
+    u = rng.standard_normal(n * bs)
+    Pu = tr.prolong_lagrange(mesh, mesh2, pcell, npf, p, u, bs=bs)
+    lhs, rhs = np.sum(Pu * r2), np.sum(u * r)
+    nd = (p + 1) * (p + 2) // 2
+    assert abs(lhs - rhs) <= (terms + nd + (n + n2) * bs) * U * np.sum(np.abs(u) * Aref)
+    # the mask
+    fixed = rng.random(n * bs) < 0.3
+    rm = tr.restrict_lagrange(mesh, mesh2, pcell, npf, p, r2, bs=bs, fixed=fixed)
+    assert np.all(rm[fixed] == 0.0) and np.array_equal(rm[~fixed], r[~fixed])
+    return worst, terms
+
+
 def restrict_terms(mesh, p):
     """(statement, product): roundings along the longest chain of one entry of the restriction and of P^T r2 by a
     matrix product, each bounded by 2^-53 of the abs-sum |P|^T |r2|, in the way primal_cases.chain_terms counts.

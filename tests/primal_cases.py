@@ -1,6 +1,7 @@
-"""Shared by tests/test_primal_host.py and tests/test_gpu_primal_solve.py: the Galerkin matrix and load of the P_p
-Poisson problem assembled the way tests/galerkin.py assembles them (quadrature on physical gradients, scipy), as the
-independently rounded computation the statement of dolfinx_eqlb_amd/lsolver/primal.py is compared with."""
+"""Shared by tests/test_primal_host.py, tests/test_primal_meshes_host.py and tests/test_gpu_primal_solve.py: the Galerkin
+matrix and load of the P_p Poisson problem assembled the way tests/galerkin.py assembles them (quadrature on physical
+gradients, scipy), as the independently rounded computation the statement of dolfinx_eqlb_amd/lsolver/primal.py is
+compared with, and that comparison itself (check_statement)."""
 
 import numpy as np
 import scipy.sparse as sp
@@ -59,3 +60,57 @@ def chain_terms(p, valence, nq):
 def kappa_of(ncells, seed=11):
     """log-uniform in [1, 100] per cell"""
     return 10.0 ** (2.0 * np.random.default_rng(seed).random(ncells))
+
+
+def ratio(diff, bound):
+    """max of diff / bound with 0 / 0 = 0 (printed); the assertion is diff <= bound entry by entry"""
+    return float(np.max(np.where(bound > 0.0, diff / np.where(bound > 0.0, bound, 1.0), np.where(diff > 0.0, np.inf, 0.0))))
+
+
+def check_statement(mesh, p, name):
+    """The statement (lsolver.primal.PoissonOperator) against the assembled operator on one mesh: apply, load and
+    diagonal within chain_terms of the mesh's own valence, b_extra added as it is, residual and mask.  Returns the
+    largest |diff| / bound of (apply, load, diagonal)."""
+    from dolfinx_eqlb_amd.lsolver import primal
+    rng = np.random.default_rng(5 + p)
+    kappa = kappa_of(mesh.ncells)
+    op = primal.PoissonOperator(mesh, p, kappa)
+    d = min(p - 1, 3) if p > 1 else 1
+    nd = (d + 1) * (d + 2) // 2
+    f = rng.standard_normal(mesh.ncells * nd)
+    A, Aabs, b, babs = assemble(mesh, p, kappa, d, f)
+    assert A.shape[0] == op.ndofs
+    u = rng.standard_normal(op.ndofs)
+    valence = int(np.diff(mesh.node_cells_offsets).max())
+    ts, ta = chain_terms(p, valence, make_quadrature_triangle(2 * p + 4)[1].size)
+    terms = (ts, ta)
+    ratios = []
+    # operator
+    y, yabs = op.apply(u, return_abs=True)
+    diff, bound = np.abs(y - A @ u), U * (ts * yabs + ta * (Aabs @ np.abs(u)))
+    ratios.append(ratio(diff, bound))
+    print(f"{name} p={p}: apply max |diff| / bound = {ratios[-1]:.3f} (terms {terms})")
+    assert np.all(diff <= bound)
+    # load (b_extra is added as it is)
+    e = rng.standard_normal(op.ndofs)
+    bs, bsabs = op.load(d, f, return_abs=True)
+    diff, bound = np.abs(bs - b), U * (ts * bsabs + ta * babs)
+    ratios.append(ratio(diff, bound))
+    print(f"{name} p={p}: load max |diff| / bound = {ratios[-1]:.3f}")
+    assert np.all(diff <= bound)
+    assert np.array_equal(op.load(d, f, e), bs + e)
+    # diagonal
+    dg, dabs = op.diagonal(return_abs=True)
+    diff, bound = np.abs(dg - A.diagonal()), U * (ts * dabs + ta * Aabs.diagonal())
+    ratios.append(ratio(diff, bound))
+    print(f"{name} p={p}: diagonal max |diff| / bound = {ratios[-1]:.3f}")
+    assert np.all(diff <= bound) and np.all(dg > 0.0)
+    # residual and mask
+    op.set_dirichlet(mesh.boundary_facets())
+    r = op.residual(bs, u)
+    assert np.array_equal(r[~op.fixed], (bs - y)[~op.fixed]) and np.all(r[op.fixed] == 0.0)
+    ym = op.apply(u, masked=True)
+    assert np.array_equal(ym[~op.fixed], y[~op.fixed]) and np.all(ym[op.fixed] == 0.0)
+    assert op.fixed.sum() == np.unique(mesh.facet_nodes[mesh.boundary_facets()]).size \
+        + (p - 1) * mesh.boundary_facets().size
+    return tuple(ratios)

@@ -83,7 +83,8 @@ def hierarchy(problem, p, nlevels=3, bc="all"):
     return _CACHE[key]
 
 
-CASES = [("poisson", 1), ("poisson", 2), ("poisson", 3), ("poisson", 4), ("elasticity", 1), ("elasticity", 2)]
+CASES = [("poisson", 1), ("poisson", 2), ("poisson", 3), ("poisson", 4), ("elasticity", 1), ("elasticity", 2),
+         ("elasticity", 3), ("elasticity", 4)]
 
 
 # ---- 1. bit for bit --------------------------------------------------------------------------------------------------

@@ -46,30 +46,7 @@ def test_restriction_is_the_transpose(p, bs):
     mesh, mesh2 = meshes[0], meshes[1]
     pcell, npf = links[0]
     assert sorted(set(np.bincount(pcell, minlength=mesh.ncells))) == [1, 2, 3, 4]
-    P = mc.dense_prolongation(mesh, mesh2, pcell, npf, p)
-    n, n2 = P.shape[1], P.shape[0]
-    rng = np.random.default_rng(10 * p + bs)
-    r2 = rng.standard_normal(n2 * bs)
-    r, A = tr.restrict_lagrange(mesh, mesh2, pcell, npf, p, r2, bs=bs, return_abs=True)
-    ref = (P.T @ r2.reshape(n2, bs)).ravel()
-    Aref = (np.abs(P).T @ np.abs(r2).reshape(n2, bs)).ravel()
-    # the abs-sum of the statement is |P|^T |r2|, added in another order
-    terms = sum(mc.restrict_terms(mesh, p))
-    assert np.all(np.abs(A - Aref) <= terms * U * Aref)
-    dev = np.abs(r - ref)
-    print(f"p={p} bs={bs}: max deviation / (2^-53 abs-sum) {np.max(dev / (U * Aref)):.2f}, allowed {terms}")
-    assert np.all(dev <= terms * U * Aref)
-    # the pairing <P u, r2> = <u, R r2>: the bound above per entry against |u|, the prolongation's own nd_p roundings per
-    # entry against |r2|, and the two inner products
-    u = rng.standard_normal(n * bs)
-    Pu = tr.prolong_lagrange(mesh, mesh2, pcell, npf, p, u, bs=bs)
-    lhs, rhs = np.sum(Pu * r2), np.sum(u * r)
-    nd = (p + 1) * (p + 2) // 2
-    assert abs(lhs - rhs) <= (terms + nd + (n + n2) * bs) * U * np.sum(np.abs(u) * Aref)
-    # the mask
-    fixed = rng.random(n * bs) < 0.3
-    rm = tr.restrict_lagrange(mesh, mesh2, pcell, npf, p, r2, bs=bs, fixed=fixed)
-    assert np.all(rm[fixed] == 0.0) and np.array_equal(rm[~fixed], r[~fixed])
+    mc.check_restriction(mesh, mesh2, pcell, npf, p, bs)
 
 
 def test_restriction_refuses_bad_input():

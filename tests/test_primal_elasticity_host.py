@@ -17,6 +17,7 @@ from dolfinx_eqlb_amd.elmtlib.lagrange import Lagrange
 from dolfinx_eqlb_amd.elmtlib.quadrature import make_quadrature_triangle
 from dolfinx_eqlb_amd.lsolver import primal
 from dolfinx_eqlb_amd.mesh import create_unit_square
+from primal_cases import ratio as _ratio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID_ARGUMENT = -1
@@ -27,11 +28,6 @@ ENTRIES = ("eqlb_get_cross_table", "eqlb_elasticity_create", "eqlb_elasticity_nd
 METHODS = ("set_dirichlet", "load", "apply", "diagonal", "residual", "solve")
 
 MESH = create_unit_square(4, shuffle_seed=3, perturb=0.15)
-
-
-def _ratio(diff, bound):
-    """max of diff / bound with 0 / 0 = 0 (printed); the assertion is diff <= bound entry by entry"""
-    return float(np.max(np.where(bound > 0.0, diff / np.where(bound > 0.0, bound, 1.0), np.where(diff > 0.0, np.inf, 0.0))))
 
 
 # ---- the table ------------------------------------------------------------------------------------------------------
@@ -84,42 +80,7 @@ def test_library_table_is_the_generated_one():
 @pytest.mark.parametrize("per_cell", [False, True])
 @pytest.mark.parametrize("p", [1, 2, 3, 4])
 def test_statement_equals_the_assembled_operator(p, per_cell):
-    mesh = MESH
-    rng = np.random.default_rng(5 + p)
-    pi_1, cell_pi1 = (1.0, ec.pi1_of(mesh.ncells)) if per_cell else (3.5, None)
-    op = primal.ElasticityOperator(mesh, p, pi_1, cell_pi1)
-    d = min(p - 1, 3) if p > 1 else 1
-    nd = (d + 1) * (d + 2) // 2
-    f = rng.standard_normal((2, mesh.ncells * nd))
-    A, Aabs, b, babs = ec.assemble(mesh, p, pi_1, cell_pi1, d, f)
-    assert A.shape[0] == 2 * op.ndofs
-    u = rng.standard_normal(2 * op.ndofs)
-    valence = int(np.diff(mesh.node_cells_offsets).max())
-    ts, ta = ec.chain_terms(p, valence, make_quadrature_triangle(2 * p + 4)[1].size)
-    # operator
-    y, yabs = op.apply(u, return_abs=True)
-    diff, bound = np.abs(y - A @ u), U * (ts * yabs + ta * (Aabs @ np.abs(u)))
-    print(f"p={p} per_cell={per_cell}: apply max |diff| / bound = {_ratio(diff, bound):.3f} (terms {(ts, ta)})")
-    assert np.all(diff <= bound)
-    # load (b_extra is added as it is)
-    e = rng.standard_normal(2 * op.ndofs)
-    bs, bsabs = op.load(d, f, return_abs=True)
-    diff, bound = np.abs(bs - b), U * (ts * bsabs + ta * babs)
-    print(f"p={p} per_cell={per_cell}: load max |diff| / bound = {_ratio(diff, bound):.3f}")
-    assert np.all(diff <= bound)
-    assert np.array_equal(op.load(d, f, e), bs + e)
-    # diagonal
-    dg, dabs = op.diagonal(return_abs=True)
-    diff, bound = np.abs(dg - A.diagonal()), U * (ts * dabs + ta * Aabs.diagonal())
-    print(f"p={p} per_cell={per_cell}: diagonal max |diff| / bound = {_ratio(diff, bound):.3f}")
-    assert np.all(diff <= bound) and np.all(dg > 0.0)
-    # residual and mask
-    bf = mesh.boundary_facets()
-    op.set_dirichlet(bf, bf)
-    r = op.residual(bs, u)
-    assert np.array_equal(r[~op.fixed], (bs - y)[~op.fixed]) and np.all(r[op.fixed] == 0.0)
-    ym = op.apply(u, masked=True)
-    assert np.array_equal(ym[~op.fixed], y[~op.fixed]) and np.all(ym[op.fixed] == 0.0)
+    ec.check_statement(MESH, p, per_cell)
 
 
 # ---- the mask -------------------------------------------------------------------------------------------------------

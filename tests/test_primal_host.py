@@ -36,9 +36,7 @@ def _meshes():
 MESHES = _meshes()
 
 
-def _ratio(diff, bound):
-    """max of diff / bound with 0 / 0 = 0 (printed); the assertion is diff <= bound entry by entry"""
-    return float(np.max(np.where(bound > 0.0, diff / np.where(bound > 0.0, bound, 1.0), np.where(diff > 0.0, np.inf, 0.0))))
+_ratio = pc.ratio
 
 
 # ---- tables ---------------------------------------------------------------------------------------------------------
@@ -116,44 +114,7 @@ def test_library_tables_are_the_generated_ones():
 @pytest.mark.parametrize("name", sorted(MESHES))
 @pytest.mark.parametrize("p", [1, 2, 3, 4])
 def test_statement_equals_the_assembled_operator(name, p):
-    mesh = MESHES[name]
-    rng = np.random.default_rng(5 + p)
-    kappa = pc.kappa_of(mesh.ncells)
-    op = primal.PoissonOperator(mesh, p, kappa)
-    d = min(p - 1, 3) if p > 1 else 1
-    nd = (d + 1) * (d + 2) // 2
-    f = rng.standard_normal(mesh.ncells * nd)
-    A, Aabs, b, babs = pc.assemble(mesh, p, kappa, d, f)
-    assert A.shape[0] == op.ndofs
-    u = rng.standard_normal(op.ndofs)
-    valence = int(np.diff(mesh.node_cells_offsets).max())
-    ts, ta = pc.chain_terms(p, valence, make_quadrature_triangle(2 * p + 4)[1].size)
-    terms = (ts, ta)
-    # operator
-    y, yabs = op.apply(u, return_abs=True)
-    diff, bound = np.abs(y - A @ u), U * (ts * yabs + ta * (Aabs @ np.abs(u)))
-    print(f"{name} p={p}: apply max |diff| / bound = {_ratio(diff, bound):.3f} (terms {terms})")
-    assert np.all(diff <= bound)
-    # load (b_extra is added as it is)
-    e = rng.standard_normal(op.ndofs)
-    bs, bsabs = op.load(d, f, return_abs=True)
-    diff, bound = np.abs(bs - b), U * (ts * bsabs + ta * babs)
-    print(f"{name} p={p}: load max |diff| / bound = {_ratio(diff, bound):.3f}")
-    assert np.all(diff <= bound)
-    assert np.array_equal(op.load(d, f, e), bs + e)
-    # diagonal
-    dg, dabs = op.diagonal(return_abs=True)
-    diff, bound = np.abs(dg - A.diagonal()), U * (ts * dabs + ta * Aabs.diagonal())
-    print(f"{name} p={p}: diagonal max |diff| / bound = {_ratio(diff, bound):.3f}")
-    assert np.all(diff <= bound) and np.all(dg > 0.0)
-    # residual and mask
-    op.set_dirichlet(mesh.boundary_facets())
-    r = op.residual(bs, u)
-    assert np.array_equal(r[~op.fixed], (bs - y)[~op.fixed]) and np.all(r[op.fixed] == 0.0)
-    ym = op.apply(u, masked=True)
-    assert np.array_equal(ym[~op.fixed], y[~op.fixed]) and np.all(ym[op.fixed] == 0.0)
-    assert op.fixed.sum() == np.unique(mesh.facet_nodes[mesh.boundary_facets()]).size \
-        + (p - 1) * mesh.boundary_facets().size
+    pc.check_statement(MESHES[name], p, name)
 
 
 def test_dirichlet_mask_replaces_and_refuses():
