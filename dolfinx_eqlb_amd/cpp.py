@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_hierarchy_solve",
     "eqlb_primal_apply_many", "eqlb_primal_solve_many", "eqlb_hierarchy_precondition_many",
     "eqlb_hierarchy_solve_many",
+    "eqlb_hierarchy_set_local", "eqlb_hierarchy_active", "eqlb_hierarchy_active_count",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -1675,11 +1676,15 @@ class Multilevel:
     solvers[l + 1].  Everything is borrowed (and kept alive here); masks and diagonals are read when a call runs, so
     set_dirichlet on a level takes effect at the next call.  One level is plain Jacobi.  The methods take and return host
     arrays; the `_raw` variants take raw pointers (ints) in `memspace`, ordered on `stream`.  The calls use the work
-    space of the solver handles: one stream, one call after the other."""
+    space of the solver handles: one stream, one call after the other.
+    local=True (or the `local` property, at any time): local smoothing for adaptively refined hierarchies - a level
+    l >= 1 smooths only the rows whose basis function is new or changed there (Hierarchy(..., local=True) states the
+    rule); precondition, solve and their _many forms honour it.  active(level) / active_count(level) show the rows."""
 
-    def __init__(self, solvers, refinements, stream=0):
+    def __init__(self, solvers, refinements, local=False, stream=0):
         self.solvers, self.refinements = list(solvers), list(refinements)
         self._h = C.c_void_p()
+        self._local = False
         n = len(self.solvers)
         if n < 1 or len(self.refinements) != n - 1:
             raise RuntimeError("Multilevel: one Refinement per pair of neighbouring levels expected")
@@ -1694,10 +1699,42 @@ class Multilevel:
         pl = (C.c_void_p * max(n - 1, 1))(*[q._h.value for q in plans])
         _check(lib().eqlb_hierarchy_create(C.c_int32(n), C.c_int32(self.bs), sv, pl, ms, C.c_void_p(stream),
                                            C.byref(self._h)))
+        if local:
+            self.set_local(True, stream)
 
     @property
     def nlevels(self):
         return len(self.solvers)
+
+    @property
+    def local(self):
+        return self._local
+
+    @local.setter
+    def local(self, on):
+        self.set_local(on)
+
+    def set_local(self, on, stream=0):
+        """eqlb_hierarchy_set_local: switching on writes the masks on `stream` and waits for the device."""
+        flag = int(on) if isinstance(on, (bool, int, np.integer)) else -1
+        _check(lib().eqlb_hierarchy_set_local(self._h, C.c_int32(flag), C.c_void_p(stream)))
+        self._local = bool(flag)
+
+    def active(self, level, stream=0):
+        """bool [bs * ndofs_level]: the rows the local rule smooths on `level` (all of level 0)."""
+        ok = 0 <= level < self.nlevels
+        out = np.zeros(self.nrows[level] if ok else 1, dtype=np.uint8)
+        self.active_raw(level, out.ctypes.data, out.size, MEM_HOST, stream)
+        return out.astype(bool)
+
+    def active_raw(self, level, out, capacity, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_hierarchy_active(self._h, C.c_int32(level), _vp(out), C.c_int64(capacity),
+                                           C.c_int32(memspace), C.c_void_p(stream)))
+
+    def active_count(self, level):
+        n = C.c_int64(0)
+        _check(lib().eqlb_hierarchy_active_count(self._h, C.c_int32(level), C.byref(n)))
+        return int(n.value)
 
     def _vec(self, a, level):
         v = np.ascontiguousarray(a, dtype=np.float64).ravel()

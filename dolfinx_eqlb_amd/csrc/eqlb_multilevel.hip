@@ -11,6 +11,8 @@
 //  k_ml_mask     r_L = r with the fixed rows set to 0
 //  k_ml_combine  z = t + r / diag on the free rows, 0 on the fixed ones (t: the prolonged z of the level below; none on
 //                the coarsest level); quotient and sum rounded singly, contraction off
+//  k_ml_combine_local  the same with the mask of the local rule: a free row that is not active on its level takes t as it
+//                is - no quotient, no addition; r and diag are read on the active rows only
 //  k_ml_update   k_pcg_update without the fused z = r / diag: u += alpha d, r -= alpha q, block partials of r.r
 //  k_ml_dot      block partials of r.z in the fixed order of the other inner products, into channel 1
 // The scalar steps are k_pcg_scalar; those that consume r.z (start, beta, replace) run with its `ml` flag: one more
@@ -25,10 +27,16 @@
 // works on the columns of a ManyCols, the prolongation takes the columns as its nrhs - still 2 + 4 L launches.  The work
 // space for one column (r_l, z_l and the prolongation temporary t_l of every level) is carved out of one allocation at
 // create; the one for more columns is grown by the first call that needs it (prepare).
+// Local smoothing (eqlb_hierarchy_set_local; the rule: the head of lsolver/multilevel.py): a mask uint8 [bs ndofs_l] per
+// level l >= 1, owned by the handle, written by k_ml_active from the parent-to-children table the plan of link l - 1
+// keeps for k_prolong and k_restrict (coff) and the dofmap of level l.  With the switch on, the combines of the levels
+// l >= 1 are k_ml_combine_local; the launches of an application stay 2 + 4 L, and with the switch off they are the
+// launches of a handle that never saw the switch.
 #include "eqlb_device_common.h"
 #include "eqlb_refine_plan.h" // (eqlb_mesh_handle.h, eqlb_host_util.h)
 #include "eqlb_primal_common.h" // PcgState, the scalar and vector kernels and the host loop of the CG
 
+#include <algorithm>
 #include <climits>
 #include <vector>
 
@@ -80,6 +88,85 @@ k_ml_combine(int64_t n, const ManyCols cols, const double* __restrict__ t, const
       z[k * n + d] = fx ? 0.0 : v;
     }
   }
+}
+
+// the combine of a level l >= 1 under the local rule: t is there, and so is the mask of the level
+template <int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_combine_local(int64_t n, const ManyCols cols, const double* __restrict__ t, const double* __restrict__ r,
+                   const double* __restrict__ diag, const uint8_t* __restrict__ fixed,
+                   const uint8_t* __restrict__ active, double* __restrict__ z)
+{
+#pragma clang fp contract(off) // the statement rounds the quotient and the sum singly
+  const uint32_t live = cols_live<NC>(cols);
+  if (!live)
+    return;
+  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; d < n; d += (int64_t)gridDim.x * PS_THREADS)
+  {
+    const bool fx = fixed[d];
+    const bool on = !fx && active[d];
+    const double dg = on ? diag[d] : 1.0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+    {
+      if (!col_on<NC>(live, k))
+        continue;
+      double v = 0.0;
+      if (!fx)
+      {
+        v = t[k * n + d];
+        if (on)
+          v = v + r[k * n + d] / dg;
+      }
+      z[k * n + d] = v;
+    }
+  }
+}
+
+// The mask of one level l >= 1: one thread per cell of the level below, which walks its children - the fine cells, in
+// the order k_restrict walks them.  The children of a bisected cell (more than one child) write 1 to the bs rows of
+// every DOF of their row of the dofmap: the same byte from several threads, plain stores, no atomics (k_elast_mask
+// does the same).  The mask is cleared before the launch; an index outside the level addresses nothing.
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_active(int32_t ncells, int64_t ncells2, const uint32_t* __restrict__ coff, int nd, int bs,
+            const int32_t* __restrict__ cell_dofs2, int64_t ndofs2, uint8_t* __restrict__ active)
+{
+  const int64_t c = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (c >= ncells)
+    return;
+  const int64_t first = coff[c], last = coff[c + 1];
+  if (last - first < 2 || last > ncells2)
+    return;
+  for (int64_t c2 = first; c2 < last; ++c2)
+    for (int i = 0; i < nd; ++i)
+    {
+      const int64_t d = cell_dofs2[c2 * nd + i];
+      if (d < 0 || d >= ndofs2)
+        continue;
+      for (int b = 0; b < bs; ++b)
+        active[d * bs + b] = 1;
+    }
+}
+
+// the population of a mask, added to *count (cleared before the launch): one integer atomic per block
+__global__ void __launch_bounds__(PS_THREADS)
+k_ml_count(int64_t n, const uint8_t* __restrict__ active, unsigned long long* __restrict__ count)
+{
+  __shared__ unsigned long long sh[PS_THREADS];
+  const int t = threadIdx.x;
+  unsigned long long mine = 0;
+  for (int64_t d = (int64_t)blockIdx.x * PS_THREADS + t; d < n; d += (int64_t)gridDim.x * PS_THREADS)
+    mine += active[d] ? 1u : 0u;
+  sh[t] = mine;
+  __syncthreads();
+  for (int half = PS_THREADS / 2; half > 0; half >>= 1)
+  {
+    if (t < half)
+      sh[t] += sh[t + half];
+    __syncthreads();
+  }
+  if (t == 0 && sh[0])
+    atomicAdd(count, sh[0]);
 }
 
 // u += alpha d, r -= alpha q on the free rows; partials of r.r of column k: part[2 k][block]
@@ -176,6 +263,13 @@ struct eqlb_hierarchy
   std::vector<Vectors> one, wide;              // the views for one column, and for wide_R of them: grown on demand
   int wide_R = 0;
   eqlb::DevBuf<char> wide_mem;
+  // local smoothing: the masks of the levels l >= 1 (level 0 has none), carved at create and allocated by the first
+  // eqlb_hierarchy_set_local(1); their populations
+  int local = 0;
+  eqlb::DevCarve act_mem;
+  std::vector<eqlb::DevPiece<uint8_t>> act;
+  eqlb::DevPiece<unsigned long long> act_count_dev; // [nlevels]
+  std::vector<int64_t> act_count;
 };
 
 namespace eqlb
@@ -250,8 +344,13 @@ int enqueue_precondition(const char* who, const eqlb_hierarchy& h, const ManyCol
     EQLB_TRY(eqlb_refine_prolong_lagrange(h.plans[l - 1], h.lv[l].mesh, h.p, h.bs, c.R, h.lv[l - 1].cell_dofs,
                                           h.lv[l - 1].ndofs, v[l - 1].z, h.lv[l].cell_dofs, h.lv[l].ndofs, v[l].t,
                                           EQLB_MEM_DEVICE, stream));
-    EQLB_LAUNCH_COLS(MANY_R, k_ml_combine, c.R, h.n[l], stream, h.n[l], c, static_cast<const double*>(v[l].t),
-                     static_cast<const double*>(v[l].r), h.lv[l].diag, h.lv[l].fixed, l == L ? z : v[l].z);
+    if (h.local)
+      EQLB_LAUNCH_COLS(MANY_R, k_ml_combine_local, c.R, h.n[l], stream, h.n[l], c, static_cast<const double*>(v[l].t),
+                       static_cast<const double*>(v[l].r), h.lv[l].diag, h.lv[l].fixed,
+                       static_cast<const uint8_t*>(h.act[l].get()), l == L ? z : v[l].z);
+    else
+      EQLB_LAUNCH_COLS(MANY_R, k_ml_combine, c.R, h.n[l], stream, h.n[l], c, static_cast<const double*>(v[l].t),
+                       static_cast<const double*>(v[l].r), h.lv[l].diag, h.lv[l].fixed, l == L ? z : v[l].z);
     HIP_TRY(hipGetLastError());
   }
   return EQLB_OK;
@@ -437,12 +536,117 @@ try
   h->one.resize(nlevels);
   for (int l = 0; l < nlevels; ++l)
     h->one[l] = {h->r[l].get(), h->z[l].get(), h->t[l].get()};
+  h->act.resize(nlevels);
+  for (int l = 1; l < nlevels; ++l)
+    h->act[l] = h->act_mem.piece<uint8_t>((size_t)h->n[l]);
+  h->act_count_dev = h->act_mem.piece<unsigned long long>((size_t)nlevels);
+  h->act_count.assign(nlevels, 0);
   *out = h.release();
   return EQLB_OK;
 }
 EQLB_CATCH_ALL
 
 void eqlb_hierarchy_destroy(eqlb_hierarchy_t* handle) { delete handle; }
+
+int eqlb_hierarchy_set_local(eqlb_hierarchy_t* h, int32_t local, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_set_local";
+  if (!h)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (local != 0 && local != 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: local = %d is not 0 or 1", who, (int)local);
+  if (local == h->local)
+    return EQLB_OK;
+  if (local == 0)
+  {
+    h->local = 0;
+    return EQLB_OK;
+  }
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!h->act_mem.base())
+    HIP_TRY(h->act_mem.alloc());
+  // (the masks follow from the plans alone, but they are written again on the stream of this call: what runs behind it
+  // on that stream finds them)
+  HIP_TRY(hipMemsetAsync(h->act_mem.base(), 0, h->act_mem.bytes(), stream));
+  const int nd = nd_of(h->p);
+  for (int l = 1; l < h->nlevels; ++l)
+  {
+    const eqlb_refine& pl = *h->plans[l - 1];
+    hipLaunchKernelGGL(k_ml_active, dim3(grid_of(pl.ncells, PS_THREADS)), dim3(PS_THREADS), 0, stream, pl.ncells,
+                       (int64_t)pl.ncells2, static_cast<const uint32_t*>(pl.coff.get()), nd, h->bs, h->lv[l].cell_dofs,
+                       h->lv[l].ndofs, h->act[l].get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ml_count, dim3(stream_blocks(h->n[l])), dim3(PS_THREADS), 0, stream, h->n[l],
+                       static_cast<const uint8_t*>(h->act[l].get()), h->act_count_dev.get() + l);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<unsigned long long> cnt(h->nlevels, 0);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), h->act_count_dev.get(), cnt.size() * sizeof(cnt[0]), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int l = 1; l < h->nlevels; ++l)
+    h->act_count[l] = (int64_t)cnt[l];
+  h->act_count[0] = h->n[0];
+  h->local = 1;
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_active(eqlb_hierarchy_t* h, int32_t level, uint8_t* out, int64_t capacity, int32_t memspace,
+                          void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_active";
+  if (!h || !out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (!h->local)
+    return fail(EQLB_ERR_INVALID_ARGUMENT,
+                "%s: the hierarchy smooths every row: switch local smoothing on first (eqlb_hierarchy_set_local)", who);
+  if (level < 0 || level > h->nlevels - 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: level = %d outside 0 ... %d", who, (int)level, h->nlevels - 1);
+  EQLB_TRY(check_memspace(who, memspace));
+  const int64_t n = h->n[level];
+  if (capacity < n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: capacity = %lld below the %lld rows of level %d", who,
+                (long long)capacity, (long long)n, (int)level);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (memspace == EQLB_MEM_DEVICE)
+  {
+    if (level == 0)
+      HIP_TRY(hipMemsetAsync(out, 1, (size_t)n, stream));
+    else
+      HIP_TRY(hipMemcpyAsync(out, h->act[level].get(), (size_t)n, hipMemcpyDeviceToDevice, stream));
+    return EQLB_OK;
+  }
+  if (level == 0)
+  {
+    std::fill(out, out + n, (uint8_t)1);
+    return EQLB_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(out, h->act[level].get(), (size_t)n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_active_count(eqlb_hierarchy_t* h, int32_t level, int64_t* count)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_active_count";
+  if (!h || !count)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (!h->local)
+    return fail(EQLB_ERR_INVALID_ARGUMENT,
+                "%s: the hierarchy smooths every row: switch local smoothing on first (eqlb_hierarchy_set_local)", who);
+  if (level < 0 || level > h->nlevels - 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: level = %d outside 0 ... %d", who, (int)level, h->nlevels - 1);
+  *count = h->act_count[level];
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
 
 int eqlb_hierarchy_restrict(eqlb_hierarchy_t* h, int32_t level, const double* r_fine, double* r_coarse, int32_t masked,
                             int32_t memspace, void* stream_)

@@ -526,9 +526,10 @@ struct Multilevel
   eqlb_hierarchy_t* h = nullptr;
   py::list keep_solvers, keep_transfers; // everything is borrowed: it stays alive with the carrier
   int bs = 1, nlevels = 0;
+  bool local = false;                    // local smoothing (eqlb_hierarchy_set_local)
   std::vector<int64_t> n;                // rows of a vector per level
 
-  Multilevel(py::list solvers, py::list transfers) : keep_solvers(solvers), keep_transfers(transfers)
+  Multilevel(py::list solvers, py::list transfers, bool local_) : keep_solvers(solvers), keep_transfers(transfers)
   {
     nlevels = (int)py::len(solvers);
     if (nlevels < 1 || (int)py::len(transfers) != nlevels - 1)
@@ -554,11 +555,42 @@ struct Multilevel
         pl.push_back(transfers[l].cast<std::shared_ptr<Transfer>>()->plan);
     }
     check(eqlb_hierarchy_create(nlevels, bs, sv.data(), pl.data(), ms.data(), nullptr, &h));
+    if (local_)
+    {
+      const int st = eqlb_hierarchy_set_local(h, 1, nullptr);
+      if (st != EQLB_OK)
+        eqlb_hierarchy_destroy(h); // (the destructor of an object whose constructor throws does not run)
+      check(st);
+      local = true;
+    }
   }
   ~Multilevel() { eqlb_hierarchy_destroy(h); }
   Multilevel(const Multilevel&) = delete;
   Multilevel& operator=(const Multilevel&) = delete;
 
+  void set_local(bool on)
+  {
+    check(eqlb_hierarchy_set_local(h, on ? 1 : 0, nullptr));
+    local = on;
+  }
+  // the rows the local rule smooths on `level`
+  py::array_t<bool> active(int level) const
+  {
+    const bool ok = level >= 0 && level < nlevels;
+    std::vector<uint8_t> v((size_t)(ok ? n[level] : 1));
+    check(eqlb_hierarchy_active(h, level, v.data(), (int64_t)v.size(), EQLB_MEM_HOST, nullptr));
+    py::array_t<bool> out((py::ssize_t)v.size());
+    bool* o = out.mutable_data();
+    for (size_t i = 0; i < v.size(); ++i)
+      o[i] = v[i] != 0;
+    return out;
+  }
+  int64_t active_count(int level) const
+  {
+    int64_t c = 0;
+    check(eqlb_hierarchy_active_count(h, level, &c));
+    return c;
+  }
   // level + 1 -> level
   darray restrict(int level, darray r, bool masked) const
   {
@@ -1494,7 +1526,11 @@ PYBIND11_MODULE(_cpp, m)
       m, "Multilevel", "Multilevel preconditioner (BPX) over the levels of an adaptive loop: solvers coarsest first (all "
                        "PrimalPoisson or all PrimalElasticity), transfers[l] the Transfer of Mesh.refine(..., "
                        "keep_plan=True) between level l and l + 1 (eqlb_hierarchy_*)")
-      .def(py::init<py::list, py::list>(), py::arg("solvers"), py::arg("transfers"))
+      .def(py::init<py::list, py::list, bool>(), py::arg("solvers"), py::arg("transfers"), py::arg("local") = false)
+      .def_property("local", [](const Multilevel& self) { return self.local; }, &Multilevel::set_local,
+                    "local smoothing: a level l >= 1 smooths only the rows whose basis function is new or changed there")
+      .def("active", &Multilevel::active, py::arg("level"), "bool [bs ndofs_level]: the rows smoothed on `level`")
+      .def("active_count", &Multilevel::active_count, py::arg("level"), "the number of rows smoothed on `level`")
       .def("restrict", &Multilevel::restrict, py::arg("level"), py::arg("r"), py::arg("masked") = true,
            "r [level + 1] -> P^T r [level]; masked: 0 on the fixed rows of the coarse level")
       .def("precondition", &Multilevel::precondition, py::arg("r"), "z = M r on the finest level")

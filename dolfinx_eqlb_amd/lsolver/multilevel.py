@@ -23,18 +23,38 @@ reproduced bit for bit, because nothing in them reduces across threads except ow
              reference norm, the true residual decides, replacement.  One more breakdown: r . z <= 0 (or NaN)
 
 One level is plain Jacobi.
+
+Local smoothing (Hierarchy(ops, links, local=True); eqlb_hierarchy_set_local).  The sum above smooths every row of every
+level.  Where an adaptive loop refines a few percent of the cells per step, most rows of level l + 1 carry the basis
+function they carried on level l, and the full sum counts that function once per level it survives.  With local=True a
+level l >= 1 smooths only the rows whose basis function is new or changed there:
+
+  changed    a cell of level l whose parent has more than one child: np.bincount(parent_cell)[parent_cell] > 1 on
+             links[l - 1]
+  active     a scalar DOF of level l that belongs to a changed cell (mesh.transfer.lagrange_dofmap); row bs dof + r with
+             its DOF; on level 0 every row
+  down, coarsest   as above
+  up         a fixed row is 0; an active free row is prolong(z_l)[row] + r_{l+1}[row] / diag_{l+1}[row], quotient and sum
+             rounded singly; an inactive free row takes prolong(z_l)[row] as it is - no addition, a -0.0 stays -0.0
+
+A cell with one child is its parent, so an inactive row is a unit row of the prolongation: its function is the one of
+the level below.  The preconditioner is still a sum of P M P^T terms with M diagonal and non-negative and level 0 in
+full, so it is symmetric; and it is positive definite on the free rows because every free fine row is reached: a DOF
+that is new on a level lies in a bisected cell and is active there, and one that was there from the start is active on
+level 0.  On uniformly refined levels every row is active and the result is that of local=False bit for bit.
 """
 
 import numpy as np
 
-from ..mesh.transfer import prolong_lagrange, restrict_lagrange
+from ..mesh.transfer import lagrange_dofmap, prolong_lagrange, restrict_lagrange
 from .primal import PoissonOperator, pcg_columns
 
 
 class Hierarchy:
-    """Hierarchy(ops, links): the statements on a hierarchy of levels, coarsest first."""
+    """Hierarchy(ops, links, local=False): the statements on a hierarchy of levels, coarsest first.  local: smooth on
+    the levels l >= 1 only the rows whose basis function is new or changed there (the head of this file)."""
 
-    def __init__(self, ops, links):
+    def __init__(self, ops, links, local=False):
         ops, links = list(ops), list(links)
         if len(ops) < 1 or len(links) != len(ops) - 1:
             raise ValueError("Hierarchy: one link per pair of neighbouring levels expected")
@@ -49,6 +69,8 @@ class Hierarchy:
             if pc.size != ops[l + 1].mesh.ncells:
                 raise ValueError(f"Hierarchy: link {l} does not fit the mesh of level {l + 1}")
         self._diag = [None] * len(ops)
+        self.local = bool(local)
+        self._active = [None] * len(ops)
 
     @property
     def nlevels(self):
@@ -58,6 +80,25 @@ class Hierarchy:
         if self._diag[level] is None:
             self._diag[level] = self.ops[level].diagonal()
         return self._diag[level]
+
+    def active(self, level):
+        """bool [bs * ndofs_level]: the rows the local rule smooths on `level` (local=True only)."""
+        if not self.local:
+            raise ValueError("Hierarchy.active: the hierarchy smooths every row (local=False)")
+        if level < 0 or level >= self.nlevels:
+            raise ValueError(f"Hierarchy.active: level = {level} outside 0 ... {self.nlevels - 1}")
+        if self._active[level] is None:
+            op = self.ops[level]
+            if level == 0:
+                dofs = np.ones(op.ndofs, dtype=bool)
+            else:
+                pc = self.links[level - 1][0].astype(np.int64)
+                changed = np.bincount(pc)[pc] > 1
+                cell_dofs, ndofs = lagrange_dofmap(op.mesh, self.p)
+                dofs = np.zeros(ndofs, dtype=bool)
+                dofs[cell_dofs[changed].ravel()] = True
+            self._active[level] = np.repeat(dofs, self.bs)
+        return self._active[level]
 
     def restrict(self, level, r_fine, masked=True, return_abs=False):
         """level + 1 -> level."""
@@ -82,7 +123,11 @@ class Hierarchy:
             rs[l] = self.restrict(l, rs[l + 1])
         z = np.where(self.ops[0].fixed, 0.0, rs[0] / self.diag(0))
         for l in range(1, L + 1):
-            z = np.where(self.ops[l].fixed, 0.0, self.prolong(l - 1, z) + rs[l] / self.diag(l))
+            t = self.prolong(l - 1, z)
+            z = t + rs[l] / self.diag(l)
+            if self.local:
+                z = np.where(self.active(l), z, t)
+            z = np.where(self.ops[l].fixed, 0.0, z)
         return z
 
     def pcg(self, b, u, rtol=1e-8, atol=0.0, maxit=1000):

@@ -1040,8 +1040,8 @@ int eqlb_elasticity_solve(eqlb_elasticity_t* handle, const double* b, double* u,
  * Refused by name before anything is launched: null arguments, nlevels < 1, bs not 1 or 2, levels of different p, a
  * plan whose counts do not fit its two meshes, a solver whose mesh is not that of its level, `level` outside
  * 0 ... nlevels - 2, an unknown memory space.  nlevels = 1 is plain Jacobi.
- * Not provided: the multiplicative cycle, skipping the unchanged regions of locally refined levels, a solve on the
- * coarsest level. */
+ * Not provided: the multiplicative cycle, transfers that skip the unchanged regions of locally refined levels (local
+ * smoothing below leaves the cost of an application where it was), a solve on the coarsest level. */
 typedef struct eqlb_hierarchy eqlb_hierarchy_t;
 int eqlb_hierarchy_create(int32_t nlevels, int32_t bs, void* const* solvers, eqlb_refine_t* const* plans,
                           eqlb_mesh_t* const* meshes, void* stream, eqlb_hierarchy_t** out);
@@ -1051,6 +1051,30 @@ int eqlb_hierarchy_restrict(eqlb_hierarchy_t* handle, int32_t level, const doubl
 int eqlb_hierarchy_precondition(eqlb_hierarchy_t* handle, const double* r, double* z, int32_t memspace, void* stream);
 int eqlb_hierarchy_solve(eqlb_hierarchy_t* handle, const double* b, double* u, double rtol, double atol,
                          int32_t maxit, double* info, int32_t memspace, void* stream);
+/* Local smoothing for adaptively refined hierarchies.  The sum above smooths every row of every level; where a step
+ * refines a few percent of the cells, most rows of level l + 1 carry the basis function of level l, which the sum then
+ * counts once per level it survives.  With the switch on, a level l >= 1 smooths only the rows whose basis function is
+ * new or changed there (dolfinx_eqlb_amd/lsolver/multilevel.py: Hierarchy(..., local=True) states it):
+ *   active    a cell of level l is changed when its parent has more than one child; a DOF of level l is active when it
+ *             belongs to a changed cell, row bs dof + r with its DOF; every row of level 0 is active
+ *   up        z_{l+1} = prolong(z_l) + r_{l+1} / diag_{l+1} on the active free rows, prolong(z_l) as it is on the other
+ *             free rows (no addition: -0.0 stays -0.0), 0 on the fixed rows.  Down and the coarsest level are unchanged
+ * Every free fine row is reached (a new DOF on the level where it appears, an old one on level 0), so the
+ * preconditioner stays symmetric positive definite on the free rows; on uniformly refined levels it is the full sum
+ * bit for bit.  eqlb_hierarchy_precondition, _precondition_many, _solve and _solve_many honour the switch; their
+ * checks, texts, info and launch count (2 + 4 L) do not change, and a handle whose switch is off (as created) gives
+ * the bits it gave before the switch existed.
+ *   set_local     local = 1 writes the masks (uint8 [bs ndofs_l] per level l >= 1, owned by the handle, allocated by the
+ *                 first call) on `stream`, one launch per level over the cells of the plan of link l - 1 and its
+ *                 children, counts them, and waits for the device; local = 0 switches back.  Idempotent.  Any other
+ *                 value: EQLB_ERR_INVALID_ARGUMENT
+ *   active        out [capacity >= bs ndofs_level] of 0 / 1 in `memspace`; level 0: all ones
+ *   active_count  the number of ones
+ * active and active_count with the switch off: EQLB_ERR_INVALID_ARGUMENT, the text names eqlb_hierarchy_set_local. */
+int eqlb_hierarchy_set_local(eqlb_hierarchy_t* handle, int32_t local, void* stream);
+int eqlb_hierarchy_active(eqlb_hierarchy_t* handle, int32_t level, uint8_t* out, int64_t capacity, int32_t memspace,
+                          void* stream);
+int eqlb_hierarchy_active_count(eqlb_hierarchy_t* handle, int32_t level, int64_t* count);
 /* Several right-hand sides on a hierarchy of Poisson handles, by the rule of eqlb_primal_solve_many: column c of
  * eqlb_hierarchy_precondition_many is eqlb_hierarchy_precondition of r_c, column c of eqlb_hierarchy_solve_many is
  * eqlb_hierarchy_solve of (b_c, u_c) - the same bits, the same info [nrhs][8].  Vectors [nrhs][ndofs_L], groups of at
