@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_primal_apply_many", "eqlb_primal_solve_many", "eqlb_hierarchy_precondition_many",
     "eqlb_hierarchy_solve_many",
     "eqlb_hierarchy_set_local", "eqlb_hierarchy_active", "eqlb_hierarchy_active_count",
+    "eqlb_hierarchy_set_coarse", "eqlb_hierarchy_coarse_rows", "eqlb_hierarchy_coarse_factor",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -1679,12 +1680,17 @@ class Multilevel:
     space of the solver handles: one stream, one call after the other.
     local=True (or the `local` property, at any time): local smoothing for adaptively refined hierarchies - a level
     l >= 1 smooths only the rows whose basis function is new or changed there (Hierarchy(..., local=True) states the
-    rule); precondition, solve and their _many forms honour it.  active(level) / active_count(level) show the rows."""
+    rule); precondition, solve and their _many forms honour it.  active(level) / active_count(level) show the rows.
+    coarse=True (or the `coarse` property, at any time): level 0 is solved exactly on its free rows (at most 4096) by a
+    dense LDL^T factor in the place of its diagonal (Hierarchy(..., coarse=True) states the rule).  The factor is a
+    snapshot of the mask and the coefficient of level 0: every set_coarse(True) factors again, and set_dirichlet or a
+    new coefficient on level 0 needs another one.  coarse_rows / coarse_factor() show it."""
 
-    def __init__(self, solvers, refinements, local=False, stream=0):
+    def __init__(self, solvers, refinements, local=False, stream=0, coarse=False):
         self.solvers, self.refinements = list(solvers), list(refinements)
         self._h = C.c_void_p()
         self._local = False
+        self._coarse = False
         n = len(self.solvers)
         if n < 1 or len(self.refinements) != n - 1:
             raise RuntimeError("Multilevel: one Refinement per pair of neighbouring levels expected")
@@ -1701,6 +1707,8 @@ class Multilevel:
                                            C.byref(self._h)))
         if local:
             self.set_local(True, stream)
+        if coarse:
+            self.set_coarse(True, stream)
 
     @property
     def nlevels(self):
@@ -1735,6 +1743,42 @@ class Multilevel:
         n = C.c_int64(0)
         _check(lib().eqlb_hierarchy_active_count(self._h, C.c_int32(level), C.byref(n)))
         return int(n.value)
+
+    @property
+    def coarse(self):
+        return self._coarse
+
+    @coarse.setter
+    def coarse(self, on):
+        self.set_coarse(on)
+
+    def set_coarse(self, on, stream=0):
+        """eqlb_hierarchy_set_coarse: switching on factors level 0 on `stream` (again, if it was on) and waits for the
+        device; a refusal leaves the switch off."""
+        flag = int(on) if isinstance(on, (bool, int, np.integer)) else -1
+        if flag == 1:
+            self._coarse = False
+        _check(lib().eqlb_hierarchy_set_coarse(self._h, C.c_int32(flag), C.c_void_p(stream)))
+        self._coarse = bool(flag)
+
+    @property
+    def coarse_rows(self):
+        """the number of free rows of level 0 the factor was formed on"""
+        n = C.c_int64(0)
+        _check(lib().eqlb_hierarchy_coarse_rows(self._h, C.byref(n)))
+        return int(n.value)
+
+    def coarse_factor(self, stream=0):
+        """(rows int32 [n], d [n], W [n][n]): the free rows of level 0, the pivots and the unit lower triangular
+        W = L^-1 of the factor."""
+        n = self.coarse_rows
+        rows, d, W = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros((n, n))
+        self.coarse_factor_raw(rows.ctypes.data, d.ctypes.data, W.ctypes.data, n, MEM_HOST, stream)
+        return rows, d, W
+
+    def coarse_factor_raw(self, rows, d, W, capacity, memspace=MEM_DEVICE, stream=0):
+        _check(lib().eqlb_hierarchy_coarse_factor(self._h, _vp(rows), _vp(d), _vp(W), C.c_int64(capacity),
+                                                  C.c_int32(memspace), C.c_void_p(stream)))
 
     def _vec(self, a, level):
         v = np.ascontiguousarray(a, dtype=np.float64).ravel()

@@ -7,6 +7,7 @@
 //       eqlb_tiling_host.hip, eqlb_bc_carry.hip,
 //     and eqlb_refine_plan.h by eqlb_mesh_refine.hip, eqlb_transfer.hip, eqlb_bc_carry.hip, eqlb_multilevel.hip,
 //     directly by eqlb_mesh_build.hip, eqlb_marking.hip, eqlb_primal_flux.hip, eqlb_primal_solve.hip,
+//   through eqlb_coarse.h by eqlb_coarse.hip, eqlb_multilevel.hip,
 //   through eqlb_estimate_kernels.h by eqlb_estimate.hip, eqlb_estimate_lowdeg.hip, eqlb_estimate_lowdeg_k4.hip,
 //   directly by eqlb_tiling_device.hip, eqlb_halo_rccl.hip.
 #pragma once

@@ -32,7 +32,12 @@
 // keeps for k_prolong and k_restrict (coff) and the dofmap of level l.  With the switch on, the combines of the levels
 // l >= 1 are k_ml_combine_local; the launches of an application stay 2 + 4 L, and with the switch off they are the
 // launches of a handle that never saw the switch.
+// Exact solve on level 0 (eqlb_hierarchy_set_coarse; the rule: the head of lsolver/multilevel.py; the factor and the two
+// kernels of its application: eqlb_coarse.hip).  With the switch on, the combine of level 0 is not launched: the two
+// launches of coarse_apply stand in its place, and an application is 3 + 4 L launches.  With the switch off the
+// launches are those of a handle that never saw the switch.
 #include "eqlb_device_common.h"
+#include "eqlb_coarse.h"
 #include "eqlb_refine_plan.h" // (eqlb_mesh_handle.h, eqlb_host_util.h)
 #include "eqlb_primal_common.h" // PcgState, the scalar and vector kernels and the host loop of the CG
 
@@ -270,6 +275,8 @@ struct eqlb_hierarchy
   std::vector<eqlb::DevPiece<uint8_t>> act;
   eqlb::DevPiece<unsigned long long> act_count_dev; // [nlevels]
   std::vector<int64_t> act_count;
+  // the exact solve on level 0: the factor of the last eqlb_hierarchy_set_coarse(1), kept until the handle ends
+  eqlb::CoarseSolve coarse;
 };
 
 namespace eqlb
@@ -317,26 +324,34 @@ int enqueue_restrict(const char* who, const eqlb_hierarchy& h, int level, const 
   return EQLB_OK;
 }
 
-// z = M r on the finest level, on the columns of c; r, z DEVICE [R][n_L]; 2 + 4 L launches whatever R is
+// z_0 on level 0 from r_0, on the columns of c: the diagonal, or the exact solve (eqlb_coarse.hip)
+int enqueue_coarsest(const eqlb_hierarchy& h, const ManyCols& c, const double* r, double* z, hipStream_t stream)
+{
+  if (h.coarse.on)
+  {
+    HIP_TRY(coarse_apply(h.coarse, c, r, h.lv[0].fixed, z, stream));
+    return EQLB_OK;
+  }
+  const double* const none = nullptr;
+  EQLB_LAUNCH_COLS(MANY_R, k_ml_combine, c.R, h.n[0], stream, h.n[0], c, none, r, h.lv[0].diag, h.lv[0].fixed, z);
+  HIP_TRY(hipGetLastError());
+  return EQLB_OK;
+}
+
+// z = M r on the finest level, on the columns of c; r, z DEVICE [R][n_L]; 2 + 4 L launches whatever R is (3 + 4 L with
+// the exact solve on level 0)
 int enqueue_precondition(const char* who, const eqlb_hierarchy& h, const ManyCols& c, const double* r, double* z,
                          hipStream_t stream)
 {
   const int L = h.nlevels - 1;
-  const double* const none = nullptr;
   if (L == 0)
-  {
-    EQLB_LAUNCH_COLS(MANY_R, k_ml_combine, c.R, h.n[0], stream, h.n[0], c, none, r, h.lv[0].diag, h.lv[0].fixed, z);
-    HIP_TRY(hipGetLastError());
-    return EQLB_OK;
-  }
+    return enqueue_coarsest(h, c, r, z, stream);
   const std::vector<eqlb_hierarchy::Vectors>& v = c.R == 1 ? h.one : h.wide;
   EQLB_LAUNCH_COLS(MANY_R, k_ml_mask, c.R, h.n[L], stream, h.n[L], c, r, h.lv[L].fixed, v[L].r);
   HIP_TRY(hipGetLastError());
   for (int l = L - 1; l >= 0; --l)
     EQLB_TRY(enqueue_restrict(who, h, l, c, v[l + 1].r, v[l].r, true, stream));
-  EQLB_LAUNCH_COLS(MANY_R, k_ml_combine, c.R, h.n[0], stream, h.n[0], c, none, static_cast<const double*>(v[0].r),
-                   h.lv[0].diag, h.lv[0].fixed, v[0].z);
-  HIP_TRY(hipGetLastError());
+  EQLB_TRY(enqueue_coarsest(h, c, v[0].r, v[0].z, stream));
   for (int l = 1; l <= L; ++l)
   {
     // (k_prolong knows no stop flag and no columns to leave out: it prolongs all R, into a t_l whose idle columns
@@ -589,6 +604,69 @@ try
     h->act_count[l] = (int64_t)cnt[l];
   h->act_count[0] = h->n[0];
   h->local = 1;
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_set_coarse(eqlb_hierarchy_t* h, int32_t coarse, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_set_coarse";
+  if (!h)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (coarse != 0 && coarse != 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: coarse = %d is not 0 or 1", who, (int)coarse);
+  if (coarse == 0)
+  {
+    h->coarse.on = 0; // (the factor keeps its memory)
+    return EQLB_OK;
+  }
+  // (every call factors again: the factor is a snapshot of the mask and the coefficient of level 0)
+  return coarse_setup(who, h->coarse, h->lv[0], reinterpret_cast<hipStream_t>(stream_));
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_coarse_rows(eqlb_hierarchy_t* h, int64_t* n)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_coarse_rows";
+  if (!h || !n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (!h->coarse.on)
+    return fail(EQLB_ERR_INVALID_ARGUMENT,
+                "%s: level 0 is treated by its diagonal: switch the exact solve on first (eqlb_hierarchy_set_coarse)", who);
+  *n = h->coarse.n;
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
+
+int eqlb_hierarchy_coarse_factor(eqlb_hierarchy_t* h, int32_t* rows, double* d, double* W, int64_t capacity,
+                                 int32_t memspace, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* const who = "eqlb_hierarchy_coarse_factor";
+  if (!h || !rows || !d || !W)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (!h->coarse.on)
+    return fail(EQLB_ERR_INVALID_ARGUMENT,
+                "%s: level 0 is treated by its diagonal: switch the exact solve on first (eqlb_hierarchy_set_coarse)", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  const size_t n = (size_t)h->coarse.n;
+  if (capacity < (int64_t)n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: capacity = %lld below the %lld free rows of level 0", who,
+                (long long)capacity, (long long)n);
+  if (n == 0)
+    return EQLB_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const hipMemcpyKind kind = memspace == EQLB_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  HIP_TRY(hipMemcpyAsync(rows, h->coarse.rows.get(), n * sizeof(int32_t), kind, stream));
+  HIP_TRY(hipMemcpyAsync(d, h->coarse.d.get(), n * sizeof(double), kind, stream));
+  HIP_TRY(hipMemcpyAsync(W, h->coarse.W.get(), n * n * sizeof(double), kind, stream));
+  if (memspace == EQLB_MEM_HOST)
+    HIP_TRY(hipStreamSynchronize(stream));
   return EQLB_OK;
 }
 EQLB_CATCH_ALL

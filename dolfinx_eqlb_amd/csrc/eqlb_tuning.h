@@ -54,6 +54,17 @@
 #define EQLB_PRIMAL_CHECK_EVERY 64
 #endif
 
+// ---- exact solve on the coarsest level of a hierarchy (eqlb_coarse.hip) ----
+#ifndef EQLB_COARSE_MAX_ROWS
+#define EQLB_COARSE_MAX_ROWS 4096 // free rows of level 0 at the most: n^2 * 8 B per layout of the factor, two layouts (268 MB)
+#endif
+#ifndef EQLB_COARSE_BLOCK
+#define EQLB_COARSE_BLOCK 32 // columns per step of the blocked LDL^T: the entries of a row of the panel in registers (2 ... 32)
+#endif
+#ifndef EQLB_COARSE_TILE
+#define EQLB_COARSE_TILE 64 // rows and columns of a tile of the trailing updates (two operand tiles of 17 KB in LDS); threads of the per-row kernels (a multiple of 16, at most 64)
+#endif
+
 // ---- weak-symmetry kernels (eqlb_se_weaksym*.hip) ----
 #ifndef EQLB_WS_LEAN_WAVES
 #define EQLB_WS_LEAN_WAVES 2 // waves per SIMD asked for k_se_weaksym_lean

@@ -527,9 +527,11 @@ struct Multilevel
   py::list keep_solvers, keep_transfers; // everything is borrowed: it stays alive with the carrier
   int bs = 1, nlevels = 0;
   bool local = false;                    // local smoothing (eqlb_hierarchy_set_local)
+  bool coarse = false;                   // exact solve on level 0 (eqlb_hierarchy_set_coarse)
   std::vector<int64_t> n;                // rows of a vector per level
 
-  Multilevel(py::list solvers, py::list transfers, bool local_) : keep_solvers(solvers), keep_transfers(transfers)
+  Multilevel(py::list solvers, py::list transfers, bool local_, bool coarse_)
+      : keep_solvers(solvers), keep_transfers(transfers)
   {
     nlevels = (int)py::len(solvers);
     if (nlevels < 1 || (int)py::len(transfers) != nlevels - 1)
@@ -563,6 +565,14 @@ struct Multilevel
       check(st);
       local = true;
     }
+    if (coarse_)
+    {
+      const int st = eqlb_hierarchy_set_coarse(h, 1, nullptr);
+      if (st != EQLB_OK)
+        eqlb_hierarchy_destroy(h);
+      check(st);
+      coarse = true;
+    }
   }
   ~Multilevel() { eqlb_hierarchy_destroy(h); }
   Multilevel(const Multilevel&) = delete;
@@ -572,6 +582,31 @@ struct Multilevel
   {
     check(eqlb_hierarchy_set_local(h, on ? 1 : 0, nullptr));
     local = on;
+  }
+  // (switching on factors level 0, again if it was on; a refusal leaves the switch off)
+  void set_coarse(bool on)
+  {
+    if (on)
+      coarse = false;
+    check(eqlb_hierarchy_set_coarse(h, on ? 1 : 0, nullptr));
+    coarse = on;
+  }
+  int64_t coarse_rows() const
+  {
+    int64_t c = 0;
+    check(eqlb_hierarchy_coarse_rows(h, &c));
+    return c;
+  }
+  // (rows, d, W) of the factor of level 0
+  py::tuple coarse_factor() const
+  {
+    const int64_t c = coarse_rows();
+    py::array_t<int32_t> rows((py::ssize_t)c);
+    darray d((py::ssize_t)c);
+    py::array_t<double, py::array::c_style> W({(py::ssize_t)c, (py::ssize_t)c});
+    check(eqlb_hierarchy_coarse_factor(h, rows.mutable_data(), d.mutable_data(), W.mutable_data(), c, EQLB_MEM_HOST,
+                                       nullptr));
+    return py::make_tuple(rows, d, W);
   }
   // the rows the local rule smooths on `level`
   py::array_t<bool> active(int level) const
@@ -1526,7 +1561,13 @@ PYBIND11_MODULE(_cpp, m)
       m, "Multilevel", "Multilevel preconditioner (BPX) over the levels of an adaptive loop: solvers coarsest first (all "
                        "PrimalPoisson or all PrimalElasticity), transfers[l] the Transfer of Mesh.refine(..., "
                        "keep_plan=True) between level l and l + 1 (eqlb_hierarchy_*)")
-      .def(py::init<py::list, py::list, bool>(), py::arg("solvers"), py::arg("transfers"), py::arg("local") = false)
+      .def(py::init<py::list, py::list, bool, bool>(), py::arg("solvers"), py::arg("transfers"),
+           py::arg("local") = false, py::arg("coarse") = false)
+      .def_property("coarse", [](const Multilevel& self) { return self.coarse; }, &Multilevel::set_coarse,
+                    "exact solve on the free rows of level 0 by a dense LDL^T factor (a snapshot: set it again after "
+                    "set_dirichlet or a new coefficient on level 0)")
+      .def_property_readonly("coarse_rows", &Multilevel::coarse_rows, "the free rows of level 0 the factor was formed on")
+      .def("coarse_factor", &Multilevel::coarse_factor, "(rows int32 [n], d [n], W [n][n]): the factor of level 0")
       .def_property("local", [](const Multilevel& self) { return self.local; }, &Multilevel::set_local,
                     "local smoothing: a level l >= 1 smooths only the rows whose basis function is new or changed there")
       .def("active", &Multilevel::active, py::arg("level"), "bool [bs ndofs_level]: the rows smoothed on `level`")

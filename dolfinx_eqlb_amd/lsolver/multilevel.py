@@ -42,6 +42,25 @@ the level below.  The preconditioner is still a sum of P M P^T terms with M diag
 full, so it is symmetric; and it is positive definite on the free rows because every free fine row is reached: a DOF
 that is new on a level lies in a bisected cell and is active there, and one that was there from the start is active on
 level 0.  On uniformly refined levels every row is active and the result is that of local=False bit for bit.
+
+Exact coarse-level solve (Hierarchy(ops, links, coarse=True); eqlb_hierarchy_set_coarse).  Level 0 is treated by its
+diagonal alone above.  With coarse=True it is solved on its free rows by a dense factor, formed once:
+
+  rows       the free rows of level 0 (~ops[0].fixed), ascending in the row index bs dof + r; their count is n
+  matrix     column j of A_0 is ops[0].apply(e_rows[j], masked=True) restricted to rows; only the lower triangle is read
+  factor     right-looking LDL^T without a square root; for k = 0 ... n - 1: d_k = a_kk; c_i = a_ik and l_i = c_i / d_k
+             for i > k; a_ij <- a_ij - l_i c_j for i >= j > k; W starts as the identity and w_ij <- w_ij - l_i w_kj
+             for i > k >= j.  Every product and every difference is rounded singly, so each entry sees k ascending.
+             The result: d [n] and the unit lower triangular W = L^-1 [n][n]
+  coarsest   z_0[rows] = W^T ((W r_0[rows]) / d), 0 on the fixed rows, in the place of z_0 = r_0 / diag_0:
+             y_i = sum_{k <= i} w_ik r_k with k ascending, y_i / d_i, z_j = sum_{i >= j} w_ij y_i with i ascending; every
+             sum starts from 0.0, products and sums are rounded singly
+  down, up, local   as above
+
+The preconditioner is the sum of P M_l P^T with M_0 = W^T D^-1 W, symmetric positive definite for any nonsingular W and
+positive d whatever the rounding did; a pivot that is not > 0 is refused.  One level with coarse=True is the direct
+solve as a preconditioner.  The factor is a snapshot of the mask and the coefficient of level 0 when it is first asked
+for (coarse_factor, precondition).
 """
 
 import numpy as np
@@ -51,10 +70,11 @@ from .primal import PoissonOperator, pcg_columns
 
 
 class Hierarchy:
-    """Hierarchy(ops, links, local=False): the statements on a hierarchy of levels, coarsest first.  local: smooth on
-    the levels l >= 1 only the rows whose basis function is new or changed there (the head of this file)."""
+    """Hierarchy(ops, links, local=False, coarse=False): the statements on a hierarchy of levels, coarsest first.
+    local: smooth on the levels l >= 1 only the rows whose basis function is new or changed there; coarse: solve level 0
+    exactly on its free rows by a dense LDL^T factor in the place of its diagonal (the head of this file)."""
 
-    def __init__(self, ops, links, local=False):
+    def __init__(self, ops, links, local=False, coarse=False):
         ops, links = list(ops), list(links)
         if len(ops) < 1 or len(links) != len(ops) - 1:
             raise ValueError("Hierarchy: one link per pair of neighbouring levels expected")
@@ -71,6 +91,12 @@ class Hierarchy:
         self._diag = [None] * len(ops)
         self.local = bool(local)
         self._active = [None] * len(ops)
+        self.coarse = bool(coarse)
+        self._factor = None
+        if self.coarse:
+            for c in range(self.bs):
+                if not ops[0].fixed[c::self.bs].any():
+                    raise ValueError(f"Hierarchy: coarse=True: component {c} of level 0 has no Dirichlet DOF")
 
     @property
     def nlevels(self):
@@ -100,6 +126,61 @@ class Hierarchy:
             self._active[level] = np.repeat(dofs, self.bs)
         return self._active[level]
 
+    def coarse_matrix(self):
+        """(rows int32 [n], A_0 [n][n]): the free rows of level 0 and the operator of level 0 on them, column by column
+        from apply (coarse=True or not)."""
+        op = self.ops[0]
+        rows = np.nonzero(~op.fixed)[0].astype(np.int32)
+        A = np.zeros((rows.size, rows.size))
+        e = np.zeros(op.fixed.size)
+        for j, row in enumerate(rows):
+            e[row] = 1.0
+            A[:, j] = op.apply(e, masked=True)[rows]
+            e[row] = 0.0
+        return rows, A
+
+    def coarse_factor(self):
+        """(rows int32 [n], d [n], W [n][n]): the factor of the exact solve on level 0 (coarse=True only); W is unit
+        lower triangular with zeros above the diagonal."""
+        if not self.coarse:
+            raise ValueError("Hierarchy.coarse_factor: level 0 is treated by its diagonal (coarse=False)")
+        if self._factor is None:
+            rows, A = self.coarse_matrix()
+            n = rows.size
+            A = np.tril(A)
+            W, d = np.eye(n), np.zeros(n)
+            for k in range(n):
+                d[k] = A[k, k]
+                if not d[k] > 0.0:
+                    raise ValueError(f"Hierarchy.coarse_factor: singular: pivot {k} (row {rows[k]} of level 0) is "
+                                     f"{d[k]}, not positive")
+                c = A[k + 1:, k].copy()
+                l = c / d[k]
+                # (in chunks of rows, each up to its last column of the lower triangle: what lies above the diagonal
+                # inside a chunk is computed too and never read)
+                for i0 in range(k + 1, n, 256):
+                    i1 = min(i0 + 256, n)
+                    A[i0:i1, k + 1:i1] = A[i0:i1, k + 1:i1] - l[i0 - k - 1:i1 - k - 1, None] * c[None, :i1 - k - 1]
+                W[k + 1:, :k + 1] = W[k + 1:, :k + 1] - l[:, None] * W[k, :k + 1][None, :]
+            self._factor = (rows, d, W)
+        return self._factor
+
+    def coarse_solve(self, r0):
+        """z_0 of the exact rule from r_0 [bs ndofs_0]."""
+        rows, d, W = self.coarse_factor()
+        n = rows.size
+        r = np.asarray(r0, dtype=np.float64)[rows]
+        y = np.zeros(n)
+        for k in range(n):
+            y[k:] = y[k:] + W[k:, k] * r[k]
+        y = y / d
+        z = np.zeros(n)
+        for i in range(n):
+            z[:i + 1] = z[:i + 1] + W[i, :i + 1] * y[i]
+        z0 = np.zeros(self.ops[0].fixed.size)
+        z0[rows] = z
+        return z0
+
     def restrict(self, level, r_fine, masked=True, return_abs=False):
         """level + 1 -> level."""
         if level < 0 or level >= self.nlevels - 1:
@@ -121,7 +202,10 @@ class Hierarchy:
         rs[L] = np.where(self.ops[L].fixed, 0.0, np.asarray(r, dtype=np.float64))
         for l in range(L - 1, -1, -1):
             rs[l] = self.restrict(l, rs[l + 1])
-        z = np.where(self.ops[0].fixed, 0.0, rs[0] / self.diag(0))
+        if self.coarse:
+            z = self.coarse_solve(rs[0])
+        else:
+            z = np.where(self.ops[0].fixed, 0.0, rs[0] / self.diag(0))
         for l in range(1, L + 1):
             t = self.prolong(l - 1, z)
             z = t + rs[l] / self.diag(l)

@@ -1041,7 +1041,7 @@ int eqlb_elasticity_solve(eqlb_elasticity_t* handle, const double* b, double* u,
  * plan whose counts do not fit its two meshes, a solver whose mesh is not that of its level, `level` outside
  * 0 ... nlevels - 2, an unknown memory space.  nlevels = 1 is plain Jacobi.
  * Not provided: the multiplicative cycle, transfers that skip the unchanged regions of locally refined levels (local
- * smoothing below leaves the cost of an application where it was), a solve on the coarsest level. */
+ * smoothing below leaves the cost of an application where it was).  The exact solve on level 0 is opt-in, below. */
 typedef struct eqlb_hierarchy eqlb_hierarchy_t;
 int eqlb_hierarchy_create(int32_t nlevels, int32_t bs, void* const* solvers, eqlb_refine_t* const* plans,
                           eqlb_mesh_t* const* meshes, void* stream, eqlb_hierarchy_t** out);
@@ -1075,6 +1075,43 @@ int eqlb_hierarchy_set_local(eqlb_hierarchy_t* handle, int32_t local, void* stre
 int eqlb_hierarchy_active(eqlb_hierarchy_t* handle, int32_t level, uint8_t* out, int64_t capacity, int32_t memspace,
                           void* stream);
 int eqlb_hierarchy_active_count(eqlb_hierarchy_t* handle, int32_t level, int64_t* count);
+/* Exact solve on level 0.  The sum above treats level 0 by its diagonal alone; from a coarsest mesh of a thousand cells
+ * that costs iterations, and local smoothing then loses to the full sum.  With the switch on, level 0 is solved on its
+ * free rows by a dense factor (dolfinx_eqlb_amd/lsolver/multilevel.py: Hierarchy(..., coarse=True) states it; factor and
+ * application are reproduced bit for bit):
+ *   rows      the free rows of level 0, ascending in the row index bs dof + r; n of them
+ *   matrix    column j of A_0 is eqlb_*_apply (masked) of the unit vector of rows[j], restricted to rows; only the
+ *             lower triangle is read
+ *   factor    right-looking LDL^T without a square root: for k = 0 ... n - 1: d_k = a_kk; c_i = a_ik, l_i = c_i / d_k for
+ *             i > k; a_ij -= l_i c_j for i >= j > k; W starts as the identity, w_ij -= l_i w_kj for i > k >= j; every
+ *             product and difference rounded singly.  d [n] and the unit lower triangular W = L^-1 [n][n]
+ *   coarsest  z_0[rows] = W^T ((W r_0[rows]) / d), 0 on the fixed rows, in the place of z_0 = r_0 / diag_0:
+ *             y_i = sum_{k <= i} w_ik r_k (k ascending), y_i / d_i, z_j = sum_{i >= j} w_ij y_i (i ascending); the sums
+ *             start from 0.0, products and sums rounded singly.  Down, up and the local rule are unchanged
+ * The preconditioner stays symmetric positive definite on the free rows (M_0 = W^T D^-1 W with positive d, whatever the
+ * rounding did); one level with the switch on is the direct solve as a preconditioner.  eqlb_hierarchy_precondition,
+ * _precondition_many, _solve and _solve_many honour the switch: the combine of level 0 is replaced by two launches
+ * (3 + 4 L per application); their checks, texts and info do not change, and a handle whose switch is off (as created)
+ * launches what it launched and gives the bits it gave before the switch existed.
+ *   set_coarse    coarse = 1 takes the free rows from the mask of level 0, builds A_0 with the product launches of the
+ *                 level-0 handle, factors it on `stream` (a blocked kernel sequence on the vector ALU, about n^3 / 3
+ *                 multiply-subtract pairs) and waits for the device.  EVERY such call factors again: the factor is a
+ *                 snapshot of the mask and the coefficient of level 0, and eqlb_*_set_dirichlet or a new coefficient
+ *                 on level 0 needs another call.  The memory (two layouts of n^2 doubles) is allocated by the first
+ *                 call, grown by one with more rows, kept by coarse = 0 and freed by eqlb_hierarchy_destroy.  n = 0
+ *                 factors nothing and z_0 = 0.  Refusals, after which the switch is off:
+ *                   EQLB_ERR_INVALID_ARGUMENT  a component of level 0 without a Dirichlet DOF; a value other than 0, 1
+ *                   EQLB_ERR_UNSUPPORTED       n above 4096 (the text gives both numbers), before anything is allocated
+ *                   EQLB_ERR_SINGULAR          a pivot that is not > 0, or NaN; the text names the row
+ *   coarse_rows   n
+ *   coarse_factor rows int32 [n], d [n] and W row-major [n][n] packed, ones on the diagonal and zeros above it, in
+ *                 `memspace`; capacity >= n is the number of rows the three arrays hold
+ * coarse_rows and coarse_factor with the switch off: EQLB_ERR_INVALID_ARGUMENT, the text names
+ * eqlb_hierarchy_set_coarse. */
+int eqlb_hierarchy_set_coarse(eqlb_hierarchy_t* handle, int32_t coarse, void* stream);
+int eqlb_hierarchy_coarse_rows(eqlb_hierarchy_t* handle, int64_t* n);
+int eqlb_hierarchy_coarse_factor(eqlb_hierarchy_t* handle, int32_t* rows, double* d, double* W, int64_t capacity,
+                                 int32_t memspace, void* stream);
 /* Several right-hand sides on a hierarchy of Poisson handles, by the rule of eqlb_primal_solve_many: column c of
  * eqlb_hierarchy_precondition_many is eqlb_hierarchy_precondition of r_c, column c of eqlb_hierarchy_solve_many is
  * eqlb_hierarchy_solve of (b_c, u_c) - the same bits, the same info [nrhs][8].  Vectors [nrhs][ndofs_L], groups of at
