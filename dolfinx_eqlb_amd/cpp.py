@@ -1383,12 +1383,109 @@ def _columns(a, n):
     return v
 
 
-class PrimalPoisson:
+class _PrimalSolver:
+    """What PrimalPoisson and PrimalElasticity share: the entries of the C ABI that differ by the symbol prefix and by
+    the vector length _bs * ndofs only.  A subclass creates the handle `_h` and sets `dmesh`, `p`, `ndofs`."""
+
+    _prefix = None   # "eqlb_primal_" / "eqlb_elasticity_"
+    _bs = None       # components per DOF
+
+    def _fn(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    def _read_ndofs(self):
+        n = C.c_int64(0)
+        _check(self._fn("ndofs")(self._h, C.byref(n)))
+        self.ndofs = int(n.value)
+
+    def _vec(self, a):
+        v = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if v.size != self._bs * self.ndofs:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        return v
+
+    def load(self, degree_dg, rhs_dg, b_extra=None, stream=0):
+        """b [bs ndofs] from the DG_d nodal values rhs_dg [bs][ncells * nd_d] of the bs components (1: Poisson,
+        2: elasticity), + b_extra [bs ndofs] where given (elasticity: lsolver.traction_load)."""
+        d = max(int(degree_dg), 0)
+        f = np.ascontiguousarray(rhs_dg, dtype=np.float64).ravel()
+        if 0 <= degree_dg <= 3 and f.size != self._bs * self.dmesh.counts()[1] * (d + 1) * (d + 2) // 2:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        e = None if b_extra is None else self._vec(b_extra)
+        b = np.zeros(self._bs * self.ndofs)
+        self.load_raw(degree_dg, f.ctypes.data, None if e is None else e.ctypes.data, b.ctypes.data, MEM_HOST, stream)
+        return b
+
+    def load_raw(self, degree_dg, rhs_dg, b_extra, b, memspace=MEM_DEVICE, stream=0):
+        _check(self._fn("load")(self._h, C.c_int32(degree_dg), _vp(rhs_dg), _vp(b_extra), _vp(b),
+                                C.c_int32(memspace), C.c_void_p(stream)))
+
+    def apply(self, u, masked=False, stream=0):
+        """y = A u; masked: 0 on the fixed rows."""
+        uu, y = self._vec(u), np.zeros(self._bs * self.ndofs)
+        self.apply_raw(uu.ctypes.data, y.ctypes.data, masked, MEM_HOST, stream)
+        return y
+
+    def apply_raw(self, u, y, masked=False, memspace=MEM_DEVICE, stream=0):
+        _check(self._fn("apply")(self._h, _vp(u), _vp(y), C.c_int32(1 if masked else 0), C.c_int32(memspace),
+                                 C.c_void_p(stream)))
+
+    def diagonal(self, stream=0):
+        out = np.zeros(self._bs * self.ndofs)
+        self.diagonal_raw(out.ctypes.data, MEM_HOST, stream)
+        return out
+
+    def diagonal_raw(self, out, memspace=MEM_DEVICE, stream=0):
+        _check(self._fn("diagonal")(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def residual(self, b, u, norms=False, stream=0):
+        """r = b - A u with 0 on the fixed rows; norms=True: (r, || r ||_2, nb)."""
+        bb, uu, r = self._vec(b), self._vec(u), np.zeros(self._bs * self.ndofs)
+        nv = np.zeros(2)
+        self.residual_raw(bb.ctypes.data, uu.ctypes.data, r.ctypes.data, nv.ctypes.data if norms else None, MEM_HOST,
+                          stream)
+        return (r, float(nv[0]), float(nv[1])) if norms else r
+
+    def residual_raw(self, b, u, r, norms=None, memspace=MEM_DEVICE, stream=0):
+        _check(self._fn("residual")(self._h, _vp(b), _vp(u), _vp(r), _vp(norms), C.c_int32(memspace),
+                                    C.c_void_p(stream)))
+
+    def solve(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
+        """Jacobi-preconditioned CG from the start u (its fixed rows hold the Dirichlet values).  Returns (u, info):
+        the solution and a dict with the keys of PRIMAL_INFO.  Not converged is a result, not an error."""
+        bb = self._vec(b)
+        uu = self._vec(u).copy()
+        info = self.solve_raw(bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
+        return uu, info
+
+    def solve_raw(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
+        """eqlb_primal_solve / eqlb_elasticity_solve on raw pointers: u is overwritten by the solution; waits for the
+        device; returns info."""
+        v = (C.c_double * 8)()
+        _check(self._fn("solve")(self._h, _vp(b), _vp(u), C.c_double(rtol), C.c_double(atol), C.c_int32(maxit), v,
+                                 C.c_int32(memspace), C.c_void_p(stream)))
+        return _primal_info(v)
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PrimalPoisson(_PrimalSolver):
     """eqlb_primal_t: -div(coeff grad u) = f on the conforming P_p space of the handle (1 <= p <= 4), in the numbering
     of DeviceMesh.lagrange_dofmap: the operator matrix-free, the load vector, the residual and a Jacobi-preconditioned
     CG on the device (lsolver.primal.PoissonOperator is the numpy statement).  coeff: host array [ncells] or None (1).
     The methods take and return host arrays; the `_raw` variants take raw pointers (ints) in `memspace`, ordered on
     `stream`.  The entries of one handle share its work space: one stream, one call after the other."""
+
+    _prefix, _bs = "eqlb_primal_", 1
 
     def __init__(self, dmesh: DeviceMesh, p: int, coeff=None, stream=0):
         self.dmesh = dmesh   # the handle reads the mesh: keep it alive
@@ -1401,9 +1498,7 @@ class PrimalPoisson:
                 raise RuntimeError("Local solver: Input sizes does not match")
         _check(lib().eqlb_primal_create(dmesh._h, C.c_int32(p), _hp(kc) if kc is not None else None,
                                         C.c_int32(MEM_HOST), C.c_void_p(stream), C.byref(self._h)))
-        n = C.c_int64(0)
-        _check(lib().eqlb_primal_ndofs(self._h, C.byref(n)))
-        self.ndofs = int(n.value)
+        self._read_ndofs()
 
     @classmethod
     def create_raw(cls, dmesh: DeviceMesh, p: int, coeff=None, memspace=MEM_DEVICE, stream=0):
@@ -1412,16 +1507,8 @@ class PrimalPoisson:
         self.dmesh, self.p, self._h = dmesh, int(p), C.c_void_p()
         _check(lib().eqlb_primal_create(dmesh._h, C.c_int32(p), _vp(coeff), C.c_int32(memspace), C.c_void_p(stream),
                                         C.byref(self._h)))
-        n = C.c_int64(0)
-        _check(lib().eqlb_primal_ndofs(self._h, C.byref(n)))
-        self.ndofs = int(n.value)
+        self._read_ndofs()
         return self
-
-    def _vec(self, a):
-        v = np.ascontiguousarray(a, dtype=np.float64).ravel()
-        if v.size != self.ndofs:
-            raise RuntimeError("Local solver: Input sizes does not match")
-        return v
 
     def set_dirichlet(self, facets, stream=0):
         """Fixed are the vertex and facet DOFs of the listed facets; a repeated call replaces the mask."""
@@ -1431,69 +1518,6 @@ class PrimalPoisson:
     def set_dirichlet_raw(self, nlist, facets, memspace=MEM_DEVICE, stream=0):
         _check(lib().eqlb_primal_set_dirichlet(self._h, C.c_int32(nlist), _vp(facets), C.c_int32(memspace),
                                                C.c_void_p(stream)))
-
-    def load(self, degree_dg, rhs_dg, b_extra=None, stream=0):
-        """b [ndofs] from the DG_d nodal values rhs_dg [ncells * nd_d], + b_extra [ndofs] where given."""
-        d = max(int(degree_dg), 0)
-        f = np.ascontiguousarray(rhs_dg, dtype=np.float64).ravel()
-        if 0 <= degree_dg <= 3 and f.size != self.dmesh.counts()[1] * (d + 1) * (d + 2) // 2:
-            raise RuntimeError("Local solver: Input sizes does not match")
-        e = None if b_extra is None else self._vec(b_extra)
-        b = np.zeros(self.ndofs)
-        self.load_raw(degree_dg, f.ctypes.data, None if e is None else e.ctypes.data, b.ctypes.data, MEM_HOST, stream)
-        return b
-
-    def load_raw(self, degree_dg, rhs_dg, b_extra, b, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_primal_load(self._h, C.c_int32(degree_dg), _vp(rhs_dg), _vp(b_extra), _vp(b),
-                                      C.c_int32(memspace), C.c_void_p(stream)))
-
-    def apply(self, u, masked=False, stream=0):
-        """y = A u; masked: 0 on the fixed rows."""
-        uu, y = self._vec(u), np.zeros(self.ndofs)
-        self.apply_raw(uu.ctypes.data, y.ctypes.data, masked, MEM_HOST, stream)
-        return y
-
-    def apply_raw(self, u, y, masked=False, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_primal_apply(self._h, _vp(u), _vp(y), C.c_int32(1 if masked else 0), C.c_int32(memspace),
-                                       C.c_void_p(stream)))
-
-    def diagonal(self, stream=0):
-        out = np.zeros(self.ndofs)
-        self.diagonal_raw(out.ctypes.data, MEM_HOST, stream)
-        return out
-
-    def diagonal_raw(self, out, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_primal_diagonal(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
-
-    def residual(self, b, u, norms=False, stream=0):
-        """r = b - A u with 0 on the fixed rows; norms=True: (r, || r ||_2, nb)."""
-        bb, uu, r = self._vec(b), self._vec(u), np.zeros(self.ndofs)
-        nv = np.zeros(2)
-        self.residual_raw(bb.ctypes.data, uu.ctypes.data, r.ctypes.data, nv.ctypes.data if norms else None, MEM_HOST,
-                          stream)
-        return (r, float(nv[0]), float(nv[1])) if norms else r
-
-    def residual_raw(self, b, u, r, norms=None, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_primal_residual(self._h, _vp(b), _vp(u), _vp(r), _vp(norms), C.c_int32(memspace),
-                                          C.c_void_p(stream)))
-
-    def solve(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
-        """Jacobi-preconditioned CG from the start u (its fixed rows hold the Dirichlet values).  Returns (u, info):
-        the solution and a dict with the keys of PRIMAL_INFO.  Not converged is a result, not an error."""
-        bb = self._vec(b)
-        uu = self._vec(u).copy()
-        info = self.solve_raw(bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
-        return uu, info
-
-    def solve_raw(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
-        """eqlb_primal_solve on raw pointers: u is overwritten by the solution; waits for the device; returns info."""
-        v = (C.c_double * 8)()
-        _check(lib().eqlb_primal_solve(self._h, _vp(b), _vp(u), C.c_double(rtol), C.c_double(atol), C.c_int32(maxit),
-                                       v, C.c_int32(memspace), C.c_void_p(stream)))
-        info = dict(zip(PRIMAL_INFO, [float(x) for x in v]))
-        for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
-            info[key] = int(info[key])
-        return info
 
     def apply_many(self, U, masked=False, stream=0):
         """Y [nrhs][ndofs]: row c is apply(U[c]), bit for bit, in one call."""
@@ -1525,25 +1549,16 @@ class PrimalPoisson:
                                             C.c_void_p(stream)))
         return [_primal_info(v[8 * c:8 * c + 8]) for c in range(int(nrhs))]
 
-    def close(self):
-        if self._h:
-            lib().eqlb_primal_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PrimalElasticity:
+class PrimalElasticity(_PrimalSolver):
     """eqlb_elasticity_t: -div(2 eps(u) + pi_1 div(u) I) = f on [P_p]^2 (1 <= p <= 4) with the pi_1 / cell_pi1 convention
     of primal_stress_dg, in the scalar numbering of DeviceMesh.lagrange_dofmap, blocked: x[2 dof + r].  `ndofs` is the
     scalar count; every vector has 2 ndofs rows.  The operator matrix-free, the load vector, the residual and a
     Jacobi-preconditioned CG on the device (lsolver.primal.ElasticityOperator is the numpy statement).  cell_pi1: host
     array [ncells] or None (the scalar everywhere).  Shaped as PrimalPoisson: the methods take and return host arrays;
     the `_raw` variants take raw pointers (ints) in `memspace`, ordered on `stream`."""
+
+    _prefix, _bs = "eqlb_elasticity_", 2
 
     def __init__(self, dmesh: DeviceMesh, p: int, pi_1: float = 1.0, cell_pi1=None, stream=0):
         self.dmesh = dmesh   # the handle reads the mesh: keep it alive
@@ -1569,17 +1584,6 @@ class PrimalElasticity:
         self._read_ndofs()
         return self
 
-    def _read_ndofs(self):
-        n = C.c_int64(0)
-        _check(lib().eqlb_elasticity_ndofs(self._h, C.byref(n)))
-        self.ndofs = int(n.value)
-
-    def _vec(self, a):
-        v = np.ascontiguousarray(a, dtype=np.float64).ravel()
-        if v.size != 2 * self.ndofs:
-            raise RuntimeError("Local solver: Input sizes does not match")
-        return v
-
     def set_dirichlet(self, facets0, facets1, stream=0):
         """Fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r (the facets
         with type 1 in row r of a stress handle); a repeated call replaces the mask."""
@@ -1592,81 +1596,6 @@ class PrimalElasticity:
         _check(lib().eqlb_elasticity_set_dirichlet(self._h, C.c_int32(nlist0), _vp(facets0), C.c_int32(nlist1),
                                                    _vp(facets1), C.c_int32(memspace), C.c_void_p(stream)))
 
-    def load(self, degree_dg, rhs_dg, b_extra=None, stream=0):
-        """b [2 ndofs] from the DG_d nodal values rhs_dg [2][ncells * nd_d] of the two components, + b_extra [2 ndofs]
-        where given (lsolver.traction_load)."""
-        d = max(int(degree_dg), 0)
-        f = np.ascontiguousarray(rhs_dg, dtype=np.float64).ravel()
-        if 0 <= degree_dg <= 3 and f.size != 2 * self.dmesh.counts()[1] * (d + 1) * (d + 2) // 2:
-            raise RuntimeError("Local solver: Input sizes does not match")
-        e = None if b_extra is None else self._vec(b_extra)
-        b = np.zeros(2 * self.ndofs)
-        self.load_raw(degree_dg, f.ctypes.data, None if e is None else e.ctypes.data, b.ctypes.data, MEM_HOST, stream)
-        return b
-
-    def load_raw(self, degree_dg, rhs_dg, b_extra, b, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_elasticity_load(self._h, C.c_int32(degree_dg), _vp(rhs_dg), _vp(b_extra), _vp(b),
-                                          C.c_int32(memspace), C.c_void_p(stream)))
-
-    def apply(self, u, masked=False, stream=0):
-        """y = A u; masked: 0 on the fixed rows."""
-        uu, y = self._vec(u), np.zeros(2 * self.ndofs)
-        self.apply_raw(uu.ctypes.data, y.ctypes.data, masked, MEM_HOST, stream)
-        return y
-
-    def apply_raw(self, u, y, masked=False, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_elasticity_apply(self._h, _vp(u), _vp(y), C.c_int32(1 if masked else 0),
-                                           C.c_int32(memspace), C.c_void_p(stream)))
-
-    def diagonal(self, stream=0):
-        out = np.zeros(2 * self.ndofs)
-        self.diagonal_raw(out.ctypes.data, MEM_HOST, stream)
-        return out
-
-    def diagonal_raw(self, out, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_elasticity_diagonal(self._h, _vp(out), C.c_int32(memspace), C.c_void_p(stream)))
-
-    def residual(self, b, u, norms=False, stream=0):
-        """r = b - A u with 0 on the fixed rows; norms=True: (r, || r ||_2, nb)."""
-        bb, uu, r = self._vec(b), self._vec(u), np.zeros(2 * self.ndofs)
-        nv = np.zeros(2)
-        self.residual_raw(bb.ctypes.data, uu.ctypes.data, r.ctypes.data, nv.ctypes.data if norms else None, MEM_HOST,
-                          stream)
-        return (r, float(nv[0]), float(nv[1])) if norms else r
-
-    def residual_raw(self, b, u, r, norms=None, memspace=MEM_DEVICE, stream=0):
-        _check(lib().eqlb_elasticity_residual(self._h, _vp(b), _vp(u), _vp(r), _vp(norms), C.c_int32(memspace),
-                                              C.c_void_p(stream)))
-
-    def solve(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, stream=0):
-        """Jacobi-preconditioned CG from the start u (its fixed rows hold the Dirichlet values).  Returns (u, info):
-        the solution and a dict with the keys of PRIMAL_INFO.  Not converged is a result, not an error."""
-        bb = self._vec(b)
-        uu = self._vec(u).copy()
-        info = self.solve_raw(bb.ctypes.data, uu.ctypes.data, rtol, atol, maxit, MEM_HOST, stream)
-        return uu, info
-
-    def solve_raw(self, b, u, rtol=1e-8, atol=0.0, maxit=10000, memspace=MEM_DEVICE, stream=0):
-        """eqlb_elasticity_solve on raw pointers: u is overwritten by the solution; waits for the device; returns
-        info."""
-        v = (C.c_double * 8)()
-        _check(lib().eqlb_elasticity_solve(self._h, _vp(b), _vp(u), C.c_double(rtol), C.c_double(atol),
-                                           C.c_int32(maxit), v, C.c_int32(memspace), C.c_void_p(stream)))
-        info = dict(zip(PRIMAL_INFO, [float(x) for x in v]))
-        for key in ("iterations", "converged", "replacements", "breakdown", "facets_skipped"):
-            info[key] = int(info[key])
-        return info
-
-    def close(self):
-        if self._h:
-            lib().eqlb_elasticity_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Multilevel:

@@ -130,7 +130,7 @@ k_ml_combine_local(int64_t n, const ManyCols cols, const double* __restrict__ t,
 
 // The mask of one level l >= 1: one thread per cell of the level below, which walks its children - the fine cells, in
 // the order k_restrict walks them.  The children of a bisected cell (more than one child) write 1 to the bs rows of
-// every DOF of their row of the dofmap: the same byte from several threads, plain stores, no atomics (k_elast_mask
+// every DOF of their row of the dofmap: the same byte from several threads, plain stores, no atomics (k_primal_mask
 // does the same).  The mask is cleared before the launch; an index outside the level addresses nothing.
 __global__ void __launch_bounds__(PS_THREADS)
 k_ml_active(int32_t ncells, int64_t ncells2, const uint32_t* __restrict__ coff, int nd, int bs,

@@ -14,12 +14,15 @@
 // R <= MANY_R columns per group, a larger count runs group after group.  The column slots of a kernel are its template
 // parameter NC (arrays [NC], shared [NC or 2 NC][PS_THREADS]): NC = 1 serves one column, NC = MANY_R two to four.
 //  k_primal_slots    builds the slot lists of the sum pass once at create (scalar numbering: both problems use it)
+//  k_primal_mask<BS> the Dirichlet mask of one component from a list of facets
 //  k_primal_gather<BS, NC>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
 //                    x[BS * dof + r]; columns for BS = 1 only
 //  k_pcg_*<NC>       work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
 //  k_pcg_scalar      the scalar steps; `ml`: the breakdown rule of a preconditioner that is no positive diagonal
 //  pcg_solve         the host side of the iteration on a PcgWork; the preconditioner enters through its `steps`
 //                    (JacobiSteps here; the hierarchy unit eqlb_multilevel.hip brings its own)
+// The host side of the two solver handles on these kernels (the handle base, its launches, the bodies of the C entries)
+// lies in eqlb_primal_handle.h.
 #pragma once
 
 #include "eqlb_device_common.h"
@@ -104,6 +107,29 @@ k_primal_slots(const SpaceArgs s, const int32_t* __restrict__ node_cells, const 
     }
     slots[beg + k] = (int32_t)(c * s.nd + loc);
   }
+}
+
+// the mask of component r: the rows BS dof + r of the vertex and facet DOFs of the listed facets; ids outside the mesh are
+// skipped and counted (status[0]), valid ones counted per component (status[1 + r])
+template <int BS>
+__global__ void __launch_bounds__(PS_THREADS)
+k_primal_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t r, int32_t nnodes, int32_t nfacets, int32_t ne,
+              const int32_t* __restrict__ facet_nodes, uint8_t* __restrict__ fixed, int32_t* __restrict__ status)
+{
+  const int32_t i = blockIdx.x * PS_THREADS + threadIdx.x;
+  if (i >= nlist)
+    return;
+  const int32_t f = facets[i];
+  if (f < 0 || f >= nfacets)
+  {
+    atomicAdd(status, 1);
+    return;
+  }
+  atomicAdd(status + 1 + r, 1);
+  fixed[BS * (int64_t)facet_nodes[2 * (int64_t)f] + r] = 1;
+  fixed[BS * (int64_t)facet_nodes[2 * (int64_t)f + 1] + r] = 1;
+  for (int j = 0; j < ne; ++j)
+    fixed[BS * ((int64_t)nnodes + (int64_t)f * ne + j) + r] = 1;
 }
 
 enum GatherDot

@@ -22,13 +22,19 @@
 //    so do the output rows y_loc [ncells][nd_p][2].
 //  k_primal_gather<2, 1>, k_pcg_*<1>, pcg_solve: eqlb_primal_common.h, on one column of n = 2 ndofs rows with the
 //    mask per row.
+// This unit holds the cell kernel, its dispatch on p and d, the table getter and the C entries; the handle, the
+// launches on it and the bodies of the C entries are those of eqlb_primal_handle.h at bs = 2 and one column.
 #include "eqlb_device_common.h"
-#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
-#include "eqlb_primal_common.h"
+#include "eqlb_primal_handle.h" // the host side of a solver handle; eqlb_primal_common.h: the kernels it launches
 #include "eqlb_tables_gen.h"
 
-#include <climits>
 #include <cmath>
+
+// the handle behind eqlb_elasticity_t; the per-cell coefficient of the base is cell_pi1
+struct eqlb_elasticity : eqlb::SolverHandle<2, 1>
+{
+  double pi_1 = 1.0;
+};
 
 namespace eqlb
 {
@@ -198,28 +204,6 @@ __global__ void __launch_bounds__(ES_THREADS) k_elast_cell(const ElastCellArgs a
     o[e] = sbuf[(e / W) * S + (e % W)];
 }
 
-// the mask of component r: the rows 2 dof + r of the vertex and facet DOFs of the listed facets; ids outside the mesh are
-// skipped and counted (status[0]), valid ones counted per component (status[1 + r])
-__global__ void __launch_bounds__(PS_THREADS)
-k_elast_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t r, int32_t nnodes, int32_t nfacets, int32_t ne,
-             const int32_t* __restrict__ facet_nodes, uint8_t* __restrict__ fixed, int32_t* __restrict__ status)
-{
-  const int32_t i = blockIdx.x * PS_THREADS + threadIdx.x;
-  if (i >= nlist)
-    return;
-  const int32_t f = facets[i];
-  if (f < 0 || f >= nfacets)
-  {
-    atomicAdd(status, 1);
-    return;
-  }
-  atomicAdd(status + 1 + r, 1);
-  fixed[2 * (int64_t)facet_nodes[2 * (int64_t)f] + r] = 1;
-  fixed[2 * (int64_t)facet_nodes[2 * (int64_t)f + 1] + r] = 1;
-  for (int j = 0; j < ne; ++j)
-    fixed[2 * ((int64_t)nnodes + (int64_t)f * ne + j) + r] = 1;
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------
 template <int P, int MODE>
 hipError_t launch_cell_d(int d, const ElastCellArgs& a, hipStream_t stream)
@@ -260,157 +244,29 @@ hipError_t launch_cell(int p, int d, const ElastCellArgs& a, hipStream_t stream)
     return launch_cell_d<4, MODE>(d, a, stream);
   }
 }
-} // namespace
-} // namespace eqlb
 
-// the handle behind eqlb_elasticity_t: everything is carved out of one allocation at create
-struct eqlb_elasticity
-{
-  eqlb_mesh* mesh = nullptr;
-  int p = 0, nd = 0;
-  int64_t ndofs = 0; // scalar; the vectors have 2 ndofs rows
-  bool has_pi1 = false;
-  double pi_1 = 1.0;
-  eqlb::SpaceArgs space{};
-  eqlb::DevCarve mem;
-  // status: skipped facet ids, listed valid ones of component 0, of component 1, unmatched slots
-  eqlb::DevPiece<int32_t> cell_dofs, slots, status;
-  eqlb::DevPiece<double> cell_pi1, yloc, diag, r, z, d, q, part;
-  eqlb::DevPiece<uint8_t> fixed;
-  eqlb::DevPiece<eqlb::PcgState> st;
-};
-
-namespace eqlb
-{
-namespace
-{
-const ManyCols ONE_COLUMN{1, 1u, 0, nullptr}; // a launch that knows no state (the handle has one column)
-
-ElastCellArgs cell_args(const eqlb_elasticity& h, const ManyCols& c, const double* u, bool only_fixed)
+// the hook of eqlb_primal_handle.h, the store pass on the one column of c: u [2 ndofs] (load: rhs_dg) into the y_loc of
+// the handle
+template <int MODE>
+hipError_t launch_cell(const eqlb_elasticity& h, const ManyCols& c, int d, const double* u, bool only_fixed,
+                       hipStream_t stream)
 {
   ElastCellArgs a{};
   a.ncells = h.space.ncells;
   a.cell_dofs = h.cell_dofs;
   a.cellJ = h.mesh->m.cellJ;
-  a.cell_pi1 = h.has_pi1 ? h.cell_pi1.get() : nullptr;
+  a.cell_pi1 = h.has_coeff ? h.coeff.get() : nullptr;
   a.pi_1 = h.pi_1;
   a.u = u;
   a.fixed = h.fixed;
   a.only_fixed = only_fixed ? 1 : 0;
   a.yloc = h.yloc;
   a.st = c.check ? c.st : nullptr;
-  return a;
-}
-
-GatherArgs gather_args(const eqlb_elasticity& h, const ManyCols& c, bool masked)
-{
-  GatherArgs g{};
-  g.s = h.space;
-  g.yloc = h.yloc;
-  g.fixed = masked ? h.fixed.get() : nullptr;
-  g.part = h.part;
-  g.cols = c;
-  return g;
-}
-
-hipError_t launch_gather(const eqlb_elasticity& h, const GatherArgs& g, hipStream_t stream)
-{
-  hipLaunchKernelGGL((k_primal_gather<2, 1>), dim3(stream_blocks(2 * h.ndofs)), dim3(PS_THREADS), 0, stream, g);
-  return hipGetLastError();
-}
-
-PcgWork pcg_work(const eqlb_elasticity& h)
-{
-  return PcgWork{2 * h.ndofs, 1, h.diag, h.fixed, h.yloc, h.r, h.z, h.d, h.q, h.part, h.st};
-}
-
-// y = owner sum of y_loc (masked or raw); y DEVICE
-hipError_t enqueue_owner_sum(const eqlb_elasticity& h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
-{
-  GatherArgs g = gather_args(h, c, masked);
-  g.y = y;
-  return launch_gather(h, g, stream);
-}
-
-// y = A u (masked or raw); all pointers DEVICE
-hipError_t enqueue_apply(const eqlb_elasticity& h, const double* u, double* y, bool masked, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, ONE_COLUMN, u, false), stream);
-  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, y, masked, stream);
-}
-
-hipError_t enqueue_diagonal(const eqlb_elasticity& h, double* out, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_DIAGONAL>(h.p, 0, cell_args(h, ONE_COLUMN, nullptr, false), stream);
-  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, out, false, stream);
-}
-
-// r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in h.part
-hipError_t enqueue_residual(const eqlb_elasticity& h, const ManyCols& c, const double* b, const double* u, double* r,
-                            bool only_fixed, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, c, u, only_fixed), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, c, true);
-  g.b = b;
-  g.r = r;
-  g.dot = DOT_R_R;
-  return launch_gather(h, g, stream);
-}
-
-// q = A d on the free rows (the direction d of the handle), the block partials of d.q in h.part
-hipError_t enqueue_product(const eqlb_elasticity& h, const ManyCols& c, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h.p, 0, cell_args(h, c, h.d, false), stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, c, true);
-  g.y = h.q;
-  g.w = h.d;
-  g.dot = DOT_W_Y;
-  return launch_gather(h, g, stream);
-}
-
-int check_handle(const char* who, const eqlb_elasticity* h)
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
-  return EQLB_OK;
+  return launch_cell<MODE>(h.p, d, a, stream);
 }
 } // namespace
 
-// the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
-void elasticity_level(eqlb_elasticity* h, SolverLevel& v)
-{
-  v = SolverLevel{};
-  v.handle = h;
-  v.mesh = h->mesh;
-  v.p = h->p;
-  v.bs = 2;
-  v.ndofs = h->ndofs;
-  v.cell_dofs = h->cell_dofs;
-  v.diag = h->diag;
-  v.fixed = h->fixed;
-  v.status = h->status;
-  v.work = [](void* hh, int R, PcgWork& w) {
-    if (R != 1)
-      return fail(EQLB_ERR_UNSUPPORTED,
-                  "elasticity_level: several right-hand sides are provided for Poisson handles (bs = 1) only");
-    w = pcg_work(*static_cast<eqlb_elasticity*>(hh));
-    return (int)EQLB_OK;
-  };
-  v.owner_sum = [](void* hh, const ManyCols& c, double* y, bool masked, hipStream_t stream) {
-    return enqueue_owner_sum(*static_cast<eqlb_elasticity*>(hh), c, y, masked, stream);
-  };
-  v.residual = [](void* hh, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
-                  hipStream_t stream) {
-    return enqueue_residual(*static_cast<eqlb_elasticity*>(hh), c, b, u, r, only_fixed, stream);
-  };
-  v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
-    return enqueue_product(*static_cast<eqlb_elasticity*>(hh), c, stream);
-  };
-}
+void elasticity_level(eqlb_elasticity* h, SolverLevel& v) { solver_level(h, v); }
 } // namespace eqlb
 
 extern "C" {
@@ -435,74 +291,9 @@ int eqlb_elasticity_create(eqlb_mesh_t* mesh, int32_t p, double pi_1, const doub
                            void* stream_, eqlb_elasticity_t** handle)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_create";
-  if (p < 1 || p > PS_PMAX)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4", who, (int)p);
-  if (!mesh || !handle)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  const DeviceMesh& m = mesh->m;
-  const int ne = p - 1, ni = (p - 1) * (p - 2) / 2, nd = nd_of(p);
-  const int64_t ndofs = (int64_t)m.nnodes + (int64_t)m.nfacets * ne + (int64_t)m.ncells * ni;
-  if (ndofs > INT32_MAX || (int64_t)m.ncells * nd > INT32_MAX || m.ncells < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %lld DOFs, %lld cell entries do not fit 32 bits", who, (long long)ndofs,
-                (long long)m.ncells * nd);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  // a handle of eqlb_mesh_create keeps node -> cell on the host until somebody needs it on the device
-  const int32_t* node_cells = nullptr;
-  if (mesh_node_cells(mesh, &node_cells))
-    return EQLB_ERR_DEVICE;
-  std::unique_ptr<eqlb_elasticity> h(new eqlb_elasticity);
-  h->mesh = mesh;
-  h->p = p;
-  h->nd = nd;
-  h->ndofs = ndofs;
-  h->has_pi1 = cell_pi1 != nullptr;
+  auto h = std::make_unique<eqlb_elasticity>();
   h->pi_1 = pi_1;
-  const size_t nc = (size_t)m.ncells, nslots = 3 * nc * (size_t)(1 + ne), nv = 2 * (size_t)ndofs;
-  h->cell_dofs = h->mem.piece<int32_t>(nc * nd);
-  h->slots = h->mem.piece<int32_t>(nslots);
-  h->status = h->mem.piece<int32_t>(4);
-  h->cell_pi1 = h->mem.piece<double>(nc);
-  h->yloc = h->mem.piece<double>(2 * nc * nd);
-  h->diag = h->mem.piece<double>(nv);
-  h->r = h->mem.piece<double>(nv);
-  h->z = h->mem.piece<double>(nv);
-  h->d = h->mem.piece<double>(nv);
-  h->q = h->mem.piece<double>(nv);
-  h->part = h->mem.piece<double>(2 * (size_t)PS_MAXBLOCKS);
-  h->fixed = h->mem.piece<uint8_t>(nv);
-  h->st = h->mem.piece<PcgState>(1);
-  HIP_TRY(h->mem.alloc());
-  SpaceArgs& s = h->space;
-  s.ndofs = ndofs;
-  s.nnodes = m.nnodes;
-  s.nfacets = m.nfacets;
-  s.ncells = m.ncells;
-  s.ne = ne;
-  s.ni = ni > 0 ? ni : 1;
-  s.nd = nd;
-  s.nco = m.node_cells_off;
-  s.fco = m.facet_cells_off;
-  s.slots = h->slots;
-  HIP_TRY(hipMemsetAsync(h->status, 0, 4 * sizeof(int32_t), stream));
-  HIP_TRY(hipMemsetAsync(h->fixed, 0, nv, stream));
-  if (cell_pi1)
-    HIP_TRY(hipMemcpyAsync(h->cell_pi1, cell_pi1, nc * sizeof(double),
-                           memspace == EQLB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-  // the dofmap, by the kernel behind eqlb_mesh_lagrange_dofmap (device memory space: one launch, nothing waits)
-  EQLB_TRY(eqlb_mesh_lagrange_dofmap(mesh, p, h->cell_dofs.get(), nullptr, EQLB_MEM_DEVICE, stream_));
-  const int64_t nshared = (int64_t)m.nnodes + (int64_t)m.nfacets * ne;
-  // (k_primal_slots counts an unmatched slot in the third word behind its status pointer: status[3] here)
-  hipLaunchKernelGGL(k_primal_slots, dim3(grid_of(nshared, PS_THREADS)), dim3(PS_THREADS), 0, stream, s, node_cells,
-                     m.facet_cells, h->cell_dofs.get(), h->slots.get(), h->status.get() + 1);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
-  if (memspace == EQLB_MEM_HOST)
-    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)
-  *handle = h.release();
-  return EQLB_OK;
+  return eqlb::solver_create("eqlb_elasticity_create", std::move(h), mesh, p, cell_pi1, memspace, stream_, handle);
 }
 EQLB_CATCH_ALL
 
@@ -510,52 +301,16 @@ void eqlb_elasticity_destroy(eqlb_elasticity_t* handle) { delete handle; }
 
 int eqlb_elasticity_ndofs(const eqlb_elasticity_t* handle, int64_t* ndofs)
 {
-  using namespace eqlb;
-  if (!handle || !ndofs)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_elasticity_ndofs: null argument");
-  *ndofs = handle->ndofs;
-  return EQLB_OK;
+  return eqlb::solver_ndofs("eqlb_elasticity_ndofs", handle, ndofs);
 }
 
 int eqlb_elasticity_set_dirichlet(eqlb_elasticity_t* h, int32_t nlist0, const int32_t* facets0, int32_t nlist1,
                                   const int32_t* facets1, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_set_dirichlet";
-  const int32_t nlist[2] = {nlist0, nlist1};
-  const int32_t* const facets[2] = {facets0, facets1};
-  for (int r = 0; r < 2; ++r)
-    if (nlist[r] < 0 || (nlist[r] > 0 && !facets[r]))
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist%d = %d, or a null list", who, r, (int)nlist[r]);
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  const DeviceMesh& m = h->mesh->m;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  if (host)
-    for (int r = 0; r < 2; ++r)
-      for (int32_t i = 0; i < nlist[r]; ++i)
-        if (facets[r][i] < 0 || facets[r][i] >= m.nfacets)
-          return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets%d[%d] = %d is no facet of the mesh (%d facets)", who, r,
-                      (int)i, (int)facets[r][i], (int)m.nfacets);
-  HostCall s; // (a device-memory call stages nothing: no allocation, no copy and no wait)
-  const DevPiece<int32_t> d_f[2] = {s.in(host ? facets0 : nullptr, (size_t)nlist0),
-                                    s.in(host ? facets1 : nullptr, (size_t)nlist1)};
-  if (host && (nlist0 > 0 || nlist1 > 0))
-    HIP_TRY(s.upload(stream));
-  s.note(hipMemsetAsync(h->fixed, 0, 2 * (size_t)h->ndofs, stream));
-  s.note(hipMemsetAsync(h->status, 0, 3 * sizeof(int32_t), stream));
-  for (int r = 0; r < 2; ++r)
-    if (nlist[r] > 0)
-    {
-      hipLaunchKernelGGL(k_elast_mask, dim3(grid_of(nlist[r], PS_THREADS)), dim3(PS_THREADS), 0, stream, nlist[r],
-                         host ? d_f[r].get() : facets[r], r, m.nnodes, m.nfacets, h->space.ne, m.facet_nodes,
-                         h->fixed.get(), h->status.get());
-      s.note(hipGetLastError());
-    }
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  const int32_t nlists[2] = {nlist0, nlist1};
+  const int32_t* const lists[2] = {facets0, facets1};
+  return eqlb::solver_set_dirichlet("eqlb_elasticity_set_dirichlet", h, nlists, lists, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -563,29 +318,7 @@ int eqlb_elasticity_load(eqlb_elasticity_t* h, int32_t degree_dg, const double* 
                          double* b, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_load";
-  if (degree_dg < 0 || degree_dg > PS_DMAX)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degree_dg = %d outside 0 ... 3", who, (int)degree_dg);
-  EQLB_TRY(check_handle(who, h));
-  if (!rhs_dg || !b)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t nf = 2 * (size_t)h->space.ncells * nd_of(degree_dg), n = 2 * (size_t)h->ndofs;
-  HostCall s;
-  const auto d_f = s.in(host ? rhs_dg : nullptr, nf), d_e = s.in(host ? b_extra : nullptr, n);
-  const auto d_b = s.out(host ? b : nullptr, n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  s.note(launch_cell<CELL_LOAD>(h->p, degree_dg, cell_args(*h, ONE_COLUMN, host ? d_f.get() : rhs_dg, false), stream));
-  GatherArgs g = gather_args(*h, ONE_COLUMN, false);
-  g.add = host ? d_e.get() : b_extra;
-  g.y = host ? d_b.get() : b;
-  s.note(launch_gather(*h, g, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_load("eqlb_elasticity_load", h, degree_dg, rhs_dg, b_extra, b, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -593,44 +326,14 @@ int eqlb_elasticity_apply(eqlb_elasticity_t* h, const double* u, double* y, int3
                           void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_apply";
-  EQLB_TRY(check_handle(who, h));
-  if (!u || !y)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = 2 * (size_t)h->ndofs;
-  HostCall s;
-  const auto d_u = s.in(host ? u : nullptr, n);
-  const auto d_y = s.out(host ? y : nullptr, n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  s.note(enqueue_apply(*h, host ? d_u.get() : u, host ? d_y.get() : y, masked != 0, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_apply("eqlb_elasticity_apply", h, 1, u, y, masked, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
 int eqlb_elasticity_diagonal(eqlb_elasticity_t* h, double* out, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_diagonal";
-  EQLB_TRY(check_handle(who, h));
-  if (!out)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  HostCall s;
-  const auto d_o = s.out(host ? out : nullptr, 2 * (size_t)h->ndofs);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  s.note(enqueue_diagonal(*h, host ? d_o.get() : out, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_diagonal("eqlb_elasticity_diagonal", h, out, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -638,34 +341,7 @@ int eqlb_elasticity_residual(eqlb_elasticity_t* h, const double* b, const double
                              int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_residual";
-  EQLB_TRY(check_handle(who, h));
-  if (!b || !u || !r)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = 2 * (size_t)h->ndofs;
-  HostCall s;
-  const auto d_b = s.in(host ? b : nullptr, n), d_u = s.in(host ? u : nullptr, n);
-  const auto d_r = s.out(host ? r : nullptr, n);
-  const auto d_n = s.out(host ? norms : nullptr, 2);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  const double *pb = host ? d_b.get() : b, *pu = host ? d_u.get() : u;
-  double* pn = host ? d_n.get() : norms;
-  if (pn)
-  {
-    // the reference norm first, into the work vector q: the residual proper then leaves r as the caller sees it
-    s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, h->q, true, stream));
-    s.note(launch_scalar(pcg_work(*h), 1u, STEP_NORM, 0, 0.0, 0.0, pn + 1, stream));
-  }
-  s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, host ? d_r.get() : r, false, stream));
-  if (pn)
-    s.note(launch_scalar(pcg_work(*h), 1u, STEP_NORM, 0, 0.0, 0.0, pn, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_residual("eqlb_elasticity_residual", h, b, u, r, norms, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -673,36 +349,9 @@ int eqlb_elasticity_solve(eqlb_elasticity_t* h, const double* b, double* u, doub
                           double* info, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_elasticity_solve";
-  if (maxit < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
-  if (!(rtol >= 0.0) || !(atol >= 0.0))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
-  EQLB_TRY(check_handle(who, h));
-  if (!b || !u || !info)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
-  int32_t status[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  for (int r = 0; r < 2; ++r)
-    if (status[1 + r] < 1)
-      return fail(EQLB_ERR_INVALID_ARGUMENT,
-                  "%s: singular: component %d has no Dirichlet DOF (eqlb_elasticity_set_dirichlet first)", who, r);
-  auto residual = [&](const ManyCols& c, const double* pb, const double* pu, double* r, bool only_fixed) {
-    return enqueue_residual(*h, c, pb, pu, r, only_fixed, stream);
-  };
-  auto product = [&](const ManyCols& c) { return enqueue_product(*h, c, stream); };
-  const PcgWork w = pcg_work(*h);
-  return pcg_solve_groups(w.n, 1, b, u, info, memspace == EQLB_MEM_HOST, stream,
-                          [&](int, const double* pb, double* pu, double* pinfo) {
-                            return pcg_solve(w, residual, product, JacobiSteps<1>{w, stream}, pb, pu, rtol, atol, maxit,
-                                             pinfo, status[0], stream);
-                          });
+  return eqlb::solver_solve("eqlb_elasticity_solve", h, 1, b, u, rtol, atol, maxit, info, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
 } // extern "C"
+

@@ -1,0 +1,496 @@
+// The host side of a P_p solver handle, ONCE for the Poisson unit (eqlb_primal_solve.hip: eqlb_primal, bs = 1, up to
+// MANY_R columns) and the elasticity unit (eqlb_primal_elasticity.hip: eqlb_elasticity, bs = 2, one column): the
+// handle base, the launches on its work space, the view the hierarchy unit gets and the bodies of the C entries.  A unit
+// adds its cell kernel and, for its handle type H, the one hook the code here finds by overload:
+//   template <int MODE> hipError_t launch_cell(const H&, const ManyCols&, int d, const double* u, bool only_fixed,
+//                                              hipStream_t)
+// the store pass on the columns of c (u [R][bs ndofs]; load: rhs_dg of degree d) into the y_loc of work_of(h, c.R).
+// bs and the column limit are constants of H, so a unit instantiates the kernels of its own bs and column count only.
+// Everything lies in an unnamed namespace, as in eqlb_primal_common.h.
+//
+// THE STATUS WORD of a handle, int32 [4] in device memory:
+//   [0]        listed facet ids outside the mesh, skipped (device memory space only; info[7] of a solve)
+//   [1 .. bs]  listed valid ids of component 0 .. bs - 1: a solve refuses a component without one as singular
+//   [1 + bs]   slots of the sum pass that matched no local index (a broken table), counted at create
+// set_dirichlet clears the 1 + bs words of the mask and leaves the last one; k_primal_slots counts in the third word
+// behind its status pointer, so it gets status + (bs - 1).
+#pragma once
+
+#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
+#include "eqlb_primal_common.h"
+
+#include <climits>
+#include <memory>
+
+namespace eqlb
+{
+namespace
+{
+// what eqlb_primal_t and eqlb_elasticity_t share; everything but the grown work space is carved out of one allocation at
+// create
+template <int BS, int MAXC>
+struct SolverHandle
+{
+  static_assert((BS == 1 && MAXC == MANY_R) || (BS == 2 && MAXC == 1), "columns for scalar spaces only");
+  static constexpr int bs = BS;         // components per DOF: the vectors have bs * ndofs rows
+  static constexpr int max_cols = MAXC; // columns of a launch at the most
+  eqlb_mesh* mesh = nullptr;
+  int p = 0, nd = 0;
+  int64_t ndofs = 0; // scalar count
+  bool has_coeff = false;
+  SpaceArgs space{};
+  DevCarve mem;
+  DevPiece<int32_t> cell_dofs, slots, status;
+  DevPiece<double> coeff, yloc, diag, r, z, d, q, part; // coeff [ncells]: kappa, or pi_1 per cell
+  DevPiece<uint8_t> fixed;
+  DevPiece<PcgState> st;
+  // the work space for 2 ... max_cols columns (wide.R of them): grown by the first call that needs it, then reused
+  DevBuf<char> wide_mem;
+  PcgWork wide{};
+};
+
+constexpr int STATUS_WORDS = 4;
+
+// the hook of a unit (above); this declaration only makes the name a template for the calls below
+template <int MODE, class H>
+hipError_t launch_cell(const H& h, const ManyCols& c, int d, const double* u, bool only_fixed, hipStream_t stream);
+
+const ManyCols ONE_COLUMN{1, 1u, 0, nullptr}; // a launch on one vector that knows no state
+
+// the work space the launches on R columns use: the carve of the handle for one, the grown one (primal_work) for more
+template <class H>
+PcgWork work_of(const H& h, int R)
+{
+  PcgWork w = R == 1 ? PcgWork{H::bs * h.ndofs, 1, h.diag, h.fixed, h.yloc, h.r, h.z, h.d, h.q, h.part, h.st} : h.wide;
+  w.R = R;
+  return w;
+}
+
+// the work space for R columns, grown if need be; a handle type of one column refuses more
+template <class H>
+int primal_work(H* h, int R, PcgWork& w)
+{
+  if constexpr (H::max_cols == 1)
+  {
+    if (R != 1)
+      return fail(EQLB_ERR_UNSUPPORTED,
+                  "elasticity_level: several right-hand sides are provided for Poisson handles (bs = 1) only");
+  }
+  else if (R > 1 && R > h->wide.R)
+  {
+    const size_t n = (size_t)H::bs * h->ndofs, ny = (size_t)H::bs * h->space.ncells * h->nd;
+    size_t off = 0;
+    auto piece = [&](size_t bytes) {
+      const size_t o = off;
+      off += round_up256(bytes);
+      return o;
+    };
+    const size_t o_y = piece(R * ny * sizeof(double)), o_r = piece(R * n * sizeof(double)),
+                 o_z = piece(R * n * sizeof(double)), o_d = piece(R * n * sizeof(double)),
+                 o_q = piece(R * n * sizeof(double)), o_p = piece((size_t)R * 2 * PS_MAXBLOCKS * sizeof(double)),
+                 o_s = piece(R * sizeof(PcgState));
+    h->wide = PcgWork{};
+    HIP_TRY(h->wide_mem.alloc_raw(off)); // (frees the smaller one first)
+    char* base = h->wide_mem.get();
+    auto dp = [&](size_t o) { return reinterpret_cast<double*>(base + o); };
+    h->wide = PcgWork{(int64_t)n, R,       h->diag, h->fixed, dp(o_y), dp(o_r),
+                      dp(o_z),    dp(o_d), dp(o_q), dp(o_p),  reinterpret_cast<PcgState*>(base + o_s)};
+  }
+  w = work_of(*h, R);
+  return EQLB_OK;
+}
+
+template <class H>
+GatherArgs gather_args(const H& h, const ManyCols& c, bool masked)
+{
+  const PcgWork w = work_of(h, c.R);
+  GatherArgs g{};
+  g.s = h.space;
+  g.yloc = w.yloc;
+  g.fixed = masked ? h.fixed.get() : nullptr;
+  g.part = w.part;
+  g.cols = c;
+  g.ystride = (int64_t)H::bs * h.space.ncells * h.nd;
+  return g;
+}
+
+template <class H>
+hipError_t launch_gather(const H& h, const GatherArgs& g, hipStream_t stream)
+{
+  const dim3 grid(stream_blocks(H::bs * h.ndofs)), block(PS_THREADS);
+  if constexpr (H::max_cols == 1)
+    hipLaunchKernelGGL((k_primal_gather<H::bs, 1>), grid, block, 0, stream, g);
+  else if (g.cols.R == 1)
+    hipLaunchKernelGGL((k_primal_gather<H::bs, 1>), grid, block, 0, stream, g);
+  else
+    hipLaunchKernelGGL((k_primal_gather<H::bs, MANY_R>), grid, block, 0, stream, g);
+  return hipGetLastError();
+}
+
+// y = owner sum of y_loc (masked or raw) on the columns of c; y DEVICE [R][bs ndofs]
+template <class H>
+hipError_t enqueue_owner_sum(const H& h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
+{
+  GatherArgs g = gather_args(h, c, masked);
+  g.y = y;
+  return launch_gather(h, g, stream);
+}
+
+template <class H>
+hipError_t enqueue_diagonal(const H& h, double* out, hipStream_t stream)
+{
+  const hipError_t e = launch_cell<CELL_DIAGONAL>(h, ONE_COLUMN, 0, nullptr, false, stream);
+  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, out, false, stream);
+}
+
+// r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in part
+template <class H>
+hipError_t enqueue_residual(const H& h, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
+                            hipStream_t stream)
+{
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h, c, 0, u, only_fixed, stream);
+  if (e != hipSuccess)
+    return e;
+  GatherArgs g = gather_args(h, c, true);
+  g.b = b;
+  g.r = r;
+  g.dot = DOT_R_R;
+  return launch_gather(h, g, stream);
+}
+
+// q = A d on the free rows (the direction d of the work space), the block partials of d.q in part
+template <class H>
+hipError_t enqueue_product(const H& h, const ManyCols& c, hipStream_t stream)
+{
+  const PcgWork w = work_of(h, c.R);
+  const hipError_t e = launch_cell<CELL_OPERATOR>(h, c, 0, w.d, false, stream);
+  if (e != hipSuccess)
+    return e;
+  GatherArgs g = gather_args(h, c, true);
+  g.y = w.q;
+  g.w = w.d;
+  g.dot = DOT_W_Y;
+  return launch_gather(h, g, stream);
+}
+
+// the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
+template <class H>
+void solver_level(H* h, SolverLevel& v)
+{
+  v = SolverLevel{};
+  v.handle = h;
+  v.mesh = h->mesh;
+  v.p = h->p;
+  v.bs = H::bs;
+  v.ndofs = h->ndofs;
+  v.cell_dofs = h->cell_dofs;
+  v.diag = h->diag;
+  v.fixed = h->fixed;
+  v.status = h->status;
+  v.work = [](void* hh, int R, PcgWork& w) { return primal_work(static_cast<H*>(hh), R, w); };
+  v.owner_sum = [](void* hh, const ManyCols& c, double* y, bool masked, hipStream_t stream) {
+    return enqueue_owner_sum(*static_cast<H*>(hh), c, y, masked, stream);
+  };
+  v.residual = [](void* hh, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
+                  hipStream_t stream) {
+    return enqueue_residual(*static_cast<H*>(hh), c, b, u, r, only_fixed, stream);
+  };
+  v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
+    return enqueue_product(*static_cast<H*>(hh), c, stream);
+  };
+}
+
+// ---- the C entries behind their names (`who`) -------------------------------------------------------------------------
+inline int check_handle(const char* who, const void* h)
+{
+  if (!h)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
+  return EQLB_OK;
+}
+
+// what every *_many entry checks about its column count
+inline int check_nrhs(const char* who, int32_t nrhs)
+{
+  if (nrhs < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d (at least 1)", who, (int)nrhs);
+  return EQLB_OK;
+}
+
+// h: a fresh handle that holds what only its unit knows; cell_coeff [ncells] in `memspace` or nullptr
+template <class H>
+int solver_create(const char* who, std::unique_ptr<H> h, eqlb_mesh* mesh, int32_t p, const double* cell_coeff,
+                  int32_t memspace, void* stream_, H** handle)
+{
+  if (p < 1 || p > PS_PMAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4", who, (int)p);
+  if (!mesh || !handle)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  const DeviceMesh& m = mesh->m;
+  const int ne = p - 1, ni = (p - 1) * (p - 2) / 2, nd = nd_of(p);
+  const int64_t ndofs = (int64_t)m.nnodes + (int64_t)m.nfacets * ne + (int64_t)m.ncells * ni;
+  if (ndofs > INT32_MAX || (int64_t)m.ncells * nd > INT32_MAX || m.ncells < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %lld DOFs, %lld cell entries do not fit 32 bits", who, (long long)ndofs,
+                (long long)m.ncells * nd);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  // a handle of eqlb_mesh_create keeps node -> cell on the host until somebody needs it on the device
+  const int32_t* node_cells = nullptr;
+  if (mesh_node_cells(mesh, &node_cells))
+    return EQLB_ERR_DEVICE;
+  h->mesh = mesh;
+  h->p = p;
+  h->nd = nd;
+  h->ndofs = ndofs;
+  h->has_coeff = cell_coeff != nullptr;
+  const size_t nc = (size_t)m.ncells, nslots = 3 * nc * (size_t)(1 + ne), nv = (size_t)H::bs * ndofs;
+  h->cell_dofs = h->mem.template piece<int32_t>(nc * nd);
+  h->slots = h->mem.template piece<int32_t>(nslots);
+  h->status = h->mem.template piece<int32_t>(STATUS_WORDS);
+  h->coeff = h->mem.template piece<double>(nc);
+  h->yloc = h->mem.template piece<double>(H::bs * nc * nd);
+  h->diag = h->mem.template piece<double>(nv);
+  h->r = h->mem.template piece<double>(nv);
+  h->z = h->mem.template piece<double>(nv);
+  h->d = h->mem.template piece<double>(nv);
+  h->q = h->mem.template piece<double>(nv);
+  h->part = h->mem.template piece<double>(2 * (size_t)PS_MAXBLOCKS);
+  h->fixed = h->mem.template piece<uint8_t>(nv);
+  h->st = h->mem.template piece<PcgState>(1);
+  HIP_TRY(h->mem.alloc());
+  SpaceArgs& s = h->space;
+  s.ndofs = ndofs;
+  s.nnodes = m.nnodes;
+  s.nfacets = m.nfacets;
+  s.ncells = m.ncells;
+  s.ne = ne;
+  s.ni = ni > 0 ? ni : 1;
+  s.nd = nd;
+  s.nco = m.node_cells_off;
+  s.fco = m.facet_cells_off;
+  s.slots = h->slots;
+  HIP_TRY(hipMemsetAsync(h->status, 0, STATUS_WORDS * sizeof(int32_t), stream));
+  HIP_TRY(hipMemsetAsync(h->fixed, 0, nv, stream));
+  if (cell_coeff)
+    HIP_TRY(hipMemcpyAsync(h->coeff, cell_coeff, nc * sizeof(double),
+                           memspace == EQLB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+  // the dofmap, by the kernel behind eqlb_mesh_lagrange_dofmap (device memory space: one launch, nothing waits)
+  EQLB_TRY(eqlb_mesh_lagrange_dofmap(mesh, p, h->cell_dofs.get(), nullptr, EQLB_MEM_DEVICE, stream_));
+  const int64_t nshared = (int64_t)m.nnodes + (int64_t)m.nfacets * ne;
+  hipLaunchKernelGGL(k_primal_slots, dim3(grid_of(nshared, PS_THREADS)), dim3(PS_THREADS), 0, stream, s, node_cells,
+                     m.facet_cells, h->cell_dofs.get(), h->slots.get(), h->status.get() + (H::bs - 1));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (memspace == EQLB_MEM_HOST)
+    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's coefficient array has been read)
+  *handle = h.release();
+  return EQLB_OK;
+}
+
+template <class H>
+int solver_ndofs(const char* who, const H* h, int64_t* ndofs)
+{
+  if (!h || !ndofs)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  *ndofs = h->ndofs;
+  return EQLB_OK;
+}
+
+// the list of component r is facets[r] [nlist[r]]; the messages name the lists as the unit's entry does: "nlist",
+// "facets" for one component, "nlist0", "facets1" for two
+template <class H>
+int solver_set_dirichlet(const char* who, H* h, const int32_t (&nlist)[H::bs], const int32_t* const (&facets)[H::bs],
+                         int32_t memspace, void* stream_)
+{
+  constexpr int bs = H::bs;
+  const char* const tag[2] = {bs == 1 ? "" : "0", "1"};
+  for (int r = 0; r < bs; ++r)
+    if (nlist[r] < 0 || (nlist[r] > 0 && !facets[r]))
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist%s = %d, or a null list", who, tag[r], (int)nlist[r]);
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  const DeviceMesh& m = h->mesh->m;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  if (host)
+    for (int r = 0; r < bs; ++r)
+      for (int32_t i = 0; i < nlist[r]; ++i)
+        if (facets[r][i] < 0 || facets[r][i] >= m.nfacets)
+          return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets%s[%d] = %d is no facet of the mesh (%d facets)", who, tag[r],
+                      (int)i, (int)facets[r][i], (int)m.nfacets);
+  HostCall s; // (a device-memory call stages nothing: no allocation, no copy and no wait)
+  DevPiece<int32_t> d_f[bs];
+  bool any = false;
+  for (int r = 0; r < bs; ++r)
+  {
+    d_f[r] = s.in(host ? facets[r] : nullptr, (size_t)nlist[r]);
+    any = any || nlist[r] > 0;
+  }
+  if (host && any)
+    HIP_TRY(s.upload(stream));
+  s.note(hipMemsetAsync(h->fixed, 0, (size_t)bs * h->ndofs, stream));
+  s.note(hipMemsetAsync(h->status, 0, (1 + bs) * sizeof(int32_t), stream));
+  for (int r = 0; r < bs; ++r)
+    if (nlist[r] > 0)
+    {
+      hipLaunchKernelGGL(k_primal_mask<bs>, dim3(grid_of(nlist[r], PS_THREADS)), dim3(PS_THREADS), 0, stream, nlist[r],
+                         host ? d_f[r].get() : facets[r], r, m.nnodes, m.nfacets, h->space.ne, m.facet_nodes,
+                         h->fixed.get(), h->status.get());
+      s.note(hipGetLastError());
+    }
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+template <class H>
+int solver_load(const char* who, H* h, int32_t degree_dg, const double* rhs_dg, const double* b_extra, double* b,
+                int32_t memspace, void* stream_)
+{
+  if (degree_dg < 0 || degree_dg > PS_DMAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degree_dg = %d outside 0 ... 3", who, (int)degree_dg);
+  EQLB_TRY(check_handle(who, h));
+  if (!rhs_dg || !b)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t nf = (size_t)H::bs * h->space.ncells * nd_of(degree_dg), n = (size_t)H::bs * h->ndofs;
+  HostCall s;
+  const auto d_f = s.in(host ? rhs_dg : nullptr, nf), d_e = s.in(host ? b_extra : nullptr, n);
+  const auto d_b = s.out(host ? b : nullptr, n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  s.note(launch_cell<CELL_LOAD>(*h, ONE_COLUMN, degree_dg, host ? d_f.get() : rhs_dg, false, stream));
+  GatherArgs g = gather_args(*h, ONE_COLUMN, false);
+  g.add = host ? d_e.get() : b_extra;
+  g.y = host ? d_b.get() : b;
+  s.note(launch_gather(*h, g, stream));
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+// u, y [nrhs][bs ndofs]: groups of up to max_cols columns, one store pass and one sum pass each
+template <class H>
+int solver_apply(const char* who, H* h, int32_t nrhs, const double* u, double* y, int32_t masked, int32_t memspace,
+                 void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_nrhs(who, nrhs));
+  if (!u || !y)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)H::bs * h->ndofs;
+  PcgWork w;
+  EQLB_TRY(primal_work(h, nrhs < H::max_cols ? nrhs : H::max_cols, w));
+  HostCall s;
+  const auto d_u = s.in(host ? u : nullptr, nrhs * n);
+  const auto d_y = s.out(host ? y : nullptr, nrhs * n);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double* pu = host ? d_u.get() : u;
+  double* py = host ? d_y.get() : y;
+  for (int32_t c0 = 0; c0 < nrhs; c0 += H::max_cols)
+  {
+    const int R = nrhs - c0 < H::max_cols ? nrhs - c0 : H::max_cols;
+    const ManyCols cols{R, (1u << R) - 1u, 0, nullptr};
+    s.note(launch_cell<CELL_OPERATOR>(*h, cols, 0, pu + c0 * n, false, stream));
+    s.note(enqueue_owner_sum(*h, cols, py + c0 * n, masked != 0, stream));
+  }
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+template <class H>
+int solver_diagonal(const char* who, H* h, double* out, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  if (!out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  HostCall s;
+  const auto d_o = s.out(host ? out : nullptr, (size_t)H::bs * h->ndofs);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  s.note(enqueue_diagonal(*h, host ? d_o.get() : out, stream));
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+template <class H>
+int solver_residual(const char* who, H* h, const double* b, const double* u, double* r, double* norms, int32_t memspace,
+                    void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  if (!b || !u || !r)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t n = (size_t)H::bs * h->ndofs;
+  HostCall s;
+  const auto d_b = s.in(host ? b : nullptr, n), d_u = s.in(host ? u : nullptr, n);
+  const auto d_r = s.out(host ? r : nullptr, n);
+  const auto d_n = s.out(host ? norms : nullptr, 2);
+  if (host)
+    HIP_TRY(s.upload(stream));
+  const double *pb = host ? d_b.get() : b, *pu = host ? d_u.get() : u;
+  double* pn = host ? d_n.get() : norms;
+  if (pn)
+  {
+    // the reference norm first, into the work vector q: the residual proper then leaves r as the caller sees it
+    s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, h->q, true, stream));
+    s.note(launch_scalar(work_of(*h, 1), 1u, STEP_NORM, 0, 0.0, 0.0, pn + 1, stream));
+  }
+  s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, host ? d_r.get() : r, false, stream));
+  if (pn)
+    s.note(launch_scalar(work_of(*h, 1), 1u, STEP_NORM, 0, 0.0, 0.0, pn, stream));
+  HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+// b, u [nrhs][bs ndofs], info HOST [nrhs][8]
+template <class H>
+int solver_solve(const char* who, H* h, int32_t nrhs, const double* b, double* u, double rtol, double atol,
+                 int32_t maxit, double* info, int32_t memspace, void* stream_)
+{
+  if (maxit < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
+  if (!(rtol >= 0.0) || !(atol >= 0.0))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_nrhs(who, nrhs));
+  if (!b || !u || !info)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
+  int32_t status[STATUS_WORDS] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int r = 0; r < H::bs; ++r)
+    if (status[1 + r] < 1)
+    {
+      if constexpr (H::bs == 1)
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
+      else
+        return fail(EQLB_ERR_INVALID_ARGUMENT,
+                    "%s: singular: component %d has no Dirichlet DOF (eqlb_elasticity_set_dirichlet first)", who, r);
+    }
+  PcgWork grown;
+  EQLB_TRY(primal_work(h, nrhs < H::max_cols ? nrhs : H::max_cols, grown));
+  auto residual = [&](const ManyCols& c, const double* xb, const double* xu, double* r, bool only_fixed) {
+    return enqueue_residual(*h, c, xb, xu, r, only_fixed, stream);
+  };
+  auto product = [&](const ManyCols& c) { return enqueue_product(*h, c, stream); };
+  return pcg_solve_groups(H::bs * h->ndofs, nrhs, b, u, info, memspace == EQLB_MEM_HOST, stream,
+                          [&](int R, const double* pb, double* pu, double* pinfo) {
+                            const PcgWork w = work_of(*h, R);
+                            return pcg_solve(w, residual, product, JacobiSteps<H::max_cols>{w, stream}, pb, pu, rtol,
+                                             atol, maxit, pinfo, status[0], stream);
+                          });
+}
+} // namespace
+} // namespace eqlb

@@ -23,17 +23,22 @@
 // forms alpha, beta, rho and the stop flag IN DEVICE MEMORY (PcgState) for the next kernel.  Once the flag is set the
 // remaining kernels of a batch return at once, so the result does not depend on how often the host looks: it reads
 // the state every EQLB_PRIMAL_CHECK_EVERY iterations.  Nothing is allocated inside the iteration.
-// The sum pass, the CG kernels and the host loop lie in eqlb_primal_common.h, which eqlb_primal_elasticity.hip shares.
+// This unit holds the cell kernel, its dispatch on p, d and R, the table getters and the C entries.  The sum pass, the
+// mask, the CG kernels and the host loop lie in eqlb_primal_common.h; the handle, the launches on it and the bodies of the
+// C entries in eqlb_primal_handle.h.  eqlb_primal_elasticity.hip shares both.
 // Several right-hand sides in one call (eqlb_primal_apply_many, eqlb_primal_solve_many) run on the same kernels and
 // the same host loop: k_primal_cell<P, CELL_OPERATOR, 0, R> here, the rest in eqlb_primal_common.h, which states the
 // rule.  The work space for one column is carved at create, the one for more is grown on demand (primal_work).
 #include "eqlb_device_common.h"
-#include "eqlb_mesh_handle.h" // (eqlb_host_util.h)
-#include "eqlb_primal_common.h" // the sum pass, the kernels and the host loop of the CG: shared with the elasticity unit
+#include "eqlb_primal_handle.h" // the host side of a solver handle; eqlb_primal_common.h: the kernels it launches
 #include "eqlb_tables_gen.h"
 
-#include <climits>
 #include <cmath>
+
+// the handle behind eqlb_primal_t
+struct eqlb_primal : eqlb::SolverHandle<1, eqlb::MANY_R>
+{
+};
 
 namespace eqlb
 {
@@ -214,28 +219,6 @@ __global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a, co
   }
 }
 
-// the mask of the listed facets; ids outside the mesh are skipped and counted (status[0]), valid ones counted (status[1])
-__global__ void __launch_bounds__(PS_THREADS)
-k_primal_mask(int32_t nlist, const int32_t* __restrict__ facets, int32_t nnodes, int32_t nfacets, int32_t ne,
-              const int32_t* __restrict__ facet_nodes, uint8_t* __restrict__ fixed, int32_t* __restrict__ status)
-{
-  const int32_t i = blockIdx.x * PS_THREADS + threadIdx.x;
-  if (i >= nlist)
-    return;
-  const int32_t f = facets[i];
-  if (f < 0 || f >= nfacets)
-  {
-    atomicAdd(status, 1);
-    return;
-  }
-  atomicAdd(status + 1, 1);
-  fixed[facet_nodes[2 * (int64_t)f]] = 1;
-  fixed[facet_nodes[2 * (int64_t)f + 1]] = 1;
-  for (int j = 0; j < ne; ++j)
-    fixed[(int64_t)nnodes + (int64_t)f * ne + j] = 1;
-}
-
-
 // ---- host side ------------------------------------------------------------------------------------------------
 // the launch on the columns of c: the load by its DG degree d, the operator by its column count, the diagonal as it is
 template <int P, int MODE>
@@ -297,69 +280,9 @@ hipError_t launch_cell(int p, int d, const CellArgs& a, const ManyCols& c, int64
     return launch_cell_p<4, MODE>(d, a, c, ustride, ystride, stream);
   }
 }
-} // namespace
-} // namespace eqlb
 
-// the handle behind eqlb_primal_t: everything is carved out of one allocation at create
-struct eqlb_primal
-{
-  eqlb_mesh* mesh = nullptr;
-  int p = 0, nd = 0;
-  int64_t ndofs = 0;
-  bool has_coeff = false;
-  eqlb::SpaceArgs space{};
-  eqlb::DevCarve mem;
-  eqlb::DevPiece<int32_t> cell_dofs, slots, status; // status: skipped facet ids, listed valid ones, unmatched slots
-  eqlb::DevPiece<double> coeff, yloc, diag, r, z, d, q, part;
-  eqlb::DevPiece<uint8_t> fixed;
-  eqlb::DevPiece<eqlb::PcgState> st;
-  // the work space for 2 ... MANY_R columns (wide.R of them): grown by the first call that needs it, then reused
-  eqlb::DevBuf<char> wide_mem;
-  eqlb::PcgWork wide{};
-};
-
-namespace eqlb
-{
-namespace
-{
-const ManyCols ONE_COLUMN{1, 1u, 0, nullptr}; // a launch on one vector that knows no state
-
-// the work space the launches on R columns use: the carve of the handle for one, the grown one (primal_work) for more
-PcgWork work_of(const eqlb_primal& h, int R)
-{
-  PcgWork w = R == 1 ? PcgWork{h.ndofs, 1, h.diag, h.fixed, h.yloc, h.r, h.z, h.d, h.q, h.part, h.st} : h.wide;
-  w.R = R;
-  return w;
-}
-
-// grows the work space for R > 1 columns if need be
-int primal_work(eqlb_primal* h, int R, PcgWork& w)
-{
-  if (R > 1 && R > h->wide.R)
-  {
-    const size_t n = (size_t)h->ndofs, ny = (size_t)h->space.ncells * h->nd;
-    size_t off = 0;
-    auto piece = [&](size_t bytes) {
-      const size_t o = off;
-      off += round_up256(bytes);
-      return o;
-    };
-    const size_t o_y = piece(R * ny * sizeof(double)), o_r = piece(R * n * sizeof(double)),
-                 o_z = piece(R * n * sizeof(double)), o_d = piece(R * n * sizeof(double)),
-                 o_q = piece(R * n * sizeof(double)), o_p = piece((size_t)R * 2 * PS_MAXBLOCKS * sizeof(double)),
-                 o_s = piece(R * sizeof(PcgState));
-    h->wide = PcgWork{};
-    HIP_TRY(h->wide_mem.alloc_raw(off)); // (frees the smaller one first)
-    char* base = h->wide_mem.get();
-    auto dp = [&](size_t o) { return reinterpret_cast<double*>(base + o); };
-    h->wide = PcgWork{h->ndofs, R,        h->diag,  h->fixed, dp(o_y), dp(o_r),
-                      dp(o_z),  dp(o_d),  dp(o_q),  dp(o_p),  reinterpret_cast<PcgState*>(base + o_s)};
-  }
-  w = work_of(*h, R);
-  return EQLB_OK;
-}
-
-// the store pass on the columns of c: u [R][ndofs] (load: rhs_dg) into the y_loc of the work space for c.R columns
+// the hook of eqlb_primal_handle.h, the store pass on the columns of c: u [R][ndofs] (load: rhs_dg) into the y_loc of the
+// work space for c.R columns
 template <int MODE>
 hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const double* u, bool only_fixed,
                        hipStream_t stream)
@@ -375,179 +298,9 @@ hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const dou
   a.yloc = work_of(h, c.R).yloc;
   return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, stream);
 }
-
-GatherArgs gather_args(const eqlb_primal& h, const ManyCols& c, bool masked)
-{
-  const PcgWork w = work_of(h, c.R);
-  GatherArgs g{};
-  g.s = h.space;
-  g.yloc = w.yloc;
-  g.fixed = masked ? h.fixed.get() : nullptr;
-  g.part = w.part;
-  g.cols = c;
-  g.ystride = (int64_t)h.space.ncells * h.nd;
-  return g;
-}
-
-hipError_t launch_gather(const eqlb_primal& h, const GatherArgs& g, hipStream_t stream)
-{
-  const dim3 grid(stream_blocks(h.ndofs)), block(PS_THREADS);
-  if (g.cols.R == 1)
-    hipLaunchKernelGGL((k_primal_gather<1, 1>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((k_primal_gather<1, MANY_R>), grid, block, 0, stream, g);
-  return hipGetLastError();
-}
-
-// y = owner sum of y_loc (masked or raw) on the columns of c; y DEVICE [R][ndofs]
-hipError_t enqueue_owner_sum(const eqlb_primal& h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
-{
-  GatherArgs g = gather_args(h, c, masked);
-  g.y = y;
-  return launch_gather(h, g, stream);
-}
-
-hipError_t enqueue_diagonal(const eqlb_primal& h, double* out, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_DIAGONAL>(h, ONE_COLUMN, 0, nullptr, false, stream);
-  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, out, false, stream);
-}
-
-// r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in part
-hipError_t enqueue_residual(const eqlb_primal& h, const ManyCols& c, const double* b, const double* u, double* r,
-                            bool only_fixed, hipStream_t stream)
-{
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h, c, 0, u, only_fixed, stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, c, true);
-  g.b = b;
-  g.r = r;
-  g.dot = DOT_R_R;
-  return launch_gather(h, g, stream);
-}
-
-// q = A d on the free rows (the direction d of the work space), the block partials of d.q in part
-hipError_t enqueue_product(const eqlb_primal& h, const ManyCols& c, hipStream_t stream)
-{
-  const PcgWork w = work_of(h, c.R);
-  const hipError_t e = launch_cell<CELL_OPERATOR>(h, c, 0, w.d, false, stream);
-  if (e != hipSuccess)
-    return e;
-  GatherArgs g = gather_args(h, c, true);
-  g.y = w.q;
-  g.w = w.d;
-  g.dot = DOT_W_Y;
-  return launch_gather(h, g, stream);
-}
-
-int check_handle(const char* who, const eqlb_primal* h)
-{
-  if (!h)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
-  return EQLB_OK;
-}
-
-// what every *_many entry checks about its column count
-int check_nrhs(const char* who, int32_t nrhs)
-{
-  if (nrhs < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d (at least 1)", who, (int)nrhs);
-  return EQLB_OK;
-}
-
-// eqlb_primal_apply and eqlb_primal_apply_many behind their names
-int primal_apply(const char* who, eqlb_primal* h, int32_t nrhs, const double* u, double* y, int32_t masked,
-                 int32_t memspace, void* stream_)
-{
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_nrhs(who, nrhs));
-  if (!u || !y)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)h->ndofs;
-  PcgWork w;
-  EQLB_TRY(primal_work(h, nrhs < MANY_R ? nrhs : MANY_R, w));
-  HostCall s;
-  const auto d_u = s.in(host ? u : nullptr, nrhs * n);
-  const auto d_y = s.out(host ? y : nullptr, nrhs * n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  const double* pu = host ? d_u.get() : u;
-  double* py = host ? d_y.get() : y;
-  for (int32_t c0 = 0; c0 < nrhs; c0 += MANY_R)
-  {
-    const int R = nrhs - c0 < MANY_R ? nrhs - c0 : MANY_R;
-    const ManyCols cols{R, (1u << R) - 1u, 0, nullptr};
-    s.note(launch_cell<CELL_OPERATOR>(*h, cols, 0, pu + c0 * n, false, stream));
-    s.note(enqueue_owner_sum(*h, cols, py + c0 * n, masked != 0, stream));
-  }
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
-}
-
-// eqlb_primal_solve and eqlb_primal_solve_many behind their names
-int primal_solve(const char* who, eqlb_primal* h, int32_t nrhs, const double* b, double* u, double rtol, double atol,
-                 int32_t maxit, double* info, int32_t memspace, void* stream_)
-{
-  if (maxit < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: maxit = %d (at least 1)", who, (int)maxit);
-  if (!(rtol >= 0.0) || !(atol >= 0.0))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: rtol = %g, atol = %g negative or NaN", who, rtol, atol);
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_nrhs(who, nrhs));
-  if (!b || !u || !info)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  // the status word of the mask: the call waits by nature, and nothing is launched for a singular problem
-  int32_t status[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (status[1] < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);
-  PcgWork grown;
-  EQLB_TRY(primal_work(h, nrhs < MANY_R ? nrhs : MANY_R, grown));
-  auto residual = [&](const ManyCols& c, const double* xb, const double* xu, double* r, bool only_fixed) {
-    return enqueue_residual(*h, c, xb, xu, r, only_fixed, stream);
-  };
-  auto product = [&](const ManyCols& c) { return enqueue_product(*h, c, stream); };
-  return pcg_solve_groups(h->ndofs, nrhs, b, u, info, memspace == EQLB_MEM_HOST, stream,
-                          [&](int R, const double* pb, double* pu, double* pinfo) {
-                            const PcgWork w = work_of(*h, R);
-                            return pcg_solve(w, residual, product, JacobiSteps<MANY_R>{w, stream}, pb, pu, rtol, atol, maxit,
-                                             pinfo, status[0], stream);
-                          });
-}
 } // namespace
 
-// the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
-void primal_level(eqlb_primal* h, SolverLevel& v)
-{
-  v = SolverLevel{};
-  v.handle = h;
-  v.mesh = h->mesh;
-  v.p = h->p;
-  v.bs = 1;
-  v.ndofs = h->ndofs;
-  v.cell_dofs = h->cell_dofs;
-  v.diag = h->diag;
-  v.fixed = h->fixed;
-  v.status = h->status;
-  v.work = [](void* hh, int R, PcgWork& w) { return primal_work(static_cast<eqlb_primal*>(hh), R, w); };
-  v.owner_sum = [](void* hh, const ManyCols& c, double* y, bool masked, hipStream_t stream) {
-    return enqueue_owner_sum(*static_cast<eqlb_primal*>(hh), c, y, masked, stream);
-  };
-  v.residual = [](void* hh, const ManyCols& c, const double* b, const double* u, double* r, bool only_fixed,
-                  hipStream_t stream) {
-    return enqueue_residual(*static_cast<eqlb_primal*>(hh), c, b, u, r, only_fixed, stream);
-  };
-  v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
-    return enqueue_product(*static_cast<eqlb_primal*>(hh), c, stream);
-  };
-}
+void primal_level(eqlb_primal* h, SolverLevel& v) { solver_level(h, v); }
 } // namespace eqlb
 
 extern "C" {
@@ -602,72 +355,8 @@ int eqlb_primal_create(eqlb_mesh_t* mesh, int32_t p, const double* cell_coeff, i
                        eqlb_primal_t** handle)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_create";
-  if (p < 1 || p > PS_PMAX)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: p = %d outside 1 ... 4", who, (int)p);
-  if (!mesh || !handle)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  const DeviceMesh& m = mesh->m;
-  const int ne = p - 1, ni = (p - 1) * (p - 2) / 2, nd = nd_of(p);
-  const int64_t ndofs = (int64_t)m.nnodes + (int64_t)m.nfacets * ne + (int64_t)m.ncells * ni;
-  if (ndofs > INT32_MAX || (int64_t)m.ncells * nd > INT32_MAX || m.ncells < 1)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %lld DOFs, %lld cell entries do not fit 32 bits", who, (long long)ndofs,
-                (long long)m.ncells * nd);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  // a handle of eqlb_mesh_create keeps node -> cell on the host until somebody needs it on the device
-  const int32_t* node_cells = nullptr;
-  if (mesh_node_cells(mesh, &node_cells))
-    return EQLB_ERR_DEVICE;
-  std::unique_ptr<eqlb_primal> h(new eqlb_primal);
-  h->mesh = mesh;
-  h->p = p;
-  h->nd = nd;
-  h->ndofs = ndofs;
-  h->has_coeff = cell_coeff != nullptr;
-  const size_t nc = (size_t)m.ncells, nslots = 3 * nc * (size_t)(1 + ne);
-  h->cell_dofs = h->mem.piece<int32_t>(nc * nd);
-  h->slots = h->mem.piece<int32_t>(nslots);
-  h->status = h->mem.piece<int32_t>(4);
-  h->coeff = h->mem.piece<double>(nc);
-  h->yloc = h->mem.piece<double>(nc * nd);
-  h->diag = h->mem.piece<double>((size_t)ndofs);
-  h->r = h->mem.piece<double>((size_t)ndofs);
-  h->z = h->mem.piece<double>((size_t)ndofs);
-  h->d = h->mem.piece<double>((size_t)ndofs);
-  h->q = h->mem.piece<double>((size_t)ndofs);
-  h->part = h->mem.piece<double>(2 * (size_t)PS_MAXBLOCKS);
-  h->fixed = h->mem.piece<uint8_t>((size_t)ndofs);
-  h->st = h->mem.piece<PcgState>(1);
-  HIP_TRY(h->mem.alloc());
-  SpaceArgs& s = h->space;
-  s.ndofs = ndofs;
-  s.nnodes = m.nnodes;
-  s.nfacets = m.nfacets;
-  s.ncells = m.ncells;
-  s.ne = ne;
-  s.ni = ni > 0 ? ni : 1;
-  s.nd = nd;
-  s.nco = m.node_cells_off;
-  s.fco = m.facet_cells_off;
-  s.slots = h->slots;
-  HIP_TRY(hipMemsetAsync(h->status, 0, 4 * sizeof(int32_t), stream));
-  HIP_TRY(hipMemsetAsync(h->fixed, 0, (size_t)ndofs, stream));
-  if (cell_coeff)
-    HIP_TRY(hipMemcpyAsync(h->coeff, cell_coeff, nc * sizeof(double),
-                           memspace == EQLB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-  // the dofmap, by the kernel behind eqlb_mesh_lagrange_dofmap (device memory space: one launch, nothing waits)
-  EQLB_TRY(eqlb_mesh_lagrange_dofmap(mesh, p, h->cell_dofs.get(), nullptr, EQLB_MEM_DEVICE, stream_));
-  const int64_t nshared = (int64_t)m.nnodes + (int64_t)m.nfacets * ne;
-  hipLaunchKernelGGL(k_primal_slots, dim3(grid_of(nshared, PS_THREADS)), dim3(PS_THREADS), 0, stream, s, node_cells,
-                     m.facet_cells, h->cell_dofs.get(), h->slots.get(), h->status.get());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
-  if (memspace == EQLB_MEM_HOST)
-    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's coefficient array has been read)
-  *handle = h.release();
-  return EQLB_OK;
+  return eqlb::solver_create("eqlb_primal_create", std::make_unique<eqlb_primal>(), mesh, p, cell_coeff, memspace,
+                             stream_, handle);
 }
 EQLB_CATCH_ALL
 
@@ -675,45 +364,15 @@ void eqlb_primal_destroy(eqlb_primal_t* handle) { delete handle; }
 
 int eqlb_primal_ndofs(const eqlb_primal_t* handle, int64_t* ndofs)
 {
-  using namespace eqlb;
-  if (!handle || !ndofs)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_primal_ndofs: null argument");
-  *ndofs = handle->ndofs;
-  return EQLB_OK;
+  return eqlb::solver_ndofs("eqlb_primal_ndofs", handle, ndofs);
 }
 
 int eqlb_primal_set_dirichlet(eqlb_primal_t* h, int32_t nlist, const int32_t* facets, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_set_dirichlet";
-  if (nlist < 0 || (nlist > 0 && !facets))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d, or a null list", who, (int)nlist);
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  const DeviceMesh& m = h->mesh->m;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  if (host)
-    for (int32_t i = 0; i < nlist; ++i)
-      if (facets[i] < 0 || facets[i] >= m.nfacets)
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is no facet of the mesh (%d facets)", who, (int)i,
-                    (int)facets[i], (int)m.nfacets);
-  HostCall s; // (a device-memory call stages nothing: no allocation, no copy and no wait)
-  const auto d_f = s.in(host ? facets : nullptr, (size_t)nlist);
-  if (host && nlist > 0)
-    HIP_TRY(s.upload(stream));
-  s.note(hipMemsetAsync(h->fixed, 0, (size_t)h->ndofs, stream));
-  s.note(hipMemsetAsync(h->status, 0, 2 * sizeof(int32_t), stream));
-  if (nlist > 0)
-  {
-    hipLaunchKernelGGL(k_primal_mask, dim3(grid_of(nlist, PS_THREADS)), dim3(PS_THREADS), 0, stream, nlist,
-                       host ? d_f.get() : facets, m.nnodes, m.nfacets, h->space.ne, m.facet_nodes, h->fixed.get(),
-                       h->status.get());
-    s.note(hipGetLastError());
-  }
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  const int32_t nlists[1] = {nlist};
+  const int32_t* const lists[1] = {facets};
+  return eqlb::solver_set_dirichlet("eqlb_primal_set_dirichlet", h, nlists, lists, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -721,36 +380,14 @@ int eqlb_primal_load(eqlb_primal_t* h, int32_t degree_dg, const double* rhs_dg, 
                      int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_load";
-  if (degree_dg < 0 || degree_dg > PS_DMAX)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degree_dg = %d outside 0 ... 3", who, (int)degree_dg);
-  EQLB_TRY(check_handle(who, h));
-  if (!rhs_dg || !b)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t nf = (size_t)h->space.ncells * nd_of(degree_dg), n = (size_t)h->ndofs;
-  HostCall s;
-  const auto d_f = s.in(host ? rhs_dg : nullptr, nf), d_e = s.in(host ? b_extra : nullptr, n);
-  const auto d_b = s.out(host ? b : nullptr, n);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  s.note(launch_cell<CELL_LOAD>(*h, ONE_COLUMN, degree_dg, host ? d_f.get() : rhs_dg, false, stream));
-  GatherArgs g = gather_args(*h, ONE_COLUMN, false);
-  g.add = host ? d_e.get() : b_extra;
-  g.y = host ? d_b.get() : b;
-  s.note(launch_gather(*h, g, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_load("eqlb_primal_load", h, degree_dg, rhs_dg, b_extra, b, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
 int eqlb_primal_apply(eqlb_primal_t* h, const double* u, double* y, int32_t masked, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::primal_apply("eqlb_primal_apply", h, 1, u, y, masked, memspace, stream_);
+  return eqlb::solver_apply("eqlb_primal_apply", h, 1, u, y, masked, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -758,28 +395,14 @@ int eqlb_primal_apply_many(eqlb_primal_t* h, int32_t nrhs, const double* u, doub
                            int32_t memspace, void* stream_)
 try
 {
-  return eqlb::primal_apply("eqlb_primal_apply_many", h, nrhs, u, y, masked, memspace, stream_);
+  return eqlb::solver_apply("eqlb_primal_apply_many", h, nrhs, u, y, masked, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
 int eqlb_primal_diagonal(eqlb_primal_t* h, double* out, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_diagonal";
-  EQLB_TRY(check_handle(who, h));
-  if (!out)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  HostCall s;
-  const auto d_o = s.out(host ? out : nullptr, (size_t)h->ndofs);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  s.note(enqueue_diagonal(*h, host ? d_o.get() : out, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_diagonal("eqlb_primal_diagonal", h, out, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -787,34 +410,7 @@ int eqlb_primal_residual(eqlb_primal_t* h, const double* b, const double* u, dou
                          int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* const who = "eqlb_primal_residual";
-  EQLB_TRY(check_handle(who, h));
-  if (!b || !u || !r)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)h->ndofs;
-  HostCall s;
-  const auto d_b = s.in(host ? b : nullptr, n), d_u = s.in(host ? u : nullptr, n);
-  const auto d_r = s.out(host ? r : nullptr, n);
-  const auto d_n = s.out(host ? norms : nullptr, 2);
-  if (host)
-    HIP_TRY(s.upload(stream));
-  const double *pb = host ? d_b.get() : b, *pu = host ? d_u.get() : u;
-  double* pn = host ? d_n.get() : norms;
-  if (pn)
-  {
-    // the reference norm first, into the work vector q: the residual proper then leaves r as the caller sees it
-    s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, h->q, true, stream));
-    s.note(launch_scalar(work_of(*h, 1), 1u, STEP_NORM, 0, 0.0, 0.0, pn + 1, stream));
-  }
-  s.note(enqueue_residual(*h, ONE_COLUMN, pb, pu, host ? d_r.get() : r, false, stream));
-  if (pn)
-    s.note(launch_scalar(work_of(*h, 1), 1u, STEP_NORM, 0, 0.0, 0.0, pn, stream));
-  HIP_TRY(s.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_residual("eqlb_primal_residual", h, b, u, r, norms, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -822,7 +418,7 @@ int eqlb_primal_solve(eqlb_primal_t* h, const double* b, double* u, double rtol,
                       double* info, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::primal_solve("eqlb_primal_solve", h, 1, b, u, rtol, atol, maxit, info, memspace, stream_);
+  return eqlb::solver_solve("eqlb_primal_solve", h, 1, b, u, rtol, atol, maxit, info, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -830,7 +426,7 @@ int eqlb_primal_solve_many(eqlb_primal_t* h, int32_t nrhs, const double* b, doub
                            int32_t maxit, double* info, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::primal_solve("eqlb_primal_solve_many", h, nrhs, b, u, rtol, atol, maxit, info, memspace, stream_);
+  return eqlb::solver_solve("eqlb_primal_solve_many", h, nrhs, b, u, rtol, atol, maxit, info, memspace, stream_);
 }
 EQLB_CATCH_ALL
 

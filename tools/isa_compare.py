@@ -7,7 +7,7 @@ REV's copy written to a temporary directory with `git show` (as tools/build_head
 the generated eqlb_tables_build_gen.h).  The gfx950 code object is unbundled, disassembled
 (llvm-objdump -d) and its notes read (llvm-readelf --notes).  The comparison is per symbol, not
 per file offset, since the emission order inside a unit may change: the instruction text without
-address and encoding, and per kernel the VGPR/AGPR/SGPR counts, private and group segment size,
+address and encoding (and without the "..." of the padding up to the next symbol), and per kernel the VGPR/AGPR/SGPR counts, private and group segment size,
 kernarg size and maximum workgroup size.  One summary line per unit; kernels present on one side
 only and kernels that differ are listed, and any of them makes the exit status 1.  Units without
 device code are skipped.  It only diffs two builds against each other.
@@ -69,7 +69,7 @@ def functions_of(disasm, ignore_pcrel=False):
             cur = funcs.setdefault(m.group(1), [])
         elif cur is not None and line.startswith(("\t", " ")):
             text = line.split("//")[0].strip()
-            if text:
+            if text and text != "...":  # ("...": zero padding up to the next symbol, which moves with the order)
                 if ignore_pcrel and cur and cur[-1].startswith("s_getpc_b64") and text.startswith("s_add_u32"):
                     text = re.sub(r"0x[0-9a-f]+$", "<pcrel>", text)
                 cur.append(text)
