@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = [
     "eqlb_hierarchy_solve_many",
     "eqlb_hierarchy_set_local", "eqlb_hierarchy_active", "eqlb_hierarchy_active_count",
     "eqlb_hierarchy_set_coarse", "eqlb_hierarchy_coarse_rows", "eqlb_hierarchy_coarse_factor",
+    "eqlb_get_mass_table", "eqlb_primal_set_reaction", "eqlb_elasticity_set_reaction",
+    "eqlb_primal_value_dg", "eqlb_get_value_table",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -1335,6 +1337,62 @@ def primal_stress_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, n
                                        C.c_void_p(stream)))
 
 
+def get_value_table(p: int, degree_dg: int):
+    """The built-in table PV<p,d> [nd_d, nd_p] of primal_value_dg (eqlb_get_value_table): DG_d nodal values of the L2
+    projection of the P_p basis functions onto P_d (lsolver.primal.value_table_exact)."""
+    ndp, nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2, (max(int(degree_dg), 0) + 1) * (max(int(degree_dg), 0) + 2) // 2
+    out = np.zeros((nd, ndp))
+    n = lib().eqlb_get_value_table(C.c_int32(p), C.c_int32(degree_dg), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
+def primal_value_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, coeff=None, op=None):
+    """eqlb_primal_value_dg on host arrays: the DG_{degree_dg} DOFs of coeff Pi_d u_h for u_h in P_p given by its cell
+    dofmap cell_dofs [ncells, nd_p] and vectors u [nrhs, ndofs] (or [ndofs]); coeff [ncells] or None (no
+    multiplication); op [nd_d, nd_p] replaces the built-in table.  Returns [nrhs, ncells*nd_d]: with coeff = c_T the
+    reaction part of the right-hand side an equilibrator needs, rhs = Pi_d f - primal_value_dg(u_h, c)."""
+    m = dmesh.mesh
+    ndp, nd = _primal_sizes(p, degree_dg)
+    cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+    uu = np.ascontiguousarray(u, dtype=np.float64)
+    uu = uu.reshape(1, -1) if uu.ndim < 2 else uu.reshape(uu.shape[0], -1)
+    kc = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.float64)
+    if cd.size != m.ncells * ndp or uu.size == 0 or (kc is not None and kc.size != m.ncells):
+        raise RuntimeError("Local solver: Input sizes does not match")
+    t = None
+    if op is not None:
+        t = np.ascontiguousarray(op, dtype=np.float64)
+        if t.size != nd * ndp:
+            raise RuntimeError("Local solver: Input sizes does not match")
+    out = np.zeros((uu.shape[0], m.ncells * nd))
+    primal_value_dg_raw(dmesh, p, degree_dg, uu.shape[0], _hp(cd), uu.shape[1], _hp(uu),
+                        _hp(kc) if kc is not None else None, _hp(out), t, MEM_HOST)
+    return out
+
+
+def primal_value_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, nrhs: int, cell_dofs, ndofs: int, u, coeff,
+                        value_dg, op=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_primal_value_dg on raw pointers (ints; coeff may be None) in `memspace`, ordered on `stream`: cell_dofs
+    int32 [ncells, nd_p], u [nrhs, ndofs], value_dg [nrhs, ncells*nd_d].  op is a host array or None.  Device memory:
+    one kernel, nothing waits for the device."""
+    t = None if op is None else np.ascontiguousarray(op, dtype=np.float64)
+    _check(lib().eqlb_primal_value_dg(dmesh._h, C.c_int32(p), C.c_int32(degree_dg), C.c_int32(nrhs), _vp(cell_dofs),
+                                      C.c_int64(ndofs), _vp(u), _vp(coeff), _hp(t) if t is not None else None,
+                                      _vp(value_dg), C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def get_mass_table(p: int):
+    """The built-in table Mass<p> [nd_p, nd_p] of the reaction term (eqlb_get_mass_table), 1 <= p <= 4."""
+    nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2
+    out = np.zeros((nd, nd))
+    n = lib().eqlb_get_mass_table(C.c_int32(p), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
 def get_stiffness_table(p: int):
     """The built-in table Stiff<p> [3, nd_p, nd_p] of PrimalPoisson (eqlb_get_stiffness_table), 1 <= p <= 4."""
     nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2
@@ -1419,6 +1477,22 @@ class _PrimalSolver:
     def load_raw(self, degree_dg, rhs_dg, b_extra, b, memspace=MEM_DEVICE, stream=0):
         _check(self._fn("load")(self._h, C.c_int32(degree_dg), _vp(rhs_dg), _vp(b_extra), _vp(b),
                                 C.c_int32(memspace), C.c_void_p(stream)))
+
+    def set_reaction(self, c=0.0, cell_c=None, stream=0):
+        """The operator gains + c u (eqlb_primal_set_reaction / eqlb_elasticity_set_reaction): cell_c, a host array
+        [ncells], where given, else the scalar c on every cell; c == 0 without an array switches the term off.  A
+        repeated call replaces the coefficient; a negative, NaN or infinite one is refused and the handle stays as it
+        was.  The diagonal is formed again; Multilevel.set_coarse(True) has to be called again afterwards."""
+        kc = None
+        if cell_c is not None:
+            kc = np.ascontiguousarray(cell_c, dtype=np.float64).ravel()
+            if kc.size != self.dmesh.counts()[1]:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        self.set_reaction_raw(c, None if kc is None else kc.ctypes.data, MEM_HOST, stream)
+
+    def set_reaction_raw(self, c=0.0, cell_c=None, memspace=MEM_DEVICE, stream=0):
+        """cell_c: a raw pointer (int) to [ncells] in `memspace`, or None (the scalar c)."""
+        _check(self._fn("set_reaction")(self._h, C.c_double(c), _vp(cell_c), C.c_int32(memspace), C.c_void_p(stream)))
 
     def apply(self, u, masked=False, stream=0):
         """y = A u; masked: 0 on the fixed rows."""

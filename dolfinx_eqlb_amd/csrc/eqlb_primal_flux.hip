@@ -221,6 +221,81 @@ k_primal_flux(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __rest
   }
 }
 
+// The projected VALUE of a P_p function, the piece that turns c u_h into the right-hand side the equilibrator needs for
+// an operator with a reaction term (rhs = Pi_d f - c_T Pi_d u_h):
+//   out[r][c][n] = cell_coeff[c] sum_i PV<p,d>[n][i] u[r][cell_dofs[c][i]]
+// ascending i, every product rounded on its own (a caller's `op` with permuted columns therefore gives other last bits:
+// the statement is the ascending sum).  The launch shape, the staging through LDS and the index check are those of
+// k_primal_flux; a row has nd_d values.
+template <int P, int D>
+struct ValueOp
+{
+  double v[nd_of(D) * nd_of(P)]; // PV[n][i]
+};
+
+template <int P, int D>
+__global__ void __launch_bounds__(PF_THREADS)
+k_primal_value(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __restrict__ cell_dofs,
+               const double* __restrict__ u, const double* __restrict__ coeff, const ValueOp<P, D> op,
+               double* __restrict__ out)
+{
+#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
+  constexpr int NP = nd_of(P), ND = nd_of(D), ROW = ND, S = ROW | 1;
+  constexpr int NBUF = (PF_THREADS * S > (PF_THREADS * NP + 1) / 2) ? PF_THREADS * S : (PF_THREADS * NP + 1) / 2;
+  __shared__ double sPV[ND * NP];
+  __shared__ double sbuf[NBUF]; // first the index rows of the workgroup, then its output rows
+  const int t = threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * PF_THREADS;
+  const int nloc = (ncells - base < PF_THREADS) ? (int)(ncells - base) : PF_THREADS;
+  const bool active = t < nloc;
+  for (int i = t; i < ND * NP; i += PF_THREADS)
+    sPV[i] = op.v[i];
+  int32_t* sidx = reinterpret_cast<int32_t*>(sbuf);
+  const int32_t* rows = cell_dofs + base * NP;
+  for (int e = t; e < nloc * NP; e += PF_THREADS)
+    sidx[e] = rows[e];
+  __syncthreads();
+  int32_t idx[NP];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < NP; ++i)
+  {
+    idx[i] = active ? sidx[t * NP + i] : 0;
+    ok = ok && idx[i] >= 0 && (int64_t)idx[i] < ndofs;
+  }
+  const bool scaled = coeff != nullptr;
+  const double kap = (active && scaled) ? coeff[base + t] : 1.0;
+  const double bad = __longlong_as_double(0x7ff8000000000000ll);
+  __syncthreads(); // the index rows are in registers: sbuf takes the output rows
+  for (int r = 0; r < nrhs; ++r)
+  {
+    if (active)
+    {
+      const double* ur = u + (int64_t)r * ndofs;
+      double uu[NP];
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+        uu[i] = ok ? ur[idx[i]] : 0.0;
+#pragma unroll
+      for (int n = 0; n < ND; ++n)
+      {
+        double v = sPV[n * NP] * uu[0];
+#pragma unroll
+        for (int i = 1; i < NP; ++i)
+          v = v + sPV[n * NP + i] * uu[i];
+        if (scaled)
+          v = kap * v;
+        sbuf[t * S + n] = ok ? v : bad;
+      }
+    }
+    __syncthreads();
+    double* o = out + ((int64_t)r * ncells + base) * ROW;
+    for (int e = t; e < nloc * ROW; e += PF_THREADS)
+      o[e] = sbuf[(e / ROW) * S + (e % ROW)];
+    __syncthreads();
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------
 template <int P, int D>
 static void builtin_table(double* out)
@@ -348,9 +423,125 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
   return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
 }
 
+// ---- eqlb_primal_value_dg ---------------------------------------------------------------------------------------------
+template <int P, int D>
+static int value_table_pd(double* out)
+{
+  using T = eqlb_tables::Value<P, D>;
+  static_assert(T::NP == nd_of(P) && T::ND == nd_of(D), "table shape");
+  for (int i = 0; i < T::ND * T::NP; ++i)
+    out[i] = T::PV[i];
+  return T::ND * T::NP;
+}
+
+template <int P, int D>
+static hipError_t launch_value_pd(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs, const double* u,
+                                  const double* coeff, const double* op, double* out, hipStream_t stream)
+{
+  ValueOp<P, D> tab;
+  if (op)
+    std::memcpy(tab.v, op, sizeof(tab.v));
+  else
+    value_table_pd<P, D>(tab.v);
+  const unsigned grid = (unsigned)(((int64_t)ncells + PF_THREADS - 1) / PF_THREADS);
+  hipLaunchKernelGGL((k_primal_value<P, D>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs, cell_dofs, u,
+                     coeff, tab, out);
+  return hipGetLastError();
+}
+
+// f<P, D>(args...) for the runtime degrees p in 1 ... 4, d in 0 ... 3
+#define EQLB_VALUE_DISPATCH(F, p, d, ...)                                                                              \
+  [&] {                                                                                                                \
+    switch ((p)*4 + (d))                                                                                               \
+    {                                                                                                                  \
+    case 4: return F<1, 0>(__VA_ARGS__);                                                                               \
+    case 5: return F<1, 1>(__VA_ARGS__);                                                                               \
+    case 6: return F<1, 2>(__VA_ARGS__);                                                                               \
+    case 7: return F<1, 3>(__VA_ARGS__);                                                                               \
+    case 8: return F<2, 0>(__VA_ARGS__);                                                                               \
+    case 9: return F<2, 1>(__VA_ARGS__);                                                                               \
+    case 10: return F<2, 2>(__VA_ARGS__);                                                                              \
+    case 11: return F<2, 3>(__VA_ARGS__);                                                                              \
+    case 12: return F<3, 0>(__VA_ARGS__);                                                                              \
+    case 13: return F<3, 1>(__VA_ARGS__);                                                                              \
+    case 14: return F<3, 2>(__VA_ARGS__);                                                                              \
+    case 15: return F<3, 3>(__VA_ARGS__);                                                                              \
+    case 16: return F<4, 0>(__VA_ARGS__);                                                                              \
+    case 17: return F<4, 1>(__VA_ARGS__);                                                                              \
+    case 18: return F<4, 2>(__VA_ARGS__);                                                                              \
+    default: return F<4, 3>(__VA_ARGS__);                                                                              \
+    }                                                                                                                  \
+  }()
+
+// all pointers but op DEVICE; enqueues on stream
+static hipError_t launch_primal_value(int p, int d, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
+                                      const double* u, const double* coeff, const double* op, double* out,
+                                      hipStream_t stream)
+{
+  return EQLB_VALUE_DISPATCH(launch_value_pd, p, d, ncells, nrhs, ndofs, cell_dofs, u, coeff, op, out, stream);
+}
+
+static int primal_value_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32_t d, int32_t nrhs,
+                             const int32_t* cell_dofs, int64_t ndofs, const double* u, const double* coeff,
+                             const double* op, double* value_dg, int32_t memspace, void* stream_)
+{
+  if (p < 1 || p > PF_PMAX || d < 0 || d > PF_DMAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degrees p = %d, degree_dg = %d outside 1 ... 4, 0 ... 3", who, (int)p,
+                (int)d);
+  if (nrhs < 1)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nrhs = %d", who, (int)nrhs);
+  if (!mesh || !cell_dofs || !u || !value_dg || ndofs < 1 || ndofs > INT32_MAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid argument", who);
+  EQLB_TRY(check_memspace(who, memspace));
+  const int np = nd_of(p), nd = nd_of(d);
+  const int32_t ncells = mesh->m.ncells;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (memspace == EQLB_MEM_DEVICE)
+  {
+    const hipError_t e = launch_primal_value(p, d, ncells, nrhs, ndofs, cell_dofs, u, coeff, op, value_dg, stream);
+    return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+  }
+  // host memory: bad tables are caught here, before anything is launched
+  const size_t nidx = (size_t)ncells * np;
+  for (size_t i = 0; i < nidx; ++i)
+    if (cell_dofs[i] < 0 || (int64_t)cell_dofs[i] >= ndofs)
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_dofs[%lld][%d] = %d outside [0, %lld)", who,
+                  (long long)(i / np), (int)(i % np), (int)cell_dofs[i], (long long)ndofs);
+  HostCall s;
+  const auto d_idx = s.in(cell_dofs, nidx);
+  const auto d_u = s.in(u, (size_t)ndofs * nrhs), d_c = s.in(coeff, (size_t)ncells);
+  const auto d_out = s.out(value_dg, (size_t)nrhs * ncells * nd);
+  if (s.upload(stream) != hipSuccess)
+    return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
+  s.note(launch_primal_value(p, d, ncells, nrhs, ndofs, d_idx, d_u, d_c, op, d_out, stream));
+  const hipError_t e = s.finish(stream);
+  return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+}
+
 } // namespace eqlb
 
 extern "C" {
+
+int eqlb_primal_value_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
+                         int64_t ndofs, const double* u, const double* cell_coeff, const double* op, double* value_dg,
+                         int32_t memspace, void* stream)
+{
+  return eqlb::primal_value_call("eqlb_primal_value_dg", mesh, p, degree_dg, nrhs, cell_dofs, ndofs, u, cell_coeff, op,
+                                 value_dg, memspace, stream);
+}
+
+int eqlb_get_value_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity)
+{
+  using namespace eqlb;
+  if (!out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_value_table: null output");
+  if (p < 1 || p > PF_PMAX || degree_dg < 0 || degree_dg > PF_DMAX)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_value_table: degrees p = %d, degree_dg = %d outside 1 ... 4, 0 ... 3",
+                (int)p, (int)degree_dg);
+  if (capacity < nd_of(degree_dg) * nd_of(p))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_value_table: capacity too small");
+  return EQLB_VALUE_DISPATCH(value_table_pd, p, degree_dg, out);
+}
 
 int eqlb_primal_flux_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
                         int64_t ndofs, const double* u, const double* cell_coeff, const double* op, double* flux_dg,

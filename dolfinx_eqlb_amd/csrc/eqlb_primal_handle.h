@@ -20,12 +20,21 @@
 #include "eqlb_primal_common.h"
 
 #include <climits>
+#include <cmath>
 #include <memory>
 
 namespace eqlb
 {
 namespace
 {
+// the reaction term of a cell kernel (include/eqlb.h): c_T = cell_c[cell] where given, else the scalar c.  A kernel
+// argument of its own, which the kernels without the term do not take.
+struct ReactArgs
+{
+  const double* cell_c = nullptr; // [ncells] or nullptr
+  double c = 0.0;
+};
+
 // what eqlb_primal_t and eqlb_elasticity_t share; everything but the grown work space is carved out of one allocation at
 // create
 template <int BS, int MAXC>
@@ -47,7 +56,18 @@ struct SolverHandle
   // the work space for 2 ... max_cols columns (wide.R of them): grown by the first call that needs it, then reused
   DevBuf<char> wide_mem;
   PcgWork wide{};
+  // the reaction term (solver_set_reaction): off as created.  The cell array is allocated by the first call that
+  // brings one and kept; react_cell says whether the kernels read it or the scalar
+  bool has_react = false, react_cell = false;
+  double react_c = 0.0;
+  DevBuf<double> react;
 };
+
+template <class H>
+ReactArgs react_args(const H& h)
+{
+  return ReactArgs{h.react_cell ? h.react.get() : nullptr, h.react_c};
+}
 
 constexpr int STATUS_WORDS = 4;
 
@@ -338,6 +358,43 @@ int solver_set_dirichlet(const char* who, H* h, const int32_t (&nlist)[H::bs], c
       s.note(hipGetLastError());
     }
   HIP_TRY(s.finish(stream));
+  return EQLB_OK;
+}
+
+// c_T = cell_c [ncells] in `memspace` where given, else the scalar c; c == 0 without an array switches the term off.  The
+// diagonal of the handle is formed again in place on the stream.
+template <class H>
+int solver_set_reaction(const char* who, H* h, double c, const double* cell_c, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  if (!cell_c && !(c >= 0.0 && std::isfinite(c)))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: c = %g is negative, NaN or infinite", who, c);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t nc = (size_t)h->space.ncells;
+  if (cell_c && host)
+    for (size_t i = 0; i < nc; ++i)
+      if (!(cell_c[i] >= 0.0 && std::isfinite(cell_c[i])))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_c[%lld] = %g is negative, NaN or infinite", who, (long long)i,
+                    cell_c[i]);
+  if (cell_c)
+  {
+    if (!h->react.get())
+    {
+      const hipError_t e = h->react.alloc_raw(nc);
+      if (e != hipSuccess)
+        return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed: %s", who, hipGetErrorString(e));
+    }
+    HIP_TRY(hipMemcpyAsync(h->react.get(), cell_c, nc * sizeof(double),
+                           host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+  }
+  h->react_cell = cell_c != nullptr;
+  h->react_c = cell_c ? 0.0 : c;
+  h->has_react = cell_c != nullptr || c != 0.0;
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (host)
+    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)
   return EQLB_OK;
 }
 

@@ -60,172 +60,50 @@ struct CellArgs
 // order.  With R > 1 the R rows of a cell stay in registers (R nd_p solution values, R nd_p results) and go out column
 // by column through the one sbuf, so the LDS footprint does not depend on R; with R = 1 the row goes straight to sbuf.
 // Columns that do not run (ManyCols) are neither read nor written.  Diagonal and load know one column.
-template <int P, int MODE, int D, int R>
-__global__ void __launch_bounds__(PS_THREADS) k_primal_cell(const CellArgs a, const ManyCols cols, int64_t ustride,
-                                                            int64_t ystride)
-{
-#pragma clang fp contract(off) // the statement rounds every product and every sum on its own
-  constexpr int NP = nd_of(P), ND = nd_of(D), S = NP | 1;
-  constexpr int NTAB = (MODE == CELL_LOAD) ? NP * ND : 3 * NP * NP;
-  static_assert(eqlb_tables::Stiff<P>::ND == NP && eqlb_tables::Load<P, D>::NP == NP && eqlb_tables::Load<P, D>::ND == ND,
-                "table shape");
-  static_assert(R >= 1 && R <= MANY_R && (R == 1 || MODE == CELL_OPERATOR), "columns for the operator only");
-  __shared__ double sT[NTAB];
-  __shared__ double sbuf[PS_THREADS * S]; // first the index rows of the workgroup, then its output rows, a column at a time
-  const uint32_t live = cols_live<R>(cols);
-  if (!live)
-    return;
-  const int t = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * PS_THREADS;
-  const int nloc = (a.ncells - base < PS_THREADS) ? (int)(a.ncells - base) : PS_THREADS;
-  const bool active = t < nloc;
-  for (int i = t; i < NTAB; i += PS_THREADS)
-  {
-    if constexpr (MODE == CELL_LOAD)
-      sT[i] = eqlb_tables::Load<P, D>::LD[i];
-    else
-      sT[i] = eqlb_tables::Stiff<P>::ST[i];
-  }
-  [[maybe_unused]] int32_t idx[NP];
-  if constexpr (MODE == CELL_OPERATOR)
-  {
-    int32_t* sidx = reinterpret_cast<int32_t*>(sbuf);
-    const int32_t* rows = a.cell_dofs + base * NP;
-    for (int e = t; e < nloc * NP; e += PS_THREADS)
-      sidx[e] = rows[e];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-      idx[i] = active ? sidx[t * NP + i] : 0;
-  }
-  __syncthreads(); // the table is staged; the index rows are in registers: sbuf takes the output rows
-  [[maybe_unused]] double out[R > 1 ? R : 1][R > 1 ? NP : 1];
-  if constexpr (R > 1)
-  {
-#pragma unroll
-    for (int c = 0; c < R; ++c)
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-        out[c][i] = 0.0;
-  }
-  if (active)
-  {
-    const double2* Jp = reinterpret_cast<const double2*>(a.cellJ + 4 * (base + t));
-    const double2 r0 = Jp[0], r1 = Jp[1]; // J00 J01 | J10 J11
-    const double det = r0.x * r1.y - r0.y * r1.x;
-    const double adet = fabs(det);
-    if constexpr (MODE == CELL_LOAD)
-    {
-      const double* f = a.u + (base + t) * ND;
-      double fv[ND];
-#pragma unroll
-      for (int n = 0; n < ND; ++n)
-        fv[n] = f[n];
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-      {
-        double s = sT[i * ND] * fv[0];
-#pragma unroll
-        for (int n = 1; n < ND; ++n)
-          s = s + sT[i * ND + n] * fv[n];
-        sbuf[t * S + i] = adet * s;
-      }
-    }
-    else
-    {
-      const double idet = 1.0 / det;
-      const double K00 = r1.y * idet, K01 = -r0.y * idet, K10 = -r1.x * idet, K11 = r0.x * idet;
-      const double C00 = K00 * K00 + K01 * K01, C01 = K00 * K10 + K01 * K11, C11 = K10 * K10 + K11 * K11;
-      const double w = (a.coeff ? a.coeff[base + t] : 1.0) * adet;
-      [[maybe_unused]] double uu[R][NP];
-      if constexpr (MODE == CELL_OPERATOR)
-      {
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-        {
-          const bool zero = a.only_fixed && !a.fixed[idx[i]];
-#pragma unroll
-          for (int c = 0; c < R; ++c)
-          {
-            const double v = col_on<R>(live, c) ? a.u[c * ustride + idx[i]] : 0.0;
-            uu[c][i] = zero ? 0.0 : v;
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-      {
-        double tm[R][3];
-#pragma unroll
-        for (int m = 0; m < 3; ++m)
-        {
-          const double* row = sT + (m * NP + i) * NP;
-          if constexpr (MODE == CELL_DIAGONAL)
-            tm[0][m] = row[i];
-          else
-          {
-            double s[R];
-            {
-              const double e = row[0];
-#pragma unroll
-              for (int c = 0; c < R; ++c)
-                s[c] = e * uu[c][0];
-            }
-#pragma unroll
-            for (int j = 1; j < NP; ++j)
-            {
-              const double e = row[j];
-#pragma unroll
-              for (int c = 0; c < R; ++c)
-                s[c] = s[c] + e * uu[c][j];
-            }
-#pragma unroll
-            for (int c = 0; c < R; ++c)
-              tm[c][m] = s[c];
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-        {
-          const double v = w * ((C00 * tm[c][0] + C01 * tm[c][1]) + C11 * tm[c][2]);
-          if constexpr (R == 1)
-            sbuf[t * S + i] = v;
-          else
-            out[c][i] = v;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < R; ++c)
-  {
-    if (!col_on<R>(live, c)) // (the same in every thread)
-      continue;
-    if constexpr (R > 1)
-    {
-      if (active)
-      {
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-          sbuf[t * S + i] = out[c][i];
-      }
-    }
-    __syncthreads();
-    double* o = a.yloc + c * ystride + base * NP;
-    for (int e = t; e < nloc * NP; e += PS_THREADS)
-      o[e] = sbuf[(e / NP) * S + (e % NP)];
-    if constexpr (R > 1)
-      __syncthreads(); // (the next column overwrites sbuf)
-  }
-}
+// RX adds the reaction term (include/eqlb.h): Mass<P> is staged behind the stiffness tables, an entry is read once and
+// multiplied into the R sums as the stiffness entries are, and wm m[i] (diagonal: wm Mass[i][i]) is added to the value
+// formed without the term.  The reaction variant is a kernel of its own, k_primal_cell_react, from the same source
+// (eqlb_primal_cell.inc), so that a handle without the term launches the instantiations - symbols, arguments and code -
+// it launched before the term existed.
+#define EQLB_CELL_REACT 0
+#include "eqlb_primal_cell.inc"
+#undef EQLB_CELL_REACT
+#define EQLB_CELL_REACT 1
+#include "eqlb_primal_cell.inc"
+#undef EQLB_CELL_REACT
 
 // ---- host side ------------------------------------------------------------------------------------------------
 // the launch on the columns of c: the load by its DG degree d, the operator by its column count, the diagonal as it is
 template <int P, int MODE>
 hipError_t launch_cell_p(int d, const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride,
-                         hipStream_t stream)
+                         const ReactArgs* rx, hipStream_t stream)
 {
   const dim3 grid(grid_of(a.ncells, PS_THREADS)), block(PS_THREADS);
+  if constexpr (MODE != CELL_LOAD)
+    if (rx) // the variants with the reaction term; without it the launches below, as before the term existed
+    {
+#define EQLB_CELL_RX(RR)                                                                                               \
+  hipLaunchKernelGGL((k_primal_cell_react<P, MODE, 0, RR>), grid, block, 0, stream, a, c, ustride, ystride, *rx)
+      if constexpr (MODE == CELL_DIAGONAL)
+        EQLB_CELL_RX(1);
+      else
+        switch (c.R)
+        {
+        case 1:
+          EQLB_CELL_RX(1);
+          break;
+        case 2:
+          EQLB_CELL_RX(2);
+          break;
+        case 3:
+          EQLB_CELL_RX(3);
+          break;
+        default:
+          EQLB_CELL_RX(4);
+        }
+#undef EQLB_CELL_RX
+      return hipGetLastError();
+    }
 #define EQLB_CELL(DD, RR)                                                                                              \
   hipLaunchKernelGGL((k_primal_cell<P, MODE, DD, RR>), grid, block, 0, stream, a, c, ustride, ystride)
   if constexpr (MODE == CELL_LOAD)
@@ -266,18 +144,18 @@ hipError_t launch_cell_p(int d, const CellArgs& a, const ManyCols& c, int64_t us
 
 template <int MODE>
 hipError_t launch_cell(int p, int d, const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride,
-                       hipStream_t stream)
+                       const ReactArgs* rx, hipStream_t stream)
 {
   switch (p)
   {
   case 1:
-    return launch_cell_p<1, MODE>(d, a, c, ustride, ystride, stream);
+    return launch_cell_p<1, MODE>(d, a, c, ustride, ystride, rx, stream);
   case 2:
-    return launch_cell_p<2, MODE>(d, a, c, ustride, ystride, stream);
+    return launch_cell_p<2, MODE>(d, a, c, ustride, ystride, rx, stream);
   case 3:
-    return launch_cell_p<3, MODE>(d, a, c, ustride, ystride, stream);
+    return launch_cell_p<3, MODE>(d, a, c, ustride, ystride, rx, stream);
   default:
-    return launch_cell_p<4, MODE>(d, a, c, ustride, ystride, stream);
+    return launch_cell_p<4, MODE>(d, a, c, ustride, ystride, rx, stream);
   }
 }
 
@@ -296,7 +174,8 @@ hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const dou
   a.fixed = h.fixed;
   a.only_fixed = only_fixed ? 1 : 0;
   a.yloc = work_of(h, c.R).yloc;
-  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, stream);
+  const ReactArgs rx = react_args(h);
+  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, h.has_react ? &rx : nullptr, stream);
 }
 } // namespace
 
@@ -316,6 +195,22 @@ int eqlb_get_stiffness_table(int32_t p, double* out, int32_t capacity)
   const double* t = p == 1 ? eqlb_tables::Stiff<1>::ST
                            : p == 2 ? eqlb_tables::Stiff<2>::ST
                                     : p == 3 ? eqlb_tables::Stiff<3>::ST : eqlb_tables::Stiff<4>::ST;
+  for (int i = 0; i < n; ++i)
+    out[i] = t[i];
+  return n;
+}
+
+int eqlb_get_mass_table(int32_t p, double* out, int32_t capacity)
+{
+  using namespace eqlb;
+  if (p < 1 || p > PS_PMAX || !out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_mass_table: p = %d outside 1 ... 4, or null output", (int)p);
+  const int n = nd_of(p) * nd_of(p);
+  if (capacity < n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_mass_table: capacity too small");
+  const double* t = p == 1 ? eqlb_tables::Mass<1>::MS
+                           : p == 2 ? eqlb_tables::Mass<2>::MS
+                                    : p == 3 ? eqlb_tables::Mass<3>::MS : eqlb_tables::Mass<4>::MS;
   for (int i = 0; i < n; ++i)
     out[i] = t[i];
   return n;
@@ -373,6 +268,13 @@ try
   const int32_t nlists[1] = {nlist};
   const int32_t* const lists[1] = {facets};
   return eqlb::solver_set_dirichlet("eqlb_primal_set_dirichlet", h, nlists, lists, memspace, stream_);
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_set_reaction(eqlb_primal_t* h, double c, const double* cell_c, int32_t memspace, void* stream_)
+try
+{
+  return eqlb::solver_set_reaction("eqlb_primal_set_reaction", h, c, cell_c, memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -338,6 +338,18 @@ struct PrimalPoisson
     check(eqlb_primal_set_dirichlet(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, EQLB_MEM_HOST,
                                     nullptr));
   }
+  // + c u: cell_c [ncells] where given, else the scalar c; c == 0 without an array switches the term off
+  void set_reaction(double c, py::object cell_c)
+  {
+    carray<double> kc;
+    if (!cell_c.is_none())
+    {
+      kc = cell_c.cast<carray<double>>();
+      if (kc.size() != mesh->ncells)
+        throw std::runtime_error("PrimalPoisson.set_reaction: cell_c [ncells] expected");
+    }
+    check(eqlb_primal_set_reaction(h, c, cell_c.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
+  }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
     if (degree_dg >= 0 && degree_dg <= 3
@@ -456,6 +468,18 @@ struct PrimalElasticity
     check(eqlb_elasticity_set_dirichlet(h, (int32_t)facets0.size(), facets0.size() ? facets0.data() : nullptr,
                                         (int32_t)facets1.size(), facets1.size() ? facets1.data() : nullptr,
                                         EQLB_MEM_HOST, nullptr));
+  }
+  // + c u: cell_c [ncells] where given, else the scalar c; c == 0 without an array switches the term off
+  void set_reaction(double c, py::object cell_c)
+  {
+    carray<double> kc;
+    if (!cell_c.is_none())
+    {
+      kc = cell_c.cast<carray<double>>();
+      if (kc.size() != mesh->ncells)
+        throw std::runtime_error("PrimalElasticity.set_reaction: cell_c [ncells] expected");
+    }
+    check(eqlb_elasticity_set_reaction(h, c, cell_c.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
   }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
@@ -1518,6 +1542,9 @@ PYBIND11_MODULE(_cpp, m)
            py::arg("coeff") = py::none())
       .def("set_dirichlet", &PrimalPoisson::set_dirichlet, py::arg("facets"),
            "fixed are the vertex and facet DOFs of the listed facets; a repeated call replaces the mask")
+      .def("set_reaction", &PrimalPoisson::set_reaction, py::arg("c") = 0.0, py::arg("cell_c") = py::none(),
+           "the operator gains + c u: cell_c [ncells] where given, else the scalar; c = 0 without an array switches "
+           "the term off; Multilevel.set_coarse(True) has to be called again afterwards")
       .def("load", &PrimalPoisson::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
            "b [ndofs] from DG_d nodal values rhs_dg [ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalPoisson::apply, py::arg("u"), py::arg("masked") = false, "y = A u; masked: 0 on the fixed rows")
@@ -1544,6 +1571,9 @@ PYBIND11_MODULE(_cpp, m)
       .def("set_dirichlet", &PrimalElasticity::set_dirichlet, py::arg("facets0"), py::arg("facets1"),
            "fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r; a repeated "
            "call replaces the mask")
+      .def("set_reaction", &PrimalElasticity::set_reaction, py::arg("c") = 0.0, py::arg("cell_c") = py::none(),
+           "the operator gains + c u: cell_c [ncells] where given, else the scalar; c = 0 without an array switches "
+           "the term off; Multilevel.set_coarse(True) has to be called again afterwards")
       .def("load", &PrimalElasticity::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
            "b [2 ndofs] from DG_d nodal values rhs_dg [2, ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalElasticity::apply, py::arg("u"), py::arg("masked") = false,
@@ -1722,6 +1752,32 @@ PYBIND11_MODULE(_cpp, m)
       .def("bytes", &HaloExchange::bytes, "(bytes sent, bytes received) per reduction");
   m.def("set_stream", [](uintptr_t s) { g_stream = reinterpret_cast<void*>(s); }, py::arg("stream"),
         "hipStream_t used by calls on device-memory Functions (0: default stream)");
+  m.def(
+      "primal_value_dg",
+      [](std::shared_ptr<Mesh> mesh, int p, int degree_dg, carray<int32_t> cell_dofs, darray u, py::object coeff,
+         py::object op) {
+        if (p < 1 || p > 4 || degree_dg < 0 || degree_dg > 3)
+          throw std::runtime_error("primal_value_dg: degrees outside 1 ... 4, 0 ... 3");
+        const py::ssize_t ndp = (p + 1) * (p + 2) / 2, nd = (degree_dg + 1) * (degree_dg + 2) / 2;
+        const py::ssize_t nrhs = u.ndim() == 2 ? u.shape(0) : 1;
+        carray<double> kc, t;
+        if (!coeff.is_none())
+          kc = coeff.cast<carray<double>>();
+        if (!op.is_none())
+          t = op.cast<carray<double>>();
+        if (cell_dofs.size() != (py::ssize_t)mesh->ncells * ndp || u.size() == 0 || u.size() % nrhs
+            || (!coeff.is_none() && kc.size() != mesh->ncells) || (!op.is_none() && t.size() != nd * ndp))
+          throw std::runtime_error("primal_value_dg: Input sizes does not match");
+        darray out({nrhs, (py::ssize_t)mesh->ncells * nd});
+        check(eqlb_primal_value_dg(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs, u.data(),
+                                   coeff.is_none() ? nullptr : kc.data(), op.is_none() ? nullptr : t.data(),
+                                   out.mutable_data(), EQLB_MEM_HOST, nullptr));
+        return out;
+      },
+      py::arg("mesh"), py::arg("p"), py::arg("degree_dg"), py::arg("cell_dofs"), py::arg("u"),
+      py::arg("coeff") = py::none(), py::arg("op") = py::none(),
+      "[nrhs, ncells*nd_d]: the DG_d DOFs of coeff Pi_d u_h for u_h in P_p (eqlb_primal_value_dg); coeff [ncells] or "
+      "None, op [nd_d, nd_p] replaces the built-in table");
   m.def("device_count", &eqlb_device_count);
   m.def("synchronize_and_check", [](std::shared_ptr<BoundaryData> bd) {
     if (bd->se)

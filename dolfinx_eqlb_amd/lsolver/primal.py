@@ -23,6 +23,24 @@ the diagonal and the residual bit for bit.
   diagonal  w ((C00 S0[i][i] + C01 S1[i][i]) + C11 S2[i][i]) through the same owner sum
   residual  r = b - A u, 0 on the rows where `fixed` is set
 
+THE REACTION TERM (set_reaction; eqlb_primal_set_reaction / eqlb_elasticity_set_reaction): the operator becomes
+-div(kappa grad u) + c u, or -div(2 eps(u) + pi_1 div(u) I) + c u, with c_T >= 0 per cell, one scalar or a cell-wise
+array in the pi_1 / cell_pi1 convention.  New table Mass<p> [nd_p][nd_p] = int phi_i phi_j on the reference triangle,
+exact Fractions, each rounded once.  Per cell
+  wm        = c_T |det|
+  m^s[i]    = sum_j Mass[i][j] u_s[j], ascending j, every product rounded on its own, no fused multiply-add
+  Poisson   : y_loc[c][i]    = (the value of the rule above) + wm m[i]
+  elasticity: y_loc[c][i][r] = (the value of the rule below) + wm m^r[i]
+  diagonal  : (the value above / below) + wm Mass[i][i], for both units and both components
+one product and one addition on top of the value formed without the term; everything before that addition, the load,
+the owner sum, the mask, the residual, the reference norm and pcg are unchanged.  c = 0 without an array switches the
+term off: the operator is then the one of a fresh object, bit for bit.
+
+value_dg states eqlb_primal_value_dg, the piece that turns c u_h into the right-hand side the equilibrator needs
+(rhs = Pi_d f - c_T Pi_d u_h): out[r][c][n] = coeff[c] sum_i PV<p,d>[n][i] u[r][cell_dofs[c][i]], ascending i, every
+product rounded on its own, with PV<p,d> [nd_d][nd_p] the DG_d nodal values of the L2 projection of phi_i onto P_d:
+interpolation for d >= p, Mass<d>^-1 Load<p,d>^T in Fractions below.
+
 Every statement can return the sum of the absolute values of its terms (return_abs), so that a test bounds the
 comparison with an independently rounded computation by terms * 2^-53 * abs-sum.
 
@@ -91,6 +109,81 @@ def cross_table_exact(p):
     dx, dy = [P.ddx(b) for b in basis], [P.ddy(b) for b in basis]
     n = len(basis)
     return tuple(tuple(P.integrate_triangle(P.mul(dx[i], dy[j])) for j in range(n)) for i in range(n))
+
+
+@lru_cache(maxsize=None)
+def mass_table_exact(p):
+    """Mass [nd_p][nd_p] Fractions: int phi_i phi_j on the reference triangle, 0 <= p <= 4 (the device knows p >= 1;
+    p = 0 serves the projection identity of value_table_exact)."""
+    if p < 0 or p > 4:
+        raise ValueError(f"mass_table_exact: p = {p} outside 0 ... 4")
+    basis = Lagrange(p).basis
+    n = len(basis)
+    return tuple(tuple(P.integrate_triangle(P.mul(basis[i], basis[j])) for j in range(n)) for i in range(n))
+
+
+def mass_table(p):
+    """The table [nd_p, nd_p] as doubles, each entry rounded once."""
+    if p < 1:
+        raise ValueError(f"mass_table: p = {p} outside 1 ... 4")
+    return np.array([[float(v) for v in row] for row in mass_table_exact(p)])
+
+
+@lru_cache(maxsize=None)
+def value_table_exact(p, d):
+    """PV [nd_d][nd_p] Fractions: DG_d nodal value n of the L2 projection of phi_i (the basis of P_p) onto P_d.  For
+    d >= p that is the value of phi_i at node n of DG_d; below it is Mass<d>^-1 Load<p,d>^T, whose |det J| cancels on an
+    affine cell."""
+    if p < 1 or p > 4 or d < 0 or d > 3:
+        raise ValueError(f"value_table: p = {p}, d = {d} outside 1 ... 4, 0 ... 3")
+    phi, dg = Lagrange(p).basis, Lagrange(d)
+    if d >= p:
+        def at(q, x, y):
+            return sum((c * x ** a * y ** b for (a, b), c in q.items()), Fraction(0))
+        return tuple(tuple(at(q, *dg.nodes[n]) for q in phi) for n in range(dg.ndofs))
+    load = load_table_exact(p, d)
+    rhs = [[load[i][n] for i in range(len(phi))] for n in range(dg.ndofs)]
+    return tuple(tuple(row) for row in P.solve_exact([list(r) for r in mass_table_exact(d)], rhs))
+
+
+def value_table(p, d):
+    """The table [nd_d, nd_p] as doubles, each entry rounded once."""
+    return np.array([[float(v) for v in row] for row in value_table_exact(p, d)])
+
+
+def value_dg(p, degree_dg, cell_dofs, u, coeff=None, op=None, return_abs=False):
+    """The statement of eqlb_primal_value_dg: out [nrhs, ncells * nd_d] from u [nrhs, ndofs] (or [ndofs]), cell_dofs
+    [ncells, nd_p]; coeff [ncells] or None (no multiplication); op [nd_d, nd_p] replaces the built-in table."""
+    T = value_table(p, degree_dg) if op is None else np.asarray(op, dtype=np.float64).reshape(nd_of(degree_dg), nd_of(p))
+    cd = np.asarray(cell_dofs, dtype=np.int64).reshape(-1, nd_of(p))
+    uu = np.asarray(u, dtype=np.float64)
+    uu = uu.reshape(1, -1) if uu.ndim < 2 else uu
+    out, Ab = [], []
+    for r in range(uu.shape[0]):
+        v, A = _sum_products(T, uu[r][cd])
+        if coeff is not None:
+            k = np.asarray(coeff, dtype=np.float64).ravel()[:, None]
+            v, A = k * v, np.abs(k) * A
+        out.append(v.ravel())
+        Ab.append(A.ravel())
+    return (np.stack(out), np.stack(Ab)) if return_abs else np.stack(out)
+
+
+def reaction_coefficient(who, ncells, c=0.0, cell_c=None):
+    """c_T [ncells] of set_reaction, or None where the term is switched off (c == 0 without an array).  A coefficient
+    that is negative, NaN or infinite is refused, the cell named."""
+    if cell_c is None:
+        c = float(c)
+        if not (c >= 0.0 and np.isfinite(c)):
+            raise ValueError(f"{who}: c = {c} is negative, NaN or infinite")
+        return None if c == 0.0 else np.full(ncells, c)
+    cc = np.array(cell_c, dtype=np.float64).ravel()
+    if cc.size != ncells:
+        raise ValueError(f"{who}: cell_c [ncells] expected")
+    bad = np.nonzero(~((cc >= 0.0) & np.isfinite(cc)))[0]
+    if bad.size:
+        raise ValueError(f"{who}: cell_c[{int(bad[0])}] = {cc[bad[0]]} is negative, NaN or infinite")
+    return cc
 
 
 def cross_table(p):
@@ -195,6 +288,8 @@ class PoissonOperator:
             raise ValueError("PoissonOperator: coeff [ncells] expected")
         self.w = kappa * self.adet
         self.S = stiffness_table(p)
+        self.Mass = mass_table(p)
+        self.wm = None                        # c_T |det| [ncells]; None: no reaction term
         self.fixed = np.zeros(self.ndofs, dtype=bool)
         self._slots()
 
@@ -224,6 +319,19 @@ class PoissonOperator:
         """A repeated call replaces the mask."""
         self.fixed = dirichlet_mask(self.mesh, self.p, facets)
 
+    def set_reaction(self, c=0.0, cell_c=None):
+        """The operator gains + c u: c_T = cell_c [ncells] where given, else the scalar c on every cell.  c == 0 without
+        an array switches the term off; a repeated call replaces the coefficient."""
+        cc = reaction_coefficient("set_reaction", self.mesh.ncells, c, cell_c)
+        self.wm = None if cc is None else cc * self.adet
+
+    def _add_reaction(self, val, A, m, mA):
+        """val + wm m on [ncells, nd] (A: the same with absolute values, or None); unchanged without the term."""
+        if self.wm is None:
+            return val, A
+        wm = self.wm[:, None]
+        return val + wm * m, (None if A is None else A + wm * mA)
+
     # ---- the statements ----
     def _combine(self, t, w, A=None):
         """w ((C00 t0 + C01 t1) + C11 t2) on [3][ncells, nd]; with A the same with absolute values."""
@@ -238,6 +346,8 @@ class PoissonOperator:
         uc = np.asarray(u, dtype=np.float64)[self.cell_dofs]
         t, A = zip(*[_sum_products(self.S[m], uc) for m in range(3)])
         val, Ab = self._combine(t, self.w, A)
+        if self.wm is not None:
+            val, Ab = self._add_reaction(val, Ab, *_sum_products(self.Mass, uc))
         return (val, Ab) if return_abs else val
 
     def owner_sum(self, y_loc, return_abs=False):
@@ -291,6 +401,8 @@ class PoissonOperator:
         """The diagonal of the cell matrices through the owner sum."""
         t = [np.broadcast_to(np.diagonal(self.S[m])[None, :], (self.mesh.ncells, self.nd)) for m in range(3)]
         val, A = self._combine(t, self.w, [np.abs(x) for x in t])
+        md = np.broadcast_to(np.diagonal(self.Mass)[None, :], (self.mesh.ncells, self.nd))
+        val, A = self._add_reaction(val, A, md, md)
         d = self.owner_sum(val)
         return (d, self.owner_sum(A)) if return_abs else d
 
@@ -429,6 +541,8 @@ class ElasticityOperator(PoissonOperator):
         S = stiffness_table(p)
         C = cross_table(p)
         self.M = (S[0], C, np.ascontiguousarray(C.T), S[2])                     # M_00, M_01, M_10, M_11
+        self.Mass = mass_table(p)
+        self.wm = None
         self.fixed = np.zeros(2 * self.ndofs, dtype=bool)
         self._slots()
 
@@ -463,12 +577,19 @@ class ElasticityOperator(PoissonOperator):
         n = lambda s, a, b: D[s][a][b][1]   # noqa: E731
         y0 = w * (((v(0, 0, 0) + v(0, 1, 1)) + (v(0, 0, 0) + v(1, 1, 0))) + pi * (v(0, 0, 0) + v(1, 0, 1)))
         y1 = w * (((v(1, 0, 0) + v(1, 1, 1)) + (v(0, 0, 1) + v(1, 1, 1))) + pi * (v(0, 1, 0) + v(1, 1, 1)))
-        val = np.stack([y0, y1], axis=2)
+        ys = [y0, y1]
+        mm = [_sum_products(self.Mass, uc[:, :, r]) for r in range(2)] if self.wm is not None else None
+        if mm is not None:
+            ys = [self._add_reaction(ys[r], None, *mm[r])[0] for r in range(2)]
+        val = np.stack(ys, axis=2)
         if not return_abs:
             return val
         a0 = wa * (((n(0, 0, 0) + n(0, 1, 1)) + (n(0, 0, 0) + n(1, 1, 0))) + pa * (n(0, 0, 0) + n(1, 0, 1)))
         a1 = wa * (((n(1, 0, 0) + n(1, 1, 1)) + (n(0, 0, 1) + n(1, 1, 1))) + pa * (n(0, 1, 0) + n(1, 1, 1)))
-        return val, np.stack([a0, a1], axis=2)
+        ab = [a0, a1]
+        if mm is not None:
+            ab = [ab[r] + self.wm[:, None] * mm[r][1] for r in range(2)]
+        return val, np.stack(ab, axis=2)
 
     def owner_sum(self, y_loc, return_abs=False):
         """y [2 ndofs] from y_loc [ncells, nd, 2]: the scalar owner sum per component."""
@@ -501,6 +622,8 @@ class ElasticityOperator(PoissonOperator):
         w, pi = self.adet[:, None], self.pi[:, None]
         val = [w * (((D[0][0][0] + D[1][1][0]) + D[r][r][0]) + pi * D[r][r][0]) for r in range(2)]
         A = [np.abs(w) * (((D[0][0][1] + D[1][1][1]) + D[r][r][1]) + np.abs(pi) * D[r][r][1]) for r in range(2)]
+        md = np.broadcast_to(np.diagonal(self.Mass)[None, :], (self.mesh.ncells, self.nd))
+        val, A = zip(*[self._add_reaction(val[r], A[r], md, md) for r in range(2)])
         d = self.owner_sum(np.stack(val, axis=2))
         return (d, self.owner_sum(np.stack(A, axis=2))) if return_abs else d
 

@@ -44,6 +44,18 @@ class PrimalStress:
     row: int
 
 
+@dataclasses.dataclass
+class PrimalValue:
+    """coeff Pi_d u_h of a conforming P_p function as an entry of `data` of local_projection (bs = 1): u [ndofs],
+    cell_dofs [ncells, (p+1)(p+2)/2], coeff [ncells] or None (no multiplication).  Formed on the device from the vector
+    (cpp.primal_value_dg), without quadrature: with coeff = c_T the reaction part of the right-hand side an
+    equilibrator needs (rhs = Pi_d f - c_T Pi_d u_h), with coeff = 1 / tau the u_old / tau of an implicit time step."""
+    p: int
+    cell_dofs: typing.Any
+    u: typing.Any
+    coeff: typing.Any = None
+
+
 def _device_mesh(dmesh):
     """The cpp.DeviceMesh behind `dmesh` (made once per flat mesh container and kept on it)."""
     from .. import cpp
@@ -63,6 +75,10 @@ def _check_primal(mesh, bs, d):
     ndp = (d.p + 1) * (d.p + 2) // 2
     stress = isinstance(d, PrimalStress)
     usize = np.size(d.u)
+    if isinstance(d, PrimalValue):
+        if bs != 1 or np.size(d.cell_dofs) != mesh.ncells * ndp or usize == 0:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        return
     if (bs != 2 or np.size(d.cell_dofs) != mesh.ncells * ndp or usize == 0 or (stress and usize % 2)
             or (stress and d.row not in (0, 1))):
         raise RuntimeError("Local solver: Input sizes does not match")
@@ -71,6 +87,9 @@ def _check_primal(mesh, bs, d):
 def _project_primal(dmesh, degree, d):
     from .. import cpp
     dm = _device_mesh(dmesh)
+    if isinstance(d, PrimalValue):
+        return cpp.primal_value_dg(dm, d.p, degree, d.cell_dofs, np.asarray(d.u, dtype=np.float64).reshape(1, -1),
+                                   d.coeff)[0]
     if isinstance(d, PrimalStress):
         per_cell = np.ndim(d.pi_1) > 0
         out = cpp.primal_stress_dg(dm, d.p, degree, d.cell_dofs, d.u, 1.0 if per_cell else float(d.pi_1),
@@ -84,8 +103,9 @@ def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int 
                      quadrature_degree: typing.Optional[int] = None,
                      solver: str = "cholesky") -> typing.List[np.ndarray]:
     """Project every entry of `data` into DG_degree (block size bs); returns the DOF arrays
-    [ncells*nd*bs] (cell-major, x[bs*dof+cb]).  data[i]: callable(x, y), array [ncells, nq, bs], or a PrimalFlux /
-    PrimalStress (bs = 2: the flux or a stress row of a P_p solution, formed on the device from its DOFs).
+    [ncells*nd*bs] (cell-major, x[bs*dof+cb]).  data[i]: callable(x, y), array [ncells, nq, bs], a PrimalFlux /
+    PrimalStress (bs = 2: the flux or a stress row of a P_p solution, formed on the device from its DOFs), or a
+    PrimalValue (bs = 1: the projected value of a P_p function, times a cell-wise coefficient).
     `dmesh`: flat mesh container (or a `cpp.DeviceMesh` of one).  The solve runs through
     `local_solver_<solver>` of the compiled module (names of python/dolfinx_eqlb/wrappers.cpp:52-80):
     a = (u, v) on DG_degree, l_i = (f_i, v) given by the point values of f_i."""
@@ -95,7 +115,7 @@ def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int 
     qdeg = 2 * degree + 2 if quadrature_degree is None else quadrature_degree
     qp, qw = make_quadrature_triangle(qdeg)
     xq = None
-    is_primal = [isinstance(d, (PrimalFlux, PrimalStress)) for d in data]
+    is_primal = [isinstance(d, (PrimalFlux, PrimalStress, PrimalValue)) for d in data]
     for d, pr in zip(data, is_primal):
         if pr:
             _check_primal(mesh, bs, d)

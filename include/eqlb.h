@@ -371,6 +371,28 @@ int eqlb_primal_stress_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const
  * returns the number of doubles copied (<= capacity), or a negative error. */
 int eqlb_get_primal_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity);
 
+/* The projected VALUE of a conforming P_p function, formed on the device from its vector: the piece that turns c u_h
+ * into the right-hand side the equilibrator needs when the operator has a reaction term (eqlb_primal_set_reaction):
+ * the flux of -div(kappa grad u) + c u = f is equilibrated against rhs_dg = Pi_d f - c_T Pi_d u_h, and an implicit time
+ * step takes f + u_old / tau as its load through the same projection of u_old.
+ *   value_dg[r][c][n] = cell_coeff[c] sum_i PV<p,d>[n][i] u[r][cell_dofs[c][i]]
+ * the sum in ascending i, every product rounded on its own, no fused multiply-add; cell_coeff == NULL: no multiplication.
+ * PV<p,d> [nd_d][nd_p] holds the DG_d nodal values of the L2 projection of the basis function phi_i onto P_d: the
+ * interpolation for degree_dg >= p, Mass<d>^-1 Load<p,d>^T below (exact rationals, each rounded once,
+ * tools/gen_tables.py; the |det J| of an affine cell cancels).  1 <= p <= 4, 0 <= degree_dg <= 3, nrhs >= 1.
+ *   value_dg   [nrhs][ncells*nd_d]   OVERWRITTEN, in the layout of rhs_dg of eqlb_se_equilibrate and eqlb_primal_load
+ *   op         HOST, [nd_d][nd_p] row-major, or NULL: replaces the built-in PV<p,d> for a caller's own P_p basis, as op
+ *              of eqlb_primal_flux_dg does.  The sum stays the ascending one over the columns as the caller orders them.
+ * cell_dofs, u, the index checks (host memory space: refused before anything is launched; device memory space: the
+ * values of that cell are NaN, nothing is read out of range), the memory spaces and the launch (one thread per cell, one
+ * kernel on `stream`, nothing waits in device memory space) as eqlb_primal_flux_dg.  dolfinx_eqlb_amd/lsolver/primal.py
+ * (value_dg) states it in numpy; the device gives its bits.
+ * eqlb_get_value_table: the built-in PV<p,d>, host only: the number of doubles copied, or a negative error. */
+int eqlb_primal_value_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
+                         int64_t ndofs, const double* u, const double* cell_coeff, const double* op, double* value_dg,
+                         int32_t memspace, void* stream);
+int eqlb_get_value_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity);
+
 /* Largest number of cells of a patch of the mesh (OrientedPatch::ncells_max). */
 int32_t eqlb_mesh_max_patch_cells(const eqlb_mesh_t* mesh);
 
@@ -873,6 +895,33 @@ void eqlb_refine_destroy(eqlb_refine_t* plan);
  *   eqlb_get_stiffness_table  Stiff<p> [3][nd_p][nd_p]: S0 = int dX phi_i dX phi_j, S1 = int (dX phi_i dY phi_j +
  *                             dY phi_i dX phi_j), S2 = int dY phi_i dY phi_j on the reference triangle
  *   eqlb_get_load_table       Load<p,d> [nd_p][nd_d] = int phi_i chi_n, chi_n the DG_d nodal basis of rhs_dg
+ *   eqlb_get_mass_table       Mass<p> [nd_p][nd_p] = int phi_i phi_j (the reaction term below)
+ *
+ * THE REACTION TERM: eqlb_primal_set_reaction / eqlb_elasticity_set_reaction turn the operator into
+ * -div(kappa grad u) + c u, or -div(2 eps(u) + pi_1 div(u) I) + c u: an implicit step of the heat equation (c = 1 / tau,
+ * load f + u_old / tau through eqlb_primal_value_dg), reaction-diffusion, an implicit step of elastodynamics
+ * (c = rho / tau^2).  With c_T >= 0 the coefficient of the cell - cell_c[c] where the array is given, else the scalar c,
+ * the pi_1 / cell_pi1 convention - and Mass<p> the table above (exact Fractions, each rounded once):
+ *   wm        = c_T |det J|
+ *   m^s[i]    = sum_j Mass[i][j] u_s[j]      ascending j, every product rounded on its own, no fused multiply-add
+ *   Poisson   : y_loc[c][i]    = (the value of the rule above) + wm m[i]
+ *   elasticity: y_loc[c][i][r] = (the value of the elasticity rule) + wm m^r[i]
+ *   diagonal  : (the value without the term) + wm Mass[i][i], for both units and both components
+ * one product and one addition on top of the value formed without the term.  Everything before that addition, the
+ * load, the owner sum, the mask, the residual, the reference norm and the CG are unchanged; apply, apply_many, diagonal,
+ * residual, solve, solve_many and a hierarchy that holds the handle pick the variant from the handle.
+ *   cell_c == NULL           the scalar c on every cell; c == 0 then switches the term off: the handle is as created
+ *                            and launches the kernels it launched before.  A repeated call replaces the coefficient
+ *   cell_c [ncells]          in `memspace`, copied into an array the handle owns, allocated by the first call that
+ *                            brings one (nothing is allocated at create); c is ignored
+ *   diagonal                 formed again in place on `stream`, so a hierarchy that holds the handle preconditions with
+ *                            the new one at its next call.  The dense factor of eqlb_hierarchy_set_coarse is a SNAPSHOT,
+ *                            as it is for the mask and kappa: call eqlb_hierarchy_set_coarse(.., 1, ..) again after the
+ *                            reaction of level 0 changes
+ *   host memory space        a coefficient (the scalar, or cell_c[i]) that is negative, NaN or infinite is refused with
+ *                            EQLB_ERR_INVALID_ARGUMENT, the cell named, before anything changes; the call waits
+ *   device memory space      the array is taken as it is, nothing waits (but for the first allocation): an indefinite
+ *                            operator shows in the breakdown flag of the CG.  The scalar is checked as above
  */
 typedef struct eqlb_primal eqlb_primal_t;
 int eqlb_get_stiffness_table(int32_t p, double* out, int32_t capacity);
@@ -881,6 +930,8 @@ int eqlb_primal_create(eqlb_mesh_t* mesh, int32_t p, const double* cell_coeff, i
                        eqlb_primal_t** handle);
 void eqlb_primal_destroy(eqlb_primal_t* handle);
 int eqlb_primal_ndofs(const eqlb_primal_t* handle, int64_t* ndofs);
+int eqlb_get_mass_table(int32_t p, double* out, int32_t capacity);
+int eqlb_primal_set_reaction(eqlb_primal_t* handle, double c, const double* cell_c, int32_t memspace, void* stream);
 
 /* Fixed are the vertex and facet DOFs of the listed facets [nlist] (the lists eqlb_refine_child_facets carries across
  * a refinement); a repeated call replaces the mask, nlist = 0 clears it.  A facet id outside the mesh: host memory
@@ -998,6 +1049,9 @@ void eqlb_elasticity_destroy(eqlb_elasticity_t* handle);
 int eqlb_elasticity_ndofs(const eqlb_elasticity_t* handle, int64_t* ndofs);
 int eqlb_elasticity_set_dirichlet(eqlb_elasticity_t* handle, int32_t nlist0, const int32_t* facets0, int32_t nlist1,
                                   const int32_t* facets1, int32_t memspace, void* stream);
+/* The reaction term + c u of eqlb_primal_set_reaction, word for word (the rule is stated there). */
+int eqlb_elasticity_set_reaction(eqlb_elasticity_t* handle, double c, const double* cell_c, int32_t memspace,
+                                 void* stream);
 int eqlb_elasticity_load(eqlb_elasticity_t* handle, int32_t degree_dg, const double* rhs_dg, const double* b_extra,
                          double* b, int32_t memspace, void* stream);
 int eqlb_elasticity_apply(eqlb_elasticity_t* handle, const double* u, double* y, int32_t masked, int32_t memspace,

@@ -29,6 +29,9 @@ Basix nor quadrature loops:
   LD[nd_p][nd_d]       int phi_i chi_n, chi_n the DG_d nodal basis: the load of P_p against DG_d data (load_table_exact)
   CR[nd_p][nd_p]       int dX phi_i dY phi_j: with ST the four reference blocks of the elasticity operator
                        (eqlb_primal_elasticity.hip; lsolver/primal.py: cross_table_exact)
+  MS[nd_p][nd_p]       int phi_i phi_j: the reaction term of both operators (lsolver/primal.py: mass_table_exact)
+  PV[nd_d][nd_p]       DG_d nodal values of the L2 projection of phi_i onto P_d: interpolation for d >= p,
+                       MS<d>^-1 LD<p,d>^T below (eqlb_primal_flux.hip: eqlb_primal_value_dg; value_table_exact)
 
 Run:  python tools/gen_tables.py   (rewrites dolfinx_eqlb_amd/csrc/eqlb_tables_gen.h; the pairs of PAIRS_BUILD
       go to the header `python tools/gen_tables.py --build PATH` writes, which the build runs)
@@ -434,6 +437,30 @@ def emit(path):
         lines.append(f"template <> struct Cross<{p}> {{")
         lines.append(f"  static constexpr int ND = {n};")
         lines.append(f"  static constexpr double CR[{n * n}] = {{"
+                     + ", ".join(repr(float(v)) for row in t for v in row) + "};")
+        lines.append("};")
+    lines.append("")
+    from dolfinx_eqlb_amd.lsolver.primal import mass_table_exact, value_table_exact
+    lines.append("// reference mass of P_p: MS[i][j] = int phi_i phi_j, the reaction term of eqlb_primal_* and eqlb_elasticity_*")
+    lines.append("// (lsolver/primal.py: mass_table_exact)")
+    lines.append("template <int P> struct Mass;")
+    for p in range(1, 5):
+        t = mass_table_exact(p)
+        n = len(t)
+        lines.append(f"template <> struct Mass<{p}> {{")
+        lines.append(f"  static constexpr int ND = {n};")
+        lines.append(f"  static constexpr double MS[{n * n}] = {{"
+                     + ", ".join(repr(float(v)) for row in t for v in row) + "};")
+        lines.append("};")
+    lines.append("")
+    lines.append("// L2 projection of P_p onto DG_d: PV[n][i] = DG_d nodal value n of the projection of phi_i (interpolation for")
+    lines.append("// d >= p, MS<d>^-1 LD<p,d>^T below); eqlb_primal_value_dg (eqlb_primal_flux.hip)")
+    lines.append("template <int P, int D> struct Value;")
+    for (p, d) in PAIRS_PRIMAL:
+        t = value_table_exact(p, d)
+        lines.append(f"template <> struct Value<{p}, {d}> {{")
+        lines.append(f"  static constexpr int NP = {len(t[0])}, ND = {len(t)};")
+        lines.append(f"  static constexpr double PV[{len(t) * len(t[0])}] = {{"
                      + ", ".join(repr(float(v)) for row in t for v in row) + "};")
         lines.append("};")
     lines.append("")

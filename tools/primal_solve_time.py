@@ -32,6 +32,16 @@ tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all ar
              (repeated for at least 40 ms and until two agree within 1 %, at most 24); median and spread (max - min)
              of the wall time of the calls, which wait for the device, are printed, and whether the gain of the
              many-solve exceeds the spread of the R single calls
+  --reaction  instead of the figures above: the reaction term + c u of set_reaction.  (1) At --n, for every degree (with
+             --elasticity also for the elasticity product): one masked product without and with the term (a cell-wise c,
+             uniform in [0, 1000]) ON THE SAME HANDLE in one process, switched by set_reaction: after clock-settle
+             probes, --repeats (>= 5) alternating blocks of --products products each; median and spread (max - min) of
+             the time per product, and whether the difference exceeds the spread.  With --plain-only the blocks without
+             the term alone: the figure of the same-call A/B against the parent commit (tools/build_head.sh,
+             tools/run_variants.sh).  (2) On the hierarchy of --multilevel, Poisson: one implicit heat step, c = 1 / tau
+             on every level for every tau of --taus (1e-2 and 1e-4) next to c = 0: iterations and time to rtol 1e-8 from zero of the
+             Jacobi entry, of the hierarchy, and of the hierarchy with local smoothing and the exact coarse solve
+             (factored again after every change of c).  One run each
   --check-every LIB:N ...   the PCG of P_2 to rtol 1e-8 from zero once per library (builds of libeqlb_amd.so with
              -DEQLB_PRIMAL_CHECK_EVERY=N, tools/build_variant.sh NAME "-D..." eqlb_primal_solve), each in a child process
 Prints one line per figure and, last, one JSON line with all of them.  Nothing here is a pass/fail condition.
@@ -419,6 +429,79 @@ def run_multilevel(args, cpp, torch, res):
             res[f"ML_{P}{p}"] = r
 
 
+def run_reaction(args, cpp, torch, res):
+    """the figures of --reaction"""
+    from dolfinx_eqlb_amd.mesh import create_unit_square
+    dm = cpp.DeviceMesh(create_unit_square(args.n, shuffle_seed=3, perturb=0.15))
+    nc = dm.mesh.ncells
+    cc = 1000.0 * torch.rand(nc, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    for elasticity in ([False, True] if args.elasticity else [False]):
+        bs, P = (2, "E") if elasticity else (1, "P")
+        for p in args.degrees:
+            h, _ = make_problem(cpp, torch, dm, p, elasticity)
+            n = bs * h.ndofs
+            x = torch.from_numpy(np.random.default_rng(0).standard_normal(n)).cuda()
+            y = torch.empty_like(x)
+
+            def product():
+                h.apply_raw(x.data_ptr(), y.data_ptr(), True)
+
+            def probe():
+                product()
+                torch.cuda.synchronize()
+
+            states = ("off",) if args.plain_only else ("off", "on")
+            probes = settle_probes(probe)
+            t = {s: [] for s in states}
+            for _ in range(args.repeats):
+                for s in states:
+                    if not args.plain_only:
+                        h.set_reaction_raw(0.0, cc.data_ptr() if s == "on" else None)
+                    t[s].append(timed_calls(torch, product, args.products))
+            r = dict(cells=nc, rows=n, products=args.products, repeats=args.repeats, settle_probes=len(probes))
+            for s in states:
+                r[s] = dict(median_ms=float(np.median(t[s])), spread_ms=float(np.ptp(t[s])), all_ms=t[s])
+            line = f"{P}_{p}: {n} rows; product without the term {r['off']['median_ms']:.4f} ms (spread " \
+                   f"{r['off']['spread_ms']:.4f})"
+            if not args.plain_only:
+                diff = r["on"]["median_ms"] - r["off"]["median_ms"]
+                r["ratio"] = r["on"]["median_ms"] / r["off"]["median_ms"]
+                r["difference_exceeds_spread"] = bool(abs(diff) > max(r["on"]["spread_ms"], r["off"]["spread_ms"]))
+                line += f", with it {r['on']['median_ms']:.4f} ms (spread {r['on']['spread_ms']:.4f}) = {r['ratio']:.3f} " \
+                        f"of it; the difference exceeds the spread: {r['difference_exceeds_spread']}"
+            say(line + f"; median of {args.repeats} blocks of {args.products} products after {len(probes)} probes")
+            res[f"REACTION_PRODUCT_{P}{p}"] = r
+            h.close()
+    if args.plain_only or not args.multilevel:
+        return
+    dms, refs, cells = device_hierarchy(args, cpp)
+    for p in args.degrees:
+        hs = []
+        for d in dms[:-1]:
+            hs.append(cpp.PrimalPoisson(d, p))
+            hs[-1].set_dirichlet(d.mesh.boundary_facets())
+        top, b = make_problem(cpp, torch, dms[-1], p)
+        hs.append(top)
+        ml = cpp.Multilevel(hs, refs)
+        mlc = cpp.Multilevel(hs, refs, local=True, coarse=True)
+        zero = torch.zeros(top.ndofs, dtype=torch.float64, device="cuda")
+        for tau in [None] + list(args.taus):
+            for h in hs:
+                h.set_reaction(0.0 if tau is None else 1.0 / tau)
+            mlc.set_coarse(True)     # (the factor is a snapshot of the operator of level 0)
+            r = dict(levels=len(dms), cells=cells[-1], ndofs=top.ndofs, c=0.0 if tau is None else 1.0 / tau)
+            for name, h in (("jacobi", top), ("hierarchy", ml), ("local_coarse", mlc)):
+                info, ms, _ = timed_solve(torch, h, b, zero, 1e-8, args.maxit)
+                r[name] = dict(iterations=info["iterations"], ms=ms, converged=info["converged"],
+                               breakdown=info["breakdown"])
+            say(f"P_{p} heat step tau = {tau}: " + "; ".join(
+                f"{name} {r[name]['iterations']} iterations in {r[name]['ms']:.1f} ms"
+                for name in ("jacobi", "hierarchy", "local_coarse")) + " (one run each)")
+            res[f"HEAT_P{p}_tau{tau}"] = r
+        ml.close()
+        mlc.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=500, help="squares per side (4 n^2 triangles)")
@@ -435,7 +518,13 @@ def main():
     ap.add_argument("--coarse-n", type=int, default=2, help="--multilevel: squares per side of the coarsest mesh")
     ap.add_argument("--nrhs", type=int, nargs="+", default=[], metavar="R",
                     help="several right-hand sides in one call against one call each, on the hierarchy of --multilevel")
-    ap.add_argument("--repeats", type=int, default=5, help="--nrhs: timed repeats of every pair (at least 5)")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="--nrhs, --reaction: timed repeats of every pair (at least 5)")
+    ap.add_argument("--reaction", action="store_true", help="the figures of the reaction term instead")
+    ap.add_argument("--taus", type=float, nargs="+", default=[1e-2, 1e-4], metavar="TAU",
+                    help="--reaction --multilevel: the time steps of the heat step, next to c = 0")
+    ap.add_argument("--plain-only", action="store_true",
+                    help="--reaction: time the product without the term alone (runs on a library without the term too)")
     ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
     ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -464,6 +553,10 @@ def main():
     torch.cuda.init()
     from dolfinx_eqlb_amd import cpp
     from dolfinx_eqlb_amd.mesh import create_unit_square
+    if args.reaction:
+        run_reaction(args, cpp, torch, res)
+        print(json.dumps(res))
+        return
     if args.nrhs:
         run_many(args, cpp, torch, res)
         print(json.dumps(res))
