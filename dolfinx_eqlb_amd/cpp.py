@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_hierarchy_set_coarse", "eqlb_hierarchy_coarse_rows", "eqlb_hierarchy_coarse_factor",
     "eqlb_get_mass_table", "eqlb_primal_set_reaction", "eqlb_elasticity_set_reaction",
     "eqlb_primal_value_dg", "eqlb_get_value_table",
+    "eqlb_elasticity_set_shear", "eqlb_primal_stress_dg_mu", "eqlb_se_estimate_stress_mu",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -1063,11 +1064,36 @@ def estimate_raw(dmesh: DeviceMesh, k: int, nrhs: int, flux_hdiv, flux_dg, rhs_d
         _check(fn(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), *ptrs, *tail))
 
 
-def estimate_stress(dmesh: DeviceMesh, k: int, flux_hdiv, korn=None, pi_1: float = 1.0):
+def _cell_array(a, ncells):
+    """A cell-wise coefficient as a contiguous float64 array [ncells], or None."""
+    if a is None:
+        return None
+    v = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    if v.size != ncells:
+        raise RuntimeError("Equilibration: Input sizes does not match")
+    return v
+
+
+def estimate_stress(dmesh: DeviceMesh, k: int, flux_hdiv, korn=None, pi_1: float = 1.0, cell_pi1=None,
+                    mu: float = 1.0, cell_mu=None):
     """eqlb_se_estimate_stress on host arrays: flux_hdiv [2, ncells*k(k+2)] (rows of the equilibrated
     stress), korn [ncells] cell-wise Korn constants or None.  Returns (cell_energy [ncells],
-    cell_wsym [ncells], node_asym [nnodes])."""
+    cell_wsym [ncells], node_asym [nnodes]).
+    With cell_pi1 [ncells], mu or cell_mu [ncells] (eqlb_se_estimate_stress_mu): the terms for
+    sigma = mu_T (2 eps(u) + pi_T div(u) I) - energy and wsym are formed with pi_T and divided by mu_T > 0, node_asym is
+    unchanged.  The oscillation term takes the same weight through its own argument: oscillation(..., korn=korn /
+    np.sqrt(cell_mu)).  A DG_0 coefficient crosses a refinement through Refinement.prolong_dg(0, ...).  Without the
+    new keywords the call is the one it was."""
     m = dmesh.mesh
+    if cell_pi1 is not None or cell_mu is not None or mu != 1.0:
+        x = np.ascontiguousarray(flux_hdiv, dtype=np.float64)
+        kc, kp, km = _cell_array(korn, m.ncells), _cell_array(cell_pi1, m.ncells), _cell_array(cell_mu, m.ncells)
+        if x.size != 2 * m.ncells * k * (k + 2):
+            raise RuntimeError("Equilibration: Input sizes does not match")
+        energy, wsym, asym = np.zeros(m.ncells), np.zeros(m.ncells), np.zeros(m.nnodes)
+        estimate_stress_mu_raw(dmesh, k, _hp(x), None if kc is None else _hp(kc), pi_1, None if kp is None else _hp(kp),
+                               mu, None if km is None else _hp(km), _hp(energy), _hp(wsym), _hp(asym), MEM_HOST)
+        return energy, wsym, asym
     x = np.ascontiguousarray(flux_hdiv, dtype=np.float64)
     if x.size != 2 * m.ncells * k * (k + 2):
         raise RuntimeError("Equilibration: Input sizes does not match")
@@ -1079,6 +1105,15 @@ def estimate_stress(dmesh: DeviceMesh, k: int, flux_hdiv, korn=None, pi_1: float
                                          C.c_double(pi_1), _hp(energy), _hp(wsym), _hp(asym),
                                          C.c_int32(MEM_HOST), None))
     return energy, wsym, asym
+
+
+def estimate_stress_mu_raw(dmesh: DeviceMesh, k: int, flux_hdiv, korn, pi_1: float, cell_pi1, mu: float, cell_mu,
+                           cell_energy, cell_wsym, node_asym, memspace=MEM_DEVICE, stream=0):
+    """eqlb_se_estimate_stress_mu on raw pointers (ints, or None for an array that is not given / an output that is not
+    wanted) in `memspace`, ordered on `stream`."""
+    _check(lib().eqlb_se_estimate_stress_mu(dmesh._h, C.c_int32(k), _vp(flux_hdiv), _vp(korn), C.c_double(pi_1),
+                                            _vp(cell_pi1), C.c_double(mu), _vp(cell_mu), _vp(cell_energy),
+                                            _vp(cell_wsym), _vp(node_asym), C.c_int32(memspace), C.c_void_p(stream)))
 
 
 def oscillation(dmesh: DeviceMesh, k: int, flux, flux_dg, qpoints, qweights, fvalues, korn=None, degree_dg=None):
@@ -1308,10 +1343,12 @@ def primal_flux_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, nrhs: int, cel
 
 
 def primal_stress_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, pi_1: float = 1.0, cell_pi1=None,
-                     op=None):
+                     op=None, mu: float = 1.0, cell_mu=None):
     """eqlb_primal_stress_dg on host arrays: rows of -(2 eps(u_h) + pi_1 div(u_h) I) for the blocked displacement
     u [ndofs, 2] in P_p^2 (scalar dofmap cell_dofs), pi_1 per cell where cell_pi1 [ncells] is given.  Returns
-    [2, ncells*nd_d*2]."""
+    [2, ncells*nd_d*2].  With mu or cell_mu [ncells] (eqlb_primal_stress_dg_mu): rows of -mu_T (2 eps(u_h) + pi_1
+    div(u_h) I), every value mu_T > 0 times the value formed without it, rounded once; a DG_0 cell_mu crosses a
+    refinement through Refinement.prolong_dg(0, ...).  Without the new keywords the call is the one it was."""
     m = dmesh.mesh
     ndp, nd = _primal_sizes(p, degree_dg)
     cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
@@ -1321,6 +1358,14 @@ def primal_stress_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, pi
         raise RuntimeError("Local solver: Input sizes does not match")
     t = _primal_op(op, nd, ndp)
     out = np.zeros((2, m.ncells * nd * 2))
+    if cell_mu is not None or mu != 1.0:
+        km = None if cell_mu is None else np.ascontiguousarray(cell_mu, dtype=np.float64).ravel()
+        if km is not None and km.size != m.ncells:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        primal_stress_dg_mu_raw(dmesh, p, degree_dg, _hp(cd), uu.size // 2, _hp(uu), pi_1,
+                                _hp(kc) if kc is not None else None, mu, _hp(km) if km is not None else None,
+                                _hp(out), t, MEM_HOST)
+        return out
     primal_stress_dg_raw(dmesh, p, degree_dg, _hp(cd), uu.size // 2, _hp(uu), pi_1,
                          _hp(kc) if kc is not None else None, _hp(out), t, MEM_HOST)
     return out
@@ -1335,6 +1380,17 @@ def primal_stress_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, n
                                        C.c_int64(ndofs), _vp(u), C.c_double(pi_1), _vp(cell_pi1),
                                        _hp(t) if t is not None else None, _vp(flux_dg), C.c_int32(memspace),
                                        C.c_void_p(stream)))
+
+
+def primal_stress_dg_mu_raw(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, ndofs: int, u, pi_1: float, cell_pi1,
+                            mu: float, cell_mu, flux_dg, op=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_primal_stress_dg_mu on raw pointers (ints; cell_pi1 and cell_mu may be None) in `memspace`, ordered on
+    `stream`: u [ndofs, 2] blocked, flux_dg [2, ncells*nd_d*2]."""
+    t = None if op is None else np.ascontiguousarray(op, dtype=np.float64)
+    _check(lib().eqlb_primal_stress_dg_mu(dmesh._h, C.c_int32(p), C.c_int32(degree_dg), _vp(cell_dofs),
+                                          C.c_int64(ndofs), _vp(u), C.c_double(pi_1), _vp(cell_pi1), C.c_double(mu),
+                                          _vp(cell_mu), _hp(t) if t is not None else None, _vp(flux_dg),
+                                          C.c_int32(memspace), C.c_void_p(stream)))
 
 
 def get_value_table(p: int, degree_dg: int):
@@ -1669,6 +1725,25 @@ class PrimalElasticity(_PrimalSolver):
     def set_dirichlet_raw(self, nlist0, facets0, nlist1, facets1, memspace=MEM_DEVICE, stream=0):
         _check(lib().eqlb_elasticity_set_dirichlet(self._h, C.c_int32(nlist0), _vp(facets0), C.c_int32(nlist1),
                                                    _vp(facets1), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def set_shear(self, mu=1.0, cell_mu=None, stream=0):
+        """The stress becomes mu (2 eps(u) + pi_1 div(u) I) (eqlb_elasticity_set_shear): cell_mu, a host array [ncells],
+        where given, else the scalar mu on every cell, mu > 0; mu == 1 without an array switches the term off.  The
+        reaction term is not scaled.  A repeated call replaces the coefficient; one that is <= 0, NaN or infinite is
+        refused, the cell named, and the handle stays as it was.  The diagonal is formed again;
+        Multilevel.set_coarse(True) has to be called again afterwards.  A DG_0 coefficient crosses a refinement through
+        Refinement.prolong_dg(0, cell_mu): the children of a cell take its value."""
+        kc = None
+        if cell_mu is not None:
+            kc = np.ascontiguousarray(cell_mu, dtype=np.float64).ravel()
+            if kc.size != self.dmesh.counts()[1]:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        self.set_shear_raw(mu, None if kc is None else kc.ctypes.data, MEM_HOST, stream)
+
+    def set_shear_raw(self, mu=1.0, cell_mu=None, memspace=MEM_DEVICE, stream=0):
+        """cell_mu: a raw pointer (int) to [ncells] in `memspace`, or None (the scalar mu)."""
+        _check(lib().eqlb_elasticity_set_shear(self._h, C.c_double(mu), _vp(cell_mu), C.c_int32(memspace),
+                                               C.c_void_p(stream)))
 
 
 

@@ -552,35 +552,72 @@ int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t
                        memspace, stream, -1.0, 0.0);
 }
 
-int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv, const double* korn,
-                            double pi_1, double* cell_energy, double* cell_wsym, double* node_asym,
-                            int32_t memspace, void* stream_)
+// the body of eqlb_se_estimate_stress and eqlb_se_estimate_stress_mu; co: the cell-wise coefficients of the latter, its
+// arrays in `memspace`, or nullptr (the scalar pi_1, mu = 1)
+static int estimate_stress_call(const char* who, eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv,
+                                const double* korn, double pi_1, const eqlb::StressCoeffArgs* co, double* cell_energy,
+                                double* cell_wsym, double* node_asym, int32_t memspace, void* stream_)
 {
   if (!mesh || !flux_hdiv || k < 1 || k > 4 || !(pi_1 > -1.0))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate_stress: invalid argument");
-  EQLB_TRY(eqlb::check_memspace("eqlb_se_estimate_stress", memspace));
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid argument", who);
+  EQLB_TRY(eqlb::check_memspace(who, memspace));
   const eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (co && memspace == EQLB_MEM_HOST)
+    for (int32_t i = 0; i < m.ncells; ++i)
+    {
+      if (co->cell_mu && !(co->cell_mu[i] > 0.0 && std::isfinite(co->cell_mu[i])))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
+                    co->cell_mu[i]);
+      if (co->cell_pi1 && !(co->cell_pi1[i] > -1.0))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_pi1[%d] = %g is not above -1", who, (int)i, co->cell_pi1[i]);
+    }
   const int32_t* node_cells = nullptr; // (first use from several threads: the handle's lock is taken there)
   if (node_asym && eqlb::mesh_node_cells(mesh, &node_cells))
-    return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate_stress: device allocation failed");
+    return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
   const size_t nx = (size_t)m.ncells * k * (k + 2);
   int rc;
   if (memspace == EQLB_MEM_DEVICE)
     rc = eqlb::launch_estimate_stress(m, node_cells, k, flux_hdiv, flux_hdiv + nx, korn, pi_1, cell_energy,
-                                      cell_wsym, node_asym, stream);
+                                      cell_wsym, node_asym, stream, co);
   else
   {
     eqlb::HostCall s;
     const auto d_x = s.in(flux_hdiv, 2 * nx), d_k = s.in(korn, m.ncells);
+    const auto d_p = s.in(co ? co->cell_pi1 : nullptr, m.ncells), d_m = s.in(co ? co->cell_mu : nullptr, m.ncells);
     const auto d_e = s.out(cell_energy, m.ncells), d_w = s.out(cell_wsym, m.ncells), d_a = s.out(node_asym, m.nnodes);
     if (s.upload(stream) != hipSuccess)
-      return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate_stress: device allocation failed");
-    rc = eqlb::launch_estimate_stress(m, node_cells, k, d_x, d_x + nx, d_k, pi_1, d_e, d_w, d_a, stream);
+      return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
+    eqlb::StressCoeffArgs dco;
+    if (co)
+      dco = eqlb::StressCoeffArgs{co->cell_pi1 ? d_p.get() : nullptr, co->cell_mu ? d_m.get() : nullptr, co->pi_1, co->mu};
+    rc = eqlb::launch_estimate_stress(m, node_cells, k, d_x, d_x + nx, d_k, pi_1, d_e, d_w, d_a, stream,
+                                      co ? &dco : nullptr);
     if (s.finish(stream) != hipSuccess)
       rc = EQLB_ERR_DEVICE;
   }
-  return rc ? fail(rc, "eqlb_se_estimate_stress: device error") : EQLB_OK;
+  return rc ? fail(rc, "%s: device error", who) : EQLB_OK;
+}
+
+int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv, const double* korn,
+                            double pi_1, double* cell_energy, double* cell_wsym, double* node_asym,
+                            int32_t memspace, void* stream)
+{
+  return estimate_stress_call("eqlb_se_estimate_stress", mesh, k, flux_hdiv, korn, pi_1, nullptr, cell_energy, cell_wsym,
+                              node_asym, memspace, stream);
+}
+
+int eqlb_se_estimate_stress_mu(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv, const double* korn, double pi_1,
+                               const double* cell_pi1, double mu, const double* cell_mu, double* cell_energy,
+                               double* cell_wsym, double* node_asym, int32_t memspace, void* stream)
+{
+  const char* who = "eqlb_se_estimate_stress_mu";
+  if (!cell_mu && !(mu > 0.0 && std::isfinite(mu)))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: mu = %g is zero, negative, NaN or infinite", who, mu);
+  const eqlb::StressCoeffArgs co{cell_pi1, cell_mu, pi_1, mu};
+  const bool plain = !cell_pi1 && !cell_mu && mu == 1.0; // the kernel of eqlb_se_estimate_stress
+  return estimate_stress_call(who, mesh, k, flux_hdiv, korn, cell_pi1 ? 0.0 : pi_1, plain ? nullptr : &co, cell_energy,
+                              cell_wsym, node_asym, memspace, stream);
 }
 
 int eqlb_oscillation(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* flux, const double* flux_dg,

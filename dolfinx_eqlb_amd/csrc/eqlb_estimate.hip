@@ -46,89 +46,14 @@ int launch_boundary_residual(const DeviceMesh& m, int k, int deg, int nrhs, cons
 //   wsym   = int (C_K (dsig_01 - dsig_10) / 2)^2                                                         (:108,121)
 //   asym3  = int (dsig_01 - dsig_10) hat_v  per vertex (the weak symmetry condition,
 //            python/dolfinx_eqlb/eqlb/check_eqlb_conditions.py:476-521, before assembly over the nodes)
-template <int K>
-__global__ void __launch_bounds__(256)
-k_estimate_stress_cells(int32_t ncells, const double* __restrict__ tab, const double* __restrict__ cellJ,
-                        const double* __restrict__ x0, const double* __restrict__ x1,
-                        const double* __restrict__ korn, const double pi_1, double* __restrict__ energy,
-                        double* __restrict__ wsym, double* __restrict__ asym3)
-{
-  using R = eqlb_tables::Ref<K, K - 1>;
-  constexpr int NRT = R::NRT, NSU = R::SU_SIZE, NV = R::V_SIZE;
-  extern __shared__ double st[];
-  for (int i = threadIdx.x; i < NSU + NV; i += 256)
-    st[i] = tab[i];
-  __syncthreads();
-  const int32_t c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncells)
-    return;
-  const double* J = cellJ + 4 * (int64_t)c;
-  const double Jm[2][2] = {{J[0], J[1]}, {J[2], J[3]}};
-  const double detJ = J[0] * J[3] - J[1] * J[2], ia = 1.0 / fabs(detJ);
-  double c0[NRT], c1[NRT];
-#pragma unroll
-  for (int i = 0; i < NRT; ++i)
-  {
-    c0[i] = x0[(int64_t)c * NRT + i];
-    c1[i] = x1[(int64_t)c * NRT + i];
-  }
-  // W[t][r][s] = c_r^T SU_t c_s, t = (xx, xy, yy)
-  double W[3][2][2];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-  {
-    double w00 = 0.0, w01 = 0.0, w10 = 0.0, w11 = 0.0;
-    for (int i = 0; i < NRT; ++i)
-    {
-      double u0 = 0.0, u1 = 0.0;
-#pragma unroll
-      for (int j = 0; j < NRT; ++j)
-      {
-        const double a = st[(t * NRT + i) * NRT + j];
-        u0 += a * c0[j];
-        u1 += a * c1[j];
-      }
-      w00 += c0[i] * u0;
-      w01 += c0[i] * u1;
-      w10 += c1[i] * u0;
-      w11 += c1[i] * u1;
-    }
-    W[t][0][0] = w00;
-    W[t][0][1] = w01;
-    W[t][1][0] = w10;
-    W[t][1][1] = w11;
-  }
-  // int_T sigma_r^x sigma_s^y
-  auto prod = [&](int x, int y, int r, int s) {
-    return ia
-           * (Jm[x][0] * Jm[y][0] * W[0][r][s] + Jm[x][0] * Jm[y][1] * W[1][r][s] + Jm[x][1] * Jm[y][0] * W[1][s][r]
-              + Jm[x][1] * Jm[y][1] * W[2][r][s]);
-  };
-  const double fro = prod(0, 0, 0, 0) + prod(1, 1, 0, 0) + prod(0, 0, 1, 1) + prod(1, 1, 1, 1);
-  const double tr2 = prod(0, 0, 0, 0) + 2.0 * prod(0, 1, 0, 1) + prod(1, 1, 1, 1);
-  const double as2 = prod(1, 1, 0, 0) - 2.0 * prod(1, 0, 0, 1) + prod(0, 0, 1, 1);
-  const double ck = korn ? korn[c] : 1.0;
-  if (energy)
-    energy[c] = 0.5 * (fro - pi_1 / (2.0 + 2.0 * pi_1) * tr2);
-  if (wsym)
-    wsym[c] = 0.25 * ck * ck * as2;
-  if (asym3)
-  {
-    const double sg = (detJ > 0.0) ? 1.0 : -1.0;
-    const double* V = st + NSU; // V[v][i][a] = int hat_v phi_i^a
-#pragma unroll
-    for (int v = 0; v < 3; ++v)
-    {
-      double r = 0.0;
-      for (int i = 0; i < NRT; ++i)
-      {
-        const double v0 = V[(v * NRT + i) * 2], v1 = V[(v * NRT + i) * 2 + 1];
-        r += c0[i] * (Jm[1][0] * v0 + Jm[1][1] * v1) - c1[i] * (Jm[0][0] * v0 + Jm[0][1] * v1);
-      }
-      asym3[(int64_t)c * 3 + v] = sg * r;
-    }
-  }
-}
+// With a shear modulus (eqlb_se_estimate_stress_mu): sigma = mu_T (2 eps + pi_T div I), A_T = A(pi_T) / mu_T, and the Korn
+// bound of the weak-symmetry term picks up 1 / mu_T as well: energy and wsym are divided by mu_T, asym3 is unchanged.
+#define EQLB_EST_MU 0
+#include "eqlb_estimate_stress_cells.inc"
+#undef EQLB_EST_MU
+#define EQLB_EST_MU 1
+#include "eqlb_estimate_stress_cells.inc"
+#undef EQLB_EST_MU
 
 // node value = sum of the vertex values of the cells around the node, in the order of the CSR list
 __global__ void __launch_bounds__(256)
@@ -151,8 +76,8 @@ k_gather_vertex_values(int32_t nnodes, const int32_t* __restrict__ node_cells_of
 
 template <int K>
 static int launch_estimate_stress_k(const DeviceMesh& m, const int32_t* node_cells, const double* x0,
-                                    const double* x1, const double* korn, double pi_1, double* energy,
-                                    double* wsym, double* node_asym, hipStream_t stream)
+                                    const double* x1, const double* korn, double pi_1, const StressCoeffArgs* co,
+                                    double* energy, double* wsym, double* node_asym, hipStream_t stream)
 {
   using R = eqlb_tables::Ref<K, K - 1>;
   std::vector<double> t(R::SU, R::SU + R::SU_SIZE);
@@ -163,9 +88,14 @@ static int launch_estimate_stress_k(const DeviceMesh& m, const int32_t* node_cel
   hipError_t e = hipMemcpyAsync(d_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, stream);
   if (e == hipSuccess)
   {
-    hipLaunchKernelGGL(k_estimate_stress_cells<K>, dim3((m.ncells + 255) / 256), dim3(256),
-                       t.size() * sizeof(double), stream, m.ncells, d_t, m.cellJ, x0, x1, korn, pi_1, energy, wsym,
-                       d_a);
+    if (co) // the variant with cell-wise coefficients; without them the launch as before they existed
+      hipLaunchKernelGGL(k_estimate_stress_cells_mu<K>, dim3((m.ncells + 255) / 256), dim3(256),
+                         t.size() * sizeof(double), stream, m.ncells, d_t, m.cellJ, x0, x1, korn, *co, energy, wsym,
+                         d_a);
+    else
+      hipLaunchKernelGGL(k_estimate_stress_cells<K>, dim3((m.ncells + 255) / 256), dim3(256),
+                         t.size() * sizeof(double), stream, m.ncells, d_t, m.cellJ, x0, x1, korn, pi_1, energy, wsym,
+                         d_a);
     if (node_asym)
       hipLaunchKernelGGL(k_gather_vertex_values, dim3((m.nnodes + 255) / 256), dim3(256), 0, stream, m.nnodes,
                          m.node_cells_off, node_cells, m.cell_nodes, d_a, node_asym);
@@ -178,16 +108,16 @@ static int launch_estimate_stress_k(const DeviceMesh& m, const int32_t* node_cel
 
 int launch_estimate_stress(const DeviceMesh& m, const int32_t* node_cells, int k, const double* x0,
                            const double* x1, const double* korn, double pi_1, double* energy, double* wsym,
-                           double* node_asym, hipStream_t stream)
+                           double* node_asym, hipStream_t stream, const StressCoeffArgs* co)
 {
   if (k == 1)
-    return launch_estimate_stress_k<1>(m, node_cells, x0, x1, korn, pi_1, energy, wsym, node_asym, stream);
+    return launch_estimate_stress_k<1>(m, node_cells, x0, x1, korn, pi_1, co, energy, wsym, node_asym, stream);
   if (k == 2)
-    return launch_estimate_stress_k<2>(m, node_cells, x0, x1, korn, pi_1, energy, wsym, node_asym, stream);
+    return launch_estimate_stress_k<2>(m, node_cells, x0, x1, korn, pi_1, co, energy, wsym, node_asym, stream);
   if (k == 3)
-    return launch_estimate_stress_k<3>(m, node_cells, x0, x1, korn, pi_1, energy, wsym, node_asym, stream);
+    return launch_estimate_stress_k<3>(m, node_cells, x0, x1, korn, pi_1, co, energy, wsym, node_asym, stream);
   if (k == 4)
-    return launch_estimate_stress_k<4>(m, node_cells, x0, x1, korn, pi_1, energy, wsym, node_asym, stream);
+    return launch_estimate_stress_k<4>(m, node_cells, x0, x1, korn, pi_1, co, energy, wsym, node_asym, stream);
   return EQLB_ERR_UNSUPPORTED;
 }
 

@@ -276,9 +276,18 @@ int launch_estimate(const DeviceMesh& m, int k, int deg, int nrhs, const double*
 int launch_boundary_residual(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
                              const double* flux_dg, int32_t nlist, const int32_t* facets, const double* bvals,
                              double* out, hipStream_t stream);
+// the cell-wise coefficients of eqlb_se_estimate_stress_mu: pi_T = cell_pi1[cell] and mu_T = cell_mu[cell] where given,
+// else the scalars.  A kernel argument of the variant with them, which the kernel of eqlb_se_estimate_stress does not take
+struct StressCoeffArgs
+{
+  const double* cell_pi1 = nullptr; // [ncells] or nullptr
+  const double* cell_mu = nullptr;  // [ncells] or nullptr
+  double pi_1 = 1.0, mu = 1.0;
+};
+// co == nullptr: the kernel with the scalar pi_1 and mu = 1
 int launch_estimate_stress(const DeviceMesh& m, const int32_t* node_cells, int k, const double* x0,
                            const double* x1, const double* korn, double pi_1, double* energy, double* wsym,
-                           double* node_asym, hipStream_t stream);
+                           double* node_asym, hipStream_t stream, const StressCoeffArgs* co = nullptr);
 int launch_oscillation(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                        int nq, const double* qpoints, const double* qweights, const double* fvalues,
                        const double* korn, double* out, hipStream_t stream);

@@ -1,12 +1,20 @@
-// The cell kernel of eqlb_primal_elasticity.hip, which includes this file twice inside its unnamed namespace:
-//   EQLB_CELL_REACT 0  k_elast_cell<P, MODE, D>: the operator, the diagonal and the load of -div(2 eps(u) + pi_1 div(u) I)
-//   EQLB_CELL_REACT 1  k_elast_cell_react<P, MODE, D>: operator and diagonal with the reaction term + c u
-// One source for both, and two kernels rather than one with a further template argument: a handle without the term
+// The cell kernel of eqlb_primal_elasticity.hip, which includes this file four times inside its unnamed namespace:
+//   EQLB_CELL_REACT 0, EQLB_CELL_SHEAR 0  k_elast_cell<P, MODE, D>: the operator, the diagonal and the load of
+//                                         -div(2 eps(u) + pi_1 div(u) I)
+//   EQLB_CELL_REACT 1, EQLB_CELL_SHEAR 0  k_elast_cell_react<P, MODE, D>: operator and diagonal with the reaction term + c u
+//   EQLB_CELL_REACT 0, EQLB_CELL_SHEAR 1  k_elast_cell_shear<P, MODE, D>: operator and diagonal of
+//                                         -div(mu (2 eps(u) + pi_1 div(u) I)), mu_T per cell
+//   EQLB_CELL_REACT 1, EQLB_CELL_SHEAR 1  k_elast_cell_react_shear<P, MODE, D>: both terms
+// One source for all, and separate kernels rather than one with further template arguments: a handle without a term
 // launches the symbols it launched before the term existed, with their arguments and their code (a shared __device__
 // body that takes the arguments by reference does not give the same code: tools/isa_compare.py).
 template <int P, int MODE, int D>
 __global__ void __launch_bounds__(ES_THREADS)
-#if EQLB_CELL_REACT
+#if EQLB_CELL_REACT && EQLB_CELL_SHEAR
+k_elast_cell_react_shear(const ElastCellArgs a, const ReactArgs rx, const ShearArgs sx)
+#elif EQLB_CELL_SHEAR
+k_elast_cell_shear(const ElastCellArgs a, const ShearArgs sx)
+#elif EQLB_CELL_REACT
 k_elast_cell_react(const ElastCellArgs a, const ReactArgs rx)
 #else
 k_elast_cell(const ElastCellArgs a)
@@ -14,16 +22,19 @@ k_elast_cell(const ElastCellArgs a)
 {
 #pragma clang fp contract(off) // the statement rounds every product and every sum on its own
   constexpr int NP = nd_of(P), ND = nd_of(D), W = 2 * NP, S = W | 1, NN = NP * NP;
-  constexpr bool RX = EQLB_CELL_REACT != 0;
+  constexpr bool RX = EQLB_CELL_REACT != 0, SH = EQLB_CELL_SHEAR != 0;
   constexpr int NTAB = (MODE == CELL_LOAD) ? NP * ND : (RX ? 4 : 3) * NN;
   static_assert(eqlb_tables::Stiff<P>::ND == NP && eqlb_tables::Cross<P>::ND == NP && eqlb_tables::Load<P, D>::NP == NP
                     && eqlb_tables::Load<P, D>::ND == ND && eqlb_tables::Mass<P>::ND == NP,
                 "table shape");
-  static_assert(!RX || MODE != CELL_LOAD, "the load knows no reaction term");
+  static_assert(!(RX || SH) || MODE != CELL_LOAD, "the load knows neither the reaction term nor the shear modulus");
   __shared__ double sT[NTAB];
   __shared__ double sbuf[ES_THREADS * S]; // first the index rows of the workgroup, then its output rows
 #if !EQLB_CELL_REACT
   [[maybe_unused]] const ReactArgs rx{}; // (the discarded branches below name it)
+#endif
+#if !EQLB_CELL_SHEAR
+  [[maybe_unused]] const ShearArgs sx{};
 #endif
   if (a.st && a.st->done)
     return;
@@ -101,6 +112,9 @@ k_elast_cell(const ElastCellArgs a)
       [[maybe_unused]] double wm = 0.0;
       if constexpr (RX)
         wm = (rx.cell_c ? rx.cell_c[base + t] : rx.c) * adet;
+      [[maybe_unused]] double mu = 1.0;
+      if constexpr (SH)
+        mu = sx.cell_mu ? sx.cell_mu[base + t] : sx.mu;
       [[maybe_unused]] double uu[2][NP];
       if constexpr (MODE == CELL_OPERATOR)
       {
@@ -135,6 +149,8 @@ k_elast_cell(const ElastCellArgs a)
           for (int r = 0; r < 2; ++r)
           {
             double v = adet * (((Dd[0][0] + Dd[1][1]) + Dd[r][r]) + pi * Dd[r][r]);
+            if constexpr (SH) // one product on top of the value formed without the term
+              v = mu * v;
             if constexpr (RX)
               v = v + wm * MS[i * NP + i];
             sbuf[t * S + 2 * i + r] = v;
@@ -166,6 +182,11 @@ k_elast_cell(const ElastCellArgs a)
                               + pi * (Dd[0][0][0] + Dd[1][0][1]));
           double v1 = adet * (((Dd[1][0][0] + Dd[1][1][1]) + (Dd[0][0][1] + Dd[1][1][1]))
                               + pi * (Dd[0][1][0] + Dd[1][1][1]));
+          if constexpr (SH) // one product on top of the value formed without the term; the reaction term is not scaled
+          {
+            v0 = mu * v0;
+            v1 = mu * v1;
+          }
           if constexpr (RX)
           {
             double m0 = MS[i * NP] * uu[0][0], m1 = MS[i * NP] * uu[1][0];

@@ -34,6 +34,11 @@
 struct eqlb_elasticity : eqlb::SolverHandle<2, 1>
 {
   double pi_1 = 1.0;
+  // the shear modulus (solver_set_shear): off (mu = 1) as created.  The cell array is allocated by the first call that
+  // brings one and kept; shear_cell says whether the kernels read it or the scalar
+  bool has_shear = false, shear_cell = false;
+  double shear_mu = 1.0;
+  eqlb::DevBuf<double> shear;
 };
 
 namespace eqlb
@@ -59,21 +64,40 @@ struct ElastCellArgs
 // (eqlb_primal_elast_cell.inc): Mass<P> is staged behind the three tables and wm m^r[i] (diagonal: wm Mass[i][i]) is
 // added to the value formed without the term.  A kernel of its own, so that a handle without the term launches the
 // instantiations - symbols, arguments and code - it launched before the term existed.
+//
+// The kernels with a cell-wise shear modulus (eqlb_elasticity_set_shear) are k_elast_cell_shear and
+// k_elast_cell_react_shear, again from the same source: y_loc = mu_T v with v the value formed without the term, then
+// + wm m as above.  The coefficient is a kernel argument of its own (ShearArgs), as ReactArgs is.
+#define EQLB_CELL_SHEAR 0
 #define EQLB_CELL_REACT 0
 #include "eqlb_primal_elast_cell.inc"
 #undef EQLB_CELL_REACT
 #define EQLB_CELL_REACT 1
 #include "eqlb_primal_elast_cell.inc"
 #undef EQLB_CELL_REACT
+#undef EQLB_CELL_SHEAR
+#define EQLB_CELL_SHEAR 1
+#define EQLB_CELL_REACT 0
+#include "eqlb_primal_elast_cell.inc"
+#undef EQLB_CELL_REACT
+#define EQLB_CELL_REACT 1
+#include "eqlb_primal_elast_cell.inc"
+#undef EQLB_CELL_REACT
+#undef EQLB_CELL_SHEAR
 
 // ---- host side ------------------------------------------------------------------------------------------------
 template <int P, int MODE>
-hipError_t launch_cell_d(int d, const ElastCellArgs& a, const ReactArgs* rx, hipStream_t stream)
+hipError_t launch_cell_d(int d, const ElastCellArgs& a, const ReactArgs* rx, const ShearArgs* sx, hipStream_t stream)
 {
   const dim3 grid(grid_of(a.ncells, ES_THREADS)), block(ES_THREADS);
   if constexpr (MODE != CELL_LOAD)
   {
-    if (rx) // the variant with the reaction term; without it the launch as before the term existed
+    // the variant with the terms the handle has; without one the launch as before the terms existed
+    if (rx && sx)
+      hipLaunchKernelGGL((k_elast_cell_react_shear<P, MODE, 0>), grid, block, 0, stream, a, *rx, *sx);
+    else if (sx)
+      hipLaunchKernelGGL((k_elast_cell_shear<P, MODE, 0>), grid, block, 0, stream, a, *sx);
+    else if (rx)
       hipLaunchKernelGGL((k_elast_cell_react<P, MODE, 0>), grid, block, 0, stream, a, *rx);
     else
       hipLaunchKernelGGL((k_elast_cell<P, MODE, 0>), grid, block, 0, stream, a);
@@ -97,18 +121,19 @@ hipError_t launch_cell_d(int d, const ElastCellArgs& a, const ReactArgs* rx, hip
 }
 
 template <int MODE>
-hipError_t launch_cell(int p, int d, const ElastCellArgs& a, const ReactArgs* rx, hipStream_t stream)
+hipError_t launch_cell(int p, int d, const ElastCellArgs& a, const ReactArgs* rx, const ShearArgs* sx,
+                       hipStream_t stream)
 {
   switch (p)
   {
   case 1:
-    return launch_cell_d<1, MODE>(d, a, rx, stream);
+    return launch_cell_d<1, MODE>(d, a, rx, sx, stream);
   case 2:
-    return launch_cell_d<2, MODE>(d, a, rx, stream);
+    return launch_cell_d<2, MODE>(d, a, rx, sx, stream);
   case 3:
-    return launch_cell_d<3, MODE>(d, a, rx, stream);
+    return launch_cell_d<3, MODE>(d, a, rx, sx, stream);
   default:
-    return launch_cell_d<4, MODE>(d, a, rx, stream);
+    return launch_cell_d<4, MODE>(d, a, rx, sx, stream);
   }
 }
 
@@ -130,7 +155,8 @@ hipError_t launch_cell(const eqlb_elasticity& h, const ManyCols& c, int d, const
   a.yloc = h.yloc;
   a.st = c.check ? c.st : nullptr;
   const ReactArgs rx = react_args(h);
-  return launch_cell<MODE>(h.p, d, a, h.has_react ? &rx : nullptr, stream);
+  const ShearArgs sx{h.shear_cell ? h.shear.get() : nullptr, h.shear_mu};
+  return launch_cell<MODE>(h.p, d, a, h.has_react ? &rx : nullptr, h.has_shear ? &sx : nullptr, stream);
 }
 } // namespace
 
@@ -186,6 +212,13 @@ int eqlb_elasticity_set_reaction(eqlb_elasticity_t* h, double c, const double* c
 try
 {
   return eqlb::solver_set_reaction("eqlb_elasticity_set_reaction", h, c, cell_c, memspace, stream_);
+}
+EQLB_CATCH_ALL
+
+int eqlb_elasticity_set_shear(eqlb_elasticity_t* h, double mu, const double* cell_mu, int32_t memspace, void* stream_)
+try
+{
+  return eqlb::solver_set_shear("eqlb_elasticity_set_shear", h, mu, cell_mu, memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -81,145 +81,24 @@ __device__ __forceinline__ double sorted_sum(double (&t)[N])
   return s;
 }
 
-template <int P, int D, bool STRESS>
-__global__ void __launch_bounds__(PF_THREADS)
-k_primal_flux(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __restrict__ cell_dofs,
-              const double* __restrict__ u, const double* __restrict__ cellJ, const double* __restrict__ coeff,
-              double pi_1, const PrimalOp<P, D> op, double* __restrict__ out)
+// the shear modulus of eqlb_primal_stress_dg_mu: mu_T = cell_mu[cell] where given, else the scalar mu.  A kernel
+// argument of its own, which k_primal_flux does not take.
+struct StressMuArgs
 {
-  constexpr int NP = nd_of(P), ND = nd_of(D), ROW = 2 * ND, S = ROW + 1;
-  constexpr int NBUF = (PF_THREADS * S > (PF_THREADS * NP + 1) / 2) ? PF_THREADS * S : (PF_THREADS * NP + 1) / 2;
-  __shared__ double sPG[2 * ND * NP];
-  __shared__ double sbuf[NBUF]; // first the index rows of the workgroup, then its output rows
-  const int t = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * PF_THREADS;
-  const int nloc = (ncells - base < PF_THREADS) ? (int)(ncells - base) : PF_THREADS;
-  const bool active = t < nloc;
-  for (int i = t; i < 2 * ND * NP; i += PF_THREADS)
-    sPG[i] = op.v[i];
-  int32_t* sidx = reinterpret_cast<int32_t*>(sbuf);
-  const int32_t* rows = cell_dofs + base * NP;
-  for (int e = t; e < nloc * NP; e += PF_THREADS)
-    sidx[e] = rows[e];
-  __syncthreads();
-  int32_t idx[NP];
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < NP; ++i)
-  {
-    idx[i] = active ? sidx[t * NP + i] : 0;
-    ok = ok && idx[i] >= 0 && (int64_t)idx[i] < ndofs;
-  }
-  double K00 = 0.0, K01 = 0.0, K10 = 0.0, K11 = 0.0, kap = 1.0;
-  if (active)
-  {
-    const double2* Jp = reinterpret_cast<const double2*>(cellJ + 4 * (base + t));
-    const double2 r0 = Jp[0], r1 = Jp[1]; // J00 J01 | J10 J11
-    const double idet = 1.0 / (r0.x * r1.y - r0.y * r1.x);
-    K00 = r1.y * idet;
-    K01 = -r0.y * idet;
-    K10 = -r1.x * idet;
-    K11 = r0.x * idet;
-    if (coeff)
-      kap = coeff[base + t];
-    else if constexpr (STRESS)
-      kap = pi_1;
-  }
-  const double bad = __longlong_as_double(0x7ff8000000000000ll);
-  __syncthreads(); // the index rows are in registers: sbuf takes the output rows
-  if constexpr (!STRESS)
-  {
-    for (int r = 0; r < nrhs; ++r)
-    {
-      if (active)
-      {
-        const double* ur = u + (int64_t)r * ndofs;
-        double uu[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-          uu[i] = ok ? ur[idx[i]] : 0.0;
-#pragma unroll
-        for (int n = 0; n < ND; ++n)
-        {
-          double g[2];
-#pragma unroll
-          for (int X = 0; X < 2; ++X)
-          {
-            double tt[NP];
-#pragma unroll
-            for (int i = 0; i < NP; ++i)
-              tt[i] = __dmul_rn(sPG[(X * ND + n) * NP + i], uu[i]);
-            g[X] = sorted_sum<NP>(tt);
-          }
-          const double f0 = -kap * (K00 * g[0] + K10 * g[1]), f1 = -kap * (K01 * g[0] + K11 * g[1]);
-          sbuf[t * S + 2 * n] = ok ? f0 : bad;
-          sbuf[t * S + 2 * n + 1] = ok ? f1 : bad;
-        }
-      }
-      __syncthreads();
-      double* o = out + ((int64_t)r * ncells + base) * ROW;
-      for (int e = t; e < nloc * ROW; e += PF_THREADS)
-        o[e] = sbuf[(e / ROW) * S + (e % ROW)];
-      __syncthreads();
-    }
-  }
-  else
-  {
-    double val[2][ROW]; // rows of -sigma
-    if (active)
-    {
-      double uu[2][NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-      {
-        const double2 w = ok ? reinterpret_cast<const double2*>(u)[idx[i]] : make_double2(0.0, 0.0);
-        uu[0][i] = w.x;
-        uu[1][i] = w.y;
-      }
-#pragma unroll
-      for (int n = 0; n < ND; ++n)
-      {
-        double gu[2][2]; // gu[r][d] = d_d u_r
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-        {
-          double g[2];
-#pragma unroll
-          for (int X = 0; X < 2; ++X)
-          {
-            double tt[NP];
-#pragma unroll
-            for (int i = 0; i < NP; ++i)
-              tt[i] = __dmul_rn(sPG[(X * ND + n) * NP + i], uu[r][i]);
-            g[X] = sorted_sum<NP>(tt);
-          }
-          gu[r][0] = K00 * g[0] + K10 * g[1];
-          gu[r][1] = K01 * g[0] + K11 * g[1];
-        }
-        const double ld = kap * (gu[0][0] + gu[1][1]), sh = gu[0][1] + gu[1][0];
-        val[0][2 * n] = ok ? -(2.0 * gu[0][0] + ld) : bad;
-        val[0][2 * n + 1] = ok ? -sh : bad;
-        val[1][2 * n] = ok ? -sh : bad;
-        val[1][2 * n + 1] = ok ? -(2.0 * gu[1][1] + ld) : bad;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-    {
-      if (active)
-      {
-#pragma unroll
-        for (int j = 0; j < ROW; ++j)
-          sbuf[t * S + j] = val[r][j];
-      }
-      __syncthreads();
-      double* o = out + ((int64_t)r * ncells + base) * ROW;
-      for (int e = t; e < nloc * ROW; e += PF_THREADS)
-        o[e] = sbuf[(e / ROW) * S + (e % ROW)];
-      __syncthreads();
-    }
-  }
-}
+  const double* cell_mu = nullptr; // [ncells] or nullptr
+  double mu = 1.0;
+};
+
+// k_primal_flux<P, D, STRESS> and, from the same source (eqlb_primal_flux_kernel.inc), k_primal_stress_mu<P, D>: the
+// stress with a cell-wise shear modulus, every output value mu_T times the value k_primal_flux<P, D, true> forms,
+// rounded once.  A kernel of its own, so that eqlb_primal_flux_dg and eqlb_primal_stress_dg launch the symbols,
+// arguments and code they launched before (tools/isa_compare.py).
+#define EQLB_FLUX_MU 0
+#include "eqlb_primal_flux_kernel.inc"
+#undef EQLB_FLUX_MU
+#define EQLB_FLUX_MU 1
+#include "eqlb_primal_flux_kernel.inc"
+#undef EQLB_FLUX_MU
 
 // The projected VALUE of a P_p function, the piece that turns c u_h into the right-hand side the equilibrator needs for
 // an operator with a reaction term (rhs = Pi_d f - c_T Pi_d u_h):
@@ -308,7 +187,7 @@ static void builtin_table(double* out)
 template <int P, int D>
 static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
                             const double* u, const double* cellJ, const double* coeff, double pi_1, const double* op,
-                            double* out, hipStream_t stream)
+                            double* out, const StressMuArgs* sx, hipStream_t stream)
 {
   PrimalOp<P, D> tab;
   if (op)
@@ -316,7 +195,10 @@ static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t n
   else
     builtin_table<P, D>(tab.v);
   const unsigned grid = (unsigned)(((int64_t)ncells + PF_THREADS - 1) / PF_THREADS);
-  if (stress)
+  if (stress && sx) // the variant with the shear modulus; without it the launch as before the term existed
+    hipLaunchKernelGGL((k_primal_stress_mu<P, D>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs, cell_dofs,
+                       u, cellJ, coeff, pi_1, tab, out, *sx);
+  else if (stress)
     hipLaunchKernelGGL((k_primal_flux<P, D, true>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs,
                        cell_dofs, u, cellJ, coeff, pi_1, tab, out);
   else
@@ -328,18 +210,18 @@ static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t n
 template <int P>
 static hipError_t launch_p(int d, bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
                            const double* u, const double* cellJ, const double* coeff, double pi_1, const double* op,
-                           double* out, hipStream_t stream)
+                           double* out, const StressMuArgs* sx, hipStream_t stream)
 {
   switch (d)
   {
   case 0:
-    return launch_pd<P, 0>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_pd<P, 0>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   case 1:
-    return launch_pd<P, 1>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_pd<P, 1>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   case 2:
-    return launch_pd<P, 2>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_pd<P, 2>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   default:
-    return launch_pd<P, 3>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_pd<P, 3>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   }
 }
 
@@ -347,18 +229,18 @@ static hipError_t launch_p(int d, bool stress, int32_t ncells, int32_t nrhs, int
 static hipError_t launch_primal_flux(int p, int d, bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs,
                                      const int32_t* cell_dofs, const double* u, const double* cellJ,
                                      const double* coeff, double pi_1, const double* op, double* out,
-                                     hipStream_t stream)
+                                     const StressMuArgs* sx, hipStream_t stream)
 {
   switch (p)
   {
   case 1:
-    return launch_p<1>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_p<1>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   case 2:
-    return launch_p<2>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_p<2>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   case 3:
-    return launch_p<3>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_p<3>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   default:
-    return launch_p<4>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, stream);
+    return launch_p<4>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
   }
 }
 
@@ -382,10 +264,12 @@ static int table_p(int d, double* out)
   return 2 * nd_of(d) * nd_of(P);
 }
 
-// the common body of the two entry points; stress: u [ndofs][2], two output rows, coeff = cell_pi1
+// the common body of the entry points; stress: u [ndofs][2], two output rows, coeff = cell_pi1.  shear: the mu / cell_mu
+// of eqlb_primal_stress_dg_mu (cell_mu in `memspace`) or nullptr; mu == 1 without an array is the call without it
 static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32_t d, int32_t nrhs, bool stress,
                             const int32_t* cell_dofs, int64_t ndofs, const double* u, const double* coeff,
-                            double pi_1, const double* op, double* flux_dg, int32_t memspace, void* stream_)
+                            double pi_1, const double* op, double* flux_dg, int32_t memspace, void* stream_,
+                            const StressMuArgs* shear = nullptr)
 {
   if (p < 1 || p > PF_PMAX || d < 0 || d > PF_DMAX)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degrees p = %d, degree_dg = %d outside 1 ... 4, 0 ... 3", who, (int)p,
@@ -395,16 +279,28 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
   if (!mesh || !cell_dofs || !u || !flux_dg || ndofs < 1 || ndofs > INT32_MAX)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: invalid argument", who);
   EQLB_TRY(check_memspace(who, memspace));
+  if (shear && !shear->cell_mu)
+  {
+    if (!(shear->mu > 0.0 && std::isfinite(shear->mu)))
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: mu = %g is zero, negative, NaN or infinite", who, shear->mu);
+    if (shear->mu == 1.0)
+      shear = nullptr; // the kernel without the term
+  }
   const DeviceMesh& m = mesh->m;
   const int np = nd_of(p), nd = nd_of(d);
   const int32_t ncells = m.ncells;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (memspace == EQLB_MEM_DEVICE)
   {
-    const hipError_t e
-        = launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, cell_dofs, u, m.cellJ, coeff, pi_1, op, flux_dg, stream);
+    const hipError_t e = launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, cell_dofs, u, m.cellJ, coeff, pi_1, op,
+                                            flux_dg, shear, stream);
     return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
   }
+  if (shear && shear->cell_mu)
+    for (int32_t i = 0; i < ncells; ++i)
+      if (!(shear->cell_mu[i] > 0.0 && std::isfinite(shear->cell_mu[i])))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
+                    shear->cell_mu[i]);
   // host memory: bad tables are caught here, before anything is launched
   const size_t nidx = (size_t)ncells * np;
   for (size_t i = 0; i < nidx; ++i)
@@ -415,10 +311,13 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
   HostCall s;
   const auto d_idx = s.in(cell_dofs, nidx);
   const auto d_u = s.in(u, nu), d_c = s.in(coeff, (size_t)ncells);
+  const auto d_mu = s.in(shear ? shear->cell_mu : nullptr, (size_t)ncells);
   const auto d_out = s.out(flux_dg, nout);
   if (s.upload(stream) != hipSuccess)
     return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
-  s.note(launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, d_idx, d_u, m.cellJ, d_c, pi_1, op, d_out, stream));
+  const StressMuArgs sx{shear && shear->cell_mu ? d_mu.get() : nullptr, shear ? shear->mu : 1.0};
+  s.note(launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, d_idx, d_u, m.cellJ, d_c, pi_1, op, d_out,
+                            shear ? &sx : nullptr, stream));
   const hipError_t e = s.finish(stream);
   return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
 }
@@ -557,6 +456,15 @@ int eqlb_primal_stress_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const
 {
   return eqlb::primal_flux_call("eqlb_primal_stress_dg", mesh, p, degree_dg, 1, true, cell_dofs, ndofs, u, cell_pi1,
                                 pi_1, op, flux_dg, memspace, stream);
+}
+
+int eqlb_primal_stress_dg_mu(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const int32_t* cell_dofs, int64_t ndofs,
+                             const double* u, double pi_1, const double* cell_pi1, double mu, const double* cell_mu,
+                             const double* op, double* flux_dg, int32_t memspace, void* stream)
+{
+  const eqlb::StressMuArgs shear{cell_mu, mu};
+  return eqlb::primal_flux_call("eqlb_primal_stress_dg_mu", mesh, p, degree_dg, 1, true, cell_dofs, ndofs, u, cell_pi1,
+                                pi_1, op, flux_dg, memspace, stream, &shear);
 }
 
 int eqlb_get_primal_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity)

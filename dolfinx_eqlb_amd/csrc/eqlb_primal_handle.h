@@ -35,6 +35,14 @@ struct ReactArgs
   double c = 0.0;
 };
 
+// the shear modulus of the elasticity cell kernel (include/eqlb.h): mu_T = cell_mu[cell] where given, else the scalar mu.
+// A kernel argument of its own, which the kernels without the term do not take.
+struct ShearArgs
+{
+  const double* cell_mu = nullptr; // [ncells] or nullptr
+  double mu = 1.0;
+};
+
 // what eqlb_primal_t and eqlb_elasticity_t share; everything but the grown work space is carved out of one allocation at
 // create
 template <int BS, int MAXC>
@@ -392,6 +400,45 @@ int solver_set_reaction(const char* who, H* h, double c, const double* cell_c, i
   h->react_cell = cell_c != nullptr;
   h->react_c = cell_c ? 0.0 : c;
   h->has_react = cell_c != nullptr || c != 0.0;
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (host)
+    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)
+  return EQLB_OK;
+}
+
+// mu_T = cell_mu [ncells] in `memspace` where given, else the scalar mu; mu == 1 without an array switches the term off.
+// For a handle type that holds the members has_shear, shear_cell, shear_mu and shear (the elasticity unit).  A host
+// array is checked before the handle changes; one in device memory is the caller's responsibility, as cell_c is.  The
+// diagonal of the handle is formed again in place on the stream.
+template <class H>
+int solver_set_shear(const char* who, H* h, double mu, const double* cell_mu, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  if (!cell_mu && !(mu > 0.0 && std::isfinite(mu)))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: mu = %g is zero, negative, NaN or infinite", who, mu);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t nc = (size_t)h->space.ncells;
+  if (cell_mu && host)
+    for (size_t i = 0; i < nc; ++i)
+      if (!(cell_mu[i] > 0.0 && std::isfinite(cell_mu[i])))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%lld] = %g is zero, negative, NaN or infinite", who,
+                    (long long)i, cell_mu[i]);
+  if (cell_mu)
+  {
+    if (!h->shear.get())
+    {
+      const hipError_t e = h->shear.alloc_raw(nc);
+      if (e != hipSuccess)
+        return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed: %s", who, hipGetErrorString(e));
+    }
+    HIP_TRY(hipMemcpyAsync(h->shear.get(), cell_mu, nc * sizeof(double),
+                           host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+  }
+  h->shear_cell = cell_mu != nullptr;
+  h->shear_mu = cell_mu ? 1.0 : mu;
+  h->has_shear = cell_mu != nullptr || mu != 1.0;
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
   if (host)
     HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)

@@ -481,6 +481,19 @@ struct PrimalElasticity
     }
     check(eqlb_elasticity_set_reaction(h, c, cell_c.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
   }
+  // sigma = mu (2 eps(u) + pi_1 div(u) I): cell_mu [ncells] where given, else the scalar mu; mu == 1 without an array
+  // switches the term off
+  void set_shear(double mu, py::object cell_mu)
+  {
+    carray<double> kc;
+    if (!cell_mu.is_none())
+    {
+      kc = cell_mu.cast<carray<double>>();
+      if (kc.size() != mesh->ncells)
+        throw std::runtime_error("PrimalElasticity.set_shear: cell_mu [ncells] expected");
+    }
+    check(eqlb_elasticity_set_shear(h, mu, cell_mu.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
+  }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
     if (degree_dg >= 0 && degree_dg <= 3
@@ -1574,6 +1587,10 @@ PYBIND11_MODULE(_cpp, m)
       .def("set_reaction", &PrimalElasticity::set_reaction, py::arg("c") = 0.0, py::arg("cell_c") = py::none(),
            "the operator gains + c u: cell_c [ncells] where given, else the scalar; c = 0 without an array switches "
            "the term off; Multilevel.set_coarse(True) has to be called again afterwards")
+      .def("set_shear", &PrimalElasticity::set_shear, py::arg("mu") = 1.0, py::arg("cell_mu") = py::none(),
+           "the stress becomes mu (2 eps(u) + pi_1 div(u) I): cell_mu [ncells] where given, else the scalar, mu > 0; "
+           "mu = 1 without an array switches the term off; the reaction term is not scaled; "
+           "Multilevel.set_coarse(True) has to be called again afterwards")
       .def("load", &PrimalElasticity::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
            "b [2 ndofs] from DG_d nodal values rhs_dg [2, ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalElasticity::apply, py::arg("u"), py::arg("masked") = false,

@@ -245,10 +245,14 @@ def check_weak_symmetry_condition(mesh, k, sigma, rtol=1e-5, atol=1e-8) -> bool:
     return bool(np.allclose(weak_symmetry_residual(mesh, k, sigma)[1], 0.0, rtol=rtol, atol=atol))
 
 
-def stress_estimator_terms(mesh, k, sigma, korn=None, pi_1=1.0):
+def stress_estimator_terms(mesh, k, sigma, korn=None, pi_1=1.0, cell_pi1=None, mu=1.0, cell_mu=None):
     """Cell-wise terms of the stress estimator (demo/elasticity/demo_error_estimation.py:100-121), numpy
     statement with quadrature: (int dsig : A dsig, int (C_K (dsig_01 - dsig_10) / 2)^2) for the rows
-    sigma [2, ncells*k(k+2)]; A tau = (tau - pi_1 / (2 + 2 pi_1) tr(tau) I) / 2."""
+    sigma [2, ncells*k(k+2)]; A tau = (tau - pi_1 / (2 + 2 pi_1) tr(tau) I) / 2.
+    For sigma = mu_T (2 eps(u) + pi_T div(u) I) (eqlb_se_estimate_stress_mu): cell_pi1 [ncells] replaces the scalar pi_1,
+    and both terms are divided by mu_T = cell_mu [ncells] where given, else the scalar mu - A_T = A(pi_T) / mu_T, and the
+    Korn bound of the weak-symmetry term picks up 1 / mu_T since |||e|||^2_T >= 2 mu_T ||eps(e)||^2_T.  The defaults
+    give the values without the keywords."""
     J, detJ, K = cell_geometry(mesh)
     rt = ert.HierarchicRT(k)
     qp, qw = make_quadrature_triangle(2 * k)
@@ -260,8 +264,15 @@ def stress_estimator_terms(mesh, k, sigma, korn=None, pi_1=1.0):
     tr = val[0, ..., 0] + val[1, ..., 1]
     asym = val[0, ..., 1] - val[1, ..., 0]
     ck = np.ones(mesh.ncells) if korn is None else np.asarray(korn)
+    if cell_pi1 is not None:
+        pi_1 = np.asarray(cell_pi1, dtype=np.float64).ravel()
     energy = 0.5 * (fro - pi_1 / (2.0 + 2.0 * pi_1) * np.einsum("cq,cq,cq->c", w, tr, tr))
     wsym = 0.25 * ck ** 2 * np.einsum("cq,cq,cq->c", w, asym, asym)
+    if cell_mu is not None or mu != 1.0:
+        m = np.asarray(cell_mu, dtype=np.float64).ravel() if cell_mu is not None else float(mu)
+        if not np.all((m > 0.0) & np.isfinite(m)):
+            raise ValueError("stress_estimator_terms: mu is zero, negative, NaN or infinite")
+        energy, wsym = energy / m, wsym / m
     return energy, wsym
 
 

@@ -36,6 +36,14 @@ one product and one addition on top of the value formed without the term; everyt
 the owner sum, the mask, the residual, the reference norm and pcg are unchanged.  c = 0 without an array switches the
 term off: the operator is then the one of a fresh object, bit for bit.
 
+THE SHEAR MODULUS (ElasticityOperator.set_shear; eqlb_elasticity_set_shear): the operator becomes
+-div(mu (2 eps(u) + pi_1 div(u) I)) [+ c u] with mu_T > 0 per cell, one scalar or a cell-wise array in the pi_1 /
+cell_pi1 convention.  Per cell, with v the value of the elasticity rule below (before any reaction term),
+  y_loc[c][i][r] = mu_T v;   with a reaction term  y_loc[c][i][r] = (mu_T v) + wm m^r[i]
+one product on top of the value formed without the term, no fused multiply-add; the reaction term is not scaled by
+mu.  The diagonal follows the same rule, the load is unchanged.  mu = 1 without an array switches the term off: the
+operator is then the one of a fresh object, bit for bit; a uniform power of two scales every bit pattern exactly.
+
 value_dg states eqlb_primal_value_dg, the piece that turns c u_h into the right-hand side the equilibrator needs
 (rhs = Pi_d f - c_T Pi_d u_h): out[r][c][n] = coeff[c] sum_i PV<p,d>[n][i] u[r][cell_dofs[c][i]], ascending i, every
 product rounded on its own, with PV<p,d> [nd_d][nd_p] the DG_d nodal values of the L2 projection of phi_i onto P_d:
@@ -184,6 +192,23 @@ def reaction_coefficient(who, ncells, c=0.0, cell_c=None):
     if bad.size:
         raise ValueError(f"{who}: cell_c[{int(bad[0])}] = {cc[bad[0]]} is negative, NaN or infinite")
     return cc
+
+
+def shear_coefficient(who, ncells, mu=1.0, cell_mu=None):
+    """mu_T [ncells] of set_shear, or None where the term is switched off (mu == 1 without an array).  A coefficient
+    that is zero, negative, NaN or infinite is refused, the cell named."""
+    if cell_mu is None:
+        mu = float(mu)
+        if not (mu > 0.0 and np.isfinite(mu)):
+            raise ValueError(f"{who}: mu = {mu} is zero, negative, NaN or infinite")
+        return None if mu == 1.0 else np.full(ncells, mu)
+    mm = np.array(cell_mu, dtype=np.float64).ravel()
+    if mm.size != ncells:
+        raise ValueError(f"{who}: cell_mu [ncells] expected")
+    bad = np.nonzero(~((mm > 0.0) & np.isfinite(mm)))[0]
+    if bad.size:
+        raise ValueError(f"{who}: cell_mu[{int(bad[0])}] = {mm[bad[0]]} is zero, negative, NaN or infinite")
+    return mm
 
 
 def cross_table(p):
@@ -543,8 +568,23 @@ class ElasticityOperator(PoissonOperator):
         self.M = (S[0], C, np.ascontiguousarray(C.T), S[2])                     # M_00, M_01, M_10, M_11
         self.Mass = mass_table(p)
         self.wm = None
+        self.mu = None                        # mu_T [ncells]; None: no shear modulus (mu = 1)
         self.fixed = np.zeros(2 * self.ndofs, dtype=bool)
         self._slots()
+
+    def set_shear(self, mu=1.0, cell_mu=None):
+        """The stress becomes mu (2 eps(u) + pi_1 div(u) I): mu_T = cell_mu [ncells] where given, else the scalar mu on
+        every cell, mu_T > 0.  mu == 1 without an array switches the term off; a repeated call replaces the coefficient.
+        The reaction term of set_reaction is not scaled.  A DG_0 coefficient crosses a refinement through
+        Refinement.prolong_dg(0, cell_mu)."""
+        self.mu = shear_coefficient("set_shear", self.mesh.ncells, mu, cell_mu)
+
+    def _scale_shear(self, val, A=None):
+        """mu_T val on [ncells, nd] (A: the same, or None); unchanged without the term."""
+        if self.mu is None:
+            return val, A
+        m = self.mu[:, None]
+        return m * val, (None if A is None else m * A)
 
     def set_dirichlet(self, facets_row0, facets_row1):
         """Fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r (the facets
@@ -577,7 +617,7 @@ class ElasticityOperator(PoissonOperator):
         n = lambda s, a, b: D[s][a][b][1]   # noqa: E731
         y0 = w * (((v(0, 0, 0) + v(0, 1, 1)) + (v(0, 0, 0) + v(1, 1, 0))) + pi * (v(0, 0, 0) + v(1, 0, 1)))
         y1 = w * (((v(1, 0, 0) + v(1, 1, 1)) + (v(0, 0, 1) + v(1, 1, 1))) + pi * (v(0, 1, 0) + v(1, 1, 1)))
-        ys = [y0, y1]
+        ys = [self._scale_shear(y)[0] for y in (y0, y1)]
         mm = [_sum_products(self.Mass, uc[:, :, r]) for r in range(2)] if self.wm is not None else None
         if mm is not None:
             ys = [self._add_reaction(ys[r], None, *mm[r])[0] for r in range(2)]
@@ -586,7 +626,7 @@ class ElasticityOperator(PoissonOperator):
             return val
         a0 = wa * (((n(0, 0, 0) + n(0, 1, 1)) + (n(0, 0, 0) + n(1, 1, 0))) + pa * (n(0, 0, 0) + n(1, 0, 1)))
         a1 = wa * (((n(1, 0, 0) + n(1, 1, 1)) + (n(0, 0, 1) + n(1, 1, 1))) + pa * (n(0, 1, 0) + n(1, 1, 1)))
-        ab = [a0, a1]
+        ab = [self._scale_shear(a0, a0)[1], self._scale_shear(a1, a1)[1]]
         if mm is not None:
             ab = [ab[r] + self.wm[:, None] * mm[r][1] for r in range(2)]
         return val, np.stack(ab, axis=2)
@@ -623,6 +663,7 @@ class ElasticityOperator(PoissonOperator):
         val = [w * (((D[0][0][0] + D[1][1][0]) + D[r][r][0]) + pi * D[r][r][0]) for r in range(2)]
         A = [np.abs(w) * (((D[0][0][1] + D[1][1][1]) + D[r][r][1]) + np.abs(pi) * D[r][r][1]) for r in range(2)]
         md = np.broadcast_to(np.diagonal(self.Mass)[None, :], (self.mesh.ncells, self.nd))
+        val, A = zip(*[self._scale_shear(val[r], A[r]) for r in range(2)])
         val, A = zip(*[self._add_reaction(val[r], A[r], md, md) for r in range(2)])
         d = self.owner_sum(np.stack(val, axis=2))
         return (d, self.owner_sum(np.stack(A, axis=2))) if return_abs else d

@@ -35,13 +35,17 @@ class PrimalFlux:
 
 @dataclasses.dataclass
 class PrimalStress:
-    """Row `row` (0 or 1) of sigma_h = -(2 eps(u_h) + pi_1 div(u_h) I) of a displacement u [ndofs, 2] in P_p^2 as an
-    entry of `data` of local_projection (cpp.primal_stress_dg); pi_1 a number or an array [ncells]."""
+    """Row `row` (0 or 1) of sigma_h = -mu (2 eps(u_h) + pi_1 div(u_h) I) of a displacement u [ndofs, 2] in P_p^2 as an
+    entry of `data` of local_projection (cpp.primal_stress_dg); pi_1 a number or an array [ncells].  The shear modulus
+    is mu > 0 everywhere, or cell_mu [ncells] where given; a DG_0 cell_mu crosses a refinement through
+    Refinement.prolong_dg(0, cell_mu).  The defaults give the non-dimensional stress (mu = 1)."""
     u: typing.Any
     cell_dofs: typing.Any
     p: int
     pi_1: typing.Any
     row: int
+    mu: float = 1.0
+    cell_mu: typing.Any = None
 
 
 @dataclasses.dataclass
@@ -93,7 +97,7 @@ def _project_primal(dmesh, degree, d):
     if isinstance(d, PrimalStress):
         per_cell = np.ndim(d.pi_1) > 0
         out = cpp.primal_stress_dg(dm, d.p, degree, d.cell_dofs, d.u, 1.0 if per_cell else float(d.pi_1),
-                                   d.pi_1 if per_cell else None)
+                                   d.pi_1 if per_cell else None, mu=float(d.mu), cell_mu=d.cell_mu)
         return np.ascontiguousarray(out[d.row])
     return cpp.primal_flux_dg(dm, d.p, degree, d.cell_dofs, np.asarray(d.u, dtype=np.float64).reshape(1, -1),
                               d.coeff)[0]

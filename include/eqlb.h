@@ -367,6 +367,19 @@ int eqlb_primal_stress_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const
                           const double* u, double pi_1, const double* cell_pi1, const double* op, double* flux_dg,
                           int32_t memspace, void* stream);
 
+/* eqlb_primal_stress_dg with a shear modulus: sigma_h = mu_T (2 eps(u_h) + pi_1,T div(u_h) I), the dimensional law of a
+ * heterogeneous medium (a stiff inclusion, a laminate, a bimaterial interface).
+ *   mu, cell_mu [ncells] or NULL  mu_T > 0 per cell where cell_mu (in `memspace`) is given, else the scalar
+ * Every output value is mu_T times the value eqlb_primal_stress_dg forms, rounded once: a kernel variant compiled from
+ * the same source.  With mu = 1 and no array the entry launches the kernel of eqlb_primal_stress_dg and gives its bits.
+ * A coefficient that is <= 0, NaN or infinite: EQLB_ERR_INVALID_ARGUMENT, the cell named (the scalar always; an array
+ * in the host memory space: before anything is launched; an array in device memory is the caller's responsibility).
+ * A DG_0 coefficient crosses a refinement through eqlb_refine_prolong_dg (degree 0).  Everything else as
+ * eqlb_primal_stress_dg, which is untouched. */
+int eqlb_primal_stress_dg_mu(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const int32_t* cell_dofs, int64_t ndofs,
+                             const double* u, double pi_1, const double* cell_pi1, double mu, const double* cell_mu,
+                             const double* op, double* flux_dg, int32_t memspace, void* stream);
+
 /* The built-in table PG<p,d> [2][nd_d][nd_p] of eqlb_primal_flux_dg, host only (like eqlb_get_reference_table):
  * returns the number of doubles copied (<= capacity), or a negative error. */
 int eqlb_get_primal_table(int32_t p, int32_t degree_dg, double* out, int32_t capacity);
@@ -489,6 +502,26 @@ int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t
 int eqlb_se_estimate_stress(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv, const double* korn,
                             double pi_1, double* cell_energy, double* cell_wsym, double* node_asym,
                             int32_t memspace, void* stream);
+
+/* eqlb_se_estimate_stress for sigma = mu_T (2 eps(u) + pi_T div(u) I) with cell-wise coefficients:
+ *   pi_1, cell_pi1 [ncells] or NULL  pi_T per cell where cell_pi1 is given, else the scalar
+ *   mu, cell_mu [ncells] or NULL     mu_T > 0 per cell where cell_mu is given, else the scalar
+ *   cell_energy = (0.5 (fro - pi_T / (2 + 2 pi_T) tr2)) / mu_T      fro, tr2, as2: the integrals of |delta_sigma|^2,
+ *   cell_wsym   = (0.25 C_K^2 as2) / mu_T                           tr(delta_sigma)^2, (delta_sigma_01 - delta_sigma_10)^2
+ *   node_asym   unchanged                                           that eqlb_se_estimate_stress forms
+ * that is the value of eqlb_se_estimate_stress with pi_1 = pi_T, divided by mu_T (one more rounding).  With no arrays
+ * and mu = 1 the entry launches the kernel of eqlb_se_estimate_stress and gives its bits.
+ * Why 1 / mu_T: the compliance of the law is A_T = A(pi_T) / mu_T, which gives the energy term.  The error's energy norm
+ * satisfies |||e|||^2_T >= 2 mu_T ||eps(e)||^2_T, so every term that bounds a product (., grad e)_T through the Korn
+ * constant, ||grad e||_T <= C_K ||eps(e)||_T <= C_K |||e|||_T / sqrt(2 mu_T), picks up 1 / mu_T next to C_K^2.  For a
+ * global constant mu = m the bound is that of mu = 1 with both sides divided by m, exactly.  The oscillation term needs
+ * no entry of its own: pass korn / sqrt(cell_mu) as the `korn` argument of eqlb_oscillation.  The Korn constants
+ * themselves are those of the mesh (mu does not enter eqlb_se_kornconst).
+ * Refused (EQLB_ERR_INVALID_ARGUMENT): mu or, in the host memory space, a cell_mu[i] that is <= 0, NaN or infinite, the
+ * cell named; pi_1 or a cell_pi1[i] not above -1.  Arrays in device memory are the caller's responsibility. */
+int eqlb_se_estimate_stress_mu(eqlb_mesh_t* mesh, int32_t k, const double* flux_hdiv, const double* korn, double pi_1,
+                               const double* cell_pi1, double mu, const double* cell_mu, double* cell_energy,
+                               double* cell_wsym, double* node_asym, int32_t memspace, void* stream);
 
 /* Data oscillation per cell,  out [nrhs][ncells] = C_K^2 (h_T / pi)^2 || f - div(sigma) ||^2_L2(T)
  * (err_osc of demo/poisson/demo_error_estimation.py:96-98 and, with the Korn constant, of
@@ -1052,6 +1085,21 @@ int eqlb_elasticity_set_dirichlet(eqlb_elasticity_t* handle, int32_t nlist0, con
 /* The reaction term + c u of eqlb_primal_set_reaction, word for word (the rule is stated there). */
 int eqlb_elasticity_set_reaction(eqlb_elasticity_t* handle, double c, const double* cell_c, int32_t memspace,
                                  void* stream);
+/* The shear modulus: the operator becomes -div(mu_T (2 eps(u) + pi_1,T div(u) I)) [+ c u], mu_T > 0 per cell: cell_mu
+ * [ncells] in `memspace` where given (copied), else the scalar mu, in the pi_1 / cell_pi1 convention.  One product on
+ * top of the value v = |det J| ((...) + pi_c (...)) the cell kernel forms without the term, no fused multiply-add:
+ *   y_loc = mu_T v;   with a reaction term y_loc = (mu_T v) + wm m (the reaction term is NOT scaled by mu);
+ * the diagonal follows the same rule and the load is unchanged.  The kernels are variants compiled from the same source
+ * with the coefficient as an argument of their own: a handle without the term launches the symbols, arguments and code
+ * it launched before.  apply, diagonal, residual and solve pick the variant from the handle, and so does a hierarchy
+ * that holds it.  set_shear(1.0, NULL) switches the term off again: the bits are those of a fresh handle.  A repeated
+ * call replaces the coefficient.  The stored diagonal of the handle is formed again on `stream`; after a change on level
+ * 0 of a hierarchy eqlb_hierarchy_set_coarse(handle, 1, ...) has to be called again, since the factor of the exact
+ * coarse solve is not.  Refused (EQLB_ERR_INVALID_ARGUMENT), the handle left as it was: a null handle, an unknown memory
+ * space, mu or, in the host memory space, a cell_mu[i] that is <= 0, NaN or infinite, the cell named.  An array in device
+ * memory is the caller's responsibility, as for eqlb_primal_set_reaction. */
+int eqlb_elasticity_set_shear(eqlb_elasticity_t* handle, double mu, const double* cell_mu, int32_t memspace,
+                              void* stream);
 int eqlb_elasticity_load(eqlb_elasticity_t* handle, int32_t degree_dg, const double* rhs_dg, const double* b_extra,
                          double* b, int32_t memspace, void* stream);
 int eqlb_elasticity_apply(eqlb_elasticity_t* handle, const double* u, double* y, int32_t masked, int32_t memspace,

@@ -42,6 +42,16 @@ tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all ar
              on every level for every tau of --taus (1e-2 and 1e-4) next to c = 0: iterations and time to rtol 1e-8 from zero of the
              Jacobi entry, of the hierarchy, and of the hierarchy with local smoothing and the exact coarse solve
              (factored again after every change of c).  One run each
+  --shear    instead of the figures above: the cell-wise shear modulus of set_shear (elasticity only).  (1) At --n, for every
+             degree: one masked elasticity product without and with the term (a cell-wise mu, log-uniform in [1e-3, 1e3])
+             ON THE SAME HANDLE in one process, switched by set_shear, and primal_stress_dg_mu (degree p - 1, the same mu)
+             against primal_stress_dg: after clock-settle probes, --repeats (>= 5) alternating blocks of --products calls
+             each; median and spread (max - min) of the time per call, and whether the difference exceeds the spread.
+             (2) With --multilevel: mu = the contrast on the cells of the coarsest mesh whose centroid lies right of
+             x = 1/2 and on their descendants, mu = 1 on the others, pi_1 = 1, for the contrasts 1, 10 and 1000, on the nine uniform levels of --multilevel and on an adaptive hierarchy
+             (create_unit_square(16), ten steps that refine the cells with a vertex on the interface; mu crosses the
+             refinements through prolong_dg): iterations and time to rtol 1e-8 from zero of the Jacobi entry, of the
+             hierarchy, and (adaptive) of the hierarchy with local smoothing and the exact coarse solve.  One run each
   --check-every LIB:N ...   the PCG of P_2 to rtol 1e-8 from zero once per library (builds of libeqlb_amd.so with
              -DEQLB_PRIMAL_CHECK_EVERY=N, tools/build_variant.sh NAME "-D..." eqlb_primal_solve), each in a child process
 Prints one line per figure and, last, one JSON line with all of them.  Nothing here is a pass/fail condition.
@@ -502,6 +512,129 @@ def run_reaction(args, cpp, torch, res):
         mlc.close()
 
 
+def run_shear(args, cpp, torch, res):
+    """the figures of --shear"""
+    from dolfinx_eqlb_amd.mesh import create_unit_square
+    dm = cpp.DeviceMesh(create_unit_square(args.n, shuffle_seed=3, perturb=0.15))
+    nc = dm.mesh.ncells
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    mu = 10.0 ** (-3.0 + 6.0 * torch.rand(nc, dtype=torch.float64, device="cuda", generator=gen))
+
+    def blocks(fns, probe):
+        """median, spread and all block times per state of fns = {state: (prepare, call)}"""
+        probes = settle_probes(probe)
+        t = {s_: [] for s_ in fns}
+        for _ in range(args.repeats):
+            for s_, (prepare, call) in fns.items():
+                prepare()
+                t[s_].append(timed_calls(torch, call, args.products))
+        r = dict(products=args.products, repeats=args.repeats, settle_probes=len(probes))
+        for s_ in fns:
+            r[s_] = dict(median_ms=float(np.median(t[s_])), spread_ms=float(np.ptp(t[s_])), all_ms=t[s_])
+        r["ratio"] = r["on"]["median_ms"] / r["off"]["median_ms"]
+        diff = r["on"]["median_ms"] - r["off"]["median_ms"]
+        r["difference_exceeds_spread"] = bool(abs(diff) > max(r["on"]["spread_ms"], r["off"]["spread_ms"]))
+        return r
+
+    def line(what, r):
+        return (f"{what} without the term {r['off']['median_ms']:.4f} ms (spread {r['off']['spread_ms']:.4f}), with it "
+                f"{r['on']['median_ms']:.4f} ms (spread {r['on']['spread_ms']:.4f}) = {r['ratio']:.3f} of it; the "
+                f"difference exceeds the spread: {r['difference_exceeds_spread']}; median of {args.repeats} blocks of "
+                f"{args.products} calls after {r['settle_probes']} probes")
+
+    for p in args.degrees:
+        h, _ = make_problem(cpp, torch, dm, p, True)
+        n = 2 * h.ndofs
+        x = torch.from_numpy(np.random.default_rng(0).standard_normal(n)).cuda()
+        y = torch.empty_like(x)
+
+        def product():
+            h.apply_raw(x.data_ptr(), y.data_ptr(), True)
+
+        def probe():
+            product()
+            torch.cuda.synchronize()
+
+        r = blocks({"off": (lambda: h.set_shear_raw(1.0, None), product),
+                    "on": (lambda: h.set_shear_raw(1.0, mu.data_ptr()), product)}, probe)
+        r.update(cells=nc, rows=n)
+        say(f"E_{p}: {n} rows; product " + line("", r))
+        res[f"SHEAR_PRODUCT_E{p}"] = r
+        h.close()
+        # the projected stress of degree p - 1
+        cd, ndofs = dm.lagrange_dofmap(p, device=True)
+        d = p - 1
+        out = torch.empty(2 * nc * (d + 1) * (d + 2), dtype=torch.float64, device="cuda")
+        u = x[:2 * ndofs]
+
+        def plain():
+            cpp.primal_stress_dg_raw(dm, p, d, cd.data_ptr(), ndofs, u.data_ptr(), 1.0, None, out.data_ptr())
+
+        def with_mu():
+            cpp.primal_stress_dg_mu_raw(dm, p, d, cd.data_ptr(), ndofs, u.data_ptr(), 1.0, None, 1.0, mu.data_ptr(),
+                                        out.data_ptr())
+
+        def probe_stress():
+            plain()
+            torch.cuda.synchronize()
+
+        r = blocks({"off": (lambda: None, plain), "on": (lambda: None, with_mu)}, probe_stress)
+        r.update(cells=nc, degree_dg=d)
+        say(f"E_{p}: primal_stress_dg of degree {d} " + line("", r))
+        res[f"SHEAR_STRESS_E{p}"] = r
+    if not args.multilevel:
+        return
+
+    def right_of(mesh):
+        return (mesh.x[mesh.cell_nodes, 0].mean(axis=1) > 0.5).astype(np.float64)
+
+    def contrasts(tag, dms, refs, forms):
+        right = [right_of(dms[0].mesh)]
+        for ref in refs:                                   # the side of a cell crosses a refinement as mu does
+            right.append(np.ascontiguousarray(ref.prolong_dg(0, right[-1])).ravel())
+        for p in args.degrees:
+            hs = []
+            for d_ in dms[:-1]:
+                bf = d_.mesh.boundary_facets()
+                hs.append(cpp.PrimalElasticity(d_, p, 1.0))
+                hs[-1].set_dirichlet(bf, bf)
+            top, b = make_problem(cpp, torch, dms[-1], p, True)
+            hs.append(top)
+            mls = {name: cpp.Multilevel(hs, refs, **kw) for name, kw in forms.items()}
+            zero = torch.zeros(2 * top.ndofs, dtype=torch.float64, device="cuda")
+            for contrast in (1.0, 10.0, 1000.0):
+                for h_, rt in zip(hs, right):
+                    h_.set_shear(cell_mu=1.0 + (contrast - 1.0) * rt)
+                for name, kw in forms.items():
+                    if kw.get("coarse"):
+                        mls[name].set_coarse(True)         # (the factor is a snapshot of the operator of level 0)
+                r = dict(levels=len(dms), cells=dms[-1].mesh.ncells, rows=2 * top.ndofs, contrast=contrast)
+                for name, h_ in [("jacobi", top)] + list(mls.items()):
+                    info, ms, _ = timed_solve(torch, h_, b, zero, 1e-8, args.maxit)
+                    r[name] = dict(iterations=info["iterations"], ms=ms, converged=info["converged"],
+                                   breakdown=info["breakdown"])
+                say(f"{tag} E_{p} contrast {contrast:g}: " + "; ".join(
+                    f"{name} {r[name]['iterations']} iterations in {r[name]['ms']:.1f} ms"
+                    for name in ["jacobi"] + list(forms)) + f" ({r['levels']} levels, {r['cells']} cells, one run each)")
+                res[f"SHEAR_{tag}_E{p}_contrast{contrast:g}"] = r
+            for ml in mls.values():
+                ml.close()
+            for h_ in hs:
+                h_.close()
+
+    dms, refs, _ = device_hierarchy(args, cpp)
+    contrasts("UNIFORM", dms, refs, dict(hierarchy=dict()))
+    base = create_unit_square(16, shuffle_seed=3)
+    dms, refs = [cpp.DeviceMesh(base)], []
+    for _ in range(10):
+        m = dms[-1].mesh
+        on = np.abs(m.x[m.cell_nodes, 0] - 0.5).min(axis=1) < 1e-12
+        refs.append(dms[-1].refine(np.nonzero(on)[0].astype(np.int32), keep_plan=True))
+        dms.append(refs[-1].dmesh)
+    say(f"adaptive hierarchy: cells {[d_.mesh.ncells for d_ in dms]}")
+    contrasts("ADAPTIVE", dms, refs, dict(hierarchy=dict(), local_coarse=dict(local=True, coarse=True)))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=500, help="squares per side (4 n^2 triangles)")
@@ -525,6 +658,7 @@ def main():
                     help="--reaction --multilevel: the time steps of the heat step, next to c = 0")
     ap.add_argument("--plain-only", action="store_true",
                     help="--reaction: time the product without the term alone (runs on a library without the term too)")
+    ap.add_argument("--shear", action="store_true", help="the figures of the cell-wise shear modulus instead")
     ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
     ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -555,6 +689,10 @@ def main():
     from dolfinx_eqlb_amd.mesh import create_unit_square
     if args.reaction:
         run_reaction(args, cpp, torch, res)
+        print(json.dumps(res))
+        return
+    if args.shear:
+        run_shear(args, cpp, torch, res)
         print(json.dumps(res))
         return
     if args.nrhs:
