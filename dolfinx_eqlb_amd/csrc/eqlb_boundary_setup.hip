@@ -246,6 +246,25 @@ try
   const eqlb::PlanOptions opt{h->k, h->deg, h->nrhs, h->nrt, h->stress, h->mode, h->large_patches,
                               h->large_patches_stress, eqlb::large_patch_weaksym_ws_doubles};
   const eqlb::HostTopology topo = host_topology(*h->mesh);
+  // A cell of zero area: the patches of its three vertices are left out like masked nodes, and every sweep reports
+  // them through the status word (flat_swept).  Inside a patch kernel their inf and NaN would not stay in their own
+  // lanes - the chains of the shuffle solver multiply what they drag in from the neighbouring patch group by an exact
+  // zero, which is no zero for a NaN -, and RT_1 has no pivot that could report them
+  const uint8_t* flat = nullptr;
+  EQLB_TRY(eqlb::mesh_flat_nodes(h->mesh, &flat));
+  std::vector<uint8_t> healthy_mask;
+  bool flat_swept = false;
+  if (flat)
+  {
+    healthy_mask.resize((size_t)topo.nnodes);
+    for (int32_t i = 0; i < topo.nnodes; ++i)
+    {
+      const bool asked = !node_mask || node_mask[i];
+      flat_swept = flat_swept || (asked && flat[i]);
+      healthy_mask[i] = (asked && !flat[i]) ? 1 : 0;
+    }
+    node_mask = healthy_mask.data();
+  }
   BoundaryPlan plan; // (plan_boundary, in its two halves)
   int st = eqlb::check_boundary_table(topo, opt, facet_type, node_mask, plan);
   tm.lap("checks");
@@ -261,6 +280,7 @@ try
 
   h->bt = BoundaryTables{}; // (the slot buffer as well: re-zeroed by the next sweep, node_mask may have changed)
   h->bt.t_stress = plan.t_stress;
+  h->bt.flat_swept = flat_swept;
   tm.lap("free old tables");
   EQLB_TRY(build_plain_soa(h, plan, facet_type, boundary_values));
   tm.lap("plain SoA: upload + builder");

@@ -24,6 +24,8 @@ struct BoundaryTables
 {
   bool boundary_set = false;
   bool stress_flux_bcs = true;      // some facet of stress row 0 / 1 carries a flux BC
+  bool flat_swept = false;          // a node of the mask is a vertex of a cell of zero area: its patch is left out, every
+                                    // sweep raises the status word
   int64_t npatch_total = 0, nslots = 0;
   Bin bins[MAX_BINS];
   DevBuf<int8_t> facet_type;        // [nrhs][nfacets]

@@ -193,6 +193,10 @@ struct BuildArgs
 void launch_build_patches(const BuildArgs& a, hipStream_t stream);
 void launch_cell_geometry(int32_t ncells, const double* x, const int32_t* cell_nodes,
                           double* cellJ, hipStream_t stream);
+// cells whose det J is zero to rounding or not finite: node_flat [nnodes] (zeroed by the caller) gets 1 at their three
+// vertices, *count their number
+void launch_flat_cell_nodes(int32_t ncells, const double* cellJ, const int32_t* cell_nodes, uint8_t* node_flat,
+                            int32_t* count, hipStream_t stream);
 // returns 0 or EQLB_ERR_UNSUPPORTED
 int launch_se_patch(int k, int deg, int P, int solver, int scatter, const SeArgs& a,
                     hipStream_t stream, int mode = 0);

@@ -32,6 +32,9 @@ struct eqlb_mesh
   // depends on the mesh alone, so further handles on the mesh (SE + EV, a stress handle ...) and further
   // eqlb_se_set_boundary calls reuse it
   std::map<int, std::vector<int32_t>> tiling_order;
+  // nodes of the cells of zero area (mesh_flat_nodes): found once per mesh, empty on a mesh without such a cell
+  bool flat_known = false;
+  std::vector<uint8_t> flat_nodes;
 };
 
 namespace eqlb
@@ -50,6 +53,39 @@ inline int mesh_node_cells(eqlb_mesh* mesh, const int32_t** out)
     mesh->m.node_cells = mesh->node_cells;
   }
   *out = mesh->m.node_cells;
+  return EQLB_OK;
+}
+
+// The vertices of the cells whose det J is zero to rounding or not finite (launch_flat_cell_nodes): *out is [nnodes], 1
+// at such a vertex, or nullptr on a mesh without such a cell.  The element matrices of a flat cell are inf and NaN, so no
+// patch that holds one can be equilibrated; the handles leave those patches out and report them (eqlb_se_set_boundary).
+// One kernel over the cells and a copy of four bytes at the first call on a mesh, the answer is kept
+inline int mesh_flat_nodes(eqlb_mesh* mesh, const uint8_t** out)
+{
+  std::lock_guard<std::mutex> g(mesh->tiling_mutex);
+  if (!mesh->flat_known)
+  {
+    const DeviceMesh& m = mesh->m;
+    DevBuf<uint8_t> flags;
+    DevBuf<int32_t> count;
+    if (flags.alloc((size_t)m.nnodes) || count.alloc(1))
+      return EQLB_ERR_DEVICE;
+    HIP_TRY(hipMemset(flags, 0, (size_t)m.nnodes));
+    HIP_TRY(hipMemset(count, 0, sizeof(int32_t)));
+    launch_flat_cell_nodes(m.ncells, m.cellJ, m.cell_nodes, flags, count, nullptr);
+    HIP_TRY(hipGetLastError());
+    int32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, count, sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<uint8_t> nodes;
+    if (n > 0)
+    {
+      nodes.resize((size_t)m.nnodes);
+      HIP_TRY(hipMemcpy(nodes.data(), flags, nodes.size(), hipMemcpyDeviceToHost));
+    }
+    mesh->flat_nodes = std::move(nodes);
+    mesh->flat_known = true;
+  }
+  *out = mesh->flat_nodes.empty() ? nullptr : mesh->flat_nodes.data();
   return EQLB_OK;
 }
 } // namespace eqlb

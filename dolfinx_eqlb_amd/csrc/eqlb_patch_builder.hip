@@ -273,6 +273,36 @@ k_cell_geometry(int32_t ncells, const double* x, const int32_t* cell_nodes, doub
   J[3] = x2[1] - x0[1];
 }
 
+// A cell is flat when det J = J00 J11 - J01 J10 is not larger than the rounding of its two products, or not finite.  The
+// patch kernels evaluate the same expression, each as its compiler contracts it: at that level the variants differ in
+// sign and size, and 1 / |det J| turns the element matrices into inf and NaN.
+__global__ void __launch_bounds__(256)
+k_flat_cell_nodes(int32_t ncells, const double* cellJ, const int32_t* cell_nodes, uint8_t* node_flat, int32_t* count)
+{
+  const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells)
+    return;
+  const double* J = cellJ + 4 * (int64_t)c;
+  const double p = J[0] * J[3], q = J[1] * J[2];
+  const double det = fabs(p - q);
+  const bool flat = !(det > 4.0 * 2.220446049250313e-16 * (fabs(p) + fabs(q))) || !(det < __builtin_inf());
+  if (!flat)
+    return;
+  const int32_t* cn = cell_nodes + 3 * (int64_t)c;
+  for (int i = 0; i < 3; ++i)
+    node_flat[cn[i]] = 1;
+  atomicAdd(count, 1);
+}
+
+void launch_flat_cell_nodes(int32_t ncells, const double* cellJ, const int32_t* cell_nodes, uint8_t* node_flat,
+                            int32_t* count, hipStream_t stream)
+{
+  const int block = 256;
+  const int grid = (ncells + block - 1) / block;
+  if (grid > 0)
+    hipLaunchKernelGGL(k_flat_cell_nodes, dim3(grid), dim3(block), 0, stream, ncells, cellJ, cell_nodes, node_flat, count);
+}
+
 void launch_build_patches(const BuildArgs& a, hipStream_t stream)
 {
   const int block = 256;

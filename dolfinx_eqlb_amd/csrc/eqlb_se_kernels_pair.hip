@@ -28,7 +28,9 @@ struct PairDpp
   static __device__ __forceinline__ double cst(double c) { return c; }
   static __device__ __forceinline__ double fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
   static __device__ __forceinline__ double rcp(double a) { return rcp_d(a); }
-  static __device__ __forceinline__ bool pos(double a) { return a > 0.0; }
+  // a pivot passes if it is positive and finite: one class test (+denormal | +normal) in place of the compare with
+  // zero, which +inf passes as well
+  static __device__ __forceinline__ bool pos(double a) { return __builtin_amdgcn_class(a, 0x180); }
   static __device__ __forceinline__ bool both(bool a, bool b) { return a && b; }
   static __device__ __forceinline__ double dn(double v) { return dpp_d<0x93>(v); }  // quad_perm [3,0,1,2]
   static __device__ __forceinline__ double up(double v) { return dpp_d<0x39>(v); }  // quad_perm [1,2,3,0]

@@ -574,6 +574,10 @@ int equilibrate_lists(eqlb_se_t* h, const double* const* g_in, const double* con
     return st;
   if (evs)
     ++h->ev_calls;
+  // patches of a cell of zero area were left out (eqlb_se_set_boundary): the call reports them like a patch system that
+  // is not positive definite, behind its kernels on the caller's stream
+  if (h->bt.flat_swept)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(static_cast<int32_t*>(h->status)), 1, 1, stream));
   HIP_TRY(hipGetLastError());
   if (memspace == EQLB_MEM_HOST)
     return stage_out(h, s_x, x_io, d_x.data(), stream);

@@ -437,7 +437,11 @@ int eqlb_se_equilibrate_tiles(eqlb_se_t* handle, const double* flux_dg, const do
  * positive definite (degenerate cell geometry; the matrix does not depend on the data) cannot be
  * reported by the call itself: the kernels raise a flag on the device.  eqlb_se_check_status waits for `stream`, reads and clears
  * the flag: EQLB_OK or EQLB_ERR_SINGULAR (the reference has no such check: Eigen's LLT / LU results
- * are used unchecked, se/PatchData.hpp:576-663).  Host-memory calls check it themselves. */
+ * are used unchecked, se/PatchData.hpp:576-663).  Host-memory calls check it themselves.
+ * A cell of zero area (det J zero to rounding, or not finite) is found when the boundary is set: the patches of its
+ * three vertices are left out as if the node mask were 0 there, and every sweep of the handle raises the flag.  The
+ * output of such a call is finite: on every cell the sum over the patches of the other nodes.  A node mask without
+ * the three vertices gives the same values and no flag. */
 int eqlb_se_check_status(eqlb_se_t* handle, void* stream);
 
 /* With option "timing" = 1 every equilibrate call records HIP events on the launch stream around
