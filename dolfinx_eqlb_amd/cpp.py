@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_get_mass_table", "eqlb_primal_set_reaction", "eqlb_elasticity_set_reaction",
     "eqlb_primal_value_dg", "eqlb_get_value_table",
     "eqlb_elasticity_set_shear", "eqlb_primal_stress_dg_mu", "eqlb_se_estimate_stress_mu",
+    "eqlb_primal_set_diffusion", "eqlb_primal_flux_dg_tensor", "eqlb_se_estimate_weighted", "eqlb_ev_estimate_weighted",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -1024,11 +1025,17 @@ def _degree_dg(k: int, degree_dg):
     return int(degree_dg)
 
 
-def estimate(dmesh: DeviceMesh, k: int, flux_hdiv, flux_dg, rhs_dg, conforming_flux=False, degree_dg=None):
+def estimate(dmesh: DeviceMesh, k: int, flux_hdiv, flux_dg, rhs_dg, conforming_flux=False, degree_dg=None, coeff=None,
+             cell_D=None):
     """eqlb_se_estimate (eqlb_ev_estimate with conforming_flux=True: the flux is an EV result in
     the broken layout) on host arrays [nrhs, ...]: returns (cell_div2 [nrhs, ncells],
     cell_sig2 [nrhs, ncells], facet_jump [nrhs, nfacets]).  degree_dg: flux_dg / rhs_dg are DG_{degree_dg}
-    data, 0 <= degree_dg <= k-1 (eqlb_se_estimate_dg / eqlb_ev_estimate_dg); None: DG_{k-1}."""
+    data, 0 <= degree_dg <= k-1 (eqlb_se_estimate_dg / eqlb_ev_estimate_dg); None: DG_{k-1}.
+    With coeff [ncells] and / or cell_D [ncells, 3] = (d00, d01, d11) (eqlb_se_estimate_weighted /
+    eqlb_ev_estimate_weighted): cell_sig2 in the energy norm of -div(coeff D grad u), the integral of e^T W e with
+    W = adj(D) / (coeff det D); cell_div2 and facet_jump are bit for bit those of the call without them
+    (eqlb.check_eqlb_conditions.weighted_flux_norm is the statement).  The data oscillation takes the weight
+    lsolver.primal.diffusion_oscillation_weight(cell_D, coeff).  Without the new keywords the call is the one it was."""
     m = dmesh.mesh
     deg = _degree_dg(k, degree_dg)
     nrt, nd = k * (k + 2), (deg + 1) * (deg + 2) // 2
@@ -1041,6 +1048,14 @@ def estimate(dmesh: DeviceMesh, k: int, flux_hdiv, flux_dg, rhs_dg, conforming_f
     div2 = np.zeros((nrhs, m.ncells))
     sig2 = np.zeros((nrhs, m.ncells))
     jump = np.zeros((nrhs, m.nfacets))
+    if coeff is not None or cell_D is not None:
+        kc = _cell_array(coeff, m.ncells)
+        kd = None if cell_D is None else np.ascontiguousarray(cell_D, dtype=np.float64).ravel()
+        if kd is not None and kd.size != 3 * m.ncells:
+            raise RuntimeError("Equilibration: Input sizes does not match")
+        estimate_weighted_raw(dmesh, k, deg, nrhs, _hp(x), _hp(g), _hp(f), None if kc is None else _hp(kc),
+                              None if kd is None else _hp(kd), _hp(div2), _hp(sig2), _hp(jump), conforming_flux, MEM_HOST)
+        return div2, sig2, jump
     estimate_raw(dmesh, k, nrhs, _hp(x), _hp(g), _hp(f), _hp(div2), _hp(sig2), _hp(jump), conforming_flux,
                  degree_dg, MEM_HOST)
     return div2, sig2, jump
@@ -1062,6 +1077,17 @@ def estimate_raw(dmesh: DeviceMesh, k: int, nrhs: int, flux_hdiv, flux_dg, rhs_d
     else:
         fn = lib().eqlb_ev_estimate_dg if conforming_flux else lib().eqlb_se_estimate_dg
         _check(fn(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), *ptrs, *tail))
+
+
+def estimate_weighted_raw(dmesh: DeviceMesh, k: int, degree_dg: int, nrhs: int, flux_hdiv, flux_dg, rhs_dg, cell_coeff,
+                          cell_D, cell_div2, cell_sig2, facet_jump, conforming_flux=False, memspace=MEM_DEVICE,
+                          stream=0):
+    """eqlb_se_estimate_weighted / eqlb_ev_estimate_weighted on raw pointers (ints, or None for a coefficient that is
+    not given / an output that is not wanted) in `memspace`, ordered on `stream`; degree_dg is explicit."""
+    fn = lib().eqlb_ev_estimate_weighted if conforming_flux else lib().eqlb_se_estimate_weighted
+    _check(fn(dmesh._h, C.c_int32(k), C.c_int32(degree_dg), C.c_int32(nrhs), _vp(flux_hdiv), _vp(flux_dg), _vp(rhs_dg),
+              _vp(cell_coeff), _vp(cell_D), _vp(cell_div2), _vp(cell_sig2), _vp(facet_jump), C.c_int32(memspace),
+              C.c_void_p(stream)))
 
 
 def _cell_array(a, ncells):
@@ -1312,10 +1338,13 @@ def get_flux_bc_prolong_table(k: int):
     return out
 
 
-def primal_flux_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, coeff=None, op=None):
+def primal_flux_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, coeff=None, op=None, cell_D=None):
     """eqlb_primal_flux_dg on host arrays: the DG_{degree_dg}^2 DOFs of -coeff grad(u_h) for u_h in P_p given by
     its cell dofmap cell_dofs [ncells, nd_p] and solution vectors u [nrhs, ndofs] (or [ndofs]); coeff [ncells]
-    or None (1); op [2, nd_d, nd_p] replaces the built-in table.  Returns [nrhs, ncells*nd_d*2]."""
+    or None (1); op [2, nd_d, nd_p] replaces the built-in table.  Returns [nrhs, ncells*nd_d*2].
+    With cell_D [ncells, 3] = (d00, d01, d11) (eqlb_primal_flux_dg_tensor): the flux -coeff D grad(u_h) of
+    PrimalPoisson.set_diffusion; lsolver.primal.flux_dg_tensor is its statement.  Without it the call is the one it
+    was."""
     m = dmesh.mesh
     ndp, nd = _primal_sizes(p, degree_dg)
     cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
@@ -1326,9 +1355,27 @@ def primal_flux_dg(dmesh: DeviceMesh, p: int, degree_dg: int, cell_dofs, u, coef
         raise RuntimeError("Local solver: Input sizes does not match")
     t = _primal_op(op, nd, ndp)
     out = np.zeros((uu.shape[0], m.ncells * nd * 2))
+    if cell_D is not None:
+        kd = np.ascontiguousarray(cell_D, dtype=np.float64).ravel()
+        if kd.size != 3 * m.ncells:
+            raise RuntimeError("Local solver: Input sizes does not match")
+        primal_flux_dg_tensor_raw(dmesh, p, degree_dg, uu.shape[0], _hp(cd), uu.shape[1], _hp(uu),
+                                  _hp(kc) if kc is not None else None, _hp(kd), _hp(out), t, MEM_HOST)
+        return out
     primal_flux_dg_raw(dmesh, p, degree_dg, uu.shape[0], _hp(cd), uu.shape[1], _hp(uu),
                        _hp(kc) if kc is not None else None, _hp(out), t, MEM_HOST)
     return out
+
+
+def primal_flux_dg_tensor_raw(dmesh: DeviceMesh, p: int, degree_dg: int, nrhs: int, cell_dofs, ndofs: int, u, coeff,
+                              cell_D, flux_dg, op=None, memspace=MEM_DEVICE, stream=0):
+    """eqlb_primal_flux_dg_tensor on raw pointers (ints; coeff may be None) in `memspace`, ordered on `stream`: the
+    arrays of primal_flux_dg_raw and cell_D [ncells, 3].  Device memory: one kernel, nothing waits for the device."""
+    t = None if op is None else np.ascontiguousarray(op, dtype=np.float64)
+    _check(lib().eqlb_primal_flux_dg_tensor(dmesh._h, C.c_int32(p), C.c_int32(degree_dg), C.c_int32(nrhs),
+                                            _vp(cell_dofs), C.c_int64(ndofs), _vp(u), _vp(coeff), _vp(cell_D),
+                                            _hp(t) if t is not None else None, _vp(flux_dg), C.c_int32(memspace),
+                                            C.c_void_p(stream)))
 
 
 def primal_flux_dg_raw(dmesh: DeviceMesh, p: int, degree_dg: int, nrhs: int, cell_dofs, ndofs: int, u, coeff,
@@ -1648,6 +1695,23 @@ class PrimalPoisson(_PrimalSolver):
     def set_dirichlet_raw(self, nlist, facets, memspace=MEM_DEVICE, stream=0):
         _check(lib().eqlb_primal_set_dirichlet(self._h, C.c_int32(nlist), _vp(facets), C.c_int32(memspace),
                                                C.c_void_p(stream)))
+
+    def set_diffusion(self, cell_D=None, stream=0):
+        """The operator becomes -div(coeff D grad u) (eqlb_primal_set_diffusion): cell_D, a host array [ncells][3] =
+        (d00, d01, d11) of the symmetric positive definite tensor of each cell; None switches the term off.  A repeated
+        call replaces the tensor; a cell whose values are not finite or not positive definite is refused by name and the
+        handle stays as it was.  The diagonal is formed again; Multilevel.set_coarse(True) has to be called again
+        afterwards.  D crosses a refinement through Refinement.prolong_dg(0, cell_D.ravel(), bs=3)."""
+        kd = None
+        if cell_D is not None:
+            kd = np.ascontiguousarray(cell_D, dtype=np.float64).ravel()
+            if kd.size != 3 * self.dmesh.counts()[1]:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        self.set_diffusion_raw(None if kd is None else kd.ctypes.data, MEM_HOST, stream)
+
+    def set_diffusion_raw(self, cell_D=None, memspace=MEM_DEVICE, stream=0):
+        """cell_D: a raw pointer (int) to [ncells][3] in `memspace`, or None (the term off)."""
+        _check(lib().eqlb_primal_set_diffusion(self._h, _vp(cell_D), C.c_int32(memspace), C.c_void_p(stream)))
 
     def apply_many(self, U, masked=False, stream=0):
         """Y [nrhs][ndofs]: row c is apply(U[c]), bit for bit, in one call."""

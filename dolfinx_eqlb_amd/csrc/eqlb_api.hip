@@ -490,7 +490,7 @@ static int check_degree_dg(const char* who, int32_t k, int32_t degree_dg)
 static int estimate_impl(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_hdiv,
                          const double* flux_dg, const double* rhs_dg, double* cell_div2,
                          double* cell_sig2, double* facet_jump, int32_t memspace, void* stream_,
-                         double alpha, double beta)
+                         double alpha, double beta, const eqlb::EstWeightArgs* weight = nullptr)
 {
   if (!mesh || !flux_hdiv || !flux_dg || !rhs_dg || nrhs < 1 || k < 1 || k > 4)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_se_estimate: invalid argument");
@@ -505,16 +505,23 @@ static int estimate_impl(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_
   if (memspace == EQLB_MEM_DEVICE)
   {
     const int st = eqlb::launch_estimate(m, k, degree_dg, nrhs, flux_hdiv, flux_dg, rhs_dg, cell_div2, cell_sig2,
-                                         facet_jump, alpha, beta, stream);
+                                         facet_jump, alpha, beta, stream, weight);
     return st ? fail(st, "eqlb_se_estimate: kernel launch failed") : EQLB_OK;
   }
   EQLB_TRY(eqlb::check_memspace("eqlb_se_estimate", memspace));
   eqlb::HostCall s;
   const auto d_x = s.in(flux_hdiv, n_x), d_g = s.in(flux_dg, n_g), d_f = s.in(rhs_dg, n_f);
   const auto d_d = s.out(cell_div2, n_c), d_s = s.out(cell_sig2, n_c), d_j = s.out(facet_jump, n_e);
+  const auto d_wc = s.in(weight ? weight->cell_coeff : nullptr, (size_t)m.ncells),
+             d_wd = s.in(weight ? weight->cell_D : nullptr, 3 * (size_t)m.ncells);
   int rc = EQLB_OK;
   if (s.upload(stream) == hipSuccess)
-    rc = eqlb::launch_estimate(m, k, degree_dg, nrhs, d_x, d_g, d_f, d_d, d_s, d_j, alpha, beta, stream);
+  {
+    const eqlb::EstWeightArgs wx{weight && weight->cell_coeff ? d_wc.get() : nullptr,
+                                 weight && weight->cell_D ? d_wd.get() : nullptr};
+    rc = eqlb::launch_estimate(m, k, degree_dg, nrhs, d_x, d_g, d_f, d_d, d_s, d_j, alpha, beta, stream,
+                               weight ? &wx : nullptr);
+  }
   if (s.finish(stream) != hipSuccess || rc)
     return fail(EQLB_ERR_DEVICE, "eqlb_se_estimate: device error");
   return EQLB_OK;
@@ -550,6 +557,51 @@ int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t
 {
   return estimate_impl(mesh, k, degree_dg, nrhs, flux_broken, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump,
                        memspace, stream, -1.0, 0.0);
+}
+
+// the body of the weighted entries: without a coefficient and a tensor the call of the entry without a weight; host
+// arrays are checked cell by cell before anything is launched, device arrays are the caller's responsibility
+static int estimate_weighted_call(const char* who, eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs,
+                                  const double* flux, const double* flux_dg, const double* rhs_dg,
+                                  const double* cell_coeff, const double* cell_D, double* cell_div2, double* cell_sig2,
+                                  double* facet_jump, int32_t memspace, void* stream, double alpha, double beta)
+{
+  if (mesh && memspace == EQLB_MEM_HOST)
+    for (int32_t i = 0; i < mesh->m.ncells; ++i)
+    {
+      if (cell_coeff && !(cell_coeff[i] > 0.0 && std::isfinite(cell_coeff[i])))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_coeff[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
+                    cell_coeff[i]);
+      if (!cell_D)
+        continue;
+      const double d00 = cell_D[3 * i], d01 = cell_D[3 * i + 1], d11 = cell_D[3 * i + 2];
+      if (!(std::isfinite(d00) && std::isfinite(d01) && std::isfinite(d11)))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not finite", who, (int)i, d00, d01, d11);
+      if (!(d00 > 0.0 && d00 * d11 - d01 * d01 > 0.0))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not positive definite", who, (int)i, d00,
+                    d01, d11);
+    }
+  const eqlb::EstWeightArgs weight{cell_coeff, cell_D};
+  return estimate_impl(mesh, k, degree_dg, nrhs, flux, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump, memspace,
+                       stream, alpha, beta, (cell_coeff || cell_D) ? &weight : nullptr);
+}
+
+int eqlb_se_estimate_weighted(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_hdiv,
+                              const double* flux_dg, const double* rhs_dg, const double* cell_coeff,
+                              const double* cell_D, double* cell_div2, double* cell_sig2, double* facet_jump,
+                              int32_t memspace, void* stream)
+{
+  return estimate_weighted_call("eqlb_se_estimate_weighted", mesh, k, degree_dg, nrhs, flux_hdiv, flux_dg, rhs_dg,
+                                cell_coeff, cell_D, cell_div2, cell_sig2, facet_jump, memspace, stream, 0.0, 1.0);
+}
+
+int eqlb_ev_estimate_weighted(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_broken,
+                              const double* flux_dg, const double* rhs_dg, const double* cell_coeff,
+                              const double* cell_D, double* cell_div2, double* cell_sig2, double* facet_jump,
+                              int32_t memspace, void* stream)
+{
+  return estimate_weighted_call("eqlb_ev_estimate_weighted", mesh, k, degree_dg, nrhs, flux_broken, flux_dg, rhs_dg,
+                                cell_coeff, cell_D, cell_div2, cell_sig2, facet_jump, memspace, stream, -1.0, 0.0);
 }
 
 // the body of eqlb_se_estimate_stress and eqlb_se_estimate_stress_mu; co: the cell-wise coefficients of the latter, its

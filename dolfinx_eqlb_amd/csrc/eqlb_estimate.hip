@@ -7,18 +7,18 @@ namespace eqlb
 
 int launch_estimate(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                     const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                    double beta, hipStream_t stream)
+                    double beta, hipStream_t stream, const EstWeightArgs* wx)
 {
   if (deg != k - 1)
-    return launch_estimate_lowdeg(m, k, deg, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_lowdeg(m, k, deg, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 1)
-    return launch_estimate_kd<1, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<1, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 2)
-    return launch_estimate_kd<2, 1>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<2, 1>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 3)
-    return launch_estimate_kd<3, 2>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<3, 2>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 4)
-    return launch_estimate_kd<4, 3>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<4, 3>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   return EQLB_ERR_UNSUPPORTED;
 }
 

@@ -46,142 +46,18 @@ struct EstTables
   }
 };
 
-// one thread per cell: divergence residual and flux norm
-template <int K, int DEG>
-__global__ void __launch_bounds__(256)
-k_estimate_cells(int32_t ncells, const double* __restrict__ tab, const double* __restrict__ cellJ,
-                 const double* __restrict__ x_eq, const double* __restrict__ flux_dg,
-                 const double* __restrict__ rhs_dg, double* __restrict__ div2, double* __restrict__ sig2,
-                 const double alpha, const double beta)
-{
-  using E = EstTables<K, DEG>;
-  constexpr int NRT = E::NRT, ND = E::ND, NQ = E::NQ;
-  extern __shared__ double st[];
-  for (int i = threadIdx.x; i < E::TOTAL; i += 256)
-    st[i] = tab[i];
-  __syncthreads();
-  const int32_t c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncells)
-    return;
-  const double* J = cellJ + 4 * (int64_t)c;
-  const double J00 = J[0], J01 = J[1], J10 = J[2], J11 = J[3];
-  const double detJ = J00 * J11 - J01 * J10, ia = 1.0 / fabs(detJ);
-  const double a00 = J11, a01 = -J01, a10 = -J10, a11 = J00; // adj = detJ * K
-  const double* co = x_eq + (int64_t)c * NRT;
-  double cf[NRT];
-#pragma unroll
-  for (int i = 0; i < NRT; ++i)
-    cf[i] = co[i];
-  if (div2)
-  {
-    double m[NQ];
-    // moments of the reference divergence: q = 0 from the zero-order facet DOFs (facet 1 measures the
-    // outward flux, facets 0 and 2 the inward one), q >= 1 are the div DOFs themselves
-    m[0] = -(-cf[0] + cf[K] - cf[2 * K]);
-#pragma unroll
-    for (int q = 1; q < NQ; ++q)
-      m[q] = -cf[3 * K + q - 1];
-    const double* G = flux_dg + (int64_t)c * ND * 2;
-    const double* f = rhs_dg + (int64_t)c * ND;
-#pragma unroll
-    for (int i = 0; i < ND; ++i)
-    {
-      const double gx = G[2 * i], gy = G[2 * i + 1];
-      const double h0 = beta * (a00 * gx + a01 * gy), h1 = beta * (a10 * gx + a11 * gy), fd = detJ * f[i];
-      if constexpr (DEG == 0 && K >= 2)
-      {
-        // P0 data: div G = 0, the rows of DM are zero (RT_1 keeps the generic contraction)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          m[q] += fd * st[E::OFF_HG + i * NQ + q];
-      }
-      else
-      {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          m[q] += fd * st[E::OFF_HG + i * NQ + q] - h0 * st[E::OFF_DM + (i * 2 + 0) * NQ + q]
-                  - h1 * st[E::OFF_DM + (i * 2 + 1) * NQ + q];
-      }
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-    {
-      double r = 0.0;
-#pragma unroll
-      for (int p = 0; p < NQ; ++p)
-        r += st[E::OFF_GMI + q * NQ + p] * m[p];
-      s += m[q] * r;
-    }
-    div2[c] = s * ia;
-  }
-  if (sig2)
-  {
-    const double g0 = (J00 * J00 + J10 * J10) * ia, g1 = (J00 * J01 + J10 * J11) * ia,
-                 g2 = (J01 * J01 + J11 * J11) * ia;
-    double s = 0.0;
-    // The loops over the rows of S (and of MRD below) are unrolled in full at d < k - 1, so that cf stays in
-    // registers.  The d = k - 1 instances keep the loop the compiler makes of it (RT_4 / DG_3 indexes cf in 208 B
-    // of scratch): their code is left as it was, hence the two copies.
-    if constexpr (DEG == K - 1)
-    {
-      for (int i = 0; i < NRT; ++i)
-      {
-        double r = 0.0;
-#pragma unroll
-        for (int j = 0; j < NRT; ++j)
-          r += (g0 * st[E::OFF_S + i * NRT + j] + g1 * st[E::OFF_S + (NRT + i) * NRT + j]
-                + g2 * st[E::OFF_S + (2 * NRT + i) * NRT + j])
-               * cf[j];
-        s += cf[i] * r;
-      }
-    }
-    else
-    {
-#pragma unroll
-      for (int i = 0; i < NRT; ++i)
-      {
-        double r = 0.0;
-#pragma unroll
-        for (int j = 0; j < NRT; ++j)
-          r += (g0 * st[E::OFF_S + i * NRT + j] + g1 * st[E::OFF_S + (NRT + i) * NRT + j]
-                + g2 * st[E::OFF_S + (2 * NRT + i) * NRT + j])
-               * cf[j];
-        s += cf[i] * r;
-      }
-    }
-    // S1 holds phi_i^x phi_j^y + phi_i^y phi_j^x, so c^T S1 c counts the mixed term twice as needed
-    if (alpha != 0.0)
-    {
-      // || sigma + alpha G ||^2 = || sigma ||^2 + 2 alpha (sigma, G) + alpha^2 (G, G)
-      const double sg = (detJ > 0.0) ? 1.0 : -1.0;
-      const double* G = flux_dg + (int64_t)c * ND * 2;
-      double sgm = 0.0, gg = 0.0;
-#pragma unroll
-      for (int d = 0; d < ND; ++d)
-      {
-        const double gx = G[2 * d], gy = G[2 * d + 1];
-        const double t0 = J00 * gx + J10 * gy, t1 = J01 * gx + J11 * gy; // J^T G_d
-        if constexpr (DEG == K - 1)
-        {
-          for (int i = 0; i < NRT; ++i)
-            sgm += cf[i] * (st[E::OFF_MRD + (i * ND + d) * 2] * t0 + st[E::OFF_MRD + (i * ND + d) * 2 + 1] * t1);
-        }
-        else
-        {
-#pragma unroll
-          for (int i = 0; i < NRT; ++i)
-            sgm += cf[i] * (st[E::OFF_MRD + (i * ND + d) * 2] * t0 + st[E::OFF_MRD + (i * ND + d) * 2 + 1] * t1);
-        }
-#pragma unroll
-        for (int e = 0; e < ND; ++e)
-          gg += st[E::OFF_MPS + d * ND + e] * (gx * G[2 * e] + gy * G[2 * e + 1]);
-      }
-      s += 2.0 * alpha * sg * sgm + alpha * alpha * fabs(detJ) * gg;
-    }
-    sig2[c] = s;
-  }
-}
+// k_estimate_cells<K, DEG> and, from the same source (eqlb_estimate_cells.inc), k_estimate_cells_weighted<K, DEG>: the
+// flux norm in the energy norm of -div(kappa D grad u), cell_sig2 = int_T (sigma_eq - sigma_h)^T W (sigma_eq - sigma_h)
+// with W = adj(D) / (kappa det D) formed per cell from `wx` (eqlb_se_estimate_weighted / eqlb_ev_estimate_weighted).  A
+// kernel of its own, so that the entries without a weight launch the symbols, arguments and code they launched before
+// (tools/isa_compare.py); it forms cell_sig2 only - the divergence residual of a weighted call comes from
+// k_estimate_cells itself and is therefore bit for bit the one of the unweighted entry.
+#define EQLB_EST_WEIGHTED 0
+#include "eqlb_estimate_cells.inc"
+#undef EQLB_EST_WEIGHTED
+#define EQLB_EST_WEIGHTED 1
+#include "eqlb_estimate_cells.inc"
+#undef EQLB_EST_WEIGHTED
 
 // outward moments of (sigma_eq + G) on local facet lf of cell c
 template <int K, int DEG>
@@ -325,7 +201,7 @@ k_boundary_residual(int32_t nlist, int32_t nfacets, const int32_t* __restrict__ 
 template <int K, int DEG>
 static int launch_estimate_kd(const DeviceMesh& m, int nrhs, const double* x_eq, const double* flux_dg,
                               const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                              double beta, hipStream_t stream)
+                              double beta, hipStream_t stream, const EstWeightArgs* wx = nullptr)
 {
   using E = EstTables<K, DEG>;
   std::vector<double> t;
@@ -338,7 +214,17 @@ static int launch_estimate_kd(const DeviceMesh& m, int nrhs, const double* x_eq,
   const int64_t nx = (int64_t)m.ncells * E::NRT, ng = (int64_t)m.ncells * E::ND * 2, nf = (int64_t)m.ncells * E::ND;
   for (int r = 0; r < nrhs && e == hipSuccess; ++r)
   {
-    if (div2 || sig2)
+    if (wx && sig2) // the weighted flux norm by its own kernel; the divergence residual by the one below, as it was
+    {
+      if (div2)
+        hipLaunchKernelGGL((k_estimate_cells<K, DEG>), dim3((m.ncells + 255) / 256), dim3(256), lds, stream, m.ncells,
+                           d_t, m.cellJ, x_eq + r * nx, flux_dg + r * ng, rhs_dg + r * nf,
+                           div2 + (int64_t)r * m.ncells, static_cast<double*>(nullptr), alpha, beta);
+      hipLaunchKernelGGL((k_estimate_cells_weighted<K, DEG>), dim3((m.ncells + 255) / 256), dim3(256), lds, stream,
+                         m.ncells, d_t, m.cellJ, x_eq + r * nx, flux_dg + r * ng, sig2 + (int64_t)r * m.ncells, alpha,
+                         *wx);
+    }
+    else if (div2 || sig2)
       hipLaunchKernelGGL((k_estimate_cells<K, DEG>), dim3((m.ncells + 255) / 256), dim3(256), lds, stream, m.ncells,
                          d_t, m.cellJ, x_eq + r * nx, flux_dg + r * ng, rhs_dg + r * nf,
                          div2 ? div2 + (int64_t)r * m.ncells : nullptr,

@@ -10,16 +10,16 @@ namespace eqlb
 
 int launch_estimate_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                            const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                           double beta, hipStream_t stream)
+                           double beta, hipStream_t stream, const EstWeightArgs* wx)
 {
   if (k == 4)
-    return launch_estimate_k4_lowdeg(m, deg, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_k4_lowdeg(m, deg, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 2 && deg == 0)
-    return launch_estimate_kd<2, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<2, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 3 && deg == 1)
-    return launch_estimate_kd<3, 1>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<3, 1>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   if (k == 3 && deg == 0)
-    return launch_estimate_kd<3, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream);
+    return launch_estimate_kd<3, 0>(m, nrhs, x_eq, flux_dg, rhs_dg, div2, sig2, jump, alpha, beta, stream, wx);
   return EQLB_ERR_UNSUPPORTED;
 }
 

@@ -273,10 +273,19 @@ void launch_korn(const DeviceMesh& m, const int64_t* node_slot, const int64_t* n
                  const uint8_t* pflag, double* cks, double* korn, hipStream_t stream, int64_t l_npatch = 0,
                  const int32_t* l_nodes = nullptr, const int32_t* l_off = nullptr, const int32_t* l_slot_cell = nullptr,
                  const uint32_t* l_slot_info = nullptr, const uint8_t* l_pflag = nullptr);
-// estimator step (eqlb_estimate.hip); flux_dg / rhs_dg in DG_deg, 0 <= deg <= k - 1
+// the weight of eqlb_se_estimate_weighted / eqlb_ev_estimate_weighted: W_T = adj(D_T) / (kappa_T det D_T) with
+// kappa_T = cell_coeff[cell] and D_T = (d00, d01, d11) = cell_D[cell] where given, else 1 and the identity.  A kernel
+// argument of the weighted variant, which the kernels of the entries without a weight do not take
+struct EstWeightArgs
+{
+  const double* cell_coeff = nullptr; // [ncells] or nullptr
+  const double* cell_D = nullptr;     // [ncells][3] or nullptr
+};
+// estimator step (eqlb_estimate.hip); flux_dg / rhs_dg in DG_deg, 0 <= deg <= k - 1.  wx == nullptr: the kernels without
+// a weight; else sig2 is the weighted flux norm
 int launch_estimate(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                     const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                    double beta, hipStream_t stream);
+                    double beta, hipStream_t stream, const EstWeightArgs* wx = nullptr);
 int launch_boundary_residual(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
                              const double* flux_dg, int32_t nlist, const int32_t* facets, const double* bvals,
                              double* out, hipStream_t stream);
@@ -299,7 +308,7 @@ int launch_oscillation(const DeviceMesh& m, int k, int deg, int nrhs, const doub
 // the launchers above hand every call with deg != k - 1 over to these
 int launch_estimate_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                            const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                           double beta, hipStream_t stream);
+                           double beta, hipStream_t stream, const EstWeightArgs* wx = nullptr);
 int launch_boundary_residual_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, const double* x_eq,
                                     const double* flux_dg, int32_t nlist, const int32_t* facets,
                                     const double* bvals, double* out, hipStream_t stream);
@@ -308,7 +317,7 @@ int launch_oscillation_lowdeg(const DeviceMesh& m, int k, int deg, int nrhs, con
                               const double* fvalues, const double* korn, double* out, hipStream_t stream);
 int launch_estimate_k4_lowdeg(const DeviceMesh& m, int deg, int nrhs, const double* x_eq, const double* flux_dg,
                               const double* rhs_dg, double* div2, double* sig2, double* jump, double alpha,
-                              double beta, hipStream_t stream);
+                              double beta, hipStream_t stream, const EstWeightArgs* wx = nullptr);
 int launch_boundary_residual_k4_lowdeg(const DeviceMesh& m, int deg, int nrhs, const double* x_eq,
                                        const double* flux_dg, int32_t nlist, const int32_t* facets,
                                        const double* bvals, double* out, hipStream_t stream);

@@ -1,12 +1,22 @@
-// The cell kernel of eqlb_primal_solve.hip, which includes this file twice inside its unnamed namespace:
-//   EQLB_CELL_REACT 0  k_primal_cell<P, MODE, D, R>: the operator, the diagonal and the load of -div(kappa grad u)
-//   EQLB_CELL_REACT 1  k_primal_cell_react<P, MODE, D, R>: operator and diagonal with the reaction term + c u
-// One source for both, and two kernels rather than one with a further template argument: a handle without the term
-// launches the symbols it launched before the term existed, with their arguments and their code (a shared __device__
-// body that takes the arguments by reference does not give the same code: tools/isa_compare.py).
+// The cell kernel of eqlb_primal_solve.hip, which includes this file four times inside its unnamed namespace:
+//   EQLB_CELL_REACT 0, EQLB_CELL_DIFF 0  k_primal_cell<P, MODE, D, R>: the operator, the diagonal and the load of
+//                                        -div(kappa grad u)
+//   EQLB_CELL_REACT 1, EQLB_CELL_DIFF 0  k_primal_cell_react<P, MODE, D, R>: operator and diagonal with the reaction
+//                                        term + c u
+//   EQLB_CELL_REACT 0, EQLB_CELL_DIFF 1  k_primal_cell_diff<P, MODE, D, R>: operator and diagonal of
+//                                        -div(kappa D grad u) with the cell-wise tensor of `dx`
+//   EQLB_CELL_REACT 1, EQLB_CELL_DIFF 1  k_primal_cell_diff_react<P, MODE, D, R>: tensor and reaction term
+// One source for all, and kernels of their own rather than one with a further template argument: a handle without a
+// term launches the symbols it launched before the term existed, with their arguments and their code (a shared
+// __device__ body that takes the arguments by reference does not give the same code: tools/isa_compare.py).
 template <int P, int MODE, int D, int R>
 __global__ void __launch_bounds__(PS_THREADS)
-#if EQLB_CELL_REACT
+#if EQLB_CELL_REACT && EQLB_CELL_DIFF
+k_primal_cell_diff_react(const CellArgs a, const ManyCols cols, int64_t ustride, int64_t ystride, const ReactArgs rx,
+                         const DiffArgs dx)
+#elif EQLB_CELL_DIFF
+k_primal_cell_diff(const CellArgs a, const ManyCols cols, int64_t ustride, int64_t ystride, const DiffArgs dx)
+#elif EQLB_CELL_REACT
 k_primal_cell_react(const CellArgs a, const ManyCols cols, int64_t ustride, int64_t ystride, const ReactArgs rx)
 #else
 k_primal_cell(const CellArgs a, const ManyCols cols, int64_t ustride, int64_t ystride)
@@ -21,6 +31,7 @@ k_primal_cell(const CellArgs a, const ManyCols cols, int64_t ustride, int64_t ys
                 "table shape");
   static_assert(R >= 1 && R <= MANY_R && (R == 1 || MODE == CELL_OPERATOR), "columns for the operator only");
   static_assert(!RX || MODE != CELL_LOAD, "the load knows no reaction term");
+  static_assert(!EQLB_CELL_DIFF || MODE != CELL_LOAD, "the load knows no tensor");
   __shared__ double sT[NTAB];
   __shared__ double sbuf[PS_THREADS * S]; // first the index rows of the workgroup, then its output rows, a column at a time
 #if !EQLB_CELL_REACT
@@ -91,7 +102,16 @@ k_primal_cell(const CellArgs a, const ManyCols cols, int64_t ustride, int64_t ys
     {
       const double idet = 1.0 / det;
       const double K00 = r1.y * idet, K01 = -r0.y * idet, K10 = -r1.x * idet, K11 = r0.x * idet;
+#if EQLB_CELL_DIFF
+      // C = K D K^T with D = (d00 d01; d01 d11) of the cell: T = K D, then C_XY = T[X][0] K[Y][0] + T[X][1] K[Y][1]
+      const double* Dp = dx.cell_D + 3 * (base + t);
+      const double d00 = Dp[0], d01 = Dp[1], d11 = Dp[2];
+      const double T00 = K00 * d00 + K01 * d01, T01 = K00 * d01 + K01 * d11;
+      const double T10 = K10 * d00 + K11 * d01, T11 = K10 * d01 + K11 * d11;
+      const double C00 = T00 * K00 + T01 * K01, C01 = T00 * K10 + T01 * K11, C11 = T10 * K10 + T11 * K11;
+#else
       const double C00 = K00 * K00 + K01 * K01, C01 = K00 * K10 + K01 * K11, C11 = K10 * K10 + K11 * K11;
+#endif
       const double w = (a.coeff ? a.coeff[base + t] : 1.0) * adet;
       [[maybe_unused]] double wm = 0.0;
       if constexpr (RX)

@@ -93,12 +93,26 @@ struct StressMuArgs
 // stress with a cell-wise shear modulus, every output value mu_T times the value k_primal_flux<P, D, true> forms,
 // rounded once.  A kernel of its own, so that eqlb_primal_flux_dg and eqlb_primal_stress_dg launch the symbols,
 // arguments and code they launched before (tools/isa_compare.py).
+// k_primal_flux_tensor<P, D>, the third variant: the flux -kappa_T D_T grad u_h of eqlb_primal_flux_dg_tensor with the
+// symmetric tensor D_T = (d00, d01, d11) of the cell, one 2 x 2 product per DG coefficient on top of the gradient.
+struct FluxTensorArgs
+{
+  const double* cell_D = nullptr; // [ncells][3]
+};
+
+#define EQLB_FLUX_TENSOR 0
 #define EQLB_FLUX_MU 0
 #include "eqlb_primal_flux_kernel.inc"
 #undef EQLB_FLUX_MU
 #define EQLB_FLUX_MU 1
 #include "eqlb_primal_flux_kernel.inc"
 #undef EQLB_FLUX_MU
+#undef EQLB_FLUX_TENSOR
+#define EQLB_FLUX_TENSOR 1
+#define EQLB_FLUX_MU 0
+#include "eqlb_primal_flux_kernel.inc"
+#undef EQLB_FLUX_MU
+#undef EQLB_FLUX_TENSOR
 
 // The projected VALUE of a P_p function, the piece that turns c u_h into the right-hand side the equilibrator needs for
 // an operator with a reaction term (rhs = Pi_d f - c_T Pi_d u_h):
@@ -187,7 +201,7 @@ static void builtin_table(double* out)
 template <int P, int D>
 static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
                             const double* u, const double* cellJ, const double* coeff, double pi_1, const double* op,
-                            double* out, const StressMuArgs* sx, hipStream_t stream)
+                            double* out, const StressMuArgs* sx, const FluxTensorArgs* tx, hipStream_t stream)
 {
   PrimalOp<P, D> tab;
   if (op)
@@ -195,7 +209,10 @@ static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t n
   else
     builtin_table<P, D>(tab.v);
   const unsigned grid = (unsigned)(((int64_t)ncells + PF_THREADS - 1) / PF_THREADS);
-  if (stress && sx) // the variant with the shear modulus; without it the launch as before the term existed
+  if (!stress && tx) // the variant with the diffusion tensor
+    hipLaunchKernelGGL((k_primal_flux_tensor<P, D>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs,
+                       cell_dofs, u, cellJ, coeff, pi_1, tab, out, *tx);
+  else if (stress && sx) // the variant with the shear modulus; without it the launch as before the term existed
     hipLaunchKernelGGL((k_primal_stress_mu<P, D>), dim3(grid), dim3(PF_THREADS), 0, stream, ncells, nrhs, ndofs, cell_dofs,
                        u, cellJ, coeff, pi_1, tab, out, *sx);
   else if (stress)
@@ -210,18 +227,18 @@ static hipError_t launch_pd(bool stress, int32_t ncells, int32_t nrhs, int64_t n
 template <int P>
 static hipError_t launch_p(int d, bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* cell_dofs,
                            const double* u, const double* cellJ, const double* coeff, double pi_1, const double* op,
-                           double* out, const StressMuArgs* sx, hipStream_t stream)
+                           double* out, const StressMuArgs* sx, const FluxTensorArgs* tx, hipStream_t stream)
 {
   switch (d)
   {
   case 0:
-    return launch_pd<P, 0>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_pd<P, 0>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   case 1:
-    return launch_pd<P, 1>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_pd<P, 1>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   case 2:
-    return launch_pd<P, 2>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_pd<P, 2>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   default:
-    return launch_pd<P, 3>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_pd<P, 3>(stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   }
 }
 
@@ -229,18 +246,18 @@ static hipError_t launch_p(int d, bool stress, int32_t ncells, int32_t nrhs, int
 static hipError_t launch_primal_flux(int p, int d, bool stress, int32_t ncells, int32_t nrhs, int64_t ndofs,
                                      const int32_t* cell_dofs, const double* u, const double* cellJ,
                                      const double* coeff, double pi_1, const double* op, double* out,
-                                     const StressMuArgs* sx, hipStream_t stream)
+                                     const StressMuArgs* sx, const FluxTensorArgs* tx, hipStream_t stream)
 {
   switch (p)
   {
   case 1:
-    return launch_p<1>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_p<1>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   case 2:
-    return launch_p<2>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_p<2>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   case 3:
-    return launch_p<3>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_p<3>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   default:
-    return launch_p<4>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, stream);
+    return launch_p<4>(d, stress, ncells, nrhs, ndofs, cell_dofs, u, cellJ, coeff, pi_1, op, out, sx, tx, stream);
   }
 }
 
@@ -265,11 +282,12 @@ static int table_p(int d, double* out)
 }
 
 // the common body of the entry points; stress: u [ndofs][2], two output rows, coeff = cell_pi1.  shear: the mu / cell_mu
-// of eqlb_primal_stress_dg_mu (cell_mu in `memspace`) or nullptr; mu == 1 without an array is the call without it
+// of eqlb_primal_stress_dg_mu (cell_mu in `memspace`) or nullptr; mu == 1 without an array is the call without it.
+// cell_D: the tensor [ncells][3] of eqlb_primal_flux_dg_tensor in `memspace` (flux only) or nullptr
 static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32_t d, int32_t nrhs, bool stress,
                             const int32_t* cell_dofs, int64_t ndofs, const double* u, const double* coeff,
                             double pi_1, const double* op, double* flux_dg, int32_t memspace, void* stream_,
-                            const StressMuArgs* shear = nullptr)
+                            const StressMuArgs* shear = nullptr, const double* cell_D = nullptr)
 {
   if (p < 1 || p > PF_PMAX || d < 0 || d > PF_DMAX)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: degrees p = %d, degree_dg = %d outside 1 ... 4, 0 ... 3", who, (int)p,
@@ -292,8 +310,9 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (memspace == EQLB_MEM_DEVICE)
   {
+    const FluxTensorArgs tx{cell_D};
     const hipError_t e = launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, cell_dofs, u, m.cellJ, coeff, pi_1, op,
-                                            flux_dg, shear, stream);
+                                            flux_dg, shear, cell_D ? &tx : nullptr, stream);
     return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
   }
   if (shear && shear->cell_mu)
@@ -301,6 +320,16 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
       if (!(shear->cell_mu[i] > 0.0 && std::isfinite(shear->cell_mu[i])))
         return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
                     shear->cell_mu[i]);
+  if (cell_D)
+    for (int32_t i = 0; i < ncells; ++i)
+    {
+      const double d00 = cell_D[3 * i], d01 = cell_D[3 * i + 1], d11 = cell_D[3 * i + 2];
+      if (!(std::isfinite(d00) && std::isfinite(d01) && std::isfinite(d11)))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not finite", who, (int)i, d00, d01, d11);
+      if (!(d00 > 0.0 && d00 * d11 - d01 * d01 > 0.0))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not positive definite", who, (int)i, d00,
+                    d01, d11);
+    }
   // host memory: bad tables are caught here, before anything is launched
   const size_t nidx = (size_t)ncells * np;
   for (size_t i = 0; i < nidx; ++i)
@@ -312,12 +341,14 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
   const auto d_idx = s.in(cell_dofs, nidx);
   const auto d_u = s.in(u, nu), d_c = s.in(coeff, (size_t)ncells);
   const auto d_mu = s.in(shear ? shear->cell_mu : nullptr, (size_t)ncells);
+  const auto d_D = s.in(cell_D, 3 * (size_t)ncells);
   const auto d_out = s.out(flux_dg, nout);
   if (s.upload(stream) != hipSuccess)
     return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
   const StressMuArgs sx{shear && shear->cell_mu ? d_mu.get() : nullptr, shear ? shear->mu : 1.0};
+  const FluxTensorArgs tx{cell_D ? d_D.get() : nullptr};
   s.note(launch_primal_flux(p, d, stress, ncells, nrhs, ndofs, d_idx, d_u, m.cellJ, d_c, pi_1, op, d_out,
-                            shear ? &sx : nullptr, stream));
+                            shear ? &sx : nullptr, cell_D ? &tx : nullptr, stream));
   const hipError_t e = s.finish(stream);
   return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
 }
@@ -448,6 +479,17 @@ int eqlb_primal_flux_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t
 {
   return eqlb::primal_flux_call("eqlb_primal_flux_dg", mesh, p, degree_dg, nrhs, false, cell_dofs, ndofs, u,
                                 cell_coeff, 1.0, op, flux_dg, memspace, stream);
+}
+
+int eqlb_primal_flux_dg_tensor(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
+                               int64_t ndofs, const double* u, const double* cell_coeff, const double* cell_D,
+                               const double* op, double* flux_dg, int32_t memspace, void* stream)
+{
+  if (!cell_D)
+    return fail(EQLB_ERR_INVALID_ARGUMENT,
+                "eqlb_primal_flux_dg_tensor: cell_D is null (eqlb_primal_flux_dg is the entry without a tensor)");
+  return eqlb::primal_flux_call("eqlb_primal_flux_dg_tensor", mesh, p, degree_dg, nrhs, false, cell_dofs, ndofs, u,
+                                cell_coeff, 1.0, op, flux_dg, memspace, stream, nullptr, cell_D);
 }
 
 int eqlb_primal_stress_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, const int32_t* cell_dofs, int64_t ndofs,

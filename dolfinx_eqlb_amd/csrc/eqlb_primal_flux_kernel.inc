@@ -1,7 +1,18 @@
-// The kernel of eqlb_primal_flux.hip, which includes this file twice:
-//   EQLB_FLUX_MU 0  k_primal_flux<P, D, STRESS>: the flux of a P_p solution, or the stress of a displacement
-//   EQLB_FLUX_MU 1  k_primal_stress_mu<P, D>: the stress times the cell-wise shear modulus of `sx`
-#if EQLB_FLUX_MU
+// The kernel of eqlb_primal_flux.hip, which includes this file three times:
+//   EQLB_FLUX_MU 0, EQLB_FLUX_TENSOR 0  k_primal_flux<P, D, STRESS>: the flux of a P_p solution, or the stress of a
+//                                       displacement
+//   EQLB_FLUX_MU 1, EQLB_FLUX_TENSOR 0  k_primal_stress_mu<P, D>: the stress times the cell-wise shear modulus of `sx`
+//   EQLB_FLUX_MU 0, EQLB_FLUX_TENSOR 1  k_primal_flux_tensor<P, D>: the flux -kappa D grad u_h with the cell-wise tensor
+//                                       of `tx`
+#if EQLB_FLUX_TENSOR
+template <int P, int D>
+__global__ void __launch_bounds__(PF_THREADS)
+k_primal_flux_tensor(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __restrict__ cell_dofs,
+                     const double* __restrict__ u, const double* __restrict__ cellJ, const double* __restrict__ coeff,
+                     double pi_1, const PrimalOp<P, D> op, double* __restrict__ out, const FluxTensorArgs tx)
+{
+  constexpr bool STRESS = false;
+#elif EQLB_FLUX_MU
 template <int P, int D>
 __global__ void __launch_bounds__(PF_THREADS)
 k_primal_stress_mu(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __restrict__ cell_dofs,
@@ -45,7 +56,16 @@ k_primal_flux(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __rest
   {
     const double2* Jp = reinterpret_cast<const double2*>(cellJ + 4 * (base + t));
     const double2 r0 = Jp[0], r1 = Jp[1]; // J00 J01 | J10 J11
+#if EQLB_FLUX_TENSOR
+    // (the statement of this variant rounds the two products of the determinant on their own)
+    double idet;
+    {
+#pragma clang fp contract(off)
+      idet = 1.0 / (r0.x * r1.y - r0.y * r1.x);
+    }
+#else
     const double idet = 1.0 / (r0.x * r1.y - r0.y * r1.x);
+#endif
     K00 = r1.y * idet;
     K01 = -r0.y * idet;
     K10 = -r1.x * idet;
@@ -55,6 +75,16 @@ k_primal_flux(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __rest
     else if constexpr (STRESS)
       kap = pi_1;
   }
+#if EQLB_FLUX_TENSOR
+  double d00 = 1.0, d01 = 0.0, d11 = 1.0;
+  if (active)
+  {
+    const double* Dp = tx.cell_D + 3 * (base + t);
+    d00 = Dp[0];
+    d01 = Dp[1];
+    d11 = Dp[2];
+  }
+#endif
   const double bad = __longlong_as_double(0x7ff8000000000000ll);
   __syncthreads(); // the index rows are in registers: sbuf takes the output rows
   if constexpr (!STRESS)
@@ -81,7 +111,20 @@ k_primal_flux(int32_t ncells, int32_t nrhs, int64_t ndofs, const int32_t* __rest
               tt[i] = __dmul_rn(sPG[(X * ND + n) * NP + i], uu[i]);
             g[X] = sorted_sum<NP>(tt);
           }
+#if EQLB_FLUX_TENSOR
+          // grad u_h = K^T g, then one 2 x 2 product with D and the factor -kappa: every product and every sum rounded
+          // on its own (contraction is switched off for this block; the rounding intrinsics alone do not keep the
+          // compiler from fusing their results)
+          double f0, f1;
+          {
+#pragma clang fp contract(off)
+            const double gx = K00 * g[0] + K10 * g[1], gy = K01 * g[0] + K11 * g[1];
+            f0 = -kap * (d00 * gx + d01 * gy);
+            f1 = -kap * (d01 * gx + d11 * gy);
+          }
+#else
           const double f0 = -kap * (K00 * g[0] + K10 * g[1]), f1 = -kap * (K01 * g[0] + K11 * g[1]);
+#endif
           sbuf[t * S + 2 * n] = ok ? f0 : bad;
           sbuf[t * S + 2 * n + 1] = ok ? f1 : bad;
         }

@@ -43,6 +43,13 @@ struct ShearArgs
   double mu = 1.0;
 };
 
+// the diffusion tensor of the Poisson cell kernel (include/eqlb.h): D_T = (d00, d01, d11) = cell_D[cell].  A kernel
+// argument of its own, which the kernels without the term do not take.
+struct DiffArgs
+{
+  const double* cell_D = nullptr; // [ncells][3]
+};
+
 // what eqlb_primal_t and eqlb_elasticity_t share; everything but the grown work space is carved out of one allocation at
 // create
 template <int BS, int MAXC>
@@ -69,6 +76,10 @@ struct SolverHandle
   bool has_react = false, react_cell = false;
   double react_c = 0.0;
   DevBuf<double> react;
+  // the diffusion tensor (solver_set_diffusion, the Poisson unit): off as created.  The array [ncells][3] is allocated by
+  // the first call that brings one and kept; has_diff says whether the kernels read it
+  bool has_diff = false;
+  DevBuf<double> diff;
 };
 
 template <class H>
@@ -439,6 +450,47 @@ int solver_set_shear(const char* who, H* h, double mu, const double* cell_mu, in
   h->shear_cell = cell_mu != nullptr;
   h->shear_mu = cell_mu ? 1.0 : mu;
   h->has_shear = cell_mu != nullptr || mu != 1.0;
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (host)
+    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)
+  return EQLB_OK;
+}
+
+// D_T = cell_D [ncells][3] = (d00, d01, d11) in `memspace`; nullptr switches the term off.  A host array is checked cell
+// by cell before the handle changes: finite, d00 > 0 and d00 d11 - d01^2 > 0 (the products rounded as written here); one
+// in device memory is the caller's responsibility, as cell_c is.  The diagonal of the handle is formed again in place
+// on the stream.
+template <class H>
+int solver_set_diffusion(const char* who, H* h, const double* cell_D, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const size_t nc = (size_t)h->space.ncells;
+  if (cell_D && host)
+    for (size_t i = 0; i < nc; ++i)
+    {
+      const double d00 = cell_D[3 * i], d01 = cell_D[3 * i + 1], d11 = cell_D[3 * i + 2];
+      if (!(std::isfinite(d00) && std::isfinite(d01) && std::isfinite(d11)))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%lld] = (%g, %g, %g) is not finite", who, (long long)i, d00,
+                    d01, d11);
+      if (!(d00 > 0.0 && d00 * d11 - d01 * d01 > 0.0))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%lld] = (%g, %g, %g) is not positive definite", who,
+                    (long long)i, d00, d01, d11);
+    }
+  if (cell_D)
+  {
+    if (!h->diff.get())
+    {
+      const hipError_t e = h->diff.alloc_raw(3 * nc);
+      if (e != hipSuccess)
+        return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed: %s", who, hipGetErrorString(e));
+    }
+    HIP_TRY(hipMemcpyAsync(h->diff.get(), cell_D, 3 * nc * sizeof(double),
+                           host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+  }
+  h->has_diff = cell_D != nullptr;
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
   if (host)
     HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)

@@ -65,20 +65,65 @@ struct CellArgs
 // formed without the term.  The reaction variant is a kernel of its own, k_primal_cell_react, from the same source
 // (eqlb_primal_cell.inc), so that a handle without the term launches the instantiations - symbols, arguments and code -
 // it launched before the term existed.
+// DX replaces the metric K K^T of a cell by K D K^T with the symmetric tensor D_T of eqlb_primal_set_diffusion (include/
+// eqlb.h): eight products and four sums more per cell and nothing more per table entry.  Again kernels of their own,
+// k_primal_cell_diff and k_primal_cell_diff_react, with an argument the others do not take.
+#define EQLB_CELL_DIFF 0
 #define EQLB_CELL_REACT 0
 #include "eqlb_primal_cell.inc"
 #undef EQLB_CELL_REACT
 #define EQLB_CELL_REACT 1
 #include "eqlb_primal_cell.inc"
 #undef EQLB_CELL_REACT
+#undef EQLB_CELL_DIFF
+#define EQLB_CELL_DIFF 1
+#define EQLB_CELL_REACT 0
+#include "eqlb_primal_cell.inc"
+#undef EQLB_CELL_REACT
+#define EQLB_CELL_REACT 1
+#include "eqlb_primal_cell.inc"
+#undef EQLB_CELL_REACT
+#undef EQLB_CELL_DIFF
 
 // ---- host side ------------------------------------------------------------------------------------------------
 // the launch on the columns of c: the load by its DG degree d, the operator by its column count, the diagonal as it is
 template <int P, int MODE>
 hipError_t launch_cell_p(int d, const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride,
-                         const ReactArgs* rx, hipStream_t stream)
+                         const ReactArgs* rx, const DiffArgs* dx, hipStream_t stream)
 {
   const dim3 grid(grid_of(a.ncells, PS_THREADS)), block(PS_THREADS);
+  if constexpr (MODE != CELL_LOAD)
+    if (dx) // the variants with the tensor, with the reaction term or without it
+    {
+#define EQLB_CELL_DX(RR)                                                                                               \
+  do                                                                                                                   \
+  {                                                                                                                    \
+    if (rx)                                                                                                            \
+      hipLaunchKernelGGL((k_primal_cell_diff_react<P, MODE, 0, RR>), grid, block, 0, stream, a, c, ustride, ystride,  \
+                         *rx, *dx);                                                                                    \
+    else                                                                                                               \
+      hipLaunchKernelGGL((k_primal_cell_diff<P, MODE, 0, RR>), grid, block, 0, stream, a, c, ustride, ystride, *dx);  \
+  } while (0)
+      if constexpr (MODE == CELL_DIAGONAL)
+        EQLB_CELL_DX(1);
+      else
+        switch (c.R)
+        {
+        case 1:
+          EQLB_CELL_DX(1);
+          break;
+        case 2:
+          EQLB_CELL_DX(2);
+          break;
+        case 3:
+          EQLB_CELL_DX(3);
+          break;
+        default:
+          EQLB_CELL_DX(4);
+        }
+#undef EQLB_CELL_DX
+      return hipGetLastError();
+    }
   if constexpr (MODE != CELL_LOAD)
     if (rx) // the variants with the reaction term; without it the launches below, as before the term existed
     {
@@ -144,18 +189,18 @@ hipError_t launch_cell_p(int d, const CellArgs& a, const ManyCols& c, int64_t us
 
 template <int MODE>
 hipError_t launch_cell(int p, int d, const CellArgs& a, const ManyCols& c, int64_t ustride, int64_t ystride,
-                       const ReactArgs* rx, hipStream_t stream)
+                       const ReactArgs* rx, const DiffArgs* dx, hipStream_t stream)
 {
   switch (p)
   {
   case 1:
-    return launch_cell_p<1, MODE>(d, a, c, ustride, ystride, rx, stream);
+    return launch_cell_p<1, MODE>(d, a, c, ustride, ystride, rx, dx, stream);
   case 2:
-    return launch_cell_p<2, MODE>(d, a, c, ustride, ystride, rx, stream);
+    return launch_cell_p<2, MODE>(d, a, c, ustride, ystride, rx, dx, stream);
   case 3:
-    return launch_cell_p<3, MODE>(d, a, c, ustride, ystride, rx, stream);
+    return launch_cell_p<3, MODE>(d, a, c, ustride, ystride, rx, dx, stream);
   default:
-    return launch_cell_p<4, MODE>(d, a, c, ustride, ystride, rx, stream);
+    return launch_cell_p<4, MODE>(d, a, c, ustride, ystride, rx, dx, stream);
   }
 }
 
@@ -175,7 +220,9 @@ hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const dou
   a.only_fixed = only_fixed ? 1 : 0;
   a.yloc = work_of(h, c.R).yloc;
   const ReactArgs rx = react_args(h);
-  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, h.has_react ? &rx : nullptr, stream);
+  const DiffArgs dx{h.diff.get()};
+  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, h.has_react ? &rx : nullptr,
+                           h.has_diff ? &dx : nullptr, stream);
 }
 } // namespace
 
@@ -275,6 +322,13 @@ int eqlb_primal_set_reaction(eqlb_primal_t* h, double c, const double* cell_c, i
 try
 {
   return eqlb::solver_set_reaction("eqlb_primal_set_reaction", h, c, cell_c, memspace, stream_);
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_set_diffusion(eqlb_primal_t* h, const double* cell_D, int32_t memspace, void* stream_)
+try
+{
+  return eqlb::solver_set_diffusion("eqlb_primal_set_diffusion", h, cell_D, memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -350,6 +350,18 @@ struct PrimalPoisson
     }
     check(eqlb_primal_set_reaction(h, c, cell_c.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
   }
+  // -div(coeff D grad u): cell_D [ncells][3] = (d00, d01, d11) per cell; None switches the term off
+  void set_diffusion(py::object cell_D)
+  {
+    carray<double> kd;
+    if (!cell_D.is_none())
+    {
+      kd = cell_D.cast<carray<double>>();
+      if (kd.size() != (py::ssize_t)mesh->ncells * 3)
+        throw std::runtime_error("PrimalPoisson.set_diffusion: cell_D [ncells][3] expected");
+    }
+    check(eqlb_primal_set_diffusion(h, cell_D.is_none() ? nullptr : kd.data(), EQLB_MEM_HOST, nullptr));
+  }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
     if (degree_dg >= 0 && degree_dg <= 3
@@ -1558,6 +1570,9 @@ PYBIND11_MODULE(_cpp, m)
       .def("set_reaction", &PrimalPoisson::set_reaction, py::arg("c") = 0.0, py::arg("cell_c") = py::none(),
            "the operator gains + c u: cell_c [ncells] where given, else the scalar; c = 0 without an array switches "
            "the term off; Multilevel.set_coarse(True) has to be called again afterwards")
+      .def("set_diffusion", &PrimalPoisson::set_diffusion, py::arg("cell_D") = py::none(),
+           "the operator becomes -div(coeff D grad u): cell_D [ncells][3] = (d00, d01, d11), symmetric positive "
+           "definite per cell; None switches the term off; Multilevel.set_coarse(True) has to be called again afterwards")
       .def("load", &PrimalPoisson::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
            "b [ndofs] from DG_d nodal values rhs_dg [ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalPoisson::apply, py::arg("u"), py::arg("masked") = false, "y = A u; masked: 0 on the fixed rows")
@@ -1795,6 +1810,41 @@ PYBIND11_MODULE(_cpp, m)
       py::arg("coeff") = py::none(), py::arg("op") = py::none(),
       "[nrhs, ncells*nd_d]: the DG_d DOFs of coeff Pi_d u_h for u_h in P_p (eqlb_primal_value_dg); coeff [ncells] or "
       "None, op [nd_d, nd_p] replaces the built-in table");
+  m.def(
+      "primal_flux_dg",
+      [](std::shared_ptr<Mesh> mesh, int p, int degree_dg, carray<int32_t> cell_dofs, darray u, py::object coeff,
+         py::object op, py::object cell_D) {
+        if (p < 1 || p > 4 || degree_dg < 0 || degree_dg > 3)
+          throw std::runtime_error("primal_flux_dg: degrees outside 1 ... 4, 0 ... 3");
+        const py::ssize_t ndp = (p + 1) * (p + 2) / 2, nd = (degree_dg + 1) * (degree_dg + 2) / 2;
+        const py::ssize_t nrhs = u.ndim() == 2 ? u.shape(0) : 1;
+        carray<double> kc, t, kd;
+        if (!coeff.is_none())
+          kc = coeff.cast<carray<double>>();
+        if (!op.is_none())
+          t = op.cast<carray<double>>();
+        if (!cell_D.is_none())
+          kd = cell_D.cast<carray<double>>();
+        if (cell_dofs.size() != (py::ssize_t)mesh->ncells * ndp || u.size() == 0 || u.size() % nrhs
+            || (!coeff.is_none() && kc.size() != mesh->ncells) || (!op.is_none() && t.size() != 2 * nd * ndp)
+            || (!cell_D.is_none() && kd.size() != (py::ssize_t)mesh->ncells * 3))
+          throw std::runtime_error("primal_flux_dg: Input sizes does not match");
+        darray out({nrhs, (py::ssize_t)mesh->ncells * nd * 2});
+        const double* pk = coeff.is_none() ? nullptr : kc.data();
+        const double* pt = op.is_none() ? nullptr : t.data();
+        if (cell_D.is_none())
+          check(eqlb_primal_flux_dg(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs, u.data(), pk,
+                                    pt, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+        else
+          check(eqlb_primal_flux_dg_tensor(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs,
+                                           u.data(), pk, kd.data(), pt, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+        return out;
+      },
+      py::arg("mesh"), py::arg("p"), py::arg("degree_dg"), py::arg("cell_dofs"), py::arg("u"),
+      py::arg("coeff") = py::none(), py::arg("op") = py::none(), py::arg("cell_D") = py::none(),
+      "[nrhs, ncells*nd_d*2]: the DG_d^2 DOFs of -coeff grad(u_h) for u_h in P_p (eqlb_primal_flux_dg), or of "
+      "-coeff D grad(u_h) with cell_D [ncells][3] = (d00, d01, d11) (eqlb_primal_flux_dg_tensor); coeff [ncells] or "
+      "None, op [2, nd_d, nd_p] replaces the built-in table");
   m.def("device_count", &eqlb_device_count);
   m.def("synchronize_and_check", [](std::shared_ptr<BoundaryData> bd) {
     if (bd->se)

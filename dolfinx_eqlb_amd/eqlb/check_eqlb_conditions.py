@@ -276,6 +276,109 @@ def stress_estimator_terms(mesh, k, sigma, korn=None, pi_1=1.0, cell_pi1=None, m
     return energy, wsym
 
 
+def det_sym2(d00, d01, d11):
+    """d00 d11 - d01^2 within two units of the last place in the number type of the arrays (float64 or long double),
+    however close the tensor is to singular: the two products are split exactly (Veltkamp / Dekker) and their
+    residuals join the difference, as the fused multiply-adds of the estimator kernel do."""
+    T = np.result_type(d00, d01, d11).type
+    split = T(2.0 ** (27 if T is np.float64 else 32) + 1.0)
+
+    def two_prod(a, b):
+        p = a * b
+        ah = split * a
+        ah = ah - (ah - a)
+        bh = split * b
+        bh = bh - (bh - b)
+        al, bl = a - ah, b - bh
+        return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+    a, b, c = np.asarray(d00, dtype=T), np.asarray(d01, dtype=T), np.asarray(d11, dtype=T)
+    p1, e1 = two_prod(a, c)
+    p2, e2 = two_prod(b, b)
+    return (p1 - p2) + (e1 - e2)
+
+
+_FLUX_NORM_TABLES = {}
+
+
+def _flux_norm_tables(k, d):
+    """Exact integrals over the reference triangle as nested lists of Fractions: S[a][b][i][j] = int phi_i^a phi_j^b of
+    the hierarchic RT_k basis, R[a][i][e] = int phi_i^a chi_e and PP[e][g] = int chi_e chi_g with the DG_d nodal basis."""
+    if (k, d) not in _FLUX_NORM_TABLES:
+        from ..elmtlib import polynomials as P
+        rt, dg = ert.HierarchicRT(k), Lagrange(d)
+        comp = [[b[0] for b in rt.basis], [b[1] for b in rt.basis]]
+        n, nd, I = rt.ndofs, dg.ndofs, P.integrate_triangle
+        S = [[[[I(P.mul(comp[a][i], comp[b][j])) for j in range(n)] for i in range(n)] for b in range(2)]
+             for a in range(2)]
+        R = [[[I(P.mul(comp[a][i], dg.basis[e])) for e in range(nd)] for i in range(n)] for a in range(2)]
+        PP = [[I(P.mul(dg.basis[e], dg.basis[g])) for g in range(nd)] for e in range(nd)]
+        _FLUX_NORM_TABLES[(k, d)] = (S, R, PP)
+    return _FLUX_NORM_TABLES[(k, d)]
+
+
+def _rounded(nested, T):
+    """Fractions rounded once to T: float for float64, head + tail for long double"""
+    from fractions import Fraction
+    a = np.array(nested, dtype=object)
+    out = np.empty(a.shape, dtype=T)
+    for idx in np.ndindex(a.shape):
+        hi = float(a[idx])
+        out[idx] = T(hi) if T is np.float64 else T(hi) + T(float(Fraction(a[idx]) - Fraction(hi)))
+    return out
+
+
+def weighted_flux_norm(mesh, k, sigma, flux_dg=None, degree_dg=None, coeff=None, cell_D=None, conforming=False,
+                       dtype=np.float64, return_abs=False):
+    """cell_sig2 [ncells] of eqlb_se_estimate_weighted / eqlb_ev_estimate_weighted, the numpy statement:
+    int_T e^T W e with W_T = adj(D_T) / (kappa_T det D_T) = (kappa_T D_T)^-1, the flux error of -div(kappa D grad u) = f
+    in its energy norm.  e = sigma (the corrector of the discontinuous SE flux; the total flux is sigma + G) or, with
+    conforming=True, sigma - G (an EV flux in the broken layout), sigma [ncells*k(k+2)], G = flux_dg [ncells*nd*2] in
+    DG_d^2, d = degree_dg (k - 1 if None).  coeff [ncells] is kappa (None: 1), cell_D [ncells, 3] = (d00, d01, d11)
+    (None: the identity).  Quadrature-free, evaluated in `dtype` (np.float64 or np.longdouble) from the coordinates and
+    exact reference integrals rounded once: with c the coefficients of a cell,
+      sum_ab (J^T W J)_ab / |det J|  c^T S_ab c  - 2 sign(det J) sum c_i (J^T W G_e)_a R_aie  + |det J| sum G_e^T W G_g PP_eg
+    (the last two terms with conforming=True only).  det D is formed by det_sym2.  return_abs: also the same expression
+    on the absolute values of every factor and term, which bounds the rounding error of any evaluation order."""
+    T = np.dtype(dtype).type
+    d = k - 1 if degree_dg is None else int(degree_dg)
+    S, R, PP = (_rounded(t, T) for t in _flux_norm_tables(k, d))
+    nrt, nd, nc = k * (k + 2), (d + 1) * (d + 2) // 2, mesh.ncells
+    x = mesh.x[:, :2].astype(T)
+    cn = mesh.cell_nodes
+    J = np.stack([x[cn[:, 1]] - x[cn[:, 0]], x[cn[:, 2]] - x[cn[:, 0]]], axis=2)       # J[c, x, a]
+    det = J[:, 0, 0] * J[:, 1, 1] - J[:, 0, 1] * J[:, 1, 0]
+    kap = np.ones(nc, dtype=T) if coeff is None else np.asarray(coeff).astype(T).ravel()
+    W = np.zeros((nc, 2, 2), dtype=T)
+    if cell_D is None:
+        W[:, 0, 0] = W[:, 1, 1] = T(1) / kap
+    else:
+        dd = np.asarray(cell_D).astype(T).reshape(nc, 3)
+        iw = T(1) / (kap * det_sym2(dd[:, 0], dd[:, 1], dd[:, 2]))
+        W[:, 0, 0], W[:, 0, 1], W[:, 1, 0], W[:, 1, 1] = dd[:, 2] * iw, -dd[:, 1] * iw, -dd[:, 1] * iw, dd[:, 0] * iw
+    c = np.asarray(sigma).astype(T).reshape(nc, nrt)
+    ad = np.abs(det)
+
+    def quad(v, SS, M):
+        u = np.einsum("abij,cj->cabi", SS, v)
+        return np.einsum("cab,cab->c", M, np.einsum("ci,cabi->cab", v, u))
+
+    M = np.einsum("cxa,cxy,cyb->cab", J, W, J) / ad[:, None, None]
+    Ma = np.einsum("cxa,cxy,cyb->cab", np.abs(J), np.abs(W), np.abs(J)) / ad[:, None, None]
+    val, A = quad(c, S, M), quad(np.abs(c), np.abs(S), Ma)
+    if conforming:
+        g = np.asarray(flux_dg).astype(T).reshape(nc, nd, 2)
+        wg, wga = np.einsum("cxy,cey->cex", W, g), np.einsum("cxy,cey->cex", np.abs(W), np.abs(g))
+        jg, jga = np.einsum("cxa,cex->cae", J, wg), np.einsum("cxa,cex->cae", np.abs(J), wga)
+        sgn = np.where(det > 0, T(1), T(-1))
+        sg = sgn * np.einsum("ci,cai->c", c, np.einsum("aie,cae->cai", R, jg))
+        sga = np.einsum("ci,cai->c", np.abs(c), np.einsum("aie,cae->cai", np.abs(R), jga))
+        gg = ad * np.einsum("cex,cex->c", wg, np.einsum("eg,cgx->cex", PP, g))
+        gga = ad * np.einsum("cex,cex->c", wga, np.einsum("eg,cgx->cex", np.abs(PP), np.abs(g)))
+        val, A = val - 2 * sg + gg, A + 2 * sga + gga
+    return (val, A) if return_abs else val
+
+
 def cell_diameter(mesh):
     """Longest edge per cell (dolfinx::mesh::h on triangles)."""
     x = mesh.x[mesh.cell_nodes, :2]

@@ -36,6 +36,18 @@ one product and one addition on top of the value formed without the term; everyt
 the owner sum, the mask, the residual, the reference norm and pcg are unchanged.  c = 0 without an array switches the
 term off: the operator is then the one of a fresh object, bit for bit.
 
+THE DIFFUSION TENSOR (PoissonOperator.set_diffusion; eqlb_primal_set_diffusion): the operator becomes
+-div(kappa D grad u) [+ c u] with a symmetric positive definite D_T per cell, cell_D [ncells, 3] = (d00, d01, d11).
+Per cell, with K[X][d] as above and D[0][1] = D[1][0] = d01,
+  T[X][b]   = K[X][0] D[0][b] + K[X][1] D[1][b]
+  C_XY      = T[X][0] K[Y][0] + T[X][1] K[Y][1]        for XY = 00, 01, 11
+every product and every sum rounded on its own; C00, C01, C11 and w = kappa |det| then enter the cell rule, the diagonal
+and the reaction variant exactly as above.  The load is unchanged.  D = I gives the values of an operator without the
+term (signs of zero aside); None switches the term off: the operator is then the one of a fresh object, bit for bit.
+A cell with a value that is not finite, or where d00 > 0 and d00 d11 - d01^2 > 0 do not both hold, is refused by name.
+D is DG_0 data with three components: it crosses a refinement through Refinement.prolong_dg(0, cell_D.ravel(), bs=3).
+diffusion_oscillation_weight gives the factor 1 / sqrt(lambda_min(kappa_T D_T)) of the data oscillation.
+
 THE SHEAR MODULUS (ElasticityOperator.set_shear; eqlb_elasticity_set_shear): the operator becomes
 -div(mu (2 eps(u) + pi_1 div(u) I)) [+ c u] with mu_T > 0 per cell, one scalar or a cell-wise array in the pi_1 /
 cell_pi1 convention.  Per cell, with v the value of the elasticity rule below (before any reaction term),
@@ -211,6 +223,82 @@ def shear_coefficient(who, ncells, mu=1.0, cell_mu=None):
     return mm
 
 
+def diffusion_tensor(who, ncells, cell_D=None):
+    """D_T [ncells, 3] = (d00, d01, d11) of set_diffusion, or None where the term is switched off.  A cell with a value
+    that is not finite, or where d00 > 0 and d00 d11 - d01^2 > 0 do not both hold, is refused, the cell named."""
+    if cell_D is None:
+        return None
+    dd = np.array(cell_D, dtype=np.float64)
+    if dd.size != 3 * ncells:
+        raise ValueError(f"{who}: cell_D [ncells][3] expected")
+    dd = dd.reshape(ncells, 3)
+    fin = np.isfinite(dd).all(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        spd = (dd[:, 0] > 0.0) & (dd[:, 0] * dd[:, 2] - dd[:, 1] * dd[:, 1] > 0.0)
+    bad = np.nonzero(~(fin & spd))[0]
+    if bad.size:
+        i = int(bad[0])
+        why = "not finite" if not fin[i] else "not positive definite"
+        raise ValueError(f"{who}: cell_D[{i}] = ({dd[i, 0]}, {dd[i, 1]}, {dd[i, 2]}) is {why}")
+    return dd
+
+
+def diffusion_min_eigenvalue(cell_D, coeff=None):
+    """lambda_min(kappa_T D_T) [ncells] of cell_D [ncells, 3] = (d00, d01, d11) and the cell-wise kappa (None: 1):
+    kappa ((d00 + d11) / 2 - sqrt(((d00 - d11) / 2)^2 + d01^2)), formed as det D / lambda_max with the accurate
+    determinant of eqlb.check_eqlb_conditions.det_sym2, so that a small eigenvalue keeps its digits."""
+    from ..eqlb.check_eqlb_conditions import det_sym2
+    dd = np.asarray(cell_D, dtype=np.float64).reshape(-1, 3)
+    m, h = 0.5 * (dd[:, 0] + dd[:, 2]), 0.5 * (dd[:, 0] - dd[:, 2])
+    lmax = m + np.sqrt(h * h + dd[:, 1] * dd[:, 1])
+    lmin = det_sym2(dd[:, 0], dd[:, 1], dd[:, 2]) / lmax
+    return lmin if coeff is None else np.asarray(coeff, dtype=np.float64).ravel() * lmin
+
+
+def diffusion_oscillation_weight(cell_D, coeff=None):
+    """The factor 1 / sqrt(lambda_min(kappa_T D_T)) [ncells] that weights the data oscillation h_T / pi || f - Pi f ||_T
+    of a cell in the energy norm of -div(kappa D grad u): hand it to cpp.oscillation as `korn` (the cell-wise factor of
+    the oscillation term), or multiply the unweighted term by it.  A host array operation, no kernel."""
+    return 1.0 / np.sqrt(diffusion_min_eigenvalue(cell_D, coeff))
+
+
+def flux_dg_tensor(mesh, p, degree_dg, cell_dofs, u, cell_D, PG, coeff=None):
+    """The statement of eqlb_primal_flux_dg_tensor, bit for bit: out [nrhs, ncells * nd_d * 2], the DG_d^2 DOFs of
+    -kappa_T D_T grad(u_h) from u [nrhs, ndofs] (or [ndofs]), cell_dofs [ncells, nd_p], cell_D [ncells, 3] = (d00, d01,
+    d11), coeff [ncells] or None (kappa = 1) and the table PG [2, nd_d, nd_p] (cpp.get_primal_table, or the caller's op).
+      gref[n][X] = the nd_p products PG[X][n][i] u[cell_dofs[c][i]], each rounded, sorted ascending and added from the
+                   smallest up (the sum of eqlb_primal_flux_dg, which depends on the set of products only)
+      gx = K00 gref[n][0] + K10 gref[n][1],  gy = K01 gref[n][0] + K11 gref[n][1]     (K = J^-1 as PoissonOperator forms it)
+      out[c][n]  = ((-kappa) (d00 gx + d01 gy), (-kappa) (d01 gx + d11 gy))
+    every product and every sum rounded on its own."""
+    nd, ndp = nd_of(degree_dg), nd_of(p)
+    T = np.asarray(PG, dtype=np.float64).reshape(2, nd, ndp)
+    cd = np.asarray(cell_dofs, dtype=np.int64).reshape(-1, ndp)
+    uu = np.asarray(u, dtype=np.float64)
+    uu = uu.reshape(1, -1) if uu.ndim < 2 else uu
+    dd = diffusion_tensor("flux_dg_tensor", mesh.ncells, cell_D)
+    if dd is None:
+        raise ValueError("flux_dg_tensor: cell_D [ncells][3] expected")
+    x, cn = mesh.x, mesh.cell_nodes
+    J00, J01 = x[cn[:, 1], 0] - x[cn[:, 0], 0], x[cn[:, 2], 0] - x[cn[:, 0], 0]
+    J10, J11 = x[cn[:, 1], 1] - x[cn[:, 0], 1], x[cn[:, 2], 1] - x[cn[:, 0], 1]
+    idet = 1.0 / (J00 * J11 - J01 * J10)
+    K00, K01, K10, K11 = (J11 * idet)[:, None], (-J01 * idet)[:, None], (-J10 * idet)[:, None], (J00 * idet)[:, None]
+    kap = np.ones(mesh.ncells) if coeff is None else np.asarray(coeff, dtype=np.float64).ravel()
+    mk = (-kap)[:, None]
+    d00, d01, d11 = dd[:, 0, None], dd[:, 1, None], dd[:, 2, None]
+    out = []
+    for r in range(uu.shape[0]):
+        prod = np.sort(T[:, None, :, :] * uu[r][cd][None, :, None, :], axis=3)        # [X, c, n, i] ascending in i
+        g = prod[..., 0]
+        for i in range(1, ndp):
+            g = g + prod[..., i]
+        gx, gy = K00 * g[0] + K10 * g[1], K01 * g[0] + K11 * g[1]
+        f0, f1 = mk * (d00 * gx + d01 * gy), mk * (d01 * gx + d11 * gy)
+        out.append(np.stack([f0, f1], axis=2).ravel())
+    return np.stack(out)
+
+
 def cross_table(p):
     """The table [nd_p, nd_p] as doubles, each entry rounded once."""
     return np.array([[float(v) for v in row] for row in cross_table_exact(p)])
@@ -304,9 +392,9 @@ class PoissonOperator:
         det = J00 * J11 - J01 * J10
         idet = 1.0 / det
         K00, K01, K10, K11 = J11 * idet, -J01 * idet, -J10 * idet, J00 * idet
-        self.C00 = K00 * K00 + K01 * K01
-        self.C01 = K00 * K10 + K01 * K11
-        self.C11 = K10 * K10 + K11 * K11
+        self.K = ((K00, K01), (K10, K11))     # K[X][d]
+        self.cell_D = None                    # (d00, d01, d11) [ncells, 3]; None: no diffusion tensor
+        self._metric()
         self.adet = np.abs(det)
         kappa = np.ones(mesh.ncells) if coeff is None else np.asarray(coeff, dtype=np.float64).ravel()
         if kappa.size != mesh.ncells:
@@ -350,6 +438,37 @@ class PoissonOperator:
         cc = reaction_coefficient("set_reaction", self.mesh.ncells, c, cell_c)
         self.wm = None if cc is None else cc * self.adet
 
+    def _metric(self):
+        """C00, C01, C11 [ncells]: K K^T, or K D K^T with the tensor of set_diffusion (the head of this file).  Cabs: what
+        return_abs puts in their place: |C| without the tensor, as before it existed; with it the same two-stage sum on
+        the absolute values of K and D, since K D K^T can cancel where K K^T cannot."""
+        K = self.K
+        if self.cell_D is None:
+            self.C00 = K[0][0] * K[0][0] + K[0][1] * K[0][1]
+            self.C01 = K[0][0] * K[1][0] + K[0][1] * K[1][1]
+            self.C11 = K[1][0] * K[1][0] + K[1][1] * K[1][1]
+            self.Cabs = (np.abs(self.C00), np.abs(self.C01), np.abs(self.C11))
+            return
+        d00, d01, d11 = self.cell_D[:, 0], self.cell_D[:, 1], self.cell_D[:, 2]
+        D = ((d00, d01), (d01, d11))
+        T = [[K[X][0] * D[0][b] + K[X][1] * D[1][b] for b in range(2)] for X in range(2)]
+        self.C00 = T[0][0] * K[0][0] + T[0][1] * K[0][1]
+        self.C01 = T[0][0] * K[1][0] + T[0][1] * K[1][1]
+        self.C11 = T[1][0] * K[1][0] + T[1][1] * K[1][1]
+        Ka = [[np.abs(v) for v in row] for row in K]
+        Da = [[np.abs(v) for v in row] for row in D]
+        Ta = [[Ka[X][0] * Da[0][b] + Ka[X][1] * Da[1][b] for b in range(2)] for X in range(2)]
+        self.Cabs = (Ta[0][0] * Ka[0][0] + Ta[0][1] * Ka[0][1], Ta[0][0] * Ka[1][0] + Ta[0][1] * Ka[1][1],
+                     Ta[1][0] * Ka[1][0] + Ta[1][1] * Ka[1][1])
+
+    def set_diffusion(self, cell_D=None):
+        """The operator becomes -div(kappa D grad u): cell_D [ncells, 3] = (d00, d01, d11) of the symmetric positive
+        definite tensor of each cell; None switches the term off.  A repeated call replaces the tensor; a refused one
+        leaves the operator as it was.  A hierarchy with coarse=True has to be built again afterwards (on the device:
+        Multilevel.set_coarse(True)).  D crosses a refinement through Refinement.prolong_dg(0, cell_D.ravel(), bs=3)."""
+        self.cell_D = diffusion_tensor("set_diffusion", self.mesh.ncells, cell_D)
+        self._metric()
+
     def _add_reaction(self, val, A, m, mA):
         """val + wm m on [ncells, nd] (A: the same with absolute values, or None); unchanged without the term."""
         if self.wm is None:
@@ -364,7 +483,8 @@ class PoissonOperator:
         val = w[:, None] * ((c0 * t[0] + c1 * t[1]) + c2 * t[2])
         if A is None:
             return val
-        return val, np.abs(w)[:, None] * ((np.abs(c0) * A[0] + np.abs(c1) * A[1]) + np.abs(c2) * A[2])
+        a0, a1, a2 = (v[:, None] for v in self.Cabs)
+        return val, np.abs(w)[:, None] * ((a0 * A[0] + a1 * A[1]) + a2 * A[2])
 
     def cell_product(self, u, return_abs=False):
         """y_loc [ncells, nd]."""
@@ -571,6 +691,10 @@ class ElasticityOperator(PoissonOperator):
         self.mu = None                        # mu_T [ncells]; None: no shear modulus (mu = 1)
         self.fixed = np.zeros(2 * self.ndofs, dtype=bool)
         self._slots()
+
+    def set_diffusion(self, cell_D=None):
+        """The elasticity operator knows no diffusion tensor."""
+        raise ValueError("set_diffusion: provided for PoissonOperator only")
 
     def set_shear(self, mu=1.0, cell_mu=None):
         """The stress becomes mu (2 eps(u) + pi_1 div(u) I): mu_T = cell_mu [ncells] where given, else the scalar mu on

@@ -26,11 +26,14 @@ def quadrature_points_physical(mesh, qpoints):
 class PrimalFlux:
     """sigma_h = -coeff grad(u_h) of a conforming P_p solution as an entry of `data` of local_projection: u [ndofs],
     cell_dofs [ncells, (p+1)(p+2)/2] (DOF transformations applied), coeff [ncells] or None.  Formed on the device
-    from the solution vector (cpp.primal_flux_dg), without quadrature."""
+    from the solution vector (cpp.primal_flux_dg), without quadrature.  With cell_D [ncells, 3] = (d00, d01, d11) the
+    flux is -coeff D grad(u_h), the one of PrimalPoisson.set_diffusion; a DG_0 tensor crosses a refinement through
+    Refinement.prolong_dg(0, cell_D.ravel(), bs=3)."""
     u: typing.Any
     cell_dofs: typing.Any
     p: int
     coeff: typing.Any = None
+    cell_D: typing.Any = None
 
 
 @dataclasses.dataclass
@@ -100,7 +103,7 @@ def _project_primal(dmesh, degree, d):
                                    d.pi_1 if per_cell else None, mu=float(d.mu), cell_mu=d.cell_mu)
         return np.ascontiguousarray(out[d.row])
     return cpp.primal_flux_dg(dm, d.p, degree, d.cell_dofs, np.asarray(d.u, dtype=np.float64).reshape(1, -1),
-                              d.coeff)[0]
+                              d.coeff, cell_D=d.cell_D)[0]
 
 
 def local_projection(dmesh, degree: int, data: typing.List[typing.Any], bs: int = 1,

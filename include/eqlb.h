@@ -356,6 +356,20 @@ int eqlb_primal_flux_dg(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t
                         int64_t ndofs, const double* u, const double* cell_coeff, const double* op, double* flux_dg,
                         int32_t memspace, void* stream);
 
+/* eqlb_primal_flux_dg with a diffusion tensor: sigma_h = -kappa_T D_T grad(u_h) in DG_d^2, the flux of
+ * -div(kappa D grad u) = f (eqlb_primal_set_diffusion), with cell_D [ncells][3] = (d00, d01, d11) the symmetric positive
+ * definite tensor of each cell in `memspace` (required; eqlb_primal_flux_dg is the entry without one).  Per cell and DG
+ * coefficient n, with gref[n][X] the sorted sum of eqlb_primal_flux_dg (the same tables, `op` and nrhs) and K = J^-1:
+ *   gx = K00 gref[n][0] + K10 gref[n][1],   gy = K01 gref[n][0] + K11 gref[n][1]            (grad u_h = K^T gref)
+ *   flux_dg[c][n] = ( (-kappa) (d00 gx + d01 gy),  (-kappa) (d01 gx + d11 gy) )
+ * every product and every sum rounded on its own, no fused multiply-add: one 2 x 2 product per DG coefficient on top
+ * of the gradient.  A kernel variant of its own; eqlb_primal_flux_dg launches what it launched before.  Host memory
+ * space: a cell of cell_D with a value that is not finite, or where d00 > 0 and d00 d11 - d01^2 > 0 do not both hold,
+ * is refused by name before anything is launched; device memory space: the array is the caller's responsibility. */
+int eqlb_primal_flux_dg_tensor(eqlb_mesh_t* mesh, int32_t p, int32_t degree_dg, int32_t nrhs, const int32_t* cell_dofs,
+                               int64_t ndofs, const double* u, const double* cell_coeff, const double* cell_D,
+                               const double* op, double* flux_dg, int32_t memspace, void* stream);
+
 /* The same for a displacement u_h in P_p^2 and the stress of demo/elasticity_adaptive/demo_cook.py,
  * sigma_h = 2 eps(u_h) + pi_1 div(u_h) I (local_projection of its rows, lsolver/projection.py:17-77):
  *   u        [ndofs][2]  blocked displacement (x[2*dof + r]), cell_dofs the scalar dofmap as above
@@ -492,6 +506,28 @@ int eqlb_ev_estimate(eqlb_mesh_t* mesh, int32_t k, int32_t nrhs, const double* f
 int eqlb_ev_estimate_dg(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_broken,
                         const double* flux_dg, const double* rhs_dg, double* cell_div2, double* cell_sig2,
                         double* facet_jump, int32_t memspace, void* stream);
+
+/* eqlb_se_estimate_dg / eqlb_ev_estimate_dg in the energy norm of -div(kappa D grad u) = f: only cell_sig2 changes,
+ *   cell_sig2 = int_T e^T W e,   W_T = adj(D_T) / (kappa_T det D_T) = (kappa_T D_T)^-1,
+ * with e = sigma_eq (SE) or sigma_eq - G (EV) as in the entries above, kappa_T = cell_coeff[c] (NULL: 1) and
+ * D_T = cell_D[c] = (d00, d01, d11) (NULL: the identity), both in `memspace`; adj(D) = (d11, -d01; -d01, d00), formed in
+ * the kernel.  In the quadrature-free form of the unweighted entries this is three substitutions: the metric
+ * J^T W J / |det J| for J^T J / |det J|, the cross term J^T W G_d for J^T G_d, and G_d^T W G_e for G_d . G_e.
+ * cell_div2 and facet_jump come from the kernels of eqlb_se_estimate_dg / eqlb_ev_estimate_dg themselves: bit for bit the
+ * values of the unweighted entry.  degree_dg is explicit, 0 <= degree_dg <= k - 1.  With both arrays NULL the call is
+ * the unweighted one.  Host memory space: a cell_coeff[i] that is not > 0 and finite, or a cell of cell_D with a value
+ * that is not finite or where d00 > 0 and d00 d11 - d01^2 > 0 do not both hold, is refused by name before anything is
+ * launched; device memory space: the arrays are the caller's responsibility.
+ * The data oscillation of such a problem is weighted by 1 / sqrt(lambda_min(kappa_T D_T)) per cell: the `korn` factor of
+ * eqlb_oscillation (lsolver.primal.diffusion_oscillation_weight forms it on the host). */
+int eqlb_se_estimate_weighted(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_hdiv,
+                              const double* flux_dg, const double* rhs_dg, const double* cell_coeff,
+                              const double* cell_D, double* cell_div2, double* cell_sig2, double* facet_jump,
+                              int32_t memspace, void* stream);
+int eqlb_ev_estimate_weighted(eqlb_mesh_t* mesh, int32_t k, int32_t degree_dg, int32_t nrhs, const double* flux_broken,
+                              const double* flux_dg, const double* rhs_dg, const double* cell_coeff,
+                              const double* cell_D, double* cell_div2, double* cell_sig2, double* facet_jump,
+                              int32_t memspace, void* stream);
 
 /* Stress estimator terms of demo/elasticity/demo_error_estimation.py:49-148 for an equilibrated stress
  * delta_sigma = (row 0; row 1), flux_hdiv [2][ncells*k(k+2)] as eqlb_se_equilibrate writes it, per cell:
@@ -959,6 +995,29 @@ void eqlb_refine_destroy(eqlb_refine_t* plan);
  *                            EQLB_ERR_INVALID_ARGUMENT, the cell named, before anything changes; the call waits
  *   device memory space      the array is taken as it is, nothing waits (but for the first allocation): an indefinite
  *                            operator shows in the breakdown flag of the CG.  The scalar is checked as above
+ *
+ * THE DIFFUSION TENSOR: eqlb_primal_set_diffusion turns the operator into -div(kappa D grad u) (+ c u) with a symmetric
+ * positive definite D_T per cell - anisotropic diffusion, layered media, rotated principal axes, heat conduction in
+ * composites, Darcy flow.  cell_D [ncells][3] = (d00, d01, d11) per cell; kappa_T stays the coefficient of create.  With
+ * K = J^-1 as formed above, K[X][d] (K[0][0] = K00, K[0][1] = K01, K[1][0] = K10, K[1][1] = K11), and D[0][0] = d00,
+ * D[0][1] = D[1][0] = d01, D[1][1] = d11:
+ *   T[X][b]   = K[X][0] D[0][b] + K[X][1] D[1][b]
+ *   C_XY      = T[X][0] K[Y][0] + T[X][1] K[Y][1]        for XY = 00, 01, 11
+ * every product and every sum rounded on its own, no fused multiply-add; C00, C01, C11 and w = kappa |det J| are then
+ * used exactly as in the rule above, in the operator and in the diagonal, with the reaction term or without it.  D = I
+ * gives the values of a handle without the term (signs of zero aside).  The load knows no tensor.  apply, apply_many,
+ * diagonal, residual, solve, solve_many and a hierarchy that holds the handle pick the variant from the handle.
+ *   cell_D == NULL           switches the term off: the handle launches the kernels it launched before
+ *   cell_D [ncells][3]       in `memspace`, copied into an array the handle owns, allocated by the first call that
+ *                            brings one (nothing is allocated at create).  A repeated call replaces the tensor
+ *   diagonal                 formed again in place on `stream`; the dense factor of eqlb_hierarchy_set_coarse is a
+ *                            SNAPSHOT: call eqlb_hierarchy_set_coarse(.., 1, ..) again after the tensor of level 0 changes
+ *   host memory space        a cell with a value that is not finite, or where d00 > 0 and d00 d11 - d01^2 > 0 do not both
+ *                            hold, is refused with EQLB_ERR_INVALID_ARGUMENT, the cell named, before anything changes;
+ *                            the call waits
+ *   device memory space      the array is taken as it is, nothing waits (but for the first allocation)
+ * D is cell-wise constant data: it crosses a refinement through eqlb_refine_prolong_dg at degree 0 with bs = 3, nrhs = 1
+ * on the array as it is ([ncells][3] is the layout x[bs dof + cb] of DG_0 data with three components).
  */
 typedef struct eqlb_primal eqlb_primal_t;
 int eqlb_get_stiffness_table(int32_t p, double* out, int32_t capacity);
@@ -969,6 +1028,7 @@ void eqlb_primal_destroy(eqlb_primal_t* handle);
 int eqlb_primal_ndofs(const eqlb_primal_t* handle, int64_t* ndofs);
 int eqlb_get_mass_table(int32_t p, double* out, int32_t capacity);
 int eqlb_primal_set_reaction(eqlb_primal_t* handle, double c, const double* cell_c, int32_t memspace, void* stream);
+int eqlb_primal_set_diffusion(eqlb_primal_t* handle, const double* cell_D, int32_t memspace, void* stream);
 
 /* Fixed are the vertex and facet DOFs of the listed facets [nlist] (the lists eqlb_refine_child_facets carries across
  * a refinement); a repeated call replaces the mask, nlist = 0 clears it.  A facet id outside the mesh: host memory

@@ -42,6 +42,12 @@ tests/test_estimator_bound.py projected to DG_{p-1}, kappa = 1, Dirichlet all ar
              on every level for every tau of --taus (1e-2 and 1e-4) next to c = 0: iterations and time to rtol 1e-8 from zero of the
              Jacobi entry, of the hierarchy, and of the hierarchy with local smoothing and the exact coarse solve
              (factored again after every change of c).  One run each
+  --diffusion  instead of the figures above: the cell-wise diffusion tensor of set_diffusion (Poisson only; random rotations
+             of diag(1, 1e-2)).  At --n, for every degree: the masked product without and with the tensor ON THE SAME
+             HANDLE in one process, switched by set_diffusion; primal_flux_dg of degree p - 1 against
+             primal_flux_dg_tensor; cell_sig2 of estimate at k = p against the weighted entry.  Medians of --repeats
+             blocks of --products calls, the spread beside them.  With --plain-only the product without the term alone
+             (runs on a library without the term too: EQLB_AMD_LIB, for an A/B against another build in one session).
   --shear    instead of the figures above: the cell-wise shear modulus of set_shear (elasticity only).  (1) At --n, for every
              degree: one masked elasticity product without and with the term (a cell-wise mu, log-uniform in [1e-3, 1e3])
              ON THE SAME HANDLE in one process, switched by set_shear, and primal_stress_dg_mu (degree p - 1, the same mu)
@@ -512,6 +518,110 @@ def run_reaction(args, cpp, torch, res):
         mlc.close()
 
 
+def on_off_blocks(args, torch, fns, probe):
+    """median, spread and all block times per state of fns = {state: (prepare, call)}; the states are off and on"""
+    probes = settle_probes(probe)
+    t = {s_: [] for s_ in fns}
+    for _ in range(args.repeats):
+        for s_, (prepare, call) in fns.items():
+            prepare()
+            t[s_].append(timed_calls(torch, call, args.products))
+    r = dict(products=args.products, repeats=args.repeats, settle_probes=len(probes))
+    for s_ in fns:
+        r[s_] = dict(median_ms=float(np.median(t[s_])), spread_ms=float(np.ptp(t[s_])), all_ms=t[s_])
+    r["ratio"] = r["on"]["median_ms"] / r["off"]["median_ms"]
+    diff = r["on"]["median_ms"] - r["off"]["median_ms"]
+    r["difference_exceeds_spread"] = bool(abs(diff) > max(r["on"]["spread_ms"], r["off"]["spread_ms"]))
+    return r
+
+
+def on_off_line(args, r):
+    return (f" without the term {r['off']['median_ms']:.4f} ms (spread {r['off']['spread_ms']:.4f}), with it "
+            f"{r['on']['median_ms']:.4f} ms (spread {r['on']['spread_ms']:.4f}) = {r['ratio']:.3f} of it; the "
+            f"difference exceeds the spread: {r['difference_exceeds_spread']}; median of {args.repeats} blocks of "
+            f"{args.products} calls after {r['settle_probes']} probes")
+
+
+def run_diffusion(args, cpp, torch, res):
+    """the figures of --diffusion"""
+    from dolfinx_eqlb_amd.mesh import create_unit_square
+    dm = cpp.DeviceMesh(create_unit_square(args.n, shuffle_seed=3, perturb=0.15))
+    nc = dm.mesh.ncells
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    th = np.pi * torch.rand(nc, dtype=torch.float64, device="cuda", generator=gen)
+    c, s_, eps = torch.cos(th), torch.sin(th), 1e-2
+    D = torch.stack([c * c + eps * s_ * s_, c * s_ * (1.0 - eps), s_ * s_ + eps * c * c], dim=1).contiguous()
+    for p in args.degrees:
+        h, _ = make_problem(cpp, torch, dm, p)
+        n = h.ndofs
+        x = torch.from_numpy(np.random.default_rng(0).standard_normal(n)).cuda()
+        y = torch.empty_like(x)
+
+        def product():
+            h.apply_raw(x.data_ptr(), y.data_ptr(), True)
+
+        def probe():
+            product()
+            torch.cuda.synchronize()
+
+        if args.plain_only:
+            probes = settle_probes(probe)
+            t = [timed_calls(torch, product, args.products) for _ in range(args.repeats)]
+            r = dict(cells=nc, rows=n, products=args.products, repeats=args.repeats, settle_probes=len(probes),
+                     off=dict(median_ms=float(np.median(t)), spread_ms=float(np.ptp(t)), all_ms=t))
+            say(f"P_{p}: {n} rows; product without the term {r['off']['median_ms']:.4f} ms (spread "
+                f"{r['off']['spread_ms']:.4f}); median of {args.repeats} blocks of {args.products} products after "
+                f"{len(probes)} probes")
+            res[f"DIFFUSION_PRODUCT_P{p}"] = r
+            h.close()
+            continue
+        r = on_off_blocks(args, torch, {"off": (lambda: h.set_diffusion_raw(None), product),
+                                        "on": (lambda: h.set_diffusion_raw(D.data_ptr()), product)}, probe)
+        r.update(cells=nc, rows=n)
+        say(f"P_{p}: {n} rows; product" + on_off_line(args, r))
+        res[f"DIFFUSION_PRODUCT_P{p}"] = r
+        h.close()
+        # the projected flux of degree p - 1
+        cd, ndofs = dm.lagrange_dofmap(p, device=True)
+        d = p - 1
+        nd = (d + 1) * (d + 2) // 2
+        G = torch.empty(nc * nd * 2, dtype=torch.float64, device="cuda")
+
+        def plain():
+            cpp.primal_flux_dg_raw(dm, p, d, 1, cd.data_ptr(), ndofs, x.data_ptr(), None, G.data_ptr())
+
+        def tensor():
+            cpp.primal_flux_dg_tensor_raw(dm, p, d, 1, cd.data_ptr(), ndofs, x.data_ptr(), None, D.data_ptr(), G.data_ptr())
+
+        def probe_flux():
+            plain()
+            torch.cuda.synchronize()
+
+        r = on_off_blocks(args, torch, {"off": (lambda: None, plain), "on": (lambda: None, tensor)}, probe_flux)
+        r.update(cells=nc, degree_dg=d)
+        say(f"P_{p}: primal_flux_dg of degree {d}" + on_off_line(args, r))
+        res[f"DIFFUSION_FLUX_P{p}"] = r
+        # the flux norm of the estimator at k = p with DG_{k-1} data (every call waits for the device by itself)
+        k = p
+        xe = torch.from_numpy(np.random.default_rng(1).standard_normal(nc * k * (k + 2))).cuda()
+        fe = torch.from_numpy(np.random.default_rng(2).standard_normal(nc * nd)).cuda()
+        sig = torch.empty(nc, dtype=torch.float64, device="cuda")
+        tensor()
+
+        def est_plain():
+            cpp.estimate_raw(dm, k, 1, xe.data_ptr(), G.data_ptr(), fe.data_ptr(), None, sig.data_ptr(), None,
+                             degree_dg=d)
+
+        def est_weighted():
+            cpp.estimate_weighted_raw(dm, k, d, 1, xe.data_ptr(), G.data_ptr(), fe.data_ptr(), None, D.data_ptr(), None,
+                                      sig.data_ptr(), None)
+
+        r = on_off_blocks(args, torch, {"off": (lambda: None, est_plain), "on": (lambda: None, est_weighted)}, est_plain)
+        r.update(cells=nc, k=k, degree_dg=d)
+        say(f"RT_{k}: cell_sig2 of the estimate" + on_off_line(args, r))
+        res[f"DIFFUSION_ESTIMATE_K{k}"] = r
+
+
 def run_shear(args, cpp, torch, res):
     """the figures of --shear"""
     from dolfinx_eqlb_amd.mesh import create_unit_square
@@ -521,26 +631,10 @@ def run_shear(args, cpp, torch, res):
     mu = 10.0 ** (-3.0 + 6.0 * torch.rand(nc, dtype=torch.float64, device="cuda", generator=gen))
 
     def blocks(fns, probe):
-        """median, spread and all block times per state of fns = {state: (prepare, call)}"""
-        probes = settle_probes(probe)
-        t = {s_: [] for s_ in fns}
-        for _ in range(args.repeats):
-            for s_, (prepare, call) in fns.items():
-                prepare()
-                t[s_].append(timed_calls(torch, call, args.products))
-        r = dict(products=args.products, repeats=args.repeats, settle_probes=len(probes))
-        for s_ in fns:
-            r[s_] = dict(median_ms=float(np.median(t[s_])), spread_ms=float(np.ptp(t[s_])), all_ms=t[s_])
-        r["ratio"] = r["on"]["median_ms"] / r["off"]["median_ms"]
-        diff = r["on"]["median_ms"] - r["off"]["median_ms"]
-        r["difference_exceeds_spread"] = bool(abs(diff) > max(r["on"]["spread_ms"], r["off"]["spread_ms"]))
-        return r
+        return on_off_blocks(args, torch, fns, probe)
 
     def line(what, r):
-        return (f"{what} without the term {r['off']['median_ms']:.4f} ms (spread {r['off']['spread_ms']:.4f}), with it "
-                f"{r['on']['median_ms']:.4f} ms (spread {r['on']['spread_ms']:.4f}) = {r['ratio']:.3f} of it; the "
-                f"difference exceeds the spread: {r['difference_exceeds_spread']}; median of {args.repeats} blocks of "
-                f"{args.products} calls after {r['settle_probes']} probes")
+        return what + on_off_line(args, r)[1:]
 
     for p in args.degrees:
         h, _ = make_problem(cpp, torch, dm, p, True)
@@ -659,6 +753,7 @@ def main():
     ap.add_argument("--plain-only", action="store_true",
                     help="--reaction: time the product without the term alone (runs on a library without the term too)")
     ap.add_argument("--shear", action="store_true", help="the figures of the cell-wise shear modulus instead")
+    ap.add_argument("--diffusion", action="store_true", help="the figures of the cell-wise diffusion tensor instead")
     ap.add_argument("--check-every", nargs="*", default=[], metavar="LIB:N")
     ap.add_argument("--check-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -693,6 +788,10 @@ def main():
         return
     if args.shear:
         run_shear(args, cpp, torch, res)
+        print(json.dumps(res))
+        return
+    if args.diffusion:
+        run_diffusion(args, cpp, torch, res)
         print(json.dumps(res))
         return
     if args.nrhs:
