@@ -65,6 +65,9 @@ EXPORTED_SYMBOLS = [
     "eqlb_primal_value_dg", "eqlb_get_value_table",
     "eqlb_elasticity_set_shear", "eqlb_primal_stress_dg_mu", "eqlb_se_estimate_stress_mu",
     "eqlb_primal_set_diffusion", "eqlb_primal_flux_dg_tensor", "eqlb_se_estimate_weighted", "eqlb_ev_estimate_weighted",
+    "eqlb_primal_matrix_pattern", "eqlb_primal_matrix_export", "eqlb_primal_matrix_values", "eqlb_primal_matrix_release",
+    "eqlb_elasticity_matrix_pattern", "eqlb_elasticity_matrix_export", "eqlb_elasticity_matrix_values",
+    "eqlb_elasticity_matrix_release", "eqlb_csr_apply",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -195,7 +198,8 @@ def lib():
         for name in ("eqlb_mesh_destroy", "eqlb_se_destroy", "eqlb_ev_destroy", "eqlb_halo_destroy",
                      "eqlb_rccl_comm_destroy"):
             getattr(L, name).restype = None
-        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy", "eqlb_elasticity_destroy", "eqlb_hierarchy_destroy"):
+        for name in ("eqlb_refine_destroy", "eqlb_primal_destroy", "eqlb_elasticity_destroy", "eqlb_hierarchy_destroy",
+                     "eqlb_primal_matrix_release", "eqlb_elasticity_matrix_release"):
             if hasattr(L, name):   # (a library of an earlier revision, EQLB_AMD_LIB: A/B runs of bench.py)
                 getattr(L, name).restype = None
         _lib = L
@@ -1643,6 +1647,58 @@ class _PrimalSolver:
                                  C.c_int32(memspace), C.c_void_p(stream)))
         return _primal_info(v)
 
+    # ---- the operator as CSR (eqlb_primal_matrix_* / eqlb_elasticity_matrix_*; lsolver.primal: matrix, csr_apply) ----
+    def matrix_pattern_raw(self, stream=0):
+        """nnz: builds the pattern on `stream` at the first call (which waits for the count), then it is cached."""
+        n = C.c_int64(0)
+        _check(self._fn("matrix_pattern")(self._h, C.byref(n), C.c_void_p(stream)))
+        return int(n.value)
+
+    def matrix_export_raw(self, indptr, indices, memspace=MEM_DEVICE, stream=0):
+        """indptr int64 [bs ndofs + 1] and indices int32 [nnz] behind raw pointers in `memspace`."""
+        _check(self._fn("matrix_export")(self._h, _vp(indptr), _vp(indices), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def matrix_values_raw(self, eliminate, values, capacity, memspace=MEM_DEVICE, stream=0):
+        """values float64 [nnz] behind a raw pointer in `memspace`, from what the handle holds now."""
+        _check(self._fn("matrix_values")(self._h, C.c_int32(eliminate), _vp(values), C.c_int64(capacity),
+                                         C.c_int32(memspace), C.c_void_p(stream)))
+
+    def matrix_values(self, eliminate=False, device=False, stream=0):
+        """values [nnz] of the matrix from the coefficients, the terms and the mask the handle has now: the refill after
+        set_reaction, set_shear, set_diffusion or set_dirichlet, on the pattern as it stands.  eliminate: P A P + (I - P)
+        on the mask.  device=True: a torch tensor on the device, written on `stream`."""
+        flag = int(eliminate) if isinstance(eliminate, (bool, int, np.integer)) else -1
+        nnz = self.matrix_pattern_raw(stream)
+        if device:
+            import torch
+            v = torch.empty(nnz, dtype=torch.float64, device="cuda")
+            self.matrix_values_raw(flag, v.data_ptr(), nnz, MEM_DEVICE, stream)
+            return v
+        v = np.zeros(nnz)
+        self.matrix_values_raw(flag, v.ctypes.data, nnz, MEM_HOST, stream)
+        return v
+
+    def matrix(self, eliminate=False, device=False, stream=0):
+        """(indptr int64 [n + 1], indices int32 [nnz], values float64 [nnz]), n = bs ndofs: the operator as CSR,
+        scipy.sparse.csr_matrix((values, indices, indptr), shape=(n, n)); lsolver.primal states the rule, the arrays
+        have its bits.  The pattern is built at the first call and kept in the handle (matrix_release frees it).
+        device=True: torch tensors on the device, written on `stream`."""
+        nnz = self.matrix_pattern_raw(stream)
+        n = self._bs * self.ndofs
+        if device:
+            import torch
+            ip = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+            ix = torch.empty(nnz, dtype=torch.int32, device="cuda")
+            self.matrix_export_raw(ip.data_ptr(), ix.data_ptr(), MEM_DEVICE, stream)
+        else:
+            ip, ix = np.zeros(n + 1, dtype=np.int64), np.zeros(nnz, dtype=np.int32)
+            self.matrix_export_raw(ip.ctypes.data, ix.ctypes.data, MEM_HOST, stream)
+        return ip, ix, self.matrix_values(eliminate, device, stream)
+
+    def matrix_release(self):
+        """Frees the cached pattern; the next matrix() builds it again."""
+        self._fn("matrix_release")(self._h)
+
     def close(self):
         if self._h:
             self._fn("destroy")(self._h)
@@ -1653,6 +1709,33 @@ class _PrimalSolver:
             self.close()
         except Exception:
             pass
+
+
+def csr_apply_raw(n, indptr, indices, values, x, y, memspace=MEM_DEVICE, stream=0):
+    """eqlb_csr_apply on raw pointers in `memspace`."""
+    _check(lib().eqlb_csr_apply(C.c_int64(n), _vp(indptr), _vp(indices), _vp(values), _vp(x), _vp(y),
+                                C.c_int32(memspace), C.c_void_p(stream)))
+
+
+def csr_apply(indptr, indices, values, x, stream=0):
+    """y = A x for a CSR matrix on the device (eqlb_csr_apply; lsolver.primal.csr_apply states the sum): host arrays, or
+    torch tensors on the device (int64, int32, float64, float64), which are read on `stream`."""
+    if not isinstance(x, np.ndarray) and hasattr(x, "data_ptr"):
+        import torch
+        y = torch.empty_like(x)
+        csr_apply_raw(x.numel(), indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), x.data_ptr(), y.data_ptr(),
+                      MEM_DEVICE, stream)
+        return y
+    ip = np.ascontiguousarray(indptr, dtype=np.int64).ravel()
+    ix = np.ascontiguousarray(indices, dtype=np.int32).ravel()
+    v = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    xx = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    if ip.size != xx.size + 1 or ix.size != v.size or (ip.size and int(ip[-1]) != v.size):
+        raise RuntimeError("csr_apply: Input sizes does not match")
+    y = np.zeros(xx.size)
+    csr_apply_raw(xx.size, ip.ctypes.data, ix.ctypes.data, v.ctypes.data, xx.ctypes.data, y.ctypes.data, MEM_HOST,
+                  stream)
+    return y
 
 
 class PrimalPoisson(_PrimalSolver):

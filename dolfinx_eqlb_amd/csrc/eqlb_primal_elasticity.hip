@@ -161,6 +161,14 @@ hipError_t launch_cell(const eqlb_elasticity& h, const ManyCols& c, int d, const
 } // namespace
 
 void elasticity_level(eqlb_elasticity* h, SolverLevel& v) { solver_level(h, v); }
+void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v)
+{
+  solver_matrix_view(h, v);
+  v.pi_1 = h->pi_1;
+  v.has_shear = h->has_shear;
+  v.shear_cell = h->shear_cell ? h->shear.get() : nullptr;
+  v.shear_mu = h->shear_mu;
+}
 } // namespace eqlb
 
 extern "C" {

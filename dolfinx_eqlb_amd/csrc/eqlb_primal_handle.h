@@ -25,6 +25,39 @@
 
 namespace eqlb
 {
+// The CSR pattern of a handle's operator (include/eqlb.h: eqlb_primal_matrix_pattern), built once by
+// eqlb_primal_matrix.hip and kept until eqlb_*_matrix_release or the end of the handle.  It is the SCALAR pattern - the
+// sorted distinct pairs (d, d') of DOFs with a common cell; the bs * bs blocked entries of a pair follow from it by
+// index arithmetic (row bs d + r: first bs bs sptr[d] + r bs len(d), then bs k + s), so a [P_p]^2 handle stores a
+// quarter of its index arrays.
+struct MatrixPattern
+{
+  bool built = false;
+  int64_t snnz = 0;           // pairs; the matrix has bs * bs * snnz entries
+  DevBuf<int64_t> sptr;       // [ndofs + 1] first pair of a DOF's row
+  DevBuf<int32_t> srow, scol; // [snnz] the DOFs of a pair
+  size_t peak_bytes = 0;      // device memory at the peak of the build, the kept arrays included
+};
+
+// A solver handle as eqlb_primal_matrix.hip sees it: a view that owns nothing, all pointers DEVICE.  coeff: kappa
+// (bs = 1) or pi_1 (bs = 2) per cell, or nullptr (1, or the scalar pi_1)
+struct MatrixView
+{
+  int bs = 1, p = 0, nd = 0;
+  int64_t ndofs = 0;
+  int32_t nnodes = 0, nfacets = 0, ncells = 0, ne = 0, ni = 1;
+  const int32_t *nco = nullptr, *fco = nullptr, *slots = nullptr, *cell_dofs = nullptr;
+  const double *cellJ = nullptr, *coeff = nullptr;
+  double pi_1 = 1.0;
+  bool has_react = false, has_shear = false, has_diff = false;
+  const double *react_cell = nullptr, *shear_cell = nullptr, *diff = nullptr;
+  double react_c = 0.0, shear_mu = 1.0;
+  const uint8_t* fixed = nullptr;
+  MatrixPattern* pattern = nullptr;
+};
+void primal_matrix_view(eqlb_primal* h, MatrixView& v);         // eqlb_primal_solve.hip
+void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v); // eqlb_primal_elasticity.hip
+
 namespace
 {
 // the reaction term of a cell kernel (include/eqlb.h): c_T = cell_c[cell] where given, else the scalar c.  A kernel
@@ -80,6 +113,8 @@ struct SolverHandle
   // the first call that brings one and kept; has_diff says whether the kernels read it
   bool has_diff = false;
   DevBuf<double> diff;
+  // the CSR pattern of the operator (eqlb_primal_matrix.hip): empty until eqlb_*_matrix_pattern
+  MatrixPattern pattern;
 };
 
 template <class H>
@@ -237,6 +272,36 @@ void solver_level(H* h, SolverLevel& v)
   v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
     return enqueue_product(*static_cast<H*>(hh), c, stream);
   };
+}
+
+// the handle as the matrix unit sees it; a unit with further coefficients (pi_1, the shear modulus) adds them
+template <class H>
+void solver_matrix_view(H* h, MatrixView& v)
+{
+  v = MatrixView{};
+  const SpaceArgs& s = h->space;
+  v.bs = H::bs;
+  v.p = h->p;
+  v.nd = h->nd;
+  v.ndofs = h->ndofs;
+  v.nnodes = s.nnodes;
+  v.nfacets = s.nfacets;
+  v.ncells = s.ncells;
+  v.ne = s.ne;
+  v.ni = s.ni;
+  v.nco = s.nco;
+  v.fco = s.fco;
+  v.slots = s.slots;
+  v.cell_dofs = h->cell_dofs;
+  v.cellJ = h->mesh->m.cellJ;
+  v.coeff = h->has_coeff ? h->coeff.get() : nullptr;
+  v.has_react = h->has_react;
+  v.react_cell = h->react_cell ? h->react.get() : nullptr;
+  v.react_c = h->react_c;
+  v.has_diff = h->has_diff;
+  v.diff = h->has_diff ? h->diff.get() : nullptr;
+  v.fixed = h->fixed;
+  v.pattern = &h->pattern;
 }
 
 // ---- the C entries behind their names (`who`) -------------------------------------------------------------------------

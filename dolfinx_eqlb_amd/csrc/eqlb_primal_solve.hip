@@ -227,6 +227,7 @@ hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const dou
 } // namespace
 
 void primal_level(eqlb_primal* h, SolverLevel& v) { solver_level(h, v); }
+void primal_matrix_view(eqlb_primal* h, MatrixView& v) { solver_matrix_view(h, v); }
 } // namespace eqlb
 
 extern "C" {

@@ -54,6 +54,26 @@
 #define EQLB_PRIMAL_CHECK_EVERY 64
 #endif
 
+// ---- the product with an assembled matrix (eqlb_primal_matrix.hip: k_csr_apply) ----
+// CSR_GROUP: lanes that sum the rows of a bundle together (a power of two, 2 ... 64); CSR_GROUP_MIN: entries of the longest
+// row of a bundle from which they do.  One eqlb_csr_apply at 1M triangles, ms, P_1 / P_2 Poisson, [P_1]^2 / [P_2]^2
+// elasticity (7, 11.5, 14 and 23 entries per row; tools/matrix_time.py --product-only, medians of 5 blocks of 200 calls,
+// one run each, spreads below 0.006):
+//   one row per thread only   0.0209  0.2083  0.1043  1.3428
+//   2, 16    0.0205  0.1762  0.0896  0.8175        2, 8     0.0253  0.1955  0.0929  0.8160
+//   4, 16    0.0206  0.1641  0.0835  0.7453        4, 8     0.0259  0.2176  0.0916  0.7469
+//   4, 12    0.0212  0.1717  0.0819  0.7441        4, 24    0.0206  0.1637  0.1035  0.7828
+//   8, 16    0.0214  0.1737  0.0991  0.9080        8, 8     0.0350  0.2877  0.1270  0.9096
+//   16, 24   0.0215  0.1906  0.1039  0.9501        16, 12   0.0216  0.2091  0.1523  1.3874
+//   32, 24   0.0218  0.2249  0.1043  1.1504
+// The result does not depend on the values: the sum of a row runs in the one order
+#ifndef EQLB_CSR_GROUP
+#define EQLB_CSR_GROUP 4
+#endif
+#ifndef EQLB_CSR_GROUP_MIN
+#define EQLB_CSR_GROUP_MIN 16
+#endif
+
 // ---- exact solve on the coarsest level of a hierarchy (eqlb_coarse.hip) ----
 #ifndef EQLB_COARSE_MAX_ROWS
 #define EQLB_COARSE_MAX_ROWS 4096 // free rows of level 0 at the most: n^2 * 8 B per layout of the factor, two layouts (268 MB)

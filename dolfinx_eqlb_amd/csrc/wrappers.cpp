@@ -303,6 +303,41 @@ static py::list many_info(const std::vector<double>& v)
   return out;
 }
 
+// (indptr int64 [n + 1], indices int32 [nnz], values [nnz]) of a solver handle as CSR, on host arrays: `pattern`,
+// `exp` and `vals` are the eqlb_*_matrix_* entries of the handle type
+template <class H, class Pattern, class Export, class Values>
+py::tuple matrix_of(H* h, int64_t rows, bool eliminate, Pattern pattern, Export exp, Values vals)
+{
+  int64_t nnz = 0;
+  check(pattern(h, &nnz, nullptr));
+  py::array_t<int64_t> indptr((py::ssize_t)(rows + 1));
+  py::array_t<int32_t> indices((py::ssize_t)nnz);
+  darray values((py::ssize_t)nnz);
+  check(exp(h, indptr.mutable_data(), indices.mutable_data(), EQLB_MEM_HOST, nullptr));
+  check(vals(h, eliminate ? 1 : 0, values.mutable_data(), nnz, EQLB_MEM_HOST, nullptr));
+  return py::make_tuple(indptr, indices, values);
+}
+template <class H, class Pattern, class Values>
+darray matrix_values_of(H* h, bool eliminate, Pattern pattern, Values vals)
+{
+  int64_t nnz = 0;
+  check(pattern(h, &nnz, nullptr));
+  darray values((py::ssize_t)nnz);
+  check(vals(h, eliminate ? 1 : 0, values.mutable_data(), nnz, EQLB_MEM_HOST, nullptr));
+  return values;
+}
+
+// y = A x for a CSR matrix, on the device (eqlb_csr_apply), on host arrays
+darray csr_apply(carray<int64_t> indptr, carray<int32_t> indices, carray<double> values, carray<double> x)
+{
+  if (indptr.size() != x.size() + 1 || indices.size() != values.size())
+    throw std::runtime_error("csr_apply: Input sizes does not match");
+  darray y((py::ssize_t)x.size());
+  check(eqlb_csr_apply((int64_t)x.size(), indptr.data(), indices.data(), values.data(), x.data(), y.mutable_data(),
+                       EQLB_MEM_HOST, nullptr));
+  return y;
+}
+
 // -div(coeff grad u) = f on the conforming P_p space of the mesh, in the numbering of Mesh.lagrange_dofmap: operator,
 // load, residual and Jacobi-preconditioned CG on the device (eqlb_primal_*), on host arrays
 struct PrimalPoisson
@@ -421,6 +456,17 @@ struct PrimalPoisson
     info["facets_skipped"] = (int64_t)v[7];
     return py::make_tuple(x, info);
   }
+  // the operator as CSR: (indptr, indices, values); the pattern is built at the first call and kept in the handle
+  py::tuple matrix(bool eliminate) const
+  {
+    return matrix_of(h, ndofs, eliminate, eqlb_primal_matrix_pattern, eqlb_primal_matrix_export,
+                     eqlb_primal_matrix_values);
+  }
+  darray matrix_values(bool eliminate) const
+  {
+    return matrix_values_of(h, eliminate, eqlb_primal_matrix_pattern, eqlb_primal_matrix_values);
+  }
+  void matrix_release() { eqlb_primal_matrix_release(h); }
   // Y [nrhs][ndofs]: row c is apply(U[c])
   darray apply_many(darray U, bool masked) const
   {
@@ -545,6 +591,17 @@ struct PrimalElasticity
     check(eqlb_elasticity_residual(h, b.data(), u.data(), r.mutable_data(), norms, EQLB_MEM_HOST, nullptr));
     return py::make_tuple(r, norms[0], norms[1]);
   }
+  // the operator as CSR: (indptr, indices, values), 2 ndofs rows; the pattern is built at the first call and kept
+  py::tuple matrix(bool eliminate) const
+  {
+    return matrix_of(h, 2 * ndofs, eliminate, eqlb_elasticity_matrix_pattern, eqlb_elasticity_matrix_export,
+                     eqlb_elasticity_matrix_values);
+  }
+  darray matrix_values(bool eliminate) const
+  {
+    return matrix_values_of(h, eliminate, eqlb_elasticity_matrix_pattern, eqlb_elasticity_matrix_values);
+  }
+  void matrix_release() { eqlb_elasticity_matrix_release(h); }
   // (u, info): the solution from the start u (its fixed rows hold the Dirichlet values) and the info dict
   py::tuple solve(darray b, darray u, double rtol, double atol, int maxit) const
   {
@@ -1577,6 +1634,12 @@ PYBIND11_MODULE(_cpp, m)
            "b [ndofs] from DG_d nodal values rhs_dg [ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalPoisson::apply, py::arg("u"), py::arg("masked") = false, "y = A u; masked: 0 on the fixed rows")
       .def("diagonal", &PrimalPoisson::diagonal)
+      .def("matrix", &PrimalPoisson::matrix, py::arg("eliminate") = false,
+           "(indptr int64 [n + 1], indices int32 [nnz], values [nnz]): the operator as CSR, assembled on the device; "
+           "eliminate: P A P + (I - P) on the mask; scipy.sparse.csr_matrix((values, indices, indptr), shape=(n, n))")
+      .def("matrix_values", &PrimalPoisson::matrix_values, py::arg("eliminate") = false,
+           "values [nnz] from the coefficients, the terms and the mask the handle has now, on the pattern as it stands")
+      .def("matrix_release", &PrimalPoisson::matrix_release, "frees the cached pattern; the next matrix() builds it again")
       .def("residual", &PrimalPoisson::residual, py::arg("b"), py::arg("u"),
            "(r, || r ||_2, nb): r = b - A u with 0 on the fixed rows")
       .def("solve", &PrimalPoisson::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
@@ -1611,6 +1674,12 @@ PYBIND11_MODULE(_cpp, m)
       .def("apply", &PrimalElasticity::apply, py::arg("u"), py::arg("masked") = false,
            "y = A u; masked: 0 on the fixed rows")
       .def("diagonal", &PrimalElasticity::diagonal)
+      .def("matrix", &PrimalElasticity::matrix, py::arg("eliminate") = false,
+           "(indptr int64 [n + 1], indices int32 [nnz], values [nnz]): the operator as CSR, assembled on the device; "
+           "eliminate: P A P + (I - P) on the mask; scipy.sparse.csr_matrix((values, indices, indptr), shape=(n, n))")
+      .def("matrix_values", &PrimalElasticity::matrix_values, py::arg("eliminate") = false,
+           "values [nnz] from the coefficients, the terms and the mask the handle has now, on the pattern as it stands")
+      .def("matrix_release", &PrimalElasticity::matrix_release, "frees the cached pattern; the next matrix() builds it again")
       .def("residual", &PrimalElasticity::residual, py::arg("b"), py::arg("u"),
            "(r, || r ||_2, nb): r = b - A u with 0 on the fixed rows")
       .def("solve", &PrimalElasticity::solve, py::arg("b"), py::arg("u"), py::arg("rtol") = 1e-8, py::arg("atol") = 0.0,
@@ -1618,6 +1687,9 @@ PYBIND11_MODULE(_cpp, m)
       .def_readonly("mesh", &PrimalElasticity::mesh)
       .def_readonly("p", &PrimalElasticity::p)
       .def_readonly("ndofs", &PrimalElasticity::ndofs);
+
+  m.def("csr_apply", &csr_apply, py::arg("indptr"), py::arg("indices"), py::arg("values"), py::arg("x"),
+        "y = A x for a CSR matrix, on the device: the row sum in ascending positions, each product and sum rounded singly");
 
   py::class_<Multilevel, std::shared_ptr<Multilevel>>(
       m, "Multilevel", "Multilevel preconditioner (BPX) over the levels of an adaptive loop: solvers coarsest first (all "

@@ -84,6 +84,29 @@ non-dimensional form and with the pi_1 / cell_pi1 convention of eqlb_primal_stre
   owner sum as above, per (dof, r)
   load      per cell and component |det| (sum_n Load[i][n] rhs_dg[r][c][n]) through the owner sum, + b_extra[2 d + r]
   diagonal  g_XY = M_XY[i][i], D_ab as above, |det| (((D_00 + D_11) + D_rr) + pi_c D_rr) through the owner sum
+
+THE ASSEMBLED MATRIX (PoissonOperator.matrix, ElasticityOperator.matrix, csr_apply; eqlb_primal_matrix_*,
+eqlb_elasticity_matrix_*, eqlb_csr_apply of include/eqlb.h, csrc/eqlb_primal_matrix.hip): the operator as CSR,
+(indptr int64 [n + 1], indices int32 [nnz], values float64 [nnz]) with n = bs ndofs rows in the numbering of the vectors
+(elasticity blocked, 2 dof + r); the device reproduces the three arrays bit for bit.
+  pattern   row bs d + r holds every column bs d' + s (all s) such that d and d' lie in a common cell; columns ascending,
+            each once; an entry whose value happens to be 0.0 stays.  It depends on the mesh and p alone
+  cell entry, Poisson      the rule of `diagonal` with the table entry [i][j] in the place of [i][i]:
+            w ((C00 S0[i][j] + C01 S1[i][j]) + C11 S2[i][j]), then + wm Mass[i][j] with a reaction term; C from K, or from
+            K D K^T with set_diffusion, as above
+  cell entry, elasticity   D_ab of `diagonal` with g_XY = M_XY[i][j] (g_01 = Cross[i][j], g_10 = Cross[j][i]); entry
+            ((i, r), (j, s)) = |det| (((D_00 + D_11) + D_rr) + pi_c D_rr)   for r == s
+                             = |det| (D_sr + pi_c D_rs)                      for r != s
+            the terms of y_loc[c][i][r] that carry u_s[j], in their order, absent terms dropped (not added as zeros); with
+            set_shear times mu_T; with set_reaction + wm Mass[i][j] for r == s only, after the shear product
+  sum       over the cells of the row's DOF that also hold the column's DOF, from the first on, in the order of the slot
+            list of the row's DOF (the owner sum).  The diagonal of the raw matrix therefore has the bits of diagonal()
+  eliminate False: the raw operator, what apply(u, masked=False) applies.  True: P A P + (I - P): an entry with a fixed
+            row or column is 0.0 off the diagonal and 1.0 on it, and stays in the pattern.  The lifting of inhomogeneous
+            Dirichlet values is what residual(b, u_D) returns
+  csr_apply y[row] = the sum over the positions of the row in ascending order, the first product starts it, then
+            s = s + v x, product and sum rounded on their own; an empty row gives 0.0
+every operation rounded on its own, no fused multiply-add.
 """
 
 from fractions import Fraction
@@ -377,6 +400,27 @@ def _sum_products(T, v):
     return val, A
 
 
+def csr_apply(indptr, indices, values, x, return_abs=False):
+    """The statement of eqlb_csr_apply: y [n] with y[row] the sum of values[k] x[indices[k]] over the positions k of the
+    row in ascending order: the first product starts the sum, then s = s + v x, each rounded on its own.  An empty row
+    gives 0.0.  return_abs: also the same sum on the absolute values."""
+    ip = np.asarray(indptr, dtype=np.int64)
+    ix = np.asarray(indices, dtype=np.int64)
+    v = np.asarray(values, dtype=np.float64)
+    xx = np.asarray(x, dtype=np.float64)
+    n = ip.size - 1
+    cnt = np.diff(ip)
+    y, A = np.zeros(n), np.zeros(n)
+    for k in range(int(cnt.max()) if n else 0):
+        sel = np.nonzero(cnt > k)[0]
+        pos = ip[sel] + k
+        t = v[pos] * xx[ix[pos]]
+        ta = np.abs(v[pos]) * np.abs(xx[ix[pos]])
+        y[sel] = t if k == 0 else y[sel] + t
+        A[sel] = ta if k == 0 else A[sel] + ta
+    return (y, A) if return_abs else y
+
+
 class PoissonOperator:
     """The statements on one mesh: PoissonOperator(mesh, p, coeff=None), coeff [ncells] the cell-wise kappa."""
 
@@ -550,6 +594,81 @@ class PoissonOperator:
         val, A = self._add_reaction(val, A, md, md)
         d = self.owner_sum(val)
         return (d, self.owner_sum(A)) if return_abs else d
+
+    # ---- the assembled matrix (the head of this file) ----
+    _bs = 1
+
+    def _pattern(self):
+        """(skey, srow, scol, sptr): the scalar pattern - the sorted distinct pairs (d, d') of DOFs with a common cell as
+        keys d ndofs + d', rows, columns and row offsets [ndofs + 1]."""
+        if getattr(self, "_pat", None) is None:
+            cd, nd, n = self.cell_dofs, self.nd, self.ndofs
+            key = np.unique(np.repeat(cd, nd, axis=1).ravel() * n + np.tile(cd, (1, nd)).ravel())
+            srow = key // n
+            self._pat = (key, srow, key % n, np.searchsorted(srow, np.arange(n + 1)).astype(np.int64))
+        return self._pat
+
+    def _cell_entries(self):
+        """(E, |E|) [ncells, nd, nd, 1, 1]: entry (i, j) of the cell matrices by the rule of `diagonal`."""
+        nc, nn = self.mesh.ncells, self.nd * self.nd
+        t = [np.broadcast_to(self.S[m].ravel()[None, :], (nc, nn)) for m in range(3)]
+        val, A = self._combine(t, self.w, [np.abs(x) for x in t])
+        if self.cell_D is None:
+            # an entry is compared on its own: C01 = K00 K10 + K01 K11 can cancel, which |C01| (Cabs) does not show
+            Ka = [[np.abs(v)[:, None] for v in row] for row in self.K]
+            a0, a1, a2 = (Ka[0][0] * Ka[0][0] + Ka[0][1] * Ka[0][1], Ka[0][0] * Ka[1][0] + Ka[0][1] * Ka[1][1],
+                          Ka[1][0] * Ka[1][0] + Ka[1][1] * Ka[1][1])
+            A = np.abs(self.w)[:, None] * ((a0 * np.abs(t[0]) + a1 * np.abs(t[1])) + a2 * np.abs(t[2]))
+        mm = np.broadcast_to(self.Mass.ravel()[None, :], (nc, nn))
+        val, A = self._add_reaction(val, A, mm, np.abs(mm))
+        shape = (nc, self.nd, self.nd, 1, 1)
+        return val.reshape(shape), A.reshape(shape)
+
+    def matrix(self, eliminate=False, return_abs=False):
+        """(indptr int64 [n + 1], indices int32 [nnz], values [nnz]), n = bs ndofs: the operator as CSR by the rule at the
+        head of this file.  eliminate: P A P + (I - P) on the mask of set_dirichlet.  return_abs: a fourth array, the
+        same sums on the absolute values of the terms."""
+        bs, nd, n = self._bs, self.nd, self.ndofs
+        skey, srow, scol, sptr = self._pattern()
+        E, EA = self._cell_entries()
+        V, VA = np.zeros((skey.size, bs, bs)), np.zeros((skey.size, bs, bs))
+        seen = np.zeros(skey.size, dtype=bool)
+
+        def add(d, c, i):
+            pos = np.searchsorted(skey, d[:, None] * n + self.cell_dofs[c])                # [m, nd]
+            old = seen[pos][:, :, None, None]
+            V[pos] = np.where(old, V[pos] + E[c, i], E[c, i])
+            VA[pos] = np.where(old, VA[pos] + EA[c, i], EA[c, i])
+            seen[pos] = True
+
+        off = self.slot_off
+        cnt = np.diff(off)
+        for k in range(int(cnt.max()) if cnt.size else 0):
+            sel = np.nonzero(cnt > k)[0]
+            flat = self.slots[off[sel] + k]
+            add(sel, flat // nd, flat % nd)
+        ni = nd - 3 * self.p
+        if ni:
+            q = np.arange(self.mesh.ncells * ni)
+            add(self.nshared + q, q // ni, 3 * self.p + q % ni)
+        # the blocked layout: row bs d + r holds the columns bs d' + s, s fastest
+        length = np.diff(sptr)
+        rows = np.arange(bs * n)
+        indptr = np.concatenate([bs * bs * sptr[rows // bs] + (rows % bs) * bs * length[rows // bs], [bs * bs * skey.size]])
+        k = np.arange(skey.size) - sptr[srow]
+        r, s = np.arange(bs)[None, :, None], np.arange(bs)[None, None, :]
+        pos = (bs * bs * sptr[srow] + bs * k)[:, None, None] + r * bs * length[srow][:, None, None] + s
+        indices = np.zeros(bs * bs * skey.size, dtype=np.int32)
+        values, vabs = np.zeros(indices.size), np.zeros(indices.size)
+        indices[pos] = bs * scol[:, None, None] + s
+        values[pos], vabs[pos] = V, VA
+        if eliminate:
+            row_of = np.repeat(rows, np.diff(indptr))
+            fx = self.fixed[row_of] | self.fixed[indices]
+            unit = np.where(row_of == indices, 1.0, 0.0)
+            values, vabs = np.where(fx, unit, values), np.where(fx, unit, vabs)
+        out = (indptr.astype(np.int64), indices, values)
+        return out + (vabs,) if return_abs else out
 
     def residual(self, b, u, fixed=None, return_abs=False):
         """r = b - A u, 0 on the rows where `fixed` (default: the mask of set_dirichlet) is set."""
@@ -791,6 +910,33 @@ class ElasticityOperator(PoissonOperator):
         val, A = zip(*[self._add_reaction(val[r], A[r], md, md) for r in range(2)])
         d = self.owner_sum(np.stack(val, axis=2))
         return (d, self.owner_sum(np.stack(A, axis=2))) if return_abs else d
+
+    _bs = 2
+
+    def _cell_entries(self):
+        """(E, |E|) [ncells, nd, nd, 2, 2]: entry ((i, r), (j, s)) of the cell matrices (the head of this file)."""
+        nc, nn = self.mesh.ncells, self.nd * self.nd
+        g = [np.broadcast_to(self.M[m].ravel()[None, :], (nc, nn)) for m in range(4)]      # M_10[i][j] = Cross[j][i]
+        ga = [np.abs(x) for x in g]
+        D = [[self._D(g, a, b, ga) for b in range(2)] for a in range(2)]
+        w, pi = self.adet[:, None], self.pi[:, None]
+        wa, pa = np.abs(w), np.abs(pi)
+        mm = np.broadcast_to(self.Mass.ravel()[None, :], (nc, nn))
+        E, EA = np.zeros((nc, nn, 2, 2)), np.zeros((nc, nn, 2, 2))
+        for r in range(2):
+            for s in range(2):
+                if r == s:
+                    val = w * (((D[0][0][0] + D[1][1][0]) + D[r][r][0]) + pi * D[r][r][0])
+                    A = wa * (((D[0][0][1] + D[1][1][1]) + D[r][r][1]) + pa * D[r][r][1])
+                else:
+                    val = w * (D[s][r][0] + pi * D[r][s][0])
+                    A = wa * (D[s][r][1] + pa * D[r][s][1])
+                val, A = self._scale_shear(val, A)
+                if r == s:
+                    val, A = self._add_reaction(val, A, mm, np.abs(mm))
+                E[:, :, r, s], EA[:, :, r, s] = val, A
+        shape = (nc, self.nd, self.nd, 2, 2)
+        return E.reshape(shape), EA.reshape(shape)
 
     def pcg(self, b, u, rtol=1e-8, atol=0.0, maxit=1000):
         """The CG of PoissonOperator.pcg on the blocked vectors (eqlb_elasticity_solve).  Each component needs a
