@@ -1,20 +1,15 @@
 // Weak symmetry of equilibrated stresses on gfx950: impose_weak_symmetry
 // (cpp/dolfinx_eqlb/se/solve_patch_weaksym.hpp:59-233) with assemble_stressminimiser
 // (se/assembly.hpp:292-472), the kernel of se/stressmin_kernel.hpp:76-248 and the Schur solve
-// PatchData::solve_constrained_minimisation (se/PatchData.hpp:598-663).
+// PatchData::solve_constrained_minimisation (se/PatchData.hpp:598-663).  eqlb_se_weaksym_common.h states the
+// contract and holds what this kernel shares with k_se_weaksym_banded and k_se_weaksym_large.
 //
-// Runs after the row-wise flux kernels: the slot buffer then holds exactly the patch-local stress
-// rows sigma_a (one slot row per (cell, vertex)), which is what the reference feeds into the
-// constrained minimisation (:134-142).  Per patch (P lanes, one per cell, as in k_se_patch):
-//   saddle system  [A 0 B0; 0 A B1; B0^T B1^T 0(+mean-value row)] [u0; u1; gamma] = [0; 0; Lc]
-//   B0(i,j) = int (Phi_i)_y psi_j,  B1(i,j) = -int (Phi_i)_x psi_j,  Lc(j) = -int psi_j (s01 - s10)
-// over the patch-wise H(div=0) functions Phi_i and the patch P1 functions psi_j.  Quadrature-free:
-// Phi/psi products are contractions with the constant tensors V, VQ (tools/gen_tables.py).
+// Per patch P lanes, one per cell, as in k_se_patch, with the dense numbering of the unknowns (WsNumbering::gi).
 // Solve: Cholesky A = L L^T in LDS, Y_k = L^-1 B_k (one column per lane, no synchronisation),
 // Schur complement C = -sum_k Y_k^T Y_k (+ multiplier row), dense LU with partial pivoting of the
-// (npnt+1)^2 system, u_k = -L^-T (Y_k gamma); the corrections are added to the slot rows in place.
+// (npnt+1)^2 system, u_k = -L_k^-T (Y_k gamma); the corrections are added to the slot rows in place.
 // With flux BCs on a stress row the masked A (and B rows) of that row are used (:611-656).
-#include "eqlb_device_common.h"
+#include "eqlb_se_weaksym_common.h"
 #include "eqlb_tables_gen.h"
 
 namespace eqlb
@@ -54,7 +49,8 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
 {
   using W = WsSizes<K, P>;
   using Z = typename W::Z;
-  constexpr int KB = W::KB, NADD = W::NADD, NH = W::NH, NRT = W::NRT, NTE = W::NTE;
+  using N = WsNumbering<K>;
+  constexpr int KB = W::KB, NH = W::NH;
   constexpr int NPMAX = W::NPMAX, DCMAX = W::DCMAX, LDY = 2 * W::NPMAX;
 
   extern __shared__ double lds[];
@@ -84,42 +80,13 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
   const bool grouped = (flag0 & PFLAG_WS_GROUP) != 0;
   const int n = pvalid ? (int)a.pn[patch] : 0;
   const bool active = pvalid && sub < n;
-  const int32_t cell = active ? a.slot_cell[slot] : 0;
-  const uint32_t info = active ? a.slot_info[slot] : 0u;
-  const int fm = (info >> INFO_FM_SHIFT) & 3, fp = (info >> INFO_FP_SHIFT) & 3;
-  const int ln = (info >> INFO_LN_SHIFT) & 3;
-  const bool rev_m = (info & INFO_REV_M) != 0;
-  const int ci = active ? combo_index(fm, fp, rev_m) : 0;
-
-  double J[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
-  if (active)
-  {
-    const double2* Jp = reinterpret_cast<const double2*>(a.cellJ + 4 * (int64_t)cell);
-    const double2 j0 = Jp[0], j1 = Jp[1];
-    J[0][0] = j0.x;
-    J[0][1] = j0.y;
-    J[1][0] = j1.x;
-    J[1][1] = j1.y;
-  }
-  const double detJ = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-  const double sgn = (detJ > 0.0) ? 1.0 : -1.0;
-  const double pf_m = (fm == 1) ? sgn : -sgn, pf_p = (fp == 1) ? sgn : -sgn;
-
   const uint8_t flag1 = pvalid ? a.pflag[a.npatch_total + patch] : (uint8_t)PFLAG_INTERIOR;
-  const bool interior = !pvalid || (flag0 & PFLAG_INTERIOR) != 0;
-  const int nf = interior ? n : n + 1;
-  const int nn = (n > 0) ? n : 1;
-  const int fi_p = interior ? ((sub + 1 < nn) ? sub + 1 : 0) : sub + 1;
-  const int dim = pvalid ? 1 + KB * nf + NADD * n : 0;
-  const int npnt = nf + 1;
-  // flux BCs of the two rows (bits as in k_se_patch); PatchData::reinitialisation :175-206
-  const bool bc0[2] = {(flag0 & PFLAG_BC0) != 0, (flag1 & PFLAG_BC0) != 0};
-  const bool bcn[2] = {(flag0 & PFLAG_BCN) != 0, (flag1 & PFLAG_BCN) != 0};
-  const bool requires_bcs = bc0[0] || bcn[0] || bc0[1] || bcn[1];
-  // mean-value multiplier unless some row has a primal-Dirichlet end (type essnt_primal or mixed)
-  const bool row_dual[2] = {!interior && bc0[0] && bcn[0], !interior && bc0[1] && bcn[1]};
-  const bool meanvalue = interior || (row_dual[0] && row_dual[1]);
-  const int dim_c = meanvalue ? npnt + 1 : npnt;
+  // (a patch that is left out counts as an empty interior patch)
+  const WsPatch pt = ws_patch(pvalid ? flag0 : (uint8_t)(flag0 | PFLAG_INTERIOR), flag1, n);
+  const int npnt = pt.npnt, dim_c = pt.dim_c;
+  const bool requires_bcs = pt.requires_bcs, meanvalue = pt.meanvalue;
+  const int dim = pvalid ? N::dim(pt) : 0;
+  const WsCell<K> cell(a, sTE, sVQ, slot, active, pt, sub);
 
   double* Ag = sG + (tid / P) * W::GROUP; // A of row 0 (and of both rows without flux BCs)
   double* Yg = Ag + W::OFF_Y;
@@ -130,102 +97,35 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
 
   // ---- element quantities ----
   double Te[NH][NH];
-  {
-    const double ia = active ? 1.0 / fabs(detJ) : 0.0;
-    const double g0 = (J[0][0] * J[0][0] + J[1][0] * J[1][0]) * ia,
-                 g1 = (J[0][0] * J[0][1] + J[1][0] * J[1][1]) * ia,
-                 g2 = (J[0][1] * J[0][1] + J[1][1] * J[1][1]) * ia;
-    const double* te = sTE + ci * 3 * Z::NTES;
 #pragma unroll
-    for (int h = 0; h < NH; ++h)
+  for (int h = 0; h < NH; ++h)
 #pragma unroll
-      for (int g = 0; g <= h; ++g)
-      {
-        const int e = h * (h + 1) / 2 + g;
-        const double v = g0 * te[e] + g1 * te[Z::NTES + e] + g2 * te[2 * Z::NTES + e];
-        Te[h][g] = v;
-        Te[g][h] = v;
-      }
-  }
+    for (int g = 0; g <= h; ++g)
+    {
+      const double v = cell.Te(h, g);
+      Te[h][g] = v;
+      Te[g][h] = v;
+    }
   // Be[k][h][j]: k = 0: int (Phi_h)_y psi_j ; k = 1: -int (Phi_h)_x psi_j
   double Be[2][NH][3];
-  {
-    const double* vq = sVQ + ci * 2 * NH * 3;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
 #pragma unroll
     for (int h = 0; h < NH; ++h)
 #pragma unroll
       for (int j = 0; j < 3; ++j)
-      {
-        const double v0 = vq[h * 3 + j], v1 = vq[(NH + h) * 3 + j]; // X = 0, 1
-        Be[0][h][j] = active ? (J[1][0] * v0 + J[1][1] * v1) : 0.0;
-        Be[1][h][j] = active ? -(J[0][0] * v0 + J[0][1] * v1) : 0.0;
-      }
-  }
+        Be[k][h][j] = active ? cell.Be(k, h, j) : 0.0;
   // patch-local stress rows from the slots; Lc_e[j] = -int psi_j (s01 - s10), Ce = |detJ|/6
-  double* srow[2] = {nullptr, nullptr};
   double Lce[3] = {0.0, 0.0, 0.0};
   if (active)
-  {
-    srow[0] = a.out + (((int64_t)0 * a.ncells + cell) * 3 + ln) * NRT;
-    srow[1] = a.out + (((int64_t)1 * a.ncells + cell) * 3 + ln) * NRT;
-    // grouped patches (modified_patch, se/solve_patch_weaksym.hpp:100-131): the stress accumulated by
-    // the group so far = own rows + the rows of the group's two-cell patches on this cell
-    const uint32_t grows = grouped ? ((info >> INFO_GROUPROW_SHIFT) & 7u) : 0u;
-#pragma unroll
-    for (int i = 0; i < NRT; ++i)
-    {
-      double c0 = srow[0][i], c1 = srow[1][i];
-      if (grows)
-      {
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-          if (grows & (1u << v))
-          {
-            c0 += a.out[(((int64_t)0 * a.ncells + cell) * 3 + v) * NRT + i];
-            c1 += a.out[(((int64_t)1 * a.ncells + cell) * 3 + v) * NRT + i];
-          }
-      }
-      const double w0 = c0 * J[1][0] - c1 * J[0][0], w1 = c0 * J[1][1] - c1 * J[0][1];
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        Lce[j] -= sgn * (w0 * sV[(j * NRT + i) * 2] + w1 * sV[(j * NRT + i) * 2 + 1]);
-    }
-  }
-  const double Ce = active ? fabs(detJ) / 6.0 : 0.0;
+    cell.template load<true>(a.out, a.ncells, grouped, sV, Lce);
+  const double Ce = active ? cell.Ce() : 0.0;
 
   // ---- numbering ----
   int gi[NH];
-  gi[0] = 0;
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-  {
-    gi[1 + j] = 1 + sub * KB + j;
-    gi[1 + KB + j] = 1 + fi_p * KB + j;
-  }
-#pragma unroll
-  for (int q = 0; q < NADD; ++q)
-    gi[1 + 2 * KB + q] = 1 + nf * KB + sub * NADD + q;
-  // multiplier DOF of the cell's local vertex j (se/Patch.hpp:621-708)
-  int pj[3];
-  {
-    const int v_ea = 3 - fp - ln, v_eam1 = 3 - fm - ln;
-    const int p_ea = interior ? sub + 1 : ((sub + 1 == n) ? nf : sub + 1);
-    const int p_eam1 = interior ? ((sub == 0) ? n : sub) : ((sub == 0) ? nf - 1 : sub);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      pj[j] = (j == ln) ? 0 : ((j == v_ea) ? p_ea : ((j == v_eam1) ? p_eam1 : 0));
-  }
-  // fixed (flux-BC) unknowns per row k (se/assembly.hpp:46-98): local unknown h of this lane
-  auto fixed = [&](int k, int h) {
-    const bool dfx = bc0[k] || bcn[k];
-    if (h == 0)
-      return dfx;
-    if (h <= KB)
-      return bc0[k] && sub == 0;
-    if (h <= 2 * KB)
-      return bcn[k] && sub == n - 1;
-    return false;
-  };
+  N::gi(pt, sub, gi);
+  const int pj[3] = {cell.pj(0), cell.pj(1), cell.pj(2)};
+  auto fixed = [&](int k, int h) { return N::fixed(pt, k, h, sub); };
 
   // ---- zero the tile ----
   for (int e = sub; e < W::GROUP; e += P)
@@ -245,11 +145,11 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
 #pragma unroll
       for (int h = 0; h < NH; ++h)
       {
-        if (fixed(k, h) && requires_bcs)
+        if (fixed(k, h))
           continue;
 #pragma unroll
         for (int g = 0; g < NH; ++g)
-          if (gi[h] >= gi[g] && !(fixed(k, g) && requires_bcs))
+          if (gi[h] >= gi[g] && !fixed(k, g))
             atomicAdd(&Ak[tri(gi[h], gi[g])], Te[h][g]);
       }
     }
@@ -258,7 +158,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
 #pragma unroll
       for (int h = 0; h < NH; ++h)
       {
-        if (fixed(k, h) && requires_bcs)
+        if (fixed(k, h))
           continue; // rows of fixed unknowns are dropped (se/assembly.hpp:430-436)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
@@ -282,12 +182,12 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
     for (int k = 0; k < 2; ++k)
     {
       double* Ak = Ag + k * W::OFF_A1;
-      if (bc0[k] || bcn[k])
+      if (pt.bc0(k) || pt.bcn(k))
         Ak[0] = 1.0;
-      if (bc0[k])
+      if (pt.bc0(k))
         for (int j = 0; j < KB; ++j)
           Ak[tri(1 + j, 1 + j)] = 1.0;
-      if (bcn[k])
+      if (pt.bcn(k))
         for (int j = 0; j < KB; ++j)
           Ak[tri(1 + n * KB + j, 1 + n * KB + j)] = 1.0;
     }
@@ -593,19 +493,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
     }
     // back substitution over the pivot columns, right to left; gamma goes to Wg first (Rg holds the rows)
     double* gm = Wg; // free until the u_k step
-    for (int c = dim_c - 1; c >= 0; --c)
-    {
-      if (pcol[c] < 0)
-      {
-        gm[c] = 0.0;
-        continue;
-      }
-      const int r = pcol[c];
-      double t = Rg[r];
-      for (int j = c + 1; j < dim_c; ++j)
-        t -= Cg[r * DCMAX + j] * gm[j];
-      gm[c] = t / Cg[r * DCMAX + c];
-    }
+    ws_back_substitute(Cg, DCMAX, Rg, pcol, dim_c, gm, (int*)nullptr);
     for (int c = 0; c < dim_c; ++c)
       Rg[c] = gm[c];
   }
@@ -664,7 +552,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
   }
   wave_sync();
 
-  // ---- back-map and add to the slot rows (se/solve_patch_weaksym.hpp:189-232) ----
+  // ---- back-map and add to the slot rows ----
   if (active)
   {
 #pragma unroll
@@ -675,21 +563,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym(const SeArgs a)
 #pragma unroll
       for (int h = 0; h < NH; ++h)
         ul[h] = w[gi[h]];
-      double* o = srow[k];
-#pragma unroll
-      for (int j = 0; j < K; ++j)
-      {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-          s -= (rev_m ? bcoef(j, c) : ((j == c) ? 1.0 : 0.0)) * ul[c];
-        const double yp = (j == 0) ? ul[0] : ul[KB + j];
-        o[fm * K + j] += pf_m * s;
-        o[fp * K + j] += pf_p * yp;
-      }
-#pragma unroll
-      for (int q = 0; q < NADD; ++q)
-        o[3 * K + Z::NDIV + q] += sgn * ul[1 + 2 * KB + q];
+      cell.add_correction(ul, cell.row(a.out, a.ncells, k));
     }
   }
   if (status_local)
@@ -1170,13 +1044,8 @@ static int launch_ws_t(const SeArgs& a, hipStream_t stream)
   if (lds_bytes > 160 * 1024)
     return EQLB_ERR_UNSUPPORTED;
   auto kern = k_se_weaksym<K, P>;
-  if (lds_bytes > 64 * 1024)
-  {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
-        != hipSuccess)
-      return EQLB_ERR_DEVICE;
-  }
+  if (!ws_allow_lds(kern, lds_bytes))
+    return EQLB_ERR_DEVICE;
   const int64_t grid = (a.npatch * P + W::BLOCK - 1) / W::BLOCK;
   if (grid == 0)
     return 0;

@@ -1,15 +1,9 @@
 // Weak symmetry of equilibrated stresses for the large bins: RT_4 with patches of 9 ... 64 facets and RT_3
-// with 33 ... 64 facets.  Same contract and same solution as k_se_weaksym (eqlb_se_weaksym.hip) - input
-// SeArgs, corrections added to the slot rows of RHS 0 and 1 in place, grouped patches, one pass per
-// level of overlapping groups, the same rank-revealing LU of the Schur system - but the LDS grows
+// with 33 ... 64 facets.  The contract is that of eqlb_se_weaksym_common.h; against k_se_weaksym the LDS grows
 // linearly with the patch instead of quadratically, so these bins fit a workgroup.
 //
 // One patch per wave (64 lanes; lane i <-> cell T_{i+1}).  The unknowns of the patch are ordered as a
-// banded chain plus a border:
-//   chain   [a_0 | x_1 | a_1 | x_2 | ... ]   a_s: the NADD cell-bubble unknowns of cell s, x_f: the KB
-//                                           unknowns of facet f >= 1 (boundary patches end with x_n)
-//   border  [d | x_0]                        the patch-node unknown and facet 0 (closes the ring of
-//                                           interior patches)
+// banded chain plus a border (WsChain, eqlb_se_weaksym_numbering.h: chain [a_0 | x_1 | a_1 | ...], border [d | x_0]).
 // A cell couples [x_s | a_s | x_{s+1}] and the border only, so the chain has half bandwidth
 // BW = 2 KB + NADD - 1 and the Cholesky factor L = [Lc 0; Lb Lbb] keeps that profile: Lc is stored as
 // a band, Lb / Lbb as NBD = 1 + KB dense rows.  B_k (H(div=0) functions against the patch P1
@@ -23,21 +17,20 @@
 // kernel, u_k = -A_k^-1 (B_k gamma) is one forward and one back substitution per stress row.
 // With flux BCs the two rows have masked matrices: their factors are computed one after the other in the
 // same buffer (A_1 for Y_1 and u_1, A_0 again for u_0).
-#include "eqlb_device_common.h"
+#include "eqlb_se_weaksym_common.h"
 #include "eqlb_tables_gen.h"
 
 namespace eqlb
 {
 
 template <int K, int P>
-struct WsBand
+struct WsBand : WsChain<K>
 {
   using Z = Sizes<K, K - 1, P>;
-  static constexpr int KB = Z::KB, NADD = Z::NADD, NH = Z::NH, NRT = Z::NRT;
+  using C = WsChain<K>;
+  static constexpr int KB = C::KB, NADD = C::NADD, NH = C::NH, NBD = C::NBD, BW = C::BW, LDB = C::LDB;
   static constexpr int DIMMAX = Z::DIMMAX;     // H(div=0) unknowns of a patch
-  static constexpr int NBD = 1 + KB;           // border: d, x_0
   static constexpr int NCHMAX = DIMMAX - NBD;  // chain
-  static constexpr int BW = 2 * KB + NADD - 1; // half bandwidth of the chain
   static constexpr int NPMAX = P + 2;          // patch nodes (multiplier DOFs)
   static constexpr int DCMAX = NPMAX + 1;      // + mean-value multiplier
   static constexpr int LDY = 2 * NPMAX;        // row of the Y buffer: Y_0 | Y_1
@@ -62,9 +55,9 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
 {
   using W = WsBand<K, P>;
   using Z = typename W::Z;
-  constexpr int KB = W::KB, NADD = W::NADD, NH = W::NH, NRT = W::NRT, NBD = W::NBD, BW = W::BW;
+  constexpr int KB = W::KB, NH = W::NH, NBD = W::NBD, BW = W::BW, LDB = W::LDB;
   constexpr int DIMMAX = W::DIMMAX, NPMAX = W::NPMAX, DCMAX = W::DCMAX, LDY = W::LDY, RCH = W::RCH;
-  constexpr int NCT = W::NCT, LDB = BW + 1;
+  constexpr int NCT = W::NCT;
 
   const int64_t patch_local = blockIdx.x;
   const int64_t patch = a.patch_offset + patch_local;
@@ -90,136 +83,26 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
   const int sub = threadIdx.x;
   const int64_t slot = a.slot_offset + patch_local * P + sub;
   const bool grouped = (flag0 & PFLAG_WS_GROUP) != 0;
-  const int n = (int)a.pn[patch];
+  const WsPatch pt = ws_patch(flag0, a.pflag[a.npatch_total + patch], (int)a.pn[patch]);
+  const int n = pt.n, npnt = pt.npnt, dim_c = pt.dim_c;
+  const bool requires_bcs = pt.requires_bcs, meanvalue = pt.meanvalue;
+  const int dim = W::dim(pt), nch = W::nch(pt);
   const bool active = sub < n;
-  const int32_t cell = active ? a.slot_cell[slot] : 0;
-  const uint32_t info = active ? a.slot_info[slot] : 0u;
-  const int fm = (info >> INFO_FM_SHIFT) & 3, fp = (info >> INFO_FP_SHIFT) & 3;
-  const int ln = (info >> INFO_LN_SHIFT) & 3;
-  const bool rev_m = (info & INFO_REV_M) != 0;
-  const int ci = active ? combo_index(fm, fp, rev_m) : 0;
-
-  double J[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
-  if (active)
-  {
-    const double2* Jp = reinterpret_cast<const double2*>(a.cellJ + 4 * (int64_t)cell);
-    const double2 j0 = Jp[0], j1 = Jp[1];
-    J[0][0] = j0.x;
-    J[0][1] = j0.y;
-    J[1][0] = j1.x;
-    J[1][1] = j1.y;
-  }
-  const double detJ = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-  const double sgn = (detJ > 0.0) ? 1.0 : -1.0;
-  const double pf_m = (fm == 1) ? sgn : -sgn, pf_p = (fp == 1) ? sgn : -sgn;
-
-  const uint8_t flag1 = a.pflag[a.npatch_total + patch];
-  const bool interior = (flag0 & PFLAG_INTERIOR) != 0;
-  const int nf = interior ? n : n + 1;
-  const int fi_p = interior ? ((sub + 1 < n) ? sub + 1 : 0) : sub + 1;
-  const int dim = 1 + KB * nf + NADD * n;
-  const int nch = dim - NBD;
-  const int npnt = nf + 1;
-  // flux BCs of the two rows (bits as in k_se_patch); PatchData::reinitialisation :175-206
-  const bool bc0[2] = {(flag0 & PFLAG_BC0) != 0, (flag1 & PFLAG_BC0) != 0};
-  const bool bcn[2] = {(flag0 & PFLAG_BCN) != 0, (flag1 & PFLAG_BCN) != 0};
-  const bool requires_bcs = bc0[0] || bcn[0] || bc0[1] || bcn[1];
-  // mean-value multiplier unless some row has a primal-Dirichlet end (type essnt_primal or mixed)
-  const bool row_dual[2] = {!interior && bc0[0] && bcn[0], !interior && bc0[1] && bcn[1]};
-  const bool meanvalue = interior || (row_dual[0] && row_dual[1]);
-  const int dim_c = meanvalue ? npnt + 1 : npnt;
-
-  // ---- element quantities (the tables are read from global memory: they would cost the LDS of a patch) ----
-  const double ia = active ? 1.0 / fabs(detJ) : 0.0;
-  const double g0 = (J[0][0] * J[0][0] + J[1][0] * J[1][0]) * ia,
-               g1 = (J[0][0] * J[0][1] + J[1][0] * J[1][1]) * ia,
-               g2 = (J[0][1] * J[0][1] + J[1][1] * J[1][1]) * ia;
-  const double* te = a.tables + Z::OFF_TE + ci * 3 * Z::NTES;
-  auto Te = [&](int h, int g) {
-    const int e = (h >= g) ? h * (h + 1) / 2 + g : g * (g + 1) / 2 + h;
-    return g0 * te[e] + g1 * te[Z::NTES + e] + g2 * te[2 * Z::NTES + e];
-  };
-  // Be(k, h, j): k = 0: int (Phi_h)_y psi_j ; k = 1: -int (Phi_h)_x psi_j
-  const double* vq = a.tables + Z::OFF_VQ + ci * 2 * NH * 3;
-  auto Be = [&](int k, int h, int j) {
-    const double v0 = vq[h * 3 + j], v1 = vq[(NH + h) * 3 + j];
-    return (k == 0) ? (J[1][0] * v0 + J[1][1] * v1) : -(J[0][0] * v0 + J[0][1] * v1);
-  };
+  // the lane's cell; the tables are read from global memory: they would cost the LDS of a patch
+  const WsCell<K> cell(a, a.tables + Z::OFF_TE, a.tables + Z::OFF_VQ, slot, active, pt, sub);
   // patch-local stress rows from the slots; Lc_e[j] = -int psi_j (s01 - s10), Ce = |detJ|/6
-  double* srow[2] = {nullptr, nullptr};
   double Lce[3] = {0.0, 0.0, 0.0};
   if (active)
-  {
-    const double* sV = a.tables + Z::OFF_V;
-    srow[0] = a.out + (((int64_t)0 * a.ncells + cell) * 3 + ln) * NRT;
-    srow[1] = a.out + (((int64_t)1 * a.ncells + cell) * 3 + ln) * NRT;
-    // grouped patches (modified_patch, se/solve_patch_weaksym.hpp:100-131): own rows + the rows of the
-    // group's two-cell patches on this cell
-    const uint32_t grows = grouped ? ((info >> INFO_GROUPROW_SHIFT) & 7u) : 0u;
-    for (int i = 0; i < NRT; ++i)
-    {
-      double c0 = srow[0][i], c1 = srow[1][i];
-      if (grows)
-      {
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-          if (grows & (1u << v))
-          {
-            c0 += a.out[(((int64_t)0 * a.ncells + cell) * 3 + v) * NRT + i];
-            c1 += a.out[(((int64_t)1 * a.ncells + cell) * 3 + v) * NRT + i];
-          }
-      }
-      const double w0 = c0 * J[1][0] - c1 * J[0][0], w1 = c0 * J[1][1] - c1 * J[0][1];
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        Lce[j] -= sgn * (w0 * sV[(j * NRT + i) * 2] + w1 * sV[(j * NRT + i) * 2 + 1]);
-    }
-  }
-  const double Ce = active ? fabs(detJ) / 6.0 : 0.0;
+    cell.template load<false>(a.out, a.ncells, grouped, a.tables + Z::OFF_V, Lce);
+  const double Ce = active ? cell.Ce() : 0.0;
 
   // ---- numbering: position of the lane's local unknowns [d | um | up | ua] in chain + border order ----
-  auto pos_facet = [&](int f, int m) { return (f == 0) ? nch + 1 + m : (f - 1) * (KB + NADD) + NADD + m; };
+  auto pos_facet = [&](int f, int m) { return W::pos_facet(nch, f, m); };
   int pos[NH];
-  pos[0] = nch;
-#pragma unroll
-  for (int j = 0; j < KB; ++j)
-  {
-    pos[1 + j] = pos_facet(sub, j);
-    pos[1 + KB + j] = pos_facet(fi_p, j);
-  }
-#pragma unroll
-  for (int q = 0; q < NADD; ++q)
-    pos[1 + 2 * KB + q] = sub * (KB + NADD) + q;
-  // multiplier DOF of the cell's local vertex j (se/Patch.hpp:621-708), as in k_se_weaksym
-  const int v_ea = 3 - fp - ln, v_eam1 = 3 - fm - ln;
-  int pj[3];
-  {
-    const int p_ea = interior ? sub + 1 : ((sub + 1 == n) ? nf : sub + 1);
-    const int p_eam1 = interior ? ((sub == 0) ? n : sub) : ((sub == 0) ? nf - 1 : sub);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      pj[j] = (j == ln) ? 0 : ((j == v_ea) ? p_ea : ((j == v_eam1) ? p_eam1 : 0));
-  }
-  // slot of vertex j in a compressed row of B: 0 the patch node, 1 the ring point of the row's facet
-  // (of facet s for the bubbles of cell s), 2 / 3 the other ring point of the cell before / after it
-  auto bslot = [&](int h, int j) {
-    if (j == ln)
-      return 0;
-    const bool uprow = h > KB && h <= 2 * KB;
-    return uprow ? ((j == v_ea) ? 1 : 2) : ((j == v_eam1) ? 1 : 3);
-  };
-  // fixed (flux-BC) unknowns per row k (se/assembly.hpp:46-98): local unknown h of this lane
-  auto fixed = [&](int k, int h) {
-    if (!requires_bcs)
-      return false;
-    if (h == 0)
-      return bc0[k] || bcn[k];
-    if (h <= KB)
-      return bc0[k] && sub == 0;
-    if (h <= 2 * KB)
-      return bcn[k] && sub == n - 1;
-    return false;
-  };
+  W::pos(pt, sub, pos);
+  const int pj[3] = {cell.pj(0), cell.pj(1), cell.pj(2)};
+  auto bslot = [&](int h, int j) { return W::bslot(cell.fm, cell.fp, cell.ln, h, j); };
+  auto fixed = [&](int k, int h) { return W::fixed(pt, k, h, sub); };
   // entry (p, q), p >= q, of the factor buffer
   auto Lref = [&](int p, int q) -> double& {
     return (p < nch) ? band[p * LDB + (p - q)] : bord[(p - nch) * DIMMAX + q];
@@ -245,7 +128,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
         {
-          const double v = Be(k, h, j);
+          const double v = cell.Be(k, h, j);
           if (h == 0)
             atomicAdd(&Bd[k * NPMAX + pj[j]], v);
           else
@@ -290,19 +173,19 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
 #pragma unroll
         for (int g = 0; g < NH; ++g)
           if (pos[h] >= pos[g] && !fixed(k, g))
-            atomicAdd(&Lref(pos[h], pos[g]), Te(h, g));
+            atomicAdd(&Lref(pos[h], pos[g]), cell.Te(h, g));
       }
     }
     wave_sync();
     if (requires_bcs && sub == 0) // identity rows of the fixed unknowns
     {
-      if (bc0[k] || bcn[k])
+      if (pt.bc0(k) || pt.bcn(k))
         bord[nch] = 1.0;
       for (int m = 0; m < KB; ++m)
       {
-        if (bc0[k])
+        if (pt.bc0(k))
           Lref(nch + 1 + m, nch + 1 + m) = 1.0;
-        if (bcn[k])
+        if (pt.bcn(k))
           Lref(pos_facet(n, m), pos_facet(n, m)) = 1.0;
       }
     }
@@ -633,25 +516,8 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
       ++nr;
       wave_sync();
     }
-    // back substitution over the pivot columns, right to left
     if (sub == 0)
-    {
-      for (int c = dim_c - 1; c >= 0; --c)
-      {
-        if (pcol[c] < 0)
-        {
-          Gg[c] = 0.0;
-          continue;
-        }
-        const int r = pcol[c];
-        double t = Rg[r];
-        for (int j = c + 1; j < dim_c; ++j)
-          t -= Cg[r * DCMAX + j] * Gg[j];
-        Gg[c] = t / Cg[r * DCMAX + c];
-        if (!isfinite(Gg[c]))
-          status_local = 1;
-      }
-    }
+      ws_back_substitute(Cg, DCMAX, Rg, pcol, dim_c, Gg, &status_local);
     wave_sync();
   }
 
@@ -664,7 +530,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
     solve_u(0);
   }
 
-  // ---- back-map and add to the slot rows (se/solve_patch_weaksym.hpp:189-232) ----
+  // ---- back-map and add to the slot rows ----
   if (active)
   {
 #pragma unroll
@@ -675,21 +541,7 @@ __global__ void __launch_bounds__(64) k_se_weaksym_banded(const SeArgs a)
 #pragma unroll
       for (int h = 0; h < NH; ++h)
         ul[h] = w[pos[h]];
-      double* o = srow[k];
-#pragma unroll
-      for (int j = 0; j < K; ++j)
-      {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-          s -= (rev_m ? bcoef(j, c) : ((j == c) ? 1.0 : 0.0)) * ul[c];
-        const double yp = (j == 0) ? ul[0] : ul[KB + j];
-        o[fm * K + j] += pf_m * s;
-        o[fp * K + j] += pf_p * yp;
-      }
-#pragma unroll
-      for (int q = 0; q < NADD; ++q)
-        o[3 * K + Z::NDIV + q] += sgn * ul[1 + 2 * KB + q];
+      cell.add_correction(ul, cell.row(a.out, a.ncells, k));
     }
   }
   if (status_local)
@@ -703,13 +555,8 @@ static int launch_ws_banded_t(const SeArgs& a, hipStream_t stream)
   const size_t lds_bytes = sizeof(double) * (size_t)W::lds_doubles();
   static_assert(sizeof(double) * W::lds_doubles() <= 160 * 1024, "banded weak-symmetry kernel: LDS");
   auto kern = k_se_weaksym_banded<K, P>;
-  if (lds_bytes > 64 * 1024)
-  {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
-        != hipSuccess)
-      return EQLB_ERR_DEVICE;
-  }
+  if (!ws_allow_lds(kern, lds_bytes))
+    return EQLB_ERR_DEVICE;
   if (a.npatch == 0)
     return 0;
   hipLaunchKernelGGL(kern, dim3((unsigned)a.npatch), dim3(64), lds_bytes, stream, a);

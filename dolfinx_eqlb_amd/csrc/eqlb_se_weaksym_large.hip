@@ -1,12 +1,9 @@
 // Weak symmetry of equilibrated stresses on vertex patches that do not fit one wavefront (more than 63 cells or more
 // than 64 patch facets; option "large_patches_stress"): one WORKGROUP per patch, the cells of the fan strided over its
-// threads.  The formulation is that of k_se_weaksym_banded (eqlb_se_weaksym_banded.hip) - the patch unknowns as a
-// banded chain [a_0 | x_1 | a_1 | x_2 | ...] of half bandwidth BW = 2 KB + NADD - 1 plus the border [d | x_0], the
-// Cholesky factor in that profile, B_k in compressed rows (patch node + three ring points, the dense row of d apart),
-// S = sum_k Y_k^T Y_k with Y_k = L_k^-1 B_k folded chunk by chunk without storing Y, the rank-revealing elimination of
-// the Schur system with the threshold of the dense kernel, u_k = -A_k^-1 B_k gamma per stress row, masked matrices per
-// row where the rows carry different flux BCs, the mean-value multiplier rule - carried to a workgroup the way
-// k_se_patch_large (eqlb_se_large.hip) carries the flux:
+// threads.  The contract is that of eqlb_se_weaksym_common.h, the formulation that of k_se_weaksym_banded
+// (eqlb_se_weaksym_banded.hip) - the patch unknowns as a banded chain plus a border (WsChain), the Cholesky factor in
+// that profile, B_k in compressed rows, S = sum_k Y_k^T Y_k folded chunk by chunk without storing Y - carried to a
+// workgroup the way k_se_patch_large (eqlb_se_large.hip) carries the flux:
 //   * nothing assumes lane = cell; the cell count is the difference of the CSR offsets of the large-patch SoA
 //   * everything whose size grows with the patch - band, border rows, compressed B, Schur matrix, right-hand sides, the
 //     sliding windows of the forward substitution - lives in a global work space sized at eqlb_se_set_boundary
@@ -20,7 +17,7 @@
 // and adds the corrections in place.  A large patch is never part of a group of boundary patches (refused at
 // eqlb_se_set_boundary), so there is one pass and no row of another patch is read.
 // It is a coverage path: the columns of the factorisation and of the elimination are barriers apart.
-#include "eqlb_device_common.h"
+#include "eqlb_se_weaksym_common.h"
 
 namespace eqlb
 {
@@ -31,13 +28,11 @@ constexpr int WL_BLOCK = 256;
 
 // work space of one patch of n cells (doubles), laid out for the larger of the two cases (boundary patch: n + 1 facets)
 template <int K>
-struct WsLarge
+struct WsLarge : WsChain<K>
 {
   using Z = Sizes<K, K - 1, 64>;
-  static constexpr int KB = Z::KB, NADD = Z::NADD, NH = Z::NH, NRT = Z::NRT;
-  static constexpr int NBD = 1 + KB;           // border: d, x_0
-  static constexpr int BW = 2 * KB + NADD - 1; // half bandwidth of the chain
-  static constexpr int LDB = BW + 1;
+  using C = WsChain<K>;
+  static constexpr int KB = C::KB, NADD = C::NADD, NH = C::NH, NBD = C::NBD, BW = C::BW, LDB = C::LDB;
   static constexpr int RCH = 16;               // rows of Y per chunk
   static constexpr int NWIN = BW + NBD;        // per column of B: window of the chain + sums of the border rows
   static constexpr int NCB = 5;                // per cell: Te(d, d) | B_0(d, node) | B_1(d, node) | load(node) | |T|/6
@@ -99,7 +94,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
 {
   using W = WsLarge<K>;
   using Z = typename W::Z;
-  constexpr int KB = W::KB, NADD = W::NADD, NH = W::NH, NRT = W::NRT, NBD = W::NBD, BW = W::BW, LDB = W::LDB;
+  constexpr int KB = W::KB, NH = W::NH, NBD = W::NBD, BW = W::BW, LDB = W::LDB;
   constexpr int RCH = W::RCH, NWIN = W::NWIN, NCB = W::NCB;
   __shared__ double red_v[WL_BLOCK / 64];
   __shared__ int red_i[WL_BLOCK / 64];
@@ -108,21 +103,10 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
   const int tid = threadIdx.x;
   const int64_t s0 = la.off[patch];
   const int n = (int)(la.off[patch + 1] - s0);
-  const uint8_t flag0 = a.pflag[patch];
-  const uint8_t flag1 = a.pflag[a.npatch_total + patch];
-  const bool interior = (flag0 & PFLAG_INTERIOR) != 0;
-  const int nf = interior ? n : n + 1;
-  const int dim = 1 + KB * nf + NADD * n;
-  const int nch = dim - NBD;
-  const int npnt = nf + 1;
-  // flux BCs of the two rows (bits as in k_se_patch); PatchData::reinitialisation :175-206
-  const bool bc0[2] = {(flag0 & PFLAG_BC0) != 0, (flag1 & PFLAG_BC0) != 0};
-  const bool bcn[2] = {(flag0 & PFLAG_BCN) != 0, (flag1 & PFLAG_BCN) != 0};
-  const bool requires_bcs = bc0[0] || bcn[0] || bc0[1] || bcn[1];
-  // mean-value multiplier unless some row has a primal-Dirichlet end (type essnt_primal or mixed)
-  const bool row_dual[2] = {!interior && bc0[0] && bcn[0], !interior && bc0[1] && bcn[1]};
-  const bool meanvalue = interior || (row_dual[0] && row_dual[1]);
-  const int dim_c = meanvalue ? npnt + 1 : npnt;
+  const WsPatch pt = ws_patch(a.pflag[patch], a.pflag[a.npatch_total + patch], n);
+  const int npnt = pt.npnt, dim_c = pt.dim_c;
+  const bool requires_bcs = pt.requires_bcs, meanvalue = pt.meanvalue;
+  const int dim = W::dim(pt), nch = W::nch(pt);
 
   const W L(n);
   const int64_t dimm = L.dimm, npm = L.npm, dcm = L.dcm, LDY = 2 * L.npm;
@@ -143,86 +127,10 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
   double* const cb = wsp + L.cb;
   double* const hd = wsp + L.hd;
 
-  // ---- what a thread knows of cell i of the fan (recomputed where it is needed: nothing is kept per lane) ----
-  struct Cell
-  {
-    int32_t cell;
-    int fm, fp, ln, ci, v_ea, v_eam1;
-    bool rev_m;
-    double J00, J01, J10, J11, sgn, g0, g1, g2;
-    int pos[NH]; // position of the local unknowns [d | um | up | ua] in chain + border order
-    int pj[3];   // multiplier DOF of the local vertices (se/Patch.hpp:621-708)
-  };
-  auto pos_facet = [&](int f, int m) { return (f == 0) ? nch + 1 + m : (f - 1) * (KB + NADD) + NADD + m; };
-  auto load_cell = [&](int i, Cell& c) {
-    c.cell = a.slot_cell[s0 + i];
-    const uint32_t info = a.slot_info[s0 + i];
-    c.fm = (info >> INFO_FM_SHIFT) & 3;
-    c.fp = (info >> INFO_FP_SHIFT) & 3;
-    c.ln = (info >> INFO_LN_SHIFT) & 3;
-    c.rev_m = (info & INFO_REV_M) != 0;
-    c.ci = combo_index(c.fm, c.fp, c.rev_m);
-    const double* Jp = a.cellJ + 4 * (int64_t)c.cell;
-    c.J00 = Jp[0];
-    c.J01 = Jp[1];
-    c.J10 = Jp[2];
-    c.J11 = Jp[3];
-    const double detJ = c.J00 * c.J11 - c.J01 * c.J10;
-    c.sgn = (detJ > 0.0) ? 1.0 : -1.0;
-    const double ia = 1.0 / fabs(detJ);
-    c.g0 = (c.J00 * c.J00 + c.J10 * c.J10) * ia;
-    c.g1 = (c.J00 * c.J01 + c.J10 * c.J11) * ia;
-    c.g2 = (c.J01 * c.J01 + c.J11 * c.J11) * ia;
-    const int fi_p = interior ? ((i + 1 < n) ? i + 1 : 0) : i + 1;
-    c.pos[0] = nch;
-#pragma unroll
-    for (int j = 0; j < KB; ++j)
-    {
-      c.pos[1 + j] = pos_facet(i, j);
-      c.pos[1 + KB + j] = pos_facet(fi_p, j);
-    }
-#pragma unroll
-    for (int q = 0; q < NADD; ++q)
-      c.pos[1 + 2 * KB + q] = i * (KB + NADD) + q;
-    c.v_ea = 3 - c.fp - c.ln;
-    c.v_eam1 = 3 - c.fm - c.ln;
-    const int p_ea = interior ? i + 1 : ((i + 1 == n) ? nf : i + 1);
-    const int p_eam1 = interior ? ((i == 0) ? n : i) : ((i == 0) ? nf - 1 : i);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      c.pj[j] = (j == c.ln) ? 0 : ((j == c.v_ea) ? p_ea : ((j == c.v_eam1) ? p_eam1 : 0));
-  };
-  auto Te = [&](const Cell& c, int h, int g) {
-    const double* te = a.tables + Z::OFF_TE + c.ci * 3 * Z::NTES;
-    const int e = (h >= g) ? h * (h + 1) / 2 + g : g * (g + 1) / 2 + h;
-    return c.g0 * te[e] + c.g1 * te[Z::NTES + e] + c.g2 * te[2 * Z::NTES + e];
-  };
-  // Be(k, h, j): k = 0: int (Phi_h)_y psi_j ; k = 1: -int (Phi_h)_x psi_j
-  auto Be = [&](const Cell& c, int k, int h, int j) {
-    const double* vq = a.tables + Z::OFF_VQ + c.ci * 2 * NH * 3;
-    const double v0 = vq[h * 3 + j], v1 = vq[(NH + h) * 3 + j];
-    return (k == 0) ? (c.J10 * v0 + c.J11 * v1) : -(c.J00 * v0 + c.J01 * v1);
-  };
-  // slot of vertex j in a compressed row of B: 0 the patch node, 1 the ring point of the row's facet (of facet s for
-  // the bubbles of cell s), 2 / 3 the other ring point of the cell before / after it
-  auto bslot = [&](const Cell& c, int h, int j) {
-    if (j == c.ln)
-      return 0;
-    const bool uprow = h > KB && h <= 2 * KB;
-    return uprow ? ((j == c.v_ea) ? 1 : 2) : ((j == c.v_eam1) ? 1 : 3);
-  };
-  // fixed (flux-BC) unknowns per row k (se/assembly.hpp:46-98): local unknown h of cell i
-  auto fixed = [&](int k, int h, int i) {
-    if (!requires_bcs)
-      return false;
-    if (h == 0)
-      return bc0[k] || bcn[k];
-    if (h <= KB)
-      return bc0[k] && i == 0;
-    if (h <= 2 * KB)
-      return bcn[k] && i == n - 1;
-    return false;
-  };
+  // ---- what a thread knows of cell i of the fan is recomputed where it is needed: nothing is kept per lane ----
+  const double* const te_table = a.tables + Z::OFF_TE;
+  const double* const vq_table = a.tables + Z::OFF_VQ;
+  auto pos_facet = [&](int f, int m) { return W::pos_facet(nch, f, m); };
   // Neighbours in the fan share the unknowns of a facet, the first and the last cell of a ring those of facet 0:
   // the cells of one phase share no entry but those of the patch node
   auto phase_of = [&](int i) { return ((n & 1) && i == n - 1) ? 2 : (i & 1); };
@@ -241,45 +149,34 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
     {
       if (phase_of(i) != ph)
         continue;
-      Cell c;
-      load_cell(i, c);
+      const WsCell<K> c(a, te_table, vq_table, s0 + i, true, pt, i);
+      int pos[NH];
+      W::pos(pt, i, pos);
       // patch-local stress rows from the slots; Lc_e[j] = -int psi_j (s01 - s10), Ce = |detJ|/6
       double Lce[3] = {0.0, 0.0, 0.0};
-      {
-        const double* sV = a.tables + Z::OFF_V;
-        const double* r0 = a.out + (((int64_t)0 * a.ncells + c.cell) * 3 + c.ln) * NRT;
-        const double* r1 = a.out + (((int64_t)1 * a.ncells + c.cell) * 3 + c.ln) * NRT;
-        for (int q = 0; q < NRT; ++q)
-        {
-          const double c0 = r0[q], c1 = r1[q];
-          const double w0 = c0 * c.J10 - c1 * c.J00, w1 = c0 * c.J11 - c1 * c.J01;
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            Lce[j] -= c.sgn * (w0 * sV[(j * NRT + q) * 2] + w1 * sV[(j * NRT + q) * 2 + 1]);
-        }
-      }
-      const double Ce = fabs(c.J00 * c.J11 - c.J01 * c.J10) / 6.0;
-      double cbv[NCB] = {Te(c, 0, 0), 0.0, 0.0, 0.0, Ce};
+      c.template load<false>(a.out, a.ncells, false, a.tables + Z::OFF_V, Lce);
+      const double Ce = c.Ce();
+      double cbv[NCB] = {c.Te(0, 0), 0.0, 0.0, 0.0, Ce};
 #pragma unroll
       for (int k = 0; k < 2; ++k)
 #pragma unroll
         for (int h = 0; h < NH; ++h)
         {
-          if (fixed(k, h, i))
+          if (W::fixed(pt, k, h, i))
             continue; // rows of fixed unknowns are dropped (se/assembly.hpp:430-436)
 #pragma unroll
           for (int j = 0; j < 3; ++j)
           {
-            const double v = Be(c, k, h, j);
+            const double v = c.Be(k, h, j);
             if (h == 0)
             {
               if (j == c.ln)
                 cbv[1 + k] = v;
               else
-                Bd[k * npm + c.pj[j]] += v;
+                Bd[k * npm + c.pj(j)] += v;
             }
             else
-              Bv[((int64_t)k * dimm + c.pos[h]) * 4 + bslot(c, h, j)] += v;
+              Bv[((int64_t)k * dimm + pos[h]) * 4 + W::bslot(c.fm, c.fp, c.ln, h, j)] += v;
           }
         }
 #pragma unroll
@@ -287,9 +184,9 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
 #pragma unroll
         for (int j = 0; j < 3; ++j)
         {
-          const int s = bslot(c, h, j);
+          const int s = W::bslot(c.fm, c.fp, c.ln, h, j);
           if (s > 0)
-            Bp[(int64_t)c.pos[h] * 4 + (s - 1)] = c.pj[j];
+            Bp[(int64_t)pos[h] * 4 + (s - 1)] = c.pj(j);
         }
 #pragma unroll
       for (int j = 0; j < 3; ++j)
@@ -299,11 +196,11 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
           cbv[3] = Lce[j];
           continue;
         }
-        Rg[c.pj[j]] += Lce[j];
+        Rg[c.pj(j)] += Lce[j];
         if (meanvalue)
         {
-          Cg[c.pj[j] * dcm + npnt] += Ce;
-          Cg[npnt * dcm + c.pj[j]] += Ce;
+          Cg[c.pj(j) * dcm + npnt] += Ce;
+          Cg[npnt * dcm + c.pj(j)] += Ce;
         }
       }
 #pragma unroll
@@ -344,17 +241,18 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
       {
         if (phase_of(i) != ph)
           continue;
-        Cell c;
-        load_cell(i, c);
+        const WsCell<K> c(a, te_table, vq_table, s0 + i, true, pt, i);
+        int pos[NH];
+        W::pos(pt, i, pos);
 #pragma unroll
         for (int h = 0; h < NH; ++h)
         {
-          if (fixed(k, h, i))
+          if (W::fixed(pt, k, h, i))
             continue;
 #pragma unroll
           for (int g = 0; g < NH; ++g)
-            if (c.pos[h] >= c.pos[g] && !fixed(k, g, i) && (h > 0 || g > 0))
-              Lref(c.pos[h], c.pos[g]) += Te(c, h, g);
+            if (pos[h] >= pos[g] && !W::fixed(pt, k, g, i) && (h > 0 || g > 0))
+              Lref(pos[h], pos[g]) += c.Te(h, g);
         }
       }
       __syncthreads();
@@ -362,14 +260,14 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
     if (tid == 0)
     {
       // the patch node: sum over the cells, or the identity row of a fixed unknown; identity rows of the fixed facets
-      const bool dfix = requires_bcs && (bc0[k] || bcn[k]);
+      const bool dfix = requires_bcs && (pt.bc0(k) || pt.bcn(k));
       bord[nch] = dfix ? 1.0 : hd[0];
       if (requires_bcs)
         for (int m = 0; m < KB; ++m)
         {
-          if (bc0[k])
+          if (pt.bc0(k))
             Lref(nch + 1 + m, nch + 1 + m) = 1.0;
-          if (bcn[k])
+          if (pt.bcn(k))
             Lref(pos_facet(n, m), pos_facet(n, m)) = 1.0;
         }
     }
@@ -739,25 +637,8 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
       __syncthreads();
     }
     __syncthreads();
-    // back substitution over the pivot columns, right to left
     if (tid == 0)
-    {
-      for (int c = dim_c - 1; c >= 0; --c)
-      {
-        if (pcol[c] < 0)
-        {
-          Gg[c] = 0.0;
-          continue;
-        }
-        const int64_t r = pcol[c];
-        double t = Rg[r];
-        for (int j = c + 1; j < dim_c; ++j)
-          t -= Cg[r * dcm + j] * Gg[j];
-        Gg[c] = t / Cg[r * dcm + c];
-        if (!isfinite(Gg[c]))
-          status_local = 1;
-      }
-    }
+      ws_back_substitute(Cg, dcm, Rg, pcol, dim_c, Gg, &status_local);
     __syncthreads();
   }
 
@@ -770,12 +651,12 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
     solve_u(0);
   }
 
-  // ---- back-map and add to the slot rows (se/solve_patch_weaksym.hpp:189-232) ----
+  // ---- back-map and add to the slot rows ----
   for (int i = tid; i < n; i += WL_BLOCK)
   {
-    Cell c;
-    load_cell(i, c);
-    const double pf_m = (c.fm == 1) ? c.sgn : -c.sgn, pf_p = (c.fp == 1) ? c.sgn : -c.sgn;
+    const WsCell<K> c(a, te_table, vq_table, s0 + i, true, pt, i);
+    int pos[NH];
+    W::pos(pt, i, pos);
 #pragma unroll
     for (int k = 0; k < 2; ++k)
     {
@@ -783,22 +664,8 @@ __global__ void __launch_bounds__(WL_BLOCK) k_se_weaksym_large(const SeArgs a, c
       double ul[NH];
 #pragma unroll
       for (int h = 0; h < NH; ++h)
-        ul[h] = w[c.pos[h]];
-      double* o = a.out + (((int64_t)k * a.ncells + c.cell) * 3 + c.ln) * NRT;
-#pragma unroll
-      for (int j = 0; j < K; ++j)
-      {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < K; ++q)
-          s -= (c.rev_m ? bcoef(j, q) : ((j == q) ? 1.0 : 0.0)) * ul[q];
-        const double yp = (j == 0) ? ul[0] : ul[KB + j];
-        o[c.fm * K + j] += pf_m * s;
-        o[c.fp * K + j] += pf_p * yp;
-      }
-#pragma unroll
-      for (int q = 0; q < NADD; ++q)
-        o[3 * K + Z::NDIV + q] += c.sgn * ul[1 + 2 * KB + q];
+        ul[h] = w[pos[h]];
+      c.add_correction(ul, c.row(a.out, a.ncells, k));
     }
   }
   if (status_local)
