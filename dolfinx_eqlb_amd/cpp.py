@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_primal_matrix_pattern", "eqlb_primal_matrix_export", "eqlb_primal_matrix_values", "eqlb_primal_matrix_release",
     "eqlb_elasticity_matrix_pattern", "eqlb_elasticity_matrix_export", "eqlb_elasticity_matrix_values",
     "eqlb_elasticity_matrix_release", "eqlb_csr_apply",
+    "eqlb_get_facet_mass_table", "eqlb_primal_set_robin", "eqlb_primal_robin_weights", "eqlb_primal_robin_flux",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -644,6 +645,20 @@ class Refinement:
         out = np.zeros((fl.size, 2), dtype=np.int32)
         plan.child_facets_raw(self.dmesh, fl.size, fl.ctypes.data, out.ctypes.data, MEM_HOST, stream)
         return out[out >= 0] if flat else out
+
+    def carry_robin(self, old, new, stream=0):
+        """The Robin list of the solver handle `old` (PrimalPoisson on the mesh that was refined) on the refined mesh:
+        the list goes through child_facets, a child takes its parent's alpha, and `new` (PrimalPoisson on the refined
+        mesh) gets it through set_robin (the rule: mesh.refine.carry_robin_list).  Returns (facets2, facet_alpha2), host
+        arrays.  `old` must have received its list through set_robin (host arrays); one without the term switches the
+        term of `new` off."""
+        f, a = old.robin_list()
+        ch = self.child_facets(f, stream=stream)
+        keep = ch >= 0
+        f2 = ch[keep].astype(np.int32)
+        a2 = np.repeat(a[:, None], 2, axis=1)[keep]
+        new.set_robin(f2, facet_alpha=a2, stream=stream)
+        return f2, a2
 
     def prolong_flux_bc(self, k, boundary_values, facets2, stream=0):
         """The table boundary_values [nrhs, ncells*k(k+2)] (or 1-D) of the old mesh -> dofs [nrhs, nlist, k] of the
@@ -1500,6 +1515,16 @@ def get_mass_table(p: int):
     return out
 
 
+def get_facet_mass_table(p: int):
+    """The built-in table FacetMass<p> [p+1, p+1] of the Robin term (eqlb_get_facet_mass_table), 1 <= p <= 4."""
+    n1 = max(int(p), 0) + 1
+    out = np.zeros((n1, n1))
+    n = lib().eqlb_get_facet_mass_table(C.c_int32(p), _hp(out), C.c_int32(out.size))
+    if n < 0:
+        _check(n)
+    return out
+
+
 def get_stiffness_table(p: int):
     """The built-in table Stiff<p> [3, nd_p, nd_p] of PrimalPoisson (eqlb_get_stiffness_table), 1 <= p <= 4."""
     nd = (max(int(p), 0) + 1) * (max(int(p), 0) + 2) // 2
@@ -1795,6 +1820,76 @@ class PrimalPoisson(_PrimalSolver):
     def set_diffusion_raw(self, cell_D=None, memspace=MEM_DEVICE, stream=0):
         """cell_D: a raw pointer (int) to [ncells][3] in `memspace`, or None (the term off)."""
         _check(lib().eqlb_primal_set_diffusion(self._h, _vp(cell_D), C.c_int32(memspace), C.c_void_p(stream)))
+
+    def set_robin(self, facets, alpha=1.0, facet_alpha=None, stream=0):
+        """The operator gains the boundary mass int alpha u v over the listed boundary facets (eqlb_primal_set_robin):
+        -(coeff D grad u) . n = alpha (u - u_ext) there; alpha_f = facet_alpha [nlist] where given, else the scalar.
+        An empty list switches the term off; a repeated call replaces the list.  Refused by facet, the handle as it
+        was: a facet that is no boundary facet, one listed twice, an alpha that is negative, NaN or infinite.  With some
+        alpha_f > 0 the solves no longer ask for a Dirichlet DOF.  The diagonal is formed again;
+        Multilevel.set_coarse(True) has to be called again afterwards.  The datum u_ext enters the load through
+        lsolver.robin_load; Refinement.carry_robin carries the list to the refined mesh."""
+        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+        fa = None
+        if facet_alpha is not None:
+            fa = np.ascontiguousarray(facet_alpha, dtype=np.float64).ravel()
+            if fa.size != fl.size:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        self.set_robin_raw(fl.size, fl.ctypes.data if fl.size else None, alpha,
+                           fa.ctypes.data if fa is not None and fa.size else None, MEM_HOST, stream)
+        self._robin_list = (fl.copy(), np.full(fl.size, float(alpha)) if fa is None else fa.copy())
+
+    def robin_list(self):
+        """(facets int32 [nlist], facet_alpha [nlist]) as the last accepted set_robin took them (empty without one)."""
+        return getattr(self, "_robin_list", (np.zeros(0, dtype=np.int32), np.zeros(0)))
+
+    def set_robin_raw(self, nlist, facets, alpha=1.0, facet_alpha=None, memspace=MEM_DEVICE, stream=0):
+        """facets int32 [nlist], facet_alpha float64 [nlist] or None behind raw pointers in `memspace`.  Device memory
+        space: a listed id that is no boundary facet is skipped; the call waits for the stream."""
+        _check(lib().eqlb_primal_set_robin(self._h, C.c_int32(nlist), _vp(facets), C.c_double(alpha), _vp(facet_alpha),
+                                           C.c_int32(memspace), C.c_void_p(stream)))
+
+    def robin_count(self):
+        """The number of listed facets of the Robin term (0 without it)."""
+        n = C.c_int32(0)
+        _check(lib().eqlb_primal_robin_weights(self._h, C.byref(n), None, C.c_int32(0), C.c_int32(MEM_HOST), None))
+        return int(n.value)
+
+    def robin_weights(self, stream=0):
+        """w_f = alpha_f |E_f| [nlist] in the order of the list (eqlb_primal_robin_weights)."""
+        w = np.zeros(self.robin_count())
+        if w.size:
+            self.robin_weights_raw(w.ctypes.data, w.size, MEM_HOST, stream)
+        return w
+
+    def robin_weights_raw(self, w, capacity, memspace=MEM_DEVICE, stream=0):
+        n = C.c_int32(0)
+        _check(lib().eqlb_primal_robin_weights(self._h, C.byref(n), _vp(w), C.c_int32(capacity), C.c_int32(memspace),
+                                               C.c_void_p(stream)))
+        return int(n.value)
+
+    def robin_flux(self, u, s, u_ext=None, stream=0):
+        """out [nlist, nq] = alpha_i (u_h(x_q) - u_ext[i][q]) on the handle's Robin list at the facet parameters s [nq]
+        in the frame of facet_points (eqlb_primal_robin_flux): the point values of the flux condition
+        sigma_eq . n that update_flux_bc takes with vector=False.  u_ext [nlist, nq] or None (0)."""
+        uu = self._vec(u)
+        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+        n = self.robin_count()
+        ue = None
+        if u_ext is not None:
+            ue = np.ascontiguousarray(u_ext, dtype=np.float64).ravel()
+            if ue.size != n * ss.size:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        out = np.zeros((n, ss.size))
+        self.robin_flux_raw(uu.ctypes.data, ss, None if ue is None else ue.ctypes.data, out.ctypes.data, MEM_HOST,
+                            stream)
+        return out
+
+    def robin_flux_raw(self, u, s, u_ext, out, memspace=MEM_DEVICE, stream=0):
+        """u [ndofs], u_ext [nlist][nq] or None and out [nlist][nq] behind raw pointers in `memspace`; s a host array."""
+        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+        _check(lib().eqlb_primal_robin_flux(self._h, _vp(u), C.c_int32(ss.size), _hp(ss), _vp(u_ext), _vp(out),
+                                            C.c_int32(memspace), C.c_void_p(stream)))
 
     def apply_many(self, U, masked=False, stream=0):
         """Y [nrhs][ndofs]: row c is apply(U[c]), bit for bit, in one call."""

@@ -431,7 +431,7 @@ int coarse_setup(const char* who, CoarseSolve& cs, const SolverLevel& lv, hipStr
   HIP_TRY(hipMemcpyAsync(fixed.data(), lv.fixed, (size_t)n0, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (int c = 0; c < lv.bs; ++c)
-    if (status[1 + c] < 1)
+    if (status[1 + c] < 1 && !lv.definite(lv.handle))
       return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: component %d of level 0 has no Dirichlet DOF", who, c);
   std::vector<int32_t> rows;
   for (int64_t e = 0; e < n0; ++e)

@@ -422,6 +422,8 @@ struct SolverLevel
                          hipStream_t stream);
   // q = A d on the free rows, the block partials of d.q in part
   hipError_t (*product)(void* handle, const ManyCols& c, hipStream_t stream);
+  // the operator is positive definite without a fixed DOF: a Robin term with some weight > 0 (eqlb_primal_set_robin)
+  bool (*definite)(void* handle);
 };
 void primal_level(eqlb_primal* h, SolverLevel& v);
 void elasticity_level(eqlb_elasticity* h, SolverLevel& v);

@@ -460,7 +460,7 @@ int hierarchy_solve(const char* who, bool many, eqlb_hierarchy* h, int32_t nrhs,
   HIP_TRY(hipMemcpyAsync(status, top.status, sizeof(status), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (int c = 0; c < h->bs; ++c)
-    if (status[1 + c] < 1)
+    if (status[1 + c] < 1 && !top.definite(top.handle))
       return many ? fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: the finest level has no Dirichlet DOF", who)
                   : fail(EQLB_ERR_INVALID_ARGUMENT,
                          "%s: singular: component %d of the finest level has no Dirichlet DOF", who, c);

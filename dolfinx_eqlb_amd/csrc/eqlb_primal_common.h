@@ -16,7 +16,8 @@
 //  k_primal_slots    builds the slot lists of the sum pass once at create (scalar numbering: both problems use it)
 //  k_primal_mask<BS> the Dirichlet mask of one component from a list of facets
 //  k_primal_gather<BS, NC>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
-//                    x[BS * dof + r]; columns for BS = 1 only
+//                    x[BS * dof + r]; columns for BS = 1 only.  eqlb_primal_gather.inc, included twice: the second
+//                    time as k_primal_gather_robin, which adds the facet values of a Robin term
 //  k_pcg_*<NC>       work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
 //  k_pcg_scalar      the scalar steps; `ml`: the breakdown rule of a preconditioner that is no positive diagonal
 //  pcg_solve         the host side of the iteration on a PcgWork; the preconditioner enters through its `steps`
@@ -167,88 +168,29 @@ struct GatherArgs
       hipLaunchKernelGGL(KERNEL<MANY_R>, dim3(stream_blocks(n)), dim3(PS_THREADS), 0, stream, __VA_ARGS__);            \
   } while (0)
 
-// the sum pass with BS components per DOF on the live columns: e = BS d + r runs over the blocked vectors, y_loc holds
-// BS values per (cell, local index), the component fastest.  The slot range of a DOF is found once; the sum of a
-// column runs in the order of the slot list
-template <int BS, int NC>
-__global__ void __launch_bounds__(PS_THREADS) k_primal_gather(const GatherArgs a)
+// the Robin term of the sum pass (include/eqlb.h: eqlb_primal_set_robin), all pointers DEVICE: the table a row finds its
+// facets through, built at set_robin.  A kernel argument of its own, which the sum pass without the term does not take.
+constexpr int ROBIN_ROW = PS_PMAX + 1; // row stride of dofs: the p + 1 rows of a facet in its local order
+struct RobinArgs
 {
-#pragma clang fp contract(off)
-  static_assert(BS == 1 || NC == 1, "columns for scalar spaces only");
-  __shared__ double sh[NC][PS_THREADS];
-  const uint32_t live = cols_live<NC>(a.cols);
-  if (!live)
-    return;
-  const SpaceArgs& s = a.s;
-  const int t = threadIdx.x;
-  const int64_t nshared = (int64_t)s.nnodes + (int64_t)s.nfacets * s.ne, n = s.ndofs * BS;
-  double acc[NC];
-#pragma unroll
-  for (int k = 0; k < NC; ++k)
-    acc[k] = 0.0;
-  for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + t; e < n; e += (int64_t)gridDim.x * PS_THREADS)
-  {
-    const int64_t d = e / BS;
-    const int r = (int)(e - d * BS);
-    int64_t beg = 0;
-    int cnt = 0;
-    if (d < nshared)
-      slot_range(s, d, beg, cnt);
-    else
-    {
-      const int64_t q = d - nshared, c = q / s.ni;
-      beg = c * s.nd + 3 + 3 * s.ne + (q - c * s.ni); // (the one entry of an interior DOF)
-    }
-    bool fx = false;
-    if constexpr (NC > 1)
-      fx = a.fixed && a.fixed[e]; // (once for the columns; the one-column instance asks behind its sum)
-#pragma unroll
-    for (int k = 0; k < NC; ++k)
-    {
-      if (!col_on<NC>(live, k))
-        continue;
-      const double* yl = a.yloc + k * a.ystride;
-      double v;
-      if (d < nshared)
-      {
-        v = cnt > 0 ? yl[(int64_t)s.slots[beg] * BS + r] : 0.0;
-        for (int j = 1; j < cnt; ++j)
-          v = v + yl[(int64_t)s.slots[beg + j] * BS + r];
-      }
-      else
-        v = yl[beg * BS + r];
-      const int64_t x = k * n + e;
-      if constexpr (NC == 1)
-      {
-        if (a.add)
-          v = v + a.add[x];
-        fx = a.fixed && a.fixed[e];
-      }
-      const double yv = fx ? 0.0 : v;
-      if (a.y)
-        a.y[x] = yv;
-      double rv = 0.0;
-      if (a.r)
-      {
-        rv = fx ? 0.0 : a.b[x] - v;
-        a.r[x] = rv;
-      }
-      if (a.dot == DOT_W_Y)
-        acc[k] = acc[k] + a.w[x] * yv;
-      else if (a.dot == DOT_R_R)
-        acc[k] = acc[k] + rv * rv;
-    }
-  }
-  if (a.dot == DOT_NONE)
-    return;
-#pragma unroll
-  for (int k = 0; k < NC; ++k)
-    sh[k][t] = acc[k];
-  __syncthreads();
-  EQLB_BLOCK_TREE_SUM(sh, t, NC, PS_THREADS)
-  if (t < NC && col_on<NC>(live, t))
-    a.part[(int64_t)(2 * t) * gridDim.x + blockIdx.x] = sh[t][0];
-}
+  const int32_t* chunk; // [ceil(ndofs / PS_THREADS) + 1] first position in rows[] of a chunk of PS_THREADS rows
+  const int32_t* rows;  // [m] the rows that lie in a Robin facet, ascending
+  const int32_t* off;   // [m + 1] the entries of a row in ent[]
+  const int32_t* ent;   // list position * 8 + local index of the row in that facet, facet ids ascending
+  const int32_t* dofs;  // [nlist][ROBIN_ROW]
+  const double* w;      // [nlist] alpha_f |E_f|
+  const double* fm;     // FacetMass<p> [n1][n1]
+  const double* u;      // column 0 of [R][ndofs]; nullptr: the diagonal
+  const uint8_t* fixed; // only_fixed: the free rows of u read as 0
+  int32_t only_fixed, n1;
+};
+
+#define EQLB_GATHER_ROBIN 0
+#include "eqlb_primal_gather.inc"
+#undef EQLB_GATHER_ROBIN
+#define EQLB_GATHER_ROBIN 1
+#include "eqlb_primal_gather.inc"
+#undef EQLB_GATHER_ROBIN
 
 // ---- vector kernels of the iteration (grid-stride, block partials in a fixed order): the columns of a DOF in one
 // thread.  Channel j of column k: sh[2 k + j], part[(2 k + j) G + block] ----------------------------------------------

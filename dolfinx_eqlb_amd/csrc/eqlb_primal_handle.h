@@ -54,6 +54,11 @@ struct MatrixView
   double react_c = 0.0, shear_mu = 1.0;
   const uint8_t* fixed = nullptr;
   MatrixPattern* pattern = nullptr;
+  // the Robin term (bs = 1), the table of RobinArgs (eqlb_primal_common.h): m rows lie in a Robin facet
+  bool has_robin = false;
+  int32_t robin_m = 0, robin_n1 = 0;
+  const int32_t *robin_rows = nullptr, *robin_off = nullptr, *robin_ent = nullptr, *robin_dofs = nullptr;
+  const double *robin_w = nullptr, *robin_fm = nullptr;
 };
 void primal_matrix_view(eqlb_primal* h, MatrixView& v);         // eqlb_primal_solve.hip
 void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v); // eqlb_primal_elasticity.hip
@@ -113,6 +118,13 @@ struct SolverHandle
   // the first call that brings one and kept; has_diff says whether the kernels read it
   bool has_diff = false;
   DevBuf<double> diff;
+  // the Robin term (eqlb_primal_set_robin, the Poisson unit): off as created.  Both arrays are allocated by a call that
+  // brings a list and replaced as a whole by the next one
+  bool has_robin = false, robin_pos = false; // robin_pos: some w_f > 0 - the operator is definite without a fixed DOF
+  int32_t robin_n = 0;                       // listed facets
+  DevBuf<int32_t> robin_tab;                 // facets [n] | dofs [n][ROBIN_ROW] | chunk | rows | off | ent
+  DevBuf<double> robin_val;                  // w [n] | alpha [n] | FacetMass<p> [(p + 1)^2]
+  size_t robin_chunk = 0, robin_rows = 0, robin_off = 0, robin_ent = 0, robin_nent = 0; // positions in robin_tab
   // the CSR pattern of the operator (eqlb_primal_matrix.hip): empty until eqlb_*_matrix_pattern
   MatrixPattern pattern;
 };
@@ -174,6 +186,27 @@ int primal_work(H* h, int R, PcgWork& w)
   return EQLB_OK;
 }
 
+// the table of the handle's Robin term for a sum pass: u the vector of the store pass (column 0), nullptr: the diagonal
+template <class H>
+RobinArgs robin_args(const H& h, const double* u, bool only_fixed)
+{
+  RobinArgs x{};
+  const int32_t* tab = h.robin_tab.get();
+  const size_t n = (size_t)h.robin_n;
+  x.dofs = tab + n;
+  x.chunk = tab + h.robin_chunk;
+  x.rows = tab + h.robin_rows;
+  x.off = tab + h.robin_off;
+  x.ent = tab + h.robin_ent;
+  x.w = h.robin_val.get();
+  x.fm = h.robin_val.get() + 2 * n;
+  x.u = u;
+  x.fixed = h.fixed;
+  x.only_fixed = only_fixed ? 1 : 0;
+  x.n1 = h.p + 1;
+  return x;
+}
+
 template <class H>
 GatherArgs gather_args(const H& h, const ManyCols& c, bool masked)
 {
@@ -201,6 +234,26 @@ hipError_t launch_gather(const H& h, const GatherArgs& g, hipStream_t stream)
   return hipGetLastError();
 }
 
+// the sum pass behind a store pass of the OPERATOR (u: what that pass read, nullptr: the diagonal): with a Robin term on
+// the handle the variant that adds the facet values, else the launch above.  The sum pass of the load and of the
+// restriction of a hierarchy (enqueue_owner_sum) never carries the term
+template <class H>
+hipError_t launch_gather_op(const H& h, const GatherArgs& g, const double* u, bool only_fixed, hipStream_t stream)
+{
+  if constexpr (H::bs == 1)
+    if (h.has_robin)
+    {
+      const dim3 grid(stream_blocks(h.ndofs)), block(PS_THREADS);
+      const RobinArgs x = robin_args(h, u, only_fixed);
+      if (g.cols.R == 1)
+        hipLaunchKernelGGL((k_primal_gather_robin<1, 1>), grid, block, 0, stream, g, x);
+      else
+        hipLaunchKernelGGL((k_primal_gather_robin<1, MANY_R>), grid, block, 0, stream, g, x);
+      return hipGetLastError();
+    }
+  return launch_gather(h, g, stream);
+}
+
 // y = owner sum of y_loc (masked or raw) on the columns of c; y DEVICE [R][bs ndofs]
 template <class H>
 hipError_t enqueue_owner_sum(const H& h, const ManyCols& c, double* y, bool masked, hipStream_t stream)
@@ -214,7 +267,11 @@ template <class H>
 hipError_t enqueue_diagonal(const H& h, double* out, hipStream_t stream)
 {
   const hipError_t e = launch_cell<CELL_DIAGONAL>(h, ONE_COLUMN, 0, nullptr, false, stream);
-  return e != hipSuccess ? e : enqueue_owner_sum(h, ONE_COLUMN, out, false, stream);
+  if (e != hipSuccess)
+    return e;
+  GatherArgs g = gather_args(h, ONE_COLUMN, false);
+  g.y = out;
+  return launch_gather_op(h, g, nullptr, false, stream);
 }
 
 // r = b - A u (0 on the fixed rows), u^ instead of u with only_fixed; the block partials of r.r are left in part
@@ -229,7 +286,7 @@ hipError_t enqueue_residual(const H& h, const ManyCols& c, const double* b, cons
   g.b = b;
   g.r = r;
   g.dot = DOT_R_R;
-  return launch_gather(h, g, stream);
+  return launch_gather_op(h, g, u, only_fixed, stream);
 }
 
 // q = A d on the free rows (the direction d of the work space), the block partials of d.q in part
@@ -244,7 +301,7 @@ hipError_t enqueue_product(const H& h, const ManyCols& c, hipStream_t stream)
   g.y = w.q;
   g.w = w.d;
   g.dot = DOT_W_Y;
-  return launch_gather(h, g, stream);
+  return launch_gather_op(h, g, w.d, false, stream);
 }
 
 // the handle as the hierarchy unit sees it (eqlb_internal.h: SolverLevel)
@@ -272,6 +329,7 @@ void solver_level(H* h, SolverLevel& v)
   v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
     return enqueue_product(*static_cast<H*>(hh), c, stream);
   };
+  v.definite = [](void* hh) { return static_cast<H*>(hh)->has_robin && static_cast<H*>(hh)->robin_pos; };
 }
 
 // the handle as the matrix unit sees it; a unit with further coefficients (pi_1, the shear modulus) adds them
@@ -302,6 +360,20 @@ void solver_matrix_view(H* h, MatrixView& v)
   v.diff = h->has_diff ? h->diff.get() : nullptr;
   v.fixed = h->fixed;
   v.pattern = &h->pattern;
+  if constexpr (H::bs == 1)
+    if (h->has_robin)
+    {
+      const RobinArgs x = robin_args(*h, nullptr, false);
+      v.has_robin = true;
+      v.robin_m = (int32_t)(h->robin_off - h->robin_rows);
+      v.robin_n1 = x.n1;
+      v.robin_rows = x.rows;
+      v.robin_off = x.off;
+      v.robin_ent = x.ent;
+      v.robin_dofs = x.dofs;
+      v.robin_w = x.w;
+      v.robin_fm = x.fm;
+    }
 }
 
 // ---- the C entries behind their names (`who`) -------------------------------------------------------------------------
@@ -616,7 +688,9 @@ int solver_apply(const char* who, H* h, int32_t nrhs, const double* u, double* y
     const int R = nrhs - c0 < H::max_cols ? nrhs - c0 : H::max_cols;
     const ManyCols cols{R, (1u << R) - 1u, 0, nullptr};
     s.note(launch_cell<CELL_OPERATOR>(*h, cols, 0, pu + c0 * n, false, stream));
-    s.note(enqueue_owner_sum(*h, cols, py + c0 * n, masked != 0, stream));
+    GatherArgs g = gather_args(*h, cols, masked != 0);
+    g.y = py + c0 * n;
+    s.note(launch_gather_op(*h, g, pu + c0 * n, false, stream));
   }
   HIP_TRY(s.finish(stream));
   return EQLB_OK;
@@ -692,7 +766,7 @@ int solver_solve(const char* who, H* h, int32_t nrhs, const double* b, double* u
   HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (int r = 0; r < H::bs; ++r)
-    if (status[1 + r] < 1)
+    if (status[1 + r] < 1 && !(h->has_robin && h->robin_pos)) // (a Robin term with some w_f > 0: definite as it is)
     {
       if constexpr (H::bs == 1)
         return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);

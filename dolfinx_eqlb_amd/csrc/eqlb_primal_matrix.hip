@@ -259,6 +259,57 @@ __global__ void __launch_bounds__(MX_THREADS) k_matrix_fill(const FillArgs a)
   }
 }
 
+// The Robin term of a Poisson handle (include/eqlb.h: eqlb_primal_set_robin) on top of the filled values: one thread per
+// row that lies in a Robin facet walks the facets of the row in ascending id (the table of the sum pass) and adds
+// w_f FacetMass[i][j] to the entry (d, d_j) of every row d_j of the facet, each by one addition - the cell sums first,
+// then the facets ascending, as the statement has it; the diagonal entry gets the bits of the handle's diagonal.  The
+// pattern holds every such pair (both rows lie in the facet's cell); an eliminated entry keeps its 0.0 or 1.0.
+struct RobinFillArgs
+{
+  int32_t m, n1;
+  const int32_t *rows, *off, *ent, *dofs;
+  const double *w, *fm;
+  const uint8_t* fixed; // nullptr: the raw operator
+  const int64_t* sptr;
+  const int32_t* scol;
+  double* values;
+};
+
+__global__ void __launch_bounds__(MX_THREADS) k_matrix_robin(const RobinFillArgs a)
+{
+#pragma clang fp contract(off)
+  for (int32_t mi = blockIdx.x * MX_THREADS + threadIdx.x; mi < a.m; mi += gridDim.x * MX_THREADS)
+  {
+    const int64_t d = a.rows[mi];
+    const int64_t p0 = a.sptr[d], p1 = a.sptr[d + 1];
+    for (int q = a.off[mi]; q < a.off[mi + 1]; ++q)
+    {
+      const int32_t en = a.ent[q];
+      const int i = en & 7;
+      const int64_t li = en >> 3;
+      const int32_t* dd = a.dofs + li * ROBIN_ROW;
+      const double w = a.w[li];
+      for (int j = 0; j < a.n1; ++j)
+      {
+        const int32_t dc = dd[j];
+        if (a.fixed && (a.fixed[d] || a.fixed[dc]))
+          continue;
+        int64_t lo = p0, hi = p1;
+        while (lo < hi)
+        {
+          const int64_t mid = (lo + hi) >> 1;
+          if (a.scol[mid] < dc)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        if (lo < p1 && a.scol[lo] == dc)
+          a.values[lo] = a.values[lo] + w * a.fm[i * a.n1 + j];
+      }
+    }
+  }
+}
+
 // y[row] = the sum over the positions of the row in ascending order, the first product starts it.  One row per thread;
 // a bundle of G consecutive rows (the rows of G neighbouring lanes) one of which has CSR_GROUP_MIN entries or more is
 // summed by the G lanes together, row after row: the lanes read G consecutive entries of the row at once and form the
@@ -507,6 +558,14 @@ int matrix_values(const char* who, const MatrixView& v, int32_t eliminate, doubl
     HIP_TRY(s.upload(stream));
   double* pv = host ? d_v.get() : values;
   s.note(v.bs == 1 ? launch_fill<1>(v, eliminate != 0, pv, stream) : launch_fill<2>(v, eliminate != 0, pv, stream));
+  if (v.bs == 1 && v.has_robin && v.robin_m > 0)
+  {
+    const RobinFillArgs a{v.robin_m,   v.robin_n1, v.robin_rows, v.robin_off, v.robin_ent,          v.robin_dofs,
+                          v.robin_w,   v.robin_fm, eliminate ? v.fixed : nullptr, v.pattern->sptr.get(),
+                          v.pattern->scol.get(), pv};
+    hipLaunchKernelGGL(k_matrix_robin, dim3(mx_blocks(v.robin_m)), dim3(MX_THREADS), 0, stream, a);
+    s.note(hipGetLastError());
+  }
   HIP_TRY(s.finish(stream));
   return EQLB_OK;
 }

@@ -33,7 +33,10 @@
 #include "eqlb_primal_handle.h" // the host side of a solver handle; eqlb_primal_common.h: the kernels it launches
 #include "eqlb_tables_gen.h"
 
+#include <algorithm>
 #include <cmath>
+#include <unordered_set>
+#include <vector>
 
 // the handle behind eqlb_primal_t
 struct eqlb_primal : eqlb::SolverHandle<1, eqlb::MANY_R>
@@ -224,6 +227,262 @@ hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const dou
   return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, h.has_react ? &rx : nullptr,
                            h.has_diff ? &dx : nullptr, stream);
 }
+// ---- the Robin term (include/eqlb.h: eqlb_primal_set_robin) --------------------------------------------------------
+// One thread per listed facet: its rows in the local order (lower node id, higher node id, nnodes + f (p-1) + j), its
+// weight w = alpha |E| with |E| = sqrt(dx dx + dy dy) from facet_nodes, every operation rounded on its own, and what the
+// host needs to refuse or skip it: flag 1 a boundary facet, 2 a facet between two cells, 0 an id or a node outside the
+// mesh (nothing of it is read).  A facet that is not flagged 1 gets the weight 0 and the rows -1.
+__global__ void __launch_bounds__(PS_THREADS)
+k_robin_prepare(int32_t nlist, const int32_t* __restrict__ facets, double alpha, const double* __restrict__ facet_alpha,
+                int32_t nnodes, int32_t nfacets, int32_t ne, const double* __restrict__ x,
+                const int32_t* __restrict__ facet_nodes, const int32_t* __restrict__ fco, int32_t* __restrict__ flist,
+                int32_t* __restrict__ dofs, int32_t* __restrict__ flag, double* __restrict__ w, double* __restrict__ al)
+{
+#pragma clang fp contract(off)
+  const int32_t i = blockIdx.x * PS_THREADS + threadIdx.x;
+  if (i >= nlist)
+    return;
+  const int32_t f = facets[i];
+  const double a = facet_alpha ? facet_alpha[i] : alpha;
+  int32_t* dd = dofs + (int64_t)i * ROBIN_ROW;
+  int32_t fl = 0, n0 = -1, n1 = -1;
+  if (f >= 0 && f < nfacets)
+  {
+    n0 = facet_nodes[2 * (int64_t)f];
+    n1 = facet_nodes[2 * (int64_t)f + 1];
+    if (n0 >= 0 && n0 < nnodes && n1 >= 0 && n1 < nnodes)
+      fl = (fco[f + 1] - fco[f] == 1) ? 1 : 2;
+  }
+  flist[i] = f;
+  flag[i] = fl;
+  al[i] = a;
+  if (fl != 1)
+  {
+    w[i] = 0.0;
+    for (int j = 0; j < ROBIN_ROW; ++j)
+      dd[j] = -1;
+    return;
+  }
+  const double dx = x[3 * (int64_t)n1] - x[3 * (int64_t)n0], dy = x[3 * (int64_t)n1 + 1] - x[3 * (int64_t)n0 + 1];
+  w[i] = a * sqrt(dx * dx + dy * dy);
+  dd[0] = n0 < n1 ? n0 : n1;
+  dd[1] = n0 < n1 ? n1 : n0;
+  for (int j = 0; j < ROBIN_ROW - 2; ++j)
+    dd[2 + j] = j < ne ? nnodes + f * ne + j : -1;
+}
+
+constexpr int RF_MAX_NQ = 64;
+struct RobinRule
+{
+  double s[RF_MAX_NQ];
+};
+
+// One thread per (listed facet, point): out[i][q] = alpha_i (u_h(x_q) - u_ext[i][q]) at the facet parameter s_q in the
+// frame of eqlb_facet_points (the facet seen from its one cell, the low local vertex first).  The parameter of the
+// facet's own frame (0 at the lower node id) is s or 1 - s; l_j is the product over the other nodes k, in the local
+// order, of (s - x_k) / (x_j - x_k) with x = (0, 1, 1/p ... (p-1)/p), the first factor starts it; u_h is the sum of
+// l_j u[dof_j] in ascending j, the first product starts it.  Every operation rounded on its own.  A facet the list
+// skipped gives NaN; every index is checked before it is used.
+__global__ void __launch_bounds__(PS_THREADS)
+k_robin_flux(int32_t nlist, int32_t nq, int32_t p, const RobinRule rule, const int32_t* __restrict__ flist,
+             const int32_t* __restrict__ dofs, const double* __restrict__ al, int32_t ncells,
+             const int32_t* __restrict__ cell_nodes, const int32_t* __restrict__ cell_facets,
+             const int32_t* __restrict__ fco, const int32_t* __restrict__ facet_cells, const double* __restrict__ u,
+             const double* __restrict__ u_ext, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= (int64_t)nlist * nq)
+    return;
+  const int64_t i = t / nq;
+  const int q = (int)(t - i * nq);
+  const int32_t* dd = dofs + i * ROBIN_ROW;
+  const int32_t f = flist[i];
+  int lf = -1;
+  int32_t cell = -1;
+  if (dd[0] >= 0) // (a boundary facet inside the mesh: k_robin_prepare)
+  {
+    cell = facet_cells[fco[f]];
+    if (cell >= 0 && cell < ncells)
+      for (int l = 0; l < 3; ++l)
+        if (cell_facets[(int64_t)cell * 3 + l] == f)
+          lf = l;
+  }
+  if (lf < 0)
+  {
+    out[t] = __builtin_nan("");
+    return;
+  }
+  const int va = (lf == 0) ? 1 : 0, vb = (lf == 2) ? 1 : 2; // the low local vertex first
+  const bool same = cell_nodes[(int64_t)cell * 3 + va] < cell_nodes[(int64_t)cell * 3 + vb];
+  const double s = same ? rule.s[q] : 1.0 - rule.s[q];
+  double xn[PS_PMAX + 1];
+  xn[0] = 0.0;
+  xn[1] = 1.0;
+  for (int j = 1; j < p; ++j)
+    xn[1 + j] = (double)j / (double)p;
+  double uh = 0.0;
+  for (int j = 0; j <= p; ++j)
+  {
+    double l = 1.0;
+    bool first = true;
+    for (int k = 0; k <= p; ++k)
+      if (k != j)
+      {
+        const double fac = (s - xn[k]) / (xn[j] - xn[k]);
+        l = first ? fac : l * fac;
+        first = false;
+      }
+    const double pr = l * u[dd[j]];
+    uh = j == 0 ? pr : uh + pr;
+  }
+  if (u_ext)
+    uh = uh - u_ext[t];
+  out[t] = al[i] * uh;
+}
+
+const double* facet_mass_of(int p)
+{
+  return p == 1 ? eqlb_tables::FacetMass<1>::FM
+                : p == 2 ? eqlb_tables::FacetMass<2>::FM
+                         : p == 3 ? eqlb_tables::FacetMass<3>::FM : eqlb_tables::FacetMass<4>::FM;
+}
+
+// the body of eqlb_primal_set_robin.  The list is prepared on the device into fresh arrays, looked at on the host, where
+// the table of the sum pass is built (the listed facets are O(sqrt N)), and only then put in the place of the old ones:
+// a refused call leaves the handle as it was.  The call waits for the stream in both memory spaces.
+int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32_t* facets, double alpha,
+                     const double* facet_alpha, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  if (nlist < 0 || (nlist > 0 && !facets))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d, or a null list", who, (int)nlist);
+  if (nlist >= (1 << 28))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d: at most 2^28 - 1 facets", who, (int)nlist);
+  if (!facet_alpha && !(alpha >= 0.0 && std::isfinite(alpha)))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: alpha = %g is negative, NaN or infinite", who, alpha);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const DeviceMesh& m = h->mesh->m;
+  const size_t n = (size_t)nlist;
+  const int n1 = h->p + 1;
+  if (nlist == 0)
+  {
+    h->has_robin = h->robin_pos = false;
+    h->robin_n = 0;
+    HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+    if (host)
+      HIP_TRY(hipStreamSynchronize(stream));
+    return EQLB_OK;
+  }
+  DevBuf<double> val;
+  DevBuf<int32_t> head; // facets | dofs | flag
+  if (val.alloc_raw(2 * n + (size_t)n1 * n1) != hipSuccess || head.alloc_raw(n * (2 + ROBIN_ROW)) != hipSuccess)
+    return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
+  std::vector<int32_t> hh(n * (2 + ROBIN_ROW));
+  std::vector<double> hw(n);
+  {
+    HostCall s;
+    const auto d_f = s.in(host ? facets : nullptr, n);
+    const auto d_a = s.in(host ? facet_alpha : nullptr, n);
+    if (host)
+      HIP_TRY(s.upload(stream));
+    int32_t* flist = head.get();
+    hipLaunchKernelGGL(k_robin_prepare, dim3(grid_of(nlist, PS_THREADS)), dim3(PS_THREADS), 0, stream, nlist,
+                       host ? d_f.get() : facets, alpha, host ? d_a.get() : facet_alpha, m.nnodes, m.nfacets, h->space.ne,
+                       m.x, m.facet_nodes, m.facet_cells_off, flist, flist + n, flist + n * (1 + ROBIN_ROW), val.get(),
+                       val.get() + n);
+    s.note(hipGetLastError());
+    s.note(hipMemcpyAsync(val.get() + 2 * n, facet_mass_of(h->p), (size_t)n1 * n1 * sizeof(double),
+                          hipMemcpyHostToDevice, stream));
+    s.note(hipMemcpyAsync(hh.data(), head.get(), hh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    s.note(hipMemcpyAsync(hw.data(), val.get(), n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    s.note(hipStreamSynchronize(stream));
+    HIP_TRY(s.finish(stream));
+  }
+  const int32_t* hd = hh.data() + n;
+  const int32_t* hflag = hh.data() + n * (1 + ROBIN_ROW);
+  if (host)
+  {
+    std::unordered_set<int32_t> seen;
+    for (int32_t i = 0; i < nlist; ++i)
+    {
+      if (hflag[i] != 1)
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is no boundary facet of the mesh", who, (int)i,
+                    (int)facets[i]);
+      if (!seen.insert(facets[i]).second)
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is listed twice", who, (int)i, (int)facets[i]);
+      if (facet_alpha && !(facet_alpha[i] >= 0.0 && std::isfinite(facet_alpha[i])))
+        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facet_alpha[%d] = %g is negative, NaN or infinite", who, (int)i,
+                    facet_alpha[i]);
+    }
+  }
+  // the entries (row, facet, list position, local index), sorted by row, then facet, then position
+  struct Entry
+  {
+    int32_t row, facet, pos, loc;
+  };
+  std::vector<Entry> ent;
+  bool positive = false;
+  for (int32_t i = 0; i < nlist; ++i)
+  {
+    if (hflag[i] != 1)
+      continue; // (device memory space: skipped)
+    positive = positive || hw[(size_t)i] > 0.0;
+    for (int j = 0; j < n1; ++j)
+      ent.push_back(Entry{hd[(size_t)i * ROBIN_ROW + j], hh[(size_t)i], i, j});
+  }
+  std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) {
+    return a.row != b.row ? a.row < b.row : a.facet != b.facet ? a.facet < b.facet : a.pos < b.pos;
+  });
+  const size_t nch = (size_t)((h->ndofs + PS_THREADS - 1) / PS_THREADS);
+  std::vector<int32_t> rows, off, packed(ent.size());
+  for (size_t k = 0; k < ent.size(); ++k)
+  {
+    if (k == 0 || ent[k].row != ent[k - 1].row)
+    {
+      rows.push_back(ent[k].row);
+      off.push_back((int32_t)k);
+    }
+    packed[k] = ent[k].pos * 8 + ent[k].loc;
+  }
+  off.push_back((int32_t)ent.size());
+  std::vector<int32_t> chunk(nch + 1);
+  for (size_t c = 0; c <= nch; ++c)
+    chunk[c] = (int32_t)(std::lower_bound(rows.begin(), rows.end(), (int32_t)std::min<int64_t>((int64_t)c * PS_THREADS,
+                                                                                              INT32_MAX))
+                         - rows.begin());
+  chunk[nch] = (int32_t)rows.size();
+  // one array: facets | dofs | chunk | rows | off | ent
+  const size_t o_chunk = n * (1 + ROBIN_ROW), o_rows = o_chunk + chunk.size(), o_off = o_rows + rows.size(),
+               o_ent = o_off + off.size(), total = o_ent + packed.size();
+  std::vector<int32_t> tab(total);
+  std::copy(hh.begin(), hh.begin() + (std::ptrdiff_t)o_chunk, tab.begin());
+  std::copy(chunk.begin(), chunk.end(), tab.begin() + (std::ptrdiff_t)o_chunk);
+  std::copy(rows.begin(), rows.end(), tab.begin() + (std::ptrdiff_t)o_rows);
+  std::copy(off.begin(), off.end(), tab.begin() + (std::ptrdiff_t)o_off);
+  std::copy(packed.begin(), packed.end(), tab.begin() + (std::ptrdiff_t)o_ent);
+  DevBuf<int32_t> dtab;
+  if (dtab.alloc_raw(total) != hipSuccess)
+    return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
+  HIP_TRY(hipMemcpyAsync(dtab.get(), tab.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream)); // (tab ends with this call; nothing on the stream reads the old table any more)
+  h->robin_tab = std::move(dtab);
+  h->robin_val = std::move(val);
+  h->robin_n = nlist;
+  h->robin_chunk = o_chunk;
+  h->robin_rows = o_rows;
+  h->robin_off = o_off;
+  h->robin_ent = o_ent;
+  h->robin_nent = packed.size();
+  h->has_robin = true;
+  h->robin_pos = positive;
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (host)
+    HIP_TRY(hipStreamSynchronize(stream));
+  return EQLB_OK;
+}
 } // namespace
 
 void primal_level(eqlb_primal* h, SolverLevel& v) { solver_level(h, v); }
@@ -330,6 +589,96 @@ int eqlb_primal_set_diffusion(eqlb_primal_t* h, const double* cell_D, int32_t me
 try
 {
   return eqlb::solver_set_diffusion("eqlb_primal_set_diffusion", h, cell_D, memspace, stream_);
+}
+EQLB_CATCH_ALL
+
+int eqlb_get_facet_mass_table(int32_t p, double* out, int32_t capacity)
+{
+  using namespace eqlb;
+  if (p < 1 || p > PS_PMAX || !out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_facet_mass_table: p = %d outside 1 ... 4, or null output", (int)p);
+  const int n = (p + 1) * (p + 1);
+  if (capacity < n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "eqlb_get_facet_mass_table: capacity too small");
+  const double* t = facet_mass_of(p);
+  for (int i = 0; i < n; ++i)
+    out[i] = t[i];
+  return n;
+}
+
+int eqlb_primal_set_robin(eqlb_primal_t* h, int32_t nlist, const int32_t* facets, double alpha,
+                          const double* facet_alpha, int32_t memspace, void* stream_)
+try
+{
+  return eqlb::primal_set_robin("eqlb_primal_set_robin", h, nlist, facets, alpha, facet_alpha, memspace, stream_);
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_robin_weights(eqlb_primal_t* h, int32_t* nlist, double* w, int32_t capacity, int32_t memspace,
+                              void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* who = "eqlb_primal_robin_weights";
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  const int32_t n = h->has_robin ? h->robin_n : 0;
+  if (nlist)
+    *nlist = n;
+  if (!w || n == 0)
+    return EQLB_OK;
+  if (capacity < n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: capacity = %d is less than the %d listed facets", who, (int)capacity,
+                (int)n);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  HIP_TRY(hipMemcpyAsync(w, h->robin_val.get(), (size_t)n * sizeof(double),
+                         host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+  if (host)
+    HIP_TRY(hipStreamSynchronize(stream));
+  return EQLB_OK;
+}
+EQLB_CATCH_ALL
+
+int eqlb_primal_robin_flux(eqlb_primal_t* h, const double* u, int32_t nq, const double* s, const double* u_ext,
+                           double* out, int32_t memspace, void* stream_)
+try
+{
+  using namespace eqlb;
+  const char* who = "eqlb_primal_robin_flux";
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  if (!u || !s || !out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (nq < 1 || nq > RF_MAX_NQ)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nq = %d outside 1 ... %d", who, (int)nq, RF_MAX_NQ);
+  RobinRule rule{};
+  for (int q = 0; q < nq; ++q)
+  {
+    if (!(s[q] >= 0.0 && s[q] <= 1.0))
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: s[%d] = %g outside [0, 1]", who, q, s[q]);
+    rule.s[q] = s[q];
+  }
+  if (!h->has_robin)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: the handle has no Robin term (eqlb_primal_set_robin first)", who);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const DeviceMesh& m = h->mesh->m;
+  const size_t n = (size_t)h->robin_n, no = n * (size_t)nq;
+  HostCall c;
+  const auto d_u = c.in(host ? u : nullptr, (size_t)h->ndofs);
+  const auto d_e = c.in(host ? u_ext : nullptr, no);
+  const auto d_o = c.out(host ? out : nullptr, no);
+  if (host)
+    HIP_TRY(c.upload(stream));
+  const int32_t* tab = h->robin_tab.get();
+  hipLaunchKernelGGL(k_robin_flux, dim3(grid_of((int64_t)no, PS_THREADS)), dim3(PS_THREADS), 0, stream, h->robin_n, nq,
+                     (int32_t)h->p, rule, tab, tab + n, static_cast<const double*>(h->robin_val.get() + n), m.ncells,
+                     m.cell_nodes, m.cell_facets, m.facet_cells_off, m.facet_cells, host ? d_u.get() : u,
+                     host ? d_e.get() : u_ext, host ? d_o.get() : out);
+  c.note(hipGetLastError());
+  HIP_TRY(c.finish(stream));
+  return EQLB_OK;
 }
 EQLB_CATCH_ALL
 

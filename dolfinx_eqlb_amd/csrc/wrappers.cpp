@@ -397,6 +397,47 @@ struct PrimalPoisson
     }
     check(eqlb_primal_set_diffusion(h, cell_D.is_none() ? nullptr : kd.data(), EQLB_MEM_HOST, nullptr));
   }
+  // the Robin term int alpha u v over the listed boundary facets: facet_alpha [nlist] where given, else the scalar alpha;
+  // an empty list switches the term off
+  void set_robin(carray<int32_t> facets, double alpha, py::object facet_alpha)
+  {
+    carray<double> fa;
+    if (!facet_alpha.is_none())
+    {
+      fa = facet_alpha.cast<carray<double>>();
+      if (fa.size() != facets.size())
+        throw std::runtime_error("PrimalPoisson.set_robin: facet_alpha [nlist] expected");
+    }
+    check(eqlb_primal_set_robin(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, alpha,
+                                !facet_alpha.is_none() && fa.size() ? fa.data() : nullptr, EQLB_MEM_HOST, nullptr));
+  }
+  darray robin_weights() const
+  {
+    int32_t n = 0;
+    check(eqlb_primal_robin_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
+    darray w(n);
+    if (n)
+      check(eqlb_primal_robin_weights(h, &n, w.mutable_data(), n, EQLB_MEM_HOST, nullptr));
+    return w;
+  }
+  // out [nlist, nq] = alpha_i (u_h(x_q) - u_ext[i][q]) on the Robin list at the facet parameters s [nq]
+  darray robin_flux(darray u, darray s, py::object u_ext) const
+  {
+    need(u, "robin_flux");
+    int32_t n = 0;
+    check(eqlb_primal_robin_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
+    darray e;
+    if (!u_ext.is_none())
+    {
+      e = u_ext.cast<darray>();
+      if (e.size() != (py::ssize_t)n * s.size())
+        throw std::runtime_error("PrimalPoisson.robin_flux: u_ext [nlist, nq] expected");
+    }
+    darray out({(py::ssize_t)n, (py::ssize_t)s.size()});
+    check(eqlb_primal_robin_flux(h, u.data(), (int32_t)s.size(), s.data(), u_ext.is_none() ? nullptr : e.data(),
+                                 out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
     if (degree_dg >= 0 && degree_dg <= 3
@@ -1630,6 +1671,14 @@ PYBIND11_MODULE(_cpp, m)
       .def("set_diffusion", &PrimalPoisson::set_diffusion, py::arg("cell_D") = py::none(),
            "the operator becomes -div(coeff D grad u): cell_D [ncells][3] = (d00, d01, d11), symmetric positive "
            "definite per cell; None switches the term off; Multilevel.set_coarse(True) has to be called again afterwards")
+      .def("set_robin", &PrimalPoisson::set_robin, py::arg("facets"), py::arg("alpha") = 1.0,
+           py::arg("facet_alpha") = py::none(),
+           "the operator gains int alpha u v over the listed boundary facets: facet_alpha [nlist] where given, else the "
+           "scalar; an empty list switches the term off; Multilevel.set_coarse(True) has to be called again afterwards")
+      .def("robin_weights", &PrimalPoisson::robin_weights, "w_f = alpha_f |E_f| [nlist] in the order of the list")
+      .def("robin_flux", &PrimalPoisson::robin_flux, py::arg("u"), py::arg("s"), py::arg("u_ext") = py::none(),
+           "out [nlist, nq] = alpha_i (u_h(x_q) - u_ext[i][q]) on the Robin list at the facet parameters s: the point "
+           "values of the flux condition that update_flux_bc takes with vector = False")
       .def("load", &PrimalPoisson::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
            "b [ndofs] from DG_d nodal values rhs_dg [ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalPoisson::apply, py::arg("u"), py::arg("masked") = false, "y = A u; masked: 0 on the fixed rows")

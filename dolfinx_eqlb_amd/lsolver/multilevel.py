@@ -95,7 +95,7 @@ class Hierarchy:
         self._factor = None
         if self.coarse:
             for c in range(self.bs):
-                if not ops[0].fixed[c::self.bs].any():
+                if not ops[0].fixed[c::self.bs].any() and not ops[0].robin_positive():
                     raise ValueError(f"Hierarchy: coarse=True: component {c} of level 0 has no Dirichlet DOF")
 
     @property
@@ -223,7 +223,7 @@ class Hierarchy:
         if not (rtol >= 0.0 and atol >= 0.0):
             raise ValueError(f"pcg: rtol = {rtol}, atol = {atol} negative or NaN")
         for c in range(self.bs):
-            if not op.fixed[c::self.bs].any():
+            if not op.fixed[c::self.bs].any() and not op.robin_positive():
                 raise ValueError("pcg: singular: no Dirichlet DOF")
         u = np.array(u, dtype=np.float64)
         b = np.asarray(b, dtype=np.float64)

@@ -56,6 +56,27 @@ one product on top of the value formed without the term, no fused multiply-add; 
 mu.  The diagonal follows the same rule, the load is unchanged.  mu = 1 without an array switches the term off: the
 operator is then the one of a fresh object, bit for bit; a uniform power of two scales every bit pattern exactly.
 
+THE ROBIN TERM (PoissonOperator.set_robin; eqlb_primal_set_robin, Poisson only): on the listed boundary facets
+-(kappa D grad u) . n = alpha (u - u_ext) with alpha_f >= 0 per facet, one scalar or a list-wise array.  The operator gains
+the boundary mass int_E alpha u v; the datum int_E alpha u_ext v is a load (robin_load).  New table FacetMass<p> [p+1][p+1]
+= int_0^1 l_i l_j ds, l the equispaced 1-D Lagrange basis of degree p in the local order (lower node id, higher node id,
+interior 0 ... p-2 from the lower to the higher node) - the order of the global DOFs lo, hi, nnodes + f (p-1) + j of a
+facet, so no cell is needed to find a facet's rows.  Exact Fractions, each rounded once.  Per listed facet
+  w_f       = alpha_f |E_f|, |E| = sqrt(dx dx + dy dy), dx = x[n1] - x[n0] from facet_nodes, every operation rounded on its
+              own; formed once at set_robin and kept (robin_weights)
+  t_f[i]    = w_f (sum_j FacetMass[i][j] u[dof_j]), ascending j, every product rounded on its own, no fused multiply-add
+  row d     : the owner sum as above, then the t_f[i] of the Robin facets that hold d, in ascending facet id, each by one
+              addition; b_extra, the mask, r = b - v and the inner products behind that are unchanged.  The lifting (u^)
+              reads the free rows of u as 0 in the facet term too
+  diagonal  : the owner sum, then + w_f FacetMass[i][i] in the same place
+  matrix    : + w_f FacetMass[i][j] on entry (d, d') after the cell sums, facets ascending; the pattern holds every pair
+An empty list switches the term off: the operator is then the one of a fresh object, bit for bit; alpha_f = 0 on a listed
+facet is allowed.  Refused by facet, before anything changes: a listed facet that is no boundary facet, a facet listed
+twice, an alpha that is negative, NaN or infinite.  With some alpha_f > 0 the operator is positive definite without a
+fixed DOF, and pcg no longer asks for one.  The owner sum of the load and of the restriction of a hierarchy stays plain.
+robin_flux states eqlb_primal_robin_flux, alpha (u_h - u_ext) at points of the listed facets: the flux condition
+sigma_eq . n of the equilibrator that the discrete solution implies.  Springs on an elasticity operator are not provided.
+
 value_dg states eqlb_primal_value_dg, the piece that turns c u_h into the right-hand side the equilibrator needs
 (rhs = Pi_d f - c_T Pi_d u_h): out[r][c][n] = coeff[c] sum_i PV<p,d>[n][i] u[r][cell_dofs[c][i]], ascending i, every
 product rounded on its own, with PV<p,d> [nd_d][nd_p] the DG_d nodal values of the L2 projection of phi_i onto P_d:
@@ -192,6 +213,135 @@ def value_table_exact(p, d):
 def value_table(p, d):
     """The table [nd_d, nd_p] as doubles, each entry rounded once."""
     return np.array([[float(v) for v in row] for row in value_table_exact(p, d)])
+
+
+def _lagrange_1d_exact(p):
+    """Coefficient lists (ascending powers, Fractions) of the equispaced 1-D Lagrange basis of degree p on [0, 1] in the
+    local order of a facet: the node at 0, the node at 1, then the interior nodes 1/p ... (p-1)/p."""
+    nodes = [Fraction(0), Fraction(1)] + [Fraction(j, p) for j in range(1, p)]
+    out = []
+    for i, xi in enumerate(nodes):
+        c = [Fraction(1)]
+        for k, xk in enumerate(nodes):
+            if k != i:
+                den = xi - xk
+                c = [(c[n - 1] if n else Fraction(0)) / den - (c[n] * xk / den if n < len(c) else Fraction(0))
+                     for n in range(len(c) + 1)]
+        out.append(tuple(c))
+    return tuple(out)
+
+
+@lru_cache(maxsize=None)
+def facet_mass_table_exact(p):
+    """FacetMass [p+1][p+1] Fractions: int_0^1 l_i l_j ds in the local order of a facet (the head of this file)."""
+    if p < 1 or p > 4:
+        raise ValueError(f"facet_mass_table: p = {p} outside 1 ... 4")
+    L = _lagrange_1d_exact(p)
+
+    def integ(a, b):
+        return sum((ca * cb / (m + n + 1) for m, ca in enumerate(a) for n, cb in enumerate(b)), Fraction(0))
+    return tuple(tuple(integ(a, b) for b in L) for a in L)
+
+
+def facet_mass_table(p):
+    """The table [p+1, p+1] as doubles, each entry rounded once."""
+    return np.array([[float(v) for v in row] for row in facet_mass_table_exact(p)])
+
+
+def facet_basis(p, s):
+    """l_i(s) [nq, p+1] of the equispaced 1-D Lagrange basis in the local order of a facet: the product over the other
+    nodes k, in that order, of (s - x_k) / (x_i - x_k) with x = (0, 1, 1/p ... (p-1)/p) formed as j / p in doubles; the
+    first factor starts the product, every operation rounded on its own (the rule of eqlb_primal_robin_flux)."""
+    s = np.asarray(s, dtype=np.float64).ravel()
+    x = [0.0, 1.0] + [j / float(p) for j in range(1, p)]
+    out = np.empty((s.size, p + 1))
+    for i in range(p + 1):
+        v = None
+        for k in range(p + 1):
+            if k != i:
+                fac = (s - x[k]) / (x[i] - x[k])
+                v = fac if v is None else v * fac
+        out[:, i] = v
+    return out
+
+
+def robin_list(who, mesh, facets, alpha=1.0, facet_alpha=None):
+    """(facets int64 [n], alpha [n]) of set_robin in the order given, or (None, None) for an empty list.  Refused by
+    facet: one that is no boundary facet of the mesh, one listed twice, an alpha that is negative, NaN or infinite."""
+    f = np.asarray([] if facets is None else facets, dtype=np.int64).ravel()
+    if facet_alpha is None:
+        a = float(alpha)
+        if not (a >= 0.0 and np.isfinite(a)):
+            raise ValueError(f"{who}: alpha = {a} is negative, NaN or infinite")
+        al = np.full(f.size, a)
+    else:
+        al = np.array(facet_alpha, dtype=np.float64).ravel()
+        if al.size != f.size:
+            raise ValueError(f"{who}: facet_alpha [nlist] expected")
+    fco = mesh.facet_cells_offsets
+    seen = set()
+    for i, v in enumerate(f):
+        v = int(v)
+        if v < 0 or v >= mesh.nfacets or fco[v + 1] - fco[v] != 1:
+            raise ValueError(f"{who}: facets[{i}] = {v} is no boundary facet of the mesh")
+        if v in seen:
+            raise ValueError(f"{who}: facets[{i}] = {v} is listed twice")
+        seen.add(v)
+        if not (al[i] >= 0.0 and np.isfinite(al[i])):
+            raise ValueError(f"{who}: facet_alpha[{i}] = {al[i]} is negative, NaN or infinite")
+    return (None, None) if f.size == 0 else (f, al)
+
+
+def facet_lengths(mesh, facets):
+    """|E_f| = sqrt(dx dx + dy dy), dx = x[n1] - x[n0] from facet_nodes, every operation rounded on its own."""
+    fn = mesh.facet_nodes[np.asarray(facets, dtype=np.int64)]
+    dx = mesh.x[fn[:, 1], 0] - mesh.x[fn[:, 0], 0]
+    dy = mesh.x[fn[:, 1], 1] - mesh.x[fn[:, 0], 1]
+    return np.sqrt(dx * dx + dy * dy)
+
+
+def facet_dofs(mesh, p, facets):
+    """[n, p+1] int64: the rows of a facet in its local order: lower node id, higher node id, nnodes + f (p-1) + j."""
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    fn = mesh.facet_nodes[f].astype(np.int64)
+    cols = [fn.min(axis=1), fn.max(axis=1)] + [mesh.nnodes + f * (p - 1) + j for j in range(p - 1)]
+    return np.stack(cols, axis=1)
+
+
+def robin_load(mesh, p, facets, alpha, u_ext, quadrature_degree=None):
+    """b_extra [ndofs] = int_E alpha u_ext phi_i over the listed boundary facets, on the host: BY DEFINITION
+    neumann_load with g = -alpha u_ext, bit for bit that call.  alpha: a scalar or one value per listed facet; u_ext a
+    callable (x, y) -> values."""
+    from types import SimpleNamespace
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    al = np.broadcast_to(np.asarray(alpha, dtype=np.float64), f.shape)
+    bcs = [SimpleNamespace(facets=[int(v)], scalar=True,
+                           value=(lambda x, y, a=float(a): -a * np.asarray(u_ext(x, y), dtype=np.float64)))
+           for v, a in zip(f, al)]
+    return neumann_load(mesh, p, bcs, quadrature_degree)
+
+
+def robin_flux(mesh, p, facets, facet_alpha, u, s, u_ext=None):
+    """The statement of eqlb_primal_robin_flux: out [n, nq] = alpha_i (u_h(x_q) - u_ext[i][q]) on the listed facets at
+    the facet parameters s [nq] in the frame of eqlb_facet_points;
+    u_h = sum_j l_j(s_q) u[dof_j], ascending j, every product rounded on its own, l of facet_basis; u_ext None: 0."""
+    s = np.asarray(s, dtype=np.float64).ravel()
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    # the frame of eqlb_facet_points: the facet seen from its one cell, the low local vertex first; the facet's own
+    # frame has 0 at the lower node id, so its parameter is s or 1 - s
+    cells = mesh.facet_cells[mesh.facet_cells_offsets[f]]
+    lf = np.argmax(mesh.cell_facets[cells] == f[:, None], axis=1)
+    va, vb = np.where(lf == 0, 1, 0), np.where(lf == 2, 1, 2)
+    rows = np.arange(f.size)
+    same = mesh.cell_nodes[cells][rows, va] < mesh.cell_nodes[cells][rows, vb]
+    B = np.where(same[:, None, None], facet_basis(p, s)[None], facet_basis(p, 1.0 - s)[None])   # [n, nq, p+1]
+    uu = np.asarray(u, dtype=np.float64)[facet_dofs(mesh, p, f)]             # [n, p+1]
+    v = B[:, :, 0] * uu[:, None, 0]
+    for j in range(1, p + 1):
+        v = v + B[:, :, j] * uu[:, None, j]
+    if u_ext is not None:
+        v = v - np.asarray(u_ext, dtype=np.float64).reshape(v.shape)
+    return np.asarray(facet_alpha, dtype=np.float64).ravel()[:, None] * v
 
 
 def value_dg(p, degree_dg, cell_dofs, u, coeff=None, op=None, return_abs=False):
@@ -450,6 +600,52 @@ class PoissonOperator:
         self.fixed = np.zeros(self.ndofs, dtype=bool)
         self._slots()
 
+    # the Robin term (the head of this file): None without it; else the list sorted by facet id
+    robin_f = robin_alpha = robin_w = robin_dofs = None
+    _robin_order = None
+
+    def set_robin(self, facets, alpha=1.0, facet_alpha=None):
+        """The operator gains int alpha u v over the listed boundary facets: alpha_f = facet_alpha [nlist] where given,
+        else the scalar alpha.  An empty list switches the term off; a repeated call replaces the list; a refused one
+        leaves the operator as it was.  A hierarchy with coarse=True has to be built again afterwards."""
+        if self._bs != 1:
+            raise ValueError("set_robin: provided for PoissonOperator only")
+        f, al = robin_list("set_robin", self.mesh, facets, alpha, facet_alpha)
+        if f is None:
+            self.robin_f = self.robin_alpha = self.robin_w = self.robin_dofs = self._robin_order = None
+            return
+        w = al * facet_lengths(self.mesh, f)
+        order = np.argsort(f, kind="stable")
+        self._robin_order = order
+        self.robin_f, self.robin_alpha, self.robin_w = f[order], al[order], w[order]
+        self.robin_dofs = facet_dofs(self.mesh, self.p, self.robin_f)
+
+    def robin_weights(self):
+        """w_f [nlist] in the order of the list given to set_robin (empty without the term)."""
+        if self.robin_f is None:
+            return np.zeros(0)
+        out = np.empty(self.robin_w.size)
+        out[self._robin_order] = self.robin_w
+        return out
+
+    def robin_positive(self):
+        """Whether the term is on with some alpha_f > 0: the operator is then definite without a fixed DOF."""
+        return self.robin_f is not None and bool((self.robin_alpha > 0.0).any())
+
+    def _add_robin(self, y, u, A=None):
+        """y (and A, the absolute sums) with the facet values t_f[i] added, facets ascending, one addition each."""
+        if self.robin_f is None:
+            return y, A
+        FM = facet_mass_table(self.p)
+        t, tA = _sum_products(FM, np.asarray(u, dtype=np.float64)[self.robin_dofs])
+        t, tA = self.robin_w[:, None] * t, self.robin_w[:, None] * tA
+        for k in range(self.robin_f.size):          # (a row lies in several facets: one after the other)
+            d = self.robin_dofs[k]
+            y[d] = y[d] + t[k]
+            if A is not None:
+                A[d] = A[d] + tA[k]
+        return y, A
+
     def _slots(self):
         """slot lists of the owner sum: for every vertex and facet DOF the flat indices c * nd + i of its y_loc entries
         in the order of the node -> cell / facet -> cell table; the local index comes from matching ids."""
@@ -567,6 +763,7 @@ class PoissonOperator:
             A = self.owner_sum(Al)
         else:
             y, A = self.owner_sum(self.cell_product(u)), None
+        y, A = self._add_robin(y, u, A)
         if masked:
             y[self.fixed] = 0.0
         return (y, A) if return_abs else y
@@ -592,8 +789,14 @@ class PoissonOperator:
         val, A = self._combine(t, self.w, [np.abs(x) for x in t])
         md = np.broadcast_to(np.diagonal(self.Mass)[None, :], (self.mesh.ncells, self.nd))
         val, A = self._add_reaction(val, A, md, md)
-        d = self.owner_sum(val)
-        return (d, self.owner_sum(A)) if return_abs else d
+        d, dA = self.owner_sum(val), self.owner_sum(A)
+        if self.robin_f is not None:
+            fm = np.diagonal(facet_mass_table(self.p))
+            for k in range(self.robin_f.size):
+                rows = self.robin_dofs[k]
+                d[rows] = d[rows] + self.robin_w[k] * fm
+                dA[rows] = dA[rows] + self.robin_w[k] * fm
+        return (d, dA) if return_abs else d
 
     # ---- the assembled matrix (the head of this file) ----
     _bs = 1
@@ -651,6 +854,14 @@ class PoissonOperator:
         if ni:
             q = np.arange(self.mesh.ncells * ni)
             add(self.nshared + q, q // ni, 3 * self.p + q % ni)
+        if self.robin_f is not None:
+            FM = facet_mass_table(self.p)
+            for k in range(self.robin_f.size):
+                rows = self.robin_dofs[k]
+                pos = np.searchsorted(skey, rows[:, None] * n + rows[None, :])
+                e = self.robin_w[k] * FM
+                V[pos, 0, 0] = V[pos, 0, 0] + e
+                VA[pos, 0, 0] = VA[pos, 0, 0] + e
         # the blocked layout: row bs d + r holds the columns bs d' + s, s fastest
         length = np.diff(sptr)
         rows = np.arange(bs * n)
@@ -700,7 +911,7 @@ class PoissonOperator:
             raise ValueError(f"pcg: maxit = {maxit}")
         if not (rtol >= 0.0 and atol >= 0.0):
             raise ValueError(f"pcg: rtol = {rtol}, atol = {atol} negative or NaN")
-        if not self.fixed.any():
+        if not self.fixed.any() and not self.robin_positive():
             raise ValueError("pcg: singular: no Dirichlet DOF")
         u = np.array(u, dtype=np.float64)
         b = np.asarray(b, dtype=np.float64)

@@ -20,7 +20,7 @@ With every cell marked this is the longest-edge 4-split, not a red refinement.
 
 Between the facets of the two meshes: parent_facets (eqlb_refine_parent_facets), and from it carry_facet_types
 (eqlb_refine_facet_types: the type table of the equilibrator on the refined mesh) and its inverse for facet lists,
-child_facets (eqlb_refine_child_facets).
+child_facets (eqlb_refine_child_facets); carry_robin_list states Refinement.carry_robin on top of it.
 """
 
 import numpy as np
@@ -179,3 +179,16 @@ def child_facets(mesh, node_parent_facet, mesh2, facets=None):
     first = np.where(cut, find(lo, np.where(cut, m, hi)), find(lo, hi))
     second = np.where(cut, find(np.where(cut, m, lo), hi), -1)
     return np.stack([first, second], axis=1).astype(np.int32)
+
+
+def carry_robin_list(mesh, node_parent_facet, mesh2, facets, facet_alpha):
+    """(facets2 int32, facet_alpha2) of a Robin list (PoissonOperator.set_robin) on the refined mesh `mesh2` - the
+    statement of Refinement.carry_robin: the children of every listed facet through child_facets, in the order of the
+    list, first child first, the -1 of an unbisected facet left out; a child takes its parent's alpha."""
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    a = np.asarray(facet_alpha, dtype=np.float64).ravel()
+    if a.size != f.size:
+        raise ValueError("carry_robin_list: facet_alpha [nlist] expected")
+    ch = child_facets(mesh, node_parent_facet, mesh2, f)
+    keep = ch >= 0
+    return ch[keep].astype(np.int32), np.repeat(a[:, None], 2, axis=1)[keep]

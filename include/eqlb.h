@@ -1018,6 +1018,60 @@ void eqlb_refine_destroy(eqlb_refine_t* plan);
  *   device memory space      the array is taken as it is, nothing waits (but for the first allocation)
  * D is cell-wise constant data: it crosses a refinement through eqlb_refine_prolong_dg at degree 0 with bs = 3, nrhs = 1
  * on the array as it is ([ncells][3] is the layout x[bs dof + cb] of DG_0 data with three components).
+ *
+ * THE ROBIN TERM: eqlb_primal_set_robin states -(kappa D grad u) . n = alpha (u - u_ext) on the listed boundary facets,
+ * alpha_f >= 0 per facet - convection to an ambient temperature, a leaky boundary, a penalised Dirichlet side.  The
+ * operator gains the boundary mass int_E alpha u v; the datum int_E alpha u_ext v is a load (b_extra;
+ * lsolver.robin_load).  Poisson handles only: springs on an elasticity handle are not provided.
+ *   table      FacetMass<p> [p+1][p+1] = int_0^1 l_i l_j ds (eqlb_get_facet_mass_table), l the equispaced 1-D Lagrange
+ *              basis of degree p in the local order (lower node id, higher node id, interior 0 ... p-2 from the lower to
+ *              the higher node) - the order of the global DOFs lo, hi, nnodes + f (p-1) + j of facet f, so no cell is
+ *              needed to find a facet's rows.  Exact Fractions, each rounded once
+ *   weight     w_f = alpha_f |E_f|, |E| = sqrt(dx dx + dy dy), dx = x[n1] - x[n0] from facet_nodes, every operation
+ *              rounded on its own (a correctly rounded square root); formed once at set_robin and kept
+ *              (eqlb_primal_robin_weights)
+ *   facet      t_f[i] = w_f (sum_j FacetMass[i][j] u[dof_j]), ascending j, the first product starts the sum, products
+ *              rounded one by one, no fused multiply-add
+ *   row d      the owner sum as above; then the t_f[i] of the Robin facets that hold d are added in ascending facet id,
+ *              each by one addition.  Everything behind that is unchanged: b_extra, the mask, r = b - v, the fused inner
+ *              products.  The lifting (the reference norm: u^) reads the free rows of u as 0 in the facet term too
+ *   diagonal   the owner sum, then + w_f FacetMass[i][i] in the same place
+ *   matrix     eqlb_primal_matrix_values adds w_f FacetMass[i][j] to entry (d, d') after the cell sums, facets
+ *              ascending; the pattern already holds every such pair, the raw diagonal keeps the bits of the diagonal;
+ *              eliminate acts as before
+ * The term is formed inside the sum pass (no further launch per product, no atomics); a handle without it launches the
+ * kernels it launched before.  The owner sum of eqlb_primal_load and of the restriction of a hierarchy stays the plain
+ * one: a Robin handle inside a hierarchy restricts exactly as before.  apply, apply_many, diagonal, residual, solve,
+ * solve_many, matrix_values and a hierarchy that holds the handle (BPX, local, coarse, the _many forms) carry the term.
+ *   nlist = 0                switches the term off: the operator is the one of a fresh handle, bit for bit
+ *   facet_alpha == NULL      the scalar alpha on every listed facet; else facet_alpha [nlist] in `memspace`.  alpha_f = 0
+ *                            on a listed facet is allowed.  A repeated call replaces list and coefficients
+ *   diagonal                 formed again in place on `stream`; the dense factor of eqlb_hierarchy_set_coarse is a
+ *                            SNAPSHOT: call eqlb_hierarchy_set_coarse(.., 1, ..) again after the term of level 0 changes
+ *   no Dirichlet DOF         with the term on and some w_f > 0 the operator is positive definite without a fixed DOF:
+ *                            eqlb_primal_solve, _solve_many, eqlb_hierarchy_solve[_many] and eqlb_hierarchy_set_coarse no
+ *                            longer refuse such a handle as singular (every handle without the term is refused as
+ *                            before; the pivot test of the coarse factor stays)
+ *   host memory space        refused with EQLB_ERR_INVALID_ARGUMENT by facet, in the order of the list, before anything
+ *                            changes: a listed facet that is no boundary facet of the mesh, a facet listed twice, an alpha
+ *                            (the scalar, or facet_alpha[i]) that is negative, NaN or infinite
+ *   device memory space      list and coefficients are the caller's responsibility: an id that is no boundary facet is
+ *                            skipped (weight 0, no row), nothing is read out of range; the scalar is checked as above
+ *   both                     the table that lets a row find its facets is built on the host from the O(sqrt N) listed
+ *                            facets: the call waits for `stream`
+ * eqlb_primal_robin_weights: *nlist (HOST, or NULL) receives the number of listed facets, w [capacity >= nlist] in
+ * `memspace` (or NULL: the count only) the weights in the order of the list.
+ * eqlb_primal_robin_flux: THE FLUX CONDITION OF THE EQUILIBRATOR that the discrete solution implies,
+ *   out[i][q] = alpha_i (u_h(x_q) - u_ext[i][q]),   out, u_ext [nlist][nq] in `memspace`, u_ext NULL = 0, u [ndofs],
+ * on the handle's list at the facet parameters s [nq] (HOST array, 1 <= nq <= 64, 0 <= s <= 1) in the frame of
+ * eqlb_facet_points.  One thread per (facet, point).  The parameter in the facet's own frame (0 at the lower node id) is
+ * s or 1 - s; l_j is the product over the other nodes k, in the local order, of (s - x_k) / (x_j - x_k) with x = (0, 1,
+ * 1/p ... (p-1)/p) formed as j / p, the first factor starts it; u_h = sum_j l_j u[dof_j], ascending j, the first
+ * product starts it; no fused multiply-add: bit for bit lsolver.primal.robin_flux.  A facet the list skipped gives NaN.
+ * Its output is what eqlb_se_update_flux_bc / eqlb_ev_update_flux_bc take with nq >= 1, vector = 0 on facets of type
+ * EQLB_FACET_ESSNT_DUAL: the flux conditions of a Robin problem follow u_h on the device without rebuilding a patch.
+ * Errors: null handle or argument, nq or s out of range, unknown memory space, a handle without the term:
+ * EQLB_ERR_INVALID_ARGUMENT.
  */
 typedef struct eqlb_primal eqlb_primal_t;
 int eqlb_get_stiffness_table(int32_t p, double* out, int32_t capacity);
@@ -1029,6 +1083,13 @@ int eqlb_primal_ndofs(const eqlb_primal_t* handle, int64_t* ndofs);
 int eqlb_get_mass_table(int32_t p, double* out, int32_t capacity);
 int eqlb_primal_set_reaction(eqlb_primal_t* handle, double c, const double* cell_c, int32_t memspace, void* stream);
 int eqlb_primal_set_diffusion(eqlb_primal_t* handle, const double* cell_D, int32_t memspace, void* stream);
+int eqlb_get_facet_mass_table(int32_t p, double* out, int32_t capacity);
+int eqlb_primal_set_robin(eqlb_primal_t* handle, int32_t nlist, const int32_t* facets, double alpha,
+                          const double* facet_alpha, int32_t memspace, void* stream);
+int eqlb_primal_robin_weights(eqlb_primal_t* handle, int32_t* nlist, double* w, int32_t capacity, int32_t memspace,
+                              void* stream);
+int eqlb_primal_robin_flux(eqlb_primal_t* handle, const double* u, int32_t nq, const double* s, const double* u_ext,
+                           double* out, int32_t memspace, void* stream);
 
 /* Fixed are the vertex and facet DOFs of the listed facets [nlist] (the lists eqlb_refine_child_facets carries across
  * a refinement); a repeated call replaces the mask, nlist = 0 clears it.  A facet id outside the mesh: host memory

@@ -476,6 +476,20 @@ def emit(path):
                      + ", ".join(repr(float(v)) for m in t for row in m for v in row) + "};")
         lines.append("};")
     lines.append("")
+    from dolfinx_eqlb_amd.lsolver.primal import facet_mass_table_exact
+    lines.append("// mass of the trace of P_p on a facet of unit length: FM[i][j] = int_0^1 l_i l_j ds, l the equispaced 1-D Lagrange")
+    lines.append("// basis in the local order (lower node id, higher node id, interior 0 ... p-2 from the lower to the higher node);")
+    lines.append("// the Robin term of eqlb_primal_set_robin (lsolver/primal.py: facet_mass_table_exact)")
+    lines.append("template <int P> struct FacetMass;")
+    for p in range(1, 5):
+        t = facet_mass_table_exact(p)
+        n = len(t)
+        lines.append(f"template <> struct FacetMass<{p}> {{")
+        lines.append(f"  static constexpr int N = {n};")
+        lines.append(f"  static constexpr double FM[{n * n}] = {{"
+                     + ", ".join(repr(float(v)) for row in t for v in row) + "};")
+        lines.append("};")
+    lines.append("")
     lines.append("// reference facet normals of the RT functionals (e_raviart_thomas.py:82) and whether the")
     lines.append("// functional measures the outward flux")
     lines.append("static constexpr double NREF[3][2] = {{-1.0, -1.0}, {-1.0, 0.0}, {0.0, 1.0}};")
