@@ -567,20 +567,7 @@ static int estimate_weighted_call(const char* who, eqlb_mesh_t* mesh, int32_t k,
                                   double* facet_jump, int32_t memspace, void* stream, double alpha, double beta)
 {
   if (mesh && memspace == EQLB_MEM_HOST)
-    for (int32_t i = 0; i < mesh->m.ncells; ++i)
-    {
-      if (cell_coeff && !(cell_coeff[i] > 0.0 && std::isfinite(cell_coeff[i])))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_coeff[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
-                    cell_coeff[i]);
-      if (!cell_D)
-        continue;
-      const double d00 = cell_D[3 * i], d01 = cell_D[3 * i + 1], d11 = cell_D[3 * i + 2];
-      if (!(std::isfinite(d00) && std::isfinite(d01) && std::isfinite(d11)))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not finite", who, (int)i, d00, d01, d11);
-      if (!(d00 > 0.0 && d00 * d11 - d01 * d01 > 0.0))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not positive definite", who, (int)i, d00,
-                    d01, d11);
-    }
+    EQLB_TRY(eqlb::check_cells(who, mesh->m.ncells, {{eqlb::CELL_COEFF, cell_coeff}, {eqlb::CELL_D, cell_D}}));
   const eqlb::EstWeightArgs weight{cell_coeff, cell_D};
   return estimate_impl(mesh, k, degree_dg, nrhs, flux, flux_dg, rhs_dg, cell_div2, cell_sig2, facet_jump, memspace,
                        stream, alpha, beta, (cell_coeff || cell_D) ? &weight : nullptr);
@@ -616,14 +603,7 @@ static int estimate_stress_call(const char* who, eqlb_mesh_t* mesh, int32_t k, c
   const eqlb::DeviceMesh& m = mesh->m;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (co && memspace == EQLB_MEM_HOST)
-    for (int32_t i = 0; i < m.ncells; ++i)
-    {
-      if (co->cell_mu && !(co->cell_mu[i] > 0.0 && std::isfinite(co->cell_mu[i])))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
-                    co->cell_mu[i]);
-      if (co->cell_pi1 && !(co->cell_pi1[i] > -1.0))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_pi1[%d] = %g is not above -1", who, (int)i, co->cell_pi1[i]);
-    }
+    EQLB_TRY(eqlb::check_cells(who, m.ncells, {{eqlb::CELL_MU, co->cell_mu}, {eqlb::CELL_PI1, co->cell_pi1}}));
   const int32_t* node_cells = nullptr; // (first use from several threads: the handle's lock is taken there)
   if (node_asym && eqlb::mesh_node_cells(mesh, &node_cells))
     return fail(EQLB_ERR_DEVICE, "%s: device allocation failed", who);
@@ -664,8 +644,8 @@ int eqlb_se_estimate_stress_mu(eqlb_mesh_t* mesh, int32_t k, const double* flux_
                                double* cell_wsym, double* node_asym, int32_t memspace, void* stream)
 {
   const char* who = "eqlb_se_estimate_stress_mu";
-  if (!cell_mu && !(mu > 0.0 && std::isfinite(mu)))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: mu = %g is zero, negative, NaN or infinite", who, mu);
+  if (!cell_mu)
+    EQLB_TRY(eqlb::check_scalar(who, "mu", *eqlb::CELL_MU.rule, mu));
   const eqlb::StressCoeffArgs co{cell_pi1, cell_mu, pi_1, mu};
   const bool plain = !cell_pi1 && !cell_mu && mu == 1.0; // the kernel of eqlb_se_estimate_stress
   return estimate_stress_call(who, mesh, k, flux_hdiv, korn, cell_pi1 ? 0.0 : pi_1, plain ? nullptr : &co, cell_energy,

@@ -1,7 +1,8 @@
 // Host helpers of every translation unit that allocates device memory or stages a host-memory call: error return,
 // the owners of device memory (DevBuf, DevCarve, StreamBuf - no other file names the allocator) and of events and
 // streams (DevEvent, DevStream - no other file creates or destroys one), the staged host call (HostCall), the exception
-// barrier of the entry points, set-up profiling.  Host code only.  Included
+// barrier of the entry points, set-up profiling, and the coefficient rules of eqlb_cell_coeff.h (which it includes) as
+// refusals of an entry point.  Host code only.  Included
 //   through eqlb_mesh_handle.h (the units that dereference a mesh handle)
 //     and eqlb_handle.h by eqlb_api.hip, eqlb_boundary_setup.hip, eqlb_boundary_update.hip, eqlb_sweep.hip,
 //       eqlb_tiling_host.hip, eqlb_bc_carry.hip,
@@ -12,6 +13,7 @@
 //   directly by eqlb_tiling_device.hip, eqlb_halo_rccl.hip.
 #pragma once
 
+#include "eqlb_cell_coeff.h"
 #include "eqlb_internal.h"
 
 #include <chrono>
@@ -19,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <initializer_list>
 #include <new>
 #include <utility>
 #include <vector>
@@ -148,6 +151,48 @@ inline int check_memspace(const char* who, int32_t memspace)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: unknown memory space", who);
   return EQLB_OK;
 }
+
+// ---- the coefficient rules of eqlb_cell_coeff.h as refusals of an entry point ---------------------------------------
+namespace
+{
+// entry i of a breaks the rule of c
+inline int fail_cell(const char* who, const CellCoeff& c, const double* a, long long i)
+{
+  char msg[256];
+  format_cell(msg, sizeof(msg), who, c, a, i);
+  return fail(EQLB_ERR_INVALID_ARGUMENT, "%s", msg);
+}
+
+// a scalar, checked where no array takes its place
+inline int check_scalar(const char* who, const char* name, const ScalarRule& rule, double x)
+{
+  if (rule.ok(x))
+    return EQLB_OK;
+  char msg[256];
+  format_scalar(msg, sizeof(msg), who, name, rule, x);
+  return fail(EQLB_ERR_INVALID_ARGUMENT, "%s", msg);
+}
+
+// HOST arrays of n cells (nullptr: not given): the first CELL that breaks a rule is refused, and within it the array
+// that stands first
+struct CellArray
+{
+  const CellCoeff& coeff;
+  const double* a;
+};
+inline int check_cells(const char* who, long long n, std::initializer_list<CellArray> arrays)
+{
+  const CellArray* worst = nullptr;
+  long long at = n;
+  for (const CellArray& x : arrays)
+    if (const long long i = x.a ? x.coeff.first_bad(x.a, at) : -1; i >= 0)
+    {
+      worst = &x;
+      at = i; // (the arrays behind this one are read up to this cell only)
+    }
+  return worst ? fail_cell(who, worst->coeff, worst->a, at) : EQLB_OK;
+}
+} // namespace
 
 // One device allocation carved into typed pieces: declare the pieces, alloc() once, read the pointers back from the
 // pieces.  Every piece starts on a multiple of 256 bytes; one of length zero is allowed.  Not movable (the pieces

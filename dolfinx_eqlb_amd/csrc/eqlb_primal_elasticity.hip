@@ -34,11 +34,7 @@
 struct eqlb_elasticity : eqlb::SolverHandle<2, 1>
 {
   double pi_1 = 1.0;
-  // the shear modulus (solver_set_shear): off (mu = 1) as created.  The cell array is allocated by the first call that
-  // brings one and kept; shear_cell says whether the kernels read it or the scalar
-  bool has_shear = false, shear_cell = false;
-  double shear_mu = 1.0;
-  eqlb::DevBuf<double> shear;
+  eqlb::CellTerm shear{eqlb::SHEAR}; // the shear modulus (solver_set_cell_term): off (mu = 1) as created
 };
 
 namespace eqlb
@@ -154,9 +150,9 @@ hipError_t launch_cell(const eqlb_elasticity& h, const ManyCols& c, int d, const
   a.only_fixed = only_fixed ? 1 : 0;
   a.yloc = h.yloc;
   a.st = c.check ? c.st : nullptr;
-  const ReactArgs rx = react_args(h);
-  const ShearArgs sx{h.shear_cell ? h.shear.get() : nullptr, h.shear_mu};
-  return launch_cell<MODE>(h.p, d, a, h.has_react ? &rx : nullptr, h.has_shear ? &sx : nullptr, stream);
+  const ReactArgs rx = react_args(h.react);
+  const ShearArgs sx = shear_args(h.shear);
+  return launch_cell<MODE>(h.p, d, a, h.react.on ? &rx : nullptr, h.shear.on ? &sx : nullptr, stream);
 }
 } // namespace
 
@@ -165,9 +161,8 @@ void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v)
 {
   solver_matrix_view(h, v);
   v.pi_1 = h->pi_1;
-  v.has_shear = h->has_shear;
-  v.shear_cell = h->shear_cell ? h->shear.get() : nullptr;
-  v.shear_mu = h->shear_mu;
+  v.has_shear = h->shear.on;
+  v.sx = shear_args(h->shear);
 }
 } // namespace eqlb
 
@@ -219,14 +214,16 @@ EQLB_CATCH_ALL
 int eqlb_elasticity_set_reaction(eqlb_elasticity_t* h, double c, const double* cell_c, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::solver_set_reaction("eqlb_elasticity_set_reaction", h, c, cell_c, memspace, stream_);
+  return eqlb::solver_set_cell_term("eqlb_elasticity_set_reaction", h, eqlb::REACTION, &eqlb_elasticity::react, c,
+                                    cell_c, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
 int eqlb_elasticity_set_shear(eqlb_elasticity_t* h, double mu, const double* cell_mu, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::solver_set_shear("eqlb_elasticity_set_shear", h, mu, cell_mu, memspace, stream_);
+  return eqlb::solver_set_cell_term("eqlb_elasticity_set_shear", h, eqlb::SHEAR, &eqlb_elasticity::shear, mu, cell_mu,
+                                    memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -299,8 +299,7 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
   EQLB_TRY(check_memspace(who, memspace));
   if (shear && !shear->cell_mu)
   {
-    if (!(shear->mu > 0.0 && std::isfinite(shear->mu)))
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: mu = %g is zero, negative, NaN or infinite", who, shear->mu);
+    EQLB_TRY(check_scalar(who, "mu", *CELL_MU.rule, shear->mu));
     if (shear->mu == 1.0)
       shear = nullptr; // the kernel without the term
   }
@@ -315,21 +314,8 @@ static int primal_flux_call(const char* who, eqlb_mesh_t* mesh, int32_t p, int32
                                             flux_dg, shear, cell_D ? &tx : nullptr, stream);
     return e == hipSuccess ? EQLB_OK : fail(EQLB_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
   }
-  if (shear && shear->cell_mu)
-    for (int32_t i = 0; i < ncells; ++i)
-      if (!(shear->cell_mu[i] > 0.0 && std::isfinite(shear->cell_mu[i])))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%d] = %g is zero, negative, NaN or infinite", who, (int)i,
-                    shear->cell_mu[i]);
-  if (cell_D)
-    for (int32_t i = 0; i < ncells; ++i)
-    {
-      const double d00 = cell_D[3 * i], d01 = cell_D[3 * i + 1], d11 = cell_D[3 * i + 2];
-      if (!(std::isfinite(d00) && std::isfinite(d01) && std::isfinite(d11)))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not finite", who, (int)i, d00, d01, d11);
-      if (!(d00 > 0.0 && d00 * d11 - d01 * d01 > 0.0))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%d] = (%g, %g, %g) is not positive definite", who, (int)i, d00,
-                    d01, d11);
-    }
+  EQLB_TRY(check_cells(who, ncells, {{CELL_MU, shear ? shear->cell_mu : nullptr}}));
+  EQLB_TRY(check_cells(who, ncells, {{CELL_D, cell_D}}));
   // host memory: bad tables are caught here, before anything is launched
   const size_t nidx = (size_t)ncells * np;
   for (size_t i = 0; i < nidx; ++i)

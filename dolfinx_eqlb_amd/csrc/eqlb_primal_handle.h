@@ -20,7 +20,6 @@
 #include "eqlb_primal_common.h"
 
 #include <climits>
-#include <cmath>
 #include <memory>
 
 namespace eqlb
@@ -38,30 +37,6 @@ struct MatrixPattern
   DevBuf<int32_t> srow, scol; // [snnz] the DOFs of a pair
   size_t peak_bytes = 0;      // device memory at the peak of the build, the kept arrays included
 };
-
-// A solver handle as eqlb_primal_matrix.hip sees it: a view that owns nothing, all pointers DEVICE.  coeff: kappa
-// (bs = 1) or pi_1 (bs = 2) per cell, or nullptr (1, or the scalar pi_1)
-struct MatrixView
-{
-  int bs = 1, p = 0, nd = 0;
-  int64_t ndofs = 0;
-  int32_t nnodes = 0, nfacets = 0, ncells = 0, ne = 0, ni = 1;
-  const int32_t *nco = nullptr, *fco = nullptr, *slots = nullptr, *cell_dofs = nullptr;
-  const double *cellJ = nullptr, *coeff = nullptr;
-  double pi_1 = 1.0;
-  bool has_react = false, has_shear = false, has_diff = false;
-  const double *react_cell = nullptr, *shear_cell = nullptr, *diff = nullptr;
-  double react_c = 0.0, shear_mu = 1.0;
-  const uint8_t* fixed = nullptr;
-  MatrixPattern* pattern = nullptr;
-  // the Robin term (bs = 1), the table of RobinArgs (eqlb_primal_common.h): m rows lie in a Robin facet
-  bool has_robin = false;
-  int32_t robin_m = 0, robin_n1 = 0;
-  const int32_t *robin_rows = nullptr, *robin_off = nullptr, *robin_ent = nullptr, *robin_dofs = nullptr;
-  const double *robin_w = nullptr, *robin_fm = nullptr;
-};
-void primal_matrix_view(eqlb_primal* h, MatrixView& v);         // eqlb_primal_solve.hip
-void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v); // eqlb_primal_elasticity.hip
 
 namespace
 {
@@ -87,6 +62,71 @@ struct DiffArgs
 {
   const double* cell_D = nullptr; // [ncells][3]
 };
+} // namespace
+
+// A solver handle as eqlb_primal_matrix.hip sees it: a view that owns nothing, all pointers DEVICE.  coeff: kappa
+// (bs = 1) or pi_1 (bs = 2) per cell, or nullptr (1, or the scalar pi_1).  The space and the terms come as the kernel
+// arguments the handle hands out (the same plain structs in every unit that sees the view)
+struct MatrixView
+{
+  int bs = 1, p = 0;
+  SpaceArgs s{};
+  const int32_t* cell_dofs = nullptr;
+  const double *cellJ = nullptr, *coeff = nullptr;
+  double pi_1 = 1.0;
+  bool has_react = false, has_shear = false, has_diff = false;
+  ReactArgs rx;
+  ShearArgs sx;
+  DiffArgs dx;
+  const uint8_t* fixed = nullptr;
+  MatrixPattern* pattern = nullptr;
+  // the Robin term (bs = 1), the table of a sum pass on the diagonal: robin_m rows lie in a Robin facet
+  bool has_robin = false;
+  int32_t robin_m = 0;
+  RobinArgs robin{};
+};
+void primal_matrix_view(eqlb_primal* h, MatrixView& v);         // eqlb_primal_solve.hip
+void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v); // eqlb_primal_elasticity.hip
+
+namespace
+{
+// A per-cell term of a handle as its setter needs it (solver_set_cell_term): the array with its name and rule
+// (eqlb_cell_coeff.h; its width follows from the rule), the name of the scalar in messages (nullptr: the term has
+// none) and the scalar's neutral value, which without an array switches the term off
+struct CellTermSpec
+{
+  CellCoeff array;
+  const char* scalar;
+  double neutral;
+};
+constexpr CellTermSpec REACTION{CELL_C, "c", 0.0}, SHEAR{CELL_MU, "mu", 1.0}, DIFFUSION{CELL_D, nullptr, 0.0};
+
+// ... and as the handle holds it: off as created.  The array is allocated by the first call that brings one and kept;
+// `cell` says whether the kernels read it or the scalar.  The kernel arguments are handed out below
+struct CellTerm
+{
+  bool on = false, cell = false;
+  double scalar;
+  DevBuf<double> buf;
+  explicit CellTerm(const CellTermSpec& d) : scalar(d.neutral) {}
+  const double* array() const { return cell ? buf.get() : nullptr; }
+};
+inline ReactArgs react_args(const CellTerm& t) { return ReactArgs{t.array(), t.scalar}; }
+inline ShearArgs shear_args(const CellTerm& t) { return ShearArgs{t.array(), t.scalar}; }
+inline DiffArgs diff_args(const CellTerm& t) { return DiffArgs{t.array()}; }
+
+// where the pieces of a handle's Robin table lie: facets [n] | dofs [n][ROBIN_ROW] | chunk | rows [m] | off [m + 1] |
+// ent, from the piece sizes
+struct RobinLayout
+{
+  size_t dofs = 0, chunk = 0, rows = 0, off = 0, ent = 0, total = 0;
+  RobinLayout() = default;
+  RobinLayout(size_t n, size_t nchunk, size_t m, size_t nent)
+      : dofs(n), chunk(n * (1 + ROBIN_ROW)), rows(chunk + nchunk), off(rows + m), ent(off + m + 1), total(ent + nent)
+  {
+  }
+  size_t m() const { return off - rows; }
+};
 
 // what eqlb_primal_t and eqlb_elasticity_t share; everything but the grown work space is carved out of one allocation at
 // create
@@ -109,31 +149,18 @@ struct SolverHandle
   // the work space for 2 ... max_cols columns (wide.R of them): grown by the first call that needs it, then reused
   DevBuf<char> wide_mem;
   PcgWork wide{};
-  // the reaction term (solver_set_reaction): off as created.  The cell array is allocated by the first call that
-  // brings one and kept; react_cell says whether the kernels read it or the scalar
-  bool has_react = false, react_cell = false;
-  double react_c = 0.0;
-  DevBuf<double> react;
-  // the diffusion tensor (solver_set_diffusion, the Poisson unit): off as created.  The array [ncells][3] is allocated by
-  // the first call that brings one and kept; has_diff says whether the kernels read it
-  bool has_diff = false;
-  DevBuf<double> diff;
+  // the reaction term and, for the Poisson unit, the diffusion tensor (solver_set_cell_term)
+  CellTerm react{REACTION}, diff{DIFFUSION};
   // the Robin term (eqlb_primal_set_robin, the Poisson unit): off as created.  Both arrays are allocated by a call that
   // brings a list and replaced as a whole by the next one
   bool has_robin = false, robin_pos = false; // robin_pos: some w_f > 0 - the operator is definite without a fixed DOF
   int32_t robin_n = 0;                       // listed facets
-  DevBuf<int32_t> robin_tab;                 // facets [n] | dofs [n][ROBIN_ROW] | chunk | rows | off | ent
+  DevBuf<int32_t> robin_tab;                 // the pieces of RobinLayout ...
+  RobinLayout robin_at;                      // ... and where they lie
   DevBuf<double> robin_val;                  // w [n] | alpha [n] | FacetMass<p> [(p + 1)^2]
-  size_t robin_chunk = 0, robin_rows = 0, robin_off = 0, robin_ent = 0, robin_nent = 0; // positions in robin_tab
   // the CSR pattern of the operator (eqlb_primal_matrix.hip): empty until eqlb_*_matrix_pattern
   MatrixPattern pattern;
 };
-
-template <class H>
-ReactArgs react_args(const H& h)
-{
-  return ReactArgs{h.react_cell ? h.react.get() : nullptr, h.react_c};
-}
 
 constexpr int STATUS_WORDS = 4;
 
@@ -192,14 +219,14 @@ RobinArgs robin_args(const H& h, const double* u, bool only_fixed)
 {
   RobinArgs x{};
   const int32_t* tab = h.robin_tab.get();
-  const size_t n = (size_t)h.robin_n;
-  x.dofs = tab + n;
-  x.chunk = tab + h.robin_chunk;
-  x.rows = tab + h.robin_rows;
-  x.off = tab + h.robin_off;
-  x.ent = tab + h.robin_ent;
+  const RobinLayout& at = h.robin_at;
+  x.dofs = tab + at.dofs;
+  x.chunk = tab + at.chunk;
+  x.rows = tab + at.rows;
+  x.off = tab + at.off;
+  x.ent = tab + at.ent;
   x.w = h.robin_val.get();
-  x.fm = h.robin_val.get() + 2 * n;
+  x.fm = h.robin_val.get() + 2 * (size_t)h.robin_n;
   x.u = u;
   x.fixed = h.fixed;
   x.only_fixed = only_fixed ? 1 : 0;
@@ -337,42 +364,24 @@ template <class H>
 void solver_matrix_view(H* h, MatrixView& v)
 {
   v = MatrixView{};
-  const SpaceArgs& s = h->space;
   v.bs = H::bs;
   v.p = h->p;
-  v.nd = h->nd;
-  v.ndofs = h->ndofs;
-  v.nnodes = s.nnodes;
-  v.nfacets = s.nfacets;
-  v.ncells = s.ncells;
-  v.ne = s.ne;
-  v.ni = s.ni;
-  v.nco = s.nco;
-  v.fco = s.fco;
-  v.slots = s.slots;
+  v.s = h->space;
   v.cell_dofs = h->cell_dofs;
   v.cellJ = h->mesh->m.cellJ;
   v.coeff = h->has_coeff ? h->coeff.get() : nullptr;
-  v.has_react = h->has_react;
-  v.react_cell = h->react_cell ? h->react.get() : nullptr;
-  v.react_c = h->react_c;
-  v.has_diff = h->has_diff;
-  v.diff = h->has_diff ? h->diff.get() : nullptr;
+  v.has_react = h->react.on;
+  v.rx = react_args(h->react);
+  v.has_diff = h->diff.on;
+  v.dx = diff_args(h->diff);
   v.fixed = h->fixed;
   v.pattern = &h->pattern;
   if constexpr (H::bs == 1)
     if (h->has_robin)
     {
-      const RobinArgs x = robin_args(*h, nullptr, false);
       v.has_robin = true;
-      v.robin_m = (int32_t)(h->robin_off - h->robin_rows);
-      v.robin_n1 = x.n1;
-      v.robin_rows = x.rows;
-      v.robin_off = x.off;
-      v.robin_ent = x.ent;
-      v.robin_dofs = x.dofs;
-      v.robin_w = x.w;
-      v.robin_fm = x.fm;
+      v.robin_m = (int32_t)h->robin_at.m();
+      v.robin = robin_args(*h, nullptr, false);
     }
 }
 
@@ -517,117 +526,39 @@ int solver_set_dirichlet(const char* who, H* h, const int32_t (&nlist)[H::bs], c
   return EQLB_OK;
 }
 
-// c_T = cell_c [ncells] in `memspace` where given, else the scalar c; c == 0 without an array switches the term off.  The
-// diagonal of the handle is formed again in place on the stream.
-template <class H>
-int solver_set_reaction(const char* who, H* h, double c, const double* cell_c, int32_t memspace, void* stream_)
+// The setter of the per-cell term d (`term`: its CellTerm in H or the base of H): the array `cell` [ncells][width] in
+// `memspace` where given, else the scalar x where the term has one; x == neutral without an array switches the term
+// off.  The scalar (only where no array is given; before the handle is read) and a host array are checked before the
+// handle changes; an array in device memory is the caller's responsibility.  The diagonal of the handle is formed again
+// in place on the stream.
+template <class H, class B>
+int solver_set_cell_term(const char* who, H* h, const CellTermSpec& d, CellTerm B::*term, double x, const double* cell,
+                         int32_t memspace, void* stream_)
 {
   EQLB_TRY(check_handle(who, h));
   EQLB_TRY(check_memspace(who, memspace));
-  if (!cell_c && !(c >= 0.0 && std::isfinite(c)))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: c = %g is negative, NaN or infinite", who, c);
+  if (!cell && d.scalar)
+    EQLB_TRY(check_scalar(who, d.scalar, *d.array.rule, x));
+  CellTerm& t = h->*term;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const bool host = memspace == EQLB_MEM_HOST;
-  const size_t nc = (size_t)h->space.ncells;
-  if (cell_c && host)
-    for (size_t i = 0; i < nc; ++i)
-      if (!(cell_c[i] >= 0.0 && std::isfinite(cell_c[i])))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_c[%lld] = %g is negative, NaN or infinite", who, (long long)i,
-                    cell_c[i]);
-  if (cell_c)
+  const size_t nc = (size_t)h->space.ncells, n = nc * d.array.width();
+  if (cell && host)
+    EQLB_TRY(check_cells(who, (long long)nc, {{d.array, cell}}));
+  if (cell)
   {
-    if (!h->react.get())
+    if (!t.buf.get())
     {
-      const hipError_t e = h->react.alloc_raw(nc);
+      const hipError_t e = t.buf.alloc_raw(n);
       if (e != hipSuccess)
         return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed: %s", who, hipGetErrorString(e));
     }
-    HIP_TRY(hipMemcpyAsync(h->react.get(), cell_c, nc * sizeof(double),
-                           host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(t.buf.get(), cell, n * sizeof(double), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                           stream));
   }
-  h->react_cell = cell_c != nullptr;
-  h->react_c = cell_c ? 0.0 : c;
-  h->has_react = cell_c != nullptr || c != 0.0;
-  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
-  if (host)
-    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)
-  return EQLB_OK;
-}
-
-// mu_T = cell_mu [ncells] in `memspace` where given, else the scalar mu; mu == 1 without an array switches the term off.
-// For a handle type that holds the members has_shear, shear_cell, shear_mu and shear (the elasticity unit).  A host
-// array is checked before the handle changes; one in device memory is the caller's responsibility, as cell_c is.  The
-// diagonal of the handle is formed again in place on the stream.
-template <class H>
-int solver_set_shear(const char* who, H* h, double mu, const double* cell_mu, int32_t memspace, void* stream_)
-{
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  if (!cell_mu && !(mu > 0.0 && std::isfinite(mu)))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: mu = %g is zero, negative, NaN or infinite", who, mu);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t nc = (size_t)h->space.ncells;
-  if (cell_mu && host)
-    for (size_t i = 0; i < nc; ++i)
-      if (!(cell_mu[i] > 0.0 && std::isfinite(cell_mu[i])))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_mu[%lld] = %g is zero, negative, NaN or infinite", who,
-                    (long long)i, cell_mu[i]);
-  if (cell_mu)
-  {
-    if (!h->shear.get())
-    {
-      const hipError_t e = h->shear.alloc_raw(nc);
-      if (e != hipSuccess)
-        return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed: %s", who, hipGetErrorString(e));
-    }
-    HIP_TRY(hipMemcpyAsync(h->shear.get(), cell_mu, nc * sizeof(double),
-                           host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-  }
-  h->shear_cell = cell_mu != nullptr;
-  h->shear_mu = cell_mu ? 1.0 : mu;
-  h->has_shear = cell_mu != nullptr || mu != 1.0;
-  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
-  if (host)
-    HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)
-  return EQLB_OK;
-}
-
-// D_T = cell_D [ncells][3] = (d00, d01, d11) in `memspace`; nullptr switches the term off.  A host array is checked cell
-// by cell before the handle changes: finite, d00 > 0 and d00 d11 - d01^2 > 0 (the products rounded as written here); one
-// in device memory is the caller's responsibility, as cell_c is.  The diagonal of the handle is formed again in place
-// on the stream.
-template <class H>
-int solver_set_diffusion(const char* who, H* h, const double* cell_D, int32_t memspace, void* stream_)
-{
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const size_t nc = (size_t)h->space.ncells;
-  if (cell_D && host)
-    for (size_t i = 0; i < nc; ++i)
-    {
-      const double d00 = cell_D[3 * i], d01 = cell_D[3 * i + 1], d11 = cell_D[3 * i + 2];
-      if (!(std::isfinite(d00) && std::isfinite(d01) && std::isfinite(d11)))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%lld] = (%g, %g, %g) is not finite", who, (long long)i, d00,
-                    d01, d11);
-      if (!(d00 > 0.0 && d00 * d11 - d01 * d01 > 0.0))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: cell_D[%lld] = (%g, %g, %g) is not positive definite", who,
-                    (long long)i, d00, d01, d11);
-    }
-  if (cell_D)
-  {
-    if (!h->diff.get())
-    {
-      const hipError_t e = h->diff.alloc_raw(3 * nc);
-      if (e != hipSuccess)
-        return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed: %s", who, hipGetErrorString(e));
-    }
-    HIP_TRY(hipMemcpyAsync(h->diff.get(), cell_D, 3 * nc * sizeof(double),
-                           host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-  }
-  h->has_diff = cell_D != nullptr;
+  t.cell = cell != nullptr;
+  t.scalar = cell ? d.neutral : x;
+  t.on = cell != nullptr || x != d.neutral;
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
   if (host)
     HIP_TRY(hipStreamSynchronize(stream)); // (the caller's array has been read)

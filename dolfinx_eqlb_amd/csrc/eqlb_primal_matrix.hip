@@ -394,23 +394,14 @@ hipError_t launch_fill(const MatrixView& v, bool eliminate, double* values, hipS
 {
   const MatrixPattern& pt = *v.pattern;
   FillArgs a{};
-  a.s.ndofs = v.ndofs;
-  a.s.nnodes = v.nnodes;
-  a.s.nfacets = v.nfacets;
-  a.s.ncells = v.ncells;
-  a.s.ne = v.ne;
-  a.s.ni = v.ni;
-  a.s.nd = v.nd;
-  a.s.nco = v.nco;
-  a.s.fco = v.fco;
-  a.s.slots = v.slots;
+  a.s = v.s;
   a.cell_dofs = v.cell_dofs;
   a.cellJ = v.cellJ;
   a.coeff = v.coeff;
   a.pi_1 = v.pi_1;
-  a.rx = ReactArgs{v.react_cell, v.react_c};
-  a.sx = ShearArgs{v.shear_cell, v.shear_mu};
-  a.dx = DiffArgs{v.diff};
+  a.rx = v.rx;
+  a.sx = v.sx;
+  a.dx = v.dx;
   a.fixed = eliminate ? v.fixed : nullptr;
   a.sptr = pt.sptr;
   a.srow = pt.srow;
@@ -442,7 +433,7 @@ int matrix_pattern(const char* who, MatrixView& v, int64_t* nnz, hipStream_t str
     *nnz = bb * pt.snnz;
     return EQLB_OK;
   }
-  const MatrixPlan plan = matrix_plan(v.bs, v.nd, v.ncells, v.ndofs);
+  const MatrixPlan plan = matrix_plan(v.bs, v.s.nd, v.s.ncells, v.s.ndofs);
   if (!plan.ok)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %lld rows or %lld keys are more than the index types hold", who,
                 (long long)plan.rows, (long long)plan.nkeys);
@@ -461,7 +452,7 @@ int matrix_pattern(const char* who, MatrixView& v, int64_t* nnz, hipStream_t str
   DevBuf<char> tmp;
   if (tmp.alloc_raw(tmp_bytes) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation of %zu bytes failed", who, tmp_bytes);
-  hipLaunchKernelGGL(k_matrix_keys, dim3(mx_blocks(plan.nkeys)), dim3(MX_THREADS), 0, stream, plan.nkeys, v.nd, v.ndofs,
+  hipLaunchKernelGGL(k_matrix_keys, dim3(mx_blocks(plan.nkeys)), dim3(MX_THREADS), 0, stream, plan.nkeys, v.s.nd, v.s.ndofs,
                      v.cell_dofs, keys_in);
   HIP_TRY(hipGetLastError());
   {
@@ -480,19 +471,19 @@ int matrix_pattern(const char* who, MatrixView& v, int64_t* nnz, hipStream_t str
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: %llu entries per block are more than the index types hold", who, found);
   const int64_t snnz = (int64_t)found;
   MatrixPattern fresh;
-  if (fresh.sptr.alloc_raw((size_t)v.ndofs + 1) != hipSuccess || fresh.srow.alloc_raw((size_t)snnz) != hipSuccess
+  if (fresh.sptr.alloc_raw((size_t)v.s.ndofs + 1) != hipSuccess || fresh.srow.alloc_raw((size_t)snnz) != hipSuccess
       || fresh.scol.alloc_raw((size_t)snnz) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation of the pattern (%lld pairs) failed", who, (long long)snnz);
-  hipLaunchKernelGGL(k_matrix_rows, dim3(mx_blocks(snnz)), dim3(MX_THREADS), 0, stream, snnz, v.ndofs, keys_in,
+  hipLaunchKernelGGL(k_matrix_rows, dim3(mx_blocks(snnz)), dim3(MX_THREADS), 0, stream, snnz, v.s.ndofs, keys_in,
                      fresh.sptr.get(), fresh.srow.get(), fresh.scol.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(stream)); // (the keys end with this call)
   fresh.snnz = snnz;
   fresh.built = true;
-  fresh.peak_bytes = pool.bytes() + tmp_bytes + matrix_kept_bytes(v.ndofs, snnz);
+  fresh.peak_bytes = pool.bytes() + tmp_bytes + matrix_kept_bytes(v.s.ndofs, snnz);
   if (getenv("EQLB_PROFILE_SETUP")) // (the switch of SetupTimer)
     fprintf(stderr, "[eqlb setup] %s: %lld keys, %lld pairs, peak work space %zu bytes (kept %zu)\n", who,
-            (long long)plan.nkeys, (long long)snnz, fresh.peak_bytes, matrix_kept_bytes(v.ndofs, snnz));
+            (long long)plan.nkeys, (long long)snnz, fresh.peak_bytes, matrix_kept_bytes(v.s.ndofs, snnz));
   pt = std::move(fresh);
   *nnz = bb * snnz;
   return EQLB_OK;
@@ -516,7 +507,7 @@ int matrix_export(const char* who, const MatrixView& v, int64_t* indptr, int32_t
   const MatrixPattern& pt = *v.pattern;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const bool host = memspace == EQLB_MEM_HOST;
-  const size_t n = (size_t)v.bs * v.ndofs, nnz = (size_t)v.bs * v.bs * pt.snnz;
+  const size_t n = (size_t)v.bs * v.s.ndofs, nnz = (size_t)v.bs * v.bs * pt.snnz;
   HostCall s;
   const auto d_p = s.out(host ? indptr : nullptr, n + 1);
   const auto d_i = s.out(host ? indices : nullptr, nnz);
@@ -527,10 +518,10 @@ int matrix_export(const char* who, const MatrixView& v, int64_t* indptr, int32_t
   const int64_t most = pt.snnz > (int64_t)n + 1 ? pt.snnz : (int64_t)n + 1;
   const dim3 grid(mx_blocks(most)), block(MX_THREADS);
   if (v.bs == 1)
-    hipLaunchKernelGGL(k_matrix_export<1>, grid, block, 0, stream, v.ndofs, pt.snnz, pt.sptr.get(), pt.srow.get(),
+    hipLaunchKernelGGL(k_matrix_export<1>, grid, block, 0, stream, v.s.ndofs, pt.snnz, pt.sptr.get(), pt.srow.get(),
                        pt.scol.get(), pp, pi);
   else
-    hipLaunchKernelGGL(k_matrix_export<2>, grid, block, 0, stream, v.ndofs, pt.snnz, pt.sptr.get(), pt.srow.get(),
+    hipLaunchKernelGGL(k_matrix_export<2>, grid, block, 0, stream, v.s.ndofs, pt.snnz, pt.sptr.get(), pt.srow.get(),
                        pt.scol.get(), pp, pi);
   s.note(hipGetLastError());
   HIP_TRY(s.finish(stream));
@@ -560,9 +551,9 @@ int matrix_values(const char* who, const MatrixView& v, int32_t eliminate, doubl
   s.note(v.bs == 1 ? launch_fill<1>(v, eliminate != 0, pv, stream) : launch_fill<2>(v, eliminate != 0, pv, stream));
   if (v.bs == 1 && v.has_robin && v.robin_m > 0)
   {
-    const RobinFillArgs a{v.robin_m,   v.robin_n1, v.robin_rows, v.robin_off, v.robin_ent,          v.robin_dofs,
-                          v.robin_w,   v.robin_fm, eliminate ? v.fixed : nullptr, v.pattern->sptr.get(),
-                          v.pattern->scol.get(), pv};
+    const RobinArgs& x = v.robin;
+    const RobinFillArgs a{v.robin_m, x.n1, x.rows, x.off, x.ent, x.dofs, x.w, x.fm, eliminate ? v.fixed : nullptr,
+                          v.pattern->sptr.get(), v.pattern->scol.get(), pv};
     hipLaunchKernelGGL(k_matrix_robin, dim3(mx_blocks(v.robin_m)), dim3(MX_THREADS), 0, stream, a);
     s.note(hipGetLastError());
   }

@@ -222,10 +222,10 @@ hipError_t launch_cell(const eqlb_primal& h, const ManyCols& c, int d, const dou
   a.fixed = h.fixed;
   a.only_fixed = only_fixed ? 1 : 0;
   a.yloc = work_of(h, c.R).yloc;
-  const ReactArgs rx = react_args(h);
-  const DiffArgs dx{h.diff.get()};
-  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, h.has_react ? &rx : nullptr,
-                           h.has_diff ? &dx : nullptr, stream);
+  const ReactArgs rx = react_args(h.react);
+  const DiffArgs dx = diff_args(h.diff);
+  return launch_cell<MODE>(h.p, d, a, c, h.ndofs, (int64_t)h.space.ncells * h.nd, h.react.on ? &rx : nullptr,
+                           h.diff.on ? &dx : nullptr, stream);
 }
 // ---- the Robin term (include/eqlb.h: eqlb_primal_set_robin) --------------------------------------------------------
 // One thread per listed facet: its rows in the local order (lower node id, higher node id, nnodes + f (p-1) + j), its
@@ -360,8 +360,8 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d, or a null list", who, (int)nlist);
   if (nlist >= (1 << 28))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d: at most 2^28 - 1 facets", who, (int)nlist);
-  if (!facet_alpha && !(alpha >= 0.0 && std::isfinite(alpha)))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: alpha = %g is negative, NaN or infinite", who, alpha);
+  if (!facet_alpha)
+    EQLB_TRY(check_scalar(who, "alpha", *FACET_ALPHA.rule, alpha));
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const bool host = memspace == EQLB_MEM_HOST;
   const DeviceMesh& m = h->mesh->m;
@@ -413,9 +413,8 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
                     (int)facets[i]);
       if (!seen.insert(facets[i]).second)
         return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is listed twice", who, (int)i, (int)facets[i]);
-      if (facet_alpha && !(facet_alpha[i] >= 0.0 && std::isfinite(facet_alpha[i])))
-        return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facet_alpha[%d] = %g is negative, NaN or infinite", who, (int)i,
-                    facet_alpha[i]);
+      if (facet_alpha && !FACET_ALPHA.rule->ok(facet_alpha[i]))
+        return fail_cell(who, FACET_ALPHA, facet_alpha, i);
     }
   }
   // the entries (row, facet, list position, local index), sorted by row, then facet, then position
@@ -454,28 +453,23 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
                                                                                               INT32_MAX))
                          - rows.begin());
   chunk[nch] = (int32_t)rows.size();
-  // one array: facets | dofs | chunk | rows | off | ent
-  const size_t o_chunk = n * (1 + ROBIN_ROW), o_rows = o_chunk + chunk.size(), o_off = o_rows + rows.size(),
-               o_ent = o_off + off.size(), total = o_ent + packed.size();
-  std::vector<int32_t> tab(total);
-  std::copy(hh.begin(), hh.begin() + (std::ptrdiff_t)o_chunk, tab.begin());
-  std::copy(chunk.begin(), chunk.end(), tab.begin() + (std::ptrdiff_t)o_chunk);
-  std::copy(rows.begin(), rows.end(), tab.begin() + (std::ptrdiff_t)o_rows);
-  std::copy(off.begin(), off.end(), tab.begin() + (std::ptrdiff_t)o_off);
-  std::copy(packed.begin(), packed.end(), tab.begin() + (std::ptrdiff_t)o_ent);
+  // one array (facets and dofs as the device left them in hh)
+  const RobinLayout at(n, chunk.size(), rows.size(), packed.size());
+  std::vector<int32_t> tab(at.total);
+  std::copy(hh.begin(), hh.begin() + (std::ptrdiff_t)at.chunk, tab.begin());
+  std::copy(chunk.begin(), chunk.end(), tab.begin() + (std::ptrdiff_t)at.chunk);
+  std::copy(rows.begin(), rows.end(), tab.begin() + (std::ptrdiff_t)at.rows);
+  std::copy(off.begin(), off.end(), tab.begin() + (std::ptrdiff_t)at.off);
+  std::copy(packed.begin(), packed.end(), tab.begin() + (std::ptrdiff_t)at.ent);
   DevBuf<int32_t> dtab;
-  if (dtab.alloc_raw(total) != hipSuccess)
+  if (dtab.alloc_raw(at.total) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
-  HIP_TRY(hipMemcpyAsync(dtab.get(), tab.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(dtab.get(), tab.data(), at.total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipStreamSynchronize(stream)); // (tab ends with this call; nothing on the stream reads the old table any more)
   h->robin_tab = std::move(dtab);
   h->robin_val = std::move(val);
   h->robin_n = nlist;
-  h->robin_chunk = o_chunk;
-  h->robin_rows = o_rows;
-  h->robin_off = o_off;
-  h->robin_ent = o_ent;
-  h->robin_nent = packed.size();
+  h->robin_at = at;
   h->has_robin = true;
   h->robin_pos = positive;
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
@@ -581,14 +575,16 @@ EQLB_CATCH_ALL
 int eqlb_primal_set_reaction(eqlb_primal_t* h, double c, const double* cell_c, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::solver_set_reaction("eqlb_primal_set_reaction", h, c, cell_c, memspace, stream_);
+  return eqlb::solver_set_cell_term("eqlb_primal_set_reaction", h, eqlb::REACTION, &eqlb_primal::react, c, cell_c,
+                                    memspace, stream_);
 }
 EQLB_CATCH_ALL
 
 int eqlb_primal_set_diffusion(eqlb_primal_t* h, const double* cell_D, int32_t memspace, void* stream_)
 try
 {
-  return eqlb::solver_set_diffusion("eqlb_primal_set_diffusion", h, cell_D, memspace, stream_);
+  return eqlb::solver_set_cell_term("eqlb_primal_set_diffusion", h, eqlb::DIFFUSION, &eqlb_primal::diff, 0.0, cell_D,
+                                    memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -673,7 +669,7 @@ try
     HIP_TRY(c.upload(stream));
   const int32_t* tab = h->robin_tab.get();
   hipLaunchKernelGGL(k_robin_flux, dim3(grid_of((int64_t)no, PS_THREADS)), dim3(PS_THREADS), 0, stream, h->robin_n, nq,
-                     (int32_t)h->p, rule, tab, tab + n, static_cast<const double*>(h->robin_val.get() + n), m.ncells,
+                     (int32_t)h->p, rule, tab, tab + h->robin_at.dofs, static_cast<const double*>(h->robin_val.get() + n), m.ncells,
                      m.cell_nodes, m.cell_facets, m.facet_cells_off, m.facet_cells, host ? d_u.get() : u,
                      host ? d_e.get() : u_ext, host ? d_o.get() : out);
   c.note(hipGetLastError());

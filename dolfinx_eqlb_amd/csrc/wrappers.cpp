@@ -44,6 +44,26 @@ using darray = py::array_t<double, py::array::c_style | py::array::forcecast>;
 template <typename T>
 using carray = py::array_t<T, py::array::c_style | py::array::forcecast>;
 
+// an optional array argument: the array, kept alive, and its data - nullptr for None.  One of another size than n
+// throws `what`
+struct OptArray
+{
+  carray<double> a;
+  const double* p = nullptr;
+};
+OptArray opt_array(const py::object& o, py::ssize_t n, const std::string& what)
+{
+  OptArray r;
+  if (!o.is_none())
+  {
+    r.a = o.cast<carray<double>>();
+    if (r.a.size() != n)
+      throw std::runtime_error(what);
+    r.p = r.a.data();
+  }
+  return r;
+}
+
 [[noreturn]] void raise_last(int status)
 {
   const char* msg = eqlb_last_error();
@@ -349,14 +369,8 @@ struct PrimalPoisson
 
   PrimalPoisson(std::shared_ptr<Mesh> mesh_, int p_, py::object coeff) : mesh(mesh_), p(p_)
   {
-    carray<double> kc;
-    if (!coeff.is_none())
-    {
-      kc = coeff.cast<carray<double>>();
-      if (kc.size() != mesh->ncells)
-        throw std::runtime_error("PrimalPoisson: coeff [ncells] expected");
-    }
-    check(eqlb_primal_create(mesh->h, p, coeff.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr, &h));
+    const OptArray kc = opt_array(coeff, mesh->ncells, "PrimalPoisson: coeff [ncells] expected");
+    check(eqlb_primal_create(mesh->h, p, kc.p, EQLB_MEM_HOST, nullptr, &h));
     check(eqlb_primal_ndofs(h, &ndofs));
   }
   ~PrimalPoisson() { eqlb_primal_destroy(h); }
@@ -376,40 +390,24 @@ struct PrimalPoisson
   // + c u: cell_c [ncells] where given, else the scalar c; c == 0 without an array switches the term off
   void set_reaction(double c, py::object cell_c)
   {
-    carray<double> kc;
-    if (!cell_c.is_none())
-    {
-      kc = cell_c.cast<carray<double>>();
-      if (kc.size() != mesh->ncells)
-        throw std::runtime_error("PrimalPoisson.set_reaction: cell_c [ncells] expected");
-    }
-    check(eqlb_primal_set_reaction(h, c, cell_c.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
+    const OptArray kc = opt_array(cell_c, mesh->ncells, "PrimalPoisson.set_reaction: cell_c [ncells] expected");
+    check(eqlb_primal_set_reaction(h, c, kc.p, EQLB_MEM_HOST, nullptr));
   }
   // -div(coeff D grad u): cell_D [ncells][3] = (d00, d01, d11) per cell; None switches the term off
   void set_diffusion(py::object cell_D)
   {
-    carray<double> kd;
-    if (!cell_D.is_none())
-    {
-      kd = cell_D.cast<carray<double>>();
-      if (kd.size() != (py::ssize_t)mesh->ncells * 3)
-        throw std::runtime_error("PrimalPoisson.set_diffusion: cell_D [ncells][3] expected");
-    }
-    check(eqlb_primal_set_diffusion(h, cell_D.is_none() ? nullptr : kd.data(), EQLB_MEM_HOST, nullptr));
+    const OptArray kd = opt_array(cell_D, (py::ssize_t)mesh->ncells * 3,
+                                  "PrimalPoisson.set_diffusion: cell_D [ncells][3] expected");
+    check(eqlb_primal_set_diffusion(h, kd.p, EQLB_MEM_HOST, nullptr));
   }
   // the Robin term int alpha u v over the listed boundary facets: facet_alpha [nlist] where given, else the scalar alpha;
   // an empty list switches the term off
   void set_robin(carray<int32_t> facets, double alpha, py::object facet_alpha)
   {
-    carray<double> fa;
-    if (!facet_alpha.is_none())
-    {
-      fa = facet_alpha.cast<carray<double>>();
-      if (fa.size() != facets.size())
-        throw std::runtime_error("PrimalPoisson.set_robin: facet_alpha [nlist] expected");
-    }
+    const OptArray fa = opt_array(facet_alpha, facets.size(), "PrimalPoisson.set_robin: facet_alpha [nlist] expected");
+    // (an empty facet_alpha goes down as nullptr)
     check(eqlb_primal_set_robin(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, alpha,
-                                !facet_alpha.is_none() && fa.size() ? fa.data() : nullptr, EQLB_MEM_HOST, nullptr));
+                                fa.a.size() ? fa.p : nullptr, EQLB_MEM_HOST, nullptr));
   }
   darray robin_weights() const
   {
@@ -426,16 +424,10 @@ struct PrimalPoisson
     need(u, "robin_flux");
     int32_t n = 0;
     check(eqlb_primal_robin_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
-    darray e;
-    if (!u_ext.is_none())
-    {
-      e = u_ext.cast<darray>();
-      if (e.size() != (py::ssize_t)n * s.size())
-        throw std::runtime_error("PrimalPoisson.robin_flux: u_ext [nlist, nq] expected");
-    }
+    const OptArray e = opt_array(u_ext, (py::ssize_t)n * s.size(), "PrimalPoisson.robin_flux: u_ext [nlist, nq] expected");
     darray out({(py::ssize_t)n, (py::ssize_t)s.size()});
-    check(eqlb_primal_robin_flux(h, u.data(), (int32_t)s.size(), s.data(), u_ext.is_none() ? nullptr : e.data(),
-                                 out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    check(eqlb_primal_robin_flux(h, u.data(), (int32_t)s.size(), s.data(), e.p, out.mutable_data(), EQLB_MEM_HOST,
+                                 nullptr));
     return out;
   }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
@@ -443,14 +435,9 @@ struct PrimalPoisson
     if (degree_dg >= 0 && degree_dg <= 3
         && rhs_dg.size() != (py::ssize_t)mesh->ncells * ((degree_dg + 1) * (degree_dg + 2) / 2))
       throw std::runtime_error("PrimalPoisson.load: Input sizes does not match");
-    darray e;
-    if (!b_extra.is_none())
-    {
-      e = b_extra.cast<darray>();
-      need(e, "load");
-    }
+    const OptArray e = opt_array(b_extra, ndofs, "PrimalPoisson.load: Input sizes does not match");
     darray b((py::ssize_t)ndofs);
-    check(eqlb_primal_load(h, degree_dg, rhs_dg.data(), b_extra.is_none() ? nullptr : e.data(), b.mutable_data(),
+    check(eqlb_primal_load(h, degree_dg, rhs_dg.data(), e.p, b.mutable_data(),
                            EQLB_MEM_HOST, nullptr));
     return b;
   }
@@ -542,15 +529,8 @@ struct PrimalElasticity
 
   PrimalElasticity(std::shared_ptr<Mesh> mesh_, int p_, double pi_1, py::object cell_pi1) : mesh(mesh_), p(p_)
   {
-    carray<double> kc;
-    if (!cell_pi1.is_none())
-    {
-      kc = cell_pi1.cast<carray<double>>();
-      if (kc.size() != mesh->ncells)
-        throw std::runtime_error("PrimalElasticity: cell_pi1 [ncells] expected");
-    }
-    check(eqlb_elasticity_create(mesh->h, p, pi_1, cell_pi1.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr,
-                                 &h));
+    const OptArray kc = opt_array(cell_pi1, mesh->ncells, "PrimalElasticity: cell_pi1 [ncells] expected");
+    check(eqlb_elasticity_create(mesh->h, p, pi_1, kc.p, EQLB_MEM_HOST, nullptr, &h));
     check(eqlb_elasticity_ndofs(h, &ndofs));
   }
   ~PrimalElasticity() { eqlb_elasticity_destroy(h); }
@@ -571,41 +551,24 @@ struct PrimalElasticity
   // + c u: cell_c [ncells] where given, else the scalar c; c == 0 without an array switches the term off
   void set_reaction(double c, py::object cell_c)
   {
-    carray<double> kc;
-    if (!cell_c.is_none())
-    {
-      kc = cell_c.cast<carray<double>>();
-      if (kc.size() != mesh->ncells)
-        throw std::runtime_error("PrimalElasticity.set_reaction: cell_c [ncells] expected");
-    }
-    check(eqlb_elasticity_set_reaction(h, c, cell_c.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
+    const OptArray kc = opt_array(cell_c, mesh->ncells, "PrimalElasticity.set_reaction: cell_c [ncells] expected");
+    check(eqlb_elasticity_set_reaction(h, c, kc.p, EQLB_MEM_HOST, nullptr));
   }
   // sigma = mu (2 eps(u) + pi_1 div(u) I): cell_mu [ncells] where given, else the scalar mu; mu == 1 without an array
   // switches the term off
   void set_shear(double mu, py::object cell_mu)
   {
-    carray<double> kc;
-    if (!cell_mu.is_none())
-    {
-      kc = cell_mu.cast<carray<double>>();
-      if (kc.size() != mesh->ncells)
-        throw std::runtime_error("PrimalElasticity.set_shear: cell_mu [ncells] expected");
-    }
-    check(eqlb_elasticity_set_shear(h, mu, cell_mu.is_none() ? nullptr : kc.data(), EQLB_MEM_HOST, nullptr));
+    const OptArray kc = opt_array(cell_mu, mesh->ncells, "PrimalElasticity.set_shear: cell_mu [ncells] expected");
+    check(eqlb_elasticity_set_shear(h, mu, kc.p, EQLB_MEM_HOST, nullptr));
   }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
     if (degree_dg >= 0 && degree_dg <= 3
         && rhs_dg.size() != 2 * (py::ssize_t)mesh->ncells * ((degree_dg + 1) * (degree_dg + 2) / 2))
       throw std::runtime_error("PrimalElasticity.load: Input sizes does not match");
-    darray e;
-    if (!b_extra.is_none())
-    {
-      e = b_extra.cast<darray>();
-      need(e, "load");
-    }
+    const OptArray e = opt_array(b_extra, 2 * ndofs, "PrimalElasticity.load: Input sizes does not match");
     darray b((py::ssize_t)(2 * ndofs));
-    check(eqlb_elasticity_load(h, degree_dg, rhs_dg.data(), b_extra.is_none() ? nullptr : e.data(), b.mutable_data(),
+    check(eqlb_elasticity_load(h, degree_dg, rhs_dg.data(), e.p, b.mutable_data(),
                                EQLB_MEM_HOST, nullptr));
     return b;
   }
@@ -1913,18 +1876,13 @@ PYBIND11_MODULE(_cpp, m)
           throw std::runtime_error("primal_value_dg: degrees outside 1 ... 4, 0 ... 3");
         const py::ssize_t ndp = (p + 1) * (p + 2) / 2, nd = (degree_dg + 1) * (degree_dg + 2) / 2;
         const py::ssize_t nrhs = u.ndim() == 2 ? u.shape(0) : 1;
-        carray<double> kc, t;
-        if (!coeff.is_none())
-          kc = coeff.cast<carray<double>>();
-        if (!op.is_none())
-          t = op.cast<carray<double>>();
-        if (cell_dofs.size() != (py::ssize_t)mesh->ncells * ndp || u.size() == 0 || u.size() % nrhs
-            || (!coeff.is_none() && kc.size() != mesh->ncells) || (!op.is_none() && t.size() != nd * ndp))
-          throw std::runtime_error("primal_value_dg: Input sizes does not match");
+        const char* what = "primal_value_dg: Input sizes does not match";
+        const OptArray kc = opt_array(coeff, mesh->ncells, what), t = opt_array(op, nd * ndp, what);
+        if (cell_dofs.size() != (py::ssize_t)mesh->ncells * ndp || u.size() == 0 || u.size() % nrhs)
+          throw std::runtime_error(what);
         darray out({nrhs, (py::ssize_t)mesh->ncells * nd});
         check(eqlb_primal_value_dg(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs, u.data(),
-                                   coeff.is_none() ? nullptr : kc.data(), op.is_none() ? nullptr : t.data(),
-                                   out.mutable_data(), EQLB_MEM_HOST, nullptr));
+                                   kc.p, t.p, out.mutable_data(), EQLB_MEM_HOST, nullptr));
         return out;
       },
       py::arg("mesh"), py::arg("p"), py::arg("degree_dg"), py::arg("cell_dofs"), py::arg("u"),
@@ -1939,26 +1897,18 @@ PYBIND11_MODULE(_cpp, m)
           throw std::runtime_error("primal_flux_dg: degrees outside 1 ... 4, 0 ... 3");
         const py::ssize_t ndp = (p + 1) * (p + 2) / 2, nd = (degree_dg + 1) * (degree_dg + 2) / 2;
         const py::ssize_t nrhs = u.ndim() == 2 ? u.shape(0) : 1;
-        carray<double> kc, t, kd;
-        if (!coeff.is_none())
-          kc = coeff.cast<carray<double>>();
-        if (!op.is_none())
-          t = op.cast<carray<double>>();
-        if (!cell_D.is_none())
-          kd = cell_D.cast<carray<double>>();
-        if (cell_dofs.size() != (py::ssize_t)mesh->ncells * ndp || u.size() == 0 || u.size() % nrhs
-            || (!coeff.is_none() && kc.size() != mesh->ncells) || (!op.is_none() && t.size() != 2 * nd * ndp)
-            || (!cell_D.is_none() && kd.size() != (py::ssize_t)mesh->ncells * 3))
-          throw std::runtime_error("primal_flux_dg: Input sizes does not match");
+        const char* what = "primal_flux_dg: Input sizes does not match";
+        const OptArray kc = opt_array(coeff, mesh->ncells, what), t = opt_array(op, 2 * nd * ndp, what),
+                       kd = opt_array(cell_D, (py::ssize_t)mesh->ncells * 3, what);
+        if (cell_dofs.size() != (py::ssize_t)mesh->ncells * ndp || u.size() == 0 || u.size() % nrhs)
+          throw std::runtime_error(what);
         darray out({nrhs, (py::ssize_t)mesh->ncells * nd * 2});
-        const double* pk = coeff.is_none() ? nullptr : kc.data();
-        const double* pt = op.is_none() ? nullptr : t.data();
-        if (cell_D.is_none())
-          check(eqlb_primal_flux_dg(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs, u.data(), pk,
-                                    pt, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+        if (!kd.p)
+          check(eqlb_primal_flux_dg(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs, u.data(),
+                                    kc.p, t.p, out.mutable_data(), EQLB_MEM_HOST, nullptr));
         else
           check(eqlb_primal_flux_dg_tensor(mesh->h, p, degree_dg, (int32_t)nrhs, cell_dofs.data(), u.size() / nrhs,
-                                           u.data(), pk, kd.data(), pt, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+                                           u.data(), kc.p, kd.p, t.p, out.mutable_data(), EQLB_MEM_HOST, nullptr));
         return out;
       },
       py::arg("mesh"), py::arg("p"), py::arg("degree_dg"), py::arg("cell_dofs"), py::arg("u"),
