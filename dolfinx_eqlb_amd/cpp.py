@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "eqlb_elasticity_matrix_pattern", "eqlb_elasticity_matrix_export", "eqlb_elasticity_matrix_values",
     "eqlb_elasticity_matrix_release", "eqlb_csr_apply",
     "eqlb_get_facet_mass_table", "eqlb_primal_set_robin", "eqlb_primal_robin_weights", "eqlb_primal_robin_flux",
+    "eqlb_elasticity_set_springs", "eqlb_elasticity_spring_weights", "eqlb_elasticity_spring_flux",
 ]
 
 # eqlb_se_tiling_blocks: per bin (P = 4, 8, 16, 32, 64) the wave-blocks of each body instance and the padding copies,
@@ -659,6 +660,20 @@ class Refinement:
         a2 = np.repeat(a[:, None], 2, axis=1)[keep]
         new.set_robin(f2, facet_alpha=a2, stream=stream)
         return f2, a2
+
+    def carry_springs(self, old, new, stream=0):
+        """The spring list of the solver handle `old` (PrimalElasticity on the mesh that was refined) on the refined
+        mesh: the list goes through child_facets, a child takes its parent's tensor K as it is - K is stated in global
+        axes, so nothing is rotated - and `new` (PrimalElasticity on the refined mesh) gets it through set_springs (the
+        rule: mesh.refine.carry_springs_list).  Returns (facets2, facet_k2), host arrays.  `old` must have received its
+        list through set_springs (host arrays); one without the term switches the term of `new` off."""
+        f, K = old.spring_list()
+        ch = self.child_facets(f, stream=stream)
+        keep = ch >= 0
+        f2 = ch[keep].astype(np.int32)
+        K2 = np.repeat(K.reshape(f.size, 1, 3), 2, axis=1)[keep]
+        new.set_springs(f2, facet_k=K2, stream=stream)
+        return f2, K2
 
     def prolong_flux_bc(self, k, boundary_values, facets2, stream=0):
         """The table boundary_values [nrhs, ncells*k(k+2)] (or 1-D) of the old mesh -> dofs [nrhs, nlist, k] of the
@@ -1986,6 +2001,87 @@ class PrimalElasticity(_PrimalSolver):
         """cell_mu: a raw pointer (int) to [ncells] in `memspace`, or None (the scalar mu)."""
         _check(lib().eqlb_elasticity_set_shear(self._h, C.c_double(mu), _vp(cell_mu), C.c_int32(memspace),
                                                C.c_void_p(stream)))
+
+    def set_springs(self, facets, k=1.0, facet_k=None, stream=0):
+        """The operator gains int_E v^T K u over the listed boundary facets (eqlb_elasticity_set_springs):
+        sigma(u) n = -K (u - u_ext) there; K_f = facet_k [nlist, 3] = (k00, k01, k11), symmetric positive semidefinite
+        in global axes, where given, else k I.  An empty list switches the term off; a repeated call replaces the list.
+        Refused by facet, the handle as it was: a facet that is no boundary facet, one listed twice, an entry that is
+        not finite, k00 < 0, k11 < 0, k01 k01 > k00 k11 (1 + 2^-49).  With a positive definite K_f on some facet the
+        solves ask for no Dirichlet DOF.  The diagonal is formed again; Multilevel.set_coarse(True) has to be called
+        again afterwards.  The datum u_ext enters the load through lsolver.spring_load; lsolver.spring_tensor gives
+        K = kn n x n + kt t x t; Refinement.carry_springs carries the list to the refined mesh."""
+        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+        fk = None
+        if facet_k is not None:
+            fk = np.ascontiguousarray(facet_k, dtype=np.float64).ravel()
+            if fk.size != 3 * fl.size:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        self.set_springs_raw(fl.size, fl.ctypes.data if fl.size else None, k,
+                             fk.ctypes.data if fk is not None and fk.size else None, MEM_HOST, stream)
+        kk = float(k)
+        self._spring_list = (fl.copy(), np.tile(np.array([kk, 0.0, kk]), (fl.size, 1)) if fk is None
+                             else fk.reshape(fl.size, 3).copy())
+
+    def spring_list(self):
+        """(facets int32 [nlist], facet_k [nlist, 3]) as the last accepted set_springs took them (empty without one)."""
+        known = getattr(self, "_spring_list", None)
+        if known is None or known[0].size != self.spring_count():
+            if self.spring_count() != 0:
+                raise RuntimeError("spring_list: the handle's list was not given through set_springs (host arrays)")
+            return np.zeros(0, dtype=np.int32), np.zeros((0, 3))
+        return known
+
+    def set_springs_raw(self, nlist, facets, k=1.0, facet_k=None, memspace=MEM_DEVICE, stream=0):
+        """facets int32 [nlist], facet_k float64 [nlist][3] or None behind raw pointers in `memspace`.  Device memory
+        space: a listed id that is no boundary facet is skipped; the call waits for the stream.  spring_list() knows
+        nothing of a list given here: it is emptied, and Refinement.carry_springs refuses such a handle."""
+        self._spring_list = None
+        _check(lib().eqlb_elasticity_set_springs(self._h, C.c_int32(nlist), _vp(facets), C.c_double(k), _vp(facet_k),
+                                                 C.c_int32(memspace), C.c_void_p(stream)))
+
+    def spring_count(self):
+        """The number of listed facets of the spring term (0 without it)."""
+        n = C.c_int32(0)
+        _check(lib().eqlb_elasticity_spring_weights(self._h, C.byref(n), None, C.c_int32(0), C.c_int32(MEM_HOST), None))
+        return int(n.value)
+
+    def spring_weights(self, stream=0):
+        """Kw_f = |E_f| (k00, k01, k11) [nlist, 3] in the order of the list (eqlb_elasticity_spring_weights)."""
+        w = np.zeros((self.spring_count(), 3))
+        if w.size:
+            self.spring_weights_raw(w.ctypes.data, w.shape[0], MEM_HOST, stream)
+        return w
+
+    def spring_weights_raw(self, kw, capacity, memspace=MEM_DEVICE, stream=0):
+        n = C.c_int32(0)
+        _check(lib().eqlb_elasticity_spring_weights(self._h, C.byref(n), _vp(kw), C.c_int32(capacity),
+                                                    C.c_int32(memspace), C.c_void_p(stream)))
+        return int(n.value)
+
+    def spring_flux(self, u, s, u_ext=None, stream=0):
+        """out [2, nlist, nq]: out[r] = (K (u_h - u_ext))_r on the handle's spring list at the facet parameters s [nq] in
+        the frame of facet_points (eqlb_elasticity_spring_flux): row r holds the point values of the flux condition that
+        row r of a stress handle takes in update_flux_bc with vector=False.  u_ext [2, nlist, nq] or None (0)."""
+        uu = self._vec(u)
+        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+        n = self.spring_count()
+        ue = None
+        if u_ext is not None:
+            ue = np.ascontiguousarray(u_ext, dtype=np.float64).ravel()
+            if ue.size != 2 * n * ss.size:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        out = np.zeros((2, n, ss.size))
+        self.spring_flux_raw(uu.ctypes.data, ss, None if ue is None else ue.ctypes.data, out.ctypes.data, MEM_HOST,
+                             stream)
+        return out
+
+    def spring_flux_raw(self, u, s, u_ext, out, memspace=MEM_DEVICE, stream=0):
+        """u [2 ndofs], u_ext [2][nlist][nq] or None and out [2][nlist][nq] behind raw pointers in `memspace`; s a host
+        array."""
+        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+        _check(lib().eqlb_elasticity_spring_flux(self._h, _vp(u), C.c_int32(ss.size), _hp(ss), _vp(u_ext), _vp(out),
+                                                 C.c_int32(memspace), C.c_void_p(stream)))
 
 
 

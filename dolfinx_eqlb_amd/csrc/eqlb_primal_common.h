@@ -16,8 +16,9 @@
 //  k_primal_slots    builds the slot lists of the sum pass once at create (scalar numbering: both problems use it)
 //  k_primal_mask<BS> the Dirichlet mask of one component from a list of facets
 //  k_primal_gather<BS, NC>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
-//                    x[BS * dof + r]; columns for BS = 1 only.  eqlb_primal_gather.inc, included twice: the second
-//                    time as k_primal_gather_robin, which adds the facet values of a Robin term
+//                    x[BS * dof + r]; columns for BS = 1 only.  eqlb_primal_gather.inc, included three times: the
+//                    second time as k_primal_gather_robin, which adds the facet values of a Robin term (BS = 1), the
+//                    third as k_primal_gather_spring, which adds those of a spring term (BS = 2)
 //  k_pcg_*<NC>       work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
 //  k_pcg_scalar      the scalar steps; `ml`: the breakdown rule of a preconditioner that is no positive diagonal
 //  pcg_solve         the host side of the iteration on a PcgWork; the preconditioner enters through its `steps`
@@ -185,10 +186,30 @@ struct RobinArgs
   int32_t only_fixed, n1;
 };
 
+// the spring term of the sum pass on a blocked space, bs = 2 (include/eqlb.h: eqlb_elasticity_set_springs): the table of
+// the Robin term over the scalar DOFs d - both rows 2 d + r of a DOF lie in the same facets - with the tensor weights
+// in the place of the scalar one.  A chunk of PS_THREADS consecutive rows e holds PS_THREADS / 2 consecutive DOFs.
+struct SpringArgs
+{
+  const int32_t* chunk; // [ceil(2 ndofs / PS_THREADS) + 1] first position in rows[] of a chunk of PS_THREADS / 2 DOFs
+  const int32_t* rows;  // [m] the DOFs d that lie in a spring facet, ascending
+  const int32_t* off;   // [m + 1] the entries of a DOF in ent[]
+  const int32_t* ent;   // list position * 8 + local index of the DOF in that facet, facet ids ascending
+  const int32_t* dofs;  // [nlist][ROBIN_ROW], scalar DOFs
+  const double* kw;     // [nlist][3] |E_f| (k00, k01, k11)
+  const double* fm;     // FacetMass<p> [n1][n1]
+  const double* u;      // [2 ndofs] blocked; nullptr: the diagonal
+  const uint8_t* fixed; // [2 ndofs]; only_fixed: the free rows of u read as 0
+  int32_t only_fixed, n1;
+};
+
 #define EQLB_GATHER_ROBIN 0
 #include "eqlb_primal_gather.inc"
 #undef EQLB_GATHER_ROBIN
 #define EQLB_GATHER_ROBIN 1
+#include "eqlb_primal_gather.inc"
+#undef EQLB_GATHER_ROBIN
+#define EQLB_GATHER_ROBIN 2
 #include "eqlb_primal_gather.inc"
 #undef EQLB_GATHER_ROBIN
 

@@ -5,11 +5,23 @@
 //                        one addition, before b_extra, the mask, r = b - v and the inner product.  A kernel of its own with
 //                        an argument the other does not take, so that a handle without the term launches the symbol,
 //                        the arguments and the code it launched before the term existed.  Scalar spaces only.
+//   EQLB_GATHER_ROBIN 2  k_primal_gather_spring the same for the spring term of a blocked space, BS = 2, one column
+//                        (include/eqlb.h: eqlb_elasticity_set_springs): row e = 2 d + r gets t_f[i][r] = Kw[r][0] m[i][0] +
+//                        Kw[r][1] m[i][1] with m[i][s] = sum_j FacetMass[i][j] u[2 dof_j + s].  Again a kernel and an
+//                        argument (SpringArgs) of its own.  The table runs over the scalar DOFs d, since both rows of a
+//                        DOF lie in the same facets: a chunk of PS_THREADS rows e is PS_THREADS / 2 DOFs, and the two
+//                        lanes of a DOF find the same piece of it.
 // A row finds its facets through the table of RobinArgs: the rows of a grid-stride step of a block are one chunk of
 // PS_THREADS consecutive rows, and chunk[] says where the chunk's rows start in the sorted list of Robin rows - one
 // wave-uniform read per chunk.  Only a chunk that holds a Robin row searches (bisection inside its piece of the list).
-#if EQLB_GATHER_ROBIN
+#if EQLB_GATHER_ROBIN == 2
+#define EQLB_GATHER_NAME k_primal_gather_spring
+#define EQLB_GATHER_TABLE SpringArgs
+#define EQLB_GATHER_KEY d // what rows[] holds: the scalar DOF
+#elif EQLB_GATHER_ROBIN
 #define EQLB_GATHER_NAME k_primal_gather_robin
+#define EQLB_GATHER_TABLE RobinArgs
+#define EQLB_GATHER_KEY e // what rows[] holds: the row
 #else
 #define EQLB_GATHER_NAME k_primal_gather
 #endif
@@ -21,14 +33,16 @@ template <int BS, int NC>
 __global__ void __launch_bounds__(PS_THREADS) EQLB_GATHER_NAME(const GatherArgs a
 #if EQLB_GATHER_ROBIN
                                                                ,
-                                                               const RobinArgs rx
+                                                               const EQLB_GATHER_TABLE rx
 #endif
 )
 {
 #pragma clang fp contract(off)
   static_assert(BS == 1 || NC == 1, "columns for scalar spaces only");
-#if EQLB_GATHER_ROBIN
+#if EQLB_GATHER_ROBIN == 1
   static_assert(BS == 1, "the Robin term for scalar spaces only");
+#elif EQLB_GATHER_ROBIN == 2
+  static_assert(BS == 2 && NC == 1, "the spring term for one column of a blocked space only");
 #endif
   __shared__ double sh[NC][PS_THREADS];
   const uint32_t live = cols_live<NC>(a.cols);
@@ -86,13 +100,13 @@ __global__ void __launch_bounds__(PS_THREADS) EQLB_GATHER_NAME(const GatherArgs 
         while (lo < hi)
         {
           const int mid = (lo + hi) >> 1;
-          if (rx.rows[mid] < e)
+          if (rx.rows[mid] < EQLB_GATHER_KEY)
             lo = mid + 1;
           else
             hi = mid;
         }
         rb = re = 0;
-        if (lo < c1 && rx.rows[lo] == e)
+        if (lo < c1 && rx.rows[lo] == EQLB_GATHER_KEY)
         {
           rb = rx.off[lo];
           re = rx.off[lo + 1];
@@ -105,6 +119,27 @@ __global__ void __launch_bounds__(PS_THREADS) EQLB_GATHER_NAME(const GatherArgs 
         const int64_t li = en >> 3;
         const int32_t* dd = rx.dofs + li * ROBIN_ROW;
         double tv;
+#if EQLB_GATHER_ROBIN == 2
+        const double* kw = rx.kw + 3 * li; // row r of Kw: (kw[r], kw[r + 1])
+        if (!rx.u)
+          tv = kw[2 * r] * rx.fm[i * rx.n1 + i]; // (the diagonal: Kw[r][r])
+        else
+        {
+          double m0 = 0.0, m1 = 0.0;
+          for (int j = 0; j < rx.n1; ++j)
+          {
+            const int64_t ej = 2 * (int64_t)dd[j];
+            const double f = rx.fm[i * rx.n1 + j];
+            const double u0 = (rx.only_fixed && !rx.fixed[ej]) ? 0.0 : rx.u[ej];
+            const double u1 = (rx.only_fixed && !rx.fixed[ej + 1]) ? 0.0 : rx.u[ej + 1];
+            const double p0 = f * u0, p1 = f * u1;
+            m0 = j == 0 ? p0 : m0 + p0;
+            m1 = j == 0 ? p1 : m1 + p1;
+          }
+          tv = kw[r] * m0 + kw[r + 1] * m1;
+        }
+        v = v + tv;
+#else
         if (!rx.u)
           tv = rx.fm[i * rx.n1 + i]; // (the diagonal)
         else
@@ -120,6 +155,7 @@ __global__ void __launch_bounds__(PS_THREADS) EQLB_GATHER_NAME(const GatherArgs 
           }
         }
         v = v + rx.w[li] * tv;
+#endif
       }
 #endif
       const int64_t x = k * n + e;
@@ -155,3 +191,5 @@ __global__ void __launch_bounds__(PS_THREADS) EQLB_GATHER_NAME(const GatherArgs 
     a.part[(int64_t)(2 * t) * gridDim.x + blockIdx.x] = sh[t][0];
 }
 #undef EQLB_GATHER_NAME
+#undef EQLB_GATHER_TABLE
+#undef EQLB_GATHER_KEY

@@ -20,7 +20,9 @@
 #include "eqlb_primal_common.h"
 
 #include <climits>
+#include <functional>
 #include <memory>
+#include <vector>
 
 namespace eqlb
 {
@@ -80,11 +82,30 @@ struct MatrixView
   DiffArgs dx;
   const uint8_t* fixed = nullptr;
   MatrixPattern* pattern = nullptr;
-  // the Robin term (bs = 1), the table of a sum pass on the diagonal: robin_m rows lie in a Robin facet
+  // the Robin term (bs = 1) or the spring term (bs = 2), the table of a sum pass on the diagonal: robin_m rows
+  // (bs = 2: DOFs) lie in a listed facet
   bool has_robin = false;
   int32_t robin_m = 0;
   RobinArgs robin{};
+  SpringArgs spring{};
 };
+
+// What the planner of a facet term leaves for the setter that called it (eqlb_primal_solve.hip: facet_term_plan): the
+// device arrays a handle takes over, the sizes of the table's pieces (RobinLayout), and on the host the weight and the
+// flag of every listed facet (1: a boundary facet; anything else was skipped).  `refuse` is asked per facet, in the
+// order of the list and behind the tests on the facet itself, in host memory space: the caller's coefficient test.
+// chunk_dofs: the DOFs of a chunk of PS_THREADS rows of the sum pass, PS_THREADS / bs.
+struct FacetTermPlan
+{
+  DevBuf<int32_t> tab; // facets [n] | dofs [n][ROBIN_ROW] | chunk | rows [m] | off [m + 1] | ent
+  DevBuf<double> val;  // w [n] = alpha_f |E_f| | alpha [n] | FacetMass<p> [(p + 1)^2]
+  size_t nchunk = 0, m = 0, nent = 0;
+  std::vector<double> w;
+  std::vector<int32_t> flag;
+};
+int facet_term_plan(const char* who, eqlb_mesh* mesh, int p, int64_t ndofs, int chunk_dofs, int32_t nlist,
+                    const int32_t* facets, double alpha, const double* facet_alpha, int32_t memspace, hipStream_t stream,
+                    const std::function<int(int32_t)>& refuse, FacetTermPlan& out);
 void primal_matrix_view(eqlb_primal* h, MatrixView& v);         // eqlb_primal_solve.hip
 void elasticity_matrix_view(eqlb_elasticity* h, MatrixView& v); // eqlb_primal_elasticity.hip
 
@@ -151,13 +172,15 @@ struct SolverHandle
   PcgWork wide{};
   // the reaction term and, for the Poisson unit, the diffusion tensor (solver_set_cell_term)
   CellTerm react{REACTION}, diff{DIFFUSION};
-  // the Robin term (eqlb_primal_set_robin, the Poisson unit): off as created.  Both arrays are allocated by a call that
-  // brings a list and replaced as a whole by the next one
+  // the Robin term (eqlb_primal_set_robin, the Poisson unit) or the spring term (eqlb_elasticity_set_springs, the
+  // elasticity unit: robin_val holds |E_f| with alpha = 1, the tensors lie in spring_kw): off as created.  The arrays
+  // are allocated by a call that brings a list and replaced as a whole by the next one
   bool has_robin = false, robin_pos = false; // robin_pos: some w_f > 0 - the operator is definite without a fixed DOF
   int32_t robin_n = 0;                       // listed facets
   DevBuf<int32_t> robin_tab;                 // the pieces of RobinLayout ...
   RobinLayout robin_at;                      // ... and where they lie
   DevBuf<double> robin_val;                  // w [n] | alpha [n] | FacetMass<p> [(p + 1)^2]
+  DevBuf<double> spring_kw;                  // bs = 2: Kw [n][3] = |E_f| (k00, k01, k11) | K [n][3]
   // the CSR pattern of the operator (eqlb_primal_matrix.hip): empty until eqlb_*_matrix_pattern
   MatrixPattern pattern;
 };
@@ -234,6 +257,14 @@ RobinArgs robin_args(const H& h, const double* u, bool only_fixed)
   return x;
 }
 
+// ... and of its spring term (bs = 2): u [2 ndofs] blocked
+template <class H>
+SpringArgs spring_args(const H& h, const double* u, bool only_fixed)
+{
+  const RobinArgs r = robin_args(h, u, only_fixed);
+  return SpringArgs{r.chunk, r.rows, r.off, r.ent, r.dofs, h.spring_kw.get(), r.fm, u, r.fixed, r.only_fixed, r.n1};
+}
+
 template <class H>
 GatherArgs gather_args(const H& h, const ManyCols& c, bool masked)
 {
@@ -261,8 +292,8 @@ hipError_t launch_gather(const H& h, const GatherArgs& g, hipStream_t stream)
   return hipGetLastError();
 }
 
-// the sum pass behind a store pass of the OPERATOR (u: what that pass read, nullptr: the diagonal): with a Robin term on
-// the handle the variant that adds the facet values, else the launch above.  The sum pass of the load and of the
+// the sum pass behind a store pass of the OPERATOR (u: what that pass read, nullptr: the diagonal): with a Robin term
+// (bs = 1) or a spring term (bs = 2) on the handle the variant that adds the facet values, else the launch above.  The sum pass of the load and of the
 // restriction of a hierarchy (enqueue_owner_sum) never carries the term
 template <class H>
 hipError_t launch_gather_op(const H& h, const GatherArgs& g, const double* u, bool only_fixed, hipStream_t stream)
@@ -276,6 +307,14 @@ hipError_t launch_gather_op(const H& h, const GatherArgs& g, const double* u, bo
         hipLaunchKernelGGL((k_primal_gather_robin<1, 1>), grid, block, 0, stream, g, x);
       else
         hipLaunchKernelGGL((k_primal_gather_robin<1, MANY_R>), grid, block, 0, stream, g, x);
+      return hipGetLastError();
+    }
+  if constexpr (H::bs == 2)
+    if (h.has_robin)
+    {
+      const SpringArgs x = spring_args(h, u, only_fixed);
+      hipLaunchKernelGGL((k_primal_gather_spring<2, 1>), dim3(stream_blocks(2 * h.ndofs)), dim3(PS_THREADS), 0, stream, g,
+                         x);
       return hipGetLastError();
     }
   return launch_gather(h, g, stream);
@@ -383,6 +422,13 @@ void solver_matrix_view(H* h, MatrixView& v)
       v.robin_m = (int32_t)h->robin_at.m();
       v.robin = robin_args(*h, nullptr, false);
     }
+  if constexpr (H::bs == 2)
+    if (h->has_robin)
+    {
+      v.has_robin = true;
+      v.robin_m = (int32_t)h->robin_at.m();
+      v.spring = spring_args(*h, nullptr, false);
+    }
 }
 
 // ---- the C entries behind their names (`who`) -------------------------------------------------------------------------
@@ -391,6 +437,105 @@ inline int check_handle(const char* who, const void* h)
   if (!h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null handle", who);
   return EQLB_OK;
+}
+
+// what a setter of a facet term checks about its list
+inline int check_facet_list(const char* who, int32_t nlist, const int32_t* facets)
+{
+  if (nlist < 0 || (nlist > 0 && !facets))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d, or a null list", who, (int)nlist);
+  if (nlist >= (1 << 28))
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d: at most 2^28 - 1 facets", who, (int)nlist);
+  return EQLB_OK;
+}
+
+// the end of a setter of a facet term, an empty list: the term off, the diagonal formed again
+template <class H>
+int solver_facet_term_off(H* h, int32_t memspace, hipStream_t stream)
+{
+  h->has_robin = h->robin_pos = false;
+  h->robin_n = 0;
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (memspace == EQLB_MEM_HOST)
+    HIP_TRY(hipStreamSynchronize(stream));
+  return EQLB_OK;
+}
+
+// ... and with a plan (FacetTermPlan): its arrays in the place of the old ones, the diagonal formed again.  kw: the
+// tensor weights of a spring term (bs = 2), which go in here with the rest, so that nothing of the handle changes before
+// this point
+template <class H>
+int solver_facet_term_commit(H* h, FacetTermPlan& plan, int32_t nlist, bool positive, int32_t memspace,
+                             hipStream_t stream, DevBuf<double>* kw = nullptr)
+{
+  if (kw)
+    h->spring_kw = std::move(*kw);
+  h->robin_tab = std::move(plan.tab);
+  h->robin_val = std::move(plan.val);
+  h->robin_n = nlist;
+  h->robin_at = RobinLayout((size_t)nlist, plan.nchunk, plan.m, plan.nent);
+  h->has_robin = true;
+  h->robin_pos = positive;
+  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
+  if (memspace == EQLB_MEM_HOST)
+    HIP_TRY(hipStreamSynchronize(stream));
+  return EQLB_OK;
+}
+
+// the points of eqlb_primal_robin_flux and eqlb_elasticity_spring_flux, a kernel argument
+constexpr int RF_MAX_NQ = 64;
+struct RobinRule
+{
+  double s[RF_MAX_NQ];
+};
+
+// A point of a listed facet for the flux kernels, the rule of eqlb_primal_robin_flux (include/eqlb.h): the facet
+// parameter sq of the frame of eqlb_facet_points (the facet seen from its one cell, the low local vertex first) becomes
+// the parameter of the facet's own frame (0 at the lower node id), sq or 1 - sq, and l[j] the value there of the
+// equispaced 1-D Lagrange basis in the facet-local order: the product over the other nodes k, in that order, of
+// (s - x_k) / (x_j - x_k) with x = (0, 1, 1/p ... (p-1)/p) formed as j / p, the first factor starts it, every operation
+// rounded on its own.  dd: the facet's rows (k_robin_prepare; dd[0] < 0: skipped).  False, and nothing written, for a
+// facet the list skipped or whose cell does not hold it; every index is checked before it is used.  k_spring_flux uses
+// it; k_robin_flux holds the same lines in its body, as it did before this helper existed.
+__device__ __forceinline__ bool facet_point_basis(int32_t f, const int32_t* dd, double sq, int p, int32_t ncells,
+                                                  const int32_t* cell_nodes, const int32_t* cell_facets,
+                                                  const int32_t* fco, const int32_t* facet_cells, double* l)
+{
+#pragma clang fp contract(off)
+  int lf = -1;
+  int32_t cell = -1;
+  if (dd[0] >= 0)
+  {
+    cell = facet_cells[fco[f]];
+    if (cell >= 0 && cell < ncells)
+      for (int k = 0; k < 3; ++k)
+        if (cell_facets[(int64_t)cell * 3 + k] == f)
+          lf = k;
+  }
+  if (lf < 0)
+    return false;
+  const int va = (lf == 0) ? 1 : 0, vb = (lf == 2) ? 1 : 2; // the low local vertex first
+  const bool same = cell_nodes[(int64_t)cell * 3 + va] < cell_nodes[(int64_t)cell * 3 + vb];
+  const double s = same ? sq : 1.0 - sq;
+  double xn[PS_PMAX + 1];
+  xn[0] = 0.0;
+  xn[1] = 1.0;
+  for (int j = 1; j < p; ++j)
+    xn[1 + j] = (double)j / (double)p;
+  for (int j = 0; j <= p; ++j)
+  {
+    double v = 1.0;
+    bool first = true;
+    for (int k = 0; k <= p; ++k)
+      if (k != j)
+      {
+        const double fac = (s - xn[k]) / (xn[j] - xn[k]);
+        v = first ? fac : v * fac;
+        first = false;
+      }
+    l[j] = v;
+  }
+  return true;
 }
 
 // what every *_many entry checks about its column count

@@ -310,6 +310,64 @@ __global__ void __launch_bounds__(MX_THREADS) k_matrix_robin(const RobinFillArgs
   }
 }
 
+// The spring term of an elasticity handle (include/eqlb.h: eqlb_elasticity_set_springs), the bs = 2 counterpart: one
+// thread per DOF d that lies in a spring facet walks the facets of the DOF in ascending id and adds Kw[r][s]
+// FacetMass[i][j] to the entry (2 d + r, 2 d_j + s) of every DOF d_j of the facet, each by one addition.  The pattern
+// is the scalar one and every pair of DOFs of a cell carries its full 2 x 2 block, so every such entry exists: row
+// 2 d + r starts at 4 sptr[d] + 2 r len(d), and pair k of the row holds the columns at 2 k + s.
+struct SpringFillArgs
+{
+  int32_t m, n1;
+  const int32_t *rows, *off, *ent, *dofs;
+  const double *kw, *fm;
+  const uint8_t* fixed; // [2 ndofs]; nullptr: the raw operator
+  const int64_t* sptr;
+  const int32_t* scol;
+  double* values;
+};
+
+__global__ void __launch_bounds__(MX_THREADS) k_matrix_spring(const SpringFillArgs a)
+{
+#pragma clang fp contract(off)
+  for (int32_t mi = blockIdx.x * MX_THREADS + threadIdx.x; mi < a.m; mi += gridDim.x * MX_THREADS)
+  {
+    const int64_t d = a.rows[mi];
+    const int64_t p0 = a.sptr[d], p1 = a.sptr[d + 1], len = p1 - p0;
+    for (int q = a.off[mi]; q < a.off[mi + 1]; ++q)
+    {
+      const int32_t en = a.ent[q];
+      const int i = en & 7;
+      const int64_t li = en >> 3;
+      const int32_t* dd = a.dofs + li * ROBIN_ROW;
+      const double* kw = a.kw + 3 * li;
+      for (int j = 0; j < a.n1; ++j)
+      {
+        const int32_t dc = dd[j];
+        int64_t lo = p0, hi = p1;
+        while (lo < hi)
+        {
+          const int64_t mid = (lo + hi) >> 1;
+          if (a.scol[mid] < dc)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        if (!(lo < p1 && a.scol[lo] == dc))
+          continue;
+        const double f = a.fm[i * a.n1 + j];
+        for (int r = 0; r < 2; ++r)
+          for (int s = 0; s < 2; ++s)
+          {
+            if (a.fixed && (a.fixed[2 * d + r] || a.fixed[2 * (int64_t)dc + s]))
+              continue;
+            const int64_t pos = 4 * p0 + r * 2 * len + 2 * (lo - p0) + s;
+            a.values[pos] = a.values[pos] + kw[r + s] * f;
+          }
+      }
+    }
+  }
+}
+
 // y[row] = the sum over the positions of the row in ascending order, the first product starts it.  One row per thread;
 // a bundle of G consecutive rows (the rows of G neighbouring lanes) one of which has CSR_GROUP_MIN entries or more is
 // summed by the G lanes together, row after row: the lanes read G consecutive entries of the row at once and form the
@@ -555,6 +613,14 @@ int matrix_values(const char* who, const MatrixView& v, int32_t eliminate, doubl
     const RobinFillArgs a{v.robin_m, x.n1, x.rows, x.off, x.ent, x.dofs, x.w, x.fm, eliminate ? v.fixed : nullptr,
                           v.pattern->sptr.get(), v.pattern->scol.get(), pv};
     hipLaunchKernelGGL(k_matrix_robin, dim3(mx_blocks(v.robin_m)), dim3(MX_THREADS), 0, stream, a);
+    s.note(hipGetLastError());
+  }
+  if (v.bs == 2 && v.has_robin && v.robin_m > 0)
+  {
+    const SpringArgs& x = v.spring;
+    const SpringFillArgs a{v.robin_m, x.n1, x.rows, x.off, x.ent, x.dofs, x.kw, x.fm, eliminate ? v.fixed : nullptr,
+                           v.pattern->sptr.get(), v.pattern->scol.get(), pv};
+    hipLaunchKernelGGL(k_matrix_spring, dim3(mx_blocks(v.robin_m)), dim3(MX_THREADS), 0, stream, a);
     s.note(hipGetLastError());
   }
   HIP_TRY(s.finish(stream));

@@ -34,6 +34,7 @@
 #include "eqlb_tables_gen.h"
 
 #include <algorithm>
+#include <functional>
 #include <cmath>
 #include <unordered_set>
 #include <vector>
@@ -271,12 +272,6 @@ k_robin_prepare(int32_t nlist, const int32_t* __restrict__ facets, double alpha,
     dd[2 + j] = j < ne ? nnodes + f * ne + j : -1;
 }
 
-constexpr int RF_MAX_NQ = 64;
-struct RobinRule
-{
-  double s[RF_MAX_NQ];
-};
-
 // One thread per (listed facet, point): out[i][q] = alpha_i (u_h(x_q) - u_ext[i][q]) at the facet parameter s_q in the
 // frame of eqlb_facet_points (the facet seen from its one cell, the low local vertex first).  The parameter of the
 // facet's own frame (0 at the lower node id) is s or 1 - s; l_j is the product over the other nodes k, in the local
@@ -348,40 +343,27 @@ const double* facet_mass_of(int p)
                          : p == 3 ? eqlb_tables::FacetMass<3>::FM : eqlb_tables::FacetMass<4>::FM;
 }
 
-// the body of eqlb_primal_set_robin.  The list is prepared on the device into fresh arrays, looked at on the host, where
-// the table of the sum pass is built (the listed facets are O(sqrt N)), and only then put in the place of the old ones:
-// a refused call leaves the handle as it was.  The call waits for the stream in both memory spaces.
-int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32_t* facets, double alpha,
-                     const double* facet_alpha, int32_t memspace, void* stream_)
+} // namespace
+
+// The planner of a facet term (eqlb_primal_handle.h: FacetTermPlan), shared by eqlb_primal_set_robin and
+// eqlb_elasticity_set_springs.  The list (nlist >= 1) is prepared on the device into fresh arrays, looked at on the
+// host, where the table of the sum pass is built (the listed facets are O(sqrt N)); nothing of a handle is touched, so
+// that a refused call leaves it as it was.  The call waits for the stream in both memory spaces.
+int facet_term_plan(const char* who, eqlb_mesh* mesh, int p, int64_t ndofs, int chunk_dofs, int32_t nlist,
+                    const int32_t* facets, double alpha, const double* facet_alpha, int32_t memspace, hipStream_t stream,
+                    const std::function<int(int32_t)>& refuse, FacetTermPlan& out)
 {
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  if (nlist < 0 || (nlist > 0 && !facets))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d, or a null list", who, (int)nlist);
-  if (nlist >= (1 << 28))
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d: at most 2^28 - 1 facets", who, (int)nlist);
-  if (!facet_alpha)
-    EQLB_TRY(check_scalar(who, "alpha", *FACET_ALPHA.rule, alpha));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const bool host = memspace == EQLB_MEM_HOST;
-  const DeviceMesh& m = h->mesh->m;
+  const DeviceMesh& m = mesh->m;
   const size_t n = (size_t)nlist;
-  const int n1 = h->p + 1;
-  if (nlist == 0)
-  {
-    h->has_robin = h->robin_pos = false;
-    h->robin_n = 0;
-    HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
-    if (host)
-      HIP_TRY(hipStreamSynchronize(stream));
-    return EQLB_OK;
-  }
-  DevBuf<double> val;
+  const int n1 = p + 1;
+  DevBuf<double>& val = out.val;
   DevBuf<int32_t> head; // facets | dofs | flag
   if (val.alloc_raw(2 * n + (size_t)n1 * n1) != hipSuccess || head.alloc_raw(n * (2 + ROBIN_ROW)) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
   std::vector<int32_t> hh(n * (2 + ROBIN_ROW));
-  std::vector<double> hw(n);
+  std::vector<double>& hw = out.w;
+  hw.assign(n, 0.0);
   {
     HostCall s;
     const auto d_f = s.in(host ? facets : nullptr, n);
@@ -390,11 +372,11 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
       HIP_TRY(s.upload(stream));
     int32_t* flist = head.get();
     hipLaunchKernelGGL(k_robin_prepare, dim3(grid_of(nlist, PS_THREADS)), dim3(PS_THREADS), 0, stream, nlist,
-                       host ? d_f.get() : facets, alpha, host ? d_a.get() : facet_alpha, m.nnodes, m.nfacets, h->space.ne,
+                       host ? d_f.get() : facets, alpha, host ? d_a.get() : facet_alpha, m.nnodes, m.nfacets, p - 1,
                        m.x, m.facet_nodes, m.facet_cells_off, flist, flist + n, flist + n * (1 + ROBIN_ROW), val.get(),
                        val.get() + n);
     s.note(hipGetLastError());
-    s.note(hipMemcpyAsync(val.get() + 2 * n, facet_mass_of(h->p), (size_t)n1 * n1 * sizeof(double),
+    s.note(hipMemcpyAsync(val.get() + 2 * n, facet_mass_of(p), (size_t)n1 * n1 * sizeof(double),
                           hipMemcpyHostToDevice, stream));
     s.note(hipMemcpyAsync(hh.data(), head.get(), hh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     s.note(hipMemcpyAsync(hw.data(), val.get(), n * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -413,8 +395,7 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
                     (int)facets[i]);
       if (!seen.insert(facets[i]).second)
         return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: facets[%d] = %d is listed twice", who, (int)i, (int)facets[i]);
-      if (facet_alpha && !FACET_ALPHA.rule->ok(facet_alpha[i]))
-        return fail_cell(who, FACET_ALPHA, facet_alpha, i);
+      EQLB_TRY(refuse(i));
     }
   }
   // the entries (row, facet, list position, local index), sorted by row, then facet, then position
@@ -423,19 +404,17 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
     int32_t row, facet, pos, loc;
   };
   std::vector<Entry> ent;
-  bool positive = false;
   for (int32_t i = 0; i < nlist; ++i)
   {
     if (hflag[i] != 1)
       continue; // (device memory space: skipped)
-    positive = positive || hw[(size_t)i] > 0.0;
     for (int j = 0; j < n1; ++j)
       ent.push_back(Entry{hd[(size_t)i * ROBIN_ROW + j], hh[(size_t)i], i, j});
   }
   std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) {
     return a.row != b.row ? a.row < b.row : a.facet != b.facet ? a.facet < b.facet : a.pos < b.pos;
   });
-  const size_t nch = (size_t)((h->ndofs + PS_THREADS - 1) / PS_THREADS);
+  const size_t nch = (size_t)((ndofs + chunk_dofs - 1) / chunk_dofs);
   std::vector<int32_t> rows, off, packed(ent.size());
   for (size_t k = 0; k < ent.size(); ++k)
   {
@@ -449,7 +428,7 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
   off.push_back((int32_t)ent.size());
   std::vector<int32_t> chunk(nch + 1);
   for (size_t c = 0; c <= nch; ++c)
-    chunk[c] = (int32_t)(std::lower_bound(rows.begin(), rows.end(), (int32_t)std::min<int64_t>((int64_t)c * PS_THREADS,
+    chunk[c] = (int32_t)(std::lower_bound(rows.begin(), rows.end(), (int32_t)std::min<int64_t>((int64_t)c * chunk_dofs,
                                                                                               INT32_MAX))
                          - rows.begin());
   chunk[nch] = (int32_t)rows.size();
@@ -461,21 +440,43 @@ int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32
   std::copy(rows.begin(), rows.end(), tab.begin() + (std::ptrdiff_t)at.rows);
   std::copy(off.begin(), off.end(), tab.begin() + (std::ptrdiff_t)at.off);
   std::copy(packed.begin(), packed.end(), tab.begin() + (std::ptrdiff_t)at.ent);
-  DevBuf<int32_t> dtab;
+  DevBuf<int32_t>& dtab = out.tab;
   if (dtab.alloc_raw(at.total) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
   HIP_TRY(hipMemcpyAsync(dtab.get(), tab.data(), at.total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipStreamSynchronize(stream)); // (tab ends with this call; nothing on the stream reads the old table any more)
-  h->robin_tab = std::move(dtab);
-  h->robin_val = std::move(val);
-  h->robin_n = nlist;
-  h->robin_at = at;
-  h->has_robin = true;
-  h->robin_pos = positive;
-  HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
-  if (host)
-    HIP_TRY(hipStreamSynchronize(stream));
+  out.nchunk = chunk.size();
+  out.m = rows.size();
+  out.nent = packed.size();
+  out.flag.assign(hflag, hflag + n);
   return EQLB_OK;
+}
+
+namespace
+{
+// the body of eqlb_primal_set_robin: the plan above, and only then the new arrays in the place of the old ones
+int primal_set_robin(const char* who, eqlb_primal* h, int32_t nlist, const int32_t* facets, double alpha,
+                     const double* facet_alpha, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  EQLB_TRY(check_facet_list(who, nlist, facets));
+  if (!facet_alpha)
+    EQLB_TRY(check_scalar(who, "alpha", *FACET_ALPHA.rule, alpha));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (nlist == 0)
+    return solver_facet_term_off(h, memspace, stream);
+  FacetTermPlan plan;
+  EQLB_TRY(facet_term_plan(
+      who, h->mesh, h->p, h->ndofs, PS_THREADS, nlist, facets, alpha, facet_alpha, memspace, stream,
+      [&](int32_t i) {
+        return facet_alpha && !FACET_ALPHA.rule->ok(facet_alpha[i]) ? fail_cell(who, FACET_ALPHA, facet_alpha, i) : EQLB_OK;
+      },
+      plan));
+  bool positive = false;
+  for (int32_t i = 0; i < nlist; ++i)
+    positive = positive || (plan.flag[(size_t)i] == 1 && plan.w[(size_t)i] > 0.0);
+  return solver_facet_term_commit(h, plan, nlist, positive, memspace, stream);
 }
 } // namespace
 

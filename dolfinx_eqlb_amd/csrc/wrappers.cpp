@@ -561,6 +561,51 @@ struct PrimalElasticity
     const OptArray kc = opt_array(cell_mu, mesh->ncells, "PrimalElasticity.set_shear: cell_mu [ncells] expected");
     check(eqlb_elasticity_set_shear(h, mu, kc.p, EQLB_MEM_HOST, nullptr));
   }
+  // the spring term int_E v^T K u over the listed boundary facets: facet_k [nlist, 3] = (k00, k01, k11) where given,
+  // else k I; an empty list switches the term off
+  void set_springs(carray<int32_t> facets, double k, py::object facet_k)
+  {
+    carray<double> fk;
+    if (!facet_k.is_none())
+    {
+      fk = facet_k.cast<carray<double>>();
+      if (fk.size() != 3 * facets.size())
+        throw std::runtime_error("PrimalElasticity.set_springs: facet_k [nlist, 3] expected");
+    }
+    check(eqlb_elasticity_set_springs(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, k,
+                                      !facet_k.is_none() && fk.size() ? fk.data() : nullptr, EQLB_MEM_HOST, nullptr));
+  }
+  int spring_count() const
+  {
+    int32_t n = 0;
+    check(eqlb_elasticity_spring_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
+    return n;
+  }
+  darray spring_weights() const
+  {
+    int32_t n = spring_count();
+    darray w({(py::ssize_t)n, (py::ssize_t)3});
+    if (n)
+      check(eqlb_elasticity_spring_weights(h, &n, w.mutable_data(), n, EQLB_MEM_HOST, nullptr));
+    return w;
+  }
+  // out [2, nlist, nq] = K_i (u_h(x_q) - u_ext[.][i][q]) on the spring list at the facet parameters s [nq]
+  darray spring_flux(darray u, darray s, py::object u_ext) const
+  {
+    need(u, "spring_flux");
+    const int32_t n = spring_count();
+    darray e;
+    if (!u_ext.is_none())
+    {
+      e = u_ext.cast<darray>();
+      if (e.size() != 2 * (py::ssize_t)n * s.size())
+        throw std::runtime_error("PrimalElasticity.spring_flux: u_ext [2, nlist, nq] expected");
+    }
+    darray out({(py::ssize_t)2, (py::ssize_t)n, (py::ssize_t)s.size()});
+    check(eqlb_elasticity_spring_flux(h, u.data(), (int32_t)s.size(), s.data(), u_ext.is_none() ? nullptr : e.data(),
+                                      out.mutable_data(), EQLB_MEM_HOST, nullptr));
+    return out;
+  }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
     if (degree_dg >= 0 && degree_dg <= 3
@@ -1681,6 +1726,17 @@ PYBIND11_MODULE(_cpp, m)
            "the stress becomes mu (2 eps(u) + pi_1 div(u) I): cell_mu [ncells] where given, else the scalar, mu > 0; "
            "mu = 1 without an array switches the term off; the reaction term is not scaled; "
            "Multilevel.set_coarse(True) has to be called again afterwards")
+      .def("set_springs", &PrimalElasticity::set_springs, py::arg("facets"), py::arg("k") = 1.0,
+           py::arg("facet_k") = py::none(),
+           "the operator gains int_E v^T K u over the listed boundary facets: facet_k [nlist, 3] = (k00, k01, k11) where "
+           "given, else k I; an empty list switches the term off; Multilevel.set_coarse(True) has to be called again "
+           "afterwards")
+      .def("spring_count", &PrimalElasticity::spring_count, "the number of listed facets of the spring term")
+      .def("spring_weights", &PrimalElasticity::spring_weights,
+           "Kw_f = |E_f| (k00, k01, k11) [nlist, 3] in the order of the list")
+      .def("spring_flux", &PrimalElasticity::spring_flux, py::arg("u"), py::arg("s"), py::arg("u_ext") = py::none(),
+           "out [2, nlist, nq] = K_i (u_h(x_q) - u_ext[.][i][q]) on the spring list at the facet parameters s: row r "
+           "holds the point values of the flux condition of stress row r (update_flux_bc with vector = False)")
       .def("load", &PrimalElasticity::load, py::arg("degree_dg"), py::arg("rhs_dg"), py::arg("b_extra") = py::none(),
            "b [2 ndofs] from DG_d nodal values rhs_dg [2, ncells*nd_d], + b_extra where given")
       .def("apply", &PrimalElasticity::apply, py::arg("u"), py::arg("masked") = false,

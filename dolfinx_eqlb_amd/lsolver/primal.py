@@ -75,7 +75,28 @@ facet is allowed.  Refused by facet, before anything changes: a listed facet tha
 twice, an alpha that is negative, NaN or infinite.  With some alpha_f > 0 the operator is positive definite without a
 fixed DOF, and pcg no longer asks for one.  The owner sum of the load and of the restriction of a hierarchy stays plain.
 robin_flux states eqlb_primal_robin_flux, alpha (u_h - u_ext) at points of the listed facets: the flux condition
-sigma_eq . n of the equilibrator that the discrete solution implies.  Springs on an elasticity operator are not provided.
+sigma_eq . n of the equilibrator that the discrete solution implies.
+
+THE SPRING TERM (ElasticityOperator.set_springs; eqlb_elasticity_set_springs): the counterpart on the blocked space,
+sigma(u) n = -K_f (u - u_ext) on the listed boundary facets with K_f a symmetric positive semidefinite 2 x 2 tensor per
+facet in global axes, facet_k [nlist][3] = (k00, k01, k11), the layout of cell_D - an elastic foundation, a compliant
+support, a penalised sliding (K = kn n x n, spring_tensor) or clamped side.  The operator gains int_E v^T K u; the datum
+int_E v^T K u_ext is a load (spring_load).  FacetMass<p> and the local order of a facet are those of the Robin term.
+  Kw_f      = (|E_f| k00, |E_f| k01, |E_f| k11), |E_f| of facet_lengths, one product per entry; formed once at
+              set_springs and kept (spring_weights)
+  m[i][s]   = sum_j FacetMass[i][j] u[2 dof_j + s], ascending j, every product rounded on its own
+  t_f[i][r] = Kw[r][0] m[i][0] + Kw[r][1] m[i][1]: two products and one addition, no fused multiply-add
+  row 2d+r  : the owner sum, then the t_f[i][r] of the spring facets that hold d, in ascending facet id, each by one
+              addition; everything behind that unchanged, the lifting reads a free row 2 dof_j + s as 0 here too
+  diagonal  : the owner sum, then + Kw[r][r] FacetMass[i][i] in the same place
+  matrix    : + Kw[r][s] FacetMass[i][j] on entry (2 d_i + r, 2 d_j + s) after the cell sums, facets ascending; the
+              blocked pattern holds the full 2 x 2 block of every pair of DOFs of a cell, hence of a facet
+Refused by facet in list order, before anything changes (spring_list): no boundary facet, listed twice, an entry that
+is not finite, k00 < 0, k11 < 0, k01 k01 > (k00 k11) (1 + 2^-49) - the allowance lets a rank-one tensor formed in
+floating point as kn n_a n_b pass.  With some listed facet of |E_f| > 0 and K_f positive definite, k00 > 0 and
+k01 k01 < (k00 k11) (1 - 2^-49), no rigid motion is left and pcg asks for no Dirichlet DOF in either component
+(spring_positive); a list of rank-one tensors leaves the per-component rule as it was.  spring_flux states
+eqlb_elasticity_spring_flux, K (u_h - u_ext) at points of the listed facets: row r is the flux condition of stress row r.
 
 value_dg states eqlb_primal_value_dg, the piece that turns c u_h into the right-hand side the equilibrator needs
 (rhs = Pi_d f - c_T Pi_d u_h): out[r][c][n] = coeff[c] sum_i PV<p,d>[n][i] u[r][cell_dofs[c][i]], ascending i, every
@@ -342,6 +363,134 @@ def robin_flux(mesh, p, facets, facet_alpha, u, s, u_ext=None):
     if u_ext is not None:
         v = v - np.asarray(u_ext, dtype=np.float64).reshape(v.shape)
     return np.asarray(facet_alpha, dtype=np.float64).ravel()[:, None] * v
+
+
+SPRING_ALLOWANCE = 2.0 ** -49   # of the semidefiniteness test of a spring tensor (the head of this file)
+
+
+def spring_list(who, mesh, facets, k=1.0, facet_k=None):
+    """(facets int64 [n], K [n, 3]) of set_springs in the order given, or (None, None) for an empty list; the scalar k
+    stands for K = k I.  Refused by facet, in this order: one that is no boundary facet of the mesh, one listed twice,
+    an entry of K that is not finite, k00 < 0, k11 < 0, k01 k01 > (k00 k11) (1 + 2^-49)."""
+    f = np.asarray([] if facets is None else facets, dtype=np.int64).ravel()
+    if facet_k is None:
+        kk = float(k)
+        if not (kk >= 0.0 and np.isfinite(kk)):
+            raise ValueError(f"{who}: k = {kk} is negative, NaN or infinite")
+        K = np.tile(np.array([kk, 0.0, kk]), (f.size, 1))
+    else:
+        K = np.array(facet_k, dtype=np.float64)
+        if K.size != 3 * f.size:
+            raise ValueError(f"{who}: facet_k [nlist][3] expected")
+        K = K.reshape(f.size, 3)
+    fco = mesh.facet_cells_offsets
+    seen = set()
+    for i, v in enumerate(f):
+        v = int(v)
+        if v < 0 or v >= mesh.nfacets or fco[v + 1] - fco[v] != 1:
+            raise ValueError(f"{who}: facets[{i}] = {v} is no boundary facet of the mesh")
+        if v in seen:
+            raise ValueError(f"{who}: facets[{i}] = {v} is listed twice")
+        seen.add(v)
+        k00, k01, k11 = (float(x) for x in K[i])
+        if not (np.isfinite(k00) and np.isfinite(k01) and np.isfinite(k11)):
+            raise ValueError(f"{who}: facet_k[{i}] = ({k00}, {k01}, {k11}) is not finite")
+        if k00 < 0.0:
+            raise ValueError(f"{who}: facet_k[{i}]: k00 = {k00} is negative")
+        if k11 < 0.0:
+            raise ValueError(f"{who}: facet_k[{i}]: k11 = {k11} is negative")
+        if not spring_semidefinite(K[i])[0]:
+            raise ValueError(f"{who}: facet_k[{i}] = ({k00}, {k01}, {k11}) is not positive semidefinite")
+    return (None, None) if f.size == 0 else (f, K)
+
+
+def spring_semidefinite(K):
+    """[n] bool: not k01 k01 > (k00 k11) (1 + 2^-49) - the last of the tests of spring_list, on finite tensors with
+    k00, k11 >= 0."""
+    K = np.asarray(K, dtype=np.float64).reshape(-1, 3)
+    return ~(K[:, 1] * K[:, 1] > (K[:, 0] * K[:, 2]) * (1.0 + SPRING_ALLOWANCE))
+
+
+def spring_definite(K):
+    """[n] bool: k00 > 0 and k01 k01 < (k00 k11) (1 - 2^-49), the test for a positive definite tensor."""
+    K = np.asarray(K, dtype=np.float64).reshape(-1, 3)
+    return (K[:, 0] > 0.0) & (K[:, 1] * K[:, 1] < (K[:, 0] * K[:, 2]) * (1.0 - SPRING_ALLOWANCE))
+
+
+def facet_normals(mesh, facets):
+    """[n, 2]: the outward unit normal of each listed boundary facet: (dy, -dx) / |E| of facet_nodes with the |E| of
+    facet_lengths, turned away from the vertex of the facet's cell that lies opposite."""
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    fco = mesh.facet_cells_offsets
+    for i, v in enumerate(f):
+        if v < 0 or v >= mesh.nfacets or fco[v + 1] - fco[v] != 1:
+            raise ValueError(f"facet_normals: facets[{i}] = {int(v)} is no boundary facet of the mesh")
+    fn = mesh.facet_nodes[f]
+    xa, xb = mesh.x[fn[:, 0], :2], mesh.x[fn[:, 1], :2]
+    length = facet_lengths(mesh, f)
+    n = np.stack([(xb[:, 1] - xa[:, 1]) / length, -(xb[:, 0] - xa[:, 0]) / length], axis=1)
+    cells = mesh.facet_cells[fco[f]]
+    lf = np.argmax(mesh.cell_facets[cells] == f[:, None], axis=1)
+    xo = mesh.x[mesh.cell_nodes[cells, lf], :2]
+    inward = np.sum(n * (xa - xo), axis=1) < 0.0
+    return np.where(inward[:, None], -n, n)
+
+
+def spring_tensor(mesh, facets, kn, kt=0.0):
+    """facet_k [n, 3] of K = kn n x n + kt t x t with n the outward unit normal of each listed boundary facet
+    (facet_normals) and t = (-n1, n0); kn, kt scalars or one value per facet.  Entry (a, b) is (kn n_a) n_b + (kt t_a)
+    t_b, every operation rounded on its own; with kt = 0 the second term is left out, so that the tensor is the rank-one
+    product kn n_a n_b that spring_list's allowance is made for."""
+    return spring_tensor_of_normals(facet_normals(mesh, np.asarray(facets, dtype=np.int64).ravel()), kn, kt)
+
+
+def spring_tensor_of_normals(n, kn, kt=0.0):
+    """spring_tensor on given unit normals n [m, 2]."""
+    n = np.asarray(n, dtype=np.float64).reshape(-1, 2)
+    t = np.stack([-n[:, 1], n[:, 0]], axis=1)
+    kn = np.broadcast_to(np.asarray(kn, dtype=np.float64), n.shape[:1])
+    kt = np.broadcast_to(np.asarray(kt, dtype=np.float64), n.shape[:1])
+    out = np.empty((n.shape[0], 3))
+    for c, (a, b) in enumerate(((0, 0), (0, 1), (1, 1))):
+        vn = (kn * n[:, a]) * n[:, b]
+        out[:, c] = np.where(kt == 0.0, vn, vn + (kt * t[:, a]) * t[:, b])
+    return out
+
+
+def spring_load(mesh, p, facets, facet_k, u_ext, quadrature_degree=None):
+    """b_extra [2 ndofs], blocked, = int_E phi_i (K u_ext)_r over the listed boundary facets, on the host: BY DEFINITION
+    traction_load with the traction t = K u_ext, bit for bit that call - row r gets the flux condition g_r = -t_r =
+    -(k_r0 u_ext,0 + k_r1 u_ext,1), and neumann_load returns -int_E g phi_i (the sign convention written in
+    traction_load).  facet_k [n, 3]; u_ext a callable (x, y) -> (values of component 0, values of component 1)."""
+    from types import SimpleNamespace
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    K = np.asarray(facet_k, dtype=np.float64).reshape(f.size, 3)
+
+    def row(kr0, kr1):
+        def value(x, y):
+            u0, u1 = u_ext(x, y)
+            return -(kr0 * np.asarray(u0, dtype=np.float64) + kr1 * np.asarray(u1, dtype=np.float64))
+        return value
+    bcs = [[SimpleNamespace(facets=[int(v)], scalar=True, value=row(float(kk[r]), float(kk[r + 1])))
+            for v, kk in zip(f, K)] for r in range(2)]
+    return traction_load(mesh, p, bcs, quadrature_degree)
+
+
+def spring_flux(mesh, p, facets, facet_k, u, s, u_ext=None):
+    """The statement of eqlb_elasticity_spring_flux: out [2, n, nq], out[r][i][q] = K_i[r][0] d_0 + K_i[r][1] d_1 with
+    d_s = u_h,s(x_q) - u_ext[s][i][q] on the listed facets at the facet parameters s [nq] in the frame of
+    eqlb_facet_points.  u [2 ndofs] blocked; u_h,s is robin_flux with alpha = 1 on component s (facet_basis, ascending
+    j); the contraction with K is two products and one addition.  u_ext [2, n, nq] or None (0).  Row r is what row r of
+    a stress handle takes as its flux condition: -sigma_r . n = (K (u_h - u_ext))_r."""
+    s = np.asarray(s, dtype=np.float64).ravel()
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    K = np.asarray(facet_k, dtype=np.float64).reshape(f.size, 3)
+    uu = np.asarray(u, dtype=np.float64).reshape(-1, 2)
+    ue = None if u_ext is None else np.asarray(u_ext, dtype=np.float64).reshape(2, f.size, s.size)
+    one = np.ones(f.size)
+    d = [robin_flux(mesh, p, f, one, np.ascontiguousarray(uu[:, c]), s, None if ue is None else ue[c])
+         for c in range(2)]
+    return np.stack([K[:, r, None] * d[0] + K[:, r + 1, None] * d[1] for r in range(2)])
 
 
 def value_dg(p, degree_dg, cell_dofs, u, coeff=None, op=None, return_abs=False):
@@ -827,6 +976,18 @@ class PoissonOperator:
         shape = (nc, self.nd, self.nd, 1, 1)
         return val.reshape(shape), A.reshape(shape)
 
+    def _add_facet_entries(self, V, VA, skey):
+        """The facet term on top of the cell sums V [pairs, bs, bs] (VA: the absolute sums), facets ascending."""
+        if self.robin_f is None:
+            return
+        FM = facet_mass_table(self.p)
+        for k in range(self.robin_f.size):
+            rows = self.robin_dofs[k]
+            pos = np.searchsorted(skey, rows[:, None] * self.ndofs + rows[None, :])
+            e = self.robin_w[k] * FM
+            V[pos, 0, 0] = V[pos, 0, 0] + e
+            VA[pos, 0, 0] = VA[pos, 0, 0] + e
+
     def matrix(self, eliminate=False, return_abs=False):
         """(indptr int64 [n + 1], indices int32 [nnz], values [nnz]), n = bs ndofs: the operator as CSR by the rule at the
         head of this file.  eliminate: P A P + (I - P) on the mask of set_dirichlet.  return_abs: a fourth array, the
@@ -854,14 +1015,7 @@ class PoissonOperator:
         if ni:
             q = np.arange(self.mesh.ncells * ni)
             add(self.nshared + q, q // ni, 3 * self.p + q % ni)
-        if self.robin_f is not None:
-            FM = facet_mass_table(self.p)
-            for k in range(self.robin_f.size):
-                rows = self.robin_dofs[k]
-                pos = np.searchsorted(skey, rows[:, None] * n + rows[None, :])
-                e = self.robin_w[k] * FM
-                V[pos, 0, 0] = V[pos, 0, 0] + e
-                VA[pos, 0, 0] = VA[pos, 0, 0] + e
+        self._add_facet_entries(V, VA, skey)
         # the blocked layout: row bs d + r holds the columns bs d' + s, s fastest
         length = np.diff(sptr)
         rows = np.arange(bs * n)
@@ -1040,6 +1194,79 @@ class ElasticityOperator(PoissonOperator):
         m = self.mu[:, None]
         return m * val, (None if A is None else m * A)
 
+    # the spring term (the head of this file): None without it; else the list sorted by facet id
+    spring_f = spring_k = spring_kw = spring_dofs = None
+    _spring_order = None
+
+    def set_springs(self, facets, k=1.0, facet_k=None):
+        """The operator gains int_E v^T K u over the listed boundary facets: K_f = facet_k [nlist, 3] = (k00, k01, k11)
+        where given, else k I.  An empty list switches the term off; a repeated call replaces the list; a refused one
+        (spring_list) leaves the operator as it was.  A hierarchy with coarse=True has to be built again afterwards."""
+        f, K = spring_list("set_springs", self.mesh, facets, k, facet_k)
+        if f is None:
+            self.spring_f = self.spring_k = self.spring_kw = self.spring_dofs = self._spring_order = None
+            return
+        kw = facet_lengths(self.mesh, f)[:, None] * K
+        order = np.argsort(f, kind="stable")
+        self._spring_order = order
+        self.spring_f, self.spring_k, self.spring_kw = f[order], K[order], kw[order]
+        self.spring_dofs = facet_dofs(self.mesh, self.p, self.spring_f)
+
+    def spring_weights(self):
+        """Kw_f [nlist, 3] in the order of the list given to set_springs (empty without the term)."""
+        if self.spring_f is None:
+            return np.zeros((0, 3))
+        out = np.empty(self.spring_kw.shape)
+        out[self._spring_order] = self.spring_kw
+        return out
+
+    def spring_positive(self):
+        """Whether some listed facet has |E_f| > 0 and a positive definite K_f: the operator is then definite without a
+        fixed DOF in either component."""
+        if self.spring_f is None:
+            return False
+        return bool((spring_definite(self.spring_k) & (facet_lengths(self.mesh, self.spring_f) > 0.0)).any())
+
+    robin_positive = spring_positive      # what pcg and Hierarchy ask a level before they call it singular
+
+    def _spring_rows(self):
+        """((Kw[0][0], Kw[0][1]), (Kw[1][0], Kw[1][1])), each [nlist, 1]."""
+        kw = self.spring_kw
+        return ((kw[:, 0:1], kw[:, 1:2]), (kw[:, 1:2], kw[:, 2:3]))
+
+    def _add_robin(self, y, u, A=None):
+        """y [2 ndofs] (and A, the absolute sums) with the facet values t_f[i][r] added, facets ascending, one addition
+        each."""
+        if self.spring_f is None:
+            return y, A
+        FM = facet_mass_table(self.p)
+        uu = np.asarray(u, dtype=np.float64).reshape(self.ndofs, 2)[self.spring_dofs]      # [n, p+1, 2]
+        m, mA = zip(*[_sum_products(FM, uu[:, :, s]) for s in range(2)])
+        Kw = self._spring_rows()
+        for r in range(2):
+            t = Kw[r][0] * m[0] + Kw[r][1] * m[1]
+            tA = np.abs(Kw[r][0]) * mA[0] + np.abs(Kw[r][1]) * mA[1]
+            for k in range(self.spring_f.size):     # (a row lies in several facets: one after the other)
+                e = 2 * self.spring_dofs[k] + r
+                y[e] = y[e] + t[k]
+                if A is not None:
+                    A[e] = A[e] + tA[k]
+        return y, A
+
+    def _add_facet_entries(self, V, VA, skey):
+        if self.spring_f is None:
+            return
+        FM = facet_mass_table(self.p)
+        Kw = self._spring_rows()
+        for k in range(self.spring_f.size):
+            rows = self.spring_dofs[k]
+            pos = np.searchsorted(skey, rows[:, None] * self.ndofs + rows[None, :])
+            for r in range(2):
+                for s in range(2):
+                    e = Kw[r][s][k, 0] * FM
+                    V[pos, r, s] = V[pos, r, s] + e
+                    VA[pos, r, s] = VA[pos, r, s] + np.abs(e)
+
     def set_dirichlet(self, facets_row0, facets_row1):
         """Fixed are the rows 2 dof + r of the vertex and facet DOFs of the facets listed for component r (the facets
         with ft[r] == 1 of a stress handle's facet types).  A repeated call replaces the mask."""
@@ -1119,8 +1346,16 @@ class ElasticityOperator(PoissonOperator):
         md = np.broadcast_to(np.diagonal(self.Mass)[None, :], (self.mesh.ncells, self.nd))
         val, A = zip(*[self._scale_shear(val[r], A[r]) for r in range(2)])
         val, A = zip(*[self._add_reaction(val[r], A[r], md, md) for r in range(2)])
-        d = self.owner_sum(np.stack(val, axis=2))
-        return (d, self.owner_sum(np.stack(A, axis=2))) if return_abs else d
+        d, dA = self.owner_sum(np.stack(val, axis=2)), self.owner_sum(np.stack(A, axis=2))
+        if self.spring_f is not None:
+            fm = np.diagonal(facet_mass_table(self.p))
+            for k in range(self.spring_f.size):
+                for r in range(2):
+                    e = 2 * self.spring_dofs[k] + r
+                    t = self.spring_kw[k, 2 * r] * fm
+                    d[e] = d[e] + t
+                    dA[e] = dA[e] + np.abs(t)
+        return (d, dA) if return_abs else d
 
     _bs = 2
 
@@ -1151,8 +1386,9 @@ class ElasticityOperator(PoissonOperator):
 
     def pcg(self, b, u, rtol=1e-8, atol=0.0, maxit=1000):
         """The CG of PoissonOperator.pcg on the blocked vectors (eqlb_elasticity_solve).  Each component needs a
-        Dirichlet DOF; a rotation the mask leaves free is the caller's responsibility."""
+        Dirichlet DOF, unless a spring facet with a positive definite tensor holds every rigid motion (spring_positive);
+        a rotation the mask leaves free is the caller's responsibility."""
         for r in range(2):
-            if not self.fixed[r::2].any():
+            if not self.fixed[r::2].any() and not self.spring_positive():
                 raise ValueError(f"pcg: singular: component {r} has no Dirichlet DOF")
         return PoissonOperator.pcg(self, b, u, rtol, atol, maxit)

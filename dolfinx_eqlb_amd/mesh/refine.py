@@ -20,7 +20,8 @@ With every cell marked this is the longest-edge 4-split, not a red refinement.
 
 Between the facets of the two meshes: parent_facets (eqlb_refine_parent_facets), and from it carry_facet_types
 (eqlb_refine_facet_types: the type table of the equilibrator on the refined mesh) and its inverse for facet lists,
-child_facets (eqlb_refine_child_facets); carry_robin_list states Refinement.carry_robin on top of it.
+child_facets (eqlb_refine_child_facets); carry_robin_list states Refinement.carry_robin on top of it, and
+carry_springs_list states Refinement.carry_springs.
 """
 
 import numpy as np
@@ -192,3 +193,17 @@ def carry_robin_list(mesh, node_parent_facet, mesh2, facets, facet_alpha):
     ch = child_facets(mesh, node_parent_facet, mesh2, f)
     keep = ch >= 0
     return ch[keep].astype(np.int32), np.repeat(a[:, None], 2, axis=1)[keep]
+
+
+def carry_springs_list(mesh, node_parent_facet, mesh2, facets, facet_k):
+    """(facets2 int32, facet_k2 [n2, 3]) of a spring list (ElasticityOperator.set_springs) on the refined mesh `mesh2` -
+    the statement of Refinement.carry_springs: the rule of carry_robin_list, and a child takes its parent's tensor K as
+    it is: K is stated in global axes, and a child of a straight facet has its parent's normal, so nothing is
+    rotated."""
+    f = np.asarray(facets, dtype=np.int64).ravel()
+    K = np.asarray(facet_k, dtype=np.float64)
+    if K.size != 3 * f.size:
+        raise ValueError("carry_springs_list: facet_k [nlist][3] expected")
+    ch = child_facets(mesh, node_parent_facet, mesh2, f)
+    keep = ch >= 0
+    return ch[keep].astype(np.int32), np.repeat(K.reshape(f.size, 1, 3), 2, axis=1)[keep]

@@ -1022,7 +1022,7 @@ void eqlb_refine_destroy(eqlb_refine_t* plan);
  * THE ROBIN TERM: eqlb_primal_set_robin states -(kappa D grad u) . n = alpha (u - u_ext) on the listed boundary facets,
  * alpha_f >= 0 per facet - convection to an ambient temperature, a leaky boundary, a penalised Dirichlet side.  The
  * operator gains the boundary mass int_E alpha u v; the datum int_E alpha u_ext v is a load (b_extra;
- * lsolver.robin_load).  Poisson handles only: springs on an elasticity handle are not provided.
+ * lsolver.robin_load).  The counterpart on an elasticity handle is eqlb_elasticity_set_springs.
  *   table      FacetMass<p> [p+1][p+1] = int_0^1 l_i l_j ds (eqlb_get_facet_mass_table), l the equispaced 1-D Lagrange
  *              basis of degree p in the local order (lower node id, higher node id, interior 0 ... p-2 from the lower to
  *              the higher node) - the order of the global DOFs lo, hi, nnodes + f (p-1) + j of facet f, so no cell is
@@ -1225,6 +1225,65 @@ int eqlb_elasticity_set_reaction(eqlb_elasticity_t* handle, double c, const doub
  * memory is the caller's responsibility, as for eqlb_primal_set_reaction. */
 int eqlb_elasticity_set_shear(eqlb_elasticity_t* handle, double mu, const double* cell_mu, int32_t memspace,
                               void* stream);
+/* THE SPRING TERM (an elastic foundation): sigma(u) n = -K_f (u - u_ext) on the listed boundary facets, K_f a symmetric
+ * positive SEMIdefinite 2 x 2 tensor per facet in global axes, facet_k [nlist][3] = (k00, k01, k11) in `memspace` (the
+ * layout of cell_D), or NULL: K = k I with the scalar k >= 0 - Winkler bedding, a compliant support, a penalised sliding
+ * (K = kn n x n, rank one) or clamped side, a contact-like layer.  The operator gains int_E v^T K u; the datum
+ * int_E v^T K u_ext is a load (b_extra; lsolver.spring_load).  The bs = 2 counterpart of eqlb_primal_set_robin:
+ *   table      FacetMass<p> and the local order of a facet (lower node id, higher node id, interior), unchanged: no new
+ *              table and no cell lookup
+ *   weights    Kw_f = (|E_f| k00, |E_f| k01, |E_f| k11), |E_f| as for the Robin term, one product per entry, rounded on
+ *              its own; formed once at set_springs and kept (eqlb_elasticity_spring_weights: kw [nlist][3] in the order
+ *              of the list)
+ *   facet      m[i][s] = sum_j FacetMass[i][j] u[2 dof_j + s], s = 0, 1: ascending j, the first product starts the sum,
+ *              products rounded one by one;  t_f[i][r] = Kw[r][0] m[i][0] + Kw[r][1] m[i][1]: two products and one
+ *              addition, no fused multiply-add
+ *   row 2d+r   the owner sum; then the t_f[i][r] of the spring facets that hold d are added in ascending facet id, each
+ *              by one addition.  Everything behind that is unchanged: b_extra, the mask per component, r = b - v, the
+ *              fused inner products.  The lifting reads a free row, fixed[2 dof_j + s] == 0, as 0 in the facet term too
+ *   diagonal   the owner sum, then + Kw[r][r] FacetMass[i][i] in the same place
+ *   matrix     eqlb_elasticity_matrix_values adds Kw[r][s] FacetMass[i][j] to entry (2 d_i + r, 2 d_j + s) after the cell
+ *              sums, facets ascending.  The pattern is the scalar one - the pairs of DOFs with a common cell - and every
+ *              pair carries its full 2 x 2 block, so it already holds every such entry (the DOFs of a boundary facet
+ *              lie in its cell): no pattern changes.  The raw diagonal keeps the bits of the diagonal; eliminate acts
+ *              as before
+ * The term is formed inside the sum pass, in a kernel and with an argument of its own (no further launch per product,
+ * no atomics); a handle without it launches the kernels it launched before.  The owner sum of eqlb_elasticity_load and
+ * of the restriction of a hierarchy stays plain.  apply, diagonal, residual, solve, matrix_values and a hierarchy that
+ * holds the handle (BPX, local, coarse) carry the term.
+ *   nlist = 0                switches the term off: the operator is the one of a fresh handle, bit for bit
+ *   diagonal                 formed again in place on `stream`; call eqlb_hierarchy_set_coarse(.., 1, ..) again after the
+ *                            term of level 0 changes: the factor is a snapshot
+ *   no Dirichlet DOF         with some listed facet of |E_f| > 0 and K_f positive definite - the test is k00 > 0 &&
+ *                            k01 k01 < (k00 k11) (1 - 2^-49) - no rigid motion is left (one that vanishes in the K-norm
+ *                            on a segment is zero): eqlb_elasticity_solve, eqlb_hierarchy_solve and
+ *                            eqlb_hierarchy_set_coarse no longer ask for a Dirichlet DOF in either component.  A rule per
+ *                            handle, as loose as the Robin one; the breakdown flag of the CG and the pivot test of the
+ *                            coarse factor stay.  Only normal or only tangential stiffness (rank one) leaves the
+ *                            per-component Dirichlet rule in force, unchanged
+ *   host memory space        refused with EQLB_ERR_INVALID_ARGUMENT by facet, in the order of the list, before anything
+ *                            changes: a facet that is no boundary facet; a facet listed twice; an entry of facet_k that
+ *                            is not finite; k00 < 0; k11 < 0; k01 k01 > (k00 k11) (1 + 2^-49).  The allowance lets a
+ *                            rank-one tensor formed in floating point as kn n_a n_b pass: its two sides differ by about
+ *                            ten roundings at the most.  The scalar k: negative, NaN or infinite is refused
+ *   device memory space      as eqlb_primal_set_robin: an id that is no boundary facet is skipped (weight 0, no row),
+ *                            nothing is read out of range; the tensors are the caller's responsibility
+ *   both                     the table is that of the Robin term over the scalar DOFs (both rows of a DOF lie in the
+ *                            same facets), built on the host by the same planner: the call waits for `stream`
+ * eqlb_elasticity_spring_flux: THE FLUX CONDITIONS OF THE TWO STRESS ROWS that the discrete solution implies,
+ *   out[r][i][q] = K_i[r][0] d_0 + K_i[r][1] d_1,  d_s = u_h,s(x_q) - u_ext[s][i][q],   out, u_ext [2][nlist][nq] in
+ * `memspace`, u_ext NULL = 0, u [2 ndofs] blocked, s [nq] HOST, 1 <= nq <= 64, 0 <= s <= 1, in the frame of
+ * eqlb_facet_points.  One thread per (facet, point) writes both rows; u_h,s is formed per component exactly as in
+ * eqlb_primal_robin_flux, the contraction with K is two products and one addition: bit for bit lsolver.spring_flux.  A
+ * facet the list skipped gives NaN.  Row r is what row r of a stress handle takes in eqlb_se_update_flux_bc with
+ * vector = 0 on facets of type EQLB_FACET_ESSNT_DUAL, since -sigma_r . n = (K (u_h - u_ext))_r.
+ * Errors as for the Robin entries. */
+int eqlb_elasticity_set_springs(eqlb_elasticity_t* handle, int32_t nlist, const int32_t* facets, double k,
+                                const double* facet_k, int32_t memspace, void* stream);
+int eqlb_elasticity_spring_weights(eqlb_elasticity_t* handle, int32_t* nlist, double* kw, int32_t capacity,
+                                   int32_t memspace, void* stream);
+int eqlb_elasticity_spring_flux(eqlb_elasticity_t* handle, const double* u, int32_t nq, const double* s,
+                                const double* u_ext, double* out, int32_t memspace, void* stream);
 int eqlb_elasticity_load(eqlb_elasticity_t* handle, int32_t degree_dg, const double* rhs_dg, const double* b_extra,
                          double* b, int32_t memspace, void* stream);
 int eqlb_elasticity_apply(eqlb_elasticity_t* handle, const double* u, double* y, int32_t masked, int32_t memspace,
