@@ -647,19 +647,24 @@ class Refinement:
         plan.child_facets_raw(self.dmesh, fl.size, fl.ctypes.data, out.ctypes.data, MEM_HOST, stream)
         return out[out >= 0] if flat else out
 
+    def _carry_facet_term(self, old, new, stream):
+        """The list of the facet term of `old` (its _facet names the term) through child_facets - in the order of the
+        list, first child first, a child takes its parent's values - into the host setter of `new`."""
+        f, v = old._facet_list()
+        ch = self.child_facets(f, stream=stream)
+        keep = ch >= 0
+        f2 = ch[keep].astype(np.int32)
+        v2 = np.repeat(v[:, None], 2, axis=1)[keep]
+        new._facet_set(f2, [1.0], v2, stream)   # (the scalar at its default: the values are given per facet)
+        return f2, v2
+
     def carry_robin(self, old, new, stream=0):
         """The Robin list of the solver handle `old` (PrimalPoisson on the mesh that was refined) on the refined mesh:
         the list goes through child_facets, a child takes its parent's alpha, and `new` (PrimalPoisson on the refined
         mesh) gets it through set_robin (the rule: mesh.refine.carry_robin_list).  Returns (facets2, facet_alpha2), host
-        arrays.  `old` must have received its list through set_robin (host arrays); one without the term switches the
-        term of `new` off."""
-        f, a = old.robin_list()
-        ch = self.child_facets(f, stream=stream)
-        keep = ch >= 0
-        f2 = ch[keep].astype(np.int32)
-        a2 = np.repeat(a[:, None], 2, axis=1)[keep]
-        new.set_robin(f2, facet_alpha=a2, stream=stream)
-        return f2, a2
+        arrays.  `old` must have received its list through set_robin (host arrays) - one whose list came through
+        set_robin_raw is refused, and `new` stays as it was; one without the term switches the term of `new` off."""
+        return self._carry_facet_term(old, new, stream)
 
     def carry_springs(self, old, new, stream=0):
         """The spring list of the solver handle `old` (PrimalElasticity on the mesh that was refined) on the refined
@@ -667,13 +672,7 @@ class Refinement:
         axes, so nothing is rotated - and `new` (PrimalElasticity on the refined mesh) gets it through set_springs (the
         rule: mesh.refine.carry_springs_list).  Returns (facets2, facet_k2), host arrays.  `old` must have received its
         list through set_springs (host arrays); one without the term switches the term of `new` off."""
-        f, K = old.spring_list()
-        ch = self.child_facets(f, stream=stream)
-        keep = ch >= 0
-        f2 = ch[keep].astype(np.int32)
-        K2 = np.repeat(K.reshape(f.size, 1, 3), 2, axis=1)[keep]
-        new.set_springs(f2, facet_k=K2, stream=stream)
-        return f2, K2
+        return self._carry_facet_term(old, new, stream)
 
     def prolong_flux_bc(self, k, boundary_values, facets2, stream=0):
         """The table boundary_values [nrhs, ncells*k(k+2)] (or 1-D) of the old mesh -> dofs [nrhs, nlist, k] of the
@@ -1641,6 +1640,80 @@ class _PrimalSolver:
         """cell_c: a raw pointer (int) to [ncells] in `memspace`, or None (the scalar c)."""
         _check(self._fn("set_reaction")(self._h, C.c_double(c), _vp(cell_c), C.c_int32(memspace), C.c_void_p(stream)))
 
+    # ---- the facet term: the Robin term of PrimalPoisson, the spring term of PrimalElasticity.  A subclass names it in
+    # _facet = (setter, stem, width): the entries set_<...>, <stem>_weights and <stem>_flux of the C ABI, the public
+    # names <setter>, <stem>_list in messages, and the values per listed facet (alpha: 1, (k00, k01, k11): 3).  The
+    # flux has _bs rows.  The public methods of the subclasses are thin calls of these.
+    _facet = None
+
+    def _facet_set(self, facets, scalar_row, values, stream):
+        """The list from host arrays; values [nlist, width] or None: scalar_row [width] on every facet.  The accepted
+        list is remembered for <stem>_list()."""
+        width = self._facet[2]
+        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
+        fv = None
+        if values is not None:
+            fv = np.ascontiguousarray(values, dtype=np.float64).ravel()
+            if fv.size != width * fl.size:
+                raise RuntimeError("Local solver: Input sizes does not match")
+        self._facet_set_raw(fl.size, fl.ctypes.data if fl.size else None, scalar_row[0],
+                            fv.ctypes.data if fv is not None and fv.size else None, MEM_HOST, stream)
+        rows = np.tile(np.asarray(scalar_row, dtype=np.float64), (fl.size, 1)) if fv is None else fv.copy()
+        self._facet_known = (fl.copy(), rows.reshape(self._facet_shape(fl.size)))
+
+    def _facet_shape(self, n):
+        return (n,) if self._facet[2] == 1 else (n, self._facet[2])
+
+    def _facet_list(self):
+        """(facets, values) as the last accepted host setter took them; empty without the term.  A handle whose
+        non-empty list came through the raw setter is refused: the host does not know that list."""
+        setter, stem, _ = self._facet
+        known = getattr(self, "_facet_known", None)
+        if known is None or known[0].size != self._facet_count():
+            if self._facet_count() != 0:
+                raise RuntimeError(f"{stem}_list: the handle's list was not given through {setter} (host arrays)")
+            return np.zeros(0, dtype=np.int32), np.zeros(self._facet_shape(0))
+        return known
+
+    def _facet_set_raw(self, nlist, facets, scalar, values, memspace, stream):
+        _check(self._fn(self._facet[0])(self._h, C.c_int32(nlist), _vp(facets), C.c_double(scalar), _vp(values),
+                                        C.c_int32(memspace), C.c_void_p(stream)))
+        self._facet_known = None   # (a refused call has left the handle, and so the remembered list, as it was)
+
+    def _facet_count(self):
+        return self._facet_weights_raw(None, 0, MEM_HOST, 0)
+
+    def _facet_weights(self, stream):
+        w = np.zeros(self._facet_shape(self._facet_count()))
+        if w.size:
+            self._facet_weights_raw(w.ctypes.data, w.shape[0], MEM_HOST, stream)
+        return w
+
+    def _facet_weights_raw(self, w, capacity, memspace, stream):
+        n = C.c_int32(0)
+        _check(self._fn(self._facet[1] + "_weights")(self._h, C.byref(n), _vp(w), C.c_int32(capacity),
+                                                     C.c_int32(memspace), C.c_void_p(stream)))
+        return int(n.value)
+
+    def _facet_flux(self, u, s, u_ext, stream):
+        uu = self._vec(u)
+        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+        shape = (self._facet_count(), ss.size) if self._bs == 1 else (self._bs, self._facet_count(), ss.size)
+        ue = None
+        if u_ext is not None:
+            ue = np.ascontiguousarray(u_ext, dtype=np.float64).ravel()
+            if ue.size != int(np.prod(shape)):
+                raise RuntimeError("Local solver: Input sizes does not match")
+        out = np.zeros(shape)
+        self._facet_flux_raw(uu.ctypes.data, ss, None if ue is None else ue.ctypes.data, out.ctypes.data, MEM_HOST,
+                             stream)
+        return out
+
+    def _facet_flux_raw(self, u, s, u_ext, out, memspace, stream):
+        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
+        _check(self._fn(self._facet[1] + "_flux")(self._h, _vp(u), C.c_int32(ss.size), _hp(ss), _vp(u_ext), _vp(out),
+                                                  C.c_int32(memspace), C.c_void_p(stream)))
+
     def apply(self, u, masked=False, stream=0):
         """y = A u; masked: 0 on the fixed rows."""
         uu, y = self._vec(u), np.zeros(self._bs * self.ndofs)
@@ -1786,6 +1859,7 @@ class PrimalPoisson(_PrimalSolver):
     `stream`.  The entries of one handle share its work space: one stream, one call after the other."""
 
     _prefix, _bs = "eqlb_primal_", 1
+    _facet = ("set_robin", "robin", 1)
 
     def __init__(self, dmesh: DeviceMesh, p: int, coeff=None, stream=0):
         self.dmesh = dmesh   # the handle reads the mesh: keep it alive
@@ -1844,67 +1918,40 @@ class PrimalPoisson(_PrimalSolver):
         alpha_f > 0 the solves no longer ask for a Dirichlet DOF.  The diagonal is formed again;
         Multilevel.set_coarse(True) has to be called again afterwards.  The datum u_ext enters the load through
         lsolver.robin_load; Refinement.carry_robin carries the list to the refined mesh."""
-        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
-        fa = None
-        if facet_alpha is not None:
-            fa = np.ascontiguousarray(facet_alpha, dtype=np.float64).ravel()
-            if fa.size != fl.size:
-                raise RuntimeError("Local solver: Input sizes does not match")
-        self.set_robin_raw(fl.size, fl.ctypes.data if fl.size else None, alpha,
-                           fa.ctypes.data if fa is not None and fa.size else None, MEM_HOST, stream)
-        self._robin_list = (fl.copy(), np.full(fl.size, float(alpha)) if fa is None else fa.copy())
+        self._facet_set(facets, [float(alpha)], facet_alpha, stream)
 
     def robin_list(self):
-        """(facets int32 [nlist], facet_alpha [nlist]) as the last accepted set_robin took them (empty without one)."""
-        return getattr(self, "_robin_list", (np.zeros(0, dtype=np.int32), np.zeros(0)))
+        """(facets int32 [nlist], facet_alpha [nlist]) as the last accepted set_robin took them (empty without the term).
+        Raises for a handle that holds a non-empty list that was not given through set_robin: the host does not know a
+        list given through set_robin_raw."""
+        return self._facet_list()
 
     def set_robin_raw(self, nlist, facets, alpha=1.0, facet_alpha=None, memspace=MEM_DEVICE, stream=0):
         """facets int32 [nlist], facet_alpha float64 [nlist] or None behind raw pointers in `memspace`.  Device memory
-        space: a listed id that is no boundary facet is skipped; the call waits for the stream."""
-        _check(lib().eqlb_primal_set_robin(self._h, C.c_int32(nlist), _vp(facets), C.c_double(alpha), _vp(facet_alpha),
-                                           C.c_int32(memspace), C.c_void_p(stream)))
+        space: a listed id that is no boundary facet is skipped; the call waits for the stream.  robin_list() knows
+        nothing of a list given here: it is emptied, and Refinement.carry_robin refuses such a handle."""
+        self._facet_set_raw(nlist, facets, alpha, facet_alpha, memspace, stream)
 
     def robin_count(self):
         """The number of listed facets of the Robin term (0 without it)."""
-        n = C.c_int32(0)
-        _check(lib().eqlb_primal_robin_weights(self._h, C.byref(n), None, C.c_int32(0), C.c_int32(MEM_HOST), None))
-        return int(n.value)
+        return self._facet_count()
 
     def robin_weights(self, stream=0):
         """w_f = alpha_f |E_f| [nlist] in the order of the list (eqlb_primal_robin_weights)."""
-        w = np.zeros(self.robin_count())
-        if w.size:
-            self.robin_weights_raw(w.ctypes.data, w.size, MEM_HOST, stream)
-        return w
+        return self._facet_weights(stream)
 
     def robin_weights_raw(self, w, capacity, memspace=MEM_DEVICE, stream=0):
-        n = C.c_int32(0)
-        _check(lib().eqlb_primal_robin_weights(self._h, C.byref(n), _vp(w), C.c_int32(capacity), C.c_int32(memspace),
-                                               C.c_void_p(stream)))
-        return int(n.value)
+        return self._facet_weights_raw(w, capacity, memspace, stream)
 
     def robin_flux(self, u, s, u_ext=None, stream=0):
         """out [nlist, nq] = alpha_i (u_h(x_q) - u_ext[i][q]) on the handle's Robin list at the facet parameters s [nq]
         in the frame of facet_points (eqlb_primal_robin_flux): the point values of the flux condition
         sigma_eq . n that update_flux_bc takes with vector=False.  u_ext [nlist, nq] or None (0)."""
-        uu = self._vec(u)
-        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
-        n = self.robin_count()
-        ue = None
-        if u_ext is not None:
-            ue = np.ascontiguousarray(u_ext, dtype=np.float64).ravel()
-            if ue.size != n * ss.size:
-                raise RuntimeError("Local solver: Input sizes does not match")
-        out = np.zeros((n, ss.size))
-        self.robin_flux_raw(uu.ctypes.data, ss, None if ue is None else ue.ctypes.data, out.ctypes.data, MEM_HOST,
-                            stream)
-        return out
+        return self._facet_flux(u, s, u_ext, stream)
 
     def robin_flux_raw(self, u, s, u_ext, out, memspace=MEM_DEVICE, stream=0):
         """u [ndofs], u_ext [nlist][nq] or None and out [nlist][nq] behind raw pointers in `memspace`; s a host array."""
-        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
-        _check(lib().eqlb_primal_robin_flux(self._h, _vp(u), C.c_int32(ss.size), _hp(ss), _vp(u_ext), _vp(out),
-                                            C.c_int32(memspace), C.c_void_p(stream)))
+        self._facet_flux_raw(u, s, u_ext, out, memspace, stream)
 
     def apply_many(self, U, masked=False, stream=0):
         """Y [nrhs][ndofs]: row c is apply(U[c]), bit for bit, in one call."""
@@ -1946,6 +1993,7 @@ class PrimalElasticity(_PrimalSolver):
     the `_raw` variants take raw pointers (ints) in `memspace`, ordered on `stream`."""
 
     _prefix, _bs = "eqlb_elasticity_", 2
+    _facet = ("set_springs", "spring", 3)
 
     def __init__(self, dmesh: DeviceMesh, p: int, pi_1: float = 1.0, cell_pi1=None, stream=0):
         self.dmesh = dmesh   # the handle reads the mesh: keep it alive
@@ -2011,78 +2059,40 @@ class PrimalElasticity(_PrimalSolver):
         solves ask for no Dirichlet DOF.  The diagonal is formed again; Multilevel.set_coarse(True) has to be called
         again afterwards.  The datum u_ext enters the load through lsolver.spring_load; lsolver.spring_tensor gives
         K = kn n x n + kt t x t; Refinement.carry_springs carries the list to the refined mesh."""
-        fl = np.ascontiguousarray(facets, dtype=np.int32).ravel()
-        fk = None
-        if facet_k is not None:
-            fk = np.ascontiguousarray(facet_k, dtype=np.float64).ravel()
-            if fk.size != 3 * fl.size:
-                raise RuntimeError("Local solver: Input sizes does not match")
-        self.set_springs_raw(fl.size, fl.ctypes.data if fl.size else None, k,
-                             fk.ctypes.data if fk is not None and fk.size else None, MEM_HOST, stream)
-        kk = float(k)
-        self._spring_list = (fl.copy(), np.tile(np.array([kk, 0.0, kk]), (fl.size, 1)) if fk is None
-                             else fk.reshape(fl.size, 3).copy())
+        self._facet_set(facets, [float(k), 0.0, float(k)], facet_k, stream)
 
     def spring_list(self):
-        """(facets int32 [nlist], facet_k [nlist, 3]) as the last accepted set_springs took them (empty without one)."""
-        known = getattr(self, "_spring_list", None)
-        if known is None or known[0].size != self.spring_count():
-            if self.spring_count() != 0:
-                raise RuntimeError("spring_list: the handle's list was not given through set_springs (host arrays)")
-            return np.zeros(0, dtype=np.int32), np.zeros((0, 3))
-        return known
+        """(facets int32 [nlist], facet_k [nlist, 3]) as the last accepted set_springs took them (empty without the
+        term).  Raises for a handle that holds a non-empty list that was not given through set_springs."""
+        return self._facet_list()
 
     def set_springs_raw(self, nlist, facets, k=1.0, facet_k=None, memspace=MEM_DEVICE, stream=0):
         """facets int32 [nlist], facet_k float64 [nlist][3] or None behind raw pointers in `memspace`.  Device memory
         space: a listed id that is no boundary facet is skipped; the call waits for the stream.  spring_list() knows
         nothing of a list given here: it is emptied, and Refinement.carry_springs refuses such a handle."""
-        self._spring_list = None
-        _check(lib().eqlb_elasticity_set_springs(self._h, C.c_int32(nlist), _vp(facets), C.c_double(k), _vp(facet_k),
-                                                 C.c_int32(memspace), C.c_void_p(stream)))
+        self._facet_set_raw(nlist, facets, k, facet_k, memspace, stream)
 
     def spring_count(self):
         """The number of listed facets of the spring term (0 without it)."""
-        n = C.c_int32(0)
-        _check(lib().eqlb_elasticity_spring_weights(self._h, C.byref(n), None, C.c_int32(0), C.c_int32(MEM_HOST), None))
-        return int(n.value)
+        return self._facet_count()
 
     def spring_weights(self, stream=0):
         """Kw_f = |E_f| (k00, k01, k11) [nlist, 3] in the order of the list (eqlb_elasticity_spring_weights)."""
-        w = np.zeros((self.spring_count(), 3))
-        if w.size:
-            self.spring_weights_raw(w.ctypes.data, w.shape[0], MEM_HOST, stream)
-        return w
+        return self._facet_weights(stream)
 
     def spring_weights_raw(self, kw, capacity, memspace=MEM_DEVICE, stream=0):
-        n = C.c_int32(0)
-        _check(lib().eqlb_elasticity_spring_weights(self._h, C.byref(n), _vp(kw), C.c_int32(capacity),
-                                                    C.c_int32(memspace), C.c_void_p(stream)))
-        return int(n.value)
+        return self._facet_weights_raw(kw, capacity, memspace, stream)
 
     def spring_flux(self, u, s, u_ext=None, stream=0):
         """out [2, nlist, nq]: out[r] = (K (u_h - u_ext))_r on the handle's spring list at the facet parameters s [nq] in
         the frame of facet_points (eqlb_elasticity_spring_flux): row r holds the point values of the flux condition that
         row r of a stress handle takes in update_flux_bc with vector=False.  u_ext [2, nlist, nq] or None (0)."""
-        uu = self._vec(u)
-        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
-        n = self.spring_count()
-        ue = None
-        if u_ext is not None:
-            ue = np.ascontiguousarray(u_ext, dtype=np.float64).ravel()
-            if ue.size != 2 * n * ss.size:
-                raise RuntimeError("Local solver: Input sizes does not match")
-        out = np.zeros((2, n, ss.size))
-        self.spring_flux_raw(uu.ctypes.data, ss, None if ue is None else ue.ctypes.data, out.ctypes.data, MEM_HOST,
-                             stream)
-        return out
+        return self._facet_flux(u, s, u_ext, stream)
 
     def spring_flux_raw(self, u, s, u_ext, out, memspace=MEM_DEVICE, stream=0):
         """u [2 ndofs], u_ext [2][nlist][nq] or None and out [2][nlist][nq] behind raw pointers in `memspace`; s a host
         array."""
-        ss = np.ascontiguousarray(s, dtype=np.float64).ravel()
-        _check(lib().eqlb_elasticity_spring_flux(self._h, _vp(u), C.c_int32(ss.size), _hp(ss), _vp(u_ext), _vp(out),
-                                                 C.c_int32(memspace), C.c_void_p(stream)))
-
+        self._facet_flux_raw(u, s, u_ext, out, memspace, stream)
 
 
 class Multilevel:

@@ -16,9 +16,9 @@
 //  k_primal_slots    builds the slot lists of the sum pass once at create (scalar numbering: both problems use it)
 //  k_primal_mask<BS> the Dirichlet mask of one component from a list of facets
 //  k_primal_gather<BS, NC>  one thread per (DOF, component): BS values per y_loc entry, the vectors blocked
-//                    x[BS * dof + r]; columns for BS = 1 only.  eqlb_primal_gather.inc, included three times: the
-//                    second time as k_primal_gather_robin, which adds the facet values of a Robin term (BS = 1), the
-//                    third as k_primal_gather_spring, which adds those of a spring term (BS = 2)
+//                    x[BS * dof + r]; columns for BS = 1 only.  eqlb_primal_gather.inc, included twice: the second
+//                    time as k_primal_gather_facet, which adds the facet values of a Robin term (BS = 1) or a spring
+//                    term (BS = 2)
 //  k_pcg_*<NC>       work on any length n with a byte mask [n]: n = ndofs or 2 ndofs
 //  k_pcg_scalar      the scalar steps; `ml`: the breakdown rule of a preconditioner that is no positive diagonal
 //  pcg_solve         the host side of the iteration on a PcgWork; the preconditioner enters through its `steps`
@@ -28,6 +28,7 @@
 #pragma once
 
 #include "eqlb_device_common.h"
+#include "eqlb_facet_plan.h"
 #include "eqlb_host_util.h"
 #include "eqlb_reduce.h"
 
@@ -169,49 +170,32 @@ struct GatherArgs
       hipLaunchKernelGGL(KERNEL<MANY_R>, dim3(stream_blocks(n)), dim3(PS_THREADS), 0, stream, __VA_ARGS__);            \
   } while (0)
 
-// the Robin term of the sum pass (include/eqlb.h: eqlb_primal_set_robin), all pointers DEVICE: the table a row finds its
-// facets through, built at set_robin.  A kernel argument of its own, which the sum pass without the term does not take.
-constexpr int ROBIN_ROW = PS_PMAX + 1; // row stride of dofs: the p + 1 rows of a facet in its local order
-struct RobinArgs
+// A facet term of the sum pass, all pointers DEVICE: the Robin term of a scalar space (include/eqlb.h:
+// eqlb_primal_set_robin) or the spring term of a blocked one, bs = 2 (eqlb_elasticity_set_springs).  The table a row
+// finds its facets through (eqlb_facet_plan.h) runs over the scalar DOFs d - with bs = 2 both rows 2 d + r of a DOF lie
+// in the same facets, and a chunk of PS_THREADS consecutive rows holds PS_THREADS / 2 consecutive DOFs.  A kernel
+// argument of its own, which the sum pass without the term does not take.
+static_assert(FACET_ROW == PS_PMAX + 1, "the p + 1 rows of a facet in its local order");
+struct FacetTermArgs
 {
-  const int32_t* chunk; // [ceil(ndofs / PS_THREADS) + 1] first position in rows[] of a chunk of PS_THREADS rows
-  const int32_t* rows;  // [m] the rows that lie in a Robin facet, ascending
-  const int32_t* off;   // [m + 1] the entries of a row in ent[]
-  const int32_t* ent;   // list position * 8 + local index of the row in that facet, facet ids ascending
-  const int32_t* dofs;  // [nlist][ROBIN_ROW]
-  const double* w;      // [nlist] alpha_f |E_f|
-  const double* fm;     // FacetMass<p> [n1][n1]
-  const double* u;      // column 0 of [R][ndofs]; nullptr: the diagonal
-  const uint8_t* fixed; // only_fixed: the free rows of u read as 0
-  int32_t only_fixed, n1;
-};
-
-// the spring term of the sum pass on a blocked space, bs = 2 (include/eqlb.h: eqlb_elasticity_set_springs): the table of
-// the Robin term over the scalar DOFs d - both rows 2 d + r of a DOF lie in the same facets - with the tensor weights
-// in the place of the scalar one.  A chunk of PS_THREADS consecutive rows e holds PS_THREADS / 2 consecutive DOFs.
-struct SpringArgs
-{
-  const int32_t* chunk; // [ceil(2 ndofs / PS_THREADS) + 1] first position in rows[] of a chunk of PS_THREADS / 2 DOFs
-  const int32_t* rows;  // [m] the DOFs d that lie in a spring facet, ascending
+  const int32_t* chunk; // [ceil(bs ndofs / PS_THREADS) + 1] first position in rows[] of a chunk of PS_THREADS / bs DOFs
+  const int32_t* rows;  // [m] the DOFs that lie in a listed facet, ascending
   const int32_t* off;   // [m + 1] the entries of a DOF in ent[]
   const int32_t* ent;   // list position * 8 + local index of the DOF in that facet, facet ids ascending
-  const int32_t* dofs;  // [nlist][ROBIN_ROW], scalar DOFs
-  const double* kw;     // [nlist][3] |E_f| (k00, k01, k11)
+  const int32_t* dofs;  // [nlist][FACET_ROW], scalar DOFs
+  const double* w;      // bs = 1: [nlist] alpha_f |E_f|; bs = 2: [nlist][3] |E_f| (k00, k01, k11)
   const double* fm;     // FacetMass<p> [n1][n1]
-  const double* u;      // [2 ndofs] blocked; nullptr: the diagonal
-  const uint8_t* fixed; // [2 ndofs]; only_fixed: the free rows of u read as 0
+  const double* u;      // column 0 of [R][bs ndofs], blocked; nullptr: the diagonal
+  const uint8_t* fixed; // [bs ndofs]; only_fixed: the free rows of u read as 0
   int32_t only_fixed, n1;
 };
 
-#define EQLB_GATHER_ROBIN 0
+#define EQLB_GATHER_FACET 0
 #include "eqlb_primal_gather.inc"
-#undef EQLB_GATHER_ROBIN
-#define EQLB_GATHER_ROBIN 1
+#undef EQLB_GATHER_FACET
+#define EQLB_GATHER_FACET 1
 #include "eqlb_primal_gather.inc"
-#undef EQLB_GATHER_ROBIN
-#define EQLB_GATHER_ROBIN 2
-#include "eqlb_primal_gather.inc"
-#undef EQLB_GATHER_ROBIN
+#undef EQLB_GATHER_FACET
 
 // ---- vector kernels of the iteration (grid-stride, block partials in a fixed order): the columns of a DOF in one
 // thread.  Channel j of column k: sh[2 k + j], part[(2 k + j) G + block] ----------------------------------------------

@@ -170,49 +170,7 @@ inline bool spring_definite(const double* k)
   return k[0] > 0.0 && k[1] * k[1] < (k[0] * k[2]) * (1.0 - SPRING_ALLOWANCE);
 }
 
-// One thread per (listed facet, point), both rows: out[r][i][q] = K_i[r][0] d_0 + K_i[r][1] d_1 with
-// d_s = u_h,s(x_q) - u_ext[s][i][q]; the frame and the basis l_j come from facet_point_basis (eqlb_primal_handle.h), the
-// rule of k_robin_flux, and the sums over j are its sums on each component of the blocked u; the contraction with K is
-// two products and one addition, every operation rounded on its own.  A facet the list skipped gives NaN.
-__global__ void __launch_bounds__(PS_THREADS)
-k_spring_flux(int32_t nlist, int32_t nq, int32_t p, const RobinRule rule, const int32_t* __restrict__ flist,
-              const int32_t* __restrict__ dofs, const double* __restrict__ K, int32_t ncells,
-              const int32_t* __restrict__ cell_nodes, const int32_t* __restrict__ cell_facets,
-              const int32_t* __restrict__ fco, const int32_t* __restrict__ facet_cells, const double* __restrict__ u,
-              const double* __restrict__ u_ext, double* __restrict__ out)
-{
-#pragma clang fp contract(off)
-  const int64_t total = (int64_t)nlist * nq;
-  const int64_t t = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= total)
-    return;
-  const int64_t i = t / nq;
-  const int q = (int)(t - i * nq);
-  const int32_t* dd = dofs + i * ROBIN_ROW;
-  double l[PS_PMAX + 1];
-  if (!facet_point_basis(flist[i], dd, rule.s[q], p, ncells, cell_nodes, cell_facets, fco, facet_cells, l))
-  {
-    out[t] = out[total + t] = __builtin_nan("");
-    return;
-  }
-  double d0 = 0.0, d1 = 0.0;
-  for (int j = 0; j <= p; ++j)
-  {
-    const double p0 = l[j] * u[2 * (int64_t)dd[j]], p1 = l[j] * u[2 * (int64_t)dd[j] + 1];
-    d0 = j == 0 ? p0 : d0 + p0;
-    d1 = j == 0 ? p1 : d1 + p1;
-  }
-  if (u_ext)
-  {
-    d0 = d0 - u_ext[t];
-    d1 = d1 - u_ext[total + t];
-  }
-  const double* k = K + 3 * i;
-  out[t] = k[0] * d0 + k[1] * d1;
-  out[total + t] = k[1] * d0 + k[2] * d1;
-}
-
-// the body of eqlb_elasticity_set_springs: the planner of the Robin term (facet_term_plan) with alpha = 1, so that its
+// the body of eqlb_elasticity_set_springs: the planner of a facet term (facet_term_plan) with alpha = 1, so that its
 // weights are the lengths |E_f|; the tensors are looked at and weighted on the host (O(sqrt N) facets, one product per
 // entry), and only then everything is put in the place of the old arrays: a refused call leaves the handle as it was.
 int elasticity_set_springs(const char* who, eqlb_elasticity* h, int32_t nlist, const int32_t* facets, double k,
@@ -362,25 +320,7 @@ int eqlb_elasticity_spring_weights(eqlb_elasticity_t* h, int32_t* nlist, double*
                                    int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* who = "eqlb_elasticity_spring_weights";
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  const int32_t n = h->has_robin ? h->robin_n : 0;
-  if (nlist)
-    *nlist = n;
-  if (!kw || n == 0)
-    return EQLB_OK;
-  if (capacity < n)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: capacity = %d is less than the %d listed facets", who, (int)capacity,
-                (int)n);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  HIP_TRY(hipMemcpyAsync(kw, h->spring_kw.get(), 3 * (size_t)n * sizeof(double),
-                         host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
-  if (host)
-    HIP_TRY(hipStreamSynchronize(stream));
-  return EQLB_OK;
+  return eqlb::solver_facet_weights("eqlb_elasticity_spring_weights", h, nlist, kw, capacity, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -388,42 +328,8 @@ int eqlb_elasticity_spring_flux(eqlb_elasticity_t* h, const double* u, int32_t n
                                 const double* u_ext, double* out, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* who = "eqlb_elasticity_spring_flux";
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  if (!u || !s || !out)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  if (nq < 1 || nq > RF_MAX_NQ)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nq = %d outside 1 ... %d", who, (int)nq, RF_MAX_NQ);
-  RobinRule rule{};
-  for (int q = 0; q < nq; ++q)
-  {
-    if (!(s[q] >= 0.0 && s[q] <= 1.0))
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: s[%d] = %g outside [0, 1]", who, q, s[q]);
-    rule.s[q] = s[q];
-  }
-  if (!h->has_robin)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: the handle has no spring term (eqlb_elasticity_set_springs first)", who);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const DeviceMesh& m = h->mesh->m;
-  const size_t n = (size_t)h->robin_n, no = 2 * n * (size_t)nq;
-  HostCall c;
-  const auto d_u = c.in(host ? u : nullptr, 2 * (size_t)h->ndofs);
-  const auto d_e = c.in(host ? u_ext : nullptr, no);
-  const auto d_o = c.out(host ? out : nullptr, no);
-  if (host)
-    HIP_TRY(c.upload(stream));
-  const int32_t* tab = h->robin_tab.get();
-  hipLaunchKernelGGL(k_spring_flux, dim3(grid_of((int64_t)(n * (size_t)nq), PS_THREADS)), dim3(PS_THREADS), 0, stream,
-                     h->robin_n, nq, (int32_t)h->p, rule, tab, tab + h->robin_at.dofs,
-                     static_cast<const double*>(h->spring_kw.get() + 3 * n), m.ncells, m.cell_nodes, m.cell_facets,
-                     m.facet_cells_off, m.facet_cells, host ? d_u.get() : u, host ? d_e.get() : u_ext,
-                     host ? d_o.get() : out);
-  c.note(hipGetLastError());
-  HIP_TRY(c.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_facet_flux("eqlb_elasticity_spring_flux", "spring", "eqlb_elasticity_set_springs", h, u, nq, s,
+                                 u_ext, out, memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -82,24 +82,22 @@ struct MatrixView
   DiffArgs dx;
   const uint8_t* fixed = nullptr;
   MatrixPattern* pattern = nullptr;
-  // the Robin term (bs = 1) or the spring term (bs = 2), the table of a sum pass on the diagonal: robin_m rows
-  // (bs = 2: DOFs) lie in a listed facet
-  bool has_robin = false;
-  int32_t robin_m = 0;
-  RobinArgs robin{};
-  SpringArgs spring{};
+  // the facet term, the table of a sum pass on the diagonal: facet_m DOFs lie in a listed facet
+  bool has_facet = false;
+  int32_t facet_m = 0;
+  FacetTermArgs facet{};
 };
 
 // What the planner of a facet term leaves for the setter that called it (eqlb_primal_solve.hip: facet_term_plan): the
-// device arrays a handle takes over, the sizes of the table's pieces (RobinLayout), and on the host the weight and the
+// device arrays a handle takes over, where the table's pieces lie (FacetLayout), and on the host the weight and the
 // flag of every listed facet (1: a boundary facet; anything else was skipped).  `refuse` is asked per facet, in the
 // order of the list and behind the tests on the facet itself, in host memory space: the caller's coefficient test.
 // chunk_dofs: the DOFs of a chunk of PS_THREADS rows of the sum pass, PS_THREADS / bs.
 struct FacetTermPlan
 {
-  DevBuf<int32_t> tab; // facets [n] | dofs [n][ROBIN_ROW] | chunk | rows [m] | off [m + 1] | ent
+  DevBuf<int32_t> tab; // facets [n] | dofs [n][FACET_ROW] | chunk | rows [m] | off [m + 1] | ent
   DevBuf<double> val;  // w [n] = alpha_f |E_f| | alpha [n] | FacetMass<p> [(p + 1)^2]
-  size_t nchunk = 0, m = 0, nent = 0;
+  FacetLayout at;
   std::vector<double> w;
   std::vector<int32_t> flag;
 };
@@ -136,17 +134,18 @@ inline ReactArgs react_args(const CellTerm& t) { return ReactArgs{t.array(), t.s
 inline ShearArgs shear_args(const CellTerm& t) { return ShearArgs{t.array(), t.scalar}; }
 inline DiffArgs diff_args(const CellTerm& t) { return DiffArgs{t.array()}; }
 
-// where the pieces of a handle's Robin table lie: facets [n] | dofs [n][ROBIN_ROW] | chunk | rows [m] | off [m + 1] |
-// ent, from the piece sizes
-struct RobinLayout
+// A facet term as the handle holds it - the Robin term of the Poisson unit (eqlb_primal_set_robin) or the spring term
+// of the elasticity unit (eqlb_elasticity_set_springs): off as created.  The arrays are allocated by a setter that
+// brings a list and replaced as a whole by the next one (solver_facet_term_commit).  A spring term has alpha = 1, so
+// that the w of val are the lengths |E_f|, and its tensors in kw
+struct FacetTerm
 {
-  size_t dofs = 0, chunk = 0, rows = 0, off = 0, ent = 0, total = 0;
-  RobinLayout() = default;
-  RobinLayout(size_t n, size_t nchunk, size_t m, size_t nent)
-      : dofs(n), chunk(n * (1 + ROBIN_ROW)), rows(chunk + nchunk), off(rows + m), ent(off + m + 1), total(ent + nent)
-  {
-  }
-  size_t m() const { return off - rows; }
+  bool on = false, positive = false; // positive: some weight > 0 - the operator is definite without a fixed DOF
+  int32_t n = 0;                     // listed facets
+  DevBuf<int32_t> tab;               // the pieces of FacetLayout ...
+  FacetLayout at;                    // ... and where they lie
+  DevBuf<double> val;                // w [n] | alpha [n] | FacetMass<p> [(p + 1)^2]
+  DevBuf<double> kw;                 // bs = 2: Kw [n][3] = |E_f| (k00, k01, k11) | K [n][3]
 };
 
 // what eqlb_primal_t and eqlb_elasticity_t share; everything but the grown work space is carved out of one allocation at
@@ -172,15 +171,7 @@ struct SolverHandle
   PcgWork wide{};
   // the reaction term and, for the Poisson unit, the diffusion tensor (solver_set_cell_term)
   CellTerm react{REACTION}, diff{DIFFUSION};
-  // the Robin term (eqlb_primal_set_robin, the Poisson unit) or the spring term (eqlb_elasticity_set_springs, the
-  // elasticity unit: robin_val holds |E_f| with alpha = 1, the tensors lie in spring_kw): off as created.  The arrays
-  // are allocated by a call that brings a list and replaced as a whole by the next one
-  bool has_robin = false, robin_pos = false; // robin_pos: some w_f > 0 - the operator is definite without a fixed DOF
-  int32_t robin_n = 0;                       // listed facets
-  DevBuf<int32_t> robin_tab;                 // the pieces of RobinLayout ...
-  RobinLayout robin_at;                      // ... and where they lie
-  DevBuf<double> robin_val;                  // w [n] | alpha [n] | FacetMass<p> [(p + 1)^2]
-  DevBuf<double> spring_kw;                  // bs = 2: Kw [n][3] = |E_f| (k00, k01, k11) | K [n][3]
+  FacetTerm facet;
   // the CSR pattern of the operator (eqlb_primal_matrix.hip): empty until eqlb_*_matrix_pattern
   MatrixPattern pattern;
 };
@@ -236,33 +227,38 @@ int primal_work(H* h, int R, PcgWork& w)
   return EQLB_OK;
 }
 
-// the table of the handle's Robin term for a sum pass: u the vector of the store pass (column 0), nullptr: the diagonal
+// the weights of the handle's facet term as the kernels of its bs read them, w [n] or Kw [n][3], and the coefficients
+// behind them, alpha [n] or K [n][3]
 template <class H>
-RobinArgs robin_args(const H& h, const double* u, bool only_fixed)
+const double* facet_weights(const H& h)
 {
-  RobinArgs x{};
-  const int32_t* tab = h.robin_tab.get();
-  const RobinLayout& at = h.robin_at;
+  return H::bs == 1 ? h.facet.val.get() : h.facet.kw.get();
+}
+template <class H>
+const double* facet_coeffs(const H& h)
+{
+  return facet_weights(h) + (H::bs == 1 ? 1 : 3) * (size_t)h.facet.n;
+}
+
+// the table of the handle's facet term for a sum pass: u the vector of the store pass (column 0), nullptr: the diagonal
+template <class H>
+FacetTermArgs facet_args(const H& h, const double* u, bool only_fixed)
+{
+  FacetTermArgs x{};
+  const int32_t* tab = h.facet.tab.get();
+  const FacetLayout& at = h.facet.at;
   x.dofs = tab + at.dofs;
   x.chunk = tab + at.chunk;
   x.rows = tab + at.rows;
   x.off = tab + at.off;
   x.ent = tab + at.ent;
-  x.w = h.robin_val.get();
-  x.fm = h.robin_val.get() + 2 * (size_t)h.robin_n;
+  x.w = facet_weights(h);
+  x.fm = h.facet.val.get() + 2 * (size_t)h.facet.n;
   x.u = u;
   x.fixed = h.fixed;
   x.only_fixed = only_fixed ? 1 : 0;
   x.n1 = h.p + 1;
   return x;
-}
-
-// ... and of its spring term (bs = 2): u [2 ndofs] blocked
-template <class H>
-SpringArgs spring_args(const H& h, const double* u, bool only_fixed)
-{
-  const RobinArgs r = robin_args(h, u, only_fixed);
-  return SpringArgs{r.chunk, r.rows, r.off, r.ent, r.dofs, h.spring_kw.get(), r.fm, u, r.fixed, r.only_fixed, r.n1};
 }
 
 template <class H>
@@ -292,32 +288,23 @@ hipError_t launch_gather(const H& h, const GatherArgs& g, hipStream_t stream)
   return hipGetLastError();
 }
 
-// the sum pass behind a store pass of the OPERATOR (u: what that pass read, nullptr: the diagonal): with a Robin term
-// (bs = 1) or a spring term (bs = 2) on the handle the variant that adds the facet values, else the launch above.  The sum pass of the load and of the
+// the sum pass behind a store pass of the OPERATOR (u: what that pass read, nullptr: the diagonal): with a facet term
+// on the handle the variant that adds the facet values, else the launch above.  The sum pass of the load and of the
 // restriction of a hierarchy (enqueue_owner_sum) never carries the term
 template <class H>
 hipError_t launch_gather_op(const H& h, const GatherArgs& g, const double* u, bool only_fixed, hipStream_t stream)
 {
-  if constexpr (H::bs == 1)
-    if (h.has_robin)
-    {
-      const dim3 grid(stream_blocks(h.ndofs)), block(PS_THREADS);
-      const RobinArgs x = robin_args(h, u, only_fixed);
-      if (g.cols.R == 1)
-        hipLaunchKernelGGL((k_primal_gather_robin<1, 1>), grid, block, 0, stream, g, x);
-      else
-        hipLaunchKernelGGL((k_primal_gather_robin<1, MANY_R>), grid, block, 0, stream, g, x);
-      return hipGetLastError();
-    }
-  if constexpr (H::bs == 2)
-    if (h.has_robin)
-    {
-      const SpringArgs x = spring_args(h, u, only_fixed);
-      hipLaunchKernelGGL((k_primal_gather_spring<2, 1>), dim3(stream_blocks(2 * h.ndofs)), dim3(PS_THREADS), 0, stream, g,
-                         x);
-      return hipGetLastError();
-    }
-  return launch_gather(h, g, stream);
+  if (!h.facet.on)
+    return launch_gather(h, g, stream);
+  const dim3 grid(stream_blocks(H::bs * h.ndofs)), block(PS_THREADS);
+  const FacetTermArgs x = facet_args(h, u, only_fixed);
+  if constexpr (H::max_cols == 1)
+    hipLaunchKernelGGL((k_primal_gather_facet<H::bs, 1>), grid, block, 0, stream, g, x);
+  else if (g.cols.R == 1)
+    hipLaunchKernelGGL((k_primal_gather_facet<H::bs, 1>), grid, block, 0, stream, g, x);
+  else
+    hipLaunchKernelGGL((k_primal_gather_facet<H::bs, MANY_R>), grid, block, 0, stream, g, x);
+  return hipGetLastError();
 }
 
 // y = owner sum of y_loc (masked or raw) on the columns of c; y DEVICE [R][bs ndofs]
@@ -395,7 +382,7 @@ void solver_level(H* h, SolverLevel& v)
   v.product = [](void* hh, const ManyCols& c, hipStream_t stream) {
     return enqueue_product(*static_cast<H*>(hh), c, stream);
   };
-  v.definite = [](void* hh) { return static_cast<H*>(hh)->has_robin && static_cast<H*>(hh)->robin_pos; };
+  v.definite = [](void* hh) { return static_cast<H*>(hh)->facet.on && static_cast<H*>(hh)->facet.positive; };
 }
 
 // the handle as the matrix unit sees it; a unit with further coefficients (pi_1, the shear modulus) adds them
@@ -415,20 +402,12 @@ void solver_matrix_view(H* h, MatrixView& v)
   v.dx = diff_args(h->diff);
   v.fixed = h->fixed;
   v.pattern = &h->pattern;
-  if constexpr (H::bs == 1)
-    if (h->has_robin)
-    {
-      v.has_robin = true;
-      v.robin_m = (int32_t)h->robin_at.m();
-      v.robin = robin_args(*h, nullptr, false);
-    }
-  if constexpr (H::bs == 2)
-    if (h->has_robin)
-    {
-      v.has_robin = true;
-      v.robin_m = (int32_t)h->robin_at.m();
-      v.spring = spring_args(*h, nullptr, false);
-    }
+  if (h->facet.on)
+  {
+    v.has_facet = true;
+    v.facet_m = (int32_t)h->facet.at.m();
+    v.facet = facet_args(*h, nullptr, false);
+  }
 }
 
 // ---- the C entries behind their names (`who`) -------------------------------------------------------------------------
@@ -444,7 +423,7 @@ inline int check_facet_list(const char* who, int32_t nlist, const int32_t* facet
 {
   if (nlist < 0 || (nlist > 0 && !facets))
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d, or a null list", who, (int)nlist);
-  if (nlist >= (1 << 28))
+  if (nlist >= FACET_LIST_END) // (2^28: eqlb_facet_plan.h)
     return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nlist = %d: at most 2^28 - 1 facets", who, (int)nlist);
   return EQLB_OK;
 }
@@ -453,8 +432,8 @@ inline int check_facet_list(const char* who, int32_t nlist, const int32_t* facet
 template <class H>
 int solver_facet_term_off(H* h, int32_t memspace, hipStream_t stream)
 {
-  h->has_robin = h->robin_pos = false;
-  h->robin_n = 0;
+  h->facet.on = h->facet.positive = false;
+  h->facet.n = 0;
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
   if (memspace == EQLB_MEM_HOST)
     HIP_TRY(hipStreamSynchronize(stream));
@@ -468,14 +447,15 @@ template <class H>
 int solver_facet_term_commit(H* h, FacetTermPlan& plan, int32_t nlist, bool positive, int32_t memspace,
                              hipStream_t stream, DevBuf<double>* kw = nullptr)
 {
+  FacetTerm& t = h->facet;
   if (kw)
-    h->spring_kw = std::move(*kw);
-  h->robin_tab = std::move(plan.tab);
-  h->robin_val = std::move(plan.val);
-  h->robin_n = nlist;
-  h->robin_at = RobinLayout((size_t)nlist, plan.nchunk, plan.m, plan.nent);
-  h->has_robin = true;
-  h->robin_pos = positive;
+    t.kw = std::move(*kw);
+  t.tab = std::move(plan.tab);
+  t.val = std::move(plan.val);
+  t.n = nlist;
+  t.at = plan.at;
+  t.on = true;
+  t.positive = positive;
   HIP_TRY(enqueue_diagonal(*h, h->diag, stream));
   if (memspace == EQLB_MEM_HOST)
     HIP_TRY(hipStreamSynchronize(stream));
@@ -484,7 +464,7 @@ int solver_facet_term_commit(H* h, FacetTermPlan& plan, int32_t nlist, bool posi
 
 // the points of eqlb_primal_robin_flux and eqlb_elasticity_spring_flux, a kernel argument
 constexpr int RF_MAX_NQ = 64;
-struct RobinRule
+struct FacetRule
 {
   double s[RF_MAX_NQ];
 };
@@ -495,8 +475,7 @@ struct RobinRule
 // equispaced 1-D Lagrange basis in the facet-local order: the product over the other nodes k, in that order, of
 // (s - x_k) / (x_j - x_k) with x = (0, 1, 1/p ... (p-1)/p) formed as j / p, the first factor starts it, every operation
 // rounded on its own.  dd: the facet's rows (k_robin_prepare; dd[0] < 0: skipped).  False, and nothing written, for a
-// facet the list skipped or whose cell does not hold it; every index is checked before it is used.  k_spring_flux uses
-// it; k_robin_flux holds the same lines in its body, as it did before this helper existed.
+// facet the list skipped or whose cell does not hold it; every index is checked before it is used.
 __device__ __forceinline__ bool facet_point_basis(int32_t f, const int32_t* dd, double sq, int p, int32_t ncells,
                                                   const int32_t* cell_nodes, const int32_t* cell_facets,
                                                   const int32_t* fco, const int32_t* facet_cells, double* l)
@@ -536,6 +515,132 @@ __device__ __forceinline__ bool facet_point_basis(int32_t f, const int32_t* dd, 
     l[j] = v;
   }
   return true;
+}
+
+// One thread per (listed facet, point), all BS rows, the kernel of eqlb_primal_robin_flux (BS = 1) and
+// eqlb_elasticity_spring_flux (BS = 2): with d_s = u_h,s(x_q) - u_ext[s][i][q] on component s of the blocked u,
+//   BS = 1  out[i][q] = alpha_i d_0                              coeff: alpha [nlist]
+//   BS = 2  out[r][i][q] = K_i[r][0] d_0 + K_i[r][1] d_1         coeff: K [nlist][3] = (k00, k01, k11)
+// The frame and the basis l_j come from facet_point_basis; u_h,s is the sum of l_j u[BS dof_j + s] in ascending j, the
+// first product starts it; u_ext is subtracted last; the contraction with K is two products and one addition.  Every
+// operation rounded on its own.  A facet the list skipped gives NaN.
+template <int BS>
+__global__ void __launch_bounds__(PS_THREADS)
+k_facet_flux(int32_t nlist, int32_t nq, int32_t p, const FacetRule rule, const int32_t* __restrict__ flist,
+             const int32_t* __restrict__ dofs, const double* __restrict__ coeff, int32_t ncells,
+             const int32_t* __restrict__ cell_nodes, const int32_t* __restrict__ cell_facets,
+             const int32_t* __restrict__ fco, const int32_t* __restrict__ facet_cells, const double* __restrict__ u,
+             const double* __restrict__ u_ext, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  static_assert(BS == 1 || BS == 2, "a Robin term (BS = 1) or a spring term (BS = 2)");
+  const int64_t total = (int64_t)nlist * nq;
+  const int64_t t = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= total)
+    return;
+  const int64_t i = t / nq;
+  const int q = (int)(t - i * nq);
+  const int32_t* dd = dofs + i * FACET_ROW;
+  double l[PS_PMAX + 1];
+  if (!facet_point_basis(flist[i], dd, rule.s[q], p, ncells, cell_nodes, cell_facets, fco, facet_cells, l))
+  {
+    if constexpr (BS == 2)
+      out[total + t] = __builtin_nan("");
+    out[t] = __builtin_nan("");
+    return;
+  }
+  double d0 = 0.0, d1 = 0.0; // (d1: BS = 2 only)
+  for (int j = 0; j <= p; ++j)
+  {
+    const double p0 = l[j] * u[BS * (int64_t)dd[j]];
+    d0 = j == 0 ? p0 : d0 + p0;
+    if constexpr (BS == 2)
+    {
+      const double p1 = l[j] * u[2 * (int64_t)dd[j] + 1];
+      d1 = j == 0 ? p1 : d1 + p1;
+    }
+  }
+  if (u_ext)
+  {
+    d0 = d0 - u_ext[t];
+    if constexpr (BS == 2)
+      d1 = d1 - u_ext[total + t];
+  }
+  if constexpr (BS == 1)
+    out[t] = coeff[i] * d0;
+  else
+  {
+    const double* k = coeff + 3 * i;
+    out[t] = k[0] * d0 + k[1] * d1;
+    out[total + t] = k[1] * d0 + k[2] * d1;
+  }
+}
+
+// the body of eqlb_primal_robin_weights / eqlb_elasticity_spring_weights: *nlist (or nullptr) the listed facets, w
+// [capacity >= nlist] rows of one weight (bs = 1) or three (bs = 2) in `memspace`
+template <class H>
+int solver_facet_weights(const char* who, H* h, int32_t* nlist, double* w, int32_t capacity, int32_t memspace,
+                         void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  const int32_t n = h->facet.on ? h->facet.n : 0;
+  if (nlist)
+    *nlist = n;
+  if (!w || n == 0)
+    return EQLB_OK;
+  if (capacity < n)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: capacity = %d is less than the %d listed facets", who, (int)capacity,
+                (int)n);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  HIP_TRY(hipMemcpyAsync(w, facet_weights(*h), (H::bs == 1 ? 1 : 3) * (size_t)n * sizeof(double),
+                         host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+  if (host)
+    HIP_TRY(hipStreamSynchronize(stream));
+  return EQLB_OK;
+}
+
+// the body of eqlb_primal_robin_flux / eqlb_elasticity_spring_flux (k_facet_flux): u [bs ndofs], s HOST [nq], u_ext
+// (or nullptr) and out [bs][nlist][nq].  `term` and `setter` name the term and its entry in the message of a handle
+// without one
+template <class H>
+int solver_facet_flux(const char* who, const char* term, const char* setter, H* h, const double* u, int32_t nq,
+                      const double* s, const double* u_ext, double* out, int32_t memspace, void* stream_)
+{
+  EQLB_TRY(check_handle(who, h));
+  EQLB_TRY(check_memspace(who, memspace));
+  if (!u || !s || !out)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (nq < 1 || nq > RF_MAX_NQ)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nq = %d outside 1 ... %d", who, (int)nq, RF_MAX_NQ);
+  FacetRule rule{};
+  for (int q = 0; q < nq; ++q)
+  {
+    if (!(s[q] >= 0.0 && s[q] <= 1.0))
+      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: s[%d] = %g outside [0, 1]", who, q, s[q]);
+    rule.s[q] = s[q];
+  }
+  if (!h->facet.on)
+    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: the handle has no %s term (%s first)", who, term, setter);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const bool host = memspace == EQLB_MEM_HOST;
+  const DeviceMesh& m = h->mesh->m;
+  const size_t np = (size_t)h->facet.n * (size_t)nq, no = H::bs * np;
+  HostCall c;
+  const auto d_u = c.in(host ? u : nullptr, (size_t)H::bs * h->ndofs);
+  const auto d_e = c.in(host ? u_ext : nullptr, no);
+  const auto d_o = c.out(host ? out : nullptr, no);
+  if (host)
+    HIP_TRY(c.upload(stream));
+  const int32_t* tab = h->facet.tab.get();
+  hipLaunchKernelGGL(k_facet_flux<H::bs>, dim3(grid_of((int64_t)np, PS_THREADS)), dim3(PS_THREADS), 0, stream,
+                     h->facet.n, nq, (int32_t)h->p, rule, tab, tab + h->facet.at.dofs, facet_coeffs(*h), m.ncells,
+                     m.cell_nodes, m.cell_facets, m.facet_cells_off, m.facet_cells, host ? d_u.get() : u,
+                     host ? d_e.get() : u_ext, host ? d_o.get() : out);
+  c.note(hipGetLastError());
+  HIP_TRY(c.finish(stream));
+  return EQLB_OK;
 }
 
 // what every *_many entry checks about its column count
@@ -842,7 +947,7 @@ int solver_solve(const char* who, H* h, int32_t nrhs, const double* b, double* u
   HIP_TRY(hipMemcpyAsync(status, h->status.get(), sizeof(status), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (int r = 0; r < H::bs; ++r)
-    if (status[1 + r] < 1 && !(h->has_robin && h->robin_pos)) // (a Robin term with some w_f > 0: definite as it is)
+    if (status[1 + r] < 1 && !(h->facet.on && h->facet.positive)) // (a facet term with some weight > 0: definite as it is)
     {
       if constexpr (H::bs == 1)
         return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: singular: no Dirichlet DOF (eqlb_primal_set_dirichlet first)", who);

@@ -259,74 +259,28 @@ __global__ void __launch_bounds__(MX_THREADS) k_matrix_fill(const FillArgs a)
   }
 }
 
-// The Robin term of a Poisson handle (include/eqlb.h: eqlb_primal_set_robin) on top of the filled values: one thread per
-// row that lies in a Robin facet walks the facets of the row in ascending id (the table of the sum pass) and adds
-// w_f FacetMass[i][j] to the entry (d, d_j) of every row d_j of the facet, each by one addition - the cell sums first,
-// then the facets ascending, as the statement has it; the diagonal entry gets the bits of the handle's diagonal.  The
-// pattern holds every such pair (both rows lie in the facet's cell); an eliminated entry keeps its 0.0 or 1.0.
-struct RobinFillArgs
+// The facet term of a handle on top of the filled values: one thread per DOF d that lies in a listed facet walks the
+// facets of the DOF in ascending id (the table of the sum pass) and adds to the entries of every DOF d_j of the facet,
+// each by one addition - the cell sums first, then the facets ascending, as the statement has it; the diagonal entry
+// gets the bits of the handle's diagonal.  An eliminated entry keeps its 0.0 or 1.0.
+//   BS = 1  the Robin term (include/eqlb.h: eqlb_primal_set_robin): w_f FacetMass[i][j] to the entry (d, d_j).  The
+//           pattern holds every such pair (both rows lie in the facet's cell)
+//   BS = 2  the spring term (eqlb_elasticity_set_springs): Kw[r][s] FacetMass[i][j] to the entry (2 d + r, 2 d_j + s).
+//           The pattern is the scalar one and every pair of DOFs of a cell carries its full 2 x 2 block, so every such
+//           entry exists: row 2 d + r starts at 4 sptr[d] + 2 r len(d), and pair k of the row holds the columns at 2 k + s
+struct FacetFillArgs
 {
   int32_t m, n1;
   const int32_t *rows, *off, *ent, *dofs;
-  const double *w, *fm;
-  const uint8_t* fixed; // nullptr: the raw operator
+  const double *w, *fm; // w: [nlist] (BS = 1) or [nlist][3] (BS = 2), FacetTermArgs
+  const uint8_t* fixed; // [BS ndofs]; nullptr: the raw operator
   const int64_t* sptr;
   const int32_t* scol;
   double* values;
 };
 
-__global__ void __launch_bounds__(MX_THREADS) k_matrix_robin(const RobinFillArgs a)
-{
-#pragma clang fp contract(off)
-  for (int32_t mi = blockIdx.x * MX_THREADS + threadIdx.x; mi < a.m; mi += gridDim.x * MX_THREADS)
-  {
-    const int64_t d = a.rows[mi];
-    const int64_t p0 = a.sptr[d], p1 = a.sptr[d + 1];
-    for (int q = a.off[mi]; q < a.off[mi + 1]; ++q)
-    {
-      const int32_t en = a.ent[q];
-      const int i = en & 7;
-      const int64_t li = en >> 3;
-      const int32_t* dd = a.dofs + li * ROBIN_ROW;
-      const double w = a.w[li];
-      for (int j = 0; j < a.n1; ++j)
-      {
-        const int32_t dc = dd[j];
-        if (a.fixed && (a.fixed[d] || a.fixed[dc]))
-          continue;
-        int64_t lo = p0, hi = p1;
-        while (lo < hi)
-        {
-          const int64_t mid = (lo + hi) >> 1;
-          if (a.scol[mid] < dc)
-            lo = mid + 1;
-          else
-            hi = mid;
-        }
-        if (lo < p1 && a.scol[lo] == dc)
-          a.values[lo] = a.values[lo] + w * a.fm[i * a.n1 + j];
-      }
-    }
-  }
-}
-
-// The spring term of an elasticity handle (include/eqlb.h: eqlb_elasticity_set_springs), the bs = 2 counterpart: one
-// thread per DOF d that lies in a spring facet walks the facets of the DOF in ascending id and adds Kw[r][s]
-// FacetMass[i][j] to the entry (2 d + r, 2 d_j + s) of every DOF d_j of the facet, each by one addition.  The pattern
-// is the scalar one and every pair of DOFs of a cell carries its full 2 x 2 block, so every such entry exists: row
-// 2 d + r starts at 4 sptr[d] + 2 r len(d), and pair k of the row holds the columns at 2 k + s.
-struct SpringFillArgs
-{
-  int32_t m, n1;
-  const int32_t *rows, *off, *ent, *dofs;
-  const double *kw, *fm;
-  const uint8_t* fixed; // [2 ndofs]; nullptr: the raw operator
-  const int64_t* sptr;
-  const int32_t* scol;
-  double* values;
-};
-
-__global__ void __launch_bounds__(MX_THREADS) k_matrix_spring(const SpringFillArgs a)
+template <int BS>
+__global__ void __launch_bounds__(MX_THREADS) k_matrix_facet(const FacetFillArgs a)
 {
 #pragma clang fp contract(off)
   for (int32_t mi = blockIdx.x * MX_THREADS + threadIdx.x; mi < a.m; mi += gridDim.x * MX_THREADS)
@@ -338,11 +292,14 @@ __global__ void __launch_bounds__(MX_THREADS) k_matrix_spring(const SpringFillAr
       const int32_t en = a.ent[q];
       const int i = en & 7;
       const int64_t li = en >> 3;
-      const int32_t* dd = a.dofs + li * ROBIN_ROW;
-      const double* kw = a.kw + 3 * li;
+      const int32_t* dd = a.dofs + li * FACET_ROW;
+      const double* w = a.w + (BS == 1 ? 1 : 3) * li;
       for (int j = 0; j < a.n1; ++j)
       {
         const int32_t dc = dd[j];
+        if constexpr (BS == 1)
+          if (a.fixed && (a.fixed[d] || a.fixed[dc]))
+            continue;
         int64_t lo = p0, hi = p1;
         while (lo < hi)
         {
@@ -355,14 +312,17 @@ __global__ void __launch_bounds__(MX_THREADS) k_matrix_spring(const SpringFillAr
         if (!(lo < p1 && a.scol[lo] == dc))
           continue;
         const double f = a.fm[i * a.n1 + j];
-        for (int r = 0; r < 2; ++r)
-          for (int s = 0; s < 2; ++s)
-          {
-            if (a.fixed && (a.fixed[2 * d + r] || a.fixed[2 * (int64_t)dc + s]))
-              continue;
-            const int64_t pos = 4 * p0 + r * 2 * len + 2 * (lo - p0) + s;
-            a.values[pos] = a.values[pos] + kw[r + s] * f;
-          }
+        if constexpr (BS == 1)
+          a.values[lo] = a.values[lo] + w[0] * f;
+        else
+          for (int r = 0; r < 2; ++r)
+            for (int s = 0; s < 2; ++s)
+            {
+              if (a.fixed && (a.fixed[2 * d + r] || a.fixed[2 * (int64_t)dc + s]))
+                continue;
+              const int64_t pos = 4 * p0 + r * 2 * len + 2 * (lo - p0) + s;
+              a.values[pos] = a.values[pos] + w[r + s] * f;
+            }
       }
     }
   }
@@ -607,20 +567,16 @@ int matrix_values(const char* who, const MatrixView& v, int32_t eliminate, doubl
     HIP_TRY(s.upload(stream));
   double* pv = host ? d_v.get() : values;
   s.note(v.bs == 1 ? launch_fill<1>(v, eliminate != 0, pv, stream) : launch_fill<2>(v, eliminate != 0, pv, stream));
-  if (v.bs == 1 && v.has_robin && v.robin_m > 0)
+  if (v.has_facet && v.facet_m > 0)
   {
-    const RobinArgs& x = v.robin;
-    const RobinFillArgs a{v.robin_m, x.n1, x.rows, x.off, x.ent, x.dofs, x.w, x.fm, eliminate ? v.fixed : nullptr,
+    const FacetTermArgs& x = v.facet;
+    const FacetFillArgs a{v.facet_m, x.n1, x.rows, x.off, x.ent, x.dofs, x.w, x.fm, eliminate ? v.fixed : nullptr,
                           v.pattern->sptr.get(), v.pattern->scol.get(), pv};
-    hipLaunchKernelGGL(k_matrix_robin, dim3(mx_blocks(v.robin_m)), dim3(MX_THREADS), 0, stream, a);
-    s.note(hipGetLastError());
-  }
-  if (v.bs == 2 && v.has_robin && v.robin_m > 0)
-  {
-    const SpringArgs& x = v.spring;
-    const SpringFillArgs a{v.robin_m, x.n1, x.rows, x.off, x.ent, x.dofs, x.kw, x.fm, eliminate ? v.fixed : nullptr,
-                           v.pattern->sptr.get(), v.pattern->scol.get(), pv};
-    hipLaunchKernelGGL(k_matrix_spring, dim3(mx_blocks(v.robin_m)), dim3(MX_THREADS), 0, stream, a);
+    const dim3 grid(mx_blocks(v.facet_m)), block(MX_THREADS);
+    if (v.bs == 1)
+      hipLaunchKernelGGL(k_matrix_facet<1>, grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL(k_matrix_facet<2>, grid, block, 0, stream, a);
     s.note(hipGetLastError());
   }
   HIP_TRY(s.finish(stream));

@@ -245,7 +245,7 @@ k_robin_prepare(int32_t nlist, const int32_t* __restrict__ facets, double alpha,
     return;
   const int32_t f = facets[i];
   const double a = facet_alpha ? facet_alpha[i] : alpha;
-  int32_t* dd = dofs + (int64_t)i * ROBIN_ROW;
+  int32_t* dd = dofs + (int64_t)i * FACET_ROW;
   int32_t fl = 0, n0 = -1, n1 = -1;
   if (f >= 0 && f < nfacets)
   {
@@ -260,7 +260,7 @@ k_robin_prepare(int32_t nlist, const int32_t* __restrict__ facets, double alpha,
   if (fl != 1)
   {
     w[i] = 0.0;
-    for (int j = 0; j < ROBIN_ROW; ++j)
+    for (int j = 0; j < FACET_ROW; ++j)
       dd[j] = -1;
     return;
   }
@@ -268,72 +268,8 @@ k_robin_prepare(int32_t nlist, const int32_t* __restrict__ facets, double alpha,
   w[i] = a * sqrt(dx * dx + dy * dy);
   dd[0] = n0 < n1 ? n0 : n1;
   dd[1] = n0 < n1 ? n1 : n0;
-  for (int j = 0; j < ROBIN_ROW - 2; ++j)
+  for (int j = 0; j < FACET_ROW - 2; ++j)
     dd[2 + j] = j < ne ? nnodes + f * ne + j : -1;
-}
-
-// One thread per (listed facet, point): out[i][q] = alpha_i (u_h(x_q) - u_ext[i][q]) at the facet parameter s_q in the
-// frame of eqlb_facet_points (the facet seen from its one cell, the low local vertex first).  The parameter of the
-// facet's own frame (0 at the lower node id) is s or 1 - s; l_j is the product over the other nodes k, in the local
-// order, of (s - x_k) / (x_j - x_k) with x = (0, 1, 1/p ... (p-1)/p), the first factor starts it; u_h is the sum of
-// l_j u[dof_j] in ascending j, the first product starts it.  Every operation rounded on its own.  A facet the list
-// skipped gives NaN; every index is checked before it is used.
-__global__ void __launch_bounds__(PS_THREADS)
-k_robin_flux(int32_t nlist, int32_t nq, int32_t p, const RobinRule rule, const int32_t* __restrict__ flist,
-             const int32_t* __restrict__ dofs, const double* __restrict__ al, int32_t ncells,
-             const int32_t* __restrict__ cell_nodes, const int32_t* __restrict__ cell_facets,
-             const int32_t* __restrict__ fco, const int32_t* __restrict__ facet_cells, const double* __restrict__ u,
-             const double* __restrict__ u_ext, double* __restrict__ out)
-{
-#pragma clang fp contract(off)
-  const int64_t t = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= (int64_t)nlist * nq)
-    return;
-  const int64_t i = t / nq;
-  const int q = (int)(t - i * nq);
-  const int32_t* dd = dofs + i * ROBIN_ROW;
-  const int32_t f = flist[i];
-  int lf = -1;
-  int32_t cell = -1;
-  if (dd[0] >= 0) // (a boundary facet inside the mesh: k_robin_prepare)
-  {
-    cell = facet_cells[fco[f]];
-    if (cell >= 0 && cell < ncells)
-      for (int l = 0; l < 3; ++l)
-        if (cell_facets[(int64_t)cell * 3 + l] == f)
-          lf = l;
-  }
-  if (lf < 0)
-  {
-    out[t] = __builtin_nan("");
-    return;
-  }
-  const int va = (lf == 0) ? 1 : 0, vb = (lf == 2) ? 1 : 2; // the low local vertex first
-  const bool same = cell_nodes[(int64_t)cell * 3 + va] < cell_nodes[(int64_t)cell * 3 + vb];
-  const double s = same ? rule.s[q] : 1.0 - rule.s[q];
-  double xn[PS_PMAX + 1];
-  xn[0] = 0.0;
-  xn[1] = 1.0;
-  for (int j = 1; j < p; ++j)
-    xn[1 + j] = (double)j / (double)p;
-  double uh = 0.0;
-  for (int j = 0; j <= p; ++j)
-  {
-    double l = 1.0;
-    bool first = true;
-    for (int k = 0; k <= p; ++k)
-      if (k != j)
-      {
-        const double fac = (s - xn[k]) / (xn[j] - xn[k]);
-        l = first ? fac : l * fac;
-        first = false;
-      }
-    const double pr = l * u[dd[j]];
-    uh = j == 0 ? pr : uh + pr;
-  }
-  if (u_ext)
-    uh = uh - u_ext[t];
-  out[t] = al[i] * uh;
 }
 
 const double* facet_mass_of(int p)
@@ -359,9 +295,9 @@ int facet_term_plan(const char* who, eqlb_mesh* mesh, int p, int64_t ndofs, int 
   const int n1 = p + 1;
   DevBuf<double>& val = out.val;
   DevBuf<int32_t> head; // facets | dofs | flag
-  if (val.alloc_raw(2 * n + (size_t)n1 * n1) != hipSuccess || head.alloc_raw(n * (2 + ROBIN_ROW)) != hipSuccess)
+  if (val.alloc_raw(2 * n + (size_t)n1 * n1) != hipSuccess || head.alloc_raw(n * (2 + FACET_ROW)) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
-  std::vector<int32_t> hh(n * (2 + ROBIN_ROW));
+  std::vector<int32_t> hh(n * (2 + FACET_ROW));
   std::vector<double>& hw = out.w;
   hw.assign(n, 0.0);
   {
@@ -373,7 +309,7 @@ int facet_term_plan(const char* who, eqlb_mesh* mesh, int p, int64_t ndofs, int 
     int32_t* flist = head.get();
     hipLaunchKernelGGL(k_robin_prepare, dim3(grid_of(nlist, PS_THREADS)), dim3(PS_THREADS), 0, stream, nlist,
                        host ? d_f.get() : facets, alpha, host ? d_a.get() : facet_alpha, m.nnodes, m.nfacets, p - 1,
-                       m.x, m.facet_nodes, m.facet_cells_off, flist, flist + n, flist + n * (1 + ROBIN_ROW), val.get(),
+                       m.x, m.facet_nodes, m.facet_cells_off, flist, flist + n, flist + n * (1 + FACET_ROW), val.get(),
                        val.get() + n);
     s.note(hipGetLastError());
     s.note(hipMemcpyAsync(val.get() + 2 * n, facet_mass_of(p), (size_t)n1 * n1 * sizeof(double),
@@ -384,7 +320,7 @@ int facet_term_plan(const char* who, eqlb_mesh* mesh, int p, int64_t ndofs, int 
     HIP_TRY(s.finish(stream));
   }
   const int32_t* hd = hh.data() + n;
-  const int32_t* hflag = hh.data() + n * (1 + ROBIN_ROW);
+  const int32_t* hflag = hh.data() + n * (1 + FACET_ROW);
   if (host)
   {
     std::unordered_set<int32_t> seen;
@@ -398,56 +334,21 @@ int facet_term_plan(const char* who, eqlb_mesh* mesh, int p, int64_t ndofs, int 
       EQLB_TRY(refuse(i));
     }
   }
-  // the entries (row, facet, list position, local index), sorted by row, then facet, then position
-  struct Entry
-  {
-    int32_t row, facet, pos, loc;
-  };
-  std::vector<Entry> ent;
-  for (int32_t i = 0; i < nlist; ++i)
-  {
-    if (hflag[i] != 1)
-      continue; // (device memory space: skipped)
-    for (int j = 0; j < n1; ++j)
-      ent.push_back(Entry{hd[(size_t)i * ROBIN_ROW + j], hh[(size_t)i], i, j});
-  }
-  std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) {
-    return a.row != b.row ? a.row < b.row : a.facet != b.facet ? a.facet < b.facet : a.pos < b.pos;
-  });
-  const size_t nch = (size_t)((ndofs + chunk_dofs - 1) / chunk_dofs);
-  std::vector<int32_t> rows, off, packed(ent.size());
-  for (size_t k = 0; k < ent.size(); ++k)
-  {
-    if (k == 0 || ent[k].row != ent[k - 1].row)
-    {
-      rows.push_back(ent[k].row);
-      off.push_back((int32_t)k);
-    }
-    packed[k] = ent[k].pos * 8 + ent[k].loc;
-  }
-  off.push_back((int32_t)ent.size());
-  std::vector<int32_t> chunk(nch + 1);
-  for (size_t c = 0; c <= nch; ++c)
-    chunk[c] = (int32_t)(std::lower_bound(rows.begin(), rows.end(), (int32_t)std::min<int64_t>((int64_t)c * chunk_dofs,
-                                                                                              INT32_MAX))
-                         - rows.begin());
-  chunk[nch] = (int32_t)rows.size();
-  // one array (facets and dofs as the device left them in hh)
-  const RobinLayout at(n, chunk.size(), rows.size(), packed.size());
+  // the table of the sum pass (eqlb_facet_plan.h), in one array behind the facets and dofs as the device left them in hh
+  const FacetTable t = facet_plan(n, hflag, hh.data(), hd, n1, ndofs, chunk_dofs);
+  const FacetLayout& at = t.at;
   std::vector<int32_t> tab(at.total);
   std::copy(hh.begin(), hh.begin() + (std::ptrdiff_t)at.chunk, tab.begin());
-  std::copy(chunk.begin(), chunk.end(), tab.begin() + (std::ptrdiff_t)at.chunk);
-  std::copy(rows.begin(), rows.end(), tab.begin() + (std::ptrdiff_t)at.rows);
-  std::copy(off.begin(), off.end(), tab.begin() + (std::ptrdiff_t)at.off);
-  std::copy(packed.begin(), packed.end(), tab.begin() + (std::ptrdiff_t)at.ent);
+  std::copy(t.chunk.begin(), t.chunk.end(), tab.begin() + (std::ptrdiff_t)at.chunk);
+  std::copy(t.rows.begin(), t.rows.end(), tab.begin() + (std::ptrdiff_t)at.rows);
+  std::copy(t.off.begin(), t.off.end(), tab.begin() + (std::ptrdiff_t)at.off);
+  std::copy(t.ent.begin(), t.ent.end(), tab.begin() + (std::ptrdiff_t)at.ent);
   DevBuf<int32_t>& dtab = out.tab;
   if (dtab.alloc_raw(at.total) != hipSuccess)
     return fail(EQLB_ERR_NO_MEMORY, "%s: device allocation failed", who);
   HIP_TRY(hipMemcpyAsync(dtab.get(), tab.data(), at.total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipStreamSynchronize(stream)); // (tab ends with this call; nothing on the stream reads the old table any more)
-  out.nchunk = chunk.size();
-  out.m = rows.size();
-  out.nent = packed.size();
+  out.at = at;
   out.flag.assign(hflag, hflag + n);
   return EQLB_OK;
 }
@@ -615,25 +516,7 @@ int eqlb_primal_robin_weights(eqlb_primal_t* h, int32_t* nlist, double* w, int32
                               void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* who = "eqlb_primal_robin_weights";
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  const int32_t n = h->has_robin ? h->robin_n : 0;
-  if (nlist)
-    *nlist = n;
-  if (!w || n == 0)
-    return EQLB_OK;
-  if (capacity < n)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: capacity = %d is less than the %d listed facets", who, (int)capacity,
-                (int)n);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  HIP_TRY(hipMemcpyAsync(w, h->robin_val.get(), (size_t)n * sizeof(double),
-                         host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
-  if (host)
-    HIP_TRY(hipStreamSynchronize(stream));
-  return EQLB_OK;
+  return eqlb::solver_facet_weights("eqlb_primal_robin_weights", h, nlist, w, capacity, memspace, stream_);
 }
 EQLB_CATCH_ALL
 
@@ -641,41 +524,8 @@ int eqlb_primal_robin_flux(eqlb_primal_t* h, const double* u, int32_t nq, const 
                            double* out, int32_t memspace, void* stream_)
 try
 {
-  using namespace eqlb;
-  const char* who = "eqlb_primal_robin_flux";
-  EQLB_TRY(check_handle(who, h));
-  EQLB_TRY(check_memspace(who, memspace));
-  if (!u || !s || !out)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  if (nq < 1 || nq > RF_MAX_NQ)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: nq = %d outside 1 ... %d", who, (int)nq, RF_MAX_NQ);
-  RobinRule rule{};
-  for (int q = 0; q < nq; ++q)
-  {
-    if (!(s[q] >= 0.0 && s[q] <= 1.0))
-      return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: s[%d] = %g outside [0, 1]", who, q, s[q]);
-    rule.s[q] = s[q];
-  }
-  if (!h->has_robin)
-    return fail(EQLB_ERR_INVALID_ARGUMENT, "%s: the handle has no Robin term (eqlb_primal_set_robin first)", who);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool host = memspace == EQLB_MEM_HOST;
-  const DeviceMesh& m = h->mesh->m;
-  const size_t n = (size_t)h->robin_n, no = n * (size_t)nq;
-  HostCall c;
-  const auto d_u = c.in(host ? u : nullptr, (size_t)h->ndofs);
-  const auto d_e = c.in(host ? u_ext : nullptr, no);
-  const auto d_o = c.out(host ? out : nullptr, no);
-  if (host)
-    HIP_TRY(c.upload(stream));
-  const int32_t* tab = h->robin_tab.get();
-  hipLaunchKernelGGL(k_robin_flux, dim3(grid_of((int64_t)no, PS_THREADS)), dim3(PS_THREADS), 0, stream, h->robin_n, nq,
-                     (int32_t)h->p, rule, tab, tab + h->robin_at.dofs, static_cast<const double*>(h->robin_val.get() + n), m.ncells,
-                     m.cell_nodes, m.cell_facets, m.facet_cells_off, m.facet_cells, host ? d_u.get() : u,
-                     host ? d_e.get() : u_ext, host ? d_o.get() : out);
-  c.note(hipGetLastError());
-  HIP_TRY(c.finish(stream));
-  return EQLB_OK;
+  return eqlb::solver_facet_flux("eqlb_primal_robin_flux", "Robin", "eqlb_primal_set_robin", h, u, nq, s, u_ext, out,
+                                 memspace, stream_);
 }
 EQLB_CATCH_ALL
 

@@ -358,6 +358,37 @@ darray csr_apply(carray<int64_t> indptr, carray<int32_t> indices, carray<double>
   return y;
 }
 
+// The facet term of a solver handle on host arrays - the Robin term of PrimalPoisson (one weight per facet, one row of
+// the flux), the spring term of PrimalElasticity (three weights, two rows): `weights` and `flux` are the entries
+// eqlb_*_weights and eqlb_*_flux of the handle type
+template <class H, class Weights>
+int32_t facet_count(H* h, Weights weights)
+{
+  int32_t n = 0;
+  check(weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
+  return n;
+}
+template <class H, class Weights>
+darray facet_weights(H* h, int width, Weights weights)
+{
+  int32_t n = facet_count(h, weights);
+  darray w = width == 1 ? darray((py::ssize_t)n) : darray({(py::ssize_t)n, (py::ssize_t)width});
+  if (n)
+    check(weights(h, &n, w.mutable_data(), n, EQLB_MEM_HOST, nullptr));
+  return w;
+}
+// out [nlist, nq] (rows = 1) or [rows, nlist, nq]; `expected`: the message for a u_ext of another size
+template <class H, class Weights, class Flux>
+darray facet_flux(H* h, int rows, const darray& u, const darray& s, py::object u_ext, const char* expected,
+                  Weights weights, Flux flux)
+{
+  const py::ssize_t n = facet_count(h, weights);
+  const OptArray e = opt_array(u_ext, rows * n * s.size(), expected);
+  darray out = rows == 1 ? darray({n, (py::ssize_t)s.size()}) : darray({(py::ssize_t)rows, n, (py::ssize_t)s.size()});
+  check(flux(h, u.data(), (int32_t)s.size(), s.data(), e.p, out.mutable_data(), EQLB_MEM_HOST, nullptr));
+  return out;
+}
+
 // -div(coeff grad u) = f on the conforming P_p space of the mesh, in the numbering of Mesh.lagrange_dofmap: operator,
 // load, residual and Jacobi-preconditioned CG on the device (eqlb_primal_*), on host arrays
 struct PrimalPoisson
@@ -409,26 +440,13 @@ struct PrimalPoisson
     check(eqlb_primal_set_robin(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, alpha,
                                 fa.a.size() ? fa.p : nullptr, EQLB_MEM_HOST, nullptr));
   }
-  darray robin_weights() const
-  {
-    int32_t n = 0;
-    check(eqlb_primal_robin_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
-    darray w(n);
-    if (n)
-      check(eqlb_primal_robin_weights(h, &n, w.mutable_data(), n, EQLB_MEM_HOST, nullptr));
-    return w;
-  }
+  darray robin_weights() const { return facet_weights(h, 1, eqlb_primal_robin_weights); }
   // out [nlist, nq] = alpha_i (u_h(x_q) - u_ext[i][q]) on the Robin list at the facet parameters s [nq]
   darray robin_flux(darray u, darray s, py::object u_ext) const
   {
     need(u, "robin_flux");
-    int32_t n = 0;
-    check(eqlb_primal_robin_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
-    const OptArray e = opt_array(u_ext, (py::ssize_t)n * s.size(), "PrimalPoisson.robin_flux: u_ext [nlist, nq] expected");
-    darray out({(py::ssize_t)n, (py::ssize_t)s.size()});
-    check(eqlb_primal_robin_flux(h, u.data(), (int32_t)s.size(), s.data(), e.p, out.mutable_data(), EQLB_MEM_HOST,
-                                 nullptr));
-    return out;
+    return facet_flux(h, 1, u, s, u_ext, "PrimalPoisson.robin_flux: u_ext [nlist, nq] expected",
+                      eqlb_primal_robin_weights, eqlb_primal_robin_flux);
   }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {
@@ -575,36 +593,14 @@ struct PrimalElasticity
     check(eqlb_elasticity_set_springs(h, (int32_t)facets.size(), facets.size() ? facets.data() : nullptr, k,
                                       !facet_k.is_none() && fk.size() ? fk.data() : nullptr, EQLB_MEM_HOST, nullptr));
   }
-  int spring_count() const
-  {
-    int32_t n = 0;
-    check(eqlb_elasticity_spring_weights(h, &n, nullptr, 0, EQLB_MEM_HOST, nullptr));
-    return n;
-  }
-  darray spring_weights() const
-  {
-    int32_t n = spring_count();
-    darray w({(py::ssize_t)n, (py::ssize_t)3});
-    if (n)
-      check(eqlb_elasticity_spring_weights(h, &n, w.mutable_data(), n, EQLB_MEM_HOST, nullptr));
-    return w;
-  }
+  int spring_count() const { return facet_count(h, eqlb_elasticity_spring_weights); }
+  darray spring_weights() const { return facet_weights(h, 3, eqlb_elasticity_spring_weights); }
   // out [2, nlist, nq] = K_i (u_h(x_q) - u_ext[.][i][q]) on the spring list at the facet parameters s [nq]
   darray spring_flux(darray u, darray s, py::object u_ext) const
   {
     need(u, "spring_flux");
-    const int32_t n = spring_count();
-    darray e;
-    if (!u_ext.is_none())
-    {
-      e = u_ext.cast<darray>();
-      if (e.size() != 2 * (py::ssize_t)n * s.size())
-        throw std::runtime_error("PrimalElasticity.spring_flux: u_ext [2, nlist, nq] expected");
-    }
-    darray out({(py::ssize_t)2, (py::ssize_t)n, (py::ssize_t)s.size()});
-    check(eqlb_elasticity_spring_flux(h, u.data(), (int32_t)s.size(), s.data(), u_ext.is_none() ? nullptr : e.data(),
-                                      out.mutable_data(), EQLB_MEM_HOST, nullptr));
-    return out;
+    return facet_flux(h, 2, u, s, u_ext, "PrimalElasticity.spring_flux: u_ext [2, nlist, nq] expected",
+                      eqlb_elasticity_spring_weights, eqlb_elasticity_spring_flux);
   }
   darray load(int degree_dg, darray rhs_dg, py::object b_extra) const
   {

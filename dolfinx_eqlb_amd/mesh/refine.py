@@ -182,6 +182,15 @@ def child_facets(mesh, node_parent_facet, mesh2, facets=None):
     return np.stack([first, second], axis=1).astype(np.int32)
 
 
+def _carry_facet_list(mesh, node_parent_facet, mesh2, f, values):
+    """The rule of a facet list with one row of values per facet across a refinement: the children of every listed facet
+    through child_facets, in the order of the list, first child first, the -1 of an unbisected facet left out; the
+    parent's row of values [nlist, ...] is copied to both."""
+    ch = child_facets(mesh, node_parent_facet, mesh2, f)
+    keep = ch >= 0
+    return ch[keep].astype(np.int32), np.repeat(values[:, None], 2, axis=1)[keep]
+
+
 def carry_robin_list(mesh, node_parent_facet, mesh2, facets, facet_alpha):
     """(facets2 int32, facet_alpha2) of a Robin list (PoissonOperator.set_robin) on the refined mesh `mesh2` - the
     statement of Refinement.carry_robin: the children of every listed facet through child_facets, in the order of the
@@ -190,9 +199,7 @@ def carry_robin_list(mesh, node_parent_facet, mesh2, facets, facet_alpha):
     a = np.asarray(facet_alpha, dtype=np.float64).ravel()
     if a.size != f.size:
         raise ValueError("carry_robin_list: facet_alpha [nlist] expected")
-    ch = child_facets(mesh, node_parent_facet, mesh2, f)
-    keep = ch >= 0
-    return ch[keep].astype(np.int32), np.repeat(a[:, None], 2, axis=1)[keep]
+    return _carry_facet_list(mesh, node_parent_facet, mesh2, f, a)
 
 
 def carry_springs_list(mesh, node_parent_facet, mesh2, facets, facet_k):
@@ -204,6 +211,4 @@ def carry_springs_list(mesh, node_parent_facet, mesh2, facets, facet_k):
     K = np.asarray(facet_k, dtype=np.float64)
     if K.size != 3 * f.size:
         raise ValueError("carry_springs_list: facet_k [nlist][3] expected")
-    ch = child_facets(mesh, node_parent_facet, mesh2, f)
-    keep = ch >= 0
-    return ch[keep].astype(np.int32), np.repeat(K.reshape(f.size, 1, 3), 2, axis=1)[keep]
+    return _carry_facet_list(mesh, node_parent_facet, mesh2, f, K.reshape(f.size, 3))

@@ -4,7 +4,9 @@ primal.py: PoissonOperator.set_robin) everywhere - apply (masked and not), diago
 comparison with np.sqrt is the test that the device square root is correctly rounded), matrix and matrix_values at
 p = 1 ... 4, the many-column forms, lists in device memory on a non-blocking stream, a three-level hierarchy with
 carry_robin between the levels (restrict carries no Robin term, precondition does), and the flux condition
-alpha (u_h - u_ext) handed to the equilibrator, against the oracle within the 1e-11 of tests/test_inhomogeneous_bc.py.
+alpha (u_h - u_ext) handed to the equilibrator, against the oracle within the 1e-11 of tests/test_inhomogeneous_bc.py;
+robin_flux at p = 1 ... 4 and nq = 1, 4, 64 in host and device memory, the NaN rows of ids a device-memory list skipped,
+and what robin_list() and carry_robin do with a list that was given through set_robin_raw.
 
 The cases: the 576-cell square of tests/test_gpu_primal_many.py with facet-wise random alpha in [0, 10] including exact
 zeros - Robin on two sides, Dirichlet on one, Neumann on one, and the same without the Dirichlet side - and from
@@ -356,3 +358,131 @@ def test_robin_flux_feeds_the_equilibrator(oracle_mod, k):
     print(f"k={k}: max |x - ref| / max |ref| = {np.abs(x - ref).max() / np.abs(ref).max():.2e}, max |ref| = "
           f"{np.abs(ref).max():.2e}, max |G| = {np.abs(lv['G']).max():.2e}")
     assert np.abs(x - ref).max() <= 1e-11 * np.abs(ref).max()
+
+
+# ---- robin_flux at every degree and point count ------------------------------------------------------------------------
+def flux_rules():
+    """the point sets of the flux tests: one point at each end of the facet, four and RF_MAX_NQ = 64 points with both
+    ends among them"""
+    rng = np.random.default_rng(64)
+    inner4, inner64 = rng.random(2), rng.random(62)
+    return [np.array([0.0]), np.array([1.0]), np.concatenate([[0.0], inner4, [1.0]]),
+            np.concatenate([[1.0], inner64, [0.0]])]
+
+
+@pytest.mark.parametrize("name", ["bowtie", "triangle"])
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_robin_flux_bit_for_bit_at_every_degree(name, p):
+    """robin_flux against primal.robin_flux at nq = 1, 4 and 64, with and without u_ext, through host memory and through
+    device memory on a non-blocking stream.  `bowtie` has facets of both orientations against their cell and the pinch
+    node, `triangle` every vertex in two listed facets; s = 0 and s = 1 are among the points."""
+    import torch
+    from dolfinx_eqlb_amd import cpp
+    c = case(name, p)
+    h, mesh, robin, alpha = c["h"], c["mesh"], c["robin"], c["alpha"]
+    rules = flux_rules()
+    assert [s.size for s in rules] == [1, 1, 4, 64]
+    rng = np.random.default_rng(pm.seed_of("robin_flux", mesh.ncells, p))
+    u = rng.standard_normal(c["op"].ndofs)
+    dev = torch.device("cuda:0")
+    st = torch.cuda.Stream(device=dev)      # non-blocking: not ordered against the default stream
+    torch.cuda.synchronize()
+    for s in rules:
+        for ue in (None, rng.standard_normal((robin.size, s.size))):
+            ref = primal.robin_flux(mesh, p, robin, alpha, u, s, ue)
+            assert ref.shape == (robin.size, s.size) and np.all(np.isfinite(ref))
+            assert np.array_equal(bits(h.robin_flux(u, s, ue)), bits(ref))
+            with torch.cuda.stream(st):
+                d_u = torch.from_numpy(u).to(dev)
+                d_e = None if ue is None else torch.from_numpy(ue).to(dev)
+                d_o = torch.full((robin.size, s.size), float("nan"), dtype=torch.float64, device=dev)
+                h.robin_flux_raw(d_u.data_ptr(), s, None if ue is None else d_e.data_ptr(), d_o.data_ptr(),
+                                 cpp.MEM_DEVICE, st.cuda_stream)
+            st.synchronize()
+            assert np.array_equal(bits(d_o.cpu().numpy()), bits(ref))
+
+
+def test_skipped_ids_of_a_device_memory_list_give_nan_rows():
+    """a list in device memory with an interior facet and an id >= nfacets in its middle: those rows of the flux are
+    NaN, in host and in device memory, and every other row has the bits of the statement on the list without them"""
+    import torch
+    from dolfinx_eqlb_amd import cpp
+    p = 2
+    c = case("square576", p)
+    mesh, robin, alpha = c["mesh"], c["robin"], c["alpha"]
+    interior = int(np.nonzero(np.diff(mesh.facet_cells_offsets) == 2)[0][0])
+    at = np.array([3, 11])
+    lst = np.insert(robin, at, [interior, mesh.nfacets]).astype(np.int32)       # (positions 3 and 12 of lst)
+    al = np.insert(alpha, at, [2.0, 3.0])
+    bad = np.zeros(lst.size, dtype=bool)
+    bad[[3, 12]] = True
+    assert np.array_equal(lst[~bad], robin) and lst[3] == interior and lst[12] == mesh.nfacets
+    dev = torch.device("cuda:0")
+    h = cpp.PrimalPoisson(c["dm"], p, c["kappa"])
+    d_f, d_a = torch.from_numpy(lst).to(dev), torch.from_numpy(al).to(dev)
+    torch.cuda.synchronize()
+    h.set_robin_raw(lst.size, d_f.data_ptr(), 1.0, d_a.data_ptr(), cpp.MEM_DEVICE, 0)
+    assert h.robin_count() == lst.size
+    s = np.array([0.0, 0.25, 0.6, 1.0])
+    rng = np.random.default_rng(12)
+    u, ue = rng.standard_normal(c["op"].ndofs), rng.standard_normal((lst.size, s.size))
+    for e in (None, ue):
+        ref = primal.robin_flux(mesh, p, robin, alpha, u, s, None if e is None else e[~bad])
+        d_u = torch.from_numpy(u).to(dev)
+        d_e = None if e is None else torch.from_numpy(e).to(dev)
+        d_o = torch.zeros((lst.size, s.size), dtype=torch.float64, device=dev)
+        h.robin_flux_raw(d_u.data_ptr(), s, None if e is None else d_e.data_ptr(), d_o.data_ptr(), cpp.MEM_DEVICE, 0)
+        torch.cuda.synchronize()
+        for got in (d_o.cpu().numpy(), h.robin_flux(u, s, e)):
+            assert np.all(np.isnan(got[bad])) and np.array_equal(bits(got[~bad]), bits(ref))
+
+
+def test_a_raw_list_is_not_remembered_and_not_carried():
+    """set_robin(A), then set_robin_raw(B) in device memory: the host does not know B, so robin_list() raises and does
+    not return A; set_robin(C) makes it return C.  Refinement.carry_robin of a handle that was given only a raw list
+    raises and leaves `new` as it was."""
+    import torch
+    from dolfinx_eqlb_amd import cpp
+    from dolfinx_eqlb_amd.mesh import create_unit_square
+    mesh = create_unit_square(4, shuffle_seed=3, perturb=0.15)
+    dm = cpp.DeviceMesh(mesh)
+    ref = dm.refine(np.arange(mesh.ncells, dtype=np.int32), keep_plan=True)
+    left, bottom, right, top = rb.sides(mesh)
+    A, B, C_ = right, np.concatenate([top, left]).astype(np.int32), bottom
+    aA, aC = rb.alpha_of(A.size), rb.alpha_of(C_.size, seed=3)
+    p = 2
+    message = r"robin_list: the handle's list was not given through set_robin \(host arrays\)"
+    dev = torch.device("cuda:0")
+    d_B = torch.from_numpy(B).to(dev)
+    torch.cuda.synchronize()
+
+    h = cpp.PrimalPoisson(dm, p)
+    assert h.robin_list()[0].size == 0 and h.robin_list()[1].shape == (0,)
+    h.set_robin(A, facet_alpha=aA)
+    assert np.array_equal(h.robin_list()[0], A) and np.array_equal(bits(h.robin_list()[1]), bits(aA))
+    h.set_robin_raw(B.size, d_B.data_ptr(), 2.0, None, cpp.MEM_DEVICE, 0)
+    assert h.robin_count() == B.size
+    with pytest.raises(RuntimeError, match=message):
+        h.robin_list()
+    h.set_robin(C_, facet_alpha=aC)
+    assert np.array_equal(h.robin_list()[0], C_) and np.array_equal(bits(h.robin_list()[1]), bits(aC))
+    h.set_robin_raw(0, None, 1.0, None, cpp.MEM_DEVICE, 0)          # (an empty raw list: the term off, nothing to know)
+    assert h.robin_count() == 0 and h.robin_list()[0].size == 0
+
+    # carry_robin: `old` knows only a raw list; `new` holds a list of its own and keeps it
+    old, new = cpp.PrimalPoisson(dm, p), cpp.PrimalPoisson(ref.dmesh, p)
+    old.set_robin_raw(B.size, d_B.data_ptr(), 2.0, None, cpp.MEM_DEVICE, 0)
+    mesh2 = ref.dmesh.mesh
+    D = rb.sides(mesh2)[1]
+    aD = rb.alpha_of(D.size, seed=4)
+    new.set_robin(D, facet_alpha=aD)
+    u = np.random.default_rng(8).standard_normal(new.ndofs)
+    before = (new.apply(u), new.diagonal(), new.robin_weights())
+    with pytest.raises(RuntimeError, match=message):
+        ref.carry_robin(old, new)
+    assert np.array_equal(new.robin_list()[0], D) and np.array_equal(bits(new.robin_list()[1]), bits(aD))
+    for was, now in zip(before, (new.apply(u), new.diagonal(), new.robin_weights())):
+        assert np.array_equal(bits(was), bits(now))
+    op = primal.PoissonOperator(mesh2, p)
+    op.set_robin(D, facet_alpha=aD)
+    assert np.array_equal(bits(new.apply(u)), bits(op.apply(u)))
